@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- MEMs/sec of the MI355X MEM engine on BASELINE.json's headline workload.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the last step's output if --dump-outputs is given, and prints
+the result line: `value` (MEMs/s), `ms_per_step` and what the timed steps themselves recorded.  Everything that needs work
+of its own -- `roofline` (a diagnostic launch and a line-rate probe), the CPU baselines with the sample parity check, the
+host-to-host legs and, with N > 1, the other scaling mode -- runs only with --full.
 
 N > 1 without WORLD_SIZE in the environment: bench.py starts N ranks ITSELF (a child `python -m torch.distributed.run
 --nproc-per-node N ... bench.py`, spawned before this process touches the GPU) and exits with the child's code; under
@@ -17,10 +22,13 @@ across ranks with no data-path collective (slamem.c:90-95: records are independe
 0 and broadcast over RCCL/xGMI straight from its arena; per-rank MEM counts are gathered every step.
   --scaling weak   (default; the contract's mode for sharded paths) every rank matches its own 10 M reads
   --scaling strong the SAME 10 M reads split into N contiguous ranges (slamem_amd/shard.py::shard_bounds)
-With N > 1 the line also carries the other mode's rate, measured in the same process after the headline loop
+With N > 1 and --full the line also carries the other mode's rate, measured in the same process after the headline loop
 (`strong_scaling` / `weak_scaling`), so one launch gives both.
 
-Rank 0 prints ONE JSON line.
+--dump-outputs DIR (rank 0, its own batch): what the last timed step handed its caller, as float64 .npy files (see
+dump_outputs); the inputs are generated from --seed on the GPU, so the same arguments give the same inputs on every run.
+
+Rank 0 prints ONE JSON line.  With --full it also carries:
   roofline      the dominant kernel (K8s k_seed_mems since round 4; K8 k_find_mems_v3 when the batch does not take the seed
                 path): `traffic` = bytes the kernel's lanes asked the memory system for, counted by the kernel's
                 diagnostic instantiation on the same batch in this run (K8s: 64 B per seed-table line = one per window looked up,
@@ -77,6 +85,12 @@ def parse_args(argv=None):
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--rc-percent", type=int, default=50)
     p.add_argument("--forward-only", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's output (a fixed sample of it, and sums over all of it) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: roofline, CPU baselines and the sample parity "
+                        "check, host-to-host legs, the other scaling mode (N > 1)")
+    # the options below shape the --full measurements only
     p.add_argument("--cpu-sample-reads", type=int, default=250_000)
     p.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-cores CPU leg (0 = this box's share)")
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -157,6 +171,44 @@ def cpu_baseline(ref_host, reads_host, read_len: int, min_len: int, both: bool, 
             x.join()
         out["mt"] = {"threads": T, "reads": T * S, "mems": int(sum(res)), "match_s": time.time() - t0}
     return out
+
+
+# ---- --dump-outputs -------------------------------------------------------------------------------------------------
+DUMP_SAMPLE_BLOCKS = 1 << 18
+DUMP_SAMPLE_SEED = 20260601
+DUMP_LIMIT_BYTES = 64_000_000  # all files together, their headers included
+
+
+def dump_outputs(out_dir: str, matcher, nblocks: int) -> None:
+    """What the last step handed its caller: Matcher.block_offsets (strand block b owns MEM rows [off[b], off[b+1])) and
+    Matcher.mems (rows of ref_pos, query_pos, length), as float64 (exact below 2^53).  All of it is 8 B per block and 12 B
+    per MEM in 32 bits (~450 MB in 64 bits on the default batch), so a fixed seeded sample of blocks goes out whole, next
+    to sums over the whole output:
+      sample_blocks.npy      (S,)     the sampled block numbers, ascending (every block when there are at most S)
+      sample_block_mems.npy  (S,)     MEMs of each sampled block
+      sample_mems.npy        (R, 3)   their MEMs, block by block in the engine's order (cut at the size limit)
+      totals.npy             (4,)     MEMs in the whole output; sums of ref_pos, query_pos and length over all of them"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = matcher.last_total
+    boff = matcher.block_offsets[: nblocks + 1]
+    m = matcher.mems[:total]  # int32 storage of uint32 fields
+    sums = (m.sum(0, dtype=torch.int64) + (m < 0).sum(0, dtype=torch.int64) * (1 << 32)).cpu().numpy()
+    S = min(nblocks, DUMP_SAMPLE_BLOCKS)
+    blocks = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nblocks, size=S, replace=False))
+    sel = torch.from_numpy(blocks.astype(np.int64)).to(boff.device)
+    lo = boff[sel]
+    cnt = boff[sel + 1] - lo
+    n = int(cnt.sum().item())
+    rows = torch.repeat_interleave(lo - (torch.cumsum(cnt, 0) - cnt), cnt, output_size=n)
+    rows += torch.arange(n, dtype=torch.int64, device=boff.device)
+    keep = (DUMP_LIMIT_BYTES - 16 * S - 4096) // 24
+    mems = matcher.mems[rows[:keep]].cpu().numpy().view(np.uint32)
+    np.save(os.path.join(out_dir, "sample_blocks.npy"), blocks.astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_block_mems.npy"), cnt.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_mems.npy"), mems.astype(np.float64))
+    np.save(os.path.join(out_dir, "totals.npy"), np.array([total, *sums], dtype=np.float64))
 
 
 def main():
@@ -281,8 +333,10 @@ def main():
 
     main_batch = weak_batch() if a.scaling == "weak" else strong_batch()
     r = timed(main_batch, a.steps, a.warmup)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, r["matcher"], r["batch"][2] * strands)
     other = None
-    if world > 1:  # the other sharding, same process, fewer steps
+    if world > 1 and a.full:  # the other sharding, same process, fewer steps
         r["matcher"] = None if rank != 0 else r["matcher"]
         other = timed(strong_batch() if a.scaling == "weak" else weak_batch(), max(2, a.steps // 2), 1)
         other.pop("matcher")
@@ -332,6 +386,7 @@ def main():
                 "value": other["mems"] / ps, "ms_per_step": ps * 1e3, "reads_total": other["reads"],
                 "kernel_ms_max": other["kernel_ms"], "kernel_ms_min": other["kernel_ms_min"]}
 
+    if rank == 0 and a.full:
         # ---- roofline of the dominant kernel, from counters of THIS run ---------------------------------------------
         st = engine.search_stats(matcher, reads, offsets, a.min_len) if not a.no_stats else None
         if st is None:
@@ -467,6 +522,7 @@ def main():
             out["value_note"] = ("`value` is the device-resident rate (inputs in HBM when the clock starts: the bench contract); "
                                  "`value_host_to_host` is SURVEY 8(d)'s metric as defined -- reads in host memory -> MEM triples in "
                                  "host memory through slamem_stream_*, median of the passes")
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

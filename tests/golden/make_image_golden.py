@@ -3,7 +3,7 @@
 
 Build container only (needs oracle/_ref/slaMEM):
 
-    make -C oracle ref && python tests/golden/make_image_golden.py
+    make -C oracle ref && python tests/golden/make_image_golden.py            (random_cases.json alone: ... make_image_golden.py random)
 
 Writes tests/golden/image/<case>/{mems.txt (input made here, seeded), expected.bmp, expected-stdout.txt (the reference's own
 output, byte for byte)} and tests/golden/image/manifest.json (names and lengths of the FASTA records: the tool uses nothing else
@@ -12,6 +12,7 @@ no reference source text is stored.  Cases stay where the reference's output is 
 a row of the picture (there the reference's run-length coder skips bytes and ends by reading behind its pixel buffer, so two runs
 of the reference itself differ) -- that regime is covered by tests/test_image_tool.py's decoder-based check instead.
 """
+import hashlib
 import json
 import os
 import random
@@ -113,7 +114,28 @@ def main():
     for name in sorted(manifest):
         d = os.path.join(OUT, name)
         print(name, manifest[name]["rc"], manifest[name]["image"], sum(os.path.getsize(os.path.join(d, x)) for x in os.listdir(d)))
+    record_random_cases()
+
+
+def record_random_cases():
+    """tests/golden/image/random_cases.json: per seed of image_cases.write_random_case, the reference's exit status and the
+    sha256 of its stdout and of its picture (null: none written)"""
+    sha = lambda b: None if b is None else hashlib.sha256(b).hexdigest()
+    out = {}
+    for seed in range(12):
+        d = tempfile.mkdtemp()
+        try:
+            image_cases.write_random_case(d, seed)
+            r = subprocess.run([REF_BIN, "-v", "mems.txt", "ref.fa", "q.fa"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                               timeout=120)
+            bmp = os.path.join(d, "mems.bmp")
+            out[str(seed)] = [r.returncode, sha(r.stdout), sha(open(bmp, "rb").read()) if os.path.exists(bmp) else None]
+        finally:
+            shutil.rmtree(d)
+    with open(image_cases.RANDOM_CASES, "w") as f:
+        json.dump(out, f, indent=1)
+    print("random cases", out)
 
 
 if __name__ == "__main__":
-    main()
+    record_random_cases() if sys.argv[1:] == ["random"] else main()

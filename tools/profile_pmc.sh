@@ -1,12 +1,13 @@
 #!/bin/bash
 # PMC passes over bench.py (one timed step, no CPU baseline); one counter group per pass, never combined with
-# the trace domains gpurun refuses.  Summaries land in gpurun_out/prof/<tag>; tools/summarize_pmc.py reads them.
+# tracing (counters are collected in runs of their own).  Summaries land in $RESULTS/prof/<tag> (default results/);
+# tools/summarize_pmc.py reads them.
 # usage: tools/profile_pmc.sh <tag> [extra bench args]
 set -e
 TAG=${1:-r01}; shift || true
 export TMPDIR=/tmp
 R=$PWD
-OUT=$R/gpurun_out/prof/$TAG
+OUT=$R/${RESULTS:-results}/prof/$TAG
 mkdir -p $OUT
 run() { # name counters...
   local name=$1; shift
