@@ -99,7 +99,7 @@ typedef struct {
     double prefilter_ms_sum;
     double k8_ms_sum;
     float seed_ms;            /* K8s k_seed_mems (seed-and-compare for reads; runs in K8a's place), part of search_kernel_ms (ABI 4) */
-    float reserved0;
+    float mum_filter_ms;      /* -mum: the filter behind K9 (mum_filter.hip), large blocks included; 0 for -mem and -mam */
     double seed_ms_sum;
 } slamem_timings;
 
@@ -308,6 +308,20 @@ int slamem_find_mams_device(const slamem_index *idx, const void *queries_dev, co
                             slamem_mem *mems_dev, uint64_t mems_capacity, uint64_t *block_offsets_dev,
                             void *workspace_dev, uint64_t workspace_bytes, void *stream, uint64_t *total_out);
 
+/* The same batch in MUM mode (option -mum: matchType 2, the mode the reference reserves, slamem.c:35,539, and never built):
+ * the -mem rows of a strand block that no other -mem row of the same block contains, in query coordinates or in reference
+ * coordinates -- given the complete -mem list, the rows whose string occurs exactly once in the text and once in the scanned
+ * strand.  Same arguments, layout and errors as slamem_find_mems_device, rows in the -mem order, every block kept (empty
+ * ones too).  mems_capacity must hold the -mem list the filter starts from: when it does not, the call returns
+ * SLAMEM_ERR_CAPACITY with *total_out = the -mem count a retry needs; on success *total_out is the MUM count.  The workspace
+ * is slamem_find_mums_workspace_bytes() bytes (the -mem workspace and the filter's behind it). */
+int slamem_find_mums_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes,
+                                     uint64_t mems_capacity, uint64_t *bytes_out);
+int slamem_find_mums_device(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,
+                            uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands,
+                            slamem_mem *mems_dev, uint64_t mems_capacity, uint64_t *block_offsets_dev,
+                            void *workspace_dev, uint64_t workspace_bytes, void *stream, uint64_t *total_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -315,6 +329,9 @@ int slamem_find_mems_host(const slamem_index *idx, const char *queries, const ui
                           uint32_t num_queries, uint32_t min_len, int both_strands,
                           slamem_mem **mems_out, uint64_t **block_offsets_out, uint64_t *total_out);
 int slamem_find_mams_host(const slamem_index *idx, const char *queries, const uint64_t *offsets,
+                          uint32_t num_queries, uint32_t min_len, int both_strands,
+                          slamem_mem **mems_out, uint64_t **block_offsets_out, uint64_t *total_out);
+int slamem_find_mums_host(const slamem_index *idx, const char *queries, const uint64_t *offsets,
                           uint32_t num_queries, uint32_t min_len, int both_strands,
                           slamem_mem **mems_out, uint64_t **block_offsets_out, uint64_t *total_out);
 void slamem_host_free(void *p);
@@ -327,7 +344,8 @@ void slamem_host_free(void *p);
  * not kernels + PCIe.  Four or five slots keep all three stages busy beside the result the caller is working on.
  *
  *   slamem_stream_create   max_batch_chars / max_batch_queries: what to reserve per slot (a larger batch makes its slot
- *                          grow); match_type 0 = MEM, 1 = MAM (-mam)
+ *                          grow); match_type 0 = MEM, 1 = MAM (-mam), 2 = MUM (-mum:
+ *                          only the kept rows come back)
  *   slamem_stream_submit   record i of the batch is queries[offsets[i] .. offsets[i+1]) -- offsets[0] need not be 0, so
  *                          a front end passes its whole character buffer and a window of its offsets array.  Returns at
  *                          once; the characters and offsets must stay unchanged until the batch has been collected.

@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "slamem_char_at_bwt_pos_batch",
     "slamem_find_mems_workspace_bytes", "slamem_find_mems_device", "slamem_find_mems_host", "slamem_host_free",
     "slamem_find_mams_device", "slamem_find_mams_host",
+    "slamem_find_mums_workspace_bytes", "slamem_find_mums_device", "slamem_find_mums_host",
     "slamem_stream_create", "slamem_stream_submit", "slamem_stream_submit_packed", "slamem_pack_reads", "slamem_stream_next",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
@@ -75,7 +76,7 @@ class Timings(C.Structure):
                 ("search_kernel_ms", C.c_float), ("search_total_ms", C.c_float),
                 ("search_launches", C.c_uint64), ("search_kernel_ms_sum", C.c_double),
                 ("prefilter_ms", C.c_float), ("k8_ms", C.c_float), ("prefilter_ms_sum", C.c_double),
-                ("k8_ms_sum", C.c_double), ("seed_ms", C.c_float), ("reserved0", C.c_float), ("seed_ms_sum", C.c_double)]
+                ("k8_ms_sum", C.c_double), ("seed_ms", C.c_float), ("mum_filter_ms", C.c_float), ("seed_ms_sum", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -139,6 +140,9 @@ def _declare(L):
                                         C.POINTER(C.POINTER(u64)), C.POINTER(u64)]
     L.slamem_find_mams_device.argtypes = L.slamem_find_mems_device.argtypes
     L.slamem_find_mams_host.argtypes = L.slamem_find_mems_host.argtypes
+    L.slamem_find_mums_workspace_bytes.argtypes = L.slamem_find_mems_workspace_bytes.argtypes
+    L.slamem_find_mums_device.argtypes = L.slamem_find_mems_device.argtypes
+    L.slamem_find_mums_host.argtypes = L.slamem_find_mems_host.argtypes
     L.slamem_stream_create.argtypes = [vp, i32, u64, u32, i32, i32, C.POINTER(vp)]
     L.slamem_stream_submit.argtypes = [vp, vp, vp, u32, u32]
     L.slamem_copy_to_host.argtypes = [vp, vp, u64]

@@ -306,10 +306,21 @@ int find_mems_device(const slamem_index* idx, const void* queries_dev, const uin
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
                      uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out);
 uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity);
+// The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum: the -mem workspace and the filter's behind it)
+uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type);
+// -mum (mum_filter.hip): the filter's part of the workspace; where in it K9 places the -mem list; the filter behind K9 (blocks of
+// up to 256 MEMs; host_scalars[0] = rows kept, [1] = large blocks << 40 | their rows, both copied asynchronously), and the
+// large blocks' path when host_scalars[1] was not 0 (synchronous: *total_out = rows kept)
+uint64_t mum_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
+void mum_list_buffers(void* mum_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
+int mum_filter_small(void* mum_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem* out_mems, uint64_t* out_boff,
+                     unsigned long long* host_scalars, hipStream_t stream);
+int mum_filter_large(void* mum_ws, uint64_t num_blocks, uint64_t capacity, unsigned long long large_ctr, slamem_mem* out_mems,
+                     uint64_t* out_boff, hipStream_t stream, uint64_t* total_out);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).
-// host_scalars: nine 64-bit words, pinned if possible (nullptr: the job's own).
+// host_scalars: sixteen 64-bit words, pinned if possible (nullptr: the job's own).
 struct SearchJob;
 SearchJob* search_job_new();
 void search_job_delete(SearchJob* j);
@@ -335,4 +346,7 @@ int search_job_carried_out(const SearchJob* j);
 int search_job_flush(SearchJob* j, hipStream_t stream);
 int search_job_place(SearchJob* j, hipStream_t stream);
 int search_job_collect(SearchJob* j, uint64_t* total_out);
+// -mum, after a successful collect: the blocks too large for the filter's lanes, when the batch has some (synchronous on
+// `stream`); *total_out = the MUMs of the batch.  Nothing to do otherwise.
+int search_job_finish(SearchJob* j, hipStream_t stream, uint64_t* total_out);
 }  // namespace slamem

@@ -3507,6 +3507,13 @@ uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint6
     return layout_workspace(num_queries, both_strands ? 2 : 1, query_bytes, mems_capacity).bytes;
 }
 
+// -mum: the -mem workspace, then the filter's (mum_filter.hip: the -mem list K9 places, and what the filter needs beside it)
+uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type) {
+    const uint64_t mem = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity);
+    if (match_type != 2) return mem;
+    return mem + mum_workspace_bytes(num_queries * (both_strands ? 2u : 1u), mems_capacity);
+}
+
 // SLAMEM_MAM_WHOLE=1: -mam with one lane per whole strand (k_find_mams), no slices
 static bool mam_whole_strands() {
     static const bool on = [] { const char* v = getenv("SLAMEM_MAM_WHOLE"); return v && atoi(v) != 0; }();
@@ -3535,10 +3542,18 @@ struct SearchJob {
     bool seeded = false;  // this batch's MEMs come from K8s (k_seed_mems); K8 scans only the strands it left
     uint32_t seed_words = 0, seed_words_avg = 0;  // plane words a strand of this batch's K8s launch, and what the average read length alone asks for
     bool mam_v3 = false;  // -mam on a batch without long records: K8's kMam instantiation (set by tables())
-    unsigned long long scal_own[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // -mum: the search runs as -mem into the workspace (mems_dev / block_offsets_dev point there) and the filter writes the kept
+    // rows to the caller's buffers; mum_large: the batch has a block too large for the filter's lanes (finish() runs the sorts)
+    bool mum = false;
+    slamem_mem* out_mems = nullptr;
+    uint64_t* out_boff = nullptr;
+    void* mum_ws = nullptr;
+    unsigned long long mum_large = 0;
+    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter behind K9
+    unsigned long long scal_own[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t k8_wave_cap = 0;  // waves of this batch's K8 (0: as many as the chip holds); a pipeline that keeps two K8 launches in flight gives each a part of the chip
     uint32_t slices_hint = 0xFFFFFFFFu;  // a caller that has the offsets on the host and knows the slice count (no record longer than a slice: one per record) saves tables() its round trip
-    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs; pinned memory if the caller has some
+    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, -mum: [9] rows kept, [10] large blocks; pinned memory if the caller has some
     ~SearchJob();
     int init(const slamem_index* idx_, const void* queries_dev_, const uint64_t* offsets_dev_, uint32_t num_queries_,
              uint64_t query_bytes_, uint32_t min_len_, int both_strands_, int match_type_, slamem_mem* mems_dev_,
@@ -3556,6 +3571,7 @@ struct SearchJob {
     int flush(hipStream_t stream);                   // a launch without new work that finishes the lanes this job passed on
     int place(hipStream_t stream);                   // K9 + the batch's scalars to the host
     int collect();
+    int finish(hipStream_t stream);                  // -mum after collect(): the large blocks, when the batch has some
     bool carried_out = false;
     bool chunked = false;  // this launch ran the kChunk instantiation (its overflow list has unused places)
 };
@@ -3575,6 +3591,7 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
     min_len = min_len_; both_strands = both_strands_; match_type = match_type_; mems_dev = mems_dev_; mems_capacity = mems_capacity_;
     block_offsets_dev = block_offsets_dev_; workspace_dev = workspace_dev_; workspace_bytes = workspace_bytes_;
     total = 0; nitems = 0; prefiltered = false; timed_k8 = false; launched = false;
+    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr;
     if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity) || (!queries_dev && num_queries)) {
         set_error("slamem_find_mems_device: null argument");
         return SLAMEM_ERR_ARG;
@@ -3594,20 +3611,40 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         set_error("slamem_find_mems_device: at most 2^32 - 2^20 work items per call");
         return SLAMEM_ERR_ARG;
     }
-    if (workspace_bytes < w.bytes) {
+    if (match_type == 2) {
+        // -mum: the -mem search, then the filter (mum_filter.hip); the row places of the filter are 32-bit
+        if (mems_capacity >= 0xFFFFFFFFull) {
+            set_error("slamem_find_mums_device: at most 2^32 - 2 MEMs of capacity per call");
+            return SLAMEM_ERR_ARG;
+        }
+        mum = true;
+        match_type = 0;
+    }
+    const uint64_t need_ws = mum ? w.bytes + mum_workspace_bytes(num_blocks, mems_capacity) : w.bytes;
+    if (workspace_bytes < need_ws) {
         set_error("slamem_find_mems_device: workspace too small (%llu < %llu bytes)",
-                  (unsigned long long)workspace_bytes, (unsigned long long)w.bytes);
+                  (unsigned long long)workspace_bytes, (unsigned long long)need_ws);
         return SLAMEM_ERR_ARG;
+    }
+    if (mum) {
+        out_mems = mems_dev;
+        out_boff = block_offsets_dev;
+        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
+        mum_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
     }
     want_stats = search_stats_wanted();
     for (int i = 0; i < 6; i++)
         if (!ev[i]) SLAMEM_HIP(hipEventCreate(&ev[i]));
+    for (int i = 0; i < 2 && mum; i++)
+        if (!ev_mum[i]) SLAMEM_HIP(hipEventCreate(&ev_mum[i]));
     return SLAMEM_OK;
 }
 
 SearchJob::~SearchJob() {
     for (int i = 0; i < 6; i++)
         if (ev[i]) (void)hipEventDestroy(ev[i]);
+    for (int i = 0; i < 2; i++)
+        if (ev_mum[i]) (void)hipEventDestroy(ev_mum[i]);
 }
 
 #define STEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
@@ -4116,6 +4153,12 @@ int SearchJob::place(hipStream_t stream) {
     // [0] listed; u32 word 8: survivors of K8a, word 9: ordinal overflow flag; [8] all MEMs
     STEP(hipMemcpyAsync(h_scal, d_total, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "memcpy");
     STEP(hipMemcpyAsync(h_scal + 8, d_itemoff + nitems, 8, hipMemcpyDeviceToHost, stream), "memcpy");
+    if (mum) {  // -mum: the filter, right behind K9; its two scalars go back with the others
+        (void)hipEventRecord(ev_mum[0], stream);
+        int rc = mum_filter_small(mum_ws, num_blocks, mems_capacity, out_mems, out_boff, h_scal + 9, stream);
+        if (rc != SLAMEM_OK) return rc;
+        (void)hipEventRecord(ev_mum[1], stream);
+    }
     return SLAMEM_OK;
 }
 
@@ -4202,6 +4245,29 @@ int SearchJob::collect() {
                   (unsigned long long)mems_capacity);
         return SLAMEM_ERR_CAPACITY;
     }
+    tm.t.mum_filter_ms = 0;
+    if (mum) {
+        // (the -mem list fitted: the filter's result is the batch's, or, with a large block, finish() completes it)
+        mum_large = h_scal[10];
+        if (!mum_large) total = h_scal[9];
+        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
+    }
+    return SLAMEM_OK;
+}
+
+int SearchJob::finish(hipStream_t stream) {
+    if (!mum || !mum_large) return SLAMEM_OK;
+    SLAMEM_HIP(hipSetDevice(idx->device));
+    (void)hipEventRecord(ev_mum[0], stream);
+    uint64_t kept = 0;
+    int rc = mum_filter_large(mum_ws, num_blocks, mems_capacity, mum_large, out_mems, out_boff, stream, &kept);
+    if (rc != SLAMEM_OK) return rc;
+    (void)hipEventRecord(ev_mum[1], stream);
+    float ms = 0;
+    if (hipEventSynchronize(ev_mum[1]) == hipSuccess && hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess)
+        thread_timings().t.mum_filter_ms += ms;
+    total = kept;
+    mum_large = 0;
     return SLAMEM_OK;
 }
 #undef STEP
@@ -4220,6 +4286,7 @@ static int run_job(SearchJob& job, const slamem_index* idx, const void* queries_
         if (e != hipSuccess && rc == SLAMEM_OK) rc = hip_fail(e, "MEM search (sync)", __FILE__, __LINE__);
     }
     if (rc == SLAMEM_OK) rc = job.collect();
+    if (rc == SLAMEM_OK && !job.saw_long) rc = job.finish(stream);
     return rc;
 }
 int find_mems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
@@ -4265,6 +4332,11 @@ int search_job_flush(SearchJob* j, hipStream_t stream) { return j->flush(stream)
 int search_job_place(SearchJob* j, hipStream_t stream) { return j->place(stream); }
 int search_job_collect(SearchJob* j, uint64_t* total_out) {
     int rc = j->collect();
+    if (total_out) *total_out = j->total;
+    return rc;
+}
+int search_job_finish(SearchJob* j, hipStream_t stream, uint64_t* total_out) {
+    int rc = j->finish(stream);
     if (total_out) *total_out = j->total;
     return rc;
 }

@@ -127,7 +127,7 @@ int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search sta
     if (sl.d_ws) (void)hipFree(sl.d_ws);
     sl.d_mems = nullptr; sl.d_ws = nullptr;
     sl.cap = need_cap;
-    sl.ws_bytes = find_mems_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap);
+    sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, s->match_type);
     SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mems), sl.cap * sizeof(slamem_mem) + 16));
     SLAMEM_HIP(hipMalloc(&sl.d_ws, sl.ws_bytes));
     return SLAMEM_OK;
@@ -412,6 +412,7 @@ int stage_download(slamem_stream* s, Slot& sl) {
         SLAMEM_HIP(hipStreamSynchronize(st));
         if (rc == SLAMEM_OK) rc = search_job_collect(sl.job, &sl.total);
     }
+    if (rc == SLAMEM_OK) rc = search_job_finish(sl.job, st, &sl.total);  // -mum: a batch with a large block
     (void)slamem_get_timings(&sl.tm);
     if (rc != SLAMEM_OK) return rc;
     {
@@ -604,8 +605,8 @@ int slamem_stream_destroy(slamem_stream* s) {
 
 int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream** out) {
-    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type != 0 && match_type != 1)) {
-        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 or 1)");
+    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 2)) {
+        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0, 1 or 2)");
         return SLAMEM_ERR_ARG;
     }
     *out = nullptr;

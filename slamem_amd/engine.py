@@ -189,12 +189,15 @@ class Index:
 
     # ---- GetMatches (slamem.c:90-207) for a batch ---------------------------------------------------------
     def matcher(self, num_queries: int, both_strands: bool, mems_capacity: int, query_bytes: int,
-                mam: bool = False) -> "Matcher":
-        return Matcher(self, num_queries, both_strands, mems_capacity, query_bytes, mam)
+                mam: bool = False, mum: bool = False) -> "Matcher":
+        return Matcher(self, num_queries, both_strands, mems_capacity, query_bytes, mam, mum)
 
-    def find_mems(self, queries, offsets, min_len: int = 20, both_strands: bool = False, mam: bool = False):
+    def find_mems(self, queries, offsets, min_len: int = 20, both_strands: bool = False, mam: bool = False,
+                  mum: bool = False):
         """Convenience: host arrays in, (mems structured array, block_offsets) out.  mam=True: -mam mode
-        (slamem_find_mams_device; slamem.c:131,657)."""
+        (slamem_find_mams_device; slamem.c:131,657).  mum=True: -mum mode, the MEMs no other MEM of their strand
+        block contains in either coordinate (slamem_find_mums_device)."""
+        _match_type(mam, mum)
         dev = self.device
         q = np.ascontiguousarray(np.frombuffer(queries, dtype=np.uint8) if isinstance(queries, (bytes, bytearray))
                                  else queries, dtype=np.uint8)
@@ -206,7 +209,7 @@ class Index:
         od = torch.from_numpy(offsets.view(np.int64)).to(dev)
         cap = max(1024, q.shape[0] // 8 + 4 * num)
         while True:
-            m = self.matcher(num, both_strands, cap, int(offsets[-1]) if num else 0, mam)
+            m = self.matcher(num, both_strands, cap, int(offsets[-1]) if num else 0, mam, mum)
             try:
                 total = m.run(qd, od, min_len)
                 break
@@ -220,13 +223,22 @@ class Index:
         return out, m.block_offsets.cpu().numpy().view(np.uint64)
 
 
+def _match_type(mam: bool, mum: bool) -> int:
+    """The C ABI's match type: 0 -mem, 1 -mam, 2 -mum.  The reference has one matchType (slamem.c:35): not both."""
+    if mam and mum:
+        raise ValueError("mam and mum exclude each other: one match type per search")
+    return 2 if mum else (1 if mam else 0)
+
+
 class Matcher:
     """Pre-allocated output + workspace buffers for repeated slamem_find_mems_device calls (bench loop)."""
 
     def __init__(self, index: Index, num_queries: int, both_strands: bool, mems_capacity: int, query_bytes: int,
-                 mam: bool = False):
+                 mam: bool = False, mum: bool = False):
         self.index = index
-        self.mam = bool(mam)
+        self.match_type = _match_type(mam, mum)
+        self.mam = self.match_type == 1
+        self.mum = self.match_type == 2
         self.num_queries = int(num_queries)
         self.both = bool(both_strands)
         self.capacity = int(mems_capacity)
@@ -234,8 +246,8 @@ class Matcher:
         dev = index.device
         nb = self.num_queries * (2 if self.both else 1)
         need = C.c_uint64()
-        capi.check(capi.lib().slamem_find_mems_workspace_bytes(self.num_queries, int(self.both), self.query_bytes,
-                                                               self.capacity, C.byref(need)))
+        ws_fn = capi.lib().slamem_find_mums_workspace_bytes if self.mum else capi.lib().slamem_find_mems_workspace_bytes
+        capi.check(ws_fn(self.num_queries, int(self.both), self.query_bytes, self.capacity, C.byref(need)))
         self.workspace = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
         self.mems = torch.empty((max(self.capacity, 1), 3), dtype=torch.int32, device=dev)
         self.block_offsets = torch.empty(nb + 1, dtype=torch.int64, device=dev)
@@ -244,7 +256,8 @@ class Matcher:
     def run(self, queries_dev: torch.Tensor, offsets_dev: torch.Tensor, min_len: int) -> int:
         dev = self.index.device
         total = C.c_uint64()
-        fn = capi.lib().slamem_find_mams_device if self.mam else capi.lib().slamem_find_mems_device
+        L = capi.lib()
+        fn = (L.slamem_find_mems_device, L.slamem_find_mams_device, L.slamem_find_mums_device)[self.match_type]
         rc = fn(
             self.index._h, _ptr(queries_dev), _ptr(offsets_dev), self.num_queries, self.query_bytes, int(min_len),
             int(self.both),
@@ -282,12 +295,13 @@ class Stream:
     query loop of GetMatches (slamem.c:90-207) for reads that live in host memory."""
 
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
-                 mam: bool = False):
+                 mam: bool = False, mum: bool = False):
+        match_type = _match_type(mam, mum)
         self.index = index
         self.both = bool(both_strands)
         self._h = C.c_void_p()
         capi.check(capi.lib().slamem_stream_create(index._h, int(slots), int(max_batch_chars), int(max_batch_queries),
-                                                   int(self.both), int(bool(mam)), C.byref(self._h)))
+                                                   int(self.both), match_type, C.byref(self._h)))
         self._keep = []
 
     def submit(self, chars: np.ndarray, offsets: np.ndarray, min_len: int) -> None:

@@ -608,6 +608,7 @@ int main(int argc, char **argv) {
         if (argc != 3) { printf("Usage: %s -c <fasta_file>\n\n", argv[0]); return -1; }
         return slh_clean_fasta(argv[2], stdout);
     }
+    if (o.match_type < 0) exit_message("Options -mam and -mum exclude each other"); /* before any GPU work */
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
     if (o.ref_name_given && o.ref_name_empty) exit_message("No reference name string provided");
     if ((env = getenv("SLAMEM_DEVICE")) != NULL) device = atoi(env);
@@ -843,7 +844,7 @@ int main(int argc, char **argv) {
         g_writer.started = pthread_create(&g_writer.tid, NULL, writer_run, &g_writer) == 0;
         double ts0 = now_s();
         for (g = 0; g < ngpu && (nranges || overlap); g++) { /* batch b is searched on GPU b mod ngpu: no data-path collective */
-            rc = slamem_stream_create(gpus[g], slots, max_chars, max_recs, o.both_strands, o.match_type == 1 ? 1 : 0, &g_streams[g]);
+            rc = slamem_stream_create(gpus[g], slots, max_chars, max_recs, o.both_strands, o.match_type, &g_streams[g]);
             if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("setting up the search pipeline", rc); }
             g_nstreams = g + 1;
             inflight[g] = 0;

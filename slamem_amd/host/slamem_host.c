@@ -739,6 +739,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
     }
     o->image_arg = slh_parse_argument(argc, argv, "V", 2);
     o->match_type = slh_parse_argument(argc, argv, "MA", 0) ? 1 : 0;
+    if (slh_parse_argument(argc, argv, "MU", 0)) /* -mum: the match type the reference reserves ("EAU", slamem.c:35) */
+        o->match_type = o->match_type == 1 ? -1 : 2;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;

@@ -69,7 +69,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...)                             */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), -1 both    */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
