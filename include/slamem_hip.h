@@ -99,7 +99,7 @@ typedef struct {
     double prefilter_ms_sum;
     double k8_ms_sum;
     float seed_ms;            /* K8s k_seed_mems (seed-and-compare for reads; runs in K8a's place), part of search_kernel_ms (ABI 4) */
-    float mum_filter_ms;      /* -mum: the filter behind K9 (mum_filter.hip), large blocks included; 0 for -mem and -mam */
+    float mum_filter_ms;      /* -mum / -smem: the filter behind K9 (mum_filter.hip, smem_filter.hip), large blocks included; 0 for -mem and -mam */
     double seed_ms_sum;
 } slamem_timings;
 
@@ -322,6 +322,22 @@ int slamem_find_mums_device(const slamem_index *idx, const void *queries_dev, co
                             slamem_mem *mems_dev, uint64_t mems_capacity, uint64_t *block_offsets_dev,
                             void *workspace_dev, uint64_t workspace_bytes, void *stream, uint64_t *total_out);
 
+/* The same batch in SMEM mode (option -smem: matchType 3, the seeds of read mappers): the -mem rows of a
+ * strand block whose query interval [q, q+L) no other -mem row of the same block strictly contains -- given the complete
+ * -mem list, the rows whose string extends to neither side anywhere in the merged text.  Rows of one interval on different
+ * diagonals are its occurrences and are kept together.  max_occ > 0 (option -occ N) drops the intervals that more than max_occ
+ * rows of their block share (0: no cap).  Same arguments, layout and errors as slamem_find_mums_device, rows in the -mem
+ * order, every block kept (empty ones too), the same capacity rule (SLAMEM_ERR_CAPACITY with *total_out = the -mem count a
+ * retry needs).  Every block is decided on the device: one host round trip per batch, as for -mem.  A block whose -mem rows
+ * are not in the emission order (query start descending, then length non-increasing) fails the call with SLAMEM_ERR_ARG and
+ * a message.  The workspace is slamem_find_smems_workspace_bytes() bytes. */
+int slamem_find_smems_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes,
+                                      uint64_t mems_capacity, uint64_t *bytes_out);
+int slamem_find_smems_device(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,
+                             uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands,
+                             uint32_t max_occ, slamem_mem *mems_dev, uint64_t mems_capacity, uint64_t *block_offsets_dev,
+                             void *workspace_dev, uint64_t workspace_bytes, void *stream, uint64_t *total_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -334,6 +350,9 @@ int slamem_find_mams_host(const slamem_index *idx, const char *queries, const ui
 int slamem_find_mums_host(const slamem_index *idx, const char *queries, const uint64_t *offsets,
                           uint32_t num_queries, uint32_t min_len, int both_strands,
                           slamem_mem **mems_out, uint64_t **block_offsets_out, uint64_t *total_out);
+int slamem_find_smems_host(const slamem_index *idx, const char *queries, const uint64_t *offsets,
+                           uint32_t num_queries, uint32_t min_len, int both_strands, uint32_t max_occ,
+                           slamem_mem **mems_out, uint64_t **block_offsets_out, uint64_t *total_out);
 void slamem_host_free(void *p);
 
 /* ---- (b') MEM retrieval, host to host, pipelined -------------------------------
@@ -345,7 +364,9 @@ void slamem_host_free(void *p);
  *
  *   slamem_stream_create   max_batch_chars / max_batch_queries: what to reserve per slot (a larger batch makes its slot
  *                          grow); match_type 0 = MEM, 1 = MAM (-mam), 2 = MUM (-mum:
- *                          only the kept rows come back)
+ *                          only the kept rows come back), 3 = SMEM (-smem: likewise)
+ *   slamem_stream_set_max_occ  -smem: the occurrence cap of every batch (0: none, the default); before the first submit
+ *                          (SLAMEM_ERR_ARG after it, or with a cap on a stream of another match type)
  *   slamem_stream_submit   record i of the batch is queries[offsets[i] .. offsets[i+1]) -- offsets[0] need not be 0, so
  *                          a front end passes its whole character buffer and a window of its offsets array.  Returns at
  *                          once; the characters and offsets must stay unchanged until the batch has been collected.
@@ -363,6 +384,7 @@ void slamem_host_free(void *p);
 typedef struct slamem_stream slamem_stream;
 int slamem_stream_create(const slamem_index *idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream **out);
+int slamem_stream_set_max_occ(slamem_stream *s, uint32_t max_occ);
 int slamem_stream_submit(slamem_stream *s, const char *queries, const uint64_t *offsets, uint32_t num_queries,
                          uint32_t min_len);
 /* The same for reads the caller holds PACKED (ABI 4; no reference counterpart: the reference reads letters, sequence.c:89-270).

@@ -455,11 +455,27 @@ int slamem_find_mums_device(const slamem_index* idx, const void* queries_dev, co
                             total_out);
 }
 
+int slamem_find_smems_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                      uint64_t* bytes_out) {
+    if (!bytes_out) return SLAMEM_ERR_ARG;
+    *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, 3);
+    return SLAMEM_OK;
+}
+
+int slamem_find_smems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
+                             uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_occ,
+                             slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
+                             uint64_t workspace_bytes, void* stream, uint64_t* total_out) {
+    return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 3, mems_dev,
+                            mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
+                            total_out, max_occ);
+}
+
 void slamem_host_free(void* p) { free(p); }
 
 static int find_matches_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                              uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out,
-                             uint64_t** block_offsets_out, uint64_t* total_out);
+                             uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ = 0);
 
 int slamem_find_mems_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                           uint32_t min_len, int both_strands, slamem_mem** mems_out, uint64_t** block_offsets_out,
@@ -479,9 +495,16 @@ int slamem_find_mums_host(const slamem_index* idx, const char* queries, const ui
     return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 2, mems_out, block_offsets_out, total_out);
 }
 
+int slamem_find_smems_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
+                           uint32_t min_len, int both_strands, uint32_t max_occ, slamem_mem** mems_out,
+                           uint64_t** block_offsets_out, uint64_t* total_out) {
+    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 3, mems_out, block_offsets_out, total_out,
+                             max_occ);
+}
+
 static int find_matches_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                              uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out,
-                             uint64_t** block_offsets_out, uint64_t* total_out) {
+                             uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ) {
     if (!idx || !offsets || !mems_out || !block_offsets_out || !total_out || (num_queries && !queries)) {
         set_error("slamem_find_mems_host: null argument");
         return SLAMEM_ERR_ARG;
@@ -507,7 +530,7 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
         HOST_TRY(hipMalloc(&d_ws, ws_bytes));
         rc = find_mems_device(idx, d_q, static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands,
                               match_type, static_cast<slamem_mem*>(d_mems), cap, static_cast<uint64_t*>(d_boff), d_ws, ws_bytes,
-                              nullptr, total_out);
+                              nullptr, total_out, max_occ);
         if (rc != SLAMEM_ERR_CAPACITY) break;
         (void)hipFree(d_mems); d_mems = nullptr;
         (void)hipFree(d_ws); d_ws = nullptr;

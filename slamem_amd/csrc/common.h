@@ -304,9 +304,9 @@ int estimate_build_bytes(uint32_t n, int layout, uint64_t* arena_bytes, uint64_t
 int find_mems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out);
+                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ = 0);
 uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity);
-// The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum: the -mem workspace and the filter's behind it)
+// The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum, 3 -smem: the -mem workspace and the filter's behind it)
 uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type);
 // -mum (mum_filter.hip): the filter's part of the workspace; where in it K9 places the -mem list; the filter behind K9 (blocks of
 // up to 256 MEMs; host_scalars[0] = rows kept, [1] = large blocks << 40 | their rows, both copied asynchronously), and the
@@ -317,6 +317,13 @@ int mum_filter_small(void* mum_ws, uint64_t num_blocks, uint64_t capacity, slame
                      unsigned long long* host_scalars, hipStream_t stream);
 int mum_filter_large(void* mum_ws, uint64_t num_blocks, uint64_t capacity, unsigned long long large_ctr, slamem_mem* out_mems,
                      uint64_t* out_boff, hipStream_t stream, uint64_t* total_out);
+// -smem (smem_filter.hip): the filter's part of the workspace; where in it K9 places the -mem list; the filter behind K9, all
+// blocks, asynchronous (max_occ: the occurrence cap, 0 none; host_scalars[0] = rows kept, [1] = the first block out of the
+// emission order + 1, 0 when there is none)
+uint64_t smem_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
+void smem_list_buffers(void* smem_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
+int smem_filter(void* smem_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_occ, slamem_mem* out_mems, uint64_t* out_boff,
+                unsigned long long* host_scalars, hipStream_t stream);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).
@@ -333,6 +340,8 @@ int search_job_init(SearchJob* j, const slamem_index* idx, const void* queries_d
 void search_job_slices_hint(SearchJob* j, uint32_t slices);
 // (between init and the search) at most this many waves for the batch's K8 (0: the whole chip)
 void search_job_k8_wave_cap(SearchJob* j, uint32_t waves);
+// (between init and the search) -smem: the occurrence cap of the batch (0: none)
+void search_job_max_occ(SearchJob* j, uint32_t max_occ);
 constexpr uint32_t kSearchSliceLen = 4096;
 int search_job_tables(SearchJob* j, hipStream_t stream);
 int search_job_prep(SearchJob* j, hipStream_t stream);

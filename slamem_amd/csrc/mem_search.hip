@@ -3507,11 +3507,14 @@ uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint6
     return layout_workspace(num_queries, both_strands ? 2 : 1, query_bytes, mems_capacity).bytes;
 }
 
-// -mum: the -mem workspace, then the filter's (mum_filter.hip: the -mem list K9 places, and what the filter needs beside it)
+// -mum / -smem: the -mem workspace, then the filter's (mum_filter.hip / smem_filter.hip: the -mem list K9 places, and what the
+// filter needs beside it)
 uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type) {
     const uint64_t mem = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity);
-    if (match_type != 2) return mem;
-    return mem + mum_workspace_bytes(num_queries * (both_strands ? 2u : 1u), mems_capacity);
+    const uint64_t nb = num_queries * (both_strands ? 2u : 1u);
+    if (match_type == 2) return mem + mum_workspace_bytes(nb, mems_capacity);
+    if (match_type == 3) return mem + smem_workspace_bytes(nb, mems_capacity);
+    return mem;
 }
 
 // SLAMEM_MAM_WHOLE=1: -mam with one lane per whole strand (k_find_mams), no slices
@@ -3549,11 +3552,14 @@ struct SearchJob {
     uint64_t* out_boff = nullptr;
     void* mum_ws = nullptr;
     unsigned long long mum_large = 0;
-    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter behind K9
+    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter behind K9 (-mum and -smem)
+    // -smem: as -mum, with smem_filter.hip behind K9 (every block on the device: nothing for finish()); max_occ: the cap (0: none)
+    bool smem = false;
+    uint32_t max_occ = 0;
     unsigned long long scal_own[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t k8_wave_cap = 0;  // waves of this batch's K8 (0: as many as the chip holds); a pipeline that keeps two K8 launches in flight gives each a part of the chip
     uint32_t slices_hint = 0xFFFFFFFFu;  // a caller that has the offsets on the host and knows the slice count (no record longer than a slice: one per record) saves tables() its round trip
-    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, -mum: [9] rows kept, [10] large blocks; pinned memory if the caller has some
+    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, -mum: [9] rows kept, [10] large blocks, -smem: [9] rows kept, [10] a block out of order + 1; pinned memory if the caller has some
     ~SearchJob();
     int init(const slamem_index* idx_, const void* queries_dev_, const uint64_t* offsets_dev_, uint32_t num_queries_,
              uint64_t query_bytes_, uint32_t min_len_, int both_strands_, int match_type_, slamem_mem* mems_dev_,
@@ -3591,7 +3597,7 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
     min_len = min_len_; both_strands = both_strands_; match_type = match_type_; mems_dev = mems_dev_; mems_capacity = mems_capacity_;
     block_offsets_dev = block_offsets_dev_; workspace_dev = workspace_dev_; workspace_bytes = workspace_bytes_;
     total = 0; nitems = 0; prefiltered = false; timed_k8 = false; launched = false;
-    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr;
+    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false;
     if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity) || (!queries_dev && num_queries)) {
         set_error("slamem_find_mems_device: null argument");
         return SLAMEM_ERR_ARG;
@@ -3619,8 +3625,17 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         }
         mum = true;
         match_type = 0;
+    } else if (match_type == 3) {
+        // -smem: the -mem search, then the filter (smem_filter.hip); its row places and tiles are 32-bit
+        if (mems_capacity >= 0xFFFF0000ull) {
+            set_error("slamem_find_smems_device: at most 2^32 - 2^16 MEMs of capacity per call");
+            return SLAMEM_ERR_ARG;
+        }
+        smem = true;
+        match_type = 0;
     }
-    const uint64_t need_ws = mum ? w.bytes + mum_workspace_bytes(num_blocks, mems_capacity) : w.bytes;
+    const uint64_t need_ws = mum ? w.bytes + mum_workspace_bytes(num_blocks, mems_capacity)
+                                 : smem ? w.bytes + smem_workspace_bytes(num_blocks, mems_capacity) : w.bytes;
     if (workspace_bytes < need_ws) {
         set_error("slamem_find_mems_device: workspace too small (%llu < %llu bytes)",
                   (unsigned long long)workspace_bytes, (unsigned long long)need_ws);
@@ -3631,11 +3646,16 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         out_boff = block_offsets_dev;
         mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
         mum_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
+    } else if (smem) {
+        out_mems = mems_dev;
+        out_boff = block_offsets_dev;
+        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
+        smem_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
     }
     want_stats = search_stats_wanted();
     for (int i = 0; i < 6; i++)
         if (!ev[i]) SLAMEM_HIP(hipEventCreate(&ev[i]));
-    for (int i = 0; i < 2 && mum; i++)
+    for (int i = 0; i < 2 && (mum || smem); i++)
         if (!ev_mum[i]) SLAMEM_HIP(hipEventCreate(&ev_mum[i]));
     return SLAMEM_OK;
 }
@@ -4158,6 +4178,11 @@ int SearchJob::place(hipStream_t stream) {
         int rc = mum_filter_small(mum_ws, num_blocks, mems_capacity, out_mems, out_boff, h_scal + 9, stream);
         if (rc != SLAMEM_OK) return rc;
         (void)hipEventRecord(ev_mum[1], stream);
+    } else if (smem) {  // -smem: the same place; every block is decided on the device, its two scalars go back with the others
+        (void)hipEventRecord(ev_mum[0], stream);
+        int rc = smem_filter(mum_ws, num_blocks, mems_capacity, max_occ, out_mems, out_boff, h_scal + 9, stream);
+        if (rc != SLAMEM_OK) return rc;
+        (void)hipEventRecord(ev_mum[1], stream);
     }
     return SLAMEM_OK;
 }
@@ -4251,6 +4276,16 @@ int SearchJob::collect() {
         mum_large = h_scal[10];
         if (!mum_large) total = h_scal[9];
         if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
+    } else if (smem && !saw_long) {
+        // (a batch that found a record longer than a slice is searched again: its list here is not the batch's)
+        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
+        if (h_scal[10]) {
+            set_error("slamem_find_smems_device: the -mem rows of strand block %llu are not in the emission order (query start "
+                      "descending, then length non-increasing); no SMEMs returned", h_scal[10] - 1ull);
+            total = 0;
+            return SLAMEM_ERR_ARG;
+        }
+        total = h_scal[9];
     }
     return SLAMEM_OK;
 }
@@ -4275,9 +4310,10 @@ int SearchJob::finish(hipStream_t stream) {
 static int run_job(SearchJob& job, const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                    uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                    slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                   uint64_t workspace_bytes, hipStream_t stream) {
+                   uint64_t workspace_bytes, hipStream_t stream, uint32_t max_occ) {
     int rc = job.init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                       mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
+    job.max_occ = max_occ;
     if (rc == SLAMEM_OK) rc = job.tables(stream);
     if (rc == SLAMEM_OK) rc = job.prep(stream);
     if (rc == SLAMEM_OK) rc = job.search(stream);
@@ -4292,16 +4328,16 @@ static int run_job(SearchJob& job, const slamem_index* idx, const void* queries_
 int find_mems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out) {
+                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ) {
     if (!total_out) { set_error("slamem_find_mems_device: null argument"); return SLAMEM_ERR_ARG; }
     SearchJob job;
     job.speculate = true;
     int rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream);
+                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ);
     if (rc == SLAMEM_OK && job.saw_long) {  // a record longer than a slice among the reads: once more, with the item tables
         job.speculate = false;
         rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream);
+                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ);
     }
     *total_out = job.total;
     return rc;
@@ -4317,11 +4353,13 @@ int search_job_init(SearchJob* j, const slamem_index* idx, const void* queries_d
     j->h_scal = host_scalars ? host_scalars : j->scal_own;
     j->slices_hint = 0xFFFFFFFFu;
     j->k8_wave_cap = 0;
+    j->max_occ = 0;
     return j->init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                    mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
 }
 void search_job_slices_hint(SearchJob* j, uint32_t slices) { j->slices_hint = slices; }
 void search_job_k8_wave_cap(SearchJob* j, uint32_t waves) { j->k8_wave_cap = waves; }
+void search_job_max_occ(SearchJob* j, uint32_t max_occ) { j->max_occ = max_occ; }
 int search_job_tables(SearchJob* j, hipStream_t stream) { return j->tables(stream); }
 int search_job_prep(SearchJob* j, hipStream_t stream) { return j->prep(stream); }
 int search_job_search(SearchJob* j, hipStream_t stream) { return j->search(stream); }

@@ -90,6 +90,7 @@ using namespace slamem;
 struct slamem_stream {
     const slamem_index* idx = nullptr;
     int nslots = 0, both = 0, match_type = 0;
+    uint32_t max_occ = 0;  // -smem: the occurrence cap of every batch (slamem_stream_set_max_occ; 0: none)
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     Slot slot[kMaxSlots];
@@ -318,8 +319,10 @@ int job_setup(slamem_stream* s, Slot& sl) {
     if (!sl.ev_done) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
     if (!sl.ev_k8) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_k8, hipEventDisableTiming));
     if (!sl.h_scal) SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_scal), 16 * sizeof(unsigned long long), hipHostMallocDefault));
-    return search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, s->match_type, sl.d_mems,
-                           sl.cap, sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal);
+    int rc = search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, s->match_type,
+                             sl.d_mems, sl.cap, sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal);
+    search_job_max_occ(sl.job, s->max_occ);
+    return rc;
 }
 int stage_prepare(slamem_stream* s, Slot& sl) {
     int rc = job_setup(s, sl);
@@ -605,8 +608,8 @@ int slamem_stream_destroy(slamem_stream* s) {
 
 int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream** out) {
-    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 2)) {
-        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0, 1 or 2)");
+    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 3)) {
+        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0, 1, 2 or 3)");
         return SLAMEM_ERR_ARG;
     }
     *out = nullptr;
@@ -676,6 +679,21 @@ int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_
     }
     for (int k = 0; k < s->nthreads; k++) s->th[k] = std::thread(worker, s, k);
     *out = s;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_set_max_occ(slamem_stream* s, uint32_t max_occ) {
+    if (!s) { set_error("slamem_stream_set_max_occ: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type != 3 && max_occ != 0) {
+        set_error("slamem_stream_set_max_occ: an occurrence cap needs match type 3 (-smem)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (s->submitted != 0) {
+        set_error("slamem_stream_set_max_occ: the stream has batches already (set the cap before the first submit)");
+        return SLAMEM_ERR_ARG;
+    }
+    s->max_occ = max_occ;
     return SLAMEM_OK;
 }
 

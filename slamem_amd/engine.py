@@ -189,15 +189,17 @@ class Index:
 
     # ---- GetMatches (slamem.c:90-207) for a batch ---------------------------------------------------------
     def matcher(self, num_queries: int, both_strands: bool, mems_capacity: int, query_bytes: int,
-                mam: bool = False, mum: bool = False) -> "Matcher":
-        return Matcher(self, num_queries, both_strands, mems_capacity, query_bytes, mam, mum)
+                mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0) -> "Matcher":
+        return Matcher(self, num_queries, both_strands, mems_capacity, query_bytes, mam, mum, smem, max_occ)
 
     def find_mems(self, queries, offsets, min_len: int = 20, both_strands: bool = False, mam: bool = False,
-                  mum: bool = False):
+                  mum: bool = False, smem: bool = False, max_occ: int = 0):
         """Convenience: host arrays in, (mems structured array, block_offsets) out.  mam=True: -mam mode
         (slamem_find_mams_device; slamem.c:131,657).  mum=True: -mum mode, the MEMs no other MEM of their strand
-        block contains in either coordinate (slamem_find_mums_device)."""
-        _match_type(mam, mum)
+        block contains in either coordinate (slamem_find_mums_device).  smem=True: -smem mode, the MEMs whose query
+        interval no other MEM of their strand block strictly contains; max_occ > 0 also drops the intervals that more than
+        max_occ MEMs of the block share (slamem_find_smems_device)."""
+        _match_type(mam, mum, smem, max_occ)
         dev = self.device
         q = np.ascontiguousarray(np.frombuffer(queries, dtype=np.uint8) if isinstance(queries, (bytes, bytearray))
                                  else queries, dtype=np.uint8)
@@ -209,7 +211,7 @@ class Index:
         od = torch.from_numpy(offsets.view(np.int64)).to(dev)
         cap = max(1024, q.shape[0] // 8 + 4 * num)
         while True:
-            m = self.matcher(num, both_strands, cap, int(offsets[-1]) if num else 0, mam, mum)
+            m = self.matcher(num, both_strands, cap, int(offsets[-1]) if num else 0, mam, mum, smem, max_occ)
             try:
                 total = m.run(qd, od, min_len)
                 break
@@ -223,22 +225,29 @@ class Index:
         return out, m.block_offsets.cpu().numpy().view(np.uint64)
 
 
-def _match_type(mam: bool, mum: bool) -> int:
-    """The C ABI's match type: 0 -mem, 1 -mam, 2 -mum.  The reference has one matchType (slamem.c:35): not both."""
-    if mam and mum:
-        raise ValueError("mam and mum exclude each other: one match type per search")
-    return 2 if mum else (1 if mam else 0)
+def _match_type(mam: bool, mum: bool, smem: bool = False, max_occ: int = 0) -> int:
+    """The C ABI's match type: 0 -mem, 1 -mam, 2 -mum, 3 -smem.  The reference has one matchType (slamem.c:35): not two.
+    max_occ (the occurrence cap, 0: none) only with smem."""
+    if int(bool(mam)) + int(bool(mum)) + int(bool(smem)) > 1:
+        raise ValueError("mam, mum and smem exclude each other: one match type per search")
+    if max_occ and not smem:
+        raise ValueError("max_occ is the occurrence cap of smem: it needs smem=True")
+    if not 0 <= int(max_occ) < 2 ** 32:
+        raise ValueError("max_occ must be in [0, 2^32)")
+    return 3 if smem else (2 if mum else (1 if mam else 0))
 
 
 class Matcher:
     """Pre-allocated output + workspace buffers for repeated slamem_find_mems_device calls (bench loop)."""
 
     def __init__(self, index: Index, num_queries: int, both_strands: bool, mems_capacity: int, query_bytes: int,
-                 mam: bool = False, mum: bool = False):
+                 mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0):
         self.index = index
-        self.match_type = _match_type(mam, mum)
+        self.match_type = _match_type(mam, mum, smem, max_occ)
         self.mam = self.match_type == 1
         self.mum = self.match_type == 2
+        self.smem = self.match_type == 3
+        self.max_occ = int(max_occ)
         self.num_queries = int(num_queries)
         self.both = bool(both_strands)
         self.capacity = int(mems_capacity)
@@ -246,7 +255,9 @@ class Matcher:
         dev = index.device
         nb = self.num_queries * (2 if self.both else 1)
         need = C.c_uint64()
-        ws_fn = capi.lib().slamem_find_mums_workspace_bytes if self.mum else capi.lib().slamem_find_mems_workspace_bytes
+        L = capi.lib()
+        ws_fn = (L.slamem_find_mems_workspace_bytes, L.slamem_find_mems_workspace_bytes, L.slamem_find_mums_workspace_bytes,
+                 L.slamem_find_smems_workspace_bytes)[self.match_type]
         capi.check(ws_fn(self.num_queries, int(self.both), self.query_bytes, self.capacity, C.byref(need)))
         self.workspace = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
         self.mems = torch.empty((max(self.capacity, 1), 3), dtype=torch.int32, device=dev)
@@ -257,10 +268,12 @@ class Matcher:
         dev = self.index.device
         total = C.c_uint64()
         L = capi.lib()
-        fn = (L.slamem_find_mems_device, L.slamem_find_mams_device, L.slamem_find_mums_device)[self.match_type]
+        fn = (L.slamem_find_mems_device, L.slamem_find_mams_device, L.slamem_find_mums_device,
+              L.slamem_find_smems_device)[self.match_type]
+        occ = (self.max_occ,) if self.smem else ()
         rc = fn(
             self.index._h, _ptr(queries_dev), _ptr(offsets_dev), self.num_queries, self.query_bytes, int(min_len),
-            int(self.both),
+            int(self.both), *occ,
             _ptr(self.mems), self.capacity, _ptr(self.block_offsets), _ptr(self.workspace), self.workspace.numel(),
             _stream_handle(dev), C.byref(total))
         self.last_total = int(total.value)
@@ -295,13 +308,15 @@ class Stream:
     query loop of GetMatches (slamem.c:90-207) for reads that live in host memory."""
 
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
-                 mam: bool = False, mum: bool = False):
-        match_type = _match_type(mam, mum)
+                 mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0):
+        match_type = _match_type(mam, mum, smem, max_occ)
         self.index = index
         self.both = bool(both_strands)
         self._h = C.c_void_p()
         capi.check(capi.lib().slamem_stream_create(index._h, int(slots), int(max_batch_chars), int(max_batch_queries),
                                                    int(self.both), match_type, C.byref(self._h)))
+        if max_occ:
+            capi.check(capi.lib().slamem_stream_set_max_occ(self._h, int(max_occ)))
         self._keep = []
 
     def submit(self, chars: np.ndarray, offsets: np.ndarray, min_len: int) -> None:

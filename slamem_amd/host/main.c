@@ -41,7 +41,9 @@
 #include "slamem_host.h"
 
 #define VERSION "0.8.2"
-static const char MATCH_TYPE_CHAR[] = "EAU";
+/* what the output lines call a match of each type: M%cM with the reference's "EAU" (slamem.c:35), and SMEM for -smem */
+static const char *const MATCH_TYPE_NAME[4] = {"MEM", "MAM", "MUM", "SMEM"};
+#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 4 ? (t) : 0]
 
 /* the device warm-up thread (see main) is joined before the process ends, whichever way it ends */
 static pthread_t g_warm_tid;
@@ -563,6 +565,8 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("Options:\n");
     printf("\t-mem\tfind MEMs: any number of occurrences in both ref and query (default)\n");
     printf("\t-mam\tfind MAMs: unique in ref but any number in query\n");
+    printf("\t-smem\tfind SMEMs: MEMs whose query interval no other MEM of the strand contains\n");
+    printf("\t-occ\twith -smem: drop SMEMs found at more than this many places in ref (default: no limit)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
     printf("\t-b\tprocess both forward and reverse strands\n");
@@ -587,7 +591,7 @@ int main(int argc, char **argv) {
     char *out_name;
     FILE *out;
     slamem_index *idx = NULL, *gpus[16];
-    int rc, ngpu = 1;
+    int rc, ngpu = 1, max_occ = 0;
     double t0;
     long long total_matches = 0, total_sum = 0;
     slh_buffer buf = {0, 0, 0};
@@ -608,7 +612,15 @@ int main(int argc, char **argv) {
         if (argc != 3) { printf("Usage: %s -c <fasta_file>\n\n", argv[0]); return -1; }
         return slh_clean_fasta(argv[2], stdout);
     }
-    if (o.match_type < 0) exit_message("Options -mam and -mum exclude each other"); /* before any GPU work */
+    if (o.match_type < 0) { /* before any GPU work */
+        if (slh_parse_argument(argc, argv, "SM", 0)) exit_message("Option -smem excludes -mam and -mum");
+        exit_message("Options -mam and -mum exclude each other");
+    }
+    switch (slh_parse_max_occ(argc, argv, &max_occ)) {
+    case -1: exit_message("Option -occ needs a whole number of at least 1"); break;
+    case 1: if (o.match_type != 3) exit_message("Option -occ needs -smem"); break;
+    default: break;
+    }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
     if (o.ref_name_given && o.ref_name_empty) exit_message("No reference name string provided");
     if ((env = getenv("SLAMEM_DEVICE")) != NULL) device = atoi(env);
@@ -709,8 +721,10 @@ int main(int argc, char **argv) {
     else out_name = argv[o.out_arg];
 
     /* GetMatches (slamem.c:37-218) */
-    say("> Using options: minimum M%cM length = %d ; strand = %s\n", MATCH_TYPE_CHAR[o.match_type], o.min_mem_len,
+    say("> Using options: minimum %s length = %d ; strand = %s", MATCH_NAME(o.match_type), o.min_mem_len,
            o.both_strands == 0 ? "forward only" : "forward + reverse");
+    if (max_occ > 0) say(" ; maximum occurrences = %d", max_occ);
+    say("\n");
     out = fopen(out_name, "w");
     if (!out) {
         release_stdout();
@@ -845,6 +859,10 @@ int main(int argc, char **argv) {
         double ts0 = now_s();
         for (g = 0; g < ngpu && (nranges || overlap); g++) { /* batch b is searched on GPU b mod ngpu: no data-path collective */
             rc = slamem_stream_create(gpus[g], slots, max_chars, max_recs, o.both_strands, o.match_type, &g_streams[g]);
+            if (rc == SLAMEM_OK && max_occ > 0) {
+                g_nstreams = g + 1; /* (so that a failure below tears this stream down too) */
+                rc = slamem_stream_set_max_occ(g_streams[g], (uint32_t)max_occ);
+            }
             if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("setting up the search pipeline", rc); }
             g_nstreams = g + 1;
             inflight[g] = 0;
@@ -917,7 +935,7 @@ int main(int argc, char **argv) {
                     dots = slh_progress_dots(q->recs[ri].size);
                     say(":: \"%s%s\" ", q->recs[ri].name, sidx ? " Reverse" : "");
                     for (d = 0; d < dots; d++) fputc('.', g_mo ? g_mo : stdout);
-                    say(" (%d M%cMs ; avg size = %d bp)\n", (int)cnt, MATCH_TYPE_CHAR[o.match_type], (int)(cnt ? sum / cnt : 0));
+                    say(" (%d %ss ; avg size = %d bp)\n", (int)cnt, MATCH_NAME(o.match_type), (int)(cnt ? sum / cnt : 0));
                     printed++;
                 }
                 if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
@@ -986,11 +1004,11 @@ int main(int argc, char **argv) {
     }
     double t_end0 = now_s(), t_end1;
     if (total_queries != 1) /* slamem.c:210-212 (the reference divides by zero when nothing matched) */
-        printf(":: Average %d M%cMs found per query sequence (total = %lld, avg size = %d bp)\n",
-               (int)(total_matches / total_queries), MATCH_TYPE_CHAR[o.match_type], total_matches,
+        printf(":: Average %d %ss found per query sequence (total = %lld, avg size = %d bp)\n",
+               (int)(total_matches / total_queries), MATCH_NAME(o.match_type), total_matches,
                (int)(total_matches ? total_sum / total_matches : 0));
     fflush(stdout);
-    printf("> Saving M%cMs to <%s> ... ", MATCH_TYPE_CHAR[o.match_type], out_name);
+    printf("> Saving %ss to <%s> ... ", MATCH_NAME(o.match_type), out_name);
     if (fflush(out) != 0 || ferror(out)) exit_message("Cannot write output file");
     if (getenv("SLAMEM_FULL_TEARDOWN") != NULL && fclose(out) != 0) exit_message("Cannot write output file");
     t_end1 = now_s();

@@ -5,6 +5,7 @@
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
+#include <errno.h>
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
@@ -650,6 +651,25 @@ int slh_parse_argument(int argc, char **argv, const char *optionchars, int parse
     return parse ? -1 : 0;
 }
 
+int slh_parse_max_occ(int argc, char **argv, int *out) {
+    int i;
+    *out = 0;
+    for (i = 1; i < argc; i++) {
+        const char *a = argv[i];
+        char *end;
+        long v;
+        /* the two letters "oc" decide, as for every option; an 'o' option takes the next argument ("-o" alone is the output) */
+        if (a[0] != '-' || (a[1] != 'o' && a[1] != 'O') || (a[2] != 'c' && a[2] != 'C')) continue;
+        if (i == argc - 1) return -1;
+        errno = 0;
+        v = strtol(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) return -1;
+        *out = (int)v;
+        return 1;
+    }
+    return 0;
+}
+
 char *slh_append_to_basename(const char *filename, const char *extra) {
     int n = (int)strlen(filename), i;
     char *res;
@@ -741,6 +761,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
     o->match_type = slh_parse_argument(argc, argv, "MA", 0) ? 1 : 0;
     if (slh_parse_argument(argc, argv, "MU", 0)) /* -mum: the match type the reference reserves ("EAU", slamem.c:35) */
         o->match_type = o->match_type == 1 ? -1 : 2;
+    if (slh_parse_argument(argc, argv, "SM", 0)) /* -smem: super-maximal matches (an 's' option takes no value; "-s" alone is the sort tool) */
+        o->match_type = o->match_type != 0 ? -1 : 3;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;
