@@ -99,7 +99,7 @@ typedef struct {
     double prefilter_ms_sum;
     double k8_ms_sum;
     float seed_ms;            /* K8s k_seed_mems (seed-and-compare for reads; runs in K8a's place), part of search_kernel_ms (ABI 4) */
-    float mum_filter_ms;      /* -mum / -smem: the filter behind K9 (mum_filter.hip, smem_filter.hip), large blocks included; 0 for -mem and -mam */
+    float mum_filter_ms;      /* -mum / -smem / -chain: the filter behind K9 (mum_filter.hip, smem_filter.hip, chain_filter.hip), large blocks included; 0 for -mem and -mam */
     double seed_ms_sum;
 } slamem_timings;
 
@@ -338,6 +338,23 @@ int slamem_find_smems_device(const slamem_index *idx, const void *queries_dev, c
                              uint32_t max_occ, slamem_mem *mems_dev, uint64_t mems_capacity, uint64_t *block_offsets_dev,
                              void *workspace_dev, uint64_t workspace_bytes, void *stream, uint64_t *total_out);
 
+/* The same batch in chain mode (option -chain: matchType 4): of every strand block's -mem rows, the best
+ * collinear chain.  With eq = q + L, ep = p + L and G = max_gap (option -mgap; 0: the default 5000; below 2^31), row j may
+ * precede row i iff 0 < q_i - q_j <= G, 0 < p_i - p_j <= G, eq_j < eq_i and ep_j < ep_i; a chain's score is the length of its
+ * first row plus min(L_i, eq_i - eq_j, ep_i - ep_j) - |(p_i - q_i) - (p_j - q_j)| for every consecutive pair.  The rows of the
+ * block's best chain are kept (ties: DESIGN 4.12), in the -mem order; block_scores_dev (may be NULL) takes a uint32 per
+ * strand block, the chain's score, 0 for an empty block.  p is a merged-reference coordinate: a chain may step from one
+ * reference record into the next.  Otherwise as slamem_find_smems_device: every block kept (empty ones too), the capacity
+ * rule (SLAMEM_ERR_CAPACITY with *total_out = the -mem count a retry needs), one host round trip per batch, a block out of the
+ * emission order fails the call with SLAMEM_ERR_ARG.  The workspace is slamem_find_chains_workspace_bytes() bytes. */
+int slamem_find_chains_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes,
+                                       uint64_t mems_capacity, uint64_t *bytes_out);
+int slamem_find_chains_device(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,
+                              uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands,
+                              uint32_t max_gap, slamem_mem *mems_dev, uint64_t mems_capacity, uint64_t *block_offsets_dev,
+                              uint32_t *block_scores_dev /* may be NULL */, void *workspace_dev, uint64_t workspace_bytes,
+                              void *stream, uint64_t *total_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -353,6 +370,11 @@ int slamem_find_mums_host(const slamem_index *idx, const char *queries, const ui
 int slamem_find_smems_host(const slamem_index *idx, const char *queries, const uint64_t *offsets,
                            uint32_t num_queries, uint32_t min_len, int both_strands, uint32_t max_occ,
                            slamem_mem **mems_out, uint64_t **block_offsets_out, uint64_t *total_out);
+/* (block_scores_out may be NULL; otherwise a third malloc()ed array, a uint32 per strand block) */
+int slamem_find_chains_host(const slamem_index *idx, const char *queries, const uint64_t *offsets,
+                            uint32_t num_queries, uint32_t min_len, int both_strands, uint32_t max_gap,
+                            slamem_mem **mems_out, uint64_t **block_offsets_out, uint32_t **block_scores_out,
+                            uint64_t *total_out);
 void slamem_host_free(void *p);
 
 /* ---- (b') MEM retrieval, host to host, pipelined -------------------------------
@@ -364,9 +386,12 @@ void slamem_host_free(void *p);
  *
  *   slamem_stream_create   max_batch_chars / max_batch_queries: what to reserve per slot (a larger batch makes its slot
  *                          grow); match_type 0 = MEM, 1 = MAM (-mam), 2 = MUM (-mum:
- *                          only the kept rows come back), 3 = SMEM (-smem: likewise)
+ *                          only the kept rows come back), 3 = SMEM (-smem: likewise), 4 = chain (-chain: likewise; rows
+ *                          and offsets, no scores)
  *   slamem_stream_set_max_occ  -smem: the occurrence cap of every batch (0: none, the default); before the first submit
  *                          (SLAMEM_ERR_ARG after it, or with a cap on a stream of another match type)
+ *   slamem_stream_set_max_gap  -chain: the maximum gap of every batch (0: the default 5000); before the first submit
+ *                          (SLAMEM_ERR_ARG after it, with a gap on a stream of another match type, or from 2^31)
  *   slamem_stream_submit   record i of the batch is queries[offsets[i] .. offsets[i+1]) -- offsets[0] need not be 0, so
  *                          a front end passes its whole character buffer and a window of its offsets array.  Returns at
  *                          once; the characters and offsets must stay unchanged until the batch has been collected.
@@ -385,6 +410,7 @@ typedef struct slamem_stream slamem_stream;
 int slamem_stream_create(const slamem_index *idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream **out);
 int slamem_stream_set_max_occ(slamem_stream *s, uint32_t max_occ);
+int slamem_stream_set_max_gap(slamem_stream *s, uint32_t max_gap);
 int slamem_stream_submit(slamem_stream *s, const char *queries, const uint64_t *offsets, uint32_t num_queries,
                          uint32_t min_len);
 /* The same for reads the caller holds PACKED (ABI 4; no reference counterpart: the reference reads letters, sequence.c:89-270).

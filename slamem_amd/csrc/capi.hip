@@ -471,11 +471,36 @@ int slamem_find_smems_device(const slamem_index* idx, const void* queries_dev, c
                             total_out, max_occ);
 }
 
+int slamem_find_chains_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                       uint64_t* bytes_out) {
+    if (!bytes_out) return SLAMEM_ERR_ARG;
+    *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, 4);
+    return SLAMEM_OK;
+}
+
+static bool chain_gap_ok(uint32_t max_gap, const char* who) {
+    if (max_gap < 0x80000000u) return true;
+    set_error("%s: the maximum gap must be below 2^31 (0: the default, %u)", who, kChainDefaultGap);
+    return false;
+}
+
+int slamem_find_chains_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
+                              uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap,
+                              slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev,
+                              uint32_t* block_scores_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream,
+                              uint64_t* total_out) {
+    if (!chain_gap_ok(max_gap, "slamem_find_chains_device")) return SLAMEM_ERR_ARG;
+    return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 4, mems_dev,
+                            mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
+                            total_out, 0, max_gap, block_scores_dev);
+}
+
 void slamem_host_free(void* p) { free(p); }
 
 static int find_matches_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                              uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out,
-                             uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ = 0);
+                             uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ = 0, uint32_t max_gap = 0,
+                             uint32_t** block_scores_out = nullptr);
 
 int slamem_find_mems_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                           uint32_t min_len, int both_strands, slamem_mem** mems_out, uint64_t** block_offsets_out,
@@ -502,9 +527,18 @@ int slamem_find_smems_host(const slamem_index* idx, const char* queries, const u
                              max_occ);
 }
 
+int slamem_find_chains_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
+                            uint32_t min_len, int both_strands, uint32_t max_gap, slamem_mem** mems_out,
+                            uint64_t** block_offsets_out, uint32_t** block_scores_out, uint64_t* total_out) {
+    if (!chain_gap_ok(max_gap, "slamem_find_chains_host")) return SLAMEM_ERR_ARG;
+    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 4, mems_out, block_offsets_out, total_out,
+                             0, max_gap, block_scores_out);
+}
+
 static int find_matches_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                              uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out,
-                             uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ) {
+                             uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ, uint32_t max_gap,
+                             uint32_t** block_scores_out) {
     if (!idx || !offsets || !mems_out || !block_offsets_out || !total_out || (num_queries && !queries)) {
         set_error("slamem_find_mems_host: null argument");
         return SLAMEM_ERR_ARG;
@@ -512,9 +546,10 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
     SLAMEM_HIP(hipSetDevice(idx->device));
     const uint64_t qbytes = offsets[num_queries];
     const uint64_t num_blocks = (uint64_t)num_queries * (both_strands ? 2 : 1);
-    void *d_q = nullptr, *d_off = nullptr, *d_boff = nullptr, *d_mems = nullptr, *d_ws = nullptr;
+    void *d_q = nullptr, *d_off = nullptr, *d_boff = nullptr, *d_mems = nullptr, *d_ws = nullptr, *d_score = nullptr;
     slamem_mem* h_mems = nullptr;
     uint64_t* h_boff = nullptr;
+    uint32_t* h_score = nullptr;
     int rc = SLAMEM_OK;
     uint64_t cap = qbytes / 16 + 4 * (uint64_t)num_blocks + 1024;  // first guess; grown on SLAMEM_ERR_CAPACITY
     hipError_t e;
@@ -522,6 +557,7 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
     HOST_TRY(hipMalloc(&d_q, qbytes + 16));
     HOST_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
     HOST_TRY(hipMalloc(&d_boff, (num_blocks + 1) * 8));
+    if (block_scores_out) HOST_TRY(hipMalloc(&d_score, (num_blocks + 1) * 4));
     HOST_TRY(hipMemcpy(d_q, queries, qbytes, hipMemcpyHostToDevice));
     HOST_TRY(hipMemcpy(d_off, offsets, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
     for (int attempt = 0; attempt < 3; attempt++) {
@@ -530,7 +566,7 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
         HOST_TRY(hipMalloc(&d_ws, ws_bytes));
         rc = find_mems_device(idx, d_q, static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands,
                               match_type, static_cast<slamem_mem*>(d_mems), cap, static_cast<uint64_t*>(d_boff), d_ws, ws_bytes,
-                              nullptr, total_out, max_occ);
+                              nullptr, total_out, max_occ, max_gap, static_cast<uint32_t*>(d_score));
         if (rc != SLAMEM_ERR_CAPACITY) break;
         (void)hipFree(d_mems); d_mems = nullptr;
         (void)hipFree(d_ws); d_ws = nullptr;
@@ -539,9 +575,15 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
     if (rc) goto done;
     h_mems = static_cast<slamem_mem*>(malloc((*total_out ? *total_out : 1) * sizeof(slamem_mem)));
     h_boff = static_cast<uint64_t*>(malloc((num_blocks + 1) * 8));
-    if (!h_mems || !h_boff) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
+    if (block_scores_out) h_score = static_cast<uint32_t*>(malloc((num_blocks + 1) * 4));
+    if (!h_mems || !h_boff || (block_scores_out && !h_score)) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
     if (*total_out) HOST_TRY(hipMemcpy(h_mems, d_mems, *total_out * sizeof(slamem_mem), hipMemcpyDeviceToHost));
     HOST_TRY(hipMemcpy(h_boff, d_boff, (num_blocks + 1) * 8, hipMemcpyDeviceToHost));
+    if (block_scores_out) {
+        if (num_blocks) HOST_TRY(hipMemcpy(h_score, d_score, num_blocks * 4, hipMemcpyDeviceToHost));
+        *block_scores_out = h_score;
+        h_score = nullptr;
+    }
     *mems_out = h_mems;
     *block_offsets_out = h_boff;
     h_mems = nullptr;
@@ -550,6 +592,8 @@ done:
 #undef HOST_TRY
     free(h_mems);
     free(h_boff);
+    free(h_score);
+    if (d_score) (void)hipFree(d_score);
     if (d_q) (void)hipFree(d_q);
     if (d_off) (void)hipFree(d_off);
     if (d_boff) (void)hipFree(d_boff);

@@ -304,9 +304,10 @@ int estimate_build_bytes(uint32_t n, int layout, uint64_t* arena_bytes, uint64_t
 int find_mems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ = 0);
+                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ = 0, uint32_t max_gap = 0,
+                     uint32_t* block_scores_dev = nullptr);
 uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity);
-// The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum, 3 -smem: the -mem workspace and the filter's behind it)
+// The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum, 3 -smem, 4 -chain: the -mem workspace and the filter's behind it)
 uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type);
 // -mum (mum_filter.hip): the filter's part of the workspace; where in it K9 places the -mem list; the filter behind K9 (blocks of
 // up to 256 MEMs; host_scalars[0] = rows kept, [1] = large blocks << 40 | their rows, both copied asynchronously), and the
@@ -324,6 +325,13 @@ uint64_t smem_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
 void smem_list_buffers(void* smem_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
 int smem_filter(void* smem_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_occ, slamem_mem* out_mems, uint64_t* out_boff,
                 unsigned long long* host_scalars, hipStream_t stream);
+// -chain (chain_filter.hip): the same three for the best collinear chain of every block (max_gap: the maximum gap, >= 1;
+// out_scores: a uint32 per block, or nullptr; host_scalars as for -smem)
+constexpr uint32_t kChainDefaultGap = 5000;
+uint64_t chain_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
+void chain_list_buffers(void* chain_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
+int chain_filter(void* chain_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, slamem_mem* out_mems, uint64_t* out_boff,
+                 uint32_t* out_scores, unsigned long long* host_scalars, hipStream_t stream);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).
@@ -342,6 +350,8 @@ void search_job_slices_hint(SearchJob* j, uint32_t slices);
 void search_job_k8_wave_cap(SearchJob* j, uint32_t waves);
 // (between init and the search) -smem: the occurrence cap of the batch (0: none)
 void search_job_max_occ(SearchJob* j, uint32_t max_occ);
+// (between init and the search) -chain: the maximum gap of the batch (0: kChainDefaultGap)
+void search_job_max_gap(SearchJob* j, uint32_t max_gap);
 constexpr uint32_t kSearchSliceLen = 4096;
 int search_job_tables(SearchJob* j, hipStream_t stream);
 int search_job_prep(SearchJob* j, hipStream_t stream);

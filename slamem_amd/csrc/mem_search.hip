@@ -3507,13 +3507,14 @@ uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint6
     return layout_workspace(num_queries, both_strands ? 2 : 1, query_bytes, mems_capacity).bytes;
 }
 
-// -mum / -smem: the -mem workspace, then the filter's (mum_filter.hip / smem_filter.hip: the -mem list K9 places, and what the
-// filter needs beside it)
+// -mum / -smem / -chain: the -mem workspace, then the filter's (mum_filter.hip / smem_filter.hip / chain_filter.hip: the -mem
+// list K9 places, and what the filter needs beside it)
 uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type) {
     const uint64_t mem = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity);
     const uint64_t nb = num_queries * (both_strands ? 2u : 1u);
     if (match_type == 2) return mem + mum_workspace_bytes(nb, mems_capacity);
     if (match_type == 3) return mem + smem_workspace_bytes(nb, mems_capacity);
+    if (match_type == 4) return mem + chain_workspace_bytes(nb, mems_capacity);
     return mem;
 }
 
@@ -3552,14 +3553,18 @@ struct SearchJob {
     uint64_t* out_boff = nullptr;
     void* mum_ws = nullptr;
     unsigned long long mum_large = 0;
-    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter behind K9 (-mum and -smem)
+    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter behind K9 (-mum, -smem and -chain)
     // -smem: as -mum, with smem_filter.hip behind K9 (every block on the device: nothing for finish()); max_occ: the cap (0: none)
     bool smem = false;
     uint32_t max_occ = 0;
+    // -chain: as -smem, with chain_filter.hip behind K9; max_gap: the maximum gap (0: the default); scores_dev: a uint32 per block, or null
+    bool chain = false;
+    uint32_t max_gap = 0;
+    uint32_t* scores_dev = nullptr;
     unsigned long long scal_own[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t k8_wave_cap = 0;  // waves of this batch's K8 (0: as many as the chip holds); a pipeline that keeps two K8 launches in flight gives each a part of the chip
     uint32_t slices_hint = 0xFFFFFFFFu;  // a caller that has the offsets on the host and knows the slice count (no record longer than a slice: one per record) saves tables() its round trip
-    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, -mum: [9] rows kept, [10] large blocks, -smem: [9] rows kept, [10] a block out of order + 1; pinned memory if the caller has some
+    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, -mum: [9] rows kept, [10] large blocks, -smem and -chain: [9] rows kept, [10] a block out of order + 1; pinned memory if the caller has some
     ~SearchJob();
     int init(const slamem_index* idx_, const void* queries_dev_, const uint64_t* offsets_dev_, uint32_t num_queries_,
              uint64_t query_bytes_, uint32_t min_len_, int both_strands_, int match_type_, slamem_mem* mems_dev_,
@@ -3597,7 +3602,7 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
     min_len = min_len_; both_strands = both_strands_; match_type = match_type_; mems_dev = mems_dev_; mems_capacity = mems_capacity_;
     block_offsets_dev = block_offsets_dev_; workspace_dev = workspace_dev_; workspace_bytes = workspace_bytes_;
     total = 0; nitems = 0; prefiltered = false; timed_k8 = false; launched = false;
-    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false;
+    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false; chain = false;
     if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity) || (!queries_dev && num_queries)) {
         set_error("slamem_find_mems_device: null argument");
         return SLAMEM_ERR_ARG;
@@ -3633,9 +3638,18 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         }
         smem = true;
         match_type = 0;
+    } else if (match_type == 4) {
+        // -chain: the -mem search, then the filter (chain_filter.hip); its row places are 32-bit, its differences 64-bit signed
+        if (mems_capacity >= 0xFFFF0000ull) {
+            set_error("slamem_find_chains_device: at most 2^32 - 2^16 MEMs of capacity per call");
+            return SLAMEM_ERR_ARG;
+        }
+        chain = true;
+        match_type = 0;
     }
     const uint64_t need_ws = mum ? w.bytes + mum_workspace_bytes(num_blocks, mems_capacity)
-                                 : smem ? w.bytes + smem_workspace_bytes(num_blocks, mems_capacity) : w.bytes;
+                                 : smem ? w.bytes + smem_workspace_bytes(num_blocks, mems_capacity)
+                                 : chain ? w.bytes + chain_workspace_bytes(num_blocks, mems_capacity) : w.bytes;
     if (workspace_bytes < need_ws) {
         set_error("slamem_find_mems_device: workspace too small (%llu < %llu bytes)",
                   (unsigned long long)workspace_bytes, (unsigned long long)need_ws);
@@ -3651,11 +3665,16 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         out_boff = block_offsets_dev;
         mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
         smem_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
+    } else if (chain) {
+        out_mems = mems_dev;
+        out_boff = block_offsets_dev;
+        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
+        chain_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
     }
     want_stats = search_stats_wanted();
     for (int i = 0; i < 6; i++)
         if (!ev[i]) SLAMEM_HIP(hipEventCreate(&ev[i]));
-    for (int i = 0; i < 2 && (mum || smem); i++)
+    for (int i = 0; i < 2 && (mum || smem || chain); i++)
         if (!ev_mum[i]) SLAMEM_HIP(hipEventCreate(&ev_mum[i]));
     return SLAMEM_OK;
 }
@@ -4183,6 +4202,12 @@ int SearchJob::place(hipStream_t stream) {
         int rc = smem_filter(mum_ws, num_blocks, mems_capacity, max_occ, out_mems, out_boff, h_scal + 9, stream);
         if (rc != SLAMEM_OK) return rc;
         (void)hipEventRecord(ev_mum[1], stream);
+    } else if (chain) {  // -chain: likewise
+        (void)hipEventRecord(ev_mum[0], stream);
+        int rc = chain_filter(mum_ws, num_blocks, mems_capacity, max_gap ? max_gap : kChainDefaultGap, out_mems, out_boff, scores_dev,
+                              h_scal + 9, stream);
+        if (rc != SLAMEM_OK) return rc;
+        (void)hipEventRecord(ev_mum[1], stream);
     }
     return SLAMEM_OK;
 }
@@ -4286,6 +4311,15 @@ int SearchJob::collect() {
             return SLAMEM_ERR_ARG;
         }
         total = h_scal[9];
+    } else if (chain && !saw_long) {
+        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
+        if (h_scal[10]) {
+            set_error("slamem_find_chains_device: the -mem rows of strand block %llu are not in the emission order (query start "
+                      "descending, then length non-increasing); no chains returned", h_scal[10] - 1ull);
+            total = 0;
+            return SLAMEM_ERR_ARG;
+        }
+        total = h_scal[9];
     }
     return SLAMEM_OK;
 }
@@ -4310,10 +4344,12 @@ int SearchJob::finish(hipStream_t stream) {
 static int run_job(SearchJob& job, const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                    uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                    slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                   uint64_t workspace_bytes, hipStream_t stream, uint32_t max_occ) {
+                   uint64_t workspace_bytes, hipStream_t stream, uint32_t max_occ, uint32_t max_gap, uint32_t* scores_dev) {
     int rc = job.init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                       mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
     job.max_occ = max_occ;
+    job.max_gap = max_gap;
+    job.scores_dev = scores_dev;
     if (rc == SLAMEM_OK) rc = job.tables(stream);
     if (rc == SLAMEM_OK) rc = job.prep(stream);
     if (rc == SLAMEM_OK) rc = job.search(stream);
@@ -4328,16 +4364,17 @@ static int run_job(SearchJob& job, const slamem_index* idx, const void* queries_
 int find_mems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ) {
+                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ, uint32_t max_gap,
+                     uint32_t* block_scores_dev) {
     if (!total_out) { set_error("slamem_find_mems_device: null argument"); return SLAMEM_ERR_ARG; }
     SearchJob job;
     job.speculate = true;
     int rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ);
+                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev);
     if (rc == SLAMEM_OK && job.saw_long) {  // a record longer than a slice among the reads: once more, with the item tables
         job.speculate = false;
         rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ);
+                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev);
     }
     *total_out = job.total;
     return rc;
@@ -4354,12 +4391,15 @@ int search_job_init(SearchJob* j, const slamem_index* idx, const void* queries_d
     j->slices_hint = 0xFFFFFFFFu;
     j->k8_wave_cap = 0;
     j->max_occ = 0;
+    j->max_gap = 0;
+    j->scores_dev = nullptr;
     return j->init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                    mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
 }
 void search_job_slices_hint(SearchJob* j, uint32_t slices) { j->slices_hint = slices; }
 void search_job_k8_wave_cap(SearchJob* j, uint32_t waves) { j->k8_wave_cap = waves; }
 void search_job_max_occ(SearchJob* j, uint32_t max_occ) { j->max_occ = max_occ; }
+void search_job_max_gap(SearchJob* j, uint32_t max_gap) { j->max_gap = max_gap; }
 int search_job_tables(SearchJob* j, hipStream_t stream) { return j->tables(stream); }
 int search_job_prep(SearchJob* j, hipStream_t stream) { return j->prep(stream); }
 int search_job_search(SearchJob* j, hipStream_t stream) { return j->search(stream); }

@@ -91,6 +91,7 @@ struct slamem_stream {
     const slamem_index* idx = nullptr;
     int nslots = 0, both = 0, match_type = 0;
     uint32_t max_occ = 0;  // -smem: the occurrence cap of every batch (slamem_stream_set_max_occ; 0: none)
+    uint32_t max_gap = 0;  // -chain: the maximum gap of every batch (slamem_stream_set_max_gap; 0: the default)
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     Slot slot[kMaxSlots];
@@ -322,6 +323,7 @@ int job_setup(slamem_stream* s, Slot& sl) {
     int rc = search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, s->match_type,
                              sl.d_mems, sl.cap, sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal);
     search_job_max_occ(sl.job, s->max_occ);
+    search_job_max_gap(sl.job, s->max_gap);
     return rc;
 }
 int stage_prepare(slamem_stream* s, Slot& sl) {
@@ -608,8 +610,8 @@ int slamem_stream_destroy(slamem_stream* s) {
 
 int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream** out) {
-    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 3)) {
-        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0, 1, 2 or 3)");
+    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 4)) {
+        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 4)");
         return SLAMEM_ERR_ARG;
     }
     *out = nullptr;
@@ -694,6 +696,25 @@ int slamem_stream_set_max_occ(slamem_stream* s, uint32_t max_occ) {
         return SLAMEM_ERR_ARG;
     }
     s->max_occ = max_occ;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_set_max_gap(slamem_stream* s, uint32_t max_gap) {
+    if (!s) { set_error("slamem_stream_set_max_gap: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type != 4 && max_gap != 0) {
+        set_error("slamem_stream_set_max_gap: a maximum gap needs match type 4 (-chain)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (max_gap >= 0x80000000u) {
+        set_error("slamem_stream_set_max_gap: the maximum gap must be below 2^31");
+        return SLAMEM_ERR_ARG;
+    }
+    if (s->submitted != 0) {
+        set_error("slamem_stream_set_max_gap: the stream has batches already (set the gap before the first submit)");
+        return SLAMEM_ERR_ARG;
+    }
+    s->max_gap = max_gap;
     return SLAMEM_OK;
 }
 

@@ -189,17 +189,29 @@ class Index:
 
     # ---- GetMatches (slamem.c:90-207) for a batch ---------------------------------------------------------
     def matcher(self, num_queries: int, both_strands: bool, mems_capacity: int, query_bytes: int,
-                mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0) -> "Matcher":
-        return Matcher(self, num_queries, both_strands, mems_capacity, query_bytes, mam, mum, smem, max_occ)
+                mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
+                max_gap: int = 0) -> "Matcher":
+        return Matcher(self, num_queries, both_strands, mems_capacity, query_bytes, mam, mum, smem, max_occ, chain, max_gap)
 
     def find_mems(self, queries, offsets, min_len: int = 20, both_strands: bool = False, mam: bool = False,
-                  mum: bool = False, smem: bool = False, max_occ: int = 0):
+                  mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False, max_gap: int = 0):
         """Convenience: host arrays in, (mems structured array, block_offsets) out.  mam=True: -mam mode
         (slamem_find_mams_device; slamem.c:131,657).  mum=True: -mum mode, the MEMs no other MEM of their strand
         block contains in either coordinate (slamem_find_mums_device).  smem=True: -smem mode, the MEMs whose query
         interval no other MEM of their strand block strictly contains; max_occ > 0 also drops the intervals that more than
-        max_occ MEMs of the block share (slamem_find_smems_device)."""
-        _match_type(mam, mum, smem, max_occ)
+        max_occ MEMs of the block share (slamem_find_smems_device).  chain=True: -chain mode, the MEMs of each strand
+        block's best collinear chain; max_gap: the maximum gap, 0 for the default 5000 (slamem_find_chains_device;
+        find_chains also returns the scores)."""
+        mems, boff, _ = self._find(queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap)
+        return mems, boff
+
+    def find_chains(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0):
+        """-chain mode: (mems, block_offsets, scores) -- the MEMs of each strand block's best collinear chain in the -mem
+        order, and a uint32 score per strand block (0 for an empty block).  DESIGN.md 4.12 has the definition."""
+        return self._find(queries, offsets, min_len, both_strands, False, False, False, 0, True, max_gap)
+
+    def _find(self, queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap):
+        _match_type(mam, mum, smem, max_occ, chain, max_gap)
         dev = self.device
         q = np.ascontiguousarray(np.frombuffer(queries, dtype=np.uint8) if isinstance(queries, (bytes, bytearray))
                                  else queries, dtype=np.uint8)
@@ -211,7 +223,7 @@ class Index:
         od = torch.from_numpy(offsets.view(np.int64)).to(dev)
         cap = max(1024, q.shape[0] // 8 + 4 * num)
         while True:
-            m = self.matcher(num, both_strands, cap, int(offsets[-1]) if num else 0, mam, mum, smem, max_occ)
+            m = self.matcher(num, both_strands, cap, int(offsets[-1]) if num else 0, mam, mum, smem, max_occ, chain, max_gap)
             try:
                 total = m.run(qd, od, min_len)
                 break
@@ -222,32 +234,44 @@ class Index:
         mems = m.mems[:total].cpu().numpy().view(np.uint32).reshape(-1, 3)
         out = np.empty(total, dtype=MEM_DTYPE)
         out["ref_pos"], out["query_pos"], out["length"] = mems[:, 0], mems[:, 1], mems[:, 2]
-        return out, m.block_offsets.cpu().numpy().view(np.uint64)
+        scores = m.scores.cpu().numpy().view(np.uint32) if m.chain else None
+        return out, m.block_offsets.cpu().numpy().view(np.uint64), scores
 
 
-def _match_type(mam: bool, mum: bool, smem: bool = False, max_occ: int = 0) -> int:
-    """The C ABI's match type: 0 -mem, 1 -mam, 2 -mum, 3 -smem.  The reference has one matchType (slamem.c:35): not two.
-    max_occ (the occurrence cap, 0: none) only with smem."""
+def _match_type(mam: bool, mum: bool, smem: bool = False, max_occ: int = 0, chain: bool = False, max_gap: int = 0) -> int:
+    """The C ABI's match type: 0 -mem, 1 -mam, 2 -mum, 3 -smem, 4 -chain.  The reference has one matchType (slamem.c:35): not
+    two.  max_occ (the occurrence cap, 0: none) only with smem; max_gap (the maximum gap, 0: the default) only with chain."""
     if int(bool(mam)) + int(bool(mum)) + int(bool(smem)) > 1:
         raise ValueError("mam, mum and smem exclude each other: one match type per search")
+    if chain and (mam or mum or smem):
+        raise ValueError("chain excludes mam, mum and smem: one match type per search")
+    if max_occ and chain:
+        raise ValueError("max_occ is the occurrence cap of smem: not with chain")
+    if max_gap and not chain:
+        raise ValueError("max_gap is the maximum gap of chain: it needs chain=True")
+    if not 0 <= int(max_gap) < 2 ** 31:
+        raise ValueError("max_gap must be in [0, 2^31)")
     if max_occ and not smem:
         raise ValueError("max_occ is the occurrence cap of smem: it needs smem=True")
     if not 0 <= int(max_occ) < 2 ** 32:
         raise ValueError("max_occ must be in [0, 2^32)")
-    return 3 if smem else (2 if mum else (1 if mam else 0))
+    return 4 if chain else (3 if smem else (2 if mum else (1 if mam else 0)))
 
 
 class Matcher:
     """Pre-allocated output + workspace buffers for repeated slamem_find_mems_device calls (bench loop)."""
 
     def __init__(self, index: Index, num_queries: int, both_strands: bool, mems_capacity: int, query_bytes: int,
-                 mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0):
+                 mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
+                 max_gap: int = 0):
         self.index = index
-        self.match_type = _match_type(mam, mum, smem, max_occ)
+        self.match_type = _match_type(mam, mum, smem, max_occ, chain, max_gap)
         self.mam = self.match_type == 1
         self.mum = self.match_type == 2
         self.smem = self.match_type == 3
         self.max_occ = int(max_occ)
+        self.chain = self.match_type == 4
+        self.max_gap = int(max_gap)
         self.num_queries = int(num_queries)
         self.both = bool(both_strands)
         self.capacity = int(mems_capacity)
@@ -257,11 +281,13 @@ class Matcher:
         need = C.c_uint64()
         L = capi.lib()
         ws_fn = (L.slamem_find_mems_workspace_bytes, L.slamem_find_mems_workspace_bytes, L.slamem_find_mums_workspace_bytes,
-                 L.slamem_find_smems_workspace_bytes)[self.match_type]
+                 L.slamem_find_smems_workspace_bytes, L.slamem_find_chains_workspace_bytes)[self.match_type]
         capi.check(ws_fn(self.num_queries, int(self.both), self.query_bytes, self.capacity, C.byref(need)))
         self.workspace = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
         self.mems = torch.empty((max(self.capacity, 1), 3), dtype=torch.int32, device=dev)
         self.block_offsets = torch.empty(nb + 1, dtype=torch.int64, device=dev)
+        if self.chain:  # a uint32 per strand block: the score of its chain
+            self.scores = torch.zeros(nb, dtype=torch.int32, device=dev)
         self.last_total = 0
 
     def run(self, queries_dev: torch.Tensor, offsets_dev: torch.Tensor, min_len: int) -> int:
@@ -269,12 +295,13 @@ class Matcher:
         total = C.c_uint64()
         L = capi.lib()
         fn = (L.slamem_find_mems_device, L.slamem_find_mams_device, L.slamem_find_mums_device,
-              L.slamem_find_smems_device)[self.match_type]
-        occ = (self.max_occ,) if self.smem else ()
+              L.slamem_find_smems_device, L.slamem_find_chains_device)[self.match_type]
+        occ = (self.max_occ,) if self.smem else (self.max_gap,) if self.chain else ()
+        scores = (_ptr(self.scores),) if self.chain else ()
         rc = fn(
             self.index._h, _ptr(queries_dev), _ptr(offsets_dev), self.num_queries, self.query_bytes, int(min_len),
             int(self.both), *occ,
-            _ptr(self.mems), self.capacity, _ptr(self.block_offsets), _ptr(self.workspace), self.workspace.numel(),
+            _ptr(self.mems), self.capacity, _ptr(self.block_offsets), *scores, _ptr(self.workspace), self.workspace.numel(),
             _stream_handle(dev), C.byref(total))
         self.last_total = int(total.value)
         capi.check(rc)
@@ -308,8 +335,9 @@ class Stream:
     query loop of GetMatches (slamem.c:90-207) for reads that live in host memory."""
 
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
-                 mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0):
-        match_type = _match_type(mam, mum, smem, max_occ)
+                 mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
+                 max_gap: int = 0):
+        match_type = _match_type(mam, mum, smem, max_occ, chain, max_gap)
         self.index = index
         self.both = bool(both_strands)
         self._h = C.c_void_p()
@@ -317,6 +345,8 @@ class Stream:
                                                    int(self.both), match_type, C.byref(self._h)))
         if max_occ:
             capi.check(capi.lib().slamem_stream_set_max_occ(self._h, int(max_occ)))
+        if max_gap:
+            capi.check(capi.lib().slamem_stream_set_max_gap(self._h, int(max_gap)))
         self._keep = []
 
     def submit(self, chars: np.ndarray, offsets: np.ndarray, min_len: int) -> None:

@@ -41,9 +41,10 @@
 #include "slamem_host.h"
 
 #define VERSION "0.8.2"
-/* what the output lines call a match of each type: M%cM with the reference's "EAU" (slamem.c:35), and SMEM for -smem */
-static const char *const MATCH_TYPE_NAME[4] = {"MEM", "MAM", "MUM", "SMEM"};
-#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 4 ? (t) : 0]
+/* what the output lines call a match of each type: M%cM with the reference's "EAU" (slamem.c:35), SMEM for -smem, and
+ * "chained MEM" for the rows -chain keeps */
+static const char *const MATCH_TYPE_NAME[5] = {"MEM", "MAM", "MUM", "SMEM", "chained MEM"};
+#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 5 ? (t) : 0]
 
 /* the device warm-up thread (see main) is joined before the process ends, whichever way it ends */
 static pthread_t g_warm_tid;
@@ -567,6 +568,8 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-mam\tfind MAMs: unique in ref but any number in query\n");
     printf("\t-smem\tfind SMEMs: MEMs whose query interval no other MEM of the strand contains\n");
     printf("\t-occ\twith -smem: drop SMEMs found at more than this many places in ref (default: no limit)\n");
+    printf("\t-chain\tkeep the MEMs of the best collinear chain of each strand\n");
+    printf("\t-mgap\twith -chain: maximum gap between chained MEMs in ref and in query (default=5000)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
     printf("\t-b\tprocess both forward and reverse strands\n");
@@ -591,7 +594,7 @@ int main(int argc, char **argv) {
     char *out_name;
     FILE *out;
     slamem_index *idx = NULL, *gpus[16];
-    int rc, ngpu = 1, max_occ = 0;
+    int rc, ngpu = 1, max_occ = 0, max_gap = 0;
     double t0;
     long long total_matches = 0, total_sum = 0;
     slh_buffer buf = {0, 0, 0};
@@ -613,12 +616,18 @@ int main(int argc, char **argv) {
         return slh_clean_fasta(argv[2], stdout);
     }
     if (o.match_type < 0) { /* before any GPU work */
+        if (slh_parse_argument(argc, argv, "CH", 0)) exit_message("Option -chain excludes -mam, -mum and -smem");
         if (slh_parse_argument(argc, argv, "SM", 0)) exit_message("Option -smem excludes -mam and -mum");
         exit_message("Options -mam and -mum exclude each other");
     }
     switch (slh_parse_max_occ(argc, argv, &max_occ)) {
     case -1: exit_message("Option -occ needs a whole number of at least 1"); break;
     case 1: if (o.match_type != 3) exit_message("Option -occ needs -smem"); break;
+    default: break;
+    }
+    switch (slh_parse_max_gap(argc, argv, &max_gap)) {
+    case -1: exit_message("Option -mgap needs a whole number of at least 1"); break;
+    case 1: if (o.match_type != 4) exit_message("Option -mgap needs -chain"); break;
     default: break;
     }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
@@ -724,6 +733,7 @@ int main(int argc, char **argv) {
     say("> Using options: minimum %s length = %d ; strand = %s", MATCH_NAME(o.match_type), o.min_mem_len,
            o.both_strands == 0 ? "forward only" : "forward + reverse");
     if (max_occ > 0) say(" ; maximum occurrences = %d", max_occ);
+    if (o.match_type == 4) say(" ; maximum gap = %d", max_gap > 0 ? max_gap : 5000);
     say("\n");
     out = fopen(out_name, "w");
     if (!out) {
@@ -862,6 +872,10 @@ int main(int argc, char **argv) {
             if (rc == SLAMEM_OK && max_occ > 0) {
                 g_nstreams = g + 1; /* (so that a failure below tears this stream down too) */
                 rc = slamem_stream_set_max_occ(g_streams[g], (uint32_t)max_occ);
+            }
+            if (rc == SLAMEM_OK && max_gap > 0) {
+                g_nstreams = g + 1;
+                rc = slamem_stream_set_max_gap(g_streams[g], (uint32_t)max_gap);
             }
             if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("setting up the search pipeline", rc); }
             g_nstreams = g + 1;

@@ -670,6 +670,26 @@ int slh_parse_max_occ(int argc, char **argv, int *out) {
     return 0;
 }
 
+int slh_parse_max_gap(int argc, char **argv, int *out) {
+    int i;
+    *out = 0;
+    for (i = 1; i < argc; i++) {
+        const char *a = argv[i];
+        char *end;
+        long v;
+        /* the two letters "mg" decide, as for every option; an 'm' option takes the next argument ("-m" alone is the minimum
+           sequence length, "-ma", "-mu" the match types) */
+        if (a[0] != '-' || (a[1] != 'm' && a[1] != 'M') || (a[2] != 'g' && a[2] != 'G')) continue;
+        if (i == argc - 1) return -1;
+        errno = 0;
+        v = strtol(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) return -1;
+        *out = (int)v;
+        return 1;
+    }
+    return 0;
+}
+
 char *slh_append_to_basename(const char *filename, const char *extra) {
     int n = (int)strlen(filename), i;
     char *res;
@@ -763,6 +783,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type == 1 ? -1 : 2;
     if (slh_parse_argument(argc, argv, "SM", 0)) /* -smem: super-maximal matches (an 's' option takes no value; "-s" alone is the sort tool) */
         o->match_type = o->match_type != 0 ? -1 : 3;
+    if (slh_parse_argument(argc, argv, "CH", 0)) /* -chain: the best collinear chain (a 'c' option takes no value; "-c" alone is the clean tool) */
+        o->match_type = o->match_type != 0 ? -1 : 4;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;

@@ -69,7 +69,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), -1 two of them */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), -1 two of them */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
@@ -84,6 +84,8 @@ int slh_parse_argument(int argc, char **argv, const char *optionchars, int parse
 /* -occ N (-oc...): the occurrence cap of -smem.  0 and *out = 0 when absent; 1 and *out = N for an integer N >= 1;
  * -1 when the value is missing, not an integer or < 1.  (Not a field of slh_options, whose layout callers mirror.) */
 int slh_parse_max_occ(int argc, char **argv, int *out);
+/* -mgap N (-mg...): the maximum gap of -chain, with the same results for an integer N in [1, 2^31). */
+int slh_parse_max_gap(int argc, char **argv, int *out);
 /* AppendToBasename (tools.c:65-79): everything before the last '.' of the whole path + extra */
 char *slh_append_to_basename(const char *filename, const char *extra);
 
