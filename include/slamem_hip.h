@@ -99,7 +99,7 @@ typedef struct {
     double prefilter_ms_sum;
     double k8_ms_sum;
     float seed_ms;            /* K8s k_seed_mems (seed-and-compare for reads; runs in K8a's place), part of search_kernel_ms (ABI 4) */
-    float mum_filter_ms;      /* -mum / -smem / -chain: the filter behind K9 (mum_filter.hip, smem_filter.hip, chain_filter.hip), large blocks included; 0 for -mem and -mam */
+    float mum_filter_ms;      /* -mum / -smem / -chain / -ext: the filter behind K9 (mum_filter.hip, smem_filter.hip, chain_filter.hip, ext_filter.hip), large blocks included; 0 for -mem and -mam */
     double seed_ms_sum;
 } slamem_timings;
 
@@ -355,6 +355,28 @@ int slamem_find_chains_device(const slamem_index *idx, const void *queries_dev, 
                               uint32_t *block_scores_dev /* may be NULL */, void *workspace_dev, uint64_t workspace_bytes,
                               void *stream, uint64_t *total_out);
 
+/* The same batch in extension mode (option -ext: matchType 5): every -mem row (p, q, L) of a strand block is
+ * extended on its own diagonal, to the left and to the right, through mismatches.  A matching letter scores +1, a mismatch
+ * -mismatch_penalty (option -pen; 0: the default 4); a side ends in front of a letter outside either sequence or not one of
+ * A,C,G,T, or when the running score has fallen more than xdrop (option -xdrop; SLAMEM_EXT_XDROP_DEFAULT = UINT32_MAX: the
+ * default 20; 0 is a value of its own: the side ends at its first mismatch) below its best, and is cut back to the shortest
+ * prefix of the best score.  The row becomes (p - extL, q - extL, extL + L + extR); mismatches_dev (may be NULL) takes a
+ * uint32 per returned row, the positions inside it whose letters differ, in the order of mems_dev (room for mems_capacity
+ * rows).  Of the rows of a block that extend to the same segment only the first is kept; the others keep their order.
+ * Otherwise as slamem_find_smems_device: every block kept (empty ones too), the capacity rule (SLAMEM_ERR_CAPACITY with
+ * *total_out = the -mem count a retry needs), one host round trip per batch, a block out of the emission order fails the call
+ * with SLAMEM_ERR_ARG.  The filter compares the reads with the text planes of the index: an index without them (the COMPACT
+ * layout, or one built with the seed sections switched off) is refused with SLAMEM_ERR_ARG and nothing is run.  The workspace
+ * is slamem_find_exts_workspace_bytes() bytes. */
+#define SLAMEM_EXT_XDROP_DEFAULT 0xFFFFFFFFu
+int slamem_find_exts_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes,
+                                     uint64_t mems_capacity, uint64_t *bytes_out);
+int slamem_find_exts_device(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,
+                            uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands,
+                            uint32_t mismatch_penalty, uint32_t xdrop, slamem_mem *mems_dev, uint64_t mems_capacity,
+                            uint64_t *block_offsets_dev, uint32_t *mismatches_dev /* may be NULL */, void *workspace_dev,
+                            uint64_t workspace_bytes, void *stream, uint64_t *total_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -375,6 +397,11 @@ int slamem_find_chains_host(const slamem_index *idx, const char *queries, const 
                             uint32_t num_queries, uint32_t min_len, int both_strands, uint32_t max_gap,
                             slamem_mem **mems_out, uint64_t **block_offsets_out, uint32_t **block_scores_out,
                             uint64_t *total_out);
+/* (mismatches_out may be NULL; otherwise a third malloc()ed array, a uint32 per returned row) */
+int slamem_find_exts_host(const slamem_index *idx, const char *queries, const uint64_t *offsets,
+                          uint32_t num_queries, uint32_t min_len, int both_strands, uint32_t mismatch_penalty, uint32_t xdrop,
+                          slamem_mem **mems_out, uint64_t **block_offsets_out, uint32_t **mismatches_out,
+                          uint64_t *total_out);
 void slamem_host_free(void *p);
 
 /* ---- (b') MEM retrieval, host to host, pipelined -------------------------------
@@ -387,11 +414,17 @@ void slamem_host_free(void *p);
  *   slamem_stream_create   max_batch_chars / max_batch_queries: what to reserve per slot (a larger batch makes its slot
  *                          grow); match_type 0 = MEM, 1 = MAM (-mam), 2 = MUM (-mum:
  *                          only the kept rows come back), 3 = SMEM (-smem: likewise), 4 = chain (-chain: likewise; rows
- *                          and offsets, no scores)
+ *                          and offsets, no scores), 5 = extension (-ext: the extended rows; their mismatches through
+ *                          slamem_stream_mismatches)
  *   slamem_stream_set_max_occ  -smem: the occurrence cap of every batch (0: none, the default); before the first submit
  *                          (SLAMEM_ERR_ARG after it, or with a cap on a stream of another match type)
  *   slamem_stream_set_max_gap  -chain: the maximum gap of every batch (0: the default 5000); before the first submit
  *                          (SLAMEM_ERR_ARG after it, with a gap on a stream of another match type, or from 2^31)
+ *   slamem_stream_set_ext_params  -ext: mismatch penalty (0: the default 4) and X-drop (SLAMEM_EXT_XDROP_DEFAULT: the default
+ *                          20) of every batch; before the first submit (SLAMEM_ERR_ARG after it, or with values other than the
+ *                          defaults' placeholders on a stream of another match type)
+ *   slamem_stream_mismatches  -ext: the mismatches (a uint32 per row) of the batch slamem_stream_next returned last, in the
+ *                          stream's pinned memory; valid as long as that batch's rows.  The same for submit and submit_packed.
  *   slamem_stream_submit   record i of the batch is queries[offsets[i] .. offsets[i+1]) -- offsets[0] need not be 0, so
  *                          a front end passes its whole character buffer and a window of its offsets array.  Returns at
  *                          once; the characters and offsets must stay unchanged until the batch has been collected.
@@ -411,6 +444,8 @@ int slamem_stream_create(const slamem_index *idx, int slots, uint64_t max_batch_
                          int both_strands, int match_type, slamem_stream **out);
 int slamem_stream_set_max_occ(slamem_stream *s, uint32_t max_occ);
 int slamem_stream_set_max_gap(slamem_stream *s, uint32_t max_gap);
+int slamem_stream_set_ext_params(slamem_stream *s, uint32_t mismatch_penalty, uint32_t xdrop);
+int slamem_stream_mismatches(slamem_stream *s, const uint32_t **out);
 int slamem_stream_submit(slamem_stream *s, const char *queries, const uint64_t *offsets, uint32_t num_queries,
                          uint32_t min_len);
 /* The same for reads the caller holds PACKED (ABI 4; no reference counterpart: the reference reads letters, sequence.c:89-270).

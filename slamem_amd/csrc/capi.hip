@@ -495,12 +495,28 @@ int slamem_find_chains_device(const slamem_index* idx, const void* queries_dev, 
                             total_out, 0, max_gap, block_scores_dev);
 }
 
+int slamem_find_exts_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                     uint64_t* bytes_out) {
+    if (!bytes_out) return SLAMEM_ERR_ARG;
+    *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, 5);
+    return SLAMEM_OK;
+}
+
+int slamem_find_exts_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                            uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t mismatch_penalty, uint32_t xdrop,
+                            slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, uint32_t* mismatches_dev,
+                            void* workspace_dev, uint64_t workspace_bytes, void* stream, uint64_t* total_out) {
+    return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 5, mems_dev,
+                            mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
+                            total_out, 0, 0, mismatches_dev, mismatch_penalty, xdrop);
+}
+
 void slamem_host_free(void* p) { free(p); }
 
 static int find_matches_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                              uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out,
                              uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ = 0, uint32_t max_gap = 0,
-                             uint32_t** block_scores_out = nullptr);
+                             uint32_t** block_scores_out = nullptr, uint32_t ext_penalty = 0, uint32_t ext_xdrop = kExtXdropUnset);
 
 int slamem_find_mems_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                           uint32_t min_len, int both_strands, slamem_mem** mems_out, uint64_t** block_offsets_out,
@@ -535,10 +551,18 @@ int slamem_find_chains_host(const slamem_index* idx, const char* queries, const 
                              0, max_gap, block_scores_out);
 }
 
+int slamem_find_exts_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
+                          uint32_t min_len, int both_strands, uint32_t mismatch_penalty, uint32_t xdrop, slamem_mem** mems_out,
+                          uint64_t** block_offsets_out, uint32_t** mismatches_out, uint64_t* total_out) {
+    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 5, mems_out, block_offsets_out, total_out,
+                             0, 0, mismatches_out, mismatch_penalty, xdrop);
+}
+
+// (block_scores_out: -chain's uint32 per strand block, or -ext's uint32 per returned row)
 static int find_matches_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                              uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out,
                              uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ, uint32_t max_gap,
-                             uint32_t** block_scores_out) {
+                             uint32_t** block_scores_out, uint32_t ext_penalty, uint32_t ext_xdrop) {
     if (!idx || !offsets || !mems_out || !block_offsets_out || !total_out || (num_queries && !queries)) {
         set_error("slamem_find_mems_host: null argument");
         return SLAMEM_ERR_ARG;
@@ -557,16 +581,21 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
     HOST_TRY(hipMalloc(&d_q, qbytes + 16));
     HOST_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
     HOST_TRY(hipMalloc(&d_boff, (num_blocks + 1) * 8));
-    if (block_scores_out) HOST_TRY(hipMalloc(&d_score, (num_blocks + 1) * 4));
+    if (block_scores_out && match_type != 5) HOST_TRY(hipMalloc(&d_score, (num_blocks + 1) * 4));
     HOST_TRY(hipMemcpy(d_q, queries, qbytes, hipMemcpyHostToDevice));
     HOST_TRY(hipMemcpy(d_off, offsets, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
     for (int attempt = 0; attempt < 3; attempt++) {
         uint64_t ws_bytes = search_workspace_bytes(num_queries, both_strands, qbytes, cap, match_type);
         HOST_TRY(hipMalloc(&d_mems, cap * sizeof(slamem_mem) + 16));
         HOST_TRY(hipMalloc(&d_ws, ws_bytes));
+        if (block_scores_out && match_type == 5) {  // (a uint32 per row: grows with the capacity)
+            if (d_score) (void)hipFree(d_score);
+            d_score = nullptr;
+            HOST_TRY(hipMalloc(&d_score, (cap + 1) * 4));
+        }
         rc = find_mems_device(idx, d_q, static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands,
                               match_type, static_cast<slamem_mem*>(d_mems), cap, static_cast<uint64_t*>(d_boff), d_ws, ws_bytes,
-                              nullptr, total_out, max_occ, max_gap, static_cast<uint32_t*>(d_score));
+                              nullptr, total_out, max_occ, max_gap, static_cast<uint32_t*>(d_score), ext_penalty, ext_xdrop);
         if (rc != SLAMEM_ERR_CAPACITY) break;
         (void)hipFree(d_mems); d_mems = nullptr;
         (void)hipFree(d_ws); d_ws = nullptr;
@@ -575,12 +604,13 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
     if (rc) goto done;
     h_mems = static_cast<slamem_mem*>(malloc((*total_out ? *total_out : 1) * sizeof(slamem_mem)));
     h_boff = static_cast<uint64_t*>(malloc((num_blocks + 1) * 8));
-    if (block_scores_out) h_score = static_cast<uint32_t*>(malloc((num_blocks + 1) * 4));
+    if (block_scores_out) h_score = static_cast<uint32_t*>(malloc(((match_type == 5 ? *total_out : num_blocks) + 1) * 4));
     if (!h_mems || !h_boff || (block_scores_out && !h_score)) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
     if (*total_out) HOST_TRY(hipMemcpy(h_mems, d_mems, *total_out * sizeof(slamem_mem), hipMemcpyDeviceToHost));
     HOST_TRY(hipMemcpy(h_boff, d_boff, (num_blocks + 1) * 8, hipMemcpyDeviceToHost));
     if (block_scores_out) {
-        if (num_blocks) HOST_TRY(hipMemcpy(h_score, d_score, num_blocks * 4, hipMemcpyDeviceToHost));
+        const uint64_t nscore = match_type == 5 ? *total_out : num_blocks;
+        if (nscore) HOST_TRY(hipMemcpy(h_score, d_score, nscore * 4, hipMemcpyDeviceToHost));
         *block_scores_out = h_score;
         h_score = nullptr;
     }

@@ -305,9 +305,9 @@ int find_mems_device(const slamem_index* idx, const void* queries_dev, const uin
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
                      uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ = 0, uint32_t max_gap = 0,
-                     uint32_t* block_scores_dev = nullptr);
+                     uint32_t* block_scores_dev = nullptr, uint32_t ext_penalty = 0, uint32_t ext_xdrop = 0xFFFFFFFFu);
 uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity);
-// The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum, 3 -smem, 4 -chain: the -mem workspace and the filter's behind it)
+// The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum, 3 -smem, 4 -chain, 5 -ext: the -mem workspace and the filter's behind it)
 uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type);
 // -mum (mum_filter.hip): the filter's part of the workspace; where in it K9 places the -mem list; the filter behind K9 (blocks of
 // up to 256 MEMs; host_scalars[0] = rows kept, [1] = large blocks << 40 | their rows, both copied asynchronously), and the
@@ -332,6 +332,16 @@ uint64_t chain_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
 void chain_list_buffers(void* chain_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
 int chain_filter(void* chain_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, slamem_mem* out_mems, uint64_t* out_boff,
                  uint32_t* out_scores, unsigned long long* host_scalars, hipStream_t stream);
+// -ext (ext_filter.hip): the same three for the ungapped X-drop extension of every row (penalty >= 1, xdrop >= 0; the batch's
+// letters and the text planes of the index are what it compares; out_mm: a uint32 per kept row, or nullptr; host_scalars as for
+// -smem).  In find_mems_device the per-row column travels in block_scores_dev.
+constexpr uint32_t kExtDefaultPenalty = 4, kExtDefaultXdrop = 20, kExtXdropUnset = 0xFFFFFFFFu;
+uint64_t ext_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity);
+void ext_list_buffers(void* ext_ws, uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity,
+                      slamem_mem** rows_out, uint64_t** boff_out);
+int ext_filter(void* ext_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
+               uint32_t strands, uint64_t query_bytes, uint64_t capacity, uint32_t penalty, uint32_t xdrop, slamem_mem* out_mems,
+               uint64_t* out_boff, uint32_t* out_mm, unsigned long long* host_scalars, hipStream_t stream);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).
@@ -352,6 +362,9 @@ void search_job_k8_wave_cap(SearchJob* j, uint32_t waves);
 void search_job_max_occ(SearchJob* j, uint32_t max_occ);
 // (between init and the search) -chain: the maximum gap of the batch (0: kChainDefaultGap)
 void search_job_max_gap(SearchJob* j, uint32_t max_gap);
+// (between init and the search) -ext: the mismatch penalty (0: kExtDefaultPenalty), the drop (kExtXdropUnset: kExtDefaultXdrop)
+// and where the mismatches of the kept rows go (a uint32 per row of capacity, or nullptr)
+void search_job_ext(SearchJob* j, uint32_t penalty, uint32_t xdrop, uint32_t* mismatches_dev);
 constexpr uint32_t kSearchSliceLen = 4096;
 int search_job_tables(SearchJob* j, hipStream_t stream);
 int search_job_prep(SearchJob* j, hipStream_t stream);

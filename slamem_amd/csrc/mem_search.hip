@@ -3507,14 +3507,15 @@ uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint6
     return layout_workspace(num_queries, both_strands ? 2 : 1, query_bytes, mems_capacity).bytes;
 }
 
-// -mum / -smem / -chain: the -mem workspace, then the filter's (mum_filter.hip / smem_filter.hip / chain_filter.hip: the -mem
-// list K9 places, and what the filter needs beside it)
+// -mum / -smem / -chain / -ext: the -mem workspace, then the filter's (mum_filter.hip / smem_filter.hip / chain_filter.hip /
+// ext_filter.hip: the -mem list K9 places, and what the filter needs beside it)
 uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type) {
     const uint64_t mem = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity);
     const uint64_t nb = num_queries * (both_strands ? 2u : 1u);
     if (match_type == 2) return mem + mum_workspace_bytes(nb, mems_capacity);
     if (match_type == 3) return mem + smem_workspace_bytes(nb, mems_capacity);
     if (match_type == 4) return mem + chain_workspace_bytes(nb, mems_capacity);
+    if (match_type == 5) return mem + ext_workspace_bytes(num_queries, nb, query_bytes, mems_capacity);
     return mem;
 }
 
@@ -3553,7 +3554,7 @@ struct SearchJob {
     uint64_t* out_boff = nullptr;
     void* mum_ws = nullptr;
     unsigned long long mum_large = 0;
-    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter behind K9 (-mum, -smem and -chain)
+    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter behind K9 (-mum, -smem, -chain and -ext)
     // -smem: as -mum, with smem_filter.hip behind K9 (every block on the device: nothing for finish()); max_occ: the cap (0: none)
     bool smem = false;
     uint32_t max_occ = 0;
@@ -3561,10 +3562,15 @@ struct SearchJob {
     bool chain = false;
     uint32_t max_gap = 0;
     uint32_t* scores_dev = nullptr;
+    // -ext: as -smem, with ext_filter.hip behind K9; penalty: the mismatch penalty (0: the default), xdrop: the drop (0xFFFFFFFF: the
+    // default); mism_dev: a uint32 per kept row, or null
+    bool ext = false;
+    uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;
+    uint32_t* mism_dev = nullptr;
     unsigned long long scal_own[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t k8_wave_cap = 0;  // waves of this batch's K8 (0: as many as the chip holds); a pipeline that keeps two K8 launches in flight gives each a part of the chip
     uint32_t slices_hint = 0xFFFFFFFFu;  // a caller that has the offsets on the host and knows the slice count (no record longer than a slice: one per record) saves tables() its round trip
-    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, -mum: [9] rows kept, [10] large blocks, -smem and -chain: [9] rows kept, [10] a block out of order + 1; pinned memory if the caller has some
+    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, -mum: [9] rows kept, [10] large blocks, -smem, -chain and -ext: [9] rows kept, [10] a block out of order + 1; pinned memory if the caller has some
     ~SearchJob();
     int init(const slamem_index* idx_, const void* queries_dev_, const uint64_t* offsets_dev_, uint32_t num_queries_,
              uint64_t query_bytes_, uint32_t min_len_, int both_strands_, int match_type_, slamem_mem* mems_dev_,
@@ -3602,7 +3608,7 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
     min_len = min_len_; both_strands = both_strands_; match_type = match_type_; mems_dev = mems_dev_; mems_capacity = mems_capacity_;
     block_offsets_dev = block_offsets_dev_; workspace_dev = workspace_dev_; workspace_bytes = workspace_bytes_;
     total = 0; nitems = 0; prefiltered = false; timed_k8 = false; launched = false;
-    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false; chain = false;
+    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false; chain = false; ext = false;
     if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity) || (!queries_dev && num_queries)) {
         set_error("slamem_find_mems_device: null argument");
         return SLAMEM_ERR_ARG;
@@ -3646,10 +3652,25 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         }
         chain = true;
         match_type = 0;
+    } else if (match_type == 5) {
+        // -ext: the -mem search, then the filter (ext_filter.hip), which compares the reads with the text planes of the index
+        if (idx->hdr.off_tpl == 0 || !idx->view.tpl) {
+            set_error("slamem_find_exts_device: -ext needs the text planes of the index, and this index has none (%s layout%s); "
+                      "build it in the full layout with the seed sections", idx->hdr.layout == 2u ? "compact" : "full",
+                      idx->hdr.layout == 2u ? "" : ", built without the seed sections");
+            return SLAMEM_ERR_ARG;
+        }
+        if (mems_capacity >= 0xFFFF0000ull || num_blocks >= 0xFFFFFFFFull) {
+            set_error("slamem_find_exts_device: at most 2^32 - 2^16 MEMs of capacity and 2^32 - 2 strand blocks per call");
+            return SLAMEM_ERR_ARG;
+        }
+        ext = true;
+        match_type = 0;
     }
     const uint64_t need_ws = mum ? w.bytes + mum_workspace_bytes(num_blocks, mems_capacity)
                                  : smem ? w.bytes + smem_workspace_bytes(num_blocks, mems_capacity)
-                                 : chain ? w.bytes + chain_workspace_bytes(num_blocks, mems_capacity) : w.bytes;
+                                 : chain ? w.bytes + chain_workspace_bytes(num_blocks, mems_capacity)
+                                 : ext ? w.bytes + ext_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity) : w.bytes;
     if (workspace_bytes < need_ws) {
         set_error("slamem_find_mems_device: workspace too small (%llu < %llu bytes)",
                   (unsigned long long)workspace_bytes, (unsigned long long)need_ws);
@@ -3670,11 +3691,16 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         out_boff = block_offsets_dev;
         mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
         chain_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
+    } else if (ext) {
+        out_mems = mems_dev;
+        out_boff = block_offsets_dev;
+        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
+        ext_list_buffers(mum_ws, num_queries, num_blocks, query_bytes, mems_capacity, &mems_dev, &block_offsets_dev);
     }
     want_stats = search_stats_wanted();
     for (int i = 0; i < 6; i++)
         if (!ev[i]) SLAMEM_HIP(hipEventCreate(&ev[i]));
-    for (int i = 0; i < 2 && (mum || smem || chain); i++)
+    for (int i = 0; i < 2 && (mum || smem || chain || ext); i++)
         if (!ev_mum[i]) SLAMEM_HIP(hipEventCreate(&ev_mum[i]));
     return SLAMEM_OK;
 }
@@ -4208,6 +4234,13 @@ int SearchJob::place(hipStream_t stream) {
                               h_scal + 9, stream);
         if (rc != SLAMEM_OK) return rc;
         (void)hipEventRecord(ev_mum[1], stream);
+    } else if (ext) {  // -ext: likewise
+        (void)hipEventRecord(ev_mum[0], stream);
+        int rc = ext_filter(mum_ws, idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity,
+                            ext_penalty ? ext_penalty : kExtDefaultPenalty, ext_xdrop == kExtXdropUnset ? kExtDefaultXdrop : ext_xdrop,
+                            out_mems, out_boff, mism_dev, h_scal + 9, stream);
+        if (rc != SLAMEM_OK) return rc;
+        (void)hipEventRecord(ev_mum[1], stream);
     }
     return SLAMEM_OK;
 }
@@ -4320,6 +4353,15 @@ int SearchJob::collect() {
             return SLAMEM_ERR_ARG;
         }
         total = h_scal[9];
+    } else if (ext && !saw_long) {
+        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
+        if (h_scal[10]) {
+            set_error("slamem_find_exts_device: the -mem rows of strand block %llu are not in the emission order (query start "
+                      "descending, then length non-increasing); no extended MEMs returned", h_scal[10] - 1ull);
+            total = 0;
+            return SLAMEM_ERR_ARG;
+        }
+        total = h_scal[9];
     }
     return SLAMEM_OK;
 }
@@ -4344,12 +4386,16 @@ int SearchJob::finish(hipStream_t stream) {
 static int run_job(SearchJob& job, const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                    uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                    slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                   uint64_t workspace_bytes, hipStream_t stream, uint32_t max_occ, uint32_t max_gap, uint32_t* scores_dev) {
+                   uint64_t workspace_bytes, hipStream_t stream, uint32_t max_occ, uint32_t max_gap, uint32_t* scores_dev,
+                   uint32_t ext_penalty, uint32_t ext_xdrop) {
     int rc = job.init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                       mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
     job.max_occ = max_occ;
     job.max_gap = max_gap;
     job.scores_dev = scores_dev;
+    job.ext_penalty = ext_penalty;
+    job.ext_xdrop = ext_xdrop;
+    job.mism_dev = scores_dev;  // (-ext: the per-row column travels in the place of -chain's per-block one)
     if (rc == SLAMEM_OK) rc = job.tables(stream);
     if (rc == SLAMEM_OK) rc = job.prep(stream);
     if (rc == SLAMEM_OK) rc = job.search(stream);
@@ -4365,16 +4411,18 @@ int find_mems_device(const slamem_index* idx, const void* queries_dev, const uin
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
                      uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ, uint32_t max_gap,
-                     uint32_t* block_scores_dev) {
+                     uint32_t* block_scores_dev, uint32_t ext_penalty, uint32_t ext_xdrop) {
     if (!total_out) { set_error("slamem_find_mems_device: null argument"); return SLAMEM_ERR_ARG; }
     SearchJob job;
     job.speculate = true;
     int rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev);
+                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev,
+                     ext_penalty, ext_xdrop);
     if (rc == SLAMEM_OK && job.saw_long) {  // a record longer than a slice among the reads: once more, with the item tables
         job.speculate = false;
         rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev);
+                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev,
+                     ext_penalty, ext_xdrop);
     }
     *total_out = job.total;
     return rc;
@@ -4393,6 +4441,9 @@ int search_job_init(SearchJob* j, const slamem_index* idx, const void* queries_d
     j->max_occ = 0;
     j->max_gap = 0;
     j->scores_dev = nullptr;
+    j->ext_penalty = 0;
+    j->ext_xdrop = kExtXdropUnset;
+    j->mism_dev = nullptr;
     return j->init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                    mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
 }
@@ -4400,6 +4451,11 @@ void search_job_slices_hint(SearchJob* j, uint32_t slices) { j->slices_hint = sl
 void search_job_k8_wave_cap(SearchJob* j, uint32_t waves) { j->k8_wave_cap = waves; }
 void search_job_max_occ(SearchJob* j, uint32_t max_occ) { j->max_occ = max_occ; }
 void search_job_max_gap(SearchJob* j, uint32_t max_gap) { j->max_gap = max_gap; }
+void search_job_ext(SearchJob* j, uint32_t penalty, uint32_t xdrop, uint32_t* mismatches_dev) {
+    j->ext_penalty = penalty;
+    j->ext_xdrop = xdrop;
+    j->mism_dev = mismatches_dev;
+}
 int search_job_tables(SearchJob* j, hipStream_t stream) { return j->tables(stream); }
 int search_job_prep(SearchJob* j, hipStream_t stream) { return j->prep(stream); }
 int search_job_search(SearchJob* j, hipStream_t stream) { return j->search(stream); }

@@ -55,6 +55,10 @@ struct Slot {
     uint64_t* h_boff = nullptr;
     slamem_mem* h_mems = nullptr;
     uint64_t h_cap = 0, h_boff_cap = 0;
+    // -ext: the mismatches of the batch's rows, a uint32 each (device: room for `cap` rows; pinned host: for `h_mm_cap`)
+    uint32_t* d_mm = nullptr;
+    uint32_t* h_mm = nullptr;
+    uint64_t h_mm_cap = 0;
     // the batch
     uint64_t seq = 0;
     const char* chars = nullptr;
@@ -92,6 +96,7 @@ struct slamem_stream {
     int nslots = 0, both = 0, match_type = 0;
     uint32_t max_occ = 0;  // -smem: the occurrence cap of every batch (slamem_stream_set_max_occ; 0: none)
     uint32_t max_gap = 0;  // -chain: the maximum gap of every batch (slamem_stream_set_max_gap; 0: the default)
+    uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;  // -ext: penalty and drop of every batch (slamem_stream_set_ext_params)
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     Slot slot[kMaxSlots];
@@ -127,11 +132,13 @@ namespace {
 int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search stage: device output + workspace
     if (sl.d_mems) (void)hipFree(sl.d_mems);
     if (sl.d_ws) (void)hipFree(sl.d_ws);
-    sl.d_mems = nullptr; sl.d_ws = nullptr;
+    if (sl.d_mm) (void)hipFree(sl.d_mm);
+    sl.d_mems = nullptr; sl.d_ws = nullptr; sl.d_mm = nullptr;
     sl.cap = need_cap;
     sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, s->match_type);
     SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mems), sl.cap * sizeof(slamem_mem) + 16));
     SLAMEM_HIP(hipMalloc(&sl.d_ws, sl.ws_bytes));
+    if (s->match_type == 5) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mm), sl.cap * 4 + 16));
     return SLAMEM_OK;
 }
 
@@ -264,8 +271,10 @@ int stage_upload(slamem_stream* s, Slot& sl) {
         if (sl.d_boff) (void)hipFree(sl.d_boff);
         if (sl.d_mems) (void)hipFree(sl.d_mems);
         if (sl.d_ws) (void)hipFree(sl.d_ws);
+        if (sl.d_mm) (void)hipFree(sl.d_mm);
         if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
         sl.d_ucnt = nullptr;
+        sl.d_mm = nullptr;
         sl.d_q = nullptr; sl.d_off = nullptr; sl.d_boff = nullptr; sl.d_mems = nullptr; sl.d_ws = nullptr;  // (the prepare stage sizes its own)
         sl.cap_chars = 0; sl.cap_q = 0;  // until all three are there: a failed allocation must not leave stale room behind
         SLAMEM_HIP(hipMalloc(&sl.d_q, nchars + 2 * kFront + 32));
@@ -324,6 +333,7 @@ int job_setup(slamem_stream* s, Slot& sl) {
                              sl.d_mems, sl.cap, sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal);
     search_job_max_occ(sl.job, s->max_occ);
     search_job_max_gap(sl.job, s->max_gap);
+    if (s->match_type == 5) search_job_ext(sl.job, s->ext_penalty, s->ext_xdrop, sl.d_mm);
     return rc;
 }
 int stage_prepare(slamem_stream* s, Slot& sl) {
@@ -441,6 +451,15 @@ int stage_download(slamem_stream* s, Slot& sl) {
         sl.h_cap = sl.cap;
     }
     if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_mems, sl.d_mems, sl.total * sizeof(slamem_mem), hipMemcpyDeviceToHost, st));
+    if (s->match_type == 5) {
+        if (sl.h_mm_cap < sl.cap || !sl.h_mm) {
+            if (sl.h_mm) (void)hipHostFree(sl.h_mm);
+            sl.h_mm = nullptr;
+            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_mm), sl.cap * 4 + 16, hipHostMallocDefault));
+            sl.h_mm_cap = sl.cap;
+        }
+        if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_mm, sl.d_mm, sl.total * 4, hipMemcpyDeviceToHost, st));
+    }
     SLAMEM_HIP(hipMemcpyAsync(sl.h_boff, sl.d_boff, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
     SLAMEM_HIP(hipStreamSynchronize(st));
     return SLAMEM_OK;
@@ -493,6 +512,8 @@ void free_slot(Slot& sl) {
     if (sl.d_boff) (void)hipFree(sl.d_boff);
     if (sl.d_mems) (void)hipFree(sl.d_mems);
     if (sl.d_ws) (void)hipFree(sl.d_ws);
+    if (sl.d_mm) (void)hipFree(sl.d_mm);
+    if (sl.h_mm) (void)hipHostFree(sl.h_mm);
     if (sl.d_planes) (void)hipFree(sl.d_planes);
     if (sl.d_other) (void)hipFree(sl.d_other);
     if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
@@ -610,8 +631,8 @@ int slamem_stream_destroy(slamem_stream* s) {
 
 int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream** out) {
-    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 4)) {
-        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 4)");
+    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 5)) {
+        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 5)");
         return SLAMEM_ERR_ARG;
     }
     *out = nullptr;
@@ -715,6 +736,37 @@ int slamem_stream_set_max_gap(slamem_stream* s, uint32_t max_gap) {
         return SLAMEM_ERR_ARG;
     }
     s->max_gap = max_gap;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_set_ext_params(slamem_stream* s, uint32_t mismatch_penalty, uint32_t xdrop) {
+    if (!s) { set_error("slamem_stream_set_ext_params: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type != 5 && (mismatch_penalty != 0 || xdrop != kExtXdropUnset)) {
+        set_error("slamem_stream_set_ext_params: a mismatch penalty or an X-drop needs match type 5 (-ext)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (s->submitted != 0) {
+        set_error("slamem_stream_set_ext_params: the stream has batches already (set the parameters before the first submit)");
+        return SLAMEM_ERR_ARG;
+    }
+    s->ext_penalty = mismatch_penalty;
+    s->ext_xdrop = xdrop;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_mismatches(slamem_stream* s, const uint32_t** out) {
+    if (!s || !out) { set_error("slamem_stream_mismatches: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    *out = nullptr;
+    if (s->match_type != 5) { set_error("slamem_stream_mismatches: the stream's match type is not 5 (-ext)"); return SLAMEM_ERR_ARG; }
+    if (s->returned == 0) { set_error("slamem_stream_mismatches: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
+    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
+    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
+        set_error("slamem_stream_mismatches: the batch slamem_stream_next returned last has no rows to show");
+        return SLAMEM_ERR_ARG;
+    }
+    *out = sl.h_mm;
     return SLAMEM_OK;
 }
 

@@ -190,19 +190,24 @@ class Index:
     # ---- GetMatches (slamem.c:90-207) for a batch ---------------------------------------------------------
     def matcher(self, num_queries: int, both_strands: bool, mems_capacity: int, query_bytes: int,
                 mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
-                max_gap: int = 0) -> "Matcher":
-        return Matcher(self, num_queries, both_strands, mems_capacity, query_bytes, mam, mum, smem, max_occ, chain, max_gap)
+                max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None) -> "Matcher":
+        return Matcher(self, num_queries, both_strands, mems_capacity, query_bytes, mam, mum, smem, max_occ, chain, max_gap,
+                       ext, penalty, xdrop)
 
     def find_mems(self, queries, offsets, min_len: int = 20, both_strands: bool = False, mam: bool = False,
-                  mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False, max_gap: int = 0):
+                  mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False, max_gap: int = 0,
+                  ext: bool = False, penalty: int = 0, xdrop=None):
         """Convenience: host arrays in, (mems structured array, block_offsets) out.  mam=True: -mam mode
         (slamem_find_mams_device; slamem.c:131,657).  mum=True: -mum mode, the MEMs no other MEM of their strand
         block contains in either coordinate (slamem_find_mums_device).  smem=True: -smem mode, the MEMs whose query
         interval no other MEM of their strand block strictly contains; max_occ > 0 also drops the intervals that more than
         max_occ MEMs of the block share (slamem_find_smems_device).  chain=True: -chain mode, the MEMs of each strand
         block's best collinear chain; max_gap: the maximum gap, 0 for the default 5000 (slamem_find_chains_device;
-        find_chains also returns the scores)."""
-        mems, boff, _ = self._find(queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap)
+        find_chains also returns the scores).  ext=True: -ext mode, every MEM extended through mismatches on its diagonal;
+        penalty: the mismatch penalty, 0 for the default 4; xdrop: the drop, None for the default 20
+        (slamem_find_exts_device; find_exts also returns the mismatches)."""
+        mems, boff, _ = self._find(queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap, ext, penalty,
+                                   xdrop)
         return mems, boff
 
     def find_chains(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0):
@@ -210,8 +215,15 @@ class Index:
         order, and a uint32 score per strand block (0 for an empty block).  DESIGN.md 4.12 has the definition."""
         return self._find(queries, offsets, min_len, both_strands, False, False, False, 0, True, max_gap)
 
-    def _find(self, queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap):
-        _match_type(mam, mum, smem, max_occ, chain, max_gap)
+    def find_exts(self, queries, offsets, min_len: int = 20, both_strands: bool = False, penalty: int = 0, xdrop=None):
+        """-ext mode: (rows, block_offsets, mismatches) -- every MEM of a strand block extended on its diagonal by the X-drop
+        rule of DESIGN.md 4.13 (a match +1, a mismatch -penalty, default 4; drop xdrop, default 20), rows that extend to the
+        same segment once, and a uint32 of mismatches per row."""
+        return self._find(queries, offsets, min_len, both_strands, False, False, False, 0, False, 0, True, penalty, xdrop)
+
+    def _find(self, queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap, ext=False, penalty=0,
+              xdrop=None):
+        _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
         dev = self.device
         q = np.ascontiguousarray(np.frombuffer(queries, dtype=np.uint8) if isinstance(queries, (bytes, bytearray))
                                  else queries, dtype=np.uint8)
@@ -223,7 +235,8 @@ class Index:
         od = torch.from_numpy(offsets.view(np.int64)).to(dev)
         cap = max(1024, q.shape[0] // 8 + 4 * num)
         while True:
-            m = self.matcher(num, both_strands, cap, int(offsets[-1]) if num else 0, mam, mum, smem, max_occ, chain, max_gap)
+            m = self.matcher(num, both_strands, cap, int(offsets[-1]) if num else 0, mam, mum, smem, max_occ, chain, max_gap,
+                             ext, penalty, xdrop)
             try:
                 total = m.run(qd, od, min_len)
                 break
@@ -235,12 +248,35 @@ class Index:
         out = np.empty(total, dtype=MEM_DTYPE)
         out["ref_pos"], out["query_pos"], out["length"] = mems[:, 0], mems[:, 1], mems[:, 2]
         scores = m.scores.cpu().numpy().view(np.uint32) if m.chain else None
+        if m.ext:  # (the third value of -ext: a uint32 per row)
+            scores = m.mismatches[:total].cpu().numpy().view(np.uint32)
         return out, m.block_offsets.cpu().numpy().view(np.uint64), scores
 
 
-def _match_type(mam: bool, mum: bool, smem: bool = False, max_occ: int = 0, chain: bool = False, max_gap: int = 0) -> int:
-    """The C ABI's match type: 0 -mem, 1 -mam, 2 -mum, 3 -smem, 4 -chain.  The reference has one matchType (slamem.c:35): not
-    two.  max_occ (the occurrence cap, 0: none) only with smem; max_gap (the maximum gap, 0: the default) only with chain."""
+XDROP_DEFAULT = 0xFFFFFFFF  # SLAMEM_EXT_XDROP_DEFAULT: "the default drop" in the C ABI (0 is a drop of its own)
+
+
+def _xdrop_arg(xdrop) -> int:
+    return XDROP_DEFAULT if xdrop is None else int(xdrop)
+
+
+def _match_type(mam: bool, mum: bool, smem: bool = False, max_occ: int = 0, chain: bool = False, max_gap: int = 0,
+                ext: bool = False, penalty: int = 0, xdrop=None) -> int:
+    """The C ABI's match type: 0 -mem, 1 -mam, 2 -mum, 3 -smem, 4 -chain, 5 -ext.  The reference has one matchType
+    (slamem.c:35): not two.  max_occ (the occurrence cap, 0: none) only with smem; max_gap (the maximum gap, 0: the default) only
+    with chain; penalty (0: the default) and xdrop (None: the default) only with ext."""
+    if ext and (mam or mum or smem or chain):
+        raise ValueError("ext excludes mam, mum, smem and chain: one match type per search")
+    if ext and (max_occ or max_gap):
+        raise ValueError("max_occ and max_gap belong to smem and chain: not with ext")
+    if (penalty or xdrop is not None) and not ext:
+        raise ValueError("penalty and xdrop are the parameters of ext: they need ext=True")
+    if not 0 <= int(penalty) < 2 ** 32:
+        raise ValueError("penalty must be in [0, 2^32) (0: the default)")
+    if xdrop is not None and not 0 <= int(xdrop) < 2 ** 32 - 1:
+        raise ValueError("xdrop must be in [0, 2^32 - 1) (None: the default)")
+    if ext:
+        return 5
     if int(bool(mam)) + int(bool(mum)) + int(bool(smem)) > 1:
         raise ValueError("mam, mum and smem exclude each other: one match type per search")
     if chain and (mam or mum or smem):
@@ -263,9 +299,12 @@ class Matcher:
 
     def __init__(self, index: Index, num_queries: int, both_strands: bool, mems_capacity: int, query_bytes: int,
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
-                 max_gap: int = 0):
+                 max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None):
         self.index = index
-        self.match_type = _match_type(mam, mum, smem, max_occ, chain, max_gap)
+        self.match_type = _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
+        self.ext = self.match_type == 5
+        self.penalty = int(penalty)
+        self.xdrop = _xdrop_arg(xdrop)
         self.mam = self.match_type == 1
         self.mum = self.match_type == 2
         self.smem = self.match_type == 3
@@ -281,13 +320,16 @@ class Matcher:
         need = C.c_uint64()
         L = capi.lib()
         ws_fn = (L.slamem_find_mems_workspace_bytes, L.slamem_find_mems_workspace_bytes, L.slamem_find_mums_workspace_bytes,
-                 L.slamem_find_smems_workspace_bytes, L.slamem_find_chains_workspace_bytes)[self.match_type]
+                 L.slamem_find_smems_workspace_bytes, L.slamem_find_chains_workspace_bytes,
+                 L.slamem_find_exts_workspace_bytes)[self.match_type]
         capi.check(ws_fn(self.num_queries, int(self.both), self.query_bytes, self.capacity, C.byref(need)))
         self.workspace = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
         self.mems = torch.empty((max(self.capacity, 1), 3), dtype=torch.int32, device=dev)
         self.block_offsets = torch.empty(nb + 1, dtype=torch.int64, device=dev)
         if self.chain:  # a uint32 per strand block: the score of its chain
             self.scores = torch.zeros(nb, dtype=torch.int32, device=dev)
+        if self.ext:  # a uint32 per row: its mismatches
+            self.mismatches = torch.zeros(max(self.capacity, 1), dtype=torch.int32, device=dev)
         self.last_total = 0
 
     def run(self, queries_dev: torch.Tensor, offsets_dev: torch.Tensor, min_len: int) -> int:
@@ -295,9 +337,9 @@ class Matcher:
         total = C.c_uint64()
         L = capi.lib()
         fn = (L.slamem_find_mems_device, L.slamem_find_mams_device, L.slamem_find_mums_device,
-              L.slamem_find_smems_device, L.slamem_find_chains_device)[self.match_type]
-        occ = (self.max_occ,) if self.smem else (self.max_gap,) if self.chain else ()
-        scores = (_ptr(self.scores),) if self.chain else ()
+              L.slamem_find_smems_device, L.slamem_find_chains_device, L.slamem_find_exts_device)[self.match_type]
+        occ = (self.max_occ,) if self.smem else (self.max_gap,) if self.chain else (self.penalty, self.xdrop) if self.ext else ()
+        scores = (_ptr(self.scores),) if self.chain else (_ptr(self.mismatches),) if self.ext else ()
         rc = fn(
             self.index._h, _ptr(queries_dev), _ptr(offsets_dev), self.num_queries, self.query_bytes, int(min_len),
             int(self.both), *occ,
@@ -336,8 +378,8 @@ class Stream:
 
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
-                 max_gap: int = 0):
-        match_type = _match_type(mam, mum, smem, max_occ, chain, max_gap)
+                 max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None):
+        match_type = _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
         self.index = index
         self.both = bool(both_strands)
         self._h = C.c_void_p()
@@ -347,7 +389,10 @@ class Stream:
             capi.check(capi.lib().slamem_stream_set_max_occ(self._h, int(max_occ)))
         if max_gap:
             capi.check(capi.lib().slamem_stream_set_max_gap(self._h, int(max_gap)))
+        if penalty or xdrop is not None:
+            capi.check(capi.lib().slamem_stream_set_ext_params(self._h, int(penalty), _xdrop_arg(xdrop)))
         self._keep = []
+        self._last_total = 0
 
     def submit(self, chars: np.ndarray, offsets: np.ndarray, min_len: int) -> None:
         """chars: uint8 array holding the records; offsets: uint64[num+1] into it (offsets[0] need not be 0)."""
@@ -372,6 +417,7 @@ class Stream:
         if self._keep:
             self._keep.pop(0)
         capi.check(rc)
+        self._last_total = int(total.value)
         nb = nq.value * (2 if self.both else 1)
         m = np.ctypeslib.as_array((C.c_uint8 * (12 * max(1, total.value))).from_address(mems.value))[: 12 * total.value]
         m = m.view(MEM_DTYPE)
@@ -379,6 +425,16 @@ class Stream:
         if copy:
             m, b = m.copy(), b.copy()
         return m, b, tm.as_dict()
+
+    def mismatches(self, copy: bool = True) -> np.ndarray:
+        """-ext: the mismatches (uint32 per row) of the batch next() returned last (slamem_stream_mismatches).  copy=False
+        returns a view of the stream's pinned buffer, valid until the next call of next()."""
+        p = C.POINTER(C.c_uint32)()
+        capi.check(capi.lib().slamem_stream_mismatches(self._h, C.byref(p)))
+        if self._last_total == 0:
+            return np.zeros(0, dtype=np.uint32)
+        a = np.ctypeslib.as_array(p, shape=(self._last_total,))
+        return a.copy() if copy else a
 
     def close(self):
         h, self._h = self._h, None

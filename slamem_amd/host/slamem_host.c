@@ -690,6 +690,33 @@ int slh_parse_max_gap(int argc, char **argv, int *out) {
     return 0;
 }
 
+/* is argv[i] the option whose first two letters are c0 c1 (either case)? */
+static int two_letter_option(const char *a, char c0, char c1) {
+    return a[0] == '-' && (a[1] == c0 || a[1] == (char)(c0 - 32)) && (a[2] == c1 || a[2] == (char)(c1 - 32));
+}
+
+int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out) {
+    int i, seen = 0;
+    *penalty_out = 0;
+    *xdrop_out = -1;
+    for (i = 1; i < argc; i++) {
+        const char *a = argv[i];
+        char *end;
+        long v;
+        int pen = two_letter_option(a, 'p', 'e'), xd = two_letter_option(a, 'x', 'd');
+        if (!pen && !xd) continue;
+        if (i == argc - 1) return -1;
+        errno = 0;
+        v = strtol(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < (pen ? 1 : 0) || v > 0x7FFFFFFFL) return -1;
+        if (pen) *penalty_out = (int)v;
+        else *xdrop_out = (int)v;
+        seen = 1;
+        i++;
+    }
+    return seen;
+}
+
 char *slh_append_to_basename(const char *filename, const char *extra) {
     int n = (int)strlen(filename), i;
     char *res;
@@ -725,6 +752,7 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
             oc = argv[i][1];
             if (oc >= 'A' && oc <= 'Z') oc = (char)('a' + (oc - 'A'));
             if (oc == 'l' || oc == 'o' || oc == 'm' || oc == 'v') i++; /* any option starting with l/o/m/v eats the next argument */
+            else if (two_letter_option(argv[i], 'p', 'e') || two_letter_option(argv[i], 'x', 'd')) i++; /* -pen N, -xdrop N (of -ext) */
             else if (oc == 'r') {
                 i++;
                 if (i == argc) break;
@@ -785,6 +813,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type != 0 ? -1 : 3;
     if (slh_parse_argument(argc, argv, "CH", 0)) /* -chain: the best collinear chain (a 'c' option takes no value; "-c" alone is the clean tool) */
         o->match_type = o->match_type != 0 ? -1 : 4;
+    if (slh_parse_argument(argc, argv, "EX", 0)) /* -ext: ungapped X-drop extension of every MEM (an 'e' option takes no value) */
+        o->match_type = o->match_type != 0 ? -1 : 5;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;
@@ -844,12 +874,18 @@ static inline char *put_u32(char *p, uint32_t v) {
 
 int slh_format_block(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *mems, uint64_t count,
                      const slh_record *refs, const uint32_t *merged_start, int num_refs, uint64_t *sum_len_out) {
+    return slh_format_block_ext(buf, query_name, reverse, mems, NULL, count, refs, merged_start, num_refs, sum_len_out);
+}
+
+int slh_format_block_ext(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *mems, const uint32_t *extra,
+                         uint64_t count, const slh_record *refs, const uint32_t *merged_start, int num_refs,
+                         uint64_t *sum_len_out) {
     size_t nl = strlen(query_name);
     uint64_t i, sum = 0;
     char *p;
     /* room for the whole block at once when its lines have a known bound (one reference record: three numbers of at
        most ten digits, two tabs, a newline) */
-    if (buf_reserve(buf, nl + 16 + (num_refs == 1 ? (size_t)count * 33 : 0))) return -1;
+    if (buf_reserve(buf, nl + 16 + (num_refs == 1 ? (size_t)count * (extra ? 44 : 33) : 0))) return -1;
     p = buf->data + buf->len;
     *p++ = '>';
     memcpy(p, query_name, nl);
@@ -864,6 +900,7 @@ int slh_format_block(slh_buffer *buf, const char *query_name, int reverse, const
             p = put_u32(p, mems[3 * i + 1] + 1);
             *p++ = '\t';
             p = put_u32(p, ln);
+            if (extra) { *p++ = '\t'; p = put_u32(p, extra[i]); }
             *p++ = '\n';
             sum += ln;
         }
@@ -877,7 +914,7 @@ int slh_format_block(slh_buffer *buf, const char *query_name, int reverse, const
         int id = slh_seq_id_from_merged_pos(merged_start, num_refs, &rp);
         const char *rname = refs[id].name;
         size_t namelen = strlen(rname);
-        if (buf_reserve(buf, namelen + 48)) return -1;
+        if (buf_reserve(buf, namelen + 60)) return -1;
         p = buf->data + buf->len;
         *p++ = ' ';
         memcpy(p, rname, namelen);
@@ -888,6 +925,7 @@ int slh_format_block(slh_buffer *buf, const char *query_name, int reverse, const
         p = put_u32(p, qp + 1);
         *p++ = '\t';
         p = put_u32(p, ln);
+        if (extra) { *p++ = '\t'; p = put_u32(p, extra[i]); }
         *p++ = '\n';
         buf->len = (size_t)(p - buf->data);
         sum += ln;

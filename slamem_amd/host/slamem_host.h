@@ -69,7 +69,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), -1 two of them */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), -1 two of them */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
@@ -86,6 +86,10 @@ int slh_parse_argument(int argc, char **argv, const char *optionchars, int parse
 int slh_parse_max_occ(int argc, char **argv, int *out);
 /* -mgap N (-mg...): the maximum gap of -chain, with the same results for an integer N in [1, 2^31). */
 int slh_parse_max_gap(int argc, char **argv, int *out);
+/* -pen N (-pe...) and -xdrop N (-xd...): the mismatch penalty (N >= 1) and the X-drop (N >= 0) of -ext.  0 when neither is there
+ * (*penalty_out = 0, *xdrop_out = -1: the defaults), 1 when at least one is, -1 when a value is missing, not an integer or out
+ * of range.  Their values are never taken for file names. */
+int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out);
 /* AppendToBasename (tools.c:65-79): everything before the last '.' of the whole path + extra */
 char *slh_append_to_basename(const char *filename, const char *extra);
 
@@ -98,6 +102,11 @@ typedef struct {
 } slh_buffer;
 int slh_format_block(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *mems, uint64_t count,
                      const slh_record *refs, const uint32_t *merged_start, int num_refs, uint64_t *sum_len_out);
+/* The same with a fourth column (-ext: the mismatches of each row): extra[i] is printed behind the length of row i, as it
+ * is; extra == NULL: slh_format_block. */
+int slh_format_block_ext(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *mems, const uint32_t *extra,
+                         uint64_t count, const slh_record *refs, const uint32_t *merged_start, int num_refs,
+                         uint64_t *sum_len_out);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
