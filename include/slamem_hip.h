@@ -52,6 +52,16 @@ typedef struct {
     uint32_t length;
 } slamem_mem;
 
+/* One segment of a gapped alignment (option -aln): ref_len letters of the text from ref_pos against query_len
+ * letters of the scanned strand from query_pos, with `edits` letters under X, I and D of its CIGAR. */
+typedef struct {
+    uint32_t ref_pos;
+    uint32_t query_pos;
+    uint32_t ref_len;
+    uint32_t query_len;
+    uint32_t edits;
+} slamem_aln;
+
 typedef struct {
     uint32_t text_length;  /* n                                           */
     uint32_t bwt_size;     /* n + 1            == FMI_GetBWTSize(), bwtindex.c:263 */
@@ -99,7 +109,7 @@ typedef struct {
     double prefilter_ms_sum;
     double k8_ms_sum;
     float seed_ms;            /* K8s k_seed_mems (seed-and-compare for reads; runs in K8a's place), part of search_kernel_ms (ABI 4) */
-    float mum_filter_ms;      /* -mum / -smem / -chain / -ext: the filter behind K9 (mum_filter.hip, smem_filter.hip, chain_filter.hip, ext_filter.hip), large blocks included; 0 for -mem and -mam */
+    float mum_filter_ms;      /* -mum / -smem / -chain / -ext / -aln: the filter behind K9 (mum_filter.hip, smem_filter.hip, chain_filter.hip, ext_filter.hip, aln_filter.hip), large blocks included; 0 for -mem and -mam */
     double seed_ms_sum;
 } slamem_timings;
 
@@ -377,6 +387,29 @@ int slamem_find_exts_device(const slamem_index *idx, const void *queries_dev, co
                             uint64_t *block_offsets_dev, uint32_t *mismatches_dev /* may be NULL */, void *workspace_dev,
                             uint64_t workspace_bytes, void *stream, uint64_t *total_out);
 
+/* The same batch in alignment mode (option -aln: matchType 6): per strand block the gapped alignment built on the
+ * block's best chain (max_gap as for slamem_find_chains_device).  Consecutive chain rows are joined when the letters between
+ * them are A,C,G,T only and their unit-cost edit distance is at most max_edits (option -maxed; SLAMEM_ALN_EDITS_DEFAULT: the
+ * default 31; at most 127); a gap that does not close ends a segment.  The block's two outer ends are extended by the X-drop
+ * rule of slamem_find_exts_device (mismatch_penalty, xdrop).  segs_dev takes the segments, blocks in the order of -mem, the
+ * segments of a block with the query start descending; block_offsets_dev (num_blocks + 1) their offsets per strand block;
+ * ops_dev the CIGAR operations of all segments, `length << 4 | op` with BAM's codes (= 7, X 8, I 1, D 2), left to right in the
+ * scanned strand; op_offsets_dev (segs_capacity + 1) where each segment's operations start.  mems_capacity is the room for the
+ * batch's -mem list, which stays in the workspace.  totals_out[0..2] = -mem rows, segments, operations.  A capacity that is too
+ * small gives SLAMEM_ERR_CAPACITY with totals_out holding what a retry needs (after a -mem list that did not fit, [1] and [2]
+ * are 0: not known yet).  One host round trip per batch; a block out of the emission order and an index without text planes
+ * are refused with SLAMEM_ERR_ARG as for -ext.  The workspace is slamem_find_alns_workspace_bytes() bytes. */
+#define SLAMEM_ALN_EDITS_DEFAULT 0xFFFFFFFFu
+#define SLAMEM_ALN_EDITS_MAX 127u
+int slamem_find_alns_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                     uint64_t ops_capacity, uint32_t max_edits, uint64_t *bytes_out);
+int slamem_find_alns_device(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,
+                            uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap,
+                            uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity,
+                            slamem_aln *segs_dev, uint64_t segs_capacity, uint64_t *block_offsets_dev, uint32_t *ops_dev,
+                            uint64_t ops_capacity, uint64_t *op_offsets_dev, void *workspace_dev, uint64_t workspace_bytes,
+                            void *stream, uint64_t *totals_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -402,6 +435,12 @@ int slamem_find_exts_host(const slamem_index *idx, const char *queries, const ui
                           uint32_t num_queries, uint32_t min_len, int both_strands, uint32_t mismatch_penalty, uint32_t xdrop,
                           slamem_mem **mems_out, uint64_t **block_offsets_out, uint32_t **mismatches_out,
                           uint64_t *total_out);
+/* (four malloc()ed arrays: segments, num_blocks + 1 block offsets, operations, segments + 1 operation offsets;
+ * totals_out[0..2] as for slamem_find_alns_device) */
+int slamem_find_alns_host(const slamem_index *idx, const char *queries, const uint64_t *offsets, uint32_t num_queries,
+                          uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
+                          uint32_t max_edits, slamem_aln **segs_out, uint64_t **block_offsets_out, uint32_t **ops_out,
+                          uint64_t **op_offsets_out, uint64_t *totals_out);
 void slamem_host_free(void *p);
 
 /* ---- (b') MEM retrieval, host to host, pipelined -------------------------------
@@ -415,7 +454,9 @@ void slamem_host_free(void *p);
  *                          grow); match_type 0 = MEM, 1 = MAM (-mam), 2 = MUM (-mum:
  *                          only the kept rows come back), 3 = SMEM (-smem: likewise), 4 = chain (-chain: likewise; rows
  *                          and offsets, no scores), 5 = extension (-ext: the extended rows; their mismatches through
- *                          slamem_stream_mismatches)
+ *                          slamem_stream_mismatches), 6 = alignment (-aln: slamem_stream_next gives the block offsets and, as
+ *                          its total, the number of segments -- its rows pointer is not to be read; the segments, operations
+ *                          and operation offsets come through slamem_stream_alns)
  *   slamem_stream_set_max_occ  -smem: the occurrence cap of every batch (0: none, the default); before the first submit
  *                          (SLAMEM_ERR_ARG after it, or with a cap on a stream of another match type)
  *   slamem_stream_set_max_gap  -chain: the maximum gap of every batch (0: the default 5000); before the first submit
@@ -425,6 +466,11 @@ void slamem_host_free(void *p);
  *                          defaults' placeholders on a stream of another match type)
  *   slamem_stream_mismatches  -ext: the mismatches (a uint32 per row) of the batch slamem_stream_next returned last, in the
  *                          stream's pinned memory; valid as long as that batch's rows.  The same for submit and submit_packed.
+ *   slamem_stream_set_max_edits  -aln: the most edits in one gap of every batch (SLAMEM_ALN_EDITS_DEFAULT: the default 31; at
+ *                          most 127); before the first submit.  A stream of match type 6 also takes slamem_stream_set_max_gap
+ *                          and slamem_stream_set_ext_params, for its chain and its outer ends.
+ *   slamem_stream_alns     -aln: segments, operations, operation offsets (segments + 1) and the number of operations of the
+ *                          batch slamem_stream_next returned last, in the stream's pinned memory; valid as long as that batch.
  *   slamem_stream_submit   record i of the batch is queries[offsets[i] .. offsets[i+1]) -- offsets[0] need not be 0, so
  *                          a front end passes its whole character buffer and a window of its offsets array.  Returns at
  *                          once; the characters and offsets must stay unchanged until the batch has been collected.
@@ -446,6 +492,9 @@ int slamem_stream_set_max_occ(slamem_stream *s, uint32_t max_occ);
 int slamem_stream_set_max_gap(slamem_stream *s, uint32_t max_gap);
 int slamem_stream_set_ext_params(slamem_stream *s, uint32_t mismatch_penalty, uint32_t xdrop);
 int slamem_stream_mismatches(slamem_stream *s, const uint32_t **out);
+int slamem_stream_set_max_edits(slamem_stream *s, uint32_t max_edits);
+int slamem_stream_alns(slamem_stream *s, const slamem_aln **segs_out, const uint32_t **ops_out, const uint64_t **op_offsets_out,
+                       uint64_t *num_ops_out);
 int slamem_stream_submit(slamem_stream *s, const char *queries, const uint64_t *offsets, uint32_t num_queries,
                          uint32_t min_len);
 /* The same for reads the caller holds PACKED (ABI 4; no reference counterpart: the reference reads letters, sequence.c:89-270).

@@ -1,0 +1,594 @@
+// aln_filter.hip -- -aln (matchType 6): per strand block the gapped alignment built on the block's best chain, as segments with
+// an edit count and a CIGAR.  DESIGN.md 4.14 has the definition; in short: the rows of the best chain (4.12) are the anchors, a
+// row that overlaps its predecessor is trimmed at its start, the letters between two consecutive anchors (a of the strand, b of
+// the text) are aligned with unit costs, a gap closes iff both pieces are A,C,G,T only and the distance is at most E (-maxed),
+// a maximal run of anchors joined by closed gaps is a segment, and the block's two outer ends are extended by 4.13's X-drop rule.
+//
+// All on the stream behind K9, no host read-back:
+//   chain_filter            the chain's rows, compacted per block (chain_filter.hip, as it stands)
+//   pack_batch_planes       the batch's letters as planes (filter_shared.h)
+//   k_aln_geom              a lane per chain row: its block (binary search in the offsets), the trimming, the gap to its
+//                           predecessor, the outer ends (walk), the runs of what it decides itself.  A gap with a == b <= 64 and
+//                           at most two differing letters is decided here (distance = those letters); any other gap with
+//                           |a - b| <= E goes to a list (one atomic each)
+//   k_aln_wave              a wave per listed gap (a fixed grid of one-wave workgroups loops over the list): furthest-reaching
+//                           points f[s][k] per edit count s and diagonal k = y - x, lanes hold the diagonals, the previous
+//                           wavefront in LDS, every wavefront in the workgroup's slab for the traceback; the slide is the
+//                           64-letter XOR compare.  The traceback needs f only: D[x][y] is the first s with f[s][k] >= x.
+//   k_aln_count / 3 scans   runs, edits and segment starts per row -> places
+//   k_aln_segs / k_aln_write  block offsets, segment starts; a lane per row writes its runs (merged with the neighbours'), the
+//                           segment's rightmost row writes the segment
+#include "filter_shared.h"
+
+namespace slamem {
+
+namespace {
+
+// One-wave workgroups that share the list of gaps.  A wave spends its time waiting for the next window, so the more the chip
+// holds the better: up to 8,192 (32 a CU), fewer when the edit limit makes a workgroup's wavefront slab large -- the slabs of a
+// call together stay within 64 MiB (8,192 workgroups at the default 31 edits, 514 at 127).
+inline unsigned aln_wave_grid(uint32_t max_edits) {
+    const uint64_t slab = (uint64_t)(max_edits + 1) * (2 * max_edits + 1) * 4, fit = (64ull << 20) / slab;
+    return (unsigned)(fit > 8192 ? 8192 : fit < 256 ? 256 : fit);
+}
+constexpr uint32_t kOpEq = 7u, kOpX = 8u, kOpI = 1u, kOpD = 2u;  // BAM's codes
+constexpr uint32_t kFirst = 1u, kLast = 2u, kClosed = 4u, kListed = 8u, kGapEq = 16u, kRev = 32u;
+constexpr int32_t kNeg = -1;
+
+// a chain row: the trimmed anchor, the gap to its predecessor (in front of it in the strand), its outer ends
+struct AlnRow {
+    uint32_t tp, tq, tl;    // the anchor as used
+    uint32_t a, b;          // letters of the strand / of the text between the predecessor's end and the anchor
+    uint32_t extl, extr;    // outer ends (the block's first / last chain row only)
+    uint32_t flags;         // kFirst: first of its block in the list (the chain's LAST row); kLast: the chain's first row
+    uint32_t nfix;          // runs of the outer ends
+    uint32_t edits;         // mismatches of the outer ends
+    uint32_t gapn, gapd;    // a closed gap's runs and distance
+    uint32_t slab;          // a listed gap's runs: where in the slab
+    uint32_t rec;           // the record of the batch
+};
+
+struct AlnLayout {
+    uint64_t chain_bytes, off_ctr, off_crows, off_coff, off_ucnt, off_uoff, off_uscan, uscan_bytes, off_long, off_units, off_rows,
+        off_list, off_n, off_flag, off_ed, off_sn, off_sflag, off_sed, off_scan, scan_bytes, off_segstart, off_slab, off_f, bytes;
+};
+
+AlnLayout aln_layout(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
+                     uint32_t max_edits) {
+    AlnLayout m;
+    m.chain_bytes = align_up(chain_workspace_bytes(num_blocks, capacity), 256);  // (the -mem list K9 places lies in here)
+    uint64_t off = m.chain_bytes;
+    m.off_ctr = off;    off = align_up(off + 64, 256);                                  // [2] listed records, [3] listed gaps, [4] slab words
+    m.off_crows = off;  off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);  // the chains' rows
+    m.off_coff = off;   off = align_up(off + (num_blocks + 1) * 8, 256);                // ... and their block offsets
+    m.off_ucnt = off;   off = align_up(off + (num_queries + 1) * 4, 256);
+    m.off_uoff = off;   off = align_up(off + (num_queries + 1) * 8, 256);
+    size_t need = 0;
+    (void)scan_sum_exclusive_u32_u64(nullptr, need, nullptr, nullptr, num_queries, 0);
+    m.uscan_bytes = need;
+    m.off_uscan = off;  off = align_up(off + need, 256);
+    m.off_long = off;   off = align_up(off + (query_bytes / (64ull * kExtPackLaneUnits) + 1) * 8, 256);
+    m.off_units = off;  off = align_up(off + (query_bytes / 64 + num_queries + 1) * sizeof(QueryUnit), 256);
+    m.off_rows = off;   off = align_up(off + (capacity + 1) * sizeof(AlnRow), 256);
+    m.off_list = off;   off = align_up(off + (capacity + 1) * 4, 256);                  // listed gaps (their rows)
+    m.off_n = off;      off = align_up(off + (capacity + 2) * 4, 256);                  // runs per row
+    m.off_flag = off;   off = align_up(off + (capacity + 2) * 4, 256);                  // 1: the row is the rightmost of a segment
+    m.off_ed = off;     off = align_up(off + (capacity + 2) * 4, 256);                  // edits per row
+    m.off_sn = off;     off = align_up(off + (capacity + 2) * 8, 256);                  // their exclusive sums
+    m.off_sflag = off;  off = align_up(off + (capacity + 2) * 8, 256);
+    m.off_sed = off;    off = align_up(off + (capacity + 2) * 8, 256);
+    need = 0;
+    (void)scan_sum_exclusive_u32_u64(nullptr, need, nullptr, nullptr, capacity + 1, 0);
+    m.scan_bytes = need;
+    m.off_scan = off;   off = align_up(off + need, 256);
+    m.off_segstart = off; off = align_up(off + (capacity + 2) * 4, 256);                // the rightmost row of every segment
+    m.off_slab = off;   off = align_up(off + (ops_capacity + 1) * 4, 256);              // the runs of listed gaps
+    m.off_f = off;      off = align_up(off + (uint64_t)aln_wave_grid(max_edits) * (max_edits + 1) * (2 * max_edits + 1) * 4, 256);  // wavefronts
+    m.bytes = off;
+    return m;
+}
+
+// what a lane knows of its block's sequences
+struct Seqs {
+    const uint4* Q;
+    const uint4* T;
+    int64_t qn, tn, len, n;
+    bool rev;
+};
+
+__device__ __forceinline__ Seqs seqs_of(uint64_t rec, bool rev, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ uoff,
+                                        const QueryUnit* __restrict__ units, const TextPlanes* __restrict__ tpl, uint32_t n) {
+    Seqs s;
+    s.len = (int64_t)(offsets[rec + 1] - offsets[rec]);
+    s.qn = (s.len + 63) >> 6;
+    s.n = (int64_t)n;
+    s.tn = (s.n + 63) >> 6;
+    s.Q = reinterpret_cast<const uint4*>(units + uoff[rec]);
+    s.T = reinterpret_cast<const uint4*>(tpl);
+    s.rev = rev;
+    return s;
+}
+
+__device__ __forceinline__ uint64_t low_mask(int64_t k) { return k >= 64 ? ~0ull : (k <= 0 ? 0ull : (1ull << k) - 1ull); }
+
+// runs of one operation, merged as they come; counts them, and writes them when asked to
+struct Emit {
+    uint32_t* out;
+    uint64_t pos, cap;
+    uint32_t code, len, n;
+    bool write;
+    __device__ __forceinline__ void flush() {
+        if (len) {
+            if (write && pos < cap) out[pos] = (len << 4) | code;
+            pos++;
+            n++;
+        }
+        len = 0;
+        code = 0;
+    }
+    __device__ __forceinline__ void push(uint32_t c, uint32_t l) {
+        if (!l) return;
+        if (c != code) { flush(); code = c; }
+        len += l;
+    }
+};
+
+// the `=` / `X` runs of L letters of one diagonal, left to right (every letter inside both sequences and one of A,C,G,T)
+__device__ __forceinline__ void diag_runs(const Seqs& s, int64_t q0, int64_t p0, int64_t L, Emit& em) {
+    for (int64_t off = 0; off < L; off += 64) {
+        const Win q = strand_window(s.Q, s.qn, s.len, s.rev, q0 + off), t = window(s.T, s.tn, s.n, p0 + off);
+        const uint64_t m = (q.p0 ^ t.p0) | (q.p1 ^ t.p1);
+        const uint32_t v = L - off < 64 ? (uint32_t)(L - off) : 64u;
+        for (uint32_t i = 0; i < v;) {
+            const uint64_t rest = m >> i;
+            const bool mis = (rest & 1ull) != 0ull;
+            const uint64_t x = mis ? ~rest : rest;
+            uint32_t run = x ? (uint32_t)__builtin_ctzll(x) : 64u;
+            if (run > v - i) run = v - i;
+            em.push(mis ? kOpX : kOpEq, run);
+            i += run;
+        }
+    }
+}
+
+// ---- a lane per chain row ----------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(256) k_aln_geom(const uint64_t* __restrict__ coff, uint64_t nb, const slamem_mem* __restrict__ crows,
+                                                  uint64_t cap, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ uoff,
+                                                  const QueryUnit* __restrict__ units, const TextPlanes* __restrict__ tpl, uint32_t n,
+                                                  uint32_t strands, uint32_t penalty, uint32_t xdrop, uint32_t max_edits,
+                                                  AlnRow* __restrict__ rows, uint32_t* __restrict__ list, unsigned long long* __restrict__ ctr) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint64_t K = coff[nb];
+    if (K > cap) K = cap;
+    if (g >= K) return;
+    uint64_t lo = 0, hi = nb;  // the smallest block whose end lies behind g
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (coff[mid + 1] <= g) lo = mid + 1; else hi = mid;
+    }
+    const uint64_t blk = lo < nb ? lo : nb - 1u;
+    uint64_t s = coff[blk], e = coff[blk + 1];
+    if (e > K) e = K;
+    if (s > g) s = g;
+    const uint64_t rec = blk / strands;
+    const bool rev = (blk % strands) != 0u;
+    const Seqs sq = seqs_of(rec, rev, offsets, uoff, units, tpl, n);
+    const slamem_mem ri = crows[g];
+    const bool has_gap = g + 1u < e;
+    const slamem_mem rj = crows[has_gap ? g + 1u : g];
+    const int64_t p = ri.ref_pos, q = ri.query_pos, L = ri.length;
+    const int64_t eqj = (int64_t)rj.query_pos + rj.length, epj = (int64_t)rj.ref_pos + rj.length;
+    int64_t o = 0;
+    if (has_gap) {
+        if (eqj - q > o) o = eqj - q;
+        if (epj - p > o) o = epj - p;
+        if (o >= L) o = L - 1;  // (never for rows that may follow one another)
+    }
+    AlnRow r;
+    r.tp = (uint32_t)(p + o);
+    r.tq = (uint32_t)(q + o);
+    r.tl = (uint32_t)(L - o);
+    r.flags = (g == s ? kFirst : 0u) | (g + 1u == e ? kLast : 0u) | (rev ? kRev : 0u);
+    r.extl = r.extr = r.nfix = r.edits = r.gapn = r.gapd = r.slab = 0u;
+    r.rec = (uint32_t)rec;
+    const int64_t a = has_gap ? q + o - eqj : 0, b = has_gap ? p + o - epj : 0;
+    r.a = (uint32_t)a;
+    r.b = (uint32_t)b;
+    const bool inside = sq.qn > 0 && q + L <= sq.len && p + L <= sq.n && L > 0;  // (a row outside its sequences: nothing is read)
+    const int64_t E = max_edits;
+    if (has_gap && inside && a >= 0 && b >= 0 && (a > b ? a - b : b - a) <= E) {
+        if (a == 0 && b == 0) {
+            r.flags |= kClosed;
+        } else if (a == b && a <= 64) {
+            const Win wq = strand_window(sq.Q, sq.qn, sq.len, rev, eqj), wt = window(sq.T, sq.tn, sq.n, epj);
+            const uint64_t mk = low_mask(a);
+            const uint64_t bad = (wq.bad | wt.bad) & mk;
+            const uint64_t m = ((wq.p0 ^ wt.p0) | (wq.p1 ^ wt.p1)) & mk;
+            const uint32_t d = (uint32_t)__popcll(m);
+            // Up to two differing letters on the diagonal: D = d, and the traceback stays on the diagonal.  Pieces of one length
+            // cannot be one indel apart, so their distance is 0 (equal), 1 (one substitution, d = 1) or at least 2; with d <= 2
+            // substitutions reach it, hence D = d.  The same holds for every pair of prefixes of one length (they have at most d
+            // differing letters too), so D[x][x] = the differing letters in front of x, and the rule's diagonal step applies
+            // at every cell of the diagonal.  (Three differing letters may cost 2: an inserted and a deleted letter.)
+            if (!bad && d <= 2u) {
+                if ((int64_t)d <= E) {
+                    // runs of the mask: one per maximal stretch of equal bits
+                    const uint64_t tr = (m ^ (m >> 1)) & low_mask(a - 1);
+                    r.gapn = (uint32_t)__popcll(tr) + 1u;
+                    r.gapd = d;
+                    r.flags |= kClosed | (((m >> (a - 1)) & 1ull) ? 0u : kGapEq);
+                }
+            } else if (!bad) {
+                r.flags |= kListed;
+            }
+        } else {
+            r.flags |= kListed;
+        }
+        if (r.flags & kListed) list[atomicAdd(&ctr[3], 1ull)] = (uint32_t)g;
+    }
+    if (inside && (r.flags & (kFirst | kLast))) {
+        const int64_t P = penalty, X = xdrop;
+        Emit em = {nullptr, 0, 0, 0, 0, 0, false};
+        if (r.flags & kLast) {  // (the chain's first row is not trimmed)
+            Side left = {0, 0, 0, 0, 0, 0};
+            Win ql = mirrored(strand_window(sq.Q, sq.qn, sq.len, rev, q - 64)), tl = mirrored(window(sq.T, sq.tn, sq.n, p - 64));
+            for (uint64_t t0 = 0; !walk(left, ql, tl, t0, P, X);) {
+                t0 += 64u;
+                ql = mirrored(strand_window(sq.Q, sq.qn, sq.len, rev, q - 64 - (int64_t)t0));
+                tl = mirrored(window(sq.T, sq.tn, sq.n, p - 64 - (int64_t)t0));
+            }
+            r.extl = (uint32_t)left.ext;
+            r.edits += left.mm_best;
+            diag_runs(sq, q - (int64_t)left.ext, p - (int64_t)left.ext, (int64_t)left.ext, em);
+            em.flush();
+        }
+        if (r.flags & kFirst) {
+            Side right = {0, 0, 0, 0, 0, 0};
+            Win qr = strand_window(sq.Q, sq.qn, sq.len, rev, q + L), tr = window(sq.T, sq.tn, sq.n, p + L);
+            for (uint64_t t0 = 0; !walk(right, qr, tr, t0, P, X);) {
+                t0 += 64u;
+                qr = strand_window(sq.Q, sq.qn, sq.len, rev, q + L + (int64_t)t0);
+                tr = window(sq.T, sq.tn, sq.n, p + L + (int64_t)t0);
+            }
+            r.extr = (uint32_t)right.ext;
+            r.edits += right.mm_best;
+            diag_runs(sq, q + L, p + L, (int64_t)right.ext, em);
+            em.flush();
+        }
+        r.nfix = em.n;
+    }
+    rows[g] = r;
+}
+
+// ---- a wave per listed gap -------------------------------------------------------------------------------------------------
+
+// matching letters from (x, y) of the gap on, at most lim
+__device__ __forceinline__ int64_t slide_fwd(const Seqs& s, int64_t qa, int64_t pb, int64_t x, int64_t y, int64_t lim) {
+    int64_t done = 0;
+    while (done < lim) {
+        const Win q = strand_window(s.Q, s.qn, s.len, s.rev, qa + x + done), t = window(s.T, s.tn, s.n, pb + y + done);
+        const uint64_t m = (q.p0 ^ t.p0) | (q.p1 ^ t.p1);
+        const int64_t l = lim - done < 64 ? lim - done : 64;
+        int64_t run = m ? (int64_t)__builtin_ctzll(m) : 64;
+        if (run > l) run = l;
+        done += run;
+        if (run < 64) break;
+    }
+    return done;
+}
+
+// matching letters in front of (x, y), at most lim
+__device__ __forceinline__ int64_t slide_back(const Seqs& s, int64_t qa, int64_t pb, int64_t x, int64_t y, int64_t lim) {
+    int64_t done = 0;
+    while (done < lim) {
+        const Win q = mirrored(strand_window(s.Q, s.qn, s.len, s.rev, qa + x - done - 64));
+        const Win t = mirrored(window(s.T, s.tn, s.n, pb + y - done - 64));
+        const uint64_t m = (q.p0 ^ t.p0) | (q.p1 ^ t.p1);
+        const int64_t l = lim - done < 64 ? lim - done : 64;
+        int64_t run = m ? (int64_t)__builtin_ctzll(m) : 64;
+        if (run > l) run = l;
+        done += run;
+        if (run < 64) break;
+    }
+    return done;
+}
+
+__global__ void __launch_bounds__(64) k_aln_wave(const uint32_t* __restrict__ list, const unsigned long long* __restrict__ ctr_in,
+                                                 AlnRow* rows, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ uoff,
+                                                 const QueryUnit* __restrict__ units, const TextPlanes* __restrict__ tpl, uint32_t n,
+                                                 uint32_t max_edits, int32_t* fslab, uint32_t* __restrict__ slab, uint64_t slab_cap,
+                                                 unsigned long long* __restrict__ ctr) {
+    __shared__ int32_t wf[2][256];    // the last two wavefronts, by diagonal + E
+    __shared__ uint32_t rbuf[256];    // the traceback's runs, last first
+    __shared__ unsigned long long s_off;
+    const uint32_t lane = threadIdx.x;
+    const int32_t E = (int32_t)max_edits, W = 2 * E + 1;
+    int32_t* F = fslab + (uint64_t)blockIdx.x * (uint64_t)(E + 1) * (uint64_t)W;
+    const uint64_t nl = ctr_in[3];
+    for (uint64_t li = blockIdx.x; li < nl; li += gridDim.x) {
+        const uint32_t g = list[li];
+        const AlnRow r = rows[g];
+        const Seqs sq = seqs_of(r.rec, (r.flags & kRev) != 0u, offsets, uoff, units, tpl, n);
+        const int64_t a = r.a, b = r.b;
+        const int64_t qa = (int64_t)r.tq - a, pb = (int64_t)r.tp - b;
+        // a letter that is not A,C,G,T in either piece breaks the gap
+        bool bad = false;
+        for (int64_t w = lane; w * 64 < a; w += 64) {
+            const Win q = strand_window(sq.Q, sq.qn, sq.len, sq.rev, qa + 64 * w);
+            if (q.bad & low_mask(a - 64 * w)) bad = true;
+        }
+        for (int64_t w = lane; w * 64 < b; w += 64) {
+            const Win t = window(sq.T, sq.tn, sq.n, pb + 64 * w);
+            if (t.bad & low_mask(b - 64 * w)) bad = true;
+        }
+        __syncthreads();  // (nobody reads the last gap's LDS any more)
+        for (uint32_t d = lane; d < 256u; d += 64u) { wf[0][d] = kNeg; wf[1][d] = kNeg; }
+        if (__syncthreads_or(bad ? 1 : 0)) continue;
+        const int32_t kfin = (int32_t)(b - a);
+        int32_t s = 0;
+        bool closed = false;
+        for (;; s++) {
+            const int32_t* prev = wf[(s + 1) & 1];
+            int32_t* cur = wf[s & 1];
+            bool fin = false;
+            for (int32_t d = E - s + (int32_t)lane; d <= E + s; d += 64) {
+                const int64_t k = d - E;
+                int64_t c = kNeg;
+                if (s == 0) {
+                    c = 0;
+                } else {
+                    const int64_t fk = prev[d], fl = d > 0 ? prev[d - 1] : kNeg, fr = d + 1 < W ? prev[d + 1] : kNeg;
+                    if (fk >= 0) {  // one more letter of both, or none at an end
+                        c = fk + 1;
+                        if (c > a) c = a;
+                        if (c > b - k) c = b - k;
+                    }
+                    if (fl >= 0) {  // a text letter: from diagonal k - 1, x stays
+                        int64_t v = fl < b - k ? fl : b - k;
+                        const int64_t least = 1 - k > 0 ? 1 - k : 0;
+                        if (v >= least && v > c) c = v;
+                    }
+                    if (fr >= 0) {  // a strand letter: from diagonal k + 1, x + 1
+                        int64_t v = fr + 1 < a ? fr + 1 : a;
+                        const int64_t least = -k - 1 > 0 ? -k - 1 : 0;
+                        if (v - 1 >= least && v > c) c = v;
+                    }
+                }
+                if (c >= 0) {
+                    const int64_t lim = a - c < b - (c + k) ? a - c : b - (c + k);
+                    if (lim > 0) c += slide_fwd(sq, qa, pb, c, c + k, lim);
+                }
+                cur[d] = (int32_t)c;
+                F[(int64_t)s * W + d] = (int32_t)c;
+                if (d == kfin + E && c >= a) fin = true;
+            }
+            if (__syncthreads_or(fin ? 1 : 0)) { closed = true; break; }
+            if (s == E) break;
+        }
+        if (!closed) continue;
+        // The traceback: D[x][y] is the first s with f[s][y - x] >= x.  Every lane runs it on the same values (a, b, the planes
+        // and F are the same for all), so the lanes stay converged, their loads are one request, and the words they store to
+        // rbuf[] are identical by construction.  F[] was written by other lanes through global memory: the __syncthreads_or that
+        // ended the wavefront loop is the barrier (and the wait for the stores) that makes those words visible here.
+        // Runs: every run but those of `=` holds an edit and two runs of `=` have one between them, so at most 2 s + 1 <= 255.
+        bool overrun = false;
+        int64_t x = a, y = b;
+        int32_t d = s;
+        uint32_t nr = 0, code = 0, len = 0;
+        while (x > 0 || y > 0) {
+            if (x > 0 && y > 0) {
+                const int64_t run = slide_back(sq, qa, pb, x, y, x < y ? x : y);
+                if (run) {
+                    if (code != kOpEq) { if (len) rbuf[nr++] = (len << 4) | code; code = kOpEq; len = 0; }
+                    len += (uint32_t)run;
+                    x -= run;
+                    y -= run;
+                }
+                if (x == 0 && y == 0) break;
+            }
+            const int32_t k = (int32_t)(y - x), sp = d - 1;
+            const int32_t f_same = (sp >= 0 && k >= -sp && k <= sp) ? F[(int64_t)sp * W + k + E] : kNeg;
+            const int32_t f_left = (sp >= 0 && k - 1 >= -sp && k - 1 <= sp) ? F[(int64_t)sp * W + k - 1 + E] : kNeg;
+            uint32_t op;
+            if (x > 0 && y > 0 && f_same >= 0 && (int64_t)f_same >= x - 1) { op = kOpX; x--; y--; }
+            else if (y > 0 && (x == 0 || (f_left >= 0 && (int64_t)f_left >= x))) { op = kOpD; y--; }
+            else { op = kOpI; x--; }  // (x > 0: with x == 0 there is y > 0, and the branch above was taken)
+            d--;
+            if (code != op) { if (len) rbuf[nr++] = (len << 4) | code; code = op; len = 0; }
+            len++;
+            if (nr >= 255u) { overrun = true; break; }  // (never, by the count above; if it were, the gap is left broken)
+        }
+        if (overrun) continue;  // (uniform)
+        if (len) rbuf[nr++] = (len << 4) | code;
+        if (lane == 0u) s_off = atomicAdd(&ctr[4], (unsigned long long)nr);
+        __syncthreads();
+        const uint64_t at = s_off;
+        if (at + nr <= slab_cap)
+            for (uint32_t t = lane; t < nr; t += 64u) slab[at + t] = rbuf[nr - 1u - t];
+        if (lane == 0u) {
+            AlnRow* o = rows + g;
+            o->gapn = nr;
+            o->gapd = (uint32_t)s;
+            o->slab = (uint32_t)(at < 0xFFFFFFFFull ? at : 0xFFFFFFFFull);
+            o->flags = r.flags | kClosed | ((nr && (rbuf[0] & 15u) == kOpEq) ? kGapEq : 0u);
+        }
+    }
+}
+
+// ---- places ------------------------------------------------------------------------------------------------------------------
+
+// a row's anchor goes into the run of the row to its left when its gap is closed and empty
+__device__ __forceinline__ bool joins_left(const AlnRow& r) { return (r.flags & kClosed) && r.gapn == 0u; }
+
+__global__ void __launch_bounds__(256) k_aln_count(const uint64_t* __restrict__ coff, uint64_t nb, uint64_t cap,
+                                                   const AlnRow* __restrict__ rows, uint32_t* __restrict__ nruns, uint32_t* __restrict__ flag,
+                                                   uint32_t* __restrict__ ed) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (g > cap + 1u) return;
+    uint64_t K = coff[nb];
+    if (K > cap) K = cap;
+    if (g >= K) { nruns[g] = 0u; flag[g] = 0u; ed[g] = 0u; return; }
+    const AlnRow r = rows[g];
+    const bool closed = (r.flags & kClosed) != 0u;
+    const bool own_anchor = !(closed && (r.gapn == 0u || (r.flags & kGapEq)));
+    nruns[g] = r.nfix + (closed ? r.gapn : 0u) + (own_anchor ? 1u : 0u);
+    ed[g] = r.edits + (closed ? r.gapd : 0u);
+    // the gap to the right of row g is row g - 1's
+    flag[g] = ((r.flags & kFirst) || !(rows[g - 1u].flags & kClosed)) ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(256) k_aln_segs(const uint64_t* __restrict__ coff, uint64_t nb, uint64_t cap,
+                                                  const uint32_t* __restrict__ flag, const uint64_t* __restrict__ sflag,
+                                                  const uint64_t* __restrict__ sn, uint32_t* __restrict__ segstart,
+                                                  uint64_t* __restrict__ out_boff, uint64_t* __restrict__ op_off, uint64_t seg_cap) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint64_t K = coff[nb];
+    if (K > cap) K = cap;
+    if (i <= nb) {
+        const uint64_t c = coff[i] < K ? coff[i] : K;
+        out_boff[i] = sflag[c];
+    }
+    if (i < K && flag[i]) segstart[sflag[i]] = (uint32_t)i;
+    if (i == K) {
+        const uint64_t nseg = sflag[K];
+        segstart[nseg] = (uint32_t)K;
+        if (nseg <= seg_cap) op_off[nseg] = sn[K];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_aln_write(const uint64_t* __restrict__ coff, uint64_t nb, uint64_t cap,
+                                                   const AlnRow* __restrict__ rows, const uint64_t* __restrict__ offsets,
+                                                   const uint64_t* __restrict__ uoff, const QueryUnit* __restrict__ units,
+                                                   const TextPlanes* __restrict__ tpl, uint32_t n, const uint64_t* __restrict__ sflag,
+                                                   const uint64_t* __restrict__ sn, const uint64_t* __restrict__ sed,
+                                                   const uint32_t* __restrict__ segstart, const uint32_t* __restrict__ slab,
+                                                   uint64_t slab_cap, slamem_aln* __restrict__ segs, uint64_t seg_cap,
+                                                   uint32_t* __restrict__ ops, uint64_t ops_cap, uint64_t* __restrict__ op_off) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint64_t K = coff[nb];
+    if (K > cap) K = cap;
+    if (g >= K) return;
+    const AlnRow r = rows[g];
+    const uint64_t sg = sflag[g + 1u] - 1u;
+    const uint64_t g0 = segstart[sg], g1p = segstart[sg + 1u];
+    const Seqs sq = seqs_of(r.rec, (r.flags & kRev) != 0u, offsets, uoff, units, tpl, n);
+    Emit em = {ops, sn[g0] + (sn[g1p] - sn[g + 1u]), ops_cap, 0, 0, 0, true};
+    if (!(joins_left(r) && g + 1u < g1p)) {
+        if ((r.flags & kLast) && r.extl) diag_runs(sq, (int64_t)r.tq - r.extl, (int64_t)r.tp - r.extl, r.extl, em);
+        if ((r.flags & kClosed) && r.gapn) {
+            if (r.flags & kListed) {
+                for (uint32_t k = 0; k < r.gapn; k++) {
+                    const uint64_t at = (uint64_t)r.slab + k;
+                    const uint32_t w = at < slab_cap ? slab[at] : 0u;
+                    em.push(w & 15u, w >> 4);
+                }
+            } else {
+                diag_runs(sq, (int64_t)r.tq - r.a, (int64_t)r.tp - r.b, r.a, em);
+            }
+        }
+        uint32_t len = r.tl;
+        for (uint64_t k = g; k > g0;) {  // anchors to the right that join this run (their gap is closed and empty)
+            k--;
+            const AlnRow rk = rows[k];
+            if (!joins_left(rk)) break;
+            len += rk.tl;
+        }
+        em.push(kOpEq, len);
+    }
+    if ((r.flags & kFirst) && r.extr) diag_runs(sq, (int64_t)r.tq + r.tl, (int64_t)r.tp + r.tl, r.extr, em);
+    em.flush();
+    if (g == g0 && sg < seg_cap) {
+        const AlnRow rl = rows[g1p - 1u];
+        slamem_aln o;
+        o.ref_pos = rl.tp - rl.extl;
+        o.query_pos = rl.tq - rl.extl;
+        o.ref_len = r.tp + r.tl + r.extr - o.ref_pos;
+        o.query_len = r.tq + r.tl + r.extr - o.query_pos;
+        o.edits = (uint32_t)(sed[g1p] - sed[g0]);
+        segs[sg] = o;
+        op_off[sg] = sn[g0];
+    }
+}
+
+}  // namespace
+
+uint64_t aln_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
+                             uint32_t max_edits) {
+    return aln_layout(num_queries, num_blocks, query_bytes, capacity, ops_capacity, max_edits).bytes;
+}
+
+void aln_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out) {
+    chain_list_buffers(ws, num_blocks, capacity, rows_out, boff_out);
+}
+
+#define ASTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
+
+int aln_filter(void* ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries, uint32_t strands,
+               uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff, unsigned long long* host_scalars,
+               hipStream_t stream) {
+    const uint64_t num_blocks = num_queries * strands;
+    const AlnLayout m = aln_layout(num_queries, num_blocks, query_bytes, capacity, args.ops_capacity, args.max_edits);
+    char* p = static_cast<char*>(ws);
+    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
+    slamem_mem* crows = reinterpret_cast<slamem_mem*>(p + m.off_crows);
+    uint64_t* coff = reinterpret_cast<uint64_t*>(p + m.off_coff);
+    uint32_t* ucnt = reinterpret_cast<uint32_t*>(p + m.off_ucnt);
+    uint64_t* uoff = reinterpret_cast<uint64_t*>(p + m.off_uoff);
+    uint64_t* longs = reinterpret_cast<uint64_t*>(p + m.off_long);
+    QueryUnit* units = reinterpret_cast<QueryUnit*>(p + m.off_units);
+    AlnRow* rows = reinterpret_cast<AlnRow*>(p + m.off_rows);
+    uint32_t* list = reinterpret_cast<uint32_t*>(p + m.off_list);
+    uint32_t* nruns = reinterpret_cast<uint32_t*>(p + m.off_n);
+    uint32_t* flag = reinterpret_cast<uint32_t*>(p + m.off_flag);
+    uint32_t* ed = reinterpret_cast<uint32_t*>(p + m.off_ed);
+    uint64_t* sn = reinterpret_cast<uint64_t*>(p + m.off_sn);
+    uint64_t* sflag = reinterpret_cast<uint64_t*>(p + m.off_sflag);
+    uint64_t* sed = reinterpret_cast<uint64_t*>(p + m.off_sed);
+    uint32_t* segstart = reinterpret_cast<uint32_t*>(p + m.off_segstart);
+    uint32_t* slab = reinterpret_cast<uint32_t*>(p + m.off_slab);
+    int32_t* fslab = reinterpret_cast<int32_t*>(p + m.off_f);
+    const char* queries = static_cast<const char*>(queries_dev);
+    // the chains: [0] rows kept (replaced below), [1] the first block out of order + 1
+    int rc = chain_filter(ws, num_blocks, capacity, args.max_gap, crows, coff, nullptr, host_scalars, stream);
+    if (rc != SLAMEM_OK) return rc;
+    ASTEP(hipMemsetAsync(ctr, 0, 64, stream), "memset");
+    ASTEP(pack_batch_planes(queries, offsets_dev, num_queries, ucnt, uoff, p + m.off_uscan, m.uscan_bytes, longs, units, ctr, stream),
+          "pack_batch_planes");
+    if (num_blocks) {
+        hipLaunchKernelGGL(k_aln_geom, dim3(grid_for(capacity)), dim3(256), 0, stream, (const uint64_t*)coff, num_blocks,
+                           (const slamem_mem*)crows, capacity, offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n,
+                           strands, args.penalty, args.xdrop, args.max_edits, rows, list, ctr);
+        ASTEP(hipGetLastError(), "k_aln_geom");
+        hipLaunchKernelGGL(k_aln_wave, dim3(aln_wave_grid(args.max_edits)), dim3(64), 0, stream, (const uint32_t*)list, (const unsigned long long*)ctr, rows,
+                           offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n, args.max_edits, fslab, slab,
+                           args.ops_capacity, ctr);
+        ASTEP(hipGetLastError(), "k_aln_wave");
+    }
+    hipLaunchKernelGGL(k_aln_count, dim3(grid_for(capacity + 2)), dim3(256), 0, stream, (const uint64_t*)coff, num_blocks, capacity,
+                       (const AlnRow*)rows, nruns, flag, ed);
+    ASTEP(hipGetLastError(), "k_aln_count");
+    size_t need = m.scan_bytes;
+    ASTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, nruns, sn, capacity + 1, stream), "scan");
+    need = m.scan_bytes;
+    ASTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, flag, sflag, capacity + 1, stream), "scan");
+    need = m.scan_bytes;
+    ASTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, ed, sed, capacity + 1, stream), "scan");
+    const uint64_t most = capacity > num_blocks ? capacity : num_blocks;
+    hipLaunchKernelGGL(k_aln_segs, dim3(grid_for(most + 1)), dim3(256), 0, stream, (const uint64_t*)coff, num_blocks, capacity,
+                       (const uint32_t*)flag, (const uint64_t*)sflag, (const uint64_t*)sn, segstart, out_boff, args.op_offsets,
+                       args.segs_capacity);
+    ASTEP(hipGetLastError(), "k_aln_segs");
+    hipLaunchKernelGGL(k_aln_write, dim3(grid_for(capacity)), dim3(256), 0, stream, (const uint64_t*)coff, num_blocks, capacity,
+                       (const AlnRow*)rows, offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n,
+                       (const uint64_t*)sflag, (const uint64_t*)sn, (const uint64_t*)sed, (const uint32_t*)segstart, (const uint32_t*)slab,
+                       args.ops_capacity, args.segs, args.segs_capacity, args.ops, args.ops_capacity, args.op_offsets);
+    ASTEP(hipGetLastError(), "k_aln_write");
+    // [0] segments, [1] (chain_filter's) the first block out of order + 1, [2] operations
+    ASTEP(hipMemcpyAsync(host_scalars, sflag + capacity + 1, 8, hipMemcpyDeviceToHost, stream), "memcpy");
+    ASTEP(hipMemcpyAsync(host_scalars + 2, sn + capacity + 1, 8, hipMemcpyDeviceToHost, stream), "memcpy");
+    return SLAMEM_OK;
+}
+#undef ASTEP
+
+}  // namespace slamem

@@ -301,11 +301,13 @@ namespace slamem {
 void make_view(slamem_index* idx);
 int build_index_device(const void* text_dev, uint32_t n, int device, hipStream_t stream, int layout, slamem_index** out);
 int estimate_build_bytes(uint32_t n, int layout, uint64_t* arena_bytes, uint64_t* peak_bytes);
+struct AlnArgs;
 int find_mems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
                      uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ = 0, uint32_t max_gap = 0,
-                     uint32_t* block_scores_dev = nullptr, uint32_t ext_penalty = 0, uint32_t ext_xdrop = 0xFFFFFFFFu);
+                     uint32_t* block_scores_dev = nullptr, uint32_t ext_penalty = 0, uint32_t ext_xdrop = 0xFFFFFFFFu,
+                     const AlnArgs* aln = nullptr, uint64_t* aln_totals = nullptr);
 uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity);
 // The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum, 3 -smem, 4 -chain, 5 -ext: the -mem workspace and the filter's behind it)
 uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type);
@@ -342,6 +344,25 @@ void ext_list_buffers(void* ext_ws, uint64_t num_queries, uint64_t num_blocks, u
 int ext_filter(void* ext_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
                uint32_t strands, uint64_t query_bytes, uint64_t capacity, uint32_t penalty, uint32_t xdrop, slamem_mem* out_mems,
                uint64_t* out_boff, uint32_t* out_mm, unsigned long long* host_scalars, hipStream_t stream);
+// -aln (aln_filter.hip): the chain's passes and -ext's planes, then the gaps between consecutive chain rows and the CIGARs.  The
+// workspace starts with -chain's (K9 places the -mem list there).  args: every value resolved (no placeholders); host_scalars:
+// [0] segments, [1] the first block out of order + 1, [2] operations.  In find_mems_device (match type 6) the arguments travel
+// in `aln`, mems_dev may be null, block_offsets_dev takes the segments' block offsets and aln_totals[0..2] the three totals.
+constexpr uint32_t kAlnDefaultEdits = 31, kAlnMaxEdits = 127, kAlnEditsUnset = 0xFFFFFFFFu;
+struct AlnArgs {
+    uint32_t max_gap, penalty, xdrop, max_edits;
+    slamem_aln* segs;
+    uint64_t segs_capacity;
+    uint32_t* ops;
+    uint64_t ops_capacity;
+    uint64_t* op_offsets;  // segs_capacity + 1
+};
+uint64_t aln_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
+                             uint32_t max_edits);
+void aln_list_buffers(void* aln_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
+int aln_filter(void* aln_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
+               uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff,
+               unsigned long long* host_scalars, hipStream_t stream);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).
@@ -365,6 +386,10 @@ void search_job_max_gap(SearchJob* j, uint32_t max_gap);
 // (between init and the search) -ext: the mismatch penalty (0: kExtDefaultPenalty), the drop (kExtXdropUnset: kExtDefaultXdrop)
 // and where the mismatches of the kept rows go (a uint32 per row of capacity, or nullptr)
 void search_job_ext(SearchJob* j, uint32_t penalty, uint32_t xdrop, uint32_t* mismatches_dev);
+// -aln: the arguments of the batch, every value resolved.  BEFORE search_job_init, unlike the others: init sizes the workspace
+// by the operation capacity and the edit limit.  After collect: [0] -mem rows, [1] segments, [2] operations (what a retry needs).
+void search_job_aln(SearchJob* j, const AlnArgs& args);
+void search_job_aln_totals(const SearchJob* j, uint64_t totals[3]);
 constexpr uint32_t kSearchSliceLen = 4096;
 int search_job_tables(SearchJob* j, hipStream_t stream);
 int search_job_prep(SearchJob* j, hipStream_t stream);

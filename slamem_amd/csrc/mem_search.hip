@@ -3567,6 +3567,11 @@ struct SearchJob {
     bool ext = false;
     uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;
     uint32_t* mism_dev = nullptr;
+    // -aln: as -ext, with aln_filter.hip behind K9; alnargs: where the segments and operations go, every value resolved (set
+    // before init, which sizes the workspace by it); h_scal [9] segments, [10] a block out of order + 1, [11] operations
+    bool aln = false;
+    AlnArgs alnargs = {0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr};
+    uint64_t aln_totals[3] = {0, 0, 0};
     unsigned long long scal_own[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t k8_wave_cap = 0;  // waves of this batch's K8 (0: as many as the chip holds); a pipeline that keeps two K8 launches in flight gives each a part of the chip
     uint32_t slices_hint = 0xFFFFFFFFu;  // a caller that has the offsets on the host and knows the slice count (no record longer than a slice: one per record) saves tables() its round trip
@@ -3608,8 +3613,8 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
     min_len = min_len_; both_strands = both_strands_; match_type = match_type_; mems_dev = mems_dev_; mems_capacity = mems_capacity_;
     block_offsets_dev = block_offsets_dev_; workspace_dev = workspace_dev_; workspace_bytes = workspace_bytes_;
     total = 0; nitems = 0; prefiltered = false; timed_k8 = false; launched = false;
-    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false; chain = false; ext = false;
-    if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity) || (!queries_dev && num_queries)) {
+    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false; chain = false; ext = false; aln = false;
+    if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity && match_type_ != 6) || (!queries_dev && num_queries)) {
         set_error("slamem_find_mems_device: null argument");
         return SLAMEM_ERR_ARG;
     }
@@ -3666,11 +3671,32 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         }
         ext = true;
         match_type = 0;
+    } else if (match_type == 6) {
+        // -aln: the -mem search, then the filter (aln_filter.hip), which compares the reads with the text planes of the index
+        if (idx->hdr.off_tpl == 0 || !idx->view.tpl) {
+            set_error("slamem_find_alns_device: -aln needs the text planes of the index, and this index has none (%s layout%s); "
+                      "build it in the full layout with the seed sections", idx->hdr.layout == 2u ? "compact" : "full",
+                      idx->hdr.layout == 2u ? "" : ", built without the seed sections");
+            return SLAMEM_ERR_ARG;
+        }
+        if (mems_capacity >= 0xFFFF0000ull || num_blocks >= 0xFFFFFFFFull || alnargs.ops_capacity >= 0xFFFF0000ull) {
+            set_error("slamem_find_alns_device: at most 2^32 - 2^16 MEMs and operations of capacity and 2^32 - 2 strand blocks per call");
+            return SLAMEM_ERR_ARG;
+        }
+        if (!alnargs.op_offsets || (!alnargs.segs && alnargs.segs_capacity) || (!alnargs.ops && alnargs.ops_capacity) ||
+            alnargs.max_edits > kAlnMaxEdits) {
+            set_error("slamem_find_alns_device: null argument, or more than %u edits a gap", kAlnMaxEdits);
+            return SLAMEM_ERR_ARG;
+        }
+        aln = true;
+        match_type = 0;
     }
     const uint64_t need_ws = mum ? w.bytes + mum_workspace_bytes(num_blocks, mems_capacity)
                                  : smem ? w.bytes + smem_workspace_bytes(num_blocks, mems_capacity)
                                  : chain ? w.bytes + chain_workspace_bytes(num_blocks, mems_capacity)
-                                 : ext ? w.bytes + ext_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity) : w.bytes;
+                                 : ext ? w.bytes + ext_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity)
+                                 : aln ? w.bytes + aln_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity,
+                                                                       alnargs.ops_capacity, alnargs.max_edits) : w.bytes;
     if (workspace_bytes < need_ws) {
         set_error("slamem_find_mems_device: workspace too small (%llu < %llu bytes)",
                   (unsigned long long)workspace_bytes, (unsigned long long)need_ws);
@@ -3696,11 +3722,16 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         out_boff = block_offsets_dev;
         mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
         ext_list_buffers(mum_ws, num_queries, num_blocks, query_bytes, mems_capacity, &mems_dev, &block_offsets_dev);
+    } else if (aln) {
+        out_mems = nullptr;
+        out_boff = block_offsets_dev;
+        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
+        aln_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
     }
     want_stats = search_stats_wanted();
     for (int i = 0; i < 6; i++)
         if (!ev[i]) SLAMEM_HIP(hipEventCreate(&ev[i]));
-    for (int i = 0; i < 2 && (mum || smem || chain || ext); i++)
+    for (int i = 0; i < 2 && (mum || smem || chain || ext || aln); i++)
         if (!ev_mum[i]) SLAMEM_HIP(hipEventCreate(&ev_mum[i]));
     return SLAMEM_OK;
 }
@@ -4241,6 +4272,12 @@ int SearchJob::place(hipStream_t stream) {
                             out_mems, out_boff, mism_dev, h_scal + 9, stream);
         if (rc != SLAMEM_OK) return rc;
         (void)hipEventRecord(ev_mum[1], stream);
+    } else if (aln) {  // -aln: likewise; three scalars
+        (void)hipEventRecord(ev_mum[0], stream);
+        int rc = aln_filter(mum_ws, idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity, alnargs,
+                            out_boff, h_scal + 9, stream);
+        if (rc != SLAMEM_OK) return rc;
+        (void)hipEventRecord(ev_mum[1], stream);
     }
     return SLAMEM_OK;
 }
@@ -4318,12 +4355,14 @@ int SearchJob::collect() {
         else { tm.t.prefilter_ms = ms; tm.t.prefilter_ms_sum += ms; tm.t.seed_ms = 0; }
     }
     if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) tm.t.search_total_ms = ms_prep + ms_k8 + ms;
+    aln_totals[0] = total; aln_totals[1] = 0; aln_totals[2] = 0;  // (-aln: what a retry needs; the last two once they are known)
     if (total > mems_capacity || listed > mems_capacity) {
         // the atomic list also holds the records of abandoned slice attempts: ask for room for those too
         if (listed > total) total = listed;
         // (kChunk: the waves reserve places in chunks and may leave some unused; WHICH waves do depends on the run, the bound
         //  covers every run, so that a caller who asks again with this much room succeeds)
         if (chunked) total += kK8Waves * kOvfChunk;
+        aln_totals[0] = total;
         set_error("slamem_find_mems_device: %llu MEMs found, output capacity is %llu", (unsigned long long)total,
                   (unsigned long long)mems_capacity);
         return SLAMEM_ERR_CAPACITY;
@@ -4362,6 +4401,23 @@ int SearchJob::collect() {
             return SLAMEM_ERR_ARG;
         }
         total = h_scal[9];
+    } else if (aln && !saw_long) {
+        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
+        if (h_scal[10]) {
+            set_error("slamem_find_alns_device: the -mem rows of strand block %llu are not in the emission order (query start "
+                      "descending, then length non-increasing); no alignments returned", h_scal[10] - 1ull);
+            total = 0;
+            return SLAMEM_ERR_ARG;
+        }
+        total = h_scal[9];
+        aln_totals[1] = h_scal[9];
+        aln_totals[2] = h_scal[11];
+        if (aln_totals[1] > alnargs.segs_capacity || aln_totals[2] > alnargs.ops_capacity) {
+            set_error("slamem_find_alns_device: %llu segments with %llu operations, the capacities are %llu and %llu",
+                      (unsigned long long)aln_totals[1], (unsigned long long)aln_totals[2],
+                      (unsigned long long)alnargs.segs_capacity, (unsigned long long)alnargs.ops_capacity);
+            return SLAMEM_ERR_CAPACITY;
+        }
     }
     return SLAMEM_OK;
 }
@@ -4387,7 +4443,8 @@ static int run_job(SearchJob& job, const slamem_index* idx, const void* queries_
                    uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                    slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
                    uint64_t workspace_bytes, hipStream_t stream, uint32_t max_occ, uint32_t max_gap, uint32_t* scores_dev,
-                   uint32_t ext_penalty, uint32_t ext_xdrop) {
+                   uint32_t ext_penalty, uint32_t ext_xdrop, const AlnArgs* aln) {
+    if (aln) job.alnargs = *aln;  // (before init, unlike the parameters below: init sizes the workspace by it)
     int rc = job.init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                       mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
     job.max_occ = max_occ;
@@ -4411,20 +4468,21 @@ int find_mems_device(const slamem_index* idx, const void* queries_dev, const uin
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
                      uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ, uint32_t max_gap,
-                     uint32_t* block_scores_dev, uint32_t ext_penalty, uint32_t ext_xdrop) {
+                     uint32_t* block_scores_dev, uint32_t ext_penalty, uint32_t ext_xdrop, const AlnArgs* aln, uint64_t* aln_totals) {
     if (!total_out) { set_error("slamem_find_mems_device: null argument"); return SLAMEM_ERR_ARG; }
     SearchJob job;
     job.speculate = true;
     int rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                      mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev,
-                     ext_penalty, ext_xdrop);
+                     ext_penalty, ext_xdrop, aln);
     if (rc == SLAMEM_OK && job.saw_long) {  // a record longer than a slice among the reads: once more, with the item tables
         job.speculate = false;
         rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
                      mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev,
-                     ext_penalty, ext_xdrop);
+                     ext_penalty, ext_xdrop, aln);
     }
     *total_out = job.total;
+    if (aln_totals) { aln_totals[0] = job.aln_totals[0]; aln_totals[1] = job.aln_totals[1]; aln_totals[2] = job.aln_totals[2]; }
     return rc;
 }
 
@@ -4451,6 +4509,10 @@ void search_job_slices_hint(SearchJob* j, uint32_t slices) { j->slices_hint = sl
 void search_job_k8_wave_cap(SearchJob* j, uint32_t waves) { j->k8_wave_cap = waves; }
 void search_job_max_occ(SearchJob* j, uint32_t max_occ) { j->max_occ = max_occ; }
 void search_job_max_gap(SearchJob* j, uint32_t max_gap) { j->max_gap = max_gap; }
+void search_job_aln(SearchJob* j, const AlnArgs& args) { j->alnargs = args; }
+void search_job_aln_totals(const SearchJob* j, uint64_t totals[3]) {
+    totals[0] = j->aln_totals[0]; totals[1] = j->aln_totals[1]; totals[2] = j->aln_totals[2];
+}
 void search_job_ext(SearchJob* j, uint32_t penalty, uint32_t xdrop, uint32_t* mismatches_dev) {
     j->ext_penalty = penalty;
     j->ext_xdrop = xdrop;

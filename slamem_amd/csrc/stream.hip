@@ -59,6 +59,15 @@ struct Slot {
     uint32_t* d_mm = nullptr;
     uint32_t* h_mm = nullptr;
     uint64_t h_mm_cap = 0;
+    // -aln: segments (room for `cap`: a segment has at least one chain row), operations (room for `ops_cap`) and the
+    // operations' offsets per segment, on the device and in pinned host memory; ops_total: the batch's operations
+    slamem_aln* d_segs = nullptr;
+    uint32_t* d_ops = nullptr;
+    uint64_t* d_ooff = nullptr;
+    slamem_aln* h_segs = nullptr;
+    uint32_t* h_ops = nullptr;
+    uint64_t* h_ooff = nullptr;
+    uint64_t ops_cap = 0, h_segs_cap = 0, h_ops_cap = 0, ops_total = 0;
     // the batch
     uint64_t seq = 0;
     const char* chars = nullptr;
@@ -96,7 +105,8 @@ struct slamem_stream {
     int nslots = 0, both = 0, match_type = 0;
     uint32_t max_occ = 0;  // -smem: the occurrence cap of every batch (slamem_stream_set_max_occ; 0: none)
     uint32_t max_gap = 0;  // -chain: the maximum gap of every batch (slamem_stream_set_max_gap; 0: the default)
-    uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;  // -ext: penalty and drop of every batch (slamem_stream_set_ext_params)
+    uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;  // -ext, -aln: penalty and drop of every batch (slamem_stream_set_ext_params)
+    uint32_t max_edits = kAlnDefaultEdits;  // -aln: the most edits in a gap (slamem_stream_set_max_edits)
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     Slot slot[kMaxSlots];
@@ -136,6 +146,18 @@ int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search sta
     sl.d_mems = nullptr; sl.d_ws = nullptr; sl.d_mm = nullptr;
     sl.cap = need_cap;
     sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, s->match_type);
+    if (s->match_type == 6) {
+        if (sl.d_segs) (void)hipFree(sl.d_segs);
+        if (sl.d_ops) (void)hipFree(sl.d_ops);
+        if (sl.d_ooff) (void)hipFree(sl.d_ooff);
+        sl.d_segs = nullptr; sl.d_ops = nullptr; sl.d_ooff = nullptr;
+        if (sl.ops_cap < 2 * sl.cap + 1024) sl.ops_cap = 2 * sl.cap + 1024;  // (a first guess; SLAMEM_ERR_CAPACITY tells the need)
+        sl.ws_bytes = find_mems_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap) +
+                      aln_workspace_bytes(sl.cap_q, (uint64_t)sl.cap_q * (s->both ? 2u : 1u), sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits);
+        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_segs), (sl.cap + 1) * sizeof(slamem_aln)));
+        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ops), (sl.ops_cap + 1) * 4));
+        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ooff), (sl.cap + 2) * 8));
+    }
     SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mems), sl.cap * sizeof(slamem_mem) + 16));
     SLAMEM_HIP(hipMalloc(&sl.d_ws, sl.ws_bytes));
     if (s->match_type == 5) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mm), sl.cap * 4 + 16));
@@ -329,6 +351,17 @@ int job_setup(slamem_stream* s, Slot& sl) {
     if (!sl.ev_done) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
     if (!sl.ev_k8) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_k8, hipEventDisableTiming));
     if (!sl.h_scal) SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_scal), 16 * sizeof(unsigned long long), hipHostMallocDefault));
+    if (s->match_type == 6) {
+        AlnArgs a;
+        a.max_gap = s->max_gap ? s->max_gap : kChainDefaultGap;
+        a.penalty = s->ext_penalty ? s->ext_penalty : kExtDefaultPenalty;
+        a.xdrop = s->ext_xdrop == kExtXdropUnset ? kExtDefaultXdrop : s->ext_xdrop;
+        a.max_edits = s->max_edits;
+        a.segs = sl.d_segs; a.segs_capacity = sl.cap;
+        a.ops = sl.d_ops; a.ops_capacity = sl.ops_cap;
+        a.op_offsets = sl.d_ooff;
+        search_job_aln(sl.job, a);
+    }
     int rc = search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, s->match_type,
                              sl.d_mems, sl.cap, sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal);
     search_job_max_occ(sl.job, s->max_occ);
@@ -417,8 +450,15 @@ int stage_download(slamem_stream* s, Slot& sl) {
     (void)slamem_reset_timings();
     SLAMEM_HIP(hipEventSynchronize(sl.ev_done));
     int rc = search_job_collect(sl.job, &sl.total);
-    for (int attempt = 0; rc == SLAMEM_ERR_CAPACITY && sl.total > sl.cap && attempt < 2; attempt++) {
+    uint64_t at[3] = {0, 0, 0};  // -aln: -mem rows, segments, operations
+    if (s->match_type == 6) search_job_aln_totals(sl.job, at);
+    for (int attempt = 0; rc == SLAMEM_ERR_CAPACITY && (sl.total > sl.cap || at[2] > sl.ops_cap) &&
+                          attempt < (s->match_type == 6 ? 3 : 2); attempt++) {  // (-aln: the rows may not fit, then the operations)
         // rare (the first guess was too small): more room, and the batch once more, start to end, on this stage's stream
+        if (s->match_type == 6) {
+            if (at[2] > sl.ops_cap) sl.ops_cap = at[2] + at[2] / 8 + 1024;
+            rc = grow_outputs(s, sl, at[0] > sl.cap ? at[0] + at[0] / 8 + 1024 : sl.cap);
+        } else
         rc = grow_outputs(s, sl, sl.total + sl.total / 8 + 1024);
         if (rc == SLAMEM_OK) rc = job_setup(s, sl);
         if (rc == SLAMEM_OK) rc = search_job_tables(sl.job, st);
@@ -426,7 +466,9 @@ int stage_download(slamem_stream* s, Slot& sl) {
         if (rc == SLAMEM_OK) rc = search_job_search(sl.job, st);
         SLAMEM_HIP(hipStreamSynchronize(st));
         if (rc == SLAMEM_OK) rc = search_job_collect(sl.job, &sl.total);
+        if (s->match_type == 6) search_job_aln_totals(sl.job, at);
     }
+    sl.ops_total = at[2];
     if (rc == SLAMEM_OK) rc = search_job_finish(sl.job, st, &sl.total);  // -mum: a batch with a large block
     (void)slamem_get_timings(&sl.tm);
     if (rc != SLAMEM_OK) return rc;
@@ -450,7 +492,27 @@ int stage_download(slamem_stream* s, Slot& sl) {
         SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_mems), sl.cap * sizeof(slamem_mem) + 16, hipHostMallocDefault));
         sl.h_cap = sl.cap;
     }
-    if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_mems, sl.d_mems, sl.total * sizeof(slamem_mem), hipMemcpyDeviceToHost, st));
+    if (sl.total && s->match_type != 6)
+        SLAMEM_HIP(hipMemcpyAsync(sl.h_mems, sl.d_mems, sl.total * sizeof(slamem_mem), hipMemcpyDeviceToHost, st));
+    if (s->match_type == 6) {  // (sl.total: the segments)
+        if (sl.h_segs_cap < sl.cap || !sl.h_segs) {
+            if (sl.h_segs) (void)hipHostFree(sl.h_segs);
+            if (sl.h_ooff) (void)hipHostFree(sl.h_ooff);
+            sl.h_segs = nullptr; sl.h_ooff = nullptr;
+            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_segs), (sl.cap + 1) * sizeof(slamem_aln), hipHostMallocDefault));
+            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_ooff), (sl.cap + 2) * 8, hipHostMallocDefault));
+            sl.h_segs_cap = sl.cap;
+        }
+        if (sl.h_ops_cap < sl.ops_cap || !sl.h_ops) {
+            if (sl.h_ops) (void)hipHostFree(sl.h_ops);
+            sl.h_ops = nullptr;
+            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_ops), (sl.ops_cap + 1) * 4, hipHostMallocDefault));
+            sl.h_ops_cap = sl.ops_cap;
+        }
+        if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_segs, sl.d_segs, sl.total * sizeof(slamem_aln), hipMemcpyDeviceToHost, st));
+        if (sl.ops_total) SLAMEM_HIP(hipMemcpyAsync(sl.h_ops, sl.d_ops, sl.ops_total * 4, hipMemcpyDeviceToHost, st));
+        SLAMEM_HIP(hipMemcpyAsync(sl.h_ooff, sl.d_ooff, (sl.total + 1) * 8, hipMemcpyDeviceToHost, st));
+    }
     if (s->match_type == 5) {
         if (sl.h_mm_cap < sl.cap || !sl.h_mm) {
             if (sl.h_mm) (void)hipHostFree(sl.h_mm);
@@ -514,6 +576,13 @@ void free_slot(Slot& sl) {
     if (sl.d_ws) (void)hipFree(sl.d_ws);
     if (sl.d_mm) (void)hipFree(sl.d_mm);
     if (sl.h_mm) (void)hipHostFree(sl.h_mm);
+    if (sl.d_segs) (void)hipFree(sl.d_segs);
+    if (sl.d_ops) (void)hipFree(sl.d_ops);
+    if (sl.d_ooff) (void)hipFree(sl.d_ooff);
+    if (sl.h_segs) (void)hipHostFree(sl.h_segs);
+    if (sl.h_ops) (void)hipHostFree(sl.h_ops);
+    if (sl.h_ooff) (void)hipHostFree(sl.h_ooff);
+    sl.d_segs = nullptr; sl.d_ops = nullptr; sl.d_ooff = nullptr; sl.h_segs = nullptr; sl.h_ops = nullptr; sl.h_ooff = nullptr;
     if (sl.d_planes) (void)hipFree(sl.d_planes);
     if (sl.d_other) (void)hipFree(sl.d_other);
     if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
@@ -631,8 +700,8 @@ int slamem_stream_destroy(slamem_stream* s) {
 
 int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream** out) {
-    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 5)) {
-        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 5)");
+    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 6)) {
+        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 6)");
         return SLAMEM_ERR_ARG;
     }
     *out = nullptr;
@@ -723,7 +792,7 @@ int slamem_stream_set_max_occ(slamem_stream* s, uint32_t max_occ) {
 int slamem_stream_set_max_gap(slamem_stream* s, uint32_t max_gap) {
     if (!s) { set_error("slamem_stream_set_max_gap: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
-    if (s->match_type != 4 && max_gap != 0) {
+    if (s->match_type != 4 && s->match_type != 6 && max_gap != 0) {
         set_error("slamem_stream_set_max_gap: a maximum gap needs match type 4 (-chain)");
         return SLAMEM_ERR_ARG;
     }
@@ -742,7 +811,7 @@ int slamem_stream_set_max_gap(slamem_stream* s, uint32_t max_gap) {
 int slamem_stream_set_ext_params(slamem_stream* s, uint32_t mismatch_penalty, uint32_t xdrop) {
     if (!s) { set_error("slamem_stream_set_ext_params: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
-    if (s->match_type != 5 && (mismatch_penalty != 0 || xdrop != kExtXdropUnset)) {
+    if (s->match_type != 5 && s->match_type != 6 && (mismatch_penalty != 0 || xdrop != kExtXdropUnset)) {
         set_error("slamem_stream_set_ext_params: a mismatch penalty or an X-drop needs match type 5 (-ext)");
         return SLAMEM_ERR_ARG;
     }
@@ -752,6 +821,41 @@ int slamem_stream_set_ext_params(slamem_stream* s, uint32_t mismatch_penalty, ui
     }
     s->ext_penalty = mismatch_penalty;
     s->ext_xdrop = xdrop;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_set_max_edits(slamem_stream* s, uint32_t max_edits) {
+    if (!s) { set_error("slamem_stream_set_max_edits: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type != 6 && max_edits != kAlnEditsUnset) {
+        set_error("slamem_stream_set_max_edits: an edit limit needs match type 6 (-aln)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (max_edits != kAlnEditsUnset && max_edits > kAlnMaxEdits) {
+        set_error("slamem_stream_set_max_edits: at most %u edits a gap", kAlnMaxEdits);
+        return SLAMEM_ERR_ARG;
+    }
+    if (s->submitted != 0) {
+        set_error("slamem_stream_set_max_edits: the stream has batches already (set the limit before the first submit)");
+        return SLAMEM_ERR_ARG;
+    }
+    s->max_edits = max_edits == kAlnEditsUnset ? kAlnDefaultEdits : max_edits;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_alns(slamem_stream* s, const slamem_aln** segs_out, const uint32_t** ops_out, const uint64_t** op_offsets_out,
+                       uint64_t* num_ops_out) {
+    if (!s || !segs_out || !ops_out || !op_offsets_out || !num_ops_out) { set_error("slamem_stream_alns: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    *segs_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr; *num_ops_out = 0;
+    if (s->match_type != 6) { set_error("slamem_stream_alns: the stream's match type is not 6 (-aln)"); return SLAMEM_ERR_ARG; }
+    if (s->returned == 0) { set_error("slamem_stream_alns: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
+    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
+    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
+        set_error("slamem_stream_alns: the batch slamem_stream_next returned last has no segments to show");
+        return SLAMEM_ERR_ARG;
+    }
+    *segs_out = sl.h_segs; *ops_out = sl.h_ops; *op_offsets_out = sl.h_ooff; *num_ops_out = sl.ops_total;
     return SLAMEM_OK;
 }
 

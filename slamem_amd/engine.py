@@ -16,6 +16,9 @@ import torch
 from . import capi
 
 MEM_DTYPE = np.dtype([("ref_pos", "<u4"), ("query_pos", "<u4"), ("length", "<u4")])
+ALN_DTYPE = np.dtype([("ref_pos", "<u4"), ("query_pos", "<u4"), ("ref_len", "<u4"), ("query_len", "<u4"), ("edits", "<u4")])
+EDITS_DEFAULT = 0xFFFFFFFF  # SLAMEM_ALN_EDITS_DEFAULT: "the default 31" in the C ABI (0 is a value of its own)
+CIGAR_OPS = {7: "=", 8: "X", 1: "I", 2: "D"}  # BAM's codes; an operation is length << 4 | code
 
 
 def _ptr(t: torch.Tensor) -> int:
@@ -221,6 +224,56 @@ class Index:
         same segment once, and a uint32 of mismatches per row."""
         return self._find(queries, offsets, min_len, both_strands, False, False, False, 0, False, 0, True, penalty, xdrop)
 
+    def find_alns(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
+                  xdrop=None, max_edits=None, capacities=None):
+        """-aln mode: (segments, block_offsets, ops, op_offsets) -- per strand block the gapped alignment built on its best
+        chain.  segments: a structured array (ref_pos, query_pos, ref_len, query_len, edits), the segments
+        of a block with the query start descending; block_offsets: per strand block; ops: uint32 CIGAR operations, length << 4
+        | code with BAM's codes (CIGAR_OPS), left to right in the scanned strand; op_offsets: per segment.  max_gap, penalty
+        and xdrop as for find_chains and find_exts; max_edits: the most edits in one gap (None: 31; at most 127).
+        capacities: (mems, segments, operations) to run with exactly that room (slamem.capi.SlamemError with
+        SLAMEM_ERR_CAPACITY and .totals = what is needed when it is too small); None: grow until the batch fits."""
+        dev = self.device
+        q = np.ascontiguousarray(np.frombuffer(queries, dtype=np.uint8) if isinstance(queries, (bytes, bytearray))
+                                 else queries, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        num = offsets.shape[0] - 1
+        nb = num * (2 if both_strands else 1)
+        qbytes = int(offsets[-1]) if num else 0
+        qd = torch.zeros((q.shape[0] + 15) // 8 * 8, dtype=torch.uint8, device=dev)
+        if q.shape[0]:
+            qd[: q.shape[0]] = torch.from_numpy(q if q.flags.writeable else q.copy()).to(dev)
+        od = torch.from_numpy(offsets.view(np.int64)).to(dev)
+        edits = EDITS_DEFAULT if max_edits is None else int(max_edits)
+        cap, scap, ocap = capacities if capacities is not None else (max(1024, q.shape[0] // 8 + 4 * num), nb + 1024, 4 * nb + 4096)
+        L = capi.lib()
+        boff = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+        while True:
+            need = C.c_uint64()
+            capi.check(L.slamem_find_alns_workspace_bytes(num, int(both_strands), qbytes, cap, ocap, edits, C.byref(need)))
+            ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+            segs = torch.zeros((scap + 1) * 5, dtype=torch.int32, device=dev)
+            ops = torch.zeros(ocap + 1, dtype=torch.int32, device=dev)
+            ooff = torch.zeros(scap + 2, dtype=torch.int64, device=dev)
+            totals = (C.c_uint64 * 3)()
+            with torch.cuda.device(dev):
+                torch.cuda.current_stream(dev).synchronize()
+                rc = L.slamem_find_alns_device(self._h, _ptr(qd), _ptr(od), num, qbytes, int(min_len), int(both_strands), int(max_gap),
+                                               int(penalty), _xdrop_arg(xdrop), edits, cap, _ptr(segs), scap, _ptr(boff), _ptr(ops),
+                                               ocap, _ptr(ooff), _ptr(ws), need.value, None, totals)
+            if rc == capi.SLAMEM_ERR_CAPACITY and capacities is None:
+                cap, scap, ocap = max(cap, int(totals[0])), max(scap, int(totals[1])), max(ocap, int(totals[2]))
+                continue
+            if rc != capi.SLAMEM_OK:
+                err = capi.SlamemError(rc, L.slamem_last_error_message().decode(errors="replace"))
+                err.totals = tuple(int(t) for t in totals)
+                raise err
+            break
+        nseg, nops = int(totals[1]), int(totals[2])
+        out = segs[: nseg * 5].cpu().numpy().view(np.uint32).reshape(-1, 5).copy().view(ALN_DTYPE).reshape(-1)
+        return (out, boff.cpu().numpy().view(np.uint64), ops[:nops].cpu().numpy().view(np.uint32),
+                ooff[: nseg + 1].cpu().numpy().view(np.uint64))
+
     def _find(self, queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap, ext=False, penalty=0,
               xdrop=None):
         _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
@@ -378,8 +431,15 @@ class Stream:
 
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
-                 max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None):
-        match_type = _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
+                 max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None):
+        """aln=True: -aln mode (match type 6); it takes max_gap, penalty, xdrop and max_edits and excludes the other modes.
+        next() then returns the segments (ALN_DTYPE) in the place of the rows, alns() their operations."""
+        if aln and (mam or mum or smem or chain or ext or max_occ):
+            raise ValueError("aln excludes mam, mum, smem, chain and ext: one match type per search")
+        if max_edits is not None and not aln:
+            raise ValueError("max_edits is the edit limit of aln: it needs aln=True")
+        self.aln = bool(aln)
+        match_type = 6 if aln else _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
         self.index = index
         self.both = bool(both_strands)
         self._h = C.c_void_p()
@@ -391,6 +451,8 @@ class Stream:
             capi.check(capi.lib().slamem_stream_set_max_gap(self._h, int(max_gap)))
         if penalty or xdrop is not None:
             capi.check(capi.lib().slamem_stream_set_ext_params(self._h, int(penalty), _xdrop_arg(xdrop)))
+        if max_edits is not None:
+            capi.check(capi.lib().slamem_stream_set_max_edits(self._h, int(max_edits)))
         self._keep = []
         self._last_total = 0
 
@@ -419,12 +481,26 @@ class Stream:
         capi.check(rc)
         self._last_total = int(total.value)
         nb = nq.value * (2 if self.both else 1)
+        if self.aln:  # the segments stand in the place of the rows
+            segs, ops, ooff, nops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+            capi.check(capi.lib().slamem_stream_alns(self._h, C.byref(segs), C.byref(ops), C.byref(ooff), C.byref(nops)))
+            n = int(total.value)
+            m = np.ctypeslib.as_array((C.c_uint8 * (20 * max(1, n))).from_address(segs.value))[: 20 * n].view(ALN_DTYPE)
+            o = np.ctypeslib.as_array((C.c_uint32 * max(1, nops.value)).from_address(ops.value))[: nops.value]
+            oo = np.ctypeslib.as_array((C.c_uint64 * (n + 1)).from_address(ooff.value))
+            b = np.ctypeslib.as_array((C.c_uint64 * (nb + 1)).from_address(boff.value))
+            self._last_alns = (o.copy(), oo.copy()) if copy else (o, oo)
+            return (m.copy(), b.copy(), tm.as_dict()) if copy else (m, b, tm.as_dict())
         m = np.ctypeslib.as_array((C.c_uint8 * (12 * max(1, total.value))).from_address(mems.value))[: 12 * total.value]
         m = m.view(MEM_DTYPE)
         b = np.ctypeslib.as_array((C.c_uint64 * (nb + 1)).from_address(boff.value))
         if copy:
             m, b = m.copy(), b.copy()
         return m, b, tm.as_dict()
+
+    def alns(self):
+        """-aln: (ops, op_offsets) of the batch next() returned last (slamem_stream_alns), as next() took them."""
+        return self._last_alns
 
     def mismatches(self, copy: bool = True) -> np.ndarray:
         """-ext: the mismatches (uint32 per row) of the batch next() returned last (slamem_stream_mismatches).  copy=False

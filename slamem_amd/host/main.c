@@ -43,8 +43,8 @@
 #define VERSION "0.8.2"
 /* what the output lines call a match of each type: M%cM with the reference's "EAU" (slamem.c:35), SMEM for -smem,
  * "chained MEM" for the rows -chain keeps and "extended MEM" for the rows of -ext */
-static const char *const MATCH_TYPE_NAME[6] = {"MEM", "MAM", "MUM", "SMEM", "chained MEM", "extended MEM"};
-#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 6 ? (t) : 0]
+static const char *const MATCH_TYPE_NAME[7] = {"MEM", "MAM", "MUM", "SMEM", "chained MEM", "extended MEM", "alignment"};
+#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 7 ? (t) : 0]
 
 /* the device warm-up thread (see main) is joined before the process ends, whichever way it ends */
 static pthread_t g_warm_tid;
@@ -170,6 +170,9 @@ typedef struct {
     const slh_seqset *ref;
     const slamem_mem *mems;
     const uint32_t *mism; /* -ext: a fourth column, the mismatches of each row (NULL otherwise) */
+    const slamem_aln *segs; /* -aln: the segments in the place of the rows (NULL otherwise), their operations and offsets */
+    const uint32_t *ops;
+    const uint64_t *ooff;
     const uint64_t *boff;
     int first_rec, strands;
     uint64_t b0, b1; /* strand blocks [b0,b1) of the batch */
@@ -214,7 +217,9 @@ static void *fmt_run(void *arg) {
     for (b = j->b0; b < j->b1; b++) {
         int i = j->first_rec + (int)(b / (uint64_t)j->strands), s = (int)(b % (uint64_t)j->strands);
         uint64_t cnt = j->boff[b + 1] - j->boff[b], sum = 0;
-        if (slh_format_block_ext(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->mems + j->boff[b]),
+        if (j->segs ? slh_format_block_aln(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->segs + j->boff[b]), j->ops,
+                                           j->ooff + j->boff[b], cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)
+                    : slh_format_block_ext(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->mems + j->boff[b]),
                                  j->mism ? j->mism + j->boff[b] : NULL, cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)) {
             j->failed = 1;
             return NULL;
@@ -577,6 +582,8 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-ext\textend every MEM through mismatches (ungapped X-drop); writes a fourth column, the mismatches\n");
     printf("\t-pen\twith -ext: mismatch penalty, a match scores 1 (default=4)\n");
     printf("\t-xdrop\twith -ext: stop when the score falls this far below its best (default=20)\n");
+    printf("\t-aln\tgapped alignment of the best chain of each strand; writes ref_pos query_pos ref_len query_len edits cigar\n");
+    printf("\t-maxed\twith -aln: most edits in the gap between two chained MEMs, 0 to 127 (default=31); -mgap, -pen, -xdrop apply\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
     printf("\t-b\tprocess both forward and reverse strands\n");
@@ -601,7 +608,7 @@ int main(int argc, char **argv) {
     char *out_name;
     FILE *out;
     slamem_index *idx = NULL, *gpus[16];
-    int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1;
+    int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1;
     double t0;
     long long total_matches = 0, total_sum = 0;
     slh_buffer buf = {0, 0, 0};
@@ -623,6 +630,7 @@ int main(int argc, char **argv) {
         return slh_clean_fasta(argv[2], stdout);
     }
     if (o.match_type < 0) { /* before any GPU work */
+        if (slh_parse_argument(argc, argv, "AL", 0)) exit_message("Option -aln excludes -mam, -mum, -smem, -chain and -ext");
         if (slh_parse_argument(argc, argv, "EX", 0)) exit_message("Option -ext excludes -mam, -mum, -smem and -chain");
         if (slh_parse_argument(argc, argv, "CH", 0)) exit_message("Option -chain excludes -mam, -mum and -smem");
         if (slh_parse_argument(argc, argv, "SM", 0)) exit_message("Option -smem excludes -mam and -mum");
@@ -635,12 +643,17 @@ int main(int argc, char **argv) {
     }
     switch (slh_parse_max_gap(argc, argv, &max_gap)) {
     case -1: exit_message("Option -mgap needs a whole number of at least 1"); break;
-    case 1: if (o.match_type != 4) exit_message("Option -mgap needs -chain"); break;
+    case 1: if (o.match_type != 4 && o.match_type != 6) exit_message("Option -mgap needs -chain"); break;
     default: break;
     }
     switch (slh_parse_ext_params(argc, argv, &ext_pen, &ext_xdrop)) {
     case -1: exit_message("Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"); break;
-    case 1: if (o.match_type != 5) exit_message("Options -pen and -xdrop need -ext"); break;
+    case 1: if (o.match_type != 5 && o.match_type != 6) exit_message("Options -pen and -xdrop need -ext"); break;
+    default: break;
+    }
+    switch (slh_parse_max_edits(argc, argv, &max_edits)) {
+    case -1: exit_message("Option -maxed needs a whole number from 0 to 127"); break;
+    case 1: if (o.match_type != 6) exit_message("Option -maxed needs -aln"); break;
     default: break;
     }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
@@ -748,6 +761,9 @@ int main(int argc, char **argv) {
     if (max_occ > 0) say(" ; maximum occurrences = %d", max_occ);
     if (o.match_type == 4) say(" ; maximum gap = %d", max_gap > 0 ? max_gap : 5000);
     if (o.match_type == 5) say(" ; mismatch penalty = %d ; X-drop = %d", ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20);
+    if (o.match_type == 6)
+        say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", max_gap > 0 ? max_gap : 5000,
+            ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
     say("\n");
     out = fopen(out_name, "w");
     if (!out) {
@@ -896,6 +912,15 @@ int main(int argc, char **argv) {
                 rc = slamem_stream_set_ext_params(g_streams[g], (uint32_t)ext_pen,
                                                   ext_xdrop >= 0 ? (uint32_t)ext_xdrop : SLAMEM_EXT_XDROP_DEFAULT);
             }
+            if (rc == SLAMEM_OK && o.match_type == 6) {
+                g_nstreams = g + 1;
+                rc = slamem_stream_set_max_gap(g_streams[g], (uint32_t)max_gap);
+                if (rc == SLAMEM_OK)
+                    rc = slamem_stream_set_ext_params(g_streams[g], (uint32_t)ext_pen,
+                                                      ext_xdrop >= 0 ? (uint32_t)ext_xdrop : SLAMEM_EXT_XDROP_DEFAULT);
+                if (rc == SLAMEM_OK)
+                    rc = slamem_stream_set_max_edits(g_streams[g], max_edits >= 0 ? (uint32_t)max_edits : SLAMEM_ALN_EDITS_DEFAULT);
+            }
             if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("setting up the search pipeline", rc); }
             g_nstreams = g + 1;
             inflight[g] = 0;
@@ -926,6 +951,10 @@ int main(int argc, char **argv) {
                 if (qsets[sets_reaped].chars) reap_set(&qsets[sets_reaped]);
             const slamem_mem *mems = NULL;
             const uint32_t *mism = NULL;
+            const slamem_aln *segs = NULL;
+            const uint32_t *ops = NULL;
+            const uint64_t *ooff = NULL;
+            uint64_t nops = 0;
             const uint64_t *boff = NULL;
             uint64_t total = 0;
             double tg = now_s();
@@ -952,6 +981,10 @@ int main(int argc, char **argv) {
                 rc = slamem_stream_mismatches(g_streams[bi % (size_t)ngpu], &mism);
                 if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("MEM extension on the GPU", rc); }
             }
+            if (o.match_type == 6) { /* the segments stand in the place of the rows */
+                rc = slamem_stream_alns(g_streams[bi % (size_t)ngpu], &segs, &ops, &ooff, &nops);
+                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("alignment on the GPU", rc); }
+            }
             inflight[bi % (size_t)ngpu]--;
             t_gpu += now_s() - tg; /* time the main thread waited for the GPUs */
             tg = now_s();
@@ -965,7 +998,9 @@ int main(int argc, char **argv) {
                 for (b = 0; b < bseq; b++) {
                     int ri = first + (int)(b / strands), sidx = (int)(b % strands), d, dots;
                     uint64_t cnt = boff[b + 1] - boff[b], sum = 0;
-                    if (slh_format_block_ext(&buf, q->recs[ri].name, sidx, (const uint32_t *)(mems + boff[b]),
+                    if (segs ? slh_format_block_aln(&buf, q->recs[ri].name, sidx, (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b],
+                                                    cnt, ref.recs, ref.merged_start, ref.num, &sum)
+                             : slh_format_block_ext(&buf, q->recs[ri].name, sidx, (const uint32_t *)(mems + boff[b]),
                                              mism ? mism + boff[b] : NULL, cnt, ref.recs, ref.merged_start, ref.num, &sum))
                         pipeline_fail("Out of memory");
                     total_matches += (long long)cnt;
@@ -994,6 +1029,7 @@ int main(int argc, char **argv) {
                     per = (nblk - bseq + (uint64_t)njobs - 1) / (uint64_t)njobs;
                     for (t = 0; t < njobs; t++) {
                         jobs[t].q = q; jobs[t].ref = &ref; jobs[t].mems = mems; jobs[t].mism = mism; jobs[t].boff = boff;
+                        jobs[t].segs = segs; jobs[t].ops = ops; jobs[t].ooff = ooff;
                         jobs[t].first_rec = first; jobs[t].strands = strands;
                         jobs[t].b0 = bseq + per * (uint64_t)t < nblk ? bseq + per * (uint64_t)t : nblk;
                         jobs[t].b1 = jobs[t].b0 + per < nblk ? jobs[t].b0 + per : nblk;

@@ -717,6 +717,27 @@ int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out
     return seen;
 }
 
+static int is_maxed_option(const char *a) {
+    return two_letter_option(a, 'm', 'a') && (a[3] == 'x' || a[3] == 'X');
+}
+
+int slh_parse_max_edits(int argc, char **argv, int *out) {
+    int i;
+    *out = -1;
+    for (i = 1; i < argc; i++) {
+        char *end;
+        long v;
+        if (!is_maxed_option(argv[i])) continue;
+        if (i == argc - 1) return -1;
+        errno = 0;
+        v = strtol(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 0 || v > 127) return -1;
+        *out = (int)v;
+        return 1;
+    }
+    return 0;
+}
+
 char *slh_append_to_basename(const char *filename, const char *extra) {
     int n = (int)strlen(filename), i;
     char *res;
@@ -806,7 +827,9 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         }
     }
     o->image_arg = slh_parse_argument(argc, argv, "V", 2);
-    o->match_type = slh_parse_argument(argc, argv, "MA", 0) ? 1 : 0;
+    o->match_type = 0;
+    for (i = 1; i < argc; i++) /* -mam: "ma", but not -maxed (the edit limit of -aln) */
+        if (two_letter_option(argv[i], 'm', 'a') && !is_maxed_option(argv[i])) o->match_type = 1;
     if (slh_parse_argument(argc, argv, "MU", 0)) /* -mum: the match type the reference reserves ("EAU", slamem.c:35) */
         o->match_type = o->match_type == 1 ? -1 : 2;
     if (slh_parse_argument(argc, argv, "SM", 0)) /* -smem: super-maximal matches (an 's' option takes no value; "-s" alone is the sort tool) */
@@ -815,6 +838,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type != 0 ? -1 : 4;
     if (slh_parse_argument(argc, argv, "EX", 0)) /* -ext: ungapped X-drop extension of every MEM (an 'e' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 5;
+    if (slh_parse_argument(argc, argv, "AL", 0)) /* -aln: the gapped alignment of the best chain (an 'a' option takes no value) */
+        o->match_type = o->match_type != 0 ? -1 : 6;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;
@@ -870,6 +895,53 @@ static inline char *put_u32(char *p, uint32_t v) {
     else tmp[--n] = (char)('0' + v);
     memcpy(p, tmp + n, (size_t)(10 - n));
     return p + (10 - n);
+}
+
+int slh_format_block_aln(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *segs, const uint32_t *ops,
+                         const uint64_t *op_off, uint64_t count, const slh_record *refs, const uint32_t *merged_start,
+                         int num_refs, uint64_t *sum_len_out) {
+    static const char OPC[16] = {'?', 'I', 'D', '?', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+    size_t nl = strlen(query_name);
+    uint64_t i, k, sum = 0;
+    char *p;
+    if (buf_reserve(buf, nl + 16)) return -1;
+    p = buf->data + buf->len;
+    *p++ = '>';
+    memcpy(p, query_name, nl);
+    p += nl;
+    if (reverse) { memcpy(p, " Reverse", 8); p += 8; }
+    *p++ = '\n';
+    buf->len = (size_t)(p - buf->data);
+    for (i = 0; i < count; i++) {
+        uint32_t rp = segs[5 * i];
+        const uint64_t nops = op_off[i + 1] - op_off[i];
+        size_t namelen = 0;
+        const char *rname = NULL;
+        if (num_refs > 1) {
+            rname = refs[slh_seq_id_from_merged_pos(merged_start, num_refs, &rp)].name;
+            namelen = strlen(rname);
+        }
+        /* five numbers of at most ten digits with their tabs, and eleven characters an operation */
+        if (buf_reserve(buf, namelen + 72 + (size_t)nops * 11)) return -1;
+        p = buf->data + buf->len;
+        if (rname) {
+            *p++ = ' ';
+            memcpy(p, rname, namelen);
+            p += namelen;
+            *p++ = '\t';
+        }
+        p = put_u32(p, rp + 1);
+        *p++ = '\t';
+        p = put_u32(p, segs[5 * i + 1] + 1);
+        for (k = 2; k < 5; k++) { *p++ = '\t'; p = put_u32(p, segs[5 * i + k]); }
+        *p++ = '\t';
+        for (k = op_off[i]; k < op_off[i + 1]; k++) { p = put_u32(p, ops[k] >> 4); *p++ = OPC[ops[k] & 15u]; }
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+        sum += segs[5 * i + 3];
+    }
+    if (sum_len_out) *sum_len_out = sum;
+    return 0;
 }
 
 int slh_format_block(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *mems, uint64_t count,

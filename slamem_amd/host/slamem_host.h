@@ -69,7 +69,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), -1 two of them */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), -1 two of them */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
@@ -90,6 +90,10 @@ int slh_parse_max_gap(int argc, char **argv, int *out);
  * (*penalty_out = 0, *xdrop_out = -1: the defaults), 1 when at least one is, -1 when a value is missing, not an integer or out
  * of range.  Their values are never taken for file names. */
 int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out);
+/* -maxed N (-max...: three letters, because "-ma" is -mam): the most edits in one gap of -aln, a whole number in [0, 127].  0 when
+ * it is not there (*out = -1: the default), 1 when it is, -1 when the value is missing, not an integer or out of range.  An
+ * argument that starts with -max is never taken for -mam. */
+int slh_parse_max_edits(int argc, char **argv, int *out);
 /* AppendToBasename (tools.c:65-79): everything before the last '.' of the whole path + extra */
 char *slh_append_to_basename(const char *filename, const char *extra);
 
@@ -107,6 +111,12 @@ int slh_format_block(slh_buffer *buf, const char *query_name, int reverse, const
 int slh_format_block_ext(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *mems, const uint32_t *extra,
                          uint64_t count, const slh_record *refs, const uint32_t *merged_start, int num_refs,
                          uint64_t *sum_len_out);
+/* A strand block of the -aln file: the -mem header, then per segment ref_pos query_pos ref_len query_len edits cigar, the
+ * positions as -mem prints them.  segs: five uint32 per segment; op_off[i] .. op_off[i + 1]: segment i's operations in ops
+ * (length << 4 | BAM code of = X I D).  *sum_len_out: the query letters of the segments. */
+int slh_format_block_aln(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *segs, const uint32_t *ops,
+                         const uint64_t *op_off, uint64_t count, const slh_record *refs, const uint32_t *merged_start,
+                         int num_refs, uint64_t *sum_len_out);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
