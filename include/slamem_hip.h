@@ -62,6 +62,17 @@ typedef struct {
     uint32_t edits;
 } slamem_aln;
 
+/* One read's mapping (option -paf).  strand: 0 the read is unmapped, 1 its mapping lies on the forward strand,
+ * 2 on the reverse strand; mapq: 0 to 60; s1: the score of the primary strand block's best chain; s2: that of the best competing
+ * chain. */
+typedef struct {
+    uint32_t s1;
+    uint32_t s2;
+    uint8_t strand;
+    uint8_t mapq;
+    uint8_t reserved[2]; /* 0 */
+} slamem_map;
+
 typedef struct {
     uint32_t text_length;  /* n                                           */
     uint32_t bwt_size;     /* n + 1            == FMI_GetBWTSize(), bwtindex.c:263 */
@@ -109,7 +120,7 @@ typedef struct {
     double prefilter_ms_sum;
     double k8_ms_sum;
     float seed_ms;            /* K8s k_seed_mems (seed-and-compare for reads; runs in K8a's place), part of search_kernel_ms (ABI 4) */
-    float mum_filter_ms;      /* -mum / -smem / -chain / -ext / -aln: the filter behind K9 (mum_filter.hip, smem_filter.hip, chain_filter.hip, ext_filter.hip, aln_filter.hip), large blocks included; 0 for -mem and -mam */
+    float mum_filter_ms;      /* -mum / -smem / -chain / -ext / -aln / -paf: the filter behind K9 (mum_filter.hip, smem_filter.hip, chain_filter.hip, ext_filter.hip, aln_filter.hip, map_filter.hip), large blocks included; 0 for -mem and -mam */
     double seed_ms_sum;
 } slamem_timings;
 
@@ -410,6 +421,23 @@ int slamem_find_alns_device(const slamem_index *idx, const void *queries_dev, co
                             uint64_t ops_capacity, uint64_t *op_offsets_dev, void *workspace_dev, uint64_t workspace_bytes,
                             void *stream, uint64_t *totals_out);
 
+/* The same batch in mapping mode (option -paf: matchType 7): one mapping per read.  Per read the strand block
+ * whose best chain scores highest is the primary one (the forward block on a tie); only that block is aligned, exactly as
+ * slamem_find_alns_device aligns it, and the other block gives no segments.  reads_dev takes a slamem_map per read: the strand,
+ * the score s1 of the primary chain, the score s2 of the best competing chain (the best chain of the primary block's rows
+ * without the primary chain's, or the other block's best chain) and mapq = 60 * (s1 - s2) / s1 in whole numbers.
+ * read_offsets_dev (num_queries + 1) takes the segments' offsets per READ.  Segments, operations, capacities, totals_out, errors:
+ * as for slamem_find_alns_device; the positions are those of the scanned strand (query_pos on the reverse strand counts in the
+ * reverse complement).  The workspace is slamem_find_maps_workspace_bytes() bytes. */
+int slamem_find_maps_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                     uint64_t ops_capacity, uint32_t max_edits, uint64_t *bytes_out);
+int slamem_find_maps_device(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,
+                            uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap,
+                            uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity,
+                            slamem_aln *segs_dev, uint64_t segs_capacity, uint64_t *read_offsets_dev, uint32_t *ops_dev,
+                            uint64_t ops_capacity, uint64_t *op_offsets_dev, slamem_map *reads_dev, void *workspace_dev,
+                            uint64_t workspace_bytes, void *stream, uint64_t *totals_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -441,6 +469,12 @@ int slamem_find_alns_host(const slamem_index *idx, const char *queries, const ui
                           uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
                           uint32_t max_edits, slamem_aln **segs_out, uint64_t **block_offsets_out, uint32_t **ops_out,
                           uint64_t **op_offsets_out, uint64_t *totals_out);
+/* (five malloc()ed arrays: segments, num_queries + 1 read offsets, operations, segments + 1 operation offsets, num_queries
+ * read records; totals_out[0..2] as for slamem_find_alns_device) */
+int slamem_find_maps_host(const slamem_index *idx, const char *queries, const uint64_t *offsets, uint32_t num_queries,
+                          uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
+                          uint32_t max_edits, slamem_aln **segs_out, uint64_t **read_offsets_out, uint32_t **ops_out,
+                          uint64_t **op_offsets_out, slamem_map **reads_out, uint64_t *totals_out);
 void slamem_host_free(void *p);
 
 /* ---- (b') MEM retrieval, host to host, pipelined -------------------------------
@@ -456,7 +490,9 @@ void slamem_host_free(void *p);
  *                          and offsets, no scores), 5 = extension (-ext: the extended rows; their mismatches through
  *                          slamem_stream_mismatches), 6 = alignment (-aln: slamem_stream_next gives the block offsets and, as
  *                          its total, the number of segments -- its rows pointer is not to be read; the segments, operations
- *                          and operation offsets come through slamem_stream_alns)
+ *                          and operation offsets come through slamem_stream_alns), 7 = mapping (-paf: as 6 with the offsets
+ *                          per READ, num_queries + 1 of them, and a record per read through slamem_stream_maps; it takes the
+ *                          setters of 6)
  *   slamem_stream_set_max_occ  -smem: the occurrence cap of every batch (0: none, the default); before the first submit
  *                          (SLAMEM_ERR_ARG after it, or with a cap on a stream of another match type)
  *   slamem_stream_set_max_gap  -chain: the maximum gap of every batch (0: the default 5000); before the first submit
@@ -495,6 +531,9 @@ int slamem_stream_mismatches(slamem_stream *s, const uint32_t **out);
 int slamem_stream_set_max_edits(slamem_stream *s, uint32_t max_edits);
 int slamem_stream_alns(slamem_stream *s, const slamem_aln **segs_out, const uint32_t **ops_out, const uint64_t **op_offsets_out,
                        uint64_t *num_ops_out);
+/* -paf: the read records (num_queries of them) of the batch slamem_stream_next returned last, in the stream's pinned memory;
+ * valid as long as that batch.  Its segments and operations come through slamem_stream_alns. */
+int slamem_stream_maps(slamem_stream *s, const slamem_map **reads_out);
 int slamem_stream_submit(slamem_stream *s, const char *queries, const uint64_t *offsets, uint32_t num_queries,
                          uint32_t min_len);
 /* The same for reads the caller holds PACKED (ABI 4; no reference counterpart: the reference reads letters, sequence.c:89-270).

@@ -524,9 +524,30 @@ void aln_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_m
 
 #define ASTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
 
+void aln_chain_buffers(void* ws, uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity,
+                       const AlnArgs& args, slamem_mem** crows_out, uint64_t** coff_out) {
+    const AlnLayout m = aln_layout(num_queries, num_blocks, query_bytes, capacity, args.ops_capacity, args.max_edits);
+    char* p = static_cast<char*>(ws);
+    *crows_out = reinterpret_cast<slamem_mem*>(p + m.off_crows);
+    *coff_out = reinterpret_cast<uint64_t*>(p + m.off_coff);
+}
+
 int aln_filter(void* ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries, uint32_t strands,
                uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff, unsigned long long* host_scalars,
                hipStream_t stream) {
+    slamem_mem* crows;
+    uint64_t* coff;
+    aln_chain_buffers(ws, num_queries, num_queries * strands, query_bytes, capacity, args, &crows, &coff);
+    // the chains: [0] rows kept (replaced below), [1] the first block out of order + 1
+    const int rc = chain_filter(ws, num_queries * strands, capacity, args.max_gap, crows, coff, nullptr, host_scalars, stream);
+    if (rc != SLAMEM_OK) return rc;
+    return aln_after_chain(ws, ix, queries_dev, offsets_dev, num_queries, strands, query_bytes, capacity, args, out_boff, host_scalars,
+                           stream);
+}
+
+int aln_after_chain(void* ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
+                    uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff,
+                    unsigned long long* host_scalars, hipStream_t stream) {
     const uint64_t num_blocks = num_queries * strands;
     const AlnLayout m = aln_layout(num_queries, num_blocks, query_bytes, capacity, args.ops_capacity, args.max_edits);
     char* p = static_cast<char*>(ws);
@@ -549,9 +570,6 @@ int aln_filter(void* ws, const IndexView& ix, const void* queries_dev, const uin
     uint32_t* slab = reinterpret_cast<uint32_t*>(p + m.off_slab);
     int32_t* fslab = reinterpret_cast<int32_t*>(p + m.off_f);
     const char* queries = static_cast<const char*>(queries_dev);
-    // the chains: [0] rows kept (replaced below), [1] the first block out of order + 1
-    int rc = chain_filter(ws, num_blocks, capacity, args.max_gap, crows, coff, nullptr, host_scalars, stream);
-    if (rc != SLAMEM_OK) return rc;
     ASTEP(hipMemsetAsync(ctr, 0, 64, stream), "memset");
     ASTEP(pack_batch_planes(queries, offsets_dev, num_queries, ucnt, uoff, p + m.off_uscan, m.uscan_bytes, longs, units, ctr, stream),
           "pack_batch_planes");

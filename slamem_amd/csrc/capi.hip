@@ -553,6 +553,7 @@ int slamem_find_alns_device(const slamem_index* idx, const void* queries_dev, co
     a.ops = ops_dev;
     a.ops_capacity = ops_capacity;
     a.op_offsets = op_offsets_dev;
+    a.reads = nullptr;
     uint64_t total = 0;
     return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 6, nullptr, mems_capacity,
                             block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream), &total, 0, 0, nullptr,
@@ -637,6 +638,127 @@ done:
     if (d_ops) (void)hipFree(d_ops);
     if (d_ooff) (void)hipFree(d_ooff);
     if (d_ws) (void)hipFree(d_ws);
+    return rc;
+}
+
+int slamem_find_maps_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                     uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out) {
+    if (!bytes_out) return SLAMEM_ERR_ARG;
+    if (!aln_args_ok("slamem_find_maps_workspace_bytes", 0, max_edits)) return SLAMEM_ERR_ARG;
+    *bytes_out = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity) +
+                 map_workspace_bytes(num_queries, (uint64_t)num_queries * (both_strands ? 2u : 1u), query_bytes, mems_capacity,
+                                     ops_capacity, max_edits);
+    return SLAMEM_OK;
+}
+
+int slamem_find_maps_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                            uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty,
+                            uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity, slamem_aln* segs_dev, uint64_t segs_capacity,
+                            uint64_t* read_offsets_dev, uint32_t* ops_dev, uint64_t ops_capacity, uint64_t* op_offsets_dev,
+                            slamem_map* reads_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream, uint64_t* totals_out) {
+    if (!totals_out) { set_error("slamem_find_maps_device: null argument"); return SLAMEM_ERR_ARG; }
+    totals_out[0] = totals_out[1] = totals_out[2] = 0;
+    if (!aln_args_ok("slamem_find_maps_device", max_gap, max_edits)) return SLAMEM_ERR_ARG;
+    AlnArgs a;
+    a.max_gap = max_gap ? max_gap : kChainDefaultGap;
+    a.penalty = mismatch_penalty ? mismatch_penalty : kExtDefaultPenalty;
+    a.xdrop = xdrop == kExtXdropUnset ? kExtDefaultXdrop : xdrop;
+    a.max_edits = max_edits;
+    a.segs = segs_dev;
+    a.segs_capacity = segs_capacity;
+    a.ops = ops_dev;
+    a.ops_capacity = ops_capacity;
+    a.op_offsets = op_offsets_dev;
+    a.reads = reads_dev;
+    uint64_t total = 0;
+    return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 7, nullptr, mems_capacity,
+                            read_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream), &total, 0, 0, nullptr,
+                            0, kExtXdropUnset, &a, totals_out);
+}
+
+int slamem_find_maps_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
+                          int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
+                          slamem_aln** segs_out, uint64_t** read_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
+                          slamem_map** reads_out, uint64_t* totals_out) {
+    if (!idx || !offsets || !segs_out || !read_offsets_out || !ops_out || !op_offsets_out || !reads_out || !totals_out || (num_queries && !queries)) {
+        set_error("slamem_find_maps_host: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    *segs_out = nullptr; *read_offsets_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr; *reads_out = nullptr;
+    totals_out[0] = totals_out[1] = totals_out[2] = 0;
+    {
+        uint32_t e = max_edits;
+        if (!aln_args_ok("slamem_find_maps_host", max_gap, e)) return SLAMEM_ERR_ARG;
+    }
+    const uint64_t qbytes = offsets[num_queries] - offsets[0];
+    const uint64_t num_blocks = (uint64_t)num_queries * (both_strands ? 2u : 1u);
+    const char* q0 = queries ? queries + offsets[0] : nullptr;
+    uint64_t* rel = static_cast<uint64_t*>(malloc(((uint64_t)num_queries + 1) * 8));
+    if (!rel) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
+    for (uint64_t i = 0; i <= num_queries; i++) rel[i] = offsets[i] - offsets[0];
+    uint64_t cap = 2 * qbytes / (min_len ? min_len : 1) + 4 * num_blocks + 1024;  // the -mem list
+    uint64_t scap = num_blocks + 1024, ocap = 4 * num_blocks + 4096;                // segments, operations
+    void *d_q = nullptr, *d_off = nullptr, *d_boff = nullptr, *d_segs = nullptr, *d_ops = nullptr, *d_ooff = nullptr, *d_ws = nullptr, *d_reads = nullptr;
+    slamem_aln* h_segs = nullptr;
+    uint64_t *h_boff = nullptr, *h_ooff = nullptr;
+    uint32_t* h_ops = nullptr;
+    slamem_map* h_reads = nullptr;
+    int rc = SLAMEM_OK;
+    hipError_t e;
+#define MAP_TRY(call) if ((e = (call)) != hipSuccess) { rc = hip_fail(e, #call, __FILE__, __LINE__); goto done; }
+    MAP_TRY(hipSetDevice(idx->device));
+    MAP_TRY(hipMalloc(&d_q, qbytes + 16));
+    MAP_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
+    MAP_TRY(hipMalloc(&d_boff, ((uint64_t)num_queries + 1) * 8));
+    MAP_TRY(hipMalloc(&d_reads, ((uint64_t)num_queries + 1) * sizeof(slamem_map)));
+    if (qbytes) MAP_TRY(hipMemcpy(d_q, q0, qbytes, hipMemcpyHostToDevice));
+    MAP_TRY(hipMemcpy(d_off, rel, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
+    for (int attempt = 0; attempt < 4; attempt++) {
+        uint64_t ws_bytes = 0;
+        rc = slamem_find_maps_workspace_bytes(num_queries, both_strands, qbytes, cap, ocap, max_edits, &ws_bytes);
+        if (rc) goto done;
+        MAP_TRY(hipMalloc(&d_segs, (scap + 1) * sizeof(slamem_aln)));
+        MAP_TRY(hipMalloc(&d_ops, (ocap + 1) * 4));
+        MAP_TRY(hipMalloc(&d_ooff, (scap + 2) * 8));
+        MAP_TRY(hipMalloc(&d_ws, ws_bytes));
+        rc = slamem_find_maps_device(idx, d_q, static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands, max_gap,
+                                     mismatch_penalty, xdrop, max_edits, cap, static_cast<slamem_aln*>(d_segs), scap,
+                                     static_cast<uint64_t*>(d_boff), static_cast<uint32_t*>(d_ops), ocap, static_cast<uint64_t*>(d_ooff),
+                                     static_cast<slamem_map*>(d_reads), d_ws, ws_bytes, nullptr, totals_out);
+        if (rc != SLAMEM_ERR_CAPACITY) break;
+        (void)hipFree(d_segs); d_segs = nullptr;
+        (void)hipFree(d_ops); d_ops = nullptr;
+        (void)hipFree(d_ooff); d_ooff = nullptr;
+        (void)hipFree(d_ws); d_ws = nullptr;
+        if (totals_out[0] > cap) cap = totals_out[0] + 1024;
+        if (totals_out[1] > scap) scap = totals_out[1] + 1024;
+        if (totals_out[2] > ocap) ocap = totals_out[2] + 1024;
+    }
+    if (rc) goto done;
+    h_segs = static_cast<slamem_aln*>(malloc((totals_out[1] + 1) * sizeof(slamem_aln)));
+    h_boff = static_cast<uint64_t*>(malloc(((uint64_t)num_queries + 1) * 8));
+    h_reads = static_cast<slamem_map*>(malloc(((uint64_t)num_queries + 1) * sizeof(slamem_map)));
+    h_ops = static_cast<uint32_t*>(malloc((totals_out[2] + 1) * 4));
+    h_ooff = static_cast<uint64_t*>(malloc((totals_out[1] + 1) * 8));
+    if (!h_segs || !h_boff || !h_ops || !h_ooff || !h_reads) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
+    if (totals_out[1]) MAP_TRY(hipMemcpy(h_segs, d_segs, totals_out[1] * sizeof(slamem_aln), hipMemcpyDeviceToHost));
+    MAP_TRY(hipMemcpy(h_boff, d_boff, ((uint64_t)num_queries + 1) * 8, hipMemcpyDeviceToHost));
+    if (num_queries) MAP_TRY(hipMemcpy(h_reads, d_reads, (uint64_t)num_queries * sizeof(slamem_map), hipMemcpyDeviceToHost));
+    if (totals_out[2]) MAP_TRY(hipMemcpy(h_ops, d_ops, totals_out[2] * 4, hipMemcpyDeviceToHost));
+    MAP_TRY(hipMemcpy(h_ooff, d_ooff, (totals_out[1] + 1) * 8, hipMemcpyDeviceToHost));
+    *segs_out = h_segs; *read_offsets_out = h_boff; *ops_out = h_ops; *op_offsets_out = h_ooff; *reads_out = h_reads;
+    h_segs = nullptr; h_boff = nullptr; h_ops = nullptr; h_ooff = nullptr; h_reads = nullptr;
+done:
+#undef MAP_TRY
+    free(rel); free(h_segs); free(h_boff); free(h_ops); free(h_ooff); free(h_reads);
+    if (d_q) (void)hipFree(d_q);
+    if (d_off) (void)hipFree(d_off);
+    if (d_boff) (void)hipFree(d_boff);
+    if (d_segs) (void)hipFree(d_segs);
+    if (d_ops) (void)hipFree(d_ops);
+    if (d_ooff) (void)hipFree(d_ooff);
+    if (d_ws) (void)hipFree(d_ws);
+    if (d_reads) (void)hipFree(d_reads);
     return rc;
 }
 

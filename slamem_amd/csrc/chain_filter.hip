@@ -359,15 +359,32 @@ void chain_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem
     *boff_out = reinterpret_cast<uint64_t*>(p + m.off_boff);
 }
 
-int chain_filter(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, slamem_mem* out_mems, uint64_t* out_boff,
-                 uint32_t* out_scores, unsigned long long* host_scalars, hipStream_t stream) {
+ChainBufs chain_buffers(void* ws, uint64_t num_blocks, uint64_t capacity) {
+    const ChainLayout m = chain_layout(num_blocks, capacity);
+    char* p = static_cast<char*>(ws);
+    ChainBufs b;
+    b.ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
+    b.rows = reinterpret_cast<slamem_mem*>(p + m.off_rows);
+    b.boff = reinterpret_cast<uint64_t*>(p + m.off_boff);
+    b.cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
+    b.keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
+    b.score = reinterpret_cast<uint32_t*>(p + m.off_score);
+    b.list = reinterpret_cast<uint64_t*>(p + m.off_list);
+    b.scan = p + m.off_scan;
+    b.scan_bytes = m.scan_bytes;
+    b.lane_max = kChainLaneMax;
+    b.wave_grid = kChainWaveGrid;
+    return b;
+}
+
+// the DP and the backtrack: keep flags, kept rows and score per block
+int chain_pass(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, uint32_t* out_scores, hipStream_t stream) {
     const ChainLayout m = chain_layout(num_blocks, capacity);
     char* p = static_cast<char*>(ws);
     unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
     const slamem_mem* rows = reinterpret_cast<const slamem_mem*>(p + m.off_rows);
     const uint64_t* boff = reinterpret_cast<const uint64_t*>(p + m.off_boff);
     uint32_t* cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
-    uint64_t* newoff = reinterpret_cast<uint64_t*>(p + m.off_newoff);
     uint8_t* keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
     uint32_t* f = reinterpret_cast<uint32_t*>(p + m.off_f);
     uint32_t* pred = reinterpret_cast<uint32_t*>(p + m.off_pred);
@@ -380,6 +397,21 @@ int chain_filter(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_
     hipLaunchKernelGGL(k_chain_wave, dim3(kChainWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)ctr,
                        boff, rows, capacity, max_gap, keep, f, pred, cnt, score, ctr);
     CSTEP(hipGetLastError(), "k_chain_wave");
+    return SLAMEM_OK;
+}
+
+// the kept rows of chain_pass, in their order, with new block offsets
+int chain_compact(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem* out_mems, uint64_t* out_boff,
+                  unsigned long long* host_scalars, hipStream_t stream) {
+    const ChainLayout m = chain_layout(num_blocks, capacity);
+    char* p = static_cast<char*>(ws);
+    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
+    const slamem_mem* rows = reinterpret_cast<const slamem_mem*>(p + m.off_rows);
+    const uint64_t* boff = reinterpret_cast<const uint64_t*>(p + m.off_boff);
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
+    uint64_t* newoff = reinterpret_cast<uint64_t*>(p + m.off_newoff);
+    uint8_t* keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
+    uint64_t* list = reinterpret_cast<uint64_t*>(p + m.off_list);
     size_t need = m.scan_bytes;
     CSTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, cnt, newoff, num_blocks, stream), "scan");
     hipLaunchKernelGGL(k_chain_copy, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity,
@@ -393,6 +425,13 @@ int chain_filter(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_
     CSTEP(hipMemcpyAsync(host_scalars, newoff + num_blocks, 8, hipMemcpyDeviceToHost, stream), "memcpy");
     CSTEP(hipMemcpyAsync(host_scalars + 1, ctr + 1, 8, hipMemcpyDeviceToHost, stream), "memcpy");
     return SLAMEM_OK;
+}
+
+int chain_filter(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, slamem_mem* out_mems, uint64_t* out_boff,
+                 uint32_t* out_scores, unsigned long long* host_scalars, hipStream_t stream) {
+    const int rc = chain_pass(ws, num_blocks, capacity, max_gap, out_scores, stream);
+    if (rc != SLAMEM_OK) return rc;
+    return chain_compact(ws, num_blocks, capacity, out_mems, out_boff, host_scalars, stream);
 }
 #undef CSTEP
 

@@ -334,6 +334,27 @@ uint64_t chain_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
 void chain_list_buffers(void* chain_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
 int chain_filter(void* chain_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, slamem_mem* out_mems, uint64_t* out_boff,
                  uint32_t* out_scores, unsigned long long* host_scalars, hipStream_t stream);
+// (chain_filter = chain_pass + chain_compact.  -paf runs them apart: between the two it scores the rows the chain left and
+// clears the kept count of the blocks it drops.  chain_buffers: the parts of the workspace it reads and writes for that --
+// cnt[num_blocks] is 0, score is the workspace's own column, lane_max the rows of a block a lane handles, wave_grid the grid of
+// the wave kernels that share `list`, ctr[0] its length)
+struct ChainBufs {
+    unsigned long long* ctr;
+    slamem_mem* rows;
+    uint64_t* boff;
+    uint32_t* cnt;
+    uint8_t* keep;
+    uint32_t* score;
+    uint64_t* list;
+    void* scan;
+    size_t scan_bytes;
+    uint32_t lane_max;
+    unsigned wave_grid;
+};
+ChainBufs chain_buffers(void* chain_ws, uint64_t num_blocks, uint64_t capacity);
+int chain_pass(void* chain_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, uint32_t* out_scores, hipStream_t stream);
+int chain_compact(void* chain_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem* out_mems, uint64_t* out_boff,
+                  unsigned long long* host_scalars, hipStream_t stream);
 // -ext (ext_filter.hip): the same three for the ungapped X-drop extension of every row (penalty >= 1, xdrop >= 0; the batch's
 // letters and the text planes of the index are what it compares; out_mm: a uint32 per kept row, or nullptr; host_scalars as for
 // -smem).  In find_mems_device the per-row column travels in block_scores_dev.
@@ -356,12 +377,28 @@ struct AlnArgs {
     uint32_t* ops;
     uint64_t ops_capacity;
     uint64_t* op_offsets;  // segs_capacity + 1
+    slamem_map* reads;     // -paf: a record per read (then block_offsets_dev takes num_queries + 1 read offsets); nullptr: -aln
 };
 uint64_t aln_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
                              uint32_t max_edits);
 void aln_list_buffers(void* aln_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
 int aln_filter(void* aln_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
                uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff,
+               unsigned long long* host_scalars, hipStream_t stream);
+// (aln_filter = chain_filter into aln_chain_buffers + aln_after_chain, which -paf runs behind its own choice of chains)
+void aln_chain_buffers(void* aln_ws, uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity,
+                       const AlnArgs& args, slamem_mem** crows_out, uint64_t** coff_out);
+int aln_after_chain(void* aln_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
+                    uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff,
+                    unsigned long long* host_scalars, hipStream_t stream);
+// -paf (map_filter.hip, match type 7): one mapping per read.  The chain pass, a second chain pass over the rows it left (scores
+// only), a lane per read that picks the primary strand block, computes the quality and empties the other block, then -aln's
+// kernels over the primaries and the fold of block offsets to read offsets.  The workspace starts with -aln's.  args.reads is
+// not null; out_roff: num_queries + 1; host_scalars as for -aln.
+uint64_t map_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
+                             uint32_t max_edits);
+int map_filter(void* map_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
+               uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_roff,
                unsigned long long* host_scalars, hipStream_t stream);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)

@@ -3569,8 +3569,10 @@ struct SearchJob {
     uint32_t* mism_dev = nullptr;
     // -aln: as -ext, with aln_filter.hip behind K9; alnargs: where the segments and operations go, every value resolved (set
     // before init, which sizes the workspace by it); h_scal [9] segments, [10] a block out of order + 1, [11] operations
-    bool aln = false;
-    AlnArgs alnargs = {0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr};
+    // -paf (match type 7): -aln with map_filter.hip in aln_filter's place; alnargs.reads takes the read records, and the
+    // caller's offsets are per read
+    bool aln = false, map = false;
+    AlnArgs alnargs = {0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr, nullptr};
     uint64_t aln_totals[3] = {0, 0, 0};
     unsigned long long scal_own[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t k8_wave_cap = 0;  // waves of this batch's K8 (0: as many as the chip holds); a pipeline that keeps two K8 launches in flight gives each a part of the chip
@@ -3613,8 +3615,8 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
     min_len = min_len_; both_strands = both_strands_; match_type = match_type_; mems_dev = mems_dev_; mems_capacity = mems_capacity_;
     block_offsets_dev = block_offsets_dev_; workspace_dev = workspace_dev_; workspace_bytes = workspace_bytes_;
     total = 0; nitems = 0; prefiltered = false; timed_k8 = false; launched = false;
-    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false; chain = false; ext = false; aln = false;
-    if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity && match_type_ != 6) || (!queries_dev && num_queries)) {
+    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false; chain = false; ext = false; aln = false; map = false;
+    if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity && match_type_ != 6 && match_type_ != 7) || (!queries_dev && num_queries)) {
         set_error("slamem_find_mems_device: null argument");
         return SLAMEM_ERR_ARG;
     }
@@ -3671,8 +3673,19 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         }
         ext = true;
         match_type = 0;
-    } else if (match_type == 6) {
+    } else if (match_type == 6 || match_type == 7) {
         // -aln: the -mem search, then the filter (aln_filter.hip), which compares the reads with the text planes of the index
+        // -paf: the same with map_filter.hip, which chooses one strand block per read first
+        if (match_type == 7 && (idx->hdr.off_tpl == 0 || !idx->view.tpl)) {
+            set_error("slamem_find_maps_device: -paf needs the text planes of the index, and this index has none (%s layout%s); "
+                      "build it in the full layout with the seed sections", idx->hdr.layout == 2u ? "compact" : "full",
+                      idx->hdr.layout == 2u ? "" : ", built without the seed sections");
+            return SLAMEM_ERR_ARG;
+        }
+        if (match_type == 7 && !alnargs.reads && num_queries) {
+            set_error("slamem_find_maps_device: null argument");
+            return SLAMEM_ERR_ARG;
+        }
         if (idx->hdr.off_tpl == 0 || !idx->view.tpl) {
             set_error("slamem_find_alns_device: -aln needs the text planes of the index, and this index has none (%s layout%s); "
                       "build it in the full layout with the seed sections", idx->hdr.layout == 2u ? "compact" : "full",
@@ -3689,12 +3702,15 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
             return SLAMEM_ERR_ARG;
         }
         aln = true;
+        map = match_type == 7;
         match_type = 0;
     }
     const uint64_t need_ws = mum ? w.bytes + mum_workspace_bytes(num_blocks, mems_capacity)
                                  : smem ? w.bytes + smem_workspace_bytes(num_blocks, mems_capacity)
                                  : chain ? w.bytes + chain_workspace_bytes(num_blocks, mems_capacity)
                                  : ext ? w.bytes + ext_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity)
+                                 : map ? w.bytes + map_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity,
+                                                                       alnargs.ops_capacity, alnargs.max_edits)
                                  : aln ? w.bytes + aln_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity,
                                                                        alnargs.ops_capacity, alnargs.max_edits) : w.bytes;
     if (workspace_bytes < need_ws) {
@@ -4274,8 +4290,10 @@ int SearchJob::place(hipStream_t stream) {
         (void)hipEventRecord(ev_mum[1], stream);
     } else if (aln) {  // -aln: likewise; three scalars
         (void)hipEventRecord(ev_mum[0], stream);
-        int rc = aln_filter(mum_ws, idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity, alnargs,
-                            out_boff, h_scal + 9, stream);
+        int rc = map ? map_filter(mum_ws, idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity,
+                                  alnargs, out_boff, h_scal + 9, stream)
+                     : aln_filter(mum_ws, idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity, alnargs,
+                                  out_boff, h_scal + 9, stream);
         if (rc != SLAMEM_OK) return rc;
         (void)hipEventRecord(ev_mum[1], stream);
     }
@@ -4404,8 +4422,9 @@ int SearchJob::collect() {
     } else if (aln && !saw_long) {
         if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
         if (h_scal[10]) {
-            set_error("slamem_find_alns_device: the -mem rows of strand block %llu are not in the emission order (query start "
-                      "descending, then length non-increasing); no alignments returned", h_scal[10] - 1ull);
+            set_error("%s: the -mem rows of strand block %llu are not in the emission order (query start "
+                      "descending, then length non-increasing); no alignments returned",
+                      map ? "slamem_find_maps_device" : "slamem_find_alns_device", h_scal[10] - 1ull);
             total = 0;
             return SLAMEM_ERR_ARG;
         }
@@ -4413,8 +4432,8 @@ int SearchJob::collect() {
         aln_totals[1] = h_scal[9];
         aln_totals[2] = h_scal[11];
         if (aln_totals[1] > alnargs.segs_capacity || aln_totals[2] > alnargs.ops_capacity) {
-            set_error("slamem_find_alns_device: %llu segments with %llu operations, the capacities are %llu and %llu",
-                      (unsigned long long)aln_totals[1], (unsigned long long)aln_totals[2],
+            set_error("%s: %llu segments with %llu operations, the capacities are %llu and %llu",
+                      map ? "slamem_find_maps_device" : "slamem_find_alns_device", (unsigned long long)aln_totals[1], (unsigned long long)aln_totals[2],
                       (unsigned long long)alnargs.segs_capacity, (unsigned long long)alnargs.ops_capacity);
             return SLAMEM_ERR_CAPACITY;
         }

@@ -68,6 +68,10 @@ struct Slot {
     uint32_t* h_ops = nullptr;
     uint64_t* h_ooff = nullptr;
     uint64_t ops_cap = 0, h_segs_cap = 0, h_ops_cap = 0, ops_total = 0;
+    // -paf: a record per read (room for cap_q), on the device and in pinned host memory
+    slamem_map* d_reads = nullptr;
+    slamem_map* h_reads = nullptr;
+    uint64_t h_reads_cap = 0;
     // the batch
     uint64_t seq = 0;
     const char* chars = nullptr;
@@ -139,6 +143,9 @@ namespace {
 // Buffers are allocated by the stage that uses them, on a slot's first batch (and again if a batch needs more room):
 // setting a stream up costs nothing, the allocations (pinned host memory above all: ~0.1 ms per MB) overlap with the
 // other stages' work, and slots that are never used are never allocated.
+// -aln and -paf share the segments' buffers, capacities and setters; -paf adds the read records and has offsets per read
+inline bool is_aln(const slamem_stream* s) { return s->match_type == 6 || s->match_type == 7; }
+
 int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search stage: device output + workspace
     if (sl.d_mems) (void)hipFree(sl.d_mems);
     if (sl.d_ws) (void)hipFree(sl.d_ws);
@@ -146,14 +153,16 @@ int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search sta
     sl.d_mems = nullptr; sl.d_ws = nullptr; sl.d_mm = nullptr;
     sl.cap = need_cap;
     sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, s->match_type);
-    if (s->match_type == 6) {
+    if (is_aln(s)) {
         if (sl.d_segs) (void)hipFree(sl.d_segs);
         if (sl.d_ops) (void)hipFree(sl.d_ops);
         if (sl.d_ooff) (void)hipFree(sl.d_ooff);
         sl.d_segs = nullptr; sl.d_ops = nullptr; sl.d_ooff = nullptr;
         if (sl.ops_cap < 2 * sl.cap + 1024) sl.ops_cap = 2 * sl.cap + 1024;  // (a first guess; SLAMEM_ERR_CAPACITY tells the need)
+        const uint64_t nbq = (uint64_t)sl.cap_q * (s->both ? 2u : 1u);
         sl.ws_bytes = find_mems_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap) +
-                      aln_workspace_bytes(sl.cap_q, (uint64_t)sl.cap_q * (s->both ? 2u : 1u), sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits);
+                      (s->match_type == 7 ? map_workspace_bytes(sl.cap_q, nbq, sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits)
+                                          : aln_workspace_bytes(sl.cap_q, nbq, sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_segs), (sl.cap + 1) * sizeof(slamem_aln)));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ops), (sl.ops_cap + 1) * 4));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ooff), (sl.cap + 2) * 8));
@@ -295,13 +304,16 @@ int stage_upload(slamem_stream* s, Slot& sl) {
         if (sl.d_ws) (void)hipFree(sl.d_ws);
         if (sl.d_mm) (void)hipFree(sl.d_mm);
         if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
+        if (sl.d_reads) (void)hipFree(sl.d_reads);
         sl.d_ucnt = nullptr;
         sl.d_mm = nullptr;
+        sl.d_reads = nullptr;
         sl.d_q = nullptr; sl.d_off = nullptr; sl.d_boff = nullptr; sl.d_mems = nullptr; sl.d_ws = nullptr;  // (the prepare stage sizes its own)
         sl.cap_chars = 0; sl.cap_q = 0;  // until all three are there: a failed allocation must not leave stale room behind
         SLAMEM_HIP(hipMalloc(&sl.d_q, nchars + 2 * kFront + 32));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_off), ((uint64_t)nrec + 1) * 8));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_boff), (nb + 1) * 8));
+        if (s->match_type == 7) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_reads), ((uint64_t)nrec + 1) * sizeof(slamem_map)));
         sl.cap_chars = nchars;
         sl.cap_q = nrec;
     }
@@ -351,7 +363,7 @@ int job_setup(slamem_stream* s, Slot& sl) {
     if (!sl.ev_done) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
     if (!sl.ev_k8) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_k8, hipEventDisableTiming));
     if (!sl.h_scal) SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_scal), 16 * sizeof(unsigned long long), hipHostMallocDefault));
-    if (s->match_type == 6) {
+    if (is_aln(s)) {
         AlnArgs a;
         a.max_gap = s->max_gap ? s->max_gap : kChainDefaultGap;
         a.penalty = s->ext_penalty ? s->ext_penalty : kExtDefaultPenalty;
@@ -360,6 +372,7 @@ int job_setup(slamem_stream* s, Slot& sl) {
         a.segs = sl.d_segs; a.segs_capacity = sl.cap;
         a.ops = sl.d_ops; a.ops_capacity = sl.ops_cap;
         a.op_offsets = sl.d_ooff;
+        a.reads = s->match_type == 7 ? sl.d_reads : nullptr;
         search_job_aln(sl.job, a);
     }
     int rc = search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, s->match_type,
@@ -451,11 +464,11 @@ int stage_download(slamem_stream* s, Slot& sl) {
     SLAMEM_HIP(hipEventSynchronize(sl.ev_done));
     int rc = search_job_collect(sl.job, &sl.total);
     uint64_t at[3] = {0, 0, 0};  // -aln: -mem rows, segments, operations
-    if (s->match_type == 6) search_job_aln_totals(sl.job, at);
+    if (is_aln(s)) search_job_aln_totals(sl.job, at);
     for (int attempt = 0; rc == SLAMEM_ERR_CAPACITY && (sl.total > sl.cap || at[2] > sl.ops_cap) &&
-                          attempt < (s->match_type == 6 ? 3 : 2); attempt++) {  // (-aln: the rows may not fit, then the operations)
+                          attempt < (is_aln(s) ? 3 : 2); attempt++) {  // (-aln: the rows may not fit, then the operations)
         // rare (the first guess was too small): more room, and the batch once more, start to end, on this stage's stream
-        if (s->match_type == 6) {
+        if (is_aln(s)) {
             if (at[2] > sl.ops_cap) sl.ops_cap = at[2] + at[2] / 8 + 1024;
             rc = grow_outputs(s, sl, at[0] > sl.cap ? at[0] + at[0] / 8 + 1024 : sl.cap);
         } else
@@ -466,7 +479,7 @@ int stage_download(slamem_stream* s, Slot& sl) {
         if (rc == SLAMEM_OK) rc = search_job_search(sl.job, st);
         SLAMEM_HIP(hipStreamSynchronize(st));
         if (rc == SLAMEM_OK) rc = search_job_collect(sl.job, &sl.total);
-        if (s->match_type == 6) search_job_aln_totals(sl.job, at);
+        if (is_aln(s)) search_job_aln_totals(sl.job, at);
     }
     sl.ops_total = at[2];
     if (rc == SLAMEM_OK) rc = search_job_finish(sl.job, st, &sl.total);  // -mum: a batch with a large block
@@ -492,9 +505,9 @@ int stage_download(slamem_stream* s, Slot& sl) {
         SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_mems), sl.cap * sizeof(slamem_mem) + 16, hipHostMallocDefault));
         sl.h_cap = sl.cap;
     }
-    if (sl.total && s->match_type != 6)
+    if (sl.total && !is_aln(s))
         SLAMEM_HIP(hipMemcpyAsync(sl.h_mems, sl.d_mems, sl.total * sizeof(slamem_mem), hipMemcpyDeviceToHost, st));
-    if (s->match_type == 6) {  // (sl.total: the segments)
+    if (is_aln(s)) {  // (sl.total: the segments)
         if (sl.h_segs_cap < sl.cap || !sl.h_segs) {
             if (sl.h_segs) (void)hipHostFree(sl.h_segs);
             if (sl.h_ooff) (void)hipHostFree(sl.h_ooff);
@@ -522,6 +535,16 @@ int stage_download(slamem_stream* s, Slot& sl) {
         }
         if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_mm, sl.d_mm, sl.total * 4, hipMemcpyDeviceToHost, st));
     }
+    if (s->match_type == 7) {  // (the offsets are per read)
+        if (sl.h_reads_cap < sl.cap_q || !sl.h_reads) {
+            if (sl.h_reads) (void)hipHostFree(sl.h_reads);
+            sl.h_reads = nullptr;
+            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_reads), ((uint64_t)sl.cap_q + 1) * sizeof(slamem_map), hipHostMallocDefault));
+            sl.h_reads_cap = sl.cap_q;
+        }
+        if (sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_reads, sl.d_reads, (uint64_t)sl.nq * sizeof(slamem_map), hipMemcpyDeviceToHost, st));
+        SLAMEM_HIP(hipMemcpyAsync(sl.h_boff, sl.d_boff, ((uint64_t)sl.nq + 1) * 8, hipMemcpyDeviceToHost, st));
+    } else
     SLAMEM_HIP(hipMemcpyAsync(sl.h_boff, sl.d_boff, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
     SLAMEM_HIP(hipStreamSynchronize(st));
     return SLAMEM_OK;
@@ -583,6 +606,9 @@ void free_slot(Slot& sl) {
     if (sl.h_ops) (void)hipHostFree(sl.h_ops);
     if (sl.h_ooff) (void)hipHostFree(sl.h_ooff);
     sl.d_segs = nullptr; sl.d_ops = nullptr; sl.d_ooff = nullptr; sl.h_segs = nullptr; sl.h_ops = nullptr; sl.h_ooff = nullptr;
+    if (sl.d_reads) (void)hipFree(sl.d_reads);
+    if (sl.h_reads) (void)hipHostFree(sl.h_reads);
+    sl.d_reads = nullptr; sl.h_reads = nullptr;
     if (sl.d_planes) (void)hipFree(sl.d_planes);
     if (sl.d_other) (void)hipFree(sl.d_other);
     if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
@@ -700,8 +726,8 @@ int slamem_stream_destroy(slamem_stream* s) {
 
 int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream** out) {
-    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 6)) {
-        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 6)");
+    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 7)) {
+        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 7)");
         return SLAMEM_ERR_ARG;
     }
     *out = nullptr;
@@ -792,7 +818,7 @@ int slamem_stream_set_max_occ(slamem_stream* s, uint32_t max_occ) {
 int slamem_stream_set_max_gap(slamem_stream* s, uint32_t max_gap) {
     if (!s) { set_error("slamem_stream_set_max_gap: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
-    if (s->match_type != 4 && s->match_type != 6 && max_gap != 0) {
+    if (s->match_type != 4 && !is_aln(s) && max_gap != 0) {
         set_error("slamem_stream_set_max_gap: a maximum gap needs match type 4 (-chain)");
         return SLAMEM_ERR_ARG;
     }
@@ -811,7 +837,7 @@ int slamem_stream_set_max_gap(slamem_stream* s, uint32_t max_gap) {
 int slamem_stream_set_ext_params(slamem_stream* s, uint32_t mismatch_penalty, uint32_t xdrop) {
     if (!s) { set_error("slamem_stream_set_ext_params: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
-    if (s->match_type != 5 && s->match_type != 6 && (mismatch_penalty != 0 || xdrop != kExtXdropUnset)) {
+    if (s->match_type != 5 && !is_aln(s) && (mismatch_penalty != 0 || xdrop != kExtXdropUnset)) {
         set_error("slamem_stream_set_ext_params: a mismatch penalty or an X-drop needs match type 5 (-ext)");
         return SLAMEM_ERR_ARG;
     }
@@ -827,7 +853,7 @@ int slamem_stream_set_ext_params(slamem_stream* s, uint32_t mismatch_penalty, ui
 int slamem_stream_set_max_edits(slamem_stream* s, uint32_t max_edits) {
     if (!s) { set_error("slamem_stream_set_max_edits: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
-    if (s->match_type != 6 && max_edits != kAlnEditsUnset) {
+    if (!is_aln(s) && max_edits != kAlnEditsUnset) {
         set_error("slamem_stream_set_max_edits: an edit limit needs match type 6 (-aln)");
         return SLAMEM_ERR_ARG;
     }
@@ -848,7 +874,7 @@ int slamem_stream_alns(slamem_stream* s, const slamem_aln** segs_out, const uint
     if (!s || !segs_out || !ops_out || !op_offsets_out || !num_ops_out) { set_error("slamem_stream_alns: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
     *segs_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr; *num_ops_out = 0;
-    if (s->match_type != 6) { set_error("slamem_stream_alns: the stream's match type is not 6 (-aln)"); return SLAMEM_ERR_ARG; }
+    if (!is_aln(s)) { set_error("slamem_stream_alns: the stream's match type is not 6 (-aln)"); return SLAMEM_ERR_ARG; }
     if (s->returned == 0) { set_error("slamem_stream_alns: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
     Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
     if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
@@ -856,6 +882,21 @@ int slamem_stream_alns(slamem_stream* s, const slamem_aln** segs_out, const uint
         return SLAMEM_ERR_ARG;
     }
     *segs_out = sl.h_segs; *ops_out = sl.h_ops; *op_offsets_out = sl.h_ooff; *num_ops_out = sl.ops_total;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_maps(slamem_stream* s, const slamem_map** reads_out) {
+    if (!s || !reads_out) { set_error("slamem_stream_maps: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    *reads_out = nullptr;
+    if (s->match_type != 7) { set_error("slamem_stream_maps: the stream's match type is not 7 (-paf)"); return SLAMEM_ERR_ARG; }
+    if (s->returned == 0) { set_error("slamem_stream_maps: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
+    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
+    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
+        set_error("slamem_stream_maps: the batch slamem_stream_next returned last has no reads to show");
+        return SLAMEM_ERR_ARG;
+    }
+    *reads_out = sl.h_reads;
     return SLAMEM_OK;
 }
 

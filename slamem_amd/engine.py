@@ -17,8 +17,19 @@ from . import capi
 
 MEM_DTYPE = np.dtype([("ref_pos", "<u4"), ("query_pos", "<u4"), ("length", "<u4")])
 ALN_DTYPE = np.dtype([("ref_pos", "<u4"), ("query_pos", "<u4"), ("ref_len", "<u4"), ("query_len", "<u4"), ("edits", "<u4")])
+MAP_DTYPE = np.dtype([("strand", "u1"), ("mapq", "u1"), ("s1", "<u4"), ("s2", "<u4")])  # strand: 0 unmapped, 1 forward, 2 reverse
+_MAP_ABI = np.dtype([("s1", "<u4"), ("s2", "<u4"), ("strand", "u1"), ("mapq", "u1"), ("reserved", "u1", (2,))])  # slamem_map
 EDITS_DEFAULT = 0xFFFFFFFF  # SLAMEM_ALN_EDITS_DEFAULT: "the default 31" in the C ABI (0 is a value of its own)
 CIGAR_OPS = {7: "=", 8: "X", 1: "I", 2: "D"}  # BAM's codes; an operation is length << 4 | code
+
+
+def _map_records(raw: np.ndarray) -> np.ndarray:
+    """slamem_map records (bytes) -> MAP_DTYPE"""
+    a = raw.view(_MAP_ABI).reshape(-1)
+    out = np.zeros(a.shape[0], dtype=MAP_DTYPE)
+    for k in ("strand", "mapq", "s1", "s2"):
+        out[k] = a[k]
+    return out
 
 
 def _ptr(t: torch.Tensor) -> int:
@@ -233,6 +244,19 @@ class Index:
         and xdrop as for find_chains and find_exts; max_edits: the most edits in one gap (None: 31; at most 127).
         capacities: (mems, segments, operations) to run with exactly that room (slamem.capi.SlamemError with
         SLAMEM_ERR_CAPACITY and .totals = what is needed when it is too small); None: grow until the batch fits."""
+        return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, False)
+
+    def map_reads(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
+                  xdrop=None, max_edits=None, capacities=None):
+        """-paf mode: (segments, read_offsets, ops, op_offsets, reads) -- one mapping per read.  Per read the
+        strand block whose best chain scores highest is the primary one (the forward block on a tie) and only that block is
+        aligned, as find_alns aligns it; segments, ops and op_offsets are as find_alns returns them, in the coordinates of the
+        scanned strand; read_offsets: the segments' offsets per READ (len(offsets) entries); reads: a structured array (strand,
+        mapq, s1, s2) per read -- strand 0 unmapped, 1 forward, 2 reverse; s1 the primary chain's score, s2 the best competing
+        chain's; mapq = 60 * (s1 - s2) // s1.  The other arguments as for find_alns."""
+        return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, True)
+
+    def _aln_like(self, queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, mapping):
         dev = self.device
         q = np.ascontiguousarray(np.frombuffer(queries, dtype=np.uint8) if isinstance(queries, (bytes, bytearray))
                                  else queries, dtype=np.uint8)
@@ -247,10 +271,12 @@ class Index:
         edits = EDITS_DEFAULT if max_edits is None else int(max_edits)
         cap, scap, ocap = capacities if capacities is not None else (max(1024, q.shape[0] // 8 + 4 * num), nb + 1024, 4 * nb + 4096)
         L = capi.lib()
-        boff = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+        boff = torch.zeros((num if mapping else nb) + 1, dtype=torch.int64, device=dev)
+        recs = torch.zeros((num + 1) * 12, dtype=torch.uint8, device=dev) if mapping else None
+        ws_bytes = L.slamem_find_maps_workspace_bytes if mapping else L.slamem_find_alns_workspace_bytes
         while True:
             need = C.c_uint64()
-            capi.check(L.slamem_find_alns_workspace_bytes(num, int(both_strands), qbytes, cap, ocap, edits, C.byref(need)))
+            capi.check(ws_bytes(num, int(both_strands), qbytes, cap, ocap, edits, C.byref(need)))
             ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
             segs = torch.zeros((scap + 1) * 5, dtype=torch.int32, device=dev)
             ops = torch.zeros(ocap + 1, dtype=torch.int32, device=dev)
@@ -258,9 +284,15 @@ class Index:
             totals = (C.c_uint64 * 3)()
             with torch.cuda.device(dev):
                 torch.cuda.current_stream(dev).synchronize()
-                rc = L.slamem_find_alns_device(self._h, _ptr(qd), _ptr(od), num, qbytes, int(min_len), int(both_strands), int(max_gap),
-                                               int(penalty), _xdrop_arg(xdrop), edits, cap, _ptr(segs), scap, _ptr(boff), _ptr(ops),
-                                               ocap, _ptr(ooff), _ptr(ws), need.value, None, totals)
+                if mapping:
+                    rc = L.slamem_find_maps_device(self._h, _ptr(qd), _ptr(od), num, qbytes, int(min_len), int(both_strands),
+                                                   int(max_gap), int(penalty), _xdrop_arg(xdrop), edits, cap, _ptr(segs), scap,
+                                                   _ptr(boff), _ptr(ops), ocap, _ptr(ooff), _ptr(recs), _ptr(ws), need.value, None,
+                                                   totals)
+                else:
+                    rc = L.slamem_find_alns_device(self._h, _ptr(qd), _ptr(od), num, qbytes, int(min_len), int(both_strands),
+                                                   int(max_gap), int(penalty), _xdrop_arg(xdrop), edits, cap, _ptr(segs), scap,
+                                                   _ptr(boff), _ptr(ops), ocap, _ptr(ooff), _ptr(ws), need.value, None, totals)
             if rc == capi.SLAMEM_ERR_CAPACITY and capacities is None:
                 cap, scap, ocap = max(cap, int(totals[0])), max(scap, int(totals[1])), max(ocap, int(totals[2]))
                 continue
@@ -271,8 +303,9 @@ class Index:
             break
         nseg, nops = int(totals[1]), int(totals[2])
         out = segs[: nseg * 5].cpu().numpy().view(np.uint32).reshape(-1, 5).copy().view(ALN_DTYPE).reshape(-1)
-        return (out, boff.cpu().numpy().view(np.uint64), ops[:nops].cpu().numpy().view(np.uint32),
-                ooff[: nseg + 1].cpu().numpy().view(np.uint64))
+        res = (out, boff.cpu().numpy().view(np.uint64), ops[:nops].cpu().numpy().view(np.uint32),
+               ooff[: nseg + 1].cpu().numpy().view(np.uint64))
+        return res + (_map_records(recs[: num * 12].cpu().numpy()),) if mapping else res
 
     def _find(self, queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap, ext=False, penalty=0,
               xdrop=None):
@@ -431,15 +464,17 @@ class Stream:
 
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
-                 max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None):
+                 max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False):
         """aln=True: -aln mode (match type 6); it takes max_gap, penalty, xdrop and max_edits and excludes the other modes.
-        next() then returns the segments (ALN_DTYPE) in the place of the rows, alns() their operations."""
-        if aln and (mam or mum or smem or chain or ext or max_occ):
-            raise ValueError("aln excludes mam, mum, smem, chain and ext: one match type per search")
-        if max_edits is not None and not aln:
-            raise ValueError("max_edits is the edit limit of aln: it needs aln=True")
-        self.aln = bool(aln)
-        match_type = 6 if aln else _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
+        next() then returns the segments (ALN_DTYPE) in the place of the rows, alns() their operations.  paf=True: -paf mode
+        (match type 7), the same with the offsets per READ and maps() the read records (MAP_DTYPE)."""
+        if (aln or paf) and (mam or mum or smem or chain or ext or max_occ or (aln and paf)):
+            raise ValueError("aln and paf exclude mam, mum, smem, chain, ext and each other: one match type per search")
+        if max_edits is not None and not (aln or paf):
+            raise ValueError("max_edits is the edit limit of aln and paf: it needs aln=True or paf=True")
+        self.paf = bool(paf)
+        self.aln = bool(aln or paf)
+        match_type = 7 if paf else 6 if aln else _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
         self.index = index
         self.both = bool(both_strands)
         self._h = C.c_void_p()
@@ -480,7 +515,7 @@ class Stream:
             self._keep.pop(0)
         capi.check(rc)
         self._last_total = int(total.value)
-        nb = nq.value * (2 if self.both else 1)
+        nb = nq.value * (1 if self.paf else 2 if self.both else 1)
         if self.aln:  # the segments stand in the place of the rows
             segs, ops, ooff, nops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
             capi.check(capi.lib().slamem_stream_alns(self._h, C.byref(segs), C.byref(ops), C.byref(ooff), C.byref(nops)))
@@ -490,6 +525,11 @@ class Stream:
             oo = np.ctypeslib.as_array((C.c_uint64 * (n + 1)).from_address(ooff.value))
             b = np.ctypeslib.as_array((C.c_uint64 * (nb + 1)).from_address(boff.value))
             self._last_alns = (o.copy(), oo.copy()) if copy else (o, oo)
+            if self.paf:
+                recs = C.c_void_p()
+                capi.check(capi.lib().slamem_stream_maps(self._h, C.byref(recs)))
+                raw = np.ctypeslib.as_array((C.c_uint8 * (12 * max(1, nq.value))).from_address(recs.value))[: 12 * nq.value]
+                self._last_maps = _map_records(raw)
             return (m.copy(), b.copy(), tm.as_dict()) if copy else (m, b, tm.as_dict())
         m = np.ctypeslib.as_array((C.c_uint8 * (12 * max(1, total.value))).from_address(mems.value))[: 12 * total.value]
         m = m.view(MEM_DTYPE)
@@ -501,6 +541,10 @@ class Stream:
     def alns(self):
         """-aln: (ops, op_offsets) of the batch next() returned last (slamem_stream_alns), as next() took them."""
         return self._last_alns
+
+    def maps(self):
+        """-paf: the read records (MAP_DTYPE) of the batch next() returned last (slamem_stream_maps), as next() took them."""
+        return self._last_maps
 
     def mismatches(self, copy: bool = True) -> np.ndarray:
         """-ext: the mismatches (uint32 per row) of the batch next() returned last (slamem_stream_mismatches).  copy=False

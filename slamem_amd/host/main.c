@@ -43,8 +43,8 @@
 #define VERSION "0.8.2"
 /* what the output lines call a match of each type: M%cM with the reference's "EAU" (slamem.c:35), SMEM for -smem,
  * "chained MEM" for the rows -chain keeps and "extended MEM" for the rows of -ext */
-static const char *const MATCH_TYPE_NAME[7] = {"MEM", "MAM", "MUM", "SMEM", "chained MEM", "extended MEM", "alignment"};
-#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 7 ? (t) : 0]
+static const char *const MATCH_TYPE_NAME[8] = {"MEM", "MAM", "MUM", "SMEM", "chained MEM", "extended MEM", "alignment", "mapping"};
+#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 8 ? (t) : 0]
 
 /* the device warm-up thread (see main) is joined before the process ends, whichever way it ends */
 static pthread_t g_warm_tid;
@@ -173,6 +173,7 @@ typedef struct {
     const slamem_aln *segs; /* -aln: the segments in the place of the rows (NULL otherwise), their operations and offsets */
     const uint32_t *ops;
     const uint64_t *ooff;
+    const slamem_map *reads; /* -paf: a record per read (NULL otherwise); the blocks are then the reads, strands = 1 */
     const uint64_t *boff;
     int first_rec, strands;
     uint64_t b0, b1; /* strand blocks [b0,b1) of the batch */
@@ -217,7 +218,10 @@ static void *fmt_run(void *arg) {
     for (b = j->b0; b < j->b1; b++) {
         int i = j->first_rec + (int)(b / (uint64_t)j->strands), s = (int)(b % (uint64_t)j->strands);
         uint64_t cnt = j->boff[b + 1] - j->boff[b], sum = 0;
-        if (j->segs ? slh_format_block_aln(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->segs + j->boff[b]), j->ops,
+        if (j->reads ? slh_format_read_paf(&j->buf, j->q->recs[i].name, j->q->recs[i].size, j->reads[b].strand, j->reads[b].mapq,
+                                           j->reads[b].s1, j->reads[b].s2, (const uint32_t *)(j->segs + j->boff[b]), j->ops,
+                                           j->ooff + j->boff[b], cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)
+            : j->segs ? slh_format_block_aln(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->segs + j->boff[b]), j->ops,
                                            j->ooff + j->boff[b], cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)
                     : slh_format_block_ext(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->mems + j->boff[b]),
                                  j->mism ? j->mism + j->boff[b] : NULL, cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)) {
@@ -584,6 +588,7 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-xdrop\twith -ext: stop when the score falls this far below its best (default=20)\n");
     printf("\t-aln\tgapped alignment of the best chain of each strand; writes ref_pos query_pos ref_len query_len edits cigar\n");
     printf("\t-maxed\twith -aln: most edits in the gap between two chained MEMs, 0 to 127 (default=31); -mgap, -pen, -xdrop apply\n");
+    printf("\t-paf\tone mapping per read with a mapping quality, written as PAF with a cg:Z: CIGAR; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
     printf("\t-b\tprocess both forward and reverse strands\n");
@@ -630,6 +635,7 @@ int main(int argc, char **argv) {
         return slh_clean_fasta(argv[2], stdout);
     }
     if (o.match_type < 0) { /* before any GPU work */
+        if (slh_parse_argument(argc, argv, "PA", 0)) exit_message("Option -paf excludes -mam, -mum, -smem, -chain, -ext and -aln");
         if (slh_parse_argument(argc, argv, "AL", 0)) exit_message("Option -aln excludes -mam, -mum, -smem, -chain and -ext");
         if (slh_parse_argument(argc, argv, "EX", 0)) exit_message("Option -ext excludes -mam, -mum, -smem and -chain");
         if (slh_parse_argument(argc, argv, "CH", 0)) exit_message("Option -chain excludes -mam, -mum and -smem");
@@ -643,17 +649,17 @@ int main(int argc, char **argv) {
     }
     switch (slh_parse_max_gap(argc, argv, &max_gap)) {
     case -1: exit_message("Option -mgap needs a whole number of at least 1"); break;
-    case 1: if (o.match_type != 4 && o.match_type != 6) exit_message("Option -mgap needs -chain"); break;
+    case 1: if (o.match_type != 4 && o.match_type != 6 && o.match_type != 7) exit_message("Option -mgap needs -chain"); break;
     default: break;
     }
     switch (slh_parse_ext_params(argc, argv, &ext_pen, &ext_xdrop)) {
     case -1: exit_message("Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"); break;
-    case 1: if (o.match_type != 5 && o.match_type != 6) exit_message("Options -pen and -xdrop need -ext"); break;
+    case 1: if (o.match_type != 5 && o.match_type != 6 && o.match_type != 7) exit_message("Options -pen and -xdrop need -ext"); break;
     default: break;
     }
     switch (slh_parse_max_edits(argc, argv, &max_edits)) {
     case -1: exit_message("Option -maxed needs a whole number from 0 to 127"); break;
-    case 1: if (o.match_type != 6) exit_message("Option -maxed needs -aln"); break;
+    case 1: if (o.match_type != 6 && o.match_type != 7) exit_message("Option -maxed needs -aln"); break;
     default: break;
     }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
@@ -761,7 +767,7 @@ int main(int argc, char **argv) {
     if (max_occ > 0) say(" ; maximum occurrences = %d", max_occ);
     if (o.match_type == 4) say(" ; maximum gap = %d", max_gap > 0 ? max_gap : 5000);
     if (o.match_type == 5) say(" ; mismatch penalty = %d ; X-drop = %d", ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20);
-    if (o.match_type == 6)
+    if (o.match_type == 6 || o.match_type == 7)
         say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", max_gap > 0 ? max_gap : 5000,
             ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
     say("\n");
@@ -850,7 +856,8 @@ int main(int argc, char **argv) {
     if (!g_mo) fflush(stdout);
 
     {
-        int strands = o.both_strands ? 2 : 1;
+        /* (-paf: what is formatted and counted is a read, whichever strand its mapping lies on) */
+        int strands = o.match_type == 7 ? 1 : o.both_strands ? 2 : 1;
         long printed = 0;
         /* the list of batches (records [first,last) of one query file each), then a pipeline over it: the GPUs search
            batches b+1.. (slamem_stream_*: upload, search and download of neighbouring batches overlap), the main thread
@@ -912,7 +919,7 @@ int main(int argc, char **argv) {
                 rc = slamem_stream_set_ext_params(g_streams[g], (uint32_t)ext_pen,
                                                   ext_xdrop >= 0 ? (uint32_t)ext_xdrop : SLAMEM_EXT_XDROP_DEFAULT);
             }
-            if (rc == SLAMEM_OK && o.match_type == 6) {
+            if (rc == SLAMEM_OK && (o.match_type == 6 || o.match_type == 7)) {
                 g_nstreams = g + 1;
                 rc = slamem_stream_set_max_gap(g_streams[g], (uint32_t)max_gap);
                 if (rc == SLAMEM_OK)
@@ -955,6 +962,7 @@ int main(int argc, char **argv) {
             const uint32_t *ops = NULL;
             const uint64_t *ooff = NULL;
             uint64_t nops = 0;
+            const slamem_map *reads = NULL;
             const uint64_t *boff = NULL;
             uint64_t total = 0;
             double tg = now_s();
@@ -981,9 +989,13 @@ int main(int argc, char **argv) {
                 rc = slamem_stream_mismatches(g_streams[bi % (size_t)ngpu], &mism);
                 if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("MEM extension on the GPU", rc); }
             }
-            if (o.match_type == 6) { /* the segments stand in the place of the rows */
+            if (o.match_type == 6 || o.match_type == 7) { /* the segments stand in the place of the rows */
                 rc = slamem_stream_alns(g_streams[bi % (size_t)ngpu], &segs, &ops, &ooff, &nops);
                 if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("alignment on the GPU", rc); }
+            }
+            if (o.match_type == 7) { /* ... and the offsets are per read */
+                rc = slamem_stream_maps(g_streams[bi % (size_t)ngpu], &reads);
+                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("mapping on the GPU", rc); }
             }
             inflight[bi % (size_t)ngpu]--;
             t_gpu += now_s() - tg; /* time the main thread waited for the GPUs */
@@ -998,7 +1010,10 @@ int main(int argc, char **argv) {
                 for (b = 0; b < bseq; b++) {
                     int ri = first + (int)(b / strands), sidx = (int)(b % strands), d, dots;
                     uint64_t cnt = boff[b + 1] - boff[b], sum = 0;
-                    if (segs ? slh_format_block_aln(&buf, q->recs[ri].name, sidx, (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b],
+                    if (reads ? slh_format_read_paf(&buf, q->recs[ri].name, q->recs[ri].size, reads[b].strand, reads[b].mapq, reads[b].s1,
+                                                    reads[b].s2, (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b], cnt, ref.recs,
+                                                    ref.merged_start, ref.num, &sum)
+                        : segs ? slh_format_block_aln(&buf, q->recs[ri].name, sidx, (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b],
                                                     cnt, ref.recs, ref.merged_start, ref.num, &sum)
                              : slh_format_block_ext(&buf, q->recs[ri].name, sidx, (const uint32_t *)(mems + boff[b]),
                                              mism ? mism + boff[b] : NULL, cnt, ref.recs, ref.merged_start, ref.num, &sum))
@@ -1029,7 +1044,7 @@ int main(int argc, char **argv) {
                     per = (nblk - bseq + (uint64_t)njobs - 1) / (uint64_t)njobs;
                     for (t = 0; t < njobs; t++) {
                         jobs[t].q = q; jobs[t].ref = &ref; jobs[t].mems = mems; jobs[t].mism = mism; jobs[t].boff = boff;
-                        jobs[t].segs = segs; jobs[t].ops = ops; jobs[t].ooff = ooff;
+                        jobs[t].segs = segs; jobs[t].ops = ops; jobs[t].ooff = ooff; jobs[t].reads = reads;
                         jobs[t].first_rec = first; jobs[t].strands = strands;
                         jobs[t].b0 = bseq + per * (uint64_t)t < nblk ? bseq + per * (uint64_t)t : nblk;
                         jobs[t].b1 = jobs[t].b0 + per < nblk ? jobs[t].b0 + per : nblk;

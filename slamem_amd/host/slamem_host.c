@@ -840,6 +840,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type != 0 ? -1 : 5;
     if (slh_parse_argument(argc, argv, "AL", 0)) /* -aln: the gapped alignment of the best chain (an 'a' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 6;
+    if (slh_parse_argument(argc, argv, "PA", 0)) /* -paf: one mapping per read, written as PAF (a 'p' option takes no value) */
+        o->match_type = o->match_type != 0 ? -1 : 7;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;
@@ -939,6 +941,57 @@ int slh_format_block_aln(slh_buffer *buf, const char *query_name, int reverse, c
         *p++ = '\n';
         buf->len = (size_t)(p - buf->data);
         sum += segs[5 * i + 3];
+    }
+    if (sum_len_out) *sum_len_out = sum;
+    return 0;
+}
+
+int slh_format_read_paf(slh_buffer *buf, const char *query_name, uint32_t query_len, int strand, uint32_t mapq, uint32_t s1,
+                        uint32_t s2, const uint32_t *segs, const uint32_t *ops, const uint64_t *op_off, uint64_t count,
+                        const slh_record *refs, const uint32_t *merged_start, int num_refs, uint64_t *sum_len_out) {
+    static const char OPC[16] = {'?', 'I', 'D', '?', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+    size_t nl = strcspn(query_name, " \t");
+    uint64_t i, k, sum = 0;
+    char *p;
+    if (sum_len_out) *sum_len_out = 0;
+    if (strand != 1 && strand != 2) return 0;
+    for (i = 0; i < count; i++) {
+        uint32_t rp = segs[5 * i], qs = segs[5 * i + 1], eq = 0, all = 0;
+        const uint32_t rlen = segs[5 * i + 2], qlen = segs[5 * i + 3];
+        const uint64_t nops = op_off[i + 1] - op_off[i];
+        const slh_record *rec = &refs[num_refs > 1 ? slh_seq_id_from_merged_pos(merged_start, num_refs, &rp) : 0];
+        const size_t namelen = strcspn(rec->name, " \t");
+        if (strand == 2) qs = query_len - qs - qlen;
+        for (k = op_off[i]; k < op_off[i + 1]; k++) {
+            all += ops[k] >> 4;
+            if ((ops[k] & 15u) == 7u) eq += ops[k] >> 4;
+        }
+        /* thirteen numbers of at most ten digits, tabs and tags, and eleven characters an operation */
+        if (buf_reserve(buf, nl + namelen + 192 + (size_t)nops * 11)) return -1;
+        p = buf->data + buf->len;
+        memcpy(p, query_name, nl);
+        p += nl;
+        *p++ = '\t'; p = put_u32(p, query_len);
+        *p++ = '\t'; p = put_u32(p, qs);
+        *p++ = '\t'; p = put_u32(p, qs + qlen);
+        *p++ = '\t'; *p++ = strand == 2 ? '-' : '+';
+        *p++ = '\t';
+        memcpy(p, rec->name, namelen);
+        p += namelen;
+        *p++ = '\t'; p = put_u32(p, rec->size);
+        *p++ = '\t'; p = put_u32(p, rp);
+        *p++ = '\t'; p = put_u32(p, rp + rlen);
+        *p++ = '\t'; p = put_u32(p, eq);
+        *p++ = '\t'; p = put_u32(p, all);
+        *p++ = '\t'; p = put_u32(p, mapq);
+        memcpy(p, "\tNM:i:", 6); p += 6; p = put_u32(p, segs[5 * i + 4]);
+        memcpy(p, "\ts1:i:", 6); p += 6; p = put_u32(p, s1);
+        memcpy(p, "\ts2:i:", 6); p += 6; p = put_u32(p, s2);
+        memcpy(p, "\tcg:Z:", 6); p += 6;
+        for (k = op_off[i]; k < op_off[i + 1]; k++) { p = put_u32(p, ops[k] >> 4); *p++ = OPC[ops[k] & 15u]; }
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+        sum += qlen;
     }
     if (sum_len_out) *sum_len_out = sum;
     return 0;

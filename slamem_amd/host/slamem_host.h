@@ -69,7 +69,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), -1 two of them */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa...), -1 two of them */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
@@ -117,6 +117,15 @@ int slh_format_block_ext(slh_buffer *buf, const char *query_name, int reverse, c
 int slh_format_block_aln(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *segs, const uint32_t *ops,
                          const uint64_t *op_off, uint64_t count, const slh_record *refs, const uint32_t *merged_start,
                          int num_refs, uint64_t *sum_len_out);
+/* A read of the -paf file (plain PAF, no header lines): one line per segment, in the segments' order,
+ *   name  read_len  qs  qe  +|-  record  record_len  ts  te  letters under =  all operation lengths  mapq  NM:i:  s1:i:  s2:i:  cg:Z:
+ * both names cut at the first blank or tab; qs, qe on the read as given (strand 2, the reverse strand: qs = read_len -
+ * query_pos - query_len); ts, te local to the record that holds the segment's first reference letter.  strand 0 (an unmapped
+ * read) and count 0 write nothing.  segs, ops, op_off as for slh_format_block_aln.  *sum_len_out: the query letters of the
+ * segments. */
+int slh_format_read_paf(slh_buffer *buf, const char *query_name, uint32_t query_len, int strand, uint32_t mapq, uint32_t s1,
+                        uint32_t s2, const uint32_t *segs, const uint32_t *ops, const uint64_t *op_off, uint64_t count,
+                        const slh_record *refs, const uint32_t *merged_start, int num_refs, uint64_t *sum_len_out);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
