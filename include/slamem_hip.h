@@ -438,6 +438,41 @@ int slamem_find_maps_device(const slamem_index *idx, const void *queries_dev, co
                             uint64_t ops_capacity, uint64_t *op_offsets_dev, slamem_map *reads_dev, void *workspace_dev,
                             uint64_t workspace_bytes, void *stream, uint64_t *totals_out);
 
+/* ---- (b'') per-base pileup of the read mappings (option -pile: matchType 8) ----------------------------------
+ * What a user does with -paf's mappings: pile them onto the reference.  With n the merged text's length the table has n rows of
+ * six uint32 counters in the order A, C, G, T, D, I.  A read contributes iff its record has strand != 0 and mapq >= min_mapq;
+ * then each of its segments is walked once, left to right, p from ref_pos and q from query_pos in the scanned strand: an = or X
+ * of k counts the scanned strand's letter (upper-cased; a letter that is none of A,C,G,T is counted nowhere) in its column at
+ * rows p .. p+k-1; a D of k counts in column D of rows p .. p+k-1; an I of k counts ONCE, in column I of row p (the insertion
+ * stands in front of reference letter p; at p == n it is dropped).  Depth at a row is A+C+G+T+D.  The table is the sum over all
+ * batches added since creation or the last reset: addition commutes, so it does not depend on how the reads were split into
+ * batches, on their order, on the stream or on the GPU.  Counters are 32 bits wide: a true depth of 2^31 or more at one row is
+ * outside the contract.
+ *
+ *   slamem_pileup_create   the accumulator lives on the index's device and takes 28 bytes per text letter (a difference array
+ *                          for the = runs, 4 bytes, and the table of what differs from the text, 24).  Too little free HBM:
+ *                          SLAMEM_ERR_NOMEM with the numbers in the message.  It reads the text planes of the index: an index
+ *                          without them (the COMPACT layout) is refused with SLAMEM_ERR_ARG.  The index must outlive it.
+ *   slamem_pileup_reset    all counters to 0 (waits for the device first)
+ *   slamem_pileup_add_device  takes the outputs of slamem_find_maps_device as they are, with the batch's queries and offsets.
+ *                          Asynchronous on `stream`; nothing is validated that would need a read-back (every write is checked
+ *                          against n on the device); min_mapq above 60: SLAMEM_ERR_ARG.  Adds from several streams and threads
+ *                          into one accumulator are safe: every update is an atomic add.
+ *   slamem_pileup_counts_device  rows [first, first + count) as count x 6 uint32, asynchronous on `stream`, ordered behind the
+ *                          adds of that stream.  The accumulator is not modified: more batches may be added and the table read
+ *                          again.  Two read-outs of one accumulator must not run at the same time (they share a small scratch).
+ *                          A range outside [0, n]: SLAMEM_ERR_ARG.
+ *   slamem_pileup_counts_host  the same into host memory; waits for the device first, so it sees the adds of every stream. */
+typedef struct slamem_pileup slamem_pileup;
+int slamem_pileup_create(const slamem_index *idx, slamem_pileup **out);
+int slamem_pileup_free(slamem_pileup *pile);
+int slamem_pileup_reset(slamem_pileup *pile);
+int slamem_pileup_add_device(slamem_pileup *pile, const void *queries_dev, const uint64_t *offsets_dev, uint32_t num_queries,
+                             const slamem_aln *segs_dev, const uint64_t *read_offsets_dev, const uint32_t *ops_dev,
+                             const uint64_t *op_offsets_dev, const slamem_map *reads_dev, uint32_t min_mapq, void *stream);
+int slamem_pileup_counts_device(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t *out_dev, void *stream);
+int slamem_pileup_counts_host(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t *out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -492,7 +527,18 @@ void slamem_host_free(void *p);
  *                          its total, the number of segments -- its rows pointer is not to be read; the segments, operations
  *                          and operation offsets come through slamem_stream_alns), 7 = mapping (-paf: as 6 with the offsets
  *                          per READ, num_queries + 1 of them, and a record per read through slamem_stream_maps; it takes the
- *                          setters of 6)
+ *                          setters of 6), 8 = pileup (-pile: every batch goes the way of 7 and is then added to the accumulator
+ *                          given with slamem_stream_set_pileup, on the device; its segments and operations stay there and are
+ *                          NOT downloaded.  slamem_stream_next gives the number of segments piled as its total -- its rows and
+ *                          offsets pointers are not to be read --, slamem_stream_maps the read records; slamem_stream_alns is
+ *                          SLAMEM_ERR_ARG.  It takes the setters of 7.  When slamem_stream_next hands a batch back its reads
+ *                          are in the table.)
+ *   slamem_stream_set_pileup  -pile: the accumulator every batch is added to and the least mapping quality that counts (0 to
+ *                          60); before the first submit.  SLAMEM_ERR_ARG after it, on a stream of another match type, with an
+ *                          accumulator of another device, or with a quality above 60; a submit on a stream of match type 8
+ *                          that has no accumulator is SLAMEM_ERR_ARG too.  Several streams of one device may share one
+ *                          accumulator: every update is an atomic add.  The add is enqueued once the batch's totals have shown
+ *                          that its result stands (a batch that is run again with more room is piled once).
  *   slamem_stream_set_max_occ  -smem: the occurrence cap of every batch (0: none, the default); before the first submit
  *                          (SLAMEM_ERR_ARG after it, or with a cap on a stream of another match type)
  *   slamem_stream_set_max_gap  -chain: the maximum gap of every batch (0: the default 5000); before the first submit
@@ -531,9 +577,10 @@ int slamem_stream_mismatches(slamem_stream *s, const uint32_t **out);
 int slamem_stream_set_max_edits(slamem_stream *s, uint32_t max_edits);
 int slamem_stream_alns(slamem_stream *s, const slamem_aln **segs_out, const uint32_t **ops_out, const uint64_t **op_offsets_out,
                        uint64_t *num_ops_out);
-/* -paf: the read records (num_queries of them) of the batch slamem_stream_next returned last, in the stream's pinned memory;
+/* -paf, -pile: the read records (num_queries of them) of the batch slamem_stream_next returned last, in the stream's pinned memory;
  * valid as long as that batch.  Its segments and operations come through slamem_stream_alns. */
 int slamem_stream_maps(slamem_stream *s, const slamem_map **reads_out);
+int slamem_stream_set_pileup(slamem_stream *s, slamem_pileup *pile, uint32_t min_mapq);
 int slamem_stream_submit(slamem_stream *s, const char *queries, const uint64_t *offsets, uint32_t num_queries,
                          uint32_t min_len);
 /* The same for reads the caller holds PACKED (ABI 4; no reference counterpart: the reference reads letters, sequence.c:89-270).

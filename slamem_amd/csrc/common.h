@@ -400,6 +400,13 @@ uint64_t map_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t
 int map_filter(void* map_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
                uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_roff,
                unsigned long long* host_scalars, hipStream_t stream);
+// -pile (pile_filter.hip, match type 8 of a stream): the per-base pileup of -paf's mappings.  pileup_add enqueues the two add
+// kernels over the outputs of a -paf batch as they lie on the device (nothing is checked on the host, nothing comes back);
+// pileup_device: the device the accumulator lives on.
+int pileup_device(const slamem_pileup* p);
+int pileup_add(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+               const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
+               const slamem_map* reads_dev, uint32_t min_mapq, hipStream_t stream);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).

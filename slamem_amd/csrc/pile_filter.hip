@@ -1,0 +1,474 @@
+// pile_filter.hip -- -pile (matchType 8): the per-base pileup of the read mappings, accumulated on the device.  DESIGN.md 4.16
+// has the definition; in short, with n the merged text's length, the table has n rows of six counters A, C, G, T, D, I, and
+// every segment of a read whose record has strand != 0 and mapq >= min_mapq is walked once, left to right:
+//   = / X of k   the scanned strand's letter, if one of A,C,G,T, counts in its column at each of the k rows
+//   D of k       column D of the k rows
+//   I of k       column I of the row in front of which it stands, once (dropped at row n)
+//
+// The accumulator is a difference array and a table: int32 diff[n + 1], uint32 cnt[n][6].  An `=` run over [p, p + k) restates
+// the text, so it costs two atomics (diff[p] += 1, diff[p + k] -= 1) whatever its length; X, D and I add to cnt directly.  A
+// letter under `=` is the text's letter (that is what the operation says), so the rows of the run whose letter is none of
+// A,C,G,T are the set bits of the text's letter mask over [p, p + k): the run is split there and those rows get nothing.
+//   k_pile_lane    a lane per read: its segments of up to kPileLaneOps operations, one operation after the other
+//   k_pile_wave    a wave per 64 reads finds the reads with a longer segment (ballot) and then takes those segments one by one:
+//                  64 operations at a time, a wave scan of their lengths gives each lane the p and q of its operation
+//   k_pile_tile_sums / k_pile_tile_scan / k_pile_counts
+//                  the read-out of rows [first, first + count): the sums of diff per tile of kPileTile entries, their exclusive
+//                  prefix sums (one workgroup), and per tile the running sum of diff = match[p], which goes to the column of the
+//                  text's letter at p (none when it is not A,C,G,T) on top of cnt.  Nothing of the accumulator is written.
+// Counters are 32 bits wide and every sum is taken modulo 2^32: a true depth of 2^31 or more at one row is outside the contract.
+#include "common.h"
+
+#include <new>
+
+namespace slamem {
+
+namespace {
+
+constexpr uint32_t kPileLaneOps = 32;   // operations of a segment a lane walks alone; more: the wave kernel
+constexpr uint32_t kPileTile = 2048;    // entries of diff per workgroup of the read-out (256 lanes x 8)
+constexpr unsigned kPileWaveGrid = 2048;
+constexpr uint32_t kOpEq = 7, kOpX = 8, kOpI = 1, kOpD = 2;  // BAM's codes, as aln_filter.hip writes them
+
+inline unsigned pile_grid(uint64_t items, unsigned block) { return items ? (unsigned)((items + block - 1) / block) : 1u; }
+
+// A 0, C 1, G 2, T 3 (either case); anything else 4
+__device__ __forceinline__ uint32_t pile_code(uint32_t byte) {
+    const uint32_t u = byte & 0xDFu, y = (u >> 1) & 3u, code = y ^ (y >> 1);
+    return ((0x54474341u >> (8u * code)) & 0xFFu) == u ? code : 4u;
+}
+
+struct PileAcc {
+    const TextPlanes* tpl;
+    int32_t* diff;   // n + 1
+    uint32_t* cnt;   // n x 6
+    uint32_t n;
+};
+
+// an `=` run over rows [p, p + k): rows at and behind n are dropped, rows whose letter is none of A,C,G,T get nothing
+__device__ __forceinline__ void pile_eq(const PileAcc& a, uint64_t p, uint64_t k) {
+    if (k == 0 || p >= a.n) return;
+    if (p + k > a.n) k = a.n - p;
+    const uint64_t e = p + k;  // <= n
+    uint64_t any = 0;
+    for (uint64_t u = p >> 6; u <= (e - 1) >> 6; u++) {
+        uint64_t m = a.tpl[u].nm;
+        if (u == p >> 6) m &= ~0ull << (p & 63u);
+        if (u == (e - 1) >> 6 && (e & 63u)) m &= (1ull << (e & 63u)) - 1ull;
+        any |= m;
+    }
+    if (!any) {
+        atomicAdd(&a.diff[p], 1);
+        atomicAdd(&a.diff[e], -1);
+        return;
+    }
+    // (rare: only an anchor holds such a letter) row by row, a pair of atomics per stretch of A,C,G,T
+    uint64_t start = ~0ull;
+    for (uint64_t x = p; x < e; x++) {
+        const bool bad = (a.tpl[x >> 6].nm >> (x & 63u)) & 1ull;
+        if (!bad && start == ~0ull) start = x;
+        if (bad && start != ~0ull) {
+            atomicAdd(&a.diff[start], 1);
+            atomicAdd(&a.diff[x], -1);
+            start = ~0ull;
+        }
+    }
+    if (start != ~0ull) {
+        atomicAdd(&a.diff[start], 1);
+        atomicAdd(&a.diff[e], -1);
+    }
+}
+
+// the read as the search saw it: letter x of the scanned strand
+struct PileRead {
+    const unsigned char* rec;
+    uint64_t len;
+    bool rev;
+};
+__device__ __forceinline__ uint32_t pile_letter(const PileRead& r, uint64_t x) {
+    if (x >= r.len) return 4u;
+    if (!r.rev) return pile_code(r.rec[x]);
+    const uint32_t c = pile_code(r.rec[r.len - 1u - x]);
+    return c < 4u ? 3u - c : 4u;
+}
+
+// one operation at (p, q): every write is checked against n
+__device__ __forceinline__ void pile_op(const PileAcc& a, const PileRead& r, uint32_t op, uint64_t p, uint64_t q) {
+    const uint32_t code = op & 15u;
+    const uint64_t k = op >> 4;
+    if (code == kOpEq) {
+        pile_eq(a, p, k);
+    } else if (code == kOpX) {
+        for (uint64_t j = 0; j < k && p + j < a.n; j++) {
+            const uint32_t c = pile_letter(r, q + j);
+            if (c < 4u) atomicAdd(&a.cnt[(p + j) * 6u + c], 1u);
+        }
+    } else if (code == kOpD) {
+        for (uint64_t j = 0; j < k && p + j < a.n; j++) atomicAdd(&a.cnt[(p + j) * 6u + 4u], 1u);
+    } else if (code == kOpI) {
+        if (k && p < a.n) atomicAdd(&a.cnt[p * 6u + 5u], 1u);
+    }
+}
+__device__ __forceinline__ uint32_t pile_ref_step(uint32_t op) {
+    const uint32_t c = op & 15u;
+    return (c == kOpEq || c == kOpX || c == kOpD) ? op >> 4 : 0u;
+}
+__device__ __forceinline__ uint32_t pile_query_step(uint32_t op) {
+    const uint32_t c = op & 15u;
+    return (c == kOpEq || c == kOpX || c == kOpI) ? op >> 4 : 0u;
+}
+
+struct PileBatch {
+    const unsigned char* queries;
+    const uint64_t* offsets;
+    const slamem_aln* segs;
+    const uint64_t* roff;
+    const uint32_t* ops;
+    const uint64_t* ooff;
+    const slamem_map* reads;
+    uint64_t nq;
+    uint32_t min_mapq;
+};
+
+__device__ __forceinline__ bool pile_contributes(const PileBatch& b, uint64_t r, PileRead& out) {
+    const slamem_map m = b.reads[r];
+    if (m.strand == 0u || m.mapq < b.min_mapq) return false;
+    const uint64_t o = b.offsets[r];
+    out.rec = b.queries + o;
+    out.len = b.offsets[r + 1] - o;
+    out.rev = m.strand == 2u;
+    return true;
+}
+
+// a lane per read: its segments of up to kPileLaneOps operations
+__global__ void __launch_bounds__(256) k_pile_lane(PileBatch b, PileAcc a) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (r >= b.nq) return;
+    PileRead rd;
+    if (!pile_contributes(b, r, rd)) return;
+    const uint64_t s1 = b.roff[r + 1];
+    for (uint64_t s = b.roff[r]; s < s1; s++) {
+        const uint64_t o0 = b.ooff[s], o1 = b.ooff[s + 1];
+        if (o1 <= o0 || o1 - o0 > kPileLaneOps) continue;
+        const slamem_aln sg = b.segs[s];
+        uint64_t p = sg.ref_pos, q = sg.query_pos;
+        for (uint64_t i = o0; i < o1; i++) {
+            const uint32_t op = b.ops[i];
+            pile_op(a, rd, op, p, q);
+            p += pile_ref_step(op);
+            q += pile_query_step(op);
+        }
+    }
+}
+
+__device__ __forceinline__ uint64_t wave_scan_inclusive(uint64_t v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint64_t up = __shfl_up(v, d, 64);
+        if (lane >= d) v += up;
+    }
+    return v;
+}
+
+// a wave per 64 reads: the reads that have a segment of more than kPileLaneOps operations, one after the other; of such a read
+// those segments, 64 operations at a time
+__global__ void __launch_bounds__(64) k_pile_wave(PileBatch b, PileAcc a) {
+    const uint32_t lane = threadIdx.x;
+    const uint64_t chunks = (b.nq + 63u) >> 6;
+    for (uint64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const uint64_t r = c * 64u + lane;
+        bool big = false;
+        PileRead mine;
+        if (r < b.nq && pile_contributes(b, r, mine)) {
+            const uint64_t s1 = b.roff[r + 1];
+            for (uint64_t s = b.roff[r]; s < s1 && !big; s++) big = b.ooff[s + 1] - b.ooff[s] > kPileLaneOps && b.ooff[s + 1] > b.ooff[s];
+        }
+        unsigned long long todo = __ballot(big);
+        while (todo) {
+            const uint32_t src = (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            const uint64_t rr = c * 64u + src;
+            PileRead rd;
+            (void)pile_contributes(b, rr, rd);  // (it does: its lane said so)
+            const uint64_t s1 = b.roff[rr + 1];
+            for (uint64_t s = b.roff[rr]; s < s1; s++) {
+                const uint64_t o0 = b.ooff[s], o1 = b.ooff[s + 1];
+                if (o1 <= o0 || o1 - o0 <= kPileLaneOps) continue;
+                const slamem_aln sg = b.segs[s];
+                uint64_t p = sg.ref_pos, q = sg.query_pos;
+                for (uint64_t base = o0; base < o1; base += 64u) {
+                    const bool have = base + lane < o1;
+                    const uint32_t op = have ? b.ops[base + lane] : 0u;
+                    const uint64_t rs = pile_ref_step(op), qs = pile_query_step(op);
+                    const uint64_t ri = wave_scan_inclusive(rs, lane), qi = wave_scan_inclusive(qs, lane);
+                    if (have) pile_op(a, rd, op, p + ri - rs, q + qi - qs);
+                    p += __shfl(ri, 63, 64);
+                    q += __shfl(qi, 63, 64);
+                }
+            }
+        }
+    }
+}
+
+// ---- read-out --------------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t* lds /* 4 words */) {
+#pragma unroll
+    for (uint32_t d = 32; d >= 1u; d >>= 1) v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const uint32_t t = lds[0] + lds[1] + lds[2] + lds[3];
+    __syncthreads();
+    return t;
+}
+
+// tile t: the sum of diff[t * kPileTile .. (t + 1) * kPileTile) below `entries`
+__global__ void __launch_bounds__(256) k_pile_tile_sums(const int32_t* __restrict__ diff, uint64_t entries, uint32_t* __restrict__ tile) {
+    __shared__ uint32_t lds[4];
+    const uint64_t base = (uint64_t)blockIdx.x * kPileTile;
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kPileTile / 256u; j++) {
+        const uint64_t x = base + j * 256u + threadIdx.x;
+        if (x < entries) v += (uint32_t)diff[x];
+    }
+    v = block_sum_256(v, lds);
+    if (threadIdx.x == 0) tile[blockIdx.x] = v;
+}
+
+// in place: tile[t] = the sum of the tiles in front of t (one workgroup of 1024 lanes, a stretch of tiles each)
+__global__ void __launch_bounds__(1024) k_pile_tile_scan(uint32_t* __restrict__ tile, uint64_t tiles) {
+    __shared__ uint32_t part[1024];
+    const uint64_t per = (tiles + 1023u) / 1024u;
+    const uint64_t s = (uint64_t)threadIdx.x * per, e = s + per < tiles ? s + per : tiles;
+    uint32_t v = 0;
+    for (uint64_t x = s; x < e; x++) v += tile[x];
+    part[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (uint32_t k = 0; k < 1024u; k++) { const uint32_t t = part[k]; part[k] = run; run += t; }
+    }
+    __syncthreads();
+    uint32_t run = part[threadIdx.x];
+    for (uint64_t x = s; x < e; x++) { const uint32_t t = tile[x]; tile[x] = run; run += t; }
+}
+
+// a workgroup per tile of rows: match[p] = the sum of diff[0 .. p], then rows [first, first + count) of the table
+__global__ void __launch_bounds__(256) k_pile_counts(const int32_t* __restrict__ diff, const uint32_t* __restrict__ cnt,
+                                                     const uint32_t* __restrict__ tile, const TextPlanes* __restrict__ tpl, uint64_t tile0,
+                                                     uint64_t first, uint64_t count, uint32_t* __restrict__ out) {
+    __shared__ uint32_t match[kPileTile];
+    __shared__ uint8_t code[kPileTile];
+    __shared__ uint32_t wsum[4];
+    const uint64_t t = tile0 + blockIdx.x, base = t * kPileTile, end = first + count;  // (end <= n)
+    constexpr uint32_t per = kPileTile / 256u;
+    // a lane takes `per` consecutive entries
+    uint32_t v[per], run = 0;
+    const uint64_t x0 = base + (uint64_t)threadIdx.x * per;
+#pragma unroll
+    for (uint32_t j = 0; j < per; j++) {
+        run += x0 + j < end ? (uint32_t)diff[x0 + j] : 0u;
+        v[j] = run;
+    }
+    // the lanes' totals: inside the wave, then across the four waves
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = run;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t up = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += up;
+    }
+    if (lane == 63u) wsum[wave] = inc;
+    __syncthreads();
+    uint32_t before = tile[t] + inc - run;
+    for (uint32_t w = 0; w < wave; w++) before += wsum[w];
+#pragma unroll
+    for (uint32_t j = 0; j < per; j++) {
+        const uint64_t x = x0 + j;
+        const uint32_t at = threadIdx.x * per + j;
+        match[at] = before + v[j];
+        uint32_t c = 4u;
+        if (x < end) {
+            const TextPlanes u = tpl[x >> 6];
+            const uint32_t bit = (uint32_t)(x & 63u);
+            if (!((u.nm >> bit) & 1ull)) c = (uint32_t)((u.p0 >> bit) & 1ull) | ((uint32_t)((u.p1 >> bit) & 1ull) << 1);
+        }
+        code[at] = (uint8_t)c;
+    }
+    __syncthreads();
+    // the rows of the tile inside the range, counter by counter
+    const uint64_t lo = base > first ? base : first, hi = base + kPileTile < end ? base + kPileTile : end;
+    if (hi <= lo) return;
+    const uint64_t words = (hi - lo) * 6u;
+    const uint32_t* src = cnt + lo * 6u;
+    uint32_t* dst = out + (lo - first) * 6u;
+    for (uint64_t w = threadIdx.x; w < words; w += 256u) {
+        const uint32_t row = (uint32_t)(w / 6u), col = (uint32_t)(w - (uint64_t)row * 6u);
+        const uint32_t at = (uint32_t)(lo - base) + row;
+        dst[w] = src[w] + (code[at] == col ? match[at] : 0u);
+    }
+}
+
+}  // namespace
+
+}  // namespace slamem
+
+using namespace slamem;
+
+struct slamem_pileup {
+    const slamem_index* idx;
+    int device;
+    uint32_t n;
+    int32_t* diff;
+    uint32_t* cnt;
+    uint32_t* tile;  // the read-out's tile sums: n / kPileTile + 2 words
+};
+
+namespace slamem {
+
+int pileup_device(const slamem_pileup* p) { return p->device; }
+
+int pileup_add(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+               const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
+               const slamem_map* reads_dev, uint32_t min_mapq, hipStream_t stream) {
+    if (num_queries == 0) return SLAMEM_OK;
+    PileBatch b;
+    b.queries = static_cast<const unsigned char*>(queries_dev);
+    b.offsets = offsets_dev;
+    b.segs = segs_dev;
+    b.roff = read_offsets_dev;
+    b.ops = ops_dev;
+    b.ooff = op_offsets_dev;
+    b.reads = reads_dev;
+    b.nq = num_queries;
+    b.min_mapq = min_mapq;
+    PileAcc a;
+    a.tpl = pile->idx->view.tpl;
+    a.diff = pile->diff;
+    a.cnt = pile->cnt;
+    a.n = pile->n;
+    hipLaunchKernelGGL(k_pile_lane, dim3(pile_grid(num_queries, 256)), dim3(256), 0, stream, b, a);
+    SLAMEM_HIP(hipGetLastError());
+    const unsigned chunks = pile_grid(num_queries, 64);
+    hipLaunchKernelGGL(k_pile_wave, dim3(chunks < kPileWaveGrid ? chunks : kPileWaveGrid), dim3(64), 0, stream, b, a);
+    SLAMEM_HIP(hipGetLastError());
+    return SLAMEM_OK;
+}
+
+}  // namespace slamem
+
+extern "C" {
+
+int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
+    if (!idx || !out) { set_error("slamem_pileup_create: null argument"); return SLAMEM_ERR_ARG; }
+    *out = nullptr;
+    if (idx->hdr.off_tpl == 0 || !idx->view.tpl) {
+        set_error("slamem_pileup_create: -pile reads the text planes of the index, and this index has none (the compact layout, or "
+                  "one built without the seed sections)");
+        return SLAMEM_ERR_ARG;
+    }
+    SLAMEM_HIP(hipSetDevice(idx->device));
+    const uint64_t n = idx->hdr.n;
+    const uint64_t tiles = n / kPileTile + 2;
+    const uint64_t need = (n + 1) * 4 + n * 24 + tiles * 4;
+    size_t free_b = 0, total_b = 0;
+    SLAMEM_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b) {
+        set_error("slamem_pileup_create: the accumulator of a text of %llu letters takes %llu bytes (28 per letter), %llu are free on "
+                  "device %d", (unsigned long long)n, (unsigned long long)need, (unsigned long long)free_b, idx->device);
+        return SLAMEM_ERR_NOMEM;
+    }
+    slamem_pileup* p = new (std::nothrow) slamem_pileup();
+    if (!p) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
+    p->idx = idx; p->device = idx->device; p->n = (uint32_t)n;
+    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->diff), (n + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->cnt), n * 24 + 16);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->tile), tiles * 4);
+    if (e == hipSuccess) e = hipMemset(p->diff, 0, (n + 1) * 4);
+    if (e == hipSuccess) e = hipMemset(p->cnt, 0, n * 24);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)slamem_pileup_free(p);
+        return hip_fail(e, "slamem_pileup_create", __FILE__, __LINE__);
+    }
+    *out = p;
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_free(slamem_pileup* p) {
+    if (!p) return SLAMEM_OK;
+    (void)hipSetDevice(p->device);
+    if (p->diff) (void)hipFree(p->diff);
+    if (p->cnt) (void)hipFree(p->cnt);
+    if (p->tile) (void)hipFree(p->tile);
+    delete p;
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_reset(slamem_pileup* p) {
+    if (!p) { set_error("slamem_pileup_reset: null argument"); return SLAMEM_ERR_ARG; }
+    SLAMEM_HIP(hipSetDevice(p->device));
+    SLAMEM_HIP(hipDeviceSynchronize());  // (adds of any stream that are still on their way belong to the table that goes)
+    SLAMEM_HIP(hipMemset(p->diff, 0, ((uint64_t)p->n + 1) * 4));
+    SLAMEM_HIP(hipMemset(p->cnt, 0, (uint64_t)p->n * 24));
+    SLAMEM_HIP(hipDeviceSynchronize());
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_add_device(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                             const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev,
+                             const uint64_t* op_offsets_dev, const slamem_map* reads_dev, uint32_t min_mapq, void* stream) {
+    if (!pile || !offsets_dev || !read_offsets_dev || !op_offsets_dev || !reads_dev || (num_queries && (!queries_dev || !segs_dev || !ops_dev))) {
+        set_error("slamem_pileup_add_device: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    if (min_mapq > 60u) { set_error("slamem_pileup_add_device: the minimum mapping quality is 0 to 60"); return SLAMEM_ERR_ARG; }
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    return pileup_add(pile, queries_dev, offsets_dev, num_queries, segs_dev, read_offsets_dev, ops_dev, op_offsets_dev, reads_dev,
+                      min_mapq, static_cast<hipStream_t>(stream));
+}
+
+int slamem_pileup_counts_device(slamem_pileup* pile, uint64_t first, uint64_t count, uint32_t* out_dev, void* stream) {
+    if (!pile || (count && !out_dev)) { set_error("slamem_pileup_counts_device: null argument"); return SLAMEM_ERR_ARG; }
+    if (first > pile->n || count > pile->n - first) {
+        set_error("slamem_pileup_counts_device: rows %llu .. %llu + %llu lie outside the text's %u", (unsigned long long)first,
+                  (unsigned long long)first, (unsigned long long)count, pile->n);
+        return SLAMEM_ERR_ARG;
+    }
+    if (count == 0) return SLAMEM_OK;
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t end = first + count, tiles = (end + kPileTile - 1) / kPileTile, tile0 = first / kPileTile;
+    hipLaunchKernelGGL(k_pile_tile_sums, dim3((unsigned)tiles), dim3(256), 0, st, (const int32_t*)pile->diff, end, pile->tile);
+    SLAMEM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_pile_tile_scan, dim3(1), dim3(1024), 0, st, pile->tile, tiles);
+    SLAMEM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_pile_counts, dim3((unsigned)(tiles - tile0)), dim3(256), 0, st, (const int32_t*)pile->diff,
+                       (const uint32_t*)pile->cnt, (const uint32_t*)pile->tile, pile->idx->view.tpl, tile0, first, count, out_dev);
+    SLAMEM_HIP(hipGetLastError());
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_counts_host(slamem_pileup* pile, uint64_t first, uint64_t count, uint32_t* out) {
+    if (!pile || (count && !out)) { set_error("slamem_pileup_counts_host: null argument"); return SLAMEM_ERR_ARG; }
+    if (first > pile->n || count > pile->n - first) {
+        set_error("slamem_pileup_counts_host: rows %llu .. %llu + %llu lie outside the text's %u", (unsigned long long)first,
+                  (unsigned long long)first, (unsigned long long)count, pile->n);
+        return SLAMEM_ERR_ARG;
+    }
+    if (count == 0) return SLAMEM_OK;
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the table that is read)
+    void* d = nullptr;
+    SLAMEM_HIP(hipMalloc(&d, count * 24));
+    int rc = slamem_pileup_counts_device(pile, first, count, static_cast<uint32_t*>(d), nullptr);
+    hipError_t e = rc == SLAMEM_OK ? hipMemcpy(out, d, count * 24, hipMemcpyDeviceToHost) : hipSuccess;
+    (void)hipFree(d);
+    if (rc != SLAMEM_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
+    return SLAMEM_OK;
+}
+
+}  // extern "C"

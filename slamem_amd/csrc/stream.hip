@@ -17,6 +17,8 @@
 // kernels and memsets sat behind the first one's K8 until its tail and the chain after them was exposed -- 3.7 ms per
 // million-read batch where the kernels need 2.9; measured with rocprofv3 --kernel-trace, profiles/r03_host_leg_timeline.txt.
 // One thread per SLOT doing everything in turn was measured before that: the slots fall into lockstep, 62 ms.)
+// -pile (match type 8) is -paf whose segments stay on the device: the download stage, once the batch's totals have shown that
+// its result stands, enqueues the add to the accumulator (pile_filter.hip) on its stream and copies out the read records only.
 // No CPU fallback: every batch is searched on the GPU.
 #include "common.h"
 #include "prims.h"
@@ -111,6 +113,8 @@ struct slamem_stream {
     uint32_t max_gap = 0;  // -chain: the maximum gap of every batch (slamem_stream_set_max_gap; 0: the default)
     uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;  // -ext, -aln: penalty and drop of every batch (slamem_stream_set_ext_params)
     uint32_t max_edits = kAlnDefaultEdits;  // -aln: the most edits in a gap (slamem_stream_set_max_edits)
+    slamem_pileup* pile = nullptr;          // -pile: the accumulator every batch is added to (slamem_stream_set_pileup)
+    uint32_t min_mapq = 0;                  // -pile: the least mapping quality that counts
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     Slot slot[kMaxSlots];
@@ -144,7 +148,11 @@ namespace {
 // setting a stream up costs nothing, the allocations (pinned host memory above all: ~0.1 ms per MB) overlap with the
 // other stages' work, and slots that are never used are never allocated.
 // -aln and -paf share the segments' buffers, capacities and setters; -paf adds the read records and has offsets per read
-inline bool is_aln(const slamem_stream* s) { return s->match_type == 6 || s->match_type == 7; }
+// -pile is -paf whose segments stay on the device: the same job, buffers and setters; the download stage adds the batch to the
+// accumulator where -paf copies its segments out
+inline bool is_aln(const slamem_stream* s) { return s->match_type == 6 || s->match_type == 7 || s->match_type == 8; }
+inline bool is_map(const slamem_stream* s) { return s->match_type == 7 || s->match_type == 8; }
+inline int job_type(const slamem_stream* s) { return s->match_type == 8 ? 7 : s->match_type; }
 
 int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search stage: device output + workspace
     if (sl.d_mems) (void)hipFree(sl.d_mems);
@@ -152,7 +160,7 @@ int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search sta
     if (sl.d_mm) (void)hipFree(sl.d_mm);
     sl.d_mems = nullptr; sl.d_ws = nullptr; sl.d_mm = nullptr;
     sl.cap = need_cap;
-    sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, s->match_type);
+    sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, job_type(s));
     if (is_aln(s)) {
         if (sl.d_segs) (void)hipFree(sl.d_segs);
         if (sl.d_ops) (void)hipFree(sl.d_ops);
@@ -161,7 +169,7 @@ int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search sta
         if (sl.ops_cap < 2 * sl.cap + 1024) sl.ops_cap = 2 * sl.cap + 1024;  // (a first guess; SLAMEM_ERR_CAPACITY tells the need)
         const uint64_t nbq = (uint64_t)sl.cap_q * (s->both ? 2u : 1u);
         sl.ws_bytes = find_mems_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap) +
-                      (s->match_type == 7 ? map_workspace_bytes(sl.cap_q, nbq, sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits)
+                      (is_map(s) ? map_workspace_bytes(sl.cap_q, nbq, sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits)
                                           : aln_workspace_bytes(sl.cap_q, nbq, sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_segs), (sl.cap + 1) * sizeof(slamem_aln)));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ops), (sl.ops_cap + 1) * 4));
@@ -313,7 +321,7 @@ int stage_upload(slamem_stream* s, Slot& sl) {
         SLAMEM_HIP(hipMalloc(&sl.d_q, nchars + 2 * kFront + 32));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_off), ((uint64_t)nrec + 1) * 8));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_boff), (nb + 1) * 8));
-        if (s->match_type == 7) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_reads), ((uint64_t)nrec + 1) * sizeof(slamem_map)));
+        if (is_map(s)) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_reads), ((uint64_t)nrec + 1) * sizeof(slamem_map)));
         sl.cap_chars = nchars;
         sl.cap_q = nrec;
     }
@@ -372,10 +380,10 @@ int job_setup(slamem_stream* s, Slot& sl) {
         a.segs = sl.d_segs; a.segs_capacity = sl.cap;
         a.ops = sl.d_ops; a.ops_capacity = sl.ops_cap;
         a.op_offsets = sl.d_ooff;
-        a.reads = s->match_type == 7 ? sl.d_reads : nullptr;
+        a.reads = is_map(s) ? sl.d_reads : nullptr;
         search_job_aln(sl.job, a);
     }
-    int rc = search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, s->match_type,
+    int rc = search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, job_type(s),
                              sl.d_mems, sl.cap, sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal);
     search_job_max_occ(sl.job, s->max_occ);
     search_job_max_gap(sl.job, s->max_gap);
@@ -499,7 +507,13 @@ int stage_download(slamem_stream* s, Slot& sl) {
         sl.h_boff_cap = want > nb + 1 ? want : nb + 1;
         SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_boff), sl.h_boff_cap * 8, hipHostMallocDefault));
     }
-    if (sl.h_cap < sl.cap || !sl.h_mems) {
+    if (s->match_type == 8) {
+        // -pile: the batch's result stands (its totals fitted), so it is added to the accumulator -- here and not behind K9,
+        // where nobody knows yet whether the batch will be run again with more room.  Segments and operations stay on the device.
+        rc = pileup_add(s->pile, device_queries(sl), sl.d_off, sl.nq, sl.d_segs, sl.d_boff, sl.d_ops, sl.d_ooff, sl.d_reads,
+                        s->min_mapq, st);
+        if (rc != SLAMEM_OK) return rc;
+    } else if (sl.h_cap < sl.cap || !sl.h_mems) {
         if (sl.h_mems) (void)hipHostFree(sl.h_mems);
         sl.h_mems = nullptr;
         SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_mems), sl.cap * sizeof(slamem_mem) + 16, hipHostMallocDefault));
@@ -507,7 +521,7 @@ int stage_download(slamem_stream* s, Slot& sl) {
     }
     if (sl.total && !is_aln(s))
         SLAMEM_HIP(hipMemcpyAsync(sl.h_mems, sl.d_mems, sl.total * sizeof(slamem_mem), hipMemcpyDeviceToHost, st));
-    if (is_aln(s)) {  // (sl.total: the segments)
+    if (is_aln(s) && s->match_type != 8) {  // (sl.total: the segments)
         if (sl.h_segs_cap < sl.cap || !sl.h_segs) {
             if (sl.h_segs) (void)hipHostFree(sl.h_segs);
             if (sl.h_ooff) (void)hipHostFree(sl.h_ooff);
@@ -535,7 +549,7 @@ int stage_download(slamem_stream* s, Slot& sl) {
         }
         if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_mm, sl.d_mm, sl.total * 4, hipMemcpyDeviceToHost, st));
     }
-    if (s->match_type == 7) {  // (the offsets are per read)
+    if (is_map(s)) {  // (the offsets are per read)
         if (sl.h_reads_cap < sl.cap_q || !sl.h_reads) {
             if (sl.h_reads) (void)hipHostFree(sl.h_reads);
             sl.h_reads = nullptr;
@@ -726,8 +740,8 @@ int slamem_stream_destroy(slamem_stream* s) {
 
 int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_chars, uint32_t max_batch_queries,
                          int both_strands, int match_type, slamem_stream** out) {
-    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 7)) {
-        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 7)");
+    if (!idx || !out || slots < 2 || slots > kMaxSlots || max_batch_queries == 0 || (match_type < 0 || match_type > 8)) {
+        set_error("slamem_stream_create: bad argument (2..8 slots, at least one query per batch, match type 0 to 8)");
         return SLAMEM_ERR_ARG;
     }
     *out = nullptr;
@@ -874,6 +888,7 @@ int slamem_stream_alns(slamem_stream* s, const slamem_aln** segs_out, const uint
     if (!s || !segs_out || !ops_out || !op_offsets_out || !num_ops_out) { set_error("slamem_stream_alns: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
     *segs_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr; *num_ops_out = 0;
+    if (s->match_type == 8) { set_error("slamem_stream_alns: a stream of match type 8 (-pile) keeps its segments on the device"); return SLAMEM_ERR_ARG; }
     if (!is_aln(s)) { set_error("slamem_stream_alns: the stream's match type is not 6 (-aln)"); return SLAMEM_ERR_ARG; }
     if (s->returned == 0) { set_error("slamem_stream_alns: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
     Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
@@ -889,7 +904,7 @@ int slamem_stream_maps(slamem_stream* s, const slamem_map** reads_out) {
     if (!s || !reads_out) { set_error("slamem_stream_maps: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
     *reads_out = nullptr;
-    if (s->match_type != 7) { set_error("slamem_stream_maps: the stream's match type is not 7 (-paf)"); return SLAMEM_ERR_ARG; }
+    if (!is_map(s)) { set_error("slamem_stream_maps: the stream's match type is not 7 (-paf) or 8 (-pile)"); return SLAMEM_ERR_ARG; }
     if (s->returned == 0) { set_error("slamem_stream_maps: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
     Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
     if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
@@ -897,6 +912,31 @@ int slamem_stream_maps(slamem_stream* s, const slamem_map** reads_out) {
         return SLAMEM_ERR_ARG;
     }
     *reads_out = sl.h_reads;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_set_pileup(slamem_stream* s, slamem_pileup* pile, uint32_t min_mapq) {
+    if (!s || !pile) { set_error("slamem_stream_set_pileup: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type != 8) {
+        set_error("slamem_stream_set_pileup: an accumulator needs match type 8 (-pile)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (pileup_device(pile) != s->idx->device) {
+        set_error("slamem_stream_set_pileup: the accumulator lives on device %d, the stream's index on device %d", pileup_device(pile),
+                  s->idx->device);
+        return SLAMEM_ERR_ARG;
+    }
+    if (min_mapq > 60u) {
+        set_error("slamem_stream_set_pileup: the minimum mapping quality is 0 to 60");
+        return SLAMEM_ERR_ARG;
+    }
+    if (s->submitted != 0) {
+        set_error("slamem_stream_set_pileup: the stream has batches already (set the accumulator before the first submit)");
+        return SLAMEM_ERR_ARG;
+    }
+    s->pile = pile;
+    s->min_mapq = min_mapq;
     return SLAMEM_OK;
 }
 
@@ -919,6 +959,10 @@ int slamem_stream_submit(slamem_stream* s, const char* queries, const uint64_t* 
     if (!s || !offsets || (num_queries && !queries)) { set_error("slamem_stream_submit: null argument"); return SLAMEM_ERR_ARG; }
     if (min_len < 1) { set_error("slamem_stream_submit: minimum MEM length must be >= 1"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type == 8 && !s->pile) {
+        set_error("slamem_stream_submit: a stream of match type 8 (-pile) needs slamem_stream_set_pileup first");
+        return SLAMEM_ERR_ARG;
+    }
     Slot& sl = s->slot[s->submitted % (uint64_t)s->nslots];
     if (sl.state != FREE) {
         // a slot is released by the slamem_stream_next call AFTER the one that handed its result out: at most slots - 1
@@ -950,6 +994,10 @@ int slamem_stream_submit_packed(slamem_stream* s, const void* planes, const uint
     if (((uintptr_t)planes & 15u) != 0) { set_error("slamem_stream_submit_packed: planes must be 16-byte aligned"); return SLAMEM_ERR_ARG; }
     if (min_len < 1) { set_error("slamem_stream_submit_packed: minimum MEM length must be >= 1"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type == 8 && !s->pile) {
+        set_error("slamem_stream_submit_packed: a stream of match type 8 (-pile) needs slamem_stream_set_pileup first");
+        return SLAMEM_ERR_ARG;
+    }
     Slot& sl = s->slot[s->submitted % (uint64_t)s->nslots];
     if (sl.state != FREE) {
         set_error("slamem_stream_submit_packed: all %d slots are in use (collect a result with slamem_stream_next first)", s->nslots);

@@ -21,6 +21,7 @@ MAP_DTYPE = np.dtype([("strand", "u1"), ("mapq", "u1"), ("s1", "<u4"), ("s2", "<
 _MAP_ABI = np.dtype([("s1", "<u4"), ("s2", "<u4"), ("strand", "u1"), ("mapq", "u1"), ("reserved", "u1", (2,))])  # slamem_map
 EDITS_DEFAULT = 0xFFFFFFFF  # SLAMEM_ALN_EDITS_DEFAULT: "the default 31" in the C ABI (0 is a value of its own)
 CIGAR_OPS = {7: "=", 8: "X", 1: "I", 2: "D"}  # BAM's codes; an operation is length << 4 | code
+PILE_LANE_OPS = 32  # -pile: a segment of up to this many operations is walked by one lane, a longer one by a wave (pile_filter.hip)
 
 
 def _map_records(raw: np.ndarray) -> np.ndarray:
@@ -256,7 +257,10 @@ class Index:
         chain's; mapq = 60 * (s1 - s2) // s1.  The other arguments as for find_alns."""
         return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, True)
 
-    def _aln_like(self, queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, mapping):
+    def _aln_like(self, queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, mapping,
+                  pile=None):
+        """pile: (Pileup, min_mapq) -- the batch's mappings are added to the accumulator on the device and only the read records
+        come back (Pileup.add)."""
         dev = self.device
         q = np.ascontiguousarray(np.frombuffer(queries, dtype=np.uint8) if isinstance(queries, (bytes, bytearray))
                                  else queries, dtype=np.uint8)
@@ -301,6 +305,9 @@ class Index:
                 err.totals = tuple(int(t) for t in totals)
                 raise err
             break
+        if pile is not None:
+            pile[0]._add_device(qd, od, num, segs, boff, ops, ooff, recs, pile[1])
+            return _map_records(recs[: num * 12].cpu().numpy())
         nseg, nops = int(totals[1]), int(totals[2])
         out = segs[: nseg * 5].cpu().numpy().view(np.uint32).reshape(-1, 5).copy().view(ALN_DTYPE).reshape(-1)
         res = (out, boff.cpu().numpy().view(np.uint64), ops[:nops].cpu().numpy().view(np.uint32),
@@ -378,6 +385,66 @@ def _match_type(mam: bool, mum: bool, smem: bool = False, max_occ: int = 0, chai
     if not 0 <= int(max_occ) < 2 ** 32:
         raise ValueError("max_occ must be in [0, 2^32)")
     return 4 if chain else (3 if smem else (2 if mum else (1 if mam else 0)))
+
+
+class Pileup:
+    """slamem_pileup_*: the per-base pileup of the read mappings, accumulated on the GPU (-pile).  A table of
+    index.n rows of six uint32 counters A, C, G, T, D, I: per reference position the letters the mapped reads show there, how many
+    delete it, and how many insert in front of it.  It is the sum over every batch added since creation or the last reset(),
+    whatever the split into batches and their order.  28 bytes of HBM per text letter."""
+
+    def __init__(self, index: Index):
+        self.index = index
+        self._h = C.c_void_p()
+        capi.check(capi.lib().slamem_pileup_create(index._h, C.byref(self._h)))
+        self.last_add_ms = 0.0  # device time of the last add's own kernels (the mapping in front of them not counted)
+
+    def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
+            xdrop=None, max_edits=None, min_mapq: int = 0) -> np.ndarray:
+        """Maps the batch as Index.map_reads does and adds the mappings of the reads with mapq >= min_mapq (0 to 60) to the table,
+        on the device: segments and operations are not downloaded.  Returns the read records of map_reads (MAP_DTYPE)."""
+        if not 0 <= int(min_mapq) <= 60:
+            raise ValueError("min_mapq must be in [0, 60]")
+        return self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, None, True,
+                                    pile=(self, int(min_mapq)))
+
+    def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq):
+        dev = self.index.device
+        with torch.cuda.device(dev):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            rc = capi.lib().slamem_pileup_add_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops), _ptr(ooff),
+                                                     _ptr(recs), int(min_mapq), _stream_handle(dev))
+            t1.record()
+            capi.check(rc)
+            t1.synchronize()  # (the batch's tensors go when the caller returns)
+            self.last_add_ms = float(t0.elapsed_time(t1))
+
+    def counts(self, first: int = 0, count=None) -> np.ndarray:
+        """Rows [first, first + count) of the table as a (count, 6) uint32 array (count None: up to the text's end).  The
+        accumulator is left as it is: more batches may be added and the table read again."""
+        first = int(first)
+        count = self.index.n - first if count is None else int(count)
+        dev = self.index.device
+        out = torch.zeros((max(count, 1), 6), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            capi.check(capi.lib().slamem_pileup_counts_device(self._h, first, count, _ptr(out), _stream_handle(dev)))
+            torch.cuda.current_stream(dev).synchronize()
+        return out[:max(count, 0)].cpu().numpy().view(np.uint32)
+
+    def reset(self) -> None:
+        capi.check(capi.lib().slamem_pileup_reset(self._h))
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h:
+            capi.lib().slamem_pileup_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Matcher:
@@ -464,17 +531,26 @@ class Stream:
 
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
-                 max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False):
-        """aln=True: -aln mode (match type 6); it takes max_gap, penalty, xdrop and max_edits and excludes the other modes.
+                 max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False,
+                 pile: "Pileup" = None, min_mapq: int = 0):
+        """pile=<Pileup>: -pile mode (match type 8): every batch is mapped as with paf=True and added to the accumulator on the
+        device (the reads with mapq >= min_mapq); next() then returns (number of segments piled, None, timings) and maps() the read
+        records; the segments are not downloaded.  It takes the parameters of paf and excludes the other modes.  aln=True: -aln mode (match type 6); it takes max_gap, penalty, xdrop and max_edits and excludes the other modes.
         next() then returns the segments (ALN_DTYPE) in the place of the rows, alns() their operations.  paf=True: -paf mode
         (match type 7), the same with the offsets per READ and maps() the read records (MAP_DTYPE)."""
+        self.pile = pile
+        if pile is not None and (aln or paf):
+            raise ValueError("pile excludes aln and paf: one match type per search")
+        if min_mapq and pile is None:
+            raise ValueError("min_mapq is the threshold of pile: it needs pile=<Pileup>")
+        paf = bool(paf or pile is not None)
         if (aln or paf) and (mam or mum or smem or chain or ext or max_occ or (aln and paf)):
-            raise ValueError("aln and paf exclude mam, mum, smem, chain, ext and each other: one match type per search")
+            raise ValueError("aln, paf and pile exclude mam, mum, smem, chain, ext and each other: one match type per search")
         if max_edits is not None and not (aln or paf):
             raise ValueError("max_edits is the edit limit of aln and paf: it needs aln=True or paf=True")
         self.paf = bool(paf)
         self.aln = bool(aln or paf)
-        match_type = 7 if paf else 6 if aln else _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
+        match_type = 8 if pile is not None else 7 if paf else 6 if aln else _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
         self.index = index
         self.both = bool(both_strands)
         self._h = C.c_void_p()
@@ -488,6 +564,8 @@ class Stream:
             capi.check(capi.lib().slamem_stream_set_ext_params(self._h, int(penalty), _xdrop_arg(xdrop)))
         if max_edits is not None:
             capi.check(capi.lib().slamem_stream_set_max_edits(self._h, int(max_edits)))
+        if pile is not None:
+            capi.check(capi.lib().slamem_stream_set_pileup(self._h, pile._h, int(min_mapq)))
         self._keep = []
         self._last_total = 0
 
@@ -516,6 +594,12 @@ class Stream:
         capi.check(rc)
         self._last_total = int(total.value)
         nb = nq.value * (1 if self.paf else 2 if self.both else 1)
+        if self.pile is not None:  # the segments stayed on the device: their number, and the read records through maps()
+            recs = C.c_void_p()
+            capi.check(capi.lib().slamem_stream_maps(self._h, C.byref(recs)))
+            raw = np.ctypeslib.as_array((C.c_uint8 * (12 * max(1, nq.value))).from_address(recs.value))[: 12 * nq.value]
+            self._last_maps = _map_records(raw)
+            return int(total.value), None, tm.as_dict()
         if self.aln:  # the segments stand in the place of the rows
             segs, ops, ooff, nops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
             capi.check(capi.lib().slamem_stream_alns(self._h, C.byref(segs), C.byref(ops), C.byref(ooff), C.byref(nops)))

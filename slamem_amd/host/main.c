@@ -43,8 +43,8 @@
 #define VERSION "0.8.2"
 /* what the output lines call a match of each type: M%cM with the reference's "EAU" (slamem.c:35), SMEM for -smem,
  * "chained MEM" for the rows -chain keeps and "extended MEM" for the rows of -ext */
-static const char *const MATCH_TYPE_NAME[8] = {"MEM", "MAM", "MUM", "SMEM", "chained MEM", "extended MEM", "alignment", "mapping"};
-#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 8 ? (t) : 0]
+static const char *const MATCH_TYPE_NAME[9] = {"MEM", "MAM", "MUM", "SMEM", "chained MEM", "extended MEM", "alignment", "mapping", "pileup"};
+#define MATCH_NAME(t) MATCH_TYPE_NAME[(t) >= 0 && (t) < 9 ? (t) : 0]
 
 /* the device warm-up thread (see main) is joined before the process ends, whichever way it ends */
 static pthread_t g_warm_tid;
@@ -589,6 +589,8 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-aln\tgapped alignment of the best chain of each strand; writes ref_pos query_pos ref_len query_len edits cigar\n");
     printf("\t-maxed\twith -aln: most edits in the gap between two chained MEMs, 0 to 127 (default=31); -mgap, -pen, -xdrop apply\n");
     printf("\t-paf\tone mapping per read with a mapping quality, written as PAF with a cg:Z: CIGAR; -mgap, -pen, -xdrop, -maxed apply\n");
+    printf("\t-pile\tper-base pileup of the mappings of -paf: record, position, letter and the counts A C G T D I; -mgap, -pen, -xdrop, -maxed apply\n");
+    printf("\t-minq\twith -pile: least mapping quality of a read that counts, 0 to 60 (default=0)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
     printf("\t-b\tprocess both forward and reverse strands\n");
@@ -613,7 +615,8 @@ int main(int argc, char **argv) {
     char *out_name;
     FILE *out;
     slamem_index *idx = NULL, *gpus[16];
-    int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1;
+    int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1, min_mapq = 0;
+    slamem_pileup *piles[16];
     double t0;
     long long total_matches = 0, total_sum = 0;
     slh_buffer buf = {0, 0, 0};
@@ -635,6 +638,7 @@ int main(int argc, char **argv) {
         return slh_clean_fasta(argv[2], stdout);
     }
     if (o.match_type < 0) { /* before any GPU work */
+        if (slh_parse_argument(argc, argv, "PI", 0)) exit_message("Option -pile excludes -mam, -mum, -smem, -chain, -ext, -aln and -paf");
         if (slh_parse_argument(argc, argv, "PA", 0)) exit_message("Option -paf excludes -mam, -mum, -smem, -chain, -ext and -aln");
         if (slh_parse_argument(argc, argv, "AL", 0)) exit_message("Option -aln excludes -mam, -mum, -smem, -chain and -ext");
         if (slh_parse_argument(argc, argv, "EX", 0)) exit_message("Option -ext excludes -mam, -mum, -smem and -chain");
@@ -649,17 +653,22 @@ int main(int argc, char **argv) {
     }
     switch (slh_parse_max_gap(argc, argv, &max_gap)) {
     case -1: exit_message("Option -mgap needs a whole number of at least 1"); break;
-    case 1: if (o.match_type != 4 && o.match_type != 6 && o.match_type != 7) exit_message("Option -mgap needs -chain"); break;
+    case 1: if (o.match_type != 4 && o.match_type != 6 && o.match_type != 7 && o.match_type != 8) exit_message("Option -mgap needs -chain"); break;
     default: break;
     }
     switch (slh_parse_ext_params(argc, argv, &ext_pen, &ext_xdrop)) {
     case -1: exit_message("Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"); break;
-    case 1: if (o.match_type != 5 && o.match_type != 6 && o.match_type != 7) exit_message("Options -pen and -xdrop need -ext"); break;
+    case 1: if (o.match_type != 5 && o.match_type != 6 && o.match_type != 7 && o.match_type != 8) exit_message("Options -pen and -xdrop need -ext"); break;
     default: break;
     }
     switch (slh_parse_max_edits(argc, argv, &max_edits)) {
     case -1: exit_message("Option -maxed needs a whole number from 0 to 127"); break;
-    case 1: if (o.match_type != 6 && o.match_type != 7) exit_message("Option -maxed needs -aln"); break;
+    case 1: if (o.match_type != 6 && o.match_type != 7 && o.match_type != 8) exit_message("Option -maxed needs -aln"); break;
+    default: break;
+    }
+    switch (slh_parse_min_mapq(argc, argv, &min_mapq)) {
+    case -1: exit_message("Option -minq needs a whole number from 0 to 60"); break;
+    case 1: if (o.match_type != 8) exit_message("Option -minq needs -pile"); break;
     default: break;
     }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
@@ -767,9 +776,10 @@ int main(int argc, char **argv) {
     if (max_occ > 0) say(" ; maximum occurrences = %d", max_occ);
     if (o.match_type == 4) say(" ; maximum gap = %d", max_gap > 0 ? max_gap : 5000);
     if (o.match_type == 5) say(" ; mismatch penalty = %d ; X-drop = %d", ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20);
-    if (o.match_type == 6 || o.match_type == 7)
+    if (o.match_type == 6 || o.match_type == 7 || o.match_type == 8)
         say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", max_gap > 0 ? max_gap : 5000,
             ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
+    if (o.match_type == 8) say(" ; minimum mapping quality = %d", min_mapq);
     say("\n");
     out = fopen(out_name, "w");
     if (!out) {
@@ -850,14 +860,16 @@ int main(int argc, char **argv) {
             ngpu == 1 ? " (self-test copy)" : "s", now_s() - tr);
     }
     t_build = bj.seconds + (now_s() - t0);
-    free(ref.chars); /* the reference frees the text here too (slamem.c:75-77) */
-    ref.chars = NULL;
+    if (o.match_type != 8) { /* (-pile prints the reference letter of every row: it keeps the text) */
+        free(ref.chars); /* the reference frees the text here too (slamem.c:75-77) */
+        ref.chars = NULL;
+    }
     say("> Matching query sequences against index ...\n");
     if (!g_mo) fflush(stdout);
 
     {
         /* (-paf: what is formatted and counted is a read, whichever strand its mapping lies on) */
-        int strands = o.match_type == 7 ? 1 : o.both_strands ? 2 : 1;
+        int strands = (o.match_type == 7 || o.match_type == 8) ? 1 : o.both_strands ? 2 : 1;
         long printed = 0;
         /* the list of batches (records [first,last) of one query file each), then a pipeline over it: the GPUs search
            batches b+1.. (slamem_stream_*: upload, search and download of neighbouring batches overlap), the main thread
@@ -904,6 +916,7 @@ int main(int argc, char **argv) {
         pthread_cond_init(&g_writer.cv, NULL);
         g_writer.started = pthread_create(&g_writer.tid, NULL, writer_run, &g_writer) == 0;
         double ts0 = now_s();
+        for (g = 0; g < 16; g++) piles[g] = NULL;
         for (g = 0; g < ngpu && (nranges || overlap); g++) { /* batch b is searched on GPU b mod ngpu: no data-path collective */
             rc = slamem_stream_create(gpus[g], slots, max_chars, max_recs, o.both_strands, o.match_type, &g_streams[g]);
             if (rc == SLAMEM_OK && max_occ > 0) {
@@ -919,7 +932,12 @@ int main(int argc, char **argv) {
                 rc = slamem_stream_set_ext_params(g_streams[g], (uint32_t)ext_pen,
                                                   ext_xdrop >= 0 ? (uint32_t)ext_xdrop : SLAMEM_EXT_XDROP_DEFAULT);
             }
-            if (rc == SLAMEM_OK && (o.match_type == 6 || o.match_type == 7)) {
+            if (rc == SLAMEM_OK && o.match_type == 8) { /* one accumulator per GPU: the tables are added when the file is written */
+                g_nstreams = g + 1;
+                rc = slamem_pileup_create(gpus[g], &piles[g]);
+                if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(g_streams[g], piles[g], (uint32_t)min_mapq);
+            }
+            if (rc == SLAMEM_OK && (o.match_type == 6 || o.match_type == 7 || o.match_type == 8)) {
                 g_nstreams = g + 1;
                 rc = slamem_stream_set_max_gap(g_streams[g], (uint32_t)max_gap);
                 if (rc == SLAMEM_OK)
@@ -984,6 +1002,12 @@ int main(int argc, char **argv) {
                 printf("\n> ERROR: MEM search on GPU %d failed: %s (%s)\n", device + (int)(bi % (size_t)ngpu), slamem_strerror(rc), detail);
                 join_warmup();
                 exit(-1);
+            }
+            if (o.match_type == 8) { /* the batch is in its GPU's table: nothing came back to format (total: the segments piled) */
+                inflight[bi % (size_t)ngpu]--;
+                total_matches += (long long)total;
+                t_gpu += now_s() - tg;
+                continue;
             }
             if (o.match_type == 5) { /* the fourth column of this batch's rows */
                 rc = slamem_stream_mismatches(g_streams[bi % (size_t)ngpu], &mism);
@@ -1084,10 +1108,51 @@ int main(int argc, char **argv) {
             remove(out_name);
             exit_message("No query files provided");
         }
+        if (o.match_type == 8) {
+            /* the table, in chunks of at most 16 M rows (24 bytes a row: the table of a 100 Mbp text never sits in one buffer):
+               the GPUs' tables added up, then a line per row of a record that has a count */
+            const uint64_t chunk = 16ull << 20, n = ref.total;
+            uint32_t *rows = NULL, *more = NULL;
+            uint64_t x0;
+            int r = 0;
+            double tp = now_s();
+            if (g_nstreams > 0) {
+                rows = (uint32_t *)slh_big_malloc((size_t)(chunk < n ? chunk : n) * 24 + 24);
+                if (ngpu > 1) more = (uint32_t *)slh_big_malloc((size_t)(chunk < n ? chunk : n) * 24 + 24);
+                if (!rows || (ngpu > 1 && !more)) pipeline_fail("Out of memory");
+            }
+            for (x0 = 0; g_nstreams > 0 && x0 < n; x0 += chunk) {
+                const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
+                uint64_t x = x0, k;
+                rc = slamem_pileup_counts_host(piles[0], x0, cnt, rows);
+                for (g = 1; rc == SLAMEM_OK && g < g_nstreams; g++) {
+                    rc = slamem_pileup_counts_host(piles[g], x0, cnt, more);
+                    for (k = 0; rc == SLAMEM_OK && k < cnt * 6; k++) rows[k] += more[k];
+                }
+                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the pileup from the GPU", rc); }
+                while (x < x0 + cnt && r < ref.num) { /* the pieces of the records inside the chunk; the separators are skipped */
+                    const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, end = start + ref.recs[r].size;
+                    uint64_t a, b;
+                    if (end <= x) { r++; continue; }
+                    a = start > x ? start : x;
+                    b = end < x0 + cnt ? end : x0 + cnt;
+                    if (a >= x0 + cnt) break;
+                    if (slh_format_pile_rows(&buf, ref.recs[r].name, (uint32_t)(a - start) + 1u, ref.chars + a, rows + (a - x0) * 6, b - a))
+                        pipeline_fail("Out of memory");
+                    x = b;
+                    if (b == end) r++;
+                }
+                if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
+                if (g_writer.failed) pipeline_fail("Cannot write output file");
+            }
+            free(rows);
+            free(more);
+            t_format += now_s() - tp;
+        }
         writer_finish(&g_writer);
         t_write = g_writer.seconds;
         if (g_writer.failed) pipeline_fail("Cannot write output file");
-        if (log_limit != 0 && (long)total_queries * strands > log_limit)
+        if (log_limit != 0 && o.match_type != 8 && (long)total_queries * strands > log_limit)
             say(":: ... (%ld more strand blocks matched; set SLAMEM_VERBOSE=1 for a line each)\n",
                    (long)total_queries * strands - log_limit);
     }
@@ -1125,6 +1190,7 @@ int main(int argc, char **argv) {
     {
         double a = now_s(), b, c, d;
         shutdown_pipeline();
+        for (i = 0; i < 16 && o.match_type == 8; i++) slamem_pileup_free(piles[i]);
         b = now_s();
         for (i = 0; i < ngpu; i++) slamem_index_free(gpus[i]);
         c = now_s();

@@ -738,6 +738,24 @@ int slh_parse_max_edits(int argc, char **argv, int *out) {
     return 0;
 }
 
+int slh_parse_min_mapq(int argc, char **argv, int *out) {
+    int i;
+    *out = 0;
+    for (i = 1; i < argc; i++) {
+        char *end;
+        long v;
+        /* the two letters "mi" decide; an 'm' option takes the next argument */
+        if (!two_letter_option(argv[i], 'm', 'i')) continue;
+        if (i == argc - 1) return -1;
+        errno = 0;
+        v = strtol(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 0 || v > 60) return -1;
+        *out = (int)v;
+        return 1;
+    }
+    return 0;
+}
+
 char *slh_append_to_basename(const char *filename, const char *extra) {
     int n = (int)strlen(filename), i;
     char *res;
@@ -842,6 +860,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type != 0 ? -1 : 6;
     if (slh_parse_argument(argc, argv, "PA", 0)) /* -paf: one mapping per read, written as PAF (a 'p' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 7;
+    if (slh_parse_argument(argc, argv, "PI", 0)) /* -pile: the per-base pileup of the mappings (a 'p' option takes no value) */
+        o->match_type = o->match_type != 0 ? -1 : 8;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;
@@ -897,6 +917,31 @@ static inline char *put_u32(char *p, uint32_t v) {
     else tmp[--n] = (char)('0' + v);
     memcpy(p, tmp + n, (size_t)(10 - n));
     return p + (10 - n);
+}
+
+int slh_format_pile_rows(slh_buffer *buf, const char *record_name, uint32_t first_pos, const char *letters, const uint32_t *counts,
+                         uint64_t rows) {
+    size_t nl = 0;
+    uint64_t i;
+    int k;
+    while (record_name[nl] != '\0' && record_name[nl] != ' ' && record_name[nl] != '\t') nl++;
+    for (i = 0; i < rows; i++) {
+        const uint32_t *c = counts + 6 * i;
+        char *p, l = letters[i];
+        if (!(c[0] | c[1] | c[2] | c[3] | c[4] | c[5])) continue;
+        if (buf_reserve(buf, nl + 96)) return -1;
+        p = buf->data + buf->len;
+        memcpy(p, record_name, nl);
+        p += nl;
+        *p++ = '\t';
+        p = put_u32(p, first_pos + (uint32_t)i);
+        *p++ = '\t';
+        *p++ = (l >= 'a' && l <= 'z') ? (char)(l - 32) : l;
+        for (k = 0; k < 6; k++) { *p++ = '\t'; p = put_u32(p, c[k]); }
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+    }
+    return 0;
 }
 
 int slh_format_block_aln(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *segs, const uint32_t *ops,

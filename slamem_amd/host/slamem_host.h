@@ -69,7 +69,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa...), -1 two of them */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa...), 8 pileup (-pi...), -1 two of them */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
@@ -94,6 +94,10 @@ int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out
  * it is not there (*out = -1: the default), 1 when it is, -1 when the value is missing, not an integer or out of range.  An
  * argument that starts with -max is never taken for -mam. */
 int slh_parse_max_edits(int argc, char **argv, int *out);
+/* -minq N (-mi...): the least mapping quality that counts in -pile, a whole number in [0, 60].  0 when it is not there (*out = 0),
+ * 1 when it is, -1 when the value is missing, not an integer or out of range.  It begins with -m, so its value is never taken
+ * for a file name. */
+int slh_parse_min_mapq(int argc, char **argv, int *out);
 /* AppendToBasename (tools.c:65-79): everything before the last '.' of the whole path + extra */
 char *slh_append_to_basename(const char *filename, const char *extra);
 
@@ -126,6 +130,11 @@ int slh_format_block_aln(slh_buffer *buf, const char *query_name, int reverse, c
 int slh_format_read_paf(slh_buffer *buf, const char *query_name, uint32_t query_len, int strand, uint32_t mapq, uint32_t s1,
                         uint32_t s2, const uint32_t *segs, const uint32_t *ops, const uint64_t *op_off, uint64_t count,
                         const slh_record *refs, const uint32_t *merged_start, int num_refs, uint64_t *sum_len_out);
+/* Rows of the -pile file: one line per row with a non-zero counter,
+ *   record name (cut at the first blank or tab)  position  reference letter (upper case)  A  C  G  T  D  I
+ * counts: six uint32 per row; letters[i]: the reference letter of row i; first_pos: the 1-based position of row 0 in its record. */
+int slh_format_pile_rows(slh_buffer *buf, const char *record_name, uint32_t first_pos, const char *letters, const uint32_t *counts,
+                         uint64_t rows);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
