@@ -473,6 +473,40 @@ int slamem_pileup_add_device(slamem_pileup *pile, const void *queries_dev, const
 int slamem_pileup_counts_device(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t *out_dev, void *stream);
 int slamem_pileup_counts_host(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t *out);
 
+/* ---- (b''') the sparse read-out of the pileup (option -sites) ------------------------------------------------
+ * The rows of [first, first + count) that a rule selects, compacted on the device in ascending position.  cnt[p] is row p as
+ * slamem_pileup_counts_* gives it, L(p) the text's letter at p in upper case, d(p) = A+C+G+T+D (a 64-bit sum).
+ *   SLAMEM_SITES_NONZERO (0)  row p is selected iff one of its six counters is not 0; bit k of its allele mask is set iff
+ *                          cnt[p][k] != 0 (k in the order A C G T D I).  The thresholds and the letter play no part.
+ *   SLAMEM_SITES_VARIANT (1)  row p is selected iff L(p) is one of A,C,G,T, d(p) >= min_depth and its mask is not 0, where bit
+ *                          k (k not the column of L(p)) is set iff cnt[p][k] > 0 and 100 * cnt[p][k] >= min_pct * d(p), the
+ *                          products formed in 64 bits.  min_depth is 1 to 2^31 - 1, min_pct 0 to 100.
+ * The result is three arrays of `total` entries: pos (uint64), counts (uint32 x 6) and alleles (uint8, the mask).  It depends on
+ * the table alone, not on how the table came to be.  VCF is not written from it: the accumulator knows how many reads insert in
+ * front of a row, not what they insert, and it counts a deletion per row, not per event.
+ *
+ *   slamem_pileup_sites_device  asynchronous on `stream` up to its one host round trip, which brings the number of selected
+ *                          rows to *total_out (a host pointer).  More than `capacity`: SLAMEM_ERR_CAPACITY with *total_out
+ *                          holding the need; the first `capacity` rows are written and nothing beyond them.  A range outside
+ *                          [0, n], a mode above 1, min_pct above 100, and in mode 1 a min_depth of 0 or of 2^31 and more:
+ *                          SLAMEM_ERR_ARG.  It shares the read-outs' scratch: two read-outs of one accumulator must not run at
+ *                          the same time.  The accumulator is not modified.
+ *   slamem_pileup_sites_host  the same into host memory; waits for the device first, so it sees the adds of every stream.
+ *   slamem_pileup_add_counts_device  cnt[first + i][k] += rows[i][k] for a table of count x 6 uint32, asynchronous on `stream`:
+ *                          atomic adds, so it commutes with the adds of other streams.  The rows of slamem_pileup_counts_* of
+ *                          another accumulator make this one's read-out the sum of both tables.
+ *   slamem_pileup_add_counts_host  the same from host memory; returns when the table is added. */
+#define SLAMEM_SITES_NONZERO 0u
+#define SLAMEM_SITES_VARIANT 1u
+int slamem_pileup_sites_device(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t mode, uint32_t min_depth,
+                               uint32_t min_pct, uint64_t capacity, uint64_t *pos_dev, uint32_t *counts_dev, uint8_t *alleles_dev,
+                               uint64_t *total_out, void *stream);
+int slamem_pileup_sites_host(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t mode, uint32_t min_depth,
+                             uint32_t min_pct, uint64_t capacity, uint64_t *pos, uint32_t *counts, uint8_t *alleles,
+                             uint64_t *total_out);
+int slamem_pileup_add_counts_device(slamem_pileup *pile, uint64_t first, uint64_t count, const uint32_t *rows_dev, void *stream);
+int slamem_pileup_add_counts_host(slamem_pileup *pile, uint64_t first, uint64_t count, const uint32_t *rows);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */

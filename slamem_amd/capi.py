@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "slamem_find_maps_workspace_bytes", "slamem_find_maps_device", "slamem_find_maps_host", "slamem_stream_maps",
     "slamem_pileup_create", "slamem_pileup_free", "slamem_pileup_reset", "slamem_pileup_add_device",
     "slamem_pileup_counts_device", "slamem_pileup_counts_host", "slamem_stream_set_pileup",
+    "slamem_pileup_sites_device", "slamem_pileup_sites_host", "slamem_pileup_add_counts_device", "slamem_pileup_add_counts_host",
     "slamem_stream_create", "slamem_stream_set_max_occ", "slamem_stream_set_max_gap", "slamem_stream_submit", "slamem_stream_submit_packed", "slamem_pack_reads", "slamem_stream_next",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
@@ -187,6 +188,10 @@ def _declare(L):
     L.slamem_pileup_add_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp]
     L.slamem_pileup_counts_device.argtypes = [vp, u64, u64, vp, vp]
     L.slamem_pileup_counts_host.argtypes = [vp, u64, u64, vp]
+    L.slamem_pileup_sites_device.argtypes = [vp, u64, u64, u32, u32, u32, u64, vp, vp, vp, C.POINTER(u64), vp]
+    L.slamem_pileup_sites_host.argtypes = [vp, u64, u64, u32, u32, u32, u64, vp, vp, vp, C.POINTER(u64)]
+    L.slamem_pileup_add_counts_device.argtypes = [vp, u64, u64, vp, vp]
+    L.slamem_pileup_add_counts_host.argtypes = [vp, u64, u64, vp]
     L.slamem_stream_set_pileup.argtypes = [vp, vp, u32]
     L.slamem_stream_mismatches.argtypes = [vp, C.POINTER(C.POINTER(u32))]
     L.slamem_stream_submit.argtypes = [vp, vp, vp, u32, u32]

@@ -16,6 +16,12 @@
 //                  the read-out of rows [first, first + count): the sums of diff per tile of kPileTile entries, their exclusive
 //                  prefix sums (one workgroup), and per tile the running sum of diff = match[p], which goes to the column of the
 //                  text's letter at p (none when it is not A,C,G,T) on top of cnt.  Nothing of the accumulator is written.
+//   k_sites_count / k_sites_tile_scan / k_sites_emit
+//                  the sparse read-out (-sites): per tile the number of rows of the range that the rule selects,
+//                  the tiles' exclusive prefix sums, and the selected rows written in ascending p at base + rank in the tile
+//                  (ballots and popcounts in a wave, the waves' totals through LDS; no atomics).  The rule is evaluated twice
+//                  rather than kept as a bitmap: see 4.17.
+//   k_pile_add_counts  a table added into cnt (atomicAdd, zeros skipped; diff is not touched)
 // Counters are 32 bits wide and every sum is taken modulo 2^32: a true depth of 2^31 or more at one row is outside the contract.
 #include "common.h"
 
@@ -254,16 +260,13 @@ __global__ void __launch_bounds__(1024) k_pile_tile_scan(uint32_t* __restrict__ 
     for (uint64_t x = s; x < e; x++) { const uint32_t t = tile[x]; tile[x] = run; run += t; }
 }
 
-// a workgroup per tile of rows: match[p] = the sum of diff[0 .. p], then rows [first, first + count) of the table
-__global__ void __launch_bounds__(256) k_pile_counts(const int32_t* __restrict__ diff, const uint32_t* __restrict__ cnt,
-                                                     const uint32_t* __restrict__ tile, const TextPlanes* __restrict__ tpl, uint64_t tile0,
-                                                     uint64_t first, uint64_t count, uint32_t* __restrict__ out) {
-    __shared__ uint32_t match[kPileTile];
-    __shared__ uint8_t code[kPileTile];
-    __shared__ uint32_t wsum[4];
-    const uint64_t t = tile0 + blockIdx.x, base = t * kPileTile, end = first + count;  // (end <= n)
+// tile t of a read-out that ends at `end` (<= n): match[p] = the sum of diff[0 .. p] and the column of the text's letter (4: none
+// of A,C,G,T, or a row at or behind `end`) of its kPileTile rows, staged in LDS.  A lane takes kPileTile / 256 consecutive entries.
+__device__ __forceinline__ void pile_tile_stage(const int32_t* __restrict__ diff, const uint32_t* __restrict__ tile,
+                                                const TextPlanes* __restrict__ tpl, uint64_t t, uint64_t end, uint32_t* match,
+                                                uint8_t* code, uint32_t* wsum) {
+    const uint64_t base = t * kPileTile;
     constexpr uint32_t per = kPileTile / 256u;
-    // a lane takes `per` consecutive entries
     uint32_t v[per], run = 0;
     const uint64_t x0 = base + (uint64_t)threadIdx.x * per;
 #pragma unroll
@@ -297,6 +300,17 @@ __global__ void __launch_bounds__(256) k_pile_counts(const int32_t* __restrict__
         code[at] = (uint8_t)c;
     }
     __syncthreads();
+}
+
+// a workgroup per tile of rows: match[p] = the sum of diff[0 .. p], then rows [first, first + count) of the table
+__global__ void __launch_bounds__(256) k_pile_counts(const int32_t* __restrict__ diff, const uint32_t* __restrict__ cnt,
+                                                     const uint32_t* __restrict__ tile, const TextPlanes* __restrict__ tpl, uint64_t tile0,
+                                                     uint64_t first, uint64_t count, uint32_t* __restrict__ out) {
+    __shared__ uint32_t match[kPileTile];
+    __shared__ uint8_t code[kPileTile];
+    __shared__ uint32_t wsum[4];
+    const uint64_t t = tile0 + blockIdx.x, base = t * kPileTile, end = first + count;  // (end <= n)
+    pile_tile_stage(diff, tile, tpl, t, end, match, code, wsum);
     // the rows of the tile inside the range, counter by counter
     const uint64_t lo = base > first ? base : first, hi = base + kPileTile < end ? base + kPileTile : end;
     if (hi <= lo) return;
@@ -308,6 +322,148 @@ __global__ void __launch_bounds__(256) k_pile_counts(const int32_t* __restrict__
         const uint32_t at = (uint32_t)(lo - base) + row;
         dst[w] = src[w] + (code[at] == col ? match[at] : 0u);
     }
+}
+
+
+// ---- the sparse read-out (-sites) ------------------------------------------------------------------------------------------
+
+struct SitesRule {
+    uint32_t mode;       // 0: any counter non-zero; 1: what differs from the text's letter, with enough support
+    uint32_t min_depth;  // mode 1: A+C+G+T+D at least this
+    uint32_t min_pct;    // mode 1: 100 * counter >= min_pct * depth
+};
+
+// row x of the table as the read-out gives it: cnt[x], and match on top of the column of the text's letter
+__device__ __forceinline__ void sites_row(const uint32_t* __restrict__ cnt, uint64_t x, uint32_t letter, uint32_t match, uint32_t c[6]) {
+    const uint2* r = reinterpret_cast<const uint2*>(cnt + x * 6u);  // (24 bytes a row: 8-byte aligned)
+    const uint2 a = r[0], b = r[1], d = r[2];
+    c[0] = a.x; c[1] = a.y; c[2] = b.x; c[3] = b.y; c[4] = d.x; c[5] = d.y;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) c[k] += letter == k ? match : 0u;
+}
+
+// the allele mask of a row (bit k: column k of A C G T D I); 0: the row is not selected.  Sums and products in 64 bits.
+__device__ __forceinline__ uint32_t sites_mask(const uint32_t c[6], uint32_t letter, const SitesRule& r) {
+    uint32_t m = 0;
+    if (r.mode == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) m |= (c[k] != 0u ? 1u : 0u) << k;
+        return m;
+    }
+    if (letter >= 4u) return 0u;
+    const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4];
+    if (d < r.min_depth) return 0u;
+    const uint64_t need = (uint64_t)r.min_pct * d;
+#pragma unroll
+    for (uint32_t k = 0; k < 6u; k++)
+        if (k != letter && c[k] != 0u && 100ull * c[k] >= need) m |= 1u << k;
+    return m;
+}
+
+// the mask of row `at` of the staged tile (0 outside [lo, hi)); rows are taken 256 apart, so a wave reads 64 neighbouring rows
+__device__ __forceinline__ uint32_t sites_tile_mask(const uint32_t* __restrict__ cnt, uint64_t base, uint32_t at, uint64_t lo, uint64_t hi,
+                                                    const uint32_t* match, const uint8_t* code, const SitesRule& r) {
+    const uint64_t x = base + at;
+    if (x < lo || x >= hi) return 0u;
+    uint32_t c[6];
+    sites_row(cnt, x, code[at], match[at], c);
+    return sites_mask(c, code[at], r);
+}
+
+// a workgroup per tile of rows: sel[blockIdx.x] = how many rows of the tile inside [first, first + count) the rule selects
+__global__ void __launch_bounds__(256) k_sites_count(const int32_t* __restrict__ diff, const uint32_t* __restrict__ cnt,
+                                                     const uint32_t* __restrict__ tile, const TextPlanes* __restrict__ tpl, uint64_t tile0,
+                                                     uint64_t first, uint64_t count, SitesRule rule, uint64_t* __restrict__ sel) {
+    __shared__ uint32_t match[kPileTile];
+    __shared__ uint8_t code[kPileTile];
+    __shared__ uint32_t wsum[4];
+    const uint64_t t = tile0 + blockIdx.x, base = t * kPileTile, end = first + count;  // (end <= n)
+    pile_tile_stage(diff, tile, tpl, t, end, match, code, wsum);
+    const uint64_t lo = base > first ? base : first, hi = base + kPileTile < end ? base + kPileTile : end;
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kPileTile / 256u; j++)
+        mine += sites_tile_mask(cnt, base, j * 256u + threadIdx.x, lo, hi, match, code, rule) != 0u ? 1u : 0u;
+    const uint32_t total = block_sum_256(mine, wsum);  // (pile_tile_stage ended with a barrier: wsum is free)
+    if (threadIdx.x == 0) sel[blockIdx.x] = total;
+}
+
+// in place: sel[t] = the sum of the tiles in front of t, and sel[tiles] = the sum of all (one workgroup of 1024 lanes)
+__global__ void __launch_bounds__(1024) k_sites_tile_scan(uint64_t* __restrict__ sel, uint64_t tiles) {
+    __shared__ uint64_t part[1024];
+    const uint64_t per = (tiles + 1023u) / 1024u;
+    const uint64_t s = (uint64_t)threadIdx.x * per < tiles ? (uint64_t)threadIdx.x * per : tiles, e = s + per < tiles ? s + per : tiles;
+    uint64_t v = 0;
+    for (uint64_t x = s; x < e; x++) v += sel[x];
+    part[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t run = 0;
+        for (uint32_t k = 0; k < 1024u; k++) { const uint64_t t = part[k]; part[k] = run; run += t; }
+        sel[tiles] = run;
+    }
+    __syncthreads();
+    uint64_t run = part[threadIdx.x];
+    for (uint64_t x = s; x < e; x++) { const uint64_t t = sel[x]; sel[x] = run; run += t; }
+}
+
+// a workgroup per tile: its selected rows go to sel[blockIdx.x] + rank in the tile, rows behind `capacity` are dropped.  The order
+// inside the tile is that of the rows: pass j takes rows j * 256 .. j * 256 + 255, wave w of it 64 neighbours, a lane's rank in
+// its wave is the popcount of the ballot below it.
+__global__ void __launch_bounds__(256) k_sites_emit(const int32_t* __restrict__ diff, const uint32_t* __restrict__ cnt,
+                                                    const uint32_t* __restrict__ tile, const TextPlanes* __restrict__ tpl, uint64_t tile0,
+                                                    uint64_t first, uint64_t count, SitesRule rule, const uint64_t* __restrict__ sel,
+                                                    uint64_t capacity, uint64_t* __restrict__ pos, uint32_t* __restrict__ counts,
+                                                    uint8_t* __restrict__ alleles) {
+    __shared__ uint32_t match[kPileTile];
+    __shared__ uint8_t code[kPileTile];
+    __shared__ uint32_t wsum[4];
+    constexpr uint32_t per = kPileTile / 256u;
+    __shared__ uint32_t wcnt[per * 4u];
+    const uint64_t out0 = sel[blockIdx.x];
+    if (sel[blockIdx.x + 1] == out0 || out0 >= capacity) return;  // (the whole workgroup: nothing selected, or no room left)
+    const uint64_t t = tile0 + blockIdx.x, base = t * kPileTile, end = first + count;  // (end <= n)
+    pile_tile_stage(diff, tile, tpl, t, end, match, code, wsum);
+    const uint64_t lo = base > first ? base : first, hi = base + kPileTile < end ? base + kPileTile : end;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t mask[per], below[per];
+#pragma unroll
+    for (uint32_t j = 0; j < per; j++) {
+        mask[j] = sites_tile_mask(cnt, base, j * 256u + threadIdx.x, lo, hi, match, code, rule);
+        const unsigned long long b = __ballot(mask[j] != 0u);
+        below[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0u) wcnt[j * 4u + wave] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    uint32_t run = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < per; j++) {
+        uint32_t mine = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; w++) {
+            if (w == wave) mine = run;
+            run += wcnt[j * 4u + w];
+        }
+        const uint64_t o = out0 + mine + below[j];
+        if (mask[j] == 0u || o >= capacity) continue;
+        const uint32_t at = j * 256u + threadIdx.x;
+        uint32_t c[6];
+        sites_row(cnt, base + at, code[at], match[at], c);
+        pos[o] = base + at;
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) counts[o * 6u + k] = c[k];
+        alleles[o] = (uint8_t)mask[j];
+    }
+}
+
+// cnt[first + i][k] += rows[i][k]: a lane per counter, zeros skipped, rows at or behind n dropped
+__global__ void __launch_bounds__(256) k_pile_add_counts(uint32_t* __restrict__ cnt, uint64_t n, uint64_t first, uint64_t count,
+                                                         const uint32_t* __restrict__ rows) {
+    const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (w >= count * 6u) return;
+    const uint32_t v = rows[w];
+    const uint64_t at = first * 6u + w;
+    if (v != 0u && at < n * 6u) atomicAdd(&cnt[at], v);
 }
 
 }  // namespace
@@ -323,6 +479,7 @@ struct slamem_pileup {
     int32_t* diff;
     uint32_t* cnt;
     uint32_t* tile;  // the read-out's tile sums: n / kPileTile + 2 words
+    uint64_t* sel;   // the sparse read-out's selected rows per tile: n / kPileTile + 2 words of 64 bits
 };
 
 namespace slamem {
@@ -371,7 +528,7 @@ int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
     SLAMEM_HIP(hipSetDevice(idx->device));
     const uint64_t n = idx->hdr.n;
     const uint64_t tiles = n / kPileTile + 2;
-    const uint64_t need = (n + 1) * 4 + n * 24 + tiles * 4;
+    const uint64_t need = (n + 1) * 4 + n * 24 + tiles * 12;
     size_t free_b = 0, total_b = 0;
     SLAMEM_HIP(hipMemGetInfo(&free_b, &total_b));
     if (need > free_b) {
@@ -382,10 +539,11 @@ int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
     slamem_pileup* p = new (std::nothrow) slamem_pileup();
     if (!p) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     p->idx = idx; p->device = idx->device; p->n = (uint32_t)n;
-    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr;
+    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->diff), (n + 1) * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->cnt), n * 24 + 16);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->tile), tiles * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->sel), tiles * 8);
     if (e == hipSuccess) e = hipMemset(p->diff, 0, (n + 1) * 4);
     if (e == hipSuccess) e = hipMemset(p->cnt, 0, n * 24);
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -403,6 +561,7 @@ int slamem_pileup_free(slamem_pileup* p) {
     if (p->diff) (void)hipFree(p->diff);
     if (p->cnt) (void)hipFree(p->cnt);
     if (p->tile) (void)hipFree(p->tile);
+    if (p->sel) (void)hipFree(p->sel);
     delete p;
     return SLAMEM_OK;
 }
@@ -468,6 +627,121 @@ int slamem_pileup_counts_host(slamem_pileup* pile, uint64_t first, uint64_t coun
     (void)hipFree(d);
     if (rc != SLAMEM_OK) return rc;
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_sites_device(slamem_pileup* pile, uint64_t first, uint64_t count, uint32_t mode, uint32_t min_depth, uint32_t min_pct,
+                               uint64_t capacity, uint64_t* pos_dev, uint32_t* counts_dev, uint8_t* alleles_dev, uint64_t* total_out,
+                               void* stream) {
+    if (!pile || !total_out || (capacity && (!pos_dev || !counts_dev || !alleles_dev))) {
+        set_error("slamem_pileup_sites_device: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    *total_out = 0;
+    if (first > pile->n || count > pile->n - first) {
+        set_error("slamem_pileup_sites_device: rows %llu .. %llu + %llu lie outside the text's %u", (unsigned long long)first,
+                  (unsigned long long)first, (unsigned long long)count, pile->n);
+        return SLAMEM_ERR_ARG;
+    }
+    if (mode > 1u) { set_error("slamem_pileup_sites_device: the mode is 0 (non-zero rows) or 1 (variant rows), not %u", mode); return SLAMEM_ERR_ARG; }
+    if (min_pct > 100u) { set_error("slamem_pileup_sites_device: the least share is 0 to 100 percent, not %u", min_pct); return SLAMEM_ERR_ARG; }
+    if (mode == 1u && (min_depth == 0u || min_depth >= 0x80000000u)) {
+        set_error("slamem_pileup_sites_device: the least depth is 1 to 2^31 - 1, not %u", min_depth);
+        return SLAMEM_ERR_ARG;
+    }
+    if (count == 0) return SLAMEM_OK;
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t end = first + count, tiles = (end + kPileTile - 1) / kPileTile, tile0 = first / kPileTile, mine = tiles - tile0;
+    const SitesRule rule{mode, min_depth, min_pct};
+    hipLaunchKernelGGL(k_pile_tile_sums, dim3((unsigned)tiles), dim3(256), 0, st, (const int32_t*)pile->diff, end, pile->tile);
+    SLAMEM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_pile_tile_scan, dim3(1), dim3(1024), 0, st, pile->tile, tiles);
+    SLAMEM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_sites_count, dim3((unsigned)mine), dim3(256), 0, st, (const int32_t*)pile->diff, (const uint32_t*)pile->cnt,
+                       (const uint32_t*)pile->tile, pile->idx->view.tpl, tile0, first, count, rule, pile->sel);
+    SLAMEM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_sites_tile_scan, dim3(1), dim3(1024), 0, st, pile->sel, mine);  // (mine + 1 <= n / kPileTile + 2 words)
+    SLAMEM_HIP(hipGetLastError());
+    if (capacity) {  // rows behind `capacity` are dropped on the device, so the pass may run before the total is known
+        hipLaunchKernelGGL(k_sites_emit, dim3((unsigned)mine), dim3(256), 0, st, (const int32_t*)pile->diff, (const uint32_t*)pile->cnt,
+                           (const uint32_t*)pile->tile, pile->idx->view.tpl, tile0, first, count, rule, (const uint64_t*)pile->sel,
+                           capacity, pos_dev, counts_dev, alleles_dev);
+        SLAMEM_HIP(hipGetLastError());
+    }
+    uint64_t total = 0;  // the call's one host round trip
+    SLAMEM_HIP(hipMemcpyAsync(&total, pile->sel + mine, 8, hipMemcpyDeviceToHost, st));
+    SLAMEM_HIP(hipStreamSynchronize(st));
+    *total_out = total;
+    if (total > capacity) {
+        set_error("slamem_pileup_sites_device: %llu rows are selected, the buffers hold %llu", (unsigned long long)total,
+                  (unsigned long long)capacity);
+        return SLAMEM_ERR_CAPACITY;
+    }
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_sites_host(slamem_pileup* pile, uint64_t first, uint64_t count, uint32_t mode, uint32_t min_depth, uint32_t min_pct,
+                             uint64_t capacity, uint64_t* pos, uint32_t* counts, uint8_t* alleles, uint64_t* total_out) {
+    if (!pile || !total_out || (capacity && (!pos || !counts || !alleles))) {
+        set_error("slamem_pileup_sites_host: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the table that is read)
+    const uint64_t room = capacity < count ? capacity : count;  // (a range selects at most its rows)
+    void* d = nullptr;
+    if (room) SLAMEM_HIP(hipMalloc(&d, room * 33));
+    char* b = static_cast<char*>(d);
+    uint64_t* pd = reinterpret_cast<uint64_t*>(b);
+    uint32_t* cd = reinterpret_cast<uint32_t*>(b + room * 8);
+    uint8_t* ad = reinterpret_cast<uint8_t*>(b + room * 32);
+    const int rc = slamem_pileup_sites_device(pile, first, count, mode, min_depth, min_pct, room, pd, cd, ad, total_out, nullptr);
+    hipError_t e = hipSuccess;
+    if (rc == SLAMEM_OK || rc == SLAMEM_ERR_CAPACITY) {
+        const uint64_t got = *total_out < room ? *total_out : room;
+        if (got) e = hipMemcpy(pos, pd, got * 8, hipMemcpyDeviceToHost);
+        if (got && e == hipSuccess) e = hipMemcpy(counts, cd, got * 24, hipMemcpyDeviceToHost);
+        if (got && e == hipSuccess) e = hipMemcpy(alleles, ad, got, hipMemcpyDeviceToHost);
+    }
+    if (d) (void)hipFree(d);
+    if (rc != SLAMEM_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_add_counts_device(slamem_pileup* pile, uint64_t first, uint64_t count, const uint32_t* rows_dev, void* stream) {
+    if (!pile || (count && !rows_dev)) { set_error("slamem_pileup_add_counts_device: null argument"); return SLAMEM_ERR_ARG; }
+    if (first > pile->n || count > pile->n - first) {
+        set_error("slamem_pileup_add_counts_device: rows %llu .. %llu + %llu lie outside the text's %u", (unsigned long long)first,
+                  (unsigned long long)first, (unsigned long long)count, pile->n);
+        return SLAMEM_ERR_ARG;
+    }
+    if (count == 0) return SLAMEM_OK;
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    hipLaunchKernelGGL(k_pile_add_counts, dim3(pile_grid(count * 6u, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), pile->cnt,
+                       (uint64_t)pile->n, first, count, rows_dev);
+    SLAMEM_HIP(hipGetLastError());
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_add_counts_host(slamem_pileup* pile, uint64_t first, uint64_t count, const uint32_t* rows) {
+    if (!pile || (count && !rows)) { set_error("slamem_pileup_add_counts_host: null argument"); return SLAMEM_ERR_ARG; }
+    if (first > pile->n || count > pile->n - first) {
+        set_error("slamem_pileup_add_counts_host: rows %llu .. %llu + %llu lie outside the text's %u", (unsigned long long)first,
+                  (unsigned long long)first, (unsigned long long)count, pile->n);
+        return SLAMEM_ERR_ARG;
+    }
+    if (count == 0) return SLAMEM_OK;
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    void* d = nullptr;
+    SLAMEM_HIP(hipMalloc(&d, count * 24));
+    hipError_t e = hipMemcpy(d, rows, count * 24, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? slamem_pileup_add_counts_device(pile, first, count, static_cast<const uint32_t*>(d), nullptr) : SLAMEM_OK;
+    if (e == hipSuccess && rc == SLAMEM_OK) e = hipDeviceSynchronize();
+    (void)hipFree(d);
+    if (rc != SLAMEM_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "slamem_pileup_add_counts_host", __FILE__, __LINE__);
     return SLAMEM_OK;
 }
 

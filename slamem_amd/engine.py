@@ -21,6 +21,7 @@ MAP_DTYPE = np.dtype([("strand", "u1"), ("mapq", "u1"), ("s1", "<u4"), ("s2", "<
 _MAP_ABI = np.dtype([("s1", "<u4"), ("s2", "<u4"), ("strand", "u1"), ("mapq", "u1"), ("reserved", "u1", (2,))])  # slamem_map
 EDITS_DEFAULT = 0xFFFFFFFF  # SLAMEM_ALN_EDITS_DEFAULT: "the default 31" in the C ABI (0 is a value of its own)
 CIGAR_OPS = {7: "=", 8: "X", 1: "I", 2: "D"}  # BAM's codes; an operation is length << 4 | code
+SITES_NONZERO, SITES_VARIANT = 0, 1  # the rules of Pileup.sites (SLAMEM_SITES_*)
 PILE_LANE_OPS = 32  # -pile: a segment of up to this many operations is walked by one lane, a longer one by a wave (pile_filter.hip)
 
 
@@ -431,6 +432,52 @@ class Pileup:
             capi.check(capi.lib().slamem_pileup_counts_device(self._h, first, count, _ptr(out), _stream_handle(dev)))
             torch.cuda.current_stream(dev).synchronize()
         return out[:max(count, 0)].cpu().numpy().view(np.uint32)
+
+    def sites(self, min_depth: int = 4, min_pct: int = 20, mode: int = SITES_VARIANT, first: int = 0, count=None, capacity=None):
+        """The rows of [first, first + count) that the rule selects, compacted on the device, as (pos uint64 (m,),
+        counts uint32 (m, 6), alleles uint8 (m,)) in ascending position.  SITES_VARIANT: the text's letter is one of A,C,G,T, the
+        depth A+C+G+T+D is at least min_depth, and a counter other than the letter's own is > 0 and at least min_pct percent of
+        the depth; bit k of alleles says which (A C G T D I).  SITES_NONZERO: any counter is not 0.  capacity: rows of room for the
+        first attempt (default: one in 64 of the range, at least 4,096); when more are selected the call is made once more with
+        the need it reported."""
+        first = int(first)
+        count = self.index.n - first if count is None else int(count)
+        dev = self.index.device
+        cap = max(4096, count // 64) if capacity is None else int(capacity)
+        total = C.c_uint64()
+        with torch.cuda.device(dev):
+            for attempt in (0, 1):
+                pos = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+                rows = torch.empty((max(cap, 1), 6), dtype=torch.int32, device=dev)
+                alleles = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+                rc = capi.lib().slamem_pileup_sites_device(self._h, first, count, int(mode), int(min_depth), int(min_pct), cap, _ptr(pos),
+                                                           _ptr(rows), _ptr(alleles), C.byref(total), _stream_handle(dev))
+                if rc != capi.SLAMEM_ERR_CAPACITY or attempt:
+                    break
+                cap = int(total.value)
+            capi.check(rc)
+        m = int(total.value)
+        return pos[:m].cpu().numpy().view(np.uint64), rows[:m].cpu().numpy().view(np.uint32), alleles[:m].cpu().numpy()
+
+    def add_counts(self, table, first: int = 0) -> None:
+        """Adds a table of (m, 6) counters A C G T D I -- a numpy array or a tensor on the accumulator's device, 32-bit -- to rows
+        [first, first + m).  With counts() of another accumulator of the same text the read-out becomes the sum of both."""
+        dev = self.index.device
+        if isinstance(table, torch.Tensor):
+            t = table
+            if t.dtype not in (torch.int32, torch.uint32) or t.device != dev:
+                raise ValueError("add_counts takes a 32-bit tensor on the accumulator's device")
+        else:
+            a = np.asarray(table)
+            if a.dtype != np.uint32:
+                raise ValueError("add_counts takes a uint32 array")
+            t = torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(dev)
+        if t.dim() != 2 or t.shape[1] != 6:
+            raise ValueError("add_counts takes a table of shape (m, 6)")
+        t = t.contiguous()
+        with torch.cuda.device(dev):
+            capi.check(capi.lib().slamem_pileup_add_counts_device(self._h, int(first), t.shape[0], _ptr(t), _stream_handle(dev)))
+            torch.cuda.current_stream(dev).synchronize()  # (the table's tensor goes when the caller returns)
 
     def reset(self) -> None:
         capi.check(capi.lib().slamem_pileup_reset(self._h))

@@ -591,6 +591,9 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-paf\tone mapping per read with a mapping quality, written as PAF with a cg:Z: CIGAR; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-pile\tper-base pileup of the mappings of -paf: record, position, letter and the counts A C G T D I; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-minq\twith -pile: least mapping quality of a read that counts, 0 to 60 (default=0)\n");
+    printf("\t-sites\tvariant sites of the pileup: the rows of -pile where the reads differ from the reference, with a tenth column, the calls; -mgap, -pen, -xdrop, -maxed, -minq apply\n");
+    printf("\t-mdep\twith -sites: least depth A+C+G+T+D of a site (default=4)\n");
+    printf("\t-mpct\twith -sites: least share of the depth a call needs, in percent, 0 to 100 (default=20)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
     printf("\t-b\tprocess both forward and reverse strands\n");
@@ -616,6 +619,7 @@ int main(int argc, char **argv) {
     FILE *out;
     slamem_index *idx = NULL, *gpus[16];
     int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1, min_mapq = 0;
+    int sites = 0, min_depth = 4, min_pct = 20; /* -sites: match type 8 with the sparse read-out */
     slamem_pileup *piles[16];
     double t0;
     long long total_matches = 0, total_sum = 0;
@@ -637,7 +641,9 @@ int main(int argc, char **argv) {
         if (argc != 3) { printf("Usage: %s -c <fasta_file>\n\n", argv[0]); return -1; }
         return slh_clean_fasta(argv[2], stdout);
     }
+    sites = slh_parse_argument(argc, argv, "SI", 0);
     if (o.match_type < 0) { /* before any GPU work */
+        if (sites) exit_message("Option -sites excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf and -pile");
         if (slh_parse_argument(argc, argv, "PI", 0)) exit_message("Option -pile excludes -mam, -mum, -smem, -chain, -ext, -aln and -paf");
         if (slh_parse_argument(argc, argv, "PA", 0)) exit_message("Option -paf excludes -mam, -mum, -smem, -chain, -ext and -aln");
         if (slh_parse_argument(argc, argv, "AL", 0)) exit_message("Option -aln excludes -mam, -mum, -smem, -chain and -ext");
@@ -669,6 +675,12 @@ int main(int argc, char **argv) {
     switch (slh_parse_min_mapq(argc, argv, &min_mapq)) {
     case -1: exit_message("Option -minq needs a whole number from 0 to 60"); break;
     case 1: if (o.match_type != 8) exit_message("Option -minq needs -pile"); break;
+    default: break;
+    }
+    switch (slh_parse_sites_params(argc, argv, &min_depth, &min_pct)) {
+    case -1: exit_message("Option -mdep needs a whole number of at least 1"); break;
+    case -2: exit_message("Option -mpct needs a whole number from 0 to 100"); break;
+    case 1: if (!sites) exit_message("Options -mdep and -mpct need -sites"); break;
     default: break;
     }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
@@ -780,6 +792,7 @@ int main(int argc, char **argv) {
         say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", max_gap > 0 ? max_gap : 5000,
             ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
     if (o.match_type == 8) say(" ; minimum mapping quality = %d", min_mapq);
+    if (sites) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
     say("\n");
     out = fopen(out_name, "w");
     if (!out) {
@@ -1108,7 +1121,62 @@ int main(int argc, char **argv) {
             remove(out_name);
             exit_message("No query files provided");
         }
-        if (o.match_type == 8) {
+        if (o.match_type == 8 && sites) {
+            /* the tables of GPUs 1.. are added into GPU 0's, in chunks of 16 M rows; then GPU 0 applies the rule to the sum range
+               after range and only the selected rows come back: a line each, the separators between records skipped */
+            const uint64_t chunk = 16ull << 20, n = ref.total;
+            uint64_t x0, cap = 1ull << 20, *pos = NULL;
+            uint32_t *rows = NULL;
+            uint8_t *alleles = NULL;
+            int r = 0;
+            double tp = now_s();
+            if (g_nstreams > 1) {
+                rows = (uint32_t *)slh_big_malloc((size_t)(chunk < n ? chunk : n) * 24 + 24);
+                if (!rows) pipeline_fail("Out of memory");
+                for (g = 1; g < g_nstreams; g++)
+                    for (x0 = 0; x0 < n; x0 += chunk) {
+                        const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
+                        rc = slamem_pileup_counts_host(piles[g], x0, cnt, rows);
+                        if (rc == SLAMEM_OK) rc = slamem_pileup_add_counts_host(piles[0], x0, cnt, rows);
+                        if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("adding up the pileups of the GPUs", rc); }
+                    }
+                free(rows);
+                rows = NULL;
+            }
+            for (x0 = 0; g_nstreams > 0 && x0 < n; x0 += chunk) {
+                const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
+                uint64_t total = 0, k = 0;
+                for (;;) { /* a range that selects more rows than there is room for says how many: once more with that room */
+                    if (!pos) {
+                        pos = (uint64_t *)malloc((size_t)cap * 8);
+                        rows = (uint32_t *)malloc((size_t)cap * 24);
+                        alleles = (uint8_t *)malloc((size_t)cap);
+                        if (!pos || !rows || !alleles) pipeline_fail("Out of memory");
+                    }
+                    rc = slamem_pileup_sites_host(piles[0], x0, cnt, SLAMEM_SITES_VARIANT, (uint32_t)min_depth, (uint32_t)min_pct, cap, pos,
+                                                  rows, alleles, &total);
+                    if (rc != SLAMEM_ERR_CAPACITY || total <= cap) break;
+                    free(pos); free(rows); free(alleles);
+                    pos = NULL;
+                    cap = total;
+                }
+                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the variant sites from the GPU", rc); }
+                while (k < total && r < ref.num) { /* the rows of one record after the other */
+                    const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, end = start + ref.recs[r].size;
+                    uint64_t e = k;
+                    if (pos[k] >= end) { r++; continue; }
+                    if (pos[k] < start) { k++; continue; } /* (a separator: no record's row) */
+                    while (e < total && pos[e] < end) e++;
+                    if (slh_format_site_rows(&buf, ref.recs[r].name, start, ref.chars, pos + k, rows + k * 6, alleles + k, e - k))
+                        pipeline_fail("Out of memory");
+                    k = e;
+                }
+                if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
+                if (g_writer.failed) pipeline_fail("Cannot write output file");
+            }
+            free(pos); free(rows); free(alleles);
+            t_format += now_s() - tp;
+        } else if (o.match_type == 8) {
             /* the table, in chunks of at most 16 M rows (24 bytes a row: the table of a 100 Mbp text never sits in one buffer):
                the GPUs' tables added up, then a line per row of a record that has a count */
             const uint64_t chunk = 16ull << 20, n = ref.total;
@@ -1162,7 +1230,7 @@ int main(int argc, char **argv) {
                (int)(total_matches / total_queries), MATCH_NAME(o.match_type), total_matches,
                (int)(total_matches ? total_sum / total_matches : 0));
     fflush(stdout);
-    printf("> Saving %ss to <%s> ... ", MATCH_NAME(o.match_type), out_name);
+    printf("> Saving %ss to <%s> ... ", sites ? "variant site" : MATCH_NAME(o.match_type), out_name);
     if (fflush(out) != 0 || ferror(out)) exit_message("Cannot write output file");
     if (getenv("SLAMEM_FULL_TEARDOWN") != NULL && fclose(out) != 0) exit_message("Cannot write output file");
     t_end1 = now_s();

@@ -756,6 +756,30 @@ int slh_parse_min_mapq(int argc, char **argv, int *out) {
     return 0;
 }
 
+int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out) {
+    int i, seen = 0;
+    *min_depth_out = 4;
+    *min_pct_out = 20;
+    for (i = 1; i < argc; i++) {
+        char *end;
+        long v;
+        /* the two letters "md" and "mp" decide; an 'm' option takes the next argument */
+        int dep = two_letter_option(argv[i], 'm', 'd'), pct = two_letter_option(argv[i], 'm', 'p');
+        if (!dep && !pct) continue;
+        if (i == argc - 1) return dep ? -1 : -2;
+        errno = 0;
+        v = strtol(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0') return dep ? -1 : -2;
+        if (dep && (v < 1 || v > 0x7FFFFFFFL)) return -1;
+        if (pct && (v < 0 || v > 100)) return -2;
+        if (dep) *min_depth_out = (int)v;
+        else *min_pct_out = (int)v;
+        seen = 1;
+        i++;
+    }
+    return seen;
+}
+
 char *slh_append_to_basename(const char *filename, const char *extra) {
     int n = (int)strlen(filename), i;
     char *res;
@@ -862,6 +886,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type != 0 ? -1 : 7;
     if (slh_parse_argument(argc, argv, "PI", 0)) /* -pile: the per-base pileup of the mappings (a 'p' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 8;
+    if (slh_parse_argument(argc, argv, "SI", 0)) /* -sites: the variant sites of the pileup: match type 8 with another read-out (an 's' option takes no value) */
+        o->match_type = o->match_type != 0 ? -1 : 8;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;
@@ -938,6 +964,38 @@ int slh_format_pile_rows(slh_buffer *buf, const char *record_name, uint32_t firs
         *p++ = '\t';
         *p++ = (l >= 'a' && l <= 'z') ? (char)(l - 32) : l;
         for (k = 0; k < 6; k++) { *p++ = '\t'; p = put_u32(p, c[k]); }
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+    }
+    return 0;
+}
+
+int slh_format_site_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, const char *text, const uint64_t *pos,
+                         const uint32_t *counts, const uint8_t *alleles, uint64_t rows) {
+    size_t nl = 0;
+    uint64_t i;
+    int k;
+    while (record_name[nl] != '\0' && record_name[nl] != ' ' && record_name[nl] != '\t') nl++;
+    for (i = 0; i < rows; i++) {
+        const uint32_t *c = counts + 6 * i;
+        char *p, l = text[pos[i]];
+        int some = 0;
+        if (buf_reserve(buf, nl + 112)) return -1;
+        p = buf->data + buf->len;
+        memcpy(p, record_name, nl);
+        p += nl;
+        *p++ = '\t';
+        p = put_u32(p, (uint32_t)(pos[i] - record_start) + 1u);
+        *p++ = '\t';
+        *p++ = (l >= 'a' && l <= 'z') ? (char)(l - 32) : l;
+        for (k = 0; k < 6; k++) { *p++ = '\t'; p = put_u32(p, c[k]); }
+        *p++ = '\t';
+        for (k = 0; k < 6; k++)
+            if ((alleles[i] >> k) & 1) {
+                if (some) *p++ = ',';
+                *p++ = "ACGTDI"[k];
+                some = 1;
+            }
         *p++ = '\n';
         buf->len = (size_t)(p - buf->data);
     }

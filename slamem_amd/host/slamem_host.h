@@ -69,7 +69,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa...), 8 pileup (-pi...), -1 two of them */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa...), 8 pileup (-pi..., and -si...: its variant sites), -1 two of them */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
@@ -98,6 +98,11 @@ int slh_parse_max_edits(int argc, char **argv, int *out);
  * 1 when it is, -1 when the value is missing, not an integer or out of range.  It begins with -m, so its value is never taken
  * for a file name. */
 int slh_parse_min_mapq(int argc, char **argv, int *out);
+/* -mdep N (-md...) and -mpct P (-mp...): the least depth (N in [1, 2^31)) and the least share of the depth in percent (P in
+ * [0, 100]) of -sites.  0 when neither is there (*min_depth_out = 4, *min_pct_out = 20: the defaults), 1 when at least one is,
+ * -1 when the value of -mdep is missing, not an integer or out of range, -2 when that of -mpct is.  Both begin with -m, so their
+ * values are never taken for file names; neither is -mam, -maxed, -mgap or -minq. */
+int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out);
 /* AppendToBasename (tools.c:65-79): everything before the last '.' of the whole path + extra */
 char *slh_append_to_basename(const char *filename, const char *extra);
 
@@ -135,6 +140,12 @@ int slh_format_read_paf(slh_buffer *buf, const char *query_name, uint32_t query_
  * counts: six uint32 per row; letters[i]: the reference letter of row i; first_pos: the 1-based position of row 0 in its record. */
 int slh_format_pile_rows(slh_buffer *buf, const char *record_name, uint32_t first_pos, const char *letters, const uint32_t *counts,
                          uint64_t rows);
+/* Rows of the -sites file: one line per row given,
+ *   record name (cut at the first blank or tab)  position  reference letter (upper case)  A  C  G  T  D  I  calls
+ * pos[i]: the row's position in the merged text (inside the record, which starts at record_start), text: the merged text,
+ * counts: six uint32 per row, alleles[i]: the row's mask; calls: its set bits in the order A C G T D I, joined by commas. */
+int slh_format_site_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, const char *text, const uint64_t *pos,
+                         const uint32_t *counts, const uint8_t *alleles, uint64_t rows);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
