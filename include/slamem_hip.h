@@ -507,6 +507,58 @@ int slamem_pileup_sites_host(slamem_pileup *pile, uint64_t first, uint64_t count
 int slamem_pileup_add_counts_device(slamem_pileup *pile, uint64_t first, uint64_t count, const uint32_t *rows_dev, void *stream);
 int slamem_pileup_add_counts_host(slamem_pileup *pile, uint64_t first, uint64_t count, const uint32_t *rows);
 
+/* ---- (b'''') the indel events of the pileup (option -vcf) -----------------------------------------------------
+ * What the table above does not hold: WHICH letters the reads insert, and a deletion as one event.  With events enabled every
+ * slamem_pileup_add_device also records, for each contributing read, its I operations (an insertion of S = the k upper-cased
+ * letters of the scanned strand, in front of row p) and its D operations (a deletion of rows [p, p + k)), each left-normalised
+ * against the text: a deletion moves left while the letter in front of it equals its last letter, an insertion while the letter
+ * in front of it equals the last letter of S (which then rotates); both stop at row 0 and at a letter that is none of A,C,G,T, so
+ * no event leaves its record.  The table maps (pos, kind, len, S) to fwd and rev, the observations from reads of strand 1 and of
+ * strand 2 (uint32, modulo 2^32), summed over everything added since slamem_pileup_enable_events or the last reset, whatever the
+ * batches, their order, the streams and the GPUs.  The columns A C G T D I of the table above stay as aligned, not normalised.
+ * Observations that are counted and not stored -- skipped[0]: an insertion of more than 31 letters; skipped[1]: an observation
+ * the hash table had no room for (more slots help); skipped[2]: an insertion at row n or with a letter that is none of A,C,G,T,
+ * a deletion of more than 127 rows, beyond row n or over a row that is none of A,C,G,T (none should occur on the engine's own
+ * mappings).
+ *
+ * slamem_event: kind 0 a deletion of len rows from pos, kind 1 an insertion of len letters in front of pos; letters: the
+ * inserted letters two bits each (A 0, C 1, G 2, T 3), letter i at bits 2 * (len - 1 - i), 0 for a deletion.
+ *
+ *   slamem_pileup_enable_events  allocates the hash table of `slots` slots (a power of two of at least 64; 0: the smallest power
+ *                          of two that is at least max(65536, n / 16)) of 24 bytes and as much again for the read-out's sort.  Too
+ *                          little free HBM: SLAMEM_ERR_NOMEM with the numbers; enabled already, or a bad number of slots:
+ *                          SLAMEM_ERR_ARG.  Waits for the device.  slamem_pileup_reset also clears the events and skipped.
+ *   slamem_pileup_events_device  the events with first <= pos < first + count and fwd + rev >= min_count (>= 1), ascending in
+ *                          (pos, kind, len, S), S letter by letter with A < C < G < T, and the three skipped counters (host
+ *                          pointers, as total_out).  Asynchronous on `stream` but for one host round trip.  More than `capacity`:
+ *                          SLAMEM_ERR_CAPACITY with the need in *total_out and the first `capacity` events written; capacity 0
+ *                          with a null buffer asks for the count alone.  Events not enabled, a range outside [0, n],
+ *                          min_count 0: SLAMEM_ERR_ARG.  The table is not modified.  Two read-outs of one accumulator must not
+ *                          run at the same time, and none beside an add (they share scratch; an add may be half-way in a slot).
+ *   slamem_pileup_events_host  the same into host memory; waits for the device first.
+ *   slamem_pileup_add_events_device  every given event is validated as an observation is, normalised (a canonical event stays as
+ *                          it is) and added with its fwd and rev: the merge of another accumulator's events.  Asynchronous.
+ *   slamem_pileup_add_events_host  the same from host memory; returns when the events are added.
+ *   slamem_pileup_rows_at_device  the rows of slamem_pileup_counts_* at m listed positions (m x 6 uint32), asynchronous; a position
+ *                          at or beyond n gives a row of zeros.  Shares the read-outs' scratch.  Needs no events.
+ *   slamem_pileup_rows_at_host  the same from and into host memory; a position at or beyond n: SLAMEM_ERR_ARG. */
+typedef struct {
+    uint64_t pos;
+    uint64_t letters;
+    uint32_t fwd, rev;
+    uint8_t kind, len;
+    uint8_t pad[6]; /* 0 */
+} slamem_event;
+int slamem_pileup_enable_events(slamem_pileup *pile, uint64_t slots);
+int slamem_pileup_events_device(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t min_count, uint64_t capacity,
+                                slamem_event *events_dev, uint64_t *skipped_out /* 3 */, uint64_t *total_out, void *stream);
+int slamem_pileup_events_host(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t min_count, uint64_t capacity,
+                              slamem_event *events, uint64_t *skipped_out /* 3 */, uint64_t *total_out);
+int slamem_pileup_add_events_device(slamem_pileup *pile, const slamem_event *events_dev, uint64_t m, void *stream);
+int slamem_pileup_add_events_host(slamem_pileup *pile, const slamem_event *events, uint64_t m);
+int slamem_pileup_rows_at_device(slamem_pileup *pile, const uint64_t *pos_dev, uint64_t m, uint32_t *out_dev, void *stream);
+int slamem_pileup_rows_at_host(slamem_pileup *pile, const uint64_t *pos, uint64_t m, uint32_t *out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */

@@ -23,26 +23,13 @@
 //                  rather than kept as a bitmap: see 4.17.
 //   k_pile_add_counts  a table added into cnt (atomicAdd, zeros skipped; diff is not touched)
 // Counters are 32 bits wide and every sum is taken modulo 2^32: a true depth of 2^31 or more at one row is outside the contract.
-#include "common.h"
+#include "pile_shared.h"
 
 #include <new>
 
 namespace slamem {
 
 namespace {
-
-constexpr uint32_t kPileLaneOps = 32;   // operations of a segment a lane walks alone; more: the wave kernel
-constexpr uint32_t kPileTile = 2048;    // entries of diff per workgroup of the read-out (256 lanes x 8)
-constexpr unsigned kPileWaveGrid = 2048;
-constexpr uint32_t kOpEq = 7, kOpX = 8, kOpI = 1, kOpD = 2;  // BAM's codes, as aln_filter.hip writes them
-
-inline unsigned pile_grid(uint64_t items, unsigned block) { return items ? (unsigned)((items + block - 1) / block) : 1u; }
-
-// A 0, C 1, G 2, T 3 (either case); anything else 4
-__device__ __forceinline__ uint32_t pile_code(uint32_t byte) {
-    const uint32_t u = byte & 0xDFu, y = (u >> 1) & 3u, code = y ^ (y >> 1);
-    return ((0x54474341u >> (8u * code)) & 0xFFu) == u ? code : 4u;
-}
 
 struct PileAcc {
     const TextPlanes* tpl;
@@ -85,19 +72,6 @@ __device__ __forceinline__ void pile_eq(const PileAcc& a, uint64_t p, uint64_t k
     }
 }
 
-// the read as the search saw it: letter x of the scanned strand
-struct PileRead {
-    const unsigned char* rec;
-    uint64_t len;
-    bool rev;
-};
-__device__ __forceinline__ uint32_t pile_letter(const PileRead& r, uint64_t x) {
-    if (x >= r.len) return 4u;
-    if (!r.rev) return pile_code(r.rec[x]);
-    const uint32_t c = pile_code(r.rec[r.len - 1u - x]);
-    return c < 4u ? 3u - c : 4u;
-}
-
 // one operation at (p, q): every write is checked against n
 __device__ __forceinline__ void pile_op(const PileAcc& a, const PileRead& r, uint32_t op, uint64_t p, uint64_t q) {
     const uint32_t code = op & 15u;
@@ -115,37 +89,6 @@ __device__ __forceinline__ void pile_op(const PileAcc& a, const PileRead& r, uin
         if (k && p < a.n) atomicAdd(&a.cnt[p * 6u + 5u], 1u);
     }
 }
-__device__ __forceinline__ uint32_t pile_ref_step(uint32_t op) {
-    const uint32_t c = op & 15u;
-    return (c == kOpEq || c == kOpX || c == kOpD) ? op >> 4 : 0u;
-}
-__device__ __forceinline__ uint32_t pile_query_step(uint32_t op) {
-    const uint32_t c = op & 15u;
-    return (c == kOpEq || c == kOpX || c == kOpI) ? op >> 4 : 0u;
-}
-
-struct PileBatch {
-    const unsigned char* queries;
-    const uint64_t* offsets;
-    const slamem_aln* segs;
-    const uint64_t* roff;
-    const uint32_t* ops;
-    const uint64_t* ooff;
-    const slamem_map* reads;
-    uint64_t nq;
-    uint32_t min_mapq;
-};
-
-__device__ __forceinline__ bool pile_contributes(const PileBatch& b, uint64_t r, PileRead& out) {
-    const slamem_map m = b.reads[r];
-    if (m.strand == 0u || m.mapq < b.min_mapq) return false;
-    const uint64_t o = b.offsets[r];
-    out.rec = b.queries + o;
-    out.len = b.offsets[r + 1] - o;
-    out.rev = m.strand == 2u;
-    return true;
-}
-
 // a lane per read: its segments of up to kPileLaneOps operations
 __global__ void __launch_bounds__(256) k_pile_lane(PileBatch b, PileAcc a) {
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -165,15 +108,6 @@ __global__ void __launch_bounds__(256) k_pile_lane(PileBatch b, PileAcc a) {
             q += pile_query_step(op);
         }
     }
-}
-
-__device__ __forceinline__ uint64_t wave_scan_inclusive(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint64_t up = __shfl_up(v, d, 64);
-        if (lane >= d) v += up;
-    }
-    return v;
 }
 
 // a wave per 64 reads: the reads that have a segment of more than kPileLaneOps operations, one after the other; of such a read
@@ -472,16 +406,6 @@ __global__ void __launch_bounds__(256) k_pile_add_counts(uint32_t* __restrict__ 
 
 using namespace slamem;
 
-struct slamem_pileup {
-    const slamem_index* idx;
-    int device;
-    uint32_t n;
-    int32_t* diff;
-    uint32_t* cnt;
-    uint32_t* tile;  // the read-out's tile sums: n / kPileTile + 2 words
-    uint64_t* sel;   // the sparse read-out's selected rows per tile: n / kPileTile + 2 words of 64 bits
-};
-
 namespace slamem {
 
 int pileup_device(const slamem_pileup* p) { return p->device; }
@@ -509,6 +433,22 @@ int pileup_add(slamem_pileup* pile, const void* queries_dev, const uint64_t* off
     SLAMEM_HIP(hipGetLastError());
     const unsigned chunks = pile_grid(num_queries, 64);
     hipLaunchKernelGGL(k_pile_wave, dim3(chunks < kPileWaveGrid ? chunks : kPileWaveGrid), dim3(64), 0, stream, b, a);
+    SLAMEM_HIP(hipGetLastError());
+    if (pile->ev) return events_add(pile, &b, stream);  // (the indel events of the same batch, behind the two kernels)
+    return SLAMEM_OK;
+}
+
+int pile_tile_prefix(slamem_pileup* pile, uint64_t end, hipStream_t stream) {
+    const uint64_t tiles = (end + kPileTile - 1) / kPileTile;
+    hipLaunchKernelGGL(k_pile_tile_sums, dim3((unsigned)tiles), dim3(256), 0, stream, (const int32_t*)pile->diff, end, pile->tile);
+    SLAMEM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_pile_tile_scan, dim3(1), dim3(1024), 0, stream, pile->tile, tiles);
+    SLAMEM_HIP(hipGetLastError());
+    return SLAMEM_OK;
+}
+
+int pile_scan_counts(uint64_t* sel, uint64_t tiles, hipStream_t stream) {
+    hipLaunchKernelGGL(k_sites_tile_scan, dim3(1), dim3(1024), 0, stream, sel, tiles);
     SLAMEM_HIP(hipGetLastError());
     return SLAMEM_OK;
 }
@@ -539,7 +479,7 @@ int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
     slamem_pileup* p = new (std::nothrow) slamem_pileup();
     if (!p) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     p->idx = idx; p->device = idx->device; p->n = (uint32_t)n;
-    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr;
+    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->diff), (n + 1) * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->cnt), n * 24 + 16);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->tile), tiles * 4);
@@ -562,6 +502,7 @@ int slamem_pileup_free(slamem_pileup* p) {
     if (p->cnt) (void)hipFree(p->cnt);
     if (p->tile) (void)hipFree(p->tile);
     if (p->sel) (void)hipFree(p->sel);
+    events_free(p);
     delete p;
     return SLAMEM_OK;
 }
@@ -572,6 +513,7 @@ int slamem_pileup_reset(slamem_pileup* p) {
     SLAMEM_HIP(hipDeviceSynchronize());  // (adds of any stream that are still on their way belong to the table that goes)
     SLAMEM_HIP(hipMemset(p->diff, 0, ((uint64_t)p->n + 1) * 4));
     SLAMEM_HIP(hipMemset(p->cnt, 0, (uint64_t)p->n * 24));
+    if (p->ev) { const int rc = events_reset(p); if (rc != SLAMEM_OK) return rc; }
     SLAMEM_HIP(hipDeviceSynchronize());
     return SLAMEM_OK;
 }

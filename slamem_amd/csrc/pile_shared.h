@@ -1,0 +1,109 @@
+// pile_shared.h -- what pile_filter.hip (-pile and -sites) and event_filter.hip (the indel events of -vcf,
+// DESIGN.md 4.18) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
+// segments (letters of the scanned strand, the steps of an operation), and the two entry points of the read-out's scratch that
+// the event side borrows.
+#pragma once
+#include "common.h"
+
+namespace slamem {
+
+struct EvTable;  // event_filter.hip: the hash table of the indel events, its counters and its read-out's scratch
+
+}  // namespace slamem
+
+struct slamem_pileup {
+    const slamem_index* idx;
+    int device;
+    uint32_t n;
+    int32_t* diff;
+    uint32_t* cnt;
+    uint32_t* tile;  // the read-out's tile sums: n / kPileTile + 2 words
+    uint64_t* sel;   // the sparse read-out's selected rows per tile: n / kPileTile + 2 words of 64 bits
+    slamem::EvTable* ev;  // nullptr: events are not enabled
+};
+
+namespace slamem {
+
+namespace {
+
+constexpr uint32_t kPileLaneOps = 32;   // operations of a segment a lane walks alone; more: the wave kernel
+constexpr uint32_t kPileTile = 2048;    // entries of diff per workgroup of the read-out (256 lanes x 8)
+constexpr unsigned kPileWaveGrid = 2048;
+constexpr uint32_t kOpEq = 7, kOpX = 8, kOpI = 1, kOpD = 2;  // BAM's codes, as aln_filter.hip writes them
+
+inline unsigned pile_grid(uint64_t items, unsigned block) { return items ? (unsigned)((items + block - 1) / block) : 1u; }
+
+// A 0, C 1, G 2, T 3 (either case); anything else 4
+__device__ __forceinline__ uint32_t pile_code(uint32_t byte) {
+    const uint32_t u = byte & 0xDFu, y = (u >> 1) & 3u, code = y ^ (y >> 1);
+    return ((0x54474341u >> (8u * code)) & 0xFFu) == u ? code : 4u;
+}
+
+// the read as the search saw it: letter x of the scanned strand
+struct PileRead {
+    const unsigned char* rec;
+    uint64_t len;
+    bool rev;
+};
+__device__ __forceinline__ uint32_t pile_letter(const PileRead& r, uint64_t x) {
+    if (x >= r.len) return 4u;
+    if (!r.rev) return pile_code(r.rec[x]);
+    const uint32_t c = pile_code(r.rec[r.len - 1u - x]);
+    return c < 4u ? 3u - c : 4u;
+}
+
+__device__ __forceinline__ uint32_t pile_ref_step(uint32_t op) {
+    const uint32_t c = op & 15u;
+    return (c == kOpEq || c == kOpX || c == kOpD) ? op >> 4 : 0u;
+}
+__device__ __forceinline__ uint32_t pile_query_step(uint32_t op) {
+    const uint32_t c = op & 15u;
+    return (c == kOpEq || c == kOpX || c == kOpI) ? op >> 4 : 0u;
+}
+
+struct PileBatch {
+    const unsigned char* queries;
+    const uint64_t* offsets;
+    const slamem_aln* segs;
+    const uint64_t* roff;
+    const uint32_t* ops;
+    const uint64_t* ooff;
+    const slamem_map* reads;
+    uint64_t nq;
+    uint32_t min_mapq;
+};
+
+__device__ __forceinline__ bool pile_contributes(const PileBatch& b, uint64_t r, PileRead& out) {
+    const slamem_map m = b.reads[r];
+    if (m.strand == 0u || m.mapq < b.min_mapq) return false;
+    const uint64_t o = b.offsets[r];
+    out.rec = b.queries + o;
+    out.len = b.offsets[r + 1] - o;
+    out.rev = m.strand == 2u;
+    return true;
+}
+
+__device__ __forceinline__ uint64_t wave_scan_inclusive(uint64_t v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint64_t up = __shfl_up(v, d, 64);
+        if (lane >= d) v += up;
+    }
+    return v;
+}
+
+}  // namespace
+
+// pile_filter.hip, for the event side: pile->tile = the exclusive prefix sums of diff per tile of kPileTile entries below `end`
+// (k_pile_tile_sums and k_pile_tile_scan), and the in-place exclusive scan of `tiles` 64-bit counts with the total behind them
+// (k_sites_tile_scan)
+int pile_tile_prefix(slamem_pileup* pile, uint64_t end, hipStream_t stream);
+int pile_scan_counts(uint64_t* sel, uint64_t tiles, hipStream_t stream);
+
+// event_filter.hip, for pile_filter.hip: the two event kernels behind the two pile kernels of an add (events enabled), and what
+// reset and free do to the table
+int events_add(slamem_pileup* pile, const void* batch /* PileBatch */, hipStream_t stream);
+int events_reset(slamem_pileup* pile);
+void events_free(slamem_pileup* pile);
+
+}  // namespace slamem

@@ -22,6 +22,8 @@ _MAP_ABI = np.dtype([("s1", "<u4"), ("s2", "<u4"), ("strand", "u1"), ("mapq", "u
 EDITS_DEFAULT = 0xFFFFFFFF  # SLAMEM_ALN_EDITS_DEFAULT: "the default 31" in the C ABI (0 is a value of its own)
 CIGAR_OPS = {7: "=", 8: "X", 1: "I", 2: "D"}  # BAM's codes; an operation is length << 4 | code
 SITES_NONZERO, SITES_VARIANT = 0, 1  # the rules of Pileup.sites (SLAMEM_SITES_*)
+# slamem_event: kind 0 a deletion of len rows from pos, 1 an insertion of len letters in front of pos
+EVENT_DTYPE = np.dtype([("pos", "<u8"), ("letters", "<u8"), ("fwd", "<u4"), ("rev", "<u4"), ("kind", "u1"), ("len", "u1"), ("pad", "u1", (6,))])
 PILE_LANE_OPS = 32  # -pile: a segment of up to this many operations is walked by one lane, a longer one by a wave (pile_filter.hip)
 
 
@@ -392,12 +394,24 @@ class Pileup:
     """slamem_pileup_*: the per-base pileup of the read mappings, accumulated on the GPU (-pile).  A table of
     index.n rows of six uint32 counters A, C, G, T, D, I: per reference position the letters the mapped reads show there, how many
     delete it, and how many insert in front of it.  It is the sum over every batch added since creation or the last reset(),
-    whatever the split into batches and their order.  28 bytes of HBM per text letter."""
+    whatever the split into batches and their order.  28 bytes of HBM per text letter.  events=True: every add also records the
+    reads' insertions and deletions as left-normalised events in a hash table of event_slots slots (a power of two of at least
+    64; 0: the default) -- see events()."""
 
-    def __init__(self, index: Index):
+    def __init__(self, index: Index, events: bool = False, event_slots: int = 0):
         self.index = index
         self._h = C.c_void_p()
+        if event_slots and not events:
+            raise ValueError("event_slots is the size of the event table: it needs events=True")
         capi.check(capi.lib().slamem_pileup_create(index._h, C.byref(self._h)))
+        if events:
+            rc = capi.lib().slamem_pileup_enable_events(self._h, int(event_slots))
+            if rc != capi.SLAMEM_OK:
+                h, self._h = self._h, None
+                try:
+                    capi.check(rc)
+                finally:
+                    capi.lib().slamem_pileup_free(h)
         self.last_add_ms = 0.0  # device time of the last add's own kernels (the mapping in front of them not counted)
 
     def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
@@ -479,6 +493,55 @@ class Pileup:
             capi.check(capi.lib().slamem_pileup_add_counts_device(self._h, int(first), t.shape[0], _ptr(t), _stream_handle(dev)))
             torch.cuda.current_stream(dev).synchronize()  # (the table's tensor goes when the caller returns)
 
+    def events(self, min_count: int = 1, first: int = 0, count=None, capacity=None):
+        """(events, skipped): the indel events with first <= pos < first + count and fwd + rev >= min_count, sorted
+        on the device by (pos, kind, len, letters), as a structured array of EVENT_DTYPE, and the three counters of observations
+        that were not stored (insertions of more than 31 letters; no room in the table; malformed).  capacity: events of room for
+        the first attempt (default 4,096); when there are more the call is made once more with the need it reported."""
+        first = int(first)
+        count = self.index.n - first if count is None else int(count)
+        dev = self.index.device
+        cap = 4096 if capacity is None else int(capacity)
+        total = C.c_uint64()
+        skipped = (C.c_uint64 * 3)()
+        with torch.cuda.device(dev):
+            for attempt in (0, 1):
+                buf = torch.empty(max(cap, 1) * 32, dtype=torch.uint8, device=dev)
+                rc = capi.lib().slamem_pileup_events_device(self._h, first, count, int(min_count), cap, _ptr(buf), skipped,
+                                                            C.byref(total), _stream_handle(dev))
+                if rc != capi.SLAMEM_ERR_CAPACITY or attempt:
+                    break
+                cap = int(total.value)
+            capi.check(rc)
+            torch.cuda.current_stream(dev).synchronize()
+        m = int(total.value)
+        return buf[:m * 32].cpu().numpy().view(EVENT_DTYPE).copy(), [int(v) for v in skipped]
+
+    def add_events(self, events) -> None:
+        """Adds events (a structured array of EVENT_DTYPE, in any -- not only the canonical -- form) with their fwd and rev counts:
+        with events() of another accumulator of the same text the table becomes the sum of both."""
+        a = np.ascontiguousarray(np.asarray(events))
+        if a.dtype != EVENT_DTYPE or a.ndim != 1:
+            raise ValueError("add_events takes a one-dimensional array of EVENT_DTYPE")
+        dev = self.index.device
+        t = torch.from_numpy(a.view(np.uint8).copy()).to(dev) if len(a) else None
+        with torch.cuda.device(dev):
+            capi.check(capi.lib().slamem_pileup_add_events_device(self._h, _ptr(t) if len(a) else None, len(a), _stream_handle(dev)))
+            torch.cuda.current_stream(dev).synchronize()  # (the events' tensor goes when the caller returns)
+
+    def rows_at(self, positions) -> np.ndarray:
+        """The rows of counts() at the listed positions as an (m, 6) uint32 array; a position at or beyond n gives zeros."""
+        pos = np.ascontiguousarray(np.asarray(positions, dtype=np.uint64).reshape(-1))
+        m = len(pos)
+        dev = self.index.device
+        out = torch.zeros((max(m, 1), 6), dtype=torch.int32, device=dev)
+        if m:
+            pd = torch.from_numpy(pos.view(np.int64)).to(dev)
+            with torch.cuda.device(dev):
+                capi.check(capi.lib().slamem_pileup_rows_at_device(self._h, _ptr(pd), m, _ptr(out), _stream_handle(dev)))
+                torch.cuda.current_stream(dev).synchronize()
+        return out[:m].cpu().numpy().view(np.uint32)
+
     def reset(self) -> None:
         capi.check(capi.lib().slamem_pileup_reset(self._h))
 
@@ -492,6 +555,14 @@ class Pileup:
             self.close()
         except Exception:
             pass
+
+
+def event_letters(ev) -> bytes:
+    """The inserted letters of one event (an element of Pileup.events()' array) as bytes; b"" for a deletion."""
+    if int(ev["kind"]) != 1:
+        return b""
+    k, v = int(ev["len"]), int(ev["letters"])
+    return bytes(b"ACGT"[(v >> (2 * (k - 1 - i))) & 3] for i in range(k))
 
 
 class Matcher:

@@ -594,6 +594,8 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-sites\tvariant sites of the pileup: the rows of -pile where the reads differ from the reference, with a tenth column, the calls; -mgap, -pen, -xdrop, -maxed, -minq apply\n");
     printf("\t-mdep\twith -sites: least depth A+C+G+T+D of a site (default=4)\n");
     printf("\t-mpct\twith -sites: least share of the depth a call needs, in percent, 0 to 100 (default=20)\n");
+    printf("\t-vcf\tthe calls of the pileup as VCF 4.2: the SNVs of -sites and the reads' insertions and deletions as left-normalised events; -mgap, -pen, -xdrop, -maxed, -minq, -mdep, -mpct apply\n");
+    printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
     printf("\t-b\tprocess both forward and reverse strands\n");
@@ -620,6 +622,8 @@ int main(int argc, char **argv) {
     slamem_index *idx = NULL, *gpus[16];
     int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1, min_mapq = 0;
     int sites = 0, min_depth = 4, min_pct = 20; /* -sites: match type 8 with the sparse read-out */
+    int vcf = 0;                                /* -vcf: match type 8 with the events enabled, written as VCF */
+    uint64_t ev_slots = 0;
     slamem_pileup *piles[16];
     double t0;
     long long total_matches = 0, total_sum = 0;
@@ -642,7 +646,9 @@ int main(int argc, char **argv) {
         return slh_clean_fasta(argv[2], stdout);
     }
     sites = slh_parse_argument(argc, argv, "SI", 0);
+    vcf = slh_parse_argument(argc, argv, "VC", 0);
     if (o.match_type < 0) { /* before any GPU work */
+        if (vcf) exit_message("Option -vcf excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile and -sites");
         if (sites) exit_message("Option -sites excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf and -pile");
         if (slh_parse_argument(argc, argv, "PI", 0)) exit_message("Option -pile excludes -mam, -mum, -smem, -chain, -ext, -aln and -paf");
         if (slh_parse_argument(argc, argv, "PA", 0)) exit_message("Option -paf excludes -mam, -mum, -smem, -chain, -ext and -aln");
@@ -680,7 +686,12 @@ int main(int argc, char **argv) {
     switch (slh_parse_sites_params(argc, argv, &min_depth, &min_pct)) {
     case -1: exit_message("Option -mdep needs a whole number of at least 1"); break;
     case -2: exit_message("Option -mpct needs a whole number from 0 to 100"); break;
-    case 1: if (!sites) exit_message("Options -mdep and -mpct need -sites"); break;
+    case 1: if (!sites && !vcf) exit_message("Options -mdep and -mpct need -sites"); break;
+    default: break;
+    }
+    switch (slh_parse_event_slots(argc, argv, &ev_slots)) {
+    case -1: exit_message("Option -evs needs a power of two of at least 64"); break;
+    case 1: if (!vcf) exit_message("Option -evs needs -vcf"); break;
     default: break;
     }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
@@ -792,7 +803,7 @@ int main(int argc, char **argv) {
         say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", max_gap > 0 ? max_gap : 5000,
             ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
     if (o.match_type == 8) say(" ; minimum mapping quality = %d", min_mapq);
-    if (sites) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
+    if (sites || vcf) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
     say("\n");
     out = fopen(out_name, "w");
     if (!out) {
@@ -948,6 +959,7 @@ int main(int argc, char **argv) {
             if (rc == SLAMEM_OK && o.match_type == 8) { /* one accumulator per GPU: the tables are added when the file is written */
                 g_nstreams = g + 1;
                 rc = slamem_pileup_create(gpus[g], &piles[g]);
+                if (rc == SLAMEM_OK && vcf) rc = slamem_pileup_enable_events(piles[g], ev_slots);
                 if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(g_streams[g], piles[g], (uint32_t)min_mapq);
             }
             if (rc == SLAMEM_OK && (o.match_type == 6 || o.match_type == 7 || o.match_type == 8)) {
@@ -1121,15 +1133,20 @@ int main(int argc, char **argv) {
             remove(out_name);
             exit_message("No query files provided");
         }
-        if (o.match_type == 8 && sites) {
+        if (o.match_type == 8 && (sites || vcf)) {
             /* the tables of GPUs 1.. are added into GPU 0's, in chunks of 16 M rows; then GPU 0 applies the rule to the sum range
                after range and only the selected rows come back: a line each, the separators between records skipped */
             const uint64_t chunk = 16ull << 20, n = ref.total;
             uint64_t x0, cap = 1ull << 20, *pos = NULL;
             uint32_t *rows = NULL;
             uint8_t *alleles = NULL;
+            uint64_t ecap = 1ull << 16, skipped[3] = {0, 0, 0}, sk[3] = {0, 0, 0};
+            slamem_event *evs = NULL;
+            uint64_t *anchors = NULL;
+            uint32_t *arows = NULL;
             int r = 0;
             double tp = now_s();
+            if (vcf && slh_format_vcf_header(&buf, ref.recs, ref.num)) pipeline_fail("Out of memory");
             if (g_nstreams > 1) {
                 rows = (uint32_t *)slh_big_malloc((size_t)(chunk < n ? chunk : n) * 24 + 24);
                 if (!rows) pipeline_fail("Out of memory");
@@ -1142,6 +1159,23 @@ int main(int argc, char **argv) {
                     }
                 free(rows);
                 rows = NULL;
+            }
+            for (g = 1; vcf && g < g_nstreams; g++) { /* ... and their events, which arrive normalised and stay as they are */
+                for (x0 = 0; x0 < n; x0 += chunk) {
+                    const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
+                    uint64_t total = 0;
+                    for (;;) {
+                        if (!evs && !(evs = (slamem_event *)malloc((size_t)ecap * sizeof(slamem_event)))) pipeline_fail("Out of memory");
+                        rc = slamem_pileup_events_host(piles[g], x0, cnt, 1, ecap, evs, sk, &total);
+                        if (rc != SLAMEM_ERR_CAPACITY || total <= ecap) break;
+                        free(evs);
+                        evs = NULL;
+                        ecap = total;
+                    }
+                    if (rc == SLAMEM_OK) rc = slamem_pileup_add_events_host(piles[0], evs, total);
+                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("adding up the indel events of the GPUs", rc); }
+                }
+                skipped[0] += sk[0]; skipped[1] += sk[1]; skipped[2] += sk[2]; /* (what GPU g could not store) */
             }
             for (x0 = 0; g_nstreams > 0 && x0 < n; x0 += chunk) {
                 const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
@@ -1161,6 +1195,52 @@ int main(int argc, char **argv) {
                     cap = total;
                 }
                 if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the variant sites from the GPU", rc); }
+                if (vcf) { /* the events of the same range, the pileup rows of their anchors, and the lines of both record by record */
+                    uint64_t etotal = 0, ek = 0, j;
+                    int rr = r;
+                    for (;;) {
+                        if (!evs) {
+                            evs = (slamem_event *)malloc((size_t)ecap * sizeof(slamem_event));
+                            anchors = (uint64_t *)malloc((size_t)ecap * 8);
+                            arows = (uint32_t *)malloc((size_t)ecap * 24);
+                            if (!evs || !anchors || !arows) pipeline_fail("Out of memory");
+                        } else if (!anchors) {
+                            anchors = (uint64_t *)malloc((size_t)ecap * 8);
+                            arows = (uint32_t *)malloc((size_t)ecap * 24);
+                            if (!anchors || !arows) pipeline_fail("Out of memory");
+                        }
+                        rc = slamem_pileup_events_host(piles[0], x0, cnt, 1, ecap, evs, sk, &etotal);
+                        if (rc != SLAMEM_ERR_CAPACITY || etotal <= ecap) break;
+                        free(evs); free(anchors); free(arows);
+                        evs = NULL; anchors = NULL; arows = NULL;
+                        ecap = etotal;
+                    }
+                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the indel events from the GPU", rc); }
+                    for (j = 0; j < etotal; j++) { /* the anchor row: the letter in front, or the event's own row at a record's start */
+                        const uint64_t p = evs[j].pos;
+                        while (rr + 1 < ref.num && p >= ref.merged_start[rr + 1]) rr++;
+                        anchors[j] = p > (ref.num > 1 ? ref.merged_start[rr] : 0) ? p - 1 : p;
+                    }
+                    rc = slamem_pileup_rows_at_host(piles[0], anchors, etotal, arows);
+                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the pileup rows of the indel events from the GPU", rc); }
+                    while ((k < total || ek < etotal) && r < ref.num) {
+                        const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, end = start + ref.recs[r].size;
+                        uint64_t e = k, ee;
+                        while (k < total && pos[k] < start) k++; /* (a separator: no record's row) */
+                        while (ek < etotal && evs[ek].pos < start) ek++;
+                        for (e = k; e < total && pos[e] < end; e++) {}
+                        for (ee = ek; ee < etotal && evs[ee].pos < end; ee++) {}
+                        if (slh_format_vcf_rows(&buf, ref.recs[r].name, start, ref.recs[r].size, ref.chars, pos + k, rows + k * 6, alleles + k,
+                                                e - k, (const slh_event *)(evs + ek), arows + ek * 6, ee - ek, (uint32_t)min_depth,
+                                                (uint32_t)min_pct))
+                            pipeline_fail("Out of memory");
+                        k = e;
+                        ek = ee;
+                        if (end > x0 + cnt) break; /* (the record goes on in the next range) */
+                        r++;
+                    }
+                    k = total;
+                }
                 while (k < total && r < ref.num) { /* the rows of one record after the other */
                     const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, end = start + ref.recs[r].size;
                     uint64_t e = k;
@@ -1175,6 +1255,15 @@ int main(int argc, char **argv) {
                 if (g_writer.failed) pipeline_fail("Cannot write output file");
             }
             free(pos); free(rows); free(alleles);
+            free(evs); free(anchors); free(arows);
+            if (vcf && g_nstreams > 0) {
+                skipped[0] += sk[0]; skipped[1] += sk[1]; skipped[2] += sk[2]; /* (GPU 0's, the merge included) */
+                if (skipped[0] | skipped[1] | skipped[2])
+                    fprintf(stderr, "> WARNING: indel observations that are in no event: %llu insertions of more than 31 letters, %llu without "
+                                    "room in the event table, %llu malformed%s\n", (unsigned long long)skipped[0],
+                            (unsigned long long)skipped[1], (unsigned long long)skipped[2],
+                            skipped[1] ? " (a larger table: -evs)" : "");
+            }
             t_format += now_s() - tp;
         } else if (o.match_type == 8) {
             /* the table, in chunks of at most 16 M rows (24 bytes a row: the table of a 100 Mbp text never sits in one buffer):
@@ -1230,7 +1319,7 @@ int main(int argc, char **argv) {
                (int)(total_matches / total_queries), MATCH_NAME(o.match_type), total_matches,
                (int)(total_matches ? total_sum / total_matches : 0));
     fflush(stdout);
-    printf("> Saving %ss to <%s> ... ", sites ? "variant site" : MATCH_NAME(o.match_type), out_name);
+    printf("> Saving %ss to <%s> ... ", vcf ? "variant call" : sites ? "variant site" : MATCH_NAME(o.match_type), out_name);
     if (fflush(out) != 0 || ferror(out)) exit_message("Cannot write output file");
     if (getenv("SLAMEM_FULL_TEARDOWN") != NULL && fclose(out) != 0) exit_message("Cannot write output file");
     t_end1 = now_s();

@@ -780,6 +780,24 @@ int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_p
     return seen;
 }
 
+int slh_parse_event_slots(int argc, char **argv, uint64_t *out) {
+    int i;
+    *out = 0;
+    for (i = 1; i < argc; i++) {
+        char *end;
+        long long v;
+        /* the two letters "ev" decide; it takes the next argument */
+        if (!two_letter_option(argv[i], 'e', 'v')) continue;
+        if (i == argc - 1) return -1;
+        errno = 0;
+        v = strtoll(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 64 || v > (1LL << 31) || (v & (v - 1)) != 0) return -1;
+        *out = (uint64_t)v;
+        return 1;
+    }
+    return 0;
+}
+
 char *slh_append_to_basename(const char *filename, const char *extra) {
     int n = (int)strlen(filename), i;
     char *res;
@@ -814,7 +832,9 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         if (argv[i][0] == '-') {
             oc = argv[i][1];
             if (oc >= 'A' && oc <= 'Z') oc = (char)('a' + (oc - 'A'));
-            if (oc == 'l' || oc == 'o' || oc == 'm' || oc == 'v') i++; /* any option starting with l/o/m/v eats the next argument */
+            if (two_letter_option(argv[i], 'v', 'c')) {} /* -vcf takes no value ("-v" alone is the image tool and does) */
+            else if (oc == 'l' || oc == 'o' || oc == 'm' || oc == 'v') i++; /* any option starting with l/o/m/v eats the next argument */
+            else if (two_letter_option(argv[i], 'e', 'v')) i++; /* -evs N (of -vcf) */
             else if (two_letter_option(argv[i], 'p', 'e') || two_letter_option(argv[i], 'x', 'd')) i++; /* -pen N, -xdrop N (of -ext) */
             else if (oc == 'r') {
                 i++;
@@ -887,6 +907,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
     if (slh_parse_argument(argc, argv, "PI", 0)) /* -pile: the per-base pileup of the mappings (a 'p' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 8;
     if (slh_parse_argument(argc, argv, "SI", 0)) /* -sites: the variant sites of the pileup: match type 8 with another read-out (an 's' option takes no value) */
+        o->match_type = o->match_type != 0 ? -1 : 8;
+    if (slh_parse_argument(argc, argv, "VC", 0)) /* -vcf: the calls of the pileup as VCF: match type 8 with the events enabled and a third read-out */
         o->match_type = o->match_type != 0 ? -1 : 8;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
@@ -998,6 +1020,138 @@ int slh_format_site_rows(slh_buffer *buf, const char *record_name, uint64_t reco
             }
         *p++ = '\n';
         buf->len = (size_t)(p - buf->data);
+    }
+    return 0;
+}
+
+static size_t cut_name_len(const char *name) {
+    size_t nl = 0;
+    while (name[nl] != '\0' && name[nl] != ' ' && name[nl] != '\t') nl++;
+    return nl;
+}
+
+static inline char upper_letter(char l) { return (l >= 'a' && l <= 'z') ? (char)(l - 32) : l; }
+
+int slh_format_vcf_header(slh_buffer *buf, const slh_record *refs, int num_refs) {
+    static const char *const INFO =
+        "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Depth A+C+G+T+D at the row (SNV) or at the anchor row (indel)\">\n"
+        "##INFO=<ID=AO,Number=1,Type=Integer,Description=\"Observations of the alternate allele\">\n"
+        "##INFO=<ID=SF,Number=1,Type=Integer,Description=\"Observations of the alternate allele on forward-strand reads\">\n"
+        "##INFO=<ID=SR,Number=1,Type=Integer,Description=\"Observations of the alternate allele on reverse-strand reads\">\n"
+        "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+    static const char *const FIRST = "##fileformat=VCFv4.2\n";
+    int r;
+    char *p;
+    if (buf_reserve(buf, strlen(FIRST))) return -1;
+    memcpy(buf->data + buf->len, FIRST, strlen(FIRST));
+    buf->len += strlen(FIRST);
+    for (r = 0; r < num_refs; r++) {
+        size_t nl = cut_name_len(refs[r].name);
+        if (buf_reserve(buf, nl + 48)) return -1;
+        p = buf->data + buf->len;
+        memcpy(p, "##contig=<ID=", 13);
+        p += 13;
+        memcpy(p, refs[r].name, nl);
+        p += nl;
+        memcpy(p, ",length=", 8);
+        p += 8;
+        p = put_u32(p, refs[r].size);
+        *p++ = '>';
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+    }
+    if (buf_reserve(buf, strlen(INFO))) return -1;
+    memcpy(buf->data + buf->len, INFO, strlen(INFO));
+    buf->len += strlen(INFO);
+    return 0;
+}
+
+/* "\t.\t" REF "\t" ALT "\t.\t.\tDP=" d ";AO=" ao behind name and POS */
+static char *vcf_line_head(char *p, const char *record_name, size_t nl, uint32_t pos1) {
+    memcpy(p, record_name, nl);
+    p += nl;
+    *p++ = '\t';
+    p = put_u32(p, pos1);
+    memcpy(p, "\t.\t", 3);
+    return p + 3;
+}
+
+static char *vcf_put_u64(char *p, uint64_t v) {
+    if (v <= 0xFFFFFFFFull) return put_u32(p, (uint32_t)v);
+    p = put_u32(p, (uint32_t)(v / 1000000000ull));
+    {
+        uint32_t low = (uint32_t)(v % 1000000000ull), div = 100000000u;
+        for (; div > 0; div /= 10) *p++ = (char)('0' + (low / div) % 10);
+    }
+    return p;
+}
+
+int slh_format_vcf_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                        const uint64_t *site_pos, const uint32_t *site_counts, const uint8_t *site_alleles, uint64_t sites,
+                        const slh_event *events, const uint32_t *anchor_rows, uint64_t num_events, uint32_t min_depth,
+                        uint32_t min_pct) {
+    const size_t nl = cut_name_len(record_name);
+    const uint64_t record_end = record_start + record_size;
+    uint64_t i = 0, e = 0;
+    while (i < sites || e < num_events) {
+        uint64_t spos = i < sites ? site_pos[i] - record_start + 1 : ~0ull, epos = ~0ull;
+        char *p;
+        int k;
+        if (e < num_events) epos = events[e].pos > record_start ? events[e].pos - record_start : 1;
+        if (spos <= epos) { /* the SNVs of a row: a line per set bit of A C G T, the rows' own order */
+            const uint32_t *c = site_counts + 6 * i;
+            const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4];
+            for (k = 0; k < 4; k++) {
+                if (!((site_alleles[i] >> k) & 1)) continue;
+                if (buf_reserve(buf, nl + 96)) return -1;
+                p = vcf_line_head(buf->data + buf->len, record_name, nl, (uint32_t)spos);
+                *p++ = upper_letter(text[site_pos[i]]);
+                *p++ = '\t';
+                *p++ = "ACGT"[k];
+                memcpy(p, "\t.\t.\tDP=", 8);
+                p = vcf_put_u64(p + 8, d);
+                memcpy(p, ";AO=", 4);
+                p = put_u32(p + 4, c[k]);
+                *p++ = '\n';
+                buf->len = (size_t)(p - buf->data);
+            }
+            i++;
+        } else {
+            const slh_event *ev = &events[e];
+            const uint32_t *c = anchor_rows + 6 * e;
+            const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4], ao = (uint64_t)ev->fwd + ev->rev;
+            const uint64_t pos = ev->pos, len = ev->len;
+            const int first = pos == record_start;
+            uint64_t j;
+            e++;
+            if (d < min_depth || 100ull * ao < (uint64_t)min_pct * d) continue;
+            if (ev->kind == 0 && first && pos + len >= record_end) continue; /* (the record ends with the deletion: no following base) */
+            if (buf_reserve(buf, nl + 320)) return -1;
+            p = vcf_line_head(buf->data + buf->len, record_name, nl, (uint32_t)epos);
+            if (ev->kind == 0) { /* REF: the anchor and the deleted rows, ALT: the anchor (behind the rows at a record's start) */
+                const uint64_t from = first ? pos : pos - 1;
+                for (j = 0; j <= len; j++) *p++ = upper_letter(text[from + j]);
+                *p++ = '\t';
+                *p++ = upper_letter(text[first ? pos + len : pos - 1]);
+            } else { /* REF: the anchor, ALT: the anchor and the inserted letters (in front of it at a record's start) */
+                const char anchor = upper_letter(text[first ? pos : pos - 1]);
+                *p++ = anchor;
+                *p++ = '\t';
+                if (!first) *p++ = anchor;
+                for (j = 0; j < len; j++) *p++ = "ACGT"[(ev->letters >> (2 * (len - 1 - j))) & 3];
+                if (first) *p++ = anchor;
+            }
+            memcpy(p, "\t.\t.\tDP=", 8);
+            p = vcf_put_u64(p + 8, d);
+            memcpy(p, ";AO=", 4);
+            p = vcf_put_u64(p + 4, ao);
+            memcpy(p, ";SF=", 4);
+            p = put_u32(p + 4, ev->fwd);
+            memcpy(p, ";SR=", 4);
+            p = put_u32(p + 4, ev->rev);
+            *p++ = '\n';
+            buf->len = (size_t)(p - buf->data);
+        }
     }
     return 0;
 }

@@ -69,7 +69,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa...), 8 pileup (-pi..., and -si...: its variant sites), -1 two of them */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa...), 8 pileup (-pi..., and -si...: its variant sites, -vc...: its calls as VCF), -1 two of them */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
@@ -103,6 +103,10 @@ int slh_parse_min_mapq(int argc, char **argv, int *out);
  * -1 when the value of -mdep is missing, not an integer or out of range, -2 when that of -mpct is.  Both begin with -m, so their
  * values are never taken for file names; neither is -mam, -maxed, -mgap or -minq. */
 int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out);
+/* -evs N (-ev...): the slots of -vcf's event table, a power of two in [64, 2^31].  0 when it is not there (*out = 0: the
+ * default), 1 when it is, -1 when the value is missing, not an integer or no such power of two.  Its value is never taken for a
+ * file name. */
+int slh_parse_event_slots(int argc, char **argv, uint64_t *out);
 /* AppendToBasename (tools.c:65-79): everything before the last '.' of the whole path + extra */
 char *slh_append_to_basename(const char *filename, const char *extra);
 
@@ -146,6 +150,29 @@ int slh_format_pile_rows(slh_buffer *buf, const char *record_name, uint32_t firs
  * counts: six uint32 per row, alleles[i]: the row's mask; calls: its set bits in the order A C G T D I, joined by commas. */
 int slh_format_site_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, const char *text, const uint64_t *pos,
                          const uint32_t *counts, const uint8_t *alleles, uint64_t rows);
+/* The head of the -vcf file: ##fileformat=VCFv4.2, a ##contig line per record (the name cut at the first blank or tab), the
+ * ##INFO lines of DP, AO, SF and SR and the #CHROM line. */
+int slh_format_vcf_header(slh_buffer *buf, const slh_record *refs, int num_refs);
+/* An indel event as the engine reads it out (the layout of slamem_event): kind 0 a deletion of len rows from pos, 1 an insertion
+ * of len letters in front of pos; letters: two bits a letter (A C G T = 0..3), letter i at bits 2 * (len - 1 - i). */
+typedef struct {
+    uint64_t pos;
+    uint64_t letters;
+    uint32_t fwd, rev;
+    uint8_t kind, len;
+    uint8_t pad[6];
+} slh_event;
+/* Lines of the -vcf file for one record (record_start in the merged text, record_size letters): the SNVs of the given -sites
+ * rows (a line per set bit of A C G T: REF the text's letter, ALT the bit's letter, DP=depth;AO=count) and the given events that
+ * are called -- anchor_rows[6 e ..]: the pileup row of event e's anchor (pos - 1, or pos at the record's first letter); called iff
+ * its depth d >= min_depth and 100 (fwd + rev) >= min_pct d.  A deletion is written as anchor + deleted rows -> anchor, an
+ * insertion as anchor -> anchor + letters; at the record's first letter the following base anchors (VCF 4.2), and a deletion
+ * that reaches the record's end gives no line.  Both lists ascend and lie inside the record; the lines are sorted by POS, at one
+ * POS the SNVs first. */
+int slh_format_vcf_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                        const uint64_t *site_pos, const uint32_t *site_counts, const uint8_t *site_alleles, uint64_t sites,
+                        const slh_event *events, const uint32_t *anchor_rows, uint64_t num_events, uint32_t min_depth,
+                        uint32_t min_pct);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
