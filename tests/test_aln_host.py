@@ -2,10 +2,14 @@
 replays over the two sequences, counts and lengths agree, segments of a block do not overlap, every closed gap costs its edit
 distance by a second routine, every broken gap is over the limit or holds a letter that is not A,C,G,T -- the wavefront
 traceback the kernel uses against the matrix traceback on every gap, and a constructed known answer; on random pairs with
-substitutions and indels (both strands, N in read and text, several records) and on the golden -mem files."""
+substitutions and indels (both strands, N in read and text, several records), on the golden -mem files, and on the designed gaps
+of tests/aln_gap_cases.py at edit limits from 31 to 127."""
+import functools
+
 import numpy as np
 import pytest
 
+import aln_gap_cases
 import aln_spec
 import ext_spec
 import mum_spec
@@ -15,6 +19,7 @@ from oracle import pyoracle as po
 MEM_CASES = [c for c in CASES if "-mam" not in MANIFEST[c].get("tail", [])]
 
 
+@functools.lru_cache(maxsize=4096)  # (the designed gaps come back at every edit limit)
 def levenshtein(a: bytes, b: bytes) -> int:
     """Two rows, letter by letter, case folded: independent of aln_spec.edit_matrix."""
     prev = list(range(len(b) + 1))
@@ -144,6 +149,61 @@ def test_wavefront_traceback_on_short_random_gaps():
             assert aln_spec.wavefront_ops(A, B, E) == want
             closed += want is not None
     assert closed > 3000
+
+
+# ---- designed gaps above 31 edits --------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def designed_mems():
+    ref, q, off, _ = aln_gap_cases.catalogue()
+    mem, counts = po.OracleIndex(ref.tobytes()).match_batch(q, off, aln_gap_cases.MIN_LEN, True)
+    return ref, q, off, mem, np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+
+
+@pytest.mark.parametrize("E", aln_gap_cases.EDITS)
+def test_designed_gaps_above_31_edits(E):
+    """The catalogue with the oracle's -mem rows: every CIGAR replays, every gap's distance by the letter-wise routine, the
+    wavefront traceback equal to the matrix traceback on every gap -- and the gaps are the ones the catalogue is there for."""
+    ref, q, off, mem, boff = designed_mems()
+    gaps = []
+    blocks = aln_spec.filter_blocks(mem, boff, ref, q, off, True, E=E, gaps_out=gaps)
+    T = ref.tobytes()
+    seqs = []
+    for b in range(len(blocks)):
+        rec = q[int(off[b // 2]):int(off[b // 2 + 1])]
+        seqs.append((bytes(ext_spec.revcomp(rec)) if b % 2 else rec.tobytes(), T))
+    closed, broken = check_blocks(blocks, seqs, gaps, E)
+    assert closed + broken == len(gaps) >= len(off) - 1 and sum(len(s) > 0 for s in blocks) == len(off) - 1
+    aln_gap_cases.assert_coverage(gaps, E)
+
+
+def test_bulk_batch_lists_more_gaps_than_workgroups():
+    ref, q, off, labels = aln_gap_cases.bulk()
+    mem, counts = po.OracleIndex(ref.tobytes()).match_batch(q, off, aln_gap_cases.MIN_LEN, True)
+    gaps = []
+    aln_spec.filter_blocks(mem, np.concatenate([[0], np.cumsum(counts.astype(np.int64))]), ref, q, off, True, E=127, gaps_out=gaps)
+    assert len(labels) >= 1100 + 40 and aln_gap_cases.listed_and_closed(gaps) > 1100
+    for A, B, g in gaps[::7]:
+        assert aln_spec.wavefront_ops(A, B, 127) == g
+
+
+def test_wavefront_traceback_on_designed_pieces():
+    """The pieces as designed, before any anchor trims them (so with equal first letters, and with an empty side): the wavefront
+    form against the traceback of the full matrix at every edit limit up to 127, and the banded matrix against the full one."""
+    closed = {E: 0 for E in aln_gap_cases.EDITS}
+    for label, A, B in aln_gap_cases.pieces():
+        if not aln_spec.all_acgt(A) or not aln_spec.all_acgt(B):
+            assert aln_spec.gap_ops(A, B, 127) is None and aln_spec.wavefront_ops(A, B, 127) is None
+            continue
+        D = aln_spec.edit_matrix(A, B)
+        d = int(D[len(A)][len(B)])
+        full = (aln_spec.traceback(A, B, D), d)
+        for E in aln_gap_cases.EDITS:
+            want = full if d <= E else None
+            assert aln_spec.gap_ops(A, B, E) == want, (label, E)
+            assert aln_spec.wavefront_ops(A, B, E) == want, (label, E)
+            closed[E] += want is not None
+    assert closed[31] > 10 and closed[127] > 100 and closed[127] > closed[96] > closed[65] > closed[31]
 
 
 def test_worked_example():

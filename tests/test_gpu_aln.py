@@ -1,7 +1,8 @@
 """-aln on the MI355X (slamem_find_alns_device, Index.find_alns): every result is tests/aln_spec.py applied to the complete -mem
 list of the same engine -- on the golden files the real reference wrote (both search paths, two parameter sets), on every tier
 of the gap closure, at every kind of break, at both capacity edges -- and, without the spec, constructed reads must come back
-with the CIGAR written down from their construction."""
+with the CIGAR written down from their construction.  The edit limits here are 31, 3, 2, 1 and 0; limits from 32 to 127, where a
+lane of k_aln_wave holds several diagonals and a workgroup closes several gaps, are in tests/test_gpu_aln_edits.py."""
 import os
 import subprocess
 
