@@ -5,7 +5,7 @@
 // a maximal run of anchors joined by closed gaps is a segment, and the block's two outer ends are extended by 4.13's X-drop rule.
 //
 // All on the stream behind K9, no host read-back:
-//   chain_filter            the chain's rows, compacted per block (chain_filter.hip, as it stands)
+//   chain_pass / _compact   the chain's rows, compacted per block (chain_filter.hip, as it stands)
 //   pack_batch_planes       the batch's letters as planes (filter_shared.h)
 //   k_aln_geom              a lane per chain row: its block (binary search in the offsets), the trimming, the gap to its
 //                           predecessor, the outer ends (walk), the runs of what it decides itself.  A gap with a == b <= 64 and
@@ -53,10 +53,12 @@ struct AlnLayout {
         off_list, off_n, off_flag, off_ed, off_sn, off_sflag, off_sed, off_scan, scan_bytes, off_segstart, off_slab, off_f, bytes;
 };
 
-AlnLayout aln_layout(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
-                     uint32_t max_edits) {
+AlnLayout aln_layout(const FilterBatch& b, const FilterParams& p) {
+    const uint64_t num_queries = b.num_queries, num_blocks = b.num_blocks(), query_bytes = b.query_bytes, capacity = b.capacity;
+    const uint64_t ops_capacity = p.ops_capacity;
+    const uint32_t max_edits = p.max_edits;
     AlnLayout m;
-    m.chain_bytes = align_up(chain_workspace_bytes(num_blocks, capacity), 256);  // (the -mem list K9 places lies in here)
+    m.chain_bytes = align_up(chain_workspace_bytes(b, p), 256);  // (the -mem list K9 places lies in here)
     uint64_t off = m.chain_bytes;
     m.off_ctr = off;    off = align_up(off + 64, 256);                                  // [2] listed records, [3] listed gaps, [4] slab words
     m.off_crows = off;  off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);  // the chains' rows
@@ -513,43 +515,36 @@ __global__ void __launch_bounds__(256) k_aln_write(const uint64_t* __restrict__ 
 
 }  // namespace
 
-uint64_t aln_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
-                             uint32_t max_edits) {
-    return aln_layout(num_queries, num_blocks, query_bytes, capacity, ops_capacity, max_edits).bytes;
-}
-
-void aln_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out) {
-    chain_list_buffers(ws, num_blocks, capacity, rows_out, boff_out);
-}
+uint64_t aln_workspace_bytes(const FilterBatch& b, const FilterParams& p) { return aln_layout(b, p).bytes; }
 
 #define ASTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
 
-void aln_chain_buffers(void* ws, uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity,
-                       const AlnArgs& args, slamem_mem** crows_out, uint64_t** coff_out) {
-    const AlnLayout m = aln_layout(num_queries, num_blocks, query_bytes, capacity, args.ops_capacity, args.max_edits);
+void aln_chain_buffers(void* ws, const FilterBatch& b, const FilterParams& args, slamem_mem** crows_out, uint64_t** coff_out) {
+    const AlnLayout m = aln_layout(b, args);
     char* p = static_cast<char*>(ws);
     *crows_out = reinterpret_cast<slamem_mem*>(p + m.off_crows);
     *coff_out = reinterpret_cast<uint64_t*>(p + m.off_coff);
 }
 
-int aln_filter(void* ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries, uint32_t strands,
-               uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff, unsigned long long* host_scalars,
+int aln_filter(void* ws, const FilterBatch& b, const FilterParams& args, slamem_mem*, uint64_t* out_boff, unsigned long long* host_scalars,
                hipStream_t stream) {
     slamem_mem* crows;
     uint64_t* coff;
-    aln_chain_buffers(ws, num_queries, num_queries * strands, query_bytes, capacity, args, &crows, &coff);
+    aln_chain_buffers(ws, b, args, &crows, &coff);
     // the chains: [0] rows kept (replaced below), [1] the first block out of order + 1
-    const int rc = chain_filter(ws, num_queries * strands, capacity, args.max_gap, crows, coff, nullptr, host_scalars, stream);
+    int rc = chain_pass(ws, b.num_blocks(), b.capacity, args.max_gap, nullptr, stream);
+    if (rc == SLAMEM_OK) rc = chain_compact(ws, b.num_blocks(), b.capacity, crows, coff, host_scalars, stream);
     if (rc != SLAMEM_OK) return rc;
-    return aln_after_chain(ws, ix, queries_dev, offsets_dev, num_queries, strands, query_bytes, capacity, args, out_boff, host_scalars,
-                           stream);
+    return aln_after_chain(ws, b, args, out_boff, host_scalars, stream);
 }
 
-int aln_after_chain(void* ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
-                    uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff,
-                    unsigned long long* host_scalars, hipStream_t stream) {
-    const uint64_t num_blocks = num_queries * strands;
-    const AlnLayout m = aln_layout(num_queries, num_blocks, query_bytes, capacity, args.ops_capacity, args.max_edits);
+int aln_after_chain(void* ws, const FilterBatch& b, const FilterParams& args, uint64_t* out_boff, unsigned long long* host_scalars,
+                    hipStream_t stream) {
+    const IndexView& ix = *b.ix;
+    const uint64_t* offsets_dev = b.offsets_dev;
+    const uint64_t num_queries = b.num_queries, num_blocks = b.num_blocks(), capacity = b.capacity;
+    const uint32_t strands = b.strands;
+    const AlnLayout m = aln_layout(b, args);
     char* p = static_cast<char*>(ws);
     unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
     slamem_mem* crows = reinterpret_cast<slamem_mem*>(p + m.off_crows);
@@ -569,7 +564,7 @@ int aln_after_chain(void* ws, const IndexView& ix, const void* queries_dev, cons
     uint32_t* segstart = reinterpret_cast<uint32_t*>(p + m.off_segstart);
     uint32_t* slab = reinterpret_cast<uint32_t*>(p + m.off_slab);
     int32_t* fslab = reinterpret_cast<int32_t*>(p + m.off_f);
-    const char* queries = static_cast<const char*>(queries_dev);
+    const char* queries = static_cast<const char*>(b.queries_dev);
     ASTEP(hipMemsetAsync(ctr, 0, 64, stream), "memset");
     ASTEP(pack_batch_planes(queries, offsets_dev, num_queries, ucnt, uoff, p + m.off_uscan, m.uscan_bytes, longs, units, ctr, stream),
           "pack_batch_planes");

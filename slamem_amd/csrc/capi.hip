@@ -427,7 +427,7 @@ int slamem_find_mems_device(const slamem_index* idx, const void* queries_dev, co
                             uint64_t workspace_bytes, void* stream, uint64_t* total_out) {
     return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 0, mems_dev,
                             mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
-                            total_out);
+                            total_out, nullptr, nullptr);
 }
 
 int slamem_find_mams_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
@@ -436,52 +436,58 @@ int slamem_find_mams_device(const slamem_index* idx, const void* queries_dev, co
                             uint64_t workspace_bytes, void* stream, uint64_t* total_out) {
     return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 1, mems_dev,
                             mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
-                            total_out);
+                            total_out, nullptr, nullptr);
+}
+
+// The filtered searches: the placeholders of the public interface -> values (resolve_filter_params), then the one search.
+static int filter_workspace_bytes(const char* who, int match_type, uint32_t num_queries, int both_strands, uint64_t query_bytes,
+                                  uint64_t mems_capacity, uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out) {
+    if (!bytes_out) return SLAMEM_ERR_ARG;
+    FilterParams p;
+    if (int bad = resolve_filter_params(who, 0, 0, 0, kExtXdropUnset, max_edits, &p)) return bad;
+    p.ops_capacity = ops_capacity;
+    *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, match_type, p);
+    return SLAMEM_OK;
 }
 
 int slamem_find_mums_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
                                      uint64_t* bytes_out) {
-    if (!bytes_out) return SLAMEM_ERR_ARG;
-    *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, 2);
-    return SLAMEM_OK;
+    return filter_workspace_bytes("slamem_find_mums_workspace_bytes", 2, num_queries, both_strands, query_bytes, mems_capacity, 0,
+                                  kAlnEditsUnset, bytes_out);
 }
 
 int slamem_find_mums_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                             uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands,
                             slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
                             uint64_t workspace_bytes, void* stream, uint64_t* total_out) {
+    FilterParams p;
+    if (int bad = resolve_filter_params("slamem_find_mums_device", 0, 0, 0, kExtXdropUnset, kAlnEditsUnset, &p)) return bad;
     return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 2, mems_dev,
                             mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
-                            total_out);
+                            total_out, &p, nullptr);
 }
 
 int slamem_find_smems_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
                                       uint64_t* bytes_out) {
-    if (!bytes_out) return SLAMEM_ERR_ARG;
-    *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, 3);
-    return SLAMEM_OK;
+    return filter_workspace_bytes("slamem_find_smems_workspace_bytes", 3, num_queries, both_strands, query_bytes, mems_capacity, 0,
+                                  kAlnEditsUnset, bytes_out);
 }
 
 int slamem_find_smems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                              uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_occ,
                              slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
                              uint64_t workspace_bytes, void* stream, uint64_t* total_out) {
+    FilterParams p;
+    if (int bad = resolve_filter_params("slamem_find_smems_device", max_occ, 0, 0, kExtXdropUnset, kAlnEditsUnset, &p)) return bad;
     return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 3, mems_dev,
                             mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
-                            total_out, max_occ);
+                            total_out, &p, nullptr);
 }
 
 int slamem_find_chains_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
                                        uint64_t* bytes_out) {
-    if (!bytes_out) return SLAMEM_ERR_ARG;
-    *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, 4);
-    return SLAMEM_OK;
-}
-
-static bool chain_gap_ok(uint32_t max_gap, const char* who) {
-    if (max_gap < 0x80000000u) return true;
-    set_error("%s: the maximum gap must be below 2^31 (0: the default, %u)", who, kChainDefaultGap);
-    return false;
+    return filter_workspace_bytes("slamem_find_chains_workspace_bytes", 4, num_queries, both_strands, query_bytes, mems_capacity, 0,
+                                  kAlnEditsUnset, bytes_out);
 }
 
 int slamem_find_chains_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
@@ -489,50 +495,65 @@ int slamem_find_chains_device(const slamem_index* idx, const void* queries_dev, 
                               slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev,
                               uint32_t* block_scores_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream,
                               uint64_t* total_out) {
-    if (!chain_gap_ok(max_gap, "slamem_find_chains_device")) return SLAMEM_ERR_ARG;
+    FilterParams p;
+    if (int bad = resolve_filter_params("slamem_find_chains_device", 0, max_gap, 0, kExtXdropUnset, kAlnEditsUnset, &p)) return bad;
+    p.column_dev = block_scores_dev;
     return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 4, mems_dev,
                             mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
-                            total_out, 0, max_gap, block_scores_dev);
+                            total_out, &p, nullptr);
 }
 
 int slamem_find_exts_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
                                      uint64_t* bytes_out) {
-    if (!bytes_out) return SLAMEM_ERR_ARG;
-    *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, 5);
-    return SLAMEM_OK;
+    return filter_workspace_bytes("slamem_find_exts_workspace_bytes", 5, num_queries, both_strands, query_bytes, mems_capacity, 0,
+                                  kAlnEditsUnset, bytes_out);
 }
 
 int slamem_find_exts_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
                             uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t mismatch_penalty, uint32_t xdrop,
                             slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, uint32_t* mismatches_dev,
                             void* workspace_dev, uint64_t workspace_bytes, void* stream, uint64_t* total_out) {
+    FilterParams p;
+    if (int bad = resolve_filter_params("slamem_find_exts_device", 0, 0, mismatch_penalty, xdrop, kAlnEditsUnset, &p)) return bad;
+    p.column_dev = mismatches_dev;
     return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 5, mems_dev,
                             mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream),
-                            total_out, 0, 0, mismatches_dev, mismatch_penalty, xdrop);
-}
-
-// -aln: the placeholders of the public interface -> values
-static bool aln_args_ok(const char* who, uint32_t max_gap, uint32_t& max_edits) {
-    if (max_gap >= 0x80000000u) {
-        set_error("%s: the maximum gap must be below 2^31 (0: the default, %u)", who, kChainDefaultGap);
-        return false;
-    }
-    if (max_edits == kAlnEditsUnset) max_edits = kAlnDefaultEdits;
-    if (max_edits > kAlnMaxEdits) {
-        set_error("%s: at most %u edits a gap (SLAMEM_ALN_EDITS_DEFAULT: the default, %u)", who, kAlnMaxEdits, kAlnDefaultEdits);
-        return false;
-    }
-    return true;
+                            total_out, &p, nullptr);
 }
 
 int slamem_find_alns_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
                                      uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out) {
-    if (!bytes_out) return SLAMEM_ERR_ARG;
-    if (!aln_args_ok("slamem_find_alns_workspace_bytes", 0, max_edits)) return SLAMEM_ERR_ARG;
-    *bytes_out = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity) +
-                 aln_workspace_bytes(num_queries, (uint64_t)num_queries * (both_strands ? 2u : 1u), query_bytes, mems_capacity,
-                                     ops_capacity, max_edits);
-    return SLAMEM_OK;
+    return filter_workspace_bytes("slamem_find_alns_workspace_bytes", 6, num_queries, both_strands, query_bytes, mems_capacity,
+                                  ops_capacity, max_edits, bytes_out);
+}
+
+int slamem_find_maps_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                     uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out) {
+    return filter_workspace_bytes("slamem_find_maps_workspace_bytes", 7, num_queries, both_strands, query_bytes, mems_capacity,
+                                  ops_capacity, max_edits, bytes_out);
+}
+
+// -aln and -paf (reads_dev: -paf's record per read, then offsets_out_dev takes num_queries + 1 read offsets)
+static int find_segments_device(const char* who, const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
+                                uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap,
+                                uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity, slamem_aln* segs_dev,
+                                uint64_t segs_capacity, uint64_t* offsets_out_dev, uint32_t* ops_dev, uint64_t ops_capacity,
+                                uint64_t* op_offsets_dev, slamem_map* reads_dev, int match_type, void* workspace_dev,
+                                uint64_t workspace_bytes, void* stream, uint64_t* totals_out) {
+    if (!totals_out) { set_error("%s: null argument", who); return SLAMEM_ERR_ARG; }
+    totals_out[0] = totals_out[1] = totals_out[2] = 0;
+    FilterParams p;
+    if (int bad = resolve_filter_params(who, 0, max_gap, mismatch_penalty, xdrop, max_edits, &p)) return bad;
+    p.segs = segs_dev;
+    p.segs_capacity = segs_capacity;
+    p.ops = ops_dev;
+    p.ops_capacity = ops_capacity;
+    p.op_offsets = op_offsets_dev;
+    p.reads = reads_dev;
+    uint64_t total = 0;
+    return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, nullptr,
+                            mems_capacity, offsets_out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream), &total, &p,
+                            totals_out);
 }
 
 int slamem_find_alns_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
@@ -540,115 +561,9 @@ int slamem_find_alns_device(const slamem_index* idx, const void* queries_dev, co
                             uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity, slamem_aln* segs_dev, uint64_t segs_capacity,
                             uint64_t* block_offsets_dev, uint32_t* ops_dev, uint64_t ops_capacity, uint64_t* op_offsets_dev,
                             void* workspace_dev, uint64_t workspace_bytes, void* stream, uint64_t* totals_out) {
-    if (!totals_out) { set_error("slamem_find_alns_device: null argument"); return SLAMEM_ERR_ARG; }
-    totals_out[0] = totals_out[1] = totals_out[2] = 0;
-    if (!aln_args_ok("slamem_find_alns_device", max_gap, max_edits)) return SLAMEM_ERR_ARG;
-    AlnArgs a;
-    a.max_gap = max_gap ? max_gap : kChainDefaultGap;
-    a.penalty = mismatch_penalty ? mismatch_penalty : kExtDefaultPenalty;
-    a.xdrop = xdrop == kExtXdropUnset ? kExtDefaultXdrop : xdrop;
-    a.max_edits = max_edits;
-    a.segs = segs_dev;
-    a.segs_capacity = segs_capacity;
-    a.ops = ops_dev;
-    a.ops_capacity = ops_capacity;
-    a.op_offsets = op_offsets_dev;
-    a.reads = nullptr;
-    uint64_t total = 0;
-    return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 6, nullptr, mems_capacity,
-                            block_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream), &total, 0, 0, nullptr,
-                            0, kExtXdropUnset, &a, totals_out);
-}
-
-int slamem_find_alns_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
-                          int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
-                          slamem_aln** segs_out, uint64_t** block_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
-                          uint64_t* totals_out) {
-    if (!idx || !offsets || !segs_out || !block_offsets_out || !ops_out || !op_offsets_out || !totals_out || (num_queries && !queries)) {
-        set_error("slamem_find_alns_host: null argument");
-        return SLAMEM_ERR_ARG;
-    }
-    *segs_out = nullptr; *block_offsets_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr;
-    totals_out[0] = totals_out[1] = totals_out[2] = 0;
-    {
-        uint32_t e = max_edits;
-        if (!aln_args_ok("slamem_find_alns_host", max_gap, e)) return SLAMEM_ERR_ARG;
-    }
-    const uint64_t qbytes = offsets[num_queries] - offsets[0];
-    const uint64_t num_blocks = (uint64_t)num_queries * (both_strands ? 2u : 1u);
-    const char* q0 = queries ? queries + offsets[0] : nullptr;
-    uint64_t* rel = static_cast<uint64_t*>(malloc(((uint64_t)num_queries + 1) * 8));
-    if (!rel) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
-    for (uint64_t i = 0; i <= num_queries; i++) rel[i] = offsets[i] - offsets[0];
-    uint64_t cap = 2 * qbytes / (min_len ? min_len : 1) + 4 * num_blocks + 1024;  // the -mem list
-    uint64_t scap = num_blocks + 1024, ocap = 4 * num_blocks + 4096;                // segments, operations
-    void *d_q = nullptr, *d_off = nullptr, *d_boff = nullptr, *d_segs = nullptr, *d_ops = nullptr, *d_ooff = nullptr, *d_ws = nullptr;
-    slamem_aln* h_segs = nullptr;
-    uint64_t *h_boff = nullptr, *h_ooff = nullptr;
-    uint32_t* h_ops = nullptr;
-    int rc = SLAMEM_OK;
-    hipError_t e;
-#define ALN_TRY(call) if ((e = (call)) != hipSuccess) { rc = hip_fail(e, #call, __FILE__, __LINE__); goto done; }
-    ALN_TRY(hipSetDevice(idx->device));
-    ALN_TRY(hipMalloc(&d_q, qbytes + 16));
-    ALN_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
-    ALN_TRY(hipMalloc(&d_boff, (num_blocks + 1) * 8));
-    if (qbytes) ALN_TRY(hipMemcpy(d_q, q0, qbytes, hipMemcpyHostToDevice));
-    ALN_TRY(hipMemcpy(d_off, rel, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
-    for (int attempt = 0; attempt < 4; attempt++) {
-        uint64_t ws_bytes = 0;
-        rc = slamem_find_alns_workspace_bytes(num_queries, both_strands, qbytes, cap, ocap, max_edits, &ws_bytes);
-        if (rc) goto done;
-        ALN_TRY(hipMalloc(&d_segs, (scap + 1) * sizeof(slamem_aln)));
-        ALN_TRY(hipMalloc(&d_ops, (ocap + 1) * 4));
-        ALN_TRY(hipMalloc(&d_ooff, (scap + 2) * 8));
-        ALN_TRY(hipMalloc(&d_ws, ws_bytes));
-        rc = slamem_find_alns_device(idx, d_q, static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands, max_gap,
-                                     mismatch_penalty, xdrop, max_edits, cap, static_cast<slamem_aln*>(d_segs), scap,
-                                     static_cast<uint64_t*>(d_boff), static_cast<uint32_t*>(d_ops), ocap, static_cast<uint64_t*>(d_ooff),
-                                     d_ws, ws_bytes, nullptr, totals_out);
-        if (rc != SLAMEM_ERR_CAPACITY) break;
-        (void)hipFree(d_segs); d_segs = nullptr;
-        (void)hipFree(d_ops); d_ops = nullptr;
-        (void)hipFree(d_ooff); d_ooff = nullptr;
-        (void)hipFree(d_ws); d_ws = nullptr;
-        if (totals_out[0] > cap) cap = totals_out[0] + 1024;
-        if (totals_out[1] > scap) scap = totals_out[1] + 1024;
-        if (totals_out[2] > ocap) ocap = totals_out[2] + 1024;
-    }
-    if (rc) goto done;
-    h_segs = static_cast<slamem_aln*>(malloc((totals_out[1] + 1) * sizeof(slamem_aln)));
-    h_boff = static_cast<uint64_t*>(malloc((num_blocks + 1) * 8));
-    h_ops = static_cast<uint32_t*>(malloc((totals_out[2] + 1) * 4));
-    h_ooff = static_cast<uint64_t*>(malloc((totals_out[1] + 1) * 8));
-    if (!h_segs || !h_boff || !h_ops || !h_ooff) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
-    if (totals_out[1]) ALN_TRY(hipMemcpy(h_segs, d_segs, totals_out[1] * sizeof(slamem_aln), hipMemcpyDeviceToHost));
-    ALN_TRY(hipMemcpy(h_boff, d_boff, (num_blocks + 1) * 8, hipMemcpyDeviceToHost));
-    if (totals_out[2]) ALN_TRY(hipMemcpy(h_ops, d_ops, totals_out[2] * 4, hipMemcpyDeviceToHost));
-    ALN_TRY(hipMemcpy(h_ooff, d_ooff, (totals_out[1] + 1) * 8, hipMemcpyDeviceToHost));
-    *segs_out = h_segs; *block_offsets_out = h_boff; *ops_out = h_ops; *op_offsets_out = h_ooff;
-    h_segs = nullptr; h_boff = nullptr; h_ops = nullptr; h_ooff = nullptr;
-done:
-#undef ALN_TRY
-    free(rel); free(h_segs); free(h_boff); free(h_ops); free(h_ooff);
-    if (d_q) (void)hipFree(d_q);
-    if (d_off) (void)hipFree(d_off);
-    if (d_boff) (void)hipFree(d_boff);
-    if (d_segs) (void)hipFree(d_segs);
-    if (d_ops) (void)hipFree(d_ops);
-    if (d_ooff) (void)hipFree(d_ooff);
-    if (d_ws) (void)hipFree(d_ws);
-    return rc;
-}
-
-int slamem_find_maps_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
-                                     uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out) {
-    if (!bytes_out) return SLAMEM_ERR_ARG;
-    if (!aln_args_ok("slamem_find_maps_workspace_bytes", 0, max_edits)) return SLAMEM_ERR_ARG;
-    *bytes_out = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity) +
-                 map_workspace_bytes(num_queries, (uint64_t)num_queries * (both_strands ? 2u : 1u), query_bytes, mems_capacity,
-                                     ops_capacity, max_edits);
-    return SLAMEM_OK;
+    return find_segments_device("slamem_find_alns_device", idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands,
+                                max_gap, mismatch_penalty, xdrop, max_edits, mems_capacity, segs_dev, segs_capacity, block_offsets_dev,
+                                ops_dev, ops_capacity, op_offsets_dev, nullptr, 6, workspace_dev, workspace_bytes, stream, totals_out);
 }
 
 int slamem_find_maps_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
@@ -656,42 +571,27 @@ int slamem_find_maps_device(const slamem_index* idx, const void* queries_dev, co
                             uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity, slamem_aln* segs_dev, uint64_t segs_capacity,
                             uint64_t* read_offsets_dev, uint32_t* ops_dev, uint64_t ops_capacity, uint64_t* op_offsets_dev,
                             slamem_map* reads_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream, uint64_t* totals_out) {
-    if (!totals_out) { set_error("slamem_find_maps_device: null argument"); return SLAMEM_ERR_ARG; }
-    totals_out[0] = totals_out[1] = totals_out[2] = 0;
-    if (!aln_args_ok("slamem_find_maps_device", max_gap, max_edits)) return SLAMEM_ERR_ARG;
-    AlnArgs a;
-    a.max_gap = max_gap ? max_gap : kChainDefaultGap;
-    a.penalty = mismatch_penalty ? mismatch_penalty : kExtDefaultPenalty;
-    a.xdrop = xdrop == kExtXdropUnset ? kExtDefaultXdrop : xdrop;
-    a.max_edits = max_edits;
-    a.segs = segs_dev;
-    a.segs_capacity = segs_capacity;
-    a.ops = ops_dev;
-    a.ops_capacity = ops_capacity;
-    a.op_offsets = op_offsets_dev;
-    a.reads = reads_dev;
-    uint64_t total = 0;
-    return find_mems_device(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, 7, nullptr, mems_capacity,
-                            read_offsets_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream), &total, 0, 0, nullptr,
-                            0, kExtXdropUnset, &a, totals_out);
+    return find_segments_device("slamem_find_maps_device", idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands,
+                                max_gap, mismatch_penalty, xdrop, max_edits, mems_capacity, segs_dev, segs_capacity, read_offsets_dev,
+                                ops_dev, ops_capacity, op_offsets_dev, reads_dev, 7, workspace_dev, workspace_bytes, stream, totals_out);
 }
 
-int slamem_find_maps_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
-                          int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
-                          slamem_aln** segs_out, uint64_t** read_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
-                          slamem_map** reads_out, uint64_t* totals_out) {
-    if (!idx || !offsets || !segs_out || !read_offsets_out || !ops_out || !op_offsets_out || !reads_out || !totals_out || (num_queries && !queries)) {
-        set_error("slamem_find_maps_host: null argument");
-        return SLAMEM_ERR_ARG;
-    }
-    *segs_out = nullptr; *read_offsets_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr; *reads_out = nullptr;
+#define HOST_TRY(call) if ((e = (call)) != hipSuccess) { rc = hip_fail(e, #call, __FILE__, __LINE__); goto done; }
+
+// -aln and -paf for a caller with host memory (reads_out: -paf; then the offsets are per read).  Four attempts: the -mem rows,
+// the segments and the operations may each not fit once.
+static int find_segments_host(const char* who, const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
+                              uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
+                              uint32_t max_edits, slamem_aln** segs_out, uint64_t** offsets_out, uint32_t** ops_out,
+                              uint64_t** op_offsets_out, slamem_map** reads_out, uint64_t* totals_out) {
+    *segs_out = nullptr; *offsets_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr;
+    if (reads_out) *reads_out = nullptr;
     totals_out[0] = totals_out[1] = totals_out[2] = 0;
-    {
-        uint32_t e = max_edits;
-        if (!aln_args_ok("slamem_find_maps_host", max_gap, e)) return SLAMEM_ERR_ARG;
-    }
+    FilterParams checked;
+    if (int bad = resolve_filter_params(who, 0, max_gap, mismatch_penalty, xdrop, max_edits, &checked)) return bad;
     const uint64_t qbytes = offsets[num_queries] - offsets[0];
     const uint64_t num_blocks = (uint64_t)num_queries * (both_strands ? 2u : 1u);
+    const uint64_t noff = (reads_out ? (uint64_t)num_queries : num_blocks) + 1;  // offsets that go back
     const char* q0 = queries ? queries + offsets[0] : nullptr;
     uint64_t* rel = static_cast<uint64_t*>(malloc(((uint64_t)num_queries + 1) * 8));
     if (!rel) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
@@ -705,26 +605,27 @@ int slamem_find_maps_host(const slamem_index* idx, const char* queries, const ui
     slamem_map* h_reads = nullptr;
     int rc = SLAMEM_OK;
     hipError_t e;
-#define MAP_TRY(call) if ((e = (call)) != hipSuccess) { rc = hip_fail(e, #call, __FILE__, __LINE__); goto done; }
-    MAP_TRY(hipSetDevice(idx->device));
-    MAP_TRY(hipMalloc(&d_q, qbytes + 16));
-    MAP_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
-    MAP_TRY(hipMalloc(&d_boff, ((uint64_t)num_queries + 1) * 8));
-    MAP_TRY(hipMalloc(&d_reads, ((uint64_t)num_queries + 1) * sizeof(slamem_map)));
-    if (qbytes) MAP_TRY(hipMemcpy(d_q, q0, qbytes, hipMemcpyHostToDevice));
-    MAP_TRY(hipMemcpy(d_off, rel, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
+    HOST_TRY(hipSetDevice(idx->device));
+    HOST_TRY(hipMalloc(&d_q, qbytes + 16));
+    HOST_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
+    HOST_TRY(hipMalloc(&d_boff, noff * 8));
+    if (reads_out) HOST_TRY(hipMalloc(&d_reads, ((uint64_t)num_queries + 1) * sizeof(slamem_map)));
+    if (qbytes) HOST_TRY(hipMemcpy(d_q, q0, qbytes, hipMemcpyHostToDevice));
+    HOST_TRY(hipMemcpy(d_off, rel, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
     for (int attempt = 0; attempt < 4; attempt++) {
         uint64_t ws_bytes = 0;
-        rc = slamem_find_maps_workspace_bytes(num_queries, both_strands, qbytes, cap, ocap, max_edits, &ws_bytes);
+        rc = filter_workspace_bytes(reads_out ? "slamem_find_maps_workspace_bytes" : "slamem_find_alns_workspace_bytes", reads_out ? 7 : 6,
+                                    num_queries, both_strands, qbytes, cap, ocap, max_edits, &ws_bytes);
         if (rc) goto done;
-        MAP_TRY(hipMalloc(&d_segs, (scap + 1) * sizeof(slamem_aln)));
-        MAP_TRY(hipMalloc(&d_ops, (ocap + 1) * 4));
-        MAP_TRY(hipMalloc(&d_ooff, (scap + 2) * 8));
-        MAP_TRY(hipMalloc(&d_ws, ws_bytes));
-        rc = slamem_find_maps_device(idx, d_q, static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands, max_gap,
-                                     mismatch_penalty, xdrop, max_edits, cap, static_cast<slamem_aln*>(d_segs), scap,
-                                     static_cast<uint64_t*>(d_boff), static_cast<uint32_t*>(d_ops), ocap, static_cast<uint64_t*>(d_ooff),
-                                     static_cast<slamem_map*>(d_reads), d_ws, ws_bytes, nullptr, totals_out);
+        HOST_TRY(hipMalloc(&d_segs, (scap + 1) * sizeof(slamem_aln)));
+        HOST_TRY(hipMalloc(&d_ops, (ocap + 1) * 4));
+        HOST_TRY(hipMalloc(&d_ooff, (scap + 2) * 8));
+        HOST_TRY(hipMalloc(&d_ws, ws_bytes));
+        rc = find_segments_device(reads_out ? "slamem_find_maps_device" : "slamem_find_alns_device", idx, d_q,
+                                  static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands, max_gap, mismatch_penalty,
+                                  xdrop, max_edits, cap, static_cast<slamem_aln*>(d_segs), scap, static_cast<uint64_t*>(d_boff),
+                                  static_cast<uint32_t*>(d_ops), ocap, static_cast<uint64_t*>(d_ooff), static_cast<slamem_map*>(d_reads),
+                                  reads_out ? 7 : 6, d_ws, ws_bytes, nullptr, totals_out);
         if (rc != SLAMEM_ERR_CAPACITY) break;
         (void)hipFree(d_segs); d_segs = nullptr;
         (void)hipFree(d_ops); d_ops = nullptr;
@@ -736,20 +637,20 @@ int slamem_find_maps_host(const slamem_index* idx, const char* queries, const ui
     }
     if (rc) goto done;
     h_segs = static_cast<slamem_aln*>(malloc((totals_out[1] + 1) * sizeof(slamem_aln)));
-    h_boff = static_cast<uint64_t*>(malloc(((uint64_t)num_queries + 1) * 8));
-    h_reads = static_cast<slamem_map*>(malloc(((uint64_t)num_queries + 1) * sizeof(slamem_map)));
+    h_boff = static_cast<uint64_t*>(malloc(noff * 8));
+    if (reads_out) h_reads = static_cast<slamem_map*>(malloc(((uint64_t)num_queries + 1) * sizeof(slamem_map)));
     h_ops = static_cast<uint32_t*>(malloc((totals_out[2] + 1) * 4));
     h_ooff = static_cast<uint64_t*>(malloc((totals_out[1] + 1) * 8));
-    if (!h_segs || !h_boff || !h_ops || !h_ooff || !h_reads) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
-    if (totals_out[1]) MAP_TRY(hipMemcpy(h_segs, d_segs, totals_out[1] * sizeof(slamem_aln), hipMemcpyDeviceToHost));
-    MAP_TRY(hipMemcpy(h_boff, d_boff, ((uint64_t)num_queries + 1) * 8, hipMemcpyDeviceToHost));
-    if (num_queries) MAP_TRY(hipMemcpy(h_reads, d_reads, (uint64_t)num_queries * sizeof(slamem_map), hipMemcpyDeviceToHost));
-    if (totals_out[2]) MAP_TRY(hipMemcpy(h_ops, d_ops, totals_out[2] * 4, hipMemcpyDeviceToHost));
-    MAP_TRY(hipMemcpy(h_ooff, d_ooff, (totals_out[1] + 1) * 8, hipMemcpyDeviceToHost));
-    *segs_out = h_segs; *read_offsets_out = h_boff; *ops_out = h_ops; *op_offsets_out = h_ooff; *reads_out = h_reads;
+    if (!h_segs || !h_boff || !h_ops || !h_ooff || (reads_out && !h_reads)) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
+    if (totals_out[1]) HOST_TRY(hipMemcpy(h_segs, d_segs, totals_out[1] * sizeof(slamem_aln), hipMemcpyDeviceToHost));
+    HOST_TRY(hipMemcpy(h_boff, d_boff, noff * 8, hipMemcpyDeviceToHost));
+    if (reads_out && num_queries) HOST_TRY(hipMemcpy(h_reads, d_reads, (uint64_t)num_queries * sizeof(slamem_map), hipMemcpyDeviceToHost));
+    if (totals_out[2]) HOST_TRY(hipMemcpy(h_ops, d_ops, totals_out[2] * 4, hipMemcpyDeviceToHost));
+    HOST_TRY(hipMemcpy(h_ooff, d_ooff, (totals_out[1] + 1) * 8, hipMemcpyDeviceToHost));
+    *segs_out = h_segs; *offsets_out = h_boff; *ops_out = h_ops; *op_offsets_out = h_ooff;
+    if (reads_out) *reads_out = h_reads;
     h_segs = nullptr; h_boff = nullptr; h_ops = nullptr; h_ooff = nullptr; h_reads = nullptr;
 done:
-#undef MAP_TRY
     free(rel); free(h_segs); free(h_boff); free(h_ops); free(h_ooff); free(h_reads);
     if (d_q) (void)hipFree(d_q);
     if (d_off) (void)hipFree(d_off);
@@ -762,63 +663,94 @@ done:
     return rc;
 }
 
+int slamem_find_alns_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
+                          int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
+                          slamem_aln** segs_out, uint64_t** block_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
+                          uint64_t* totals_out) {
+    if (!idx || !offsets || !segs_out || !block_offsets_out || !ops_out || !op_offsets_out || !totals_out || (num_queries && !queries)) {
+        set_error("slamem_find_alns_host: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    return find_segments_host("slamem_find_alns_host", idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty,
+                              xdrop, max_edits, segs_out, block_offsets_out, ops_out, op_offsets_out, nullptr, totals_out);
+}
+
+int slamem_find_maps_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
+                          int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
+                          slamem_aln** segs_out, uint64_t** read_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
+                          slamem_map** reads_out, uint64_t* totals_out) {
+    if (!idx || !offsets || !segs_out || !read_offsets_out || !ops_out || !op_offsets_out || !reads_out || !totals_out || (num_queries && !queries)) {
+        set_error("slamem_find_maps_host: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    return find_segments_host("slamem_find_maps_host", idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty,
+                              xdrop, max_edits, segs_out, read_offsets_out, ops_out, op_offsets_out, reads_out, totals_out);
+}
+
 void slamem_host_free(void* p) { free(p); }
 
-static int find_matches_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
-                             uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out,
-                             uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ = 0, uint32_t max_gap = 0,
-                             uint32_t** block_scores_out = nullptr, uint32_t ext_penalty = 0, uint32_t ext_xdrop = kExtXdropUnset);
+static int find_matches_host(const char* who, const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
+                             uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out, uint64_t** block_offsets_out,
+                             uint64_t* total_out, uint32_t max_occ, uint32_t max_gap, uint32_t** column_out, uint32_t ext_penalty,
+                             uint32_t ext_xdrop);
 
 int slamem_find_mems_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                           uint32_t min_len, int both_strands, slamem_mem** mems_out, uint64_t** block_offsets_out,
                           uint64_t* total_out) {
-    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 0, mems_out, block_offsets_out, total_out);
+    return find_matches_host("slamem_find_mems_host", idx, queries, offsets, num_queries, min_len, both_strands, 0, mems_out,
+                             block_offsets_out, total_out, 0, 0, nullptr, 0, kExtXdropUnset);
 }
 
 int slamem_find_mams_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                           uint32_t min_len, int both_strands, slamem_mem** mems_out, uint64_t** block_offsets_out,
                           uint64_t* total_out) {
-    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 1, mems_out, block_offsets_out, total_out);
+    return find_matches_host("slamem_find_mams_host", idx, queries, offsets, num_queries, min_len, both_strands, 1, mems_out,
+                             block_offsets_out, total_out, 0, 0, nullptr, 0, kExtXdropUnset);
 }
 
 int slamem_find_mums_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                           uint32_t min_len, int both_strands, slamem_mem** mems_out, uint64_t** block_offsets_out,
                           uint64_t* total_out) {
-    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 2, mems_out, block_offsets_out, total_out);
+    return find_matches_host("slamem_find_mums_host", idx, queries, offsets, num_queries, min_len, both_strands, 2, mems_out,
+                             block_offsets_out, total_out, 0, 0, nullptr, 0, kExtXdropUnset);
 }
 
 int slamem_find_smems_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                            uint32_t min_len, int both_strands, uint32_t max_occ, slamem_mem** mems_out,
                            uint64_t** block_offsets_out, uint64_t* total_out) {
-    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 3, mems_out, block_offsets_out, total_out,
-                             max_occ);
+    return find_matches_host("slamem_find_smems_host", idx, queries, offsets, num_queries, min_len, both_strands, 3, mems_out,
+                             block_offsets_out, total_out, max_occ, 0, nullptr, 0, kExtXdropUnset);
 }
 
 int slamem_find_chains_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                             uint32_t min_len, int both_strands, uint32_t max_gap, slamem_mem** mems_out,
                             uint64_t** block_offsets_out, uint32_t** block_scores_out, uint64_t* total_out) {
-    if (!chain_gap_ok(max_gap, "slamem_find_chains_host")) return SLAMEM_ERR_ARG;
-    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 4, mems_out, block_offsets_out, total_out,
-                             0, max_gap, block_scores_out);
+    return find_matches_host("slamem_find_chains_host", idx, queries, offsets, num_queries, min_len, both_strands, 4, mems_out,
+                             block_offsets_out, total_out, 0, max_gap, block_scores_out, 0, kExtXdropUnset);
 }
 
 int slamem_find_exts_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                           uint32_t min_len, int both_strands, uint32_t mismatch_penalty, uint32_t xdrop, slamem_mem** mems_out,
                           uint64_t** block_offsets_out, uint32_t** mismatches_out, uint64_t* total_out) {
-    return find_matches_host(idx, queries, offsets, num_queries, min_len, both_strands, 5, mems_out, block_offsets_out, total_out,
-                             0, 0, mismatches_out, mismatch_penalty, xdrop);
+    return find_matches_host("slamem_find_exts_host", idx, queries, offsets, num_queries, min_len, both_strands, 5, mems_out,
+                             block_offsets_out, total_out, 0, 0, mismatches_out, mismatch_penalty, xdrop);
 }
 
-// (block_scores_out: -chain's uint32 per strand block, or -ext's uint32 per returned row)
-static int find_matches_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
-                             uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out,
-                             uint64_t** block_offsets_out, uint64_t* total_out, uint32_t max_occ, uint32_t max_gap,
-                             uint32_t** block_scores_out, uint32_t ext_penalty, uint32_t ext_xdrop) {
+// (column_out: -chain's uint32 per strand block, or -ext's uint32 per returned row.  `who` names the caller in the resolver's
+// messages only: the null-argument message has always named slamem_find_mems_host, and callers may match on it)
+static int find_matches_host(const char* who, const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
+                             uint32_t min_len, int both_strands, int match_type, slamem_mem** mems_out, uint64_t** block_offsets_out,
+                             uint64_t* total_out, uint32_t max_occ, uint32_t max_gap, uint32_t** column_out, uint32_t ext_penalty,
+                             uint32_t ext_xdrop) {
+    FilterParams p;
+    if (int bad = resolve_filter_params(who, max_occ, max_gap, ext_penalty, ext_xdrop, kAlnEditsUnset, &p)) return bad;
     if (!idx || !offsets || !mems_out || !block_offsets_out || !total_out || (num_queries && !queries)) {
         set_error("slamem_find_mems_host: null argument");
         return SLAMEM_ERR_ARG;
     }
     SLAMEM_HIP(hipSetDevice(idx->device));
+    const FilterDesc* filter = filter_for(match_type);
+    const bool per_row = filter && filter->column_per_row;  // (the column grows with the capacity)
     const uint64_t qbytes = offsets[num_queries];
     const uint64_t num_blocks = (uint64_t)num_queries * (both_strands ? 2 : 1);
     void *d_q = nullptr, *d_off = nullptr, *d_boff = nullptr, *d_mems = nullptr, *d_ws = nullptr, *d_score = nullptr;
@@ -828,25 +760,25 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
     int rc = SLAMEM_OK;
     uint64_t cap = qbytes / 16 + 4 * (uint64_t)num_blocks + 1024;  // first guess; grown on SLAMEM_ERR_CAPACITY
     hipError_t e;
-#define HOST_TRY(call) if ((e = (call)) != hipSuccess) { rc = hip_fail(e, #call, __FILE__, __LINE__); goto done; }
     HOST_TRY(hipMalloc(&d_q, qbytes + 16));
     HOST_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
     HOST_TRY(hipMalloc(&d_boff, (num_blocks + 1) * 8));
-    if (block_scores_out && match_type != 5) HOST_TRY(hipMalloc(&d_score, (num_blocks + 1) * 4));
+    if (column_out && !per_row) HOST_TRY(hipMalloc(&d_score, (num_blocks + 1) * 4));
     HOST_TRY(hipMemcpy(d_q, queries, qbytes, hipMemcpyHostToDevice));
     HOST_TRY(hipMemcpy(d_off, offsets, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
     for (int attempt = 0; attempt < 3; attempt++) {
-        uint64_t ws_bytes = search_workspace_bytes(num_queries, both_strands, qbytes, cap, match_type);
+        uint64_t ws_bytes = search_workspace_bytes(num_queries, both_strands, qbytes, cap, match_type, p);
         HOST_TRY(hipMalloc(&d_mems, cap * sizeof(slamem_mem) + 16));
         HOST_TRY(hipMalloc(&d_ws, ws_bytes));
-        if (block_scores_out && match_type == 5) {  // (a uint32 per row: grows with the capacity)
+        if (column_out && per_row) {
             if (d_score) (void)hipFree(d_score);
             d_score = nullptr;
             HOST_TRY(hipMalloc(&d_score, (cap + 1) * 4));
         }
+        p.column_dev = static_cast<uint32_t*>(d_score);
         rc = find_mems_device(idx, d_q, static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands,
                               match_type, static_cast<slamem_mem*>(d_mems), cap, static_cast<uint64_t*>(d_boff), d_ws, ws_bytes,
-                              nullptr, total_out, max_occ, max_gap, static_cast<uint32_t*>(d_score), ext_penalty, ext_xdrop);
+                              nullptr, total_out, filter ? &p : nullptr, nullptr);
         if (rc != SLAMEM_ERR_CAPACITY) break;
         (void)hipFree(d_mems); d_mems = nullptr;
         (void)hipFree(d_ws); d_ws = nullptr;
@@ -855,14 +787,14 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
     if (rc) goto done;
     h_mems = static_cast<slamem_mem*>(malloc((*total_out ? *total_out : 1) * sizeof(slamem_mem)));
     h_boff = static_cast<uint64_t*>(malloc((num_blocks + 1) * 8));
-    if (block_scores_out) h_score = static_cast<uint32_t*>(malloc(((match_type == 5 ? *total_out : num_blocks) + 1) * 4));
-    if (!h_mems || !h_boff || (block_scores_out && !h_score)) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
+    if (column_out) h_score = static_cast<uint32_t*>(malloc(((per_row ? *total_out : num_blocks) + 1) * 4));
+    if (!h_mems || !h_boff || (column_out && !h_score)) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
     if (*total_out) HOST_TRY(hipMemcpy(h_mems, d_mems, *total_out * sizeof(slamem_mem), hipMemcpyDeviceToHost));
     HOST_TRY(hipMemcpy(h_boff, d_boff, (num_blocks + 1) * 8, hipMemcpyDeviceToHost));
-    if (block_scores_out) {
-        const uint64_t nscore = match_type == 5 ? *total_out : num_blocks;
+    if (column_out) {
+        const uint64_t nscore = per_row ? *total_out : num_blocks;
         if (nscore) HOST_TRY(hipMemcpy(h_score, d_score, nscore * 4, hipMemcpyDeviceToHost));
-        *block_scores_out = h_score;
+        *column_out = h_score;
         h_score = nullptr;
     }
     *mems_out = h_mems;
@@ -870,7 +802,6 @@ static int find_matches_host(const slamem_index* idx, const char* queries, const
     h_mems = nullptr;
     h_boff = nullptr;
 done:
-#undef HOST_TRY
     free(h_mems);
     free(h_boff);
     free(h_score);
@@ -882,5 +813,6 @@ done:
     if (d_ws) (void)hipFree(d_ws);
     return rc;
 }
+#undef HOST_TRY
 
 }  // extern "C"

@@ -22,18 +22,14 @@
 //                       LDS and, a tile at a time, to the workspace; then lane 0 walks the predecessors from the chain's end,
 //                       staged in LDS tile by tile, and the lanes set the keep flags
 //   scan                kept rows per block -> new block offsets (scan_sum_exclusive_u32_u64)
-//   k_chain_copy / k_chain_list_copy   the kept rows, in order (listed blocks: a wave ranks 64 rows at a time with a ballot)
+//   k_filter_copy / k_chain_list_copy  the kept rows, in order (listed blocks: a wave ranks 64 rows at a time with a ballot)
 // Every row is checked against the one before it: a block out of the emission order fails the call (the first such block,
 // + 1, goes back with the batch's scalars) -- never wrong rows.
-#include "common.h"
-#include "prims.h"
+#include "filter_blocks.h"
 
 namespace slamem {
 
 namespace {
-
-inline unsigned grid_for(uint64_t items, unsigned block = 256) { return (unsigned)((items + block - 1) / block); }
-inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 // A lane tests the pairs of blocks of up to this many rows: at most 496 pairs, of which a lane retires one in some tens of
 // cycles, so the slowest lane holds its wave for tens of microseconds.  The work is quadratic: at 4.11's 256 rows one lane
@@ -43,44 +39,20 @@ constexpr uint32_t kChainTile = 1024;     // rows of a listed block staged in LD
 constexpr unsigned kChainWaveGrid = 2048; // one-wave workgroups that share the list (8 per CU)
 constexpr uint32_t kNoPred = 0xFFFFFFFFu;
 
-struct ChainLayout {
-    uint64_t off_ctr, off_rows, off_boff, off_cnt, off_newoff, off_keep, off_f, off_pred, off_score, off_scan, scan_bytes, off_list,
-        bytes;
+struct ChainLayout : FilterPrefix {
+    uint64_t off_f, off_pred, off_score, off_list, bytes;
 };
 
 ChainLayout chain_layout(uint64_t num_blocks, uint64_t capacity) {
     ChainLayout m;
-    uint64_t off = 0;
-    m.off_ctr = off;    off = align_up(off + 64, 256);                                  // [0] listed blocks, [1] order violation
-    m.off_rows = off;   off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);  // the -mem list (K9 places it here)
-    m.off_boff = off;   off = align_up(off + (num_blocks + 1) * 8, 256);                // ... and its block offsets
-    m.off_cnt = off;    off = align_up(off + (num_blocks + 1) * 4, 256);                // kept rows per block
-    m.off_newoff = off; off = align_up(off + (num_blocks + 1) * 8, 256);                // their exclusive sums
-    m.off_keep = off;   off = align_up(off + capacity + 16, 256);                       // a byte per -mem row
+    uint64_t off = m.begin(num_blocks, capacity);                                       // ctr: [0] listed blocks, [1] order violation
     m.off_f = off;      off = align_up(off + capacity * 4 + 16, 256);                   // f per -mem row
     m.off_pred = off;   off = align_up(off + capacity * 4 + 16, 256);                   // predecessor per -mem row (place in its block)
     m.off_score = off;  off = align_up(off + (num_blocks + 1) * 4, 256);                // block scores, when the caller wants none
-    size_t need = 0;
-    (void)scan_sum_exclusive_u32_u64(nullptr, need, nullptr, nullptr, num_blocks, 0);
-    m.scan_bytes = need;
-    m.off_scan = off;   off = align_up(off + need, 256);
+    off = m.scan_at(off, num_blocks);
     m.off_list = off;   off = align_up(off + (capacity / (kChainLaneMax + 1) + 1) * 8, 256);  // listed strand blocks
     m.bytes = off;
     return m;
-}
-
-__device__ __forceinline__ void clamp_block(const uint64_t* __restrict__ boff, uint64_t b, uint64_t cap, uint64_t& s, uint64_t& e) {
-    // (a batch whose -mem list did not fit has offsets beyond the capacity: its result is refused, nothing is read past it)
-    s = boff[b];
-    e = boff[b + 1];
-    if (s > cap) s = cap;
-    if (e > cap) e = cap;
-    if (e < s) e = s;
-}
-
-// the order every block must be in: q descending, then L non-increasing
-__device__ __forceinline__ bool out_of_order(const slamem_mem& prev, const slamem_mem& r) {
-    return r.query_pos > prev.query_pos || (r.query_pos == prev.query_pos && r.length > prev.length);
 }
 
 // f(j) + link(j, i) packed with j's place, or 0 when j may not precede i or gives no more than L_i.  dq = q_i - q_j is the
@@ -299,26 +271,6 @@ __global__ void __launch_bounds__(64) k_chain_wave(const uint64_t* __restrict__ 
     }
 }
 
-// one lane per strand block: new offsets, and the kept rows of blocks of up to kChainLaneMax rows
-__global__ void __launch_bounds__(256) k_chain_copy(const uint64_t* __restrict__ boff, uint64_t nb, const slamem_mem* __restrict__ rows,
-                                                    uint64_t cap, const uint8_t* __restrict__ keep, const uint64_t* __restrict__ newoff,
-                                                    slamem_mem* __restrict__ out, uint64_t* __restrict__ out_boff) {
-    const uint64_t b = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (b > nb) return;
-    uint64_t d = newoff[b];
-    out_boff[b] = d;
-    if (b == nb) return;
-    uint64_t s, e;
-    clamp_block(boff, b, cap, s, e);
-    if (e - s > kChainLaneMax) return;
-    const uint64_t d_end = newoff[b + 1];
-    for (uint64_t i = s; i < e && d < d_end; i++) {
-        if (!keep[i]) continue;
-        if (d < cap) out[d] = rows[i];
-        d++;
-    }
-}
-
 // a listed block's kept rows, in order: a wave ranks 64 rows at a time
 __global__ void __launch_bounds__(64) k_chain_list_copy(const uint64_t* __restrict__ list, const unsigned long long* __restrict__ ctr,
                                                         const uint64_t* __restrict__ boff, uint64_t cap, const slamem_mem* __restrict__ rows,
@@ -348,54 +300,33 @@ __global__ void __launch_bounds__(64) k_chain_list_copy(const uint64_t* __restri
 
 }  // namespace
 
-uint64_t chain_workspace_bytes(uint64_t num_blocks, uint64_t capacity) { return chain_layout(num_blocks, capacity).bytes; }
+uint64_t chain_workspace_bytes(const FilterBatch& b, const FilterParams&) { return chain_layout(b.num_blocks(), b.capacity).bytes; }
 
 #define CSTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
 
-void chain_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out) {
-    const ChainLayout m = chain_layout(num_blocks, capacity);
-    char* p = static_cast<char*>(ws);
-    *rows_out = reinterpret_cast<slamem_mem*>(p + m.off_rows);
-    *boff_out = reinterpret_cast<uint64_t*>(p + m.off_boff);
-}
-
 ChainBufs chain_buffers(void* ws, uint64_t num_blocks, uint64_t capacity) {
     const ChainLayout m = chain_layout(num_blocks, capacity);
+    const FilterBufs w = filter_bufs(ws, m);
     char* p = static_cast<char*>(ws);
-    ChainBufs b;
-    b.ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
-    b.rows = reinterpret_cast<slamem_mem*>(p + m.off_rows);
-    b.boff = reinterpret_cast<uint64_t*>(p + m.off_boff);
-    b.cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
-    b.keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
-    b.score = reinterpret_cast<uint32_t*>(p + m.off_score);
-    b.list = reinterpret_cast<uint64_t*>(p + m.off_list);
-    b.scan = p + m.off_scan;
-    b.scan_bytes = m.scan_bytes;
-    b.lane_max = kChainLaneMax;
-    b.wave_grid = kChainWaveGrid;
-    return b;
+    return ChainBufs{w.ctr, w.rows, w.boff, w.cnt, w.keep, reinterpret_cast<uint32_t*>(p + m.off_score),
+                     reinterpret_cast<uint64_t*>(p + m.off_list), w.scan, w.scan_bytes, kChainLaneMax, kChainWaveGrid};
 }
 
 // the DP and the backtrack: keep flags, kept rows and score per block
 int chain_pass(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, uint32_t* out_scores, hipStream_t stream) {
     const ChainLayout m = chain_layout(num_blocks, capacity);
+    const FilterBufs w = filter_bufs(ws, m);
     char* p = static_cast<char*>(ws);
-    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
-    const slamem_mem* rows = reinterpret_cast<const slamem_mem*>(p + m.off_rows);
-    const uint64_t* boff = reinterpret_cast<const uint64_t*>(p + m.off_boff);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
-    uint8_t* keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
     uint32_t* f = reinterpret_cast<uint32_t*>(p + m.off_f);
     uint32_t* pred = reinterpret_cast<uint32_t*>(p + m.off_pred);
     uint32_t* score = out_scores ? out_scores : reinterpret_cast<uint32_t*>(p + m.off_score);
     uint64_t* list = reinterpret_cast<uint64_t*>(p + m.off_list);
-    CSTEP(hipMemsetAsync(ctr, 0, 16, stream), "memset");
-    hipLaunchKernelGGL(k_chain_lane, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity, max_gap, cnt,
-                       keep, f, pred, score, list, ctr);
+    CSTEP(hipMemsetAsync(w.ctr, 0, 16, stream), "memset");
+    hipLaunchKernelGGL(k_chain_lane, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, (const uint64_t*)w.boff, num_blocks,
+                       (const slamem_mem*)w.rows, capacity, max_gap, w.cnt, w.keep, f, pred, score, list, w.ctr);
     CSTEP(hipGetLastError(), "k_chain_lane");
-    hipLaunchKernelGGL(k_chain_wave, dim3(kChainWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)ctr,
-                       boff, rows, capacity, max_gap, keep, f, pred, cnt, score, ctr);
+    hipLaunchKernelGGL(k_chain_wave, dim3(kChainWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)w.ctr,
+                       (const uint64_t*)w.boff, (const slamem_mem*)w.rows, capacity, max_gap, w.keep, f, pred, w.cnt, score, w.ctr);
     CSTEP(hipGetLastError(), "k_chain_wave");
     return SLAMEM_OK;
 }
@@ -404,34 +335,22 @@ int chain_pass(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_ga
 int chain_compact(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem* out_mems, uint64_t* out_boff,
                   unsigned long long* host_scalars, hipStream_t stream) {
     const ChainLayout m = chain_layout(num_blocks, capacity);
-    char* p = static_cast<char*>(ws);
-    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
-    const slamem_mem* rows = reinterpret_cast<const slamem_mem*>(p + m.off_rows);
-    const uint64_t* boff = reinterpret_cast<const uint64_t*>(p + m.off_boff);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
-    uint64_t* newoff = reinterpret_cast<uint64_t*>(p + m.off_newoff);
-    uint8_t* keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
-    uint64_t* list = reinterpret_cast<uint64_t*>(p + m.off_list);
-    size_t need = m.scan_bytes;
-    CSTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, cnt, newoff, num_blocks, stream), "scan");
-    hipLaunchKernelGGL(k_chain_copy, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity,
-                       (const uint8_t*)keep, (const uint64_t*)newoff, out_mems, out_boff);
-    CSTEP(hipGetLastError(), "k_chain_copy");
+    const FilterBufs w = filter_bufs(ws, m);
+    uint64_t* list = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + m.off_list);
+    CSTEP(compact_kept<kChainLaneMax>(w, num_blocks, capacity, w.rows, out_mems, out_boff, stream), "compact_kept");
     hipLaunchKernelGGL(k_chain_list_copy, dim3(kChainWaveGrid), dim3(64), 0, stream, (const uint64_t*)list,
-                       (const unsigned long long*)ctr, boff, capacity, rows, (const uint8_t*)keep, (const uint32_t*)cnt,
-                       (const uint64_t*)newoff, out_mems);
+                       (const unsigned long long*)w.ctr, (const uint64_t*)w.boff, capacity, (const slamem_mem*)w.rows,
+                       (const uint8_t*)w.keep, (const uint32_t*)w.cnt, (const uint64_t*)w.newoff, out_mems);
     CSTEP(hipGetLastError(), "k_chain_list_copy");
-    // [0] rows kept, [1] the first block out of order + 1 (0: none)
-    CSTEP(hipMemcpyAsync(host_scalars, newoff + num_blocks, 8, hipMemcpyDeviceToHost, stream), "memcpy");
-    CSTEP(hipMemcpyAsync(host_scalars + 1, ctr + 1, 8, hipMemcpyDeviceToHost, stream), "memcpy");
+    CSTEP(kept_scalars(w, num_blocks, w.ctr + 1, host_scalars, stream), "memcpy");
     return SLAMEM_OK;
 }
 
-int chain_filter(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, slamem_mem* out_mems, uint64_t* out_boff,
-                 uint32_t* out_scores, unsigned long long* host_scalars, hipStream_t stream) {
-    const int rc = chain_pass(ws, num_blocks, capacity, max_gap, out_scores, stream);
+int chain_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
+                 unsigned long long* host_scalars, hipStream_t stream) {
+    const int rc = chain_pass(ws, b.num_blocks(), b.capacity, p.max_gap, p.column_dev, stream);
     if (rc != SLAMEM_OK) return rc;
-    return chain_compact(ws, num_blocks, capacity, out_mems, out_boff, host_scalars, stream);
+    return chain_compact(ws, b.num_blocks(), b.capacity, out_mems, out_boff, host_scalars, stream);
 }
 #undef CSTEP
 

@@ -301,43 +301,101 @@ namespace slamem {
 void make_view(slamem_index* idx);
 int build_index_device(const void* text_dev, uint32_t n, int device, hipStream_t stream, int layout, slamem_index** out);
 int estimate_build_bytes(uint32_t n, int layout, uint64_t* arena_bytes, uint64_t* peak_bytes);
-struct AlnArgs;
+uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity);
+
+// ---- the filters behind K9 (match types 2..7) ---------------------------------------------------------------
+// The search runs as -mem, K9 places the -mem list at the start of the filter's workspace (behind the -mem workspace), and the
+// filter writes the kept rows to the caller's buffers.  filters.hip holds the table and the resolver; a filter is one row there
+// and one file.
+
+// A filter's parameters, every value final.  Only resolve_filter_params makes one from the placeholders of the public interface.
+struct FilterParams {
+    uint32_t max_occ;      // -smem: the occurrence cap (0: none)
+    uint32_t max_gap;      // -chain, -aln, -paf: the maximum gap, >= 1
+    uint32_t penalty;      // -ext, -aln, -paf: the mismatch penalty, >= 1
+    uint32_t xdrop;        // ... and the drop, >= 0
+    uint32_t max_edits;    // -aln, -paf: the most edits in a gap, <= kAlnMaxEdits
+    uint32_t* column_dev;  // a uint32 per strand block (-chain: scores) or per kept row (-ext: mismatches; FilterDesc::column_per_row), or nullptr
+    // -aln, -paf: where the segments and operations go (then mems_dev may be null and block_offsets_dev takes the segments' offsets)
+    slamem_aln* segs;
+    uint64_t segs_capacity;
+    uint32_t* ops;
+    uint64_t ops_capacity;
+    uint64_t* op_offsets;  // segs_capacity + 1
+    slamem_map* reads;     // -paf: a record per read (then block_offsets_dev takes num_queries + 1 read offsets)
+};
+constexpr uint32_t kChainDefaultGap = 5000, kExtDefaultPenalty = 4, kExtDefaultXdrop = 20, kAlnDefaultEdits = 31;
+constexpr uint32_t kExtXdropUnset = 0xFFFFFFFFu, kAlnEditsUnset = 0xFFFFFFFFu, kAlnMaxEdits = 127;
+// The placeholders (0: no cap, kChainDefaultGap, kExtDefaultPenalty; kExtXdropUnset; kAlnEditsUnset) -> values, the outputs null.
+// SLAMEM_ERR_ARG, with `who` in the message: a gap of 2^31 or more, more than kAlnMaxEdits edits.
+int resolve_filter_params(const char* who, uint32_t max_occ, uint32_t max_gap, uint32_t penalty, uint32_t xdrop, uint32_t max_edits,
+                          FilterParams* out);
+
+// What a filter sees of the batch (workspace_bytes: the four sizes alone)
+struct FilterBatch {
+    const IndexView* ix;
+    const void* queries_dev;
+    const uint64_t* offsets_dev;
+    uint64_t num_queries;
+    uint32_t strands;
+    uint64_t query_bytes, capacity;  // capacity: rows of the -mem list
+    uint64_t num_blocks() const { return num_queries * strands; }
+};
+
+struct FilterDesc {
+    const char* name;      // the public function the messages name
+    const char* flag;      // "-ext", ...
+    const char* noun;      // what a block out of the emission order costs ("no SMEMs returned"); nullptr: the filter asks no order
+    const char* limits;    // the whole message when a bound below is passed
+    uint64_t capacity_end; // mems_capacity must be below this
+    bool bounds_blocks;    // ... and the strand blocks below 2^32 - 1
+    bool needs_planes;     // reads the text planes of the index
+    bool column_per_row;   // FilterParams::column_dev is per kept row, not per strand block
+    bool segments;         // no rows go back (mems_dev may be null): segments and operations go where FilterParams says
+    bool needs_reads;      // ... and a record per read to FilterParams::reads
+    int scalars;           // host scalars it returns: [0] rows kept (-aln, -paf: segments), [1] the first block out of order + 1, [2] operations
+    uint64_t (*workspace_bytes)(const FilterBatch&, const FilterParams&);
+    // all on the stream, host_scalars copied asynchronously
+    int (*run)(void* ws, const FilterBatch&, const FilterParams&, slamem_mem* out_mems, uint64_t* out_boff, unsigned long long* host_scalars,
+               hipStream_t stream);
+    // (-mum) host_scalars[1] is not an order violation but the blocks too large for run's lanes, << 40 | their rows; when it is
+    // not 0, [0] is not final and this completes the batch (synchronous: *total_out = rows kept)
+    int (*finish)(void* ws, const FilterBatch&, unsigned long long host_scalar1, slamem_mem* out_mems, uint64_t* out_boff,
+                  hipStream_t stream, uint64_t* total_out);
+};
+const FilterDesc* filter_for(int match_type);  // nullptr: -mem, -mam
+// where in a filter's workspace K9 places the -mem list: the same in every filter (FilterPrefix, filter_blocks.h)
+void filter_list_buffers(void* filter_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
+// The workspace of a search in `match_type`: the -mem workspace and the filter's behind it (params: -aln and -paf size theirs by
+// ops_capacity and max_edits; the others read nothing of it)
+uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type,
+                                const FilterParams& params);
+
+// params: null for -mem and -mam.  -aln, -paf: mems_dev may be null; aln_totals[0..2] (may be null) take -mem rows, segments, operations
 int find_mems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ = 0, uint32_t max_gap = 0,
-                     uint32_t* block_scores_dev = nullptr, uint32_t ext_penalty = 0, uint32_t ext_xdrop = 0xFFFFFFFFu,
-                     const AlnArgs* aln = nullptr, uint64_t* aln_totals = nullptr);
-uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity);
-// The workspace of a search in `match_type` (0 -mem, 1 -mam, 2 -mum, 3 -smem, 4 -chain, 5 -ext: the -mem workspace and the filter's behind it)
-uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type);
-// -mum (mum_filter.hip): the filter's part of the workspace; where in it K9 places the -mem list; the filter behind K9 (blocks of
-// up to 256 MEMs; host_scalars[0] = rows kept, [1] = large blocks << 40 | their rows, both copied asynchronously), and the
-// large blocks' path when host_scalars[1] was not 0 (synchronous: *total_out = rows kept)
-uint64_t mum_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
-void mum_list_buffers(void* mum_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
-int mum_filter_small(void* mum_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem* out_mems, uint64_t* out_boff,
+                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, const FilterParams* params, uint64_t* aln_totals);
+
+// The filters' entry points (FilterDesc::workspace_bytes / run / finish), and the parts that one filter takes from another.
+// -mum (mum_filter.hip): blocks of up to 256 MEMs in run; mum_filter_large: the others, by two sorts
+uint64_t mum_workspace_bytes(const FilterBatch& b, const FilterParams& p);
+int mum_filter_small(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
                      unsigned long long* host_scalars, hipStream_t stream);
-int mum_filter_large(void* mum_ws, uint64_t num_blocks, uint64_t capacity, unsigned long long large_ctr, slamem_mem* out_mems,
-                     uint64_t* out_boff, hipStream_t stream, uint64_t* total_out);
-// -smem (smem_filter.hip): the filter's part of the workspace; where in it K9 places the -mem list; the filter behind K9, all
-// blocks, asynchronous (max_occ: the occurrence cap, 0 none; host_scalars[0] = rows kept, [1] = the first block out of the
-// emission order + 1, 0 when there is none)
-uint64_t smem_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
-void smem_list_buffers(void* smem_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
-int smem_filter(void* smem_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_occ, slamem_mem* out_mems, uint64_t* out_boff,
+int mum_filter_large(void* ws, const FilterBatch& b, unsigned long long large_ctr, slamem_mem* out_mems, uint64_t* out_boff,
+                     hipStream_t stream, uint64_t* total_out);
+// -smem (smem_filter.hip)
+uint64_t smem_workspace_bytes(const FilterBatch& b, const FilterParams& p);
+int smem_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
                 unsigned long long* host_scalars, hipStream_t stream);
-// -chain (chain_filter.hip): the same three for the best collinear chain of every block (max_gap: the maximum gap, >= 1;
-// out_scores: a uint32 per block, or nullptr; host_scalars as for -smem)
-constexpr uint32_t kChainDefaultGap = 5000;
-uint64_t chain_workspace_bytes(uint64_t num_blocks, uint64_t capacity);
-void chain_list_buffers(void* chain_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
-int chain_filter(void* chain_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, slamem_mem* out_mems, uint64_t* out_boff,
-                 uint32_t* out_scores, unsigned long long* host_scalars, hipStream_t stream);
+// -chain (chain_filter.hip): the best collinear chain of every block
+uint64_t chain_workspace_bytes(const FilterBatch& b, const FilterParams& p);
+int chain_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
+                 unsigned long long* host_scalars, hipStream_t stream);
 // (chain_filter = chain_pass + chain_compact.  -paf runs them apart: between the two it scores the rows the chain left and
-// clears the kept count of the blocks it drops.  chain_buffers: the parts of the workspace it reads and writes for that --
-// cnt[num_blocks] is 0, score is the workspace's own column, lane_max the rows of a block a lane handles, wave_grid the grid of
-// the wave kernels that share `list`, ctr[0] its length)
+// clears the kept count of the blocks it drops.  out_scores: a uint32 per block, or nullptr.  chain_buffers: the parts of the
+// workspace it reads and writes for that -- cnt[num_blocks] is 0, score is the workspace's own column, lane_max the rows of a
+// block a lane handles, wave_grid the grid of the wave kernels that share `list`, ctr[0] its length)
 struct ChainBufs {
     unsigned long long* ctr;
     slamem_mem* rows;
@@ -355,50 +413,25 @@ ChainBufs chain_buffers(void* chain_ws, uint64_t num_blocks, uint64_t capacity);
 int chain_pass(void* chain_ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_gap, uint32_t* out_scores, hipStream_t stream);
 int chain_compact(void* chain_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem* out_mems, uint64_t* out_boff,
                   unsigned long long* host_scalars, hipStream_t stream);
-// -ext (ext_filter.hip): the same three for the ungapped X-drop extension of every row (penalty >= 1, xdrop >= 0; the batch's
-// letters and the text planes of the index are what it compares; out_mm: a uint32 per kept row, or nullptr; host_scalars as for
-// -smem).  In find_mems_device the per-row column travels in block_scores_dev.
-constexpr uint32_t kExtDefaultPenalty = 4, kExtDefaultXdrop = 20, kExtXdropUnset = 0xFFFFFFFFu;
-uint64_t ext_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity);
-void ext_list_buffers(void* ext_ws, uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity,
-                      slamem_mem** rows_out, uint64_t** boff_out);
-int ext_filter(void* ext_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
-               uint32_t strands, uint64_t query_bytes, uint64_t capacity, uint32_t penalty, uint32_t xdrop, slamem_mem* out_mems,
-               uint64_t* out_boff, uint32_t* out_mm, unsigned long long* host_scalars, hipStream_t stream);
-// -aln (aln_filter.hip): the chain's passes and -ext's planes, then the gaps between consecutive chain rows and the CIGARs.  The
-// workspace starts with -chain's (K9 places the -mem list there).  args: every value resolved (no placeholders); host_scalars:
-// [0] segments, [1] the first block out of order + 1, [2] operations.  In find_mems_device (match type 6) the arguments travel
-// in `aln`, mems_dev may be null, block_offsets_dev takes the segments' block offsets and aln_totals[0..2] the three totals.
-constexpr uint32_t kAlnDefaultEdits = 31, kAlnMaxEdits = 127, kAlnEditsUnset = 0xFFFFFFFFu;
-struct AlnArgs {
-    uint32_t max_gap, penalty, xdrop, max_edits;
-    slamem_aln* segs;
-    uint64_t segs_capacity;
-    uint32_t* ops;
-    uint64_t ops_capacity;
-    uint64_t* op_offsets;  // segs_capacity + 1
-    slamem_map* reads;     // -paf: a record per read (then block_offsets_dev takes num_queries + 1 read offsets); nullptr: -aln
-};
-uint64_t aln_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
-                             uint32_t max_edits);
-void aln_list_buffers(void* aln_ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out);
-int aln_filter(void* aln_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
-               uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff,
+// -ext (ext_filter.hip): the ungapped X-drop extension of every row
+uint64_t ext_workspace_bytes(const FilterBatch& b, const FilterParams& p);
+int ext_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
                unsigned long long* host_scalars, hipStream_t stream);
-// (aln_filter = chain_filter into aln_chain_buffers + aln_after_chain, which -paf runs behind its own choice of chains)
-void aln_chain_buffers(void* aln_ws, uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity,
-                       const AlnArgs& args, slamem_mem** crows_out, uint64_t** coff_out);
-int aln_after_chain(void* aln_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
-                    uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_boff,
-                    unsigned long long* host_scalars, hipStream_t stream);
-// -paf (map_filter.hip, match type 7): one mapping per read.  The chain pass, a second chain pass over the rows it left (scores
-// only), a lane per read that picks the primary strand block, computes the quality and empties the other block, then -aln's
-// kernels over the primaries and the fold of block offsets to read offsets.  The workspace starts with -aln's.  args.reads is
-// not null; out_roff: num_queries + 1; host_scalars as for -aln.
-uint64_t map_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
-                             uint32_t max_edits);
-int map_filter(void* map_ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries,
-               uint32_t strands, uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_roff,
+// -aln (aln_filter.hip): the chain's passes and -ext's planes, then the gaps between consecutive chain rows and the CIGARs.  The
+// workspace starts with -chain's.  out_mems is not used.
+uint64_t aln_workspace_bytes(const FilterBatch& b, const FilterParams& p);
+int aln_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
+               unsigned long long* host_scalars, hipStream_t stream);
+// (aln_filter = chain_pass + chain_compact into aln_chain_buffers + aln_after_chain, which -paf runs behind its own choice of chains)
+void aln_chain_buffers(void* aln_ws, const FilterBatch& b, const FilterParams& p, slamem_mem** crows_out, uint64_t** coff_out);
+int aln_after_chain(void* aln_ws, const FilterBatch& b, const FilterParams& p, uint64_t* out_boff, unsigned long long* host_scalars,
+                    hipStream_t stream);
+// -paf (map_filter.hip): one mapping per read.  The chain pass, a second chain pass over the rows it left (scores only), a lane
+// per read that picks the primary strand block, computes the quality and empties the other block, then -aln's kernels over the
+// primaries and the fold of block offsets to read offsets.  The workspace starts with -aln's.  p.reads is not null; out_boff:
+// num_queries + 1 read offsets.
+uint64_t map_workspace_bytes(const FilterBatch& b, const FilterParams& p);
+int map_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
                unsigned long long* host_scalars, hipStream_t stream);
 // -pile (pile_filter.hip, match type 8 of a stream): the per-base pileup of -paf's mappings.  pileup_add enqueues the two add
 // kernels over the outputs of a -paf batch as they lie on the device (nothing is checked on the host, nothing comes back);
@@ -417,22 +450,13 @@ void search_job_delete(SearchJob* j);
 int search_job_init(SearchJob* j, const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
                     uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type, slamem_mem* mems_dev,
                     uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev, uint64_t workspace_bytes,
-                    unsigned long long* host_scalars);
+                    unsigned long long* host_scalars, const FilterParams* params);
 // (between init and tables) the number of slices of the batch when the caller knows it -- no record longer than a slice: one
 // per record -- which saves tables() its host round trip
 void search_job_slices_hint(SearchJob* j, uint32_t slices);
 // (between init and the search) at most this many waves for the batch's K8 (0: the whole chip)
 void search_job_k8_wave_cap(SearchJob* j, uint32_t waves);
-// (between init and the search) -smem: the occurrence cap of the batch (0: none)
-void search_job_max_occ(SearchJob* j, uint32_t max_occ);
-// (between init and the search) -chain: the maximum gap of the batch (0: kChainDefaultGap)
-void search_job_max_gap(SearchJob* j, uint32_t max_gap);
-// (between init and the search) -ext: the mismatch penalty (0: kExtDefaultPenalty), the drop (kExtXdropUnset: kExtDefaultXdrop)
-// and where the mismatches of the kept rows go (a uint32 per row of capacity, or nullptr)
-void search_job_ext(SearchJob* j, uint32_t penalty, uint32_t xdrop, uint32_t* mismatches_dev);
-// -aln: the arguments of the batch, every value resolved.  BEFORE search_job_init, unlike the others: init sizes the workspace
-// by the operation capacity and the edit limit.  After collect: [0] -mem rows, [1] segments, [2] operations (what a retry needs).
-void search_job_aln(SearchJob* j, const AlnArgs& args);
+// -aln, -paf, after collect: [0] -mem rows, [1] segments, [2] operations (what a retry needs)
 void search_job_aln_totals(const SearchJob* j, uint64_t totals[3]);
 constexpr uint32_t kSearchSliceLen = 4096;
 int search_job_tables(SearchJob* j, hipStream_t stream);

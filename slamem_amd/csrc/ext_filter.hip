@@ -20,7 +20,7 @@
 //   k_ext_dedup / _wave     a row is dropped when a row before it in the block extends to the same segment: those lie in the
 //                           contiguous run of rows before it whose (seed) query start is inside the segment
 //   scan                    kept rows per block -> new block offsets
-//   k_ext_copy / _list_copy the kept rows and their mismatches, in order
+//   k_filter_copy / k_ext_list_copy   the kept rows and their mismatches, in order
 // Every row is checked against the one before it: a block out of the emission order fails the call -- never wrong rows.
 #include "filter_shared.h"
 
@@ -31,31 +31,21 @@ namespace {
 constexpr uint32_t kExtLaneMax = 32;        // rows of a block one lane de-duplicates
 constexpr unsigned kExtWaveGrid = 2048;     // one-wave workgroups that share the list of larger blocks
 
-struct ExtLayout {
-    uint64_t off_ctr, off_rows, off_boff, off_cnt, off_newoff, off_keep, off_owner, off_xrows, off_xmm, off_scan, scan_bytes, off_list,
-        off_ucnt, off_uoff, off_uscan, uscan_bytes, off_long, off_units, bytes;
+struct ExtLayout : FilterPrefix {
+    uint64_t off_owner, off_xrows, off_xmm, off_list, off_ucnt, off_uoff, off_uscan, uscan_bytes, off_long, off_units, bytes;
 };
 
 ExtLayout ext_layout(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity) {
     ExtLayout m;
-    uint64_t off = 0;
-    m.off_ctr = off;    off = align_up(off + 64, 256);                                  // [0] listed blocks, [1] order violation, [2] listed records
-    m.off_rows = off;   off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);  // the -mem list (K9 places it here)
-    m.off_boff = off;   off = align_up(off + (num_blocks + 1) * 8, 256);                // ... and its block offsets
-    m.off_cnt = off;    off = align_up(off + (num_blocks + 1) * 4, 256);                // kept rows per block
-    m.off_newoff = off; off = align_up(off + (num_blocks + 1) * 8, 256);                // their exclusive sums
-    m.off_keep = off;   off = align_up(off + capacity + 16, 256);                       // a byte per -mem row
+    uint64_t off = m.begin(num_blocks, capacity);                                       // ctr: [0] listed blocks, [1] order violation, [2] listed records
     m.off_owner = off;  off = align_up(off + capacity * 4 + 16, 256);                   // the strand block of every -mem row
     m.off_xrows = off;  off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);  // the extended rows
     m.off_xmm = off;    off = align_up(off + capacity * 4 + 16, 256);                   // ... and their mismatches
-    size_t need = 0;
-    (void)scan_sum_exclusive_u32_u64(nullptr, need, nullptr, nullptr, num_blocks, 0);
-    m.scan_bytes = need;
-    m.off_scan = off;   off = align_up(off + need, 256);
+    off = m.scan_at(off, num_blocks);
     m.off_list = off;   off = align_up(off + (capacity / (kExtLaneMax + 1) + 1) * 8, 256);  // listed strand blocks
     m.off_ucnt = off;   off = align_up(off + (num_queries + 1) * 4, 256);               // units per record
     m.off_uoff = off;   off = align_up(off + (num_queries + 1) * 8, 256);               // their exclusive sums
-    need = 0;
+    size_t need = 0;
     (void)scan_sum_exclusive_u32_u64(nullptr, need, nullptr, nullptr, num_queries, 0);
     m.uscan_bytes = need;
     m.off_uscan = off;  off = align_up(off + need, 256);
@@ -210,30 +200,6 @@ __global__ void __launch_bounds__(64) k_ext_dedup_wave(const uint64_t* __restric
     }
 }
 
-// one lane per strand block: new offsets, and the kept rows of blocks of up to kExtLaneMax rows
-__global__ void __launch_bounds__(256) k_ext_copy(const uint64_t* __restrict__ boff, uint64_t nb, uint64_t cap,
-                                                  const slamem_mem* __restrict__ xrows, const uint32_t* __restrict__ xmm,
-                                                  const uint8_t* __restrict__ keep, const uint64_t* __restrict__ newoff,
-                                                  slamem_mem* __restrict__ out, uint32_t* __restrict__ out_mm, uint64_t* __restrict__ out_boff) {
-    const uint64_t b = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (b > nb) return;
-    uint64_t d = newoff[b];
-    out_boff[b] = d;
-    if (b == nb) return;
-    uint64_t s, e;
-    clamp_block(boff, b, cap, s, e);
-    if (e - s > kExtLaneMax) return;
-    const uint64_t d_end = newoff[b + 1];
-    for (uint64_t i = s; i < e && d < d_end; i++) {
-        if (!keep[i]) continue;
-        if (d < cap) {
-            out[d] = xrows[i];
-            if (out_mm) out_mm[d] = xmm[i];
-        }
-        d++;
-    }
-}
-
 // a listed block's kept rows, in order: a wave ranks 64 rows at a time
 __global__ void __launch_bounds__(64) k_ext_list_copy(const uint64_t* __restrict__ list, const unsigned long long* __restrict__ ctr,
                                                       const uint64_t* __restrict__ boff, uint64_t cap, const slamem_mem* __restrict__ xrows,
@@ -266,32 +232,20 @@ __global__ void __launch_bounds__(64) k_ext_list_copy(const uint64_t* __restrict
 
 }  // namespace
 
-uint64_t ext_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity) {
-    return ext_layout(num_queries, num_blocks, query_bytes, capacity).bytes;
+uint64_t ext_workspace_bytes(const FilterBatch& b, const FilterParams&) {
+    return ext_layout(b.num_queries, b.num_blocks(), b.query_bytes, b.capacity).bytes;
 }
 
 #define XSTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
 
-void ext_list_buffers(void* ws, uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, slamem_mem** rows_out,
-                      uint64_t** boff_out) {
-    const ExtLayout m = ext_layout(num_queries, num_blocks, query_bytes, capacity);
+int ext_filter(void* ws, const FilterBatch& b, const FilterParams& prm, slamem_mem* out_mems, uint64_t* out_boff,
+               unsigned long long* host_scalars, hipStream_t stream) {
+    const uint64_t num_queries = b.num_queries, num_blocks = b.num_blocks(), capacity = b.capacity;
+    const ExtLayout m = ext_layout(num_queries, num_blocks, b.query_bytes, capacity);
+    const FilterBufs w = filter_bufs(ws, m);
     char* p = static_cast<char*>(ws);
-    *rows_out = reinterpret_cast<slamem_mem*>(p + m.off_rows);
-    *boff_out = reinterpret_cast<uint64_t*>(p + m.off_boff);
-}
-
-int ext_filter(void* ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries, uint32_t strands,
-               uint64_t query_bytes, uint64_t capacity, uint32_t penalty, uint32_t xdrop, slamem_mem* out_mems, uint64_t* out_boff,
-               uint32_t* out_mm, unsigned long long* host_scalars, hipStream_t stream) {
-    const uint64_t num_blocks = num_queries * strands;
-    const ExtLayout m = ext_layout(num_queries, num_blocks, query_bytes, capacity);
-    char* p = static_cast<char*>(ws);
-    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
-    const slamem_mem* rows = reinterpret_cast<const slamem_mem*>(p + m.off_rows);
-    const uint64_t* boff = reinterpret_cast<const uint64_t*>(p + m.off_boff);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
-    uint64_t* newoff = reinterpret_cast<uint64_t*>(p + m.off_newoff);
-    uint8_t* keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
+    const slamem_mem* rows = w.rows;
+    const uint64_t* boff = w.boff;
     uint32_t* owner = reinterpret_cast<uint32_t*>(p + m.off_owner);
     slamem_mem* xrows = reinterpret_cast<slamem_mem*>(p + m.off_xrows);
     uint32_t* xmm = reinterpret_cast<uint32_t*>(p + m.off_xmm);
@@ -300,41 +254,35 @@ int ext_filter(void* ws, const IndexView& ix, const void* queries_dev, const uin
     uint64_t* uoff = reinterpret_cast<uint64_t*>(p + m.off_uoff);
     uint64_t* longs = reinterpret_cast<uint64_t*>(p + m.off_long);
     QueryUnit* units = reinterpret_cast<QueryUnit*>(p + m.off_units);
-    const char* queries = static_cast<const char*>(queries_dev);
-    XSTEP(hipMemsetAsync(ctr, 0, 24, stream), "memset");
+    uint32_t* out_mm = prm.column_dev;
+    XSTEP(hipMemsetAsync(w.ctr, 0, 24, stream), "memset");
     // the batch as planes
-    XSTEP(pack_batch_planes(queries, offsets_dev, num_queries, ucnt, uoff, p + m.off_uscan, m.uscan_bytes, longs, units, ctr, stream),
+    XSTEP(pack_batch_planes(static_cast<const char*>(b.queries_dev), b.offsets_dev, num_queries, ucnt, uoff, p + m.off_uscan, m.uscan_bytes,
+                            longs, units, w.ctr, stream),
           "pack_batch_planes");
     // the rows
-    hipLaunchKernelGGL(k_ext_mark, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity, owner, cnt, list,
-                       ctr);
+    hipLaunchKernelGGL(k_ext_mark, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity, owner, w.cnt, list,
+                       w.ctr);
     XSTEP(hipGetLastError(), "k_ext_mark");
-    hipLaunchKernelGGL(k_ext_mark_wave, dim3(kExtWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)ctr, boff,
-                       rows, capacity, owner, ctr);
+    hipLaunchKernelGGL(k_ext_mark_wave, dim3(kExtWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)w.ctr, boff,
+                       rows, capacity, owner, w.ctr);
     XSTEP(hipGetLastError(), "k_ext_mark_wave");
     hipLaunchKernelGGL(k_ext_extend, dim3(grid_for(capacity)), dim3(256), 0, stream, boff, num_blocks, rows, capacity,
-                       (const uint32_t*)owner, offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n, strands, penalty,
-                       xdrop, xrows, xmm);
+                       (const uint32_t*)owner, b.offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, b.ix->tpl, b.ix->n, b.strands,
+                       prm.penalty, prm.xdrop, xrows, xmm);
     XSTEP(hipGetLastError(), "k_ext_extend");
     hipLaunchKernelGGL(k_ext_dedup, dim3(grid_for(num_blocks)), dim3(256), 0, stream, boff, num_blocks, rows, capacity,
-                       (const slamem_mem*)xrows, keep, cnt);
+                       (const slamem_mem*)xrows, w.keep, w.cnt);
     XSTEP(hipGetLastError(), "k_ext_dedup");
-    hipLaunchKernelGGL(k_ext_dedup_wave, dim3(kExtWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)ctr,
-                       boff, rows, capacity, (const slamem_mem*)xrows, keep, cnt);
+    hipLaunchKernelGGL(k_ext_dedup_wave, dim3(kExtWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)w.ctr,
+                       boff, rows, capacity, (const slamem_mem*)xrows, w.keep, w.cnt);
     XSTEP(hipGetLastError(), "k_ext_dedup_wave");
-    size_t need = m.scan_bytes;
-    XSTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, cnt, newoff, num_blocks, stream), "scan");
-    hipLaunchKernelGGL(k_ext_copy, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, capacity,
-                       (const slamem_mem*)xrows, (const uint32_t*)xmm, (const uint8_t*)keep, (const uint64_t*)newoff, out_mems, out_mm,
-                       out_boff);
-    XSTEP(hipGetLastError(), "k_ext_copy");
-    hipLaunchKernelGGL(k_ext_list_copy, dim3(kExtWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)ctr,
-                       boff, capacity, (const slamem_mem*)xrows, (const uint32_t*)xmm, (const uint8_t*)keep, (const uint64_t*)newoff,
+    XSTEP((compact_kept<kExtLaneMax, true>(w, num_blocks, capacity, xrows, out_mems, out_boff, stream, xmm, out_mm)), "compact_kept");
+    hipLaunchKernelGGL(k_ext_list_copy, dim3(kExtWaveGrid), dim3(64), 0, stream, (const uint64_t*)list, (const unsigned long long*)w.ctr,
+                       boff, capacity, (const slamem_mem*)xrows, (const uint32_t*)xmm, (const uint8_t*)w.keep, (const uint64_t*)w.newoff,
                        out_mems, out_mm);
     XSTEP(hipGetLastError(), "k_ext_list_copy");
-    // [0] rows kept, [1] the first block out of order + 1 (0: none)
-    XSTEP(hipMemcpyAsync(host_scalars, newoff + num_blocks, 8, hipMemcpyDeviceToHost, stream), "memcpy");
-    XSTEP(hipMemcpyAsync(host_scalars + 1, ctr + 1, 8, hipMemcpyDeviceToHost, stream), "memcpy");
+    XSTEP(kept_scalars(w, num_blocks, w.ctr + 1, host_scalars, stream), "memcpy");
     return SLAMEM_OK;
 }
 #undef XSTEP

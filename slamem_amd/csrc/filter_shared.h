@@ -1,17 +1,13 @@
 // filter_shared.h -- what the filters behind K9 that read letters share (ext_filter.hip, aln_filter.hip): the batch as
-// bit-planes (k_ext_units / k_ext_pack / k_ext_pack_long), the 64-letter windows of a strand and of the text, the X-drop walk
-// over a mismatch mask, and the block helpers.  Everything sits in an unnamed namespace: each file that includes this gets
-// its own kernels.
+// bit-planes (k_ext_units / k_ext_pack / k_ext_pack_long), the 64-letter windows of a strand and of the text and the X-drop
+// walk over a mismatch mask, on top of filter_blocks.h.  Everything sits in an unnamed namespace: each file that includes this
+// gets its own kernels.
 #pragma once
-#include "common.h"
-#include "prims.h"
+#include "filter_blocks.h"
 
 namespace slamem {
 
 namespace {
-
-inline unsigned grid_for(uint64_t items, unsigned block = 256) { return items ? (unsigned)((items + block - 1) / block) : 1u; }
-inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 constexpr uint32_t kExtPackLaneUnits = 16;  // units (of 64 letters) of a record one lane packs
 constexpr unsigned kExtPackGrid = 1024;     // workgroups that share the list of longer records
@@ -19,20 +15,6 @@ constexpr unsigned kExtPackGrid = 1024;     // workgroups that share the list of
 // a unit of a packed record: the layout of TextPlanes without the occurs-once plane
 struct __attribute__((aligned(32))) QueryUnit { uint64_t p0, p1, nm, pad; };
 static_assert(sizeof(QueryUnit) == 32 && sizeof(TextPlanes) == 32, "units are two 16-byte loads");
-
-__device__ __forceinline__ void clamp_block(const uint64_t* __restrict__ boff, uint64_t b, uint64_t cap, uint64_t& s, uint64_t& e) {
-    // (a batch whose -mem list did not fit has offsets beyond the capacity: its result is refused, nothing is read past it)
-    s = boff[b];
-    e = boff[b + 1];
-    if (s > cap) s = cap;
-    if (e > cap) e = cap;
-    if (e < s) e = s;
-}
-
-// the order every block must be in: q descending, then L non-increasing
-__device__ __forceinline__ bool out_of_order(const slamem_mem& prev, const slamem_mem& r) {
-    return r.query_pos > prev.query_pos || (r.query_pos == prev.query_pos && r.length > prev.length);
-}
 
 // ---- the batch as planes -------------------------------------------------------------------------------------------------
 

@@ -1,0 +1,66 @@
+// filters.hip -- the filters behind K9 as the search sees them: one row per match type 2..7, the one place that
+// turns the placeholders of the public interface into values, and where K9 places the -mem list in a filter's workspace.
+#include "filter_blocks.h"
+
+namespace slamem {
+
+namespace {
+
+constexpr uint64_t kRows32 = 0xFFFFFFFFull, kRowsTiled = 0xFFFF0000ull;  // row places are 32-bit; ... and counted in tiles
+const char kAlnLimits[] = "slamem_find_alns_device: at most 2^32 - 2^16 MEMs and operations of capacity and 2^32 - 2 strand blocks per call";
+
+// name, flag, noun, limits, capacity_end, bounds_blocks, needs_planes, column_per_row, segments, needs_reads, scalars,
+// workspace_bytes, run, finish
+// (-paf shares -aln's bounds and their message; -mum alone finishes on the host's word)
+const FilterDesc kFilters[6] = {
+    {"slamem_find_mums_device", "-mum", nullptr, "slamem_find_mums_device: at most 2^32 - 2 MEMs of capacity per call", kRows32, false, false,
+     false, false, false, 2, mum_workspace_bytes, mum_filter_small, mum_filter_large},
+    {"slamem_find_smems_device", "-smem", "SMEMs", "slamem_find_smems_device: at most 2^32 - 2^16 MEMs of capacity per call", kRowsTiled, false,
+     false, false, false, false, 2, smem_workspace_bytes, smem_filter, nullptr},
+    {"slamem_find_chains_device", "-chain", "chains", "slamem_find_chains_device: at most 2^32 - 2^16 MEMs of capacity per call", kRowsTiled,
+     false, false, false, false, false, 2, chain_workspace_bytes, chain_filter, nullptr},
+    {"slamem_find_exts_device", "-ext", "extended MEMs",
+     "slamem_find_exts_device: at most 2^32 - 2^16 MEMs of capacity and 2^32 - 2 strand blocks per call", kRowsTiled, true, true, true, false,
+     false, 2, ext_workspace_bytes, ext_filter, nullptr},
+    {"slamem_find_alns_device", "-aln", "alignments", kAlnLimits, kRowsTiled, true, true, false, true, false, 3,
+     aln_workspace_bytes, aln_filter, nullptr},
+    {"slamem_find_maps_device", "-paf", "alignments", kAlnLimits, kRowsTiled, true, true, false, true, true, 3,
+     map_workspace_bytes, map_filter, nullptr},
+};
+
+}  // namespace
+
+const FilterDesc* filter_for(int match_type) { return match_type >= 2 && match_type <= 7 ? &kFilters[match_type - 2] : nullptr; }
+
+int resolve_filter_params(const char* who, uint32_t max_occ, uint32_t max_gap, uint32_t penalty, uint32_t xdrop, uint32_t max_edits,
+                          FilterParams* out) {
+    if (max_gap >= 0x80000000u) {
+        set_error("%s: the maximum gap must be below 2^31 (0: the default, %u)", who, kChainDefaultGap);
+        return SLAMEM_ERR_ARG;
+    }
+    if (max_edits == kAlnEditsUnset) max_edits = kAlnDefaultEdits;
+    if (max_edits > kAlnMaxEdits) {
+        set_error("%s: at most %u edits a gap (SLAMEM_ALN_EDITS_DEFAULT: the default, %u)", who, kAlnMaxEdits, kAlnDefaultEdits);
+        return SLAMEM_ERR_ARG;
+    }
+    *out = FilterParams{max_occ, max_gap ? max_gap : kChainDefaultGap, penalty ? penalty : kExtDefaultPenalty,
+                        xdrop == kExtXdropUnset ? kExtDefaultXdrop : xdrop, max_edits, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr};
+    return SLAMEM_OK;
+}
+
+void filter_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out) {
+    FilterPrefix m;
+    (void)m.begin(num_blocks, capacity);
+    *rows_out = reinterpret_cast<slamem_mem*>(static_cast<char*>(ws) + m.off_rows);
+    *boff_out = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + m.off_boff);
+}
+
+uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type,
+                                const FilterParams& params) {
+    const uint64_t mem = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity);
+    const FilterDesc* f = filter_for(match_type);
+    const FilterBatch b = {nullptr, nullptr, nullptr, num_queries, both_strands ? 2u : 1u, query_bytes, mems_capacity};
+    return f ? mem + f->workspace_bytes(b, params) : mem;
+}
+
+}  // namespace slamem

@@ -17,7 +17,7 @@
 //   chain_compact           the primaries' chain rows, compacted per block
 //   aln_after_chain         -aln's kernels (aln_filter.hip, unchanged) over them: an empty block costs them nothing
 //   k_map_fold              block offsets -> read offsets
-#include "filter_shared.h"
+#include "filter_blocks.h"
 
 namespace slamem {
 
@@ -27,24 +27,14 @@ struct MapLayout {
     uint64_t aln_bytes, off_chain2, off_boff, bytes;
 };
 
-MapLayout map_layout(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
-                     uint32_t max_edits) {
+MapLayout map_layout(const FilterBatch& b, const FilterParams& p) {
     MapLayout m;
-    m.aln_bytes = align_up(aln_workspace_bytes(num_queries, num_blocks, query_bytes, capacity, ops_capacity, max_edits), 256);
+    m.aln_bytes = align_up(aln_workspace_bytes(b, p), 256);
     uint64_t off = m.aln_bytes;
-    m.off_chain2 = off; off = align_up(off + chain_workspace_bytes(num_blocks, capacity), 256);  // the second chain pass
-    m.off_boff = off;   off = align_up(off + (num_blocks + 1) * 8, 256);                         // the segments' block offsets
+    m.off_chain2 = off; off = align_up(off + chain_workspace_bytes(b, p), 256);          // the second chain pass
+    m.off_boff = off;   off = align_up(off + (b.num_blocks() + 1) * 8, 256);             // the segments' block offsets
     m.bytes = off;
     return m;
-}
-
-__device__ __forceinline__ void map_clamp_block(const uint64_t* __restrict__ boff, uint64_t b, uint64_t cap, uint64_t& s, uint64_t& e) {
-    // (as chain_filter.hip's: a list that did not fit has offsets beyond the capacity, and nothing is read past it)
-    s = boff[b];
-    e = boff[b + 1];
-    if (s > cap) s = cap;
-    if (e > cap) e = cap;
-    if (e < s) e = s;
 }
 
 // one lane per strand block: the rows its chain left (and lane num_blocks keeps the scan's last input at 0)
@@ -54,7 +44,7 @@ __global__ void __launch_bounds__(256) k_map_rest_count(const uint64_t* __restri
     if (b > nb) return;
     if (b == nb) { rest[nb] = 0u; return; }
     uint64_t s, e;
-    map_clamp_block(boff, b, cap, s, e);
+    clamp_block(boff, b, cap, s, e);
     const uint32_t n = (uint32_t)(e - s), k = cnt[b];
     rest[b] = k < n ? n - k : 0u;
 }
@@ -66,7 +56,7 @@ __global__ void __launch_bounds__(256) k_map_rest_copy(const uint64_t* __restric
     const uint64_t b = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (b >= nb) return;
     uint64_t s, e;
-    map_clamp_block(boff, b, cap, s, e);
+    clamp_block(boff, b, cap, s, e);
     if (e - s > lane_max) return;
     uint64_t d = roff[b];
     const uint64_t d_end = roff[b + 1];
@@ -87,7 +77,7 @@ __global__ void __launch_bounds__(64) k_map_rest_list_copy(const uint64_t* __res
     for (uint64_t li = blockIdx.x; li < nl; li += gridDim.x) {
         const uint64_t b = list[li];
         uint64_t s, e;
-        map_clamp_block(boff, b, cap, s, e);
+        clamp_block(boff, b, cap, s, e);
         const uint32_t n = (uint32_t)(e - s);
         uint64_t d = roff[b];
         const uint64_t d_end = roff[b + 1];
@@ -136,25 +126,22 @@ __global__ void __launch_bounds__(256) k_map_fold(uint64_t nq, uint32_t strands,
 
 }  // namespace
 
-uint64_t map_workspace_bytes(uint64_t num_queries, uint64_t num_blocks, uint64_t query_bytes, uint64_t capacity, uint64_t ops_capacity,
-                             uint32_t max_edits) {
-    return map_layout(num_queries, num_blocks, query_bytes, capacity, ops_capacity, max_edits).bytes;
-}
+uint64_t map_workspace_bytes(const FilterBatch& b, const FilterParams& p) { return map_layout(b, p).bytes; }
 
 #define MSTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
 
-int map_filter(void* ws, const IndexView& ix, const void* queries_dev, const uint64_t* offsets_dev, uint64_t num_queries, uint32_t strands,
-               uint64_t query_bytes, uint64_t capacity, const AlnArgs& args, uint64_t* out_roff, unsigned long long* host_scalars,
+int map_filter(void* ws, const FilterBatch& bt, const FilterParams& args, slamem_mem*, uint64_t* out_roff, unsigned long long* host_scalars,
                hipStream_t stream) {
-    const uint64_t num_blocks = num_queries * strands;
-    const MapLayout m = map_layout(num_queries, num_blocks, query_bytes, capacity, args.ops_capacity, args.max_edits);
+    const uint64_t num_queries = bt.num_queries, num_blocks = bt.num_blocks(), capacity = bt.capacity;
+    const uint32_t strands = bt.strands;
+    const MapLayout m = map_layout(bt, args);
     char* p = static_cast<char*>(ws);
     void* ws2 = p + m.off_chain2;
     uint64_t* seg_boff = reinterpret_cast<uint64_t*>(p + m.off_boff);
     const ChainBufs a = chain_buffers(ws, num_blocks, capacity), b = chain_buffers(ws2, num_blocks, capacity);
     slamem_mem* crows;
     uint64_t* coff;
-    aln_chain_buffers(ws, num_queries, num_blocks, query_bytes, capacity, args, &crows, &coff);
+    aln_chain_buffers(ws, bt, args, &crows, &coff);
     int rc = chain_pass(ws, num_blocks, capacity, args.max_gap, nullptr, stream);
     if (rc != SLAMEM_OK) return rc;
     // the rows the chains left, as a list of their own (b.cnt holds their counts until the second pass writes it)
@@ -178,8 +165,7 @@ int map_filter(void* ws, const IndexView& ix, const void* queries_dev, const uin
     // [0] rows kept (replaced below), [1] the first block out of order + 1
     rc = chain_compact(ws, num_blocks, capacity, crows, coff, host_scalars, stream);
     if (rc != SLAMEM_OK) return rc;
-    rc = aln_after_chain(ws, ix, queries_dev, offsets_dev, num_queries, strands, query_bytes, capacity, args, seg_boff, host_scalars,
-                         stream);
+    rc = aln_after_chain(ws, bt, args, seg_boff, host_scalars, stream);
     if (rc != SLAMEM_OK) return rc;
     hipLaunchKernelGGL(k_map_fold, dim3(grid_for(num_queries + 1)), dim3(256), 0, stream, num_queries, strands,
                        (const uint64_t*)seg_boff, out_roff);

@@ -3507,18 +3507,6 @@ uint64_t find_mems_workspace_bytes(uint64_t num_queries, int both_strands, uint6
     return layout_workspace(num_queries, both_strands ? 2 : 1, query_bytes, mems_capacity).bytes;
 }
 
-// -mum / -smem / -chain / -ext: the -mem workspace, then the filter's (mum_filter.hip / smem_filter.hip / chain_filter.hip /
-// ext_filter.hip: the -mem list K9 places, and what the filter needs beside it)
-uint64_t search_workspace_bytes(uint64_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity, int match_type) {
-    const uint64_t mem = find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity);
-    const uint64_t nb = num_queries * (both_strands ? 2u : 1u);
-    if (match_type == 2) return mem + mum_workspace_bytes(nb, mems_capacity);
-    if (match_type == 3) return mem + smem_workspace_bytes(nb, mems_capacity);
-    if (match_type == 4) return mem + chain_workspace_bytes(nb, mems_capacity);
-    if (match_type == 5) return mem + ext_workspace_bytes(num_queries, nb, query_bytes, mems_capacity);
-    return mem;
-}
-
 // SLAMEM_MAM_WHOLE=1: -mam with one lane per whole strand (k_find_mams), no slices
 static bool mam_whole_strands() {
     static const bool on = [] { const char* v = getenv("SLAMEM_MAM_WHOLE"); return v && atoi(v) != 0; }();
@@ -3547,41 +3535,27 @@ struct SearchJob {
     bool seeded = false;  // this batch's MEMs come from K8s (k_seed_mems); K8 scans only the strands it left
     uint32_t seed_words = 0, seed_words_avg = 0;  // plane words a strand of this batch's K8s launch, and what the average read length alone asks for
     bool mam_v3 = false;  // -mam on a batch without long records: K8's kMam instantiation (set by tables())
-    // -mum: the search runs as -mem into the workspace (mems_dev / block_offsets_dev point there) and the filter writes the kept
-    // rows to the caller's buffers; mum_large: the batch has a block too large for the filter's lanes (finish() runs the sorts)
-    bool mum = false;
+    // match types 2..7: the search runs as -mem into the filter's workspace (mems_dev / block_offsets_dev point there) and the
+    // filter behind K9 writes what it keeps to the caller's buffers (out_mems: null for -aln and -paf, whose segments go where
+    // params says).  h_scal [9..11] are the filter's scalars.  mum_large: -mum's scalar [1] (finish() runs the large blocks)
+    const FilterDesc* filter = nullptr;
+    FilterParams params = {};
+    FilterBatch batch = {};
     slamem_mem* out_mems = nullptr;
     uint64_t* out_boff = nullptr;
-    void* mum_ws = nullptr;
+    void* filter_ws = nullptr;
     unsigned long long mum_large = 0;
-    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter behind K9 (-mum, -smem, -chain and -ext)
-    // -smem: as -mum, with smem_filter.hip behind K9 (every block on the device: nothing for finish()); max_occ: the cap (0: none)
-    bool smem = false;
-    uint32_t max_occ = 0;
-    // -chain: as -smem, with chain_filter.hip behind K9; max_gap: the maximum gap (0: the default); scores_dev: a uint32 per block, or null
-    bool chain = false;
-    uint32_t max_gap = 0;
-    uint32_t* scores_dev = nullptr;
-    // -ext: as -smem, with ext_filter.hip behind K9; penalty: the mismatch penalty (0: the default), xdrop: the drop (0xFFFFFFFF: the
-    // default); mism_dev: a uint32 per kept row, or null
-    bool ext = false;
-    uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;
-    uint32_t* mism_dev = nullptr;
-    // -aln: as -ext, with aln_filter.hip behind K9; alnargs: where the segments and operations go, every value resolved (set
-    // before init, which sizes the workspace by it); h_scal [9] segments, [10] a block out of order + 1, [11] operations
-    // -paf (match type 7): -aln with map_filter.hip in aln_filter's place; alnargs.reads takes the read records, and the
-    // caller's offsets are per read
-    bool aln = false, map = false;
-    AlnArgs alnargs = {0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr, nullptr};
+    hipEvent_t ev_mum[2] = {nullptr, nullptr};  // around the filter
     uint64_t aln_totals[3] = {0, 0, 0};
     unsigned long long scal_own[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t k8_wave_cap = 0;  // waves of this batch's K8 (0: as many as the chip holds); a pipeline that keeps two K8 launches in flight gives each a part of the chip
     uint32_t slices_hint = 0xFFFFFFFFu;  // a caller that has the offsets on the host and knows the slice count (no record longer than a slice: one per record) saves tables() its round trip
-    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, -mum: [9] rows kept, [10] large blocks, -smem, -chain and -ext: [9] rows kept, [10] a block out of order + 1; pinned memory if the caller has some
+    unsigned long long* h_scal = scal_own;  // where search() has the scalars copied: [0..7] the scalar block, [8] all MEMs, [9..11] the filter's (FilterDesc::scalars); pinned memory if the caller has some
     ~SearchJob();
     int init(const slamem_index* idx_, const void* queries_dev_, const uint64_t* offsets_dev_, uint32_t num_queries_,
              uint64_t query_bytes_, uint32_t min_len_, int both_strands_, int match_type_, slamem_mem* mems_dev_,
-             uint64_t mems_capacity_, uint64_t* block_offsets_dev_, void* workspace_dev_, uint64_t workspace_bytes_);
+             uint64_t mems_capacity_, uint64_t* block_offsets_dev_, void* workspace_dev_, uint64_t workspace_bytes_,
+             const FilterParams* params_);
     int tables(hipStream_t stream);
     int prep(hipStream_t stream);
     int search(hipStream_t stream) { int rc = search_k8(stream, nullptr, false); return rc != SLAMEM_OK ? rc : place(stream); }
@@ -3610,13 +3584,17 @@ struct SearchJob {
 // find_mems_device() runs them in a row on one stream.
 int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const uint64_t* offsets_dev_, uint32_t num_queries_,
                     uint64_t query_bytes_, uint32_t min_len_, int both_strands_, int match_type_, slamem_mem* mems_dev_,
-                    uint64_t mems_capacity_, uint64_t* block_offsets_dev_, void* workspace_dev_, uint64_t workspace_bytes_) {
+                    uint64_t mems_capacity_, uint64_t* block_offsets_dev_, void* workspace_dev_, uint64_t workspace_bytes_,
+                    const FilterParams* params_) {
     idx = idx_; queries_dev = queries_dev_; offsets_dev = offsets_dev_; num_queries = num_queries_; query_bytes = query_bytes_;
     min_len = min_len_; both_strands = both_strands_; match_type = match_type_; mems_dev = mems_dev_; mems_capacity = mems_capacity_;
     block_offsets_dev = block_offsets_dev_; workspace_dev = workspace_dev_; workspace_bytes = workspace_bytes_;
     total = 0; nitems = 0; prefiltered = false; timed_k8 = false; launched = false;
-    mum = false; mum_large = 0; out_mems = nullptr; out_boff = nullptr; mum_ws = nullptr; smem = false; chain = false; ext = false; aln = false; map = false;
-    if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity && match_type_ != 6 && match_type_ != 7) || (!queries_dev && num_queries)) {
+    mum_large = 0; out_mems = nullptr; out_boff = nullptr; filter_ws = nullptr;
+    filter = filter_for(match_type_);
+    const bool segments = filter && filter->segments;
+    if (!idx || !offsets_dev || !block_offsets_dev || !workspace_dev || (!mems_dev && mems_capacity && !segments) || (!queries_dev && num_queries) ||
+        (filter && !params_)) {
         set_error("slamem_find_mems_device: null argument");
         return SLAMEM_ERR_ARG;
     }
@@ -3635,119 +3613,48 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
         set_error("slamem_find_mems_device: at most 2^32 - 2^20 work items per call");
         return SLAMEM_ERR_ARG;
     }
-    if (match_type == 2) {
-        // -mum: the -mem search, then the filter (mum_filter.hip); the row places of the filter are 32-bit
-        if (mems_capacity >= 0xFFFFFFFFull) {
-            set_error("slamem_find_mums_device: at most 2^32 - 2 MEMs of capacity per call");
+    uint64_t need_ws = w.bytes;
+    if (filter) {
+        params = *params_;
+        batch = FilterBatch{&idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity};
+        if (filter->needs_planes && (idx->hdr.off_tpl == 0 || !idx->view.tpl)) {
+            set_error("%s: %s needs the text planes of the index, and this index has none (%s layout%s); "
+                      "build it in the full layout with the seed sections", filter->name, filter->flag,
+                      idx->hdr.layout == 2u ? "compact" : "full", idx->hdr.layout == 2u ? "" : ", built without the seed sections");
             return SLAMEM_ERR_ARG;
         }
-        mum = true;
-        match_type = 0;
-    } else if (match_type == 3) {
-        // -smem: the -mem search, then the filter (smem_filter.hip); its row places and tiles are 32-bit
-        if (mems_capacity >= 0xFFFF0000ull) {
-            set_error("slamem_find_smems_device: at most 2^32 - 2^16 MEMs of capacity per call");
+        if (filter->needs_reads && !params.reads && num_queries) {
+            set_error("%s: null argument", filter->name);
             return SLAMEM_ERR_ARG;
         }
-        smem = true;
-        match_type = 0;
-    } else if (match_type == 4) {
-        // -chain: the -mem search, then the filter (chain_filter.hip); its row places are 32-bit, its differences 64-bit signed
-        if (mems_capacity >= 0xFFFF0000ull) {
-            set_error("slamem_find_chains_device: at most 2^32 - 2^16 MEMs of capacity per call");
+        if (mems_capacity >= filter->capacity_end || (filter->bounds_blocks && num_blocks >= 0xFFFFFFFFull) ||
+            (segments && params.ops_capacity >= filter->capacity_end)) {
+            set_error("%s", filter->limits);
             return SLAMEM_ERR_ARG;
         }
-        chain = true;
-        match_type = 0;
-    } else if (match_type == 5) {
-        // -ext: the -mem search, then the filter (ext_filter.hip), which compares the reads with the text planes of the index
-        if (idx->hdr.off_tpl == 0 || !idx->view.tpl) {
-            set_error("slamem_find_exts_device: -ext needs the text planes of the index, and this index has none (%s layout%s); "
-                      "build it in the full layout with the seed sections", idx->hdr.layout == 2u ? "compact" : "full",
-                      idx->hdr.layout == 2u ? "" : ", built without the seed sections");
-            return SLAMEM_ERR_ARG;
-        }
-        if (mems_capacity >= 0xFFFF0000ull || num_blocks >= 0xFFFFFFFFull) {
-            set_error("slamem_find_exts_device: at most 2^32 - 2^16 MEMs of capacity and 2^32 - 2 strand blocks per call");
-            return SLAMEM_ERR_ARG;
-        }
-        ext = true;
-        match_type = 0;
-    } else if (match_type == 6 || match_type == 7) {
-        // -aln: the -mem search, then the filter (aln_filter.hip), which compares the reads with the text planes of the index
-        // -paf: the same with map_filter.hip, which chooses one strand block per read first
-        if (match_type == 7 && (idx->hdr.off_tpl == 0 || !idx->view.tpl)) {
-            set_error("slamem_find_maps_device: -paf needs the text planes of the index, and this index has none (%s layout%s); "
-                      "build it in the full layout with the seed sections", idx->hdr.layout == 2u ? "compact" : "full",
-                      idx->hdr.layout == 2u ? "" : ", built without the seed sections");
-            return SLAMEM_ERR_ARG;
-        }
-        if (match_type == 7 && !alnargs.reads && num_queries) {
-            set_error("slamem_find_maps_device: null argument");
-            return SLAMEM_ERR_ARG;
-        }
-        if (idx->hdr.off_tpl == 0 || !idx->view.tpl) {
-            set_error("slamem_find_alns_device: -aln needs the text planes of the index, and this index has none (%s layout%s); "
-                      "build it in the full layout with the seed sections", idx->hdr.layout == 2u ? "compact" : "full",
-                      idx->hdr.layout == 2u ? "" : ", built without the seed sections");
-            return SLAMEM_ERR_ARG;
-        }
-        if (mems_capacity >= 0xFFFF0000ull || num_blocks >= 0xFFFFFFFFull || alnargs.ops_capacity >= 0xFFFF0000ull) {
-            set_error("slamem_find_alns_device: at most 2^32 - 2^16 MEMs and operations of capacity and 2^32 - 2 strand blocks per call");
-            return SLAMEM_ERR_ARG;
-        }
-        if (!alnargs.op_offsets || (!alnargs.segs && alnargs.segs_capacity) || (!alnargs.ops && alnargs.ops_capacity) ||
-            alnargs.max_edits > kAlnMaxEdits) {
+        if (segments && (!params.op_offsets || (!params.segs && params.segs_capacity) || (!params.ops && params.ops_capacity) ||
+                         params.max_edits > kAlnMaxEdits)) {
             set_error("slamem_find_alns_device: null argument, or more than %u edits a gap", kAlnMaxEdits);
             return SLAMEM_ERR_ARG;
         }
-        aln = true;
-        map = match_type == 7;
         match_type = 0;
+        need_ws += filter->workspace_bytes(batch, params);
     }
-    const uint64_t need_ws = mum ? w.bytes + mum_workspace_bytes(num_blocks, mems_capacity)
-                                 : smem ? w.bytes + smem_workspace_bytes(num_blocks, mems_capacity)
-                                 : chain ? w.bytes + chain_workspace_bytes(num_blocks, mems_capacity)
-                                 : ext ? w.bytes + ext_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity)
-                                 : map ? w.bytes + map_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity,
-                                                                       alnargs.ops_capacity, alnargs.max_edits)
-                                 : aln ? w.bytes + aln_workspace_bytes(num_queries, num_blocks, query_bytes, mems_capacity,
-                                                                       alnargs.ops_capacity, alnargs.max_edits) : w.bytes;
     if (workspace_bytes < need_ws) {
         set_error("slamem_find_mems_device: workspace too small (%llu < %llu bytes)",
                   (unsigned long long)workspace_bytes, (unsigned long long)need_ws);
         return SLAMEM_ERR_ARG;
     }
-    if (mum) {
-        out_mems = mems_dev;
+    if (filter) {
+        out_mems = segments ? nullptr : mems_dev;
         out_boff = block_offsets_dev;
-        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
-        mum_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
-    } else if (smem) {
-        out_mems = mems_dev;
-        out_boff = block_offsets_dev;
-        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
-        smem_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
-    } else if (chain) {
-        out_mems = mems_dev;
-        out_boff = block_offsets_dev;
-        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
-        chain_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
-    } else if (ext) {
-        out_mems = mems_dev;
-        out_boff = block_offsets_dev;
-        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
-        ext_list_buffers(mum_ws, num_queries, num_blocks, query_bytes, mems_capacity, &mems_dev, &block_offsets_dev);
-    } else if (aln) {
-        out_mems = nullptr;
-        out_boff = block_offsets_dev;
-        mum_ws = static_cast<char*>(workspace_dev) + w.bytes;
-        aln_list_buffers(mum_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
+        filter_ws = static_cast<char*>(workspace_dev) + w.bytes;
+        filter_list_buffers(filter_ws, num_blocks, mems_capacity, &mems_dev, &block_offsets_dev);
     }
     want_stats = search_stats_wanted();
     for (int i = 0; i < 6; i++)
         if (!ev[i]) SLAMEM_HIP(hipEventCreate(&ev[i]));
-    for (int i = 0; i < 2 && (mum || smem || chain || ext || aln); i++)
+    for (int i = 0; i < 2 && filter; i++)
         if (!ev_mum[i]) SLAMEM_HIP(hipEventCreate(&ev_mum[i]));
     return SLAMEM_OK;
 }
@@ -4265,35 +4172,9 @@ int SearchJob::place(hipStream_t stream) {
     // [0] listed; u32 word 8: survivors of K8a, word 9: ordinal overflow flag; [8] all MEMs
     STEP(hipMemcpyAsync(h_scal, d_total, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "memcpy");
     STEP(hipMemcpyAsync(h_scal + 8, d_itemoff + nitems, 8, hipMemcpyDeviceToHost, stream), "memcpy");
-    if (mum) {  // -mum: the filter, right behind K9; its two scalars go back with the others
+    if (filter) {  // right behind K9; its scalars go back with the others
         (void)hipEventRecord(ev_mum[0], stream);
-        int rc = mum_filter_small(mum_ws, num_blocks, mems_capacity, out_mems, out_boff, h_scal + 9, stream);
-        if (rc != SLAMEM_OK) return rc;
-        (void)hipEventRecord(ev_mum[1], stream);
-    } else if (smem) {  // -smem: the same place; every block is decided on the device, its two scalars go back with the others
-        (void)hipEventRecord(ev_mum[0], stream);
-        int rc = smem_filter(mum_ws, num_blocks, mems_capacity, max_occ, out_mems, out_boff, h_scal + 9, stream);
-        if (rc != SLAMEM_OK) return rc;
-        (void)hipEventRecord(ev_mum[1], stream);
-    } else if (chain) {  // -chain: likewise
-        (void)hipEventRecord(ev_mum[0], stream);
-        int rc = chain_filter(mum_ws, num_blocks, mems_capacity, max_gap ? max_gap : kChainDefaultGap, out_mems, out_boff, scores_dev,
-                              h_scal + 9, stream);
-        if (rc != SLAMEM_OK) return rc;
-        (void)hipEventRecord(ev_mum[1], stream);
-    } else if (ext) {  // -ext: likewise
-        (void)hipEventRecord(ev_mum[0], stream);
-        int rc = ext_filter(mum_ws, idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity,
-                            ext_penalty ? ext_penalty : kExtDefaultPenalty, ext_xdrop == kExtXdropUnset ? kExtDefaultXdrop : ext_xdrop,
-                            out_mems, out_boff, mism_dev, h_scal + 9, stream);
-        if (rc != SLAMEM_OK) return rc;
-        (void)hipEventRecord(ev_mum[1], stream);
-    } else if (aln) {  // -aln: likewise; three scalars
-        (void)hipEventRecord(ev_mum[0], stream);
-        int rc = map ? map_filter(mum_ws, idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity,
-                                  alnargs, out_boff, h_scal + 9, stream)
-                     : aln_filter(mum_ws, idx->view, queries_dev, offsets_dev, num_queries, strands, query_bytes, mems_capacity, alnargs,
-                                  out_boff, h_scal + 9, stream);
+        int rc = filter->run(filter_ws, batch, params, out_mems, out_boff, h_scal + 9, stream);
         if (rc != SLAMEM_OK) return rc;
         (void)hipEventRecord(ev_mum[1], stream);
     }
@@ -4386,55 +4267,28 @@ int SearchJob::collect() {
         return SLAMEM_ERR_CAPACITY;
     }
     tm.t.mum_filter_ms = 0;
-    if (mum) {
-        // (the -mem list fitted: the filter's result is the batch's, or, with a large block, finish() completes it)
+    if (!filter) return SLAMEM_OK;
+    // (the -mem list fitted: the filter's result is the batch's)
+    if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
+    if (filter->finish) {  // (-mum: with a large block, finish() completes it)
         mum_large = h_scal[10];
         if (!mum_large) total = h_scal[9];
-        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
-    } else if (smem && !saw_long) {
-        // (a batch that found a record longer than a slice is searched again: its list here is not the batch's)
-        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
-        if (h_scal[10]) {
-            set_error("slamem_find_smems_device: the -mem rows of strand block %llu are not in the emission order (query start "
-                      "descending, then length non-increasing); no SMEMs returned", h_scal[10] - 1ull);
-            total = 0;
-            return SLAMEM_ERR_ARG;
-        }
-        total = h_scal[9];
-    } else if (chain && !saw_long) {
-        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
-        if (h_scal[10]) {
-            set_error("slamem_find_chains_device: the -mem rows of strand block %llu are not in the emission order (query start "
-                      "descending, then length non-increasing); no chains returned", h_scal[10] - 1ull);
-            total = 0;
-            return SLAMEM_ERR_ARG;
-        }
-        total = h_scal[9];
-    } else if (ext && !saw_long) {
-        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
-        if (h_scal[10]) {
-            set_error("slamem_find_exts_device: the -mem rows of strand block %llu are not in the emission order (query start "
-                      "descending, then length non-increasing); no extended MEMs returned", h_scal[10] - 1ull);
-            total = 0;
-            return SLAMEM_ERR_ARG;
-        }
-        total = h_scal[9];
-    } else if (aln && !saw_long) {
-        if (hipEventElapsedTime(&ms, ev_mum[0], ev_mum[1]) == hipSuccess) tm.t.mum_filter_ms = ms;
-        if (h_scal[10]) {
-            set_error("%s: the -mem rows of strand block %llu are not in the emission order (query start "
-                      "descending, then length non-increasing); no alignments returned",
-                      map ? "slamem_find_maps_device" : "slamem_find_alns_device", h_scal[10] - 1ull);
-            total = 0;
-            return SLAMEM_ERR_ARG;
-        }
-        total = h_scal[9];
+        return SLAMEM_OK;
+    }
+    if (h_scal[10]) {
+        set_error("%s: the -mem rows of strand block %llu are not in the emission order (query start "
+                  "descending, then length non-increasing); no %s returned", filter->name, h_scal[10] - 1ull, filter->noun);
+        total = 0;
+        return SLAMEM_ERR_ARG;
+    }
+    total = h_scal[9];
+    if (filter->segments) {
         aln_totals[1] = h_scal[9];
         aln_totals[2] = h_scal[11];
-        if (aln_totals[1] > alnargs.segs_capacity || aln_totals[2] > alnargs.ops_capacity) {
-            set_error("%s: %llu segments with %llu operations, the capacities are %llu and %llu",
-                      map ? "slamem_find_maps_device" : "slamem_find_alns_device", (unsigned long long)aln_totals[1], (unsigned long long)aln_totals[2],
-                      (unsigned long long)alnargs.segs_capacity, (unsigned long long)alnargs.ops_capacity);
+        if (aln_totals[1] > params.segs_capacity || aln_totals[2] > params.ops_capacity) {
+            set_error("%s: %llu segments with %llu operations, the capacities are %llu and %llu", filter->name,
+                      (unsigned long long)aln_totals[1], (unsigned long long)aln_totals[2],
+                      (unsigned long long)params.segs_capacity, (unsigned long long)params.ops_capacity);
             return SLAMEM_ERR_CAPACITY;
         }
     }
@@ -4442,11 +4296,11 @@ int SearchJob::collect() {
 }
 
 int SearchJob::finish(hipStream_t stream) {
-    if (!mum || !mum_large) return SLAMEM_OK;
+    if (!mum_large) return SLAMEM_OK;
     SLAMEM_HIP(hipSetDevice(idx->device));
     (void)hipEventRecord(ev_mum[0], stream);
     uint64_t kept = 0;
-    int rc = mum_filter_large(mum_ws, num_blocks, mems_capacity, mum_large, out_mems, out_boff, stream, &kept);
+    int rc = filter->finish(filter_ws, batch, mum_large, out_mems, out_boff, stream, &kept);
     if (rc != SLAMEM_OK) return rc;
     (void)hipEventRecord(ev_mum[1], stream);
     float ms = 0;
@@ -4458,48 +4312,29 @@ int SearchJob::finish(hipStream_t stream) {
 }
 #undef STEP
 
-static int run_job(SearchJob& job, const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
-                   uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
-                   slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                   uint64_t workspace_bytes, hipStream_t stream, uint32_t max_occ, uint32_t max_gap, uint32_t* scores_dev,
-                   uint32_t ext_penalty, uint32_t ext_xdrop, const AlnArgs* aln) {
-    if (aln) job.alnargs = *aln;  // (before init, unlike the parameters below: init sizes the workspace by it)
-    int rc = job.init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                      mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
-    job.max_occ = max_occ;
-    job.max_gap = max_gap;
-    job.scores_dev = scores_dev;
-    job.ext_penalty = ext_penalty;
-    job.ext_xdrop = ext_xdrop;
-    job.mism_dev = scores_dev;  // (-ext: the per-row column travels in the place of -chain's per-block one)
-    if (rc == SLAMEM_OK) rc = job.tables(stream);
-    if (rc == SLAMEM_OK) rc = job.prep(stream);
-    if (rc == SLAMEM_OK) rc = job.search(stream);
-    if (job.launched) {  // never return with kernels of this call in flight
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess && rc == SLAMEM_OK) rc = hip_fail(e, "MEM search (sync)", __FILE__, __LINE__);
-    }
-    if (rc == SLAMEM_OK) rc = job.collect();
-    if (rc == SLAMEM_OK && !job.saw_long) rc = job.finish(stream);
-    return rc;
-}
 int find_mems_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev,
                      uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type,
                      slamem_mem* mems_dev, uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev,
-                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, uint32_t max_occ, uint32_t max_gap,
-                     uint32_t* block_scores_dev, uint32_t ext_penalty, uint32_t ext_xdrop, const AlnArgs* aln, uint64_t* aln_totals) {
+                     uint64_t workspace_bytes, hipStream_t stream, uint64_t* total_out, const FilterParams* params, uint64_t* aln_totals) {
     if (!total_out) { set_error("slamem_find_mems_device: null argument"); return SLAMEM_ERR_ARG; }
     SearchJob job;
-    job.speculate = true;
-    int rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev,
-                     ext_penalty, ext_xdrop, aln);
-    if (rc == SLAMEM_OK && job.saw_long) {  // a record longer than a slice among the reads: once more, with the item tables
-        job.speculate = false;
-        rc = run_job(job, idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                     mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, stream, max_occ, max_gap, block_scores_dev,
-                     ext_penalty, ext_xdrop, aln);
-    }
+    auto run = [&](bool speculate) {
+        job.speculate = speculate;
+        int rc = job.init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
+                          mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, params);
+        if (rc == SLAMEM_OK) rc = job.tables(stream);
+        if (rc == SLAMEM_OK) rc = job.prep(stream);
+        if (rc == SLAMEM_OK) rc = job.search(stream);
+        if (job.launched) {  // never return with kernels of this call in flight
+            hipError_t e = hipStreamSynchronize(stream);
+            if (e != hipSuccess && rc == SLAMEM_OK) rc = hip_fail(e, "MEM search (sync)", __FILE__, __LINE__);
+        }
+        if (rc == SLAMEM_OK) rc = job.collect();
+        if (rc == SLAMEM_OK && !job.saw_long) rc = job.finish(stream);
+        return rc;
+    };
+    int rc = run(true);
+    if (rc == SLAMEM_OK && job.saw_long) rc = run(false);  // a record longer than a slice among the reads: once more, with the item tables
     *total_out = job.total;
     if (aln_totals) { aln_totals[0] = job.aln_totals[0]; aln_totals[1] = job.aln_totals[1]; aln_totals[2] = job.aln_totals[2]; }
     return rc;
@@ -4511,31 +4346,17 @@ void search_job_delete(SearchJob* j) { delete j; }
 int search_job_init(SearchJob* j, const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
                     uint64_t query_bytes, uint32_t min_len, int both_strands, int match_type, slamem_mem* mems_dev,
                     uint64_t mems_capacity, uint64_t* block_offsets_dev, void* workspace_dev, uint64_t workspace_bytes,
-                    unsigned long long* host_scalars) {
+                    unsigned long long* host_scalars, const FilterParams* params) {
     j->h_scal = host_scalars ? host_scalars : j->scal_own;
     j->slices_hint = 0xFFFFFFFFu;
     j->k8_wave_cap = 0;
-    j->max_occ = 0;
-    j->max_gap = 0;
-    j->scores_dev = nullptr;
-    j->ext_penalty = 0;
-    j->ext_xdrop = kExtXdropUnset;
-    j->mism_dev = nullptr;
     return j->init(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, match_type, mems_dev,
-                   mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes);
+                   mems_capacity, block_offsets_dev, workspace_dev, workspace_bytes, params);
 }
 void search_job_slices_hint(SearchJob* j, uint32_t slices) { j->slices_hint = slices; }
 void search_job_k8_wave_cap(SearchJob* j, uint32_t waves) { j->k8_wave_cap = waves; }
-void search_job_max_occ(SearchJob* j, uint32_t max_occ) { j->max_occ = max_occ; }
-void search_job_max_gap(SearchJob* j, uint32_t max_gap) { j->max_gap = max_gap; }
-void search_job_aln(SearchJob* j, const AlnArgs& args) { j->alnargs = args; }
 void search_job_aln_totals(const SearchJob* j, uint64_t totals[3]) {
     totals[0] = j->aln_totals[0]; totals[1] = j->aln_totals[1]; totals[2] = j->aln_totals[2];
-}
-void search_job_ext(SearchJob* j, uint32_t penalty, uint32_t xdrop, uint32_t* mismatches_dev) {
-    j->ext_penalty = penalty;
-    j->ext_xdrop = xdrop;
-    j->mism_dev = mismatches_dev;
 }
 int search_job_tables(SearchJob* j, hipStream_t stream) { return j->tables(stream); }
 int search_job_prep(SearchJob* j, hipStream_t stream) { return j->prep(stream); }

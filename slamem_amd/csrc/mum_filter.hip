@@ -7,21 +7,17 @@
 //                 the block goes to the list of large blocks (one 64-bit atomic gives it its ordinal and the place of its
 //                 rows in the gathered arrays, in the same order)
 //   scan          kept rows per block -> new block offsets
-//   k_mum_copy    one lane per block copies its kept rows; skipped when the batch has a large block (its counts are not
-//                 final yet: the host sees the flag with the batch's scalars and runs the large path, then this again)
+//   k_filter_copy one lane per block copies its kept rows; gated: skipped when the batch has a large block (its counts are
+//                 not final yet: the host sees the flag with the batch's scalars and runs the large path, then this again)
 // Large blocks (mum_filter_large): the rows are gathered and sorted per coordinate into (block ordinal, start, end
 // descending) -- two stable radix sorts, the end first -- and one workgroup per large block walks its rows in that order:
 // a row is contained when the largest end among the rows before it is >= its own end, or when the next row is the same
 // interval (two equal intervals contain each other: both go).  O(n log n) per block.
-#include "common.h"
-#include "prims.h"
+#include "filter_blocks.h"
 
 namespace slamem {
 
 namespace {
-
-inline unsigned grid_for(uint64_t items, unsigned block = 256) { return (unsigned)((items + block - 1) / block); }
-inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 constexpr uint64_t kMask40 = (1ull << 40) - 1ull;
 
@@ -36,24 +32,14 @@ struct LargeBlk {
     uint32_t n;      // its rows
 };
 
-struct MumLayout {
-    uint64_t off_ctr, off_rows, off_boff, off_cnt, off_newoff, off_keep, off_scan, scan_bytes, off_large, off_grow, off_gord,
-        off_keys_a, off_keys_b, off_vals_a, off_vals_b, off_cont, off_sort, sort_bytes, bytes;
+struct MumLayout : FilterPrefix {
+    uint64_t off_large, off_grow, off_gord, off_keys_a, off_keys_b, off_vals_a, off_vals_b, off_cont, off_sort, sort_bytes, bytes;
 };
 
 MumLayout mum_layout(uint64_t num_blocks, uint64_t capacity) {
     MumLayout m;
-    uint64_t off = 0;
-    m.off_ctr = off;    off = align_up(off + 64, 256);                              // large blocks << 40 | their rows
-    m.off_rows = off;   off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);  // the -mem list (K9 places it here)
-    m.off_boff = off;   off = align_up(off + (num_blocks + 1) * 8, 256);            // ... and its block offsets
-    m.off_cnt = off;    off = align_up(off + (num_blocks + 1) * 4, 256);            // kept rows per block
-    m.off_newoff = off; off = align_up(off + (num_blocks + 1) * 8, 256);            // their exclusive sums
-    m.off_keep = off;   off = align_up(off + capacity + 16, 256);                   // a byte per -mem row
-    size_t need = 0;
-    (void)scan_sum_exclusive_u32_u64(nullptr, need, nullptr, nullptr, num_blocks, 0);
-    m.scan_bytes = need;
-    m.off_scan = off;   off = align_up(off + need, 256);
+    uint64_t off = m.begin(num_blocks, capacity);                                   // ctr: large blocks << 40 | their rows
+    off = m.scan_at(off, num_blocks);
     // the large path: rows of all large blocks together are at most the capacity
     m.off_large = off;  off = align_up(off + (capacity / (kMumPairMax + 1) + 1) * sizeof(LargeBlk), 256);
     m.off_grow = off;   off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);
@@ -69,15 +55,6 @@ MumLayout mum_layout(uint64_t num_blocks, uint64_t capacity) {
     m.off_sort = off;   off = align_up(off + sneed, 256);
     m.bytes = off;
     return m;
-}
-
-__device__ __forceinline__ void clamp_block(const uint64_t* __restrict__ boff, uint64_t b, uint64_t cap, uint64_t& s, uint64_t& e) {
-    // (a batch whose -mem list did not fit has offsets beyond the capacity: its result is refused, nothing is read past it)
-    s = boff[b];
-    e = boff[b + 1];
-    if (s > cap) s = cap;
-    if (e > cap) e = cap;
-    if (e < s) e = s;
 }
 
 // one lane per strand block (and lane num_blocks keeps the scan's last input at 0)
@@ -120,28 +97,6 @@ __global__ void __launch_bounds__(256) k_mum_small(const uint64_t* __restrict__ 
         kept += in ? 0u : 1u;
     }
     cnt[b] = kept;
-}
-
-// one lane per strand block: new offsets and the kept rows of blocks of up to kMumPairMax MEMs (large ones: k_mum_large_copy).
-// Not final (the pass behind k_mum_small): nothing is written when the batch has a large block.
-__global__ void __launch_bounds__(256) k_mum_copy(const uint64_t* __restrict__ boff, uint64_t nb, const slamem_mem* __restrict__ rows,
-                                                  uint64_t cap, const uint8_t* __restrict__ keep, const uint64_t* __restrict__ newoff,
-                                                  slamem_mem* __restrict__ out, uint64_t* __restrict__ out_boff,
-                                                  const unsigned long long* __restrict__ large_ctr, int final_pass) {
-    const uint64_t b = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (b > nb) return;
-    if (!final_pass && *large_ctr != 0ull) return;
-    uint64_t d = newoff[b];
-    out_boff[b] = d;
-    if (b == nb) return;
-    uint64_t s, e;
-    clamp_block(boff, b, cap, s, e);
-    if (e - s > kMumPairMax) return;
-    for (uint64_t i = s; i < e; i++) {
-        if (!keep[i]) continue;
-        if (d < cap) out[d] = rows[i];
-        d++;
-    }
 }
 
 // ---- large blocks: one workgroup per block, grid = their number ----------------------------------------------------------
@@ -274,51 +229,35 @@ __global__ void __launch_bounds__(256) k_mum_large_copy(const LargeBlk* __restri
 
 }  // namespace
 
-uint64_t mum_workspace_bytes(uint64_t num_blocks, uint64_t capacity) { return mum_layout(num_blocks, capacity).bytes; }
+uint64_t mum_workspace_bytes(const FilterBatch& b, const FilterParams&) { return mum_layout(b.num_blocks(), b.capacity).bytes; }
 
 #define MSTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
 
-void mum_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out) {
-    const MumLayout m = mum_layout(num_blocks, capacity);
-    char* p = static_cast<char*>(ws);
-    *rows_out = reinterpret_cast<slamem_mem*>(p + m.off_rows);
-    *boff_out = reinterpret_cast<uint64_t*>(p + m.off_boff);
-}
-
-int mum_filter_small(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem* out_mems, uint64_t* out_boff,
+int mum_filter_small(void* ws, const FilterBatch& b, const FilterParams&, slamem_mem* out_mems, uint64_t* out_boff,
                      unsigned long long* host_scalars, hipStream_t stream) {
+    const uint64_t num_blocks = b.num_blocks(), capacity = b.capacity;
     const MumLayout m = mum_layout(num_blocks, capacity);
-    char* p = static_cast<char*>(ws);
-    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
-    const slamem_mem* rows = reinterpret_cast<const slamem_mem*>(p + m.off_rows);
-    const uint64_t* boff = reinterpret_cast<const uint64_t*>(p + m.off_boff);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
-    uint64_t* newoff = reinterpret_cast<uint64_t*>(p + m.off_newoff);
-    uint8_t* keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
-    MSTEP(hipMemsetAsync(ctr, 0, 8, stream), "memset");
-    hipLaunchKernelGGL(k_mum_small, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity, cnt, keep,
-                       reinterpret_cast<LargeBlk*>(p + m.off_large), ctr);
+    const FilterBufs w = filter_bufs(ws, m);
+    MSTEP(hipMemsetAsync(w.ctr, 0, 8, stream), "memset");
+    hipLaunchKernelGGL(k_mum_small, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, (const uint64_t*)w.boff, num_blocks,
+                       (const slamem_mem*)w.rows, capacity, w.cnt, w.keep,
+                       reinterpret_cast<LargeBlk*>(static_cast<char*>(ws) + m.off_large), w.ctr);
     MSTEP(hipGetLastError(), "k_mum_small");
-    size_t need = m.scan_bytes;
-    MSTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, cnt, newoff, num_blocks, stream), "scan");
-    hipLaunchKernelGGL(k_mum_copy, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity,
-                       (const uint8_t*)keep, (const uint64_t*)newoff, out_mems, out_boff, (const unsigned long long*)ctr, 0);
-    MSTEP(hipGetLastError(), "k_mum_copy");
+    MSTEP((compact_kept<kMumPairMax, false, true>(w, num_blocks, capacity, w.rows, out_mems, out_boff, stream, nullptr, nullptr, w.ctr)),
+          "compact_kept");
     // [0] rows kept (final when [1] is 0), [1] large blocks << 40 | their rows
-    MSTEP(hipMemcpyAsync(host_scalars, newoff + num_blocks, 8, hipMemcpyDeviceToHost, stream), "memcpy");
-    MSTEP(hipMemcpyAsync(host_scalars + 1, ctr, 8, hipMemcpyDeviceToHost, stream), "memcpy");
+    MSTEP(kept_scalars(w, num_blocks, w.ctr, host_scalars, stream), "memcpy");
     return SLAMEM_OK;
 }
 
-int mum_filter_large(void* ws, uint64_t num_blocks, uint64_t capacity, unsigned long long large_ctr, slamem_mem* out_mems,
-                     uint64_t* out_boff, hipStream_t stream, uint64_t* total_out) {
+int mum_filter_large(void* ws, const FilterBatch& b, unsigned long long large_ctr, slamem_mem* out_mems, uint64_t* out_boff,
+                     hipStream_t stream, uint64_t* total_out) {
+    const uint64_t num_blocks = b.num_blocks(), capacity = b.capacity;
     const MumLayout m = mum_layout(num_blocks, capacity);
+    const FilterBufs w = filter_bufs(ws, m);
     char* p = static_cast<char*>(ws);
-    const slamem_mem* rows = reinterpret_cast<const slamem_mem*>(p + m.off_rows);
-    const uint64_t* boff = reinterpret_cast<const uint64_t*>(p + m.off_boff);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
-    uint64_t* newoff = reinterpret_cast<uint64_t*>(p + m.off_newoff);
-    uint8_t* keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
+    const slamem_mem* rows = w.rows;
+    const uint64_t* boff = w.boff;
     const LargeBlk* large = reinterpret_cast<const LargeBlk*>(p + m.off_large);
     slamem_mem* grow = reinterpret_cast<slamem_mem*>(p + m.off_grow);
     uint32_t* gord = reinterpret_cast<uint32_t*>(p + m.off_gord);
@@ -351,18 +290,14 @@ int mum_filter_large(void* ws, uint64_t num_blocks, uint64_t capacity, unsigned 
                            coord, cont);
         MSTEP(hipGetLastError(), "k_mum_contain");
     }
-    hipLaunchKernelGGL(k_mum_large_count, dim3((unsigned)nl), dim3(256), 0, stream, large, boff, capacity, (const uint8_t*)cont, keep, cnt);
+    hipLaunchKernelGGL(k_mum_large_count, dim3((unsigned)nl), dim3(256), 0, stream, large, boff, capacity, (const uint8_t*)cont, w.keep, w.cnt);
     MSTEP(hipGetLastError(), "k_mum_large_count");
-    size_t need = m.scan_bytes;
-    MSTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, cnt, newoff, num_blocks, stream), "scan");
-    hipLaunchKernelGGL(k_mum_copy, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity,
-                       (const uint8_t*)keep, (const uint64_t*)newoff, out_mems, out_boff, (const unsigned long long*)nullptr, 1);
-    MSTEP(hipGetLastError(), "k_mum_copy");
-    hipLaunchKernelGGL(k_mum_large_copy, dim3((unsigned)nl), dim3(256), 0, stream, large, boff, capacity, rows, (const uint8_t*)keep,
-                       (const uint64_t*)newoff, out_mems);
+    MSTEP((compact_kept<kMumPairMax, false, true>(w, num_blocks, capacity, rows, out_mems, out_boff, stream)), "compact_kept");  // (no gate: final)
+    hipLaunchKernelGGL(k_mum_large_copy, dim3((unsigned)nl), dim3(256), 0, stream, large, boff, capacity, rows, (const uint8_t*)w.keep,
+                       (const uint64_t*)w.newoff, out_mems);
     MSTEP(hipGetLastError(), "k_mum_large_copy");
     unsigned long long kept = 0;
-    MSTEP(hipMemcpyAsync(&kept, newoff + num_blocks, 8, hipMemcpyDeviceToHost, stream), "memcpy");
+    MSTEP(hipMemcpyAsync(&kept, w.newoff + num_blocks, 8, hipMemcpyDeviceToHost, stream), "memcpy");
     MSTEP(hipStreamSynchronize(stream), "-mum large blocks (sync)");
     *total_out = kept;
     return SLAMEM_OK;

@@ -21,59 +21,32 @@
 //                       of each row's run), in tiles of kSmemTile rows: kSmemItems consecutive rows a thread, a wave scan
 //                       of the threads' aggregates, the running value carried from tile to tile
 //   scan                kept rows per block -> new block offsets (scan_sum_exclusive_u32_u64)
-//   k_smem_copy / k_smem_large_copy   the kept rows, in order (large blocks: tiles ranked by a workgroup scan)
+//   k_filter_copy / k_smem_large_copy the kept rows, in order (large blocks: tiles ranked by a workgroup scan)
 // Every row is checked against the one before it (one compare): a block out of that order fails the call (the first such
 // block, + 1, goes back with the batch's scalars) -- never wrong rows.
-#include "common.h"
-#include "prims.h"
+#include "filter_blocks.h"
 
 namespace slamem {
 
 namespace {
-
-inline unsigned grid_for(uint64_t items, unsigned block = 256) { return (unsigned)((items + block - 1) / block); }
-inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 // a lane walks blocks of up to this many rows (two reads of each, L1-resident); reads at -l 20 have a handful
 constexpr uint32_t kSmemLaneMax = 256;
 constexpr uint32_t kSmemWg = 256, kSmemItems = 8, kSmemTile = kSmemWg * kSmemItems;
 constexpr unsigned kSmemLargeGrid = 256;  // workgroups that share the list of large blocks (one per CU)
 
-struct SmemLayout {
-    uint64_t off_ctr, off_rows, off_boff, off_cnt, off_newoff, off_keep, off_rstart, off_scan, scan_bytes, off_large, bytes;
+struct SmemLayout : FilterPrefix {
+    uint64_t off_rstart, off_large, bytes;
 };
 
 SmemLayout smem_layout(uint64_t num_blocks, uint64_t capacity) {
     SmemLayout m;
-    uint64_t off = 0;
-    m.off_ctr = off;    off = align_up(off + 64, 256);                                  // [0] large blocks, [1] order violation
-    m.off_rows = off;   off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);  // the -mem list (K9 places it here)
-    m.off_boff = off;   off = align_up(off + (num_blocks + 1) * 8, 256);                // ... and its block offsets
-    m.off_cnt = off;    off = align_up(off + (num_blocks + 1) * 4, 256);                // kept rows per block
-    m.off_newoff = off; off = align_up(off + (num_blocks + 1) * 8, 256);                // their exclusive sums
-    m.off_keep = off;   off = align_up(off + capacity + 16, 256);                       // a byte per -mem row
+    uint64_t off = m.begin(num_blocks, capacity);                                       // ctr: [0] large blocks, [1] order violation
     m.off_rstart = off; off = align_up(off + capacity * 4 + 16, 256);                   // large blocks, with a cap: run starts
-    size_t need = 0;
-    (void)scan_sum_exclusive_u32_u64(nullptr, need, nullptr, nullptr, num_blocks, 0);
-    m.scan_bytes = need;
-    m.off_scan = off;   off = align_up(off + need, 256);
+    off = m.scan_at(off, num_blocks);
     m.off_large = off;  off = align_up(off + (capacity / (kSmemLaneMax + 1) + 1) * 8, 256);  // listed strand blocks
     m.bytes = off;
     return m;
-}
-
-__device__ __forceinline__ void clamp_block(const uint64_t* __restrict__ boff, uint64_t b, uint64_t cap, uint64_t& s, uint64_t& e) {
-    // (a batch whose -mem list did not fit has offsets beyond the capacity: its result is refused, nothing is read past it)
-    s = boff[b];
-    e = boff[b + 1];
-    if (s > cap) s = cap;
-    if (e > cap) e = cap;
-    if (e < s) e = s;
-}
-
-// the order every block must be in: q descending, then L non-increasing
-__device__ __forceinline__ bool out_of_order(const slamem_mem& prev, const slamem_mem& r) {
-    return r.query_pos > prev.query_pos || (r.query_pos == prev.query_pos && r.length > prev.length);
 }
 
 __device__ __forceinline__ bool same_interval(const slamem_mem& x, const slamem_mem& y) {
@@ -292,26 +265,6 @@ __global__ void __launch_bounds__(kSmemWg) k_smem_large(const uint64_t* __restri
     }
 }
 
-// one lane per strand block: new offsets, and the kept rows of blocks of up to kSmemLaneMax rows
-__global__ void __launch_bounds__(256) k_smem_copy(const uint64_t* __restrict__ boff, uint64_t nb, const slamem_mem* __restrict__ rows,
-                                                   uint64_t cap, const uint8_t* __restrict__ keep, const uint64_t* __restrict__ newoff,
-                                                   slamem_mem* __restrict__ out, uint64_t* __restrict__ out_boff) {
-    const uint64_t b = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (b > nb) return;
-    uint64_t d = newoff[b];
-    out_boff[b] = d;
-    if (b == nb) return;
-    uint64_t s, e;
-    clamp_block(boff, b, cap, s, e);
-    if (e - s > kSmemLaneMax) return;
-    const uint64_t d_end = newoff[b + 1];
-    for (uint64_t i = s; i < e && d < d_end; i++) {
-        if (!keep[i]) continue;
-        if (d < cap) out[d] = rows[i];
-        d++;
-    }
-}
-
 // a listed block's kept rows, in order: tiles of kSmemTile rows ranked with a workgroup scan
 __global__ void __launch_bounds__(kSmemWg) k_smem_large_copy(const uint64_t* __restrict__ large, const unsigned long long* __restrict__ ctr,
                                                              const uint64_t* __restrict__ boff, uint64_t cap, const slamem_mem* __restrict__ rows,
@@ -346,48 +299,30 @@ __global__ void __launch_bounds__(kSmemWg) k_smem_large_copy(const uint64_t* __r
 
 }  // namespace
 
-uint64_t smem_workspace_bytes(uint64_t num_blocks, uint64_t capacity) { return smem_layout(num_blocks, capacity).bytes; }
+uint64_t smem_workspace_bytes(const FilterBatch& b, const FilterParams&) { return smem_layout(b.num_blocks(), b.capacity).bytes; }
 
 #define SSTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
 
-void smem_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out) {
-    const SmemLayout m = smem_layout(num_blocks, capacity);
-    char* p = static_cast<char*>(ws);
-    *rows_out = reinterpret_cast<slamem_mem*>(p + m.off_rows);
-    *boff_out = reinterpret_cast<uint64_t*>(p + m.off_boff);
-}
-
-int smem_filter(void* ws, uint64_t num_blocks, uint64_t capacity, uint32_t max_occ, slamem_mem* out_mems, uint64_t* out_boff,
+int smem_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
                 unsigned long long* host_scalars, hipStream_t stream) {
+    const uint64_t num_blocks = b.num_blocks(), capacity = b.capacity;
     const SmemLayout m = smem_layout(num_blocks, capacity);
-    char* p = static_cast<char*>(ws);
-    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
-    const slamem_mem* rows = reinterpret_cast<const slamem_mem*>(p + m.off_rows);
-    const uint64_t* boff = reinterpret_cast<const uint64_t*>(p + m.off_boff);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(p + m.off_cnt);
-    uint64_t* newoff = reinterpret_cast<uint64_t*>(p + m.off_newoff);
-    uint8_t* keep = reinterpret_cast<uint8_t*>(p + m.off_keep);
-    uint32_t* rstart = reinterpret_cast<uint32_t*>(p + m.off_rstart);
-    uint64_t* large = reinterpret_cast<uint64_t*>(p + m.off_large);
-    SSTEP(hipMemsetAsync(ctr, 0, 16, stream), "memset");
-    hipLaunchKernelGGL(k_smem_lane, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity, max_occ, cnt,
-                       keep, large, ctr);
+    const FilterBufs w = filter_bufs(ws, m);
+    uint32_t* rstart = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + m.off_rstart);
+    uint64_t* large = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + m.off_large);
+    SSTEP(hipMemsetAsync(w.ctr, 0, 16, stream), "memset");
+    hipLaunchKernelGGL(k_smem_lane, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, (const uint64_t*)w.boff, num_blocks,
+                       (const slamem_mem*)w.rows, capacity, p.max_occ, w.cnt, w.keep, large, w.ctr);
     SSTEP(hipGetLastError(), "k_smem_lane");
-    hipLaunchKernelGGL(k_smem_large, dim3(kSmemLargeGrid), dim3(kSmemWg), 0, stream, (const uint64_t*)large, (const unsigned long long*)ctr,
-                       boff, rows, capacity, max_occ, keep, rstart, cnt, ctr);
+    hipLaunchKernelGGL(k_smem_large, dim3(kSmemLargeGrid), dim3(kSmemWg), 0, stream, (const uint64_t*)large, (const unsigned long long*)w.ctr,
+                       (const uint64_t*)w.boff, (const slamem_mem*)w.rows, capacity, p.max_occ, w.keep, rstart, w.cnt, w.ctr);
     SSTEP(hipGetLastError(), "k_smem_large");
-    size_t need = m.scan_bytes;
-    SSTEP(scan_sum_exclusive_u32_u64(p + m.off_scan, need, cnt, newoff, num_blocks, stream), "scan");
-    hipLaunchKernelGGL(k_smem_copy, dim3(grid_for(num_blocks + 1)), dim3(256), 0, stream, boff, num_blocks, rows, capacity,
-                       (const uint8_t*)keep, (const uint64_t*)newoff, out_mems, out_boff);
-    SSTEP(hipGetLastError(), "k_smem_copy");
+    SSTEP(compact_kept<kSmemLaneMax>(w, num_blocks, capacity, w.rows, out_mems, out_boff, stream), "compact_kept");
     hipLaunchKernelGGL(k_smem_large_copy, dim3(kSmemLargeGrid), dim3(kSmemWg), 0, stream, (const uint64_t*)large,
-                       (const unsigned long long*)ctr, boff, capacity, rows, (const uint8_t*)keep, (const uint32_t*)cnt,
-                       (const uint64_t*)newoff, out_mems);
+                       (const unsigned long long*)w.ctr, (const uint64_t*)w.boff, capacity, (const slamem_mem*)w.rows,
+                       (const uint8_t*)w.keep, (const uint32_t*)w.cnt, (const uint64_t*)w.newoff, out_mems);
     SSTEP(hipGetLastError(), "k_smem_large_copy");
-    // [0] rows kept, [1] the first block out of order + 1 (0: none)
-    SSTEP(hipMemcpyAsync(host_scalars, newoff + num_blocks, 8, hipMemcpyDeviceToHost, stream), "memcpy");
-    SSTEP(hipMemcpyAsync(host_scalars + 1, ctr + 1, 8, hipMemcpyDeviceToHost, stream), "memcpy");
+    SSTEP(kept_scalars(w, num_blocks, w.ctr + 1, host_scalars, stream), "memcpy");
     return SLAMEM_OK;
 }
 #undef SSTEP

@@ -112,7 +112,7 @@ struct slamem_stream {
     uint32_t max_occ = 0;  // -smem: the occurrence cap of every batch (slamem_stream_set_max_occ; 0: none)
     uint32_t max_gap = 0;  // -chain: the maximum gap of every batch (slamem_stream_set_max_gap; 0: the default)
     uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;  // -ext, -aln: penalty and drop of every batch (slamem_stream_set_ext_params)
-    uint32_t max_edits = kAlnDefaultEdits;  // -aln: the most edits in a gap (slamem_stream_set_max_edits)
+    uint32_t max_edits = kAlnEditsUnset;  // -aln: the most edits in a gap (slamem_stream_set_max_edits; kAlnEditsUnset: the default)
     slamem_pileup* pile = nullptr;          // -pile: the accumulator every batch is added to (slamem_stream_set_pileup)
     uint32_t min_mapq = 0;                  // -pile: the least mapping quality that counts
     uint64_t max_chars = 0;
@@ -154,27 +154,37 @@ inline bool is_aln(const slamem_stream* s) { return s->match_type == 6 || s->mat
 inline bool is_map(const slamem_stream* s) { return s->match_type == 7 || s->match_type == 8; }
 inline int job_type(const slamem_stream* s) { return s->match_type == 8 ? 7 : s->match_type; }
 
+// the stream's parameters (its setters have checked them) and the slot's buffers, as the filter takes them
+FilterParams slot_params(const slamem_stream* s, const Slot& sl) {
+    FilterParams p = {};  // (the setters have refused what the resolver refuses)
+    (void)resolve_filter_params("slamem_stream", s->max_occ, s->max_gap, s->ext_penalty, s->ext_xdrop, s->max_edits, &p);
+    if (s->match_type == 5) p.column_dev = sl.d_mm;
+    if (is_aln(s)) {
+        p.segs = sl.d_segs; p.segs_capacity = sl.cap;
+        p.ops = sl.d_ops; p.ops_capacity = sl.ops_cap;
+        p.op_offsets = sl.d_ooff;
+        p.reads = is_map(s) ? sl.d_reads : nullptr;
+    }
+    return p;
+}
+
 int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search stage: device output + workspace
     if (sl.d_mems) (void)hipFree(sl.d_mems);
     if (sl.d_ws) (void)hipFree(sl.d_ws);
     if (sl.d_mm) (void)hipFree(sl.d_mm);
     sl.d_mems = nullptr; sl.d_ws = nullptr; sl.d_mm = nullptr;
     sl.cap = need_cap;
-    sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, job_type(s));
     if (is_aln(s)) {
         if (sl.d_segs) (void)hipFree(sl.d_segs);
         if (sl.d_ops) (void)hipFree(sl.d_ops);
         if (sl.d_ooff) (void)hipFree(sl.d_ooff);
         sl.d_segs = nullptr; sl.d_ops = nullptr; sl.d_ooff = nullptr;
         if (sl.ops_cap < 2 * sl.cap + 1024) sl.ops_cap = 2 * sl.cap + 1024;  // (a first guess; SLAMEM_ERR_CAPACITY tells the need)
-        const uint64_t nbq = (uint64_t)sl.cap_q * (s->both ? 2u : 1u);
-        sl.ws_bytes = find_mems_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap) +
-                      (is_map(s) ? map_workspace_bytes(sl.cap_q, nbq, sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits)
-                                          : aln_workspace_bytes(sl.cap_q, nbq, sl.cap_chars, sl.cap, sl.ops_cap, s->max_edits));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_segs), (sl.cap + 1) * sizeof(slamem_aln)));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ops), (sl.ops_cap + 1) * 4));
         SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ooff), (sl.cap + 2) * 8));
     }
+    sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, job_type(s), slot_params(s, sl));
     SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mems), sl.cap * sizeof(slamem_mem) + 16));
     SLAMEM_HIP(hipMalloc(&sl.d_ws, sl.ws_bytes));
     if (s->match_type == 5) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mm), sl.cap * 4 + 16));
@@ -371,24 +381,9 @@ int job_setup(slamem_stream* s, Slot& sl) {
     if (!sl.ev_done) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
     if (!sl.ev_k8) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_k8, hipEventDisableTiming));
     if (!sl.h_scal) SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_scal), 16 * sizeof(unsigned long long), hipHostMallocDefault));
-    if (is_aln(s)) {
-        AlnArgs a;
-        a.max_gap = s->max_gap ? s->max_gap : kChainDefaultGap;
-        a.penalty = s->ext_penalty ? s->ext_penalty : kExtDefaultPenalty;
-        a.xdrop = s->ext_xdrop == kExtXdropUnset ? kExtDefaultXdrop : s->ext_xdrop;
-        a.max_edits = s->max_edits;
-        a.segs = sl.d_segs; a.segs_capacity = sl.cap;
-        a.ops = sl.d_ops; a.ops_capacity = sl.ops_cap;
-        a.op_offsets = sl.d_ooff;
-        a.reads = is_map(s) ? sl.d_reads : nullptr;
-        search_job_aln(sl.job, a);
-    }
-    int rc = search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, job_type(s),
-                             sl.d_mems, sl.cap, sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal);
-    search_job_max_occ(sl.job, s->max_occ);
-    search_job_max_gap(sl.job, s->max_gap);
-    if (s->match_type == 5) search_job_ext(sl.job, s->ext_penalty, s->ext_xdrop, sl.d_mm);
-    return rc;
+    const FilterParams p = slot_params(s, sl);
+    return search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, job_type(s), sl.d_mems, sl.cap,
+                           sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal, &p);
 }
 int stage_prepare(slamem_stream* s, Slot& sl) {
     int rc = job_setup(s, sl);
@@ -879,7 +874,7 @@ int slamem_stream_set_max_edits(slamem_stream* s, uint32_t max_edits) {
         set_error("slamem_stream_set_max_edits: the stream has batches already (set the limit before the first submit)");
         return SLAMEM_ERR_ARG;
     }
-    s->max_edits = max_edits == kAlnEditsUnset ? kAlnDefaultEdits : max_edits;
+    s->max_edits = max_edits;
     return SLAMEM_OK;
 }
 
