@@ -202,7 +202,7 @@ hipError_t scan_max_inclusive_u32(void* tmp, size_t& tmp_bytes, const uint32_t* 
     return scan_impl<MaxU32, LoadU32, LoadU32, true>(tmp, tmp_bytes, LoadU32{in}, out, n, stream);
 }
 
-// out has n+1 entries: the caller keeps in[n] = 0, so out[n] is the total
+// out has n+1 entries and n+1 inputs are scanned: in[n] is read (its value reaches no output), out[n] is the total
 hipError_t scan_sum_exclusive_u32_u64(void* tmp, size_t& tmp_bytes, const uint32_t* in, uint64_t* out, size_t n, hipStream_t stream) {
     return scan_impl<SumU64, LoadU32As64, LoadU64, false>(tmp, tmp_bytes, LoadU32As64{in}, out, n + 1, stream);
 }
