@@ -531,7 +531,7 @@ int aln_filter(void* ws, const FilterBatch& b, const FilterParams& args, slamem_
     slamem_mem* crows;
     uint64_t* coff;
     aln_chain_buffers(ws, b, args, &crows, &coff);
-    // the chains: [0] rows kept (replaced below), [1] the first block out of order + 1
+    // the chains: [0] rows kept (replaced below), [1] the highest-numbered block out of order + 1
     int rc = chain_pass(ws, b.num_blocks(), b.capacity, args.max_gap, nullptr, stream);
     if (rc == SLAMEM_OK) rc = chain_compact(ws, b.num_blocks(), b.capacity, crows, coff, host_scalars, stream);
     if (rc != SLAMEM_OK) return rc;
@@ -597,7 +597,7 @@ int aln_after_chain(void* ws, const FilterBatch& b, const FilterParams& args, ui
                        (const uint64_t*)sflag, (const uint64_t*)sn, (const uint64_t*)sed, (const uint32_t*)segstart, (const uint32_t*)slab,
                        args.ops_capacity, args.segs, args.segs_capacity, args.ops, args.ops_capacity, args.op_offsets);
     ASTEP(hipGetLastError(), "k_aln_write");
-    // [0] segments, [1] (chain_filter's) the first block out of order + 1, [2] operations
+    // [0] segments, [1] (chain_filter's) the highest-numbered block out of order + 1, [2] operations
     ASTEP(hipMemcpyAsync(host_scalars, sflag + capacity + 1, 8, hipMemcpyDeviceToHost, stream), "memcpy");
     ASTEP(hipMemcpyAsync(host_scalars + 2, sn + capacity + 1, 8, hipMemcpyDeviceToHost, stream), "memcpy");
     return SLAMEM_OK;

@@ -23,8 +23,8 @@
 //                       staged in LDS tile by tile, and the lanes set the keep flags
 //   scan                kept rows per block -> new block offsets (scan_sum_exclusive_u32_u64)
 //   k_filter_copy / k_chain_list_copy  the kept rows, in order (listed blocks: a wave ranks 64 rows at a time with a ballot)
-// Every row is checked against the one before it: a block out of the emission order fails the call (the first such block,
-// + 1, goes back with the batch's scalars) -- never wrong rows.
+// Every row is checked against the one before it: a block out of the emission order fails the call (the highest-numbered
+// such block, + 1, goes back with the batch's scalars: an atomic maximum) -- never wrong rows.
 #include "filter_blocks.h"
 
 namespace slamem {

@@ -353,7 +353,7 @@ struct FilterDesc {
     bool column_per_row;   // FilterParams::column_dev is per kept row, not per strand block
     bool segments;         // no rows go back (mems_dev may be null): segments and operations go where FilterParams says
     bool needs_reads;      // ... and a record per read to FilterParams::reads
-    int scalars;           // host scalars it returns: [0] rows kept (-aln, -paf: segments), [1] the first block out of order + 1, [2] operations
+    int scalars;           // host scalars it returns: [0] rows kept (-aln, -paf: segments), [1] the highest-numbered block out of order + 1, [2] operations
     uint64_t (*workspace_bytes)(const FilterBatch&, const FilterParams&);
     // all on the stream, host_scalars copied asynchronously
     int (*run)(void* ws, const FilterBatch&, const FilterParams&, slamem_mem* out_mems, uint64_t* out_boff, unsigned long long* host_scalars,

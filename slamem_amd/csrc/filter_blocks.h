@@ -115,7 +115,7 @@ inline hipError_t compact_kept(const FilterBufs& w, uint64_t num_blocks, uint64_
     return hipGetLastError();
 }
 
-// host_scalars[0] = rows kept, [1] = *second (the first block out of the emission order + 1, 0: none; -mum: its large blocks)
+// host_scalars[0] = rows kept, [1] = *second (the highest-numbered block out of the emission order + 1, 0: none; -mum: its large blocks)
 inline hipError_t kept_scalars(const FilterBufs& w, uint64_t num_blocks, const unsigned long long* second, unsigned long long* host_scalars,
                                hipStream_t stream) {
     const hipError_t e = hipMemcpyAsync(host_scalars, w.newoff + num_blocks, 8, hipMemcpyDeviceToHost, stream);

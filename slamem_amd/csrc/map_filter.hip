@@ -162,7 +162,7 @@ int map_filter(void* ws, const FilterBatch& bt, const FilterParams& args, slamem
     hipLaunchKernelGGL(k_map_pick, dim3(grid_for(num_queries)), dim3(256), 0, stream, num_queries, strands, (const uint32_t*)a.score,
                        (const uint32_t*)b.score, a.cnt, args.reads);
     MSTEP(hipGetLastError(), "k_map_pick");
-    // [0] rows kept (replaced below), [1] the first block out of order + 1
+    // [0] rows kept (replaced below), [1] the highest-numbered block out of order + 1
     rc = chain_compact(ws, num_blocks, capacity, crows, coff, host_scalars, stream);
     if (rc != SLAMEM_OK) return rc;
     rc = aln_after_chain(ws, bt, args, seg_boff, host_scalars, stream);

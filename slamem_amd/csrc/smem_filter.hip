@@ -22,8 +22,8 @@
 //                       of the threads' aggregates, the running value carried from tile to tile
 //   scan                kept rows per block -> new block offsets (scan_sum_exclusive_u32_u64)
 //   k_filter_copy / k_smem_large_copy the kept rows, in order (large blocks: tiles ranked by a workgroup scan)
-// Every row is checked against the one before it (one compare): a block out of that order fails the call (the first such
-// block, + 1, goes back with the batch's scalars) -- never wrong rows.
+// Every row is checked against the one before it (one compare): a block out of that order fails the call (the highest-numbered
+// such block, + 1, goes back with the batch's scalars: an atomic maximum) -- never wrong rows.
 #include "filter_blocks.h"
 
 namespace slamem {
