@@ -559,6 +559,43 @@ int slamem_pileup_add_events_host(slamem_pileup *pile, const slamem_event *event
 int slamem_pileup_rows_at_device(slamem_pileup *pile, const uint64_t *pos_dev, uint64_t m, uint32_t *out_dev, void *stream);
 int slamem_pileup_rows_at_host(slamem_pileup *pile, const uint64_t *pos, uint64_t m, uint32_t *out);
 
+/* ---- (b''''') the consensus sequence of the pileup (option -cons) --------------------------------------------
+ * The text with the majority alleles applied, one byte per emitted letter.  cnt[p], L(p) and d(p) as above; ACGT(p): L(p) is one
+ * of A,C,G,T; E: the events as slamem_pileup_events_* reads them out with min_count 1, in its order (empty when events are not
+ * enabled); obs = fwd + rev in 64 bits.  The anchor row of an event at pos is a = pos - 1 if pos >= 1 and ACGT(pos - 1), else
+ * a = pos.  An event is applied iff ACGT(a), d(a) >= min_depth and 2 * obs > d(a).  Row p emits, in this order:
+ *   1. of the applied insertions with pos == p the one with the largest obs (a tie: the first in E's order): its len letters in
+ *      upper case -- also when rule 2 drops the row;
+ *   2. nothing more if an applied deletion covers p (pos <= p < pos + len);
+ *   3. else N if not ACGT(p);
+ *   4. else L(p) in lower case if d(p) < min_depth or A+C+G+T == 0 (the row is uncalled, the text is kept);
+ *   5. else in upper case the letter with the largest of the counters A,C,G,T; a tie: L(p) if its counter is among the largest,
+ *      else the first of the tied in the order A,C,G,T.
+ * The consensus of rows [first, first + count) is the concatenation of their emissions; a row's emission does not depend on the
+ * range (the anchor of an event at `first` may be row first - 1), so every range's output is a slice of the whole text's.  For
+ * m bounds in [first, first + count], offs[j] is the number of bytes that rows [first, bounds[j]) emit: an insertion in front of
+ * row bounds[j] lies behind offs[j].  stats: rows uncalled (rule 4), rows whose called letter differs from L(p) (rule 5), rows
+ * deleted (rule 2), insertions emitted, letters inserted.
+ *
+ *   slamem_pileup_consensus_device  asynchronous on `stream` up to the host round trip that brings the number of bytes to
+ *                          *total_out and the statistics to stats_out (host pointers); with events enabled the events' read-out
+ *                          in front of it makes its own (the sort needs the number of events on the host).  More than `capacity`
+ *                          bytes: SLAMEM_ERR_CAPACITY with the need in *total_out; the first `capacity` bytes are written and
+ *                          nothing beyond them; capacity 0 with a null buffer asks for the size.  offs is complete either way.
+ *                          bounds_dev may be null with m = 0; a bound outside the range gets UINT64_MAX.  A range outside [0, n],
+ *                          min_depth of 0 or of 2^31 and more: SLAMEM_ERR_ARG.  The accumulator and the events are not
+ *                          modified.  It shares the read-outs' scratch and keeps a byte per text letter of its own from the first
+ *                          call to slamem_pileup_free: two read-outs of one accumulator must not run at the same time, and none
+ *                          beside an add.
+ *   slamem_pileup_consensus_host  the same from and into host memory; waits for the device first.  A bound outside the range:
+ *                          SLAMEM_ERR_ARG. */
+int slamem_pileup_consensus_device(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t min_depth, uint64_t capacity,
+                                   uint8_t *out_dev, const uint64_t *bounds_dev, uint64_t m, uint64_t *offs_dev,
+                                   uint64_t *stats_out /* 5 */, uint64_t *total_out, void *stream);
+int slamem_pileup_consensus_host(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t min_depth, uint64_t capacity,
+                                 uint8_t *out, const uint64_t *bounds, uint64_t m, uint64_t *offs, uint64_t *stats_out /* 5 */,
+                                 uint64_t *total_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */

@@ -542,6 +542,38 @@ class Pileup:
                 torch.cuda.current_stream(dev).synchronize()
         return out[:m].cpu().numpy().view(np.uint32)
 
+    def consensus(self, min_depth: int = 4, first: int = 0, count=None, bounds=None, capacity=None):
+        """The consensus sequence of rows [first, first + count), built on the device, as (bytes uint8 (total,),
+        offs uint64 (m,), stats): the text with the majority alleles applied -- per row the plurality letter in upper case, the
+        text's letter in lower case where the depth A+C+G+T+D is below min_depth, N where the text has none of A,C,G,T, and the
+        indel events that more than half of their anchor row's depth show.  bounds: rows in [first, first + count]; offs[j] is
+        the number of bytes the rows in front of bounds[j] emit.  stats: rows uncalled, rows called unlike the text, rows deleted,
+        insertions emitted, letters inserted.  capacity: bytes of room for the first attempt (default: the range and a 64th, at
+        least 4,096); when the consensus is longer the call is made once more with the need it reported."""
+        first = int(first)
+        count = self.index.n - first if count is None else int(count)
+        dev = self.index.device
+        b = np.zeros(0, dtype=np.uint64) if bounds is None else np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64).reshape(-1))
+        m = len(b)
+        cap = max(4096, count + count // 64) if capacity is None else int(capacity)
+        total = C.c_uint64()
+        stats = (C.c_uint64 * 5)()
+        with torch.cuda.device(dev):
+            bd = torch.from_numpy(b.view(np.int64)).to(dev) if m else None
+            offs = torch.zeros(max(m, 1), dtype=torch.int64, device=dev)
+            for attempt in (0, 1):
+                out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+                rc = capi.lib().slamem_pileup_consensus_device(self._h, first, count, int(min_depth), cap, _ptr(out),
+                                                               _ptr(bd) if m else None, m, _ptr(offs) if m else None, stats,
+                                                               C.byref(total), _stream_handle(dev))
+                if rc != capi.SLAMEM_ERR_CAPACITY or attempt:
+                    break
+                cap = int(total.value)
+            capi.check(rc)
+            torch.cuda.current_stream(dev).synchronize()
+        t = int(total.value)
+        return out[:t].cpu().numpy(), offs[:m].cpu().numpy().view(np.uint64), [int(v) for v in stats]
+
     def reset(self) -> None:
         capi.check(capi.lib().slamem_pileup_reset(self._h))
 

@@ -595,6 +595,7 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-mdep\twith -sites: least depth A+C+G+T+D of a site (default=4)\n");
     printf("\t-mpct\twith -sites: least share of the depth a call needs, in percent, 0 to 100 (default=20)\n");
     printf("\t-vcf\tthe calls of the pileup as VCF 4.2: the SNVs of -sites and the reads' insertions and deletions as left-normalised events; -mgap, -pen, -xdrop, -maxed, -minq, -mdep, -mpct apply\n");
+    printf("\t-cons\tthe consensus sequence of the mapped reads as FASTA, a record per reference record: per position the plurality letter (lower case: the reference kept below the depth of -mdep), and the insertions and deletions that more than half of the reads show; -mgap, -pen, -xdrop, -maxed, -minq, -mdep, -evs apply\n");
     printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
@@ -623,6 +624,7 @@ int main(int argc, char **argv) {
     int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1, min_mapq = 0;
     int sites = 0, min_depth = 4, min_pct = 20; /* -sites: match type 8 with the sparse read-out */
     int vcf = 0;                                /* -vcf: match type 8 with the events enabled, written as VCF */
+    int cons = 0;                               /* -cons: match type 8 with the events enabled, the consensus written as FASTA */
     uint64_t ev_slots = 0;
     slamem_pileup *piles[16];
     double t0;
@@ -647,7 +649,9 @@ int main(int argc, char **argv) {
     }
     sites = slh_parse_argument(argc, argv, "SI", 0);
     vcf = slh_parse_argument(argc, argv, "VC", 0);
+    cons = slh_parse_argument(argc, argv, "CO", 0);
     if (o.match_type < 0) { /* before any GPU work */
+        if (cons) exit_message("Option -cons excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites and -vcf");
         if (vcf) exit_message("Option -vcf excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile and -sites");
         if (sites) exit_message("Option -sites excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf and -pile");
         if (slh_parse_argument(argc, argv, "PI", 0)) exit_message("Option -pile excludes -mam, -mum, -smem, -chain, -ext, -aln and -paf");
@@ -686,12 +690,15 @@ int main(int argc, char **argv) {
     switch (slh_parse_sites_params(argc, argv, &min_depth, &min_pct)) {
     case -1: exit_message("Option -mdep needs a whole number of at least 1"); break;
     case -2: exit_message("Option -mpct needs a whole number from 0 to 100"); break;
-    case 1: if (!sites && !vcf) exit_message("Options -mdep and -mpct need -sites"); break;
+    case 1:
+        if (cons && slh_parse_argument(argc, argv, "MP", 0)) exit_message("Option -mpct has no meaning with -cons: an allele is applied when more than half of the depth shows it");
+        if (!sites && !vcf && !cons) exit_message("Options -mdep and -mpct need -sites");
+        break;
     default: break;
     }
     switch (slh_parse_event_slots(argc, argv, &ev_slots)) {
     case -1: exit_message("Option -evs needs a power of two of at least 64"); break;
-    case 1: if (!vcf) exit_message("Option -evs needs -vcf"); break;
+    case 1: if (!vcf && !cons) exit_message("Option -evs needs -vcf"); break;
     default: break;
     }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
@@ -804,6 +811,7 @@ int main(int argc, char **argv) {
             ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
     if (o.match_type == 8) say(" ; minimum mapping quality = %d", min_mapq);
     if (sites || vcf) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
+    if (cons) say(" ; minimum depth = %d", min_depth);
     say("\n");
     out = fopen(out_name, "w");
     if (!out) {
@@ -959,7 +967,7 @@ int main(int argc, char **argv) {
             if (rc == SLAMEM_OK && o.match_type == 8) { /* one accumulator per GPU: the tables are added when the file is written */
                 g_nstreams = g + 1;
                 rc = slamem_pileup_create(gpus[g], &piles[g]);
-                if (rc == SLAMEM_OK && vcf) rc = slamem_pileup_enable_events(piles[g], ev_slots);
+                if (rc == SLAMEM_OK && (vcf || cons)) rc = slamem_pileup_enable_events(piles[g], ev_slots);
                 if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(g_streams[g], piles[g], (uint32_t)min_mapq);
             }
             if (rc == SLAMEM_OK && (o.match_type == 6 || o.match_type == 7 || o.match_type == 8)) {
@@ -1133,7 +1141,7 @@ int main(int argc, char **argv) {
             remove(out_name);
             exit_message("No query files provided");
         }
-        if (o.match_type == 8 && (sites || vcf)) {
+        if (o.match_type == 8 && (sites || vcf || cons)) {
             /* the tables of GPUs 1.. are added into GPU 0's, in chunks of 16 M rows; then GPU 0 applies the rule to the sum range
                after range and only the selected rows come back: a line each, the separators between records skipped */
             const uint64_t chunk = 16ull << 20, n = ref.total;
@@ -1160,7 +1168,7 @@ int main(int argc, char **argv) {
                 free(rows);
                 rows = NULL;
             }
-            for (g = 1; vcf && g < g_nstreams; g++) { /* ... and their events, which arrive normalised and stay as they are */
+            for (g = 1; (vcf || cons) && g < g_nstreams; g++) { /* ... and their events, which arrive normalised and stay as they are */
                 for (x0 = 0; x0 < n; x0 += chunk) {
                     const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
                     uint64_t total = 0;
@@ -1177,7 +1185,7 @@ int main(int argc, char **argv) {
                 }
                 skipped[0] += sk[0]; skipped[1] += sk[1]; skipped[2] += sk[2]; /* (what GPU g could not store) */
             }
-            for (x0 = 0; g_nstreams > 0 && x0 < n; x0 += chunk) {
+            for (x0 = 0; !cons && g_nstreams > 0 && x0 < n; x0 += chunk) {
                 const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
                 uint64_t total = 0, k = 0;
                 for (;;) { /* a range that selects more rows than there is room for says how many: once more with that room */
@@ -1254,9 +1262,65 @@ int main(int argc, char **argv) {
                 if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
                 if (g_writer.failed) pipeline_fail("Cannot write output file");
             }
+            if (cons && g_nstreams > 0) {
+                /* -cons: GPU 0 builds the consensus of the summed table and events range after range; the bounds cut it at the
+                   records' first rows and ends (a separator's row, and an insertion in front of it, is no record's), and a record
+                   is written when its last piece is there */
+                uint64_t ccap = (chunk < n ? chunk : n) + (chunk < n ? chunk : n) / 64 + 64, rlen = 0, rcap = 0, stats[5] = {0, 0, 0, 0, 0};
+                uint64_t *bnd = (uint64_t *)malloc(((size_t)ref.num * 2 + 2) * 16), *offs, none = 0;
+                uint8_t *seq = NULL;
+                char *rec = NULL;
+                if (!bnd) pipeline_fail("Out of memory");
+                offs = bnd + (size_t)ref.num * 2 + 2;
+                for (x0 = 0; x0 < n; x0 += chunk) {
+                    const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
+                    uint64_t total = 0, st[5], m = 0, j;
+                    int rr;
+                    for (rr = r; rr < ref.num; rr++) { /* the pieces of the records inside the range */
+                        const uint64_t start = ref.num > 1 ? ref.merged_start[rr] : 0, end = start + ref.recs[rr].size;
+                        if (start >= x0 + cnt) break;
+                        bnd[m++] = start > x0 ? start : x0;
+                        bnd[m++] = end < x0 + cnt ? end : x0 + cnt;
+                        if (end > x0 + cnt) break;
+                    }
+                    for (;;) {
+                        if (!seq && !(seq = (uint8_t *)slh_big_malloc((size_t)ccap))) pipeline_fail("Out of memory");
+                        rc = slamem_pileup_consensus_host(piles[0], x0, cnt, (uint32_t)min_depth, ccap, seq, bnd, m, offs, st, &total);
+                        if (rc != SLAMEM_ERR_CAPACITY || total <= ccap) break;
+                        free(seq);
+                        seq = NULL;
+                        ccap = total;
+                    }
+                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the consensus from the GPU", rc); }
+                    for (j = 0; j < 5; j++) stats[j] += st[j];
+                    for (j = 0; j < m; j += 2) {
+                        const uint64_t end = (ref.num > 1 ? ref.merged_start[r] : 0) + ref.recs[r].size, got = offs[j + 1] - offs[j];
+                        if (rlen + got > rcap) {
+                            char *more;
+                            rcap = (rlen + got) * 2 + 64;
+                            if (!(more = (char *)realloc(rec, (size_t)rcap))) pipeline_fail("Out of memory");
+                            rec = more;
+                        }
+                        if (got) memcpy(rec + rlen, seq + offs[j], (size_t)got);
+                        rlen += got;
+                        if (bnd[j + 1] < end) break; /* (the record goes on in the next range) */
+                        if (slh_format_fasta_record(&buf, ref.recs[r].name, rec ? rec : "", rlen)) pipeline_fail("Out of memory");
+                        rlen = 0;
+                        r++;
+                    }
+                    if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
+                    if (g_writer.failed) pipeline_fail("Cannot write output file");
+                }
+                free(bnd); free(seq); free(rec);
+                fprintf(stderr, "> Consensus: %llu positions uncalled, %llu called unlike the reference, %llu deleted, %llu insertions of %llu letters\n",
+                        (unsigned long long)stats[0], (unsigned long long)stats[1], (unsigned long long)stats[2], (unsigned long long)stats[3],
+                        (unsigned long long)stats[4]);
+                rc = slamem_pileup_events_host(piles[0], 0, 0, 1, 0, NULL, sk, &none); /* (no event: GPU 0's skipped counters) */
+                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the indel events from the GPU", rc); }
+            }
             free(pos); free(rows); free(alleles);
             free(evs); free(anchors); free(arows);
-            if (vcf && g_nstreams > 0) {
+            if ((vcf || cons) && g_nstreams > 0) {
                 skipped[0] += sk[0]; skipped[1] += sk[1]; skipped[2] += sk[2]; /* (GPU 0's, the merge included) */
                 if (skipped[0] | skipped[1] | skipped[2])
                     fprintf(stderr, "> WARNING: indel observations that are in no event: %llu insertions of more than 31 letters, %llu without "
@@ -1319,7 +1383,7 @@ int main(int argc, char **argv) {
                (int)(total_matches / total_queries), MATCH_NAME(o.match_type), total_matches,
                (int)(total_matches ? total_sum / total_matches : 0));
     fflush(stdout);
-    printf("> Saving %ss to <%s> ... ", vcf ? "variant call" : sites ? "variant site" : MATCH_NAME(o.match_type), out_name);
+    printf("> Saving %ss to <%s> ... ", cons ? "consensus sequence" : vcf ? "variant call" : sites ? "variant site" : MATCH_NAME(o.match_type), out_name);
     if (fflush(out) != 0 || ferror(out)) exit_message("Cannot write output file");
     if (getenv("SLAMEM_FULL_TEARDOWN") != NULL && fclose(out) != 0) exit_message("Cannot write output file");
     t_end1 = now_s();

@@ -910,6 +910,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type != 0 ? -1 : 8;
     if (slh_parse_argument(argc, argv, "VC", 0)) /* -vcf: the calls of the pileup as VCF: match type 8 with the events enabled and a third read-out */
         o->match_type = o->match_type != 0 ? -1 : 8;
+    if (slh_parse_argument(argc, argv, "CO", 0)) /* -cons: the consensus of the pileup as FASTA: match type 8 with the events enabled and a fourth read-out (a 'c' option takes no value) */
+        o->match_type = o->match_type != 0 ? -1 : 8;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
     if (o->min_mem_len == -1) o->min_mem_len = 20;
@@ -1063,6 +1065,26 @@ int slh_format_vcf_header(slh_buffer *buf, const slh_record *refs, int num_refs)
     if (buf_reserve(buf, strlen(INFO))) return -1;
     memcpy(buf->data + buf->len, INFO, strlen(INFO));
     buf->len += strlen(INFO);
+    return 0;
+}
+
+int slh_format_fasta_record(slh_buffer *buf, const char *record_name, const char *letters, uint64_t len) {
+    const size_t nl = cut_name_len(record_name);
+    uint64_t i;
+    char *p;
+    if (buf_reserve(buf, nl + 2 + (size_t)len + (size_t)(len / 60) + 2)) return -1;
+    p = buf->data + buf->len;
+    *p++ = '>';
+    memcpy(p, record_name, nl);
+    p += nl;
+    *p++ = '\n';
+    for (i = 0; i < len; i += 60) {
+        const size_t k = (size_t)(len - i < 60 ? len - i : 60);
+        memcpy(p, letters + i, k);
+        p += k;
+        *p++ = '\n';
+    }
+    buf->len = (size_t)(p - buf->data);
     return 0;
 }
 

@@ -173,6 +173,9 @@ int slh_format_vcf_rows(slh_buffer *buf, const char *record_name, uint64_t recor
                         const uint64_t *site_pos, const uint32_t *site_counts, const uint8_t *site_alleles, uint64_t sites,
                         const slh_event *events, const uint32_t *anchor_rows, uint64_t num_events, uint32_t min_depth,
                         uint32_t min_pct);
+/* -cons: one FASTA record -- '>' and the record's name up to its first blank or tab, then `len` letters in lines of 60; a record
+ * of no letters is its header line alone */
+int slh_format_fasta_record(slh_buffer *buf, const char *record_name, const char *letters, uint64_t len);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
