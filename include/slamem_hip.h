@@ -596,6 +596,41 @@ int slamem_pileup_consensus_host(slamem_pileup *pile, uint64_t first, uint64_t c
                                  uint8_t *out, const uint64_t *bounds, uint64_t m, uint64_t *offs, uint64_t *stats_out /* 5 */,
                                  uint64_t *total_out);
 
+/* ---- (b'''''') the depth of coverage as runs (option -depth) -------------------------------------------------
+ * d(p) as above, the 64-bit sum of row p's first five counters as slamem_pileup_counts_* gives them.  Levels t_1 < ... < t_k
+ * (k from 0 to 16, each at least 1, strictly ascending; a host array): the value of a row is v(p) = d(p) when k == 0, else the
+ * number of i with t_i <= d(p), 0 to k.  Row p of the range [first, first + count) is a head iff p == first or v(p) != v(p - 1).
+ * The result is the heads in ascending p as records {pos, value}: run i spans [pos[i], pos[i + 1]), the last one ends at
+ * first + count, an empty range has no run, runs of depth 0 are runs like the others -- the runs tile the range.  Head-ness
+ * depends on v(p) and v(p - 1) alone, so the runs of any range are the whole text's runs clipped to it.  For m bounds, non-
+ * decreasing in [first, first + count], cum[j] is the pair (sum of d(p), number of p with d(p) >= min_depth) over rows
+ * first <= p < bounds[j]; a range's cum differs from the whole text's by the constant pair at `first`.
+ *
+ *   slamem_pileup_depth_runs_device  asynchronous on `stream` up to the one host round trip that brings the number of runs to
+ *                          *total_out (a host pointer).  More than `capacity` runs: SLAMEM_ERR_CAPACITY with the need in
+ *                          *total_out; the first `capacity` runs are written and nothing beyond them; capacity 0 with a null
+ *                          buffer asks for the size.  cum is complete either way.  bounds_dev may be null with m = 0; bounds
+ *                          outside the range or descending get unspecified cum entries, and nothing outside the buffers is
+ *                          accessed.  SLAMEM_ERR_ARG: a range outside [0, n], more than 16 levels, a level of 0 or levels that do
+ *                          not ascend strictly, min_depth of 0 or of 2^31 and more, a null pile or total_out.  The accumulator is
+ *                          not modified.  It shares the read-outs' tile sums and keeps three numbers per tile of its own from the
+ *                          first call to slamem_pileup_free: two read-outs of one accumulator must not run at the same time, and
+ *                          none beside an add.
+ *   slamem_pileup_depth_runs_host  the same from and into host memory; waits for the device first.  A bound outside the range or
+ *                          smaller than the bound in front of it: SLAMEM_ERR_ARG. */
+typedef struct {
+    uint64_t pos;   /* the run's first row */
+    uint64_t value; /* d of its rows, or with levels the number of levels they reach */
+} slamem_depth_run;
+
+int slamem_pileup_depth_runs_device(slamem_pileup *pile, uint64_t first, uint64_t count, const uint32_t *levels /* host */,
+                                    uint32_t num_levels, uint32_t min_depth, uint64_t capacity, slamem_depth_run *runs_dev,
+                                    const uint64_t *bounds_dev, uint64_t m, uint64_t *cum_dev /* 2 m */, uint64_t *total_out,
+                                    void *stream);
+int slamem_pileup_depth_runs_host(slamem_pileup *pile, uint64_t first, uint64_t count, const uint32_t *levels, uint32_t num_levels,
+                                  uint32_t min_depth, uint64_t capacity, slamem_depth_run *runs, const uint64_t *bounds, uint64_t m,
+                                  uint64_t *cum /* 2 m */, uint64_t *total_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */

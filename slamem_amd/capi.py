@@ -53,7 +53,7 @@ ABI_SYMBOLS = (
     "slamem_pileup_sites_device", "slamem_pileup_sites_host", "slamem_pileup_add_counts_device", "slamem_pileup_add_counts_host",
     "slamem_pileup_enable_events", "slamem_pileup_events_device", "slamem_pileup_events_host", "slamem_pileup_add_events_device",
     "slamem_pileup_add_events_host", "slamem_pileup_rows_at_device", "slamem_pileup_rows_at_host",
-    "slamem_pileup_consensus_device", "slamem_pileup_consensus_host",
+    "slamem_pileup_consensus_device", "slamem_pileup_consensus_host", "slamem_pileup_depth_runs_device", "slamem_pileup_depth_runs_host",
     "slamem_stream_create", "slamem_stream_set_max_occ", "slamem_stream_set_max_gap", "slamem_stream_submit", "slamem_stream_submit_packed", "slamem_pack_reads", "slamem_stream_next",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
@@ -204,6 +204,8 @@ def _declare(L):
     L.slamem_pileup_rows_at_host.argtypes = [vp, vp, u64, vp]
     L.slamem_pileup_consensus_device.argtypes = [vp, u64, u64, u32, u64, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), vp]
     L.slamem_pileup_consensus_host.argtypes = [vp, u64, u64, u32, u64, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.slamem_pileup_depth_runs_device.argtypes = [vp, u64, u64, vp, u32, u32, u64, vp, vp, u64, vp, C.POINTER(u64), vp]
+    L.slamem_pileup_depth_runs_host.argtypes = [vp, u64, u64, vp, u32, u32, u64, vp, vp, u64, vp, C.POINTER(u64)]
     L.slamem_stream_set_pileup.argtypes = [vp, vp, u32]
     L.slamem_stream_mismatches.argtypes = [vp, C.POINTER(C.POINTER(u32))]
     L.slamem_stream_submit.argtypes = [vp, vp, vp, u32, u32]

@@ -479,7 +479,7 @@ int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
     slamem_pileup* p = new (std::nothrow) slamem_pileup();
     if (!p) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     p->idx = idx; p->device = idx->device; p->n = (uint32_t)n;
-    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr; p->cons = nullptr;
+    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr; p->cons = nullptr; p->depth = nullptr;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->diff), (n + 1) * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->cnt), n * 24 + 16);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->tile), tiles * 4);
@@ -504,6 +504,7 @@ int slamem_pileup_free(slamem_pileup* p) {
     if (p->sel) (void)hipFree(p->sel);
     events_free(p);
     cons_free(p);
+    depth_free(p);
     delete p;
     return SLAMEM_OK;
 }

@@ -1,5 +1,5 @@
 // pile_shared.h -- what pile_filter.hip (-pile and -sites), event_filter.hip (the indel events of -vcf,
-// DESIGN.md 4.18) and cons_filter.hip (the consensus of -cons) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
+// DESIGN.md 4.18), cons_filter.hip (the consensus of -cons) and depth_filter.hip (the runs of -depth) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
 // segments (letters of the scanned strand, the steps of an operation), and the two entry points of the read-out's scratch that
 // the event side borrows.
 #pragma once
@@ -9,6 +9,7 @@ namespace slamem {
 
 struct EvTable;  // event_filter.hip: the hash table of the indel events, its counters and its read-out's scratch
 struct ConsScratch;  // cons_filter.hip: the consensus read-out's scratch (a flag byte per row, the sorted events and their marks)
+struct DepthScratch;  // depth_filter.hip: the depth read-out's scratch (three numbers per tile)
 
 }  // namespace slamem
 
@@ -22,6 +23,7 @@ struct slamem_pileup {
     uint64_t* sel;   // the sparse read-out's selected rows per tile: n / kPileTile + 2 words of 64 bits
     slamem::EvTable* ev;  // nullptr: events are not enabled
     slamem::ConsScratch* cons;  // nullptr: no consensus was read yet
+    slamem::DepthScratch* depth;  // nullptr: no depth runs were read yet
 };
 
 namespace slamem {
@@ -110,5 +112,8 @@ void events_free(slamem_pileup* pile);
 
 // cons_filter.hip, for pile_filter.hip: what free does to the consensus read-out's scratch
 void cons_free(slamem_pileup* pile);
+
+// depth_filter.hip, for pile_filter.hip: what free does to the depth read-out's scratch
+void depth_free(slamem_pileup* pile);
 
 }  // namespace slamem

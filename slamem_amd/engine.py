@@ -574,6 +574,38 @@ class Pileup:
         t = int(total.value)
         return out[:t].cpu().numpy(), offs[:m].cpu().numpy().view(np.uint64), [int(v) for v in stats]
 
+    def depth_runs(self, levels=None, min_depth: int = 1, first: int = 0, count=None, bounds=None, capacity=None):
+        """The depth of coverage d = A+C+G+T+D of rows [first, first + count) as runs, built on the device, as
+        (pos uint64 (r,), value uint64 (r,), cum uint64 (m, 2)): run i spans rows [pos[i], pos[i + 1]), the last one ends at
+        first + count, runs of depth 0 included.  levels: up to 16 ascending depths of at least 1; the value of a run is then the
+        number of levels its depth reaches, without levels the depth itself.  bounds: non-decreasing rows in
+        [first, first + count]; cum[j] is (the sum of d, the rows with d >= min_depth) over the rows in front of bounds[j].
+        capacity: runs of room for the first attempt (default: one in 8 of the range, at least 4,096); when there are more the
+        call is made once more with the need it reported."""
+        first = int(first)
+        count = self.index.n - first if count is None else int(count)
+        dev = self.index.device
+        lv = np.zeros(0, dtype=np.uint32) if levels is None else np.ascontiguousarray(np.asarray(levels, dtype=np.uint32).reshape(-1))
+        b = np.zeros(0, dtype=np.uint64) if bounds is None else np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64).reshape(-1))
+        m = len(b)
+        cap = max(4096, count // 8) if capacity is None else int(capacity)
+        total = C.c_uint64()
+        with torch.cuda.device(dev):
+            bd = torch.from_numpy(b.view(np.int64)).to(dev) if m else None
+            cum = torch.zeros((max(m, 1), 2), dtype=torch.int64, device=dev)
+            for attempt in (0, 1):
+                out = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
+                rc = capi.lib().slamem_pileup_depth_runs_device(self._h, first, count, lv.ctypes.data if len(lv) else None, len(lv),
+                                                                int(min_depth), cap, _ptr(out), _ptr(bd) if m else None, m,
+                                                                _ptr(cum) if m else None, C.byref(total), _stream_handle(dev))
+                if rc != capi.SLAMEM_ERR_CAPACITY or attempt:
+                    break
+                cap = int(total.value)
+            capi.check(rc)
+            torch.cuda.current_stream(dev).synchronize()
+        runs = out[:int(total.value)].cpu().numpy().view(np.uint64)
+        return np.ascontiguousarray(runs[:, 0]), np.ascontiguousarray(runs[:, 1]), cum[:m].cpu().numpy().view(np.uint64)
+
     def reset(self) -> None:
         capi.check(capi.lib().slamem_pileup_reset(self._h))
 

@@ -596,6 +596,7 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-mpct\twith -sites: least share of the depth a call needs, in percent, 0 to 100 (default=20)\n");
     printf("\t-vcf\tthe calls of the pileup as VCF 4.2: the SNVs of -sites and the reads' insertions and deletions as left-normalised events; -mgap, -pen, -xdrop, -maxed, -minq, -mdep, -mpct apply\n");
     printf("\t-cons\tthe consensus sequence of the mapped reads as FASTA, a record per reference record: per position the plurality letter (lower case: the reference kept below the depth of -mdep), and the insertions and deletions that more than half of the reads show; -mgap, -pen, -xdrop, -maxed, -minq, -mdep, -evs apply\n");
+    printf("\t-depth\tthe depth of coverage A+C+G+T+D of the mapped reads as a bedGraph: record, start, end (0-based, half-open) and the depth of each run of equal depth, the runs of depth 0 included; -mgap, -pen, -xdrop, -maxed, -minq apply; -mdep N: the depth from which a position counts as covered in the summary on stderr (default=1); -lev LIST: comma-separated ascending depths, the value of a run is the number of them it reaches; -win N: instead of the runs the mean depth of every N positions\n");
     printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
@@ -625,6 +626,9 @@ int main(int argc, char **argv) {
     int sites = 0, min_depth = 4, min_pct = 20; /* -sites: match type 8 with the sparse read-out */
     int vcf = 0;                                /* -vcf: match type 8 with the events enabled, written as VCF */
     int cons = 0;                               /* -cons: match type 8 with the events enabled, the consensus written as FASTA */
+    int depth = 0, num_levels = 0, sites_params; /* -depth: match type 8, the runs of the depth written as a bedGraph */
+    uint32_t levels[16];
+    uint64_t window = 0;
     uint64_t ev_slots = 0;
     slamem_pileup *piles[16];
     double t0;
@@ -650,7 +654,9 @@ int main(int argc, char **argv) {
     sites = slh_parse_argument(argc, argv, "SI", 0);
     vcf = slh_parse_argument(argc, argv, "VC", 0);
     cons = slh_parse_argument(argc, argv, "CO", 0);
+    depth = slh_parse_argument(argc, argv, "DE", 0);
     if (o.match_type < 0) { /* before any GPU work */
+        if (depth) exit_message("Option -depth excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites, -vcf and -cons");
         if (cons) exit_message("Option -cons excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites and -vcf");
         if (vcf) exit_message("Option -vcf excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile and -sites");
         if (sites) exit_message("Option -sites excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf and -pile");
@@ -687,14 +693,25 @@ int main(int argc, char **argv) {
     case 1: if (o.match_type != 8) exit_message("Option -minq needs -pile"); break;
     default: break;
     }
-    switch (slh_parse_sites_params(argc, argv, &min_depth, &min_pct)) {
+    switch ((sites_params = slh_parse_sites_params(argc, argv, &min_depth, &min_pct))) {
     case -1: exit_message("Option -mdep needs a whole number of at least 1"); break;
     case -2: exit_message("Option -mpct needs a whole number from 0 to 100"); break;
     case 1:
         if (cons && slh_parse_argument(argc, argv, "MP", 0)) exit_message("Option -mpct has no meaning with -cons: an allele is applied when more than half of the depth shows it");
-        if (!sites && !vcf && !cons) exit_message("Options -mdep and -mpct need -sites");
+        if (depth && slh_parse_argument(argc, argv, "MP", 0)) exit_message("Option -mpct has no meaning with -depth: the depth is written as it is");
+        if (!sites && !vcf && !cons && !depth) exit_message("Options -mdep and -mpct need -sites");
         break;
     default: break;
+    }
+    if (depth && sites_params == 0) min_depth = 1; /* (-depth: a position is covered when one read shows it) */
+    switch (slh_parse_depth_params(argc, argv, levels, &num_levels, &window)) {
+    case -1: exit_message("Option -lev needs 1 to 16 whole numbers of at least 1, ascending, separated by commas"); break;
+    case -2: exit_message("Option -win needs a whole number of at least 1"); break;
+    case 0: break;
+    case 3:
+        if (depth) exit_message("Options -lev and -win exclude each other");
+        /* fall through */
+    default: if (!depth) exit_message("Options -lev and -win need -depth"); break;
     }
     switch (slh_parse_event_slots(argc, argv, &ev_slots)) {
     case -1: exit_message("Option -evs needs a power of two of at least 64"); break;
@@ -812,6 +829,7 @@ int main(int argc, char **argv) {
     if (o.match_type == 8) say(" ; minimum mapping quality = %d", min_mapq);
     if (sites || vcf) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
     if (cons) say(" ; minimum depth = %d", min_depth);
+    if (depth) say(" ; covered from depth = %d", min_depth);
     say("\n");
     out = fopen(out_name, "w");
     if (!out) {
@@ -1141,7 +1159,7 @@ int main(int argc, char **argv) {
             remove(out_name);
             exit_message("No query files provided");
         }
-        if (o.match_type == 8 && (sites || vcf || cons)) {
+        if (o.match_type == 8 && (sites || vcf || cons || depth)) {
             /* the tables of GPUs 1.. are added into GPU 0's, in chunks of 16 M rows; then GPU 0 applies the rule to the sum range
                after range and only the selected rows come back: a line each, the separators between records skipped */
             const uint64_t chunk = 16ull << 20, n = ref.total;
@@ -1185,7 +1203,7 @@ int main(int argc, char **argv) {
                 }
                 skipped[0] += sk[0]; skipped[1] += sk[1]; skipped[2] += sk[2]; /* (what GPU g could not store) */
             }
-            for (x0 = 0; !cons && g_nstreams > 0 && x0 < n; x0 += chunk) {
+            for (x0 = 0; !cons && !depth && g_nstreams > 0 && x0 < n; x0 += chunk) {
                 const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
                 uint64_t total = 0, k = 0;
                 for (;;) { /* a range that selects more rows than there is room for says how many: once more with that room */
@@ -1318,6 +1336,81 @@ int main(int argc, char **argv) {
                 rc = slamem_pileup_events_host(piles[0], 0, 0, 1, 0, NULL, sk, &none); /* (no event: GPU 0's skipped counters) */
                 if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the indel events from the GPU", rc); }
             }
+            if (depth && g_nstreams > 0) {
+                /* -depth: GPU 0 turns the summed table into runs of equal depth range after range; the bounds are the first rows
+                   and the ends of the records' pieces inside the range (a separator's row is no record's) and with -win the
+                   windows' borders between them, and cum at the bounds gives the windows' means and the records' summaries */
+                uint64_t dcap = window ? 0 : 1ull << 20, bcap = 0, *bnd = NULL, *cum = NULL;
+                uint64_t rec_sum = 0, rec_cov = 0, wacc = 0; /* of record r so far; -win: of its window that is still open */
+                slamem_depth_run *runs = NULL;
+                slh_depth_pending pend = {0, 0, 0, 0};
+                slh_buffer sbuf = {0, 0, 0};
+                for (x0 = 0; x0 < n; x0 += chunk) {
+                    const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
+                    uint64_t total = 0, m = 0, j;
+                    int rr;
+                    for (rr = r; rr < ref.num; rr++) { /* the pieces of the records inside the range */
+                        const uint64_t start = ref.num > 1 ? ref.merged_start[rr] : 0, end = start + ref.recs[rr].size;
+                        const uint64_t a = start > x0 ? start : x0, b = end < x0 + cnt ? end : x0 + cnt;
+                        const uint64_t inside = window && b > a ? (b - start - 1) / window - (a - start) / window : 0;
+                        if (start >= x0 + cnt) break;
+                        if (m + inside + 2 > bcap) {
+                            uint64_t *more;
+                            bcap = (m + inside + 2) * 2;
+                            if (!(more = (uint64_t *)realloc(bnd, (size_t)bcap * 8))) pipeline_fail("Out of memory");
+                            bnd = more;
+                        }
+                        bnd[m++] = a;
+                        for (j = 1; j <= inside; j++) bnd[m++] = start + ((a - start) / window + j) * window;
+                        bnd[m++] = b;
+                        if (end > x0 + cnt) break;
+                    }
+                    free(cum);
+                    if (!(cum = (uint64_t *)malloc((size_t)(m + 1) * 16))) pipeline_fail("Out of memory");
+                    for (;;) { /* a range of more runs than there is room for says how many: once more with that room */
+                        if (dcap && !runs && !(runs = (slamem_depth_run *)slh_big_malloc((size_t)dcap * sizeof(slamem_depth_run))))
+                            pipeline_fail("Out of memory");
+                        rc = slamem_pileup_depth_runs_host(piles[0], x0, cnt, levels, (uint32_t)num_levels, (uint32_t)min_depth, dcap, runs, bnd,
+                                                           m, cum, &total);
+                        if (window && rc == SLAMEM_ERR_CAPACITY) rc = SLAMEM_OK; /* (the windows need the sums alone) */
+                        if (rc != SLAMEM_ERR_CAPACITY || total <= dcap) break;
+                        free(runs);
+                        runs = NULL;
+                        dcap = total;
+                    }
+                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the depth runs from the GPU", rc); }
+                    for (j = 0; j < m;) {
+                        const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, size = ref.recs[r].size, end = start + size;
+                        const uint64_t a = bnd[j], ja = j;
+                        uint64_t b;
+                        for (j++; bnd[j] < end && bnd[j] < x0 + cnt; j++) {} /* (the piece's last bound: the record's end or the range's) */
+                        b = bnd[j];
+                        if (window) { /* the windows that end in the piece; what is behind the last of them waits for the next range */
+                            const uint64_t k = j - ja - (b == end || (b - start) % window == 0 ? 0 : 1);
+                            const uint64_t sum0 = cum[2 * ja] - wacc;
+                            if (slh_format_depth_windows(&buf, ref.recs[r].name, size, window, (a - start) / window, sum0, cum + 2 * (ja + 1), k))
+                                pipeline_fail("Out of memory");
+                            wacc = cum[2 * j] - (k ? cum[2 * (ja + k)] : sum0);
+                        } else if (slh_format_depth_runs(&buf, ref.recs[r].name, start, a, b, (const slh_depth_run *)runs, total, &pend)) {
+                            pipeline_fail("Out of memory");
+                        }
+                        rec_sum += cum[2 * j] - cum[2 * ja];
+                        rec_cov += cum[2 * j + 1] - cum[2 * ja + 1];
+                        j++;
+                        if (b < end) break; /* (the record goes on in the next range) */
+                        if (slh_format_depth_flush(&buf, ref.recs[r].name, &pend) ||
+                            slh_format_depth_summary(&sbuf, ref.recs[r].name, size, rec_cov, rec_sum))
+                            pipeline_fail("Out of memory");
+                        rec_sum = rec_cov = wacc = 0;
+                        r++;
+                    }
+                    if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
+                    if (g_writer.failed) pipeline_fail("Cannot write output file");
+                }
+                if (sbuf.len) fwrite(sbuf.data, 1, sbuf.len, stderr);
+                slh_buffer_free(&sbuf);
+                free(bnd); free(cum); free(runs);
+            }
             free(pos); free(rows); free(alleles);
             free(evs); free(anchors); free(arows);
             if ((vcf || cons) && g_nstreams > 0) {
@@ -1383,7 +1476,7 @@ int main(int argc, char **argv) {
                (int)(total_matches / total_queries), MATCH_NAME(o.match_type), total_matches,
                (int)(total_matches ? total_sum / total_matches : 0));
     fflush(stdout);
-    printf("> Saving %ss to <%s> ... ", cons ? "consensus sequence" : vcf ? "variant call" : sites ? "variant site" : MATCH_NAME(o.match_type), out_name);
+    printf("> Saving %ss to <%s> ... ", depth ? "depth run" : cons ? "consensus sequence" : vcf ? "variant call" : sites ? "variant site" : MATCH_NAME(o.match_type), out_name);
     if (fflush(out) != 0 || ferror(out)) exit_message("Cannot write output file");
     if (getenv("SLAMEM_FULL_TEARDOWN") != NULL && fclose(out) != 0) exit_message("Cannot write output file");
     t_end1 = now_s();

@@ -798,6 +798,46 @@ int slh_parse_event_slots(int argc, char **argv, uint64_t *out) {
     return 0;
 }
 
+int slh_parse_depth_params(int argc, char **argv, uint32_t *levels_out, int *num_levels_out, uint64_t *window_out) {
+    int i, seen = 0;
+    *num_levels_out = 0;
+    *window_out = 0;
+    for (i = 1; i < argc; i++) {
+        /* the two letters "le" and "wi" decide; both take the next argument ("-l" alone is the minimum match length) */
+        const int lev = two_letter_option(argv[i], 'l', 'e'), win = two_letter_option(argv[i], 'w', 'i');
+        const char *a;
+        char *end;
+        if (!lev && !win) continue;
+        if (i == argc - 1) return lev ? -1 : -2;
+        a = argv[i + 1];
+        if (win) {
+            unsigned long long v;
+            errno = 0;
+            v = strtoull(a, &end, 10);
+            if (errno != 0 || end == a || *end != '\0' || a[0] < '0' || a[0] > '9' || v < 1) return -2;
+            *window_out = (uint64_t)v;
+            seen |= 2;
+        } else {
+            int k = 0;
+            for (;;) { /* a number, then a comma and the next one, or the end */
+                unsigned long long v;
+                errno = 0;
+                v = strtoull(a, &end, 10);
+                if (errno != 0 || end == a || a[0] < '0' || a[0] > '9' || v < 1 || v > 0xFFFFFFFFull || k == 16) return -1;
+                if (k && (uint32_t)v <= levels_out[k - 1]) return -1;
+                levels_out[k++] = (uint32_t)v;
+                if (*end == '\0') break;
+                if (*end != ',') return -1;
+                a = end + 1;
+            }
+            *num_levels_out = k;
+            seen |= 1;
+        }
+        i++;
+    }
+    return seen;
+}
+
 char *slh_append_to_basename(const char *filename, const char *extra) {
     int n = (int)strlen(filename), i;
     char *res;
@@ -835,6 +875,7 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
             if (two_letter_option(argv[i], 'v', 'c')) {} /* -vcf takes no value ("-v" alone is the image tool and does) */
             else if (oc == 'l' || oc == 'o' || oc == 'm' || oc == 'v') i++; /* any option starting with l/o/m/v eats the next argument */
             else if (two_letter_option(argv[i], 'e', 'v')) i++; /* -evs N (of -vcf) */
+            else if (two_letter_option(argv[i], 'w', 'i')) i++; /* -win N (of -depth; its -lev LIST begins with l) */
             else if (two_letter_option(argv[i], 'p', 'e') || two_letter_option(argv[i], 'x', 'd')) i++; /* -pen N, -xdrop N (of -ext) */
             else if (oc == 'r') {
                 i++;
@@ -911,6 +952,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
     if (slh_parse_argument(argc, argv, "VC", 0)) /* -vcf: the calls of the pileup as VCF: match type 8 with the events enabled and a third read-out */
         o->match_type = o->match_type != 0 ? -1 : 8;
     if (slh_parse_argument(argc, argv, "CO", 0)) /* -cons: the consensus of the pileup as FASTA: match type 8 with the events enabled and a fourth read-out (a 'c' option takes no value) */
+        o->match_type = o->match_type != 0 ? -1 : 8;
+    if (slh_parse_argument(argc, argv, "DE", 0)) /* -depth: the depth of coverage as runs: match type 8 with a fifth read-out (a 'd' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 8;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
@@ -1084,6 +1127,108 @@ int slh_format_fasta_record(slh_buffer *buf, const char *record_name, const char
         p += k;
         *p++ = '\n';
     }
+    buf->len = (size_t)(p - buf->data);
+    return 0;
+}
+
+static inline char *put_u64(char *p, uint64_t v) {
+    char tmp[20];
+    int n = 20;
+    do { tmp[--n] = (char)('0' + v % 10); v /= 10; } while (v);
+    memcpy(p, tmp + n, (size_t)(20 - n));
+    return p + (20 - n);
+}
+
+/* 100 * num // den (0 when den is 0; the product in 128 bits) as whole "." two digits */
+static inline char *put_hundredths(char *p, uint64_t num, uint64_t den) {
+    const uint64_t q = den ? (uint64_t)((unsigned __int128)100 * num / den) : 0;
+    p = put_u64(p, q / 100);
+    *p++ = '.';
+    memcpy(p, DIGIT_PAIRS + 2 * (q % 100), 2);
+    return p + 2;
+}
+
+/* name TAB start TAB end TAB */
+static char *depth_line_head(char *p, const char *record_name, size_t nl, uint64_t start, uint64_t end) {
+    memcpy(p, record_name, nl);
+    p += nl;
+    *p++ = '\t';
+    p = put_u64(p, start);
+    *p++ = '\t';
+    p = put_u64(p, end);
+    *p++ = '\t';
+    return p;
+}
+
+int slh_format_depth_flush(slh_buffer *buf, const char *record_name, slh_depth_pending *pend) {
+    const size_t nl = cut_name_len(record_name);
+    char *p;
+    if (!pend->open) return 0;
+    if (buf_reserve(buf, nl + 72)) return -1;
+    p = depth_line_head(buf->data + buf->len, record_name, nl, pend->start, pend->end);
+    p = put_u64(p, pend->value);
+    *p++ = '\n';
+    buf->len = (size_t)(p - buf->data);
+    pend->open = 0;
+    return 0;
+}
+
+int slh_format_depth_runs(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t a, uint64_t b,
+                          const slh_depth_run *runs, uint64_t num_runs, slh_depth_pending *pend) {
+    uint64_t lo = 0, hi = num_runs, i;
+    if (a >= b) return 0;
+    while (hi - lo > 1) { /* the run that holds row a: the last one with pos <= a */
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (runs[mid].pos <= a) lo = mid; else hi = mid;
+    }
+    for (i = lo; i < num_runs && runs[i].pos < b; i++) {
+        const uint64_t s = (runs[i].pos > a ? runs[i].pos : a) - record_start;
+        const uint64_t e = (i + 1 < num_runs && runs[i + 1].pos < b ? runs[i + 1].pos : b) - record_start;
+        if (pend->open && pend->value == runs[i].value && pend->end == s) { /* (the run went on over the border of two ranges) */
+            pend->end = e;
+            continue;
+        }
+        if (slh_format_depth_flush(buf, record_name, pend)) return -1;
+        pend->start = s;
+        pend->end = e;
+        pend->value = runs[i].value;
+        pend->open = 1;
+    }
+    return 0;
+}
+
+int slh_format_depth_windows(slh_buffer *buf, const char *record_name, uint64_t record_size, uint64_t window, uint64_t j0,
+                             uint64_t sum_at_j0, const uint64_t *cum, uint64_t k) {
+    const size_t nl = cut_name_len(record_name);
+    uint64_t i, prev = sum_at_j0;
+    for (i = 0; i < k; i++) {
+        const uint64_t s = (j0 + i) * window, e = record_size - s < window ? record_size : s + window;
+        char *p;
+        if (buf_reserve(buf, nl + 96)) return -1;
+        p = depth_line_head(buf->data + buf->len, record_name, nl, s, e);
+        p = put_hundredths(p, cum[2 * i] - prev, e - s);
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+        prev = cum[2 * i];
+    }
+    return 0;
+}
+
+int slh_format_depth_summary(slh_buffer *buf, const char *record_name, uint64_t length, uint64_t covered, uint64_t sum) {
+    static const char *const HEAD = "> Depth of ";
+    const size_t nl = cut_name_len(record_name);
+    char *p;
+    if (buf_reserve(buf, nl + 160)) return -1;
+    p = buf->data + buf->len;
+    memcpy(p, HEAD, strlen(HEAD));
+    p += strlen(HEAD);
+    memcpy(p, record_name, nl);
+    p += nl;
+    p += sprintf(p, ": %llu positions, %llu covered (", (unsigned long long)length, (unsigned long long)covered);
+    p = put_hundredths(p, 100 * covered, length);
+    p += sprintf(p, " %%), mean depth ");
+    p = put_hundredths(p, sum, length);
+    *p++ = '\n';
     buf->len = (size_t)(p - buf->data);
     return 0;
 }

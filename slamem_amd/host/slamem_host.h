@@ -107,6 +107,11 @@ int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_p
  * default), 1 when it is, -1 when the value is missing, not an integer or no such power of two.  Its value is never taken for a
  * file name. */
 int slh_parse_event_slots(int argc, char **argv, uint64_t *out);
+/* -lev LIST (-le...) and -win N (-wi...) of -depth: LIST is 1 to 16 whole numbers in [1, 2^32), strictly ascending, separated by
+ * commas (levels_out has room for 16); N is a whole number of at least 1.  0 when neither is there (*num_levels_out = 0,
+ * *window_out = 0), else bit 0 says that -lev is there and bit 1 that -win is; -1 when the value of -lev is missing or no such
+ * list, -2 when that of -win is missing or no such number.  Neither value is ever taken for a file name. */
+int slh_parse_depth_params(int argc, char **argv, uint32_t *levels_out, int *num_levels_out, uint64_t *window_out);
 /* AppendToBasename (tools.c:65-79): everything before the last '.' of the whole path + extra */
 char *slh_append_to_basename(const char *filename, const char *extra);
 
@@ -176,6 +181,30 @@ int slh_format_vcf_rows(slh_buffer *buf, const char *record_name, uint64_t recor
 /* -cons: one FASTA record -- '>' and the record's name up to its first blank or tab, then `len` letters in lines of 60; a record
  * of no letters is its header line alone */
 int slh_format_fasta_record(slh_buffer *buf, const char *record_name, const char *letters, uint64_t len);
+/* -depth.  The runs of slamem_pileup_depth_runs_* (the same two words), and the run of a record that is not written yet. */
+typedef struct {
+    uint64_t pos, value;
+} slh_depth_run;
+typedef struct {
+    uint64_t start, end, value; /* local to the record */
+    int open;
+} slh_depth_pending;
+/* The bedGraph lines (name, start, end, value; 0-based, half-open, local to the record that starts at row record_start) of rows
+ * [a, b) of a record, from the runs of a range that holds them (runs[0].pos <= a; run i ends where run i + 1 starts, the last one
+ * behind b or at it): the runs clipped to [a, b).  The piece's last run stays in *pend, and the first run of the record's next
+ * piece continues it when it has the same value and starts where it ended -- a run over the border of two ranges is one line;
+ * slh_format_depth_flush writes it (at the record's end) and is harmless when nothing is open. */
+int slh_format_depth_runs(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t a, uint64_t b,
+                          const slh_depth_run *runs, uint64_t num_runs, slh_depth_pending *pend);
+int slh_format_depth_flush(slh_buffer *buf, const char *record_name, slh_depth_pending *pend);
+/* -depth -win N: the lines of windows j0 .. j0 + k - 1 of a record of record_size rows (window j is rows [j N, (j + 1) N), the
+ * last one shorter): name, start, end and the mean depth 100 * sum // rows as whole "." two digits.  sum_at_j0 is the sum of d
+ * in front of window j0, cum[2 i] the sum in front of the end of window j0 + i (the pairs of slamem_pileup_depth_runs_*). */
+int slh_format_depth_windows(slh_buffer *buf, const char *record_name, uint64_t record_size, uint64_t window, uint64_t j0,
+                             uint64_t sum_at_j0, const uint64_t *cum, uint64_t k);
+/* -depth: the line of a record for stderr: "> Depth of NAME: L positions, C covered (P %), mean depth M", P = 10000 * C // L and
+ * M = 100 * sum // L printed as above (both 0.00 for a record of no rows) */
+int slh_format_depth_summary(slh_buffer *buf, const char *record_name, uint64_t length, uint64_t covered, uint64_t sum);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
