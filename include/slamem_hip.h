@@ -473,6 +473,32 @@ int slamem_pileup_add_device(slamem_pileup *pile, const void *queries_dev, const
 int slamem_pileup_counts_device(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t *out_dev, void *stream);
 int slamem_pileup_counts_host(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t *out);
 
+/* ---- (b'' 2) base quality: the low-quality mask of a batch (option -bq) ----------------------------------------
+ * A batch may come with a low-quality mask: a bit array over its letter buffer, indexed as the letters are.  Bit j (bit j % 64 of
+ * word j / 64 of a uint64 array of (total_letters + 63) / 64 words) belongs to queries[j], so bit offsets[r] + i belongs to letter
+ * i of read r AS GIVEN; reads share words.  With a mask, a letter whose bit is set counts NOWHERE under = or X: the row gets nothing
+ * from this read and its depth does not rise.  On strand 2 the scanned strand's letter q is the given letter len - 1 - q and has
+ * that letter's bit.  D rows, I operations and the indel events are as without a mask (samtools mpileup -Q does the same).  A mask
+ * without a set bit, or NULL, gives bit for bit what slamem_pileup_add_device gives; addition still commutes.
+ *
+ * The mask is made from quality bytes by one rule: letter j is low iff max(0, qual[j] - phred_offset) < min_bq.  min_bq is 0 to
+ * 93 (0: nothing is low), phred_offset 0 to 126 (33 for FASTQ as it is written today); anything else: SLAMEM_ERR_ARG.  The unused
+ * bits of the last word are 0.
+ *   slamem_pack_lowq_device  quality bytes in device memory -> mask_out_dev, asynchronous on `stream`
+ *   slamem_pack_lowq       the same on the host with `threads` threads: what a front end puts in front of
+ *                          slamem_stream_submit_masked, so that the link carries an eighth of a byte per letter, not one
+ *   slamem_pileup_add_masked_device  slamem_pileup_add_device with the batch's mask in device memory; no word at or behind
+ *                          (offsets[num_queries] + 63) / 64 is read, and none that holds no bit of a read.  NULL: the unmasked
+ *                          add.  slamem_pileup_add_device stays as it is. */
+int slamem_pack_lowq_device(const void *quals_dev, uint64_t total_letters, uint32_t min_bq, uint32_t phred_offset,
+                            uint64_t *mask_out_dev, void *stream);
+int slamem_pack_lowq(const char *quals, uint64_t total_letters, uint32_t min_bq, uint32_t phred_offset, uint64_t *mask_out,
+                     int threads);
+int slamem_pileup_add_masked_device(slamem_pileup *pile, const void *queries_dev, const uint64_t *offsets_dev, uint32_t num_queries,
+                                    const slamem_aln *segs_dev, const uint64_t *read_offsets_dev, const uint32_t *ops_dev,
+                                    const uint64_t *op_offsets_dev, const slamem_map *reads_dev, uint32_t min_mapq,
+                                    const uint64_t *lowq_dev, void *stream);
+
 /* ---- (b''') the sparse read-out of the pileup (option -sites) ------------------------------------------------
  * The rows of [first, first + count) that a rule selects, compacted on the device in ascending position.  cnt[p] is row p as
  * slamem_pileup_counts_* gives it, L(p) the text's letter at p in upper case, d(p) = A+C+G+T+D (a 64-bit sum).
@@ -741,6 +767,13 @@ int slamem_stream_maps(slamem_stream *s, const slamem_map **reads_out);
 int slamem_stream_set_pileup(slamem_stream *s, slamem_pileup *pile, uint32_t min_mapq);
 int slamem_stream_submit(slamem_stream *s, const char *queries, const uint64_t *offsets, uint32_t num_queries,
                          uint32_t min_len);
+/* -pile with a low-quality mask: slamem_stream_submit for a stream of match type 8, with `lowq` indexed as
+ * `queries` is -- bit offsets[i] + k is letter k of record i, whatever offsets[0] is.  The stream uploads the words that hold a
+ * bit of the batch and adds the batch with slamem_pileup_add_masked_device's kernels; lowq must stay unchanged as queries must.
+ * lowq NULL: slamem_stream_submit.  A stream of another match type: SLAMEM_ERR_ARG.  slamem_stream_submit and
+ * slamem_stream_submit_packed on the same stream remain the unmasked ones. */
+int slamem_stream_submit_masked(slamem_stream *s, const char *queries, const uint64_t *lowq, const uint64_t *offsets,
+                                uint32_t num_queries, uint32_t min_len);
 /* The same for reads the caller holds PACKED (ABI 4; no reference counterpart: the reference reads letters, sequence.c:89-270).
  * Since the search takes ~9 ms for 10 M reads the link bounds this path (1.5 GB of letters: 26 ms); packed reads are a third.
  *   planes   16-byte units {p0, p1} (two 64-bit words): bit i of p0 / p1 = low / high bit of letter 64u+i of the record

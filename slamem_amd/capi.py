@@ -55,6 +55,7 @@ ABI_SYMBOLS = (
     "slamem_pileup_add_events_host", "slamem_pileup_rows_at_device", "slamem_pileup_rows_at_host",
     "slamem_pileup_consensus_device", "slamem_pileup_consensus_host", "slamem_pileup_depth_runs_device", "slamem_pileup_depth_runs_host",
     "slamem_stream_create", "slamem_stream_set_max_occ", "slamem_stream_set_max_gap", "slamem_stream_submit", "slamem_stream_submit_packed", "slamem_pack_reads", "slamem_stream_next",
+    "slamem_pack_lowq_device", "slamem_pack_lowq", "slamem_pileup_add_masked_device", "slamem_stream_submit_masked",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
 )
@@ -189,6 +190,10 @@ def _declare(L):
     L.slamem_pileup_free.argtypes = [vp]
     L.slamem_pileup_reset.argtypes = [vp]
     L.slamem_pileup_add_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp]
+    L.slamem_pileup_add_masked_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp]
+    L.slamem_pack_lowq_device.argtypes = [vp, u64, u32, u32, vp, vp]
+    L.slamem_pack_lowq.argtypes = [vp, u64, u32, u32, vp, i32]
+    L.slamem_stream_submit_masked.argtypes = [vp, vp, vp, vp, u32, u32]
     L.slamem_pileup_counts_device.argtypes = [vp, u64, u64, vp, vp]
     L.slamem_pileup_counts_host.argtypes = [vp, u64, u64, vp]
     L.slamem_pileup_sites_device.argtypes = [vp, u64, u64, u32, u32, u32, u64, vp, vp, vp, C.POINTER(u64), vp]

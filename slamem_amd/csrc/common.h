@@ -440,6 +440,12 @@ int pileup_device(const slamem_pileup* p);
 int pileup_add(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
                const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
                const slamem_map* reads_dev, uint32_t min_mapq, hipStream_t stream);
+// the same with a low-quality mask: bit offsets[r] + i of lowq_dev belongs to letter i of read r; nullptr:
+// pileup_add.  slamem_pack_lowq_device (lowq_filter.hip) makes the mask from quality bytes on the device.
+int pileup_add_masked(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                      const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev,
+                      const uint64_t* op_offsets_dev, const slamem_map* reads_dev, uint32_t min_mapq, const uint64_t* lowq_dev,
+                      hipStream_t stream);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).

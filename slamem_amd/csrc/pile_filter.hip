@@ -22,6 +22,10 @@
 //                  (ballots and popcounts in a wave, the waves' totals through LDS; no atomics).  The rule is evaluated twice
 //                  rather than kept as a bitmap: see 4.17.
 //   k_pile_add_counts  a table added into cnt (atomicAdd, zeros skipped; diff is not touched)
+//   k_pile_lane_masked / k_pile_wave_masked
+//                  the two add kernels with a low-quality mask: a bit per letter of the batch's letter buffer,
+//                  and a letter whose bit is set counts nowhere under = and X.  The same bodies (a template parameter); an `=`
+//                  run ORs the mask's window over its letters into the text's exclusion bits, 64 rows at a time.
 // Counters are 32 bits wide and every sum is taken modulo 2^32: a true depth of 2^31 or more at one row is outside the contract.
 #include "pile_shared.h"
 
@@ -72,16 +76,87 @@ __device__ __forceinline__ void pile_eq(const PileAcc& a, uint64_t p, uint64_t k
     }
 }
 
-// one operation at (p, q): every write is checked against n
-__device__ __forceinline__ void pile_op(const PileAcc& a, const PileRead& r, uint32_t op, uint64_t p, uint64_t q) {
+// ---- the low-quality mask -----------------------------------------------------------------------------------
+// bit off + i of `words` belongs to letter i of the read as given; every load below takes a word that holds a bit of the read
+struct PileLow {
+    const uint64_t* words;
+    uint64_t off, len;
+    bool rev;
+};
+
+// bits [at, at + c) of the mask, c in 1 .. 64, all of them letters of one read: bit i of the result is bit at + i.  The window
+// comes from two neighbouring words (a funnel shift); the second one is loaded only when the window reaches into it, so that
+// it holds bit at + c - 1 -- a letter of the read, never a word behind the mask's last.
+__device__ __forceinline__ uint64_t lowq_window(const uint64_t* __restrict__ words, uint64_t at, uint32_t c) {
+    const uint32_t s = (uint32_t)(at & 63u);
+    uint64_t w = words[at >> 6] >> s;
+    if (s + c > 64u) w |= words[(at >> 6) + 1u] << (64u - s);  // (s > 0 here)
+    return c < 64u ? w & ((1ull << c) - 1ull) : w;
+}
+
+// the mask over letters [q, q + c) of the scanned strand, c in 1 .. 64: bit i belongs to letter q + i.  On strand 2 that is the
+// given letter len - 1 - q - i: the window over the mirrored range, bit-reversed.  Letters behind the read's end have no bit.
+__device__ __forceinline__ uint64_t lowq_letters(const PileLow& m, uint64_t q, uint32_t c) {
+    if (q >= m.len) return 0ull;
+    const uint32_t cv = m.len - q < c ? (uint32_t)(m.len - q) : c;
+    if (!m.rev) return lowq_window(m.words, m.off + q, cv);
+    return __brevll(lowq_window(m.words, m.off + (m.len - q - cv), cv)) >> (64u - cv);
+}
+
+// an `=` run over rows [p, p + k) that shows letters [q, q + k) of the scanned strand: as pile_eq, with the letters' mask bits
+// ORed into the text's, a text word (up to 64 rows) at a time.  A stretch between two excluded bits gets its pair of atomics;
+// ctz finds the stretches' ends, and one that reaches the chunk's end stays open into the next chunk -- a run without an
+// excluded bit costs its two atomics as before.
+__device__ __forceinline__ void pile_eq_masked(const PileAcc& a, const PileLow& m, uint64_t p, uint64_t k, uint64_t q) {
+    if (k == 0 || p >= a.n) return;
+    if (p + k > a.n) k = a.n - p;
+    const uint64_t e = p + k;  // <= n
+    uint64_t start = ~0ull;    // the first row of the open stretch
+    for (uint64_t x0 = p; x0 < e;) {
+        const uint32_t sh = (uint32_t)(x0 & 63u);
+        const uint32_t c = e - x0 < 64u - sh ? (uint32_t)(e - x0) : 64u - sh;
+        const uint64_t in = c < 64u ? (1ull << c) - 1ull : ~0ull;
+        const uint64_t bad = ((a.tpl[x0 >> 6].nm >> sh) | lowq_letters(m, q + (x0 - p), c)) & in;  // bit i: row x0 + i
+        uint32_t i = 0;
+        while (i < c) {
+            if (start == ~0ull) {
+                const uint64_t good = ~bad & in & (~0ull << i);
+                if (!good) break;
+                i = (uint32_t)__builtin_ctzll(good);
+                start = x0 + i;
+            }
+            const uint64_t stop = bad & (~0ull << i);
+            if (!stop) break;
+            i = (uint32_t)__builtin_ctzll(stop);
+            atomicAdd(&a.diff[start], 1);
+            atomicAdd(&a.diff[x0 + i], -1);
+            start = ~0ull;
+        }
+        x0 += c;
+    }
+    if (start != ~0ull) {
+        atomicAdd(&a.diff[start], 1);
+        atomicAdd(&a.diff[e], -1);
+    }
+}
+
+// one operation at (p, q): every write is checked against n.  kMasked: a letter whose mask bit is set counts nowhere under = and
+// X; D and I are as without a mask.
+template <bool kMasked>
+__device__ __forceinline__ void pile_op(const PileAcc& a, const PileRead& r, const PileLow& m, uint32_t op, uint64_t p, uint64_t q) {
     const uint32_t code = op & 15u;
     const uint64_t k = op >> 4;
     if (code == kOpEq) {
-        pile_eq(a, p, k);
+        if constexpr (kMasked) pile_eq_masked(a, m, p, k, q);
+        else pile_eq(a, p, k);
     } else if (code == kOpX) {
         for (uint64_t j = 0; j < k && p + j < a.n; j++) {
             const uint32_t c = pile_letter(r, q + j);
-            if (c < 4u) atomicAdd(&a.cnt[(p + j) * 6u + c], 1u);
+            if constexpr (kMasked) {
+                if (c < 4u && !lowq_letters(m, q + j, 1u)) atomicAdd(&a.cnt[(p + j) * 6u + c], 1u);
+            } else {
+                if (c < 4u) atomicAdd(&a.cnt[(p + j) * 6u + c], 1u);
+            }
         }
     } else if (code == kOpD) {
         for (uint64_t j = 0; j < k && p + j < a.n; j++) atomicAdd(&a.cnt[(p + j) * 6u + 4u], 1u);
@@ -89,12 +164,27 @@ __device__ __forceinline__ void pile_op(const PileAcc& a, const PileRead& r, uin
         if (k && p < a.n) atomicAdd(&a.cnt[p * 6u + 5u], 1u);
     }
 }
+
+template <bool kMasked>
+__device__ __forceinline__ PileLow pile_low(const PileBatch& b, const PileRead& rd, const uint64_t* lowq) {
+    PileLow m = {nullptr, 0, 0, false};
+    if constexpr (kMasked) {
+        m.words = lowq;
+        m.off = (uint64_t)(rd.rec - b.queries);
+        m.len = rd.len;
+        m.rev = rd.rev;
+    }
+    return m;
+}
+
 // a lane per read: its segments of up to kPileLaneOps operations
-__global__ void __launch_bounds__(256) k_pile_lane(PileBatch b, PileAcc a) {
+template <bool kMasked>
+__device__ __forceinline__ void pile_lane_body(const PileBatch& b, const PileAcc& a, const uint64_t* lowq) {
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (r >= b.nq) return;
     PileRead rd;
     if (!pile_contributes(b, r, rd)) return;
+    const PileLow m = pile_low<kMasked>(b, rd, lowq);
     const uint64_t s1 = b.roff[r + 1];
     for (uint64_t s = b.roff[r]; s < s1; s++) {
         const uint64_t o0 = b.ooff[s], o1 = b.ooff[s + 1];
@@ -103,16 +193,21 @@ __global__ void __launch_bounds__(256) k_pile_lane(PileBatch b, PileAcc a) {
         uint64_t p = sg.ref_pos, q = sg.query_pos;
         for (uint64_t i = o0; i < o1; i++) {
             const uint32_t op = b.ops[i];
-            pile_op(a, rd, op, p, q);
+            pile_op<kMasked>(a, rd, m, op, p, q);
             p += pile_ref_step(op);
             q += pile_query_step(op);
         }
     }
 }
+__global__ void __launch_bounds__(256) k_pile_lane(PileBatch b, PileAcc a) { pile_lane_body<false>(b, a, nullptr); }
+__global__ void __launch_bounds__(256) k_pile_lane_masked(PileBatch b, PileAcc a, const uint64_t* __restrict__ lowq) {
+    pile_lane_body<true>(b, a, lowq);
+}
 
 // a wave per 64 reads: the reads that have a segment of more than kPileLaneOps operations, one after the other; of such a read
 // those segments, 64 operations at a time
-__global__ void __launch_bounds__(64) k_pile_wave(PileBatch b, PileAcc a) {
+template <bool kMasked>
+__device__ __forceinline__ void pile_wave_body(const PileBatch& b, const PileAcc& a, const uint64_t* lowq) {
     const uint32_t lane = threadIdx.x;
     const uint64_t chunks = (b.nq + 63u) >> 6;
     for (uint64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
@@ -130,6 +225,7 @@ __global__ void __launch_bounds__(64) k_pile_wave(PileBatch b, PileAcc a) {
             const uint64_t rr = c * 64u + src;
             PileRead rd;
             (void)pile_contributes(b, rr, rd);  // (it does: its lane said so)
+            const PileLow m = pile_low<kMasked>(b, rd, lowq);
             const uint64_t s1 = b.roff[rr + 1];
             for (uint64_t s = b.roff[rr]; s < s1; s++) {
                 const uint64_t o0 = b.ooff[s], o1 = b.ooff[s + 1];
@@ -141,13 +237,17 @@ __global__ void __launch_bounds__(64) k_pile_wave(PileBatch b, PileAcc a) {
                     const uint32_t op = have ? b.ops[base + lane] : 0u;
                     const uint64_t rs = pile_ref_step(op), qs = pile_query_step(op);
                     const uint64_t ri = wave_scan_inclusive(rs, lane), qi = wave_scan_inclusive(qs, lane);
-                    if (have) pile_op(a, rd, op, p + ri - rs, q + qi - qs);
+                    if (have) pile_op<kMasked>(a, rd, m, op, p + ri - rs, q + qi - qs);
                     p += __shfl(ri, 63, 64);
                     q += __shfl(qi, 63, 64);
                 }
             }
         }
     }
+}
+__global__ void __launch_bounds__(64) k_pile_wave(PileBatch b, PileAcc a) { pile_wave_body<false>(b, a, nullptr); }
+__global__ void __launch_bounds__(64) k_pile_wave_masked(PileBatch b, PileAcc a, const uint64_t* __restrict__ lowq) {
+    pile_wave_body<true>(b, a, lowq);
 }
 
 // ---- read-out --------------------------------------------------------------------------------------------------------------
@@ -413,6 +513,14 @@ int pileup_device(const slamem_pileup* p) { return p->device; }
 int pileup_add(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
                const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
                const slamem_map* reads_dev, uint32_t min_mapq, hipStream_t stream) {
+    return pileup_add_masked(pile, queries_dev, offsets_dev, num_queries, segs_dev, read_offsets_dev, ops_dev, op_offsets_dev, reads_dev,
+                             min_mapq, nullptr, stream);
+}
+
+int pileup_add_masked(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                      const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev,
+                      const uint64_t* op_offsets_dev, const slamem_map* reads_dev, uint32_t min_mapq, const uint64_t* lowq_dev,
+                      hipStream_t stream) {
     if (num_queries == 0) return SLAMEM_OK;
     PileBatch b;
     b.queries = static_cast<const unsigned char*>(queries_dev);
@@ -429,11 +537,18 @@ int pileup_add(slamem_pileup* pile, const void* queries_dev, const uint64_t* off
     a.diff = pile->diff;
     a.cnt = pile->cnt;
     a.n = pile->n;
-    hipLaunchKernelGGL(k_pile_lane, dim3(pile_grid(num_queries, 256)), dim3(256), 0, stream, b, a);
-    SLAMEM_HIP(hipGetLastError());
     const unsigned chunks = pile_grid(num_queries, 64);
-    hipLaunchKernelGGL(k_pile_wave, dim3(chunks < kPileWaveGrid ? chunks : kPileWaveGrid), dim3(64), 0, stream, b, a);
-    SLAMEM_HIP(hipGetLastError());
+    if (lowq_dev) {  // (the same two kernels with the mask; without one, the instantiations that were there before)
+        hipLaunchKernelGGL(k_pile_lane_masked, dim3(pile_grid(num_queries, 256)), dim3(256), 0, stream, b, a, lowq_dev);
+        SLAMEM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_pile_wave_masked, dim3(chunks < kPileWaveGrid ? chunks : kPileWaveGrid), dim3(64), 0, stream, b, a, lowq_dev);
+        SLAMEM_HIP(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(k_pile_lane, dim3(pile_grid(num_queries, 256)), dim3(256), 0, stream, b, a);
+        SLAMEM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_pile_wave, dim3(chunks < kPileWaveGrid ? chunks : kPileWaveGrid), dim3(64), 0, stream, b, a);
+        SLAMEM_HIP(hipGetLastError());
+    }
     if (pile->ev) return events_add(pile, &b, stream);  // (the indel events of the same batch, behind the two kernels)
     return SLAMEM_OK;
 }
@@ -531,6 +646,20 @@ int slamem_pileup_add_device(slamem_pileup* pile, const void* queries_dev, const
     SLAMEM_HIP(hipSetDevice(pile->device));
     return pileup_add(pile, queries_dev, offsets_dev, num_queries, segs_dev, read_offsets_dev, ops_dev, op_offsets_dev, reads_dev,
                       min_mapq, static_cast<hipStream_t>(stream));
+}
+
+int slamem_pileup_add_masked_device(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                                    const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev,
+                                    const uint64_t* op_offsets_dev, const slamem_map* reads_dev, uint32_t min_mapq,
+                                    const uint64_t* lowq_dev, void* stream) {
+    if (!pile || !offsets_dev || !read_offsets_dev || !op_offsets_dev || !reads_dev || (num_queries && (!queries_dev || !segs_dev || !ops_dev))) {
+        set_error("slamem_pileup_add_masked_device: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    if (min_mapq > 60u) { set_error("slamem_pileup_add_masked_device: the minimum mapping quality is 0 to 60"); return SLAMEM_ERR_ARG; }
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    return pileup_add_masked(pile, queries_dev, offsets_dev, num_queries, segs_dev, read_offsets_dev, ops_dev, op_offsets_dev,
+                             reads_dev, min_mapq, lowq_dev, static_cast<hipStream_t>(stream));
 }
 
 int slamem_pileup_counts_device(slamem_pileup* pile, uint64_t first, uint64_t count, uint32_t* out_dev, void* stream) {

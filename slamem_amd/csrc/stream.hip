@@ -88,6 +88,11 @@ struct Slot {
     uint32_t* d_ucnt = nullptr;         // units per record, then their prefix sums (and the scan's scratch behind them)
     uint64_t cap_units = 0;
     uint64_t units_hint = 0;            // the batch's units as the caller counted them (0: count here)
+    // a batch handed in with a low-quality mask (slamem_stream_submit_masked): the caller's words, indexed as its
+    // letters, and the words the batch touches on the device -- d_lowq[0] is the caller's word offs[0] / 64
+    const uint64_t* lowq = nullptr;
+    uint64_t* d_lowq = nullptr;
+    uint64_t cap_lowq = 0;              // words of d_lowq
     // its result
     uint64_t total = 0;
     int rc = SLAMEM_OK;
@@ -350,6 +355,19 @@ int stage_upload(slamem_stream* s, Slot& sl) {
         at = end;
     }
     SLAMEM_HIP(hipMemcpyAsync(sl.d_off, sl.offs, ((uint64_t)sl.nq + 1) * 8, hipMemcpyHostToDevice, s->st[0]));
+    if (sl.lowq && qbytes) {
+        // the mask's words that hold a bit of the batch: [base / 64, (base + qbytes + 63) / 64).  Nothing is shifted: the add gets
+        // d_lowq - base / 64, so that bit offs[r] + i is letter i of read r there as it is in the caller's array
+        const uint64_t w0 = base >> 6, nw = ((base + qbytes + 63u) >> 6) - w0;
+        if (!sl.d_lowq || nw > sl.cap_lowq) {
+            if (sl.d_lowq) (void)hipFree(sl.d_lowq);
+            sl.d_lowq = nullptr; sl.cap_lowq = 0;
+            const uint64_t want = nw > (sl.cap_chars >> 6) + 2 ? nw : (sl.cap_chars >> 6) + 2;
+            SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_lowq), want * 8));
+            sl.cap_lowq = want;
+        }
+        SLAMEM_HIP(hipMemcpyAsync(sl.d_lowq, sl.lowq + w0, nw * 8, hipMemcpyHostToDevice, s->st[0]));
+    }
     {   // while the copy engines work: is any record longer than a slice?  (if not, the prepare stage knows the number of work
         // items without asking the device -- its one host round trip per batch goes away)
         uint64_t longest = 0;
@@ -505,8 +523,10 @@ int stage_download(slamem_stream* s, Slot& sl) {
     if (s->match_type == 8) {
         // -pile: the batch's result stands (its totals fitted), so it is added to the accumulator -- here and not behind K9,
         // where nobody knows yet whether the batch will be run again with more room.  Segments and operations stay on the device.
-        rc = pileup_add(s->pile, device_queries(sl), sl.d_off, sl.nq, sl.d_segs, sl.d_boff, sl.d_ops, sl.d_ooff, sl.d_reads,
-                        s->min_mapq, st);
+        // (a masked batch: the uploaded words start at the caller's word offs[0] / 64)
+        const uint64_t* lowq = (sl.lowq && sl.d_lowq && sl.offs[sl.nq] > sl.offs[0]) ? sl.d_lowq - (sl.offs[0] >> 6) : nullptr;
+        rc = pileup_add_masked(s->pile, device_queries(sl), sl.d_off, sl.nq, sl.d_segs, sl.d_boff, sl.d_ops, sl.d_ooff, sl.d_reads,
+                               s->min_mapq, lowq, st);
         if (rc != SLAMEM_OK) return rc;
     } else if (sl.h_cap < sl.cap || !sl.h_mems) {
         if (sl.h_mems) (void)hipHostFree(sl.h_mems);
@@ -621,6 +641,7 @@ void free_slot(Slot& sl) {
     if (sl.d_planes) (void)hipFree(sl.d_planes);
     if (sl.d_other) (void)hipFree(sl.d_other);
     if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
+    if (sl.d_lowq) (void)hipFree(sl.d_lowq);
     if (sl.h_boff) (void)hipHostFree(sl.h_boff);
     if (sl.h_mems) (void)hipHostFree(sl.h_mems);
     if (sl.h_scal) (void)hipHostFree(sl.h_scal);
@@ -970,6 +991,43 @@ int slamem_stream_submit(slamem_stream* s, const char* queries, const uint64_t* 
     sl.chars = queries;
     sl.planes = nullptr;
     sl.other = nullptr;
+    sl.lowq = nullptr;
+    sl.offs = offsets;
+    sl.nq = num_queries;
+    sl.min_len = min_len;
+    sl.rc = SLAMEM_OK;
+    sl.err[0] = 0;
+    sl.total = 0;
+    sl.state = QUEUED;
+    s->submitted++;
+    lk.unlock();
+    s->cv.notify_all();
+    return SLAMEM_OK;
+}
+
+int slamem_stream_submit_masked(slamem_stream* s, const char* queries, const uint64_t* lowq, const uint64_t* offsets, uint32_t num_queries,
+                                uint32_t min_len) {
+    if (!s || !offsets || (num_queries && !queries)) { set_error("slamem_stream_submit_masked: null argument"); return SLAMEM_ERR_ARG; }
+    if (min_len < 1) { set_error("slamem_stream_submit_masked: minimum MEM length must be >= 1"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type != 8) {
+        set_error("slamem_stream_submit_masked: a low-quality mask needs match type 8 (-pile)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (!s->pile) {
+        set_error("slamem_stream_submit_masked: a stream of match type 8 (-pile) needs slamem_stream_set_pileup first");
+        return SLAMEM_ERR_ARG;
+    }
+    Slot& sl = s->slot[s->submitted % (uint64_t)s->nslots];
+    if (sl.state != FREE) {
+        set_error("slamem_stream_submit_masked: all %d slots are in use (collect a result with slamem_stream_next first)", s->nslots);
+        return SLAMEM_ERR_ARG;
+    }
+    sl.seq = s->submitted;
+    sl.chars = queries;
+    sl.planes = nullptr;
+    sl.other = nullptr;
+    sl.lowq = lowq;  // (nullptr: the batch is an unmasked one)
     sl.offs = offsets;
     sl.nq = num_queries;
     sl.min_len = min_len;
@@ -1003,6 +1061,7 @@ int slamem_stream_submit_packed(slamem_stream* s, const void* planes, const uint
     sl.planes = planes;
     sl.other = other;
     sl.units_hint = num_units;
+    sl.lowq = nullptr;
     sl.offs = offsets;
     sl.nq = num_queries;
     sl.min_len = min_len;

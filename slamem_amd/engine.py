@@ -309,7 +309,7 @@ class Index:
                 raise err
             break
         if pile is not None:
-            pile[0]._add_device(qd, od, num, segs, boff, ops, ooff, recs, pile[1])
+            pile[0]._add_device(qd, od, num, segs, boff, ops, ooff, recs, pile[1], pile[2] if len(pile) > 2 else None)
             return _map_records(recs[: num * 12].cpu().numpy())
         nseg, nops = int(totals[1]), int(totals[2])
         out = segs[: nseg * 5].cpu().numpy().view(np.uint32).reshape(-1, 5).copy().view(ALN_DTYPE).reshape(-1)
@@ -415,21 +415,41 @@ class Pileup:
         self.last_add_ms = 0.0  # device time of the last add's own kernels (the mapping in front of them not counted)
 
     def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-            xdrop=None, max_edits=None, min_mapq: int = 0) -> np.ndarray:
+            xdrop=None, max_edits=None, min_mapq: int = 0, lowq=None) -> np.ndarray:
         """Maps the batch as Index.map_reads does and adds the mappings of the reads with mapq >= min_mapq (0 to 60) to the table,
-        on the device: segments and operations are not downloaded.  Returns the read records of map_reads (MAP_DTYPE)."""
+        on the device: segments and operations are not downloaded.  Returns the read records of map_reads (MAP_DTYPE).  lowq: the
+        batch's low-quality mask (DESIGN.md 4.21), a uint64 array of at least (offsets[-1] + 63) // 64 words (numpy, or a tensor on
+        the index's device) in which bit offsets[r] + i belongs to letter i of read r as given -- a letter whose bit is set counts
+        nowhere under = and X; pack_lowq makes it from quality bytes.  None: every letter counts."""
         if not 0 <= int(min_mapq) <= 60:
             raise ValueError("min_mapq must be in [0, 60]")
+        if lowq is not None:
+            need = (int(np.asarray(offsets)[-1]) + 63) // 64
+            if isinstance(lowq, torch.Tensor):
+                if lowq.dtype != torch.int64 or lowq.device != self.index.device or not lowq.is_contiguous():
+                    raise ValueError("lowq as a tensor: contiguous int64 words on the index's device")
+            else:
+                lowq = np.ascontiguousarray(lowq)
+                if lowq.dtype != np.uint64:
+                    raise ValueError("lowq must be a uint64 array")
+            if lowq.shape[0] < need:
+                raise ValueError(f"lowq has {lowq.shape[0]} words, the batch's letters need {need}")
         return self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, None, True,
-                                    pile=(self, int(min_mapq)))
+                                    pile=(self, int(min_mapq), lowq))
 
-    def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq):
+    def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq, lowq=None):
         dev = self.index.device
+        if lowq is not None and not isinstance(lowq, torch.Tensor):
+            lowq = torch.from_numpy(lowq.view(np.int64).copy()).to(dev) if lowq.shape[0] else None
         with torch.cuda.device(dev):
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
-            rc = capi.lib().slamem_pileup_add_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops), _ptr(ooff),
-                                                     _ptr(recs), int(min_mapq), _stream_handle(dev))
+            if lowq is not None:
+                rc = capi.lib().slamem_pileup_add_masked_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops),
+                                                                _ptr(ooff), _ptr(recs), int(min_mapq), _ptr(lowq), _stream_handle(dev))
+            else:
+                rc = capi.lib().slamem_pileup_add_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops),
+                                                         _ptr(ooff), _ptr(recs), int(min_mapq), _stream_handle(dev))
             t1.record()
             capi.check(rc)
             t1.synchronize()  # (the batch's tensors go when the caller returns)
@@ -758,6 +778,15 @@ class Stream:
         capi.check(capi.lib().slamem_stream_submit(self._h, chars.ctypes.data, offsets.ctypes.data, offsets.shape[0] - 1,
                                                    int(min_len)))
 
+    def submit_masked(self, chars: np.ndarray, lowq, offsets: np.ndarray, min_len: int) -> None:
+        """submit for a -pile stream with the batch's low-quality mask: lowq is a uint64 array indexed as chars is
+        -- bit offsets[r] + i belongs to letter i of record r, whatever offsets[0] is.  None: submit."""
+        assert chars.dtype == np.uint8 and offsets.dtype == np.uint64 and offsets.flags.c_contiguous
+        assert lowq is None or (lowq.dtype == np.uint64 and lowq.flags.c_contiguous)
+        self._keep.append((chars, lowq, offsets))
+        capi.check(capi.lib().slamem_stream_submit_masked(self._h, chars.ctypes.data, lowq.ctypes.data if lowq is not None else None,
+                                                          offsets.ctypes.data, offsets.shape[0] - 1, int(min_len)))
+
     def submit_packed(self, planes: np.ndarray, other, offsets: np.ndarray, min_len: int, units: int = 0) -> None:
         """planes: uint8 view of the batch's 16-byte units (slamem_pack_reads layout), other: uint64 per unit or None; offsets:
         uint64[num+1] in letters.  All must stay alive and unchanged until collected."""
@@ -840,6 +869,31 @@ def pack_reads(chars: np.ndarray, offsets: np.ndarray, planes_out: np.ndarray, o
     capi.check(capi.lib().slamem_pack_reads(chars.ctypes.data, offsets.ctypes.data, offsets.shape[0] - 1, planes_out.ctypes.data,
                                             other_out.ctypes.data if other_out is not None else None, C.byref(units), int(threads)))
     return int(units.value)
+
+
+def pack_lowq(quals, min_bq: int, phred_offset: int = 33, device=False, threads: int = 16):
+    """The low-quality mask of a letter buffer's quality bytes: letter j is low iff max(0, quals[j] - phred_offset)
+    < min_bq (min_bq 0 to 93, phred_offset 0 to 126).  Returns (len + 63) // 64 uint64 words, bit j % 64 of word j // 64 for
+    letter j, the last word's unused bits 0.  device=False: slamem_pack_lowq on the host, a numpy array.  device=True (or a device):
+    the bytes go up and k_lowq_pack packs them; an int64 tensor on that device, which Pileup.add(lowq=...) takes as it is."""
+    q = np.ascontiguousarray(np.frombuffer(quals, dtype=np.uint8) if isinstance(quals, (bytes, bytearray)) else quals, dtype=np.uint8)
+    total, words = int(q.shape[0]), (int(q.shape[0]) + 63) // 64
+    if not 0 <= int(min_bq) < 2 ** 32 or not 0 <= int(phred_offset) < 2 ** 32:
+        raise ValueError("min_bq and phred_offset are whole numbers from 0")
+    L = capi.lib()
+    if device is False or device is None:
+        out = np.zeros(words, dtype=np.uint64)
+        capi.check(L.slamem_pack_lowq(q.ctypes.data if total else None, total, int(min_bq), int(phred_offset),
+                                      out.ctypes.data if words else None, int(threads)))
+        return out
+    dev = _require_gpu("cuda:0" if device is True else device)
+    qd = torch.from_numpy(q if q.flags.writeable else q.copy()).to(dev)
+    out = torch.zeros(words, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(L.slamem_pack_lowq_device(_ptr(qd) if total else None, total, int(min_bq), int(phred_offset),
+                                             _ptr(out) if words else None, _stream_handle(dev)))
+        torch.cuda.current_stream(dev).synchronize()
+    return out
 
 
 def host_to_host_leg(index: Index, reads_dev: torch.Tensor, count: int, read_len: int, min_len: int, both: bool,

@@ -68,6 +68,10 @@ typedef struct {
     uint32_t min_len;
     long log_limit, piece_bytes;
     slh_seqset *sets;  /* room for every piece */
+    uint64_t **masks;  /* -bq: per piece the low-quality mask over its letters (NULL: FASTA, or -bq 0), as many entries as sets */
+    int min_bq;        /* -bq N: 0 = the qualities are not used */
+    int fasta_seen;    /* a query file without qualities came in (said once when -bq asks for them) */
+    int invalid;       /* a query file is no valid FASTQ: the run ends */
     int cap;
     pthread_mutex_t mu;
     pthread_cond_t cv;
@@ -76,6 +80,23 @@ typedef struct {
     int failed;        /* more pieces than main made room for */
     double seconds;
 } loader_t;
+
+/* -bq N: the low-quality mask of a set's letters from its quality bytes, packed by the host threads; the
+ * qualities go.  NULL when the qualities are not used or there are none. */
+static uint64_t *mask_of_quals(loader_t *ld, const slh_seqset *s, char *quals) {
+    uint64_t *mask = NULL;
+    if (!quals) { if (ld->min_bq > 0) ld->fasta_seen = 1; return NULL; }
+    if (ld->min_bq > 0) {
+        mask = (uint64_t *)slh_big_malloc(((size_t)(s->total + 63) / 64 + 1) * sizeof(uint64_t));
+        if (mask && slamem_pack_lowq(quals, s->total, (uint32_t)ld->min_bq, 33, mask, slh_thread_count()) != SLAMEM_OK) {
+            free(mask);
+            mask = NULL;
+        }
+        if (!mask) ld->invalid = 2; /* (out of memory: never count letters that were to be skipped) */
+    }
+    free(quals);
+    return mask;
+}
 
 static void *loader_run(void *arg) {
     loader_t *ld = (loader_t *)arg;
@@ -88,15 +109,21 @@ static void *loader_run(void *arg) {
         slh_pieces_release_parsed(p, ld->release_early);
         for (;;) {
             slh_seqset s;
-            int n = slh_pieces_next(p, &s);
+            char *quals = NULL;
+            uint64_t *mask;
+            int n = slh_pieces_next_q(p, &s, &quals);
+            if (n < 0) ld->invalid = 1;
             if (n <= 0) break;
+            mask = mask_of_quals(ld, &s, quals);
             pthread_mutex_lock(&ld->mu);
             if (ld->ready < ld->cap) {
+                ld->masks[ld->ready] = mask;
                 ld->sets[ld->ready++] = s;
                 ld->total_queries += n;
                 ld->numbering += n;
             } else { /* cannot happen (a piece is at least piece_bytes of its file): never drop reads silently */
                 ld->failed = 1;
+                free(mask);
                 slh_free_seqset(&s);
             }
             pthread_cond_broadcast(&ld->cv);
@@ -549,8 +576,9 @@ static int image_tool(int argc, char **argv, slh_options *o, long log_limit) {
     if (!sets) exit_message("Out of memory");
     for (f = 0; f < o->num_files; f++) {
         const char *path = argv[o->file_args[f]];
-        int n = slh_load_file(path, loaded == 0, o->no_ns, (uint32_t)o->min_seq_len, loaded == 0 ? o->ref_name : NULL, numbering,
-                              log_limit, loaded == 0 ? &ref : &sets[loaded], stdout);
+        int n = slh_load_file_q(path, loaded == 0, o->no_ns, (uint32_t)o->min_seq_len, loaded == 0 ? o->ref_name : NULL, numbering,
+                                log_limit, loaded == 0 ? &ref : &sets[loaded], NULL, stdout);
+        if (n < 0) { fflush(stdout); exit(-1); } /* (an invalid FASTQ file, or FASTQ as the reference: the loader said so) */
         if (n != 0) { loaded++; numbering += n; if (loaded > 1) queries += n; }
         if (loaded == 0) exit_message("No valid sequences found in reference file");
     }
@@ -591,6 +619,7 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-paf\tone mapping per read with a mapping quality, written as PAF with a cg:Z: CIGAR; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-pile\tper-base pileup of the mappings of -paf: record, position, letter and the counts A C G T D I; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-minq\twith -pile: least mapping quality of a read that counts, 0 to 60 (default=0)\n");
+    printf("\t-bq\twith -pile, -sites, -vcf, -cons, -depth: least base quality of a read letter that counts, 0 to 93 (default=0: all); needs FASTQ queries (a file that starts with '@')\n");
     printf("\t-sites\tvariant sites of the pileup: the rows of -pile where the reads differ from the reference, with a tenth column, the calls; -mgap, -pen, -xdrop, -maxed, -minq apply\n");
     printf("\t-mdep\twith -sites: least depth A+C+G+T+D of a site (default=4)\n");
     printf("\t-mpct\twith -sites: least share of the depth a call needs, in percent, 0 to 100 (default=20)\n");
@@ -622,7 +651,7 @@ int main(int argc, char **argv) {
     char *out_name;
     FILE *out;
     slamem_index *idx = NULL, *gpus[16];
-    int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1, min_mapq = 0;
+    int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1, min_mapq = 0, min_bq = 0, bq_given = 0;
     int sites = 0, min_depth = 4, min_pct = 20; /* -sites: match type 8 with the sparse read-out */
     int vcf = 0;                                /* -vcf: match type 8 with the events enabled, written as VCF */
     int cons = 0;                               /* -cons: match type 8 with the events enabled, the consensus written as FASTA */
@@ -691,6 +720,11 @@ int main(int argc, char **argv) {
     switch (slh_parse_min_mapq(argc, argv, &min_mapq)) {
     case -1: exit_message("Option -minq needs a whole number from 0 to 60"); break;
     case 1: if (o.match_type != 8) exit_message("Option -minq needs -pile"); break;
+    default: break;
+    }
+    switch ((bq_given = slh_parse_min_bq(argc, argv, &min_bq))) {
+    case -1: exit_message("Option -bq needs a whole number from 0 to 93"); break;
+    case 1: if (o.match_type != 8) exit_message("Option -bq needs -pile"); break;
     default: break;
     }
     switch ((sites_params = slh_parse_sites_params(argc, argv, &min_depth, &min_pct))) {
@@ -763,14 +797,17 @@ int main(int argc, char **argv) {
         g_reap_tid = (pthread_t *)calloc((size_t)ld->cap + 1, sizeof(pthread_t));
         if (!qsets || !g_reap_tid) exit_message("Out of memory");
         ld->sets = qsets;
+        ld->masks = (uint64_t **)calloc((size_t)ld->cap + 1, sizeof(uint64_t *));
+        if (!ld->masks) exit_message("Out of memory");
+        ld->min_bq = min_bq;
         pthread_mutex_init(&ld->mu, NULL);
         pthread_cond_init(&ld->cv, NULL);
     }
     for (f = 0; f < o.num_files; f++) {
         const char *path = argv[o.file_args[f]];
         if (ref_file < 0) {
-            int n = slh_load_file(path, 1, o.no_ns, (uint32_t)o.min_seq_len, o.ref_name, numbering, log_limit, &ref, stdout);
-            if (n == 0) exit_message("No valid sequences found in reference file");
+            int n = slh_load_file_q(path, 1, o.no_ns, (uint32_t)o.min_seq_len, o.ref_name, numbering, log_limit, &ref, NULL, stdout);
+            if (n <= 0) exit_message("No valid sequences found in reference file");
             ref_file = f;
             numbering += n;
             g_num_refs = ref.num;
@@ -781,8 +818,19 @@ int main(int argc, char **argv) {
             build_async = pthread_create(&build_tid, NULL, build_run, &bj) == 0;
             if (overlap) break;
         } else {
-            int n = slh_load_file(path, 0, o.no_ns, (uint32_t)o.min_seq_len, NULL, numbering, log_limit, &qsets[ld->ready], stdout);
-            if (n != 0) { numbering += n; ld->total_queries += n; ld->ready++; }
+            char *quals = NULL;
+            int n = slh_load_file_q(path, 0, o.no_ns, (uint32_t)o.min_seq_len, NULL, numbering, log_limit, &qsets[ld->ready], &quals, stdout);
+            if (n < 0) { /* an invalid FASTQ file (the loader said so): before any search */
+                if (build_async) pthread_join(build_tid, NULL);
+                join_warmup();
+                fflush(stdout);
+                exit(-1);
+            }
+            if (n != 0) {
+                ld->masks[ld->ready] = mask_of_quals(ld, &qsets[ld->ready], quals);
+                if (ld->invalid) exit_message("Out of memory");
+                numbering += n; ld->total_queries += n; ld->ready++;
+            }
         }
     }
     if (overlap) {
@@ -827,6 +875,7 @@ int main(int argc, char **argv) {
         say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", max_gap > 0 ? max_gap : 5000,
             ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
     if (o.match_type == 8) say(" ; minimum mapping quality = %d", min_mapq);
+    if (bq_given == 1) say(" ; minimum base quality = %d", min_bq); /* (only when asked for: the line of a run without -bq stays) */
     if (sites || vcf) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
     if (cons) say(" ; minimum depth = %d", min_depth);
     if (depth) say(" ; covered from depth = %d", min_depth);
@@ -1024,7 +1073,7 @@ int main(int argc, char **argv) {
             slh_seqset *q = &qsets[ranges[bi].f];
             const int first = ranges[bi].first, last = ranges[bi].last;
             for (; ld->release_early && sets_reaped < ranges[bi].f; sets_reaped++) /* every batch of the earlier sets is formatted */
-                if (qsets[sets_reaped].chars) reap_set(&qsets[sets_reaped]);
+                if (qsets[sets_reaped].chars) { reap_set(&qsets[sets_reaped]); free(ld->masks[sets_reaped]); ld->masks[sets_reaped] = NULL; }
             const slamem_mem *mems = NULL;
             const uint32_t *mism = NULL;
             const slamem_aln *segs = NULL;
@@ -1038,6 +1087,12 @@ int main(int argc, char **argv) {
             /* keep every GPU's pipeline full: slots - 1 batches in flight beside the result being formatted */
             while (submitted < nranges && inflight[submitted % (size_t)ngpu] < slots - 1) {
                 slh_seqset *qs = &qsets[ranges[submitted].f];
+                const uint64_t *qmask = ld->masks[ranges[submitted].f];
+                if (qmask) /* -bq N on FASTQ reads: the set's mask is indexed as its letters, the stream takes the batch's words */
+                    rc = slamem_stream_submit_masked(g_streams[submitted % (size_t)ngpu], qs->chars, qmask,
+                                                     qs->offsets + ranges[submitted].first,
+                                                     (uint32_t)(ranges[submitted].last - ranges[submitted].first), (uint32_t)o.min_mem_len);
+                else
                 rc = slamem_stream_submit(g_streams[submitted % (size_t)ngpu], qs->chars, qs->offsets + ranges[submitted].first,
                                           (uint32_t)(ranges[submitted].last - ranges[submitted].first), (uint32_t)o.min_mem_len);
                 if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("MEM search on the GPU", rc); }
@@ -1153,6 +1208,13 @@ int main(int argc, char **argv) {
         release_stdout(); /* the loader is done: the "successfully loaded" line, then what was held back */
         total_queries = ld->total_queries;
         if (ld->failed) pipeline_fail("Internal error: the query files came in more pieces than planned");
+        if (ld->invalid) { /* the loader thread met a query file that is no valid FASTQ (it said so), or ran out of memory */
+            shutdown_pipeline();
+            fclose(out);
+            remove(out_name);
+            exit_message(ld->invalid == 1 ? "A query file is not valid FASTQ" : "Out of memory");
+        }
+        if (ld->fasta_seen) fprintf(stderr, "> WARNING: option -bq %d has no effect on FASTA queries: they carry no base qualities\n", min_bq);
         if (ld->ready == 0) { /* slamem.c:648 (an overlapped run only knows it now) */
             shutdown_pipeline();
             fclose(out);
@@ -1513,7 +1575,8 @@ int main(int argc, char **argv) {
         slh_free_seqset(&ref);
         for (f = 0; f < g_reap_n; f++) pthread_join(g_reap_tid[f], NULL);
         free(g_reap_tid);
-        for (f = 0; f < g_ld.ready; f++) slh_free_seqset(&qsets[f]);
+        for (f = 0; f < g_ld.ready; f++) { slh_free_seqset(&qsets[f]); free(g_ld.masks[f]); }
+        free(g_ld.masks);
         free(qsets);
         pthread_mutex_lock(&g_pool_mu);
         while (g_pool_n > 0) slh_buffer_free(&g_pool[--g_pool_n]);

@@ -346,6 +346,164 @@ fail:
 }
 
 
+/* ---- FASTQ query files ---------------------------------------------------------------------------
+ * A file whose first byte is '@'.  Its lines are what '\n' separates (a final '\n' ends the last line and starts none; a '\r' at
+ * a line's end is dropped); they come in records of four: '@' and the name, the letters, a line that starts with '+', and as
+ * many quality bytes as the second line has letter bytes.  Anything else -- another first byte, a third line without '+',
+ * unequal lengths, a number of lines that is no multiple of four -- makes the file invalid.  The letters go through the table
+ * of the FASTA loader (init_table), and a byte that the table drops takes its quality byte with it, so that quals stays
+ * parallel to chars.  Records are numbered, logged, dropped when empty or shorter than min_len as FASTA records are. */
+#define FASTQ_INVALID (-1)
+#define FASTQ_NOMEM (-2)
+
+static const unsigned char *fastq_line(const unsigned char *p, const unsigned char *end, const unsigned char **next) {
+    const unsigned char *nl = (const unsigned char *)memchr(p, '\n', (size_t)(end - p));
+    const unsigned char *le = nl ? nl : end;
+    *next = nl ? nl + 1 : end;
+    if (le > p && le[-1] == '\r') le--;
+    return le;
+}
+
+/* the records of one memory range that starts at a record's '@': their number, FASTQ_INVALID or FASTQ_NOMEM (nothing is
+ * printed for those two: the caller does, once) */
+static int load_fastq_mem(const unsigned char *data, long fsize, int acgt_only, uint32_t min_len, int first_number, long log_limit,
+                          slh_seqset *out, char **quals_out, FILE *log) {
+    char table[256];
+    const unsigned char *p = data, *end = data + fsize;
+    int numseqs = 0, reccap = 0, k, rc = FASTQ_NOMEM;
+    uint64_t seqlen = 0, cap = 0, qcap = 0, offcap = 0;
+    long logged = 0;
+    char *chars = NULL, *quals = NULL;
+
+    memset(out, 0, sizeof(*out));
+    *quals_out = NULL;
+    out->file_bytes = fsize;
+    init_table(table, !acgt_only);
+    /* (two lines of a record's four hold as many bytes each as it has letters at most) */
+    if (grow(&chars, &cap, (uint64_t)fsize / 2 + 16) || grow(&quals, &qcap, (uint64_t)fsize / 2 + 16)) goto fail;
+    while (p < end) {
+        const unsigned char *name, *name_end, *seq, *seq_end, *plus, *plus_end, *ql, *ql_end, *next;
+        uint64_t rec_start = seqlen;
+        uint32_t seqsize;
+        int quiet, desclen;
+        if (*p != '@') { rc = FASTQ_INVALID; goto fail; }
+        name = p + 1;
+        name_end = fastq_line(p, end, &next);
+        if (name_end < name) name_end = name; /* (the line "@\r" cannot occur: the '@' is no '\r') */
+        seq = next;
+        if (seq >= end) { rc = FASTQ_INVALID; goto fail; } /* truncated: no second line */
+        seq_end = fastq_line(seq, end, &next);
+        plus = next;
+        if (plus >= end || *plus != '+') { rc = FASTQ_INVALID; goto fail; }
+        plus_end = fastq_line(plus, end, &next);
+        (void)plus_end;
+        ql = next;
+        if (ql >= end) { rc = FASTQ_INVALID; goto fail; } /* truncated: no fourth line */
+        ql_end = fastq_line(ql, end, &next);
+        if (ql_end - ql != seq_end - seq) { rc = FASTQ_INVALID; goto fail; }
+        p = next;
+        desclen = (int)(name_end - name);
+        quiet = !log || (log_limit > 0 && logged >= log_limit);
+        if (!quiet) {
+            fprintf(log, "# %02d [", first_number + numseqs);
+            for (k = 0; k < desclen && k < 50; k++) fputc(name[k], log);
+            for (k = desclen; k < 50; k++) fputc(' ', log);
+            fprintf(log, "] ");
+        }
+        {
+            unsigned char *dst = (unsigned char *)chars + seqlen, *qdst = (unsigned char *)quals + seqlen;
+            const size_t len = (size_t)(seq_end - seq);
+            size_t i;
+            if (line_of_letters(dst, seq, len, !acgt_only)) { /* nothing is dropped: the qualities as they are */
+                memcpy(qdst, ql, len);
+                seqsize = (uint32_t)len;
+            } else {
+                size_t w = 0;
+                for (i = 0; i < len; i++) {
+                    const unsigned char t = (unsigned char)table[seq[i]];
+                    if (!t) continue;
+                    dst[w] = t;
+                    qdst[w] = ql[i];
+                    w++;
+                }
+                seqsize = (uint32_t)w;
+            }
+            seqlen += seqsize;
+        }
+        if (seqsize == 0) {
+            if (!quiet) { fprintf(log, "EMPTY\n"); logged++; }
+            continue;
+        }
+        if (min_len != 0 && seqsize < min_len) {
+            if (!quiet) { fprintf(log, "(%u bp) TOO SHORT\n", seqsize); logged++; }
+            seqlen = rec_start;
+            continue;
+        }
+        if (!quiet) fprintf(log, "(%u bp) ", seqsize);
+        if (numseqs == reccap) {
+            int nc = reccap ? reccap * 2 : 64;
+            slh_record *nr = (slh_record *)realloc(out->recs, (size_t)nc * sizeof(slh_record));
+            if (!nr) goto fail;
+            out->recs = nr;
+            reccap = nc;
+        }
+        out->recs[numseqs].name = name_alloc(&out->name_arena, (size_t)desclen + 1);
+        if (!out->recs[numseqs].name) goto fail;
+        memcpy(out->recs[numseqs].name, name, (size_t)desclen);
+        out->recs[numseqs].name[desclen] = '\0';
+        out->recs[numseqs].size = seqsize;
+        if ((uint64_t)numseqs + 2 > offcap) {
+            uint64_t nc = offcap ? offcap * 2 : 1024;
+            uint64_t *no = (uint64_t *)realloc(out->offsets, nc * sizeof(uint64_t));
+            if (!no) goto fail;
+            out->offsets = no;
+            offcap = nc;
+        }
+        out->offsets[numseqs] = rec_start;
+        out->offsets[numseqs + 1] = seqlen;
+        numseqs++;
+        out->num = numseqs;
+        if (!quiet) { fprintf(log, "OK\n"); logged++; }
+        else if (log && log_limit > 0 && logged == log_limit) {
+            fprintf(log, "# ... (further records of this file are loaded without a line each)\n");
+            logged++;
+        }
+    }
+    if (numseqs == 0) {
+        free(chars);
+        free(quals);
+        slh_free_seqset(out);
+        out->file_bytes = fsize;
+        return 0;
+    }
+    memset(chars + seqlen, 0, 16);
+    memset(quals + seqlen, 0, 16);
+    out->chars = chars;
+    out->total = seqlen;
+    *quals_out = quals;
+    return numseqs;
+fail:
+    free(chars);
+    free(quals);
+    slh_free_seqset(out);
+    return rc;
+}
+
+/* the first record start at or behind `target`, found by counting lines from the record start `from` (a '@' may begin a
+ * quality line, so "newline + '@'" alone is no record start; four lines on from a record start is one) */
+static long fastq_cut(const unsigned char *data, long from, long fsize, long target) {
+    long p = from;
+    while (p < fsize && p < target) {
+        int k;
+        for (k = 0; k < 4; k++) {
+            const unsigned char *nl = (const unsigned char *)memchr(data + p, '\n', (size_t)(fsize - p));
+            if (!nl) return fsize;
+            p = (long)(nl - data) + 1;
+        }
+    }
+    return p;
+}
+
 /* ---- parallel loading of large query files ------------------------------------------------------- */
 #include <pthread.h>
 #include <sys/mman.h>
@@ -364,11 +522,16 @@ typedef struct {
     slh_seqset *dst;   /* second phase: this piece is copied to characters dst_cpos.. / records dst_rpos.. of dst */
     uint64_t dst_cpos;
     int dst_rpos;
+    int fastq;         /* the range holds FASTQ records: quals is parallel to set.chars, and goes to dst_quals as they go to dst */
+    char *quals, *dst_quals;
 } load_job;
 
 static void *load_job_run(void *arg) {
     load_job *j = (load_job *)arg;
-    j->n = j->size > 0 ? load_mem(j->data, j->size, 0, j->acgt_only, j->min_len, NULL, j->first_number, j->log_limit, &j->set, j->log) : 0;
+    if (j->size <= 0) j->n = 0;
+    else if (j->fastq)
+        j->n = load_fastq_mem(j->data, j->size, j->acgt_only, j->min_len, j->first_number, j->log_limit, &j->set, &j->quals, j->log);
+    else j->n = load_mem(j->data, j->size, 0, j->acgt_only, j->min_len, NULL, j->first_number, j->log_limit, &j->set, j->log);
     return NULL;
 }
 
@@ -378,8 +541,13 @@ static void *concat_job_run(void *arg) {
     load_job *j = (load_job *)arg;
     const slh_seqset *s = &j->set;
     int i;
-    if (j->n == 0) return NULL;
+    if (j->n <= 0) return NULL;
     memcpy(j->dst->chars + j->dst_cpos, s->chars, s->total);
+    if (j->quals) {
+        memcpy(j->dst_quals + j->dst_cpos, j->quals, s->total);
+        free(j->quals);
+        j->quals = NULL;
+    }
     memcpy(j->dst->recs + j->dst_rpos, s->recs, (size_t)s->num * sizeof(slh_record));
     for (i = 0; i < s->num; i++) j->dst->offsets[j->dst_rpos + i] = s->offsets[i] + j->dst_cpos;
     slh_free_seqset(&j->set); /* its names were handed over before; unmapping 100 MB pieces is worth doing in parallel too */
@@ -398,12 +566,16 @@ int slh_thread_count(void) {
  * lines, and in sequence context any '>' starts a record, sequence.c:157) and parsed by several threads; the
  * pieces are concatenated in order, so the result equals the sequential parse.  The per-record log lines come from
  * the first piece only (they are limited to the first log_limit records anyway). */
+/* A FASTQ range (fastq; it starts at a record start) is cut by counting lines from its start (fastq_cut), since there a '@'
+ * after a newline may begin a quality line: one pass of memchr over the range in front of the threads, and every piece is parsed
+ * by one thread.  *quals_out gets the qualities, parallel to out->chars; a piece that is no valid FASTQ makes the whole range
+ * FASTQ_INVALID.  Returns -1 when memory runs out (the caller parses in one piece then). */
 static int load_parallel(const unsigned char *data, long fsize, int acgt_only, uint32_t min_len, int first_number,
-                         long log_limit, slh_seqset *out, FILE *log, int threads) {
+                         long log_limit, slh_seqset *out, FILE *log, int threads, int fastq, char **quals_out) {
     load_job *jobs = (load_job *)calloc((size_t)threads, sizeof(load_job));
     pthread_t *tid = (pthread_t *)calloc((size_t)threads, sizeof(pthread_t));
     long *cut = (long *)calloc((size_t)threads + 1, sizeof(long));
-    int t, total = 0, ok = 1;
+    int t, total = 0, ok = 1, bad = 0;
     uint64_t chars_total = 0;
     if (!jobs || !tid || !cut) { free(jobs); free(tid); free(cut); return -1; }
     cut[0] = 0;
@@ -411,6 +583,8 @@ static int load_parallel(const unsigned char *data, long fsize, int acgt_only, u
     for (t = 1; t < threads; t++) {
         long p = fsize / threads * t;
         if (p < cut[t - 1]) p = cut[t - 1];
+        if (fastq) p = fastq_cut(data, cut[t - 1], fsize, p);
+        else
         while (p < fsize && !(data[p] == '>' && p > 0 && (data[p - 1] == '\n' || data[p - 1] == '\r'))) p++;
         cut[t] = p;
     }
@@ -422,17 +596,25 @@ static int load_parallel(const unsigned char *data, long fsize, int acgt_only, u
         jobs[t].first_number = first_number;
         jobs[t].log_limit = log_limit;
         jobs[t].log = t == 0 ? log : NULL;
+        jobs[t].fastq = fastq;
         if (pthread_create(&tid[t], NULL, load_job_run, &jobs[t]) != 0) { load_job_run(&jobs[t]); tid[t] = 0; }
     }
     for (t = 0; t < threads; t++) if (tid[t]) pthread_join(tid[t], NULL);
-    for (t = 0; t < threads; t++) { total += jobs[t].n; chars_total += jobs[t].set.total; }
+    for (t = 0; t < threads; t++) {
+        if (jobs[t].n < 0) { bad = jobs[t].n == FASTQ_INVALID ? FASTQ_INVALID : -1; jobs[t].n = 0; }
+        total += jobs[t].n;
+        chars_total += jobs[t].set.total;
+    }
     memset(out, 0, sizeof(*out));
     out->file_bytes = fsize;
-    if (total > 0) {
+    if (quals_out) *quals_out = NULL;
+    if (total > 0 && !bad) {
+        char *quals = NULL;
         out->recs = (slh_record *)slh_big_malloc((size_t)total * sizeof(slh_record));
         out->offsets = (uint64_t *)slh_big_malloc(((size_t)total + 1) * sizeof(uint64_t));
         out->chars = (char *)slh_big_malloc(chars_total + 16);
-        if (!out->recs || !out->offsets || !out->chars) ok = 0;
+        if (fastq) quals = (char *)slh_big_malloc(chars_total + 16);
+        if (!out->recs || !out->offsets || !out->chars || (fastq && !quals)) { ok = 0; free(quals); }
         else {
             uint64_t cpos = 0;
             int rpos = 0;
@@ -441,6 +623,7 @@ static int load_parallel(const unsigned char *data, long fsize, int acgt_only, u
                 jobs[t].dst = out;
                 jobs[t].dst_cpos = cpos;
                 jobs[t].dst_rpos = rpos;
+                jobs[t].dst_quals = quals;
                 if (jobs[t].n == 0) continue;
                 cpos += s->total;
                 rpos += s->num;
@@ -457,23 +640,30 @@ static int load_parallel(const unsigned char *data, long fsize, int acgt_only, u
             for (t = 0; t < threads; t++) if (tid[t]) pthread_join(tid[t], NULL);
             out->offsets[total] = cpos;
             memset(out->chars + cpos, 0, 16);
+            if (quals) memset(quals + cpos, 0, 16);
             out->total = cpos;
             out->num = total;
+            if (quals_out) *quals_out = quals;
+            else free(quals);
         }
     }
-    for (t = 0; t < threads; t++) slh_free_seqset(&jobs[t].set);
+    for (t = 0; t < threads; t++) { slh_free_seqset(&jobs[t].set); free(jobs[t].quals); }
     free(jobs); free(tid); free(cut);
+    if (bad) { slh_free_seqset(out); return bad; }
     if (!ok) { slh_free_seqset(out); return -1; }
     return total;
 }
 
-int slh_load_file(const char *path, int merge, int acgt_only, uint32_t min_len, const char *name_filter,
-                  int first_number, long log_limit, slh_seqset *out, FILE *log) {
+/* fastq_ok: a file whose first byte is '@' is read as FASTQ (a query file) or refused by name (the reference file); without
+ * it such a file is what it was before FASTQ was read: "not FASTA" */
+static int load_file(const char *path, int merge, int acgt_only, uint32_t min_len, const char *name_filter, int first_number,
+                     long log_limit, slh_seqset *out, char **quals_out, int fastq_ok, FILE *log) {
     FILE *f;
     unsigned char *data = NULL;
     long fsize;
     int n, threads, mapped = 0;
     memset(out, 0, sizeof(*out));
+    if (quals_out) *quals_out = NULL;
     if (log) fprintf(log, "> Loading sequences from file <%s> ... ", path);
     f = fopen(path, "rb");
     if (!f) {
@@ -500,8 +690,25 @@ int slh_load_file(const char *path, int merge, int acgt_only, uint32_t min_len, 
     }
     fclose(f);
     threads = slh_thread_count();
+    if (fastq_ok && fsize > 0 && data[0] == '@') {
+        char *quals = NULL;
+        if (merge) {
+            if (log) fprintf(log, "> ERROR: The reference file is FASTQ: the reference must be FASTA\n");
+            n = -1;
+        } else {
+            n = -1;
+            if (threads > 1 && fsize > (64L << 20) && log_limit > 0)
+                n = load_parallel(data, fsize, acgt_only, min_len, first_number, log_limit, out, log, threads, 1, &quals);
+            if (n == -1) n = load_fastq_mem(data, fsize, acgt_only, min_len, first_number, log_limit, out, &quals, log);
+            if (n == FASTQ_INVALID && log) fprintf(log, "> ERROR: Invalid FASTQ file\n");
+            if (n == FASTQ_NOMEM && log) fprintf(log, "\n> ERROR: Out of memory while loading sequences\n");
+            if (n < 0) n = -1;
+            if (quals_out) *quals_out = quals;
+            else free(quals);
+        }
+    } else
     if (!merge && threads > 1 && fsize > (64L << 20) && log_limit > 0 && data[0] == '>') {
-        n = load_parallel(data, fsize, acgt_only, min_len, first_number, log_limit, out, log, threads);
+        n = load_parallel(data, fsize, acgt_only, min_len, first_number, log_limit, out, log, threads, 0, NULL);
         if (n < 0) n = load_mem(data, fsize, merge, acgt_only, min_len, name_filter, first_number, log_limit, out, log);
     } else {
         n = load_mem(data, fsize, merge, acgt_only, min_len, name_filter, first_number, log_limit, out, log);
@@ -509,6 +716,16 @@ int slh_load_file(const char *path, int merge, int acgt_only, uint32_t min_len, 
     if (mapped) munmap(data, (size_t)fsize);
     else free(data);
     return n;
+}
+
+int slh_load_file(const char *path, int merge, int acgt_only, uint32_t min_len, const char *name_filter,
+                  int first_number, long log_limit, slh_seqset *out, FILE *log) {
+    return load_file(path, merge, acgt_only, min_len, name_filter, first_number, log_limit, out, NULL, 0, log);
+}
+
+int slh_load_file_q(const char *path, int merge, int acgt_only, uint32_t min_len, const char *name_filter,
+                    int first_number, long log_limit, slh_seqset *out, char **quals_out, FILE *log) {
+    return load_file(path, merge, acgt_only, min_len, name_filter, first_number, log_limit, out, quals_out, 1, log);
 }
 
 /* ---- a query file in pieces ----------------------------------------------------------------------------------
@@ -524,6 +741,7 @@ struct slh_pieces {
     long log_limit;
     FILE *log;
     int release_parsed; /* drop the file pages of a piece once it is parsed (slh_pieces_release_parsed) */
+    int fastq;          /* slh_pieces_next_q found a '@' at the file's start: its records are FASTQ */
 };
 
 slh_pieces *slh_pieces_open(const char *path, int acgt_only, uint32_t min_len, int first_number, long log_limit,
@@ -568,29 +786,51 @@ slh_pieces *slh_pieces_open(const char *path, int acgt_only, uint32_t min_len, i
     return p;
 }
 
-/* the next piece: number of records (> 0), 0 at the end of the file (or when the file holds no record at all) */
-int slh_pieces_next(slh_pieces *p, slh_seqset *out) {
+/* the next piece: number of records (> 0), 0 at the end of the file (or when the file holds no record at all).  fastq_ok (and
+ * quals_out) as for load_file; -1: the file is no valid FASTQ, said on the log */
+static int pieces_next(slh_pieces *p, slh_seqset *out, char **quals_out, int fastq_ok) {
     memset(out, 0, sizeof(*out));
+    if (quals_out) *quals_out = NULL;
+    if (p->first && fastq_ok && p->fsize > 0 && p->data[0] == '@') p->fastq = 1;
     while (p->pos < p->fsize) {
         long start = p->pos, end = start + p->piece_bytes;
         int n;
         if (end >= p->fsize) end = p->fsize;
+        else if (p->fastq) end = fastq_cut(p->data, start, p->fsize, end); /* (start is a record start: lines are counted from it) */
         else {
             while (end < p->fsize && !(p->data[end] == '>' && (p->data[end - 1] == '\n' || p->data[end - 1] == '\r'))) end++;
         }
         p->pos = end;
-        if (p->first && p->data[start] != '>') {  /* as load_mem: a file that does not start with '>' is not FASTA */
+        if (p->first && !p->fastq && p->data[start] != '>') {  /* as load_mem: a file that does not start with '>' is not FASTA */
             if (p->log) fprintf(p->log, "> WARNING: Invalid FASTA file\n");
             p->pos = p->fsize;
             return 0;
         }
+        if (p->fastq) {
+            char *quals = NULL;
+            n = -1;
+            if (p->threads > 1 && end - start > (16L << 20) && p->log_limit > 0)
+                n = load_parallel(p->data + start, end - start, p->acgt_only, p->min_len, p->first_number, p->log_limit, out,
+                                  p->first ? p->log : NULL, p->threads, 1, &quals);
+            if (n == -1)
+                n = load_fastq_mem(p->data + start, end - start, p->acgt_only, p->min_len, p->first_number, p->log_limit, out, &quals,
+                                   p->first ? p->log : NULL);
+            if (n < 0) {
+                if (p->log) fprintf(p->log, n == FASTQ_INVALID ? "> ERROR: Invalid FASTQ file\n" : "\n> ERROR: Out of memory while loading sequences\n");
+                p->pos = p->fsize;
+                return -1;
+            }
+            if (quals_out) *quals_out = quals;
+            else free(quals);
+        } else {
         if (p->threads > 1 && end - start > (16L << 20) && p->log_limit > 0)
             n = load_parallel(p->data + start, end - start, p->acgt_only, p->min_len, p->first_number, p->log_limit, out,
-                              p->first ? p->log : NULL, p->threads);
+                              p->first ? p->log : NULL, p->threads, 0, NULL);
         else n = -1;
         if (n < 0)
             n = load_mem(p->data + start, end - start, 0, p->acgt_only, p->min_len, NULL, p->first_number, p->log_limit, out,
                          p->first ? p->log : NULL);
+        }
         p->first = 0;
         if (p->release_parsed && p->mapped && end - start > (1L << 20)) { /* the parsed part of the file is not read again */
             long a = (start + 4095) & ~4095L, b = end & ~4095L;
@@ -601,6 +841,10 @@ int slh_pieces_next(slh_pieces *p, slh_seqset *out) {
     }
     return 0;
 }
+
+int slh_pieces_next(slh_pieces *p, slh_seqset *out) { return pieces_next(p, out, NULL, 0); }
+
+int slh_pieces_next_q(slh_pieces *p, slh_seqset *out, char **quals_out) { return pieces_next(p, out, quals_out, 1); }
 
 void slh_pieces_release_parsed(slh_pieces *p, int on) {
     if (p) p->release_parsed = on;
@@ -756,6 +1000,24 @@ int slh_parse_min_mapq(int argc, char **argv, int *out) {
     return 0;
 }
 
+int slh_parse_min_bq(int argc, char **argv, int *out) {
+    int i;
+    *out = 0;
+    for (i = 1; i < argc; i++) {
+        char *end;
+        long v;
+        /* the two letters "bq" decide ("-b" alone, the strand switch, is exactly two characters long); it takes the next argument */
+        if (!two_letter_option(argv[i], 'b', 'q')) continue;
+        if (i == argc - 1) return -1;
+        errno = 0;
+        v = strtol(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 0 || v > 93) return -1;
+        *out = (int)v;
+        return 1;
+    }
+    return 0;
+}
+
 int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out) {
     int i, seen = 0;
     *min_depth_out = 4;
@@ -875,6 +1137,7 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
             if (two_letter_option(argv[i], 'v', 'c')) {} /* -vcf takes no value ("-v" alone is the image tool and does) */
             else if (oc == 'l' || oc == 'o' || oc == 'm' || oc == 'v') i++; /* any option starting with l/o/m/v eats the next argument */
             else if (two_letter_option(argv[i], 'e', 'v')) i++; /* -evs N (of -vcf) */
+            else if (two_letter_option(argv[i], 'b', 'q')) i++; /* -bq N (of -pile and its read-outs; "-b" alone takes none) */
             else if (two_letter_option(argv[i], 'w', 'i')) i++; /* -win N (of -depth; its -lev LIST begins with l) */
             else if (two_letter_option(argv[i], 'p', 'e') || two_letter_option(argv[i], 'x', 'd')) i++; /* -pen N, -xdrop N (of -ext) */
             else if (oc == 'r') {

@@ -40,12 +40,26 @@ typedef struct {
 int slh_load_file(const char *path, int merge, int acgt_only, uint32_t min_len, const char *name_filter,
                   int first_number, long log_limit, slh_seqset *out, FILE *log);
 void slh_free_seqset(slh_seqset *s);
+/* The same for a file that may be FASTQ (its first byte is '@'): four lines a record -- '@' and the name, kept
+ * as FASTA keeps what follows '>'; the letters; a line that starts with '+'; as many quality bytes as the second line has letter
+ * bytes; "\r\n" is accepted.  The letters go through the FASTA rules, and a letter they drop drops its quality byte with it.
+ * *quals_out (release with free()) is parallel to out->chars: the quality byte of every kept letter, as the file has it; NULL for
+ * a FASTA file, and quals_out may be NULL (the qualities are dropped).  slh_seqset is as it was: callers mirror its layout.
+ * Returns -1, with "> ERROR: Invalid FASTQ file" on the log, for a file that breaks the four-line rule (a first byte that is no
+ * '@', a third line without '+', unequal lengths, a last record cut short), and -1 with a message of its own for merge=1: the
+ * reference file stays FASTA.  A FASTA file: exactly slh_load_file. */
+int slh_load_file_q(const char *path, int merge, int acgt_only, uint32_t min_len, const char *name_filter,
+                    int first_number, long log_limit, slh_seqset *out, char **quals_out, FILE *log);
 /* A query file handed out in consecutive pieces of about piece_bytes of the file each (the same records as
  * slh_load_file(path, 0, ...) would give in one set): a front end searches the first reads while the rest is parsed. */
 typedef struct slh_pieces slh_pieces;
 slh_pieces *slh_pieces_open(const char *path, int acgt_only, uint32_t min_len, int first_number, long log_limit,
                             long piece_bytes, FILE *log);
 int slh_pieces_next(slh_pieces *p, slh_seqset *out); /* records in the piece; 0 at the end */
+/* the same for a file that may be FASTQ: *quals_out as for slh_load_file_q (NULL for FASTA), -1 for an invalid FASTQ file.  A
+ * FASTQ file is cut into pieces, and a piece into the parser threads' shares, by counting lines from a known record start: a '@'
+ * behind a newline may begin a quality line. */
+int slh_pieces_next_q(slh_pieces *p, slh_seqset *out, char **quals_out);
 void slh_pieces_close(slh_pieces *p);
 /* on: the page-cache mapping of every parsed piece is dropped at once (for inputs whose footprint matters more than the
  * address-space work this causes beside the other threads; off by default) */
@@ -98,6 +112,11 @@ int slh_parse_max_edits(int argc, char **argv, int *out);
  * 1 when it is, -1 when the value is missing, not an integer or out of range.  It begins with -m, so its value is never taken
  * for a file name. */
 int slh_parse_min_mapq(int argc, char **argv, int *out);
+/* -bq N (-bq...): the least base quality of a read letter that counts in -pile and its read-outs, a whole number in [0, 93]; 0:
+ * every letter counts.  0 when it is not there (*out = 0), 1 when it is, -1 when the value is missing, not an integer or out of
+ * range.  "-b" (both strands) is a one-letter option and matches two characters exactly, so neither is taken for the other; the
+ * value of -bq is never taken for a file name. */
+int slh_parse_min_bq(int argc, char **argv, int *out);
 /* -mdep N (-md...) and -mpct P (-mp...): the least depth (N in [1, 2^31)) and the least share of the depth in percent (P in
  * [0, 100]) of -sites.  0 when neither is there (*min_depth_out = 4, *min_pct_out = 20: the defaults), 1 when at least one is,
  * -1 when the value of -mdep is missing, not an integer or out of range, -2 when that of -mpct is.  Both begin with -m, so their
