@@ -438,6 +438,33 @@ int slamem_find_maps_device(const slamem_index *idx, const void *queries_dev, co
                             uint64_t ops_capacity, uint64_t *op_offsets_dev, slamem_map *reads_dev, void *workspace_dev,
                             uint64_t workspace_bytes, void *stream, uint64_t *totals_out);
 
+/* ---- (b'+) what SAM needs of a mapped batch (option -sam) ------------------------------------------------------
+ * Behind slamem_find_maps_device, over its outputs as they lie on the device: the MD entries of every segment, its letters under
+ * `=`, and the primary segment of every read.  Segment s has the entries md_dev[md_offsets_dev[s] .. md_offsets_dev[s + 1]): one
+ * uint32 per reference letter under X or D, left to right, `m << 4 | d << 2 | c` -- m the reference letters under `=` since the
+ * segment's last entry (or its start; an I changes nothing), d 1 under D, c the text's letter there, A C G T = 0..3 -- and a
+ * closing entry `m << 4 | 8`.  (m is below 2^28: a longer run of `=` is outside the contract.)  seg_eq_dev[s] is the letters
+ * under `=` of segment s; primary_dev[r] the segment of read r with the largest of them, the first on a tie, as an index into the
+ * read's range read_offsets_dev[r] .., 0xFFFFFFFF for a read without segments.
+ *   md_capacity   the entries md_dev has room for.  The batch has (letters under X) + (letters under D) + num_segs of them, at
+ *                 most (sum of the segments' edits) + num_segs: with that much room the call cannot fail for want of it.  Too
+ *                 little: SLAMEM_ERR_CAPACITY, *md_total the need, and no word at or behind md_dev[md_capacity] is written.
+ *   md_offsets_dev  num_segs + 1 entries.  num_segs == 0 is valid: md_offsets_dev[0] = 0, every primary 0xFFFFFFFF.
+ * Everything runs on `stream`; the call ends with one copy of the total to the host and waits for it.  The letters come from the
+ * text planes of the index: one without them (the COMPACT layout) is refused with SLAMEM_ERR_ARG and nothing is run.  The
+ * workspace is slamem_maps_md_workspace_bytes() bytes.  slamem_find_maps_md_host: slamem_find_maps_host plus the four arrays
+ * (malloc()ed, released with slamem_host_free) and their number of entries. */
+int slamem_maps_md_workspace_bytes(uint64_t num_segs, uint32_t num_queries, uint64_t *bytes_out);
+int slamem_maps_md_device(const slamem_index *idx, const slamem_aln *segs_dev, uint64_t num_segs, const uint64_t *read_offsets_dev,
+                          uint32_t num_queries, const uint32_t *ops_dev, const uint64_t *op_offsets_dev, uint32_t *md_dev,
+                          uint64_t md_capacity, uint64_t *md_offsets_dev /* num_segs + 1 */, uint32_t *seg_eq_dev,
+                          uint32_t *primary_dev, void *workspace_dev, uint64_t workspace_bytes, void *stream, uint64_t *md_total);
+int slamem_find_maps_md_host(const slamem_index *idx, const char *queries, const uint64_t *offsets, uint32_t num_queries,
+                             uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
+                             uint32_t max_edits, slamem_aln **segs_out, uint64_t **read_offsets_out, uint32_t **ops_out,
+                             uint64_t **op_offsets_out, slamem_map **reads_out, uint64_t *totals_out, uint32_t **md_out,
+                             uint64_t **md_offsets_out, uint32_t **seg_eq_out, uint32_t **primary_out, uint64_t *md_total_out);
+
 /* ---- (b'') per-base pileup of the read mappings (option -pile: matchType 8) ----------------------------------
  * What a user does with -paf's mappings: pile them onto the reference.  With n the merged text's length the table has n rows of
  * six uint32 counters in the order A, C, G, T, D, I.  A read contributes iff its record has strand != 0 and mapq >= min_mapq;
@@ -765,6 +792,14 @@ int slamem_stream_alns(slamem_stream *s, const slamem_aln **segs_out, const uint
  * valid as long as that batch.  Its segments and operations come through slamem_stream_alns. */
 int slamem_stream_maps(slamem_stream *s, const slamem_map **reads_out);
 int slamem_stream_set_pileup(slamem_stream *s, slamem_pileup *pile, uint32_t min_mapq);
+/* -sam: on != 0 makes every slot of a stream of match type 7 run slamem_maps_md_device behind its batch and
+ * download the four arrays; before the first submit (SLAMEM_ERR_ARG after it, or on a stream of another match type).  A stream
+ * that never calls it behaves as before and allocates nothing for this.  slamem_stream_md gives the arrays of the batch
+ * slamem_stream_next returned last, in the stream's pinned memory, valid as long as that batch: *num_md_out entries, segments + 1
+ * offsets, a uint32 per segment, a uint32 per read.  SLAMEM_ERR_ARG on a stream whose MD pass is not switched on. */
+int slamem_stream_set_md(slamem_stream *s, int on);
+int slamem_stream_md(slamem_stream *s, const uint32_t **md_out, const uint64_t **md_offsets_out, const uint32_t **seg_eq_out,
+                     const uint32_t **primary_out, uint64_t *num_md_out);
 int slamem_stream_submit(slamem_stream *s, const char *queries, const uint64_t *offsets, uint32_t num_queries,
                          uint32_t min_len);
 /* -pile with a low-quality mask: slamem_stream_submit for a stream of match type 8, with `lowq` indexed as

@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "slamem_find_alns_workspace_bytes", "slamem_find_alns_device", "slamem_find_alns_host",
     "slamem_stream_set_max_edits", "slamem_stream_alns",
     "slamem_find_maps_workspace_bytes", "slamem_find_maps_device", "slamem_find_maps_host", "slamem_stream_maps",
+    "slamem_maps_md_workspace_bytes", "slamem_maps_md_device", "slamem_find_maps_md_host", "slamem_stream_set_md", "slamem_stream_md",
     "slamem_pileup_create", "slamem_pileup_free", "slamem_pileup_reset", "slamem_pileup_add_device",
     "slamem_pileup_counts_device", "slamem_pileup_counts_host", "slamem_stream_set_pileup",
     "slamem_pileup_sites_device", "slamem_pileup_sites_host", "slamem_pileup_add_counts_device", "slamem_pileup_add_counts_host",
@@ -186,6 +187,13 @@ def _declare(L):
     L.slamem_find_maps_host.argtypes = [vp, C.c_char_p, vp, u32, u32, i32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(vp),
                                         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.slamem_stream_maps.argtypes = [vp, C.POINTER(vp)]
+    L.slamem_maps_md_workspace_bytes.argtypes = [u64, u32, C.POINTER(u64)]
+    L.slamem_maps_md_device.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
+    L.slamem_find_maps_md_host.argtypes = [vp, C.c_char_p, vp, u32, u32, i32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(vp),
+                                           C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp),
+                                           C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    L.slamem_stream_set_md.argtypes = [vp, i32]
+    L.slamem_stream_md.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.slamem_pileup_create.argtypes = [vp, C.POINTER(vp)]
     L.slamem_pileup_free.argtypes = [vp]
     L.slamem_pileup_reset.argtypes = [vp]

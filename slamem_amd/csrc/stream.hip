@@ -74,6 +74,15 @@ struct Slot {
     slamem_map* d_reads = nullptr;
     slamem_map* h_reads = nullptr;
     uint64_t h_reads_cap = 0;
+    // -sam (slamem_stream_set_md): the MD entries (room for md_cap), their offsets and the letters under `=` per segment (room
+    // for md_segs_cap segments), the primary segment per read (room for md_q_cap), and the pass's workspace; nothing of it
+    // exists on a stream whose MD pass is off
+    uint32_t *d_md = nullptr, *d_seg_eq = nullptr, *d_primary = nullptr;
+    uint64_t* d_md_off = nullptr;
+    void* d_md_ws = nullptr;
+    uint32_t *h_md = nullptr, *h_seg_eq = nullptr, *h_primary = nullptr;
+    uint64_t* h_md_off = nullptr;
+    uint64_t md_cap = 0, md_segs_cap = 0, md_q_cap = 0, md_ws_bytes = 0, h_md_cap = 0, md_total = 0;
     // the batch
     uint64_t seq = 0;
     const char* chars = nullptr;
@@ -113,6 +122,7 @@ using namespace slamem;
 
 struct slamem_stream {
     const slamem_index* idx = nullptr;
+    int device = 0;  // idx->device, kept so that slamem_stream_destroy does not read the index
     int nslots = 0, both = 0, match_type = 0;
     uint32_t max_occ = 0;  // -smem: the occurrence cap of every batch (slamem_stream_set_max_occ; 0: none)
     uint32_t max_gap = 0;  // -chain: the maximum gap of every batch (slamem_stream_set_max_gap; 0: the default)
@@ -120,6 +130,7 @@ struct slamem_stream {
     uint32_t max_edits = kAlnEditsUnset;  // -aln: the most edits in a gap (slamem_stream_set_max_edits; kAlnEditsUnset: the default)
     slamem_pileup* pile = nullptr;          // -pile: the accumulator every batch is added to (slamem_stream_set_pileup)
     uint32_t min_mapq = 0;                  // -pile: the least mapping quality that counts
+    bool md = false;                        // -sam: every batch also goes through the MD pass (slamem_stream_set_md)
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     Slot slot[kMaxSlots];
@@ -478,6 +489,63 @@ int stage_search(slamem_stream* s, Slot& sl, bool failed, bool* issued_only) {
     return rc;
 }
 
+// -sam: the MD pass over the batch's segments as they lie on the device (sam_filter.hip), and its four arrays to pinned host
+// memory.  The entries' room starts at operations + segments (an entry per X or D letter: a first guess) and grows to what
+// SLAMEM_ERR_CAPACITY tells.
+int stage_md(slamem_stream* s, Slot& sl, hipStream_t st) {
+    const uint64_t ns = sl.total;
+    if (sl.md_segs_cap < ns + 1 || !sl.d_md_off) {
+        if (sl.d_md_off) (void)hipFree(sl.d_md_off);
+        if (sl.d_seg_eq) (void)hipFree(sl.d_seg_eq);
+        if (sl.d_md_ws) (void)hipFree(sl.d_md_ws);
+        if (sl.h_md_off) (void)hipHostFree(sl.h_md_off);
+        if (sl.h_seg_eq) (void)hipHostFree(sl.h_seg_eq);
+        sl.d_md_off = nullptr; sl.d_seg_eq = nullptr; sl.d_md_ws = nullptr; sl.h_md_off = nullptr; sl.h_seg_eq = nullptr;
+        sl.md_segs_cap = (sl.cap > ns ? sl.cap : ns) + 1;
+        int rc = slamem_maps_md_workspace_bytes(sl.md_segs_cap, sl.cap_q, &sl.md_ws_bytes);
+        if (rc != SLAMEM_OK) return rc;
+        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_md_off), (sl.md_segs_cap + 1) * 8));
+        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_seg_eq), (sl.md_segs_cap + 1) * 4));
+        SLAMEM_HIP(hipMalloc(&sl.d_md_ws, sl.md_ws_bytes));
+        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_md_off), (sl.md_segs_cap + 1) * 8, hipHostMallocDefault));
+        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_seg_eq), (sl.md_segs_cap + 1) * 4, hipHostMallocDefault));
+    }
+    if (sl.md_q_cap < (uint64_t)sl.nq + 1 || !sl.d_primary) {
+        if (sl.d_primary) (void)hipFree(sl.d_primary);
+        if (sl.h_primary) (void)hipHostFree(sl.h_primary);
+        sl.d_primary = nullptr; sl.h_primary = nullptr;
+        sl.md_q_cap = (uint64_t)(sl.cap_q > sl.nq ? sl.cap_q : sl.nq) + 1;
+        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_primary), sl.md_q_cap * 4));
+        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_primary), sl.md_q_cap * 4, hipHostMallocDefault));
+    }
+    uint64_t want = sl.ops_total + ns + 1024;
+    int rc = SLAMEM_OK;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        if (sl.md_cap < want || !sl.d_md) {
+            if (sl.d_md) (void)hipFree(sl.d_md);
+            sl.d_md = nullptr;
+            sl.md_cap = want;
+            SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_md), (sl.md_cap + 1) * 4));
+        }
+        rc = slamem_maps_md_device(s->idx, sl.d_segs, ns, sl.d_boff, sl.nq, sl.d_ops, sl.d_ooff, sl.d_md, sl.md_cap, sl.d_md_off,
+                                   sl.d_seg_eq, sl.d_primary, sl.d_md_ws, sl.md_ws_bytes, st, &sl.md_total);
+        if (rc != SLAMEM_ERR_CAPACITY) break;
+        want = sl.md_total + sl.md_total / 8 + 1024;
+    }
+    if (rc != SLAMEM_OK) return rc;
+    if (sl.h_md_cap < sl.md_cap || !sl.h_md) {
+        if (sl.h_md) (void)hipHostFree(sl.h_md);
+        sl.h_md = nullptr;
+        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_md), (sl.md_cap + 1) * 4, hipHostMallocDefault));
+        sl.h_md_cap = sl.md_cap;
+    }
+    if (sl.md_total) SLAMEM_HIP(hipMemcpyAsync(sl.h_md, sl.d_md, sl.md_total * 4, hipMemcpyDeviceToHost, st));
+    SLAMEM_HIP(hipMemcpyAsync(sl.h_md_off, sl.d_md_off, (ns + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (ns) SLAMEM_HIP(hipMemcpyAsync(sl.h_seg_eq, sl.d_seg_eq, ns * 4, hipMemcpyDeviceToHost, st));
+    if (sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_primary, sl.d_primary, (uint64_t)sl.nq * 4, hipMemcpyDeviceToHost, st));
+    return SLAMEM_OK;
+}
+
 // stage 3: the batch's totals, then MEMs and block offsets to pinned host memory
 int stage_download(slamem_stream* s, Slot& sl) {
     hipStream_t st = s->st[T_DOWN];
@@ -554,6 +622,10 @@ int stage_download(slamem_stream* s, Slot& sl) {
         if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_segs, sl.d_segs, sl.total * sizeof(slamem_aln), hipMemcpyDeviceToHost, st));
         if (sl.ops_total) SLAMEM_HIP(hipMemcpyAsync(sl.h_ops, sl.d_ops, sl.ops_total * 4, hipMemcpyDeviceToHost, st));
         SLAMEM_HIP(hipMemcpyAsync(sl.h_ooff, sl.d_ooff, (sl.total + 1) * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (s->md) {
+        const int mrc = stage_md(s, sl, st);
+        if (mrc != SLAMEM_OK) return mrc;
     }
     if (s->match_type == 5) {
         if (sl.h_mm_cap < sl.cap || !sl.h_mm) {
@@ -638,6 +710,17 @@ void free_slot(Slot& sl) {
     if (sl.d_reads) (void)hipFree(sl.d_reads);
     if (sl.h_reads) (void)hipHostFree(sl.h_reads);
     sl.d_reads = nullptr; sl.h_reads = nullptr;
+    if (sl.d_md) (void)hipFree(sl.d_md);
+    if (sl.d_md_off) (void)hipFree(sl.d_md_off);
+    if (sl.d_seg_eq) (void)hipFree(sl.d_seg_eq);
+    if (sl.d_primary) (void)hipFree(sl.d_primary);
+    if (sl.d_md_ws) (void)hipFree(sl.d_md_ws);
+    if (sl.h_md) (void)hipHostFree(sl.h_md);
+    if (sl.h_md_off) (void)hipHostFree(sl.h_md_off);
+    if (sl.h_seg_eq) (void)hipHostFree(sl.h_seg_eq);
+    if (sl.h_primary) (void)hipHostFree(sl.h_primary);
+    sl.d_md = nullptr; sl.d_md_off = nullptr; sl.d_seg_eq = nullptr; sl.d_primary = nullptr; sl.d_md_ws = nullptr;
+    sl.h_md = nullptr; sl.h_md_off = nullptr; sl.h_seg_eq = nullptr; sl.h_primary = nullptr;
     if (sl.d_planes) (void)hipFree(sl.d_planes);
     if (sl.d_other) (void)hipFree(sl.d_other);
     if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
@@ -733,7 +816,7 @@ int slamem_stream_destroy(slamem_stream* s) {
     s->cv.notify_all();
     for (int k = 0; k < s->nthreads; k++)
         if (s->th[k].joinable()) s->th[k].join();
-    (void)hipSetDevice(s->idx->device);
+    (void)hipSetDevice(s->device);
     // every copy and kernel of the stream's own HIP streams is through before buffers and streams go (the stages wait for their
     // work batch by batch; this is for whatever a failed batch left behind, and for tools that watch the copies: a profiler waited
     // 30 s at exit for completion callbacks of copies whose streams were destroyed under it, profiles/README.md)
@@ -765,6 +848,7 @@ int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_
     slamem_stream* s = new (std::nothrow) slamem_stream();
     if (!s) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     s->idx = idx;
+    s->device = idx->device;
     s->trace = getenv("SLAMEM_STREAM_TRACE") != nullptr;
     s->t0 = std::chrono::steady_clock::now();
     s->nslots = slots;
@@ -928,6 +1012,45 @@ int slamem_stream_maps(slamem_stream* s, const slamem_map** reads_out) {
         return SLAMEM_ERR_ARG;
     }
     *reads_out = sl.h_reads;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_set_md(slamem_stream* s, int on) {
+    if (!s) { set_error("slamem_stream_set_md: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type != 7) {
+        set_error("slamem_stream_set_md: the MD pass needs match type 7 (-paf)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (s->submitted != 0) {
+        set_error("slamem_stream_set_md: the stream has batches already (switch the MD pass on before the first submit)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (on && !s->idx->view.tpl) {
+        set_error("slamem_stream_set_md: the MD entries take the reference letters from the text planes of the index, and this index "
+                  "has none (the compact layout, or one built with the seed sections switched off)");
+        return SLAMEM_ERR_ARG;
+    }
+    s->md = on != 0;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_md(slamem_stream* s, const uint32_t** md_out, const uint64_t** md_offsets_out, const uint32_t** seg_eq_out,
+                     const uint32_t** primary_out, uint64_t* num_md_out) {
+    if (!s || !md_out || !md_offsets_out || !seg_eq_out || !primary_out || !num_md_out) {
+        set_error("slamem_stream_md: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    std::unique_lock<std::mutex> lk(s->mu);
+    *md_out = nullptr; *md_offsets_out = nullptr; *seg_eq_out = nullptr; *primary_out = nullptr; *num_md_out = 0;
+    if (!s->md) { set_error("slamem_stream_md: the stream's MD pass is not switched on (slamem_stream_set_md)"); return SLAMEM_ERR_ARG; }
+    if (s->returned == 0) { set_error("slamem_stream_md: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
+    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
+    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
+        set_error("slamem_stream_md: the batch slamem_stream_next returned last has no entries to show");
+        return SLAMEM_ERR_ARG;
+    }
+    *md_out = sl.h_md; *md_offsets_out = sl.h_md_off; *seg_eq_out = sl.h_seg_eq; *primary_out = sl.h_primary; *num_md_out = sl.md_total;
     return SLAMEM_OK;
 }
 

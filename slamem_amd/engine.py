@@ -24,6 +24,8 @@ CIGAR_OPS = {7: "=", 8: "X", 1: "I", 2: "D"}  # BAM's codes; an operation is len
 SITES_NONZERO, SITES_VARIANT = 0, 1  # the rules of Pileup.sites (SLAMEM_SITES_*)
 # slamem_event: kind 0 a deletion of len rows from pos, 1 an insertion of len letters in front of pos
 EVENT_DTYPE = np.dtype([("pos", "<u8"), ("letters", "<u8"), ("fwd", "<u4"), ("rev", "<u4"), ("kind", "u1"), ("len", "u1"), ("pad", "u1", (6,))])
+SAM_LANE_OPS = 32  # -sam: the MD entries of a segment of up to this many operations are written by one lane, of a longer one by a wave (sam_filter.hip)
+MD_CLOSE = 8  # the closing entry of a segment: m << 4 | 8
 PILE_LANE_OPS = 32  # -pile: a segment of up to this many operations is walked by one lane, a longer one by a wave (pile_filter.hip)
 
 
@@ -251,17 +253,43 @@ class Index:
         return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, False)
 
     def map_reads(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-                  xdrop=None, max_edits=None, capacities=None):
+                  xdrop=None, max_edits=None, capacities=None, md: bool = False):
         """-paf mode: (segments, read_offsets, ops, op_offsets, reads) -- one mapping per read.  Per read the
         strand block whose best chain scores highest is the primary one (the forward block on a tie) and only that block is
         aligned, as find_alns aligns it; segments, ops and op_offsets are as find_alns returns them, in the coordinates of the
         scanned strand; read_offsets: the segments' offsets per READ (len(offsets) entries); reads: a structured array (strand,
         mapq, s1, s2) per read -- strand 0 unmapped, 1 forward, 2 reverse; s1 the primary chain's score, s2 the best competing
-        chain's; mapq = 60 * (s1 - s2) // s1.  The other arguments as for find_alns."""
-        return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, True)
+        chain's; mapq = 60 * (s1 - s2) // s1.  The other arguments as for find_alns.  md=True appends (md, md_offsets, seg_eq,
+        primary), what SAM needs (slamem_maps_md_device over the batch as it lies on the device): the MD entries of
+        all segments, uint32 `m << 4 | d << 2 | c` and a closing `m << 4 | 8` per segment (md_text makes the tag of one segment's),
+        their offsets per segment, the letters under = per segment, and per read the index of its primary segment within the
+        read's range (0xFFFFFFFF: the read has no segment)."""
+        return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, True, md=md)
+
+    def _md_pass(self, segs, nseg, roff, num, ops, ooff, cap):
+        """slamem_maps_md_device over a mapped batch as it lies on the device, with room for cap entries: (md, md_offsets, seg_eq,
+        primary) as numpy arrays."""
+        dev = self.device
+        L = capi.lib()
+        need = C.c_uint64()
+        capi.check(L.slamem_maps_md_workspace_bytes(nseg, num, C.byref(need)))
+        ws = torch.empty(need.value + 16, dtype=torch.uint8, device=dev)
+        md = torch.empty(cap + 1, dtype=torch.int32, device=dev)
+        moff = torch.empty(nseg + 1, dtype=torch.int64, device=dev)
+        seq = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
+        prim = torch.empty(num + 1, dtype=torch.int32, device=dev)
+        total = C.c_uint64()
+        with torch.cuda.device(dev):
+            torch.cuda.current_stream(dev).synchronize()
+            capi.check(L.slamem_maps_md_device(self._h, _ptr(segs), nseg, _ptr(roff), num, _ptr(ops), _ptr(ooff), _ptr(md), cap,
+                                               _ptr(moff), _ptr(seq), _ptr(prim), _ptr(ws), need.value, None, C.byref(total)))
+            torch.cuda.synchronize(dev)
+        n = int(total.value)
+        return (md[:n].cpu().numpy().view(np.uint32), moff.cpu().numpy().view(np.uint64), seq[:nseg].cpu().numpy().view(np.uint32),
+                prim[:num].cpu().numpy().view(np.uint32))
 
     def _aln_like(self, queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, mapping,
-                  pile=None):
+                  pile=None, md=False):
         """pile: (Pileup, min_mapq) -- the batch's mappings are added to the accumulator on the device and only the read records
         come back (Pileup.add)."""
         dev = self.device
@@ -312,10 +340,14 @@ class Index:
             pile[0]._add_device(qd, od, num, segs, boff, ops, ooff, recs, pile[1], pile[2] if len(pile) > 2 else None)
             return _map_records(recs[: num * 12].cpu().numpy())
         nseg, nops = int(totals[1]), int(totals[2])
+        extra = ()
+        if md:
+            edits = int(segs[: nseg * 5].view(-1, 5)[:, 4].to(torch.int64).sum().item()) if nseg else 0
+            extra = self._md_pass(segs, nseg, boff, num, ops, ooff, edits + nseg)
         out = segs[: nseg * 5].cpu().numpy().view(np.uint32).reshape(-1, 5).copy().view(ALN_DTYPE).reshape(-1)
         res = (out, boff.cpu().numpy().view(np.uint64), ops[:nops].cpu().numpy().view(np.uint32),
                ooff[: nseg + 1].cpu().numpy().view(np.uint64))
-        return res + (_map_records(recs[: num * 12].cpu().numpy()),) if mapping else res
+        return res + (_map_records(recs[: num * 12].cpu().numpy()),) + extra if mapping else res
 
     def _find(self, queries, offsets, min_len, both_strands, mam, mum, smem, max_occ, chain, max_gap, ext=False, penalty=0,
               xdrop=None):
@@ -734,8 +766,10 @@ class Stream:
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
                  max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False,
-                 pile: "Pileup" = None, min_mapq: int = 0):
-        """pile=<Pileup>: -pile mode (match type 8): every batch is mapped as with paf=True and added to the accumulator on the
+                 pile: "Pileup" = None, min_mapq: int = 0, md: bool = False):
+        """md=True (with paf=True): every batch also goes through the MD pass and mds() gives (md, md_offsets,
+        seg_eq, primary) of the batch next() returned last, as Index.map_reads(md=True) appends them.
+        pile=<Pileup>: -pile mode (match type 8): every batch is mapped as with paf=True and added to the accumulator on the
         device (the reads with mapq >= min_mapq); next() then returns (number of segments piled, None, timings) and maps() the read
         records; the segments are not downloaded.  It takes the parameters of paf and excludes the other modes.  aln=True: -aln mode (match type 6); it takes max_gap, penalty, xdrop and max_edits and excludes the other modes.
         next() then returns the segments (ALN_DTYPE) in the place of the rows, alns() their operations.  paf=True: -paf mode
@@ -750,24 +784,35 @@ class Stream:
             raise ValueError("aln, paf and pile exclude mam, mum, smem, chain, ext and each other: one match type per search")
         if max_edits is not None and not (aln or paf):
             raise ValueError("max_edits is the edit limit of aln and paf: it needs aln=True or paf=True")
+        if md and not (paf and pile is None):
+            raise ValueError("md is the MD pass of paf: it needs paf=True")
         self.paf = bool(paf)
         self.aln = bool(aln or paf)
+        self.md = bool(md)
         match_type = 8 if pile is not None else 7 if paf else 6 if aln else _match_type(mam, mum, smem, max_occ, chain, max_gap, ext, penalty, xdrop)
         self.index = index
         self.both = bool(both_strands)
         self._h = C.c_void_p()
         capi.check(capi.lib().slamem_stream_create(index._h, int(slots), int(max_batch_chars), int(max_batch_queries),
                                                    int(self.both), match_type, C.byref(self._h)))
-        if max_occ:
-            capi.check(capi.lib().slamem_stream_set_max_occ(self._h, int(max_occ)))
-        if max_gap:
-            capi.check(capi.lib().slamem_stream_set_max_gap(self._h, int(max_gap)))
-        if penalty or xdrop is not None:
-            capi.check(capi.lib().slamem_stream_set_ext_params(self._h, int(penalty), _xdrop_arg(xdrop)))
-        if max_edits is not None:
-            capi.check(capi.lib().slamem_stream_set_max_edits(self._h, int(max_edits)))
-        if pile is not None:
-            capi.check(capi.lib().slamem_stream_set_pileup(self._h, pile._h, int(min_mapq)))
+        try:
+            if max_occ:
+                capi.check(capi.lib().slamem_stream_set_max_occ(self._h, int(max_occ)))
+            if max_gap:
+                capi.check(capi.lib().slamem_stream_set_max_gap(self._h, int(max_gap)))
+            if penalty or xdrop is not None:
+                capi.check(capi.lib().slamem_stream_set_ext_params(self._h, int(penalty), _xdrop_arg(xdrop)))
+            if max_edits is not None:
+                capi.check(capi.lib().slamem_stream_set_max_edits(self._h, int(max_edits)))
+            if pile is not None:
+                capi.check(capi.lib().slamem_stream_set_pileup(self._h, pile._h, int(min_mapq)))
+            if md:
+                capi.check(capi.lib().slamem_stream_set_md(self._h, 1))
+        except Exception:
+            # a setter refused: the stream goes at once, while its index is alive -- not when the exception's traceback, which
+            # holds this object, happens to be collected (by then the caller may have closed the index)
+            self.close()
+            raise
         self._keep = []
         self._last_total = 0
 
@@ -825,6 +870,15 @@ class Stream:
                 capi.check(capi.lib().slamem_stream_maps(self._h, C.byref(recs)))
                 raw = np.ctypeslib.as_array((C.c_uint8 * (12 * max(1, nq.value))).from_address(recs.value))[: 12 * nq.value]
                 self._last_maps = _map_records(raw)
+            if self.md:
+                p = [C.c_void_p() for _ in range(4)]
+                nmd = C.c_uint64()
+                capi.check(capi.lib().slamem_stream_md(self._h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(p[3]), C.byref(nmd)))
+                self._last_mds = (
+                    np.ctypeslib.as_array((C.c_uint32 * max(1, nmd.value)).from_address(p[0].value))[: nmd.value].copy(),
+                    np.ctypeslib.as_array((C.c_uint64 * (n + 1)).from_address(p[1].value)).copy(),
+                    np.ctypeslib.as_array((C.c_uint32 * max(1, n)).from_address(p[2].value))[:n].copy(),
+                    np.ctypeslib.as_array((C.c_uint32 * max(1, nq.value)).from_address(p[3].value))[: nq.value].copy())
             return (m.copy(), b.copy(), tm.as_dict()) if copy else (m, b, tm.as_dict())
         m = np.ctypeslib.as_array((C.c_uint8 * (12 * max(1, total.value))).from_address(mems.value))[: 12 * total.value]
         m = m.view(MEM_DTYPE)
@@ -840,6 +894,10 @@ class Stream:
     def maps(self):
         """-paf: the read records (MAP_DTYPE) of the batch next() returned last (slamem_stream_maps), as next() took them."""
         return self._last_maps
+
+    def mds(self):
+        """md=True: (md, md_offsets, seg_eq, primary) of the batch next() returned last (slamem_stream_md), copied."""
+        return self._last_mds
 
     def mismatches(self, copy: bool = True) -> np.ndarray:
         """-ext: the mismatches (uint32 per row) of the batch next() returned last (slamem_stream_mismatches).  copy=False
@@ -1084,3 +1142,25 @@ def synth_reads(ref: torch.Tensor, first: int, count: int, length: int = 150, su
     if rc:
         raise RuntimeError(f"synth kernel launch failed: hip error {rc}")
     return out
+
+
+def md_text(entries) -> bytes:
+    """The MD:Z: text of ONE segment's MD entries (rule 2): an X entry prints m and the letter; a D entry with
+    m == 0 whose predecessor is a D entry continues that ^ group, any other D entry prints m, ^ and the letter; the closing entry
+    prints m."""
+    out = []
+    prev_d = False
+    for e in entries:
+        e = int(e)
+        m = e >> 4
+        if e & MD_CLOSE:
+            out.append(b"%d" % m)
+            break
+        letter = b"ACGT"[e & 3:(e & 3) + 1]
+        if e & 4:
+            out.append(letter if (prev_d and m == 0) else b"%d^" % m + letter)
+            prev_d = True
+        else:
+            out.append(b"%d" % m + letter)
+            prev_d = False
+    return b"".join(out)

@@ -70,6 +70,8 @@ typedef struct {
     slh_seqset *sets;  /* room for every piece */
     uint64_t **masks;  /* -bq: per piece the low-quality mask over its letters (NULL: FASTA, or -bq 0), as many entries as sets */
     int min_bq;        /* -bq N: 0 = the qualities are not used */
+    int keep_quals;    /* -sam: the quality bytes of every piece are kept for the QUAL column */
+    char **quals;      /* ... per piece (NULL: FASTA), as many entries as sets */
     int fasta_seen;    /* a query file without qualities came in (said once when -bq asks for them) */
     int invalid;       /* a query file is no valid FASTQ: the run ends */
     int cap;
@@ -114,9 +116,10 @@ static void *loader_run(void *arg) {
             int n = slh_pieces_next_q(p, &s, &quals);
             if (n < 0) ld->invalid = 1;
             if (n <= 0) break;
-            mask = mask_of_quals(ld, &s, quals);
+            mask = ld->keep_quals ? NULL : mask_of_quals(ld, &s, quals);
             pthread_mutex_lock(&ld->mu);
             if (ld->ready < ld->cap) {
+                if (ld->keep_quals) { ld->quals[ld->ready] = quals; quals = NULL; }
                 ld->masks[ld->ready] = mask;
                 ld->sets[ld->ready++] = s;
                 ld->total_queries += n;
@@ -124,6 +127,7 @@ static void *loader_run(void *arg) {
             } else { /* cannot happen (a piece is at least piece_bytes of its file): never drop reads silently */
                 ld->failed = 1;
                 free(mask);
+                if (ld->keep_quals) free(quals);
                 slh_free_seqset(&s);
             }
             pthread_cond_broadcast(&ld->cv);
@@ -201,6 +205,10 @@ typedef struct {
     const uint32_t *ops;
     const uint64_t *ooff;
     const slamem_map *reads; /* -paf: a record per read (NULL otherwise); the blocks are then the reads, strands = 1 */
+    const uint32_t *md;      /* -sam: the MD entries of the batch's segments, their offsets per segment, the primary segment per read */
+    const uint64_t *mdoff;   /*       (NULL otherwise) */
+    const uint32_t *prim;
+    const char *quals;       /* -sam: the quality bytes of the set, indexed as its letters (NULL: FASTA) */
     const uint64_t *boff;
     int first_rec, strands;
     uint64_t b0, b1; /* strand blocks [b0,b1) of the batch */
@@ -234,6 +242,16 @@ static void pool_get(slh_buffer *b, size_t need) {
     pthread_mutex_unlock(&g_pool_mu);
 }
 
+/* a read of the -sam file: read b of the batch is record i of its set */
+static int format_sam_read(slh_buffer *buf, const slh_seqset *q, const char *quals, int i, uint64_t b, const slamem_map *reads,
+                           const slamem_aln *segs, const uint32_t *ops, const uint64_t *ooff, const uint64_t *boff, const uint32_t *md,
+                           const uint64_t *mdoff, const uint32_t *prim, const slh_seqset *ref, uint64_t *sum) {
+    return slh_format_read_sam(buf, q->recs[i].name, q->chars + q->offsets[i], quals ? quals + q->offsets[i] : NULL,
+                               (uint32_t)(q->offsets[i + 1] - q->offsets[i]), reads[b].strand, reads[b].mapq, reads[b].s1, reads[b].s2,
+                               (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b], md, mdoff + boff[b], prim[b],
+                               boff[b + 1] - boff[b], ref->recs, ref->merged_start, ref->num, sum);
+}
+
 static void *fmt_run(void *arg) {
     fmt_job *j = (fmt_job *)arg;
     uint64_t b;
@@ -245,7 +263,9 @@ static void *fmt_run(void *arg) {
     for (b = j->b0; b < j->b1; b++) {
         int i = j->first_rec + (int)(b / (uint64_t)j->strands), s = (int)(b % (uint64_t)j->strands);
         uint64_t cnt = j->boff[b + 1] - j->boff[b], sum = 0;
-        if (j->reads ? slh_format_read_paf(&j->buf, j->q->recs[i].name, j->q->recs[i].size, j->reads[b].strand, j->reads[b].mapq,
+        if (j->md ? format_sam_read(&j->buf, j->q, j->quals, i, b, j->reads, j->segs, j->ops, j->ooff, j->boff, j->md, j->mdoff, j->prim,
+                                    j->ref, &sum)
+            : j->reads ? slh_format_read_paf(&j->buf, j->q->recs[i].name, j->q->recs[i].size, j->reads[b].strand, j->reads[b].mapq,
                                            j->reads[b].s1, j->reads[b].s2, (const uint32_t *)(j->segs + j->boff[b]), j->ops,
                                            j->ooff + j->boff[b], cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)
             : j->segs ? slh_format_block_aln(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->segs + j->boff[b]), j->ops,
@@ -617,6 +637,7 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-aln\tgapped alignment of the best chain of each strand; writes ref_pos query_pos ref_len query_len edits cigar\n");
     printf("\t-maxed\twith -aln: most edits in the gap between two chained MEMs, 0 to 127 (default=31); -mgap, -pen, -xdrop apply\n");
     printf("\t-paf\tone mapping per read with a mapping quality, written as PAF with a cg:Z: CIGAR; -mgap, -pen, -xdrop, -maxed apply\n");
+    printf("\t-sam\tthe mappings of -paf written as SAM: a line per segment with soft clips, NM:i:, MD:Z: (built on the GPU), s1:i:, s2:i: and SA:Z:; an unmapped read gets a line with flag 4; FASTQ queries keep their qualities; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-pile\tper-base pileup of the mappings of -paf: record, position, letter and the counts A C G T D I; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-minq\twith -pile: least mapping quality of a read that counts, 0 to 60 (default=0)\n");
     printf("\t-bq\twith -pile, -sites, -vcf, -cons, -depth: least base quality of a read letter that counts, 0 to 93 (default=0: all); needs FASTQ queries (a file that starts with '@')\n");
@@ -655,6 +676,7 @@ int main(int argc, char **argv) {
     int sites = 0, min_depth = 4, min_pct = 20; /* -sites: match type 8 with the sparse read-out */
     int vcf = 0;                                /* -vcf: match type 8 with the events enabled, written as VCF */
     int cons = 0;                               /* -cons: match type 8 with the events enabled, the consensus written as FASTA */
+    int sam = 0;                                /* -sam: match type 7 with the MD pass, written as SAM */
     int depth = 0, num_levels = 0, sites_params; /* -depth: match type 8, the runs of the depth written as a bedGraph */
     uint32_t levels[16];
     uint64_t window = 0;
@@ -684,7 +706,9 @@ int main(int argc, char **argv) {
     vcf = slh_parse_argument(argc, argv, "VC", 0);
     cons = slh_parse_argument(argc, argv, "CO", 0);
     depth = slh_parse_argument(argc, argv, "DE", 0);
+    sam = slh_parse_argument(argc, argv, "SA", 0);
     if (o.match_type < 0) { /* before any GPU work */
+        if (sam) exit_message("Option -sam excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites, -vcf, -cons and -depth");
         if (depth) exit_message("Option -depth excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites, -vcf and -cons");
         if (cons) exit_message("Option -cons excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites and -vcf");
         if (vcf) exit_message("Option -vcf excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile and -sites");
@@ -800,6 +824,9 @@ int main(int argc, char **argv) {
         ld->masks = (uint64_t **)calloc((size_t)ld->cap + 1, sizeof(uint64_t *));
         if (!ld->masks) exit_message("Out of memory");
         ld->min_bq = min_bq;
+        ld->keep_quals = sam;
+        ld->quals = (char **)calloc((size_t)ld->cap + 1, sizeof(char *));
+        if (!ld->quals) exit_message("Out of memory");
         pthread_mutex_init(&ld->mu, NULL);
         pthread_cond_init(&ld->cv, NULL);
     }
@@ -827,7 +854,8 @@ int main(int argc, char **argv) {
                 exit(-1);
             }
             if (n != 0) {
-                ld->masks[ld->ready] = mask_of_quals(ld, &qsets[ld->ready], quals);
+                if (ld->keep_quals) ld->quals[ld->ready] = quals;
+                else ld->masks[ld->ready] = mask_of_quals(ld, &qsets[ld->ready], quals);
                 if (ld->invalid) exit_message("Out of memory");
                 numbering += n; ld->total_queries += n; ld->ready++;
             }
@@ -1013,6 +1041,12 @@ int main(int argc, char **argv) {
         g_writer.out = out;
         pthread_mutex_init(&g_writer.mu, NULL);
         pthread_cond_init(&g_writer.cv, NULL);
+        if (sam) { /* the header, once, in front of the first batch's lines */
+            slh_buffer hd = {0, 0, 0};
+            if (slh_format_sam_header(&hd, ref.recs, ref.num)) pipeline_fail("Out of memory");
+            if (fwrite(hd.data, 1, hd.len, out) != hd.len) pipeline_fail("Cannot write output file");
+            slh_buffer_free(&hd);
+        }
         g_writer.started = pthread_create(&g_writer.tid, NULL, writer_run, &g_writer) == 0;
         double ts0 = now_s();
         for (g = 0; g < 16; g++) piles[g] = NULL;
@@ -1046,6 +1080,10 @@ int main(int argc, char **argv) {
                 if (rc == SLAMEM_OK)
                     rc = slamem_stream_set_max_edits(g_streams[g], max_edits >= 0 ? (uint32_t)max_edits : SLAMEM_ALN_EDITS_DEFAULT);
             }
+            if (rc == SLAMEM_OK && sam) { /* every batch also goes through the MD pass */
+                g_nstreams = g + 1;
+                rc = slamem_stream_set_md(g_streams[g], 1);
+            }
             if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("setting up the search pipeline", rc); }
             g_nstreams = g + 1;
             inflight[g] = 0;
@@ -1073,7 +1111,10 @@ int main(int argc, char **argv) {
             slh_seqset *q = &qsets[ranges[bi].f];
             const int first = ranges[bi].first, last = ranges[bi].last;
             for (; ld->release_early && sets_reaped < ranges[bi].f; sets_reaped++) /* every batch of the earlier sets is formatted */
-                if (qsets[sets_reaped].chars) { reap_set(&qsets[sets_reaped]); free(ld->masks[sets_reaped]); ld->masks[sets_reaped] = NULL; }
+                if (qsets[sets_reaped].chars) {
+                    reap_set(&qsets[sets_reaped]); free(ld->masks[sets_reaped]); ld->masks[sets_reaped] = NULL;
+                    free(ld->quals[sets_reaped]); ld->quals[sets_reaped] = NULL;
+                }
             const slamem_mem *mems = NULL;
             const uint32_t *mism = NULL;
             const slamem_aln *segs = NULL;
@@ -1081,6 +1122,9 @@ int main(int argc, char **argv) {
             const uint64_t *ooff = NULL;
             uint64_t nops = 0;
             const slamem_map *reads = NULL;
+            const uint32_t *md = NULL, *seg_eq = NULL, *prim = NULL;
+            const uint64_t *mdoff = NULL;
+            uint64_t nmd = 0;
             const uint64_t *boff = NULL;
             uint64_t total = 0;
             double tg = now_s();
@@ -1127,6 +1171,11 @@ int main(int argc, char **argv) {
                 rc = slamem_stream_maps(g_streams[bi % (size_t)ngpu], &reads);
                 if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("mapping on the GPU", rc); }
             }
+            if (sam) { /* ... and the MD entries and the primary segments came with them (seg_eq and nmd are what the interface
+                          hands out beside them: the writer needs neither, the primary segment is already chosen) */
+                rc = slamem_stream_md(g_streams[bi % (size_t)ngpu], &md, &mdoff, &seg_eq, &prim, &nmd);
+                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("the MD pass on the GPU", rc); }
+            }
             inflight[bi % (size_t)ngpu]--;
             t_gpu += now_s() - tg; /* time the main thread waited for the GPUs */
             tg = now_s();
@@ -1140,7 +1189,8 @@ int main(int argc, char **argv) {
                 for (b = 0; b < bseq; b++) {
                     int ri = first + (int)(b / strands), sidx = (int)(b % strands), d, dots;
                     uint64_t cnt = boff[b + 1] - boff[b], sum = 0;
-                    if (reads ? slh_format_read_paf(&buf, q->recs[ri].name, q->recs[ri].size, reads[b].strand, reads[b].mapq, reads[b].s1,
+                    if (md ? format_sam_read(&buf, q, ld->quals[ranges[bi].f], ri, b, reads, segs, ops, ooff, boff, md, mdoff, prim, &ref, &sum)
+                        : reads ? slh_format_read_paf(&buf, q->recs[ri].name, q->recs[ri].size, reads[b].strand, reads[b].mapq, reads[b].s1,
                                                     reads[b].s2, (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b], cnt, ref.recs,
                                                     ref.merged_start, ref.num, &sum)
                         : segs ? slh_format_block_aln(&buf, q->recs[ri].name, sidx, (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b],
@@ -1175,6 +1225,7 @@ int main(int argc, char **argv) {
                     for (t = 0; t < njobs; t++) {
                         jobs[t].q = q; jobs[t].ref = &ref; jobs[t].mems = mems; jobs[t].mism = mism; jobs[t].boff = boff;
                         jobs[t].segs = segs; jobs[t].ops = ops; jobs[t].ooff = ooff; jobs[t].reads = reads;
+                        jobs[t].md = md; jobs[t].mdoff = mdoff; jobs[t].prim = prim; jobs[t].quals = ld->quals[ranges[bi].f];
                         jobs[t].first_rec = first; jobs[t].strands = strands;
                         jobs[t].b0 = bseq + per * (uint64_t)t < nblk ? bseq + per * (uint64_t)t : nblk;
                         jobs[t].b1 = jobs[t].b0 + per < nblk ? jobs[t].b0 + per : nblk;

@@ -1208,6 +1208,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type != 0 ? -1 : 6;
     if (slh_parse_argument(argc, argv, "PA", 0)) /* -paf: one mapping per read, written as PAF (a 'p' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 7;
+    if (slh_parse_argument(argc, argv, "SA", 0)) /* -sam: the mappings of -paf written as SAM: match type 7 with the MD pass (an 's' option takes no value; "-s" alone is the sort tool) */
+        o->match_type = o->match_type != 0 ? -1 : 7;
     if (slh_parse_argument(argc, argv, "PI", 0)) /* -pile: the per-base pileup of the mappings (a 'p' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 8;
     if (slh_parse_argument(argc, argv, "SI", 0)) /* -sites: the variant sites of the pileup: match type 8 with another read-out (an 's' option takes no value) */
@@ -1679,6 +1681,152 @@ int slh_format_read_paf(slh_buffer *buf, const char *query_name, uint32_t query_
         *p++ = '\n';
         buf->len = (size_t)(p - buf->data);
         sum += qlen;
+    }
+    if (sum_len_out) *sum_len_out = sum;
+    return 0;
+}
+
+/* ---- SAM ---- */
+
+static const char SAM_OPC[16] = {'?', 'I', 'D', '?', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+
+/* a line's CIGAR: soft clips around the segment's operations (at most 24 + 11 characters an operation) */
+static char *sam_put_cigar(char *p, uint32_t n, const uint32_t *seg, const uint32_t *ops, uint64_t o0, uint64_t o1) {
+    const uint32_t lead = seg[1], tail = n - seg[1] - seg[3];
+    uint64_t k;
+    if (lead) { p = put_u32(p, lead); *p++ = 'S'; }
+    for (k = o0; k < o1; k++) { p = put_u32(p, ops[k] >> 4); *p++ = SAM_OPC[ops[k] & 15u]; }
+    if (tail) { p = put_u32(p, tail); *p++ = 'S'; }
+    return p;
+}
+
+/* the MD text of one segment's entries (at most 12 characters an entry) */
+static char *sam_put_md(char *p, const uint32_t *md, uint64_t m0, uint64_t m1) {
+    int prev_d = 0;
+    uint64_t k;
+    for (k = m0; k < m1; k++) {
+        const uint32_t e = md[k], m = e >> 4;
+        if (e & 8u) { p = put_u32(p, m); break; }
+        if (e & 4u) {
+            if (!(prev_d && m == 0)) { p = put_u32(p, m); *p++ = '^'; }
+            prev_d = 1;
+        } else {
+            p = put_u32(p, m);
+            prev_d = 0;
+        }
+        *p++ = "ACGT"[e & 3u];
+    }
+    return p;
+}
+
+/* the engine's complement rule: A<->T, C<->G in either case, anything else N */
+static inline char sam_complement(char c) {
+    switch (c & 0xDF) {
+    case 'A': return 'T';
+    case 'C': return 'G';
+    case 'G': return 'C';
+    case 'T': return 'A';
+    default: return 'N';
+    }
+}
+
+int slh_format_sam_header(slh_buffer *buf, const slh_record *refs, int num_refs) {
+    static const char HD[] = "@HD\tVN:1.6\tSO:unsorted\n", PG[] = "@PG\tID:slaMEM-hip\tPN:slaMEM-hip\n";
+    int i;
+    char *p;
+    if (buf_reserve(buf, sizeof(HD))) return -1;
+    memcpy(buf->data + buf->len, HD, sizeof(HD) - 1);
+    buf->len += sizeof(HD) - 1;
+    for (i = 0; i < num_refs; i++) {
+        const size_t namelen = strcspn(refs[i].name, " \t");
+        if (buf_reserve(buf, namelen + 32)) return -1;
+        p = buf->data + buf->len;
+        memcpy(p, "@SQ\tSN:", 7); p += 7;
+        memcpy(p, refs[i].name, namelen); p += namelen;
+        memcpy(p, "\tLN:", 4); p += 4;
+        p = put_u32(p, refs[i].size);
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+    }
+    if (buf_reserve(buf, sizeof(PG))) return -1;
+    memcpy(buf->data + buf->len, PG, sizeof(PG) - 1);
+    buf->len += sizeof(PG) - 1;
+    return 0;
+}
+
+int slh_format_read_sam(slh_buffer *buf, const char *query_name, const char *letters, const char *quals, uint32_t n, int strand,
+                        uint32_t mapq, uint32_t s1, uint32_t s2, const uint32_t *segs, const uint32_t *ops, const uint64_t *op_off,
+                        const uint32_t *md, const uint64_t *md_off, uint32_t primary, uint64_t count, const slh_record *refs,
+                        const uint32_t *merged_start, int num_refs, uint64_t *sum_len_out) {
+    const size_t nl = strcspn(query_name, " \t");
+    uint64_t i, j, sum = 0;
+    size_t sa_room = 0;
+    uint32_t x;
+    char *p;
+    if (sum_len_out) *sum_len_out = 0;
+    if ((strand != 1 && strand != 2) || count == 0) {
+        if (buf_reserve(buf, nl + 2 * (size_t)n + 32)) return -1;
+        p = buf->data + buf->len;
+        memcpy(p, query_name, nl); p += nl;
+        memcpy(p, "\t4\t*\t0\t0\t*\t*\t0\t0\t", 17); p += 17;
+        memcpy(p, letters, n); p += n;
+        *p++ = '\t';
+        if (quals) { memcpy(p, quals, n); p += n; } else *p++ = '*';
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+        return 0;
+    }
+    if (count > 1) /* what the other segments' SA entries take at most: name, position, strand, CIGAR, two numbers */
+        for (i = 0; i < count; i++) {
+            uint32_t rp = segs[5 * i];
+            const slh_record *rec = &refs[num_refs > 1 ? slh_seq_id_from_merged_pos(merged_start, num_refs, &rp) : 0];
+            sa_room += strcspn(rec->name, " \t") + 64 + (size_t)(op_off[i + 1] - op_off[i]) * 11;
+        }
+    for (i = 0; i < count; i++) {
+        uint32_t rp = segs[5 * i];
+        const slh_record *rec = &refs[num_refs > 1 ? slh_seq_id_from_merged_pos(merged_start, num_refs, &rp) : 0];
+        const size_t namelen = strcspn(rec->name, " \t");
+        const uint64_t nops = op_off[i + 1] - op_off[i], nmd = md_off[i + 1] - md_off[i];
+        if (buf_reserve(buf, nl + namelen + 192 + (size_t)nops * 11 + 2 * (size_t)n + (size_t)nmd * 12 + sa_room)) return -1;
+        p = buf->data + buf->len;
+        memcpy(p, query_name, nl); p += nl;
+        *p++ = '\t'; p = put_u32(p, (strand == 2 ? 16u : 0u) | (i == primary ? 0u : 2048u));
+        *p++ = '\t'; memcpy(p, rec->name, namelen); p += namelen;
+        *p++ = '\t'; p = put_u32(p, rp + 1);
+        *p++ = '\t'; p = put_u32(p, mapq);
+        *p++ = '\t'; p = sam_put_cigar(p, n, segs + 5 * i, ops, op_off[i], op_off[i + 1]);
+        memcpy(p, "\t*\t0\t0\t", 7); p += 7;
+        if (strand == 2) for (x = 0; x < n; x++) *p++ = sam_complement(letters[n - 1 - x]);
+        else { memcpy(p, letters, n); p += n; }
+        *p++ = '\t';
+        if (!quals) *p++ = '*';
+        else if (strand == 2) for (x = 0; x < n; x++) *p++ = quals[n - 1 - x];
+        else { memcpy(p, quals, n); p += n; }
+        memcpy(p, "\tNM:i:", 6); p += 6; p = put_u32(p, segs[5 * i + 4]);
+        memcpy(p, "\tMD:Z:", 6); p += 6; p = sam_put_md(p, md, md_off[i], md_off[i + 1]);
+        memcpy(p, "\ts1:i:", 6); p += 6; p = put_u32(p, s1);
+        memcpy(p, "\ts2:i:", 6); p += 6; p = put_u32(p, s2);
+        if (count > 1) {
+            memcpy(p, "\tSA:Z:", 6); p += 6;
+            for (j = 0; j < count; j++) {
+                uint32_t op = segs[5 * j];
+                const slh_record *orec;
+                size_t on;
+                if (j == i) continue;
+                orec = &refs[num_refs > 1 ? slh_seq_id_from_merged_pos(merged_start, num_refs, &op) : 0];
+                on = strcspn(orec->name, " \t");
+                memcpy(p, orec->name, on); p += on;
+                *p++ = ','; p = put_u32(p, op + 1);
+                *p++ = ','; *p++ = strand == 2 ? '-' : '+';
+                *p++ = ','; p = sam_put_cigar(p, n, segs + 5 * j, ops, op_off[j], op_off[j + 1]);
+                *p++ = ','; p = put_u32(p, mapq);
+                *p++ = ','; p = put_u32(p, segs[5 * j + 4]);
+                *p++ = ';';
+            }
+        }
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+        sum += segs[5 * i + 3];
     }
     if (sum_len_out) *sum_len_out = sum;
     return 0;

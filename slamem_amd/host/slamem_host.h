@@ -83,7 +83,7 @@ typedef struct {
     char *ref_name;     /* -r string (malloc'ed) or NULL                     */
     int ref_name_given; /* -r present                                        */
     int ref_name_empty; /* -r present without a string                       */
-    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa...), 8 pileup (-pi..., and -si...: its variant sites, -vc...: its calls as VCF), -1 two of them */
+    int match_type;     /* 0 MEM, 1 MAM (-ma...), 2 MUM (-mu...), 3 SMEM (-sm...), 4 chain (-ch...), 5 extension (-ex...), 6 alignment (-al...), 7 mapping (-pa..., and -sa...: the same written as SAM), 8 pileup (-pi..., and -si...: its variant sites, -vc...: its calls as VCF), -1 two of them */
     int both_strands;   /* -b                                                */
     int min_mem_len;    /* -l, default 20                                    */
     int out_arg;        /* index of the -o value, or -1                      */
@@ -163,6 +163,20 @@ int slh_format_block_aln(slh_buffer *buf, const char *query_name, int reverse, c
 int slh_format_read_paf(slh_buffer *buf, const char *query_name, uint32_t query_len, int strand, uint32_t mapq, uint32_t s1,
                         uint32_t s2, const uint32_t *segs, const uint32_t *ops, const uint64_t *op_off, uint64_t count,
                         const slh_record *refs, const uint32_t *merged_start, int num_refs, uint64_t *sum_len_out);
+/* A read of the -sam file.  A read with strand 0 or count 0 gets one line, `name 4 * 0 0 * * 0 0 SEQ QUAL`;
+ * any other one line per segment, in the segments' order:
+ *   name  FLAG  record  ts + 1  mapq  CIGAR  *  0  0  SEQ  QUAL  NM:i:  MD:Z:  s1:i:  s2:i:  [SA:Z:]
+ * FLAG = 16 on strand 2 | 2048 on every segment but number `primary`; the CIGAR is <query_pos>S, the operations, <n - query_pos
+ * - query_len>S (a clip of 0 is left out), so every line carries the whole read; SEQ is the n letters as given, on strand 2
+ * their reverse complement by the engine's rule (A<->T, C<->G, anything else N); QUAL the n quality bytes, reversed on strand 2,
+ * `*` when quals is NULL.  md, md_off: the MD entries of slamem_maps_md_device, md_off[i] .. md_off[i + 1] those of segment i.
+ * With more than one segment SA:Z: lists `record,pos,+|-,CIGAR,mapq,NM;` of the others.  segs, ops, op_off, names,
+ * *sum_len_out as for slh_format_read_paf.  slh_format_sam_header: @HD, an @SQ per record, @PG (no CL:). */
+int slh_format_read_sam(slh_buffer *buf, const char *query_name, const char *letters, const char *quals, uint32_t n, int strand,
+                        uint32_t mapq, uint32_t s1, uint32_t s2, const uint32_t *segs, const uint32_t *ops, const uint64_t *op_off,
+                        const uint32_t *md, const uint64_t *md_off, uint32_t primary, uint64_t count, const slh_record *refs,
+                        const uint32_t *merged_start, int num_refs, uint64_t *sum_len_out);
+int slh_format_sam_header(slh_buffer *buf, const slh_record *refs, int num_refs);
 /* Rows of the -pile file: one line per row with a non-zero counter,
  *   record name (cut at the first blank or tab)  position  reference letter (upper case)  A  C  G  T  D  I
  * counts: six uint32 per row; letters[i]: the reference letter of row i; first_pos: the 1-based position of row 0 in its record. */
