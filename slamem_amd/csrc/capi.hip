@@ -1,6 +1,7 @@
 // capi.hip -- the extern "C" surface of libslamem_hip.so (include/slamem_hip.h).
 // Plain pointers and sizes only.  There is no CPU fallback anywhere in this library: without a
 // usable gfx950 device every compute entry point fails with SLAMEM_ERR_NO_DEVICE / SLAMEM_ERR_HIP.
+#include "buffers.h"
 #include "common.h"
 
 #include <stdarg.h>
@@ -576,8 +577,6 @@ int slamem_find_maps_device(const slamem_index* idx, const void* queries_dev, co
                                 ops_dev, ops_capacity, op_offsets_dev, reads_dev, 7, workspace_dev, workspace_bytes, stream, totals_out);
 }
 
-#define HOST_TRY(call) if ((e = (call)) != hipSuccess) { rc = hip_fail(e, #call, __FILE__, __LINE__); goto done; }
-
 // -aln and -paf for a caller with host memory (reads_out: -paf; then the offsets are per read).  Four attempts: the -mem rows,
 // the segments and the operations may each not fit once.
 static int find_segments_host(const char* who, const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
@@ -593,74 +592,57 @@ static int find_segments_host(const char* who, const slamem_index* idx, const ch
     const uint64_t num_blocks = (uint64_t)num_queries * (both_strands ? 2u : 1u);
     const uint64_t noff = (reads_out ? (uint64_t)num_queries : num_blocks) + 1;  // offsets that go back
     const char* q0 = queries ? queries + offsets[0] : nullptr;
-    uint64_t* rel = static_cast<uint64_t*>(malloc(((uint64_t)num_queries + 1) * 8));
+    HostArray<uint64_t> rel = host_array<uint64_t>((uint64_t)num_queries + 1);
     if (!rel) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     for (uint64_t i = 0; i <= num_queries; i++) rel[i] = offsets[i] - offsets[0];
     uint64_t cap = 2 * qbytes / (min_len ? min_len : 1) + 4 * num_blocks + 1024;  // the -mem list
     uint64_t scap = num_blocks + 1024, ocap = 4 * num_blocks + 4096;                // segments, operations
-    void *d_q = nullptr, *d_off = nullptr, *d_boff = nullptr, *d_segs = nullptr, *d_ops = nullptr, *d_ooff = nullptr, *d_ws = nullptr, *d_reads = nullptr;
-    slamem_aln* h_segs = nullptr;
-    uint64_t *h_boff = nullptr, *h_ooff = nullptr;
-    uint32_t* h_ops = nullptr;
-    slamem_map* h_reads = nullptr;
+    DevBuf<char> d_q, d_ws;
+    DevBuf<uint64_t> d_off, d_boff, d_ooff;
+    DevBuf<slamem_aln> d_segs;
+    DevBuf<uint32_t> d_ops;
+    DevBuf<slamem_map> d_reads;
+    SLAMEM_HIP(hipSetDevice(idx->device));
+    SLAMEM_TRY(d_q.reserve(qbytes + 16));
+    SLAMEM_TRY(d_off.reserve((uint64_t)num_queries + 1));
+    SLAMEM_TRY(d_boff.reserve(noff));
+    if (reads_out) SLAMEM_TRY(d_reads.reserve((uint64_t)num_queries + 1));
+    if (qbytes) SLAMEM_HIP(hipMemcpy(d_q.get(), q0, qbytes, hipMemcpyHostToDevice));
+    SLAMEM_HIP(hipMemcpy(d_off.get(), rel.get(), ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
     int rc = SLAMEM_OK;
-    hipError_t e;
-    HOST_TRY(hipSetDevice(idx->device));
-    HOST_TRY(hipMalloc(&d_q, qbytes + 16));
-    HOST_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
-    HOST_TRY(hipMalloc(&d_boff, noff * 8));
-    if (reads_out) HOST_TRY(hipMalloc(&d_reads, ((uint64_t)num_queries + 1) * sizeof(slamem_map)));
-    if (qbytes) HOST_TRY(hipMemcpy(d_q, q0, qbytes, hipMemcpyHostToDevice));
-    HOST_TRY(hipMemcpy(d_off, rel, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
     for (int attempt = 0; attempt < 4; attempt++) {
         uint64_t ws_bytes = 0;
-        rc = filter_workspace_bytes(reads_out ? "slamem_find_maps_workspace_bytes" : "slamem_find_alns_workspace_bytes", reads_out ? 7 : 6,
-                                    num_queries, both_strands, qbytes, cap, ocap, max_edits, &ws_bytes);
-        if (rc) goto done;
-        HOST_TRY(hipMalloc(&d_segs, (scap + 1) * sizeof(slamem_aln)));
-        HOST_TRY(hipMalloc(&d_ops, (ocap + 1) * 4));
-        HOST_TRY(hipMalloc(&d_ooff, (scap + 2) * 8));
-        HOST_TRY(hipMalloc(&d_ws, ws_bytes));
-        rc = find_segments_device(reads_out ? "slamem_find_maps_device" : "slamem_find_alns_device", idx, d_q,
-                                  static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands, max_gap, mismatch_penalty,
-                                  xdrop, max_edits, cap, static_cast<slamem_aln*>(d_segs), scap, static_cast<uint64_t*>(d_boff),
-                                  static_cast<uint32_t*>(d_ops), ocap, static_cast<uint64_t*>(d_ooff), static_cast<slamem_map*>(d_reads),
-                                  reads_out ? 7 : 6, d_ws, ws_bytes, nullptr, totals_out);
+        SLAMEM_TRY(filter_workspace_bytes(reads_out ? "slamem_find_maps_workspace_bytes" : "slamem_find_alns_workspace_bytes", reads_out ? 7 : 6,
+                                          num_queries, both_strands, qbytes, cap, ocap, max_edits, &ws_bytes));
+        SLAMEM_TRY(d_segs.reserve(scap + 1));
+        SLAMEM_TRY(d_ops.reserve(ocap + 1));
+        SLAMEM_TRY(d_ooff.reserve(scap + 2));
+        SLAMEM_TRY(d_ws.reserve(ws_bytes));
+        rc = find_segments_device(reads_out ? "slamem_find_maps_device" : "slamem_find_alns_device", idx, d_q.get(), d_off.get(), num_queries,
+                                  qbytes, min_len, both_strands, max_gap, mismatch_penalty, xdrop, max_edits, cap, d_segs.get(), scap,
+                                  d_boff.get(), d_ops.get(), ocap, d_ooff.get(), d_reads.get(), reads_out ? 7 : 6, d_ws.get(), ws_bytes, nullptr,
+                                  totals_out);
         if (rc != SLAMEM_ERR_CAPACITY) break;
-        (void)hipFree(d_segs); d_segs = nullptr;
-        (void)hipFree(d_ops); d_ops = nullptr;
-        (void)hipFree(d_ooff); d_ooff = nullptr;
-        (void)hipFree(d_ws); d_ws = nullptr;
+        d_segs.release(); d_ops.release(); d_ooff.release(); d_ws.release();  // all of the old before any of the new
         if (totals_out[0] > cap) cap = totals_out[0] + 1024;
         if (totals_out[1] > scap) scap = totals_out[1] + 1024;
         if (totals_out[2] > ocap) ocap = totals_out[2] + 1024;
     }
-    if (rc) goto done;
-    h_segs = static_cast<slamem_aln*>(malloc((totals_out[1] + 1) * sizeof(slamem_aln)));
-    h_boff = static_cast<uint64_t*>(malloc(noff * 8));
-    if (reads_out) h_reads = static_cast<slamem_map*>(malloc(((uint64_t)num_queries + 1) * sizeof(slamem_map)));
-    h_ops = static_cast<uint32_t*>(malloc((totals_out[2] + 1) * 4));
-    h_ooff = static_cast<uint64_t*>(malloc((totals_out[1] + 1) * 8));
-    if (!h_segs || !h_boff || !h_ops || !h_ooff || (reads_out && !h_reads)) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
-    if (totals_out[1]) HOST_TRY(hipMemcpy(h_segs, d_segs, totals_out[1] * sizeof(slamem_aln), hipMemcpyDeviceToHost));
-    HOST_TRY(hipMemcpy(h_boff, d_boff, noff * 8, hipMemcpyDeviceToHost));
-    if (reads_out && num_queries) HOST_TRY(hipMemcpy(h_reads, d_reads, (uint64_t)num_queries * sizeof(slamem_map), hipMemcpyDeviceToHost));
-    if (totals_out[2]) HOST_TRY(hipMemcpy(h_ops, d_ops, totals_out[2] * 4, hipMemcpyDeviceToHost));
-    HOST_TRY(hipMemcpy(h_ooff, d_ooff, (totals_out[1] + 1) * 8, hipMemcpyDeviceToHost));
-    *segs_out = h_segs; *offsets_out = h_boff; *ops_out = h_ops; *op_offsets_out = h_ooff;
-    if (reads_out) *reads_out = h_reads;
-    h_segs = nullptr; h_boff = nullptr; h_ops = nullptr; h_ooff = nullptr; h_reads = nullptr;
-done:
-    free(rel); free(h_segs); free(h_boff); free(h_ops); free(h_ooff); free(h_reads);
-    if (d_q) (void)hipFree(d_q);
-    if (d_off) (void)hipFree(d_off);
-    if (d_boff) (void)hipFree(d_boff);
-    if (d_segs) (void)hipFree(d_segs);
-    if (d_ops) (void)hipFree(d_ops);
-    if (d_ooff) (void)hipFree(d_ooff);
-    if (d_ws) (void)hipFree(d_ws);
-    if (d_reads) (void)hipFree(d_reads);
-    return rc;
+    if (rc) return rc;
+    HostArray<slamem_aln> h_segs = host_array<slamem_aln>(totals_out[1] + 1);
+    HostArray<uint64_t> h_boff = host_array<uint64_t>(noff), h_ooff = host_array<uint64_t>(totals_out[1] + 1);
+    HostArray<uint32_t> h_ops = host_array<uint32_t>(totals_out[2] + 1);
+    HostArray<slamem_map> h_reads;
+    if (reads_out) h_reads = host_array<slamem_map>((uint64_t)num_queries + 1);
+    if (!h_segs || !h_boff || !h_ops || !h_ooff || (reads_out && !h_reads)) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
+    if (totals_out[1]) SLAMEM_HIP(hipMemcpy(h_segs.get(), d_segs.get(), totals_out[1] * sizeof(slamem_aln), hipMemcpyDeviceToHost));
+    SLAMEM_HIP(hipMemcpy(h_boff.get(), d_boff.get(), noff * 8, hipMemcpyDeviceToHost));
+    if (reads_out && num_queries) SLAMEM_HIP(hipMemcpy(h_reads.get(), d_reads.get(), (uint64_t)num_queries * sizeof(slamem_map), hipMemcpyDeviceToHost));
+    if (totals_out[2]) SLAMEM_HIP(hipMemcpy(h_ops.get(), d_ops.get(), totals_out[2] * 4, hipMemcpyDeviceToHost));
+    SLAMEM_HIP(hipMemcpy(h_ooff.get(), d_ooff.get(), (totals_out[1] + 1) * 8, hipMemcpyDeviceToHost));
+    *segs_out = h_segs.release(); *offsets_out = h_boff.release(); *ops_out = h_ops.release(); *op_offsets_out = h_ooff.release();
+    if (reads_out) *reads_out = h_reads.release();
+    return SLAMEM_OK;
 }
 
 int slamem_find_alns_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
@@ -753,66 +735,46 @@ static int find_matches_host(const char* who, const slamem_index* idx, const cha
     const bool per_row = filter && filter->column_per_row;  // (the column grows with the capacity)
     const uint64_t qbytes = offsets[num_queries];
     const uint64_t num_blocks = (uint64_t)num_queries * (both_strands ? 2 : 1);
-    void *d_q = nullptr, *d_off = nullptr, *d_boff = nullptr, *d_mems = nullptr, *d_ws = nullptr, *d_score = nullptr;
-    slamem_mem* h_mems = nullptr;
-    uint64_t* h_boff = nullptr;
-    uint32_t* h_score = nullptr;
-    int rc = SLAMEM_OK;
+    DevBuf<char> d_q, d_ws;
+    DevBuf<uint64_t> d_off, d_boff;
+    DevBuf<slamem_mem> d_mems;
+    DevBuf<uint32_t> d_score;
     uint64_t cap = qbytes / 16 + 4 * (uint64_t)num_blocks + 1024;  // first guess; grown on SLAMEM_ERR_CAPACITY
-    hipError_t e;
-    HOST_TRY(hipMalloc(&d_q, qbytes + 16));
-    HOST_TRY(hipMalloc(&d_off, ((uint64_t)num_queries + 1) * 8));
-    HOST_TRY(hipMalloc(&d_boff, (num_blocks + 1) * 8));
-    if (column_out && !per_row) HOST_TRY(hipMalloc(&d_score, (num_blocks + 1) * 4));
-    HOST_TRY(hipMemcpy(d_q, queries, qbytes, hipMemcpyHostToDevice));
-    HOST_TRY(hipMemcpy(d_off, offsets, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
+    SLAMEM_TRY(d_q.reserve(qbytes + 16));
+    SLAMEM_TRY(d_off.reserve((uint64_t)num_queries + 1));
+    SLAMEM_TRY(d_boff.reserve(num_blocks + 1));
+    if (column_out && !per_row) SLAMEM_TRY(d_score.reserve(num_blocks + 1));
+    SLAMEM_HIP(hipMemcpy(d_q.get(), queries, qbytes, hipMemcpyHostToDevice));
+    SLAMEM_HIP(hipMemcpy(d_off.get(), offsets, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
+    int rc = SLAMEM_OK;
     for (int attempt = 0; attempt < 3; attempt++) {
-        uint64_t ws_bytes = search_workspace_bytes(num_queries, both_strands, qbytes, cap, match_type, p);
-        HOST_TRY(hipMalloc(&d_mems, cap * sizeof(slamem_mem) + 16));
-        HOST_TRY(hipMalloc(&d_ws, ws_bytes));
-        if (column_out && per_row) {
-            if (d_score) (void)hipFree(d_score);
-            d_score = nullptr;
-            HOST_TRY(hipMalloc(&d_score, (cap + 1) * 4));
-        }
-        p.column_dev = static_cast<uint32_t*>(d_score);
-        rc = find_mems_device(idx, d_q, static_cast<const uint64_t*>(d_off), num_queries, qbytes, min_len, both_strands,
-                              match_type, static_cast<slamem_mem*>(d_mems), cap, static_cast<uint64_t*>(d_boff), d_ws, ws_bytes,
-                              nullptr, total_out, filter ? &p : nullptr, nullptr);
+        const uint64_t ws_bytes = search_workspace_bytes(num_queries, both_strands, qbytes, cap, match_type, p);
+        SLAMEM_TRY(d_mems.reserve(cap, 16));
+        SLAMEM_TRY(d_ws.reserve(ws_bytes));
+        if (column_out && per_row) SLAMEM_TRY(d_score.reserve(cap + 1));
+        p.column_dev = d_score.get();
+        rc = find_mems_device(idx, d_q.get(), d_off.get(), num_queries, qbytes, min_len, both_strands, match_type, d_mems.get(), cap,
+                              d_boff.get(), d_ws.get(), ws_bytes, nullptr, total_out, filter ? &p : nullptr, nullptr);
         if (rc != SLAMEM_ERR_CAPACITY) break;
-        (void)hipFree(d_mems); d_mems = nullptr;
-        (void)hipFree(d_ws); d_ws = nullptr;
+        d_mems.release(); d_ws.release();  // both of the old before either of the new
         cap = *total_out;
     }
-    if (rc) goto done;
-    h_mems = static_cast<slamem_mem*>(malloc((*total_out ? *total_out : 1) * sizeof(slamem_mem)));
-    h_boff = static_cast<uint64_t*>(malloc((num_blocks + 1) * 8));
-    if (column_out) h_score = static_cast<uint32_t*>(malloc(((per_row ? *total_out : num_blocks) + 1) * 4));
-    if (!h_mems || !h_boff || (column_out && !h_score)) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
-    if (*total_out) HOST_TRY(hipMemcpy(h_mems, d_mems, *total_out * sizeof(slamem_mem), hipMemcpyDeviceToHost));
-    HOST_TRY(hipMemcpy(h_boff, d_boff, (num_blocks + 1) * 8, hipMemcpyDeviceToHost));
+    if (rc) return rc;
+    HostArray<slamem_mem> h_mems = host_array<slamem_mem>(*total_out ? *total_out : 1);
+    HostArray<uint64_t> h_boff = host_array<uint64_t>(num_blocks + 1);
+    HostArray<uint32_t> h_score;
+    if (column_out) h_score = host_array<uint32_t>((per_row ? *total_out : num_blocks) + 1);
+    if (!h_mems || !h_boff || (column_out && !h_score)) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
+    if (*total_out) SLAMEM_HIP(hipMemcpy(h_mems.get(), d_mems.get(), *total_out * sizeof(slamem_mem), hipMemcpyDeviceToHost));
+    SLAMEM_HIP(hipMemcpy(h_boff.get(), d_boff.get(), (num_blocks + 1) * 8, hipMemcpyDeviceToHost));
     if (column_out) {
         const uint64_t nscore = per_row ? *total_out : num_blocks;
-        if (nscore) HOST_TRY(hipMemcpy(h_score, d_score, nscore * 4, hipMemcpyDeviceToHost));
-        *column_out = h_score;
-        h_score = nullptr;
+        if (nscore) SLAMEM_HIP(hipMemcpy(h_score.get(), d_score.get(), nscore * 4, hipMemcpyDeviceToHost));
+        *column_out = h_score.release();
     }
-    *mems_out = h_mems;
-    *block_offsets_out = h_boff;
-    h_mems = nullptr;
-    h_boff = nullptr;
-done:
-    free(h_mems);
-    free(h_boff);
-    free(h_score);
-    if (d_score) (void)hipFree(d_score);
-    if (d_q) (void)hipFree(d_q);
-    if (d_off) (void)hipFree(d_off);
-    if (d_boff) (void)hipFree(d_boff);
-    if (d_mems) (void)hipFree(d_mems);
-    if (d_ws) (void)hipFree(d_ws);
-    return rc;
+    *mems_out = h_mems.release();
+    *block_offsets_out = h_boff.release();
+    return SLAMEM_OK;
 }
-#undef HOST_TRY
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 //   k_cons_bounds_edge  offs[] of a bound at first + count (the total) or outside the range (UINT64_MAX)
 // A row finds its insertion's letters by a binary search for (p, kind 1) in E and a walk along the run to the marked event.
 // Nothing of the accumulator or of the event table is written: the flag bytes, E and the marks are scratch of the read-out.
+#include "buffers.h"
 #include "pile_shared.h"
 #include "prims.h"
 
@@ -459,28 +460,22 @@ int slamem_pileup_consensus_host(slamem_pileup* pile, uint64_t first, uint64_t c
     SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the table that is read)
     const uint64_t most = count * 32u;  // (a row emits at most 31 inserted letters and its own)
     const uint64_t room = capacity < most ? capacity : most;
-    void *d = nullptr, *bd = nullptr;
-    if (room) SLAMEM_HIP(hipMalloc(&d, room));
-    hipError_t e = hipSuccess;
-    if (m) e = hipMalloc(&bd, m * 16);
-    uint64_t* bdev = static_cast<uint64_t*>(bd);
-    if (m && e == hipSuccess) e = hipMemcpy(bdev, bounds, m * 8, hipMemcpyHostToDevice);
-    int rc = SLAMEM_OK;
-    if (e == hipSuccess) {
-        rc = slamem_pileup_consensus_device(pile, first, count, min_depth, room, static_cast<uint8_t*>(d), bdev, m, m ? bdev + m : nullptr,
-                                            stats_out, total_out, nullptr);
-        if (rc == SLAMEM_OK || rc == SLAMEM_ERR_CAPACITY) {
-            const uint64_t got = *total_out < room ? *total_out : room;
-            e = hipDeviceSynchronize();
-            if (got && e == hipSuccess) e = hipMemcpy(out, d, got, hipMemcpyDeviceToHost);
-            if (m && e == hipSuccess) e = hipMemcpy(offs, bdev + m, m * 8, hipMemcpyDeviceToHost);
-        }
-    }
-    if (d) (void)hipFree(d);
-    if (bd) (void)hipFree(bd);
-    if (rc != SLAMEM_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "slamem_pileup_consensus_host", __FILE__, __LINE__);
-    return SLAMEM_OK;
+    DevBuf<uint8_t> d;
+    DevBuf<uint64_t> bd;  // the m bounds, then their m offsets
+    if (room) SLAMEM_TRY(d.reserve(room));
+    if (m) SLAMEM_TRY(bd.reserve(m * 2));
+    uint64_t* bdev = bd.get();
+    if (m) SLAMEM_HIP(hipMemcpy(bdev, bounds, m * 8, hipMemcpyHostToDevice));
+    const int rc = slamem_pileup_consensus_device(pile, first, count, min_depth, room, d.get(), bdev, m, m ? bdev + m : nullptr, stats_out,
+                                                  total_out, nullptr);
+    if (rc != SLAMEM_OK && rc != SLAMEM_ERR_CAPACITY) return rc;
+    // (what fitted goes back with SLAMEM_ERR_CAPACITY too; the call's code comes before a failed copy's)
+    const uint64_t got = *total_out < room ? *total_out : room;
+    hipError_t e = hipDeviceSynchronize();
+    if (got && e == hipSuccess) e = hipMemcpy(out, d.get(), got, hipMemcpyDeviceToHost);
+    if (m && e == hipSuccess) e = hipMemcpy(offs, bdev + m, m * 8, hipMemcpyDeviceToHost);
+    if (rc == SLAMEM_OK && e != hipSuccess) return hip_fail(e, "slamem_pileup_consensus_host", __FILE__, __LINE__);
+    return rc;
 }
 
 }  // extern "C"

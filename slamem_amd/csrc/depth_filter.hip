@@ -13,6 +13,7 @@
 // The first row of a tile needs v of the row in front of it: that row's match is the tile's exclusive prefix, its counters and
 // its letter are one more row to read.  Nothing of the accumulator is written: the three numbers per tile are scratch of the
 // read-out.
+#include "buffers.h"
 #include "pile_shared.h"
 
 #include <new>
@@ -376,27 +377,22 @@ int slamem_pileup_depth_runs_host(slamem_pileup* pile, uint64_t first, uint64_t 
     SLAMEM_HIP(hipSetDevice(pile->device));
     SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the table that is read)
     const uint64_t room = capacity < count ? capacity : count;  // (a range has at most a run per row)
-    void *d = nullptr, *bd = nullptr;
-    if (room) SLAMEM_HIP(hipMalloc(&d, room * sizeof(slamem_depth_run)));
-    hipError_t e = hipSuccess;
-    if (m) e = hipMalloc(&bd, m * 24);
-    uint64_t* bdev = static_cast<uint64_t*>(bd);
-    if (m && e == hipSuccess) e = hipMemcpy(bdev, bounds, m * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = slamem_pileup_depth_runs_device(pile, first, count, levels, num_levels, min_depth, room, static_cast<slamem_depth_run*>(d), bdev,
-                                             m, m ? bdev + m : nullptr, total_out, nullptr);
-        if (rc == SLAMEM_OK || rc == SLAMEM_ERR_CAPACITY) {
-            const uint64_t got = *total_out < room ? *total_out : room;
-            e = hipDeviceSynchronize();
-            if (got && e == hipSuccess) e = hipMemcpy(runs, d, got * sizeof(slamem_depth_run), hipMemcpyDeviceToHost);
-            if (m && e == hipSuccess) e = hipMemcpy(cum, bdev + m, m * 16, hipMemcpyDeviceToHost);
-        }
-    }
-    if (d) (void)hipFree(d);
-    if (bd) (void)hipFree(bd);
-    if (rc != SLAMEM_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "slamem_pileup_depth_runs_host", __FILE__, __LINE__);
-    return SLAMEM_OK;
+    DevBuf<slamem_depth_run> d;
+    DevBuf<uint64_t> bd;  // the m bounds, then two words of sums for each
+    if (room) SLAMEM_TRY(d.reserve(room));
+    if (m) SLAMEM_TRY(bd.reserve(m * 3));
+    uint64_t* bdev = bd.get();
+    if (m) SLAMEM_HIP(hipMemcpy(bdev, bounds, m * 8, hipMemcpyHostToDevice));
+    rc = slamem_pileup_depth_runs_device(pile, first, count, levels, num_levels, min_depth, room, d.get(), bdev, m, m ? bdev + m : nullptr,
+                                         total_out, nullptr);
+    if (rc != SLAMEM_OK && rc != SLAMEM_ERR_CAPACITY) return rc;
+    // (the runs that fitted go back with SLAMEM_ERR_CAPACITY too; the call's code comes before a failed copy's)
+    const uint64_t got = *total_out < room ? *total_out : room;
+    hipError_t e = hipDeviceSynchronize();
+    if (got && e == hipSuccess) e = hipMemcpy(runs, d.get(), got * sizeof(slamem_depth_run), hipMemcpyDeviceToHost);
+    if (m && e == hipSuccess) e = hipMemcpy(cum, bdev + m, m * 16, hipMemcpyDeviceToHost);
+    if (rc == SLAMEM_OK && e != hipSuccess) return hip_fail(e, "slamem_pileup_depth_runs_host", __FILE__, __LINE__);
+    return rc;
 }
 
 }  // extern "C"

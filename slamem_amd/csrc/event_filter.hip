@@ -13,6 +13,7 @@
 //                                   (behind the scan of 4.17) their key1 and slot number at base + ballot rank: no atomics
 //   k_ev_sort_key / k_ev_gather     the second sort's key (pos, kind, len from key0) and the slamem_event records in order
 //   k_pile_rows_at                  rows of counts() at listed positions, a wave per position
+#include "buffers.h"
 #include "pile_shared.h"
 #include "prims.h"
 
@@ -459,14 +460,11 @@ int slamem_pileup_add_events_host(slamem_pileup* pile, const slamem_event* event
     if (!pile->ev) { set_error("slamem_pileup_add_events_host: the events of this accumulator are not enabled"); return SLAMEM_ERR_ARG; }
     if (m == 0) return SLAMEM_OK;
     SLAMEM_HIP(hipSetDevice(pile->device));
-    void* d = nullptr;
-    SLAMEM_HIP(hipMalloc(&d, m * sizeof(slamem_event)));
-    hipError_t e = hipMemcpy(d, events, m * sizeof(slamem_event), hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? slamem_pileup_add_events_device(pile, static_cast<const slamem_event*>(d), m, nullptr) : SLAMEM_OK;
-    if (e == hipSuccess && rc == SLAMEM_OK) e = hipDeviceSynchronize();
-    (void)hipFree(d);
-    if (rc != SLAMEM_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "slamem_pileup_add_events_host", __FILE__, __LINE__);
+    DevBuf<slamem_event> d;
+    SLAMEM_TRY(d.reserve(m));
+    SLAMEM_HIP(hipMemcpy(d.get(), events, m * sizeof(slamem_event), hipMemcpyHostToDevice));
+    SLAMEM_TRY(slamem_pileup_add_events_device(pile, d.get(), m, nullptr));
+    SLAMEM_HIP(hipDeviceSynchronize());  // (the buffer goes when this returns)
     return SLAMEM_OK;
 }
 
@@ -536,20 +534,16 @@ int slamem_pileup_events_host(slamem_pileup* pile, uint64_t first, uint64_t coun
     SLAMEM_HIP(hipSetDevice(pile->device));
     SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the table that is read)
     const uint64_t room = capacity < pile->ev->nslots ? capacity : pile->ev->nslots;  // (a table gives at most its slots)
-    void* d = nullptr;
-    if (room) SLAMEM_HIP(hipMalloc(&d, room * sizeof(slamem_event)));
-    const int rc = slamem_pileup_events_device(pile, first, count, min_count, room, static_cast<slamem_event*>(d), skipped_out, total_out,
-                                               nullptr);
-    hipError_t e = hipSuccess;
-    if (rc == SLAMEM_OK || rc == SLAMEM_ERR_CAPACITY) {
-        const uint64_t got = *total_out < room ? *total_out : room;
-        e = hipDeviceSynchronize();
-        if (got && e == hipSuccess) e = hipMemcpy(events, d, got * sizeof(slamem_event), hipMemcpyDeviceToHost);
-    }
-    if (d) (void)hipFree(d);
-    if (rc != SLAMEM_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
-    return SLAMEM_OK;
+    DevBuf<slamem_event> d;
+    if (room) SLAMEM_TRY(d.reserve(room));
+    const int rc = slamem_pileup_events_device(pile, first, count, min_count, room, d.get(), skipped_out, total_out, nullptr);
+    if (rc != SLAMEM_OK && rc != SLAMEM_ERR_CAPACITY) return rc;
+    // (the events that fitted go back with SLAMEM_ERR_CAPACITY too; the call's code comes before a failed copy's)
+    const uint64_t got = *total_out < room ? *total_out : room;
+    hipError_t e = hipDeviceSynchronize();
+    if (got && e == hipSuccess) e = hipMemcpy(events, d.get(), got * sizeof(slamem_event), hipMemcpyDeviceToHost);
+    if (rc == SLAMEM_OK && e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
+    return rc;
 }
 
 int slamem_pileup_rows_at_device(slamem_pileup* pile, const uint64_t* pos_dev, uint64_t m, uint32_t* out_dev, void* stream) {
@@ -579,23 +573,16 @@ int slamem_pileup_rows_at_host(slamem_pileup* pile, const uint64_t* pos, uint64_
     if (m == 0) return SLAMEM_OK;
     SLAMEM_HIP(hipSetDevice(pile->device));
     SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the table that is read)
-    void* d = nullptr;
-    SLAMEM_HIP(hipMalloc(&d, m * 32));
-    uint64_t* pd = static_cast<uint64_t*>(d);
-    uint32_t* od = reinterpret_cast<uint32_t*>(static_cast<char*>(d) + m * 8);
-    hipError_t e = hipMemcpy(pd, pos, m * 8, hipMemcpyHostToDevice);
-    int rc = SLAMEM_OK;
-    if (e == hipSuccess) rc = pile_tile_prefix(pile, largest + 1, nullptr);  // (up to the largest position)
-    if (e == hipSuccess && rc == SLAMEM_OK) {
-        hipLaunchKernelGGL(k_pile_rows_at, dim3(pile_grid(m, 4)), dim3(256), 0, nullptr, (const int32_t*)pile->diff,
-                           (const uint32_t*)pile->cnt, (const uint32_t*)pile->tile, pile->idx->view.tpl, (uint64_t)pile->n,
-                           (const uint64_t*)pd, m, od);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && rc == SLAMEM_OK) e = hipMemcpy(out, od, m * 24, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (rc != SLAMEM_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "slamem_pileup_rows_at_host", __FILE__, __LINE__);
+    DevBuf<uint64_t> d;  // m positions, then m rows of six uint32
+    SLAMEM_TRY(d.reserve(m * 4));
+    uint64_t* pd = d.get();
+    uint32_t* od = reinterpret_cast<uint32_t*>(pd + m);
+    SLAMEM_HIP(hipMemcpy(pd, pos, m * 8, hipMemcpyHostToDevice));
+    SLAMEM_TRY(pile_tile_prefix(pile, largest + 1, nullptr));  // (up to the largest position)
+    hipLaunchKernelGGL(k_pile_rows_at, dim3(pile_grid(m, 4)), dim3(256), 0, nullptr, (const int32_t*)pile->diff, (const uint32_t*)pile->cnt,
+                       (const uint32_t*)pile->tile, pile->idx->view.tpl, (uint64_t)pile->n, (const uint64_t*)pd, m, od);
+    SLAMEM_HIP(hipGetLastError());
+    SLAMEM_HIP(hipMemcpy(out, od, m * 24, hipMemcpyDeviceToHost));
     return SLAMEM_OK;
 }
 

@@ -27,6 +27,7 @@
 //                  and a letter whose bit is set counts nowhere under = and X.  The same bodies (a template parameter); an `=`
 //                  run ORs the mask's window over its letters into the text's exclusion bits, 64 rows at a time.
 // Counters are 32 bits wide and every sum is taken modulo 2^32: a true depth of 2^31 or more at one row is outside the contract.
+#include "buffers.h"
 #include "pile_shared.h"
 
 #include <new>
@@ -693,13 +694,10 @@ int slamem_pileup_counts_host(slamem_pileup* pile, uint64_t first, uint64_t coun
     if (count == 0) return SLAMEM_OK;
     SLAMEM_HIP(hipSetDevice(pile->device));
     SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the table that is read)
-    void* d = nullptr;
-    SLAMEM_HIP(hipMalloc(&d, count * 24));
-    int rc = slamem_pileup_counts_device(pile, first, count, static_cast<uint32_t*>(d), nullptr);
-    hipError_t e = rc == SLAMEM_OK ? hipMemcpy(out, d, count * 24, hipMemcpyDeviceToHost) : hipSuccess;
-    (void)hipFree(d);
-    if (rc != SLAMEM_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
+    DevBuf<uint32_t> d;
+    SLAMEM_TRY(d.reserve(count * 6));
+    SLAMEM_TRY(slamem_pileup_counts_device(pile, first, count, d.get(), nullptr));
+    SLAMEM_HIP(hipMemcpy(out, d.get(), count * 24, hipMemcpyDeviceToHost));
     return SLAMEM_OK;
 }
 
@@ -763,24 +761,22 @@ int slamem_pileup_sites_host(slamem_pileup* pile, uint64_t first, uint64_t count
     SLAMEM_HIP(hipSetDevice(pile->device));
     SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the table that is read)
     const uint64_t room = capacity < count ? capacity : count;  // (a range selects at most its rows)
-    void* d = nullptr;
-    if (room) SLAMEM_HIP(hipMalloc(&d, room * 33));
-    char* b = static_cast<char*>(d);
+    DevBuf<char> d;
+    if (room) SLAMEM_TRY(d.reserve(room * 33));
+    char* b = d.get();
     uint64_t* pd = reinterpret_cast<uint64_t*>(b);
     uint32_t* cd = reinterpret_cast<uint32_t*>(b + room * 8);
     uint8_t* ad = reinterpret_cast<uint8_t*>(b + room * 32);
     const int rc = slamem_pileup_sites_device(pile, first, count, mode, min_depth, min_pct, room, pd, cd, ad, total_out, nullptr);
+    if (rc != SLAMEM_OK && rc != SLAMEM_ERR_CAPACITY) return rc;
+    // (the rows that fitted go back with SLAMEM_ERR_CAPACITY too; the call's code comes before a failed copy's)
+    const uint64_t got = *total_out < room ? *total_out : room;
     hipError_t e = hipSuccess;
-    if (rc == SLAMEM_OK || rc == SLAMEM_ERR_CAPACITY) {
-        const uint64_t got = *total_out < room ? *total_out : room;
-        if (got) e = hipMemcpy(pos, pd, got * 8, hipMemcpyDeviceToHost);
-        if (got && e == hipSuccess) e = hipMemcpy(counts, cd, got * 24, hipMemcpyDeviceToHost);
-        if (got && e == hipSuccess) e = hipMemcpy(alleles, ad, got, hipMemcpyDeviceToHost);
-    }
-    if (d) (void)hipFree(d);
-    if (rc != SLAMEM_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
-    return SLAMEM_OK;
+    if (got) e = hipMemcpy(pos, pd, got * 8, hipMemcpyDeviceToHost);
+    if (got && e == hipSuccess) e = hipMemcpy(counts, cd, got * 24, hipMemcpyDeviceToHost);
+    if (got && e == hipSuccess) e = hipMemcpy(alleles, ad, got, hipMemcpyDeviceToHost);
+    if (rc == SLAMEM_OK && e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
+    return rc;
 }
 
 int slamem_pileup_add_counts_device(slamem_pileup* pile, uint64_t first, uint64_t count, const uint32_t* rows_dev, void* stream) {
@@ -807,14 +803,11 @@ int slamem_pileup_add_counts_host(slamem_pileup* pile, uint64_t first, uint64_t 
     }
     if (count == 0) return SLAMEM_OK;
     SLAMEM_HIP(hipSetDevice(pile->device));
-    void* d = nullptr;
-    SLAMEM_HIP(hipMalloc(&d, count * 24));
-    hipError_t e = hipMemcpy(d, rows, count * 24, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? slamem_pileup_add_counts_device(pile, first, count, static_cast<const uint32_t*>(d), nullptr) : SLAMEM_OK;
-    if (e == hipSuccess && rc == SLAMEM_OK) e = hipDeviceSynchronize();
-    (void)hipFree(d);
-    if (rc != SLAMEM_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "slamem_pileup_add_counts_host", __FILE__, __LINE__);
+    DevBuf<uint32_t> d;
+    SLAMEM_TRY(d.reserve(count * 6));
+    SLAMEM_HIP(hipMemcpy(d.get(), rows, count * 24, hipMemcpyHostToDevice));
+    SLAMEM_TRY(slamem_pileup_add_counts_device(pile, first, count, d.get(), nullptr));
+    SLAMEM_HIP(hipDeviceSynchronize());  // (the buffer goes when this returns)
     return SLAMEM_OK;
 }
 

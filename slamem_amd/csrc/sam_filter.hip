@@ -11,6 +11,7 @@
 //                     operations' entry counts, m carried across trips and across I
 //   k_sam_primary     a lane per read: the segment with the most letters under `=`, the first on a tie
 // No store goes at or behind md_capacity; the total comes back with one copy at the end.
+#include "buffers.h"
 #include "filter_blocks.h"
 #include "pile_shared.h"
 
@@ -239,10 +240,51 @@ int slamem_maps_md_device(const slamem_index* idx, const slamem_aln* segs_dev, u
     return SLAMEM_OK;
 }
 
-#define MD_TRY(call) if ((e = (call)) != hipSuccess) { rc = hip_fail(e, #call, __FILE__, __LINE__); goto done; }
-
-// slamem_find_maps_host, then the MD pass over its arrays (uploaded again: this is the convenience path; a caller that minds the
+// the MD pass over the arrays slamem_find_maps_host gave (uploaded again: this is the convenience path; a caller that minds the
 // copies uses the device functions or a stream).  The entries' room is the sure bound, the sum of edits + the segments.
+static int md_of_host_maps(const slamem_index* idx, uint32_t num_queries, const slamem_aln* segs, const uint64_t* read_offsets,
+                           const uint32_t* ops, const uint64_t* op_offsets, const uint64_t* totals, uint32_t** md_out,
+                           uint64_t** md_offsets_out, uint32_t** seg_eq_out, uint32_t** primary_out, uint64_t* md_total_out) {
+    const uint64_t ns = totals[1], nops = totals[2];
+    uint64_t cap = ns;
+    for (uint64_t s = 0; s < ns; s++) cap += segs[s].edits;
+    uint64_t ws_bytes = 0, total = 0;
+    SLAMEM_TRY(slamem_maps_md_workspace_bytes(ns, num_queries, &ws_bytes));
+    DevBuf<slamem_aln> d_segs;
+    DevBuf<uint64_t> d_roff, d_ooff, d_moff;
+    DevBuf<uint32_t> d_ops, d_md, d_eq, d_prim;
+    DevBuf<char> d_ws;
+    SLAMEM_HIP(hipSetDevice(idx->device));
+    SLAMEM_TRY(d_segs.reserve(ns + 1));
+    SLAMEM_TRY(d_roff.reserve((uint64_t)num_queries + 1));
+    SLAMEM_TRY(d_ops.reserve(nops + 1));
+    SLAMEM_TRY(d_ooff.reserve(ns + 1));
+    SLAMEM_TRY(d_md.reserve(cap + 1));
+    SLAMEM_TRY(d_moff.reserve(ns + 1));
+    SLAMEM_TRY(d_eq.reserve(ns + 1));
+    SLAMEM_TRY(d_prim.reserve((uint64_t)num_queries + 1));
+    SLAMEM_TRY(d_ws.reserve(ws_bytes + 16));
+    if (ns) SLAMEM_HIP(hipMemcpy(d_segs.get(), segs, ns * sizeof(slamem_aln), hipMemcpyHostToDevice));
+    SLAMEM_HIP(hipMemcpy(d_roff.get(), read_offsets, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
+    if (nops) SLAMEM_HIP(hipMemcpy(d_ops.get(), ops, nops * 4, hipMemcpyHostToDevice));
+    SLAMEM_HIP(hipMemcpy(d_ooff.get(), op_offsets, (ns + 1) * 8, hipMemcpyHostToDevice));
+    SLAMEM_TRY(slamem_maps_md_device(idx, d_segs.get(), ns, d_roff.get(), num_queries, d_ops.get(), d_ooff.get(), d_md.get(), cap, d_moff.get(),
+                                     d_eq.get(), d_prim.get(), d_ws.get(), ws_bytes, nullptr, &total));
+    HostArray<uint32_t> h_md = host_array<uint32_t>(total + 1), h_eq = host_array<uint32_t>(ns + 1),
+                        h_prim = host_array<uint32_t>((uint64_t)num_queries + 1);
+    HostArray<uint64_t> h_moff = host_array<uint64_t>(ns + 1);
+    if (!h_md || !h_moff || !h_eq || !h_prim) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
+    SLAMEM_HIP(hipDeviceSynchronize());
+    if (total) SLAMEM_HIP(hipMemcpy(h_md.get(), d_md.get(), total * 4, hipMemcpyDeviceToHost));
+    SLAMEM_HIP(hipMemcpy(h_moff.get(), d_moff.get(), (ns + 1) * 8, hipMemcpyDeviceToHost));
+    if (ns) SLAMEM_HIP(hipMemcpy(h_eq.get(), d_eq.get(), ns * 4, hipMemcpyDeviceToHost));
+    if (num_queries) SLAMEM_HIP(hipMemcpy(h_prim.get(), d_prim.get(), (uint64_t)num_queries * 4, hipMemcpyDeviceToHost));
+    *md_out = h_md.release(); *md_offsets_out = h_moff.release(); *seg_eq_out = h_eq.release(); *primary_out = h_prim.release();
+    *md_total_out = total;
+    return SLAMEM_OK;
+}
+
+// slamem_find_maps_host, then the MD pass over its arrays; if the pass fails, the mapping's arrays go too
 int slamem_find_maps_md_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
                              int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
                              slamem_aln** segs_out, uint64_t** read_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
@@ -261,59 +303,8 @@ int slamem_find_maps_md_host(const slamem_index* idx, const char* queries, const
     int rc = slamem_find_maps_host(idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty, xdrop, max_edits,
                                    segs_out, read_offsets_out, ops_out, op_offsets_out, reads_out, totals_out);
     if (rc != SLAMEM_OK) return rc;
-    const uint64_t ns = totals_out[1], nops = totals_out[2];
-    uint64_t cap = ns;
-    for (uint64_t s = 0; s < ns; s++) cap += (*segs_out)[s].edits;
-    void *d_segs = nullptr, *d_roff = nullptr, *d_ops = nullptr, *d_ooff = nullptr, *d_md = nullptr, *d_moff = nullptr, *d_eq = nullptr,
-         *d_prim = nullptr, *d_ws = nullptr;
-    uint32_t *h_md = nullptr, *h_eq = nullptr, *h_prim = nullptr;
-    uint64_t* h_moff = nullptr;
-    uint64_t ws_bytes = 0, total = 0;
-    hipError_t e;
-    rc = slamem_maps_md_workspace_bytes(ns, num_queries, &ws_bytes);
-    if (rc != SLAMEM_OK) goto done;
-    MD_TRY(hipSetDevice(idx->device));
-    MD_TRY(hipMalloc(&d_segs, (ns + 1) * sizeof(slamem_aln)));
-    MD_TRY(hipMalloc(&d_roff, ((uint64_t)num_queries + 1) * 8));
-    MD_TRY(hipMalloc(&d_ops, (nops + 1) * 4));
-    MD_TRY(hipMalloc(&d_ooff, (ns + 1) * 8));
-    MD_TRY(hipMalloc(&d_md, (cap + 1) * 4));
-    MD_TRY(hipMalloc(&d_moff, (ns + 1) * 8));
-    MD_TRY(hipMalloc(&d_eq, (ns + 1) * 4));
-    MD_TRY(hipMalloc(&d_prim, ((uint64_t)num_queries + 1) * 4));
-    MD_TRY(hipMalloc(&d_ws, ws_bytes + 16));
-    if (ns) MD_TRY(hipMemcpy(d_segs, *segs_out, ns * sizeof(slamem_aln), hipMemcpyHostToDevice));
-    MD_TRY(hipMemcpy(d_roff, *read_offsets_out, ((uint64_t)num_queries + 1) * 8, hipMemcpyHostToDevice));
-    if (nops) MD_TRY(hipMemcpy(d_ops, *ops_out, nops * 4, hipMemcpyHostToDevice));
-    MD_TRY(hipMemcpy(d_ooff, *op_offsets_out, (ns + 1) * 8, hipMemcpyHostToDevice));
-    rc = slamem_maps_md_device(idx, static_cast<const slamem_aln*>(d_segs), ns, static_cast<const uint64_t*>(d_roff), num_queries,
-                               static_cast<const uint32_t*>(d_ops), static_cast<const uint64_t*>(d_ooff), static_cast<uint32_t*>(d_md), cap,
-                               static_cast<uint64_t*>(d_moff), static_cast<uint32_t*>(d_eq), static_cast<uint32_t*>(d_prim), d_ws, ws_bytes,
-                               nullptr, &total);
-    if (rc != SLAMEM_OK) goto done;
-    h_md = static_cast<uint32_t*>(malloc((total + 1) * 4));
-    h_moff = static_cast<uint64_t*>(malloc((ns + 1) * 8));
-    h_eq = static_cast<uint32_t*>(malloc((ns + 1) * 4));
-    h_prim = static_cast<uint32_t*>(malloc(((uint64_t)num_queries + 1) * 4));
-    if (!h_md || !h_moff || !h_eq || !h_prim) { set_error("out of host memory"); rc = SLAMEM_ERR_NOMEM; goto done; }
-    MD_TRY(hipDeviceSynchronize());
-    if (total) MD_TRY(hipMemcpy(h_md, d_md, total * 4, hipMemcpyDeviceToHost));
-    MD_TRY(hipMemcpy(h_moff, d_moff, (ns + 1) * 8, hipMemcpyDeviceToHost));
-    if (ns) MD_TRY(hipMemcpy(h_eq, d_eq, ns * 4, hipMemcpyDeviceToHost));
-    if (num_queries) MD_TRY(hipMemcpy(h_prim, d_prim, (uint64_t)num_queries * 4, hipMemcpyDeviceToHost));
-    *md_out = h_md; *md_offsets_out = h_moff; *seg_eq_out = h_eq; *primary_out = h_prim; *md_total_out = total;
-    h_md = nullptr; h_moff = nullptr; h_eq = nullptr; h_prim = nullptr;
-done:
-    free(h_md); free(h_moff); free(h_eq); free(h_prim);
-    if (d_segs) (void)hipFree(d_segs);
-    if (d_roff) (void)hipFree(d_roff);
-    if (d_ops) (void)hipFree(d_ops);
-    if (d_ooff) (void)hipFree(d_ooff);
-    if (d_md) (void)hipFree(d_md);
-    if (d_moff) (void)hipFree(d_moff);
-    if (d_eq) (void)hipFree(d_eq);
-    if (d_prim) (void)hipFree(d_prim);
-    if (d_ws) (void)hipFree(d_ws);
+    rc = md_of_host_maps(idx, num_queries, *segs_out, *read_offsets_out, *ops_out, *op_offsets_out, totals_out, md_out, md_offsets_out,
+                         seg_eq_out, primary_out, md_total_out);
     if (rc != SLAMEM_OK) {
         slamem_host_free(*segs_out); slamem_host_free(*read_offsets_out); slamem_host_free(*ops_out); slamem_host_free(*op_offsets_out);
         slamem_host_free(*reads_out);
@@ -321,6 +312,5 @@ done:
     }
     return rc;
 }
-#undef MD_TRY
 
 }  // extern "C"

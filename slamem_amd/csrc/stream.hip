@@ -20,11 +20,24 @@
 // -pile (match type 8) is -paf whose segments stay on the device: the download stage, once the batch's totals have shown that
 // its result stands, enqueues the add to the accumulator (pile_filter.hip) on its stream and copies out the read records only.
 // No CPU fallback: every batch is searched on the GPU.
+//
+// WHO OWNS WHAT.  Every buffer of a slot is a DevBuf or a PinnedBuf (buffers.h): freed by its destructor, grown by reserve(),
+// which lets the old memory go first.  The stage that uses a buffer reserves it on the slot's first batch -- nothing is
+// allocated at slamem_stream_create, and a batch no larger than the ones before allocates and frees nothing.
+//   upload    the inputs: letters, record offsets, block offsets, read records (and planes, unit counts, mask words)
+//   prepare   the outputs, sized by the inputs' room: rows, workspace, -ext's column, -aln's segments and operations
+//   download  the MD arrays and all pinned host memory; the outputs again when a batch's totals did not fit
+// INPUTS REGROWN => OUTPUTS DROPPED: where the upload stage regrows a slot's inputs it drops every output buffer
+// (drop_outputs), and the prepare stage, which finds no workspace, sizes them for the new room.
+// The end of a stream (teardown(): destroy, and a create that failed half way): every HIP stream waited for, then the slots
+// with their buffers, events and jobs, then the HIP streams.
+#include "buffers.h"
 #include "common.h"
 #include "prims.h"
 
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdlib.h>
@@ -44,74 +57,77 @@ enum { T_UP = 0, T_PREP = 1, T_SEARCH = 2, T_DOWN = 3 };
 
 struct Slot {
     int state = FREE;
-    // device
-    void* d_q = nullptr;
-    uint64_t* d_off = nullptr;
-    uint64_t* d_boff = nullptr;
-    slamem_mem* d_mems = nullptr;
-    void* d_ws = nullptr;
-    uint64_t cap = 0, ws_bytes = 0;
-    uint64_t cap_chars = 0;   // room of d_q (characters), of d_off / d_boff / h_boff (records): grown when a batch needs more
+    // The batch's INPUTS on the device, allocated by the upload stage: letters (cap_chars of them behind kFront bytes), record
+    // offsets, and the two arrays a record each that the search writes -- block offsets, -paf's read records -- (cap_q records).
+    // cap_chars and cap_q are what the kernels and the prepare stage are told; both are 0 until all of these are there.
+    DevBuf<char> d_q;
+    DevBuf<uint64_t> d_off, d_boff;
+    DevBuf<slamem_map> d_reads;
+    uint64_t cap_chars = 0;
     uint32_t cap_q = 0;
-    // pinned host
-    uint64_t* h_boff = nullptr;
-    slamem_mem* h_mems = nullptr;
-    uint64_t h_cap = 0, h_boff_cap = 0;
-    // -ext: the mismatches of the batch's rows, a uint32 each (device: room for `cap` rows; pinned host: for `h_mm_cap`)
-    uint32_t* d_mm = nullptr;
-    uint32_t* h_mm = nullptr;
-    uint64_t h_mm_cap = 0;
-    // -aln: segments (room for `cap`: a segment has at least one chain row), operations (room for `ops_cap`) and the
-    // operations' offsets per segment, on the device and in pinned host memory; ops_total: the batch's operations
-    slamem_aln* d_segs = nullptr;
-    uint32_t* d_ops = nullptr;
-    uint64_t* d_ooff = nullptr;
-    slamem_aln* h_segs = nullptr;
-    uint32_t* h_ops = nullptr;
-    uint64_t* h_ooff = nullptr;
-    uint64_t ops_cap = 0, h_segs_cap = 0, h_ops_cap = 0, ops_total = 0;
-    // -paf: a record per read (room for cap_q), on the device and in pinned host memory
-    slamem_map* d_reads = nullptr;
-    slamem_map* h_reads = nullptr;
-    uint64_t h_reads_cap = 0;
-    // -sam (slamem_stream_set_md): the MD entries (room for md_cap), their offsets and the letters under `=` per segment (room
-    // for md_segs_cap segments), the primary segment per read (room for md_q_cap), and the pass's workspace; nothing of it
-    // exists on a stream whose MD pass is off
-    uint32_t *d_md = nullptr, *d_seg_eq = nullptr, *d_primary = nullptr;
-    uint64_t* d_md_off = nullptr;
-    void* d_md_ws = nullptr;
-    uint32_t *h_md = nullptr, *h_seg_eq = nullptr, *h_primary = nullptr;
-    uint64_t* h_md_off = nullptr;
-    uint64_t md_cap = 0, md_segs_cap = 0, md_q_cap = 0, md_ws_bytes = 0, h_md_cap = 0, md_total = 0;
+    // a batch handed in as bit-planes (slamem_stream_submit_packed): 16-byte units {p0, p1}, the letters that are not A,C,G,T per
+    // unit (cap_units of each), and the units per record with their prefix sums and the scan's scratch behind them (sized by cap_q)
+    DevBuf<uint4> d_planes;
+    DevBuf<uint64_t> d_other;
+    DevBuf<uint32_t> d_ucnt;
+    uint64_t cap_units = 0;
+    // a batch handed in with a low-quality mask (slamem_stream_submit_masked): the words the batch touches --
+    // d_lowq[0] is the caller's word offs[0] / 64
+    DevBuf<uint64_t> d_lowq;
+    // The batch's OUTPUTS on the device, sized by the inputs' room and allocated by grow_outputs (prepare stage; download stage on
+    // a capacity retry): -mem rows (room for `cap`) and the search's workspace; -ext: a uint32 per row; -aln: segments (room for
+    // `cap`: a segment has at least one chain row), operations (room for `ops_cap`) and the operations' offsets per segment.
+    // INPUTS REGROWN => OUTPUTS DROPPED (drop_outputs): the prepare stage sizes them again from the new room.
+    DevBuf<slamem_mem> d_mems;
+    DevBuf<char> d_ws;
+    DevBuf<uint32_t> d_mm;
+    DevBuf<slamem_aln> d_segs;
+    DevBuf<uint32_t> d_ops;
+    DevBuf<uint64_t> d_ooff;
+    uint64_t cap = 0, ops_cap = 0;
+    // -sam (slamem_stream_set_md), download stage: the MD entries (room for md_cap), their offsets and the letters under `=` per
+    // segment, the primary segment per read, and the pass's workspace; nothing of it exists on a stream whose MD pass is off
+    DevBuf<uint32_t> d_md, d_seg_eq, d_primary;
+    DevBuf<uint64_t> d_md_off;
+    DevBuf<char> d_md_ws;
+    uint64_t md_cap = 0;
+    // what slamem_stream_next and the getters hand out, in pinned host memory, allocated by the download stage as large as the
+    // device buffer each is copied from; h_scal: the words K9's stream copies the batch's totals into (prepare stage)
+    PinnedBuf<uint64_t> h_boff;
+    PinnedBuf<slamem_mem> h_mems;
+    PinnedBuf<uint32_t> h_mm;
+    PinnedBuf<slamem_aln> h_segs;
+    PinnedBuf<uint32_t> h_ops;
+    PinnedBuf<uint64_t> h_ooff;
+    PinnedBuf<slamem_map> h_reads;
+    PinnedBuf<uint32_t> h_md, h_seg_eq, h_primary;
+    PinnedBuf<uint64_t> h_md_off;
+    PinnedBuf<unsigned long long> h_scal;
     // the batch
     uint64_t seq = 0;
     const char* chars = nullptr;
     const uint64_t* offs = nullptr;
     uint32_t nq = 0, min_len = 0;
     bool all_short = false;  // no record longer than a slice (seen by the upload stage while the copy engines work)
-    // a batch handed in as bit-planes (slamem_stream_submit_packed): what goes up, and the device side of it
-    const void* planes = nullptr;       // 16-byte units {p0, p1}: letters 64u .. 64u+63 of a record; a record starts a new unit
-    const uint64_t* other = nullptr;    // per unit: letters that are not A,C,G,T (nullptr: none)
-    void* d_planes = nullptr;
-    uint64_t* d_other = nullptr;
-    uint32_t* d_ucnt = nullptr;         // units per record, then their prefix sums (and the scan's scratch behind them)
-    uint64_t cap_units = 0;
-    uint64_t units_hint = 0;            // the batch's units as the caller counted them (0: count here)
-    // a batch handed in with a low-quality mask (slamem_stream_submit_masked): the caller's words, indexed as its
-    // letters, and the words the batch touches on the device -- d_lowq[0] is the caller's word offs[0] / 64
-    const uint64_t* lowq = nullptr;
-    uint64_t* d_lowq = nullptr;
-    uint64_t cap_lowq = 0;              // words of d_lowq
+    const void* planes = nullptr;       // packed: letters 64u .. 64u+63 of a record per unit; a record starts a new unit
+    const uint64_t* other = nullptr;    // packed: per unit, letters that are not A,C,G,T (nullptr: none)
+    uint64_t units_hint = 0;            // packed: the batch's units as the caller counted them (0: count here)
+    const uint64_t* lowq = nullptr;     // masked: the caller's words, indexed as its letters
     // its result
-    uint64_t total = 0;
+    uint64_t total = 0, ops_total = 0, md_total = 0;
     int rc = SLAMEM_OK;
     char err[512] = "";
     slamem_timings tm;
-    // the batch on its way through the search (mem_search.hip), the events the stages hand it over with, and the pinned
-    // words K9's stream copies the batch's totals into
+    // the batch on its way through the search (mem_search.hip) and the events the stages hand it over with
     SearchJob* job = nullptr;
     hipEvent_t ev_prep = nullptr, ev_done = nullptr, ev_k8 = nullptr;
-    unsigned long long* h_scal = nullptr;
+
+    ~Slot() {  // (the buffers free themselves)
+        if (ev_prep) (void)hipEventDestroy(ev_prep);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (ev_k8) (void)hipEventDestroy(ev_k8);
+        if (job) search_job_delete(job);
+    }
 };
 
 }  // namespace
@@ -133,7 +149,7 @@ struct slamem_stream {
     bool md = false;                        // -sam: every batch also goes through the MD pass (slamem_stream_set_md)
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
-    Slot slot[kMaxSlots];
+    std::unique_ptr<Slot[]> slot;  // nslots of them; they go in teardown(), in front of the HIP streams
     std::thread th[kThreads];
     hipStream_t st[kThreads] = {};
     hipStream_t st_upx[3] = {nullptr, nullptr, nullptr};  // more copy streams of the upload stage (SLAMEM_STREAM_UPLOAD_SPLIT = 2..4)
@@ -174,37 +190,37 @@ inline int job_type(const slamem_stream* s) { return s->match_type == 8 ? 7 : s-
 FilterParams slot_params(const slamem_stream* s, const Slot& sl) {
     FilterParams p = {};  // (the setters have refused what the resolver refuses)
     (void)resolve_filter_params("slamem_stream", s->max_occ, s->max_gap, s->ext_penalty, s->ext_xdrop, s->max_edits, &p);
-    if (s->match_type == 5) p.column_dev = sl.d_mm;
+    if (s->match_type == 5) p.column_dev = sl.d_mm.get();
     if (is_aln(s)) {
-        p.segs = sl.d_segs; p.segs_capacity = sl.cap;
-        p.ops = sl.d_ops; p.ops_capacity = sl.ops_cap;
-        p.op_offsets = sl.d_ooff;
-        p.reads = is_map(s) ? sl.d_reads : nullptr;
+        p.segs = sl.d_segs.get(); p.segs_capacity = sl.cap;
+        p.ops = sl.d_ops.get(); p.ops_capacity = sl.ops_cap;
+        p.op_offsets = sl.d_ooff.get();
+        p.reads = is_map(s) ? sl.d_reads.get() : nullptr;
     }
     return p;
 }
 
-int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search stage: device output + workspace
-    if (sl.d_mems) (void)hipFree(sl.d_mems);
-    if (sl.d_ws) (void)hipFree(sl.d_ws);
-    if (sl.d_mm) (void)hipFree(sl.d_mm);
-    sl.d_mems = nullptr; sl.d_ws = nullptr; sl.d_mm = nullptr;
+// Every device buffer that is sized by the room of the slot's inputs.  Called where the outputs get another size AND where the
+// upload stage regrows the inputs: a slot without d_ws is a slot whose outputs the prepare stage sizes anew.
+void drop_outputs(Slot& sl) {
+    sl.d_ws.release(); sl.d_mems.release(); sl.d_mm.release();
+    sl.d_segs.release(); sl.d_ops.release(); sl.d_ooff.release();
+}
+
+// device output + workspace for `need_cap` rows (prepare stage; download stage on a capacity retry).  All of the old goes
+// before any of the new is asked for; d_ws comes last, so that a slot that has it has them all.
+int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {
+    drop_outputs(sl);
     sl.cap = need_cap;
     if (is_aln(s)) {
-        if (sl.d_segs) (void)hipFree(sl.d_segs);
-        if (sl.d_ops) (void)hipFree(sl.d_ops);
-        if (sl.d_ooff) (void)hipFree(sl.d_ooff);
-        sl.d_segs = nullptr; sl.d_ops = nullptr; sl.d_ooff = nullptr;
         if (sl.ops_cap < 2 * sl.cap + 1024) sl.ops_cap = 2 * sl.cap + 1024;  // (a first guess; SLAMEM_ERR_CAPACITY tells the need)
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_segs), (sl.cap + 1) * sizeof(slamem_aln)));
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ops), (sl.ops_cap + 1) * 4));
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ooff), (sl.cap + 2) * 8));
+        SLAMEM_TRY(sl.d_segs.reserve(sl.cap + 1));
+        SLAMEM_TRY(sl.d_ops.reserve(sl.ops_cap + 1));
+        SLAMEM_TRY(sl.d_ooff.reserve(sl.cap + 2));
     }
-    sl.ws_bytes = search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, job_type(s), slot_params(s, sl));
-    SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mems), sl.cap * sizeof(slamem_mem) + 16));
-    SLAMEM_HIP(hipMalloc(&sl.d_ws, sl.ws_bytes));
-    if (s->match_type == 5) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_mm), sl.cap * 4 + 16));
-    return SLAMEM_OK;
+    SLAMEM_TRY(sl.d_mems.reserve(sl.cap, 16));
+    if (s->match_type == 5) SLAMEM_TRY(sl.d_mm.reserve(sl.cap + 4));
+    return sl.d_ws.reserve(search_workspace_bytes(sl.cap_q, s->both, sl.cap_chars, sl.cap, job_type(s), slot_params(s, sl)));
 }
 
 // stage 0: characters and offsets to the device.  The offsets go up as the caller holds them (absolute): the characters land
@@ -214,7 +230,33 @@ int grow_outputs(slamem_stream* s, Slot& sl, uint64_t need_cap) {  // search sta
 constexpr uint64_t kFront = 32;  // bytes in front of the characters: the kernels read whole aligned words around a record
 inline const char* device_queries(const Slot& sl) {
     const uint64_t base = sl.offs[0];
-    return static_cast<const char*>(sl.d_q) + kFront + (base & 15u) - base;
+    return sl.d_q.get() + kFront + (base & 15u) - base;
+}
+// Beside K8 -- which keeps the memory system at its random-request ceiling -- ONE copy engine moves 42 GB/s instead of the
+// link's 57 (measured: 3.56 ms per 158 MB instead of 2.76, which made the upload the pipeline's period); the pieces of a
+// batch go up on `upload_split` copy streams side by side.  Returns the streams used in *ways: the first is s->st[0], the
+// caller waits for the others (s->st_upx[0 .. ways - 2]).
+int copy_split(slamem_stream* s, void* dst, const void* src, uint64_t bytes, int* ways) {
+    *ways = (s->upload_split > 1 && bytes >= (8u << 20)) ? s->upload_split : 1;
+    uint64_t at = 0;
+    for (int wy = 0; wy < *ways; wy++) {
+        const uint64_t end = wy + 1 == *ways ? bytes : ((bytes * (uint64_t)(wy + 1) / (uint64_t)*ways) & ~(uint64_t)4095);
+        hipStream_t cs = wy == 0 ? s->st[0] : s->st_upx[wy - 1];
+        if (end > at)
+            SLAMEM_HIP(hipMemcpyAsync(static_cast<char*>(dst) + at, static_cast<const char*>(src) + at, end - at, hipMemcpyHostToDevice, cs));
+        at = end;
+    }
+    return SLAMEM_OK;
+}
+// while the copy engines work: is any record longer than a slice?  (if not, the prepare stage knows the number of work items
+// without asking the device -- its one host round trip per batch goes away)
+bool all_records_short(const Slot& sl) {
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < sl.nq; i++) {
+        const uint64_t len = sl.offs[i + 1] - sl.offs[i];
+        longest = len > longest ? len : longest;
+    }
+    return longest <= kSearchSliceLen;
 }
 // ---- reads that come as bit-planes (slamem_stream_submit_packed) -------------------------------------------------------------
 // The link is what bounds the host-to-host path since the search takes 9 ms for 10 M reads (1.5 GB of letters: 26 ms at 57
@@ -279,45 +321,31 @@ int stage_upload_packed(slamem_stream* s, Slot& sl, char* dst) {
     if (units == 0)
         for (uint32_t i = 0; i < sl.nq; i++) units += (sl.offs[i + 1] - sl.offs[i] + 63u) >> 6;
     if (units >= 0xFFFFFFFFull) { set_error("slamem_stream_submit_packed: fewer than 2^32 units (64 letters) per batch"); return SLAMEM_ERR_ARG; }
-    if (!sl.d_planes || units > sl.cap_units) {
-        if (sl.d_planes) (void)hipFree(sl.d_planes);
-        if (sl.d_other) (void)hipFree(sl.d_other);
-        sl.d_planes = nullptr; sl.d_other = nullptr; sl.cap_units = 0;
+    if (!sl.d_planes.get() || units > sl.cap_units) {
+        sl.d_planes.release(); sl.d_other.release();
+        sl.cap_units = 0;  // until both are there
         const uint64_t want = units > (s->max_chars >> 6) + s->max_q ? units : (s->max_chars >> 6) + s->max_q;
-        SLAMEM_HIP(hipMalloc(&sl.d_planes, (want + 1) * 16));
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_other), (want + 1) * 8));
+        SLAMEM_TRY(sl.d_planes.reserve(want + 1));
+        SLAMEM_TRY(sl.d_other.reserve(want + 1));
         sl.cap_units = want;
     }
-    if (!sl.d_ucnt) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ucnt), ((uint64_t)sl.cap_q + 2 + scan_u32_tmp_words((uint64_t)sl.cap_q + 1)) * 4));
+    SLAMEM_TRY(sl.d_ucnt.reserve((uint64_t)sl.cap_q + 2 + scan_u32_tmp_words((uint64_t)sl.cap_q + 1)));  // (goes with the inputs' room)
     hipStream_t st = s->st[0];
-    SLAMEM_HIP(hipMemcpyAsync(sl.d_off, sl.offs, ((uint64_t)sl.nq + 1) * 8, hipMemcpyHostToDevice, st));
-    // the planes on the copy streams side by side (as the letters of an ordinary batch)
-    const uint64_t pbytes = units * 16;
-    const int ways = (s->upload_split > 1 && pbytes >= (8u << 20)) ? s->upload_split : 1;
-    uint64_t at = 0;
-    for (int wy = 0; wy < ways; wy++) {
-        const uint64_t end = wy + 1 == ways ? pbytes : ((pbytes * (uint64_t)(wy + 1) / (uint64_t)ways) & ~(uint64_t)4095);
-        hipStream_t cs = wy == 0 ? st : s->st_upx[wy - 1];
-        if (end > at) SLAMEM_HIP(hipMemcpyAsync(static_cast<char*>(sl.d_planes) + at, static_cast<const char*>(sl.planes) + at, end - at, hipMemcpyHostToDevice, cs));
-        at = end;
-    }
-    if (sl.other && units) SLAMEM_HIP(hipMemcpyAsync(sl.d_other, sl.other, units * 8, hipMemcpyHostToDevice, st));
+    SLAMEM_HIP(hipMemcpyAsync(sl.d_off.get(), sl.offs, ((uint64_t)sl.nq + 1) * 8, hipMemcpyHostToDevice, st));
+    int ways = 1;  // the planes on the copy streams side by side (as the letters of an ordinary batch)
+    SLAMEM_TRY(copy_split(s, sl.d_planes.get(), sl.planes, units * 16, &ways));
+    if (sl.other && units) SLAMEM_HIP(hipMemcpyAsync(sl.d_other.get(), sl.other, units * 8, hipMemcpyHostToDevice, st));
     if (sl.nq) {
-        hipLaunchKernelGGL(k_unit_counts, dim3((unsigned)(((uint64_t)sl.nq + 1 + 255) / 256)), dim3(256), 0, st, (const uint64_t*)sl.d_off, sl.nq, sl.d_ucnt);
-        SLAMEM_HIP(exclusive_scan_u32(sl.d_ucnt, sl.d_ucnt, (uint64_t)sl.nq + 1, sl.d_ucnt + sl.cap_q + 2, st));
+        hipLaunchKernelGGL(k_unit_counts, dim3((unsigned)(((uint64_t)sl.nq + 1 + 255) / 256)), dim3(256), 0, st, (const uint64_t*)sl.d_off.get(), sl.nq,
+                           sl.d_ucnt.get());
+        SLAMEM_HIP(exclusive_scan_u32(sl.d_ucnt.get(), sl.d_ucnt.get(), (uint64_t)sl.nq + 1, sl.d_ucnt.get() + sl.cap_q + 2, st));
     }
-    {   // while the copy engines work: is any record longer than a slice?  (as in stage_upload)
-        uint64_t longest = 0;
-        for (uint32_t i = 0; i < sl.nq; i++) {
-            const uint64_t len = sl.offs[i + 1] - sl.offs[i];
-            longest = len > longest ? len : longest;
-        }
-        sl.all_short = longest <= kSearchSliceLen;
-    }
+    sl.all_short = all_records_short(sl);
     for (int wy = 1; wy < ways; wy++) SLAMEM_HIP(hipStreamSynchronize(s->st_upx[wy - 1]));  // (the letters are written on st: every piece must be there)
     if (sl.nq) {
-        hipLaunchKernelGGL(k_unpack_reads, dim3((sl.nq + kUnpackRecords - 1) / kUnpackRecords), dim3(256), 0, st, (const uint4*)sl.d_planes,
-                           sl.other ? (const uint64_t*)sl.d_other : (const uint64_t*)nullptr, (const uint32_t*)sl.d_ucnt, (const uint64_t*)sl.d_off, sl.nq, dst);
+        hipLaunchKernelGGL(k_unpack_reads, dim3((sl.nq + kUnpackRecords - 1) / kUnpackRecords), dim3(256), 0, st, (const uint4*)sl.d_planes.get(),
+                           sl.other ? (const uint64_t*)sl.d_other.get() : (const uint64_t*)nullptr, (const uint32_t*)sl.d_ucnt.get(),
+                           (const uint64_t*)sl.d_off.get(), sl.nq, dst);
         SLAMEM_HIP(hipGetLastError());
     }
     SLAMEM_HIP(hipStreamSynchronize(st));
@@ -326,68 +354,36 @@ int stage_upload_packed(slamem_stream* s, Slot& sl, char* dst) {
 
 int stage_upload(slamem_stream* s, Slot& sl) {
     const uint64_t base = sl.offs[0], qbytes = sl.offs[sl.nq] - base;
-    if (!sl.d_q || qbytes > sl.cap_chars || sl.nq > sl.cap_q) {
-        // first batch of this slot, or a batch larger than the reservation (max_batch_* of slamem_stream_create are a hint)
+    if (!sl.d_q.get() || qbytes > sl.cap_chars || sl.nq > sl.cap_q) {
+        // first batch of this slot, or a batch larger than the reservation (max_batch_* of slamem_stream_create are a hint).
+        // INPUTS REGROWN => OUTPUTS DROPPED: what is sized by the inputs' room goes with them, all of it before anything new is
+        // asked for, and the prepare stage (which finds no d_ws) sizes the outputs again
         const uint64_t nchars = qbytes > s->max_chars ? qbytes : s->max_chars;
         const uint32_t nrec = sl.nq > s->max_q ? sl.nq : s->max_q;
         const uint64_t nb = (uint64_t)nrec * (s->both ? 2 : 1);
-        if (sl.d_q) (void)hipFree(sl.d_q);
-        if (sl.d_off) (void)hipFree(sl.d_off);
-        if (sl.d_boff) (void)hipFree(sl.d_boff);
-        if (sl.d_mems) (void)hipFree(sl.d_mems);
-        if (sl.d_ws) (void)hipFree(sl.d_ws);
-        if (sl.d_mm) (void)hipFree(sl.d_mm);
-        if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
-        if (sl.d_reads) (void)hipFree(sl.d_reads);
-        sl.d_ucnt = nullptr;
-        sl.d_mm = nullptr;
-        sl.d_reads = nullptr;
-        sl.d_q = nullptr; sl.d_off = nullptr; sl.d_boff = nullptr; sl.d_mems = nullptr; sl.d_ws = nullptr;  // (the prepare stage sizes its own)
-        sl.cap_chars = 0; sl.cap_q = 0;  // until all three are there: a failed allocation must not leave stale room behind
-        SLAMEM_HIP(hipMalloc(&sl.d_q, nchars + 2 * kFront + 32));
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_off), ((uint64_t)nrec + 1) * 8));
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_boff), (nb + 1) * 8));
-        if (is_map(s)) SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_reads), ((uint64_t)nrec + 1) * sizeof(slamem_map)));
+        drop_outputs(sl);
+        sl.d_q.release(); sl.d_off.release(); sl.d_boff.release(); sl.d_reads.release(); sl.d_ucnt.release();
+        sl.cap_chars = 0; sl.cap_q = 0;  // until all are there: a failed allocation must not leave stale room behind
+        SLAMEM_TRY(sl.d_q.reserve(nchars + 2 * kFront + 32));
+        SLAMEM_TRY(sl.d_off.reserve((uint64_t)nrec + 1));
+        SLAMEM_TRY(sl.d_boff.reserve(nb + 1));
+        if (is_map(s)) SLAMEM_TRY(sl.d_reads.reserve((uint64_t)nrec + 1));
         sl.cap_chars = nchars;
         sl.cap_q = nrec;
     }
-    char* dst = static_cast<char*>(sl.d_q) + kFront + (base & 15u);
+    char* dst = sl.d_q.get() + kFront + (base & 15u);
     if (sl.planes) return stage_upload_packed(s, sl, dst);
-    const char* src = sl.chars + base;
-    // Beside K8 -- which keeps the memory system at its random-request ceiling -- ONE copy engine moves 42 GB/s instead of the
-    // link's 57 (measured: 3.56 ms per 158 MB instead of 2.76, which made the upload the pipeline's period); the pieces of a
-    // batch go up on `upload_split` copy streams side by side
-    const int ways = (s->upload_split > 1 && qbytes >= (8u << 20)) ? s->upload_split : 1;
-    uint64_t at = 0;
-    for (int wy = 0; wy < ways; wy++) {
-        const uint64_t end = wy + 1 == ways ? qbytes : ((qbytes * (uint64_t)(wy + 1) / (uint64_t)ways) & ~(uint64_t)4095);
-        hipStream_t cs = wy == 0 ? s->st[0] : s->st_upx[wy - 1];
-        if (end > at) SLAMEM_HIP(hipMemcpyAsync(dst + at, src + at, end - at, hipMemcpyHostToDevice, cs));
-        at = end;
-    }
-    SLAMEM_HIP(hipMemcpyAsync(sl.d_off, sl.offs, ((uint64_t)sl.nq + 1) * 8, hipMemcpyHostToDevice, s->st[0]));
+    int ways = 1;
+    SLAMEM_TRY(copy_split(s, dst, sl.chars + base, qbytes, &ways));
+    SLAMEM_HIP(hipMemcpyAsync(sl.d_off.get(), sl.offs, ((uint64_t)sl.nq + 1) * 8, hipMemcpyHostToDevice, s->st[0]));
     if (sl.lowq && qbytes) {
         // the mask's words that hold a bit of the batch: [base / 64, (base + qbytes + 63) / 64).  Nothing is shifted: the add gets
         // d_lowq - base / 64, so that bit offs[r] + i is letter i of read r there as it is in the caller's array
         const uint64_t w0 = base >> 6, nw = ((base + qbytes + 63u) >> 6) - w0;
-        if (!sl.d_lowq || nw > sl.cap_lowq) {
-            if (sl.d_lowq) (void)hipFree(sl.d_lowq);
-            sl.d_lowq = nullptr; sl.cap_lowq = 0;
-            const uint64_t want = nw > (sl.cap_chars >> 6) + 2 ? nw : (sl.cap_chars >> 6) + 2;
-            SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_lowq), want * 8));
-            sl.cap_lowq = want;
-        }
-        SLAMEM_HIP(hipMemcpyAsync(sl.d_lowq, sl.lowq + w0, nw * 8, hipMemcpyHostToDevice, s->st[0]));
+        if (sl.d_lowq.count() < nw) SLAMEM_TRY(sl.d_lowq.reserve(nw > (sl.cap_chars >> 6) + 2 ? nw : (sl.cap_chars >> 6) + 2));
+        SLAMEM_HIP(hipMemcpyAsync(sl.d_lowq.get(), sl.lowq + w0, nw * 8, hipMemcpyHostToDevice, s->st[0]));
     }
-    {   // while the copy engines work: is any record longer than a slice?  (if not, the prepare stage knows the number of work
-        // items without asking the device -- its one host round trip per batch goes away)
-        uint64_t longest = 0;
-        for (uint32_t i = 0; i < sl.nq; i++) {
-            const uint64_t len = sl.offs[i + 1] - sl.offs[i];
-            longest = len > longest ? len : longest;
-        }
-        sl.all_short = longest <= kSearchSliceLen;
-    }
+    sl.all_short = all_records_short(sl);
     SLAMEM_HIP(hipStreamSynchronize(s->st[0]));
     for (int wy = 1; wy < ways; wy++) SLAMEM_HIP(hipStreamSynchronize(s->st_upx[wy - 1]));
     return SLAMEM_OK;
@@ -396,23 +392,22 @@ int stage_upload(slamem_stream* s, Slot& sl) {
 // stage 1: work-item tables (one small host round trip on this stage's stream), then K8a, the work list and K7q, asynchronous
 int job_setup(slamem_stream* s, Slot& sl) {
     const uint64_t qbytes = sl.offs[sl.nq] - sl.offs[0];
-    if (!sl.d_ws) {
+    if (!sl.d_ws.get()) {
         // first guess of the room for MEMs: what the densest batch so far would need, and never less than a MEM per 32
         // characters; grown when a batch needs more (SLAMEM_ERR_CAPACITY tells how much)
         const uint64_t nb = (uint64_t)sl.cap_q * (s->both ? 2 : 1);
         uint64_t guess = sl.cap_chars / 32 + nb + 1024;
         const uint64_t seen = (uint64_t)(1.25 * s->mems_per_char * (double)sl.cap_chars) + 1024;
-        int rc = grow_outputs(s, sl, seen > guess ? seen : guess);
-        if (rc != SLAMEM_OK) return rc;
+        SLAMEM_TRY(grow_outputs(s, sl, seen > guess ? seen : guess));
     }
     if (!sl.job && !(sl.job = search_job_new())) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     if (!sl.ev_prep) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_prep, hipEventDisableTiming));
     if (!sl.ev_done) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
     if (!sl.ev_k8) SLAMEM_HIP(hipEventCreateWithFlags(&sl.ev_k8, hipEventDisableTiming));
-    if (!sl.h_scal) SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_scal), 16 * sizeof(unsigned long long), hipHostMallocDefault));
+    SLAMEM_TRY(sl.h_scal.reserve(16));
     const FilterParams p = slot_params(s, sl);
-    return search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off, sl.nq, qbytes, sl.min_len, s->both, job_type(s), sl.d_mems, sl.cap,
-                           sl.d_boff, sl.d_ws, sl.ws_bytes, sl.h_scal, &p);
+    return search_job_init(sl.job, s->idx, device_queries(sl), sl.d_off.get(), sl.nq, qbytes, sl.min_len, s->both, job_type(s), sl.d_mems.get(),
+                           sl.cap, sl.d_boff.get(), sl.d_ws.get(), sl.d_ws.count(), sl.h_scal.get(), &p);
 }
 int stage_prepare(slamem_stream* s, Slot& sl) {
     int rc = job_setup(s, sl);
@@ -494,55 +489,34 @@ int stage_search(slamem_stream* s, Slot& sl, bool failed, bool* issued_only) {
 // SLAMEM_ERR_CAPACITY tells.
 int stage_md(slamem_stream* s, Slot& sl, hipStream_t st) {
     const uint64_t ns = sl.total;
-    if (sl.md_segs_cap < ns + 1 || !sl.d_md_off) {
-        if (sl.d_md_off) (void)hipFree(sl.d_md_off);
-        if (sl.d_seg_eq) (void)hipFree(sl.d_seg_eq);
-        if (sl.d_md_ws) (void)hipFree(sl.d_md_ws);
-        if (sl.h_md_off) (void)hipHostFree(sl.h_md_off);
-        if (sl.h_seg_eq) (void)hipHostFree(sl.h_seg_eq);
-        sl.d_md_off = nullptr; sl.d_seg_eq = nullptr; sl.d_md_ws = nullptr; sl.h_md_off = nullptr; sl.h_seg_eq = nullptr;
-        sl.md_segs_cap = (sl.cap > ns ? sl.cap : ns) + 1;
-        int rc = slamem_maps_md_workspace_bytes(sl.md_segs_cap, sl.cap_q, &sl.md_ws_bytes);
-        if (rc != SLAMEM_OK) return rc;
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_md_off), (sl.md_segs_cap + 1) * 8));
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_seg_eq), (sl.md_segs_cap + 1) * 4));
-        SLAMEM_HIP(hipMalloc(&sl.d_md_ws, sl.md_ws_bytes));
-        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_md_off), (sl.md_segs_cap + 1) * 8, hipHostMallocDefault));
-        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_seg_eq), (sl.md_segs_cap + 1) * 4, hipHostMallocDefault));
+    {   // a word per segment: as many as the slot has room for segments (ns <= cap), and one more
+        const uint64_t segs = (sl.cap > ns ? sl.cap : ns) + 2;
+        uint64_t ws_bytes = 0;
+        SLAMEM_TRY(slamem_maps_md_workspace_bytes(segs - 1, sl.cap_q, &ws_bytes));
+        SLAMEM_TRY(sl.d_md_off.reserve(segs));
+        SLAMEM_TRY(sl.d_seg_eq.reserve(segs));
+        SLAMEM_TRY(sl.d_md_ws.reserve(ws_bytes));
+        SLAMEM_TRY(sl.h_md_off.reserve(segs));
+        SLAMEM_TRY(sl.h_seg_eq.reserve(segs));
     }
-    if (sl.md_q_cap < (uint64_t)sl.nq + 1 || !sl.d_primary) {
-        if (sl.d_primary) (void)hipFree(sl.d_primary);
-        if (sl.h_primary) (void)hipHostFree(sl.h_primary);
-        sl.d_primary = nullptr; sl.h_primary = nullptr;
-        sl.md_q_cap = (uint64_t)(sl.cap_q > sl.nq ? sl.cap_q : sl.nq) + 1;
-        SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_primary), sl.md_q_cap * 4));
-        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_primary), sl.md_q_cap * 4, hipHostMallocDefault));
-    }
+    SLAMEM_TRY(sl.d_primary.reserve((uint64_t)sl.cap_q + 1));  // (nq <= cap_q)
+    SLAMEM_TRY(sl.h_primary.reserve((uint64_t)sl.cap_q + 1));
     uint64_t want = sl.ops_total + ns + 1024;
     int rc = SLAMEM_OK;
     for (int attempt = 0; attempt < 2; attempt++) {
-        if (sl.md_cap < want || !sl.d_md) {
-            if (sl.d_md) (void)hipFree(sl.d_md);
-            sl.d_md = nullptr;
-            sl.md_cap = want;
-            SLAMEM_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_md), (sl.md_cap + 1) * 4));
-        }
-        rc = slamem_maps_md_device(s->idx, sl.d_segs, ns, sl.d_boff, sl.nq, sl.d_ops, sl.d_ooff, sl.d_md, sl.md_cap, sl.d_md_off,
-                                   sl.d_seg_eq, sl.d_primary, sl.d_md_ws, sl.md_ws_bytes, st, &sl.md_total);
+        if (sl.md_cap < want) sl.md_cap = want;
+        SLAMEM_TRY(sl.d_md.reserve(sl.md_cap + 1));
+        rc = slamem_maps_md_device(s->idx, sl.d_segs.get(), ns, sl.d_boff.get(), sl.nq, sl.d_ops.get(), sl.d_ooff.get(), sl.d_md.get(), sl.md_cap,
+                                   sl.d_md_off.get(), sl.d_seg_eq.get(), sl.d_primary.get(), sl.d_md_ws.get(), sl.d_md_ws.count(), st, &sl.md_total);
         if (rc != SLAMEM_ERR_CAPACITY) break;
         want = sl.md_total + sl.md_total / 8 + 1024;
     }
     if (rc != SLAMEM_OK) return rc;
-    if (sl.h_md_cap < sl.md_cap || !sl.h_md) {
-        if (sl.h_md) (void)hipHostFree(sl.h_md);
-        sl.h_md = nullptr;
-        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_md), (sl.md_cap + 1) * 4, hipHostMallocDefault));
-        sl.h_md_cap = sl.md_cap;
-    }
-    if (sl.md_total) SLAMEM_HIP(hipMemcpyAsync(sl.h_md, sl.d_md, sl.md_total * 4, hipMemcpyDeviceToHost, st));
-    SLAMEM_HIP(hipMemcpyAsync(sl.h_md_off, sl.d_md_off, (ns + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (ns) SLAMEM_HIP(hipMemcpyAsync(sl.h_seg_eq, sl.d_seg_eq, ns * 4, hipMemcpyDeviceToHost, st));
-    if (sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_primary, sl.d_primary, (uint64_t)sl.nq * 4, hipMemcpyDeviceToHost, st));
+    SLAMEM_TRY(sl.h_md.reserve(sl.md_cap + 1));
+    if (sl.md_total) SLAMEM_HIP(hipMemcpyAsync(sl.h_md.get(), sl.d_md.get(), sl.md_total * 4, hipMemcpyDeviceToHost, st));
+    SLAMEM_HIP(hipMemcpyAsync(sl.h_md_off.get(), sl.d_md_off.get(), (ns + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (ns) SLAMEM_HIP(hipMemcpyAsync(sl.h_seg_eq.get(), sl.d_seg_eq.get(), ns * 4, hipMemcpyDeviceToHost, st));
+    if (sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_primary.get(), sl.d_primary.get(), (uint64_t)sl.nq * 4, hipMemcpyDeviceToHost, st));
     return SLAMEM_OK;
 }
 
@@ -580,73 +554,42 @@ int stage_download(slamem_stream* s, Slot& sl) {
         std::lock_guard<std::mutex> lk(s->mu);
         if (d > s->mems_per_char) s->mems_per_char = d;
     }
-    const uint64_t nb = (uint64_t)sl.nq * (s->both ? 2 : 1);
-    if (!sl.h_boff || sl.h_boff_cap < nb + 1) {
-        if (sl.h_boff) (void)hipHostFree(sl.h_boff);
-        sl.h_boff = nullptr;
-        const uint64_t want = (uint64_t)sl.cap_q * (s->both ? 2 : 1) + 1;
-        sl.h_boff_cap = want > nb + 1 ? want : nb + 1;
-        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_boff), sl.h_boff_cap * 8, hipHostMallocDefault));
-    }
+    // Pinned host memory for what goes back, each array as large as the device buffer it is copied from (so it follows that
+    // buffer's growth, and a batch no larger than the ones before allocates nothing)
+    const uint64_t strands = s->both ? 2 : 1, nb = (uint64_t)sl.nq * strands;
+    SLAMEM_TRY(sl.h_boff.reserve((uint64_t)sl.cap_q * strands + 1));
     if (s->match_type == 8) {
         // -pile: the batch's result stands (its totals fitted), so it is added to the accumulator -- here and not behind K9,
         // where nobody knows yet whether the batch will be run again with more room.  Segments and operations stay on the device.
         // (a masked batch: the uploaded words start at the caller's word offs[0] / 64)
-        const uint64_t* lowq = (sl.lowq && sl.d_lowq && sl.offs[sl.nq] > sl.offs[0]) ? sl.d_lowq - (sl.offs[0] >> 6) : nullptr;
-        rc = pileup_add_masked(s->pile, device_queries(sl), sl.d_off, sl.nq, sl.d_segs, sl.d_boff, sl.d_ops, sl.d_ooff, sl.d_reads,
-                               s->min_mapq, lowq, st);
+        const uint64_t* lowq = (sl.lowq && sl.d_lowq.get() && sl.offs[sl.nq] > sl.offs[0]) ? sl.d_lowq.get() - (sl.offs[0] >> 6) : nullptr;
+        rc = pileup_add_masked(s->pile, device_queries(sl), sl.d_off.get(), sl.nq, sl.d_segs.get(), sl.d_boff.get(), sl.d_ops.get(),
+                               sl.d_ooff.get(), sl.d_reads.get(), s->min_mapq, lowq, st);
         if (rc != SLAMEM_OK) return rc;
-    } else if (sl.h_cap < sl.cap || !sl.h_mems) {
-        if (sl.h_mems) (void)hipHostFree(sl.h_mems);
-        sl.h_mems = nullptr;
-        SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_mems), sl.cap * sizeof(slamem_mem) + 16, hipHostMallocDefault));
-        sl.h_cap = sl.cap;
+    } else {
+        SLAMEM_TRY(sl.h_mems.reserve(sl.cap, 16));
     }
     if (sl.total && !is_aln(s))
-        SLAMEM_HIP(hipMemcpyAsync(sl.h_mems, sl.d_mems, sl.total * sizeof(slamem_mem), hipMemcpyDeviceToHost, st));
+        SLAMEM_HIP(hipMemcpyAsync(sl.h_mems.get(), sl.d_mems.get(), sl.total * sizeof(slamem_mem), hipMemcpyDeviceToHost, st));
     if (is_aln(s) && s->match_type != 8) {  // (sl.total: the segments)
-        if (sl.h_segs_cap < sl.cap || !sl.h_segs) {
-            if (sl.h_segs) (void)hipHostFree(sl.h_segs);
-            if (sl.h_ooff) (void)hipHostFree(sl.h_ooff);
-            sl.h_segs = nullptr; sl.h_ooff = nullptr;
-            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_segs), (sl.cap + 1) * sizeof(slamem_aln), hipHostMallocDefault));
-            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_ooff), (sl.cap + 2) * 8, hipHostMallocDefault));
-            sl.h_segs_cap = sl.cap;
-        }
-        if (sl.h_ops_cap < sl.ops_cap || !sl.h_ops) {
-            if (sl.h_ops) (void)hipHostFree(sl.h_ops);
-            sl.h_ops = nullptr;
-            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_ops), (sl.ops_cap + 1) * 4, hipHostMallocDefault));
-            sl.h_ops_cap = sl.ops_cap;
-        }
-        if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_segs, sl.d_segs, sl.total * sizeof(slamem_aln), hipMemcpyDeviceToHost, st));
-        if (sl.ops_total) SLAMEM_HIP(hipMemcpyAsync(sl.h_ops, sl.d_ops, sl.ops_total * 4, hipMemcpyDeviceToHost, st));
-        SLAMEM_HIP(hipMemcpyAsync(sl.h_ooff, sl.d_ooff, (sl.total + 1) * 8, hipMemcpyDeviceToHost, st));
+        SLAMEM_TRY(sl.h_segs.reserve(sl.cap + 1));
+        SLAMEM_TRY(sl.h_ooff.reserve(sl.cap + 2));
+        SLAMEM_TRY(sl.h_ops.reserve(sl.ops_cap + 1));
+        if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_segs.get(), sl.d_segs.get(), sl.total * sizeof(slamem_aln), hipMemcpyDeviceToHost, st));
+        if (sl.ops_total) SLAMEM_HIP(hipMemcpyAsync(sl.h_ops.get(), sl.d_ops.get(), sl.ops_total * 4, hipMemcpyDeviceToHost, st));
+        SLAMEM_HIP(hipMemcpyAsync(sl.h_ooff.get(), sl.d_ooff.get(), (sl.total + 1) * 8, hipMemcpyDeviceToHost, st));
     }
-    if (s->md) {
-        const int mrc = stage_md(s, sl, st);
-        if (mrc != SLAMEM_OK) return mrc;
-    }
+    if (s->md) SLAMEM_TRY(stage_md(s, sl, st));
     if (s->match_type == 5) {
-        if (sl.h_mm_cap < sl.cap || !sl.h_mm) {
-            if (sl.h_mm) (void)hipHostFree(sl.h_mm);
-            sl.h_mm = nullptr;
-            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_mm), sl.cap * 4 + 16, hipHostMallocDefault));
-            sl.h_mm_cap = sl.cap;
-        }
-        if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_mm, sl.d_mm, sl.total * 4, hipMemcpyDeviceToHost, st));
+        SLAMEM_TRY(sl.h_mm.reserve(sl.cap + 4));
+        if (sl.total) SLAMEM_HIP(hipMemcpyAsync(sl.h_mm.get(), sl.d_mm.get(), sl.total * 4, hipMemcpyDeviceToHost, st));
     }
     if (is_map(s)) {  // (the offsets are per read)
-        if (sl.h_reads_cap < sl.cap_q || !sl.h_reads) {
-            if (sl.h_reads) (void)hipHostFree(sl.h_reads);
-            sl.h_reads = nullptr;
-            SLAMEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_reads), ((uint64_t)sl.cap_q + 1) * sizeof(slamem_map), hipHostMallocDefault));
-            sl.h_reads_cap = sl.cap_q;
-        }
-        if (sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_reads, sl.d_reads, (uint64_t)sl.nq * sizeof(slamem_map), hipMemcpyDeviceToHost, st));
-        SLAMEM_HIP(hipMemcpyAsync(sl.h_boff, sl.d_boff, ((uint64_t)sl.nq + 1) * 8, hipMemcpyDeviceToHost, st));
+        SLAMEM_TRY(sl.h_reads.reserve((uint64_t)sl.cap_q + 1));
+        if (sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_reads.get(), sl.d_reads.get(), (uint64_t)sl.nq * sizeof(slamem_map), hipMemcpyDeviceToHost, st));
+        SLAMEM_HIP(hipMemcpyAsync(sl.h_boff.get(), sl.d_boff.get(), ((uint64_t)sl.nq + 1) * 8, hipMemcpyDeviceToHost, st));
     } else
-    SLAMEM_HIP(hipMemcpyAsync(sl.h_boff, sl.d_boff, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
+    SLAMEM_HIP(hipMemcpyAsync(sl.h_boff.get(), sl.d_boff.get(), (nb + 1) * 8, hipMemcpyDeviceToHost, st));
     SLAMEM_HIP(hipStreamSynchronize(st));
     return SLAMEM_OK;
 }
@@ -657,7 +600,7 @@ void worker(slamem_stream* s, int t) {
     static const int kDone[kThreads] = {UPLOADED, PREPARED, LAUNCHED, DONE};
     static const char* const kName[kThreads] = {"upload", "prepare", "search", "download"};
     const int want = kWant[t], done = kDone[t];
-    (void)hipSetDevice(s->idx->device);
+    (void)hipSetDevice(s->device);
     for (uint64_t seq = 0;; seq++) {
         Slot& sl = s->slot[seq % (uint64_t)s->nslots];
         {
@@ -692,46 +635,86 @@ void worker(slamem_stream* s, int t) {
     }
 }
 
-void free_slot(Slot& sl) {
-    if (sl.d_q) (void)hipFree(sl.d_q);
-    if (sl.d_off) (void)hipFree(sl.d_off);
-    if (sl.d_boff) (void)hipFree(sl.d_boff);
-    if (sl.d_mems) (void)hipFree(sl.d_mems);
-    if (sl.d_ws) (void)hipFree(sl.d_ws);
-    if (sl.d_mm) (void)hipFree(sl.d_mm);
-    if (sl.h_mm) (void)hipHostFree(sl.h_mm);
-    if (sl.d_segs) (void)hipFree(sl.d_segs);
-    if (sl.d_ops) (void)hipFree(sl.d_ops);
-    if (sl.d_ooff) (void)hipFree(sl.d_ooff);
-    if (sl.h_segs) (void)hipHostFree(sl.h_segs);
-    if (sl.h_ops) (void)hipHostFree(sl.h_ops);
-    if (sl.h_ooff) (void)hipHostFree(sl.h_ooff);
-    sl.d_segs = nullptr; sl.d_ops = nullptr; sl.d_ooff = nullptr; sl.h_segs = nullptr; sl.h_ops = nullptr; sl.h_ooff = nullptr;
-    if (sl.d_reads) (void)hipFree(sl.d_reads);
-    if (sl.h_reads) (void)hipHostFree(sl.h_reads);
-    sl.d_reads = nullptr; sl.h_reads = nullptr;
-    if (sl.d_md) (void)hipFree(sl.d_md);
-    if (sl.d_md_off) (void)hipFree(sl.d_md_off);
-    if (sl.d_seg_eq) (void)hipFree(sl.d_seg_eq);
-    if (sl.d_primary) (void)hipFree(sl.d_primary);
-    if (sl.d_md_ws) (void)hipFree(sl.d_md_ws);
-    if (sl.h_md) (void)hipHostFree(sl.h_md);
-    if (sl.h_md_off) (void)hipHostFree(sl.h_md_off);
-    if (sl.h_seg_eq) (void)hipHostFree(sl.h_seg_eq);
-    if (sl.h_primary) (void)hipHostFree(sl.h_primary);
-    sl.d_md = nullptr; sl.d_md_off = nullptr; sl.d_seg_eq = nullptr; sl.d_primary = nullptr; sl.d_md_ws = nullptr;
-    sl.h_md = nullptr; sl.h_md_off = nullptr; sl.h_seg_eq = nullptr; sl.h_primary = nullptr;
-    if (sl.d_planes) (void)hipFree(sl.d_planes);
-    if (sl.d_other) (void)hipFree(sl.d_other);
-    if (sl.d_ucnt) (void)hipFree(sl.d_ucnt);
-    if (sl.d_lowq) (void)hipFree(sl.d_lowq);
-    if (sl.h_boff) (void)hipHostFree(sl.h_boff);
-    if (sl.h_mems) (void)hipHostFree(sl.h_mems);
-    if (sl.h_scal) (void)hipHostFree(sl.h_scal);
-    if (sl.ev_prep) (void)hipEventDestroy(sl.ev_prep);
-    if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
-    if (sl.ev_k8) (void)hipEventDestroy(sl.ev_k8);
-    if (sl.job) search_job_delete(sl.job);
+// Steps 4 to 6 of a stream's end, for slamem_stream_destroy and for a slamem_stream_create that failed half way: the device is
+// set, no thread runs.  Every copy and kernel of the stream's own HIP streams is through before buffers and streams go (the
+// stages wait for their work batch by batch; this is for whatever a failed batch left behind, and for tools that watch the
+// copies: a profiler waited 30 s at exit for completion callbacks of copies whose streams were destroyed under it,
+// profiles/README.md); then the slots with their buffers, events and jobs; then the streams.
+void teardown(slamem_stream* s) {
+    hipStream_t all[kThreads + 3 + 2];
+    int n = 0;
+    for (int k = 0; k < kThreads; k++) all[n++] = s->st[k];
+    for (int k = 0; k < 3; k++) all[n++] = s->st_upx[k];
+    all[n++] = s->st_search2;
+    all[n++] = s->st_place;
+    for (int k = 0; k < n; k++)
+        if (all[k]) (void)hipStreamSynchronize(all[k]);
+    s->slot.reset();
+    for (int k = 0; k < n; k++)
+        if (all[k]) (void)hipStreamDestroy(all[k]);
+}
+
+// what every setter ends its checks with (s->mu held): the parameters of a stream are those of all its batches
+bool has_batches(const slamem_stream* s, const char* who, const char* advice) {
+    if (s->submitted == 0) return false;
+    set_error("%s: the stream has batches already (%s before the first submit)", who, advice);
+    return true;
+}
+
+// the slot of the batch slamem_stream_next returned last, for a getter (s->mu held); nullptr, with the message, if there is none
+// or it failed: it would have had `things` to show
+Slot* last_returned(slamem_stream* s, const char* who, const char* things) {
+    if (s->returned == 0) { set_error("%s: no batch has been returned yet", who); return nullptr; }
+    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
+    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
+        set_error("%s: the batch slamem_stream_next returned last has no %s to show", who, things);
+        return nullptr;
+    }
+    return &sl;
+}
+
+// a batch as one of slamem_stream_submit* takes it (which has checked its own arguments): letters or planes, never both
+struct Batch {
+    const char* chars = nullptr;
+    const void* planes = nullptr;
+    const uint64_t* other = nullptr;
+    uint64_t units = 0;
+    const uint64_t* lowq = nullptr;  // (nullptr: the batch is an unmasked one)
+    const uint64_t* offs = nullptr;
+    uint32_t nq = 0, min_len = 0;
+};
+
+int enqueue(slamem_stream* s, const char* who, const Batch& b) {
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type == 8 && !s->pile) {
+        set_error("%s: a stream of match type 8 (-pile) needs slamem_stream_set_pileup first", who);
+        return SLAMEM_ERR_ARG;
+    }
+    Slot& sl = s->slot[s->submitted % (uint64_t)s->nslots];
+    if (sl.state != FREE) {
+        // a slot is released by the slamem_stream_next call AFTER the one that handed its result out: at most slots - 1
+        // batches may be in flight beside the result the caller is working on.  Never blocks (a caller that both submits
+        // and collects on one thread would wait for itself).
+        set_error("%s: all %d slots are in use (collect a result with slamem_stream_next first)", who, s->nslots);
+        return SLAMEM_ERR_ARG;
+    }
+    sl.seq = s->submitted;
+    sl.chars = b.chars;
+    sl.planes = b.planes;
+    sl.other = b.other;
+    sl.units_hint = b.units;
+    sl.lowq = b.lowq;
+    sl.offs = b.offs;
+    sl.nq = b.nq;
+    sl.min_len = b.min_len;
+    sl.rc = SLAMEM_OK;
+    sl.err[0] = 0;
+    sl.total = 0;
+    sl.state = QUEUED;
+    s->submitted++;
+    lk.unlock();
+    s->cv.notify_all();
+    return SLAMEM_OK;
 }
 
 }  // namespace
@@ -817,22 +800,7 @@ int slamem_stream_destroy(slamem_stream* s) {
     for (int k = 0; k < s->nthreads; k++)
         if (s->th[k].joinable()) s->th[k].join();
     (void)hipSetDevice(s->device);
-    // every copy and kernel of the stream's own HIP streams is through before buffers and streams go (the stages wait for their
-    // work batch by batch; this is for whatever a failed batch left behind, and for tools that watch the copies: a profiler waited
-    // 30 s at exit for completion callbacks of copies whose streams were destroyed under it, profiles/README.md)
-    for (int k = 0; k < kThreads; k++)
-        if (s->st[k]) (void)hipStreamSynchronize(s->st[k]);
-    for (int k = 0; k < 3; k++)
-        if (s->st_upx[k]) (void)hipStreamSynchronize(s->st_upx[k]);
-    if (s->st_search2) (void)hipStreamSynchronize(s->st_search2);
-    if (s->st_place) (void)hipStreamSynchronize(s->st_place);
-    for (int k = 0; k < s->nslots; k++) free_slot(s->slot[k]);
-    for (int k = 0; k < kThreads; k++)
-        if (s->st[k]) (void)hipStreamDestroy(s->st[k]);
-    for (int k = 0; k < 3; k++)
-        if (s->st_upx[k]) (void)hipStreamDestroy(s->st_upx[k]);
-    if (s->st_search2) (void)hipStreamDestroy(s->st_search2);
-    if (s->st_place) (void)hipStreamDestroy(s->st_place);
+    teardown(s);
     delete s;
     return SLAMEM_OK;
 }
@@ -846,7 +814,8 @@ int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_
     *out = nullptr;
     SLAMEM_HIP(hipSetDevice(idx->device));
     slamem_stream* s = new (std::nothrow) slamem_stream();
-    if (!s) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
+    if (s) s->slot.reset(new (std::nothrow) Slot[slots]);
+    if (!s || !s->slot) { delete s; set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     s->idx = idx;
     s->device = idx->device;
     s->trace = getenv("SLAMEM_STREAM_TRACE") != nullptr;
@@ -901,11 +870,7 @@ int slamem_stream_create(const slamem_index* idx, int slots, uint64_t max_batch_
         }
     }
     if (rc != SLAMEM_OK) {
-        for (int k = 0; k < 3; k++)
-            if (s->st_upx[k]) (void)hipStreamDestroy(s->st_upx[k]);
-        for (int k = 0; k < slots; k++) free_slot(s->slot[k]);
-        for (int k = 0; k < kThreads; k++)
-            if (s->st[k]) (void)hipStreamDestroy(s->st[k]);
+        teardown(s);  // (every HIP stream made so far, st_place and st_search2 among them)
         delete s;
         return rc;
     }
@@ -921,10 +886,7 @@ int slamem_stream_set_max_occ(slamem_stream* s, uint32_t max_occ) {
         set_error("slamem_stream_set_max_occ: an occurrence cap needs match type 3 (-smem)");
         return SLAMEM_ERR_ARG;
     }
-    if (s->submitted != 0) {
-        set_error("slamem_stream_set_max_occ: the stream has batches already (set the cap before the first submit)");
-        return SLAMEM_ERR_ARG;
-    }
+    if (has_batches(s, "slamem_stream_set_max_occ", "set the cap")) return SLAMEM_ERR_ARG;
     s->max_occ = max_occ;
     return SLAMEM_OK;
 }
@@ -940,10 +902,7 @@ int slamem_stream_set_max_gap(slamem_stream* s, uint32_t max_gap) {
         set_error("slamem_stream_set_max_gap: the maximum gap must be below 2^31");
         return SLAMEM_ERR_ARG;
     }
-    if (s->submitted != 0) {
-        set_error("slamem_stream_set_max_gap: the stream has batches already (set the gap before the first submit)");
-        return SLAMEM_ERR_ARG;
-    }
+    if (has_batches(s, "slamem_stream_set_max_gap", "set the gap")) return SLAMEM_ERR_ARG;
     s->max_gap = max_gap;
     return SLAMEM_OK;
 }
@@ -955,10 +914,7 @@ int slamem_stream_set_ext_params(slamem_stream* s, uint32_t mismatch_penalty, ui
         set_error("slamem_stream_set_ext_params: a mismatch penalty or an X-drop needs match type 5 (-ext)");
         return SLAMEM_ERR_ARG;
     }
-    if (s->submitted != 0) {
-        set_error("slamem_stream_set_ext_params: the stream has batches already (set the parameters before the first submit)");
-        return SLAMEM_ERR_ARG;
-    }
+    if (has_batches(s, "slamem_stream_set_ext_params", "set the parameters")) return SLAMEM_ERR_ARG;
     s->ext_penalty = mismatch_penalty;
     s->ext_xdrop = xdrop;
     return SLAMEM_OK;
@@ -975,10 +931,7 @@ int slamem_stream_set_max_edits(slamem_stream* s, uint32_t max_edits) {
         set_error("slamem_stream_set_max_edits: at most %u edits a gap", kAlnMaxEdits);
         return SLAMEM_ERR_ARG;
     }
-    if (s->submitted != 0) {
-        set_error("slamem_stream_set_max_edits: the stream has batches already (set the limit before the first submit)");
-        return SLAMEM_ERR_ARG;
-    }
+    if (has_batches(s, "slamem_stream_set_max_edits", "set the limit")) return SLAMEM_ERR_ARG;
     s->max_edits = max_edits;
     return SLAMEM_OK;
 }
@@ -990,13 +943,9 @@ int slamem_stream_alns(slamem_stream* s, const slamem_aln** segs_out, const uint
     *segs_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr; *num_ops_out = 0;
     if (s->match_type == 8) { set_error("slamem_stream_alns: a stream of match type 8 (-pile) keeps its segments on the device"); return SLAMEM_ERR_ARG; }
     if (!is_aln(s)) { set_error("slamem_stream_alns: the stream's match type is not 6 (-aln)"); return SLAMEM_ERR_ARG; }
-    if (s->returned == 0) { set_error("slamem_stream_alns: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
-    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
-    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
-        set_error("slamem_stream_alns: the batch slamem_stream_next returned last has no segments to show");
-        return SLAMEM_ERR_ARG;
-    }
-    *segs_out = sl.h_segs; *ops_out = sl.h_ops; *op_offsets_out = sl.h_ooff; *num_ops_out = sl.ops_total;
+    const Slot* sl = last_returned(s, "slamem_stream_alns", "segments");
+    if (!sl) return SLAMEM_ERR_ARG;
+    *segs_out = sl->h_segs.get(); *ops_out = sl->h_ops.get(); *op_offsets_out = sl->h_ooff.get(); *num_ops_out = sl->ops_total;
     return SLAMEM_OK;
 }
 
@@ -1005,13 +954,9 @@ int slamem_stream_maps(slamem_stream* s, const slamem_map** reads_out) {
     std::unique_lock<std::mutex> lk(s->mu);
     *reads_out = nullptr;
     if (!is_map(s)) { set_error("slamem_stream_maps: the stream's match type is not 7 (-paf) or 8 (-pile)"); return SLAMEM_ERR_ARG; }
-    if (s->returned == 0) { set_error("slamem_stream_maps: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
-    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
-    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
-        set_error("slamem_stream_maps: the batch slamem_stream_next returned last has no reads to show");
-        return SLAMEM_ERR_ARG;
-    }
-    *reads_out = sl.h_reads;
+    const Slot* sl = last_returned(s, "slamem_stream_maps", "reads");
+    if (!sl) return SLAMEM_ERR_ARG;
+    *reads_out = sl->h_reads.get();
     return SLAMEM_OK;
 }
 
@@ -1022,10 +967,7 @@ int slamem_stream_set_md(slamem_stream* s, int on) {
         set_error("slamem_stream_set_md: the MD pass needs match type 7 (-paf)");
         return SLAMEM_ERR_ARG;
     }
-    if (s->submitted != 0) {
-        set_error("slamem_stream_set_md: the stream has batches already (switch the MD pass on before the first submit)");
-        return SLAMEM_ERR_ARG;
-    }
+    if (has_batches(s, "slamem_stream_set_md", "switch the MD pass on")) return SLAMEM_ERR_ARG;
     if (on && !s->idx->view.tpl) {
         set_error("slamem_stream_set_md: the MD entries take the reference letters from the text planes of the index, and this index "
                   "has none (the compact layout, or one built with the seed sections switched off)");
@@ -1044,13 +986,10 @@ int slamem_stream_md(slamem_stream* s, const uint32_t** md_out, const uint64_t**
     std::unique_lock<std::mutex> lk(s->mu);
     *md_out = nullptr; *md_offsets_out = nullptr; *seg_eq_out = nullptr; *primary_out = nullptr; *num_md_out = 0;
     if (!s->md) { set_error("slamem_stream_md: the stream's MD pass is not switched on (slamem_stream_set_md)"); return SLAMEM_ERR_ARG; }
-    if (s->returned == 0) { set_error("slamem_stream_md: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
-    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
-    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
-        set_error("slamem_stream_md: the batch slamem_stream_next returned last has no entries to show");
-        return SLAMEM_ERR_ARG;
-    }
-    *md_out = sl.h_md; *md_offsets_out = sl.h_md_off; *seg_eq_out = sl.h_seg_eq; *primary_out = sl.h_primary; *num_md_out = sl.md_total;
+    const Slot* sl = last_returned(s, "slamem_stream_md", "entries");
+    if (!sl) return SLAMEM_ERR_ARG;
+    *md_out = sl->h_md.get(); *md_offsets_out = sl->h_md_off.get(); *seg_eq_out = sl->h_seg_eq.get(); *primary_out = sl->h_primary.get();
+    *num_md_out = sl->md_total;
     return SLAMEM_OK;
 }
 
@@ -1070,10 +1009,7 @@ int slamem_stream_set_pileup(slamem_stream* s, slamem_pileup* pile, uint32_t min
         set_error("slamem_stream_set_pileup: the minimum mapping quality is 0 to 60");
         return SLAMEM_ERR_ARG;
     }
-    if (s->submitted != 0) {
-        set_error("slamem_stream_set_pileup: the stream has batches already (set the accumulator before the first submit)");
-        return SLAMEM_ERR_ARG;
-    }
+    if (has_batches(s, "slamem_stream_set_pileup", "set the accumulator")) return SLAMEM_ERR_ARG;
     s->pile = pile;
     s->min_mapq = min_mapq;
     return SLAMEM_OK;
@@ -1084,84 +1020,31 @@ int slamem_stream_mismatches(slamem_stream* s, const uint32_t** out) {
     std::unique_lock<std::mutex> lk(s->mu);
     *out = nullptr;
     if (s->match_type != 5) { set_error("slamem_stream_mismatches: the stream's match type is not 5 (-ext)"); return SLAMEM_ERR_ARG; }
-    if (s->returned == 0) { set_error("slamem_stream_mismatches: no batch has been returned yet"); return SLAMEM_ERR_ARG; }
-    Slot& sl = s->slot[(s->returned - 1) % (uint64_t)s->nslots];
-    if (sl.state != RETURNED || sl.rc != SLAMEM_OK) {
-        set_error("slamem_stream_mismatches: the batch slamem_stream_next returned last has no rows to show");
-        return SLAMEM_ERR_ARG;
-    }
-    *out = sl.h_mm;
+    const Slot* sl = last_returned(s, "slamem_stream_mismatches", "rows");
+    if (!sl) return SLAMEM_ERR_ARG;
+    *out = sl->h_mm.get();
     return SLAMEM_OK;
 }
 
 int slamem_stream_submit(slamem_stream* s, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len) {
     if (!s || !offsets || (num_queries && !queries)) { set_error("slamem_stream_submit: null argument"); return SLAMEM_ERR_ARG; }
     if (min_len < 1) { set_error("slamem_stream_submit: minimum MEM length must be >= 1"); return SLAMEM_ERR_ARG; }
-    std::unique_lock<std::mutex> lk(s->mu);
-    if (s->match_type == 8 && !s->pile) {
-        set_error("slamem_stream_submit: a stream of match type 8 (-pile) needs slamem_stream_set_pileup first");
-        return SLAMEM_ERR_ARG;
-    }
-    Slot& sl = s->slot[s->submitted % (uint64_t)s->nslots];
-    if (sl.state != FREE) {
-        // a slot is released by the slamem_stream_next call AFTER the one that handed its result out: at most slots - 1
-        // batches may be in flight beside the result the caller is working on.  Never blocks (a caller that both submits
-        // and collects on one thread would wait for itself).
-        set_error("slamem_stream_submit: all %d slots are in use (collect a result with slamem_stream_next first)", s->nslots);
-        return SLAMEM_ERR_ARG;
-    }
-    sl.seq = s->submitted;
-    sl.chars = queries;
-    sl.planes = nullptr;
-    sl.other = nullptr;
-    sl.lowq = nullptr;
-    sl.offs = offsets;
-    sl.nq = num_queries;
-    sl.min_len = min_len;
-    sl.rc = SLAMEM_OK;
-    sl.err[0] = 0;
-    sl.total = 0;
-    sl.state = QUEUED;
-    s->submitted++;
-    lk.unlock();
-    s->cv.notify_all();
-    return SLAMEM_OK;
+    Batch b;
+    b.chars = queries; b.offs = offsets; b.nq = num_queries; b.min_len = min_len;
+    return enqueue(s, "slamem_stream_submit", b);
 }
 
 int slamem_stream_submit_masked(slamem_stream* s, const char* queries, const uint64_t* lowq, const uint64_t* offsets, uint32_t num_queries,
                                 uint32_t min_len) {
     if (!s || !offsets || (num_queries && !queries)) { set_error("slamem_stream_submit_masked: null argument"); return SLAMEM_ERR_ARG; }
     if (min_len < 1) { set_error("slamem_stream_submit_masked: minimum MEM length must be >= 1"); return SLAMEM_ERR_ARG; }
-    std::unique_lock<std::mutex> lk(s->mu);
-    if (s->match_type != 8) {
+    if (s->match_type != 8) {  // (the match type is set once, at slamem_stream_create)
         set_error("slamem_stream_submit_masked: a low-quality mask needs match type 8 (-pile)");
         return SLAMEM_ERR_ARG;
     }
-    if (!s->pile) {
-        set_error("slamem_stream_submit_masked: a stream of match type 8 (-pile) needs slamem_stream_set_pileup first");
-        return SLAMEM_ERR_ARG;
-    }
-    Slot& sl = s->slot[s->submitted % (uint64_t)s->nslots];
-    if (sl.state != FREE) {
-        set_error("slamem_stream_submit_masked: all %d slots are in use (collect a result with slamem_stream_next first)", s->nslots);
-        return SLAMEM_ERR_ARG;
-    }
-    sl.seq = s->submitted;
-    sl.chars = queries;
-    sl.planes = nullptr;
-    sl.other = nullptr;
-    sl.lowq = lowq;  // (nullptr: the batch is an unmasked one)
-    sl.offs = offsets;
-    sl.nq = num_queries;
-    sl.min_len = min_len;
-    sl.rc = SLAMEM_OK;
-    sl.err[0] = 0;
-    sl.total = 0;
-    sl.state = QUEUED;
-    s->submitted++;
-    lk.unlock();
-    s->cv.notify_all();
-    return SLAMEM_OK;
+    Batch b;
+    b.chars = queries; b.lowq = lowq; b.offs = offsets; b.nq = num_queries; b.min_len = min_len;
+    return enqueue(s, "slamem_stream_submit_masked", b);
 }
 
 int slamem_stream_submit_packed(slamem_stream* s, const void* planes, const uint64_t* other, const uint64_t* offsets, uint32_t num_queries,
@@ -1169,33 +1052,9 @@ int slamem_stream_submit_packed(slamem_stream* s, const void* planes, const uint
     if (!s || !offsets || (num_queries && !planes)) { set_error("slamem_stream_submit_packed: null argument"); return SLAMEM_ERR_ARG; }
     if (((uintptr_t)planes & 15u) != 0) { set_error("slamem_stream_submit_packed: planes must be 16-byte aligned"); return SLAMEM_ERR_ARG; }
     if (min_len < 1) { set_error("slamem_stream_submit_packed: minimum MEM length must be >= 1"); return SLAMEM_ERR_ARG; }
-    std::unique_lock<std::mutex> lk(s->mu);
-    if (s->match_type == 8 && !s->pile) {
-        set_error("slamem_stream_submit_packed: a stream of match type 8 (-pile) needs slamem_stream_set_pileup first");
-        return SLAMEM_ERR_ARG;
-    }
-    Slot& sl = s->slot[s->submitted % (uint64_t)s->nslots];
-    if (sl.state != FREE) {
-        set_error("slamem_stream_submit_packed: all %d slots are in use (collect a result with slamem_stream_next first)", s->nslots);
-        return SLAMEM_ERR_ARG;
-    }
-    sl.seq = s->submitted;
-    sl.chars = nullptr;
-    sl.planes = planes;
-    sl.other = other;
-    sl.units_hint = num_units;
-    sl.lowq = nullptr;
-    sl.offs = offsets;
-    sl.nq = num_queries;
-    sl.min_len = min_len;
-    sl.rc = SLAMEM_OK;
-    sl.err[0] = 0;
-    sl.total = 0;
-    sl.state = QUEUED;
-    s->submitted++;
-    lk.unlock();
-    s->cv.notify_all();
-    return SLAMEM_OK;
+    Batch b;
+    b.planes = planes; b.other = other; b.units = num_units; b.offs = offsets; b.nq = num_queries; b.min_len = min_len;
+    return enqueue(s, "slamem_stream_submit_packed", b);
 }
 
 int slamem_stream_next(slamem_stream* s, const slamem_mem** mems_out, const uint64_t** block_offsets_out, uint64_t* total_out,
@@ -1212,8 +1071,8 @@ int slamem_stream_next(slamem_stream* s, const slamem_mem** mems_out, const uint
     s->cv.wait(lk, [&] { return sl.state == DONE; });
     sl.state = RETURNED;
     s->returned++;
-    *mems_out = sl.h_mems;
-    *block_offsets_out = sl.h_boff;
+    *mems_out = sl.h_mems.get();
+    *block_offsets_out = sl.h_boff.get();
     *total_out = sl.total;
     if (num_queries_out) *num_queries_out = sl.nq;
     if (timings_out) *timings_out = sl.tm;
