@@ -684,6 +684,47 @@ int slamem_pileup_depth_runs_host(slamem_pileup *pile, uint64_t first, uint64_t 
                                   uint32_t min_depth, uint64_t capacity, slamem_depth_run *runs, const uint64_t *bounds, uint64_t m,
                                   uint64_t *cum /* 2 m */, uint64_t *total_out);
 
+/* ---- (b''''''') duplicate reads counted once (option -dedup) -----------------------------------------------------
+ * A read is a candidate iff it would contribute to the pileup: strand != 0, mapq >= min_mapq, at least one segment.  Its key is
+ * (strand, u), u the unclipped 5' position in merged-text coordinates (signed; len the read's length):
+ *   strand 1   L the segment with the smallest query_pos:             u = ref_pos(L) - query_pos(L)
+ *   strand 2   R the segment with the largest query_pos + query_len:  u = ref_pos(R) + ref_len(R) + (len - query_pos(R) - query_len(R))
+ * Every dedup add of an accumulator gets a sequence number when it is enqueued; a read's rank is seq << 32 | its index in the
+ * batch.  A candidate is a duplicate iff another candidate with the same key has a smaller rank, and a duplicate is not piled: no
+ * counter, no diff, no indel event.  So one read per key is piled, the first in enqueue order and then in batch order -- with one
+ * stream, file order.  ADDITION WITH DEDUP DOES NOT COMMUTE ACROSS ADDS: the table of the counters is the same sum whatever the
+ * order, but which reads it is the sum of depends on the order the adds were enqueued in.
+ * The keys live in an open-addressing table in HBM beside the accumulator (16 bytes a slot, linear probing with a probe limit); a
+ * candidate that finds no slot within the limit is kept and counted as "no room".
+ *   slamem_pileup_enable_dedup  allocates the table of `slots` slots (a power of two from 64 to 2^32; 0: the smallest power of two
+ *                          that is at least 65,536 and a quarter of n; anything else SLAMEM_ERR_ARG).  Too little HBM:
+ *                          SLAMEM_ERR_NOMEM with the numbers.  A second call: SLAMEM_ERR_ARG.  Waits for the device.
+ *                          slamem_pileup_reset also clears the table, the counters and the sequence number; slamem_pileup_free
+ *                          releases them.
+ *   slamem_pileup_add_dedup_device  slamem_pileup_add_masked_device (lowq_dev may be NULL) behind the filter: reads_keep_dev takes
+ *                          num_queries records, the read records with strand 0 where the read is a duplicate, and is what the add
+ *                          kernels read -- it must stay until they are through; dup_out_dev (may be NULL) a byte per read: 0 kept
+ *                          or no candidate, 1 duplicate, 2 no room (kept).  reads_dev is left as it is.  Without
+ *                          slamem_pileup_enable_dedup: SLAMEM_ERR_ARG.  The filter's kernels of two such adds on one accumulator
+ *                          never overlap on the device, whatever streams they are enqueued on (a host mutex, an event); the add
+ *                          kernels behind them overlap freely.
+ *   slamem_pileup_dedup_stats  candidates, duplicates, candidates without room, slots newly claimed (= candidates kept with a
+ *                          slot: out[0] = out[1] + out[2] + out[3]), summed since the table was enabled or reset.  Waits for the
+ *                          device.
+ * slamem_pileup_add_device and slamem_pileup_add_masked_device on such an accumulator add every read as before, and
+ * slamem_pileup_add_counts_* and slamem_pileup_add_events_* bypass the filter: what they add are counts, not reads.
+ *   slamem_stream_set_dedup  on != 0: the download stage of a stream of match type 8 adds every batch with the filter; before the
+ *                          first submit, behind slamem_stream_set_pileup with an accumulator whose filter is enabled
+ *                          (SLAMEM_ERR_ARG otherwise).  slamem_stream_maps still gives the read records as the search wrote them.
+ *   slamem_stream_dups     the flags (a byte per read) of the batch slamem_stream_next returned last, in the stream's pinned
+ *                          memory, valid as long as that batch.  SLAMEM_ERR_ARG on a stream whose filter is not switched on. */
+int slamem_pileup_enable_dedup(slamem_pileup *pile, uint64_t slots);
+int slamem_pileup_add_dedup_device(slamem_pileup *pile, const void *queries_dev, const uint64_t *offsets_dev, uint32_t num_queries,
+                                   const slamem_aln *segs_dev, const uint64_t *read_offsets_dev, const uint32_t *ops_dev,
+                                   const uint64_t *op_offsets_dev, const slamem_map *reads_dev, uint32_t min_mapq,
+                                   const uint64_t *lowq_dev, slamem_map *reads_keep_dev, uint8_t *dup_out_dev, void *stream);
+int slamem_pileup_dedup_stats(slamem_pileup *pile, uint64_t out[4]);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -792,6 +833,9 @@ int slamem_stream_alns(slamem_stream *s, const slamem_aln **segs_out, const uint
  * valid as long as that batch.  Its segments and operations come through slamem_stream_alns. */
 int slamem_stream_maps(slamem_stream *s, const slamem_map **reads_out);
 int slamem_stream_set_pileup(slamem_stream *s, slamem_pileup *pile, uint32_t min_mapq);
+/* -dedup (described with slamem_pileup_enable_dedup above) */
+int slamem_stream_set_dedup(slamem_stream *s, int on);
+int slamem_stream_dups(slamem_stream *s, const uint8_t **flags_out);
 /* -sam: on != 0 makes every slot of a stream of match type 7 run slamem_maps_md_device behind its batch and
  * download the four arrays; before the first submit (SLAMEM_ERR_ARG after it, or on a stream of another match type).  A stream
  * that never calls it behaves as before and allocates nothing for this.  slamem_stream_md gives the arrays of the batch

@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "slamem_pileup_consensus_device", "slamem_pileup_consensus_host", "slamem_pileup_depth_runs_device", "slamem_pileup_depth_runs_host",
     "slamem_stream_create", "slamem_stream_set_max_occ", "slamem_stream_set_max_gap", "slamem_stream_submit", "slamem_stream_submit_packed", "slamem_pack_reads", "slamem_stream_next",
     "slamem_pack_lowq_device", "slamem_pack_lowq", "slamem_pileup_add_masked_device", "slamem_stream_submit_masked",
+    "slamem_pileup_enable_dedup", "slamem_pileup_add_dedup_device", "slamem_pileup_dedup_stats", "slamem_stream_set_dedup", "slamem_stream_dups",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
 )
@@ -220,6 +221,11 @@ def _declare(L):
     L.slamem_pileup_depth_runs_device.argtypes = [vp, u64, u64, vp, u32, u32, u64, vp, vp, u64, vp, C.POINTER(u64), vp]
     L.slamem_pileup_depth_runs_host.argtypes = [vp, u64, u64, vp, u32, u32, u64, vp, vp, u64, vp, C.POINTER(u64)]
     L.slamem_stream_set_pileup.argtypes = [vp, vp, u32]
+    L.slamem_pileup_enable_dedup.argtypes = [vp, u64]
+    L.slamem_pileup_add_dedup_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.slamem_pileup_dedup_stats.argtypes = [vp, C.POINTER(u64)]
+    L.slamem_stream_set_dedup.argtypes = [vp, i32]
+    L.slamem_stream_dups.argtypes = [vp, C.POINTER(vp)]
     L.slamem_stream_mismatches.argtypes = [vp, C.POINTER(C.POINTER(u32))]
     L.slamem_stream_submit.argtypes = [vp, vp, vp, u32, u32]
     L.slamem_copy_to_host.argtypes = [vp, vp, u64]

@@ -446,6 +446,14 @@ int pileup_add_masked(slamem_pileup* pile, const void* queries_dev, const uint64
                       const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev,
                       const uint64_t* op_offsets_dev, const slamem_map* reads_dev, uint32_t min_mapq, const uint64_t* lowq_dev,
                       hipStream_t stream);
+// -dedup (dedup_filter.hip): the claim and mark kernels over the batch, then pileup_add_masked over reads_keep_dev
+// (the read records with strand 0 where a read is a duplicate); dup_out_dev (a byte per read) may be nullptr.  The accumulator's
+// duplicate filter is enabled (pileup_has_dedup).
+int pileup_has_dedup(const slamem_pileup* pile);
+int pileup_add_dedup(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                     const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
+                     const slamem_map* reads_dev, uint32_t min_mapq, const uint64_t* lowq_dev, slamem_map* reads_keep_dev,
+                     uint8_t* dup_out_dev, hipStream_t stream);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).

@@ -595,7 +595,7 @@ int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
     slamem_pileup* p = new (std::nothrow) slamem_pileup();
     if (!p) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     p->idx = idx; p->device = idx->device; p->n = (uint32_t)n;
-    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr; p->cons = nullptr; p->depth = nullptr;
+    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr; p->cons = nullptr; p->depth = nullptr; p->dd = nullptr;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->diff), (n + 1) * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->cnt), n * 24 + 16);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->tile), tiles * 4);
@@ -621,6 +621,7 @@ int slamem_pileup_free(slamem_pileup* p) {
     events_free(p);
     cons_free(p);
     depth_free(p);
+    dedup_free(p);
     delete p;
     return SLAMEM_OK;
 }
@@ -632,6 +633,7 @@ int slamem_pileup_reset(slamem_pileup* p) {
     SLAMEM_HIP(hipMemset(p->diff, 0, ((uint64_t)p->n + 1) * 4));
     SLAMEM_HIP(hipMemset(p->cnt, 0, (uint64_t)p->n * 24));
     if (p->ev) { const int rc = events_reset(p); if (rc != SLAMEM_OK) return rc; }
+    if (p->dd) { const int rc = dedup_reset(p); if (rc != SLAMEM_OK) return rc; }
     SLAMEM_HIP(hipDeviceSynchronize());
     return SLAMEM_OK;
 }

@@ -1,5 +1,6 @@
 // pile_shared.h -- what pile_filter.hip (-pile and -sites), event_filter.hip (the indel events of -vcf,
-// DESIGN.md 4.18), cons_filter.hip (the consensus of -cons) and depth_filter.hip (the runs of -depth) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
+// DESIGN.md 4.18), cons_filter.hip (the consensus of -cons), depth_filter.hip (the runs of -depth) and
+// dedup_filter.hip (the duplicate filter of -dedup) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
 // segments (letters of the scanned strand, the steps of an operation), and the two entry points of the read-out's scratch that
 // the event side borrows.
 #pragma once
@@ -10,6 +11,7 @@ namespace slamem {
 struct EvTable;  // event_filter.hip: the hash table of the indel events, its counters and its read-out's scratch
 struct ConsScratch;  // cons_filter.hip: the consensus read-out's scratch (a flag byte per row, the sorted events and their marks)
 struct DepthScratch;  // depth_filter.hip: the depth read-out's scratch (three numbers per tile)
+struct DdTable;  // dedup_filter.hip: the hash table of the duplicate filter, its counters and the order of its adds
 
 }  // namespace slamem
 
@@ -24,6 +26,7 @@ struct slamem_pileup {
     slamem::EvTable* ev;  // nullptr: events are not enabled
     slamem::ConsScratch* cons;  // nullptr: no consensus was read yet
     slamem::DepthScratch* depth;  // nullptr: no depth runs were read yet
+    slamem::DdTable* dd;  // nullptr: the duplicate filter is not enabled
 };
 
 namespace slamem {
@@ -115,5 +118,9 @@ void cons_free(slamem_pileup* pile);
 
 // depth_filter.hip, for pile_filter.hip: what free does to the depth read-out's scratch
 void depth_free(slamem_pileup* pile);
+
+// dedup_filter.hip, for pile_filter.hip: what reset and free do to the duplicate filter's table
+int dedup_reset(slamem_pileup* pile);
+void dedup_free(slamem_pileup* pile);
 
 }  // namespace slamem

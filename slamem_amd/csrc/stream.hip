@@ -19,6 +19,7 @@
 // One thread per SLOT doing everything in turn was measured before that: the slots fall into lockstep, 62 ms.)
 // -pile (match type 8) is -paf whose segments stay on the device: the download stage, once the batch's totals have shown that
 // its result stands, enqueues the add to the accumulator (pile_filter.hip) on its stream and copies out the read records only.
+// With -dedup (slamem_stream_set_dedup) that add goes through the duplicate filter (dedup_filter.hip) and a flag per read comes back.
 // No CPU fallback: every batch is searched on the GPU.
 //
 // WHO OWNS WHAT.  Every buffer of a slot is a DevBuf or a PinnedBuf (buffers.h): freed by its destructor, grown by reserve(),
@@ -26,7 +27,7 @@
 // allocated at slamem_stream_create, and a batch no larger than the ones before allocates and frees nothing.
 //   upload    the inputs: letters, record offsets, block offsets, read records (and planes, unit counts, mask words)
 //   prepare   the outputs, sized by the inputs' room: rows, workspace, -ext's column, -aln's segments and operations
-//   download  the MD arrays and all pinned host memory; the outputs again when a batch's totals did not fit
+//   download  the MD arrays, -dedup's records and flags, and all pinned host memory; the outputs again when a batch's totals did not fit
 // INPUTS REGROWN => OUTPUTS DROPPED: where the upload stage regrows a slot's inputs it drops every output buffer
 // (drop_outputs), and the prepare stage, which finds no workspace, sizes them for the new room.
 // The end of a stream (teardown(): destroy, and a create that failed half way): every HIP stream waited for, then the slots
@@ -91,6 +92,11 @@ struct Slot {
     DevBuf<uint64_t> d_md_off;
     DevBuf<char> d_md_ws;
     uint64_t md_cap = 0;
+    // -dedup (slamem_stream_set_dedup), download stage: the read records the add kernels read (strand 0 where a read
+    // is a duplicate) and a flag byte per read, room for cap_q + 1 each; nothing of it exists on a stream whose filter is off
+    DevBuf<slamem_map> d_keep;
+    DevBuf<uint8_t> d_dup;
+    PinnedBuf<uint8_t> h_dup;
     // what slamem_stream_next and the getters hand out, in pinned host memory, allocated by the download stage as large as the
     // device buffer each is copied from; h_scal: the words K9's stream copies the batch's totals into (prepare stage)
     PinnedBuf<uint64_t> h_boff;
@@ -147,6 +153,7 @@ struct slamem_stream {
     slamem_pileup* pile = nullptr;          // -pile: the accumulator every batch is added to (slamem_stream_set_pileup)
     uint32_t min_mapq = 0;                  // -pile: the least mapping quality that counts
     bool md = false;                        // -sam: every batch also goes through the MD pass (slamem_stream_set_md)
+    bool dedup = false;                     // -dedup: every batch is added with the duplicate filter (slamem_stream_set_dedup)
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     std::unique_ptr<Slot[]> slot;  // nslots of them; they go in teardown(), in front of the HIP streams
@@ -563,6 +570,14 @@ int stage_download(slamem_stream* s, Slot& sl) {
         // where nobody knows yet whether the batch will be run again with more room.  Segments and operations stay on the device.
         // (a masked batch: the uploaded words start at the caller's word offs[0] / 64)
         const uint64_t* lowq = (sl.lowq && sl.d_lowq.get() && sl.offs[sl.nq] > sl.offs[0]) ? sl.d_lowq.get() - (sl.offs[0] >> 6) : nullptr;
+        if (s->dedup) {  // (this stage takes the batches in submission order, and so the filter numbers them)
+            SLAMEM_TRY(sl.d_keep.reserve((uint64_t)sl.cap_q + 1));
+            SLAMEM_TRY(sl.d_dup.reserve((uint64_t)sl.cap_q + 1));
+            SLAMEM_TRY(sl.h_dup.reserve((uint64_t)sl.cap_q + 1));
+            rc = pileup_add_dedup(s->pile, device_queries(sl), sl.d_off.get(), sl.nq, sl.d_segs.get(), sl.d_boff.get(), sl.d_ops.get(),
+                                  sl.d_ooff.get(), sl.d_reads.get(), s->min_mapq, lowq, sl.d_keep.get(), sl.d_dup.get(), st);
+            if (rc == SLAMEM_OK && sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_dup.get(), sl.d_dup.get(), sl.nq, hipMemcpyDeviceToHost, st));
+        } else
         rc = pileup_add_masked(s->pile, device_queries(sl), sl.d_off.get(), sl.nq, sl.d_segs.get(), sl.d_boff.get(), sl.d_ops.get(),
                                sl.d_ooff.get(), sl.d_reads.get(), s->min_mapq, lowq, st);
         if (rc != SLAMEM_OK) return rc;
@@ -1010,8 +1025,40 @@ int slamem_stream_set_pileup(slamem_stream* s, slamem_pileup* pile, uint32_t min
         return SLAMEM_ERR_ARG;
     }
     if (has_batches(s, "slamem_stream_set_pileup", "set the accumulator")) return SLAMEM_ERR_ARG;
+    if (s->dedup && !pileup_has_dedup(pile)) {
+        set_error("slamem_stream_set_pileup: the stream's duplicate filter is on and this accumulator has none enabled");
+        return SLAMEM_ERR_ARG;
+    }
     s->pile = pile;
     s->min_mapq = min_mapq;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_set_dedup(slamem_stream* s, int on) {
+    if (!s) { set_error("slamem_stream_set_dedup: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->match_type != 8) {
+        set_error("slamem_stream_set_dedup: the duplicate filter needs match type 8 (-pile)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (has_batches(s, "slamem_stream_set_dedup", "switch the duplicate filter on")) return SLAMEM_ERR_ARG;
+    if (on && (!s->pile || !pileup_has_dedup(s->pile))) {
+        set_error("slamem_stream_set_dedup: the stream needs an accumulator whose duplicate filter is enabled (slamem_pileup_enable_dedup, "
+                  "then slamem_stream_set_pileup)");
+        return SLAMEM_ERR_ARG;
+    }
+    s->dedup = on != 0;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_dups(slamem_stream* s, const uint8_t** flags_out) {
+    if (!s || !flags_out) { set_error("slamem_stream_dups: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    *flags_out = nullptr;
+    if (!s->dedup) { set_error("slamem_stream_dups: the stream's duplicate filter is not switched on (slamem_stream_set_dedup)"); return SLAMEM_ERR_ARG; }
+    const Slot* sl = last_returned(s, "slamem_stream_dups", "flags");
+    if (!sl) return SLAMEM_ERR_ARG;
+    *flags_out = sl->h_dup.get();
     return SLAMEM_OK;
 }
 

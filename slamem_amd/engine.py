@@ -337,7 +337,8 @@ class Index:
                 raise err
             break
         if pile is not None:
-            pile[0]._add_device(qd, od, num, segs, boff, ops, ooff, recs, pile[1], pile[2] if len(pile) > 2 else None)
+            pile[0]._add_device(qd, od, num, segs, boff, ops, ooff, recs, pile[1], pile[2] if len(pile) > 2 else None,
+                                bool(len(pile) > 3 and pile[3]))
             return _map_records(recs[: num * 12].cpu().numpy())
         nseg, nops = int(totals[1]), int(totals[2])
         extra = ()
@@ -428,31 +429,42 @@ class Pileup:
     delete it, and how many insert in front of it.  It is the sum over every batch added since creation or the last reset(),
     whatever the split into batches and their order.  28 bytes of HBM per text letter.  events=True: every add also records the
     reads' insertions and deletions as left-normalised events in a hash table of event_slots slots (a power of two of at least
-    64; 0: the default) -- see events()."""
+    64; 0: the default) -- see events().  dedup=True: the accumulator gets the duplicate filter of DESIGN.md 4.23, a table of
+    dedup_slots slots (a power of two of at least 64; 0: the default), and add(..., dedup=True) piles one read per (strand,
+    unclipped 5' position): the first in the order of the adds, then of the batch.  With it the table depends on the order of the
+    adds: addition no longer commutes across them."""
 
-    def __init__(self, index: Index, events: bool = False, event_slots: int = 0):
+    def __init__(self, index: Index, events: bool = False, event_slots: int = 0, dedup: bool = False, dedup_slots: int = 0):
         self.index = index
         self._h = C.c_void_p()
         if event_slots and not events:
             raise ValueError("event_slots is the size of the event table: it needs events=True")
+        if dedup_slots and not dedup:
+            raise ValueError("dedup_slots is the size of the duplicate filter's table: it needs dedup=True")
         capi.check(capi.lib().slamem_pileup_create(index._h, C.byref(self._h)))
-        if events:
-            rc = capi.lib().slamem_pileup_enable_events(self._h, int(event_slots))
+        for on, enable, slots in ((events, capi.lib().slamem_pileup_enable_events, event_slots),
+                                  (dedup, capi.lib().slamem_pileup_enable_dedup, dedup_slots)):
+            if not on:
+                continue
+            rc = enable(self._h, int(slots))
             if rc != capi.SLAMEM_OK:
                 h, self._h = self._h, None
                 try:
                     capi.check(rc)
                 finally:
                     capi.lib().slamem_pileup_free(h)
+        self.dedup = bool(dedup)
         self.last_add_ms = 0.0  # device time of the last add's own kernels (the mapping in front of them not counted)
 
     def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-            xdrop=None, max_edits=None, min_mapq: int = 0, lowq=None) -> np.ndarray:
+            xdrop=None, max_edits=None, min_mapq: int = 0, lowq=None, dedup: bool = False):
         """Maps the batch as Index.map_reads does and adds the mappings of the reads with mapq >= min_mapq (0 to 60) to the table,
         on the device: segments and operations are not downloaded.  Returns the read records of map_reads (MAP_DTYPE).  lowq: the
         batch's low-quality mask (DESIGN.md 4.21), a uint64 array of at least (offsets[-1] + 63) // 64 words (numpy, or a tensor on
         the index's device) in which bit offsets[r] + i belongs to letter i of read r as given -- a letter whose bit is set counts
-        nowhere under = and X; pack_lowq makes it from quality bytes.  None: every letter counts."""
+        nowhere under = and X; pack_lowq makes it from quality bytes.  None: every letter counts.  dedup=True (an accumulator made
+        with dedup=True): the batch goes through the duplicate filter and the call returns (reads, dup), dup a uint8
+        per read: 0 kept or no candidate, 1 duplicate (not piled), 2 no room in the filter's table (piled)."""
         if not 0 <= int(min_mapq) <= 60:
             raise ValueError("min_mapq must be in [0, 60]")
         if lowq is not None:
@@ -466,17 +478,25 @@ class Pileup:
                     raise ValueError("lowq must be a uint64 array")
             if lowq.shape[0] < need:
                 raise ValueError(f"lowq has {lowq.shape[0]} words, the batch's letters need {need}")
-        return self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, None, True,
-                                    pile=(self, int(min_mapq), lowq))
+        recs = self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, None, True,
+                                    pile=(self, int(min_mapq), lowq, bool(dedup)))
+        return (recs, self.last_dup) if dedup else recs
 
-    def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq, lowq=None):
+    def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq, lowq=None, dedup=False):
+        """dedup: through the duplicate filter; last_dup holds the batch's flags afterwards."""
         dev = self.index.device
         if lowq is not None and not isinstance(lowq, torch.Tensor):
             lowq = torch.from_numpy(lowq.view(np.int64).copy()).to(dev) if lowq.shape[0] else None
         with torch.cuda.device(dev):
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
-            if lowq is not None:
+            if dedup:
+                keep = torch.zeros((num + 1) * 12, dtype=torch.uint8, device=dev)
+                dup = torch.zeros(num + 1, dtype=torch.uint8, device=dev)
+                rc = capi.lib().slamem_pileup_add_dedup_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops),
+                                                               _ptr(ooff), _ptr(recs), int(min_mapq), _ptr(lowq) if lowq is not None else None,
+                                                               _ptr(keep), _ptr(dup), _stream_handle(dev))
+            elif lowq is not None:
                 rc = capi.lib().slamem_pileup_add_masked_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops),
                                                                 _ptr(ooff), _ptr(recs), int(min_mapq), _ptr(lowq), _stream_handle(dev))
             else:
@@ -486,6 +506,15 @@ class Pileup:
             capi.check(rc)
             t1.synchronize()  # (the batch's tensors go when the caller returns)
             self.last_add_ms = float(t0.elapsed_time(t1))
+            if dedup:
+                self.last_dup = dup[:num].cpu().numpy()
+
+    def dedup_stats(self) -> dict:
+        """slamem_pileup_dedup_stats: candidates, duplicates, no_room and kept (the slots newly claimed) of every add(dedup=True)
+        since creation or the last reset(); candidates = kept + duplicates + no_room."""
+        out = (C.c_uint64 * 4)()
+        capi.check(capi.lib().slamem_pileup_dedup_stats(self._h, out))
+        return dict(candidates=int(out[0]), duplicates=int(out[1]), no_room=int(out[2]), kept=int(out[3]))
 
     def counts(self, first: int = 0, count=None) -> np.ndarray:
         """Rows [first, first + count) of the table as a (count, 6) uint32 array (count None: up to the text's end).  The
@@ -766,15 +795,20 @@ class Stream:
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
                  max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False,
-                 pile: "Pileup" = None, min_mapq: int = 0, md: bool = False):
+                 pile: "Pileup" = None, min_mapq: int = 0, md: bool = False, dedup: bool = False):
         """md=True (with paf=True): every batch also goes through the MD pass and mds() gives (md, md_offsets,
         seg_eq, primary) of the batch next() returned last, as Index.map_reads(md=True) appends them.
+        dedup=True (with pile=<Pileup> made with dedup=True): every batch is added through the duplicate filter, in
+        the order of the submits, and dups() gives the flags of the batch next() returned last.
         pile=<Pileup>: -pile mode (match type 8): every batch is mapped as with paf=True and added to the accumulator on the
         device (the reads with mapq >= min_mapq); next() then returns (number of segments piled, None, timings) and maps() the read
         records; the segments are not downloaded.  It takes the parameters of paf and excludes the other modes.  aln=True: -aln mode (match type 6); it takes max_gap, penalty, xdrop and max_edits and excludes the other modes.
         next() then returns the segments (ALN_DTYPE) in the place of the rows, alns() their operations.  paf=True: -paf mode
         (match type 7), the same with the offsets per READ and maps() the read records (MAP_DTYPE)."""
         self.pile = pile
+        if dedup and pile is None:
+            raise ValueError("dedup is the duplicate filter of pile: it needs pile=<Pileup>")
+        self.dedup = bool(dedup)
         if pile is not None and (aln or paf):
             raise ValueError("pile excludes aln and paf: one match type per search")
         if min_mapq and pile is None:
@@ -806,6 +840,8 @@ class Stream:
                 capi.check(capi.lib().slamem_stream_set_max_edits(self._h, int(max_edits)))
             if pile is not None:
                 capi.check(capi.lib().slamem_stream_set_pileup(self._h, pile._h, int(min_mapq)))
+            if dedup:
+                capi.check(capi.lib().slamem_stream_set_dedup(self._h, 1))
             if md:
                 capi.check(capi.lib().slamem_stream_set_md(self._h, 1))
         except Exception:
@@ -855,6 +891,10 @@ class Stream:
             capi.check(capi.lib().slamem_stream_maps(self._h, C.byref(recs)))
             raw = np.ctypeslib.as_array((C.c_uint8 * (12 * max(1, nq.value))).from_address(recs.value))[: 12 * nq.value]
             self._last_maps = _map_records(raw)
+            if self.dedup:
+                flags = C.c_void_p()
+                capi.check(capi.lib().slamem_stream_dups(self._h, C.byref(flags)))
+                self._last_dups = np.ctypeslib.as_array((C.c_uint8 * max(1, nq.value)).from_address(flags.value))[: nq.value].copy()
             return int(total.value), None, tm.as_dict()
         if self.aln:  # the segments stand in the place of the rows
             segs, ops, ooff, nops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
@@ -894,6 +934,11 @@ class Stream:
     def maps(self):
         """-paf: the read records (MAP_DTYPE) of the batch next() returned last (slamem_stream_maps), as next() took them."""
         return self._last_maps
+
+    def dups(self):
+        """dedup=True: the duplicate flags (uint8 per read, as Pileup.add(dedup=True) returns them) of the batch next() returned
+        last (slamem_stream_dups), copied."""
+        return self._last_dups
 
     def mds(self):
         """md=True: (md, md_offsets, seg_eq, primary) of the batch next() returned last (slamem_stream_md), copied."""

@@ -647,6 +647,8 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-vcf\tthe calls of the pileup as VCF 4.2: the SNVs of -sites and the reads' insertions and deletions as left-normalised events; -mgap, -pen, -xdrop, -maxed, -minq, -mdep, -mpct apply\n");
     printf("\t-cons\tthe consensus sequence of the mapped reads as FASTA, a record per reference record: per position the plurality letter (lower case: the reference kept below the depth of -mdep), and the insertions and deletions that more than half of the reads show; -mgap, -pen, -xdrop, -maxed, -minq, -mdep, -evs apply\n");
     printf("\t-depth\tthe depth of coverage A+C+G+T+D of the mapped reads as a bedGraph: record, start, end (0-based, half-open) and the depth of each run of equal depth, the runs of depth 0 included; -mgap, -pen, -xdrop, -maxed, -minq apply; -mdep N: the depth from which a position counts as covered in the summary on stderr (default=1); -lev LIST: comma-separated ascending depths, the value of a run is the number of them it reaches; -win N: instead of the runs the mean depth of every N positions\n");
+    printf("\t-dedup\twith -pile, -sites, -vcf, -cons, -depth: reads with the same strand and unclipped 5' position (PCR and optical copies) count once, the first in file order; found on the GPU; one GPU only\n");
+    printf("\t-dslots\twith -dedup: slots of its table on the GPU, a power of two of at least 64 (default: at least 65536 and a quarter of the reference)\n");
     printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
@@ -681,6 +683,8 @@ int main(int argc, char **argv) {
     uint32_t levels[16];
     uint64_t window = 0;
     uint64_t ev_slots = 0;
+    int dedup = 0;                              /* -dedup: every batch is added through the duplicate filter */
+    uint64_t dd_slots = 0;
     slamem_pileup *piles[16];
     double t0;
     long long total_matches = 0, total_sum = 0;
@@ -705,7 +709,7 @@ int main(int argc, char **argv) {
     sites = slh_parse_argument(argc, argv, "SI", 0);
     vcf = slh_parse_argument(argc, argv, "VC", 0);
     cons = slh_parse_argument(argc, argv, "CO", 0);
-    depth = slh_parse_argument(argc, argv, "DE", 0);
+    depth = slh_parse_depth(argc, argv);
     sam = slh_parse_argument(argc, argv, "SA", 0);
     if (o.match_type < 0) { /* before any GPU work */
         if (sam) exit_message("Option -sam excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites, -vcf, -cons and -depth");
@@ -775,6 +779,18 @@ int main(int argc, char **argv) {
     case -1: exit_message("Option -evs needs a power of two of at least 64"); break;
     case 1: if (!vcf && !cons) exit_message("Option -evs needs -vcf"); break;
     default: break;
+    }
+    switch ((dedup = slh_parse_dedup(argc, argv, &dd_slots))) {
+    case -1: exit_message("Option -dslots needs a power of two of at least 64"); break;
+    case 2: exit_message("Option -dslots needs -dedup"); break;
+    case 0: break;
+    default:
+        if (o.match_type != 8) exit_message("Option -dedup needs -pile, -sites, -vcf, -cons or -depth");
+        /* one table per GPU would miss the duplicates whose copies went to different GPUs */
+        if (((env = getenv("SLAMEM_GPUS")) != NULL && atoi(env) != 1) || ((env = getenv("SLAMEM_LOGICAL_GPUS")) != NULL && atoi(env) > 1))
+            exit_message("Option -dedup runs on one GPU: every GPU would keep a table of its own and miss the duplicates whose copies went to different GPUs (leave SLAMEM_GPUS unset, or set it to 1)");
+        dedup = 1;
+        break;
     }
     if (o.num_files < 2) exit_message("Not enough input sequence files provided");
     if (o.ref_name_given && o.ref_name_empty) exit_message("No reference name string provided");
@@ -1069,7 +1085,9 @@ int main(int argc, char **argv) {
                 g_nstreams = g + 1;
                 rc = slamem_pileup_create(gpus[g], &piles[g]);
                 if (rc == SLAMEM_OK && (vcf || cons)) rc = slamem_pileup_enable_events(piles[g], ev_slots);
+                if (rc == SLAMEM_OK && dedup) rc = slamem_pileup_enable_dedup(piles[g], dd_slots);
                 if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(g_streams[g], piles[g], (uint32_t)min_mapq);
+                if (rc == SLAMEM_OK && dedup) rc = slamem_stream_set_dedup(g_streams[g], 1);
             }
             if (rc == SLAMEM_OK && (o.match_type == 6 || o.match_type == 7 || o.match_type == 8)) {
                 g_nstreams = g + 1;
@@ -1575,6 +1593,14 @@ int main(int argc, char **argv) {
             free(rows);
             free(more);
             t_format += now_s() - tp;
+        }
+        if (dedup && g_nstreams > 0) { /* (one GPU: its counters are the run's) */
+            uint64_t dd[4] = {0, 0, 0, 0};
+            rc = slamem_pileup_dedup_stats(piles[0], dd);
+            if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the duplicate filter's counters from the GPU", rc); }
+            fprintf(stderr, "> Duplicates: %llu candidate reads, %llu duplicates (%.2f %%) not counted, %llu without room in the duplicate "
+                            "table%s\n", (unsigned long long)dd[0], (unsigned long long)dd[1], dd[0] ? 100.0 * (double)dd[1] / (double)dd[0] : 0.0,
+                    (unsigned long long)dd[2], dd[2] ? " (a larger table: -dslots)" : "");
         }
         writer_finish(&g_writer);
         t_write = g_writer.seconds;

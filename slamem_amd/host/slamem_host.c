@@ -1060,6 +1060,38 @@ int slh_parse_event_slots(int argc, char **argv, uint64_t *out) {
     return 0;
 }
 
+/* -dedup: "de" as -depth, told apart by its third letter as -maxed is from -mam */
+static int is_dedup_option(const char *a) {
+    return two_letter_option(a, 'd', 'e') && (a[3] == 'd' || a[3] == 'D');
+}
+
+int slh_parse_depth(int argc, char **argv) {
+    int i;
+    for (i = 1; i < argc; i++)
+        if (two_letter_option(argv[i], 'd', 'e') && !is_dedup_option(argv[i])) return 1;
+    return 0;
+}
+
+int slh_parse_dedup(int argc, char **argv, uint64_t *slots_out) {
+    int i, seen = 0;
+    *slots_out = 0;
+    for (i = 1; i < argc; i++) {
+        char *end;
+        long long v;
+        if (is_dedup_option(argv[i])) { seen |= 1; continue; } /* (no value: it may stand anywhere) */
+        /* the two letters "ds" decide; it takes the next argument */
+        if (!two_letter_option(argv[i], 'd', 's')) continue;
+        if (i == argc - 1) return -1;
+        errno = 0;
+        v = strtoll(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 64 || v > (1LL << 32) || (v & (v - 1)) != 0) return -1;
+        *slots_out = (uint64_t)v;
+        seen |= 2;
+        i++;
+    }
+    return seen;
+}
+
 int slh_parse_depth_params(int argc, char **argv, uint32_t *levels_out, int *num_levels_out, uint64_t *window_out) {
     int i, seen = 0;
     *num_levels_out = 0;
@@ -1139,6 +1171,7 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
             else if (two_letter_option(argv[i], 'e', 'v')) i++; /* -evs N (of -vcf) */
             else if (two_letter_option(argv[i], 'b', 'q')) i++; /* -bq N (of -pile and its read-outs; "-b" alone takes none) */
             else if (two_letter_option(argv[i], 'w', 'i')) i++; /* -win N (of -depth; its -lev LIST begins with l) */
+            else if (two_letter_option(argv[i], 'd', 's')) i++; /* -dslots N (of -dedup, which takes none) */
             else if (two_letter_option(argv[i], 'p', 'e') || two_letter_option(argv[i], 'x', 'd')) i++; /* -pen N, -xdrop N (of -ext) */
             else if (oc == 'r') {
                 i++;
@@ -1218,7 +1251,7 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
         o->match_type = o->match_type != 0 ? -1 : 8;
     if (slh_parse_argument(argc, argv, "CO", 0)) /* -cons: the consensus of the pileup as FASTA: match type 8 with the events enabled and a fourth read-out (a 'c' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 8;
-    if (slh_parse_argument(argc, argv, "DE", 0)) /* -depth: the depth of coverage as runs: match type 8 with a fifth read-out (a 'd' option takes no value) */
+    if (slh_parse_depth(argc, argv)) /* -depth ("de", but not -dedup, the duplicate filter of the pileup's modes): the depth of coverage as runs: match type 8 with a fifth read-out (a 'd' option takes no value) */
         o->match_type = o->match_type != 0 ? -1 : 8;
     o->both_strands = slh_parse_argument(argc, argv, "B", 0);
     o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);

@@ -126,6 +126,11 @@ int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_p
  * default), 1 when it is, -1 when the value is missing, not an integer or no such power of two.  Its value is never taken for a
  * file name. */
 int slh_parse_event_slots(int argc, char **argv, uint64_t *out);
+/* -depth: is an option given whose first two letters are "de" and that is not -dedup? */
+int slh_parse_depth(int argc, char **argv);
+/* -dedup and -dslots N (the slots of its table, a power of two from 64 to 2^32): bit 0 of the result -dedup was given, bit 1
+   -dslots was, with its value in *slots_out (0: not given); -1: -dslots without such a value */
+int slh_parse_dedup(int argc, char **argv, uint64_t *slots_out);
 /* -lev LIST (-le...) and -win N (-wi...) of -depth: LIST is 1 to 16 whole numbers in [1, 2^32), strictly ascending, separated by
  * commas (levels_out has room for 16); N is a whole number of at least 1.  0 when neither is there (*num_levels_out = 0,
  * *window_out = 0), else bit 0 says that -lev is there and bit 1 that -win is; -1 when the value of -lev is missing or no such
