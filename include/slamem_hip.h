@@ -725,6 +725,66 @@ int slamem_pileup_add_dedup_device(slamem_pileup *pile, const void *queries_dev,
                                    const uint64_t *lowq_dev, slamem_map *reads_keep_dev, uint8_t *dup_out_dev, void *stream);
 int slamem_pileup_dedup_stats(slamem_pileup *pile, uint64_t out[4]);
 
+/* ---- (b'''''''') diploid genotypes of the pileup (option -gt) ----------------------------------------------------
+ * A likelihood-based call per row and per indel event, all in unsigned 64-bit integers, scores in milli-Phred.  The parameters:
+ * ploidy 1 or 2; match_cost M, het_cost H, err_cost E: what one observed letter costs a genotype that is homozygous for it,
+ * heterozygous with it, or does not hold it (H and E from 1, M from 0, none above 2^20; slamem_gt_costs gives the three for a
+ * constant error rate of Phred q, q = 20: 44, 3039, 24771); het_prior hp (0 to 2^20): the cost per non-reference allele of a
+ * genotype; min_depth as for -sites (1 to 2^31 - 1); min_qual in Phred, 0 to 999.
+ *   SNV rows   c[0..3] the A C G T columns of row p, r the column of L(p), d(p) = A+C+G+T+D.  Ploidy 2: the ten genotypes (j, k),
+ *              j <= k, at index g = k (k + 1) / 2 + j (AA AC CC AG CG GG AT CT GT TT); L_g = sum_i c[i] w(i, g), w = M when
+ *              i == j == k, H when j != k and i is one of them, else E.  Ploidy 1: the four genotypes i, L_i = c[i] M + (the
+ *              others) E.  S_g = L_g + hp * (distinct letters of g that are not r).  The best genotype has the smallest S; on a
+ *              tie the homozygous-reference one wins, then the smallest g.  qual = S_rr - S_best, gq = the smallest S_g - S_best
+ *              over g != best, pl[g] = L_g - min L; each saturates at 2^32 - 1 when stored.  Row p is selected iff L(p) is one of
+ *              A,C,G,T, d(p) >= min_depth, the best genotype is not rr and qual >= 1000 * min_qual.
+ *   events     ao = fwd + rev, d the depth of the anchor row, ro = d > ao ? d - ao : 0; L_00 = ro M + ao E, L_01 = (ro + ao) H
+ *              (ploidy 2 only), L_11 = ao M + ro E, priors 0, hp, hp; best, qual, gq and pl[0..2] (pl[0..1] at ploidy 1) as
+ *              above; called iff d >= min_depth, the best genotype is not 00 and qual >= 1000 * min_qual.  Every event stands
+ *              alone against everything else at its anchor: two events of one anchor are not made one multi-allelic call.
+ * slamem_genotype: a <= b are letter columns (SNV) or allele numbers 0 / 1 (event), both the one allele at ploidy 1; ref is r (0
+ * for an event); unused pl entries and the padding are 0.
+ *   slamem_gt_costs        host code: out[0..2] = M, H, E of q in 1 .. 93 with e = 10^(-q/10): round(-10000 log10(1 - e)),
+ *                          round(-10000 log10((1 - e) / 2 + e / 6)), round(-10000 log10(e / 3)); another q: SLAMEM_ERR_ARG.
+ *   slamem_pileup_genotypes_device  the selected rows of [first, first + count) in ascending position: pos (uint64), counts
+ *                          (uint32 x 6) and gts, with the capacity contract of slamem_pileup_sites_device: asynchronous up to the
+ *                          one host round trip that brings the number of selected rows to *total_out; more than `capacity`:
+ *                          SLAMEM_ERR_CAPACITY with the need there, the first `capacity` rows written and nothing beyond them.
+ *                          SLAMEM_ERR_ARG: a range outside [0, n] or parameters outside the ranges above.  It shares the
+ *                          read-outs' scratch: two read-outs of one accumulator must not run at the same time.
+ *   slamem_pileup_genotypes_host  the same into host memory; waits for the device first.
+ *   slamem_pileup_genotype_events_device  m events (as slamem_pileup_events_* gives them) and the m x 6 rows of their anchors (as
+ *                          slamem_pileup_rows_at_device gives them), both in device memory: a slamem_genotype and a `called`
+ *                          byte (0 / 1) per event; asynchronous on `stream`.
+ *   slamem_pileup_genotype_events_host  the same from and into host memory, with the anchors as m positions: their rows are
+ *                          read on the device.  An anchor at or beyond n: SLAMEM_ERR_ARG. */
+typedef struct {
+    uint32_t ploidy;     /* 1 or 2 */
+    uint32_t match_cost; /* M */
+    uint32_t het_cost;   /* H */
+    uint32_t err_cost;   /* E */
+    uint32_t het_prior;  /* hp */
+    uint32_t min_depth;
+    uint32_t min_qual;   /* Phred */
+} slamem_gt_params;
+typedef struct {
+    uint32_t qual, gq;
+    uint8_t a, b, ploidy, ref;
+    uint32_t pl[10];
+    uint8_t pad[4];
+} slamem_genotype; /* 56 bytes */
+int slamem_gt_costs(uint32_t q, uint32_t out[3]);
+int slamem_pileup_genotypes_device(slamem_pileup *pile, uint64_t first, uint64_t count, const slamem_gt_params *params,
+                                   uint64_t capacity, uint64_t *pos_dev, uint32_t *counts_dev, slamem_genotype *gts_dev,
+                                   uint64_t *total_out, void *stream);
+int slamem_pileup_genotypes_host(slamem_pileup *pile, uint64_t first, uint64_t count, const slamem_gt_params *params,
+                                 uint64_t capacity, uint64_t *pos, uint32_t *counts, slamem_genotype *gts, uint64_t *total_out);
+int slamem_pileup_genotype_events_device(slamem_pileup *pile, const slamem_event *events_dev, const uint32_t *anchor_rows_dev,
+                                         uint64_t m, const slamem_gt_params *params, slamem_genotype *gts_dev, uint8_t *called_dev,
+                                         void *stream);
+int slamem_pileup_genotype_events_host(slamem_pileup *pile, const slamem_event *events, const uint64_t *anchors, uint64_t m,
+                                       const slamem_gt_params *params, slamem_genotype *gts, uint8_t *called);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */

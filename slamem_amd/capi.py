@@ -58,6 +58,8 @@ ABI_SYMBOLS = (
     "slamem_stream_create", "slamem_stream_set_max_occ", "slamem_stream_set_max_gap", "slamem_stream_submit", "slamem_stream_submit_packed", "slamem_pack_reads", "slamem_stream_next",
     "slamem_pack_lowq_device", "slamem_pack_lowq", "slamem_pileup_add_masked_device", "slamem_stream_submit_masked",
     "slamem_pileup_enable_dedup", "slamem_pileup_add_dedup_device", "slamem_pileup_dedup_stats", "slamem_stream_set_dedup", "slamem_stream_dups",
+    "slamem_gt_costs", "slamem_pileup_genotypes_device", "slamem_pileup_genotypes_host", "slamem_pileup_genotype_events_device",
+    "slamem_pileup_genotype_events_host",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
 )
@@ -115,6 +117,12 @@ class SearchStats(C.Structure):
 
 _LIB = None
 _SYNTH = None
+
+
+class GtParams(C.Structure):
+    """slamem_gt_params (-gt)"""
+    _fields_ = [("ploidy", C.c_uint32), ("match_cost", C.c_uint32), ("het_cost", C.c_uint32), ("err_cost", C.c_uint32),
+                ("het_prior", C.c_uint32), ("min_depth", C.c_uint32), ("min_qual", C.c_uint32)]
 
 
 def _declare(L):
@@ -225,6 +233,11 @@ def _declare(L):
     L.slamem_pileup_add_dedup_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.slamem_pileup_dedup_stats.argtypes = [vp, C.POINTER(u64)]
     L.slamem_stream_set_dedup.argtypes = [vp, i32]
+    L.slamem_gt_costs.argtypes = [u32, C.POINTER(u32)]
+    L.slamem_pileup_genotypes_device.argtypes = [vp, u64, u64, C.POINTER(GtParams), u64, vp, vp, vp, C.POINTER(u64), vp]
+    L.slamem_pileup_genotypes_host.argtypes = [vp, u64, u64, C.POINTER(GtParams), u64, vp, vp, vp, C.POINTER(u64)]
+    L.slamem_pileup_genotype_events_device.argtypes = [vp, vp, vp, u64, C.POINTER(GtParams), vp, vp, vp]
+    L.slamem_pileup_genotype_events_host.argtypes = [vp, vp, vp, u64, C.POINTER(GtParams), vp, vp]
     L.slamem_stream_dups.argtypes = [vp, C.POINTER(vp)]
     L.slamem_stream_mismatches.argtypes = [vp, C.POINTER(C.POINTER(u32))]
     L.slamem_stream_submit.argtypes = [vp, vp, vp, u32, u32]

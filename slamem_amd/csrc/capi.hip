@@ -4,6 +4,7 @@
 #include "buffers.h"
 #include "common.h"
 
+#include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -143,6 +144,20 @@ const char* slamem_strerror(int code) {
 }
 
 const char* slamem_last_error_message(void) { return g_err; }
+
+// -gt: the three costs of a letter at a constant error rate of Phred q.  Host arithmetic in doubles, one
+// operation after the other as engine.gt_costs and tests/gt_spec.py write them, rounded half up.
+int slamem_gt_costs(uint32_t q, uint32_t out[3]) {
+    if (!out) { set_error("slamem_gt_costs: null argument"); return SLAMEM_ERR_ARG; }
+    if (q < 1u || q > 93u) { set_error("slamem_gt_costs: the error rate is 1 to 93 Phred, not %u", q); return SLAMEM_ERR_ARG; }
+    // (volatile: every intermediate is rounded to a double of its own, never fused with the next operation)
+    const volatile double e = pow(10.0, -(double)q / 10.0);
+    const volatile double hom = 1.0 - e, half = hom / 2.0, sixth = e / 6.0, het = half + sixth, third = e / 3.0;
+    out[0] = (uint32_t)floor(-10000.0 * log10(hom) + 0.5);
+    out[1] = (uint32_t)floor(-10000.0 * log10(het) + 0.5);
+    out[2] = (uint32_t)floor(-10000.0 * log10(third) + 0.5);
+    return SLAMEM_OK;
+}
 
 int slamem_device_count(int* count_out) {
     if (!count_out) return SLAMEM_ERR_ARG;

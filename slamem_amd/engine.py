@@ -27,6 +27,34 @@ EVENT_DTYPE = np.dtype([("pos", "<u8"), ("letters", "<u8"), ("fwd", "<u4"), ("re
 SAM_LANE_OPS = 32  # -sam: the MD entries of a segment of up to this many operations are written by one lane, of a longer one by a wave (sam_filter.hip)
 MD_CLOSE = 8  # the closing entry of a segment: m << 4 | 8
 PILE_LANE_OPS = 32  # -pile: a segment of up to this many operations is walked by one lane, a longer one by a wave (pile_filter.hip)
+# slamem_genotype: a <= b letter columns (SNV) or allele numbers 0 / 1 (event); scores in milli-Phred
+GENOTYPE_DTYPE = np.dtype([("qual", "<u4"), ("gq", "<u4"), ("a", "u1"), ("b", "u1"), ("ploidy", "u1"), ("ref", "u1"), ("pl", "<u4", (10,)),
+                           ("pad", "u1", (4,))])
+
+
+def gt_costs(q: int) -> tuple[int, int, int]:
+    """(M, H, E): what one observed letter costs a genotype that is homozygous for it, heterozygous with it, or does not hold it,
+    in milli-Phred, at a constant error rate of Phred q (1 to 93).  Host arithmetic, the same operations in the
+    same order as slamem_gt_costs; q = 20 gives (44, 3039, 24771)."""
+    import math
+    q = int(q)
+    if not 1 <= q <= 93:
+        raise ValueError("the error rate is 1 to 93 Phred")
+    e = math.pow(10.0, -float(q) / 10.0)
+    hom = 1.0 - e
+    het = hom / 2.0 + e / 6.0
+    third = e / 3.0
+    return tuple(int(math.floor(-10000.0 * math.log10(x) + 0.5)) for x in (hom, het, third))
+
+
+def _gt_params(ploidy, err_q, het_q, min_depth, min_qual) -> capi.GtParams:
+    M, H, E = gt_costs(err_q)
+    if not 0 <= int(het_q) <= 999:
+        raise ValueError("het_q is 0 to 999 Phred")
+    vals = (int(ploidy), M, H, E, 1000 * int(het_q), int(min_depth), int(min_qual))
+    if not all(0 <= v < 2 ** 32 for v in vals):
+        raise ValueError("the genotype parameters are unsigned 32-bit numbers")
+    return capi.GtParams(*vals)
 
 
 def _map_records(raw: np.ndarray) -> np.ndarray:
@@ -622,6 +650,67 @@ class Pileup:
                 capi.check(capi.lib().slamem_pileup_rows_at_device(self._h, _ptr(pd), m, _ptr(out), _stream_handle(dev)))
                 torch.cuda.current_stream(dev).synchronize()
         return out[:m].cpu().numpy().view(np.uint32)
+
+    def genotypes(self, ploidy: int = 2, err_q: int = 20, het_q: int = 30, min_depth: int = 4, min_qual: int = 20, first: int = 0,
+                  count=None, capacity=None):
+        """The rows of [first, first + count) whose best genotype is not the reference's, called and compacted on
+        the device, as (pos uint64 (m,), counts uint32 (m, 6), gts GENOTYPE_DTYPE (m,)) in ascending position.  A row's ten
+        (ploidy 1: four) genotypes are scored from its A C G T counters at a constant error rate of Phred err_q (gt_costs), with
+        a prior cost of het_q Phred per non-reference allele; it is selected iff the text's letter is one of A,C,G,T, the depth
+        A+C+G+T+D is at least min_depth, the best genotype differs from the reference's and its QUAL is at least min_qual Phred.
+        capacity: rows of room for the first attempt (default: one in 64 of the range, at least 4,096); when more are selected
+        the call is made once more with the need it reported."""
+        first = int(first)
+        count = self.index.n - first if count is None else int(count)
+        dev = self.index.device
+        params = _gt_params(ploidy, err_q, het_q, min_depth, min_qual)
+        cap = max(4096, count // 64) if capacity is None else int(capacity)
+        total = C.c_uint64()
+        with torch.cuda.device(dev):
+            for attempt in (0, 1):
+                pos = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+                rows = torch.empty((max(cap, 1), 6), dtype=torch.int32, device=dev)
+                gts = torch.empty(max(cap, 1) * GENOTYPE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                rc = capi.lib().slamem_pileup_genotypes_device(self._h, first, count, C.byref(params), cap, _ptr(pos), _ptr(rows),
+                                                               _ptr(gts), C.byref(total), _stream_handle(dev))
+                if rc != capi.SLAMEM_ERR_CAPACITY or attempt:
+                    break
+                cap = int(total.value)
+            capi.check(rc)
+        m = int(total.value)
+        return (pos[:m].cpu().numpy().view(np.uint64), rows[:m].cpu().numpy().view(np.uint32),
+                gts[:m * GENOTYPE_DTYPE.itemsize].cpu().numpy().view(GENOTYPE_DTYPE).copy())
+
+    def genotype_events(self, events, anchors, ploidy: int = 2, err_q: int = 20, het_q: int = 30, min_depth: int = 4, min_qual: int = 20):
+        """(gts GENOTYPE_DTYPE (m,), called uint8 (m,)): the genotype of every given event (a structured array of EVENT_DTYPE, as
+        events() returns it) against everything else at its anchor row (anchors: m positions below n -- the row in front of the
+        event, or the event's own row at a record's first letter), with the parameters of genotypes().  An event is called iff
+        its anchor's depth is at least min_depth, its best genotype is not 0/0 and its QUAL is at least min_qual Phred.  Every
+        event is genotyped on its own: two events of one anchor are not made one multi-allelic call."""
+        a = np.ascontiguousarray(np.asarray(events))
+        if a.dtype != EVENT_DTYPE or a.ndim != 1:
+            raise ValueError("genotype_events takes a one-dimensional array of EVENT_DTYPE")
+        pos = np.ascontiguousarray(np.asarray(anchors, dtype=np.uint64).reshape(-1))
+        m = len(a)
+        if len(pos) != m:
+            raise ValueError(f"{m} events and {len(pos)} anchors")
+        if m and int(pos.max()) >= self.index.n:
+            raise ValueError("an anchor lies at or beyond the text's end")
+        params = _gt_params(ploidy, err_q, het_q, min_depth, min_qual)
+        dev = self.index.device
+        gts = torch.zeros(max(m, 1) * GENOTYPE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        called = torch.zeros(max(m, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            ed = torch.from_numpy(a.view(np.uint8).copy()).to(dev) if m else None
+            pd = torch.from_numpy(pos.view(np.int64)).to(dev) if m else None
+            rows = torch.zeros((max(m, 1), 6), dtype=torch.int32, device=dev)
+            if m:
+                capi.check(capi.lib().slamem_pileup_rows_at_device(self._h, _ptr(pd), m, _ptr(rows), _stream_handle(dev)))
+            capi.check(capi.lib().slamem_pileup_genotype_events_device(self._h, _ptr(ed) if m else None, _ptr(rows) if m else None, m,
+                                                                       C.byref(params), _ptr(gts) if m else None,
+                                                                       _ptr(called) if m else None, _stream_handle(dev)))
+            torch.cuda.current_stream(dev).synchronize()
+        return gts[:m * GENOTYPE_DTYPE.itemsize].cpu().numpy().view(GENOTYPE_DTYPE).copy(), called[:m].cpu().numpy()
 
     def consensus(self, min_depth: int = 4, first: int = 0, count=None, bounds=None, capacity=None):
         """The consensus sequence of rows [first, first + count), built on the device, as (bytes uint8 (total,),

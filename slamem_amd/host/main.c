@@ -649,6 +649,11 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-depth\tthe depth of coverage A+C+G+T+D of the mapped reads as a bedGraph: record, start, end (0-based, half-open) and the depth of each run of equal depth, the runs of depth 0 included; -mgap, -pen, -xdrop, -maxed, -minq apply; -mdep N: the depth from which a position counts as covered in the summary on stderr (default=1); -lev LIST: comma-separated ascending depths, the value of a run is the number of them it reaches; -win N: instead of the runs the mean depth of every N positions\n");
     printf("\t-dedup\twith -pile, -sites, -vcf, -cons, -depth: reads with the same strand and unclipped 5' position (PCR and optical copies) count once, the first in file order; found on the GPU; one GPU only\n");
     printf("\t-dslots\twith -dedup: slots of its table on the GPU, a power of two of at least 64 (default: at least 65536 and a quarter of the reference)\n");
+    printf("\t-gt\twith -vcf: diploid genotypes called on the GPU from the counts at a constant error rate: one line per site with QUAL, and a sample column GT:DP:AD:GQ:PL; an indel event gets 0/1 or 1/1; -mdep applies, -mpct does not\n");
+    printf("\t-ploidy\twith -gt: 1 or 2 (default=2)\n");
+    printf("\t-err\twith -gt: the error rate of a read letter in Phred, 1 to 93 (default=20)\n");
+    printf("\t-hetq\twith -gt: the prior cost of a non-reference allele in Phred, 0 to 999 (default=30)\n");
+    printf("\t-qual\twith -gt: least QUAL of a call, 0 to 999 (default=20)\n");
     printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
@@ -684,6 +689,8 @@ int main(int argc, char **argv) {
     uint64_t window = 0;
     uint64_t ev_slots = 0;
     int dedup = 0;                              /* -dedup: every batch is added through the duplicate filter */
+    int gt = 0, gt_ploidy = 2, gt_err = 20, gt_hetq = 30, gt_qual = 20; /* -gt: -vcf with genotypes, called on the GPU */
+    slamem_gt_params gtp;
     uint64_t dd_slots = 0;
     slamem_pileup *piles[16];
     double t0;
@@ -766,6 +773,34 @@ int main(int argc, char **argv) {
     default: break;
     }
     if (depth && sites_params == 0) min_depth = 1; /* (-depth: a position is covered when one read shows it) */
+    gt = slh_parse_argument(argc, argv, "GT", 0);
+    switch (slh_parse_gt_params(argc, argv, &gt_ploidy, &gt_err, &gt_hetq, &gt_qual)) {
+    case -1: exit_message("Option -ploidy needs 1 or 2"); break;
+    case -2: exit_message("Option -err needs a whole number from 1 to 93"); break;
+    case -3: exit_message("Option -hetq needs a whole number from 0 to 999"); break;
+    case -4: exit_message("Option -qual needs a whole number from 0 to 999"); break;
+    case 1:
+        if (!gt && slh_parse_argument(argc, argv, "PL", 0)) exit_message("Option -ploidy needs -gt");
+        if (!gt && slh_parse_argument(argc, argv, "ER", 0)) exit_message("Option -err needs -gt");
+        if (!gt && slh_parse_argument(argc, argv, "HE", 0)) exit_message("Option -hetq needs -gt");
+        if (!gt) exit_message("Option -qual needs -gt");
+        break;
+    default: break;
+    }
+    if (gt && !vcf) exit_message("Option -gt needs -vcf");
+    if (gt && slh_parse_argument(argc, argv, "MP", 0)) exit_message("Option -mpct has no meaning with -gt: a call is made when its genotype's quality reaches -qual");
+    memset(&gtp, 0, sizeof(gtp));
+    if (gt) { /* host arithmetic: the three costs of a letter at the error rate of -err */
+        uint32_t costs[3];
+        if (slamem_gt_costs((uint32_t)gt_err, costs) != SLAMEM_OK) exit_message("Option -err needs a whole number from 1 to 93");
+        gtp.ploidy = (uint32_t)gt_ploidy;
+        gtp.match_cost = costs[0];
+        gtp.het_cost = costs[1];
+        gtp.err_cost = costs[2];
+        gtp.het_prior = 1000u * (uint32_t)gt_hetq;
+        gtp.min_depth = (uint32_t)min_depth;
+        gtp.min_qual = (uint32_t)gt_qual;
+    }
     switch (slh_parse_depth_params(argc, argv, levels, &num_levels, &window)) {
     case -1: exit_message("Option -lev needs 1 to 16 whole numbers of at least 1, ascending, separated by commas"); break;
     case -2: exit_message("Option -win needs a whole number of at least 1"); break;
@@ -920,7 +955,8 @@ int main(int argc, char **argv) {
             ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
     if (o.match_type == 8) say(" ; minimum mapping quality = %d", min_mapq);
     if (bq_given == 1) say(" ; minimum base quality = %d", min_bq); /* (only when asked for: the line of a run without -bq stays) */
-    if (sites || vcf) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
+    if (gt) say(" ; minimum depth = %d ; ploidy = %d ; error rate = %d Phred ; prior = %d Phred ; minimum quality = %d", min_depth, gt_ploidy, gt_err, gt_hetq, gt_qual);
+    else if (sites || vcf) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
     if (cons) say(" ; minimum depth = %d", min_depth);
     if (depth) say(" ; covered from depth = %d", min_depth);
     say("\n");
@@ -1301,9 +1337,12 @@ int main(int argc, char **argv) {
             slamem_event *evs = NULL;
             uint64_t *anchors = NULL;
             uint32_t *arows = NULL;
+            slamem_genotype *gts = NULL, *egts = NULL; /* -gt: the genotypes of the rows and of the events, and which events are called */
+            uint8_t *ecalled = NULL;
             int r = 0;
             double tp = now_s();
-            if (vcf && slh_format_vcf_header(&buf, ref.recs, ref.num)) pipeline_fail("Out of memory");
+            if (vcf && (gt ? slh_format_vcf_gt_header(&buf, ref.recs, ref.num) : slh_format_vcf_header(&buf, ref.recs, ref.num)))
+                pipeline_fail("Out of memory");
             if (g_nstreams > 1) {
                 rows = (uint32_t *)slh_big_malloc((size_t)(chunk < n ? chunk : n) * 24 + 24);
                 if (!rows) pipeline_fail("Out of memory");
@@ -1342,12 +1381,15 @@ int main(int argc, char **argv) {
                         pos = (uint64_t *)malloc((size_t)cap * 8);
                         rows = (uint32_t *)malloc((size_t)cap * 24);
                         alleles = (uint8_t *)malloc((size_t)cap);
-                        if (!pos || !rows || !alleles) pipeline_fail("Out of memory");
+                        if (gt) gts = (slamem_genotype *)malloc((size_t)cap * sizeof(slamem_genotype));
+                        if (!pos || !rows || !alleles || (gt && !gts)) pipeline_fail("Out of memory");
                     }
-                    rc = slamem_pileup_sites_host(piles[0], x0, cnt, SLAMEM_SITES_VARIANT, (uint32_t)min_depth, (uint32_t)min_pct, cap, pos,
-                                                  rows, alleles, &total);
+                    rc = gt ? slamem_pileup_genotypes_host(piles[0], x0, cnt, &gtp, cap, pos, rows, gts, &total)
+                            : slamem_pileup_sites_host(piles[0], x0, cnt, SLAMEM_SITES_VARIANT, (uint32_t)min_depth, (uint32_t)min_pct, cap, pos,
+                                                       rows, alleles, &total);
                     if (rc != SLAMEM_ERR_CAPACITY || total <= cap) break;
-                    free(pos); free(rows); free(alleles);
+                    free(pos); free(rows); free(alleles); free(gts);
+                    gts = NULL;
                     pos = NULL;
                     cap = total;
                 }
@@ -1366,10 +1408,15 @@ int main(int argc, char **argv) {
                             arows = (uint32_t *)malloc((size_t)ecap * 24);
                             if (!anchors || !arows) pipeline_fail("Out of memory");
                         }
+                        if (gt && !egts) {
+                            egts = (slamem_genotype *)malloc((size_t)ecap * sizeof(slamem_genotype));
+                            ecalled = (uint8_t *)malloc((size_t)ecap);
+                            if (!egts || !ecalled) pipeline_fail("Out of memory");
+                        }
                         rc = slamem_pileup_events_host(piles[0], x0, cnt, 1, ecap, evs, sk, &etotal);
                         if (rc != SLAMEM_ERR_CAPACITY || etotal <= ecap) break;
-                        free(evs); free(anchors); free(arows);
-                        evs = NULL; anchors = NULL; arows = NULL;
+                        free(evs); free(anchors); free(arows); free(egts); free(ecalled);
+                        evs = NULL; anchors = NULL; arows = NULL; egts = NULL; ecalled = NULL;
                         ecap = etotal;
                     }
                     if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the indel events from the GPU", rc); }
@@ -1380,6 +1427,10 @@ int main(int argc, char **argv) {
                     }
                     rc = slamem_pileup_rows_at_host(piles[0], anchors, etotal, arows);
                     if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the pileup rows of the indel events from the GPU", rc); }
+                    if (gt) { /* every event on its own against everything else at its anchor, on the GPU */
+                        rc = slamem_pileup_genotype_events_host(piles[0], evs, anchors, etotal, &gtp, egts, ecalled);
+                        if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("genotyping the indel events on the GPU", rc); }
+                    }
                     while ((k < total || ek < etotal) && r < ref.num) {
                         const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, end = start + ref.recs[r].size;
                         uint64_t e = k, ee;
@@ -1387,9 +1438,12 @@ int main(int argc, char **argv) {
                         while (ek < etotal && evs[ek].pos < start) ek++;
                         for (e = k; e < total && pos[e] < end; e++) {}
                         for (ee = ek; ee < etotal && evs[ee].pos < end; ee++) {}
-                        if (slh_format_vcf_rows(&buf, ref.recs[r].name, start, ref.recs[r].size, ref.chars, pos + k, rows + k * 6, alleles + k,
-                                                e - k, (const slh_event *)(evs + ek), arows + ek * 6, ee - ek, (uint32_t)min_depth,
-                                                (uint32_t)min_pct))
+                        if (gt ? slh_format_vcf_gt_rows(&buf, ref.recs[r].name, start, ref.recs[r].size, ref.chars, pos + k, rows + k * 6,
+                                                        (const slh_genotype *)(gts + k), e - k, (const slh_event *)(evs + ek), arows + ek * 6,
+                                                        (const slh_genotype *)(egts + ek), ecalled + ek, ee - ek)
+                               : slh_format_vcf_rows(&buf, ref.recs[r].name, start, ref.recs[r].size, ref.chars, pos + k, rows + k * 6, alleles + k,
+                                                     e - k, (const slh_event *)(evs + ek), arows + ek * 6, ee - ek, (uint32_t)min_depth,
+                                                     (uint32_t)min_pct))
                             pipeline_fail("Out of memory");
                         k = e;
                         ek = ee;
@@ -1544,6 +1598,7 @@ int main(int argc, char **argv) {
             }
             free(pos); free(rows); free(alleles);
             free(evs); free(anchors); free(arows);
+            free(gts); free(egts); free(ecalled);
             if ((vcf || cons) && g_nstreams > 0) {
                 skipped[0] += sk[0]; skipped[1] += sk[1]; skipped[2] += sk[2]; /* (GPU 0's, the merge included) */
                 if (skipped[0] | skipped[1] | skipped[2])

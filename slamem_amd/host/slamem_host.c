@@ -1060,6 +1060,32 @@ int slh_parse_event_slots(int argc, char **argv, uint64_t *out) {
     return 0;
 }
 
+int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, int *hetq_out, int *qual_out) {
+    int i, seen = 0;
+    *ploidy_out = 2;
+    *err_out = 20;
+    *hetq_out = 30;
+    *qual_out = 20;
+    for (i = 1; i < argc; i++) {
+        char *end;
+        long v;
+        /* the two letters "pl", "er", "he" and "qu" decide; each takes the next argument */
+        const int pl = two_letter_option(argv[i], 'p', 'l'), er = two_letter_option(argv[i], 'e', 'r');
+        const int he = two_letter_option(argv[i], 'h', 'e'), qu = two_letter_option(argv[i], 'q', 'u');
+        const int bad = pl ? -1 : er ? -2 : he ? -3 : -4;
+        if (!pl && !er && !he && !qu) continue;
+        if (i == argc - 1) return bad;
+        errno = 0;
+        v = strtol(argv[i + 1], &end, 10);
+        if (errno != 0 || end == argv[i + 1] || *end != '\0') return bad;
+        if (pl ? (v != 1 && v != 2) : er ? (v < 1 || v > 93) : (v < 0 || v > 999)) return bad;
+        *(pl ? ploidy_out : er ? err_out : he ? hetq_out : qual_out) = (int)v;
+        seen = 1;
+        i++;
+    }
+    return seen;
+}
+
 /* -dedup: "de" as -depth, told apart by its third letter as -maxed is from -mam */
 static int is_dedup_option(const char *a) {
     return two_letter_option(a, 'd', 'e') && (a[3] == 'd' || a[3] == 'D');
@@ -1173,6 +1199,8 @@ int slh_parse_options(int argc, char **argv, slh_options *o) {
             else if (two_letter_option(argv[i], 'w', 'i')) i++; /* -win N (of -depth; its -lev LIST begins with l) */
             else if (two_letter_option(argv[i], 'd', 's')) i++; /* -dslots N (of -dedup, which takes none) */
             else if (two_letter_option(argv[i], 'p', 'e') || two_letter_option(argv[i], 'x', 'd')) i++; /* -pen N, -xdrop N (of -ext) */
+            else if (two_letter_option(argv[i], 'p', 'l') || two_letter_option(argv[i], 'e', 'r') || two_letter_option(argv[i], 'h', 'e') ||
+                     two_letter_option(argv[i], 'q', 'u')) i++; /* -ploidy N, -err Q, -hetq N, -qual N (of -gt, which takes none) */
             else if (oc == 'r') {
                 i++;
                 if (i == argc) break;
@@ -1614,6 +1642,180 @@ int slh_format_vcf_rows(slh_buffer *buf, const char *record_name, uint64_t recor
             p = put_u32(p + 4, ev->fwd);
             memcpy(p, ";SR=", 4);
             p = put_u32(p + 4, ev->rev);
+            *p++ = '\n';
+            buf->len = (size_t)(p - buf->data);
+        }
+    }
+    return 0;
+}
+
+/* ---- -vcf -gt ---- */
+
+int slh_format_vcf_gt_header(slh_buffer *buf, const slh_record *refs, int num_refs) {
+    static const char *const TAIL =
+        "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Depth A+C+G+T+D at the row (SNV) or at the anchor row (indel)\">\n"
+        "##INFO=<ID=AO,Number=A,Type=Integer,Description=\"Observations of each alternate allele\">\n"
+        "##INFO=<ID=SF,Number=1,Type=Integer,Description=\"Observations of the alternate allele on forward-strand reads\">\n"
+        "##INFO=<ID=SR,Number=1,Type=Integer,Description=\"Observations of the alternate allele on reverse-strand reads\">\n"
+        "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+        "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Depth A+C+G+T+D at the row (SNV) or at the anchor row (indel)\">\n"
+        "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Observations of the reference and of each alternate allele\">\n"
+        "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the Phred-scaled distance to the second-best genotype, at most 99\">\n"
+        "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, the smallest 0\">\n"
+        "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n";
+    static const char *const FIRST = "##fileformat=VCFv4.2\n";
+    int r;
+    char *p;
+    if (buf_reserve(buf, strlen(FIRST))) return -1;
+    memcpy(buf->data + buf->len, FIRST, strlen(FIRST));
+    buf->len += strlen(FIRST);
+    for (r = 0; r < num_refs; r++) {
+        size_t nl = cut_name_len(refs[r].name);
+        if (buf_reserve(buf, nl + 48)) return -1;
+        p = buf->data + buf->len;
+        memcpy(p, "##contig=<ID=", 13);
+        p += 13;
+        memcpy(p, refs[r].name, nl);
+        p += nl;
+        memcpy(p, ",length=", 8);
+        p += 8;
+        p = put_u32(p, refs[r].size);
+        *p++ = '>';
+        *p++ = '\n';
+        buf->len = (size_t)(p - buf->data);
+    }
+    if (buf_reserve(buf, strlen(TAIL))) return -1;
+    memcpy(buf->data + buf->len, TAIL, strlen(TAIL));
+    buf->len += strlen(TAIL);
+    return 0;
+}
+
+/* "\tGT:DP:AD:GQ:PL\t" and the sample's values: alleles[0 .. na) are what a and b may be (REF first; na <= 3), ad their counts */
+static char *vcf_gt_sample(char *p, const slh_genotype *g, const uint8_t *alleles, int na, uint64_t dp, const uint64_t *ad) {
+    int ia = 0, ib = 0, j, k, nv = 0;
+    uint32_t vals[6], low;
+    uint64_t gq = ((uint64_t)g->gq + 500) / 1000;
+    for (j = 0; j < na; j++) {
+        if (alleles[j] == g->a) ia = j;
+        if (alleles[j] == g->b) ib = j;
+    }
+    if (ia > ib) { j = ia; ia = ib; ib = j; }
+    memcpy(p, "\tGT:DP:AD:GQ:PL\t", 16);
+    p = put_u32(p + 16, (uint32_t)ia);
+    if (g->ploidy == 2) {
+        *p++ = '/';
+        p = put_u32(p, (uint32_t)ib);
+        for (k = 0; k < na; k++)
+            for (j = 0; j <= k; j++) { /* VCF order over the allele numbers; the record's pl is indexed by the pair behind them */
+                const uint32_t lo = alleles[j] < alleles[k] ? alleles[j] : alleles[k], hi = alleles[j] < alleles[k] ? alleles[k] : alleles[j];
+                vals[nv++] = g->pl[hi * (hi + 1) / 2 + lo];
+            }
+    } else {
+        for (j = 0; j < na; j++) vals[nv++] = g->pl[alleles[j]];
+    }
+    *p++ = ':';
+    p = vcf_put_u64(p, dp);
+    for (j = 0; j < na; j++) {
+        *p++ = j ? ',' : ':';
+        p = vcf_put_u64(p, ad[j]);
+    }
+    *p++ = ':';
+    p = put_u32(p, gq > 99 ? 99u : (uint32_t)gq);
+    low = vals[0];
+    for (j = 1; j < nv; j++)
+        if (vals[j] < low) low = vals[j];
+    for (j = 0; j < nv; j++) {
+        *p++ = j ? ',' : ':';
+        p = put_u32(p, (uint32_t)(((uint64_t)(vals[j] - low) + 500) / 1000));
+    }
+    return p;
+}
+
+int slh_format_vcf_gt_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                           const uint64_t *site_pos, const uint32_t *site_counts, const slh_genotype *site_gts, uint64_t sites,
+                           const slh_event *events, const uint32_t *anchor_rows, const slh_genotype *event_gts, const uint8_t *called,
+                           uint64_t num_events) {
+    const size_t nl = cut_name_len(record_name);
+    const uint64_t record_end = record_start + record_size;
+    uint64_t i = 0, e = 0;
+    while (i < sites || e < num_events) {
+        uint64_t spos = i < sites ? site_pos[i] - record_start + 1 : ~0ull, epos = ~0ull;
+        char *p;
+        int k;
+        if (e < num_events) epos = events[e].pos > record_start ? events[e].pos - record_start : 1;
+        if (spos <= epos) { /* the row's one line: REF, the best genotype's other letters, and the sample */
+            const uint32_t *c = site_counts + 6 * i;
+            const slh_genotype *g = &site_gts[i];
+            const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4];
+            uint8_t alleles[3];
+            uint64_t ad[3];
+            int na = 1;
+            alleles[0] = (uint8_t)(g->ref & 3);
+            if (g->a != alleles[0]) alleles[na++] = (uint8_t)(g->a & 3);
+            if (g->b != alleles[0] && g->b != g->a) alleles[na++] = (uint8_t)(g->b & 3);
+            for (k = 0; k < na; k++) ad[k] = c[alleles[k]];
+            if (buf_reserve(buf, nl + 320)) return -1;
+            p = vcf_line_head(buf->data + buf->len, record_name, nl, (uint32_t)spos);
+            *p++ = upper_letter(text[site_pos[i]]);
+            for (k = 1; k < na; k++) {
+                *p++ = k == 1 ? '\t' : ',';
+                *p++ = "ACGT"[alleles[k]];
+            }
+            if (na == 1) { *p++ = '\t'; *p++ = '.'; } /* (never from the engine: a selected row's best genotype is not rr) */
+            *p++ = '\t';
+            p = vcf_put_u64(p, ((uint64_t)g->qual + 500) / 1000);
+            memcpy(p, "\t.\tDP=", 6);
+            p = vcf_put_u64(p + 6, d);
+            memcpy(p, ";AO=", 4);
+            p += 4;
+            for (k = 1; k < na; k++) {
+                if (k > 1) *p++ = ',';
+                p = vcf_put_u64(p, ad[k]);
+            }
+            p = vcf_gt_sample(p, g, alleles, na, d, ad);
+            *p++ = '\n';
+            buf->len = (size_t)(p - buf->data);
+            i++;
+        } else {
+            static const uint8_t ZERO_ONE[2] = {0, 1};
+            const slh_event *ev = &events[e];
+            const slh_genotype *g = &event_gts[e];
+            const uint32_t *c = anchor_rows + 6 * e;
+            const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4], ao = (uint64_t)ev->fwd + ev->rev;
+            const uint64_t pos = ev->pos, len = ev->len;
+            const int first = pos == record_start, is_called = called[e] != 0;
+            uint64_t j, ad[2];
+            e++;
+            if (!is_called) continue;
+            if (ev->kind == 0 && first && pos + len >= record_end) continue; /* (the record ends with the deletion: no following base) */
+            if (buf_reserve(buf, nl + 480)) return -1;
+            p = vcf_line_head(buf->data + buf->len, record_name, nl, (uint32_t)epos);
+            if (ev->kind == 0) { /* REF: the anchor and the deleted rows, ALT: the anchor (behind the rows at a record's start) */
+                const uint64_t from = first ? pos : pos - 1;
+                for (j = 0; j <= len; j++) *p++ = upper_letter(text[from + j]);
+                *p++ = '\t';
+                *p++ = upper_letter(text[first ? pos + len : pos - 1]);
+            } else { /* REF: the anchor, ALT: the anchor and the inserted letters (in front of it at a record's start) */
+                const char anchor = upper_letter(text[first ? pos : pos - 1]);
+                *p++ = anchor;
+                *p++ = '\t';
+                if (!first) *p++ = anchor;
+                for (j = 0; j < len; j++) *p++ = "ACGT"[(ev->letters >> (2 * (len - 1 - j))) & 3];
+                if (first) *p++ = anchor;
+            }
+            *p++ = '\t';
+            p = vcf_put_u64(p, ((uint64_t)g->qual + 500) / 1000);
+            memcpy(p, "\t.\tDP=", 6);
+            p = vcf_put_u64(p + 6, d);
+            memcpy(p, ";AO=", 4);
+            p = vcf_put_u64(p + 4, ao);
+            memcpy(p, ";SF=", 4);
+            p = put_u32(p + 4, ev->fwd);
+            memcpy(p, ";SR=", 4);
+            p = put_u32(p + 4, ev->rev);
+            ad[0] = d > ao ? d - ao : 0;
+            ad[1] = ao;
+            p = vcf_gt_sample(p, g, ZERO_ONE, 2, d, ad);
             *p++ = '\n';
             buf->len = (size_t)(p - buf->data);
         }

@@ -216,6 +216,31 @@ int slh_format_vcf_rows(slh_buffer *buf, const char *record_name, uint64_t recor
                         const uint64_t *site_pos, const uint32_t *site_counts, const uint8_t *site_alleles, uint64_t sites,
                         const slh_event *events, const uint32_t *anchor_rows, uint64_t num_events, uint32_t min_depth,
                         uint32_t min_pct);
+/* -vcf -gt.  A genotype as the engine writes it (the layout of slamem_genotype): scores in milli-Phred, a <= b
+ * letter columns (SNV) or allele numbers 0 / 1 (event), pl by genotype number. */
+typedef struct {
+    uint32_t qual, gq;
+    uint8_t a, b, ploidy, ref;
+    uint32_t pl[10];
+    uint8_t pad[4];
+} slh_genotype;
+/* The head of the -vcf -gt file: that of -vcf with AO as Number=A, the ##FORMAT lines of GT, DP, AD, GQ and PL, and the columns
+ * FORMAT and sample behind INFO. */
+int slh_format_vcf_gt_header(slh_buffer *buf, const slh_record *refs, int num_refs);
+/* Lines of the -vcf -gt file for one record: a line per given site (the rows slamem_pileup_genotypes_* selected) -- ALT the best
+ * genotype's letters other than the reference's, ascending; QUAL (qual + 500) / 1000; DP=depth;AO= the ALT counts; the sample
+ * column GT:DP:AD:GQ:PL with the alleles numbered over REF, ALT, joined by / (one number at ploidy 1), GQ at most 99, PL the
+ * line's genotypes in VCF order minus their own minimum, rounded as QUAL is -- and a line per given event whose called[e] is
+ * not 0: the line of slh_format_vcf_rows with QUAL and the sample column (AD = ro, ao).  Order and the rule at a record's end as
+ * there. */
+int slh_format_vcf_gt_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                           const uint64_t *site_pos, const uint32_t *site_counts, const slh_genotype *site_gts, uint64_t sites,
+                           const slh_event *events, const uint32_t *anchor_rows, const slh_genotype *event_gts, const uint8_t *called,
+                           uint64_t num_events);
+/* -ploidy 1|2 (-pl...), -err Q in [1, 93] (-er...), -hetq N in [0, 999] (-he...) and -qual N in [0, 999] (-qu...) of -gt.  0 when
+ * none is there (the defaults 2, 20, 30, 20 in the four outputs), else 1; -1, -2, -3, -4 when the value of -ploidy, -err, -hetq,
+ * -qual is missing, not an integer or out of range.  No value is ever taken for a file name. */
+int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, int *hetq_out, int *qual_out);
 /* -cons: one FASTA record -- '>' and the record's name up to its first blank or tab, then `len` letters in lines of 60; a record
  * of no letters is its header line alone */
 int slh_format_fasta_record(slh_buffer *buf, const char *record_name, const char *letters, uint64_t len);
