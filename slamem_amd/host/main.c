@@ -18,6 +18,8 @@
  * HBM and pinned memory behind the caller's back (0.3-0.4 s for the reference-sized run); never use it under a profiler
  * (the fork would follow the profiler's GPU initialisation).  SLAMEM_WAIT_HBM_S (default 30): how long start-up waits
  * for the HBM the index needs to become free (the tail of such a detached worker, or any other job) before it builds.
+ * SLAMEM_READOUT_ROWS (a test knob; default 16 Mi, at least 64): the rows of the pileup that a read-out takes from the GPU at a
+ * time, so that a test can make the records of a small reference cross the borders of these ranges.
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -195,22 +197,27 @@ static void gpu_fail_msg(const char *what, int rc, const char *detail) { /* the 
     exit(-1);
 }
 
-/* formatting of a range of strand blocks of one batch, one range per thread */
+/* What a batch's search handed back, and whose reads they are: everything the formatters of a strand block read. */
 typedef struct {
-    const slh_seqset *q;
-    const slh_seqset *ref;
+    const slh_seqset *q, *ref;
+    const char *quals;       /* -sam: the quality bytes of the set, indexed as its letters (NULL: FASTA) */
     const slamem_mem *mems;
-    const uint32_t *mism; /* -ext: a fourth column, the mismatches of each row (NULL otherwise) */
-    const slamem_aln *segs; /* -aln: the segments in the place of the rows (NULL otherwise), their operations and offsets */
+    const uint32_t *mism;    /* -ext: a fourth column, the mismatches of each row (NULL otherwise) */
+    const slamem_aln *segs;  /* -aln: the segments in the place of the rows (NULL otherwise), their operations and offsets */
     const uint32_t *ops;
     const uint64_t *ooff;
     const slamem_map *reads; /* -paf: a record per read (NULL otherwise); the blocks are then the reads, strands = 1 */
     const uint32_t *md;      /* -sam: the MD entries of the batch's segments, their offsets per segment, the primary segment per read */
     const uint64_t *mdoff;   /*       (NULL otherwise) */
     const uint32_t *prim;
-    const char *quals;       /* -sam: the quality bytes of the set, indexed as its letters (NULL: FASTA) */
     const uint64_t *boff;
+    uint64_t total;
     int first_rec, strands;
+} batch_view;
+
+/* formatting of a range of strand blocks of one batch, one range per thread */
+typedef struct {
+    const batch_view *v;
     uint64_t b0, b1; /* strand blocks [b0,b1) of the batch */
     slh_buffer buf;
     long long matches, sum;
@@ -242,45 +249,57 @@ static void pool_get(slh_buffer *b, size_t need) {
     pthread_mutex_unlock(&g_pool_mu);
 }
 
-/* a read of the -sam file: read b of the batch is record i of its set */
-static int format_sam_read(slh_buffer *buf, const slh_seqset *q, const char *quals, int i, uint64_t b, const slamem_map *reads,
-                           const slamem_aln *segs, const uint32_t *ops, const uint64_t *ooff, const uint64_t *boff, const uint32_t *md,
-                           const uint64_t *mdoff, const uint32_t *prim, const slh_seqset *ref, uint64_t *sum) {
-    return slh_format_read_sam(buf, q->recs[i].name, q->chars + q->offsets[i], quals ? quals + q->offsets[i] : NULL,
-                               (uint32_t)(q->offsets[i + 1] - q->offsets[i]), reads[b].strand, reads[b].mapq, reads[b].s1, reads[b].s2,
-                               (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b], md, mdoff + boff[b], prim[b],
-                               boff[b + 1] - boff[b], ref->recs, ref->merged_start, ref->num, sum);
+/* strand block b of a batch in the format of its mode: read b / strands of the batch is record i of its set */
+static int format_block(const batch_view *v, uint64_t b, slh_buffer *buf, uint64_t *cnt, uint64_t *sum) {
+    const int i = v->first_rec + (int)(b / (uint64_t)v->strands), s = (int)(b % (uint64_t)v->strands);
+    const slh_seqset *q = v->q, *ref = v->ref;
+    const uint64_t o = v->boff[b];
+    *cnt = v->boff[b + 1] - o;
+    *sum = 0;
+    if (v->md)
+        return slh_format_read_sam(buf, q->recs[i].name, q->chars + q->offsets[i], v->quals ? v->quals + q->offsets[i] : NULL,
+                                   (uint32_t)(q->offsets[i + 1] - q->offsets[i]), v->reads[b].strand, v->reads[b].mapq, v->reads[b].s1,
+                                   v->reads[b].s2, (const uint32_t *)(v->segs + o), v->ops, v->ooff + o, v->md, v->mdoff + o, v->prim[b],
+                                   *cnt, ref->recs, ref->merged_start, ref->num, sum);
+    if (v->reads)
+        return slh_format_read_paf(buf, q->recs[i].name, q->recs[i].size, v->reads[b].strand, v->reads[b].mapq, v->reads[b].s1,
+                                   v->reads[b].s2, (const uint32_t *)(v->segs + o), v->ops, v->ooff + o, *cnt, ref->recs,
+                                   ref->merged_start, ref->num, sum);
+    if (v->segs)
+        return slh_format_block_aln(buf, q->recs[i].name, s, (const uint32_t *)(v->segs + o), v->ops, v->ooff + o, *cnt, ref->recs,
+                                    ref->merged_start, ref->num, sum);
+    return slh_format_block_ext(buf, q->recs[i].name, s, (const uint32_t *)(v->mems + o), v->mism ? v->mism + o : NULL, *cnt,
+                                ref->recs, ref->merged_start, ref->num, sum);
 }
 
 static void *fmt_run(void *arg) {
     fmt_job *j = (fmt_job *)arg;
+    const uint64_t *boff = j->v->boff;
     uint64_t b;
     j->t_start = now_s();
     /* about 36 characters per MEM line and a header per block: reserve once instead of doubling on the way */
-    const size_t need = (size_t)(j->boff[j->b1] - j->boff[j->b0]) * (j->mism ? 44 : 36) + (size_t)(j->b1 - j->b0) * 48 + 4096;
-    pool_get(&j->buf, need);
-    (void)slh_buffer_reserve(&j->buf, need);
-    for (b = j->b0; b < j->b1; b++) {
-        int i = j->first_rec + (int)(b / (uint64_t)j->strands), s = (int)(b % (uint64_t)j->strands);
-        uint64_t cnt = j->boff[b + 1] - j->boff[b], sum = 0;
-        if (j->md ? format_sam_read(&j->buf, j->q, j->quals, i, b, j->reads, j->segs, j->ops, j->ooff, j->boff, j->md, j->mdoff, j->prim,
-                                    j->ref, &sum)
-            : j->reads ? slh_format_read_paf(&j->buf, j->q->recs[i].name, j->q->recs[i].size, j->reads[b].strand, j->reads[b].mapq,
-                                           j->reads[b].s1, j->reads[b].s2, (const uint32_t *)(j->segs + j->boff[b]), j->ops,
-                                           j->ooff + j->boff[b], cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)
-            : j->segs ? slh_format_block_aln(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->segs + j->boff[b]), j->ops,
-                                           j->ooff + j->boff[b], cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)
-                    : slh_format_block_ext(&j->buf, j->q->recs[i].name, s, (const uint32_t *)(j->mems + j->boff[b]),
-                                 j->mism ? j->mism + j->boff[b] : NULL, cnt, j->ref->recs, j->ref->merged_start, j->ref->num, &sum)) {
-            j->failed = 1;
-            return NULL;
-        }
-        j->matches += (long long)cnt;
-        j->sum += (long long)sum;
+    const size_t need = (size_t)(boff[j->b1] - boff[j->b0]) * (j->v->mism ? 44 : 36) + (size_t)(j->b1 - j->b0) * 48 + 4096;
+    /* the buffer's head and the sums stay on this thread's stack while it works: the jobs lie side by side in one array, and
+       a write per strand block into it would share cache lines with the threads that work on the neighbours */
+    slh_buffer buf = {0, 0, 0};
+    long long matches = 0, total = 0;
+    pool_get(&buf, need);
+    (void)slh_buffer_reserve(&buf, need);
+    int failed = 0;
+    for (b = j->b0; b < j->b1 && !failed; b++) {
+        uint64_t cnt, sum;
+        failed = format_block(j->v, b, &buf, &cnt, &sum) != 0;
+        matches += (long long)cnt;
+        total += (long long)sum;
     }
+    j->failed = failed;
+    j->buf = buf;
+    j->matches = matches;
+    j->sum = total;
     j->t_end = now_s();
     return NULL;
 }
+
 
 /* the formatter threads of a batch take its chunks (ranges of strand blocks) from a shared counter: equal shares per
  * thread left the batch waiting for its slowest thread (measured: twice the mean, on a box whose CPU share is smaller
@@ -668,1056 +687,1033 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t%s -v ./ref-mems.txt ./ref.fna ./query.fna\n", prog);
 }
 
-int main(int argc, char **argv) {
-    slh_options o;
+/* ------------------------------------------------------------------------------------------------ */
+/* the run: one context, and main() as the list of its stages                                        */
+/* ------------------------------------------------------------------------------------------------ */
+
+typedef struct { int f, first, last; } batch_range; /* records [first,last) of query set f */
+#define STREAM_SLOTS 6 /* upload, prepare, search and download of four batches beside the one being formatted */
+
+typedef struct {
+    int argc;
+    char **argv;
+    slh_run p;            /* what the command line says */
+    slamem_gt_params gtp; /* -gt: the costs behind p.gt_* */
+    int device, timing;
+    long log_limit;
+    uint64_t batch_bytes;  /* query characters per batch and GPU */
+    long piece_bytes;      /* bytes of a query file per piece of the loader thread */
+    uint64_t readout_rows; /* rows of the pileup per range of a read-out */
     slh_seqset ref, *qsets;
-    int i, f, total_queries = 0, device = 0, numbering = 1;
-    long log_limit = 100;
-    uint64_t batch_bytes = 256ull << 20; /* query characters per batch and GPU */
-    long piece_bytes = 128L << 20;       /* bytes of a query file per piece of the loader thread */
-    const char *env;
-    char *out_name;
-    FILE *out;
-    slamem_index *idx = NULL, *gpus[16];
-    int rc, ngpu = 1, max_occ = 0, max_gap = 0, ext_pen = 0, ext_xdrop = -1, max_edits = -1, min_mapq = 0, min_bq = 0, bq_given = 0;
-    int sites = 0, min_depth = 4, min_pct = 20; /* -sites: match type 8 with the sparse read-out */
-    int vcf = 0;                                /* -vcf: match type 8 with the events enabled, written as VCF */
-    int cons = 0;                               /* -cons: match type 8 with the events enabled, the consensus written as FASTA */
-    int sam = 0;                                /* -sam: match type 7 with the MD pass, written as SAM */
-    int depth = 0, num_levels = 0, sites_params; /* -depth: match type 8, the runs of the depth written as a bedGraph */
-    uint32_t levels[16];
-    uint64_t window = 0;
-    uint64_t ev_slots = 0;
-    int dedup = 0;                              /* -dedup: every batch is added through the duplicate filter */
-    int gt = 0, gt_ploidy = 2, gt_err = 20, gt_hetq = 30, gt_qual = 20; /* -gt: -vcf with genotypes, called on the GPU */
-    slamem_gt_params gtp;
-    uint64_t dd_slots = 0;
-    slamem_pileup *piles[16];
-    double t0;
-    long long total_matches = 0, total_sum = 0;
-    slh_buffer buf = {0, 0, 0};
+    loader_t *ld;
+    int overlap; /* the loader thread parses beside the search */
     build_job bj;
     pthread_t build_tid;
-    int build_async = 0;
+    int build_async;
+    char *out_name;
+    FILE *out;
+    slamem_index *gpus[16];
+    int ngpu;
+    slamem_pileup *piles[16];
+    int strands; /* strand blocks per read */
+    batch_range *ranges;
+    size_t nranges, cap_ranges;
+    uint64_t max_chars;
+    uint32_t max_recs;
+    int sets_seen, inflight[16];
+    long printed; /* strand blocks that got their line on stdout */
+    slh_buffer buf;
+    slh_piece *pcs; /* the record pieces of a read-out's range (room for every record) */
+    uint64_t skipped[3]; /* -vcf, -cons: indel observations that are in no event */
+    int total_queries;
+    long long total_matches, total_sum;
+    double t_start, t_load, t_build, t_join, t_streams, t_gpu, t_format, t_wait_load;
+} run_t;
 
-    printf("[ slaMEM v%s ]\n\n", VERSION);
-    if (slh_parse_options(argc, argv, &o) != 0) exit_message("Out of memory");
-    if (o.usage) { usage(argv[0]); slh_free_options(&o); return -1; }
-    if (o.hidden_sort) { /* slamem.c:555-562 */
-        slh_free_options(&o);
-        if (argc != 3) { printf("Usage: %s -s <mems_file>\n\n", argv[0]); return -1; }
-        return slh_sort_mems_file(argv[2], stdout);
+static void pipeline_gpu_fail(const char *what, int rc) {
+    shutdown_pipeline();
+    gpu_fail(what, rc);
+}
+
+static void push_text(run_t *R) { /* what a stage has formatted goes to the writer */
+    if (writer_push(&g_writer, &R->buf)) pipeline_fail("Out of memory");
+    if (g_writer.failed) pipeline_fail("Cannot write output file");
+}
+
+/* Parse and refuse, before any GPU work.  Returns 1 when the command ends here with *status: the usage text and the tools
+ * that need no GPU (-s, -c, -v). */
+static int parse_and_refuse(run_t *R, int *status) {
+    slh_options *o = &R->p.o;
+    const char *refusal, *env;
+    const int argc = R->argc, rc = slh_parse_run(R->argc, R->argv, &R->p, &refusal);
+    char **argv = R->argv;
+    if (o->usage) { usage(argv[0]); slh_free_options(o); *status = -1; return 1; }
+    if (o->hidden_sort) { /* slamem.c:555-562 */
+        slh_free_options(o);
+        if (argc != 3) { printf("Usage: %s -s <mems_file>\n\n", argv[0]); *status = -1; return 1; }
+        *status = slh_sort_mems_file(argv[2], stdout);
+        return 1;
     }
-    if (o.hidden_clean) { /* slamem.c:563-570 */
-        slh_free_options(&o);
-        if (argc != 3) { printf("Usage: %s -c <fasta_file>\n\n", argv[0]); return -1; }
-        return slh_clean_fasta(argv[2], stdout);
+    if (o->hidden_clean) { /* slamem.c:563-570 */
+        slh_free_options(o);
+        if (argc != 3) { printf("Usage: %s -c <fasta_file>\n\n", argv[0]); *status = -1; return 1; }
+        *status = slh_clean_fasta(argv[2], stdout);
+        return 1;
     }
-    sites = slh_parse_argument(argc, argv, "SI", 0);
-    vcf = slh_parse_argument(argc, argv, "VC", 0);
-    cons = slh_parse_argument(argc, argv, "CO", 0);
-    depth = slh_parse_depth(argc, argv);
-    sam = slh_parse_argument(argc, argv, "SA", 0);
-    if (o.match_type < 0) { /* before any GPU work */
-        if (sam) exit_message("Option -sam excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites, -vcf, -cons and -depth");
-        if (depth) exit_message("Option -depth excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites, -vcf and -cons");
-        if (cons) exit_message("Option -cons excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites and -vcf");
-        if (vcf) exit_message("Option -vcf excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile and -sites");
-        if (sites) exit_message("Option -sites excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf and -pile");
-        if (slh_parse_argument(argc, argv, "PI", 0)) exit_message("Option -pile excludes -mam, -mum, -smem, -chain, -ext, -aln and -paf");
-        if (slh_parse_argument(argc, argv, "PA", 0)) exit_message("Option -paf excludes -mam, -mum, -smem, -chain, -ext and -aln");
-        if (slh_parse_argument(argc, argv, "AL", 0)) exit_message("Option -aln excludes -mam, -mum, -smem, -chain and -ext");
-        if (slh_parse_argument(argc, argv, "EX", 0)) exit_message("Option -ext excludes -mam, -mum, -smem and -chain");
-        if (slh_parse_argument(argc, argv, "CH", 0)) exit_message("Option -chain excludes -mam, -mum and -smem");
-        if (slh_parse_argument(argc, argv, "SM", 0)) exit_message("Option -smem excludes -mam and -mum");
-        exit_message("Options -mam and -mum exclude each other");
-    }
-    switch (slh_parse_max_occ(argc, argv, &max_occ)) {
-    case -1: exit_message("Option -occ needs a whole number of at least 1"); break;
-    case 1: if (o.match_type != 3) exit_message("Option -occ needs -smem"); break;
-    default: break;
-    }
-    switch (slh_parse_max_gap(argc, argv, &max_gap)) {
-    case -1: exit_message("Option -mgap needs a whole number of at least 1"); break;
-    case 1: if (o.match_type != 4 && o.match_type != 6 && o.match_type != 7 && o.match_type != 8) exit_message("Option -mgap needs -chain"); break;
-    default: break;
-    }
-    switch (slh_parse_ext_params(argc, argv, &ext_pen, &ext_xdrop)) {
-    case -1: exit_message("Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"); break;
-    case 1: if (o.match_type != 5 && o.match_type != 6 && o.match_type != 7 && o.match_type != 8) exit_message("Options -pen and -xdrop need -ext"); break;
-    default: break;
-    }
-    switch (slh_parse_max_edits(argc, argv, &max_edits)) {
-    case -1: exit_message("Option -maxed needs a whole number from 0 to 127"); break;
-    case 1: if (o.match_type != 6 && o.match_type != 7 && o.match_type != 8) exit_message("Option -maxed needs -aln"); break;
-    default: break;
-    }
-    switch (slh_parse_min_mapq(argc, argv, &min_mapq)) {
-    case -1: exit_message("Option -minq needs a whole number from 0 to 60"); break;
-    case 1: if (o.match_type != 8) exit_message("Option -minq needs -pile"); break;
-    default: break;
-    }
-    switch ((bq_given = slh_parse_min_bq(argc, argv, &min_bq))) {
-    case -1: exit_message("Option -bq needs a whole number from 0 to 93"); break;
-    case 1: if (o.match_type != 8) exit_message("Option -bq needs -pile"); break;
-    default: break;
-    }
-    switch ((sites_params = slh_parse_sites_params(argc, argv, &min_depth, &min_pct))) {
-    case -1: exit_message("Option -mdep needs a whole number of at least 1"); break;
-    case -2: exit_message("Option -mpct needs a whole number from 0 to 100"); break;
-    case 1:
-        if (cons && slh_parse_argument(argc, argv, "MP", 0)) exit_message("Option -mpct has no meaning with -cons: an allele is applied when more than half of the depth shows it");
-        if (depth && slh_parse_argument(argc, argv, "MP", 0)) exit_message("Option -mpct has no meaning with -depth: the depth is written as it is");
-        if (!sites && !vcf && !cons && !depth) exit_message("Options -mdep and -mpct need -sites");
-        break;
-    default: break;
-    }
-    if (depth && sites_params == 0) min_depth = 1; /* (-depth: a position is covered when one read shows it) */
-    gt = slh_parse_argument(argc, argv, "GT", 0);
-    switch (slh_parse_gt_params(argc, argv, &gt_ploidy, &gt_err, &gt_hetq, &gt_qual)) {
-    case -1: exit_message("Option -ploidy needs 1 or 2"); break;
-    case -2: exit_message("Option -err needs a whole number from 1 to 93"); break;
-    case -3: exit_message("Option -hetq needs a whole number from 0 to 999"); break;
-    case -4: exit_message("Option -qual needs a whole number from 0 to 999"); break;
-    case 1:
-        if (!gt && slh_parse_argument(argc, argv, "PL", 0)) exit_message("Option -ploidy needs -gt");
-        if (!gt && slh_parse_argument(argc, argv, "ER", 0)) exit_message("Option -err needs -gt");
-        if (!gt && slh_parse_argument(argc, argv, "HE", 0)) exit_message("Option -hetq needs -gt");
-        if (!gt) exit_message("Option -qual needs -gt");
-        break;
-    default: break;
-    }
-    if (gt && !vcf) exit_message("Option -gt needs -vcf");
-    if (gt && slh_parse_argument(argc, argv, "MP", 0)) exit_message("Option -mpct has no meaning with -gt: a call is made when its genotype's quality reaches -qual");
-    memset(&gtp, 0, sizeof(gtp));
-    if (gt) { /* host arithmetic: the three costs of a letter at the error rate of -err */
+    if (rc == -1) exit_message(refusal);
+    memset(&R->gtp, 0, sizeof(R->gtp));
+    if (R->p.gt) { /* host arithmetic: the three costs of a letter at the error rate of -err */
         uint32_t costs[3];
-        if (slamem_gt_costs((uint32_t)gt_err, costs) != SLAMEM_OK) exit_message("Option -err needs a whole number from 1 to 93");
-        gtp.ploidy = (uint32_t)gt_ploidy;
-        gtp.match_cost = costs[0];
-        gtp.het_cost = costs[1];
-        gtp.err_cost = costs[2];
-        gtp.het_prior = 1000u * (uint32_t)gt_hetq;
-        gtp.min_depth = (uint32_t)min_depth;
-        gtp.min_qual = (uint32_t)gt_qual;
+        if (slamem_gt_costs((uint32_t)R->p.gt_err, costs) != SLAMEM_OK) exit_message("Option -err needs a whole number from 1 to 93");
+        R->gtp.ploidy = (uint32_t)R->p.gt_ploidy;
+        R->gtp.match_cost = costs[0];
+        R->gtp.het_cost = costs[1];
+        R->gtp.err_cost = costs[2];
+        R->gtp.het_prior = 1000u * (uint32_t)R->p.gt_hetq;
+        R->gtp.min_depth = (uint32_t)R->p.min_depth;
+        R->gtp.min_qual = (uint32_t)R->p.gt_qual;
     }
-    switch (slh_parse_depth_params(argc, argv, levels, &num_levels, &window)) {
-    case -1: exit_message("Option -lev needs 1 to 16 whole numbers of at least 1, ascending, separated by commas"); break;
-    case -2: exit_message("Option -win needs a whole number of at least 1"); break;
-    case 0: break;
-    case 3:
-        if (depth) exit_message("Options -lev and -win exclude each other");
-        /* fall through */
-    default: if (!depth) exit_message("Options -lev and -win need -depth"); break;
-    }
-    switch (slh_parse_event_slots(argc, argv, &ev_slots)) {
-    case -1: exit_message("Option -evs needs a power of two of at least 64"); break;
-    case 1: if (!vcf && !cons) exit_message("Option -evs needs -vcf"); break;
-    default: break;
-    }
-    switch ((dedup = slh_parse_dedup(argc, argv, &dd_slots))) {
-    case -1: exit_message("Option -dslots needs a power of two of at least 64"); break;
-    case 2: exit_message("Option -dslots needs -dedup"); break;
-    case 0: break;
-    default:
-        if (o.match_type != 8) exit_message("Option -dedup needs -pile, -sites, -vcf, -cons or -depth");
-        /* one table per GPU would miss the duplicates whose copies went to different GPUs */
-        if (((env = getenv("SLAMEM_GPUS")) != NULL && atoi(env) != 1) || ((env = getenv("SLAMEM_LOGICAL_GPUS")) != NULL && atoi(env) > 1))
-            exit_message("Option -dedup runs on one GPU: every GPU would keep a table of its own and miss the duplicates whose copies went to different GPUs (leave SLAMEM_GPUS unset, or set it to 1)");
-        dedup = 1;
-        break;
-    }
-    if (o.num_files < 2) exit_message("Not enough input sequence files provided");
-    if (o.ref_name_given && o.ref_name_empty) exit_message("No reference name string provided");
-    if ((env = getenv("SLAMEM_DEVICE")) != NULL) device = atoi(env);
-    if ((env = getenv("SLAMEM_VERBOSE")) != NULL && atoi(env) != 0) log_limit = 0;
-    if (o.image_arg != -1) return image_tool(argc, argv, &o, log_limit); /* slamem.c:652-655; host only, before any GPU call */
-    if ((env = getenv("SLAMEM_BATCH_MB")) != NULL && atoll(env) > 0) batch_bytes = (uint64_t)atoll(env) << 20;
+    /* one table per GPU would miss the duplicates whose copies went to different GPUs */
+    if (R->p.dedup && (((env = getenv("SLAMEM_GPUS")) != NULL && atoi(env) != 1) || ((env = getenv("SLAMEM_LOGICAL_GPUS")) != NULL && atoi(env) > 1)))
+        exit_message("Option -dedup runs on one GPU: every GPU would keep a table of its own and miss the duplicates whose copies went to different GPUs (leave SLAMEM_GPUS unset, or set it to 1)");
+    if (rc != 0) exit_message(refusal);
+    if ((env = getenv("SLAMEM_DEVICE")) != NULL) R->device = atoi(env);
+    if ((env = getenv("SLAMEM_VERBOSE")) != NULL && atoi(env) != 0) R->log_limit = 0;
+    if (o->image_arg != -1) { *status = image_tool(argc, argv, o, R->log_limit); return 1; } /* slamem.c:652-655; host only */
+    if ((env = getenv("SLAMEM_BATCH_MB")) != NULL && atoll(env) > 0) R->batch_bytes = (uint64_t)atoll(env) << 20;
+    if ((env = getenv("SLAMEM_READOUT_ROWS")) != NULL) R->readout_rows = atoll(env) < 64 ? 64 : (uint64_t)atoll(env);
+    R->timing = getenv("SLAMEM_TIMING") != NULL;
+    return 0;
+}
 
-    if (getenv("SLAMEM_FULL_TEARDOWN") == NULL) split_off_worker();
-    {
-        static int warm_device;
-        warm_device = device;
-        g_warm_started = pthread_create(&g_warm_tid, NULL, warmup_run, &warm_device) == 0;
-    }
-    double t_start = now_s(), t_load = 0, t_build = 0, t_gpu = 0, t_format = 0, t_write = 0, t_wait_load = 0;
-    int timing = getenv("SLAMEM_TIMING") != NULL;
-    /* load everything (slamem.c:635-651).  Query files above SLAMEM_OVERLAP_MB (default 256) in total are parsed in pieces by
-       a loader thread while the search already runs; stdout keeps the reference's order: what the main thread prints meanwhile
-       is held back until the "successfully loaded" line can be printed */
-    memset(&ref, 0, sizeof(ref));
-    memset(&bj, 0, sizeof(bj));
-    loader_t *const ld = &g_ld;
-    int overlap = 0, ref_file = -1;
-    {
-        uint64_t qbytes_total = 0, pieces_cap = 0;
-        long thr_mb = 256;
-        if ((env = getenv("SLAMEM_OVERLAP_MB")) != NULL) thr_mb = atol(env);
-        if ((env = getenv("SLAMEM_PIECE_MB")) != NULL && atol(env) > 0) piece_bytes = atol(env) << 20;
-        for (f = 1; f < o.num_files; f++) {
-            FILE *qf = fopen(argv[o.file_args[f]], "rb");
-            if (qf) {
-                long sz;
-                fseek(qf, 0L, SEEK_END);
-                sz = ftell(qf);
-                fclose(qf);
-                if (sz > 0) { qbytes_total += (uint64_t)sz; pieces_cap += (uint64_t)sz / (uint64_t)piece_bytes + 2; }
-            }
+/* Load everything (slamem.c:635-651); the index build starts on its own thread as soon as the reference is there.  Query files
+ * above SLAMEM_OVERLAP_MB (default 256) in total are parsed in pieces by a loader thread while the search already runs; stdout
+ * keeps the reference's order: what the main thread prints meanwhile is held back until the "successfully loaded" line can be
+ * printed. */
+static void load_inputs(run_t *R) {
+    const slh_options *o = &R->p.o;
+    loader_t *const ld = R->ld = &g_ld;
+    uint64_t qbytes_total = 0, pieces_cap = 0;
+    long thr_mb = 256;
+    int f, ref_file = -1, numbering = 1;
+    const char *env;
+    char **argv = R->argv;
+    if ((env = getenv("SLAMEM_OVERLAP_MB")) != NULL) thr_mb = atol(env);
+    if ((env = getenv("SLAMEM_PIECE_MB")) != NULL && atol(env) > 0) R->piece_bytes = atol(env) << 20;
+    for (f = 1; f < o->num_files; f++) {
+        FILE *qf = fopen(argv[o->file_args[f]], "rb");
+        if (qf) {
+            long sz;
+            fseek(qf, 0L, SEEK_END);
+            sz = ftell(qf);
+            fclose(qf);
+            if (sz > 0) { qbytes_total += (uint64_t)sz; pieces_cap += (uint64_t)sz / (uint64_t)R->piece_bytes + 2; }
         }
-        overlap = thr_mb >= 0 && qbytes_total > ((uint64_t)thr_mb << 20);
-        memset(ld, 0, sizeof(*ld));
-        ld->release_early = qbytes_total > ((uint64_t)((env = getenv("SLAMEM_RELEASE_EARLY_GB")) != NULL ? atol(env) : 16) << 30);
-        ld->cap = (int)(overlap ? pieces_cap + (uint64_t)o.num_files : (uint64_t)o.num_files);
-        qsets = (slh_seqset *)calloc((size_t)ld->cap + 1, sizeof(slh_seqset));
-        g_reap_tid = (pthread_t *)calloc((size_t)ld->cap + 1, sizeof(pthread_t));
-        if (!qsets || !g_reap_tid) exit_message("Out of memory");
-        ld->sets = qsets;
-        ld->masks = (uint64_t **)calloc((size_t)ld->cap + 1, sizeof(uint64_t *));
-        if (!ld->masks) exit_message("Out of memory");
-        ld->min_bq = min_bq;
-        ld->keep_quals = sam;
-        ld->quals = (char **)calloc((size_t)ld->cap + 1, sizeof(char *));
-        if (!ld->quals) exit_message("Out of memory");
-        pthread_mutex_init(&ld->mu, NULL);
-        pthread_cond_init(&ld->cv, NULL);
     }
-    for (f = 0; f < o.num_files; f++) {
-        const char *path = argv[o.file_args[f]];
+    R->overlap = thr_mb >= 0 && qbytes_total > ((uint64_t)thr_mb << 20);
+    memset(ld, 0, sizeof(*ld));
+    ld->release_early = qbytes_total > ((uint64_t)((env = getenv("SLAMEM_RELEASE_EARLY_GB")) != NULL ? atol(env) : 16) << 30);
+    ld->cap = (int)(R->overlap ? pieces_cap + (uint64_t)o->num_files : (uint64_t)o->num_files);
+    R->qsets = (slh_seqset *)calloc((size_t)ld->cap + 1, sizeof(slh_seqset));
+    g_reap_tid = (pthread_t *)calloc((size_t)ld->cap + 1, sizeof(pthread_t));
+    if (!R->qsets || !g_reap_tid) exit_message("Out of memory");
+    ld->sets = R->qsets;
+    ld->masks = (uint64_t **)calloc((size_t)ld->cap + 1, sizeof(uint64_t *));
+    if (!ld->masks) exit_message("Out of memory");
+    ld->min_bq = R->p.min_bq;
+    ld->keep_quals = R->p.sam;
+    ld->quals = (char **)calloc((size_t)ld->cap + 1, sizeof(char *));
+    if (!ld->quals) exit_message("Out of memory");
+    pthread_mutex_init(&ld->mu, NULL);
+    pthread_cond_init(&ld->cv, NULL);
+    for (f = 0; f < o->num_files; f++) {
+        const char *path = argv[o->file_args[f]];
         if (ref_file < 0) {
-            int n = slh_load_file_q(path, 1, o.no_ns, (uint32_t)o.min_seq_len, o.ref_name, numbering, log_limit, &ref, NULL, stdout);
+            int n = slh_load_file_q(path, 1, o->no_ns, (uint32_t)o->min_seq_len, o->ref_name, numbering, R->log_limit, &R->ref, NULL, stdout);
             if (n <= 0) exit_message("No valid sequences found in reference file");
             ref_file = f;
             numbering += n;
-            g_num_refs = ref.num;
-            o.file_args[0] = o.file_args[f]; /* remember which argument was the reference */
-            bj.text = ref.chars;
-            bj.n = (uint32_t)ref.total;
-            bj.device = device;
-            build_async = pthread_create(&build_tid, NULL, build_run, &bj) == 0;
-            if (overlap) break;
+            g_num_refs = R->ref.num;
+            o->file_args[0] = o->file_args[f]; /* remember which argument was the reference */
+            R->bj.text = R->ref.chars;
+            R->bj.n = (uint32_t)R->ref.total;
+            R->bj.device = R->device;
+            R->build_async = pthread_create(&R->build_tid, NULL, build_run, &R->bj) == 0;
+            if (R->overlap) break;
         } else {
             char *quals = NULL;
-            int n = slh_load_file_q(path, 0, o.no_ns, (uint32_t)o.min_seq_len, NULL, numbering, log_limit, &qsets[ld->ready], &quals, stdout);
+            int n = slh_load_file_q(path, 0, o->no_ns, (uint32_t)o->min_seq_len, NULL, numbering, R->log_limit, &R->qsets[ld->ready], &quals, stdout);
             if (n < 0) { /* an invalid FASTQ file (the loader said so): before any search */
-                if (build_async) pthread_join(build_tid, NULL);
+                if (R->build_async) pthread_join(R->build_tid, NULL);
                 join_warmup();
                 fflush(stdout);
                 exit(-1);
             }
             if (n != 0) {
                 if (ld->keep_quals) ld->quals[ld->ready] = quals;
-                else ld->masks[ld->ready] = mask_of_quals(ld, &qsets[ld->ready], quals);
+                else ld->masks[ld->ready] = mask_of_quals(ld, &R->qsets[ld->ready], quals);
                 if (ld->invalid) exit_message("Out of memory");
                 numbering += n; ld->total_queries += n; ld->ready++;
             }
         }
     }
-    if (overlap) {
-        ld->argv = argv; ld->file_args = o.file_args; ld->first_file = ref_file + 1; ld->num_files = o.num_files;
-        ld->acgt_only = o.no_ns; ld->min_len = (uint32_t)o.min_seq_len; ld->numbering = numbering; ld->log_limit = log_limit;
-        ld->piece_bytes = piece_bytes;
+    if (R->overlap) {
+        ld->argv = argv; ld->file_args = o->file_args; ld->first_file = ref_file + 1; ld->num_files = o->num_files;
+        ld->acgt_only = o->no_ns; ld->min_len = (uint32_t)o->min_seq_len; ld->numbering = numbering; ld->log_limit = R->log_limit;
+        ld->piece_bytes = R->piece_bytes;
         fflush(stdout);
         g_mo = open_memstream(&g_mo_buf, &g_mo_len);
         g_ld_started = g_mo != NULL && pthread_create(&g_ld_tid, NULL, loader_run, ld) == 0;
         if (!g_ld_started) { /* no thread: load here, as for small inputs */
             if (g_mo) release_stdout();
-            overlap = 0;
+            R->overlap = 0;
             loader_run(ld);
         }
     } else {
         ld->done = 1;
     }
-    t_load = now_s() - t_start;
-    double t_join0 = now_s();
-    if (build_async) pthread_join(build_tid, NULL); /* before any exit: never leave the process with a build in flight */
-    else build_run(&bj);
+    R->t_load = now_s() - R->t_start;
+}
+
+/* the index is there (or failed) and the device is warm before anything else happens: never leave with a build in flight */
+static void join_build(run_t *R) {
+    const double t0 = now_s();
+    if (R->build_async) pthread_join(R->build_tid, NULL);
+    else build_run(&R->bj);
     join_warmup();
-    if (g_warm_ok) bind_to_gpu_node(device); /* from the main thread, before the worker threads below exist: they inherit the mask */
-    double t_join = now_s() - t_join0, t_streams = 0;
-    if (!overlap) {
-        if (ld->ready == 0) exit_message("No query files provided"); /* slamem.c:648 */
-        printf("> %d reference%s and %d quer%s successfully loaded\n", ref.num, ref.num == 1 ? "" : "s", ld->total_queries,
-               ld->total_queries == 1 ? "y" : "ies");
+    if (g_warm_ok) bind_to_gpu_node(R->device); /* from the main thread, before the worker threads exist: they inherit the mask */
+    R->t_join = now_s() - t0;
+    if (!R->overlap) {
+        if (R->ld->ready == 0) exit_message("No query files provided"); /* slamem.c:648 */
+        printf("> %d reference%s and %d quer%s successfully loaded\n", R->ref.num, R->ref.num == 1 ? "" : "s", R->ld->total_queries,
+               R->ld->total_queries == 1 ? "y" : "ies");
     }
-    if (o.min_mem_len < 1) exit_message("Minimum match length must be at least 1");
+    if (R->p.o.min_mem_len < 1) exit_message("Minimum match length must be at least 1");
+}
 
-    if (o.out_arg == -1) out_name = slh_append_to_basename(argv[o.file_args[0]], "-mems.txt");
-    else out_name = argv[o.out_arg];
-
-    /* GetMatches (slamem.c:37-218) */
-    say("> Using options: minimum %s length = %d ; strand = %s", MATCH_NAME(o.match_type), o.min_mem_len,
-           o.both_strands == 0 ? "forward only" : "forward + reverse");
-    if (max_occ > 0) say(" ; maximum occurrences = %d", max_occ);
-    if (o.match_type == 4) say(" ; maximum gap = %d", max_gap > 0 ? max_gap : 5000);
-    if (o.match_type == 5) say(" ; mismatch penalty = %d ; X-drop = %d", ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20);
-    if (o.match_type == 6 || o.match_type == 7 || o.match_type == 8)
-        say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", max_gap > 0 ? max_gap : 5000,
-            ext_pen > 0 ? ext_pen : 4, ext_xdrop >= 0 ? ext_xdrop : 20, max_edits >= 0 ? max_edits : 31);
-    if (o.match_type == 8) say(" ; minimum mapping quality = %d", min_mapq);
-    if (bq_given == 1) say(" ; minimum base quality = %d", min_bq); /* (only when asked for: the line of a run without -bq stays) */
-    if (gt) say(" ; minimum depth = %d ; ploidy = %d ; error rate = %d Phred ; prior = %d Phred ; minimum quality = %d", min_depth, gt_ploidy, gt_err, gt_hetq, gt_qual);
-    else if (sites || vcf) say(" ; minimum depth = %d ; minimum share = %d %%", min_depth, min_pct);
-    if (cons) say(" ; minimum depth = %d", min_depth);
-    if (depth) say(" ; covered from depth = %d", min_depth);
+/* the "Using options" line of GetMatches (slamem.c:37-218), and the output file */
+static void open_output(run_t *R) {
+    const slh_run *p = &R->p;
+    const int t = p->o.match_type, gap = p->max_gap > 0 ? p->max_gap : 5000, pen = p->ext_pen > 0 ? p->ext_pen : 4;
+    const int xdrop = p->ext_xdrop >= 0 ? p->ext_xdrop : 20;
+    if (p->o.out_arg == -1) R->out_name = slh_append_to_basename(R->argv[p->o.file_args[0]], "-mems.txt");
+    else R->out_name = R->argv[p->o.out_arg];
+    say("> Using options: minimum %s length = %d ; strand = %s", MATCH_NAME(t), p->o.min_mem_len,
+        p->o.both_strands == 0 ? "forward only" : "forward + reverse");
+    if (p->max_occ > 0) say(" ; maximum occurrences = %d", p->max_occ);
+    if (t == 4) say(" ; maximum gap = %d", gap);
+    if (t == 5) say(" ; mismatch penalty = %d ; X-drop = %d", pen, xdrop);
+    if (t == 6 || t == 7 || t == 8)
+        say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", gap, pen, xdrop, p->max_edits >= 0 ? p->max_edits : 31);
+    if (t == 8) say(" ; minimum mapping quality = %d", p->min_mapq);
+    if (p->bq_given == 1) say(" ; minimum base quality = %d", p->min_bq); /* (only when asked for: the line of a run without -bq stays) */
+    if (p->gt) say(" ; minimum depth = %d ; ploidy = %d ; error rate = %d Phred ; prior = %d Phred ; minimum quality = %d", p->min_depth, p->gt_ploidy, p->gt_err, p->gt_hetq, p->gt_qual);
+    else if (p->sites || p->vcf) say(" ; minimum depth = %d ; minimum share = %d %%", p->min_depth, p->min_pct);
+    if (p->cons) say(" ; minimum depth = %d", p->min_depth);
+    if (p->depth) say(" ; covered from depth = %d", p->min_depth);
     say("\n");
-    out = fopen(out_name, "w");
-    if (!out) {
+    R->out = fopen(R->out_name, "w");
+    if (!R->out) {
         release_stdout();
-        printf("\n> ERROR: Cannot create output file <%s>\n", out_name);
+        printf("\n> ERROR: Cannot create output file <%s>\n", R->out_name);
         join_warmup();
         exit(-1);
     }
+}
+
+static void report_index(run_t *R) {
+    const build_job *bj = &R->bj;
+    const slamem_index_info *info = &bj->info;
+    const slamem_timings *tm = &bj->tm;
+    const slamem_sslcp_stats *st = &bj->st;
+    const unsigned bwt_len = info->bwt_size;
     say("> Building index for reference sequence");
-    if (ref.num == 1) say(" \"%s\"", ref.recs[0].name);
+    if (R->ref.num == 1) say(" \"%s\"", R->ref.recs[0].name);
     else say("s");
-    say(" (%u Mbp) ...\n", (unsigned)(ref.total / 1000000U));
+    say(" (%u Mbp) ...\n", (unsigned)(R->ref.total / 1000000U));
     if (!g_mo) fflush(stdout);
-    t0 = now_s();
-    idx = bj.idx;
-    if (bj.rc != SLAMEM_OK) gpu_fail_msg("index construction on the GPU", bj.rc, bj.err);
-    {
-        slamem_index_info info = bj.info;
-        slamem_timings tm = bj.tm;
-        say("> Suffix sort + BWT + LCP + parent links on GPU %d ... OK (%.3f s, overlapped with the loading of the queries; device %.1f ms: sort %.1f, BWT %.1f, LCP %.1f, links %.1f; %u doubling rounds)\n",
-               device, bj.seconds, tm.build_total_ms, tm.build_sort_ms, tm.build_bwt_ms, tm.build_lcp_ms, tm.build_links_ms,
-               info.sort_rounds);
-        say(":: Index size = %.1f MB in HBM (%s layout)\n", (double)info.arena_bytes / 1e6,
-            info.layout == SLAMEM_LAYOUT_COMPACT ? "compact" : "full");
-        {   /* the statistics lines of BuildSampledLCPArray (lcparray.c:709-711, 999-1000), from the per-row records */
-            slamem_sslcp_stats st = bj.st;
-            unsigned bwt_len = info.bwt_size;
-            if (bj.rc_stats != SLAMEM_OK) gpu_fail_msg("LCP sampling statistics", bj.rc_stats, bj.err);
-            say(":: %.2lf%% samples (%u of %u)\n", ((double)st.num_samples / (double)bwt_len) * 100.0, (unsigned)st.num_samples, bwt_len);
-            say(":: %.2lf%% oversized samples (%d of %u)\n", ((double)st.num_oversized_lcp / (double)st.num_samples) * 100.0,
-                   (int)st.num_oversized_lcp, (unsigned)st.num_samples);
-            say(":: Average LCP value = %d (max=%lld)\n", (int)(st.sum_lcp / (long long)bwt_len), (long long)st.max_lcp);
-            say(":: %.2lf%% oversized values (%d of %u)\n", ((double)st.num_oversized_links / (double)st.num_samples) * 100.0,
-                   (int)st.num_oversized_links, (unsigned)st.num_samples);
-            say(":: Average SV distance = %.2lf (max=%lld)\n", (double)st.sum_link_distance / (double)st.num_samples,
-                   (long long)st.max_link_distance);
-        }
-    }
-    /* SLAMEM_GPUS=N: replicate the index to N GPUs (device, device+1, ...) with one RCCL broadcast of its arena over
-       xGMI; every batch is then split by bases into N contiguous shares, one per GPU (no data-path collective). */
-    gpus[0] = idx;
-    int logical = 0; /* SLAMEM_LOGICAL_GPUS=N (self-test): N "GPUs" that are all this device, each with its own copy of the index */
+    if (bj->rc != SLAMEM_OK) gpu_fail_msg("index construction on the GPU", bj->rc, bj->err);
+    say("> Suffix sort + BWT + LCP + parent links on GPU %d ... OK (%.3f s, overlapped with the loading of the queries; device %.1f ms: sort %.1f, BWT %.1f, LCP %.1f, links %.1f; %u doubling rounds)\n",
+        R->device, bj->seconds, tm->build_total_ms, tm->build_sort_ms, tm->build_bwt_ms, tm->build_lcp_ms, tm->build_links_ms, info->sort_rounds);
+    say(":: Index size = %.1f MB in HBM (%s layout)\n", (double)info->arena_bytes / 1e6, info->layout == SLAMEM_LAYOUT_COMPACT ? "compact" : "full");
+    /* the statistics lines of BuildSampledLCPArray (lcparray.c:709-711, 999-1000), from the per-row records */
+    if (bj->rc_stats != SLAMEM_OK) gpu_fail_msg("LCP sampling statistics", bj->rc_stats, bj->err);
+    say(":: %.2lf%% samples (%u of %u)\n", ((double)st->num_samples / (double)bwt_len) * 100.0, (unsigned)st->num_samples, bwt_len);
+    say(":: %.2lf%% oversized samples (%d of %u)\n", ((double)st->num_oversized_lcp / (double)st->num_samples) * 100.0,
+        (int)st->num_oversized_lcp, (unsigned)st->num_samples);
+    say(":: Average LCP value = %d (max=%lld)\n", (int)(st->sum_lcp / (long long)bwt_len), (long long)st->max_lcp);
+    say(":: %.2lf%% oversized values (%d of %u)\n", ((double)st->num_oversized_links / (double)st->num_samples) * 100.0,
+        (int)st->num_oversized_links, (unsigned)st->num_samples);
+    say(":: Average SV distance = %.2lf (max=%lld)\n", (double)st->sum_link_distance / (double)st->num_samples, (long long)st->max_link_distance);
+}
+
+/* SLAMEM_GPUS=N: replicate the index to N GPUs (device, device+1, ...) with one RCCL broadcast of its arena over xGMI; every
+ * batch then goes to one of them (no data-path collective).  SLAMEM_LOGICAL_GPUS=N (self-test): N "GPUs" that are all this
+ * device, each with its own copy of the index. */
+static void replicate_index(run_t *R) {
+    typedef int (*replicate_fn)(const slamem_index *, const int *, int, int, slamem_index **);
+    const double t0 = now_s();
+    const char *env;
+    int logical = 0, devs[16], g, rc = SLAMEM_OK;
+    R->gpus[0] = R->bj.idx;
+    R->ngpu = 1;
     if ((env = getenv("SLAMEM_GPUS")) != NULL) {
         int avail = 0;
         slamem_device_count(&avail);
-        ngpu = atoi(env) <= 0 ? avail - device : atoi(env);
-        if (ngpu < 1) ngpu = 1;
-        if (ngpu > 16) ngpu = 16;
-        if (device + ngpu > avail) exit_message("SLAMEM_GPUS asks for more GPUs than are visible");
+        R->ngpu = atoi(env) <= 0 ? avail - R->device : atoi(env);
+        if (R->ngpu < 1) R->ngpu = 1;
+        if (R->ngpu > 16) R->ngpu = 16;
+        if (R->device + R->ngpu > avail) exit_message("SLAMEM_GPUS asks for more GPUs than are visible");
     } else if ((env = getenv("SLAMEM_LOGICAL_GPUS")) != NULL && atoi(env) > 1) {
-        ngpu = atoi(env) > 16 ? 16 : atoi(env);
+        R->ngpu = atoi(env) > 16 ? 16 : atoi(env);
         logical = 1;
     }
-    if (ngpu > 1 || getenv("SLAMEM_REPLICATE_SELFTEST") != NULL) {
-        int devs[16], g;
-        double tr = now_s();
-        for (g = 0; g < ngpu; g++) devs[g] = logical ? device : device + g;
-        {   /* libslamem_rccl.so (and RCCL behind it, hundreds of MB of code) is loaded only when it is needed: a
-               one-GPU run never pays for it at start-up */
-            typedef int (*replicate_fn)(const slamem_index *, const int *, int, int, slamem_index **);
-            void *h = dlopen("libslamem_rccl.so", RTLD_NOW | RTLD_GLOBAL);
-            replicate_fn fn = h ? (replicate_fn)dlsym(h, "slamem_index_replicate") : NULL;
-            if (!fn) {
-                release_stdout();
-                printf("\n> ERROR: cannot load libslamem_rccl.so (%s)\n", dlerror());
-                join_warmup();
-                exit(-1);
-            }
-            if (logical) { /* one one-rank broadcast into a fresh arena per logical GPU: the scheduling below is the real N-GPU one */
-                for (g = 1, rc = SLAMEM_OK; g < ngpu && rc == SLAMEM_OK; g++) rc = fn(idx, devs, 1, 1, &gpus[g]);
-            } else {
-                rc = fn(idx, devs, ngpu, ngpu == 1, gpus);
-            }
+    if (R->ngpu > 1 || getenv("SLAMEM_REPLICATE_SELFTEST") != NULL) {
+        /* libslamem_rccl.so (and RCCL behind it, hundreds of MB of code) is loaded only when it is needed: a one-GPU run
+           never pays for it at start-up */
+        void *h = dlopen("libslamem_rccl.so", RTLD_NOW | RTLD_GLOBAL);
+        replicate_fn fn = h ? (replicate_fn)dlsym(h, "slamem_index_replicate") : NULL;
+        for (g = 0; g < R->ngpu; g++) devs[g] = logical ? R->device : R->device + g;
+        if (!fn) {
+            release_stdout();
+            printf("\n> ERROR: cannot load libslamem_rccl.so (%s)\n", dlerror());
+            join_warmup();
+            exit(-1);
         }
+        if (logical) /* one one-rank broadcast into a fresh arena per logical GPU: the scheduling of the batches is the real N-GPU one */
+            for (g = 1; g < R->ngpu && rc == SLAMEM_OK; g++) rc = fn(R->gpus[0], devs, 1, 1, &R->gpus[g]);
+        else rc = fn(R->gpus[0], devs, R->ngpu, R->ngpu == 1, R->gpus);
         if (rc != SLAMEM_OK) gpu_fail("index replication over RCCL", rc);
-        if (ngpu == 1) { slamem_index_free(idx); idx = gpus[0]; } /* self-test: search on the broadcast copy */
-        say("> Index replicated to %d %sGPU%s by RCCL broadcast ... OK (%.3f s)\n", ngpu, logical ? "logical " : "",
-            ngpu == 1 ? " (self-test copy)" : "s", now_s() - tr);
+        if (R->ngpu == 1) slamem_index_free(R->bj.idx); /* self-test: search on the broadcast copy */
+        say("> Index replicated to %d %sGPU%s by RCCL broadcast ... OK (%.3f s)\n", R->ngpu, logical ? "logical " : "",
+            R->ngpu == 1 ? " (self-test copy)" : "s", now_s() - t0);
     }
-    t_build = bj.seconds + (now_s() - t0);
-    if (o.match_type != 8) { /* (-pile prints the reference letter of every row: it keeps the text) */
-        free(ref.chars); /* the reference frees the text here too (slamem.c:75-77) */
-        ref.chars = NULL;
+    if (R->p.o.match_type != 8) { /* (-pile prints the reference letter of every row: it keeps the text) */
+        free(R->ref.chars); /* the reference frees the text here too (slamem.c:75-77) */
+        R->ref.chars = NULL;
     }
     say("> Matching query sequences against index ...\n");
     if (!g_mo) fflush(stdout);
+}
 
-    {
-        /* (-paf: what is formatted and counted is a read, whichever strand its mapping lies on) */
-        int strands = (o.match_type == 7 || o.match_type == 8) ? 1 : o.both_strands ? 2 : 1;
-        long printed = 0;
-        /* the list of batches (records [first,last) of one query file each), then a pipeline over it: the GPUs search
-           batches b+1.. (slamem_stream_*: upload, search and download of neighbouring batches overlap), the main thread
-           formats batch b with all host threads, the writer thread writes batch b-1 */
-        typedef struct { int f, first, last; } batch_range;
-        batch_range *ranges = NULL;
-        size_t nranges = 0, cap_ranges = 0, bi, submitted = 0;
-        uint64_t max_chars = 1;
-        uint32_t max_recs = 1;
-        int inflight[16], g;
-        const int slots = 6; /* upload, prepare, search and download of four batches beside the one being formatted */
-        int sets_seen = 0, sets_reaped = 0, sets_ready = ld->ready; /* !overlap: everything is there */
-#define ADD_RANGES_OF_NEW_SETS()                                                                                              \
-        for (; sets_seen < sets_ready; sets_seen++) {                                                                          \
-            slh_seqset *q = &qsets[sets_seen];                                                                                 \
-            int first = 0;                                                                                                     \
-            while (first < q->num) {                                                                                           \
-                int last = first;                                                                                              \
-                uint64_t base = q->offsets[first];                                                                             \
-                /* the first batches are short, so that the search starts early */                                             \
-                uint64_t limit = nranges < (size_t)ngpu ? batch_bytes / 4 : nranges < 2 * (size_t)ngpu ? batch_bytes / 2 : batch_bytes; \
-                while (last < q->num && (last == first || q->offsets[last + 1] - base <= limit)) last++;                       \
-                if (nranges == cap_ranges) {                                                                                   \
-                    cap_ranges = cap_ranges ? cap_ranges * 2 : 16;                                                             \
-                    ranges = (batch_range *)realloc(ranges, cap_ranges * sizeof(batch_range));                                 \
-                    if (!ranges) pipeline_fail("Out of memory");                                                               \
-                }                                                                                                              \
-                ranges[nranges].f = sets_seen; ranges[nranges].first = first; ranges[nranges].last = last;                     \
-                if (q->offsets[last] - base > max_chars) max_chars = q->offsets[last] - base;                                  \
-                if ((uint32_t)(last - first) > max_recs) max_recs = (uint32_t)(last - first);                                  \
-                nranges++;                                                                                                     \
-                first = last;                                                                                                  \
-            }                                                                                                                  \
+/* the batches of the query sets that have come in since the last call: records [first,last) of one set each */
+static void add_ranges_of_new_sets(run_t *R, int sets_ready) {
+    for (; R->sets_seen < sets_ready; R->sets_seen++) {
+        const slh_seqset *q = &R->qsets[R->sets_seen];
+        int first = 0;
+        while (first < q->num) {
+            int last = first;
+            const uint64_t base = q->offsets[first];
+            /* the first batches are short, so that the search starts early */
+            const uint64_t limit = R->nranges < (size_t)R->ngpu ? R->batch_bytes / 4 : R->nranges < 2 * (size_t)R->ngpu ? R->batch_bytes / 2 : R->batch_bytes;
+            while (last < q->num && (last == first || q->offsets[last + 1] - base <= limit)) last++;
+            if (R->nranges == R->cap_ranges) {
+                R->cap_ranges = R->cap_ranges ? R->cap_ranges * 2 : 16;
+                R->ranges = (batch_range *)realloc(R->ranges, R->cap_ranges * sizeof(batch_range));
+                if (!R->ranges) pipeline_fail("Out of memory");
+            }
+            R->ranges[R->nranges].f = R->sets_seen; R->ranges[R->nranges].first = first; R->ranges[R->nranges].last = last;
+            if (q->offsets[last] - base > R->max_chars) R->max_chars = q->offsets[last] - base;
+            if ((uint32_t)(last - first) > R->max_recs) R->max_recs = (uint32_t)(last - first);
+            R->nranges++;
+            first = last;
         }
-        ADD_RANGES_OF_NEW_SETS();
-        if (overlap) { /* the batches are not known yet: reserve for a piece's worth, the slots grow on demand */
-            uint64_t guess = batch_bytes < (uint64_t)piece_bytes ? batch_bytes : (uint64_t)piece_bytes;
-            if (max_chars < guess) max_chars = guess;
-            if (max_recs < max_chars / 64) max_recs = (uint32_t)(max_chars / 64);
+    }
+}
+
+/* The writer thread, and a search stream per GPU with the options of the mode: batch b is searched on GPU b mod ngpu.  A stream
+ * counts for shutdown_pipeline from the moment it exists, so that a failure of its set-up tears it down too. */
+static void open_streams(run_t *R) {
+    const slh_run *p = &R->p;
+    const int t = p->o.match_type;
+    const uint32_t xdrop = p->ext_xdrop >= 0 ? (uint32_t)p->ext_xdrop : SLAMEM_EXT_XDROP_DEFAULT;
+    const double t0 = now_s();
+    int g;
+    R->max_chars = R->max_recs = 1;
+    add_ranges_of_new_sets(R, R->ld->ready); /* (!overlap: everything is there) */
+    if (R->overlap) { /* the batches are not known yet: reserve for a piece's worth, the slots grow on demand */
+        const uint64_t guess = R->batch_bytes < (uint64_t)R->piece_bytes ? R->batch_bytes : (uint64_t)R->piece_bytes;
+        if (R->max_chars < guess) R->max_chars = guess;
+        if (R->max_recs < R->max_chars / 64) R->max_recs = (uint32_t)(R->max_chars / 64);
+    }
+    memset(&g_writer, 0, sizeof(g_writer));
+    g_writer.out = R->out;
+    pthread_mutex_init(&g_writer.mu, NULL);
+    pthread_cond_init(&g_writer.cv, NULL);
+    if (p->sam) { /* the header, once, in front of the first batch's lines */
+        slh_buffer hd = {0, 0, 0};
+        if (slh_format_sam_header(&hd, R->ref.recs, R->ref.num)) pipeline_fail("Out of memory");
+        if (fwrite(hd.data, 1, hd.len, R->out) != hd.len) pipeline_fail("Cannot write output file");
+        slh_buffer_free(&hd);
+    }
+    g_writer.started = pthread_create(&g_writer.tid, NULL, writer_run, &g_writer) == 0;
+    for (g = 0; g < R->ngpu && (R->nranges || R->overlap); g++) {
+        slamem_stream *s;
+        int rc = slamem_stream_create(R->gpus[g], STREAM_SLOTS, R->max_chars, R->max_recs, p->o.both_strands, t, &g_streams[g]);
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("setting up the search pipeline", rc);
+        g_nstreams = g + 1;
+        s = g_streams[g];
+        if (p->max_occ > 0) rc = slamem_stream_set_max_occ(s, (uint32_t)p->max_occ);
+        if (rc == SLAMEM_OK && t == 8) { /* one accumulator per GPU: the tables are added when the file is written */
+            rc = slamem_pileup_create(R->gpus[g], &R->piles[g]);
+            if (rc == SLAMEM_OK && (p->vcf || p->cons)) rc = slamem_pileup_enable_events(R->piles[g], p->ev_slots);
+            if (rc == SLAMEM_OK && p->dedup) rc = slamem_pileup_enable_dedup(R->piles[g], p->dd_slots);
+            if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(s, R->piles[g], (uint32_t)p->min_mapq);
+            if (rc == SLAMEM_OK && p->dedup) rc = slamem_stream_set_dedup(s, 1);
         }
-        memset(&g_writer, 0, sizeof(g_writer));
-        g_writer.out = out;
-        pthread_mutex_init(&g_writer.mu, NULL);
-        pthread_cond_init(&g_writer.cv, NULL);
-        if (sam) { /* the header, once, in front of the first batch's lines */
-            slh_buffer hd = {0, 0, 0};
-            if (slh_format_sam_header(&hd, ref.recs, ref.num)) pipeline_fail("Out of memory");
-            if (fwrite(hd.data, 1, hd.len, out) != hd.len) pipeline_fail("Cannot write output file");
-            slh_buffer_free(&hd);
-        }
-        g_writer.started = pthread_create(&g_writer.tid, NULL, writer_run, &g_writer) == 0;
-        double ts0 = now_s();
-        for (g = 0; g < 16; g++) piles[g] = NULL;
-        for (g = 0; g < ngpu && (nranges || overlap); g++) { /* batch b is searched on GPU b mod ngpu: no data-path collective */
-            rc = slamem_stream_create(gpus[g], slots, max_chars, max_recs, o.both_strands, o.match_type, &g_streams[g]);
-            if (rc == SLAMEM_OK && max_occ > 0) {
-                g_nstreams = g + 1; /* (so that a failure below tears this stream down too) */
-                rc = slamem_stream_set_max_occ(g_streams[g], (uint32_t)max_occ);
-            }
-            if (rc == SLAMEM_OK && max_gap > 0) {
-                g_nstreams = g + 1;
-                rc = slamem_stream_set_max_gap(g_streams[g], (uint32_t)max_gap);
-            }
-            if (rc == SLAMEM_OK && o.match_type == 5) {
-                g_nstreams = g + 1;
-                rc = slamem_stream_set_ext_params(g_streams[g], (uint32_t)ext_pen,
-                                                  ext_xdrop >= 0 ? (uint32_t)ext_xdrop : SLAMEM_EXT_XDROP_DEFAULT);
-            }
-            if (rc == SLAMEM_OK && o.match_type == 8) { /* one accumulator per GPU: the tables are added when the file is written */
-                g_nstreams = g + 1;
-                rc = slamem_pileup_create(gpus[g], &piles[g]);
-                if (rc == SLAMEM_OK && (vcf || cons)) rc = slamem_pileup_enable_events(piles[g], ev_slots);
-                if (rc == SLAMEM_OK && dedup) rc = slamem_pileup_enable_dedup(piles[g], dd_slots);
-                if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(g_streams[g], piles[g], (uint32_t)min_mapq);
-                if (rc == SLAMEM_OK && dedup) rc = slamem_stream_set_dedup(g_streams[g], 1);
-            }
-            if (rc == SLAMEM_OK && (o.match_type == 6 || o.match_type == 7 || o.match_type == 8)) {
-                g_nstreams = g + 1;
-                rc = slamem_stream_set_max_gap(g_streams[g], (uint32_t)max_gap);
-                if (rc == SLAMEM_OK)
-                    rc = slamem_stream_set_ext_params(g_streams[g], (uint32_t)ext_pen,
-                                                      ext_xdrop >= 0 ? (uint32_t)ext_xdrop : SLAMEM_EXT_XDROP_DEFAULT);
-                if (rc == SLAMEM_OK)
-                    rc = slamem_stream_set_max_edits(g_streams[g], max_edits >= 0 ? (uint32_t)max_edits : SLAMEM_ALN_EDITS_DEFAULT);
-            }
-            if (rc == SLAMEM_OK && sam) { /* every batch also goes through the MD pass */
-                g_nstreams = g + 1;
-                rc = slamem_stream_set_md(g_streams[g], 1);
-            }
-            if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("setting up the search pipeline", rc); }
-            g_nstreams = g + 1;
-            inflight[g] = 0;
-        }
-        t_streams = now_s() - ts0;
-        for (bi = 0;; bi++) {
-            if (overlap) { /* take in the pieces parsed meanwhile; wait for one only when there is nothing else to do */
-                double tw = now_s();
+        if (rc == SLAMEM_OK && (t == 6 || t == 7 || t == 8 || (t == 4 && p->max_gap > 0))) rc = slamem_stream_set_max_gap(s, (uint32_t)p->max_gap);
+        if (rc == SLAMEM_OK && (t == 5 || t == 6 || t == 7 || t == 8)) rc = slamem_stream_set_ext_params(s, (uint32_t)p->ext_pen, xdrop);
+        if (rc == SLAMEM_OK && (t == 6 || t == 7 || t == 8))
+            rc = slamem_stream_set_max_edits(s, p->max_edits >= 0 ? (uint32_t)p->max_edits : SLAMEM_ALN_EDITS_DEFAULT);
+        if (rc == SLAMEM_OK && p->sam) rc = slamem_stream_set_md(s, 1); /* every batch also goes through the MD pass */
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("setting up the search pipeline", rc);
+        R->inflight[g] = 0;
+    }
+    R->t_streams = now_s() - t0;
+}
+
+/* keep every GPU's pipeline full: slots - 1 batches in flight beside the result being formatted */
+static void submit_batches(run_t *R, size_t *submitted) {
+    for (; *submitted < R->nranges && R->inflight[*submitted % (size_t)R->ngpu] < STREAM_SLOTS - 1; (*submitted)++) {
+        const batch_range *br = &R->ranges[*submitted];
+        const slh_seqset *qs = &R->qsets[br->f];
+        const uint64_t *qmask = R->ld->masks[br->f];
+        slamem_stream *s = g_streams[*submitted % (size_t)R->ngpu];
+        const uint32_t nrec = (uint32_t)(br->last - br->first), min_len = (uint32_t)R->p.o.min_mem_len;
+        /* -bq N on FASTQ reads: the set's mask is indexed as its letters, the stream takes the batch's words */
+        const int rc = qmask ? slamem_stream_submit_masked(s, qs->chars, qmask, qs->offsets + br->first, nrec, min_len)
+                             : slamem_stream_submit(s, qs->chars, qs->offsets + br->first, nrec, min_len);
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("MEM search on the GPU", rc);
+        R->inflight[*submitted % (size_t)R->ngpu]++;
+    }
+}
+
+/* the next batch's results of stream s; 0: the batch is in its GPU's pileup and nothing came back to format */
+static int fetch_batch(run_t *R, size_t bi, batch_view *v) {
+    const int t = R->p.o.match_type, g = (int)(bi % (size_t)R->ngpu);
+    slamem_stream *s = g_streams[g];
+    const uint32_t *seg_eq = NULL;
+    uint64_t nops = 0, nmd = 0;
+    int rc = slamem_stream_next(s, &v->mems, &v->boff, &v->total, NULL, NULL);
+    if (rc != SLAMEM_OK) {
+        char detail[512];
+        snprintf(detail, sizeof(detail), "%s", slamem_last_error_message());
+        shutdown_pipeline();
+        release_stdout();
+        printf("\n> ERROR: MEM search on GPU %d failed: %s (%s)\n", R->device + g, slamem_strerror(rc), detail);
+        join_warmup();
+        exit(-1);
+    }
+    if (t == 8) return 0;
+    if (t == 5 && (rc = slamem_stream_mismatches(s, &v->mism)) != SLAMEM_OK) /* the fourth column of this batch's rows */
+        pipeline_gpu_fail("MEM extension on the GPU", rc);
+    if ((t == 6 || t == 7) && (rc = slamem_stream_alns(s, &v->segs, &v->ops, &v->ooff, &nops)) != SLAMEM_OK) /* the segments stand in the place of the rows */
+        pipeline_gpu_fail("alignment on the GPU", rc);
+    if (t == 7 && (rc = slamem_stream_maps(s, &v->reads)) != SLAMEM_OK) /* ... and the offsets are per read */
+        pipeline_gpu_fail("mapping on the GPU", rc);
+    /* -sam: the MD entries and the primary segments came with them (seg_eq and nmd are what the interface hands out beside them:
+       the writer needs neither, the primary segment is already chosen) */
+    if (R->p.sam && (rc = slamem_stream_md(s, &v->md, &v->mdoff, &seg_eq, &v->prim, &nmd)) != SLAMEM_OK)
+        pipeline_gpu_fail("the MD pass on the GPU", rc);
+    return 1;
+}
+
+/* The first strand blocks get their ':: "name" ....' line (slamem.c:97,101,203) and are formatted here; the rest of the batch
+ * is formatted by all host threads, in chunks taken from a shared counter, and handed to the writer in order. */
+static void format_batch(run_t *R, const batch_view *v, uint64_t nblk) {
+    const slh_seqset *q = v->q;
+    uint64_t bseq = 0, b, per;
+    int nthr = slh_thread_count(), njobs, t;
+    fmt_job *jobs;
+    pthread_t *tid;
+    fmt_queue fq;
+    double fmt_t0, fmt_longest = 0, fmt_latest_start = 0;
+    if (R->log_limit == 0) bseq = nblk;
+    else if (R->printed < R->log_limit) bseq = (uint64_t)(R->log_limit - R->printed) < nblk ? (uint64_t)(R->log_limit - R->printed) : nblk;
+    for (b = 0; b < bseq; b++) {
+        const int ri = v->first_rec + (int)(b / (uint64_t)v->strands), sidx = (int)(b % (uint64_t)v->strands);
+        uint64_t cnt, sum;
+        int d, dots;
+        if (format_block(v, b, &R->buf, &cnt, &sum)) pipeline_fail("Out of memory");
+        R->total_matches += (long long)cnt;
+        R->total_sum += (long long)sum;
+        dots = slh_progress_dots(q->recs[ri].size);
+        say(":: \"%s%s\" ", q->recs[ri].name, sidx ? " Reverse" : "");
+        for (d = 0; d < dots; d++) fputc('.', g_mo ? g_mo : stdout);
+        say(" (%d %ss ; avg size = %d bp)\n", (int)cnt, MATCH_NAME(R->p.o.match_type), (int)(cnt ? sum / cnt : 0));
+        R->printed++;
+    }
+    if (writer_push(&g_writer, &R->buf)) pipeline_fail("Out of memory");
+    if (bseq == nblk) return;
+    fmt_t0 = now_s();
+    if ((nblk - bseq) < 4096 || nthr < 1) nthr = 1;
+    njobs = (int)((nblk - bseq + 32767) / 32768); /* chunks of 32 k strand blocks, at least one per thread */
+    if (njobs < nthr) njobs = nthr;
+    jobs = (fmt_job *)calloc((size_t)njobs, sizeof(fmt_job));
+    tid = (pthread_t *)calloc((size_t)nthr, sizeof(pthread_t));
+    if (!jobs || !tid) pipeline_fail("Out of memory");
+    per = (nblk - bseq + (uint64_t)njobs - 1) / (uint64_t)njobs;
+    for (t = 0; t < njobs; t++) {
+        jobs[t].v = v;
+        jobs[t].b0 = bseq + per * (uint64_t)t < nblk ? bseq + per * (uint64_t)t : nblk;
+        jobs[t].b1 = jobs[t].b0 + per < nblk ? jobs[t].b0 + per : nblk;
+    }
+    fq.jobs = jobs; fq.njobs = njobs; fq.next = 0;
+    for (t = 0; t + 1 < nthr; t++)
+        if (pthread_create(&tid[t], NULL, fmt_worker, &fq) != 0) tid[t] = 0;
+    fmt_worker(&fq); /* the main thread takes chunks too */
+    for (t = 0; t + 1 < nthr; t++)
+        if (tid[t]) pthread_join(tid[t], NULL);
+    for (t = 0; t < njobs; t++) {
+        if (jobs[t].failed) pipeline_fail("Out of memory");
+        g_fmt_busy += jobs[t].t_end - jobs[t].t_start;
+        if (jobs[t].t_end - jobs[t].t_start > fmt_longest) fmt_longest = jobs[t].t_end - jobs[t].t_start;
+        if (jobs[t].t_start - fmt_t0 > fmt_latest_start) fmt_latest_start = jobs[t].t_start - fmt_t0;
+        R->total_matches += jobs[t].matches;
+        R->total_sum += jobs[t].sum;
+        if (writer_push(&g_writer, &jobs[t].buf)) pipeline_fail("Out of memory");
+    }
+    free(jobs);
+    free(tid);
+    g_fmt_longest += fmt_longest;
+    g_fmt_latest_start += fmt_latest_start;
+}
+
+/* The pipeline over the list of batches: the GPUs search batches b+1.. (slamem_stream_*: upload, search and download of
+ * neighbouring batches overlap), the main thread formats batch b with all host threads, the writer thread writes batch b-1. */
+static void run_batches(run_t *R) {
+    loader_t *ld = R->ld;
+    size_t bi, submitted = 0;
+    int sets_reaped = 0;
+    for (bi = 0;; bi++) {
+        batch_view v;
+        const batch_range *br;
+        double tg;
+        if (R->overlap) { /* take in the pieces parsed meanwhile; wait for one only when there is nothing else to do */
+            const double tw = now_s();
+            int sets_ready, finished;
+            pthread_mutex_lock(&ld->mu);
+            while (bi >= R->nranges && R->sets_seen == ld->ready && !ld->done) pthread_cond_wait(&ld->cv, &ld->mu);
+            sets_ready = ld->ready;
+            pthread_mutex_unlock(&ld->mu);
+            add_ranges_of_new_sets(R, sets_ready);
+            R->t_wait_load += now_s() - tw;
+            if (bi >= R->nranges) { /* nothing new: either the loader is done or a piece without batches came in */
                 pthread_mutex_lock(&ld->mu);
-                while (bi >= nranges && sets_seen == ld->ready && !ld->done) pthread_cond_wait(&ld->cv, &ld->mu);
-                sets_ready = ld->ready;
+                finished = ld->done && R->sets_seen == ld->ready;
                 pthread_mutex_unlock(&ld->mu);
-                ADD_RANGES_OF_NEW_SETS();
-                t_wait_load += now_s() - tw;
-                if (bi >= nranges) { /* nothing new: either the loader is done or a piece without batches came in */
-                    int finished;
-                    pthread_mutex_lock(&ld->mu);
-                    finished = ld->done && sets_seen == ld->ready;
-                    pthread_mutex_unlock(&ld->mu);
-                    if (finished) break;
-                    bi--;
-                    continue;
-                }
-            } else if (bi >= nranges) break;
-            slh_seqset *q = &qsets[ranges[bi].f];
-            const int first = ranges[bi].first, last = ranges[bi].last;
-            for (; ld->release_early && sets_reaped < ranges[bi].f; sets_reaped++) /* every batch of the earlier sets is formatted */
-                if (qsets[sets_reaped].chars) {
-                    reap_set(&qsets[sets_reaped]); free(ld->masks[sets_reaped]); ld->masks[sets_reaped] = NULL;
-                    free(ld->quals[sets_reaped]); ld->quals[sets_reaped] = NULL;
-                }
-            const slamem_mem *mems = NULL;
-            const uint32_t *mism = NULL;
-            const slamem_aln *segs = NULL;
-            const uint32_t *ops = NULL;
-            const uint64_t *ooff = NULL;
-            uint64_t nops = 0;
-            const slamem_map *reads = NULL;
-            const uint32_t *md = NULL, *seg_eq = NULL, *prim = NULL;
-            const uint64_t *mdoff = NULL;
-            uint64_t nmd = 0;
-            const uint64_t *boff = NULL;
-            uint64_t total = 0;
-            double tg = now_s();
-            /* keep every GPU's pipeline full: slots - 1 batches in flight beside the result being formatted */
-            while (submitted < nranges && inflight[submitted % (size_t)ngpu] < slots - 1) {
-                slh_seqset *qs = &qsets[ranges[submitted].f];
-                const uint64_t *qmask = ld->masks[ranges[submitted].f];
-                if (qmask) /* -bq N on FASTQ reads: the set's mask is indexed as its letters, the stream takes the batch's words */
-                    rc = slamem_stream_submit_masked(g_streams[submitted % (size_t)ngpu], qs->chars, qmask,
-                                                     qs->offsets + ranges[submitted].first,
-                                                     (uint32_t)(ranges[submitted].last - ranges[submitted].first), (uint32_t)o.min_mem_len);
-                else
-                rc = slamem_stream_submit(g_streams[submitted % (size_t)ngpu], qs->chars, qs->offsets + ranges[submitted].first,
-                                          (uint32_t)(ranges[submitted].last - ranges[submitted].first), (uint32_t)o.min_mem_len);
-                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("MEM search on the GPU", rc); }
-                inflight[submitted % (size_t)ngpu]++;
-                submitted++;
-            }
-            rc = slamem_stream_next(g_streams[bi % (size_t)ngpu], &mems, &boff, &total, NULL, NULL);
-            if (rc != SLAMEM_OK) {
-                char detail[512];
-                snprintf(detail, sizeof(detail), "%s", slamem_last_error_message());
-                shutdown_pipeline();
-                release_stdout();
-                printf("\n> ERROR: MEM search on GPU %d failed: %s (%s)\n", device + (int)(bi % (size_t)ngpu), slamem_strerror(rc), detail);
-                join_warmup();
-                exit(-1);
-            }
-            if (o.match_type == 8) { /* the batch is in its GPU's table: nothing came back to format (total: the segments piled) */
-                inflight[bi % (size_t)ngpu]--;
-                total_matches += (long long)total;
-                t_gpu += now_s() - tg;
+                if (finished) break;
+                bi--;
                 continue;
             }
-            if (o.match_type == 5) { /* the fourth column of this batch's rows */
-                rc = slamem_stream_mismatches(g_streams[bi % (size_t)ngpu], &mism);
-                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("MEM extension on the GPU", rc); }
+        } else if (bi >= R->nranges) break;
+        br = &R->ranges[bi];
+        for (; ld->release_early && sets_reaped < br->f; sets_reaped++) /* every batch of the earlier sets is formatted */
+            if (R->qsets[sets_reaped].chars) {
+                reap_set(&R->qsets[sets_reaped]); free(ld->masks[sets_reaped]); ld->masks[sets_reaped] = NULL;
+                free(ld->quals[sets_reaped]); ld->quals[sets_reaped] = NULL;
             }
-            if (o.match_type == 6 || o.match_type == 7) { /* the segments stand in the place of the rows */
-                rc = slamem_stream_alns(g_streams[bi % (size_t)ngpu], &segs, &ops, &ooff, &nops);
-                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("alignment on the GPU", rc); }
-            }
-            if (o.match_type == 7) { /* ... and the offsets are per read */
-                rc = slamem_stream_maps(g_streams[bi % (size_t)ngpu], &reads);
-                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("mapping on the GPU", rc); }
-            }
-            if (sam) { /* ... and the MD entries and the primary segments came with them (seg_eq and nmd are what the interface
-                          hands out beside them: the writer needs neither, the primary segment is already chosen) */
-                rc = slamem_stream_md(g_streams[bi % (size_t)ngpu], &md, &mdoff, &seg_eq, &prim, &nmd);
-                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("the MD pass on the GPU", rc); }
-            }
-            inflight[bi % (size_t)ngpu]--;
-            t_gpu += now_s() - tg; /* time the main thread waited for the GPUs */
-            tg = now_s();
-            {
-                /* the first strand blocks get their ':: "name" ....' line (slamem.c:97,101,203) and are formatted here;
-                   the rest of the batch is formatted by all host threads and handed to the writer in order */
-                uint64_t nblk = (uint64_t)(last - first) * strands, bseq = 0, b;
-                int nthr = slh_thread_count(), t;
-                if (log_limit == 0) bseq = nblk;
-                else if (printed < log_limit) bseq = (uint64_t)(log_limit - printed) < nblk ? (uint64_t)(log_limit - printed) : nblk;
-                for (b = 0; b < bseq; b++) {
-                    int ri = first + (int)(b / strands), sidx = (int)(b % strands), d, dots;
-                    uint64_t cnt = boff[b + 1] - boff[b], sum = 0;
-                    if (md ? format_sam_read(&buf, q, ld->quals[ranges[bi].f], ri, b, reads, segs, ops, ooff, boff, md, mdoff, prim, &ref, &sum)
-                        : reads ? slh_format_read_paf(&buf, q->recs[ri].name, q->recs[ri].size, reads[b].strand, reads[b].mapq, reads[b].s1,
-                                                    reads[b].s2, (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b], cnt, ref.recs,
-                                                    ref.merged_start, ref.num, &sum)
-                        : segs ? slh_format_block_aln(&buf, q->recs[ri].name, sidx, (const uint32_t *)(segs + boff[b]), ops, ooff + boff[b],
-                                                    cnt, ref.recs, ref.merged_start, ref.num, &sum)
-                             : slh_format_block_ext(&buf, q->recs[ri].name, sidx, (const uint32_t *)(mems + boff[b]),
-                                             mism ? mism + boff[b] : NULL, cnt, ref.recs, ref.merged_start, ref.num, &sum))
-                        pipeline_fail("Out of memory");
-                    total_matches += (long long)cnt;
-                    total_sum += (long long)sum;
-                    dots = slh_progress_dots(q->recs[ri].size);
-                    say(":: \"%s%s\" ", q->recs[ri].name, sidx ? " Reverse" : "");
-                    for (d = 0; d < dots; d++) fputc('.', g_mo ? g_mo : stdout);
-                    say(" (%d %ss ; avg size = %d bp)\n", (int)cnt, MATCH_NAME(o.match_type), (int)(cnt ? sum / cnt : 0));
-                    printed++;
-                }
-                if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
-                if (bseq < nblk) {
-                    fmt_job *jobs;
-                    pthread_t *tid;
-                    fmt_queue fq;
-                    uint64_t per;
-                    int njobs;
-                    double fmt_t0 = now_s(), fmt_longest = 0, fmt_latest_start = 0;
-                    if ((nblk - bseq) < 4096 || nthr < 1) nthr = 1;
-                    /* chunks of 32 k strand blocks, at least one per thread */
-                    njobs = (int)((nblk - bseq + 32767) / 32768);
-                    if (njobs < nthr) njobs = nthr;
-                    jobs = (fmt_job *)calloc((size_t)njobs, sizeof(fmt_job));
-                    tid = (pthread_t *)calloc((size_t)nthr, sizeof(pthread_t));
-                    if (!jobs || !tid) pipeline_fail("Out of memory");
-                    per = (nblk - bseq + (uint64_t)njobs - 1) / (uint64_t)njobs;
-                    for (t = 0; t < njobs; t++) {
-                        jobs[t].q = q; jobs[t].ref = &ref; jobs[t].mems = mems; jobs[t].mism = mism; jobs[t].boff = boff;
-                        jobs[t].segs = segs; jobs[t].ops = ops; jobs[t].ooff = ooff; jobs[t].reads = reads;
-                        jobs[t].md = md; jobs[t].mdoff = mdoff; jobs[t].prim = prim; jobs[t].quals = ld->quals[ranges[bi].f];
-                        jobs[t].first_rec = first; jobs[t].strands = strands;
-                        jobs[t].b0 = bseq + per * (uint64_t)t < nblk ? bseq + per * (uint64_t)t : nblk;
-                        jobs[t].b1 = jobs[t].b0 + per < nblk ? jobs[t].b0 + per : nblk;
-                    }
-                    fq.jobs = jobs; fq.njobs = njobs; fq.next = 0;
-                    for (t = 0; t + 1 < nthr; t++)
-                        if (pthread_create(&tid[t], NULL, fmt_worker, &fq) != 0) tid[t] = 0;
-                    fmt_worker(&fq); /* the main thread takes chunks too */
-                    for (t = 0; t + 1 < nthr; t++)
-                        if (tid[t]) pthread_join(tid[t], NULL);
-                    for (t = 0; t < njobs; t++) {
-                        if (jobs[t].failed) pipeline_fail("Out of memory");
-                        g_fmt_busy += jobs[t].t_end - jobs[t].t_start;
-                        if (jobs[t].t_end - jobs[t].t_start > fmt_longest) fmt_longest = jobs[t].t_end - jobs[t].t_start;
-                        if (jobs[t].t_start - fmt_t0 > fmt_latest_start) fmt_latest_start = jobs[t].t_start - fmt_t0;
-                        total_matches += jobs[t].matches;
-                        total_sum += jobs[t].sum;
-                        if (writer_push(&g_writer, &jobs[t].buf)) pipeline_fail("Out of memory");
-                    }
-                    free(jobs);
-                    free(tid);
-                    g_fmt_longest += fmt_longest;
-                    g_fmt_latest_start += fmt_latest_start;
-                }
-                if (g_writer.failed) pipeline_fail("Cannot write output file");
-            }
-            t_format += now_s() - tg;
-        }
-#undef ADD_RANGES_OF_NEW_SETS
-        free(ranges);
-        release_stdout(); /* the loader is done: the "successfully loaded" line, then what was held back */
-        total_queries = ld->total_queries;
-        if (ld->failed) pipeline_fail("Internal error: the query files came in more pieces than planned");
-        if (ld->invalid) { /* the loader thread met a query file that is no valid FASTQ (it said so), or ran out of memory */
-            shutdown_pipeline();
-            fclose(out);
-            remove(out_name);
-            exit_message(ld->invalid == 1 ? "A query file is not valid FASTQ" : "Out of memory");
-        }
-        if (ld->fasta_seen) fprintf(stderr, "> WARNING: option -bq %d has no effect on FASTA queries: they carry no base qualities\n", min_bq);
-        if (ld->ready == 0) { /* slamem.c:648 (an overlapped run only knows it now) */
-            shutdown_pipeline();
-            fclose(out);
-            remove(out_name);
-            exit_message("No query files provided");
-        }
-        if (o.match_type == 8 && (sites || vcf || cons || depth)) {
-            /* the tables of GPUs 1.. are added into GPU 0's, in chunks of 16 M rows; then GPU 0 applies the rule to the sum range
-               after range and only the selected rows come back: a line each, the separators between records skipped */
-            const uint64_t chunk = 16ull << 20, n = ref.total;
-            uint64_t x0, cap = 1ull << 20, *pos = NULL;
-            uint32_t *rows = NULL;
-            uint8_t *alleles = NULL;
-            uint64_t ecap = 1ull << 16, skipped[3] = {0, 0, 0}, sk[3] = {0, 0, 0};
-            slamem_event *evs = NULL;
-            uint64_t *anchors = NULL;
-            uint32_t *arows = NULL;
-            slamem_genotype *gts = NULL, *egts = NULL; /* -gt: the genotypes of the rows and of the events, and which events are called */
-            uint8_t *ecalled = NULL;
-            int r = 0;
-            double tp = now_s();
-            if (vcf && (gt ? slh_format_vcf_gt_header(&buf, ref.recs, ref.num) : slh_format_vcf_header(&buf, ref.recs, ref.num)))
-                pipeline_fail("Out of memory");
-            if (g_nstreams > 1) {
-                rows = (uint32_t *)slh_big_malloc((size_t)(chunk < n ? chunk : n) * 24 + 24);
-                if (!rows) pipeline_fail("Out of memory");
-                for (g = 1; g < g_nstreams; g++)
-                    for (x0 = 0; x0 < n; x0 += chunk) {
-                        const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
-                        rc = slamem_pileup_counts_host(piles[g], x0, cnt, rows);
-                        if (rc == SLAMEM_OK) rc = slamem_pileup_add_counts_host(piles[0], x0, cnt, rows);
-                        if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("adding up the pileups of the GPUs", rc); }
-                    }
-                free(rows);
-                rows = NULL;
-            }
-            for (g = 1; (vcf || cons) && g < g_nstreams; g++) { /* ... and their events, which arrive normalised and stay as they are */
-                for (x0 = 0; x0 < n; x0 += chunk) {
-                    const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
-                    uint64_t total = 0;
-                    for (;;) {
-                        if (!evs && !(evs = (slamem_event *)malloc((size_t)ecap * sizeof(slamem_event)))) pipeline_fail("Out of memory");
-                        rc = slamem_pileup_events_host(piles[g], x0, cnt, 1, ecap, evs, sk, &total);
-                        if (rc != SLAMEM_ERR_CAPACITY || total <= ecap) break;
-                        free(evs);
-                        evs = NULL;
-                        ecap = total;
-                    }
-                    if (rc == SLAMEM_OK) rc = slamem_pileup_add_events_host(piles[0], evs, total);
-                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("adding up the indel events of the GPUs", rc); }
-                }
-                skipped[0] += sk[0]; skipped[1] += sk[1]; skipped[2] += sk[2]; /* (what GPU g could not store) */
-            }
-            for (x0 = 0; !cons && !depth && g_nstreams > 0 && x0 < n; x0 += chunk) {
-                const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
-                uint64_t total = 0, k = 0;
-                for (;;) { /* a range that selects more rows than there is room for says how many: once more with that room */
-                    if (!pos) {
-                        pos = (uint64_t *)malloc((size_t)cap * 8);
-                        rows = (uint32_t *)malloc((size_t)cap * 24);
-                        alleles = (uint8_t *)malloc((size_t)cap);
-                        if (gt) gts = (slamem_genotype *)malloc((size_t)cap * sizeof(slamem_genotype));
-                        if (!pos || !rows || !alleles || (gt && !gts)) pipeline_fail("Out of memory");
-                    }
-                    rc = gt ? slamem_pileup_genotypes_host(piles[0], x0, cnt, &gtp, cap, pos, rows, gts, &total)
-                            : slamem_pileup_sites_host(piles[0], x0, cnt, SLAMEM_SITES_VARIANT, (uint32_t)min_depth, (uint32_t)min_pct, cap, pos,
-                                                       rows, alleles, &total);
-                    if (rc != SLAMEM_ERR_CAPACITY || total <= cap) break;
-                    free(pos); free(rows); free(alleles); free(gts);
-                    gts = NULL;
-                    pos = NULL;
-                    cap = total;
-                }
-                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the variant sites from the GPU", rc); }
-                if (vcf) { /* the events of the same range, the pileup rows of their anchors, and the lines of both record by record */
-                    uint64_t etotal = 0, ek = 0, j;
-                    int rr = r;
-                    for (;;) {
-                        if (!evs) {
-                            evs = (slamem_event *)malloc((size_t)ecap * sizeof(slamem_event));
-                            anchors = (uint64_t *)malloc((size_t)ecap * 8);
-                            arows = (uint32_t *)malloc((size_t)ecap * 24);
-                            if (!evs || !anchors || !arows) pipeline_fail("Out of memory");
-                        } else if (!anchors) {
-                            anchors = (uint64_t *)malloc((size_t)ecap * 8);
-                            arows = (uint32_t *)malloc((size_t)ecap * 24);
-                            if (!anchors || !arows) pipeline_fail("Out of memory");
-                        }
-                        if (gt && !egts) {
-                            egts = (slamem_genotype *)malloc((size_t)ecap * sizeof(slamem_genotype));
-                            ecalled = (uint8_t *)malloc((size_t)ecap);
-                            if (!egts || !ecalled) pipeline_fail("Out of memory");
-                        }
-                        rc = slamem_pileup_events_host(piles[0], x0, cnt, 1, ecap, evs, sk, &etotal);
-                        if (rc != SLAMEM_ERR_CAPACITY || etotal <= ecap) break;
-                        free(evs); free(anchors); free(arows); free(egts); free(ecalled);
-                        evs = NULL; anchors = NULL; arows = NULL; egts = NULL; ecalled = NULL;
-                        ecap = etotal;
-                    }
-                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the indel events from the GPU", rc); }
-                    for (j = 0; j < etotal; j++) { /* the anchor row: the letter in front, or the event's own row at a record's start */
-                        const uint64_t p = evs[j].pos;
-                        while (rr + 1 < ref.num && p >= ref.merged_start[rr + 1]) rr++;
-                        anchors[j] = p > (ref.num > 1 ? ref.merged_start[rr] : 0) ? p - 1 : p;
-                    }
-                    rc = slamem_pileup_rows_at_host(piles[0], anchors, etotal, arows);
-                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the pileup rows of the indel events from the GPU", rc); }
-                    if (gt) { /* every event on its own against everything else at its anchor, on the GPU */
-                        rc = slamem_pileup_genotype_events_host(piles[0], evs, anchors, etotal, &gtp, egts, ecalled);
-                        if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("genotyping the indel events on the GPU", rc); }
-                    }
-                    while ((k < total || ek < etotal) && r < ref.num) {
-                        const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, end = start + ref.recs[r].size;
-                        uint64_t e = k, ee;
-                        while (k < total && pos[k] < start) k++; /* (a separator: no record's row) */
-                        while (ek < etotal && evs[ek].pos < start) ek++;
-                        for (e = k; e < total && pos[e] < end; e++) {}
-                        for (ee = ek; ee < etotal && evs[ee].pos < end; ee++) {}
-                        if (gt ? slh_format_vcf_gt_rows(&buf, ref.recs[r].name, start, ref.recs[r].size, ref.chars, pos + k, rows + k * 6,
-                                                        (const slh_genotype *)(gts + k), e - k, (const slh_event *)(evs + ek), arows + ek * 6,
-                                                        (const slh_genotype *)(egts + ek), ecalled + ek, ee - ek)
-                               : slh_format_vcf_rows(&buf, ref.recs[r].name, start, ref.recs[r].size, ref.chars, pos + k, rows + k * 6, alleles + k,
-                                                     e - k, (const slh_event *)(evs + ek), arows + ek * 6, ee - ek, (uint32_t)min_depth,
-                                                     (uint32_t)min_pct))
-                            pipeline_fail("Out of memory");
-                        k = e;
-                        ek = ee;
-                        if (end > x0 + cnt) break; /* (the record goes on in the next range) */
-                        r++;
-                    }
-                    k = total;
-                }
-                while (k < total && r < ref.num) { /* the rows of one record after the other */
-                    const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, end = start + ref.recs[r].size;
-                    uint64_t e = k;
-                    if (pos[k] >= end) { r++; continue; }
-                    if (pos[k] < start) { k++; continue; } /* (a separator: no record's row) */
-                    while (e < total && pos[e] < end) e++;
-                    if (slh_format_site_rows(&buf, ref.recs[r].name, start, ref.chars, pos + k, rows + k * 6, alleles + k, e - k))
-                        pipeline_fail("Out of memory");
-                    k = e;
-                }
-                if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
-                if (g_writer.failed) pipeline_fail("Cannot write output file");
-            }
-            if (cons && g_nstreams > 0) {
-                /* -cons: GPU 0 builds the consensus of the summed table and events range after range; the bounds cut it at the
-                   records' first rows and ends (a separator's row, and an insertion in front of it, is no record's), and a record
-                   is written when its last piece is there */
-                uint64_t ccap = (chunk < n ? chunk : n) + (chunk < n ? chunk : n) / 64 + 64, rlen = 0, rcap = 0, stats[5] = {0, 0, 0, 0, 0};
-                uint64_t *bnd = (uint64_t *)malloc(((size_t)ref.num * 2 + 2) * 16), *offs, none = 0;
-                uint8_t *seq = NULL;
-                char *rec = NULL;
-                if (!bnd) pipeline_fail("Out of memory");
-                offs = bnd + (size_t)ref.num * 2 + 2;
-                for (x0 = 0; x0 < n; x0 += chunk) {
-                    const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
-                    uint64_t total = 0, st[5], m = 0, j;
-                    int rr;
-                    for (rr = r; rr < ref.num; rr++) { /* the pieces of the records inside the range */
-                        const uint64_t start = ref.num > 1 ? ref.merged_start[rr] : 0, end = start + ref.recs[rr].size;
-                        if (start >= x0 + cnt) break;
-                        bnd[m++] = start > x0 ? start : x0;
-                        bnd[m++] = end < x0 + cnt ? end : x0 + cnt;
-                        if (end > x0 + cnt) break;
-                    }
-                    for (;;) {
-                        if (!seq && !(seq = (uint8_t *)slh_big_malloc((size_t)ccap))) pipeline_fail("Out of memory");
-                        rc = slamem_pileup_consensus_host(piles[0], x0, cnt, (uint32_t)min_depth, ccap, seq, bnd, m, offs, st, &total);
-                        if (rc != SLAMEM_ERR_CAPACITY || total <= ccap) break;
-                        free(seq);
-                        seq = NULL;
-                        ccap = total;
-                    }
-                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the consensus from the GPU", rc); }
-                    for (j = 0; j < 5; j++) stats[j] += st[j];
-                    for (j = 0; j < m; j += 2) {
-                        const uint64_t end = (ref.num > 1 ? ref.merged_start[r] : 0) + ref.recs[r].size, got = offs[j + 1] - offs[j];
-                        if (rlen + got > rcap) {
-                            char *more;
-                            rcap = (rlen + got) * 2 + 64;
-                            if (!(more = (char *)realloc(rec, (size_t)rcap))) pipeline_fail("Out of memory");
-                            rec = more;
-                        }
-                        if (got) memcpy(rec + rlen, seq + offs[j], (size_t)got);
-                        rlen += got;
-                        if (bnd[j + 1] < end) break; /* (the record goes on in the next range) */
-                        if (slh_format_fasta_record(&buf, ref.recs[r].name, rec ? rec : "", rlen)) pipeline_fail("Out of memory");
-                        rlen = 0;
-                        r++;
-                    }
-                    if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
-                    if (g_writer.failed) pipeline_fail("Cannot write output file");
-                }
-                free(bnd); free(seq); free(rec);
-                fprintf(stderr, "> Consensus: %llu positions uncalled, %llu called unlike the reference, %llu deleted, %llu insertions of %llu letters\n",
-                        (unsigned long long)stats[0], (unsigned long long)stats[1], (unsigned long long)stats[2], (unsigned long long)stats[3],
-                        (unsigned long long)stats[4]);
-                rc = slamem_pileup_events_host(piles[0], 0, 0, 1, 0, NULL, sk, &none); /* (no event: GPU 0's skipped counters) */
-                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the indel events from the GPU", rc); }
-            }
-            if (depth && g_nstreams > 0) {
-                /* -depth: GPU 0 turns the summed table into runs of equal depth range after range; the bounds are the first rows
-                   and the ends of the records' pieces inside the range (a separator's row is no record's) and with -win the
-                   windows' borders between them, and cum at the bounds gives the windows' means and the records' summaries */
-                uint64_t dcap = window ? 0 : 1ull << 20, bcap = 0, *bnd = NULL, *cum = NULL;
-                uint64_t rec_sum = 0, rec_cov = 0, wacc = 0; /* of record r so far; -win: of its window that is still open */
-                slamem_depth_run *runs = NULL;
-                slh_depth_pending pend = {0, 0, 0, 0};
-                slh_buffer sbuf = {0, 0, 0};
-                for (x0 = 0; x0 < n; x0 += chunk) {
-                    const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
-                    uint64_t total = 0, m = 0, j;
-                    int rr;
-                    for (rr = r; rr < ref.num; rr++) { /* the pieces of the records inside the range */
-                        const uint64_t start = ref.num > 1 ? ref.merged_start[rr] : 0, end = start + ref.recs[rr].size;
-                        const uint64_t a = start > x0 ? start : x0, b = end < x0 + cnt ? end : x0 + cnt;
-                        const uint64_t inside = window && b > a ? (b - start - 1) / window - (a - start) / window : 0;
-                        if (start >= x0 + cnt) break;
-                        if (m + inside + 2 > bcap) {
-                            uint64_t *more;
-                            bcap = (m + inside + 2) * 2;
-                            if (!(more = (uint64_t *)realloc(bnd, (size_t)bcap * 8))) pipeline_fail("Out of memory");
-                            bnd = more;
-                        }
-                        bnd[m++] = a;
-                        for (j = 1; j <= inside; j++) bnd[m++] = start + ((a - start) / window + j) * window;
-                        bnd[m++] = b;
-                        if (end > x0 + cnt) break;
-                    }
-                    free(cum);
-                    if (!(cum = (uint64_t *)malloc((size_t)(m + 1) * 16))) pipeline_fail("Out of memory");
-                    for (;;) { /* a range of more runs than there is room for says how many: once more with that room */
-                        if (dcap && !runs && !(runs = (slamem_depth_run *)slh_big_malloc((size_t)dcap * sizeof(slamem_depth_run))))
-                            pipeline_fail("Out of memory");
-                        rc = slamem_pileup_depth_runs_host(piles[0], x0, cnt, levels, (uint32_t)num_levels, (uint32_t)min_depth, dcap, runs, bnd,
-                                                           m, cum, &total);
-                        if (window && rc == SLAMEM_ERR_CAPACITY) rc = SLAMEM_OK; /* (the windows need the sums alone) */
-                        if (rc != SLAMEM_ERR_CAPACITY || total <= dcap) break;
-                        free(runs);
-                        runs = NULL;
-                        dcap = total;
-                    }
-                    if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the depth runs from the GPU", rc); }
-                    for (j = 0; j < m;) {
-                        const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, size = ref.recs[r].size, end = start + size;
-                        const uint64_t a = bnd[j], ja = j;
-                        uint64_t b;
-                        for (j++; bnd[j] < end && bnd[j] < x0 + cnt; j++) {} /* (the piece's last bound: the record's end or the range's) */
-                        b = bnd[j];
-                        if (window) { /* the windows that end in the piece; what is behind the last of them waits for the next range */
-                            const uint64_t k = j - ja - (b == end || (b - start) % window == 0 ? 0 : 1);
-                            const uint64_t sum0 = cum[2 * ja] - wacc;
-                            if (slh_format_depth_windows(&buf, ref.recs[r].name, size, window, (a - start) / window, sum0, cum + 2 * (ja + 1), k))
-                                pipeline_fail("Out of memory");
-                            wacc = cum[2 * j] - (k ? cum[2 * (ja + k)] : sum0);
-                        } else if (slh_format_depth_runs(&buf, ref.recs[r].name, start, a, b, (const slh_depth_run *)runs, total, &pend)) {
-                            pipeline_fail("Out of memory");
-                        }
-                        rec_sum += cum[2 * j] - cum[2 * ja];
-                        rec_cov += cum[2 * j + 1] - cum[2 * ja + 1];
-                        j++;
-                        if (b < end) break; /* (the record goes on in the next range) */
-                        if (slh_format_depth_flush(&buf, ref.recs[r].name, &pend) ||
-                            slh_format_depth_summary(&sbuf, ref.recs[r].name, size, rec_cov, rec_sum))
-                            pipeline_fail("Out of memory");
-                        rec_sum = rec_cov = wacc = 0;
-                        r++;
-                    }
-                    if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
-                    if (g_writer.failed) pipeline_fail("Cannot write output file");
-                }
-                if (sbuf.len) fwrite(sbuf.data, 1, sbuf.len, stderr);
-                slh_buffer_free(&sbuf);
-                free(bnd); free(cum); free(runs);
-            }
-            free(pos); free(rows); free(alleles);
-            free(evs); free(anchors); free(arows);
-            free(gts); free(egts); free(ecalled);
-            if ((vcf || cons) && g_nstreams > 0) {
-                skipped[0] += sk[0]; skipped[1] += sk[1]; skipped[2] += sk[2]; /* (GPU 0's, the merge included) */
-                if (skipped[0] | skipped[1] | skipped[2])
-                    fprintf(stderr, "> WARNING: indel observations that are in no event: %llu insertions of more than 31 letters, %llu without "
-                                    "room in the event table, %llu malformed%s\n", (unsigned long long)skipped[0],
-                            (unsigned long long)skipped[1], (unsigned long long)skipped[2],
-                            skipped[1] ? " (a larger table: -evs)" : "");
-            }
-            t_format += now_s() - tp;
-        } else if (o.match_type == 8) {
-            /* the table, in chunks of at most 16 M rows (24 bytes a row: the table of a 100 Mbp text never sits in one buffer):
-               the GPUs' tables added up, then a line per row of a record that has a count */
-            const uint64_t chunk = 16ull << 20, n = ref.total;
-            uint32_t *rows = NULL, *more = NULL;
-            uint64_t x0;
-            int r = 0;
-            double tp = now_s();
-            if (g_nstreams > 0) {
-                rows = (uint32_t *)slh_big_malloc((size_t)(chunk < n ? chunk : n) * 24 + 24);
-                if (ngpu > 1) more = (uint32_t *)slh_big_malloc((size_t)(chunk < n ? chunk : n) * 24 + 24);
-                if (!rows || (ngpu > 1 && !more)) pipeline_fail("Out of memory");
-            }
-            for (x0 = 0; g_nstreams > 0 && x0 < n; x0 += chunk) {
-                const uint64_t cnt = n - x0 < chunk ? n - x0 : chunk;
-                uint64_t x = x0, k;
-                rc = slamem_pileup_counts_host(piles[0], x0, cnt, rows);
-                for (g = 1; rc == SLAMEM_OK && g < g_nstreams; g++) {
-                    rc = slamem_pileup_counts_host(piles[g], x0, cnt, more);
-                    for (k = 0; rc == SLAMEM_OK && k < cnt * 6; k++) rows[k] += more[k];
-                }
-                if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the pileup from the GPU", rc); }
-                while (x < x0 + cnt && r < ref.num) { /* the pieces of the records inside the chunk; the separators are skipped */
-                    const uint64_t start = ref.num > 1 ? ref.merged_start[r] : 0, end = start + ref.recs[r].size;
-                    uint64_t a, b;
-                    if (end <= x) { r++; continue; }
-                    a = start > x ? start : x;
-                    b = end < x0 + cnt ? end : x0 + cnt;
-                    if (a >= x0 + cnt) break;
-                    if (slh_format_pile_rows(&buf, ref.recs[r].name, (uint32_t)(a - start) + 1u, ref.chars + a, rows + (a - x0) * 6, b - a))
-                        pipeline_fail("Out of memory");
-                    x = b;
-                    if (b == end) r++;
-                }
-                if (writer_push(&g_writer, &buf)) pipeline_fail("Out of memory");
-                if (g_writer.failed) pipeline_fail("Cannot write output file");
-            }
-            free(rows);
-            free(more);
-            t_format += now_s() - tp;
-        }
-        if (dedup && g_nstreams > 0) { /* (one GPU: its counters are the run's) */
-            uint64_t dd[4] = {0, 0, 0, 0};
-            rc = slamem_pileup_dedup_stats(piles[0], dd);
-            if (rc != SLAMEM_OK) { shutdown_pipeline(); gpu_fail("reading the duplicate filter's counters from the GPU", rc); }
-            fprintf(stderr, "> Duplicates: %llu candidate reads, %llu duplicates (%.2f %%) not counted, %llu without room in the duplicate "
-                            "table%s\n", (unsigned long long)dd[0], (unsigned long long)dd[1], dd[0] ? 100.0 * (double)dd[1] / (double)dd[0] : 0.0,
-                    (unsigned long long)dd[2], dd[2] ? " (a larger table: -dslots)" : "");
-        }
-        writer_finish(&g_writer);
-        t_write = g_writer.seconds;
+        tg = now_s();
+        submit_batches(R, &submitted);
+        memset(&v, 0, sizeof(v));
+        v.q = &R->qsets[br->f];
+        v.ref = &R->ref;
+        v.quals = ld->quals[br->f];
+        v.first_rec = br->first;
+        v.strands = R->strands;
+        if (!fetch_batch(R, bi, &v)) R->total_matches += (long long)v.total; /* (the segments piled) */
+        R->inflight[bi % (size_t)R->ngpu]--;
+        R->t_gpu += now_s() - tg; /* time the main thread waited for the GPUs */
+        if (R->p.o.match_type == 8) continue;
+        tg = now_s();
+        format_batch(R, &v, (uint64_t)(br->last - br->first) * (uint64_t)R->strands);
         if (g_writer.failed) pipeline_fail("Cannot write output file");
-        if (log_limit != 0 && o.match_type != 8 && (long)total_queries * strands > log_limit)
-            say(":: ... (%ld more strand blocks matched; set SLAMEM_VERBOSE=1 for a line each)\n",
-                   (long)total_queries * strands - log_limit);
+        R->t_format += now_s() - tg;
     }
-    double t_end0 = now_s(), t_end1;
-    if (total_queries != 1) /* slamem.c:210-212 (the reference divides by zero when nothing matched) */
-        printf(":: Average %d %ss found per query sequence (total = %lld, avg size = %d bp)\n",
-               (int)(total_matches / total_queries), MATCH_NAME(o.match_type), total_matches,
-               (int)(total_matches ? total_sum / total_matches : 0));
+    free(R->ranges);
+    R->ranges = NULL;
+}
+
+/* the loader is done: the "successfully loaded" line, then what was held back, and what it found wrong with the query files */
+static void check_loader(run_t *R) {
+    loader_t *ld = R->ld;
+    release_stdout();
+    R->total_queries = ld->total_queries;
+    if (ld->failed) pipeline_fail("Internal error: the query files came in more pieces than planned");
+    if (ld->invalid || ld->ready == 0) {
+        shutdown_pipeline();
+        fclose(R->out);
+        remove(R->out_name);
+        /* the loader thread met a query file that is no valid FASTQ (it said so), or ran out of memory; or slamem.c:648 (an
+           overlapped run only knows it now) */
+        exit_message(ld->invalid == 1 ? "A query file is not valid FASTQ" : ld->invalid ? "Out of memory" : "No query files provided");
+    }
+    if (ld->fasta_seen) fprintf(stderr, "> WARNING: option -bq %d has no effect on FASTA queries: they carry no base qualities\n", R->p.min_bq);
+}
+
+/* ------------------------------------------------------------------------------------------------ */
+/* the read-outs of the pileup: GPU 0's table, range after range of readout_rows rows                */
+/* ------------------------------------------------------------------------------------------------ */
+
+/* A read-out that has more to hand back than there is room for says SLAMEM_ERR_CAPACITY and how much: it is asked once more
+ * with that room.  bufs: the arrays the call fills, *cap elements each; one that is NULL is allocated, and all are released
+ * before they grow. */
+typedef struct { void **p; size_t elem; int big; } grow_buf;
+typedef int (*fetch_fn)(void *ctx, uint64_t cap, uint64_t *total);
+static int fetch_growing(uint64_t *cap, const grow_buf *bufs, int nbufs, fetch_fn call, void *ctx, uint64_t *total) {
+    for (;;) {
+        int k, rc;
+        for (k = 0; k < nbufs; k++)
+            if (*cap && !*bufs[k].p) {
+                const size_t bytes = (size_t)*cap * bufs[k].elem;
+                if (!(*bufs[k].p = bufs[k].big ? slh_big_malloc(bytes) : malloc(bytes))) pipeline_fail("Out of memory");
+            }
+        rc = call(ctx, *cap, total);
+        if (rc != SLAMEM_ERR_CAPACITY || *total <= *cap) return rc;
+        for (k = 0; k < nbufs; k++) { free(*bufs[k].p); *bufs[k].p = NULL; }
+        *cap = *total;
+    }
+}
+
+/* the pieces of the records inside rows [x0, x0 + cnt), in R->pcs; *r goes on to the record the next range begins with */
+static int pieces_of_range(run_t *R, int *r, uint64_t x0, uint64_t cnt) {
+    uint64_t x = x0;
+    int m = 0;
+    while (slh_next_piece(R->ref.recs, R->ref.merged_start, R->ref.num, r, &x, x0 + cnt, &R->pcs[m])) m++;
+    return m;
+}
+
+typedef struct { /* a range of a pileup and where its events go */
+    slamem_pileup *pile;
+    uint64_t x0, cnt, sk[3];
+    slamem_event *evs;
+} events_call;
+static int fetch_events(void *ctx, uint64_t cap, uint64_t *total) {
+    events_call *c = (events_call *)ctx;
+    return slamem_pileup_events_host(c->pile, c->x0, c->cnt, 1, cap, c->evs, c->sk, total);
+}
+
+#define FOR_RANGES(x0, cnt) for (x0 = 0; x0 < n && (cnt = n - x0 < R->readout_rows ? n - x0 : R->readout_rows) > 0; x0 += R->readout_rows)
+
+/* the tables of GPUs 1.. are added into GPU 0's, and their events, which arrive normalised and stay as they are */
+static void merge_gpu_tables(run_t *R) {
+    const uint64_t n = R->ref.total;
+    const int with_events = R->p.vcf || R->p.cons;
+    uint64_t x0, cnt, ecap = 1ull << 16, total;
+    events_call ec;
+    const grow_buf ebufs[1] = {{(void **)&ec.evs, sizeof(slamem_event), 0}};
+    uint32_t *rows;
+    int g, rc;
+    if (g_nstreams < 2) return;
+    memset(&ec, 0, sizeof(ec));
+    rows = (uint32_t *)slh_big_malloc((size_t)(R->readout_rows < n ? R->readout_rows : n) * 24 + 24);
+    if (!rows) pipeline_fail("Out of memory");
+    for (g = 1; g < g_nstreams; g++)
+        FOR_RANGES(x0, cnt) {
+            rc = slamem_pileup_counts_host(R->piles[g], x0, cnt, rows);
+            if (rc == SLAMEM_OK) rc = slamem_pileup_add_counts_host(R->piles[0], x0, cnt, rows);
+            if (rc != SLAMEM_OK) pipeline_gpu_fail("adding up the pileups of the GPUs", rc);
+        }
+    free(rows);
+    for (g = 1; with_events && g < g_nstreams; g++) {
+        FOR_RANGES(x0, cnt) {
+            ec.pile = R->piles[g]; ec.x0 = x0; ec.cnt = cnt;
+            rc = fetch_growing(&ecap, ebufs, 1, fetch_events, &ec, &total);
+            if (rc == SLAMEM_OK) rc = slamem_pileup_add_events_host(R->piles[0], ec.evs, total);
+            if (rc != SLAMEM_OK) pipeline_gpu_fail("adding up the indel events of the GPUs", rc);
+        }
+        R->skipped[0] += ec.sk[0]; R->skipped[1] += ec.sk[1]; R->skipped[2] += ec.sk[2]; /* (what GPU g could not store) */
+    }
+    free(ec.evs);
+}
+
+/* -vcf, -cons: GPU 0's own counters (the merge included) come on top of the other GPUs' */
+static void warn_skipped(run_t *R, const uint64_t sk[3]) {
+    const uint64_t s0 = R->skipped[0] + sk[0], s1 = R->skipped[1] + sk[1], s2 = R->skipped[2] + sk[2];
+    if (s0 | s1 | s2)
+        fprintf(stderr, "> WARNING: indel observations that are in no event: %llu insertions of more than 31 letters, %llu without "
+                        "room in the event table, %llu malformed%s\n", (unsigned long long)s0, (unsigned long long)s1,
+                (unsigned long long)s2, s1 ? " (a larger table: -evs)" : "");
+}
+
+/* -pile: a line per row of a record that has a count; the GPUs' tables are added up here, range after range (24 bytes a row:
+ * the table of a 100 Mbp text never sits in one buffer) */
+static void write_pile(run_t *R) {
+    const uint64_t n = R->ref.total;
+    const size_t bytes = (size_t)(R->readout_rows < n ? R->readout_rows : n) * 24 + 24;
+    uint32_t *rows = (uint32_t *)slh_big_malloc(bytes), *more = R->ngpu > 1 ? (uint32_t *)slh_big_malloc(bytes) : NULL;
+    uint64_t x0, cnt, x, k;
+    slh_piece pc;
+    int r = 0, g, rc;
+    if (!rows || (R->ngpu > 1 && !more)) pipeline_fail("Out of memory");
+    FOR_RANGES(x0, cnt) {
+        rc = slamem_pileup_counts_host(R->piles[0], x0, cnt, rows);
+        for (g = 1; rc == SLAMEM_OK && g < g_nstreams; g++) {
+            rc = slamem_pileup_counts_host(R->piles[g], x0, cnt, more);
+            for (k = 0; rc == SLAMEM_OK && k < cnt * 6; k++) rows[k] += more[k];
+        }
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the pileup from the GPU", rc);
+        for (x = x0; slh_next_piece(R->ref.recs, R->ref.merged_start, R->ref.num, &r, &x, x0 + cnt, &pc);)
+            if (slh_format_pile_rows(&R->buf, R->ref.recs[pc.rec].name, (uint32_t)(pc.a - pc.start) + 1u, R->ref.chars + pc.a,
+                                     rows + (pc.a - x0) * 6, pc.b - pc.a))
+                pipeline_fail("Out of memory");
+        push_text(R);
+    }
+    free(rows);
+    free(more);
+}
+
+typedef struct { /* -sites, -vcf: the selected rows of a range */
+    run_t *R;
+    uint64_t x0, cnt, *pos;
+    uint32_t *rows;
+    uint8_t *alleles;
+    slamem_genotype *gts;
+} sites_call;
+static int fetch_sites(void *ctx, uint64_t cap, uint64_t *total) {
+    sites_call *c = (sites_call *)ctx;
+    const slh_run *p = &c->R->p;
+    return p->gt ? slamem_pileup_genotypes_host(c->R->piles[0], c->x0, c->cnt, &c->R->gtp, cap, c->pos, c->rows, c->gts, total)
+                 : slamem_pileup_sites_host(c->R->piles[0], c->x0, c->cnt, SLAMEM_SITES_VARIANT, (uint32_t)p->min_depth,
+                                            (uint32_t)p->min_pct, cap, c->pos, c->rows, c->alleles, total);
+}
+
+/* -sites, -vcf (with and without -gt): GPU 0 applies the rule to the summed table range after range and only the selected rows
+ * come back, a line each; -vcf: with the events of the same range, the pileup rows of their anchors, and the lines of both
+ * record by record */
+static void write_sites_or_vcf(run_t *R) {
+    const slh_run *p = &R->p;
+    const slh_seqset *ref = &R->ref;
+    const uint64_t n = ref->total;
+    uint64_t x0, cnt, cap = 1ull << 20, ecap = 1ull << 16, total, etotal, k, ek, e, ee, j, *anchors = NULL;
+    uint32_t *arows = NULL;
+    slamem_genotype *egts = NULL; /* -gt: the genotypes of the events, and which events are called */
+    uint8_t *ecalled = NULL;
+    sites_call sc;
+    events_call ec;
+    const grow_buf sbufs[4] = {{(void **)&sc.pos, 8, 0}, {(void **)&sc.rows, 24, 0}, {(void **)&sc.alleles, 1, 0}, {(void **)&sc.gts, sizeof(slamem_genotype), 0}};
+    const grow_buf ebufs[5] = {{(void **)&ec.evs, sizeof(slamem_event), 0}, {(void **)&anchors, 8, 0}, {(void **)&arows, 24, 0},
+                               {(void **)&egts, sizeof(slamem_genotype), 0}, {(void **)&ecalled, 1, 0}};
+    int r = 0, m, pi, rc;
+    memset(&sc, 0, sizeof(sc));
+    memset(&ec, 0, sizeof(ec));
+    sc.R = R;
+    ec.pile = R->piles[0];
+    if (p->vcf && (p->gt ? slh_format_vcf_gt_header(&R->buf, ref->recs, ref->num) : slh_format_vcf_header(&R->buf, ref->recs, ref->num)))
+        pipeline_fail("Out of memory");
+    FOR_RANGES(x0, cnt) {
+        sc.x0 = ec.x0 = x0;
+        sc.cnt = ec.cnt = cnt;
+        rc = fetch_growing(&cap, sbufs, p->gt ? 4 : 3, fetch_sites, &sc, &total);
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the variant sites from the GPU", rc);
+        m = pieces_of_range(R, &r, x0, cnt);
+        etotal = 0;
+        if (p->vcf) {
+            rc = fetch_growing(&ecap, ebufs, p->gt ? 5 : 3, fetch_events, &ec, &etotal);
+            if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the indel events from the GPU", rc);
+            for (j = 0, pi = 0; j < etotal; j++) { /* the anchor row: the letter in front, or the event's own row at a record's start */
+                const uint64_t x = ec.evs[j].pos;
+                while (pi + 1 < m && x >= R->pcs[pi + 1].start) pi++;
+                anchors[j] = x > (m ? R->pcs[pi].start : 0) ? x - 1 : x;
+            }
+            rc = slamem_pileup_rows_at_host(R->piles[0], anchors, etotal, arows);
+            if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the pileup rows of the indel events from the GPU", rc);
+            if (p->gt) { /* every event on its own against everything else at its anchor, on the GPU */
+                rc = slamem_pileup_genotype_events_host(R->piles[0], ec.evs, anchors, etotal, &R->gtp, egts, ecalled);
+                if (rc != SLAMEM_OK) pipeline_gpu_fail("genotyping the indel events on the GPU", rc);
+            }
+        }
+        for (pi = 0, k = ek = 0; pi < m && (k < total || ek < etotal); pi++, k = e, ek = ee) { /* the rows and events of one record after the other */
+            const slh_piece *pc = &R->pcs[pi];
+            const char *name = ref->recs[pc->rec].name;
+            const uint32_t size = ref->recs[pc->rec].size;
+            while (k < total && sc.pos[k] < pc->start) k++; /* (a separator: no record's row) */
+            while (ek < etotal && ec.evs[ek].pos < pc->start) ek++;
+            for (e = k; e < total && sc.pos[e] < pc->b; e++) {}
+            for (ee = ek; ee < etotal && ec.evs[ee].pos < pc->start + size; ee++) {}
+            if (e == k && ee == ek) continue;
+            if (!p->vcf ? slh_format_site_rows(&R->buf, name, pc->start, ref->chars, sc.pos + k, sc.rows + k * 6, sc.alleles + k, e - k)
+                : p->gt ? slh_format_vcf_gt_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6,
+                                                 (const slh_genotype *)(sc.gts + k), e - k, (const slh_event *)(ec.evs + ek), arows + ek * 6,
+                                                 (const slh_genotype *)(egts + ek), ecalled + ek, ee - ek)
+                        : slh_format_vcf_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6, sc.alleles + k, e - k,
+                                              (const slh_event *)(ec.evs + ek), arows + ek * 6, ee - ek, (uint32_t)p->min_depth,
+                                              (uint32_t)p->min_pct))
+                pipeline_fail("Out of memory");
+        }
+        push_text(R);
+    }
+    free(sc.pos); free(sc.rows); free(sc.alleles); free(sc.gts);
+    free(ec.evs); free(anchors); free(arows); free(egts); free(ecalled);
+    if (p->vcf) warn_skipped(R, ec.sk);
+}
+
+typedef struct { /* -cons: the consensus of a range, cut at the bounds */
+    run_t *R;
+    uint64_t x0, cnt, *bnd, m, *offs, st[5];
+    uint8_t *seq;
+} cons_call;
+static int fetch_consensus(void *ctx, uint64_t cap, uint64_t *total) {
+    cons_call *c = (cons_call *)ctx;
+    return slamem_pileup_consensus_host(c->R->piles[0], c->x0, c->cnt, (uint32_t)c->R->p.min_depth, cap, c->seq, c->bnd, c->m, c->offs,
+                                        c->st, total);
+}
+
+/* -cons: GPU 0 builds the consensus of the summed table and events range after range; the bounds cut it at the records' first
+ * rows and ends (a separator's row, and an insertion in front of it, is no record's), and a record is written when its last
+ * piece is there */
+static void write_cons(run_t *R) {
+    const slh_seqset *ref = &R->ref;
+    const uint64_t n = ref->total, most = R->readout_rows < n ? R->readout_rows : n;
+    uint64_t x0, cnt, ccap = most + most / 64 + 64, rlen = 0, rcap = 0, stats[5] = {0, 0, 0, 0, 0}, total, none = 0, j;
+    cons_call cc;
+    events_call ec;
+    const grow_buf bufs[1] = {{(void **)&cc.seq, 1, 1}};
+    char *rec = NULL;
+    int r = 0, m, pi, rc;
+    memset(&cc, 0, sizeof(cc));
+    memset(&ec, 0, sizeof(ec));
+    cc.R = R;
+    cc.bnd = (uint64_t *)malloc(((size_t)ref->num * 2 + 2) * 16);
+    if (!cc.bnd) pipeline_fail("Out of memory");
+    cc.offs = cc.bnd + (size_t)ref->num * 2 + 2;
+    FOR_RANGES(x0, cnt) {
+        m = pieces_of_range(R, &r, x0, cnt);
+        for (pi = 0; pi < m; pi++) { cc.bnd[2 * pi] = R->pcs[pi].a; cc.bnd[2 * pi + 1] = R->pcs[pi].b; }
+        cc.x0 = x0; cc.cnt = cnt; cc.m = 2 * (uint64_t)m;
+        rc = fetch_growing(&ccap, bufs, 1, fetch_consensus, &cc, &total);
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the consensus from the GPU", rc);
+        for (j = 0; j < 5; j++) stats[j] += cc.st[j];
+        for (pi = 0; pi < m; pi++) {
+            const uint64_t got = cc.offs[2 * pi + 1] - cc.offs[2 * pi];
+            if (rlen + got > rcap) {
+                char *more;
+                rcap = (rlen + got) * 2 + 64;
+                if (!(more = (char *)realloc(rec, (size_t)rcap))) pipeline_fail("Out of memory");
+                rec = more;
+            }
+            if (got) memcpy(rec + rlen, cc.seq + cc.offs[2 * pi], (size_t)got);
+            rlen += got;
+            if (!R->pcs[pi].ends_record) break; /* (the record goes on in the next range) */
+            if (slh_format_fasta_record(&R->buf, ref->recs[R->pcs[pi].rec].name, rec ? rec : "", rlen)) pipeline_fail("Out of memory");
+            rlen = 0;
+        }
+        push_text(R);
+    }
+    free(cc.bnd); free(cc.seq); free(rec);
+    fprintf(stderr, "> Consensus: %llu positions uncalled, %llu called unlike the reference, %llu deleted, %llu insertions of %llu letters\n",
+            (unsigned long long)stats[0], (unsigned long long)stats[1], (unsigned long long)stats[2], (unsigned long long)stats[3],
+            (unsigned long long)stats[4]);
+    ec.pile = R->piles[0];
+    rc = fetch_events(&ec, 0, &none); /* (no event: GPU 0's skipped counters) */
+    if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the indel events from the GPU", rc);
+    warn_skipped(R, ec.sk);
+}
+
+typedef struct { /* -depth: the runs of a range, and the sums at the bounds */
+    run_t *R;
+    uint64_t x0, cnt, *bnd, m, *cum;
+    slamem_depth_run *runs;
+} depth_call;
+static int fetch_depth_runs(void *ctx, uint64_t cap, uint64_t *total) {
+    depth_call *c = (depth_call *)ctx;
+    const slh_run *p = &c->R->p;
+    return slamem_pileup_depth_runs_host(c->R->piles[0], c->x0, c->cnt, p->levels, (uint32_t)p->num_levels, (uint32_t)p->min_depth, cap,
+                                         c->runs, c->bnd, c->m, c->cum, total);
+}
+
+/* -win: the windows' borders of a record that lie inside its piece [a, b) */
+static uint64_t borders_inside(const slh_piece *pc, uint64_t window) {
+    return window ? (pc->b - pc->start - 1) / window - (pc->a - pc->start) / window : 0;
+}
+
+/* -depth: GPU 0 turns the summed table into runs of equal depth range after range; the bounds are the first rows and the ends of
+ * the records' pieces inside the range (a separator's row is no record's) and with -win the windows' borders between them, and
+ * cum at the bounds gives the windows' means and the records' summaries */
+static void write_depth(run_t *R) {
+    const slh_seqset *ref = &R->ref;
+    const uint64_t n = ref->total, window = R->p.window;
+    uint64_t x0, cnt, dcap = 1ull << 20, bcap = 0, total, j, ja, need;
+    uint64_t rec_sum = 0, rec_cov = 0, wacc = 0; /* of the record so far; -win: of its window that is still open */
+    depth_call dc;
+    const grow_buf bufs[1] = {{(void **)&dc.runs, sizeof(slamem_depth_run), 1}};
+    slh_depth_pending pend = {0, 0, 0, 0};
+    slh_buffer sbuf = {0, 0, 0};
+    int r = 0, m, pi, rc;
+    memset(&dc, 0, sizeof(dc));
+    dc.R = R;
+    FOR_RANGES(x0, cnt) {
+        m = pieces_of_range(R, &r, x0, cnt);
+        for (pi = 0, need = 0; pi < m; pi++) need += borders_inside(&R->pcs[pi], window) + 2;
+        if (need > bcap) {
+            uint64_t *more;
+            bcap = need * 2;
+            if (!(more = (uint64_t *)realloc(dc.bnd, (size_t)bcap * 8))) pipeline_fail("Out of memory");
+            dc.bnd = more;
+        }
+        for (pi = 0, dc.m = 0; pi < m; pi++) {
+            const slh_piece *pc = &R->pcs[pi];
+            const uint64_t inside = borders_inside(pc, window);
+            dc.bnd[dc.m++] = pc->a;
+            for (j = 1; j <= inside; j++) dc.bnd[dc.m++] = pc->start + ((pc->a - pc->start) / window + j) * window;
+            dc.bnd[dc.m++] = pc->b;
+        }
+        free(dc.cum);
+        if (!(dc.cum = (uint64_t *)malloc((size_t)(dc.m + 1) * 16))) pipeline_fail("Out of memory");
+        dc.x0 = x0; dc.cnt = cnt;
+        /* a range of more runs than there is room for says how many: once more with that room */
+        rc = window ? fetch_depth_runs(&dc, 0, &total) : fetch_growing(&dcap, bufs, 1, fetch_depth_runs, &dc, &total);
+        if (window && rc == SLAMEM_ERR_CAPACITY) rc = SLAMEM_OK; /* (the windows need the sums alone) */
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the depth runs from the GPU", rc);
+        for (pi = 0, j = 0; pi < m; pi++, j++) {
+            const slh_piece *pc = &R->pcs[pi];
+            const char *name = ref->recs[pc->rec].name;
+            const uint64_t size = ref->recs[pc->rec].size;
+            ja = j;
+            j += borders_inside(pc, window) + 1; /* (the piece's last bound: the record's end or the range's) */
+            if (window) { /* the windows that end in the piece; what is behind the last of them waits for the next range */
+                const uint64_t k = j - ja - (pc->ends_record || (pc->b - pc->start) % window == 0 ? 0 : 1);
+                const uint64_t sum0 = dc.cum[2 * ja] - wacc;
+                if (slh_format_depth_windows(&R->buf, name, size, window, (pc->a - pc->start) / window, sum0, dc.cum + 2 * (ja + 1), k))
+                    pipeline_fail("Out of memory");
+                wacc = dc.cum[2 * j] - (k ? dc.cum[2 * (ja + k)] : sum0);
+            } else if (slh_format_depth_runs(&R->buf, name, pc->start, pc->a, pc->b, (const slh_depth_run *)dc.runs, total, &pend)) {
+                pipeline_fail("Out of memory");
+            }
+            rec_sum += dc.cum[2 * j] - dc.cum[2 * ja];
+            rec_cov += dc.cum[2 * j + 1] - dc.cum[2 * ja + 1];
+            if (!pc->ends_record) break; /* (the record goes on in the next range) */
+            if (slh_format_depth_flush(&R->buf, name, &pend) || slh_format_depth_summary(&sbuf, name, size, rec_cov, rec_sum))
+                pipeline_fail("Out of memory");
+            rec_sum = rec_cov = wacc = 0;
+        }
+        push_text(R);
+    }
+    if (sbuf.len) fwrite(sbuf.data, 1, sbuf.len, stderr);
+    slh_buffer_free(&sbuf);
+    free(dc.bnd); free(dc.cum); free(dc.runs);
+}
+
+/* the read-out of the mode, and the duplicate filter's counters */
+static void write_pileup(run_t *R) {
+    const slh_run *p = &R->p;
+    const double t0 = now_s();
+    int rc;
+    if (g_nstreams == 0) return;
+    if (!(R->pcs = (slh_piece *)malloc(((size_t)R->ref.num + 1) * sizeof(slh_piece)))) pipeline_fail("Out of memory");
+    if (p->sites || p->vcf || p->cons || p->depth) merge_gpu_tables(R);
+    if (p->cons) write_cons(R);
+    else if (p->depth) write_depth(R);
+    else if (p->sites || p->vcf) write_sites_or_vcf(R);
+    else write_pile(R);
+    free(R->pcs);
+    R->t_format += now_s() - t0;
+    if (p->dedup) { /* (one GPU: its counters are the run's) */
+        uint64_t dd[4] = {0, 0, 0, 0};
+        rc = slamem_pileup_dedup_stats(R->piles[0], dd);
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the duplicate filter's counters from the GPU", rc);
+        fprintf(stderr, "> Duplicates: %llu candidate reads, %llu duplicates (%.2f %%) not counted, %llu without room in the duplicate "
+                        "table%s\n", (unsigned long long)dd[0], (unsigned long long)dd[1], dd[0] ? 100.0 * (double)dd[1] / (double)dd[0] : 0.0,
+                (unsigned long long)dd[2], dd[2] ? " (a larger table: -dslots)" : "");
+    }
+}
+
+/* the last lines of stdout, the timing lines, and the end of the process */
+static int finish(run_t *R) {
+    const slh_run *p = &R->p;
+    const int t = p->o.match_type;
+    double t_write, t_end0, t_end1;
+    char overlap_note[96] = "";
+    int i, f;
+    writer_finish(&g_writer);
+    t_write = g_writer.seconds;
+    if (g_writer.failed) pipeline_fail("Cannot write output file");
+    if (R->log_limit != 0 && t != 8 && (long)R->total_queries * R->strands > R->log_limit)
+        say(":: ... (%ld more strand blocks matched; set SLAMEM_VERBOSE=1 for a line each)\n", (long)R->total_queries * R->strands - R->log_limit);
+    t_end0 = now_s();
+    if (R->total_queries != 1) /* slamem.c:210-212 (the reference divides by zero when nothing matched) */
+        printf(":: Average %d %ss found per query sequence (total = %lld, avg size = %d bp)\n", (int)(R->total_matches / R->total_queries),
+               MATCH_NAME(t), R->total_matches, (int)(R->total_matches ? R->total_sum / R->total_matches : 0));
     fflush(stdout);
-    printf("> Saving %ss to <%s> ... ", depth ? "depth run" : cons ? "consensus sequence" : vcf ? "variant call" : sites ? "variant site" : MATCH_NAME(o.match_type), out_name);
-    if (fflush(out) != 0 || ferror(out)) exit_message("Cannot write output file");
-    if (getenv("SLAMEM_FULL_TEARDOWN") != NULL && fclose(out) != 0) exit_message("Cannot write output file");
+    printf("> Saving %ss to <%s> ... ", p->depth ? "depth run" : p->cons ? "consensus sequence" : p->vcf ? "variant call" : p->sites ? "variant site" : MATCH_NAME(t), R->out_name);
+    if (fflush(R->out) != 0 || ferror(R->out)) exit_message("Cannot write output file");
+    if (getenv("SLAMEM_FULL_TEARDOWN") != NULL && fclose(R->out) != 0) exit_message("Cannot write output file");
     t_end1 = now_s();
     printf("OK\n");
     printf("> Done!\n");
-    char overlap_note[96] = "";
     if (g_ld.seconds > 0)
-        snprintf(overlap_note, sizeof(overlap_note), " + queries parsed in pieces beside the search in %.3f s (%.3f s waited for)", g_ld.seconds, t_wait_load);
-    if (timing)
+        snprintf(overlap_note, sizeof(overlap_note), " + queries parsed in pieces beside the search in %.3f s (%.3f s waited for)", g_ld.seconds, R->t_wait_load);
+    if (R->timing)
         fprintf(stderr, "[timing] formatter threads: busy %.3f s in all; per batch the longest chunk %.3f s, the last chunk started %.3f s after the batch began (sums over the batches)\n",
                 g_fmt_busy, g_fmt_longest, g_fmt_latest_start);
-    if (timing)
+    if (R->timing)
         fprintf(stderr, "[timing] load %.3f s%s (index build of %.3f s overlapped; %.3f s more waiting for it), pipeline set-up %.3f s, "
                         "waiting for the GPU (upload + search + download, overlapped with formatting) %.3f s, format %.3f s "
                         "(writer thread busy %.3f s, overlapped; text buffers: %ld recycled, %ld fresh), close %.3f s, total %.3f s\n",
-                t_load, overlap_note, t_build, t_join, t_streams, t_gpu, t_format, t_write, g_pool_hits, g_pool_misses, t_end1 - t_end0,
-                now_s() - t_start);
+                R->t_load, overlap_note, R->t_build, R->t_join, R->t_streams, R->t_gpu, R->t_format, t_write, g_pool_hits, g_pool_misses,
+                t_end1 - t_end0, now_s() - R->t_start);
     fflush(stdout);
     fflush(stderr);
-    if (getenv("SLAMEM_FULL_TEARDOWN") == NULL) {
-        /* everything is written and nothing runs on the GPU any more: leave without returning gigabytes of buffers and
-           HBM piece by piece (0.15-0.25 s of the reference-sized run); the kernel driver reclaims them with the process */
-        leave_now();
-    }
+    /* everything is written and nothing runs on the GPU any more: leave without returning gigabytes of buffers and HBM piece by
+       piece (0.15-0.25 s of the reference-sized run); the kernel driver reclaims them with the process */
+    if (getenv("SLAMEM_FULL_TEARDOWN") == NULL) leave_now();
     {
         double a = now_s(), b, c, d;
         shutdown_pipeline();
-        for (i = 0; i < 16 && o.match_type == 8; i++) slamem_pileup_free(piles[i]);
+        for (i = 0; i < 16 && t == 8; i++) slamem_pileup_free(R->piles[i]);
         b = now_s();
-        for (i = 0; i < ngpu; i++) slamem_index_free(gpus[i]);
+        for (i = 0; i < R->ngpu; i++) slamem_index_free(R->gpus[i]);
         c = now_s();
-        if (o.out_arg == -1) free(out_name);
-        slh_buffer_free(&buf);
-        slh_free_seqset(&ref);
+        if (p->o.out_arg == -1) free(R->out_name);
+        slh_buffer_free(&R->buf);
+        slh_free_seqset(&R->ref);
         for (f = 0; f < g_reap_n; f++) pthread_join(g_reap_tid[f], NULL);
         free(g_reap_tid);
-        for (f = 0; f < g_ld.ready; f++) { slh_free_seqset(&qsets[f]); free(g_ld.masks[f]); }
+        for (f = 0; f < g_ld.ready; f++) { slh_free_seqset(&R->qsets[f]); free(g_ld.masks[f]); }
         free(g_ld.masks);
-        free(qsets);
+        free(R->qsets);
         pthread_mutex_lock(&g_pool_mu);
         while (g_pool_n > 0) slh_buffer_free(&g_pool[--g_pool_n]);
         pthread_mutex_unlock(&g_pool_mu);
         d = now_s();
-        if (timing)
+        if (R->timing)
             fprintf(stderr, "[timing] teardown: search pipeline (pinned buffers, device work space) %.3f s, index %.3f s, host buffers %.3f s\n",
                     b - a, c - b, d - c);
     }
-    slh_free_options(&o);
+    slh_free_options(&R->p.o);
     return 0;
+}
+
+int main(int argc, char **argv) {
+    static run_t run; /* (zeroed) */
+    static int warm_device;
+    run_t *R = &run;
+    double t0;
+    int status;
+    R->argc = argc;
+    R->argv = argv;
+    R->log_limit = 100;
+    R->batch_bytes = 256ull << 20;
+    R->piece_bytes = 128L << 20;
+    R->readout_rows = 16ull << 20;
+    printf("[ slaMEM v%s ]\n\n", VERSION);
+    if (parse_and_refuse(R, &status)) return status;
+    if (getenv("SLAMEM_FULL_TEARDOWN") == NULL) split_off_worker();
+    warm_device = R->device;
+    g_warm_started = pthread_create(&g_warm_tid, NULL, warmup_run, &warm_device) == 0;
+    R->t_start = now_s();
+    load_inputs(R);
+    join_build(R);
+    open_output(R);
+    t0 = now_s();
+    report_index(R);
+    replicate_index(R);
+    R->t_build = R->bj.seconds + (now_s() - t0);
+    /* (-paf, -pile: what is formatted and counted is a read, whichever strand its mapping lies on) */
+    R->strands = (R->p.o.match_type == 7 || R->p.o.match_type == 8) ? 1 : R->p.o.both_strands ? 2 : 1;
+    open_streams(R);
+    run_batches(R);
+    check_loader(R);
+    if (R->p.o.match_type == 8) write_pileup(R);
+    return finish(R);
 }

@@ -868,6 +868,24 @@ int slh_seq_id_from_merged_pos(const uint32_t *starts, int num, uint32_t *pos) {
     return lo;
 }
 
+int slh_next_piece(const slh_record *recs, const uint32_t *merged_start, int num, int *r, uint64_t *x, uint64_t range_end,
+                   slh_piece *out) {
+    while (*r < num) {
+        const uint64_t start = num > 1 ? merged_start[*r] : 0, end = start + recs[*r].size;
+        if (end <= *x) { (*r)++; continue; }
+        if (start >= range_end || *x >= range_end) return 0;
+        out->rec = *r;
+        out->start = start;
+        out->a = start > *x ? start : *x;
+        out->b = end < range_end ? end : range_end;
+        out->ends_record = out->b == end;
+        *x = out->b;
+        if (out->ends_record) (*r)++;
+        return 1;
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------------------------------------ */
 /* options                                                                                           */
 /* ------------------------------------------------------------------------------------------------ */
@@ -895,267 +913,363 @@ int slh_parse_argument(int argc, char **argv, const char *optionchars, int parse
     return parse ? -1 : 0;
 }
 
-int slh_parse_max_occ(int argc, char **argv, int *out) {
-    int i;
-    *out = 0;
-    for (i = 1; i < argc; i++) {
-        const char *a = argv[i];
-        char *end;
-        long v;
-        /* the two letters "oc" decide, as for every option; an 'o' option takes the next argument ("-o" alone is the output) */
-        if (a[0] != '-' || (a[1] != 'o' && a[1] != 'O') || (a[2] != 'c' && a[2] != 'C')) continue;
-        if (i == argc - 1) return -1;
-        errno = 0;
-        v = strtol(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) return -1;
-        *out = (int)v;
-        return 1;
-    }
-    return 0;
+/* The options, one row each.  An argument is an option of a row when its first two letters are the row's (either case; a
+ * one-letter row: when it is exactly two characters long) and the third-letter rule holds.  Everything that has to know an
+ * option reads it here: which arguments are file names (slh_parse_options), the value and its range (option_value), the
+ * refusal of a bad value and of a second mode (slh_parse_run). */
+enum { V_NONE, V_INT, V_POW2, V_DIGITS, V_LEVELS, V_ATOI, V_INDEX, V_STRING };
+typedef struct {
+    const char *name;   /* as usage() spells it; "l": a one-letter option */
+    char third, unless; /* third != 0: the third letter is name[2] (-maxed, -dedup); unless: the third letter is not this one (-mam, -depth) */
+    char kind;          /* V_NONE: no value.  V_INT: strtol's whole number in [lo, hi]; V_POW2: such a power of two; V_DIGITS: a number
+                           that begins with a digit; V_LEVELS: 1 to 16 of those, ascending, with commas; V_ATOI, V_INDEX, V_STRING: the
+                           reference's -l and -m (atoi), -o and -v (where the value stands) and -r */
+    char mode;          /* the match type the option selects (0: none) */
+    uint64_t lo, hi;
+    long long dflt;     /* what the entry points hand out when the option is absent */
+    const char *refusal; /* of a bad value; a mode's: of another mode beside it */
+} option_row;
+enum { O_MEM, O_MAM, O_MUM, O_SMEM, O_OCC, O_CHAIN, O_MGAP, O_EXT, O_PEN, O_XDROP, O_ALN, O_MAXED, O_PAF, O_SAM, O_PILE, O_MINQ, O_BQ,
+       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_EVS,
+       O_L, O_O, O_B, O_N, O_M, O_R, O_V, O_S, O_C, NUM_OPTIONS };
+#define PEN_XDROP "Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"
+static const option_row OPTIONS[NUM_OPTIONS] = {
+    [O_MEM] = {"mem", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
+    [O_MAM] = {"mam", 0, 'x', V_NONE, 1, 0, 0, 0, NULL},
+    [O_MUM] = {"mum", 0, 0, V_NONE, 2, 0, 0, 0, NULL},
+    [O_SMEM] = {"smem", 0, 0, V_NONE, 3, 0, 0, 0, "Option -smem excludes -mam and -mum"},
+    [O_OCC] = {"occ", 0, 0, V_INT, 0, 1, 0x7FFFFFFF, 0, "Option -occ needs a whole number of at least 1"},
+    [O_CHAIN] = {"chain", 0, 0, V_NONE, 4, 0, 0, 0, "Option -chain excludes -mam, -mum and -smem"},
+    [O_MGAP] = {"mgap", 0, 0, V_INT, 0, 1, 0x7FFFFFFF, 0, "Option -mgap needs a whole number of at least 1"},
+    [O_EXT] = {"ext", 0, 0, V_NONE, 5, 0, 0, 0, "Option -ext excludes -mam, -mum, -smem and -chain"},
+    [O_PEN] = {"pen", 0, 0, V_INT, 0, 1, 0x7FFFFFFF, 0, PEN_XDROP},
+    [O_XDROP] = {"xdrop", 0, 0, V_INT, 0, 0, 0x7FFFFFFF, -1, PEN_XDROP},
+    [O_ALN] = {"aln", 0, 0, V_NONE, 6, 0, 0, 0, "Option -aln excludes -mam, -mum, -smem, -chain and -ext"},
+    [O_MAXED] = {"maxed", 1, 0, V_INT, 0, 0, 127, -1, "Option -maxed needs a whole number from 0 to 127"},
+    [O_PAF] = {"paf", 0, 0, V_NONE, 7, 0, 0, 0, "Option -paf excludes -mam, -mum, -smem, -chain, -ext and -aln"},
+    [O_SAM] = {"sam", 0, 0, V_NONE, 7, 0, 0, 0, "Option -sam excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites, -vcf, -cons and -depth"},
+    [O_PILE] = {"pile", 0, 0, V_NONE, 8, 0, 0, 0, "Option -pile excludes -mam, -mum, -smem, -chain, -ext, -aln and -paf"},
+    [O_MINQ] = {"minq", 0, 0, V_INT, 0, 0, 60, 0, "Option -minq needs a whole number from 0 to 60"},
+    [O_BQ] = {"bq", 0, 0, V_INT, 0, 0, 93, 0, "Option -bq needs a whole number from 0 to 93"},
+    [O_SITES] = {"sites", 0, 0, V_NONE, 8, 0, 0, 0, "Option -sites excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf and -pile"},
+    [O_MDEP] = {"mdep", 0, 0, V_INT, 0, 1, 0x7FFFFFFF, 4, "Option -mdep needs a whole number of at least 1"},
+    [O_MPCT] = {"mpct", 0, 0, V_INT, 0, 0, 100, 20, "Option -mpct needs a whole number from 0 to 100"},
+    [O_VCF] = {"vcf", 0, 0, V_NONE, 8, 0, 0, 0, "Option -vcf excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile and -sites"},
+    [O_CONS] = {"cons", 0, 0, V_NONE, 8, 0, 0, 0, "Option -cons excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites and -vcf"},
+    [O_DEPTH] = {"depth", 0, 'd', V_NONE, 8, 0, 0, 0, "Option -depth excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -pile, -sites, -vcf and -cons"},
+    [O_LEV] = {"lev", 0, 0, V_LEVELS, 0, 1, 0xFFFFFFFFull, 0, "Option -lev needs 1 to 16 whole numbers of at least 1, ascending, separated by commas"},
+    [O_WIN] = {"win", 0, 0, V_DIGITS, 0, 1, UINT64_MAX, 0, "Option -win needs a whole number of at least 1"},
+    [O_DEDUP] = {"dedup", 1, 0, V_NONE, 0, 0, 0, 0, NULL},
+    [O_DSLOTS] = {"dslots", 0, 0, V_POW2, 0, 64, 1ull << 32, 0, "Option -dslots needs a power of two of at least 64"},
+    [O_GT] = {"gt", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
+    [O_PLOIDY] = {"ploidy", 0, 0, V_INT, 0, 1, 2, 2, "Option -ploidy needs 1 or 2"},
+    [O_ERR] = {"err", 0, 0, V_INT, 0, 1, 93, 20, "Option -err needs a whole number from 1 to 93"},
+    [O_HETQ] = {"hetq", 0, 0, V_INT, 0, 0, 999, 30, "Option -hetq needs a whole number from 0 to 999"},
+    [O_QUAL] = {"qual", 0, 0, V_INT, 0, 0, 999, 20, "Option -qual needs a whole number from 0 to 999"},
+    [O_EVS] = {"evs", 0, 0, V_POW2, 0, 64, 1ull << 31, 0, "Option -evs needs a power of two of at least 64"},
+    [O_L] = {"l", 0, 0, V_ATOI, 0, 0, 0, 20, NULL},
+    [O_O] = {"o", 0, 0, V_INDEX, 0, 0, 0, -1, NULL},
+    [O_B] = {"b", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
+    [O_N] = {"n", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
+    [O_M] = {"m", 0, 0, V_ATOI, 0, 0, 0, 0, NULL},
+    [O_R] = {"r", 0, 0, V_STRING, 0, 0, 0, 0, NULL},
+    [O_V] = {"v", 0, 0, V_INDEX, 0, 0, 0, -1, NULL},
+    [O_S] = {"s", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
+    [O_C] = {"c", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
+};
+/* the modes that exclude each other, beside -mam and -mum; a refusal names the last of them that is given */
+static const int MODES[] = {O_SMEM, O_CHAIN, O_EXT, O_ALN, O_PAF, O_PILE, O_SITES, O_VCF, O_CONS, O_DEPTH, O_SAM};
+#define NUM_MODES ((int)(sizeof(MODES) / sizeof(MODES[0])))
+
+static char lower(char c) { return c >= 'A' && c <= 'Z' ? (char)(c + 32) : c; }
+
+static int is_option(const char *a, int id) {
+    const option_row *r = &OPTIONS[id];
+    if (a[0] != '-' || a[1] == '\0' || lower(a[1]) != r->name[0]) return 0;
+    if (r->name[1] == '\0') return a[2] == '\0';
+    if (lower(a[2]) != r->name[1]) return 0;
+    if (r->third) return lower(a[3]) == r->name[2];
+    return !r->unless || lower(a[3]) != r->unless;
 }
 
-int slh_parse_max_gap(int argc, char **argv, int *out) {
-    int i;
-    *out = 0;
-    for (i = 1; i < argc; i++) {
-        const char *a = argv[i];
-        char *end;
-        long v;
-        /* the two letters "mg" decide, as for every option; an 'm' option takes the next argument ("-m" alone is the minimum
-           sequence length, "-ma", "-mu" the match types) */
-        if (a[0] != '-' || (a[1] != 'm' && a[1] != 'M') || (a[2] != 'g' && a[2] != 'G')) continue;
-        if (i == argc - 1) return -1;
-        errno = 0;
-        v = strtol(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 1 || v > 0x7FFFFFFFL) return -1;
-        *out = (int)v;
-        return 1;
-    }
-    return 0;
+/* the row of an argument, or -1 */
+static int option_of(const char *a) {
+    int id;
+    for (id = 0; id < NUM_OPTIONS; id++)
+        if (is_option(a, id)) return id;
+    return -1;
 }
 
-/* is argv[i] the option whose first two letters are c0 c1 (either case)? */
-static int two_letter_option(const char *a, char c0, char c1) {
-    return a[0] == '-' && (a[1] == c0 || a[1] == (char)(c0 - 32)) && (a[2] == c1 || a[2] == (char)(c1 - 32));
-}
-
-int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out) {
-    int i, seen = 0;
-    *penalty_out = 0;
-    *xdrop_out = -1;
-    for (i = 1; i < argc; i++) {
-        const char *a = argv[i];
-        char *end;
-        long v;
-        int pen = two_letter_option(a, 'p', 'e'), xd = two_letter_option(a, 'x', 'd');
-        if (!pen && !xd) continue;
-        if (i == argc - 1) return -1;
-        errno = 0;
-        v = strtol(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < (pen ? 1 : 0) || v > 0x7FFFFFFFL) return -1;
-        if (pen) *penalty_out = (int)v;
-        else *xdrop_out = (int)v;
-        seen = 1;
-        i++;
-    }
-    return seen;
-}
-
-static int is_maxed_option(const char *a) {
-    return two_letter_option(a, 'm', 'a') && (a[3] == 'x' || a[3] == 'X');
-}
-
-int slh_parse_max_edits(int argc, char **argv, int *out) {
-    int i;
-    *out = -1;
-    for (i = 1; i < argc; i++) {
-        char *end;
-        long v;
-        if (!is_maxed_option(argv[i])) continue;
-        if (i == argc - 1) return -1;
-        errno = 0;
-        v = strtol(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 0 || v > 127) return -1;
-        *out = (int)v;
-        return 1;
-    }
-    return 0;
-}
-
-int slh_parse_min_mapq(int argc, char **argv, int *out) {
-    int i;
-    *out = 0;
-    for (i = 1; i < argc; i++) {
-        char *end;
-        long v;
-        /* the two letters "mi" decide; an 'm' option takes the next argument */
-        if (!two_letter_option(argv[i], 'm', 'i')) continue;
-        if (i == argc - 1) return -1;
-        errno = 0;
-        v = strtol(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 0 || v > 60) return -1;
-        *out = (int)v;
-        return 1;
-    }
-    return 0;
-}
-
-int slh_parse_min_bq(int argc, char **argv, int *out) {
-    int i;
-    *out = 0;
-    for (i = 1; i < argc; i++) {
-        char *end;
-        long v;
-        /* the two letters "bq" decide ("-b" alone, the strand switch, is exactly two characters long); it takes the next argument */
-        if (!two_letter_option(argv[i], 'b', 'q')) continue;
-        if (i == argc - 1) return -1;
-        errno = 0;
-        v = strtol(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 0 || v > 93) return -1;
-        *out = (int)v;
-        return 1;
-    }
-    return 0;
-}
-
-int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out) {
-    int i, seen = 0;
-    *min_depth_out = 4;
-    *min_pct_out = 20;
-    for (i = 1; i < argc; i++) {
-        char *end;
-        long v;
-        /* the two letters "md" and "mp" decide; an 'm' option takes the next argument */
-        int dep = two_letter_option(argv[i], 'm', 'd'), pct = two_letter_option(argv[i], 'm', 'p');
-        if (!dep && !pct) continue;
-        if (i == argc - 1) return dep ? -1 : -2;
-        errno = 0;
-        v = strtol(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0') return dep ? -1 : -2;
-        if (dep && (v < 1 || v > 0x7FFFFFFFL)) return -1;
-        if (pct && (v < 0 || v > 100)) return -2;
-        if (dep) *min_depth_out = (int)v;
-        else *min_pct_out = (int)v;
-        seen = 1;
-        i++;
-    }
-    return seen;
-}
-
-int slh_parse_event_slots(int argc, char **argv, uint64_t *out) {
-    int i;
-    *out = 0;
-    for (i = 1; i < argc; i++) {
-        char *end;
-        long long v;
-        /* the two letters "ev" decide; it takes the next argument */
-        if (!two_letter_option(argv[i], 'e', 'v')) continue;
-        if (i == argc - 1) return -1;
-        errno = 0;
-        v = strtoll(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 64 || v > (1LL << 31) || (v & (v - 1)) != 0) return -1;
-        *out = (uint64_t)v;
-        return 1;
-    }
-    return 0;
-}
-
-int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, int *hetq_out, int *qual_out) {
-    int i, seen = 0;
-    *ploidy_out = 2;
-    *err_out = 20;
-    *hetq_out = 30;
-    *qual_out = 20;
-    for (i = 1; i < argc; i++) {
-        char *end;
-        long v;
-        /* the two letters "pl", "er", "he" and "qu" decide; each takes the next argument */
-        const int pl = two_letter_option(argv[i], 'p', 'l'), er = two_letter_option(argv[i], 'e', 'r');
-        const int he = two_letter_option(argv[i], 'h', 'e'), qu = two_letter_option(argv[i], 'q', 'u');
-        const int bad = pl ? -1 : er ? -2 : he ? -3 : -4;
-        if (!pl && !er && !he && !qu) continue;
-        if (i == argc - 1) return bad;
-        errno = 0;
-        v = strtol(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0') return bad;
-        if (pl ? (v != 1 && v != 2) : er ? (v < 1 || v > 93) : (v < 0 || v > 999)) return bad;
-        *(pl ? ploidy_out : er ? err_out : he ? hetq_out : qual_out) = (int)v;
-        seen = 1;
-        i++;
-    }
-    return seen;
-}
-
-/* -dedup: "de" as -depth, told apart by its third letter as -maxed is from -mam */
-static int is_dedup_option(const char *a) {
-    return two_letter_option(a, 'd', 'e') && (a[3] == 'd' || a[3] == 'D');
-}
-
-int slh_parse_depth(int argc, char **argv) {
+static int has_option(int argc, char **argv, int id) {
     int i;
     for (i = 1; i < argc; i++)
-        if (two_letter_option(argv[i], 'd', 'e') && !is_dedup_option(argv[i])) return 1;
+        if (is_option(argv[i], id)) return 1;
     return 0;
 }
 
-int slh_parse_dedup(int argc, char **argv, uint64_t *slots_out) {
-    int i, seen = 0;
-    *slots_out = 0;
-    for (i = 1; i < argc; i++) {
-        char *end;
-        long long v;
-        if (is_dedup_option(argv[i])) { seen |= 1; continue; } /* (no value: it may stand anywhere) */
-        /* the two letters "ds" decide; it takes the next argument */
-        if (!two_letter_option(argv[i], 'd', 's')) continue;
-        if (i == argc - 1) return -1;
+int slh_option_info(int k, const char **name_out) {
+    if (k < 0 || k >= NUM_OPTIONS) return -1;
+    *name_out = OPTIONS[k].name;
+    return OPTIONS[k].kind != V_NONE;
+}
+
+/* The value `a` of a row that takes a checked one: 0 and *out (V_LEVELS: the list in levels, its length in *out), or -1 and
+ * *out as it was. */
+static int option_value(const option_row *r, const char *a, uint64_t *out, uint32_t *levels) {
+    const int digits = r->kind == V_DIGITS || r->kind == V_LEVELS;
+    uint64_t v, k = 0;
+    char *end;
+    for (;;) {
         errno = 0;
-        v = strtoll(argv[i + 1], &end, 10);
-        if (errno != 0 || end == argv[i + 1] || *end != '\0' || v < 64 || v > (1LL << 32) || (v & (v - 1)) != 0) return -1;
-        *slots_out = (uint64_t)v;
-        seen |= 2;
+        if (digits) {
+            if (a[0] < '0' || a[0] > '9') return -1;
+            v = strtoull(a, &end, 10);
+        } else {
+            const long long s = strtoll(a, &end, 10);
+            if (s < 0) return -1;
+            v = (uint64_t)s;
+        }
+        if (errno != 0 || end == a || v < r->lo || v > r->hi || (r->kind == V_POW2 && (v & (v - 1)) != 0)) return -1;
+        if (r->kind != V_LEVELS) break;
+        if (k == 16 || (k && (uint32_t)v <= levels[k - 1])) return -1;
+        levels[k++] = (uint32_t)v;
+        if (*end != ',') break; /* a number, then a comma and the next one, or the end */
+        a = end + 1;
+    }
+    if (*end != '\0') return -1;
+    *out = r->kind == V_LEVELS ? k : v;
+    return 0;
+}
+
+/* Looks for the n rows ids[] among the arguments.  vals[k] starts as row k's default and takes its value, which is not looked
+ * at as an option again; first_only: the first of the rows that is found ends the search.  Returns the rows seen as bits (bit k:
+ * ids[k]), or -(k + 1) when the value of row k is missing or refused. */
+static int scan_options(int argc, char **argv, const int *ids, int n, int first_only, uint64_t *vals, uint32_t *levels) {
+    int i, k, seen = 0;
+    for (k = 0; k < n; k++) vals[k] = (uint64_t)OPTIONS[ids[k]].dflt;
+    for (i = 1; i < argc; i++) {
+        for (k = 0; k < n && !is_option(argv[i], ids[k]); k++) {}
+        if (k == n) continue;
+        seen |= 1 << k;
+        if (OPTIONS[ids[k]].kind == V_NONE) continue;
+        if (i == argc - 1 || option_value(&OPTIONS[ids[k]], argv[i + 1], &vals[k], levels)) return -(k + 1);
+        if (first_only) break;
         i++;
     }
     return seen;
 }
 
+/* the entry points with one whole number: 0 absent, 1 there, -1 refused */
+static int scan_one(int argc, char **argv, int id, uint64_t *val) {
+    return scan_options(argc, argv, &id, 1, 1, val, NULL);
+}
+static int scan_whole(int argc, char **argv, int id, int *out) {
+    uint64_t v;
+    const int rc = scan_one(argc, argv, id, &v);
+    *out = (int)(long long)v;
+    return rc;
+}
+int slh_parse_max_occ(int argc, char **argv, int *out) { return scan_whole(argc, argv, O_OCC, out); }
+int slh_parse_max_gap(int argc, char **argv, int *out) { return scan_whole(argc, argv, O_MGAP, out); }
+int slh_parse_max_edits(int argc, char **argv, int *out) { return scan_whole(argc, argv, O_MAXED, out); }
+int slh_parse_min_mapq(int argc, char **argv, int *out) { return scan_whole(argc, argv, O_MINQ, out); }
+int slh_parse_min_bq(int argc, char **argv, int *out) { return scan_whole(argc, argv, O_BQ, out); }
+int slh_parse_event_slots(int argc, char **argv, uint64_t *out) { return scan_one(argc, argv, O_EVS, out); }
+int slh_parse_depth(int argc, char **argv) { return has_option(argc, argv, O_DEPTH); }
+
+/* ... and those with several options, each of which may stand more than once (the last one counts) */
+static int scan_ints(int argc, char **argv, const int *ids, int n, int **outs) {
+    uint64_t v[4];
+    const int rc = scan_options(argc, argv, ids, n, 0, v, NULL);
+    int k;
+    for (k = 0; k < n; k++) *outs[k] = (int)(long long)v[k];
+    return rc > 0 ? 1 : rc;
+}
+int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out) {
+    static const int ids[2] = {O_PEN, O_XDROP};
+    int *outs[2] = {penalty_out, xdrop_out};
+    const int rc = scan_ints(argc, argv, ids, 2, outs);
+    return rc < 0 ? -1 : rc;
+}
+int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out) {
+    static const int ids[2] = {O_MDEP, O_MPCT};
+    int *outs[2] = {min_depth_out, min_pct_out};
+    return scan_ints(argc, argv, ids, 2, outs);
+}
+int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, int *hetq_out, int *qual_out) {
+    static const int ids[4] = {O_PLOIDY, O_ERR, O_HETQ, O_QUAL};
+    int *outs[4] = {ploidy_out, err_out, hetq_out, qual_out};
+    return scan_ints(argc, argv, ids, 4, outs);
+}
+int slh_parse_dedup(int argc, char **argv, uint64_t *slots_out) {
+    static const int ids[2] = {O_DEDUP, O_DSLOTS};
+    uint64_t v[2];
+    const int rc = scan_options(argc, argv, ids, 2, 0, v, NULL);
+    *slots_out = v[1];
+    return rc < 0 ? -1 : rc;
+}
 int slh_parse_depth_params(int argc, char **argv, uint32_t *levels_out, int *num_levels_out, uint64_t *window_out) {
-    int i, seen = 0;
-    *num_levels_out = 0;
-    *window_out = 0;
-    for (i = 1; i < argc; i++) {
-        /* the two letters "le" and "wi" decide; both take the next argument ("-l" alone is the minimum match length) */
-        const int lev = two_letter_option(argv[i], 'l', 'e'), win = two_letter_option(argv[i], 'w', 'i');
-        const char *a;
-        char *end;
-        if (!lev && !win) continue;
-        if (i == argc - 1) return lev ? -1 : -2;
-        a = argv[i + 1];
-        if (win) {
-            unsigned long long v;
-            errno = 0;
-            v = strtoull(a, &end, 10);
-            if (errno != 0 || end == a || *end != '\0' || a[0] < '0' || a[0] > '9' || v < 1) return -2;
-            *window_out = (uint64_t)v;
-            seen |= 2;
+    static const int ids[2] = {O_LEV, O_WIN};
+    uint64_t v[2];
+    const int rc = scan_options(argc, argv, ids, 2, 0, v, levels_out);
+    *num_levels_out = (int)v[0];
+    *window_out = v[1];
+    return rc;
+}
+
+/* the -r string (slamem.c:605-629): the argument at i, or when it opens with a quote the arguments up to the one that closes it,
+ * joined by blanks; copied to out when out is not NULL.  Returns its length; *i: the last argument it took (argc: none closed it) */
+static int ref_name_string(int argc, char **argv, int *i, char *out) {
+    int j = 0, n = 0;
+    char oc = argv[*i][0];
+    if (oc == '\'' || oc == '\"') j = 1;
+    else oc = '\0';
+    while (argv[*i][j] != oc) {
+        if (argv[*i][j] == '\0') {
+            (*i)++;
+            if (*i == argc) break;
+            j = 0;
+            if (out) out[n] = ' ';
         } else {
-            int k = 0;
-            for (;;) { /* a number, then a comma and the next one, or the end */
-                unsigned long long v;
-                errno = 0;
-                v = strtoull(a, &end, 10);
-                if (errno != 0 || end == a || a[0] < '0' || a[0] > '9' || v < 1 || v > 0xFFFFFFFFull || k == 16) return -1;
-                if (k && (uint32_t)v <= levels_out[k - 1]) return -1;
-                levels_out[k++] = (uint32_t)v;
-                if (*end == '\0') break;
-                if (*end != ',') return -1;
-                a = end + 1;
-            }
-            *num_levels_out = k;
-            seen |= 1;
+            if (out) out[n] = argv[*i][j];
+            j++;
         }
-        i++;
+        n++;
     }
-    return seen;
+    if (out) out[n] = '\0';
+    return n;
+}
+
+int slh_parse_options(int argc, char **argv, slh_options *o) {
+    int i, k, n = 0, ref_arg;
+    memset(o, 0, sizeof(*o));
+    o->image_arg = o->out_arg = -1;
+    o->min_mem_len = 20;
+    if (argc < 3) { o->usage = 1; return 0; }
+    o->hidden_sort = has_option(argc, argv, O_S);
+    o->hidden_clean = has_option(argc, argv, O_C);
+    o->file_args = (int *)calloc((size_t)argc, sizeof(int));
+    if (!o->file_args) return -1;
+    for (i = 1; i < argc; i++) { /* which arguments are FASTA files (slamem.c:574-600) */
+        int id;
+        char oc;
+        if (argv[i][0] != '-') { o->file_args[o->num_files++] = i; continue; }
+        id = option_of(argv[i]);
+        oc = lower(argv[i][1]);
+        if (id == O_VCF) continue; /* (the one option that begins with l/o/m/v and takes no value) */
+        /* the reference's rule: any option that begins with l/o/m/v takes the next argument, -mam and -mum included */
+        if (oc == 'l' || oc == 'o' || oc == 'm' || oc == 'v' || (id >= 0 && id != O_R && OPTIONS[id].kind != V_NONE)) i++;
+        else if (oc == 'r') { /* ... and any that begins with r a string */
+            if (++i == argc) break;
+            n = ref_name_string(argc, argv, &i, NULL);
+        }
+    }
+    o->no_ns = has_option(argc, argv, O_N);
+    o->min_seq_len = slh_parse_argument(argc, argv, "M", 1);
+    if (o->min_seq_len == -1) o->min_seq_len = 0;
+    ref_arg = slh_parse_argument(argc, argv, "R", 2);
+    if (ref_arg != -1) { /* slamem.c:605-629 */
+        o->ref_name_given = 1;
+        if (n == 0) o->ref_name_empty = 1;
+        else {
+            o->ref_name = (char *)calloc((size_t)n + 1, 1);
+            if (!o->ref_name) return -1;
+            ref_name_string(argc, argv, &ref_arg, o->ref_name);
+        }
+    }
+    o->image_arg = slh_parse_argument(argc, argv, "V", 2);
+    o->match_type = has_option(argc, argv, O_MAM) ? 1 : 0;
+    if (has_option(argc, argv, O_MUM)) o->match_type = o->match_type == 1 ? -1 : 2; /* the match type the reference reserves ("EAU", slamem.c:35) */
+    for (k = 0; k < NUM_MODES; k++)
+        if (has_option(argc, argv, MODES[k])) o->match_type = o->match_type != 0 ? -1 : OPTIONS[MODES[k]].mode;
+    o->both_strands = has_option(argc, argv, O_B);
+    o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
+    if (o->min_mem_len == -1) o->min_mem_len = 20;
+    o->out_arg = slh_parse_argument(argc, argv, "O", 2);
+    return 0;
+}
+
+static int refuse(const char **refusal, const char *msg, int rc) {
+    *refusal = msg;
+    return rc;
+}
+
+int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
+    slh_options *o = &r->o;
+    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct;
+    *refusal = NULL;
+    memset(r, 0, sizeof(*r));
+    if (slh_parse_options(argc, argv, o) != 0) return refuse(refusal, "Out of memory", -1);
+    t = o->match_type;
+    r->sites = has_option(argc, argv, O_SITES);
+    r->vcf = has_option(argc, argv, O_VCF);
+    r->cons = has_option(argc, argv, O_CONS);
+    r->depth = has_option(argc, argv, O_DEPTH);
+    r->sam = has_option(argc, argv, O_SAM);
+    r->gt = has_option(argc, argv, O_GT);
+    mpct = has_option(argc, argv, O_MPCT);
+    occ = slh_parse_max_occ(argc, argv, &r->max_occ);
+    gap = slh_parse_max_gap(argc, argv, &r->max_gap);
+    ext = slh_parse_ext_params(argc, argv, &r->ext_pen, &r->ext_xdrop);
+    edits = slh_parse_max_edits(argc, argv, &r->max_edits);
+    mapq = slh_parse_min_mapq(argc, argv, &r->min_mapq);
+    r->bq_given = slh_parse_min_bq(argc, argv, &r->min_bq);
+    sparams = slh_parse_sites_params(argc, argv, &r->min_depth, &r->min_pct);
+    if (r->depth && sparams == 0) r->min_depth = 1; /* (-depth: a position is covered when one read shows it) */
+    gtp = slh_parse_gt_params(argc, argv, &r->gt_ploidy, &r->gt_err, &r->gt_hetq, &r->gt_qual);
+    dparams = slh_parse_depth_params(argc, argv, r->levels, &r->num_levels, &r->window);
+    evs = slh_parse_event_slots(argc, argv, &r->ev_slots);
+    dd = slh_parse_dedup(argc, argv, &r->dd_slots);
+    r->dedup = dd > 0 && (dd & 1);
+    if (o->usage || o->hidden_sort || o->hidden_clean) return 0; /* (the caller's business, before any refusal) */
+
+    /* the refusals, the first that applies */
+    if (t < 0) {
+        for (k = NUM_MODES - 1; k >= 0; k--)
+            if (has_option(argc, argv, MODES[k])) return refuse(refusal, OPTIONS[MODES[k]].refusal, -1);
+        return refuse(refusal, "Options -mam and -mum exclude each other", -1);
+    }
+#define REFUSE_IF(cond, msg) do { if (cond) return refuse(refusal, msg, -1); } while (0)
+    REFUSE_IF(occ < 0, OPTIONS[O_OCC].refusal);
+    REFUSE_IF(occ && t != 3, "Option -occ needs -smem");
+    REFUSE_IF(gap < 0, OPTIONS[O_MGAP].refusal);
+    REFUSE_IF(gap && t != 4 && t != 6 && t != 7 && t != 8, "Option -mgap needs -chain");
+    REFUSE_IF(ext < 0, PEN_XDROP);
+    REFUSE_IF(ext && t != 5 && t != 6 && t != 7 && t != 8, "Options -pen and -xdrop need -ext");
+    REFUSE_IF(edits < 0, OPTIONS[O_MAXED].refusal);
+    REFUSE_IF(edits && t != 6 && t != 7 && t != 8, "Option -maxed needs -aln");
+    REFUSE_IF(mapq < 0, OPTIONS[O_MINQ].refusal);
+    REFUSE_IF(mapq && t != 8, "Option -minq needs -pile");
+    REFUSE_IF(r->bq_given < 0, OPTIONS[O_BQ].refusal);
+    REFUSE_IF(r->bq_given && t != 8, "Option -bq needs -pile");
+    REFUSE_IF(sparams < 0, OPTIONS[sparams == -1 ? O_MDEP : O_MPCT].refusal);
+    if (sparams) {
+        REFUSE_IF(r->cons && mpct, "Option -mpct has no meaning with -cons: an allele is applied when more than half of the depth shows it");
+        REFUSE_IF(r->depth && mpct, "Option -mpct has no meaning with -depth: the depth is written as it is");
+        REFUSE_IF(!r->sites && !r->vcf && !r->cons && !r->depth, "Options -mdep and -mpct need -sites");
+    }
+    REFUSE_IF(gtp < 0, OPTIONS[O_PLOIDY - 1 - gtp].refusal);
+    if (gtp && !r->gt) {
+        REFUSE_IF(has_option(argc, argv, O_PLOIDY), "Option -ploidy needs -gt");
+        REFUSE_IF(has_option(argc, argv, O_ERR), "Option -err needs -gt");
+        REFUSE_IF(has_option(argc, argv, O_HETQ), "Option -hetq needs -gt");
+        REFUSE_IF(1, "Option -qual needs -gt");
+    }
+    REFUSE_IF(r->gt && !r->vcf, "Option -gt needs -vcf");
+    REFUSE_IF(r->gt && mpct, "Option -mpct has no meaning with -gt: a call is made when its genotype's quality reaches -qual");
+    REFUSE_IF(dparams < 0, OPTIONS[dparams == -1 ? O_LEV : O_WIN].refusal);
+    REFUSE_IF(dparams == 3 && r->depth, "Options -lev and -win exclude each other");
+    REFUSE_IF(dparams && !r->depth, "Options -lev and -win need -depth");
+    REFUSE_IF(evs < 0, OPTIONS[O_EVS].refusal);
+    REFUSE_IF(evs && !r->vcf && !r->cons, "Option -evs needs -vcf");
+    REFUSE_IF(dd < 0, OPTIONS[O_DSLOTS].refusal);
+    REFUSE_IF(dd == 2, "Option -dslots needs -dedup");
+    REFUSE_IF(dd && t != 8, "Option -dedup needs -pile, -sites, -vcf, -cons or -depth");
+#undef REFUSE_IF
+    /* (here the caller refuses what depends on more than the arguments) */
+    if (o->num_files < 2) return refuse(refusal, "Not enough input sequence files provided", -2);
+    if (o->ref_name_given && o->ref_name_empty) return refuse(refusal, "No reference name string provided", -2);
+    return 0;
 }
 
 char *slh_append_to_basename(const char *filename, const char *extra) {
@@ -1177,116 +1291,6 @@ void slh_free_options(slh_options *o) {
     memset(o, 0, sizeof(*o));
 }
 
-int slh_parse_options(int argc, char **argv, slh_options *o) {
-    int i, j, n = 0, ref_arg;
-    char oc;
-    memset(o, 0, sizeof(*o));
-    o->image_arg = o->out_arg = -1;
-    o->min_mem_len = 20;
-    if (argc < 3) { o->usage = 1; return 0; }
-    o->hidden_sort = slh_parse_argument(argc, argv, "S", 0);
-    o->hidden_clean = slh_parse_argument(argc, argv, "C", 0);
-    o->file_args = (int *)calloc((size_t)argc, sizeof(int));
-    if (!o->file_args) return -1;
-    for (i = 1; i < argc; i++) { /* which arguments are FASTA files (slamem.c:574-600) */
-        if (argv[i][0] == '-') {
-            oc = argv[i][1];
-            if (oc >= 'A' && oc <= 'Z') oc = (char)('a' + (oc - 'A'));
-            if (two_letter_option(argv[i], 'v', 'c')) {} /* -vcf takes no value ("-v" alone is the image tool and does) */
-            else if (oc == 'l' || oc == 'o' || oc == 'm' || oc == 'v') i++; /* any option starting with l/o/m/v eats the next argument */
-            else if (two_letter_option(argv[i], 'e', 'v')) i++; /* -evs N (of -vcf) */
-            else if (two_letter_option(argv[i], 'b', 'q')) i++; /* -bq N (of -pile and its read-outs; "-b" alone takes none) */
-            else if (two_letter_option(argv[i], 'w', 'i')) i++; /* -win N (of -depth; its -lev LIST begins with l) */
-            else if (two_letter_option(argv[i], 'd', 's')) i++; /* -dslots N (of -dedup, which takes none) */
-            else if (two_letter_option(argv[i], 'p', 'e') || two_letter_option(argv[i], 'x', 'd')) i++; /* -pen N, -xdrop N (of -ext) */
-            else if (two_letter_option(argv[i], 'p', 'l') || two_letter_option(argv[i], 'e', 'r') || two_letter_option(argv[i], 'h', 'e') ||
-                     two_letter_option(argv[i], 'q', 'u')) i++; /* -ploidy N, -err Q, -hetq N, -qual N (of -gt, which takes none) */
-            else if (oc == 'r') {
-                i++;
-                if (i == argc) break;
-                j = 0;
-                oc = argv[i][0];
-                if (oc == '\'' || oc == '\"') j = 1;
-                else oc = '\0';
-                n = 0;
-                while (argv[i][j] != oc) {
-                    if (argv[i][j] == '\0') {
-                        i++;
-                        if (i == argc) break;
-                        j = 0;
-                    } else j++;
-                    n++;
-                }
-            }
-            continue;
-        }
-        o->file_args[o->num_files++] = i;
-    }
-    o->no_ns = slh_parse_argument(argc, argv, "N", 0);
-    o->min_seq_len = slh_parse_argument(argc, argv, "M", 1);
-    if (o->min_seq_len == -1) o->min_seq_len = 0;
-    ref_arg = slh_parse_argument(argc, argv, "R", 2);
-    if (ref_arg != -1) { /* slamem.c:605-629 */
-        o->ref_name_given = 1;
-        if (n == 0) o->ref_name_empty = 1;
-        else {
-            o->ref_name = (char *)calloc((size_t)n + 1, 1);
-            if (!o->ref_name) return -1;
-            i = ref_arg;
-            j = 0;
-            oc = argv[i][0];
-            if (oc == '\'' || oc == '\"') j = 1;
-            else oc = '\0';
-            n = 0;
-            while (argv[i][j] != oc) {
-                if (argv[i][j] == '\0') {
-                    i++;
-                    if (i == argc) break;
-                    j = 0;
-                    o->ref_name[n] = ' ';
-                } else {
-                    o->ref_name[n] = argv[i][j];
-                    j++;
-                }
-                n++;
-            }
-            o->ref_name[n] = '\0';
-        }
-    }
-    o->image_arg = slh_parse_argument(argc, argv, "V", 2);
-    o->match_type = 0;
-    for (i = 1; i < argc; i++) /* -mam: "ma", but not -maxed (the edit limit of -aln) */
-        if (two_letter_option(argv[i], 'm', 'a') && !is_maxed_option(argv[i])) o->match_type = 1;
-    if (slh_parse_argument(argc, argv, "MU", 0)) /* -mum: the match type the reference reserves ("EAU", slamem.c:35) */
-        o->match_type = o->match_type == 1 ? -1 : 2;
-    if (slh_parse_argument(argc, argv, "SM", 0)) /* -smem: super-maximal matches (an 's' option takes no value; "-s" alone is the sort tool) */
-        o->match_type = o->match_type != 0 ? -1 : 3;
-    if (slh_parse_argument(argc, argv, "CH", 0)) /* -chain: the best collinear chain (a 'c' option takes no value; "-c" alone is the clean tool) */
-        o->match_type = o->match_type != 0 ? -1 : 4;
-    if (slh_parse_argument(argc, argv, "EX", 0)) /* -ext: ungapped X-drop extension of every MEM (an 'e' option takes no value) */
-        o->match_type = o->match_type != 0 ? -1 : 5;
-    if (slh_parse_argument(argc, argv, "AL", 0)) /* -aln: the gapped alignment of the best chain (an 'a' option takes no value) */
-        o->match_type = o->match_type != 0 ? -1 : 6;
-    if (slh_parse_argument(argc, argv, "PA", 0)) /* -paf: one mapping per read, written as PAF (a 'p' option takes no value) */
-        o->match_type = o->match_type != 0 ? -1 : 7;
-    if (slh_parse_argument(argc, argv, "SA", 0)) /* -sam: the mappings of -paf written as SAM: match type 7 with the MD pass (an 's' option takes no value; "-s" alone is the sort tool) */
-        o->match_type = o->match_type != 0 ? -1 : 7;
-    if (slh_parse_argument(argc, argv, "PI", 0)) /* -pile: the per-base pileup of the mappings (a 'p' option takes no value) */
-        o->match_type = o->match_type != 0 ? -1 : 8;
-    if (slh_parse_argument(argc, argv, "SI", 0)) /* -sites: the variant sites of the pileup: match type 8 with another read-out (an 's' option takes no value) */
-        o->match_type = o->match_type != 0 ? -1 : 8;
-    if (slh_parse_argument(argc, argv, "VC", 0)) /* -vcf: the calls of the pileup as VCF: match type 8 with the events enabled and a third read-out */
-        o->match_type = o->match_type != 0 ? -1 : 8;
-    if (slh_parse_argument(argc, argv, "CO", 0)) /* -cons: the consensus of the pileup as FASTA: match type 8 with the events enabled and a fourth read-out (a 'c' option takes no value) */
-        o->match_type = o->match_type != 0 ? -1 : 8;
-    if (slh_parse_depth(argc, argv)) /* -depth ("de", but not -dedup, the duplicate filter of the pileup's modes): the depth of coverage as runs: match type 8 with a fifth read-out (a 'd' option takes no value) */
-        o->match_type = o->match_type != 0 ? -1 : 8;
-    o->both_strands = slh_parse_argument(argc, argv, "B", 0);
-    o->min_mem_len = slh_parse_argument(argc, argv, "L", 1);
-    if (o->min_mem_len == -1) o->min_mem_len = 20;
-    o->out_arg = slh_parse_argument(argc, argv, "O", 2);
-    return 0;
-}
 
 /* ------------------------------------------------------------------------------------------------ */
 /* output                                                                                            */

@@ -72,6 +72,19 @@ int slh_thread_count(void);
 /* GetSeqIdFromMergedSeqsPos (sequence.c:309-320). */
 int slh_seq_id_from_merged_pos(const uint32_t *starts, int num, uint32_t *pos);
 
+/* The walk of the read-outs over a merged text that is read in ranges of rows: the next piece of a record inside the range that
+ * ends in front of row range_end.  *r is the record to look at first (0 before the first range) and *x the row the walk has
+ * reached (the range's first row before its first piece); both move on, *r only past a record whose last row was handed out,
+ * so the next range goes on where this one stopped.  The separators between the records belong to no piece.  Returns 1 and the
+ * piece -- rows [a, b) of record rec, which starts at row `start`; ends_record: b is the record's end -- or 0 when the range
+ * holds no further piece. */
+typedef struct {
+    int rec, ends_record;
+    uint64_t start, a, b;
+} slh_piece;
+int slh_next_piece(const slh_record *recs, const uint32_t *merged_start, int num, int *r, uint64_t *x, uint64_t range_end,
+                   slh_piece *out);
+
 /* Options as the reference parses them (slamem.c:571-663; tools.c:31-62). */
 typedef struct {
     int usage;          /* argc < 3                                          */
@@ -95,47 +108,54 @@ int slh_parse_options(int argc, char **argv, slh_options *o);
 void slh_free_options(slh_options *o);
 /* ParseArgument (tools.c:31-62) */
 int slh_parse_argument(int argc, char **argv, const char *optionchars, int parse);
-/* -occ N (-oc...): the occurrence cap of -smem.  0 and *out = 0 when absent; 1 and *out = N for an integer N >= 1;
- * -1 when the value is missing, not an integer or < 1.  (Not a field of slh_options, whose layout callers mirror.) */
+/* The options behind the reference's are rows of one table in slamem_host.c: the first two letters decide, either case (-maxed
+ * and -dedup: three, because "-ma" is -mam and "-de" -depth), and the value of a row that takes one is never a file name.  Row k
+ * of the table: its name in *name_out and whether it takes a value, or -1 behind the last row. */
+int slh_option_info(int k, const char **name_out);
+/* The values, one entry point per group of options (not fields of slh_options, whose layout callers mirror).  An entry point with
+ * one option returns 0 when it is absent (the default in the output), 1 when it is there, -1 when its value is missing, no whole
+ * number or out of range; only the first occurrence is looked at.  One with several looks at every occurrence, the last one
+ * counts, and returns 0, 1 when any is there, or -k when the value of its k-th option is refused.
+ *   -occ N >= 1 (default 0); -mgap N >= 1 (0); -maxed N in [0, 127] (-1); -minq N in [0, 60] (0); -bq N in [0, 93] (0);
+ *   -evs N, a power of two in [64, 2^31] (0) */
 int slh_parse_max_occ(int argc, char **argv, int *out);
-/* -mgap N (-mg...): the maximum gap of -chain, with the same results for an integer N in [1, 2^31). */
 int slh_parse_max_gap(int argc, char **argv, int *out);
-/* -pen N (-pe...) and -xdrop N (-xd...): the mismatch penalty (N >= 1) and the X-drop (N >= 0) of -ext.  0 when neither is there
- * (*penalty_out = 0, *xdrop_out = -1: the defaults), 1 when at least one is, -1 when a value is missing, not an integer or out
- * of range.  Their values are never taken for file names. */
-int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out);
-/* -maxed N (-max...: three letters, because "-ma" is -mam): the most edits in one gap of -aln, a whole number in [0, 127].  0 when
- * it is not there (*out = -1: the default), 1 when it is, -1 when the value is missing, not an integer or out of range.  An
- * argument that starts with -max is never taken for -mam. */
 int slh_parse_max_edits(int argc, char **argv, int *out);
-/* -minq N (-mi...): the least mapping quality that counts in -pile, a whole number in [0, 60].  0 when it is not there (*out = 0),
- * 1 when it is, -1 when the value is missing, not an integer or out of range.  It begins with -m, so its value is never taken
- * for a file name. */
 int slh_parse_min_mapq(int argc, char **argv, int *out);
-/* -bq N (-bq...): the least base quality of a read letter that counts in -pile and its read-outs, a whole number in [0, 93]; 0:
- * every letter counts.  0 when it is not there (*out = 0), 1 when it is, -1 when the value is missing, not an integer or out of
- * range.  "-b" (both strands) is a one-letter option and matches two characters exactly, so neither is taken for the other; the
- * value of -bq is never taken for a file name. */
 int slh_parse_min_bq(int argc, char **argv, int *out);
-/* -mdep N (-md...) and -mpct P (-mp...): the least depth (N in [1, 2^31)) and the least share of the depth in percent (P in
- * [0, 100]) of -sites.  0 when neither is there (*min_depth_out = 4, *min_pct_out = 20: the defaults), 1 when at least one is,
- * -1 when the value of -mdep is missing, not an integer or out of range, -2 when that of -mpct is.  Both begin with -m, so their
- * values are never taken for file names; neither is -mam, -maxed, -mgap or -minq. */
-int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out);
-/* -evs N (-ev...): the slots of -vcf's event table, a power of two in [64, 2^31].  0 when it is not there (*out = 0: the
- * default), 1 when it is, -1 when the value is missing, not an integer or no such power of two.  Its value is never taken for a
- * file name. */
 int slh_parse_event_slots(int argc, char **argv, uint64_t *out);
-/* -depth: is an option given whose first two letters are "de" and that is not -dedup? */
+/* -pen N >= 1 (0) and -xdrop N >= 0 (-1): -1 for either */
+int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out);
+/* -mdep N >= 1 (4) and -mpct P in [0, 100] (20): -1 and -2 */
+int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out);
+/* -ploidy 1|2 (2), -err Q in [1, 93] (20), -hetq N in [0, 999] (30), -qual N in [0, 999] (20): -1 to -4 */
+int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, int *hetq_out, int *qual_out);
+/* -depth: is it given? */
 int slh_parse_depth(int argc, char **argv);
-/* -dedup and -dslots N (the slots of its table, a power of two from 64 to 2^32): bit 0 of the result -dedup was given, bit 1
-   -dslots was, with its value in *slots_out (0: not given); -1: -dslots without such a value */
+/* -dedup and -dslots N, a power of two in [64, 2^32] (0): bit 0 of the result says that -dedup is there, bit 1 that -dslots is;
+ * -1 when the value of -dslots is refused */
 int slh_parse_dedup(int argc, char **argv, uint64_t *slots_out);
-/* -lev LIST (-le...) and -win N (-wi...) of -depth: LIST is 1 to 16 whole numbers in [1, 2^32), strictly ascending, separated by
- * commas (levels_out has room for 16); N is a whole number of at least 1.  0 when neither is there (*num_levels_out = 0,
- * *window_out = 0), else bit 0 says that -lev is there and bit 1 that -win is; -1 when the value of -lev is missing or no such
- * list, -2 when that of -win is missing or no such number.  Neither value is ever taken for a file name. */
+/* -lev LIST and -win N >= 1 (0): LIST is 1 to 16 whole numbers in [1, 2^32), strictly ascending, separated by commas (levels_out
+ * has room for 16); both begin with a digit.  Bit 0 of the result says that -lev is there, bit 1 that -win is; -1 and -2 */
 int slh_parse_depth_params(int argc, char **argv, uint32_t *levels_out, int *num_levels_out, uint64_t *window_out);
+/* Everything the command line says, for main(): slh_options and the values of the entry points above, with the switches. */
+typedef struct {
+    slh_options o;
+    int max_occ, max_gap, ext_pen, ext_xdrop, max_edits, min_mapq;
+    int min_bq, bq_given; /* (what slh_parse_min_bq returned) */
+    int min_depth, min_pct; /* (-depth without -mdep: min_depth = 1) */
+    uint64_t ev_slots, dd_slots;
+    uint32_t levels[16];
+    int num_levels;
+    uint64_t window;
+    int gt_ploidy, gt_err, gt_hetq, gt_qual;
+    int sites, vcf, cons, depth, sam, dedup, gt;
+} slh_run;
+/* Parses, then refuses: bad values, an option without the mode it belongs to, modes that exclude each other -- the first that
+ * applies, its message in *refusal.  Returns 0 (accepted, or o.usage / o.hidden_sort / o.hidden_clean is set and nothing was
+ * refused), -1 (refused), or -2 (refused for too few files or an empty -r string: the caller first makes the checks that need
+ * more than the arguments).  Release out->o with slh_free_options. */
+int slh_parse_run(int argc, char **argv, slh_run *out, const char **refusal);
 /* AppendToBasename (tools.c:65-79): everything before the last '.' of the whole path + extra */
 char *slh_append_to_basename(const char *filename, const char *extra);
 
@@ -237,10 +257,6 @@ int slh_format_vcf_gt_rows(slh_buffer *buf, const char *record_name, uint64_t re
                            const uint64_t *site_pos, const uint32_t *site_counts, const slh_genotype *site_gts, uint64_t sites,
                            const slh_event *events, const uint32_t *anchor_rows, const slh_genotype *event_gts, const uint8_t *called,
                            uint64_t num_events);
-/* -ploidy 1|2 (-pl...), -err Q in [1, 93] (-er...), -hetq N in [0, 999] (-he...) and -qual N in [0, 999] (-qu...) of -gt.  0 when
- * none is there (the defaults 2, 20, 30, 20 in the four outputs), else 1; -1, -2, -3, -4 when the value of -ploidy, -err, -hetq,
- * -qual is missing, not an integer or out of range.  No value is ever taken for a file name. */
-int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, int *hetq_out, int *qual_out);
 /* -cons: one FASTA record -- '>' and the record's name up to its first blank or tab, then `len` letters in lines of 60; a record
  * of no letters is its header line alone */
 int slh_format_fasta_record(slh_buffer *buf, const char *record_name, const char *letters, uint64_t len);

@@ -24,6 +24,102 @@ class Options(C.Structure):
                 ("out_arg", C.c_int), ("num_files", C.c_int), ("file_args", C.POINTER(C.c_int))]
 
 
+class Run(C.Structure):
+    """slh_run: Options and the values behind the other entry points."""
+    _fields_ = [("o", Options)] + [(k, C.c_int) for k in ("max_occ", "max_gap", "ext_pen", "ext_xdrop", "max_edits", "min_mapq", "min_bq",
+                                                          "bq_given", "min_depth", "min_pct")] + \
+               [("ev_slots", C.c_uint64), ("dd_slots", C.c_uint64), ("levels", C.c_uint32 * 16), ("num_levels", C.c_int),
+                ("window", C.c_uint64)] + \
+               [(k, C.c_int) for k in ("gt_ploidy", "gt_err", "gt_hetq", "gt_qual", "sites", "vcf", "cons", "depth", "sam", "dedup", "gt")]
+
+
+class Piece(C.Structure):
+    _fields_ = [("rec", C.c_int), ("ends_record", C.c_int), ("start", C.c_uint64), ("a", C.c_uint64), ("b", C.c_uint64)]
+
+
+def c_argv(args):
+    return (C.c_char_p * (len(args) + 1))(*[a.encode() for a in args], None)
+
+
+def entry_points(args, L=None):
+    """Every slh_parse_* entry point on one argument vector: {name: [return code, outputs...]}, and the file arguments."""
+    L = L or lib()
+    argv, n = c_argv(args), len(args)
+    i = [C.c_int() for _ in range(4)]
+    u = C.c_uint64()
+    out = {}
+    for name in ("max_occ", "max_gap", "max_edits", "min_mapq", "min_bq"):
+        out[name] = [getattr(L, "slh_parse_" + name)(n, argv, C.byref(i[0])), i[0].value]
+    out["ext_params"] = [L.slh_parse_ext_params(n, argv, C.byref(i[0]), C.byref(i[1])), i[0].value, i[1].value]
+    out["sites_params"] = [L.slh_parse_sites_params(n, argv, C.byref(i[0]), C.byref(i[1])), i[0].value, i[1].value]
+    out["gt_params"] = [L.slh_parse_gt_params(n, argv, *[C.byref(x) for x in i])] + [x.value for x in i]
+    out["event_slots"] = [L.slh_parse_event_slots(n, argv, C.byref(u)), u.value]
+    out["depth"] = [L.slh_parse_depth(n, argv)]
+    out["dedup"] = [L.slh_parse_dedup(n, argv, C.byref(u)), u.value]
+    lev = (C.c_uint32 * 16)()
+    rc = L.slh_parse_depth_params(n, argv, lev, C.byref(i[0]), C.byref(u))
+    out["depth_params"] = [rc, list(lev[:i[0].value]), u.value]
+    o = Options()
+    rc = L.slh_parse_options(n, argv, C.byref(o))
+    out["options"] = [rc] + [getattr(o, k) for k, _ in Options._fields_ if k not in ("file_args", "ref_name")] + \
+                     [o.ref_name.decode(errors="replace") if o.ref_name else None]
+    out["files"] = [o.file_args[k] for k in range(o.num_files)]
+    L.slh_free_options.argtypes = [C.POINTER(Options)]
+    L.slh_free_options(C.byref(o))
+    return out
+
+
+def parse_run(args):
+    """slh_parse_run: (return code, refusal or None, the values as the old entry points name them)."""
+    L = lib()
+    r, msg = Run(), C.c_char_p()
+    rc = L.slh_parse_run(len(args), c_argv(args), C.byref(r), C.byref(msg))
+    vals = {"max_occ": r.max_occ, "max_gap": r.max_gap, "max_edits": r.max_edits, "min_mapq": r.min_mapq, "min_bq": r.min_bq,
+            "bq_given": r.bq_given, "ext_params": [r.ext_pen, r.ext_xdrop], "sites_params": [r.min_depth, r.min_pct],
+            "gt_params": [r.gt_ploidy, r.gt_err, r.gt_hetq, r.gt_qual], "event_slots": r.ev_slots, "dd_slots": r.dd_slots,
+            "levels": list(r.levels[:r.num_levels]), "window": r.window, "depth": r.depth, "dedup": r.dedup,
+            "files": [r.o.file_args[k] for k in range(r.o.num_files)] if r.o.file_args else [],
+            "flags": [r.sites, r.vcf, r.cons, r.sam, r.gt], "usage": r.o.usage, "hidden": [r.o.hidden_sort, r.o.hidden_clean],
+            "image_arg": r.o.image_arg}
+    refusal = msg.value.decode() if msg.value else None
+    L.slh_free_options(C.byref(r.o))
+    return rc, refusal, vals
+
+
+def option_rows():
+    """The rows of the option table: (name, takes a value)."""
+    L = lib()
+    rows, name, k = [], C.c_char_p(), 0
+    while (v := L.slh_option_info(k, C.byref(name))) >= 0:
+        rows.append((name.value.decode(), bool(v)))
+        k += 1
+    return rows
+
+
+def pieces(sizes, chunk):
+    """slh_next_piece over a merged text of records of these sizes, read in ranges of `chunk` rows: per range the pieces
+    (record, a, b, ends_record)."""
+    L = lib()
+    num = len(sizes)
+    recs = (Record * num)(*[Record(b"r%d" % k, s) for k, s in enumerate(sizes)])
+    starts, at = [], 0
+    for s in sizes:
+        starts.append(at)
+        at += s + 1
+    total = at - 1
+    ms = (C.c_uint32 * num)(*starts)
+    r, x, p, out = C.c_int(0), C.c_uint64(), Piece(), []
+    for x0 in range(0, total, chunk):
+        end, got = min(x0 + chunk, total), []
+        x.value = x0
+        while L.slh_next_piece(recs, ms, num, C.byref(r), C.byref(x), C.c_uint64(end), C.byref(p)):
+            assert p.start == starts[p.rec]
+            got.append((p.rec, p.a, p.b, p.ends_record))
+            assert len(got) <= num
+        out.append(got)
+    return out
+
+
 class Buffer(C.Structure):
     _fields_ = [("data", C.POINTER(C.c_char)), ("len", C.c_size_t), ("cap", C.c_size_t)]
 
