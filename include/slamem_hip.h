@@ -785,6 +785,28 @@ int slamem_pileup_genotype_events_device(slamem_pileup *pile, const slamem_event
 int slamem_pileup_genotype_events_host(slamem_pileup *pile, const slamem_event *events, const uint64_t *anchors, uint64_t m,
                                        const slamem_gt_params *params, slamem_genotype *gts, uint8_t *called);
 
+/* ---- (b''''''''') strand counts of the pileup (option -sb) -------------------------------------------------------
+ * An accumulator with strand counts owns a second one of the same layout, the forward accumulator, which receives exactly the
+ * contributions of the reads of strand 1 -- in the same kernels, which walk every read once and issue the atomics of such a read
+ * on both.  It is an ordinary accumulator without events and without a duplicate filter: every read-out (counts, rows_at, sites,
+ * genotypes, consensus, depth_runs) works on it, and the reverse strand's rows are the owner's minus its.  28 more bytes per
+ * text letter.
+ *   slamem_pileup_enable_strands  allocates the forward accumulator.  Only on an empty accumulator -- just created, or reset: after
+ *                          any add SLAMEM_ERR_ARG; a second call is a no-op.  Too little free device memory: SLAMEM_ERR_NOMEM.
+ *                          slamem_pileup_reset of the owner clears both, slamem_pileup_free frees both.
+ *   slamem_pileup_forward  the forward accumulator, borrowed: valid until the owner is freed.  Not enabled: SLAMEM_ERR_ARG.
+ * The borrowed handle refuses slamem_pileup_add_device, _add_masked_device, _add_dedup_device, _add_events_*, _enable_events,
+ * _enable_dedup, _enable_strands, slamem_stream_set_pileup and slamem_pileup_free with SLAMEM_ERR_ARG; slamem_pileup_add_counts_*
+ * on it is allowed (the tables of several GPUs are added up that way).
+ *   slamem_fisher_strand   host code: FS, the Phred-scaled two-sided Fisher exact test of the table t = (reference forward,
+ *                          reference reverse, alternative forward, alternative reverse), in doubles (slamem_fisher.h has the
+ *                          steps); 0 for an empty table or NULL.
+ *   slamem_fisher_strand_table  the table after the normalisation of its first step (cells of a sum above 400 scaled to 200). */
+int slamem_pileup_enable_strands(slamem_pileup *pile);
+int slamem_pileup_forward(slamem_pileup *pile, slamem_pileup **out);
+double slamem_fisher_strand(const uint32_t t[4]);
+void slamem_fisher_strand_table(const uint32_t t[4], uint32_t out[4]);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */

@@ -60,6 +60,7 @@ ABI_SYMBOLS = (
     "slamem_pileup_enable_dedup", "slamem_pileup_add_dedup_device", "slamem_pileup_dedup_stats", "slamem_stream_set_dedup", "slamem_stream_dups",
     "slamem_gt_costs", "slamem_pileup_genotypes_device", "slamem_pileup_genotypes_host", "slamem_pileup_genotype_events_device",
     "slamem_pileup_genotype_events_host",
+    "slamem_pileup_enable_strands", "slamem_pileup_forward", "slamem_fisher_strand", "slamem_fisher_strand_table",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
 )
@@ -238,6 +239,12 @@ def _declare(L):
     L.slamem_pileup_genotypes_host.argtypes = [vp, u64, u64, C.POINTER(GtParams), u64, vp, vp, vp, C.POINTER(u64)]
     L.slamem_pileup_genotype_events_device.argtypes = [vp, vp, vp, u64, C.POINTER(GtParams), vp, vp, vp]
     L.slamem_pileup_genotype_events_host.argtypes = [vp, vp, vp, u64, C.POINTER(GtParams), vp, vp]
+    L.slamem_pileup_enable_strands.argtypes = [vp]
+    L.slamem_pileup_forward.argtypes = [vp, C.POINTER(vp)]
+    L.slamem_fisher_strand.argtypes = [C.POINTER(u32)]
+    L.slamem_fisher_strand.restype = C.c_double
+    L.slamem_fisher_strand_table.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    L.slamem_fisher_strand_table.restype = None
     L.slamem_stream_dups.argtypes = [vp, C.POINTER(vp)]
     L.slamem_stream_mismatches.argtypes = [vp, C.POINTER(C.POINTER(u32))]
     L.slamem_stream_submit.argtypes = [vp, vp, vp, u32, u32]

@@ -3,6 +3,7 @@
 // usable gfx950 device every compute entry point fails with SLAMEM_ERR_NO_DEVICE / SLAMEM_ERR_HIP.
 #include "buffers.h"
 #include "common.h"
+#include "../../include/slamem_fisher.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -157,6 +158,16 @@ int slamem_gt_costs(uint32_t q, uint32_t out[3]) {
     out[1] = (uint32_t)floor(-10000.0 * log10(het) + 0.5);
     out[2] = (uint32_t)floor(-10000.0 * log10(third) + 0.5);
     return SLAMEM_OK;
+}
+
+// -sb: FS of a strand table and the table as the test sees it; include/slamem_fisher.h has the one definition
+double slamem_fisher_strand(const uint32_t t[4]) {
+    uint32_t norm[4];
+    return t ? slamem_fisher_strand_of(t, norm) : 0.0;
+}
+
+void slamem_fisher_strand_table(const uint32_t t[4], uint32_t out[4]) {
+    if (t && out) (void)slamem_fisher_strand_of(t, out);
 }
 
 int slamem_device_count(int* count_out) {

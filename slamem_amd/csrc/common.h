@@ -437,6 +437,9 @@ int map_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem
 // kernels over the outputs of a -paf batch as they lie on the device (nothing is checked on the host, nothing comes back);
 // pileup_device: the device the accumulator lives on.
 int pileup_device(const slamem_pileup* p);
+// for every entry point that a forward accumulator refuses (-sb): SLAMEM_OK, or SLAMEM_ERR_ARG and the message
+// "<fn>: ..." when `pile` is one
+int pile_refuse_child(const slamem_pileup* pile, const char* fn);
 int pileup_add(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
                const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
                const slamem_map* reads_dev, uint32_t min_mapq, hipStream_t stream);

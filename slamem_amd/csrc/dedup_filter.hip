@@ -205,6 +205,7 @@ extern "C" {
 
 int slamem_pileup_enable_dedup(slamem_pileup* pile, uint64_t slots) {
     if (!pile) { set_error("slamem_pileup_enable_dedup: null argument"); return SLAMEM_ERR_ARG; }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_enable_dedup"));
     if (pile->dd) { set_error("slamem_pileup_enable_dedup: the duplicate filter of this accumulator is enabled already"); return SLAMEM_ERR_ARG; }
     if (slots == 0) {  // the default: the smallest power of two that is at least max(65536, n / 4)
         const uint64_t want = (uint64_t)pile->n / 4 > 65536 ? (uint64_t)pile->n / 4 : 65536;
@@ -249,6 +250,7 @@ int slamem_pileup_add_dedup_device(slamem_pileup* pile, const void* queries_dev,
         set_error("slamem_pileup_add_dedup_device: null argument");
         return SLAMEM_ERR_ARG;
     }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_add_dedup_device"));
     if (!pile->dd) {
         set_error("slamem_pileup_add_dedup_device: the duplicate filter of this accumulator is not enabled (slamem_pileup_enable_dedup)");
         return SLAMEM_ERR_ARG;

@@ -398,6 +398,7 @@ extern "C" {
 
 int slamem_pileup_enable_events(slamem_pileup* pile, uint64_t slots) {
     if (!pile) { set_error("slamem_pileup_enable_events: null argument"); return SLAMEM_ERR_ARG; }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_enable_events"));
     if (pile->ev) { set_error("slamem_pileup_enable_events: the events of this accumulator are enabled already"); return SLAMEM_ERR_ARG; }
     if (slots == 0) {  // the default: the smallest power of two that is at least max(65536, n / 16)
         const uint64_t want = (uint64_t)pile->n / 16 > 65536 ? (uint64_t)pile->n / 16 : 65536;
@@ -446,9 +447,11 @@ int slamem_pileup_enable_events(slamem_pileup* pile, uint64_t slots) {
 
 int slamem_pileup_add_events_device(slamem_pileup* pile, const slamem_event* events_dev, uint64_t m, void* stream) {
     if (!pile || (m && !events_dev)) { set_error("slamem_pileup_add_events_device: null argument"); return SLAMEM_ERR_ARG; }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_add_events_device"));
     if (!pile->ev) { set_error("slamem_pileup_add_events_device: the events of this accumulator are not enabled"); return SLAMEM_ERR_ARG; }
     if (m == 0) return SLAMEM_OK;
     SLAMEM_HIP(hipSetDevice(pile->device));
+    pile->used.store(true, std::memory_order_relaxed);
     hipLaunchKernelGGL(k_events_insert, dim3(pile_grid(m, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), events_dev, m,
                        ev_acc(pile));
     SLAMEM_HIP(hipGetLastError());
@@ -457,6 +460,7 @@ int slamem_pileup_add_events_device(slamem_pileup* pile, const slamem_event* eve
 
 int slamem_pileup_add_events_host(slamem_pileup* pile, const slamem_event* events, uint64_t m) {
     if (!pile || (m && !events)) { set_error("slamem_pileup_add_events_host: null argument"); return SLAMEM_ERR_ARG; }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_add_events_host"));
     if (!pile->ev) { set_error("slamem_pileup_add_events_host: the events of this accumulator are not enabled"); return SLAMEM_ERR_ARG; }
     if (m == 0) return SLAMEM_OK;
     SLAMEM_HIP(hipSetDevice(pile->device));

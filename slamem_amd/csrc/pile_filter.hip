@@ -26,6 +26,10 @@
 //                  the two add kernels with a low-quality mask: a bit per letter of the batch's letter buffer,
 //                  and a letter whose bit is set counts nowhere under = and X.  The same bodies (a template parameter); an `=`
 //                  run ORs the mask's window over its letters into the text's exclusion bits, 64 rows at a time.
+//   k_strand_lane / k_strand_wave / k_strand_lane_masked / k_strand_wave_masked
+//                  the four add kernels of an accumulator with strand counts: the same bodies with a second
+//                  template parameter.  A read of strand 1 issues each of its atomics on the forward accumulator as well; the
+//                  operations, offsets and mask windows are loaded and formed once.
 // Counters are 32 bits wide and every sum is taken modulo 2^32: a true depth of 2^31 or more at one row is outside the contract.
 #include "buffers.h"
 #include "pile_shared.h"
@@ -43,8 +47,26 @@ struct PileAcc {
     uint32_t n;
 };
 
+// The writes of the walk.  kStrands: `f` is the forward accumulator (the same n, the same text) and `two` says that the read is of
+// strand 1, whose every atomic goes to both; without kStrands neither is looked at.
+template <bool kStrands>
+__device__ __forceinline__ void pile_diff(const PileAcc& a, const PileAcc& f, bool two, uint64_t x, int32_t v) {
+    atomicAdd(&a.diff[x], v);
+    if constexpr (kStrands) {
+        if (two) atomicAdd(&f.diff[x], v);
+    }
+}
+template <bool kStrands>
+__device__ __forceinline__ void pile_cnt(const PileAcc& a, const PileAcc& f, bool two, uint64_t at) {
+    atomicAdd(&a.cnt[at], 1u);
+    if constexpr (kStrands) {
+        if (two) atomicAdd(&f.cnt[at], 1u);
+    }
+}
+
 // an `=` run over rows [p, p + k): rows at and behind n are dropped, rows whose letter is none of A,C,G,T get nothing
-__device__ __forceinline__ void pile_eq(const PileAcc& a, uint64_t p, uint64_t k) {
+template <bool kStrands>
+__device__ __forceinline__ void pile_eq(const PileAcc& a, const PileAcc& f, bool two, uint64_t p, uint64_t k) {
     if (k == 0 || p >= a.n) return;
     if (p + k > a.n) k = a.n - p;
     const uint64_t e = p + k;  // <= n
@@ -56,8 +78,8 @@ __device__ __forceinline__ void pile_eq(const PileAcc& a, uint64_t p, uint64_t k
         any |= m;
     }
     if (!any) {
-        atomicAdd(&a.diff[p], 1);
-        atomicAdd(&a.diff[e], -1);
+        pile_diff<kStrands>(a, f, two, p, 1);
+        pile_diff<kStrands>(a, f, two, e, -1);
         return;
     }
     // (rare: only an anchor holds such a letter) row by row, a pair of atomics per stretch of A,C,G,T
@@ -66,14 +88,14 @@ __device__ __forceinline__ void pile_eq(const PileAcc& a, uint64_t p, uint64_t k
         const bool bad = (a.tpl[x >> 6].nm >> (x & 63u)) & 1ull;
         if (!bad && start == ~0ull) start = x;
         if (bad && start != ~0ull) {
-            atomicAdd(&a.diff[start], 1);
-            atomicAdd(&a.diff[x], -1);
+            pile_diff<kStrands>(a, f, two, start, 1);
+            pile_diff<kStrands>(a, f, two, x, -1);
             start = ~0ull;
         }
     }
     if (start != ~0ull) {
-        atomicAdd(&a.diff[start], 1);
-        atomicAdd(&a.diff[e], -1);
+        pile_diff<kStrands>(a, f, two, start, 1);
+        pile_diff<kStrands>(a, f, two, e, -1);
     }
 }
 
@@ -108,7 +130,9 @@ __device__ __forceinline__ uint64_t lowq_letters(const PileLow& m, uint64_t q, u
 // ORed into the text's, a text word (up to 64 rows) at a time.  A stretch between two excluded bits gets its pair of atomics;
 // ctz finds the stretches' ends, and one that reaches the chunk's end stays open into the next chunk -- a run without an
 // excluded bit costs its two atomics as before.
-__device__ __forceinline__ void pile_eq_masked(const PileAcc& a, const PileLow& m, uint64_t p, uint64_t k, uint64_t q) {
+template <bool kStrands>
+__device__ __forceinline__ void pile_eq_masked(const PileAcc& a, const PileAcc& f, bool two, const PileLow& m, uint64_t p, uint64_t k,
+                                               uint64_t q) {
     if (k == 0 || p >= a.n) return;
     if (p + k > a.n) k = a.n - p;
     const uint64_t e = p + k;  // <= n
@@ -129,40 +153,41 @@ __device__ __forceinline__ void pile_eq_masked(const PileAcc& a, const PileLow& 
             const uint64_t stop = bad & (~0ull << i);
             if (!stop) break;
             i = (uint32_t)__builtin_ctzll(stop);
-            atomicAdd(&a.diff[start], 1);
-            atomicAdd(&a.diff[x0 + i], -1);
+            pile_diff<kStrands>(a, f, two, start, 1);
+            pile_diff<kStrands>(a, f, two, x0 + i, -1);
             start = ~0ull;
         }
         x0 += c;
     }
     if (start != ~0ull) {
-        atomicAdd(&a.diff[start], 1);
-        atomicAdd(&a.diff[e], -1);
+        pile_diff<kStrands>(a, f, two, start, 1);
+        pile_diff<kStrands>(a, f, two, e, -1);
     }
 }
 
 // one operation at (p, q): every write is checked against n.  kMasked: a letter whose mask bit is set counts nowhere under = and
-// X; D and I are as without a mask.
-template <bool kMasked>
-__device__ __forceinline__ void pile_op(const PileAcc& a, const PileRead& r, const PileLow& m, uint32_t op, uint64_t p, uint64_t q) {
+// X; D and I are as without a mask.  kStrands: f and two as above.
+template <bool kMasked, bool kStrands>
+__device__ __forceinline__ void pile_op(const PileAcc& a, const PileAcc& f, bool two, const PileRead& r, const PileLow& m, uint32_t op,
+                                        uint64_t p, uint64_t q) {
     const uint32_t code = op & 15u;
     const uint64_t k = op >> 4;
     if (code == kOpEq) {
-        if constexpr (kMasked) pile_eq_masked(a, m, p, k, q);
-        else pile_eq(a, p, k);
+        if constexpr (kMasked) pile_eq_masked<kStrands>(a, f, two, m, p, k, q);
+        else pile_eq<kStrands>(a, f, two, p, k);
     } else if (code == kOpX) {
         for (uint64_t j = 0; j < k && p + j < a.n; j++) {
             const uint32_t c = pile_letter(r, q + j);
             if constexpr (kMasked) {
-                if (c < 4u && !lowq_letters(m, q + j, 1u)) atomicAdd(&a.cnt[(p + j) * 6u + c], 1u);
+                if (c < 4u && !lowq_letters(m, q + j, 1u)) pile_cnt<kStrands>(a, f, two, (p + j) * 6u + c);
             } else {
-                if (c < 4u) atomicAdd(&a.cnt[(p + j) * 6u + c], 1u);
+                if (c < 4u) pile_cnt<kStrands>(a, f, two, (p + j) * 6u + c);
             }
         }
     } else if (code == kOpD) {
-        for (uint64_t j = 0; j < k && p + j < a.n; j++) atomicAdd(&a.cnt[(p + j) * 6u + 4u], 1u);
+        for (uint64_t j = 0; j < k && p + j < a.n; j++) pile_cnt<kStrands>(a, f, two, (p + j) * 6u + 4u);
     } else if (code == kOpI) {
-        if (k && p < a.n) atomicAdd(&a.cnt[p * 6u + 5u], 1u);
+        if (k && p < a.n) pile_cnt<kStrands>(a, f, two, p * 6u + 5u);
     }
 }
 
@@ -179,8 +204,8 @@ __device__ __forceinline__ PileLow pile_low(const PileBatch& b, const PileRead& 
 }
 
 // a lane per read: its segments of up to kPileLaneOps operations
-template <bool kMasked>
-__device__ __forceinline__ void pile_lane_body(const PileBatch& b, const PileAcc& a, const uint64_t* lowq) {
+template <bool kMasked, bool kStrands>
+__device__ __forceinline__ void pile_lane_body(const PileBatch& b, const PileAcc& a, const PileAcc& f, const uint64_t* lowq) {
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (r >= b.nq) return;
     PileRead rd;
@@ -194,23 +219,33 @@ __device__ __forceinline__ void pile_lane_body(const PileBatch& b, const PileAcc
         uint64_t p = sg.ref_pos, q = sg.query_pos;
         for (uint64_t i = o0; i < o1; i++) {
             const uint32_t op = b.ops[i];
-            pile_op<kMasked>(a, rd, m, op, p, q);
+            pile_op<kMasked, kStrands>(a, f, !rd.rev, rd, m, op, p, q);
             p += pile_ref_step(op);
             q += pile_query_step(op);
         }
     }
 }
-__global__ void __launch_bounds__(256) k_pile_lane(PileBatch b, PileAcc a) { pile_lane_body<false>(b, a, nullptr); }
+__global__ void __launch_bounds__(256) k_pile_lane(PileBatch b, PileAcc a) { pile_lane_body<false, false>(b, a, a, nullptr); }
 __global__ void __launch_bounds__(256) k_pile_lane_masked(PileBatch b, PileAcc a, const uint64_t* __restrict__ lowq) {
-    pile_lane_body<true>(b, a, lowq);
+    pile_lane_body<true, false>(b, a, a, lowq);
+}
+__global__ void __launch_bounds__(256) k_strand_lane(PileBatch b, PileAcc a, PileAcc f) { pile_lane_body<false, true>(b, a, f, nullptr); }
+__global__ void __launch_bounds__(256) k_strand_lane_masked(PileBatch b, PileAcc a, PileAcc f, const uint64_t* __restrict__ lowq) {
+    pile_lane_body<true, true>(b, a, f, lowq);
 }
 
 // a wave per 64 reads: the reads that have a segment of more than kPileLaneOps operations, one after the other; of such a read
 // those segments, 64 operations at a time
-template <bool kMasked>
-__device__ __forceinline__ void pile_wave_body(const PileBatch& b, const PileAcc& a, const uint64_t* lowq) {
+template <bool kMasked, bool kStrands>
+__device__ __forceinline__ void pile_wave_body(const PileBatch& b, const PileAcc& a, const PileAcc& f, const uint64_t* lowq) {
     const uint32_t lane = threadIdx.x;
     const uint64_t chunks = (b.nq + 63u) >> 6;
+    PileAcc g = f;
+    if constexpr (kStrands) {
+        // (the forward pointers live in vector registers: the body is at the limit of the scalar ones, and an atomic's address ends in
+        // a vector register anyway)
+        asm volatile("" : "+v"(g.diff), "+v"(g.cnt));
+    }
     for (uint64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
         const uint64_t r = c * 64u + lane;
         bool big = false;
@@ -238,7 +273,7 @@ __device__ __forceinline__ void pile_wave_body(const PileBatch& b, const PileAcc
                     const uint32_t op = have ? b.ops[base + lane] : 0u;
                     const uint64_t rs = pile_ref_step(op), qs = pile_query_step(op);
                     const uint64_t ri = wave_scan_inclusive(rs, lane), qi = wave_scan_inclusive(qs, lane);
-                    if (have) pile_op<kMasked>(a, rd, m, op, p + ri - rs, q + qi - qs);
+                    if (have) pile_op<kMasked, kStrands>(a, g, !rd.rev, rd, m, op, p + ri - rs, q + qi - qs);
                     p += __shfl(ri, 63, 64);
                     q += __shfl(qi, 63, 64);
                 }
@@ -246,9 +281,13 @@ __device__ __forceinline__ void pile_wave_body(const PileBatch& b, const PileAcc
         }
     }
 }
-__global__ void __launch_bounds__(64) k_pile_wave(PileBatch b, PileAcc a) { pile_wave_body<false>(b, a, nullptr); }
+__global__ void __launch_bounds__(64) k_pile_wave(PileBatch b, PileAcc a) { pile_wave_body<false, false>(b, a, a, nullptr); }
 __global__ void __launch_bounds__(64) k_pile_wave_masked(PileBatch b, PileAcc a, const uint64_t* __restrict__ lowq) {
-    pile_wave_body<true>(b, a, lowq);
+    pile_wave_body<true, false>(b, a, a, lowq);
+}
+__global__ void __launch_bounds__(64) k_strand_wave(PileBatch b, PileAcc a, PileAcc f) { pile_wave_body<false, true>(b, a, f, nullptr); }
+__global__ void __launch_bounds__(64) k_strand_wave_masked(PileBatch b, PileAcc a, PileAcc f, const uint64_t* __restrict__ lowq) {
+    pile_wave_body<true, true>(b, a, f, lowq);
 }
 
 // ---- read-out --------------------------------------------------------------------------------------------------------------
@@ -539,15 +578,33 @@ int pileup_add_masked(slamem_pileup* pile, const void* queries_dev, const uint64
     a.cnt = pile->cnt;
     a.n = pile->n;
     const unsigned chunks = pile_grid(num_queries, 64);
-    if (lowq_dev) {  // (the same two kernels with the mask; without one, the instantiations that were there before)
-        hipLaunchKernelGGL(k_pile_lane_masked, dim3(pile_grid(num_queries, 256)), dim3(256), 0, stream, b, a, lowq_dev);
+    const dim3 lane_grid(pile_grid(num_queries, 256)), wave_grid(chunks < kPileWaveGrid ? chunks : kPileWaveGrid);
+    pile->used.store(true, std::memory_order_relaxed);
+    if (pile->fwd) {  // (one walk of the reads, the atomics of the strand-1 reads on both accumulators)
+        PileAcc f = a;
+        f.diff = pile->fwd->diff;
+        f.cnt = pile->fwd->cnt;
+        pile->fwd->used.store(true, std::memory_order_relaxed);
+        if (lowq_dev) {
+            hipLaunchKernelGGL(k_strand_lane_masked, lane_grid, dim3(256), 0, stream, b, a, f, lowq_dev);
+            SLAMEM_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_strand_wave_masked, wave_grid, dim3(64), 0, stream, b, a, f, lowq_dev);
+            SLAMEM_HIP(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(k_strand_lane, lane_grid, dim3(256), 0, stream, b, a, f);
+            SLAMEM_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_strand_wave, wave_grid, dim3(64), 0, stream, b, a, f);
+            SLAMEM_HIP(hipGetLastError());
+        }
+    } else if (lowq_dev) {  // (the same two kernels with the mask; without one, the instantiations that were there before)
+        hipLaunchKernelGGL(k_pile_lane_masked, lane_grid, dim3(256), 0, stream, b, a, lowq_dev);
         SLAMEM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_pile_wave_masked, dim3(chunks < kPileWaveGrid ? chunks : kPileWaveGrid), dim3(64), 0, stream, b, a, lowq_dev);
+        hipLaunchKernelGGL(k_pile_wave_masked, wave_grid, dim3(64), 0, stream, b, a, lowq_dev);
         SLAMEM_HIP(hipGetLastError());
     } else {
-        hipLaunchKernelGGL(k_pile_lane, dim3(pile_grid(num_queries, 256)), dim3(256), 0, stream, b, a);
+        hipLaunchKernelGGL(k_pile_lane, lane_grid, dim3(256), 0, stream, b, a);
         SLAMEM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_pile_wave, dim3(chunks < kPileWaveGrid ? chunks : kPileWaveGrid), dim3(64), 0, stream, b, a);
+        hipLaunchKernelGGL(k_pile_wave, wave_grid, dim3(64), 0, stream, b, a);
         SLAMEM_HIP(hipGetLastError());
     }
     if (pile->ev) return events_add(pile, &b, stream);  // (the indel events of the same batch, behind the two kernels)
@@ -563,6 +620,13 @@ int pile_tile_prefix(slamem_pileup* pile, uint64_t end, hipStream_t stream) {
     return SLAMEM_OK;
 }
 
+int pile_refuse_child(const slamem_pileup* pile, const char* fn) {
+    if (!pile->child) return SLAMEM_OK;
+    set_error("%s: this is the forward accumulator of another (slamem_pileup_forward): it is read, and counts may be added to it, but "
+              "its owner adds the reads, enables and frees", fn);
+    return SLAMEM_ERR_ARG;
+}
+
 int pile_scan_counts(uint64_t* sel, uint64_t tiles, hipStream_t stream) {
     hipLaunchKernelGGL(k_sites_tile_scan, dim3(1), dim3(1024), 0, stream, sel, tiles);
     SLAMEM_HIP(hipGetLastError());
@@ -573,14 +637,8 @@ int pile_scan_counts(uint64_t* sel, uint64_t tiles, hipStream_t stream) {
 
 extern "C" {
 
-int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
-    if (!idx || !out) { set_error("slamem_pileup_create: null argument"); return SLAMEM_ERR_ARG; }
-    *out = nullptr;
-    if (idx->hdr.off_tpl == 0 || !idx->view.tpl) {
-        set_error("slamem_pileup_create: -pile reads the text planes of the index, and this index has none (the compact layout, or "
-                  "one built without the seed sections)");
-        return SLAMEM_ERR_ARG;
-    }
+// the accumulator of slamem_pileup_create, and the forward one of slamem_pileup_enable_strands (`fn` names the caller in messages)
+static int pile_new(const slamem_index* idx, const char* fn, bool child, slamem_pileup** out) {
     SLAMEM_HIP(hipSetDevice(idx->device));
     const uint64_t n = idx->hdr.n;
     const uint64_t tiles = n / kPileTile + 2;
@@ -588,14 +646,16 @@ int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
     size_t free_b = 0, total_b = 0;
     SLAMEM_HIP(hipMemGetInfo(&free_b, &total_b));
     if (need > free_b) {
-        set_error("slamem_pileup_create: the accumulator of a text of %llu letters takes %llu bytes (28 per letter), %llu are free on "
-                  "device %d", (unsigned long long)n, (unsigned long long)need, (unsigned long long)free_b, idx->device);
+        set_error("%s: the %saccumulator of a text of %llu letters takes %llu bytes (28 per letter), %llu are free on "
+                  "device %d", fn, child ? "forward " : "", (unsigned long long)n, (unsigned long long)need, (unsigned long long)free_b,
+                  idx->device);
         return SLAMEM_ERR_NOMEM;
     }
     slamem_pileup* p = new (std::nothrow) slamem_pileup();
     if (!p) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     p->idx = idx; p->device = idx->device; p->n = (uint32_t)n;
     p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr; p->cons = nullptr; p->depth = nullptr; p->dd = nullptr;
+    p->fwd = nullptr; p->child = false; p->used.store(false, std::memory_order_relaxed);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->diff), (n + 1) * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->cnt), n * 24 + 16);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->tile), tiles * 4);
@@ -605,15 +665,49 @@ int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         (void)slamem_pileup_free(p);
-        return hip_fail(e, "slamem_pileup_create", __FILE__, __LINE__);
+        return hip_fail(e, fn, __FILE__, __LINE__);
     }
+    p->child = child;
     *out = p;
     return SLAMEM_OK;
 }
 
-int slamem_pileup_free(slamem_pileup* p) {
-    if (!p) return SLAMEM_OK;
+int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
+    if (!idx || !out) { set_error("slamem_pileup_create: null argument"); return SLAMEM_ERR_ARG; }
+    *out = nullptr;
+    if (idx->hdr.off_tpl == 0 || !idx->view.tpl) {
+        set_error("slamem_pileup_create: -pile reads the text planes of the index, and this index has none (the compact layout, or "
+                  "one built without the seed sections)");
+        return SLAMEM_ERR_ARG;
+    }
+    return pile_new(idx, "slamem_pileup_create", false, out);
+}
+
+int slamem_pileup_enable_strands(slamem_pileup* pile) {
+    if (!pile) { set_error("slamem_pileup_enable_strands: null argument"); return SLAMEM_ERR_ARG; }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_enable_strands"));
+    if (pile->fwd) return SLAMEM_OK;
+    if (pile->used.load(std::memory_order_relaxed)) {
+        set_error("slamem_pileup_enable_strands: something was added to this accumulator already; strand counts start on an empty one "
+                  "(just created, or after slamem_pileup_reset)");
+        return SLAMEM_ERR_ARG;
+    }
+    return pile_new(pile->idx, "slamem_pileup_enable_strands", true, &pile->fwd);
+}
+
+int slamem_pileup_forward(slamem_pileup* pile, slamem_pileup** out) {
+    if (!pile || !out) { set_error("slamem_pileup_forward: null argument"); return SLAMEM_ERR_ARG; }
+    *out = pile->fwd;
+    if (!pile->fwd) {
+        set_error("slamem_pileup_forward: the strand counts of this accumulator are not enabled (slamem_pileup_enable_strands)");
+        return SLAMEM_ERR_ARG;
+    }
+    return SLAMEM_OK;
+}
+
+static void pile_release(slamem_pileup* p) {
     (void)hipSetDevice(p->device);
+    if (p->fwd) { pile_release(p->fwd); p->fwd = nullptr; }
     if (p->diff) (void)hipFree(p->diff);
     if (p->cnt) (void)hipFree(p->cnt);
     if (p->tile) (void)hipFree(p->tile);
@@ -623,6 +717,12 @@ int slamem_pileup_free(slamem_pileup* p) {
     depth_free(p);
     dedup_free(p);
     delete p;
+}
+
+int slamem_pileup_free(slamem_pileup* p) {
+    if (!p) return SLAMEM_OK;
+    SLAMEM_TRY(pile_refuse_child(p, "slamem_pileup_free"));
+    pile_release(p);
     return SLAMEM_OK;
 }
 
@@ -634,7 +734,13 @@ int slamem_pileup_reset(slamem_pileup* p) {
     SLAMEM_HIP(hipMemset(p->cnt, 0, (uint64_t)p->n * 24));
     if (p->ev) { const int rc = events_reset(p); if (rc != SLAMEM_OK) return rc; }
     if (p->dd) { const int rc = dedup_reset(p); if (rc != SLAMEM_OK) return rc; }
+    if (p->fwd) {  // (a forward accumulator has neither events nor a filter)
+        SLAMEM_HIP(hipMemset(p->fwd->diff, 0, ((uint64_t)p->n + 1) * 4));
+        SLAMEM_HIP(hipMemset(p->fwd->cnt, 0, (uint64_t)p->n * 24));
+    }
     SLAMEM_HIP(hipDeviceSynchronize());
+    p->used.store(false, std::memory_order_relaxed);
+    if (p->fwd) p->fwd->used.store(false, std::memory_order_relaxed);
     return SLAMEM_OK;
 }
 
@@ -645,6 +751,7 @@ int slamem_pileup_add_device(slamem_pileup* pile, const void* queries_dev, const
         set_error("slamem_pileup_add_device: null argument");
         return SLAMEM_ERR_ARG;
     }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_add_device"));
     if (min_mapq > 60u) { set_error("slamem_pileup_add_device: the minimum mapping quality is 0 to 60"); return SLAMEM_ERR_ARG; }
     SLAMEM_HIP(hipSetDevice(pile->device));
     return pileup_add(pile, queries_dev, offsets_dev, num_queries, segs_dev, read_offsets_dev, ops_dev, op_offsets_dev, reads_dev,
@@ -659,6 +766,7 @@ int slamem_pileup_add_masked_device(slamem_pileup* pile, const void* queries_dev
         set_error("slamem_pileup_add_masked_device: null argument");
         return SLAMEM_ERR_ARG;
     }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_add_masked_device"));
     if (min_mapq > 60u) { set_error("slamem_pileup_add_masked_device: the minimum mapping quality is 0 to 60"); return SLAMEM_ERR_ARG; }
     SLAMEM_HIP(hipSetDevice(pile->device));
     return pileup_add_masked(pile, queries_dev, offsets_dev, num_queries, segs_dev, read_offsets_dev, ops_dev, op_offsets_dev,
@@ -790,6 +898,7 @@ int slamem_pileup_add_counts_device(slamem_pileup* pile, uint64_t first, uint64_
     }
     if (count == 0) return SLAMEM_OK;
     SLAMEM_HIP(hipSetDevice(pile->device));
+    pile->used.store(true, std::memory_order_relaxed);
     hipLaunchKernelGGL(k_pile_add_counts, dim3(pile_grid(count * 6u, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), pile->cnt,
                        (uint64_t)pile->n, first, count, rows_dev);
     SLAMEM_HIP(hipGetLastError());

@@ -6,6 +6,8 @@
 #pragma once
 #include "common.h"
 
+#include <atomic>
+
 namespace slamem {
 
 struct EvTable;  // event_filter.hip: the hash table of the indel events, its counters and its read-out's scratch
@@ -27,6 +29,9 @@ struct slamem_pileup {
     slamem::ConsScratch* cons;  // nullptr: no consensus was read yet
     slamem::DepthScratch* depth;  // nullptr: no depth runs were read yet
     slamem::DdTable* dd;  // nullptr: the duplicate filter is not enabled
+    slamem_pileup* fwd;   // nullptr: strand counts are not enabled; else the forward accumulator, owned
+    bool child;           // this is the forward accumulator of another: no adds of reads, nothing to enable, freed by its owner
+    std::atomic<bool> used;  // something was added since creation or the last reset
 };
 
 namespace slamem {

@@ -1010,6 +1010,7 @@ int slamem_stream_md(slamem_stream* s, const uint32_t** md_out, const uint64_t**
 
 int slamem_stream_set_pileup(slamem_stream* s, slamem_pileup* pile, uint32_t min_mapq) {
     if (!s || !pile) { set_error("slamem_stream_set_pileup: null argument"); return SLAMEM_ERR_ARG; }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_stream_set_pileup"));
     std::unique_lock<std::mutex> lk(s->mu);
     if (s->match_type != 8) {
         set_error("slamem_stream_set_pileup: an accumulator needs match type 8 (-pile)");

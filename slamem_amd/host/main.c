@@ -673,6 +673,8 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-err\twith -gt: the error rate of a read letter in Phred, 1 to 93 (default=20)\n");
     printf("\t-hetq\twith -gt: the prior cost of a non-reference allele in Phred, 0 to 999 (default=30)\n");
     printf("\t-qual\twith -gt: least QUAL of a call, 0 to 999 (default=20)\n");
+    printf("\t-sb\twith -gt: strand counts in the pileup (a second accumulator on the GPU, fed by the forward-strand reads in the same pass); every line gets the strand table SB = reference forward, reference reverse, alternative forward, alternative reverse in the sample column and FS, the Phred-scaled Fisher exact test of it, in INFO\n");
+    printf("\t-fs\twith -sb: FILTER is sb for a line whose FS is above this whole number, 0 to 999, and PASS otherwise (default: FILTER stays .)\n");
     printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
@@ -699,6 +701,7 @@ typedef struct {
     char **argv;
     slh_run p;            /* what the command line says */
     slamem_gt_params gtp; /* -gt: the costs behind p.gt_* */
+    int sb, fs;           /* -sb: strand counts; -fs N, or -1 */
     int device, timing;
     long log_limit;
     uint64_t batch_bytes;  /* query characters per batch and GPU */
@@ -761,6 +764,7 @@ static int parse_and_refuse(run_t *R, int *status) {
         return 1;
     }
     if (rc == -1) exit_message(refusal);
+    R->sb = slh_parse_sb_params(argc, argv, &R->fs) & 1; /* (refused above when the value of -fs is not one) */
     memset(&R->gtp, 0, sizeof(R->gtp));
     if (R->p.gt) { /* host arithmetic: the three costs of a letter at the error rate of -err */
         uint32_t costs[3];
@@ -909,6 +913,8 @@ static void open_output(run_t *R) {
     if (p->bq_given == 1) say(" ; minimum base quality = %d", p->min_bq); /* (only when asked for: the line of a run without -bq stays) */
     if (p->gt) say(" ; minimum depth = %d ; ploidy = %d ; error rate = %d Phred ; prior = %d Phred ; minimum quality = %d", p->min_depth, p->gt_ploidy, p->gt_err, p->gt_hetq, p->gt_qual);
     else if (p->sites || p->vcf) say(" ; minimum depth = %d ; minimum share = %d %%", p->min_depth, p->min_pct);
+    if (R->sb) say(" ; strand bias = on");
+    if (R->sb && R->fs >= 0) say(" ; maximum FS = %d", R->fs);
     if (p->cons) say(" ; minimum depth = %d", p->min_depth);
     if (p->depth) say(" ; covered from depth = %d", p->min_depth);
     say("\n");
@@ -1056,6 +1062,7 @@ static void open_streams(run_t *R) {
         if (p->max_occ > 0) rc = slamem_stream_set_max_occ(s, (uint32_t)p->max_occ);
         if (rc == SLAMEM_OK && t == 8) { /* one accumulator per GPU: the tables are added when the file is written */
             rc = slamem_pileup_create(R->gpus[g], &R->piles[g]);
+            if (rc == SLAMEM_OK && R->sb) rc = slamem_pileup_enable_strands(R->piles[g]);
             if (rc == SLAMEM_OK && (p->vcf || p->cons)) rc = slamem_pileup_enable_events(R->piles[g], p->ev_slots);
             if (rc == SLAMEM_OK && p->dedup) rc = slamem_pileup_enable_dedup(R->piles[g], p->dd_slots);
             if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(s, R->piles[g], (uint32_t)p->min_mapq);
@@ -1314,6 +1321,16 @@ static void merge_gpu_tables(run_t *R) {
             if (rc == SLAMEM_OK) rc = slamem_pileup_add_counts_host(R->piles[0], x0, cnt, rows);
             if (rc != SLAMEM_OK) pipeline_gpu_fail("adding up the pileups of the GPUs", rc);
         }
+    for (g = 1; R->sb && g < g_nstreams; g++) { /* -sb: the forward accumulators, exactly as their owners */
+        slamem_pileup *to = NULL, *from = NULL;
+        rc = slamem_pileup_forward(R->piles[0], &to);
+        if (rc == SLAMEM_OK) rc = slamem_pileup_forward(R->piles[g], &from);
+        FOR_RANGES(x0, cnt) {
+            if (rc == SLAMEM_OK) rc = slamem_pileup_counts_host(from, x0, cnt, rows);
+            if (rc == SLAMEM_OK) rc = slamem_pileup_add_counts_host(to, x0, cnt, rows);
+        }
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("adding up the forward-strand pileups of the GPUs", rc);
+    }
     free(rows);
     for (g = 1; with_events && g < g_nstreams; g++) {
         FOR_RANGES(x0, cnt) {
@@ -1386,30 +1403,36 @@ static void write_sites_or_vcf(run_t *R) {
     const slh_seqset *ref = &R->ref;
     const uint64_t n = ref->total;
     uint64_t x0, cnt, cap = 1ull << 20, ecap = 1ull << 16, total, etotal, k, ek, e, ee, j, *anchors = NULL;
-    uint32_t *arows = NULL;
+    uint32_t *arows = NULL, *frows = NULL, *afrows = NULL; /* -sb: the forward accumulator's rows at the sites and at the anchors */
+    slamem_pileup *fwd = NULL;
     slamem_genotype *egts = NULL; /* -gt: the genotypes of the events, and which events are called */
     uint8_t *ecalled = NULL;
     sites_call sc;
     events_call ec;
-    const grow_buf sbufs[4] = {{(void **)&sc.pos, 8, 0}, {(void **)&sc.rows, 24, 0}, {(void **)&sc.alleles, 1, 0}, {(void **)&sc.gts, sizeof(slamem_genotype), 0}};
-    const grow_buf ebufs[5] = {{(void **)&ec.evs, sizeof(slamem_event), 0}, {(void **)&anchors, 8, 0}, {(void **)&arows, 24, 0},
-                               {(void **)&egts, sizeof(slamem_genotype), 0}, {(void **)&ecalled, 1, 0}};
+    const grow_buf sbufs[5] = {{(void **)&sc.pos, 8, 0}, {(void **)&sc.rows, 24, 0}, {(void **)&sc.alleles, 1, 0}, {(void **)&sc.gts, sizeof(slamem_genotype), 0},
+                               {(void **)&frows, 24, 0}};
+    const grow_buf ebufs[6] = {{(void **)&ec.evs, sizeof(slamem_event), 0}, {(void **)&anchors, 8, 0}, {(void **)&arows, 24, 0},
+                               {(void **)&egts, sizeof(slamem_genotype), 0}, {(void **)&ecalled, 1, 0}, {(void **)&afrows, 24, 0}};
     int r = 0, m, pi, rc;
     memset(&sc, 0, sizeof(sc));
     memset(&ec, 0, sizeof(ec));
     sc.R = R;
     ec.pile = R->piles[0];
-    if (p->vcf && (p->gt ? slh_format_vcf_gt_header(&R->buf, ref->recs, ref->num) : slh_format_vcf_header(&R->buf, ref->recs, ref->num)))
+    if (R->sb && (rc = slamem_pileup_forward(R->piles[0], &fwd)) != SLAMEM_OK) pipeline_gpu_fail("reading the forward-strand pileup from the GPU", rc);
+    if (p->vcf && (R->sb ? slh_format_vcf_sb_header(&R->buf, ref->recs, ref->num, R->fs)
+                   : p->gt ? slh_format_vcf_gt_header(&R->buf, ref->recs, ref->num) : slh_format_vcf_header(&R->buf, ref->recs, ref->num)))
         pipeline_fail("Out of memory");
     FOR_RANGES(x0, cnt) {
         sc.x0 = ec.x0 = x0;
         sc.cnt = ec.cnt = cnt;
-        rc = fetch_growing(&cap, sbufs, p->gt ? 4 : 3, fetch_sites, &sc, &total);
+        rc = fetch_growing(&cap, sbufs, R->sb ? 5 : p->gt ? 4 : 3, fetch_sites, &sc, &total);
         if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the variant sites from the GPU", rc);
+        if (R->sb && (rc = slamem_pileup_rows_at_host(fwd, sc.pos, total, frows)) != SLAMEM_OK)
+            pipeline_gpu_fail("reading the forward-strand rows of the variant sites from the GPU", rc);
         m = pieces_of_range(R, &r, x0, cnt);
         etotal = 0;
         if (p->vcf) {
-            rc = fetch_growing(&ecap, ebufs, p->gt ? 5 : 3, fetch_events, &ec, &etotal);
+            rc = fetch_growing(&ecap, ebufs, R->sb ? 6 : p->gt ? 5 : 3, fetch_events, &ec, &etotal);
             if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the indel events from the GPU", rc);
             for (j = 0, pi = 0; j < etotal; j++) { /* the anchor row: the letter in front, or the event's own row at a record's start */
                 const uint64_t x = ec.evs[j].pos;
@@ -1417,6 +1440,7 @@ static void write_sites_or_vcf(run_t *R) {
                 anchors[j] = x > (m ? R->pcs[pi].start : 0) ? x - 1 : x;
             }
             rc = slamem_pileup_rows_at_host(R->piles[0], anchors, etotal, arows);
+            if (rc == SLAMEM_OK && R->sb) rc = slamem_pileup_rows_at_host(fwd, anchors, etotal, afrows);
             if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the pileup rows of the indel events from the GPU", rc);
             if (p->gt) { /* every event on its own against everything else at its anchor, on the GPU */
                 rc = slamem_pileup_genotype_events_host(R->piles[0], ec.evs, anchors, etotal, &R->gtp, egts, ecalled);
@@ -1433,6 +1457,9 @@ static void write_sites_or_vcf(run_t *R) {
             for (ee = ek; ee < etotal && ec.evs[ee].pos < pc->start + size; ee++) {}
             if (e == k && ee == ek) continue;
             if (!p->vcf ? slh_format_site_rows(&R->buf, name, pc->start, ref->chars, sc.pos + k, sc.rows + k * 6, sc.alleles + k, e - k)
+                : R->sb ? slh_format_vcf_sb_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6, frows + k * 6,
+                                                 (const slh_genotype *)(sc.gts + k), e - k, (const slh_event *)(ec.evs + ek), arows + ek * 6,
+                                                 afrows + ek * 6, (const slh_genotype *)(egts + ek), ecalled + ek, ee - ek, R->fs)
                 : p->gt ? slh_format_vcf_gt_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6,
                                                  (const slh_genotype *)(sc.gts + k), e - k, (const slh_event *)(ec.evs + ek), arows + ek * 6,
                                                  (const slh_genotype *)(egts + ek), ecalled + ek, ee - ek)
@@ -1444,7 +1471,7 @@ static void write_sites_or_vcf(run_t *R) {
         push_text(R);
     }
     free(sc.pos); free(sc.rows); free(sc.alleles); free(sc.gts);
-    free(ec.evs); free(anchors); free(arows); free(egts); free(ecalled);
+    free(ec.evs); free(anchors); free(arows); free(egts); free(ecalled); free(frows); free(afrows);
     if (p->vcf) warn_skipped(R, ec.sk);
 }
 

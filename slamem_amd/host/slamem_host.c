@@ -1,6 +1,7 @@
 /* slamem_host.c -- FASTA loading, option parsing and MEM text formatting of the slaMEM-compatible
  * front end.  Plain C, no GPU code; see slamem_host.h for the reference lines each piece restates. */
 #include "slamem_host.h"
+#include "../../include/slamem_fisher.h"
 
 #include <limits.h>
 #include <stdlib.h>
@@ -930,7 +931,7 @@ typedef struct {
     const char *refusal; /* of a bad value; a mode's: of another mode beside it */
 } option_row;
 enum { O_MEM, O_MAM, O_MUM, O_SMEM, O_OCC, O_CHAIN, O_MGAP, O_EXT, O_PEN, O_XDROP, O_ALN, O_MAXED, O_PAF, O_SAM, O_PILE, O_MINQ, O_BQ,
-       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_EVS,
+       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_EVS,
        O_L, O_O, O_B, O_N, O_M, O_R, O_V, O_S, O_C, NUM_OPTIONS };
 #define PEN_XDROP "Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"
 static const option_row OPTIONS[NUM_OPTIONS] = {
@@ -966,6 +967,8 @@ static const option_row OPTIONS[NUM_OPTIONS] = {
     [O_ERR] = {"err", 0, 0, V_INT, 0, 1, 93, 20, "Option -err needs a whole number from 1 to 93"},
     [O_HETQ] = {"hetq", 0, 0, V_INT, 0, 0, 999, 30, "Option -hetq needs a whole number from 0 to 999"},
     [O_QUAL] = {"qual", 0, 0, V_INT, 0, 0, 999, 20, "Option -qual needs a whole number from 0 to 999"},
+    [O_SB] = {"sb", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
+    [O_FS] = {"fs", 0, 0, V_INT, 0, 0, 999, -1, "Option -fs needs a whole number from 0 to 999"},
     [O_EVS] = {"evs", 0, 0, V_POW2, 0, 64, 1ull << 31, 0, "Option -evs needs a power of two of at least 64"},
     [O_L] = {"l", 0, 0, V_ATOI, 0, 0, 0, 20, NULL},
     [O_O] = {"o", 0, 0, V_INDEX, 0, 0, 0, -1, NULL},
@@ -1101,6 +1104,13 @@ int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, in
     int *outs[4] = {ploidy_out, err_out, hetq_out, qual_out};
     return scan_ints(argc, argv, ids, 4, outs);
 }
+int slh_parse_sb_params(int argc, char **argv, int *fs_out) {
+    static const int ids[2] = {O_SB, O_FS};
+    uint64_t v[2];
+    const int rc = scan_options(argc, argv, ids, 2, 0, v, NULL);
+    *fs_out = (int)(long long)v[1];
+    return rc < 0 ? -1 : rc;
+}
 int slh_parse_dedup(int argc, char **argv, uint64_t *slots_out) {
     static const int ids[2] = {O_DEDUP, O_DSLOTS};
     uint64_t v[2];
@@ -1196,7 +1206,7 @@ static int refuse(const char **refusal, const char *msg, int rc) {
 
 int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     slh_options *o = &r->o;
-    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct;
+    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct, sb, fs;
     *refusal = NULL;
     memset(r, 0, sizeof(*r));
     if (slh_parse_options(argc, argv, o) != 0) return refuse(refusal, "Out of memory", -1);
@@ -1220,6 +1230,7 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     dparams = slh_parse_depth_params(argc, argv, r->levels, &r->num_levels, &r->window);
     evs = slh_parse_event_slots(argc, argv, &r->ev_slots);
     dd = slh_parse_dedup(argc, argv, &r->dd_slots);
+    sb = slh_parse_sb_params(argc, argv, &fs); /* (the values are the caller's to ask for: slh_run keeps its layout) */
     r->dedup = dd > 0 && (dd & 1);
     if (o->usage || o->hidden_sort || o->hidden_clean) return 0; /* (the caller's business, before any refusal) */
 
@@ -1257,6 +1268,9 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     }
     REFUSE_IF(r->gt && !r->vcf, "Option -gt needs -vcf");
     REFUSE_IF(r->gt && mpct, "Option -mpct has no meaning with -gt: a call is made when its genotype's quality reaches -qual");
+    REFUSE_IF(sb < 0, OPTIONS[O_FS].refusal);
+    REFUSE_IF((sb & 1) && !r->gt, "Option -sb needs -gt");
+    REFUSE_IF((sb & 2) && !(sb & 1), "Option -fs needs -sb");
     REFUSE_IF(dparams < 0, OPTIONS[dparams == -1 ? O_LEV : O_WIN].refusal);
     REFUSE_IF(dparams == 3 && r->depth, "Options -lev and -win exclude each other");
     REFUSE_IF(dparams && !r->depth, "Options -lev and -win need -depth");
@@ -1825,6 +1839,135 @@ int slh_format_vcf_gt_rows(slh_buffer *buf, const char *record_name, uint64_t re
         }
     }
     return 0;
+}
+
+/* ---- -vcf -gt -sb ---- */
+
+/* the lines of `from` that begin with `prefix`, or the others */
+static int sb_copy_lines(slh_buffer *buf, const slh_buffer *from, const char *prefix, int matching) {
+    const size_t pl = strlen(prefix);
+    size_t i = 0;
+    while (i < from->len) {
+        size_t e = i;
+        while (e < from->len && from->data[e] != '\n') e++;
+        if (e < from->len) e++;
+        if ((e - i >= pl && memcmp(from->data + i, prefix, pl) == 0) == (matching != 0)) {
+            if (buf_reserve(buf, e - i)) return -1;
+            memcpy(buf->data + buf->len, from->data + i, e - i);
+            buf->len += e - i;
+        }
+        i = e;
+    }
+    return 0;
+}
+
+static int sb_put(slh_buffer *buf, const char *s) {
+    const size_t n = strlen(s);
+    if (buf_reserve(buf, n)) return -1;
+    memcpy(buf->data + buf->len, s, n);
+    buf->len += n;
+    return 0;
+}
+
+int slh_format_vcf_sb_header(slh_buffer *buf, const slh_record *refs, int num_refs, int fs_filter) {
+    slh_buffer gt = {0, 0, 0};
+    char line[160];
+    int rc = slh_format_vcf_gt_header(&gt, refs, num_refs);
+    /* the head of -vcf -gt, with FILTER in front of the INFO lines, FS behind them and SB behind the FORMAT lines */
+    if (!rc) rc = sb_copy_lines(buf, &gt, "##fileformat", 1);
+    if (!rc) rc = sb_copy_lines(buf, &gt, "##contig", 1);
+    if (!rc && fs_filter >= 0) {
+        snprintf(line, sizeof(line), "##FILTER=<ID=sb,Description=\"Strand bias: FS above %d\">\n", fs_filter);
+        rc = sb_put(buf, line);
+    }
+    if (!rc) rc = sb_copy_lines(buf, &gt, "##INFO", 1);
+    if (!rc) rc = sb_put(buf, "##INFO=<ID=FS,Number=1,Type=Float,Description=\"Phred-scaled p-value of Fisher's exact test of the strand table SB\">\n");
+    if (!rc) rc = sb_copy_lines(buf, &gt, "##FORMAT", 1);
+    if (!rc) rc = sb_put(buf, "##FORMAT=<ID=SB,Number=4,Type=Integer,Description=\"Observations of the reference on forward and reverse reads, "
+                              "then of the alternate alleles on forward and reverse reads\">\n");
+    if (!rc) rc = sb_copy_lines(buf, &gt, "#CHROM", 1);
+    slh_buffer_free(&gt);
+    return rc;
+}
+
+static uint32_t sb_cell(uint64_t v) { return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v; }
+static uint64_t sb_minus(uint64_t a, uint64_t b) { return a > b ? a - b : 0; }
+
+/* The line that slh_format_vcf_gt_rows has just written at buf->data + start, with FILTER, ;FS= behind INFO, :SB behind FORMAT
+ * and the table behind the sample; tmp: scratch that is kept between lines. */
+static int sb_decorate(slh_buffer *buf, size_t start, const uint32_t t[4], int fs_filter, slh_buffer *tmp) {
+    const size_t n = buf->len - start;
+    uint32_t norm[4];
+    const double fs = slamem_fisher_strand_of(t, norm);
+    const char *verdict = fs > (double)fs_filter ? "sb" : "PASS";
+    const char *s;
+    char *p;
+    size_t i;
+    int col = 0, k;
+    tmp->len = 0;
+    if (buf_reserve(tmp, n)) return -1;
+    memcpy(tmp->data, buf->data + start, n);
+    if (buf_reserve(buf, 128)) return -1;
+    s = tmp->data;
+    p = buf->data + start;
+    for (i = 0; i < n; i++) {
+        const char c = s[i];
+        if (c == '\t' || c == '\n') { /* a column ends: what comes behind it */
+            if (col == 7) p += snprintf(p, 32, ";FS=%.3f", fs);
+            if (col == 8) { memcpy(p, ":SB", 3); p += 3; }
+            for (k = 0; col == 9 && k < 4; k++) {
+                *p++ = k ? ',' : ':';
+                p = put_u32(p, t[k]);
+            }
+            col++;
+        } else if (col == 6 && fs_filter >= 0) { /* (the "." of -gt) */
+            memcpy(p, verdict, strlen(verdict));
+            p += strlen(verdict);
+            continue;
+        }
+        *p++ = c;
+    }
+    buf->len = (size_t)(p - buf->data);
+    return 0;
+}
+
+int slh_format_vcf_sb_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                           const uint64_t *site_pos, const uint32_t *site_counts, const uint32_t *site_fwd, const slh_genotype *site_gts,
+                           uint64_t sites, const slh_event *events, const uint32_t *anchor_rows, const uint32_t *anchor_fwd,
+                           const slh_genotype *event_gts, const uint8_t *called, uint64_t num_events, int fs_filter) {
+    slh_buffer tmp = {0, 0, 0};
+    uint64_t i = 0, e = 0;
+    int rc = 0;
+    while (!rc && (i < sites || e < num_events)) { /* the order of slh_format_vcf_gt_rows, a line at a time */
+        const uint64_t spos = i < sites ? site_pos[i] - record_start + 1 : ~0ull;
+        uint64_t epos = ~0ull;
+        const size_t start = buf->len;
+        uint32_t t[4];
+        int k;
+        if (e < num_events) epos = events[e].pos > record_start ? events[e].pos - record_start : 1;
+        if (spos <= epos) {
+            const uint32_t *c = site_counts + 6 * i, *f = site_fwd + 6 * i;
+            const slh_genotype *g = &site_gts[i];
+            const int r = g->ref & 3;
+            uint64_t af = 0, ar = 0;
+            for (k = 0; k < 4; k++) /* the line's ALT letters: the best genotype's that are not the reference's */
+                if (k != r && (k == (g->a & 3) || k == (g->b & 3))) { af += f[k]; ar += sb_minus(c[k], f[k]); }
+            t[0] = f[r]; t[1] = sb_cell(sb_minus(c[r], f[r])); t[2] = sb_cell(af); t[3] = sb_cell(ar);
+            rc = slh_format_vcf_gt_rows(buf, record_name, record_start, record_size, text, site_pos + i, c, g, 1, NULL, NULL, NULL, NULL, 0);
+            i++;
+        } else {
+            const uint32_t *c = anchor_rows + 6 * e, *f = anchor_fwd + 6 * e;
+            const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4], df = (uint64_t)f[0] + f[1] + f[2] + f[3] + f[4];
+            const uint64_t af = events[e].fwd, ar = events[e].rev;
+            t[0] = sb_cell(sb_minus(df, af)); t[1] = sb_cell(sb_minus(sb_minus(d, df), ar)); t[2] = (uint32_t)af; t[3] = (uint32_t)ar;
+            rc = slh_format_vcf_gt_rows(buf, record_name, record_start, record_size, text, NULL, NULL, NULL, 0, events + e, c, event_gts + e,
+                                        called + e, 1);
+            e++;
+        }
+        if (!rc && buf->len > start) rc = sb_decorate(buf, start, t, fs_filter, &tmp);
+    }
+    slh_buffer_free(&tmp);
+    return rc;
 }
 
 int slh_format_block_aln(slh_buffer *buf, const char *query_name, int reverse, const uint32_t *segs, const uint32_t *ops,

@@ -130,6 +130,9 @@ int slh_parse_ext_params(int argc, char **argv, int *penalty_out, int *xdrop_out
 int slh_parse_sites_params(int argc, char **argv, int *min_depth_out, int *min_pct_out);
 /* -ploidy 1|2 (2), -err Q in [1, 93] (20), -hetq N in [0, 999] (30), -qual N in [0, 999] (20): -1 to -4 */
 int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, int *hetq_out, int *qual_out);
+/* -sb and -fs N in [0, 999] (-1: absent): bit 0 of the result says that -sb is there, bit 1 that -fs is; -1 when the value of -fs
+ * is refused */
+int slh_parse_sb_params(int argc, char **argv, int *fs_out);
 /* -depth: is it given? */
 int slh_parse_depth(int argc, char **argv);
 /* -dedup and -dslots N, a power of two in [64, 2^32] (0): bit 0 of the result says that -dedup is there, bit 1 that -dslots is;
@@ -257,6 +260,19 @@ int slh_format_vcf_gt_rows(slh_buffer *buf, const char *record_name, uint64_t re
                            const uint64_t *site_pos, const uint32_t *site_counts, const slh_genotype *site_gts, uint64_t sites,
                            const slh_event *events, const uint32_t *anchor_rows, const slh_genotype *event_gts, const uint8_t *called,
                            uint64_t num_events);
+/* -vcf -gt -sb.  The head of -vcf -gt with ##INFO FS behind its INFO lines, ##FORMAT SB behind its FORMAT lines
+ * and, when fs_filter >= 0 (-fs N), ##FILTER sb in front of the INFO lines. */
+int slh_format_vcf_sb_header(slh_buffer *buf, const slh_record *refs, int num_refs, int fs_filter);
+/* The lines of slh_format_vcf_gt_rows, each with its strand table (rf, rr, af, ar: reference forward and reverse, alternative
+ * forward and reverse) as a sixth sample value SB, ;FS= its slamem_fisher.h value with three decimals behind INFO, and with
+ * fs_filter >= 0 FILTER sb when FS > fs_filter, else PASS.  site_fwd, anchor_fwd: the rows of the forward accumulator at the
+ * sites and at the events' anchors.  SNV, r the reference column: rf = fwd[r], rr = row[r] - fwd[r], af and ar the same summed
+ * over the line's ALT letters.  Event: af = fwd, ar = rev of the event, and with d, df the depths A+C+G+T+D of the two rows
+ * rf = df - af and rr = (d - df) - ar.  Every difference stops at 0 and every cell at 2^32 - 1. */
+int slh_format_vcf_sb_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                           const uint64_t *site_pos, const uint32_t *site_counts, const uint32_t *site_fwd, const slh_genotype *site_gts,
+                           uint64_t sites, const slh_event *events, const uint32_t *anchor_rows, const uint32_t *anchor_fwd,
+                           const slh_genotype *event_gts, const uint8_t *called, uint64_t num_events, int fs_filter);
 /* -cons: one FASTA record -- '>' and the record's name up to its first blank or tab, then `len` letters in lines of 60; a record
  * of no letters is its header line alone */
 int slh_format_fasta_record(slh_buffer *buf, const char *record_name, const char *letters, uint64_t len);
