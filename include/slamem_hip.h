@@ -807,6 +807,55 @@ int slamem_pileup_forward(slamem_pileup *pile, slamem_pileup **out);
 double slamem_fisher_strand(const uint32_t t[4]);
 void slamem_fisher_strand_table(const uint32_t t[4], uint32_t out[4]);
 
+/* ---- (b'''''''''') quality sums of the pileup and the weighted genotypes -----------------------------------------
+ * An accumulator with quality sums owns a second one of the same layout, the quality accumulator Q.  A letter's quality is
+ * qv(b) = 0 when its byte b is below the Phred offset, else min(b - offset, 93); the quality of letter x of the scanned strand of a
+ * strand-2 read is the byte at len - 1 - x.  Every read that contributes to the pileup of an add contributes to Q (the same
+ * min_mapq, low-quality mask and duplicate decision): wherever the pileup's walk adds 1 to column A, C, G or T of a row, Q gets qv
+ * of that letter in the same column of the same row.  D and I add nothing: those two columns of Q stay 0.  So
+ * Q[p][c] <= 93 * counts[p][c], and with every quality equal to q, Q = q * counts on the four letter columns.  Sums are taken
+ * modulo 2^32: a depth below 2^25 at a row is inside the contract.  28 more bytes per text letter.
+ *   slamem_pileup_enable_quals  allocates Q.  Only on an empty accumulator -- just created, or reset: after any add
+ *                          SLAMEM_ERR_ARG; a second call is a no-op.  Too little free device memory: SLAMEM_ERR_NOMEM.
+ *                          slamem_pileup_reset of the owner clears both, slamem_pileup_free frees both.  It combines with
+ *                          _enable_strands, _enable_events and _enable_dedup in any order.
+ *   slamem_pileup_quality  Q, borrowed: valid until the owner is freed.  Not enabled: SLAMEM_ERR_ARG.  The read-outs with a
+ *                          meaning on it are slamem_pileup_counts_*, _rows_at_* and _add_counts_* (the tables of several GPUs are
+ *                          added up that way); it refuses what the forward accumulator refuses, and _enable_quals.
+ *   slamem_pileup_add_quals_device  the add of an accumulator with quality sums, the superset of slamem_pileup_add_device,
+ *                          _add_masked_device and _add_dedup_device: lowq_dev may be NULL (no mask); quals_dev holds a byte per
+ *                          letter, indexed as queries_dev is; dedup != 0 sends the batch through the duplicate filter (which must be
+ *                          enabled) and needs reads_keep_dev, dup_out_dev may be NULL.  The quality pass is a second pair of kernels
+ *                          behind the pile kernels of the same add on `stream`.  On an accumulator with quality sums the three
+ *                          other add entries are refused with SLAMEM_ERR_ARG -- Q would fall behind the counts; on one without,
+ *                          this entry is.
+ *   slamem_pileup_genotypes_weighted_device / _host  slamem_pileup_genotypes_* with one change and one more output: a letter i that
+ *                          a genotype does not hold costs c[i] * err_cost + 1000 * Q[i] in the place of c[i] * err_cost, and
+ *                          qsums gets the A C G T columns of Q's row, four uint32 per selected row (room for `capacity` rows).
+ *                          Best genotype, tie rule, qual, gq, pl, selection, saturation and the capacity contract are those of
+ *                          slamem_pileup_genotypes_*.  1000 * 2^32 < 2^42 per letter keeps every sum below 2^56.  -wq's costs are
+ *                          match_cost 0, het_cost 3010, err_cost 4771 (round(10000 log10 2) and round(10000 log10 3)): a
+ *                          miscalled letter of quality q costs 1000 q + 4771 = round(-10000 log10(e / 3)).  With Q all zero the
+ *                          read-out equals slamem_pileup_genotypes_* byte for byte; with every letter at quality q it equals it
+ *                          with err_cost + 1000 q.  Not enabled: SLAMEM_ERR_ARG.
+ *   slamem_stream_set_quals  a -pile stream whose accumulator has quality sums: before the first submit, behind
+ *                          slamem_stream_set_pileup.  Every batch then comes through slamem_stream_submit_quals (the other submits
+ *                          are refused), which takes the quality bytes beside the letters, indexed as they are (whatever
+ *                          offsets[0] is), and the low-quality mask of slamem_stream_submit_masked or NULL (declared with the stream, below). */
+int slamem_pileup_enable_quals(slamem_pileup *pile);
+int slamem_pileup_quality(slamem_pileup *pile, slamem_pileup **out);
+int slamem_pileup_add_quals_device(slamem_pileup *pile, const void *queries_dev, const uint64_t *offsets_dev, uint32_t num_queries,
+                                   const slamem_aln *segs_dev, const uint64_t *read_offsets_dev, const uint32_t *ops_dev,
+                                   const uint64_t *op_offsets_dev, const slamem_map *reads_dev, uint32_t min_mapq,
+                                   const uint64_t *lowq_dev, const uint8_t *quals_dev, uint32_t phred_offset, int dedup,
+                                   slamem_map *reads_keep_dev, uint8_t *dup_out_dev, void *stream);
+int slamem_pileup_genotypes_weighted_device(slamem_pileup *pile, uint64_t first, uint64_t count, const slamem_gt_params *params,
+                                            uint64_t capacity, uint64_t *pos_dev, uint32_t *counts_dev, slamem_genotype *gts_dev,
+                                            uint32_t *qsums_dev, uint64_t *total_out, void *stream);
+int slamem_pileup_genotypes_weighted_host(slamem_pileup *pile, uint64_t first, uint64_t count, const slamem_gt_params *params,
+                                          uint64_t capacity, uint64_t *pos, uint32_t *counts, slamem_genotype *gts, uint32_t *qsums,
+                                          uint64_t *total_out);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -918,6 +967,10 @@ int slamem_stream_set_pileup(slamem_stream *s, slamem_pileup *pile, uint32_t min
 /* -dedup (described with slamem_pileup_enable_dedup above) */
 int slamem_stream_set_dedup(slamem_stream *s, int on);
 int slamem_stream_dups(slamem_stream *s, const uint8_t **flags_out);
+/* -wq (described with slamem_pileup_enable_quals above) */
+int slamem_stream_set_quals(slamem_stream *s, uint32_t phred_offset);
+int slamem_stream_submit_quals(slamem_stream *s, const char *queries, const uint8_t *quals, const uint64_t *lowq,
+                               const uint64_t *offsets, uint32_t num_queries, uint32_t min_len);
 /* -sam: on != 0 makes every slot of a stream of match type 7 run slamem_maps_md_device behind its batch and
  * download the four arrays; before the first submit (SLAMEM_ERR_ARG after it, or on a stream of another match type).  A stream
  * that never calls it behaves as before and allocates nothing for this.  slamem_stream_md gives the arrays of the batch

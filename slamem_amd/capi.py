@@ -61,6 +61,8 @@ ABI_SYMBOLS = (
     "slamem_gt_costs", "slamem_pileup_genotypes_device", "slamem_pileup_genotypes_host", "slamem_pileup_genotype_events_device",
     "slamem_pileup_genotype_events_host",
     "slamem_pileup_enable_strands", "slamem_pileup_forward", "slamem_fisher_strand", "slamem_fisher_strand_table",
+    "slamem_pileup_enable_quals", "slamem_pileup_quality", "slamem_pileup_add_quals_device", "slamem_pileup_genotypes_weighted_device",
+    "slamem_pileup_genotypes_weighted_host", "slamem_stream_set_quals", "slamem_stream_submit_quals",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
 )
@@ -241,6 +243,13 @@ def _declare(L):
     L.slamem_pileup_genotype_events_host.argtypes = [vp, vp, vp, u64, C.POINTER(GtParams), vp, vp]
     L.slamem_pileup_enable_strands.argtypes = [vp]
     L.slamem_pileup_forward.argtypes = [vp, C.POINTER(vp)]
+    L.slamem_pileup_enable_quals.argtypes = [vp]
+    L.slamem_pileup_quality.argtypes = [vp, C.POINTER(vp)]
+    L.slamem_pileup_add_quals_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, C.c_int, vp, vp, vp]
+    L.slamem_pileup_genotypes_weighted_device.argtypes = [vp, u64, u64, C.POINTER(GtParams), u64, vp, vp, vp, vp, C.POINTER(u64), vp]
+    L.slamem_pileup_genotypes_weighted_host.argtypes = [vp, u64, u64, C.POINTER(GtParams), u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.slamem_stream_set_quals.argtypes = [vp, u32]
+    L.slamem_stream_submit_quals.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.slamem_fisher_strand.argtypes = [C.POINTER(u32)]
     L.slamem_fisher_strand.restype = C.c_double
     L.slamem_fisher_strand_table.argtypes = [C.POINTER(u32), C.POINTER(u32)]

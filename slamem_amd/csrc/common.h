@@ -437,8 +437,8 @@ int map_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem
 // kernels over the outputs of a -paf batch as they lie on the device (nothing is checked on the host, nothing comes back);
 // pileup_device: the device the accumulator lives on.
 int pileup_device(const slamem_pileup* p);
-// for every entry point that a forward accumulator refuses (-sb): SLAMEM_OK, or SLAMEM_ERR_ARG and the message
-// "<fn>: ..." when `pile` is one
+// for every entry point that a forward accumulator (-sb) or a quality accumulator (-wq) refuses:
+// SLAMEM_OK, or SLAMEM_ERR_ARG and the message "<fn>: ..." that names which of the two `pile` is
 int pile_refuse_child(const slamem_pileup* pile, const char* fn);
 int pileup_add(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
                const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
@@ -457,6 +457,15 @@ int pileup_add_dedup(slamem_pileup* pile, const void* queries_dev, const uint64_
                      const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
                      const slamem_map* reads_dev, uint32_t min_mapq, const uint64_t* lowq_dev, slamem_map* reads_keep_dev,
                      uint8_t* dup_out_dev, hipStream_t stream);
+// -wq (qual_filter.hip): the pile kernels of the batch (through the duplicate filter
+// when `dedup`), then the two quality kernels over the same batch -- under dedup the kept records -- on pile->qual
+int pileup_has_quals(const slamem_pileup* pile);
+int pileup_add_quals(slamem_pileup* pile, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                     const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
+                     const slamem_map* reads_dev, uint32_t min_mapq, const uint64_t* lowq_dev, const unsigned char* quals_dev,
+                     uint32_t phred_offset, bool dedup, slamem_map* reads_keep_dev, uint8_t* dup_out_dev, hipStream_t stream);
+// pile_filter.hip, for the three add entries without quality bytes: SLAMEM_ERR_ARG and a message on an accumulator with quality sums
+int pile_refuse_quals(const slamem_pileup* pile, const char* fn);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):
 // tables (one small sync) -> prep (K8a, work list, K7q; asynchronous) -> search (K8, K9, scalars to host_scalars; asynchronous)
 // -> collect (after the search stream has finished the batch: totals, capacity check, timings of the calling thread).

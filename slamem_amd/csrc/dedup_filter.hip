@@ -251,6 +251,7 @@ int slamem_pileup_add_dedup_device(slamem_pileup* pile, const void* queries_dev,
         return SLAMEM_ERR_ARG;
     }
     SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_add_dedup_device"));
+    SLAMEM_TRY(pile_refuse_quals(pile, "slamem_pileup_add_dedup_device"));
     if (!pile->dd) {
         set_error("slamem_pileup_add_dedup_device: the duplicate filter of this accumulator is not enabled (slamem_pileup_enable_dedup)");
         return SLAMEM_ERR_ARG;

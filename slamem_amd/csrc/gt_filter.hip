@@ -8,6 +8,9 @@
 //   k_gt_emit            a workgroup per tile: the same again; the selected rows go to the tile's offset + their rank in the tile
 //                        (ballots and popcounts in a wave, the waves' totals through LDS; no atomics), rows at or behind
 //                        `capacity` are dropped: pos, the six counters and the slamem_genotype
+//   k_gtw_count / k_gtw_emit
+//                        the two passes of the weighted read-out (-wq): the tile of the quality accumulator is
+//                        staged beside the counts', and a letter that a genotype does not hold costs E and 1000 times its quality
 //   k_gt_events          a lane per given event: its genotype against everything else at its anchor row, and whether it is called
 // The rule is evaluated in both passes rather than kept, as -sites does it (4.17).  The ten (four, three) scores of a row are
 // formed with compile-time indices only -- every loop over genotypes is unrolled and a genotype's number is compared, never used
@@ -60,8 +63,11 @@ __device__ __forceinline__ uint32_t gt_call(const uint64_t (&L)[10], const uint6
 }
 
 // the genotype of a row with the columns c[0..3] under the text's letter r (0..3).  Returns whether the best genotype is another
-// than the homozygous-reference one; qual in 64 bits.
-__device__ __forceinline__ bool gt_snv(const uint32_t (&c)[4], uint32_t r, const GtRule& p, GtCall& out, uint64_t& qual) {
+// than the homozygous-reference one; qual in 64 bits.  kWeighted: qs[0..3] are the row's quality sums, and the
+// letters i that a genotype does not hold cost c[i] * E + 1000 * qs[i]; without it qs is not looked at.
+template <bool kWeighted>
+__device__ __forceinline__ bool gt_snv(const uint32_t (&c)[4], const uint32_t (&qs)[4], uint32_t r, const GtRule& p, GtCall& out,
+                                       uint64_t& qual) {
     uint64_t L[10], S[10];
     if (p.ploidy == 2u) {
 #pragma unroll
@@ -71,7 +77,12 @@ __device__ __forceinline__ bool gt_snv(const uint32_t (&c)[4], uint32_t r, const
                 const uint32_t g = k * (k + 1u) / 2u + j;
                 uint64_t l = 0;
 #pragma unroll
-                for (uint32_t i = 0; i < 4u; i++) l += (uint64_t)c[i] * (j == k ? (i == j ? p.M : p.E) : (i == j || i == k ? p.H : p.E));
+                for (uint32_t i = 0; i < 4u; i++) {
+                    l += (uint64_t)c[i] * (j == k ? (i == j ? p.M : p.E) : (i == j || i == k ? p.H : p.E));
+                    if constexpr (kWeighted) {
+                        if (i != j && i != k) l += 1000ull * qs[i];
+                    }
+                }
                 L[g] = l;
                 S[g] = l + (uint64_t)p.hp * ((j != r ? 1u : 0u) + (k != j && k != r ? 1u : 0u));
             }
@@ -87,10 +98,13 @@ __device__ __forceinline__ bool gt_snv(const uint32_t (&c)[4], uint32_t r, const
         return !(out.a == r && out.b == r);
     }
     const uint64_t all = (uint64_t)c[0] + c[1] + c[2] + c[3];
+    uint64_t qall = 0;
+    if constexpr (kWeighted) qall = (uint64_t)qs[0] + qs[1] + qs[2] + qs[3];
 #pragma unroll
     for (uint32_t g = 0; g < 10u; g++) {
         if (g < 4u) {
             L[g] = (uint64_t)c[g] * p.M + (all - c[g]) * p.E;
+            if constexpr (kWeighted) L[g] += 1000ull * (qall - qs[g]);
             S[g] = L[g] + (g != r ? p.hp : 0u);
         } else {
             L[g] = S[g] = 0;
@@ -197,7 +211,18 @@ __device__ __forceinline__ bool gt_row_call(const uint32_t (&c)[6], uint32_t let
     if (d < p.min_depth) return false;
     const uint32_t acgt[4] = {c[0], c[1], c[2], c[3]};
     uint64_t qual;
-    const bool variant = gt_snv(acgt, letter, p, out, qual);
+    const bool variant = gt_snv<false>(acgt, acgt, letter, p, out, qual);
+    return variant && qual >= p.min_qual;
+}
+
+// the same rule with the row's quality sums qc (the row of the quality accumulator as the read-out gives it)
+__device__ __forceinline__ bool gtw_row_call(const uint32_t (&c)[6], const uint32_t (&qc)[6], uint32_t letter, const GtRule& p, GtCall& out) {
+    if (letter >= 4u) return false;
+    const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4];
+    if (d < p.min_depth) return false;
+    const uint32_t acgt[4] = {c[0], c[1], c[2], c[3]}, qs[4] = {qc[0], qc[1], qc[2], qc[3]};
+    uint64_t qual;
+    const bool variant = gt_snv<true>(acgt, qs, letter, p, out, qual);
     return variant && qual >= p.min_qual;
 }
 
@@ -275,6 +300,100 @@ __global__ void __launch_bounds__(256) k_gt_emit(const int32_t* __restrict__ dif
         pos[o] = base + at;
 #pragma unroll
         for (uint32_t k = 0; k < 6u; k++) counts[o * 6u + k] = c[k];
+        gt_store(gts + o, call, rule.ploidy, s.code[at]);
+    }
+}
+
+// ---- the weighted read-out (-wq) ----------------------------------------------------------------------------------
+// The two passes again with the quality accumulator beside the counts: its tile is staged the same way (its own diff and tile sums,
+// the same text), so a row's quality sums are its cnt row with match on top of the column of the text's letter.
+
+struct GtwAcc {
+    const int32_t* diff;
+    const uint32_t* cnt;
+    const uint32_t* tile;
+};
+
+__device__ __forceinline__ bool gtw_tile_selected(const GtwAcc& a, const GtwAcc& q, uint64_t base, uint32_t at, uint64_t lo, uint64_t hi,
+                                                  const GtTile& s, const GtTile& sq, const GtRule& p, uint32_t (&c)[6], uint32_t (&qc)[6],
+                                                  GtCall& call) {
+    const uint64_t x = base + at;
+    if (x < lo || x >= hi) return false;
+    gt_row(a.cnt, x, s.code[at], s.match[at], c);
+    gt_row(q.cnt, x, s.code[at], sq.match[at], qc);
+    return gtw_row_call(c, qc, s.code[at], p, call);
+}
+
+__global__ void __launch_bounds__(256) k_gtw_count(GtwAcc a, GtwAcc q, const TextPlanes* __restrict__ tpl, uint64_t tile0, uint64_t first,
+                                                   uint64_t count, GtRule rule, uint64_t* __restrict__ sel) {
+    __shared__ GtTile s, sq;
+    const uint64_t t = tile0 + blockIdx.x, base = t * kPileTile, end = first + count;  // (end <= n)
+    gt_tile_stage(a.diff, a.tile, tpl, t, end, s);
+    gt_tile_stage(q.diff, q.tile, tpl, t, end, sq);
+    const uint64_t lo = base > first ? base : first, hi = base + kPileTile < end ? base + kPileTile : end;
+    uint32_t mine = 0;
+    for (uint32_t j = 0; j < kPileTile / 256u; j++) {
+        uint32_t c[6], qc[6];
+        GtCall call;
+        mine += gtw_tile_selected(a, q, base, j * 256u + threadIdx.x, lo, hi, s, sq, rule, c, qc, call) ? 1u : 0u;
+    }
+#pragma unroll
+    for (uint32_t d = 32; d >= 1u; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    if ((threadIdx.x & 63u) == 0u) s.wsum[threadIdx.x >> 6] = mine;  // (gt_tile_stage ended with a barrier: wsum is free)
+    __syncthreads();
+    if (threadIdx.x == 0) sel[blockIdx.x] = s.wsum[0] + s.wsum[1] + s.wsum[2] + s.wsum[3];
+}
+
+// as k_gt_emit; a selected row also writes its four quality sums A C G T
+__global__ void __launch_bounds__(256) k_gtw_emit(GtwAcc a, GtwAcc q, const TextPlanes* __restrict__ tpl, uint64_t tile0, uint64_t first,
+                                                  uint64_t count, GtRule rule, const uint64_t* __restrict__ sel, uint64_t capacity,
+                                                  uint64_t* __restrict__ pos, uint32_t* __restrict__ counts,
+                                                  slamem_genotype* __restrict__ gts, uint32_t* __restrict__ qsums) {
+    __shared__ GtTile s, sq;
+    constexpr uint32_t per = kPileTile / 256u;
+    __shared__ uint32_t wcnt[per * 4u];
+    const uint64_t out0 = sel[blockIdx.x];
+    if (sel[blockIdx.x + 1] == out0 || out0 >= capacity) return;  // (the whole workgroup: nothing selected, or no room left)
+    const uint64_t t = tile0 + blockIdx.x, base = t * kPileTile, end = first + count;  // (end <= n)
+    gt_tile_stage(a.diff, a.tile, tpl, t, end, s);
+    gt_tile_stage(q.diff, q.tile, tpl, t, end, sq);
+    const uint64_t lo = base > first ? base : first, hi = base + kPileTile < end ? base + kPileTile : end;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // (the output pointers live in vector registers: the kernel is at the limit of the scalar ones, and a store's address ends in a
+    // vector register anyway)
+    asm volatile("" : "+v"(qsums), "+v"(counts), "+v"(gts));
+    uint32_t chosen = 0, below[per];
+#pragma unroll
+    for (uint32_t j = 0; j < per; j++) {
+        uint32_t c[6], qc[6];
+        GtCall call;
+        const bool on = gtw_tile_selected(a, q, base, j * 256u + threadIdx.x, lo, hi, s, sq, rule, c, qc, call);
+        chosen |= (on ? 1u : 0u) << j;
+        const unsigned long long b = __ballot(on);
+        below[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0u) wcnt[j * 4u + wave] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    uint32_t run = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < per; j++) {
+        uint32_t mine = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; w++) {
+            if (w == wave) mine = run;
+            run += wcnt[j * 4u + w];
+        }
+        const uint64_t o = out0 + mine + below[j];
+        if (!((chosen >> j) & 1u) || o >= capacity) continue;
+        const uint32_t at = j * 256u + threadIdx.x;
+        uint32_t c[6], qc[6];
+        GtCall call;
+        (void)gtw_tile_selected(a, q, base, at, lo, hi, s, sq, rule, c, qc, call);  // (it is selected: the pass above said so)
+        pos[o] = base + at;
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) counts[o * 6u + k] = c[k];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) qsums[o * 4u + k] = qc[k];
         gt_store(gts + o, call, rule.ploidy, s.code[at]);
     }
 }
@@ -393,6 +512,88 @@ int slamem_pileup_genotypes_host(slamem_pileup* pile, uint64_t first, uint64_t c
     hipError_t e = hipSuccess;
     if (got) e = hipMemcpy(pos, pd, got * 8, hipMemcpyDeviceToHost);
     if (got && e == hipSuccess) e = hipMemcpy(counts, cd, got * 24, hipMemcpyDeviceToHost);
+    if (got && e == hipSuccess) e = hipMemcpy(gts, gd, got * sizeof(slamem_genotype), hipMemcpyDeviceToHost);
+    if (rc == SLAMEM_OK && e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
+    return rc;
+}
+
+int slamem_pileup_genotypes_weighted_device(slamem_pileup* pile, uint64_t first, uint64_t count, const slamem_gt_params* params,
+                                            uint64_t capacity, uint64_t* pos_dev, uint32_t* counts_dev, slamem_genotype* gts_dev,
+                                            uint32_t* qsums_dev, uint64_t* total_out, void* stream) {
+    if (!pile || !params || !total_out || (capacity && (!pos_dev || !counts_dev || !gts_dev || !qsums_dev))) {
+        set_error("slamem_pileup_genotypes_weighted_device: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    *total_out = 0;
+    GtRule rule;
+    SLAMEM_TRY(gt_check_range("slamem_pileup_genotypes_weighted_device", pile, first, count));
+    SLAMEM_TRY(gt_check("slamem_pileup_genotypes_weighted_device", params, rule));
+    if (!pile->qual) {
+        set_error("slamem_pileup_genotypes_weighted_device: the quality sums of this accumulator are not enabled (slamem_pileup_enable_quals)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (count == 0) return SLAMEM_OK;
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t end = first + count, tiles = (end + kPileTile - 1) / kPileTile, tile0 = first / kPileTile, mine = tiles - tile0;
+    SLAMEM_TRY(pile_tile_prefix(pile, end, st));
+    SLAMEM_TRY(pile_tile_prefix(pile->qual, end, st));
+    const TextPlanes* tpl = pile->idx->view.tpl;
+    const GtwAcc a{pile->diff, pile->cnt, pile->tile}, q{pile->qual->diff, pile->qual->cnt, pile->qual->tile};
+    hipLaunchKernelGGL(k_gtw_count, dim3((unsigned)mine), dim3(256), 0, st, a, q, tpl, tile0, first, count, rule, pile->sel);
+    SLAMEM_HIP(hipGetLastError());
+    SLAMEM_TRY(pile_scan_counts(pile->sel, mine, st));  // (mine + 1 <= n / kPileTile + 2 words)
+    if (capacity) {  // rows behind `capacity` are dropped on the device, so the pass may run before the total is known
+        hipLaunchKernelGGL(k_gtw_emit, dim3((unsigned)mine), dim3(256), 0, st, a, q, tpl, tile0, first, count, rule,
+                           (const uint64_t*)pile->sel, capacity, pos_dev, counts_dev, gts_dev, qsums_dev);
+        SLAMEM_HIP(hipGetLastError());
+    }
+    uint64_t total = 0;  // the call's one host round trip
+    SLAMEM_HIP(hipMemcpyAsync(&total, pile->sel + mine, 8, hipMemcpyDeviceToHost, st));
+    SLAMEM_HIP(hipStreamSynchronize(st));
+    *total_out = total;
+    if (total > capacity) {
+        set_error("slamem_pileup_genotypes_weighted_device: %llu rows are selected, the buffers hold %llu", (unsigned long long)total,
+                  (unsigned long long)capacity);
+        return SLAMEM_ERR_CAPACITY;
+    }
+    return SLAMEM_OK;
+}
+
+int slamem_pileup_genotypes_weighted_host(slamem_pileup* pile, uint64_t first, uint64_t count, const slamem_gt_params* params,
+                                          uint64_t capacity, uint64_t* pos, uint32_t* counts, slamem_genotype* gts, uint32_t* qsums,
+                                          uint64_t* total_out) {
+    if (!pile || !params || !total_out || (capacity && (!pos || !counts || !gts || !qsums))) {
+        set_error("slamem_pileup_genotypes_weighted_host: null argument");
+        return SLAMEM_ERR_ARG;
+    }
+    *total_out = 0;
+    GtRule rule;
+    SLAMEM_TRY(gt_check_range("slamem_pileup_genotypes_weighted_host", pile, first, count));
+    SLAMEM_TRY(gt_check("slamem_pileup_genotypes_weighted_host", params, rule));
+    if (!pile->qual) {
+        set_error("slamem_pileup_genotypes_weighted_host: the quality sums of this accumulator are not enabled (slamem_pileup_enable_quals)");
+        return SLAMEM_ERR_ARG;
+    }
+    SLAMEM_HIP(hipSetDevice(pile->device));
+    SLAMEM_HIP(hipDeviceSynchronize());  // (the adds of every stream so far are in the tables that are read)
+    const uint64_t room = capacity < count ? capacity : count;  // (a range selects at most its rows)
+    // per row of room: the position (8 bytes), the counters (24), the quality sums (16), the genotype (56), in this order
+    DevBuf<char> d;
+    if (room) SLAMEM_TRY(d.reserve(room * (48 + sizeof(slamem_genotype))));
+    char* b = d.get();
+    uint64_t* pd = reinterpret_cast<uint64_t*>(b);
+    uint32_t* cd = reinterpret_cast<uint32_t*>(b + room * 8);
+    uint32_t* qd = reinterpret_cast<uint32_t*>(b + room * 32);
+    slamem_genotype* gd = reinterpret_cast<slamem_genotype*>(b + room * 48);
+    const int rc = slamem_pileup_genotypes_weighted_device(pile, first, count, params, room, pd, cd, gd, qd, total_out, nullptr);
+    if (rc != SLAMEM_OK && rc != SLAMEM_ERR_CAPACITY) return rc;
+    // (the rows that fitted go back with SLAMEM_ERR_CAPACITY too; the call's code comes before a failed copy's)
+    const uint64_t got = *total_out < room ? *total_out : room;
+    hipError_t e = hipSuccess;
+    if (got) e = hipMemcpy(pos, pd, got * 8, hipMemcpyDeviceToHost);
+    if (got && e == hipSuccess) e = hipMemcpy(counts, cd, got * 24, hipMemcpyDeviceToHost);
+    if (got && e == hipSuccess) e = hipMemcpy(qsums, qd, got * 16, hipMemcpyDeviceToHost);
     if (got && e == hipSuccess) e = hipMemcpy(gts, gd, got * sizeof(slamem_genotype), hipMemcpyDeviceToHost);
     if (rc == SLAMEM_OK && e != hipSuccess) return hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
     return rc;

@@ -99,33 +99,6 @@ __device__ __forceinline__ void pile_eq(const PileAcc& a, const PileAcc& f, bool
     }
 }
 
-// ---- the low-quality mask -----------------------------------------------------------------------------------
-// bit off + i of `words` belongs to letter i of the read as given; every load below takes a word that holds a bit of the read
-struct PileLow {
-    const uint64_t* words;
-    uint64_t off, len;
-    bool rev;
-};
-
-// bits [at, at + c) of the mask, c in 1 .. 64, all of them letters of one read: bit i of the result is bit at + i.  The window
-// comes from two neighbouring words (a funnel shift); the second one is loaded only when the window reaches into it, so that
-// it holds bit at + c - 1 -- a letter of the read, never a word behind the mask's last.
-__device__ __forceinline__ uint64_t lowq_window(const uint64_t* __restrict__ words, uint64_t at, uint32_t c) {
-    const uint32_t s = (uint32_t)(at & 63u);
-    uint64_t w = words[at >> 6] >> s;
-    if (s + c > 64u) w |= words[(at >> 6) + 1u] << (64u - s);  // (s > 0 here)
-    return c < 64u ? w & ((1ull << c) - 1ull) : w;
-}
-
-// the mask over letters [q, q + c) of the scanned strand, c in 1 .. 64: bit i belongs to letter q + i.  On strand 2 that is the
-// given letter len - 1 - q - i: the window over the mirrored range, bit-reversed.  Letters behind the read's end have no bit.
-__device__ __forceinline__ uint64_t lowq_letters(const PileLow& m, uint64_t q, uint32_t c) {
-    if (q >= m.len) return 0ull;
-    const uint32_t cv = m.len - q < c ? (uint32_t)(m.len - q) : c;
-    if (!m.rev) return lowq_window(m.words, m.off + q, cv);
-    return __brevll(lowq_window(m.words, m.off + (m.len - q - cv), cv)) >> (64u - cv);
-}
-
 // an `=` run over rows [p, p + k) that shows letters [q, q + k) of the scanned strand: as pile_eq, with the letters' mask bits
 // ORed into the text's, a text word (up to 64 rows) at a time.  A stretch between two excluded bits gets its pair of atomics;
 // ctz finds the stretches' ends, and one that reaches the chunk's end stays open into the next chunk -- a run without an
@@ -189,18 +162,6 @@ __device__ __forceinline__ void pile_op(const PileAcc& a, const PileAcc& f, bool
     } else if (code == kOpI) {
         if (k && p < a.n) pile_cnt<kStrands>(a, f, two, p * 6u + 5u);
     }
-}
-
-template <bool kMasked>
-__device__ __forceinline__ PileLow pile_low(const PileBatch& b, const PileRead& rd, const uint64_t* lowq) {
-    PileLow m = {nullptr, 0, 0, false};
-    if constexpr (kMasked) {
-        m.words = lowq;
-        m.off = (uint64_t)(rd.rec - b.queries);
-        m.len = rd.len;
-        m.rev = rd.rev;
-    }
-    return m;
 }
 
 // a lane per read: its segments of up to kPileLaneOps operations
@@ -622,8 +583,16 @@ int pile_tile_prefix(slamem_pileup* pile, uint64_t end, hipStream_t stream) {
 
 int pile_refuse_child(const slamem_pileup* pile, const char* fn) {
     if (!pile->child) return SLAMEM_OK;
-    set_error("%s: this is the forward accumulator of another (slamem_pileup_forward): it is read, and counts may be added to it, but "
-              "its owner adds the reads, enables and frees", fn);
+    set_error("%s: this is the %s accumulator of another (%s): it is read, and counts may be added to it, but "
+              "its owner adds the reads, enables and frees", fn, pile->child_qual ? "quality" : "forward",
+              pile->child_qual ? "slamem_pileup_quality" : "slamem_pileup_forward");
+    return SLAMEM_ERR_ARG;
+}
+
+int pile_refuse_quals(const slamem_pileup* pile, const char* fn) {
+    if (!pile->qual) return SLAMEM_OK;
+    set_error("%s: this accumulator keeps quality sums (slamem_pileup_enable_quals), which an add without quality bytes would leave "
+              "behind its counts: add the reads with slamem_pileup_add_quals_device", fn);
     return SLAMEM_ERR_ARG;
 }
 
@@ -637,8 +606,10 @@ int pile_scan_counts(uint64_t* sel, uint64_t tiles, hipStream_t stream) {
 
 extern "C" {
 
-// the accumulator of slamem_pileup_create, and the forward one of slamem_pileup_enable_strands (`fn` names the caller in messages)
-static int pile_new(const slamem_index* idx, const char* fn, bool child, slamem_pileup** out) {
+// the accumulator of slamem_pileup_create (role 0), the forward one of slamem_pileup_enable_strands (1) and the quality one of
+// slamem_pileup_enable_quals (2); `fn` names the caller in messages
+static int pile_new(const slamem_index* idx, const char* fn, int role, slamem_pileup** out) {
+    const bool child = role != 0;
     SLAMEM_HIP(hipSetDevice(idx->device));
     const uint64_t n = idx->hdr.n;
     const uint64_t tiles = n / kPileTile + 2;
@@ -647,7 +618,7 @@ static int pile_new(const slamem_index* idx, const char* fn, bool child, slamem_
     SLAMEM_HIP(hipMemGetInfo(&free_b, &total_b));
     if (need > free_b) {
         set_error("%s: the %saccumulator of a text of %llu letters takes %llu bytes (28 per letter), %llu are free on "
-                  "device %d", fn, child ? "forward " : "", (unsigned long long)n, (unsigned long long)need, (unsigned long long)free_b,
+                  "device %d", fn, role == 1 ? "forward " : role == 2 ? "quality " : "", (unsigned long long)n, (unsigned long long)need, (unsigned long long)free_b,
                   idx->device);
         return SLAMEM_ERR_NOMEM;
     }
@@ -655,7 +626,7 @@ static int pile_new(const slamem_index* idx, const char* fn, bool child, slamem_
     if (!p) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     p->idx = idx; p->device = idx->device; p->n = (uint32_t)n;
     p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr; p->cons = nullptr; p->depth = nullptr; p->dd = nullptr;
-    p->fwd = nullptr; p->child = false; p->used.store(false, std::memory_order_relaxed);
+    p->fwd = nullptr; p->qual = nullptr; p->child = false; p->child_qual = false; p->used.store(false, std::memory_order_relaxed);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->diff), (n + 1) * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->cnt), n * 24 + 16);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->tile), tiles * 4);
@@ -668,6 +639,7 @@ static int pile_new(const slamem_index* idx, const char* fn, bool child, slamem_
         return hip_fail(e, fn, __FILE__, __LINE__);
     }
     p->child = child;
+    p->child_qual = role == 2;
     *out = p;
     return SLAMEM_OK;
 }
@@ -680,7 +652,7 @@ int slamem_pileup_create(const slamem_index* idx, slamem_pileup** out) {
                   "one built without the seed sections)");
         return SLAMEM_ERR_ARG;
     }
-    return pile_new(idx, "slamem_pileup_create", false, out);
+    return pile_new(idx, "slamem_pileup_create", 0, out);
 }
 
 int slamem_pileup_enable_strands(slamem_pileup* pile) {
@@ -692,7 +664,7 @@ int slamem_pileup_enable_strands(slamem_pileup* pile) {
                   "(just created, or after slamem_pileup_reset)");
         return SLAMEM_ERR_ARG;
     }
-    return pile_new(pile->idx, "slamem_pileup_enable_strands", true, &pile->fwd);
+    return pile_new(pile->idx, "slamem_pileup_enable_strands", 1, &pile->fwd);
 }
 
 int slamem_pileup_forward(slamem_pileup* pile, slamem_pileup** out) {
@@ -705,9 +677,32 @@ int slamem_pileup_forward(slamem_pileup* pile, slamem_pileup** out) {
     return SLAMEM_OK;
 }
 
+int slamem_pileup_enable_quals(slamem_pileup* pile) {
+    if (!pile) { set_error("slamem_pileup_enable_quals: null argument"); return SLAMEM_ERR_ARG; }
+    SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_enable_quals"));
+    if (pile->qual) return SLAMEM_OK;
+    if (pile->used.load(std::memory_order_relaxed)) {
+        set_error("slamem_pileup_enable_quals: something was added to this accumulator already; quality sums start on an empty one "
+                  "(just created, or after slamem_pileup_reset)");
+        return SLAMEM_ERR_ARG;
+    }
+    return pile_new(pile->idx, "slamem_pileup_enable_quals", 2, &pile->qual);
+}
+
+int slamem_pileup_quality(slamem_pileup* pile, slamem_pileup** out) {
+    if (!pile || !out) { set_error("slamem_pileup_quality: null argument"); return SLAMEM_ERR_ARG; }
+    *out = pile->qual;
+    if (!pile->qual) {
+        set_error("slamem_pileup_quality: the quality sums of this accumulator are not enabled (slamem_pileup_enable_quals)");
+        return SLAMEM_ERR_ARG;
+    }
+    return SLAMEM_OK;
+}
+
 static void pile_release(slamem_pileup* p) {
     (void)hipSetDevice(p->device);
     if (p->fwd) { pile_release(p->fwd); p->fwd = nullptr; }
+    if (p->qual) { pile_release(p->qual); p->qual = nullptr; }
     if (p->diff) (void)hipFree(p->diff);
     if (p->cnt) (void)hipFree(p->cnt);
     if (p->tile) (void)hipFree(p->tile);
@@ -734,13 +729,15 @@ int slamem_pileup_reset(slamem_pileup* p) {
     SLAMEM_HIP(hipMemset(p->cnt, 0, (uint64_t)p->n * 24));
     if (p->ev) { const int rc = events_reset(p); if (rc != SLAMEM_OK) return rc; }
     if (p->dd) { const int rc = dedup_reset(p); if (rc != SLAMEM_OK) return rc; }
-    if (p->fwd) {  // (a forward accumulator has neither events nor a filter)
-        SLAMEM_HIP(hipMemset(p->fwd->diff, 0, ((uint64_t)p->n + 1) * 4));
-        SLAMEM_HIP(hipMemset(p->fwd->cnt, 0, (uint64_t)p->n * 24));
+    for (slamem_pileup* c : {p->fwd, p->qual}) {  // (a forward or a quality accumulator has neither events nor a filter)
+        if (!c) continue;
+        SLAMEM_HIP(hipMemset(c->diff, 0, ((uint64_t)p->n + 1) * 4));
+        SLAMEM_HIP(hipMemset(c->cnt, 0, (uint64_t)p->n * 24));
     }
     SLAMEM_HIP(hipDeviceSynchronize());
     p->used.store(false, std::memory_order_relaxed);
     if (p->fwd) p->fwd->used.store(false, std::memory_order_relaxed);
+    if (p->qual) p->qual->used.store(false, std::memory_order_relaxed);
     return SLAMEM_OK;
 }
 
@@ -752,6 +749,7 @@ int slamem_pileup_add_device(slamem_pileup* pile, const void* queries_dev, const
         return SLAMEM_ERR_ARG;
     }
     SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_add_device"));
+    SLAMEM_TRY(pile_refuse_quals(pile, "slamem_pileup_add_device"));
     if (min_mapq > 60u) { set_error("slamem_pileup_add_device: the minimum mapping quality is 0 to 60"); return SLAMEM_ERR_ARG; }
     SLAMEM_HIP(hipSetDevice(pile->device));
     return pileup_add(pile, queries_dev, offsets_dev, num_queries, segs_dev, read_offsets_dev, ops_dev, op_offsets_dev, reads_dev,
@@ -767,6 +765,7 @@ int slamem_pileup_add_masked_device(slamem_pileup* pile, const void* queries_dev
         return SLAMEM_ERR_ARG;
     }
     SLAMEM_TRY(pile_refuse_child(pile, "slamem_pileup_add_masked_device"));
+    SLAMEM_TRY(pile_refuse_quals(pile, "slamem_pileup_add_masked_device"));
     if (min_mapq > 60u) { set_error("slamem_pileup_add_masked_device: the minimum mapping quality is 0 to 60"); return SLAMEM_ERR_ARG; }
     SLAMEM_HIP(hipSetDevice(pile->device));
     return pileup_add_masked(pile, queries_dev, offsets_dev, num_queries, segs_dev, read_offsets_dev, ops_dev, op_offsets_dev,

@@ -1,7 +1,7 @@
 // pile_shared.h -- what pile_filter.hip (-pile and -sites), event_filter.hip (the indel events of -vcf,
 // DESIGN.md 4.18), cons_filter.hip (the consensus of -cons), depth_filter.hip (the runs of -depth) and
-// dedup_filter.hip (the duplicate filter of -dedup) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
-// segments (letters of the scanned strand, the steps of an operation), and the two entry points of the read-out's scratch that
+// dedup_filter.hip (the duplicate filter of -dedup) and qual_filter.hip (the quality sums of -wq) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
+// segments (letters of the scanned strand, the steps of an operation, the low-quality mask's window), and the two entry points of the read-out's scratch that
 // the event side borrows.
 #pragma once
 #include "common.h"
@@ -30,7 +30,9 @@ struct slamem_pileup {
     slamem::DepthScratch* depth;  // nullptr: no depth runs were read yet
     slamem::DdTable* dd;  // nullptr: the duplicate filter is not enabled
     slamem_pileup* fwd;   // nullptr: strand counts are not enabled; else the forward accumulator, owned
-    bool child;           // this is the forward accumulator of another: no adds of reads, nothing to enable, freed by its owner
+    slamem_pileup* qual;  // nullptr: quality sums are not enabled; else the quality accumulator, owned
+    bool child;           // this is the forward or the quality accumulator of another: no adds of reads, nothing to enable, freed by its owner
+    bool child_qual;      // child: which of the two
     std::atomic<bool> used;  // something was added since creation or the last reset
 };
 
@@ -93,6 +95,45 @@ __device__ __forceinline__ bool pile_contributes(const PileBatch& b, uint64_t r,
     out.len = b.offsets[r + 1] - o;
     out.rev = m.strand == 2u;
     return true;
+}
+
+// ---- the low-quality mask -----------------------------------------------------------------------------------
+// bit off + i of `words` belongs to letter i of the read as given; every load below takes a word that holds a bit of the read
+struct PileLow {
+    const uint64_t* words;
+    uint64_t off, len;
+    bool rev;
+};
+
+// bits [at, at + c) of the mask, c in 1 .. 64, all of them letters of one read: bit i of the result is bit at + i.  The window
+// comes from two neighbouring words (a funnel shift); the second one is loaded only when the window reaches into it, so that
+// it holds bit at + c - 1 -- a letter of the read, never a word behind the mask's last.
+__device__ __forceinline__ uint64_t lowq_window(const uint64_t* __restrict__ words, uint64_t at, uint32_t c) {
+    const uint32_t s = (uint32_t)(at & 63u);
+    uint64_t w = words[at >> 6] >> s;
+    if (s + c > 64u) w |= words[(at >> 6) + 1u] << (64u - s);  // (s > 0 here)
+    return c < 64u ? w & ((1ull << c) - 1ull) : w;
+}
+
+// the mask over letters [q, q + c) of the scanned strand, c in 1 .. 64: bit i belongs to letter q + i.  On strand 2 that is the
+// given letter len - 1 - q - i: the window over the mirrored range, bit-reversed.  Letters behind the read's end have no bit.
+__device__ __forceinline__ uint64_t lowq_letters(const PileLow& m, uint64_t q, uint32_t c) {
+    if (q >= m.len) return 0ull;
+    const uint32_t cv = m.len - q < c ? (uint32_t)(m.len - q) : c;
+    if (!m.rev) return lowq_window(m.words, m.off + q, cv);
+    return __brevll(lowq_window(m.words, m.off + (m.len - q - cv), cv)) >> (64u - cv);
+}
+
+template <bool kMasked>
+__device__ __forceinline__ PileLow pile_low(const PileBatch& b, const PileRead& rd, const uint64_t* lowq) {
+    PileLow m = {nullptr, 0, 0, false};
+    if constexpr (kMasked) {
+        m.words = lowq;
+        m.off = (uint64_t)(rd.rec - b.queries);
+        m.len = rd.len;
+        m.rev = rd.rev;
+    }
+    return m;
 }
 
 __device__ __forceinline__ uint64_t wave_scan_inclusive(uint64_t v, uint32_t lane) {

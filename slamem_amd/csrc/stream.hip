@@ -75,6 +75,9 @@ struct Slot {
     // a batch handed in with a low-quality mask (slamem_stream_submit_masked): the words the batch touches --
     // d_lowq[0] is the caller's word offs[0] / 64
     DevBuf<uint64_t> d_lowq;
+    // a batch handed in with its quality bytes (slamem_stream_submit_quals): the bytes of the batch's letters --
+    // d_qual[0] is the caller's byte offs[0]
+    DevBuf<unsigned char> d_qual;
     // The batch's OUTPUTS on the device, sized by the inputs' room and allocated by grow_outputs (prepare stage; download stage on
     // a capacity retry): -mem rows (room for `cap`) and the search's workspace; -ext: a uint32 per row; -aln: segments (room for
     // `cap`: a segment has at least one chain row), operations (room for `ops_cap`) and the operations' offsets per segment.
@@ -119,6 +122,7 @@ struct Slot {
     const uint64_t* other = nullptr;    // packed: per unit, letters that are not A,C,G,T (nullptr: none)
     uint64_t units_hint = 0;            // packed: the batch's units as the caller counted them (0: count here)
     const uint64_t* lowq = nullptr;     // masked: the caller's words, indexed as its letters
+    const uint8_t* quals = nullptr;     // -wq: the caller's quality bytes, indexed as its letters
     // its result
     uint64_t total = 0, ops_total = 0, md_total = 0;
     int rc = SLAMEM_OK;
@@ -154,6 +158,8 @@ struct slamem_stream {
     uint32_t min_mapq = 0;                  // -pile: the least mapping quality that counts
     bool md = false;                        // -sam: every batch also goes through the MD pass (slamem_stream_set_md)
     bool dedup = false;                     // -dedup: every batch is added with the duplicate filter (slamem_stream_set_dedup)
+    bool quals = false;                     // -wq: every batch comes with its quality bytes (slamem_stream_set_quals)
+    uint32_t phred_offset = 33;             // -wq: the Phred offset of those bytes
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     std::unique_ptr<Slot[]> slot;  // nslots of them; they go in teardown(), in front of the HIP streams
@@ -390,6 +396,12 @@ int stage_upload(slamem_stream* s, Slot& sl) {
         if (sl.d_lowq.count() < nw) SLAMEM_TRY(sl.d_lowq.reserve(nw > (sl.cap_chars >> 6) + 2 ? nw : (sl.cap_chars >> 6) + 2));
         SLAMEM_HIP(hipMemcpyAsync(sl.d_lowq.get(), sl.lowq + w0, nw * 8, hipMemcpyHostToDevice, s->st[0]));
     }
+    if (sl.quals) {
+        // the quality bytes of the batch's letters: [base, base + qbytes).  The add gets d_qual - base, so that byte offs[r] + i is
+        // letter i of read r there as it is in the caller's array
+        if (!sl.d_qual.get() || sl.d_qual.count() < qbytes) SLAMEM_TRY(sl.d_qual.reserve((qbytes > sl.cap_chars ? qbytes : sl.cap_chars) + 8));
+        if (qbytes) SLAMEM_HIP(hipMemcpyAsync(sl.d_qual.get(), sl.quals + base, qbytes, hipMemcpyHostToDevice, s->st[0]));
+    }
     sl.all_short = all_records_short(sl);
     SLAMEM_HIP(hipStreamSynchronize(s->st[0]));
     for (int wy = 1; wy < ways; wy++) SLAMEM_HIP(hipStreamSynchronize(s->st_upx[wy - 1]));
@@ -574,12 +586,20 @@ int stage_download(slamem_stream* s, Slot& sl) {
             SLAMEM_TRY(sl.d_keep.reserve((uint64_t)sl.cap_q + 1));
             SLAMEM_TRY(sl.d_dup.reserve((uint64_t)sl.cap_q + 1));
             SLAMEM_TRY(sl.h_dup.reserve((uint64_t)sl.cap_q + 1));
+        }
+        if (s->quals) {  // (the quality pass behind the pile kernels of the same batch)
+            rc = pileup_add_quals(s->pile, device_queries(sl), sl.d_off.get(), sl.nq, sl.d_segs.get(), sl.d_boff.get(), sl.d_ops.get(),
+                                  sl.d_ooff.get(), sl.d_reads.get(), s->min_mapq, lowq, sl.d_qual.get() - sl.offs[0], s->phred_offset,
+                                  s->dedup, sl.d_keep.get(), sl.d_dup.get(), st);
+            if (rc == SLAMEM_OK && s->dedup && sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_dup.get(), sl.d_dup.get(), sl.nq, hipMemcpyDeviceToHost, st));
+        } else if (s->dedup) {
             rc = pileup_add_dedup(s->pile, device_queries(sl), sl.d_off.get(), sl.nq, sl.d_segs.get(), sl.d_boff.get(), sl.d_ops.get(),
                                   sl.d_ooff.get(), sl.d_reads.get(), s->min_mapq, lowq, sl.d_keep.get(), sl.d_dup.get(), st);
             if (rc == SLAMEM_OK && sl.nq) SLAMEM_HIP(hipMemcpyAsync(sl.h_dup.get(), sl.d_dup.get(), sl.nq, hipMemcpyDeviceToHost, st));
-        } else
-        rc = pileup_add_masked(s->pile, device_queries(sl), sl.d_off.get(), sl.nq, sl.d_segs.get(), sl.d_boff.get(), sl.d_ops.get(),
-                               sl.d_ooff.get(), sl.d_reads.get(), s->min_mapq, lowq, st);
+        } else {
+            rc = pileup_add_masked(s->pile, device_queries(sl), sl.d_off.get(), sl.nq, sl.d_segs.get(), sl.d_boff.get(), sl.d_ops.get(),
+                                   sl.d_ooff.get(), sl.d_reads.get(), s->min_mapq, lowq, st);
+        }
         if (rc != SLAMEM_OK) return rc;
     } else {
         SLAMEM_TRY(sl.h_mems.reserve(sl.cap, 16));
@@ -695,6 +715,7 @@ struct Batch {
     const uint64_t* other = nullptr;
     uint64_t units = 0;
     const uint64_t* lowq = nullptr;  // (nullptr: the batch is an unmasked one)
+    const uint8_t* quals = nullptr;  // (nullptr: the batch has no quality bytes)
     const uint64_t* offs = nullptr;
     uint32_t nq = 0, min_len = 0;
 };
@@ -703,6 +724,11 @@ int enqueue(slamem_stream* s, const char* who, const Batch& b) {
     std::unique_lock<std::mutex> lk(s->mu);
     if (s->match_type == 8 && !s->pile) {
         set_error("%s: a stream of match type 8 (-pile) needs slamem_stream_set_pileup first", who);
+        return SLAMEM_ERR_ARG;
+    }
+    if (s->pile && pileup_has_quals(s->pile) && !(s->quals && b.quals)) {
+        set_error("%s: the stream's accumulator keeps quality sums (slamem_pileup_enable_quals), which a batch without quality bytes would "
+                  "leave behind its counts: slamem_stream_set_quals, then slamem_stream_submit_quals", who);
         return SLAMEM_ERR_ARG;
     }
     Slot& sl = s->slot[s->submitted % (uint64_t)s->nslots];
@@ -719,6 +745,7 @@ int enqueue(slamem_stream* s, const char* who, const Batch& b) {
     sl.other = b.other;
     sl.units_hint = b.units;
     sl.lowq = b.lowq;
+    sl.quals = b.quals;
     sl.offs = b.offs;
     sl.nq = b.nq;
     sl.min_len = b.min_len;
@@ -1052,6 +1079,21 @@ int slamem_stream_set_dedup(slamem_stream* s, int on) {
     return SLAMEM_OK;
 }
 
+int slamem_stream_set_quals(slamem_stream* s, uint32_t phred_offset) {
+    if (!s) { set_error("slamem_stream_set_quals: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (has_batches(s, "slamem_stream_set_quals", "switch the quality sums on")) return SLAMEM_ERR_ARG;
+    if (!s->pile || !pileup_has_quals(s->pile)) {
+        set_error("slamem_stream_set_quals: the stream needs an accumulator whose quality sums are enabled (slamem_pileup_enable_quals, "
+                  "then slamem_stream_set_pileup)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (phred_offset > 255u) { set_error("slamem_stream_set_quals: the Phred offset is 0 to 255, not %u", phred_offset); return SLAMEM_ERR_ARG; }
+    s->quals = true;
+    s->phred_offset = phred_offset;
+    return SLAMEM_OK;
+}
+
 int slamem_stream_dups(slamem_stream* s, const uint8_t** flags_out) {
     if (!s || !flags_out) { set_error("slamem_stream_dups: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
@@ -1093,6 +1135,20 @@ int slamem_stream_submit_masked(slamem_stream* s, const char* queries, const uin
     Batch b;
     b.chars = queries; b.lowq = lowq; b.offs = offsets; b.nq = num_queries; b.min_len = min_len;
     return enqueue(s, "slamem_stream_submit_masked", b);
+}
+
+int slamem_stream_submit_quals(slamem_stream* s, const char* queries, const uint8_t* quals, const uint64_t* lowq, const uint64_t* offsets,
+                               uint32_t num_queries, uint32_t min_len) {
+    if (!s || !offsets || (num_queries && (!queries || !quals))) { set_error("slamem_stream_submit_quals: null argument"); return SLAMEM_ERR_ARG; }
+    if (min_len < 1) { set_error("slamem_stream_submit_quals: minimum MEM length must be >= 1"); return SLAMEM_ERR_ARG; }
+    if (!s->quals) {  // (set before the first batch, and never taken back)
+        set_error("slamem_stream_submit_quals: the stream's quality sums are not switched on (slamem_stream_set_quals)");
+        return SLAMEM_ERR_ARG;
+    }
+    static const uint8_t none = 0;  // (a batch without reads has no bytes; the pointer only says that the batch came this way)
+    Batch b;
+    b.chars = queries; b.lowq = lowq; b.quals = quals ? quals : &none; b.offs = offsets; b.nq = num_queries; b.min_len = min_len;
+    return enqueue(s, "slamem_stream_submit_quals", b);
 }
 
 int slamem_stream_submit_packed(slamem_stream* s, const void* planes, const uint64_t* other, const uint64_t* offsets, uint32_t num_queries,

@@ -47,6 +47,9 @@ def gt_costs(q: int) -> tuple[int, int, int]:
     return tuple(int(math.floor(-10000.0 * math.log10(x) + 0.5)) for x in (hom, het, third))
 
 
+WQ_COSTS = (0, 3010, 4771)  # -wq: M, H = round(10000 log10 2), E = round(10000 log10 3); a letter's own quality comes on top of E
+
+
 def fisher_strand(t) -> float:
     """slamem_fisher_strand: FS of -sb, the Phred-scaled two-sided Fisher exact test of the strand table
     t = (reference forward, reference reverse, alternative forward, alternative reverse), four counts below 2^32.  Host
@@ -69,8 +72,8 @@ def _strand_table(t):
     return (C.c_uint32 * 4)(*t)
 
 
-def _gt_params(ploidy, err_q, het_q, min_depth, min_qual) -> capi.GtParams:
-    M, H, E = gt_costs(err_q)
+def _gt_params(ploidy, err_q, het_q, min_depth, min_qual, costs=None) -> capi.GtParams:
+    M, H, E = gt_costs(err_q) if costs is None else (int(v) for v in costs)
     if not 0 <= int(het_q) <= 999:
         raise ValueError("het_q is 0 to 999 Phred")
     vals = (int(ploidy), M, H, E, 1000 * int(het_q), int(min_depth), int(min_qual))
@@ -388,7 +391,7 @@ class Index:
             break
         if pile is not None:
             pile[0]._add_device(qd, od, num, segs, boff, ops, ooff, recs, pile[1], pile[2] if len(pile) > 2 else None,
-                                bool(len(pile) > 3 and pile[3]))
+                                bool(len(pile) > 3 and pile[3]), pile[4] if len(pile) > 4 else None)
             return _map_records(recs[: num * 12].cpu().numpy())
         nseg, nops = int(totals[1]), int(totals[2])
         extra = ()
@@ -484,14 +487,17 @@ class Pileup:
     unclipped 5' position): the first in the order of the adds, then of the batch.  With it the table depends on the order of the
     adds: addition no longer commutes across them.  strands=True (-sb): the accumulator owns a second one, `forward`,
     which receives exactly what the reads of strand 1 contribute, in the same kernels; 28 more bytes per text letter.  The reverse
-    strand's rows are counts() - forward.counts()."""
+    strand's rows are counts() - forward.counts().  quals=True (-wq): the accumulator owns a second one, `quality`,
+    whose A C G T columns hold the sum of the base qualities of the letters that the same columns of counts() count; every add
+    then needs quals=, and genotypes(weighted=True) scores each letter by its own quality; 28 more bytes per text letter."""
 
     def __init__(self, index: Index, events: bool = False, event_slots: int = 0, dedup: bool = False, dedup_slots: int = 0,
-                 strands: bool = False):
+                 strands: bool = False, quals: bool = False):
         self.index = index
         self._h = C.c_void_p()
-        self._owner = None  # (a forward view: the Pileup that owns the handle)
+        self._owner = None  # (a forward or quality view: the Pileup that owns the handle)
         self.forward = None
+        self.quality = None
         if event_slots and not events:
             raise ValueError("event_slots is the size of the event table: it needs events=True")
         if dedup_slots and not dedup:
@@ -512,6 +518,23 @@ class Pileup:
         self.last_add_ms = 0.0  # device time of the last add's own kernels (the mapping in front of them not counted)
         if strands:
             self.enable_strands()
+        if quals:
+            self.enable_quals()
+
+    def _view(self, h) -> "Pileup":
+        view = Pileup.__new__(Pileup)
+        view.index, view._h, view._owner, view.forward, view.quality, view.dedup, view.last_add_ms = self.index, h, self, None, None, False, 0.0
+        return view
+
+    def enable_quals(self) -> None:
+        """slamem_pileup_enable_quals: from here on `quality` is the accumulator of the quality sums, a Pileup that does not own its
+        handle: counts(), rows_at() and add_counts() are the read-outs with a meaning on it; add, reset and close are its owner's.
+        Only on an empty accumulator (just made, or reset); a second call changes nothing."""
+        capi.check(capi.lib().slamem_pileup_enable_quals(self._h))
+        if self.quality is None:
+            h = C.c_void_p()
+            capi.check(capi.lib().slamem_pileup_quality(self._h, C.byref(h)))
+            self.quality = self._view(h)
 
     def enable_strands(self) -> None:
         """slamem_pileup_enable_strands: from here on `forward` is the accumulator of the strand-1 reads, a Pileup that does not
@@ -521,21 +544,35 @@ class Pileup:
         if self.forward is None:
             h = C.c_void_p()
             capi.check(capi.lib().slamem_pileup_forward(self._h, C.byref(h)))
-            view = Pileup.__new__(Pileup)
-            view.index, view._h, view._owner, view.forward, view.dedup, view.last_add_ms = self.index, h, self, None, False, 0.0
-            self.forward = view
+            self.forward = self._view(h)
 
     def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-            xdrop=None, max_edits=None, min_mapq: int = 0, lowq=None, dedup: bool = False):
+            xdrop=None, max_edits=None, min_mapq: int = 0, lowq=None, dedup: bool = False, quals=None, phred_offset: int = 33):
         """Maps the batch as Index.map_reads does and adds the mappings of the reads with mapq >= min_mapq (0 to 60) to the table,
         on the device: segments and operations are not downloaded.  Returns the read records of map_reads (MAP_DTYPE).  lowq: the
         batch's low-quality mask (DESIGN.md 4.21), a uint64 array of at least (offsets[-1] + 63) // 64 words (numpy, or a tensor on
         the index's device) in which bit offsets[r] + i belongs to letter i of read r as given -- a letter whose bit is set counts
         nowhere under = and X; pack_lowq makes it from quality bytes.  None: every letter counts.  dedup=True (an accumulator made
         with dedup=True): the batch goes through the duplicate filter and the call returns (reads, dup), dup a uint8
-        per read: 0 kept or no candidate, 1 duplicate (not piled), 2 no room in the filter's table (piled)."""
+        per read: 0 kept or no candidate, 1 duplicate (not piled), 2 no room in the filter's table (piled).  quals (an accumulator
+        made with quals=True): the batch's quality bytes, a uint8 array (numpy, or a tensor on the index's device)
+        of at least offsets[-1] bytes in which byte offsets[r] + i belongs to letter i of read r as given, Phred + phred_offset; it
+        works with lowq= and dedup= as they are."""
         if not 0 <= int(min_mapq) <= 60:
             raise ValueError("min_mapq must be in [0, 60]")
+        if quals is not None:
+            need = int(np.asarray(offsets)[-1])
+            if isinstance(quals, torch.Tensor):
+                if quals.dtype != torch.uint8 or quals.device != self.index.device or not quals.is_contiguous():
+                    raise ValueError("quals as a tensor: contiguous uint8 bytes on the index's device")
+            else:
+                quals = np.ascontiguousarray(np.frombuffer(quals, dtype=np.uint8) if isinstance(quals, (bytes, bytearray)) else quals)
+                if quals.dtype != np.uint8:
+                    raise ValueError("quals must be a uint8 array")
+            if quals.shape[0] < need:
+                raise ValueError(f"quals has {quals.shape[0]} bytes, the batch's letters need {need}")
+            if not 0 <= int(phred_offset) <= 255:
+                raise ValueError("phred_offset must be in [0, 255]")
         if lowq is not None:
             need = (int(np.asarray(offsets)[-1]) + 63) // 64
             if isinstance(lowq, torch.Tensor):
@@ -548,12 +585,17 @@ class Pileup:
             if lowq.shape[0] < need:
                 raise ValueError(f"lowq has {lowq.shape[0]} words, the batch's letters need {need}")
         recs = self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, None, True,
-                                    pile=(self, int(min_mapq), lowq, bool(dedup)))
+                                    pile=(self, int(min_mapq), lowq, bool(dedup), None if quals is None else (quals, int(phred_offset))))
         return (recs, self.last_dup) if dedup else recs
 
-    def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq, lowq=None, dedup=False):
-        """dedup: through the duplicate filter; last_dup holds the batch's flags afterwards."""
+    def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq, lowq=None, dedup=False, quals=None):
+        """dedup: through the duplicate filter; last_dup holds the batch's flags afterwards.  quals: (bytes, phred_offset)."""
         dev = self.index.device
+        if quals is not None and not isinstance(quals[0], torch.Tensor):
+            qb = torch.zeros(quals[0].shape[0] + 8, dtype=torch.uint8, device=dev)
+            if quals[0].shape[0]:
+                qb[:quals[0].shape[0]] = torch.from_numpy(quals[0] if quals[0].flags.writeable else quals[0].copy()).to(dev)
+            quals = (qb, quals[1])
         if lowq is not None and not isinstance(lowq, torch.Tensor):
             lowq = torch.from_numpy(lowq.view(np.int64).copy()).to(dev) if lowq.shape[0] else None
         with torch.cuda.device(dev):
@@ -562,6 +604,12 @@ class Pileup:
             if dedup:
                 keep = torch.zeros((num + 1) * 12, dtype=torch.uint8, device=dev)
                 dup = torch.zeros(num + 1, dtype=torch.uint8, device=dev)
+            if quals is not None:
+                rc = capi.lib().slamem_pileup_add_quals_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops),
+                                                               _ptr(ooff), _ptr(recs), int(min_mapq), _ptr(lowq) if lowq is not None else None,
+                                                               _ptr(quals[0]), quals[1], int(bool(dedup)), _ptr(keep) if dedup else None,
+                                                               _ptr(dup) if dedup else None, _stream_handle(dev))
+            elif dedup:
                 rc = capi.lib().slamem_pileup_add_dedup_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops),
                                                                _ptr(ooff), _ptr(recs), int(min_mapq), _ptr(lowq) if lowq is not None else None,
                                                                _ptr(keep), _ptr(dup), _stream_handle(dev))
@@ -693,18 +741,21 @@ class Pileup:
         return out[:m].cpu().numpy().view(np.uint32)
 
     def genotypes(self, ploidy: int = 2, err_q: int = 20, het_q: int = 30, min_depth: int = 4, min_qual: int = 20, first: int = 0,
-                  count=None, capacity=None):
+                  count=None, capacity=None, weighted: bool = False, costs=None):
         """The rows of [first, first + count) whose best genotype is not the reference's, called and compacted on
         the device, as (pos uint64 (m,), counts uint32 (m, 6), gts GENOTYPE_DTYPE (m,)) in ascending position.  A row's ten
         (ploidy 1: four) genotypes are scored from its A C G T counters at a constant error rate of Phred err_q (gt_costs), with
         a prior cost of het_q Phred per non-reference allele; it is selected iff the text's letter is one of A,C,G,T, the depth
         A+C+G+T+D is at least min_depth, the best genotype differs from the reference's and its QUAL is at least min_qual Phred.
         capacity: rows of room for the first attempt (default: one in 64 of the range, at least 4,096); when more are selected
-        the call is made once more with the need it reported."""
+        the call is made once more with the need it reported.  costs: (M, H, E) in the place of gt_costs(err_q).
+        weighted=True (an accumulator made with quals=True): a letter that a genotype does not hold costs E and
+        1000 times its own quality -- E * c[i] + 1000 * quality.counts()[p][i] per column; the costs default to WQ_COSTS, err_q is
+        not looked at, and the call returns (pos, counts, gts, qsums), qsums uint32 (m, 4) the A C G T columns of the quality sums."""
         first = int(first)
         count = self.index.n - first if count is None else int(count)
         dev = self.index.device
-        params = _gt_params(ploidy, err_q, het_q, min_depth, min_qual)
+        params = _gt_params(ploidy, err_q, het_q, min_depth, min_qual, WQ_COSTS if weighted and costs is None else costs)
         cap = max(4096, count // 64) if capacity is None else int(capacity)
         total = C.c_uint64()
         with torch.cuda.device(dev):
@@ -712,15 +763,22 @@ class Pileup:
                 pos = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
                 rows = torch.empty((max(cap, 1), 6), dtype=torch.int32, device=dev)
                 gts = torch.empty(max(cap, 1) * GENOTYPE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-                rc = capi.lib().slamem_pileup_genotypes_device(self._h, first, count, C.byref(params), cap, _ptr(pos), _ptr(rows),
-                                                               _ptr(gts), C.byref(total), _stream_handle(dev))
+                if weighted:
+                    qsums = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
+                    rc = capi.lib().slamem_pileup_genotypes_weighted_device(self._h, first, count, C.byref(params), cap, _ptr(pos),
+                                                                            _ptr(rows), _ptr(gts), _ptr(qsums), C.byref(total),
+                                                                            _stream_handle(dev))
+                else:
+                    rc = capi.lib().slamem_pileup_genotypes_device(self._h, first, count, C.byref(params), cap, _ptr(pos), _ptr(rows),
+                                                                   _ptr(gts), C.byref(total), _stream_handle(dev))
                 if rc != capi.SLAMEM_ERR_CAPACITY or attempt:
                     break
                 cap = int(total.value)
             capi.check(rc)
         m = int(total.value)
-        return (pos[:m].cpu().numpy().view(np.uint64), rows[:m].cpu().numpy().view(np.uint32),
-                gts[:m * GENOTYPE_DTYPE.itemsize].cpu().numpy().view(GENOTYPE_DTYPE).copy())
+        out = (pos[:m].cpu().numpy().view(np.uint64), rows[:m].cpu().numpy().view(np.uint32),
+               gts[:m * GENOTYPE_DTYPE.itemsize].cpu().numpy().view(GENOTYPE_DTYPE).copy())
+        return out + (qsums[:m].cpu().numpy().view(np.uint32),) if weighted else out
 
     def genotype_events(self, events, anchors, ploidy: int = 2, err_q: int = 20, het_q: int = 30, min_depth: int = 4, min_qual: int = 20):
         """(gts GENOTYPE_DTYPE (m,), called uint8 (m,)): the genotype of every given event (a structured array of EVENT_DTYPE, as
@@ -822,8 +880,9 @@ class Pileup:
 
     def close(self) -> None:
         h, self._h = self._h, None
-        if self.forward is not None:  # (the handle goes with this one)
-            self.forward._h = None
+        for view in (self.forward, getattr(self, "quality", None)):  # (the handles go with this one)
+            if view is not None:
+                view._h = None
         if h and self._owner is None:
             capi.lib().slamem_pileup_free(h)
 
@@ -927,17 +986,22 @@ class Stream:
     def __init__(self, index: Index, slots: int, max_batch_chars: int, max_batch_queries: int, both_strands: bool,
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
                  max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False,
-                 pile: "Pileup" = None, min_mapq: int = 0, md: bool = False, dedup: bool = False):
+                 pile: "Pileup" = None, min_mapq: int = 0, md: bool = False, dedup: bool = False, quals: bool = False,
+                 phred_offset: int = 33):
         """md=True (with paf=True): every batch also goes through the MD pass and mds() gives (md, md_offsets,
         seg_eq, primary) of the batch next() returned last, as Index.map_reads(md=True) appends them.
         dedup=True (with pile=<Pileup> made with dedup=True): every batch is added through the duplicate filter, in
         the order of the submits, and dups() gives the flags of the batch next() returned last.
+        quals=True (with pile=<Pileup> made with quals=True): every batch comes through submit_quals with its quality
+        bytes (Phred + phred_offset).
         pile=<Pileup>: -pile mode (match type 8): every batch is mapped as with paf=True and added to the accumulator on the
         device (the reads with mapq >= min_mapq); next() then returns (number of segments piled, None, timings) and maps() the read
         records; the segments are not downloaded.  It takes the parameters of paf and excludes the other modes.  aln=True: -aln mode (match type 6); it takes max_gap, penalty, xdrop and max_edits and excludes the other modes.
         next() then returns the segments (ALN_DTYPE) in the place of the rows, alns() their operations.  paf=True: -paf mode
         (match type 7), the same with the offsets per READ and maps() the read records (MAP_DTYPE)."""
         self.pile = pile
+        if quals and pile is None:
+            raise ValueError("quals are the quality bytes of pile: it needs pile=<Pileup>")
         if dedup and pile is None:
             raise ValueError("dedup is the duplicate filter of pile: it needs pile=<Pileup>")
         self.dedup = bool(dedup)
@@ -976,6 +1040,8 @@ class Stream:
                 capi.check(capi.lib().slamem_stream_set_dedup(self._h, 1))
             if md:
                 capi.check(capi.lib().slamem_stream_set_md(self._h, 1))
+            if quals:
+                capi.check(capi.lib().slamem_stream_set_quals(self._h, int(phred_offset)))
         except Exception:
             # a setter refused: the stream goes at once, while its index is alive -- not when the exception's traceback, which
             # holds this object, happens to be collected (by then the caller may have closed the index)
@@ -999,6 +1065,17 @@ class Stream:
         self._keep.append((chars, lowq, offsets))
         capi.check(capi.lib().slamem_stream_submit_masked(self._h, chars.ctypes.data, lowq.ctypes.data if lowq is not None else None,
                                                           offsets.ctypes.data, offsets.shape[0] - 1, int(min_len)))
+
+    def submit_quals(self, chars: np.ndarray, quals: np.ndarray, lowq, offsets: np.ndarray, min_len: int) -> None:
+        """submit for a -pile stream made with quals=True: quals is a uint8 array indexed as chars is -- byte
+        offsets[r] + i is the quality of letter i of record r, whatever offsets[0] is; lowq as in submit_masked, or None."""
+        assert chars.dtype == np.uint8 and quals.dtype == np.uint8 and quals.flags.c_contiguous
+        assert offsets.dtype == np.uint64 and offsets.flags.c_contiguous and quals.shape[0] >= int(offsets[-1])
+        assert lowq is None or (lowq.dtype == np.uint64 and lowq.flags.c_contiguous)
+        self._keep.append((chars, quals, lowq, offsets))
+        capi.check(capi.lib().slamem_stream_submit_quals(self._h, chars.ctypes.data, quals.ctypes.data,
+                                                         lowq.ctypes.data if lowq is not None else None, offsets.ctypes.data,
+                                                         offsets.shape[0] - 1, int(min_len)))
 
     def submit_packed(self, planes: np.ndarray, other, offsets: np.ndarray, min_len: int, units: int = 0) -> None:
         """planes: uint8 view of the batch's 16-byte units (slamem_pack_reads layout), other: uint64 per unit or None; offsets:

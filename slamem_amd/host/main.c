@@ -75,6 +75,9 @@ typedef struct {
     int keep_quals;    /* -sam: the quality bytes of every piece are kept for the QUAL column */
     char **quals;      /* ... per piece (NULL: FASTA), as many entries as sets */
     int fasta_seen;    /* a query file without qualities came in (said once when -bq asks for them) */
+    int wq;            /* -wq: the quality bytes of every piece are kept for the pileup's quality sums, and -bq's mask is packed as well */
+    int wq_fill;       /* -wq: the byte the letters of a FASTA piece get, 33 + -err's Q */
+    int fasta_filled;  /* -wq: a query file without qualities came in and was filled (said once) */
     int invalid;       /* a query file is no valid FASTQ: the run ends */
     int cap;
     pthread_mutex_t mu;
@@ -102,6 +105,29 @@ static uint64_t *mask_of_quals(loader_t *ld, const slh_seqset *s, char *quals) {
     return mask;
 }
 
+/* -wq: the set's quality bytes stay (a FASTA set gets wq_fill at every letter), and with -bq N the mask is packed from them as
+ * well.  Returns the mask or NULL; *quals is the set's bytes afterwards (NULL: out of memory, ld->invalid says so). */
+static uint64_t *wq_quals(loader_t *ld, const slh_seqset *s, char **quals) {
+    uint64_t *mask = NULL;
+    if (!*quals) {
+        if (ld->min_bq > 0) ld->fasta_seen = 1;
+        ld->fasta_filled = 1;
+        *quals = (char *)slh_big_malloc((size_t)s->total + 16);
+        if (!*quals) { ld->invalid = 2; return NULL; }
+        memset(*quals, ld->wq_fill, (size_t)s->total + 16);
+        return NULL;
+    }
+    if (ld->min_bq > 0) {
+        mask = (uint64_t *)slh_big_malloc(((size_t)(s->total + 63) / 64 + 1) * sizeof(uint64_t));
+        if (mask && slamem_pack_lowq(*quals, s->total, (uint32_t)ld->min_bq, 33, mask, slh_thread_count()) != SLAMEM_OK) {
+            free(mask);
+            mask = NULL;
+        }
+        if (!mask) ld->invalid = 2; /* (out of memory: never count letters that were to be skipped) */
+    }
+    return mask;
+}
+
 static void *loader_run(void *arg) {
     loader_t *ld = (loader_t *)arg;
     double t0 = now_s();
@@ -118,7 +144,7 @@ static void *loader_run(void *arg) {
             int n = slh_pieces_next_q(p, &s, &quals);
             if (n < 0) ld->invalid = 1;
             if (n <= 0) break;
-            mask = ld->keep_quals ? NULL : mask_of_quals(ld, &s, quals);
+            mask = ld->wq ? wq_quals(ld, &s, &quals) : ld->keep_quals ? NULL : mask_of_quals(ld, &s, quals);
             pthread_mutex_lock(&ld->mu);
             if (ld->ready < ld->cap) {
                 if (ld->keep_quals) { ld->quals[ld->ready] = quals; quals = NULL; }
@@ -674,6 +700,7 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-hetq\twith -gt: the prior cost of a non-reference allele in Phred, 0 to 999 (default=30)\n");
     printf("\t-qual\twith -gt: least QUAL of a call, 0 to 999 (default=20)\n");
     printf("\t-sb\twith -gt: strand counts in the pileup (a second accumulator on the GPU, fed by the forward-strand reads in the same pass); every line gets the strand table SB = reference forward, reference reverse, alternative forward, alternative reverse in the sample column and FS, the Phred-scaled Fisher exact test of it, in INFO\n");
+    printf("\t-wq\twith -gt: every letter weighs with its own base quality in the likelihood of an SNV (a third accumulator on the GPU holds the sum of the qualities per row and letter); every SNV line gets ADQ, the quality sum per allele in AD's order; -err still scores the indel events and the letters of FASTA queries\n");
     printf("\t-fs\twith -sb: FILTER is sb for a line whose FS is above this whole number, 0 to 999, and PASS otherwise (default: FILTER stays .)\n");
     printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
     printf("\t-l\tminimum match length (default=20)\n");
@@ -702,6 +729,8 @@ typedef struct {
     slh_run p;            /* what the command line says */
     slamem_gt_params gtp; /* -gt: the costs behind p.gt_* */
     int sb, fs;           /* -sb: strand counts; -fs N, or -1 */
+    int wq;               /* -wq: per-letter base qualities in the SNV likelihood */
+    slamem_gt_params gtp_wq; /* -wq: gtp with the costs 0, 3010, 4771 for the rows; the events keep gtp */
     int device, timing;
     long log_limit;
     uint64_t batch_bytes;  /* query characters per batch and GPU */
@@ -777,6 +806,9 @@ static int parse_and_refuse(run_t *R, int *status) {
         R->gtp.min_depth = (uint32_t)R->p.min_depth;
         R->gtp.min_qual = (uint32_t)R->p.gt_qual;
     }
+    R->wq = slh_parse_wq(argc, argv) && R->p.gt; /* (without -gt: refused above) */
+    R->gtp_wq = R->gtp;
+    R->gtp_wq.match_cost = 0; R->gtp_wq.het_cost = 3010; R->gtp_wq.err_cost = 4771; /* round(10000 log10 2), round(10000 log10 3) */
     /* one table per GPU would miss the duplicates whose copies went to different GPUs */
     if (R->p.dedup && (((env = getenv("SLAMEM_GPUS")) != NULL && atoi(env) != 1) || ((env = getenv("SLAMEM_LOGICAL_GPUS")) != NULL && atoi(env) > 1)))
         exit_message("Option -dedup runs on one GPU: every GPU would keep a table of its own and miss the duplicates whose copies went to different GPUs (leave SLAMEM_GPUS unset, or set it to 1)");
@@ -825,7 +857,9 @@ static void load_inputs(run_t *R) {
     ld->masks = (uint64_t **)calloc((size_t)ld->cap + 1, sizeof(uint64_t *));
     if (!ld->masks) exit_message("Out of memory");
     ld->min_bq = R->p.min_bq;
-    ld->keep_quals = R->p.sam;
+    ld->keep_quals = R->p.sam || R->wq;
+    ld->wq = R->wq;
+    ld->wq_fill = 33 + R->p.gt_err;
     ld->quals = (char **)calloc((size_t)ld->cap + 1, sizeof(char *));
     if (!ld->quals) exit_message("Out of memory");
     pthread_mutex_init(&ld->mu, NULL);
@@ -854,7 +888,8 @@ static void load_inputs(run_t *R) {
                 exit(-1);
             }
             if (n != 0) {
-                if (ld->keep_quals) ld->quals[ld->ready] = quals;
+                if (ld->wq) { ld->masks[ld->ready] = wq_quals(ld, &R->qsets[ld->ready], &quals); ld->quals[ld->ready] = quals; }
+                else if (ld->keep_quals) ld->quals[ld->ready] = quals;
                 else ld->masks[ld->ready] = mask_of_quals(ld, &R->qsets[ld->ready], quals);
                 if (ld->invalid) exit_message("Out of memory");
                 numbering += n; ld->total_queries += n; ld->ready++;
@@ -915,6 +950,7 @@ static void open_output(run_t *R) {
     else if (p->sites || p->vcf) say(" ; minimum depth = %d ; minimum share = %d %%", p->min_depth, p->min_pct);
     if (R->sb) say(" ; strand bias = on");
     if (R->sb && R->fs >= 0) say(" ; maximum FS = %d", R->fs);
+    if (R->wq) say(" ; base qualities in the likelihood = on");
     if (p->cons) say(" ; minimum depth = %d", p->min_depth);
     if (p->depth) say(" ; covered from depth = %d", p->min_depth);
     say("\n");
@@ -1063,10 +1099,12 @@ static void open_streams(run_t *R) {
         if (rc == SLAMEM_OK && t == 8) { /* one accumulator per GPU: the tables are added when the file is written */
             rc = slamem_pileup_create(R->gpus[g], &R->piles[g]);
             if (rc == SLAMEM_OK && R->sb) rc = slamem_pileup_enable_strands(R->piles[g]);
+            if (rc == SLAMEM_OK && R->wq) rc = slamem_pileup_enable_quals(R->piles[g]);
             if (rc == SLAMEM_OK && (p->vcf || p->cons)) rc = slamem_pileup_enable_events(R->piles[g], p->ev_slots);
             if (rc == SLAMEM_OK && p->dedup) rc = slamem_pileup_enable_dedup(R->piles[g], p->dd_slots);
             if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(s, R->piles[g], (uint32_t)p->min_mapq);
             if (rc == SLAMEM_OK && p->dedup) rc = slamem_stream_set_dedup(s, 1);
+            if (rc == SLAMEM_OK && R->wq) rc = slamem_stream_set_quals(s, 33);
         }
         if (rc == SLAMEM_OK && (t == 6 || t == 7 || t == 8 || (t == 4 && p->max_gap > 0))) rc = slamem_stream_set_max_gap(s, (uint32_t)p->max_gap);
         if (rc == SLAMEM_OK && (t == 5 || t == 6 || t == 7 || t == 8)) rc = slamem_stream_set_ext_params(s, (uint32_t)p->ext_pen, xdrop);
@@ -1088,7 +1126,9 @@ static void submit_batches(run_t *R, size_t *submitted) {
         slamem_stream *s = g_streams[*submitted % (size_t)R->ngpu];
         const uint32_t nrec = (uint32_t)(br->last - br->first), min_len = (uint32_t)R->p.o.min_mem_len;
         /* -bq N on FASTQ reads: the set's mask is indexed as its letters, the stream takes the batch's words */
-        const int rc = qmask ? slamem_stream_submit_masked(s, qs->chars, qmask, qs->offsets + br->first, nrec, min_len)
+        /* -wq: the set's quality bytes beside its letters, indexed as they are */
+        const int rc = R->wq ? slamem_stream_submit_quals(s, qs->chars, (const uint8_t *)R->ld->quals[br->f], qmask, qs->offsets + br->first, nrec, min_len)
+                     : qmask ? slamem_stream_submit_masked(s, qs->chars, qmask, qs->offsets + br->first, nrec, min_len)
                              : slamem_stream_submit(s, qs->chars, qs->offsets + br->first, nrec, min_len);
         if (rc != SLAMEM_OK) pipeline_gpu_fail("MEM search on the GPU", rc);
         R->inflight[*submitted % (size_t)R->ngpu]++;
@@ -1255,6 +1295,7 @@ static void check_loader(run_t *R) {
            overlapped run only knows it now) */
         exit_message(ld->invalid == 1 ? "A query file is not valid FASTQ" : ld->invalid ? "Out of memory" : "No query files provided");
     }
+    if (ld->fasta_filled) fprintf(stderr, "> NOTE: option -wq: FASTA queries carry no base qualities: their letters count with the quality of -err, %d\n", R->p.gt_err);
     if (ld->fasta_seen) fprintf(stderr, "> WARNING: option -bq %d has no effect on FASTA queries: they carry no base qualities\n", R->p.min_bq);
 }
 
@@ -1331,6 +1372,16 @@ static void merge_gpu_tables(run_t *R) {
         }
         if (rc != SLAMEM_OK) pipeline_gpu_fail("adding up the forward-strand pileups of the GPUs", rc);
     }
+    for (g = 1; R->wq && g < g_nstreams; g++) { /* -wq: the quality accumulators, the same way */
+        slamem_pileup *to = NULL, *from = NULL;
+        rc = slamem_pileup_quality(R->piles[0], &to);
+        if (rc == SLAMEM_OK) rc = slamem_pileup_quality(R->piles[g], &from);
+        FOR_RANGES(x0, cnt) {
+            if (rc == SLAMEM_OK) rc = slamem_pileup_counts_host(from, x0, cnt, rows);
+            if (rc == SLAMEM_OK) rc = slamem_pileup_add_counts_host(to, x0, cnt, rows);
+        }
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("adding up the quality sums of the GPUs", rc);
+    }
     free(rows);
     for (g = 1; with_events && g < g_nstreams; g++) {
         FOR_RANGES(x0, cnt) {
@@ -1386,10 +1437,13 @@ typedef struct { /* -sites, -vcf: the selected rows of a range */
     uint32_t *rows;
     uint8_t *alleles;
     slamem_genotype *gts;
+    uint32_t *qsums; /* -wq: four quality sums per selected row */
 } sites_call;
 static int fetch_sites(void *ctx, uint64_t cap, uint64_t *total) {
     sites_call *c = (sites_call *)ctx;
     const slh_run *p = &c->R->p;
+    if (c->R->wq)
+        return slamem_pileup_genotypes_weighted_host(c->R->piles[0], c->x0, c->cnt, &c->R->gtp_wq, cap, c->pos, c->rows, c->gts, c->qsums, total);
     return p->gt ? slamem_pileup_genotypes_host(c->R->piles[0], c->x0, c->cnt, &c->R->gtp, cap, c->pos, c->rows, c->gts, total)
                  : slamem_pileup_sites_host(c->R->piles[0], c->x0, c->cnt, SLAMEM_SITES_VARIANT, (uint32_t)p->min_depth,
                                             (uint32_t)p->min_pct, cap, c->pos, c->rows, c->alleles, total);
@@ -1409,8 +1463,8 @@ static void write_sites_or_vcf(run_t *R) {
     uint8_t *ecalled = NULL;
     sites_call sc;
     events_call ec;
-    const grow_buf sbufs[5] = {{(void **)&sc.pos, 8, 0}, {(void **)&sc.rows, 24, 0}, {(void **)&sc.alleles, 1, 0}, {(void **)&sc.gts, sizeof(slamem_genotype), 0},
-                               {(void **)&frows, 24, 0}};
+    const grow_buf sbufs[6] = {{(void **)&sc.pos, 8, 0}, {(void **)&sc.rows, 24, 0}, {(void **)&sc.alleles, 1, 0}, {(void **)&sc.gts, sizeof(slamem_genotype), 0},
+                               {(void **)&frows, 24, 0}, {(void **)&sc.qsums, 16, 0}};
     const grow_buf ebufs[6] = {{(void **)&ec.evs, sizeof(slamem_event), 0}, {(void **)&anchors, 8, 0}, {(void **)&arows, 24, 0},
                                {(void **)&egts, sizeof(slamem_genotype), 0}, {(void **)&ecalled, 1, 0}, {(void **)&afrows, 24, 0}};
     int r = 0, m, pi, rc;
@@ -1419,13 +1473,14 @@ static void write_sites_or_vcf(run_t *R) {
     sc.R = R;
     ec.pile = R->piles[0];
     if (R->sb && (rc = slamem_pileup_forward(R->piles[0], &fwd)) != SLAMEM_OK) pipeline_gpu_fail("reading the forward-strand pileup from the GPU", rc);
-    if (p->vcf && (R->sb ? slh_format_vcf_sb_header(&R->buf, ref->recs, ref->num, R->fs)
+    if (p->vcf && (R->wq ? slh_format_vcf_wq_header(&R->buf, ref->recs, ref->num, R->sb, R->fs)
+                   : R->sb ? slh_format_vcf_sb_header(&R->buf, ref->recs, ref->num, R->fs)
                    : p->gt ? slh_format_vcf_gt_header(&R->buf, ref->recs, ref->num) : slh_format_vcf_header(&R->buf, ref->recs, ref->num)))
         pipeline_fail("Out of memory");
     FOR_RANGES(x0, cnt) {
         sc.x0 = ec.x0 = x0;
         sc.cnt = ec.cnt = cnt;
-        rc = fetch_growing(&cap, sbufs, R->sb ? 5 : p->gt ? 4 : 3, fetch_sites, &sc, &total);
+        rc = fetch_growing(&cap, sbufs, R->wq ? 6 : R->sb ? 5 : p->gt ? 4 : 3, fetch_sites, &sc, &total);
         if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the variant sites from the GPU", rc);
         if (R->sb && (rc = slamem_pileup_rows_at_host(fwd, sc.pos, total, frows)) != SLAMEM_OK)
             pipeline_gpu_fail("reading the forward-strand rows of the variant sites from the GPU", rc);
@@ -1457,6 +1512,10 @@ static void write_sites_or_vcf(run_t *R) {
             for (ee = ek; ee < etotal && ec.evs[ee].pos < pc->start + size; ee++) {}
             if (e == k && ee == ek) continue;
             if (!p->vcf ? slh_format_site_rows(&R->buf, name, pc->start, ref->chars, sc.pos + k, sc.rows + k * 6, sc.alleles + k, e - k)
+                : R->wq ? slh_format_vcf_wq_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6, frows + k * 6,
+                                                 sc.qsums + k * 4, (const slh_genotype *)(sc.gts + k), e - k, (const slh_event *)(ec.evs + ek),
+                                                 arows + ek * 6, R->sb ? afrows + ek * 6 : NULL, (const slh_genotype *)(egts + ek), ecalled + ek, ee - ek, R->sb,
+                                                 R->fs)
                 : R->sb ? slh_format_vcf_sb_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6, frows + k * 6,
                                                  (const slh_genotype *)(sc.gts + k), e - k, (const slh_event *)(ec.evs + ek), arows + ek * 6,
                                                  afrows + ek * 6, (const slh_genotype *)(egts + ek), ecalled + ek, ee - ek, R->fs)
@@ -1470,7 +1529,7 @@ static void write_sites_or_vcf(run_t *R) {
         }
         push_text(R);
     }
-    free(sc.pos); free(sc.rows); free(sc.alleles); free(sc.gts);
+    free(sc.pos); free(sc.rows); free(sc.alleles); free(sc.gts); free(sc.qsums);
     free(ec.evs); free(anchors); free(arows); free(egts); free(ecalled); free(frows); free(afrows);
     if (p->vcf) warn_skipped(R, ec.sk);
 }

@@ -931,7 +931,7 @@ typedef struct {
     const char *refusal; /* of a bad value; a mode's: of another mode beside it */
 } option_row;
 enum { O_MEM, O_MAM, O_MUM, O_SMEM, O_OCC, O_CHAIN, O_MGAP, O_EXT, O_PEN, O_XDROP, O_ALN, O_MAXED, O_PAF, O_SAM, O_PILE, O_MINQ, O_BQ,
-       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_EVS,
+       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_WQ, O_EVS,
        O_L, O_O, O_B, O_N, O_M, O_R, O_V, O_S, O_C, NUM_OPTIONS };
 #define PEN_XDROP "Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"
 static const option_row OPTIONS[NUM_OPTIONS] = {
@@ -969,6 +969,7 @@ static const option_row OPTIONS[NUM_OPTIONS] = {
     [O_QUAL] = {"qual", 0, 0, V_INT, 0, 0, 999, 20, "Option -qual needs a whole number from 0 to 999"},
     [O_SB] = {"sb", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
     [O_FS] = {"fs", 0, 0, V_INT, 0, 0, 999, -1, "Option -fs needs a whole number from 0 to 999"},
+    [O_WQ] = {"wq", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
     [O_EVS] = {"evs", 0, 0, V_POW2, 0, 64, 1ull << 31, 0, "Option -evs needs a power of two of at least 64"},
     [O_L] = {"l", 0, 0, V_ATOI, 0, 0, 0, 20, NULL},
     [O_O] = {"o", 0, 0, V_INDEX, 0, 0, 0, -1, NULL},
@@ -1111,6 +1112,7 @@ int slh_parse_sb_params(int argc, char **argv, int *fs_out) {
     *fs_out = (int)(long long)v[1];
     return rc < 0 ? -1 : rc;
 }
+int slh_parse_wq(int argc, char **argv) { return has_option(argc, argv, O_WQ); }
 int slh_parse_dedup(int argc, char **argv, uint64_t *slots_out) {
     static const int ids[2] = {O_DEDUP, O_DSLOTS};
     uint64_t v[2];
@@ -1271,6 +1273,7 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     REFUSE_IF(sb < 0, OPTIONS[O_FS].refusal);
     REFUSE_IF((sb & 1) && !r->gt, "Option -sb needs -gt");
     REFUSE_IF((sb & 2) && !(sb & 1), "Option -fs needs -sb");
+    REFUSE_IF(has_option(argc, argv, O_WQ) && !r->gt, "Option -wq needs -gt");
     REFUSE_IF(dparams < 0, OPTIONS[dparams == -1 ? O_LEV : O_WIN].refusal);
     REFUSE_IF(dparams == 3 && r->depth, "Options -lev and -win exclude each other");
     REFUSE_IF(dparams && !r->depth, "Options -lev and -win need -depth");
@@ -1967,6 +1970,81 @@ int slh_format_vcf_sb_rows(slh_buffer *buf, const char *record_name, uint64_t re
         if (!rc && buf->len > start) rc = sb_decorate(buf, start, t, fs_filter, &tmp);
     }
     slh_buffer_free(&tmp);
+    return rc;
+}
+
+/* ---- -wq: the lines of -vcf -gt, with or without -sb, and the quality sums per allele behind them ---- */
+
+int slh_format_vcf_wq_header(slh_buffer *buf, const slh_record *refs, int num_refs, int sb, int fs_filter) {
+    slh_buffer base = {0, 0, 0};
+    int rc = sb ? slh_format_vcf_sb_header(&base, refs, num_refs, fs_filter) : slh_format_vcf_gt_header(&base, refs, num_refs);
+    /* the head of the file without -wq, with ADQ behind its FORMAT lines */
+    if (!rc) rc = sb_copy_lines(buf, &base, "#CHROM", 0);
+    if (!rc) rc = sb_put(buf, "##FORMAT=<ID=ADQ,Number=R,Type=Integer,Description=\"Sum of the base qualities of the observations of the reference "
+                              "and of each alternate allele\">\n");
+    if (!rc) rc = sb_copy_lines(buf, &base, "#CHROM", 1);
+    slh_buffer_free(&base);
+    return rc;
+}
+
+/* The line that has just been written at buf->data + start, with :ADQ behind FORMAT and the sums (na of them; 0: a dot) behind
+ * the sample */
+static int wq_decorate(slh_buffer *buf, size_t start, const uint32_t *adq, int na) {
+    char *p, *tab;
+    size_t tail;
+    int k;
+    if (buf_reserve(buf, 64)) return -1;
+    p = buf->data + buf->len - 1; /* the line's '\n' */
+    for (tab = p; tab > buf->data + start && *tab != '\t'; tab--) {} /* the tab in front of the sample */
+    tail = (size_t)(buf->data + buf->len - tab);
+    memmove(tab + 4, tab, tail);
+    memcpy(tab, ":ADQ", 4);
+    p += 4;
+    if (na == 0) { *p++ = ':'; *p++ = '.'; }
+    for (k = 0; k < na; k++) {
+        *p++ = k ? ',' : ':';
+        p = put_u32(p, adq[k]);
+    }
+    *p++ = '\n';
+    buf->len = (size_t)(p - buf->data);
+    return 0;
+}
+
+int slh_format_vcf_wq_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                           const uint64_t *site_pos, const uint32_t *site_counts, const uint32_t *site_fwd, const uint32_t *site_qsums,
+                           const slh_genotype *site_gts, uint64_t sites, const slh_event *events, const uint32_t *anchor_rows,
+                           const uint32_t *anchor_fwd, const slh_genotype *event_gts, const uint8_t *called, uint64_t num_events, int sb,
+                           int fs_filter) {
+    uint64_t i = 0, e = 0;
+    int rc = 0;
+    while (!rc && (i < sites || e < num_events)) { /* the order of slh_format_vcf_gt_rows, a line at a time */
+        const uint64_t spos = i < sites ? site_pos[i] - record_start + 1 : ~0ull;
+        uint64_t epos = ~0ull;
+        const size_t start = buf->len;
+        uint32_t adq[4];
+        int na = 0, k;
+        if (e < num_events) epos = events[e].pos > record_start ? events[e].pos - record_start : 1;
+        if (spos <= epos) {
+            const slh_genotype *g = &site_gts[i];
+            const uint32_t *q = site_qsums + 4 * i;
+            const int r = g->ref & 3;
+            adq[na++] = q[r]; /* AD's order: the reference, then the line's ALT letters ascending */
+            for (k = 0; k < 4; k++)
+                if (k != r && (k == (g->a & 3) || k == (g->b & 3))) adq[na++] = q[k];
+            rc = sb ? slh_format_vcf_sb_rows(buf, record_name, record_start, record_size, text, site_pos + i, site_counts + 6 * i, site_fwd + 6 * i,
+                                             g, 1, NULL, NULL, NULL, NULL, NULL, 0, fs_filter)
+                    : slh_format_vcf_gt_rows(buf, record_name, record_start, record_size, text, site_pos + i, site_counts + 6 * i, g, 1, NULL, NULL,
+                                             NULL, NULL, 0);
+            i++;
+        } else {
+            rc = sb ? slh_format_vcf_sb_rows(buf, record_name, record_start, record_size, text, NULL, NULL, NULL, NULL, 0, events + e,
+                                             anchor_rows + 6 * e, anchor_fwd + 6 * e, event_gts + e, called + e, 1, fs_filter)
+                    : slh_format_vcf_gt_rows(buf, record_name, record_start, record_size, text, NULL, NULL, NULL, 0, events + e, anchor_rows + 6 * e,
+                                             event_gts + e, called + e, 1);
+            e++;
+        }
+        if (!rc && buf->len > start) rc = wq_decorate(buf, start, adq, na);
+    }
     return rc;
 }
 

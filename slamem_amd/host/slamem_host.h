@@ -133,6 +133,8 @@ int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, in
 /* -sb and -fs N in [0, 999] (-1: absent): bit 0 of the result says that -sb is there, bit 1 that -fs is; -1 when the value of -fs
  * is refused */
 int slh_parse_sb_params(int argc, char **argv, int *fs_out);
+/* -wq (no value; needs -gt): whether it is there */
+int slh_parse_wq(int argc, char **argv);
 /* -depth: is it given? */
 int slh_parse_depth(int argc, char **argv);
 /* -dedup and -dslots N, a power of two in [64, 2^32] (0): bit 0 of the result says that -dedup is there, bit 1 that -dslots is;
@@ -273,6 +275,16 @@ int slh_format_vcf_sb_rows(slh_buffer *buf, const char *record_name, uint64_t re
                            const uint64_t *site_pos, const uint32_t *site_counts, const uint32_t *site_fwd, const slh_genotype *site_gts,
                            uint64_t sites, const slh_event *events, const uint32_t *anchor_rows, const uint32_t *anchor_fwd,
                            const slh_genotype *event_gts, const uint8_t *called, uint64_t num_events, int fs_filter);
+/* -wq: the header of -vcf -gt (sb: of -sb, with fs_filter) with ##FORMAT=<ID=ADQ,Number=R,...> behind its FORMAT
+ * lines, and the lines of slh_format_vcf_gt_rows (sb: of slh_format_vcf_sb_rows), each with one more sample value ADQ: on an SNV
+ * line the quality sums of the reference and of each ALT letter in AD's order, from site_qsums (four per site: the A C G T
+ * columns of the quality accumulator), on an indel line a dot.  site_fwd and anchor_fwd are looked at with sb only. */
+int slh_format_vcf_wq_header(slh_buffer *buf, const slh_record *refs, int num_refs, int sb, int fs_filter);
+int slh_format_vcf_wq_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                           const uint64_t *site_pos, const uint32_t *site_counts, const uint32_t *site_fwd, const uint32_t *site_qsums,
+                           const slh_genotype *site_gts, uint64_t sites, const slh_event *events, const uint32_t *anchor_rows,
+                           const uint32_t *anchor_fwd, const slh_genotype *event_gts, const uint8_t *called, uint64_t num_events, int sb,
+                           int fs_filter);
 /* -cons: one FASTA record -- '>' and the record's name up to its first blank or tab, then `len` letters in lines of 60; a record
  * of no letters is its header line alone */
 int slh_format_fasta_record(slh_buffer *buf, const char *record_name, const char *letters, uint64_t len);
