@@ -856,6 +856,59 @@ int slamem_pileup_genotypes_weighted_host(slamem_pileup *pile, uint64_t first, u
                                           uint64_t capacity, uint64_t *pos, uint32_t *counts, slamem_genotype *gts, uint32_t *qsums,
                                           uint64_t *total_out);
 
+/* ---- (c) mapping QC tables (-stats) -----------------------------------------------------------------------------
+ * A slamem_stats is an accumulator of SLAMEM_STATS_WORDS unsigned 64-bit counters on the index's device, the sum over every batch
+ * added since creation or the last reset, whatever the split into batches, their order and their streams: every number is a
+ * count.  A read is MAPPED when its record has strand != 0 and COUNTED when it is mapped and mapq >= min_mapq.  The CYCLE of letter
+ * x of the scanned strand is x on strand 1 and len - 1 - x on strand 2: the letter's index in the read as given.  A value above a
+ * section's last bin goes into that bin.  The sections, as (first word, words):
+ *   TOTALS   (0, 24)      16 used: reads; mapped; forward; reverse; counted; counted reads with more than one segment; segments of
+ *                         counted reads; letters of all reads; letters of counted reads; letters under =; letters under X; I
+ *                         operations; inserted letters; D operations; deleted reference letters; the sum of query_len over the
+ *                         segments of counted reads
+ *   MAPQ     (24, 64)     mapped reads per mapping quality
+ *   LEN      (88, 512)    all reads per length
+ *   NM       (600, 128)   counted reads per sum of `edits` over their segments
+ *   CYC_ALN  (728, 512)   letters under = or X per cycle          CYC_MM  (1240, 512)  letters under X per cycle
+ *   CYC_INS  (1752, 512)  inserted letters per cycle              CYC_DEL (2264, 512)  D operations, at the cycle of the letter of
+ *                                                                                      the scanned strand that follows the deletion
+ *   SUB      (2776, 16)   per letter under X: 4 * text letter + letter of the scanned strand (A C G T = 0..3); skipped when either
+ *                         is none of the four
+ *   Q_ALN    (2792, 96)   letters under = or X per quality min(93, max(0, byte - phred_offset)); only with quality bytes
+ *   Q_MM     (2888, 96)   letters under X per quality; only with quality bytes
+ *   INS_LEN  (2984, 64)   I operations per length                 DEL_LEN (3048, 64)   D operations per length
+ * The sections from CYC_ALN on, NM and the TOTALS from `counted` on (but `letters of all reads`) are over the counted reads.  A
+ * low-quality mask and the duplicate filter play no part: the table describes the mapping.
+ *   slamem_stats_create      the table, all zero; the index must outlive it.  slamem_stats_reset zeroes it (waits for the device).
+ *   slamem_stats_add_device  adds the batch that slamem_find_maps_device left behind these pointers: one kernel on `stream`,
+ *                            asynchronous, nothing is read back or checked on the host.  quals_dev: a byte per letter, indexed as
+ *                            queries_dev is, or NULL (Q_ALN and Q_MM stay as they are).  SLAMEM_ERR_ARG: min_mapq above 60,
+ *                            phred_offset above 126, an index without text planes (the COMPACT layout).  Adds from several streams
+ *                            and threads into one table are safe: every update is an atomic add.
+ *   slamem_stats_table_device / _host  the SLAMEM_STATS_WORDS words; _device is a copy on `stream`, _host waits for the device.
+ *   slamem_stats_add_table_host  adds a table to the accumulator (the tables of several GPUs are added up that way).
+ *   slamem_stream_set_stats  a stream of match type 7 or 8 adds every batch to `st` (of the stream's device) behind its map pass,
+ *                            counting the reads with mapq >= min_mapq; on a stream of type 8 beside the pile add, which is
+ *                            untouched.  Before the first submit; SLAMEM_ERR_ARG after it, on another match type, with another
+ *                            device's table, with min_mapq above 60 or on an index without text planes.  with_quals != 0: batches
+ *                            that come through slamem_stream_submit_quals feed Q_ALN and Q_MM with their bytes (Phred + 33, or the
+ *                            offset given to slamem_stream_set_quals); on a type-8 stream this coexists with
+ *                            slamem_stream_set_quals, on a type-7 stream it is the only use of the bytes.  A batch that comes
+ *                            through another submit has no bytes and leaves the two sections as they are.  A stream that never
+ *                            calls it behaves as before and allocates nothing for this (declared with the stream, below). */
+#define SLAMEM_STATS_WORDS 3112
+typedef struct slamem_stats slamem_stats;
+int slamem_stats_create(const slamem_index *idx, slamem_stats **out);
+int slamem_stats_free(slamem_stats *st);
+int slamem_stats_reset(slamem_stats *st);
+int slamem_stats_add_device(slamem_stats *st, const void *queries_dev, const uint64_t *offsets_dev, uint32_t num_queries,
+                            const slamem_aln *segs_dev, const uint64_t *read_offsets_dev, const uint32_t *ops_dev,
+                            const uint64_t *op_offsets_dev, const slamem_map *reads_dev, const uint8_t *quals_dev /* NULL: none */,
+                            uint32_t phred_offset, uint32_t min_mapq, void *stream);
+int slamem_stats_table_device(slamem_stats *st, uint64_t *out_dev, void *stream);
+int slamem_stats_table_host(slamem_stats *st, uint64_t *out /* SLAMEM_STATS_WORDS */);
+int slamem_stats_add_table_host(slamem_stats *st, const uint64_t *table);
+
 /* Host-buffer convenience used by the C front end: uploads the batch, runs
  * slamem_find_mems_device (growing the output buffer if needed) and returns
  * malloc()ed arrays the caller frees with slamem_host_free(). */
@@ -971,6 +1024,8 @@ int slamem_stream_dups(slamem_stream *s, const uint8_t **flags_out);
 int slamem_stream_set_quals(slamem_stream *s, uint32_t phred_offset);
 int slamem_stream_submit_quals(slamem_stream *s, const char *queries, const uint8_t *quals, const uint64_t *lowq,
                                const uint64_t *offsets, uint32_t num_queries, uint32_t min_len);
+/* -stats (described with slamem_stats_create above) */
+int slamem_stream_set_stats(slamem_stream *s, slamem_stats *st, uint32_t min_mapq, int with_quals);
 /* -sam: on != 0 makes every slot of a stream of match type 7 run slamem_maps_md_device behind its batch and
  * download the four arrays; before the first submit (SLAMEM_ERR_ARG after it, or on a stream of another match type).  A stream
  * that never calls it behaves as before and allocates nothing for this.  slamem_stream_md gives the arrays of the batch

@@ -63,6 +63,8 @@ ABI_SYMBOLS = (
     "slamem_pileup_enable_strands", "slamem_pileup_forward", "slamem_fisher_strand", "slamem_fisher_strand_table",
     "slamem_pileup_enable_quals", "slamem_pileup_quality", "slamem_pileup_add_quals_device", "slamem_pileup_genotypes_weighted_device",
     "slamem_pileup_genotypes_weighted_host", "slamem_stream_set_quals", "slamem_stream_submit_quals",
+    "slamem_stats_create", "slamem_stats_free", "slamem_stats_reset", "slamem_stats_add_device", "slamem_stats_table_device",
+    "slamem_stats_table_host", "slamem_stats_add_table_host", "slamem_stream_set_stats",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
 )
@@ -250,6 +252,14 @@ def _declare(L):
     L.slamem_pileup_genotypes_weighted_host.argtypes = [vp, u64, u64, C.POINTER(GtParams), u64, vp, vp, vp, vp, C.POINTER(u64)]
     L.slamem_stream_set_quals.argtypes = [vp, u32]
     L.slamem_stream_submit_quals.argtypes = [vp, vp, vp, vp, vp, u32, u32]
+    L.slamem_stats_create.argtypes = [vp, C.POINTER(vp)]
+    L.slamem_stats_free.argtypes = [vp]
+    L.slamem_stats_reset.argtypes = [vp]
+    L.slamem_stats_add_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u32, u32, vp]
+    L.slamem_stats_table_device.argtypes = [vp, vp, vp]
+    L.slamem_stats_table_host.argtypes = [vp, vp]
+    L.slamem_stats_add_table_host.argtypes = [vp, vp]
+    L.slamem_stream_set_stats.argtypes = [vp, vp, u32, i32]
     L.slamem_fisher_strand.argtypes = [C.POINTER(u32)]
     L.slamem_fisher_strand.restype = C.c_double
     L.slamem_fisher_strand_table.argtypes = [C.POINTER(u32), C.POINTER(u32)]

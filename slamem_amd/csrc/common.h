@@ -464,6 +464,12 @@ int pileup_add_quals(slamem_pileup* pile, const void* queries_dev, const uint64_
                      const slamem_aln* segs_dev, const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev,
                      const slamem_map* reads_dev, uint32_t min_mapq, const uint64_t* lowq_dev, const unsigned char* quals_dev,
                      uint32_t phred_offset, bool dedup, slamem_map* reads_keep_dev, uint8_t* dup_out_dev, hipStream_t stream);
+// -stats (stats_filter.hip): the batch's counts into the table, one kernel behind the map kernels; quals_dev
+// nullptr: the two quality sections stay as they are.  stats_device: the device the table lives on.
+int stats_device(const slamem_stats* st);
+int stats_add(slamem_stats* st, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries, const slamem_aln* segs_dev,
+              const uint64_t* read_offsets_dev, const uint32_t* ops_dev, const uint64_t* op_offsets_dev, const slamem_map* reads_dev,
+              const unsigned char* quals_dev, uint32_t phred_offset, uint32_t min_mapq, hipStream_t stream);
 // pile_filter.hip, for the three add entries without quality bytes: SLAMEM_ERR_ARG and a message on an accumulator with quality sums
 int pile_refuse_quals(const slamem_pileup* pile, const char* fn);
 // One batch through the search in steps that may be issued apart and on different streams (mem_search.hip; used by stream.hip):

@@ -1,7 +1,7 @@
 // pile_shared.h -- what pile_filter.hip (-pile and -sites), event_filter.hip (the indel events of -vcf,
 // DESIGN.md 4.18), cons_filter.hip (the consensus of -cons), depth_filter.hip (the runs of -depth) and
-// dedup_filter.hip (the duplicate filter of -dedup) and qual_filter.hip (the quality sums of -wq) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
-// segments (letters of the scanned strand, the steps of an operation, the low-quality mask's window), and the two entry points of the read-out's scratch that
+// dedup_filter.hip (the duplicate filter of -dedup) and qual_filter.hip (the quality sums of -wq) and stats_filter.hip (the table of -stats) have in common: the accumulator's record, a batch as slamem_pileup_add_device takes it, the walk of a read's
+// segments (letters of the scanned strand, the steps of an operation, the low-quality mask's window, the quality bytes, the text's letter), and the two entry points of the read-out's scratch that
 // the event side borrows.
 #pragma once
 #include "common.h"
@@ -134,6 +134,54 @@ __device__ __forceinline__ PileLow pile_low(const PileBatch& b, const PileRead& 
         m.rev = rd.rev;
     }
     return m;
+}
+
+// ---- the quality bytes of a read (qual_filter.hip and stats_filter.hip) ---------------------------------------
+// the quality bytes of one read as given, and the Phred offset
+struct QualRead {
+    const unsigned char* qb;
+    uint64_t len;
+    uint32_t off;
+    bool rev;
+};
+
+__device__ __forceinline__ uint32_t qual_value(uint32_t byte, uint32_t off) {
+    const uint32_t v = byte < off ? 0u : byte - off;
+    return v < 93u ? v : 93u;
+}
+
+// the byte of letter x of the scanned strand (x < len)
+__device__ __forceinline__ uint32_t qual_byte(const QualRead& r, uint64_t x) { return r.qb[r.rev ? r.len - 1u - x : x]; }
+
+// how many of the letters [x, x + c) of the scanned strand, from x on, carry the byte `byte`: eight at a time while eight are
+// left -- the eight bytes XORed with the byte in every position are 0, or the first byte in scanned order that is not says where
+// the stretch ends -- then one by one.  x + c <= len: every load lies inside the read's own bytes.  On strand 2 the letters
+// x .. x + 7 are the given bytes len - 8 - x .. len - 1 - x, the first of them the highest.
+__device__ __forceinline__ uint32_t qual_same(const QualRead& r, uint64_t x, uint32_t c, uint32_t byte) {
+    const uint64_t all = 0x0101010101010101ull * byte;
+    uint32_t i = 0;
+    while (i + 8u <= c) {
+        uint64_t w;
+        __builtin_memcpy(&w, r.qb + (r.rev ? r.len - 8u - (x + i) : x + i), 8);
+        w ^= all;
+        if (w) return i + (uint32_t)(r.rev ? __builtin_clzll(w) : __builtin_ctzll(w)) / 8u;
+        i += 8u;
+    }
+    while (i < c && qual_byte(r, x + i) == byte) i++;
+    return i;
+}
+
+__device__ __forceinline__ QualRead qual_read(const PileBatch& b, const PileRead& rd, const unsigned char* quals, uint32_t off) {
+    return QualRead{quals + (rd.rec - b.queries), rd.len, off, rd.rev};
+}
+
+// the text's letter at x as two bits (a place at or behind n, which no X or D reaches: 0); sam_filter.hip's MD entries and
+// stats_filter.hip's substitution table take it from the text planes
+__device__ __forceinline__ uint32_t md_text(const TextPlanes* __restrict__ tpl, uint64_t n, uint64_t x) {
+    if (x >= n) return 0u;
+    const TextPlanes* u = tpl + (x >> 6);
+    const uint32_t bit = (uint32_t)(x & 63u);
+    return (uint32_t)((u->p0 >> bit) & 1ull) | ((uint32_t)((u->p1 >> bit) & 1ull) << 1);
 }
 
 __device__ __forceinline__ uint64_t wave_scan_inclusive(uint64_t v, uint32_t lane) {

@@ -27,41 +27,7 @@ struct QualAcc {
     uint32_t n;
 };
 
-// the quality bytes of one read as given, and the Phred offset
-struct QualRead {
-    const unsigned char* qb;
-    uint64_t len;
-    uint32_t off;
-    bool rev;
-};
-
 constexpr uint32_t kNoByte = 0x100u;  // no byte: the level is 0 because the row is excluded, not because of a letter
-
-__device__ __forceinline__ uint32_t qual_value(uint32_t byte, uint32_t off) {
-    const uint32_t v = byte < off ? 0u : byte - off;
-    return v < 93u ? v : 93u;
-}
-
-// the byte of letter x of the scanned strand (x < len)
-__device__ __forceinline__ uint32_t qual_byte(const QualRead& r, uint64_t x) { return r.qb[r.rev ? r.len - 1u - x : x]; }
-
-// how many of the letters [x, x + c) of the scanned strand, from x on, carry the byte `byte`: eight at a time while eight are
-// left -- the eight bytes XORed with the byte in every position are 0, or the first byte in scanned order that is not says where
-// the stretch ends -- then one by one.  x + c <= len: every load lies inside the read's own bytes.  On strand 2 the letters
-// x .. x + 7 are the given bytes len - 8 - x .. len - 1 - x, the first of them the highest.
-__device__ __forceinline__ uint32_t qual_same(const QualRead& r, uint64_t x, uint32_t c, uint32_t byte) {
-    const uint64_t all = 0x0101010101010101ull * byte;
-    uint32_t i = 0;
-    while (i + 8u <= c) {
-        uint64_t w;
-        __builtin_memcpy(&w, r.qb + (r.rev ? r.len - 8u - (x + i) : x + i), 8);
-        w ^= all;
-        if (w) return i + (uint32_t)(r.rev ? __builtin_clzll(w) : __builtin_ctzll(w)) / 8u;
-        i += 8u;
-    }
-    while (i < c && qual_byte(r, x + i) == byte) i++;
-    return i;
-}
 
 // an `=` run over rows [p, p + k) that shows letters [q, q + k) of the scanned strand, a text word (up to 64 rows) at a time as
 // pile_eq_masked goes: `cur` is the level of the open stretch (0 outside one), `curb` the byte that set it.  An excluded row
@@ -126,10 +92,6 @@ __device__ __forceinline__ void qual_op(const QualAcc& a, const PileRead& rd, co
             if (v) atomicAdd(&a.cnt[(p + j) * 6u + c], v);
         }
     }
-}
-
-__device__ __forceinline__ QualRead qual_read(const PileBatch& b, const PileRead& rd, const unsigned char* quals, uint32_t off) {
-    return QualRead{quals + (rd.rec - b.queries), rd.len, off, rd.rev};
 }
 
 template <bool kMasked>

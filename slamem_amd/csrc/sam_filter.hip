@@ -33,14 +33,6 @@ __device__ __forceinline__ uint32_t md_entry_step(uint32_t op) {  // entries an 
 }
 __device__ __forceinline__ uint32_t md_eq_step(uint32_t op) { return (op & 15u) == kOpEq ? op >> 4 : 0u; }
 
-// the text's letter at x as two bits (a place at or behind n, which no X or D reaches: 0)
-__device__ __forceinline__ uint32_t md_text(const TextPlanes* __restrict__ tpl, uint64_t n, uint64_t x) {
-    if (x >= n) return 0u;
-    const TextPlanes* u = tpl + (x >> 6);
-    const uint32_t bit = (uint32_t)(x & 63u);
-    return (uint32_t)((u->p0 >> bit) & 1ull) | ((uint32_t)((u->p1 >> bit) & 1ull) << 1);
-}
-
 // the k entries of an X or D operation at reference place p, from entry `at`: the first carries m
 __device__ __forceinline__ void md_emit(const TextPlanes* __restrict__ tpl, uint64_t n, uint32_t op, uint64_t p, uint32_t m, uint64_t at,
                                         uint64_t cap, uint32_t* __restrict__ md) {

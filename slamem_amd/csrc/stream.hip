@@ -160,6 +160,9 @@ struct slamem_stream {
     bool dedup = false;                     // -dedup: every batch is added with the duplicate filter (slamem_stream_set_dedup)
     bool quals = false;                     // -wq: every batch comes with its quality bytes (slamem_stream_set_quals)
     uint32_t phred_offset = 33;             // -wq: the Phred offset of those bytes
+    slamem_stats* stats = nullptr;          // -stats: the table every batch is added to (slamem_stream_set_stats)
+    uint32_t stats_min_mapq = 0;            // -stats: the least mapping quality that counts there
+    bool stats_quals = false;               // -stats: batches may come through slamem_stream_submit_quals; their bytes feed the table
     uint64_t max_chars = 0;
     uint32_t max_q = 0;
     std::unique_ptr<Slot[]> slot;  // nslots of them; they go in teardown(), in front of the HIP streams
@@ -603,6 +606,11 @@ int stage_download(slamem_stream* s, Slot& sl) {
         if (rc != SLAMEM_OK) return rc;
     } else {
         SLAMEM_TRY(sl.h_mems.reserve(sl.cap, 16));
+    }
+    if (s->stats) {  // (the batch's result stands; its counts go to the table, from the records as the search wrote them)
+        const unsigned char* qb = (s->stats_quals && sl.quals && sl.d_qual.get()) ? sl.d_qual.get() - sl.offs[0] : nullptr;
+        SLAMEM_TRY(stats_add(s->stats, device_queries(sl), sl.d_off.get(), sl.nq, sl.d_segs.get(), sl.d_boff.get(), sl.d_ops.get(),
+                             sl.d_ooff.get(), sl.d_reads.get(), qb, s->phred_offset, s->stats_min_mapq, st));
     }
     if (sl.total && !is_aln(s))
         SLAMEM_HIP(hipMemcpyAsync(sl.h_mems.get(), sl.d_mems.get(), sl.total * sizeof(slamem_mem), hipMemcpyDeviceToHost, st));
@@ -1094,6 +1102,33 @@ int slamem_stream_set_quals(slamem_stream* s, uint32_t phred_offset) {
     return SLAMEM_OK;
 }
 
+int slamem_stream_set_stats(slamem_stream* s, slamem_stats* st, uint32_t min_mapq, int with_quals) {
+    if (!s || !st) { set_error("slamem_stream_set_stats: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (!is_map(s)) {
+        set_error("slamem_stream_set_stats: a table needs match type 7 (-paf) or 8 (-pile)");
+        return SLAMEM_ERR_ARG;
+    }
+    if (stats_device(st) != s->idx->device) {
+        set_error("slamem_stream_set_stats: the table lives on device %d, the stream's index on device %d", stats_device(st), s->idx->device);
+        return SLAMEM_ERR_ARG;
+    }
+    if (min_mapq > 60u) {
+        set_error("slamem_stream_set_stats: the minimum mapping quality is 0 to 60");
+        return SLAMEM_ERR_ARG;
+    }
+    if (has_batches(s, "slamem_stream_set_stats", "set the table")) return SLAMEM_ERR_ARG;
+    if (!s->idx->view.tpl) {
+        set_error("slamem_stream_set_stats: the substitution table takes the reference letters from the text planes of the index, and "
+                  "this index has none (the compact layout, or one built with the seed sections switched off)");
+        return SLAMEM_ERR_ARG;
+    }
+    s->stats = st;
+    s->stats_min_mapq = min_mapq;
+    s->stats_quals = with_quals != 0;
+    return SLAMEM_OK;
+}
+
 int slamem_stream_dups(slamem_stream* s, const uint8_t** flags_out) {
     if (!s || !flags_out) { set_error("slamem_stream_dups: null argument"); return SLAMEM_ERR_ARG; }
     std::unique_lock<std::mutex> lk(s->mu);
@@ -1141,8 +1176,9 @@ int slamem_stream_submit_quals(slamem_stream* s, const char* queries, const uint
                                uint32_t num_queries, uint32_t min_len) {
     if (!s || !offsets || (num_queries && (!queries || !quals))) { set_error("slamem_stream_submit_quals: null argument"); return SLAMEM_ERR_ARG; }
     if (min_len < 1) { set_error("slamem_stream_submit_quals: minimum MEM length must be >= 1"); return SLAMEM_ERR_ARG; }
-    if (!s->quals) {  // (set before the first batch, and never taken back)
-        set_error("slamem_stream_submit_quals: the stream's quality sums are not switched on (slamem_stream_set_quals)");
+    if (!s->quals && !s->stats_quals) {  // (set before the first batch, and never taken back)
+        set_error("slamem_stream_submit_quals: the stream's quality sums are not switched on (slamem_stream_set_quals, or "
+                  "slamem_stream_set_stats with its quality sections)");
         return SLAMEM_ERR_ARG;
     }
     static const uint8_t none = 0;  // (a batch without reads has no bytes; the pointer only says that the batch came this way)

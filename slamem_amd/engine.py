@@ -893,6 +893,139 @@ class Pileup:
             pass
 
 
+# -stats: the sections of the table as (first word, words), in the order of include/slamem_hip.h
+STATS_SECTIONS = {"totals": (0, 24), "mapq": (24, 64), "len": (88, 512), "nm": (600, 128), "cyc_aln": (728, 512), "cyc_mm": (1240, 512),
+                  "cyc_ins": (1752, 512), "cyc_del": (2264, 512), "sub": (2776, 16), "q_aln": (2792, 96), "q_mm": (2888, 96),
+                  "ins_len": (2984, 64), "del_len": (3048, 64)}
+STATS_WORDS = 3112  # SLAMEM_STATS_WORDS
+# the launch of the add (stats_filter.hip): lanes of a workgroup, a read each a trip; trips a workgroup makes at least; workgroups at most
+STATS_BLOCK, STATS_TRIPS, STATS_GRID = 256, 4, 1024
+
+
+class MapStats:
+    """slamem_stats_*: the mapping QC table (-stats), STATS_WORDS uint64 counters in the sections of
+    STATS_SECTIONS, added up on the GPU over every batch since creation or the last reset(), whatever the split into batches and
+    their order.  A read is counted when it is mapped and its mapq >= min_mapq; include/slamem_hip.h defines every section."""
+
+    def __init__(self, index: Index):
+        self.index = index
+        self._h = C.c_void_p()
+        capi.check(capi.lib().slamem_stats_create(index._h, C.byref(self._h)))
+        self.last_add_ms = 0.0  # device time of the last add's own kernel (the mapping in front of it not counted)
+
+    def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0, xdrop=None,
+            max_edits=None, min_mapq: int = 0, quals=None, phred_offset: int = 33):
+        """Maps the batch as Index.map_reads does and adds it to the table on the device: segments and operations are not
+        downloaded.  Returns the read records of map_reads (MAP_DTYPE).  quals: the batch's quality bytes, a uint8 array (numpy, or
+        a tensor on the index's device) of at least offsets[-1] bytes in which byte offsets[r] + i belongs to letter i of read r as
+        given, Phred + phred_offset (0 to 126); None: the sections q_aln and q_mm stay as they are."""
+        quals = self._check(offsets, min_mapq, quals, phred_offset)
+        return self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, None, True,
+                                    pile=(self, int(min_mapq), None, False, None if quals is None else (quals, int(phred_offset))))
+
+    def add_mapped(self, queries, offsets, result, min_mapq: int = 0, quals=None, phred_offset: int = 33) -> None:
+        """Adds a batch that is mapped already: result is what Index.map_reads returned for (queries, offsets) -- its first five
+        values are looked at."""
+        quals = self._check(offsets, min_mapq, quals, phred_offset)
+        dev = self.index.device
+        segs, roff, ops, ooff, reads = result[:5]
+        q = np.ascontiguousarray(np.frombuffer(queries, dtype=np.uint8) if isinstance(queries, (bytes, bytearray)) else queries, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        num = offsets.shape[0] - 1
+        if len(reads) != num or len(roff) != num + 1 or len(ooff) != len(segs) + 1:
+            raise ValueError("result is not the mapping of this batch: a record per read, read offsets, an operation offset per segment")
+
+        def up(a, dtype, pad):
+            raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            t = torch.zeros(raw.shape[0] + pad, dtype=torch.uint8, device=dev)
+            if raw.shape[0]:
+                t[: raw.shape[0]] = torch.from_numpy(raw.copy()).to(dev)
+            return t
+        abi = np.zeros(num, dtype=_MAP_ABI)
+        for f in ("s1", "s2", "strand", "mapq"):
+            abi[f] = reads[f]
+        seg5 = np.zeros((len(segs), 5), dtype=np.uint32)
+        for k, f in enumerate(("ref_pos", "query_pos", "ref_len", "query_len", "edits")):
+            seg5[:, k] = segs[f]
+        self._add_device(up(q, np.uint8, 16), up(offsets, np.uint64, 0), num, up(seg5, np.uint32, 20), up(np.asarray(roff, dtype=np.uint64), np.uint64, 0),
+                         up(np.asarray(ops, dtype=np.uint32), np.uint32, 4), up(np.asarray(ooff, dtype=np.uint64), np.uint64, 0), up(abi, _MAP_ABI, 12),
+                         int(min_mapq), quals=None if quals is None else (quals, int(phred_offset)))
+
+    def _check(self, offsets, min_mapq, quals, phred_offset):
+        if not 0 <= int(min_mapq) <= 60:
+            raise ValueError("min_mapq must be in [0, 60]")
+        if quals is None:
+            return None
+        need = int(np.asarray(offsets)[-1])
+        if isinstance(quals, torch.Tensor):
+            if quals.dtype != torch.uint8 or quals.device != self.index.device or not quals.is_contiguous():
+                raise ValueError("quals as a tensor: contiguous uint8 bytes on the index's device")
+        else:
+            quals = np.ascontiguousarray(np.frombuffer(quals, dtype=np.uint8) if isinstance(quals, (bytes, bytearray)) else quals)
+            if quals.dtype != np.uint8:
+                raise ValueError("quals must be a uint8 array")
+        if quals.shape[0] < need:
+            raise ValueError(f"quals has {quals.shape[0]} bytes, the batch's letters need {need}")
+        if not 0 <= int(phred_offset) <= 126:
+            raise ValueError("phred_offset must be in [0, 126]")
+        return quals
+
+    def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq, lowq=None, dedup=False, quals=None):
+        """The batch as it lies on the device (the signature of Pileup._add_device: Index._aln_like calls either).  quals: (bytes,
+        phred_offset)."""
+        dev = self.index.device
+        qb, off = None, 33
+        if quals is not None:
+            qb, off = quals
+            if not isinstance(qb, torch.Tensor):
+                t = torch.zeros(qb.shape[0] + 8, dtype=torch.uint8, device=dev)
+                if qb.shape[0]:
+                    t[: qb.shape[0]] = torch.from_numpy(qb if qb.flags.writeable else qb.copy()).to(dev)
+                qb = t
+        with torch.cuda.device(dev):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            rc = capi.lib().slamem_stats_add_device(self._h, _ptr(qd), _ptr(od), num, _ptr(segs), _ptr(roff), _ptr(ops), _ptr(ooff),
+                                                    _ptr(recs), _ptr(qb) if qb is not None else None, int(off), int(min_mapq),
+                                                    _stream_handle(dev))
+            t1.record()
+            capi.check(rc)
+            t1.synchronize()  # (the batch's tensors go when the caller returns)
+            self.last_add_ms = float(t0.elapsed_time(t1))
+
+    def raw(self) -> np.ndarray:
+        """The table: a uint64 array of STATS_WORDS.  The accumulator is left as it is."""
+        out = np.zeros(STATS_WORDS, dtype=np.uint64)
+        capi.check(capi.lib().slamem_stats_table_host(self._h, out.ctypes.data))
+        return out
+
+    def table(self) -> dict:
+        """The table by section: name -> a view of raw()."""
+        raw = self.raw()
+        return {k: raw[a: a + n] for k, (a, n) in STATS_SECTIONS.items()}
+
+    def add_table(self, raw) -> None:
+        """Adds another table (raw() of an accumulator, of another GPU for instance) to this one."""
+        t = np.ascontiguousarray(raw, dtype=np.uint64)
+        if t.shape != (STATS_WORDS,):
+            raise ValueError(f"a table has {STATS_WORDS} words")
+        capi.check(capi.lib().slamem_stats_add_table_host(self._h, t.ctypes.data))
+
+    def reset(self) -> None:
+        capi.check(capi.lib().slamem_stats_reset(self._h))
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h:
+            capi.lib().slamem_stats_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def event_letters(ev) -> bytes:
     """The inserted letters of one event (an element of Pileup.events()' array) as bytes; b"" for a deletion."""
     if int(ev["kind"]) != 1:
@@ -987,8 +1120,11 @@ class Stream:
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
                  max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False,
                  pile: "Pileup" = None, min_mapq: int = 0, md: bool = False, dedup: bool = False, quals: bool = False,
-                 phred_offset: int = 33):
-        """md=True (with paf=True): every batch also goes through the MD pass and mds() gives (md, md_offsets,
+                 phred_offset: int = 33, stats: "MapStats" = None):
+        """stats=<MapStats> (with paf=True or pile=<Pileup>): every batch is also added to the table on the device,
+        behind its map pass, counting the reads with mapq >= min_mapq; with quals=True the batches come through submit_quals and
+        their quality bytes feed the table's quality sections (on a pile= stream whose accumulator has quality sums, they feed both).
+        md=True (with paf=True): every batch also goes through the MD pass and mds() gives (md, md_offsets,
         seg_eq, primary) of the batch next() returned last, as Index.map_reads(md=True) appends them.
         dedup=True (with pile=<Pileup> made with dedup=True): every batch is added through the duplicate filter, in
         the order of the submits, and dups() gives the flags of the batch next() returned last.
@@ -1000,15 +1136,18 @@ class Stream:
         next() then returns the segments (ALN_DTYPE) in the place of the rows, alns() their operations.  paf=True: -paf mode
         (match type 7), the same with the offsets per READ and maps() the read records (MAP_DTYPE)."""
         self.pile = pile
-        if quals and pile is None:
-            raise ValueError("quals are the quality bytes of pile: it needs pile=<Pileup>")
+        self.stats = stats
+        if stats is not None and not (paf or pile is not None):
+            raise ValueError("stats is the table of the mappings: it needs paf=True or pile=<Pileup>")
+        if quals and pile is None and stats is None:
+            raise ValueError("quals are the quality bytes of pile and of stats: it needs pile=<Pileup> or stats=<MapStats>")
         if dedup and pile is None:
             raise ValueError("dedup is the duplicate filter of pile: it needs pile=<Pileup>")
         self.dedup = bool(dedup)
         if pile is not None and (aln or paf):
             raise ValueError("pile excludes aln and paf: one match type per search")
-        if min_mapq and pile is None:
-            raise ValueError("min_mapq is the threshold of pile: it needs pile=<Pileup>")
+        if min_mapq and pile is None and stats is None:
+            raise ValueError("min_mapq is the threshold of pile and of stats: it needs pile=<Pileup> or stats=<MapStats>")
         paf = bool(paf or pile is not None)
         if (aln or paf) and (mam or mum or smem or chain or ext or max_occ or (aln and paf)):
             raise ValueError("aln, paf and pile exclude mam, mum, smem, chain, ext and each other: one match type per search")
@@ -1040,8 +1179,12 @@ class Stream:
                 capi.check(capi.lib().slamem_stream_set_dedup(self._h, 1))
             if md:
                 capi.check(capi.lib().slamem_stream_set_md(self._h, 1))
-            if quals:
+            if quals and (stats is None or (pile is not None and pile.quality is not None)):
                 capi.check(capi.lib().slamem_stream_set_quals(self._h, int(phred_offset)))
+            elif quals and int(phred_offset) != 33:
+                raise ValueError("the quality bytes of a stats stream are Phred + 33 (another offset: an accumulator with quality sums)")
+            if stats is not None:
+                capi.check(capi.lib().slamem_stream_set_stats(self._h, stats._h, int(min_mapq), int(bool(quals))))
         except Exception:
             # a setter refused: the stream goes at once, while its index is alive -- not when the exception's traceback, which
             # holds this object, happens to be collected (by then the caller may have closed the index)
@@ -1067,7 +1210,7 @@ class Stream:
                                                           offsets.ctypes.data, offsets.shape[0] - 1, int(min_len)))
 
     def submit_quals(self, chars: np.ndarray, quals: np.ndarray, lowq, offsets: np.ndarray, min_len: int) -> None:
-        """submit for a -pile stream made with quals=True: quals is a uint8 array indexed as chars is -- byte
+        """submit for a stream made with quals=True (a -pile stream, DESIGN.md 4.27, or one with stats=): quals is a uint8 array indexed as chars is -- byte
         offsets[r] + i is the quality of letter i of record r, whatever offsets[0] is; lowq as in submit_masked, or None."""
         assert chars.dtype == np.uint8 and quals.dtype == np.uint8 and quals.flags.c_contiguous
         assert offsets.dtype == np.uint64 and offsets.flags.c_contiguous and quals.shape[0] >= int(offsets[-1])

@@ -703,6 +703,7 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-wq\twith -gt: every letter weighs with its own base quality in the likelihood of an SNV (a third accumulator on the GPU holds the sum of the qualities per row and letter); every SNV line gets ADQ, the quality sum per allele in AD's order; -err still scores the indel events and the letters of FASTA queries\n");
     printf("\t-fs\twith -sb: FILTER is sb for a line whose FS is above this whole number, 0 to 999, and PASS otherwise (default: FILTER stays .)\n");
     printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
+    printf("\t-stats\tmap the reads as -paf does and write the mapping statistics, added up on the GPU: totals (reads, mapped, strands, mismatch and indel rates), MAPQ, read lengths, edits per read, per-cycle and per-base-quality error tables, the substitution spectrum and indel lengths; -minq sets the least mapping quality of the reads that count\n");
     printf("\t-l\tminimum match length (default=20)\n");
     printf("\t-o\toutput file name (default=\"*-mems.txt\")\n");
     printf("\t-b\tprocess both forward and reverse strands\n");
@@ -747,6 +748,9 @@ typedef struct {
     slamem_index *gpus[16];
     int ngpu;
     slamem_pileup *piles[16];
+    int stats;             /* -stats: the mapping QC table; runs as -paf, nothing is formatted per read */
+    int stats_fasta;       /* ... a batch without quality bytes was submitted (said once) */
+    slamem_stats *tables[16]; /* ... one table per GPU */
     int strands; /* strand blocks per read */
     batch_range *ranges;
     size_t nranges, cap_ranges;
@@ -807,6 +811,7 @@ static int parse_and_refuse(run_t *R, int *status) {
         R->gtp.min_qual = (uint32_t)R->p.gt_qual;
     }
     R->wq = slh_parse_wq(argc, argv) && R->p.gt; /* (without -gt: refused above) */
+    R->stats = slh_parse_stats(argc, argv);
     R->gtp_wq = R->gtp;
     R->gtp_wq.match_cost = 0; R->gtp_wq.het_cost = 3010; R->gtp_wq.err_cost = 4771; /* round(10000 log10 2), round(10000 log10 3) */
     /* one table per GPU would miss the duplicates whose copies went to different GPUs */
@@ -857,7 +862,7 @@ static void load_inputs(run_t *R) {
     ld->masks = (uint64_t **)calloc((size_t)ld->cap + 1, sizeof(uint64_t *));
     if (!ld->masks) exit_message("Out of memory");
     ld->min_bq = R->p.min_bq;
-    ld->keep_quals = R->p.sam || R->wq;
+    ld->keep_quals = R->p.sam || R->wq || R->stats;
     ld->wq = R->wq;
     ld->wq_fill = 33 + R->p.gt_err;
     ld->quals = (char **)calloc((size_t)ld->cap + 1, sizeof(char *));
@@ -944,7 +949,7 @@ static void open_output(run_t *R) {
     if (t == 5) say(" ; mismatch penalty = %d ; X-drop = %d", pen, xdrop);
     if (t == 6 || t == 7 || t == 8)
         say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", gap, pen, xdrop, p->max_edits >= 0 ? p->max_edits : 31);
-    if (t == 8) say(" ; minimum mapping quality = %d", p->min_mapq);
+    if (t == 8 || R->stats) say(" ; minimum mapping quality = %d", p->min_mapq);
     if (p->bq_given == 1) say(" ; minimum base quality = %d", p->min_bq); /* (only when asked for: the line of a run without -bq stays) */
     if (p->gt) say(" ; minimum depth = %d ; ploidy = %d ; error rate = %d Phred ; prior = %d Phred ; minimum quality = %d", p->min_depth, p->gt_ploidy, p->gt_err, p->gt_hetq, p->gt_qual);
     else if (p->sites || p->vcf) say(" ; minimum depth = %d ; minimum share = %d %%", p->min_depth, p->min_pct);
@@ -1111,6 +1116,10 @@ static void open_streams(run_t *R) {
         if (rc == SLAMEM_OK && (t == 6 || t == 7 || t == 8))
             rc = slamem_stream_set_max_edits(s, p->max_edits >= 0 ? (uint32_t)p->max_edits : SLAMEM_ALN_EDITS_DEFAULT);
         if (rc == SLAMEM_OK && p->sam) rc = slamem_stream_set_md(s, 1); /* every batch also goes through the MD pass */
+        if (rc == SLAMEM_OK && R->stats) { /* one table per GPU: they are added up before the report */
+            rc = slamem_stats_create(R->gpus[g], &R->tables[g]);
+            if (rc == SLAMEM_OK) rc = slamem_stream_set_stats(s, R->tables[g], (uint32_t)p->min_mapq, 1);
+        }
         if (rc != SLAMEM_OK) pipeline_gpu_fail("setting up the search pipeline", rc);
         R->inflight[g] = 0;
     }
@@ -1127,10 +1136,13 @@ static void submit_batches(run_t *R, size_t *submitted) {
         const uint32_t nrec = (uint32_t)(br->last - br->first), min_len = (uint32_t)R->p.o.min_mem_len;
         /* -bq N on FASTQ reads: the set's mask is indexed as its letters, the stream takes the batch's words */
         /* -wq: the set's quality bytes beside its letters, indexed as they are */
-        const int rc = R->wq ? slamem_stream_submit_quals(s, qs->chars, (const uint8_t *)R->ld->quals[br->f], qmask, qs->offsets + br->first, nrec, min_len)
+        const char *sq = R->stats ? R->ld->quals[br->f] : NULL; /* -stats: a FASTQ set's bytes feed the quality sections */
+        const int rc = sq ? slamem_stream_submit_quals(s, qs->chars, (const uint8_t *)sq, NULL, qs->offsets + br->first, nrec, min_len)
+                     : R->wq ? slamem_stream_submit_quals(s, qs->chars, (const uint8_t *)R->ld->quals[br->f], qmask, qs->offsets + br->first, nrec, min_len)
                      : qmask ? slamem_stream_submit_masked(s, qs->chars, qmask, qs->offsets + br->first, nrec, min_len)
                              : slamem_stream_submit(s, qs->chars, qs->offsets + br->first, nrec, min_len);
         if (rc != SLAMEM_OK) pipeline_gpu_fail("MEM search on the GPU", rc);
+        if (R->stats && !sq) R->stats_fasta = 1;
         R->inflight[*submitted % (size_t)R->ngpu]++;
     }
 }
@@ -1151,7 +1163,7 @@ static int fetch_batch(run_t *R, size_t bi, batch_view *v) {
         join_warmup();
         exit(-1);
     }
-    if (t == 8) return 0;
+    if (t == 8 || R->stats) return 0; /* (-stats: the batch is in its GPU's table) */
     if (t == 5 && (rc = slamem_stream_mismatches(s, &v->mism)) != SLAMEM_OK) /* the fourth column of this batch's rows */
         pipeline_gpu_fail("MEM extension on the GPU", rc);
     if ((t == 6 || t == 7) && (rc = slamem_stream_alns(s, &v->segs, &v->ops, &v->ooff, &nops)) != SLAMEM_OK) /* the segments stand in the place of the rows */
@@ -1271,7 +1283,7 @@ static void run_batches(run_t *R) {
         if (!fetch_batch(R, bi, &v)) R->total_matches += (long long)v.total; /* (the segments piled) */
         R->inflight[bi % (size_t)R->ngpu]--;
         R->t_gpu += now_s() - tg; /* time the main thread waited for the GPUs */
-        if (R->p.o.match_type == 8) continue;
+        if (R->p.o.match_type == 8 || R->stats) continue;
         tg = now_s();
         format_batch(R, &v, (uint64_t)(br->last - br->first) * (uint64_t)R->strands);
         if (g_writer.failed) pipeline_fail("Cannot write output file");
@@ -1296,6 +1308,7 @@ static void check_loader(run_t *R) {
         exit_message(ld->invalid == 1 ? "A query file is not valid FASTQ" : ld->invalid ? "Out of memory" : "No query files provided");
     }
     if (ld->fasta_filled) fprintf(stderr, "> NOTE: option -wq: FASTA queries carry no base qualities: their letters count with the quality of -err, %d\n", R->p.gt_err);
+    if (R->stats_fasta) fprintf(stderr, "> NOTE: option -stats: FASTA queries carry no base qualities: the per-quality rows (BQ) count the FASTQ queries only\n");
     if (ld->fasta_seen) fprintf(stderr, "> WARNING: option -bq %d has no effect on FASTA queries: they carry no base qualities\n", R->p.min_bq);
 }
 
@@ -1704,6 +1717,22 @@ static void write_pileup(run_t *R) {
     }
 }
 
+/* -stats: the tables of GPUs 1.. are added into GPU 0's, and the report is written (nothing went through the writer thread) */
+static void write_stats(run_t *R) {
+    static uint64_t table[SLAMEM_STATS_WORDS];
+    const double t0 = now_s();
+    int g, rc = SLAMEM_OK;
+    if (g_nstreams == 0) memset(table, 0, sizeof(table));
+    for (g = 1; g < g_nstreams; g++) {
+        rc = slamem_stats_table_host(R->tables[g], table);
+        if (rc == SLAMEM_OK) rc = slamem_stats_add_table_host(R->tables[0], table);
+        if (rc != SLAMEM_OK) pipeline_gpu_fail("adding up the mapping statistics of the GPUs", rc);
+    }
+    if (g_nstreams && (rc = slamem_stats_table_host(R->tables[0], table)) != SLAMEM_OK) pipeline_gpu_fail("reading the mapping statistics from the GPU", rc);
+    if (slh_write_stats(table, R->out)) pipeline_fail("Cannot write output file");
+    R->t_format += now_s() - t0;
+}
+
 /* the last lines of stdout, the timing lines, and the end of the process */
 static int finish(run_t *R) {
     const slh_run *p = &R->p;
@@ -1721,7 +1750,7 @@ static int finish(run_t *R) {
         printf(":: Average %d %ss found per query sequence (total = %lld, avg size = %d bp)\n", (int)(R->total_matches / R->total_queries),
                MATCH_NAME(t), R->total_matches, (int)(R->total_matches ? R->total_sum / R->total_matches : 0));
     fflush(stdout);
-    printf("> Saving %ss to <%s> ... ", p->depth ? "depth run" : p->cons ? "consensus sequence" : p->vcf ? "variant call" : p->sites ? "variant site" : MATCH_NAME(t), R->out_name);
+    printf("> Saving %ss to <%s> ... ", R->stats ? "mapping statistic" : p->depth ? "depth run" : p->cons ? "consensus sequence" : p->vcf ? "variant call" : p->sites ? "variant site" : MATCH_NAME(t), R->out_name);
     if (fflush(R->out) != 0 || ferror(R->out)) exit_message("Cannot write output file");
     if (getenv("SLAMEM_FULL_TEARDOWN") != NULL && fclose(R->out) != 0) exit_message("Cannot write output file");
     t_end1 = now_s();
@@ -1747,6 +1776,7 @@ static int finish(run_t *R) {
         double a = now_s(), b, c, d;
         shutdown_pipeline();
         for (i = 0; i < 16 && t == 8; i++) slamem_pileup_free(R->piles[i]);
+        for (i = 0; i < 16; i++) slamem_stats_free(R->tables[i]);
         b = now_s();
         for (i = 0; i < R->ngpu; i++) slamem_index_free(R->gpus[i]);
         c = now_s();
@@ -1801,5 +1831,6 @@ int main(int argc, char **argv) {
     run_batches(R);
     check_loader(R);
     if (R->p.o.match_type == 8) write_pileup(R);
+    if (R->stats) write_stats(R);
     return finish(R);
 }

@@ -4,6 +4,7 @@
 #include "../../include/slamem_fisher.h"
 
 #include <limits.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <errno.h>
@@ -931,7 +932,7 @@ typedef struct {
     const char *refusal; /* of a bad value; a mode's: of another mode beside it */
 } option_row;
 enum { O_MEM, O_MAM, O_MUM, O_SMEM, O_OCC, O_CHAIN, O_MGAP, O_EXT, O_PEN, O_XDROP, O_ALN, O_MAXED, O_PAF, O_SAM, O_PILE, O_MINQ, O_BQ,
-       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_WQ, O_EVS,
+       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_WQ, O_EVS, O_STATS,
        O_L, O_O, O_B, O_N, O_M, O_R, O_V, O_S, O_C, NUM_OPTIONS };
 #define PEN_XDROP "Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"
 static const option_row OPTIONS[NUM_OPTIONS] = {
@@ -971,6 +972,7 @@ static const option_row OPTIONS[NUM_OPTIONS] = {
     [O_FS] = {"fs", 0, 0, V_INT, 0, 0, 999, -1, "Option -fs needs a whole number from 0 to 999"},
     [O_WQ] = {"wq", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
     [O_EVS] = {"evs", 0, 0, V_POW2, 0, 64, 1ull << 31, 0, "Option -evs needs a power of two of at least 64"},
+    [O_STATS] = {"stats", 0, 0, V_NONE, 7, 0, 0, 0, "Option -stats excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -sam, -pile, -sites, -vcf, -cons and -depth"},
     [O_L] = {"l", 0, 0, V_ATOI, 0, 0, 0, 20, NULL},
     [O_O] = {"o", 0, 0, V_INDEX, 0, 0, 0, -1, NULL},
     [O_B] = {"b", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
@@ -982,7 +984,7 @@ static const option_row OPTIONS[NUM_OPTIONS] = {
     [O_C] = {"c", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
 };
 /* the modes that exclude each other, beside -mam and -mum; a refusal names the last of them that is given */
-static const int MODES[] = {O_SMEM, O_CHAIN, O_EXT, O_ALN, O_PAF, O_PILE, O_SITES, O_VCF, O_CONS, O_DEPTH, O_SAM};
+static const int MODES[] = {O_SMEM, O_CHAIN, O_EXT, O_ALN, O_PAF, O_PILE, O_SITES, O_VCF, O_CONS, O_DEPTH, O_SAM, O_STATS};
 #define NUM_MODES ((int)(sizeof(MODES) / sizeof(MODES[0])))
 
 static char lower(char c) { return c >= 'A' && c <= 'Z' ? (char)(c + 32) : c; }
@@ -1113,6 +1115,7 @@ int slh_parse_sb_params(int argc, char **argv, int *fs_out) {
     return rc < 0 ? -1 : rc;
 }
 int slh_parse_wq(int argc, char **argv) { return has_option(argc, argv, O_WQ); }
+int slh_parse_stats(int argc, char **argv) { return has_option(argc, argv, O_STATS); }
 int slh_parse_dedup(int argc, char **argv, uint64_t *slots_out) {
     static const int ids[2] = {O_DEDUP, O_DSLOTS};
     uint64_t v[2];
@@ -1252,7 +1255,7 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     REFUSE_IF(edits < 0, OPTIONS[O_MAXED].refusal);
     REFUSE_IF(edits && t != 6 && t != 7 && t != 8, "Option -maxed needs -aln");
     REFUSE_IF(mapq < 0, OPTIONS[O_MINQ].refusal);
-    REFUSE_IF(mapq && t != 8, "Option -minq needs -pile");
+    REFUSE_IF(mapq && t != 8 && !has_option(argc, argv, O_STATS), "Option -minq needs -pile");
     REFUSE_IF(r->bq_given < 0, OPTIONS[O_BQ].refusal);
     REFUSE_IF(r->bq_given && t != 8, "Option -bq needs -pile");
     REFUSE_IF(sparams < 0, OPTIONS[sparams == -1 ? O_MDEP : O_MPCT].refusal);
@@ -1312,6 +1315,39 @@ void slh_free_options(slh_options *o) {
 /* ------------------------------------------------------------------------------------------------ */
 /* output                                                                                            */
 /* ------------------------------------------------------------------------------------------------ */
+
+/* -stats: the report of the table */
+int slh_write_stats(const uint64_t *t, FILE *f) {
+    static const char *const names[16] = {"reads", "mapped", "forward", "reverse", "counted", "counted split", "segments", "letters",
+                                          "counted letters", "matches", "mismatches", "insertions", "inserted letters", "deletions",
+                                          "deleted letters", "segment letters"};
+    /* histograms of one column: tag, first word, bins, whether the last bin folds */
+    static const struct { const char *tag; int first, bins, folds; } one[] = {{"MQ", 24, 64, 0}, {"RL", 88, 512, 1}, {"NM", 600, 128, 1}};
+    static const struct { const char *tag; int first; } lens[] = {{"IL", 2984}, {"DL", 3048}};
+    const uint64_t aligned = t[9] + t[10];
+    int k, i;
+    for (k = 0; k < 16; k++) fprintf(f, "SN\t%s\t%llu\n", names[k], (unsigned long long)t[k]);
+    fprintf(f, "SN\tclipped letters\t%llu\n", (unsigned long long)(t[8] > t[15] ? t[8] - t[15] : 0));
+    fprintf(f, "SN\tmismatch rate\t%.6f\n", aligned ? (double)t[10] / (double)aligned : 0.0);
+    fprintf(f, "SN\tindel rate\t%.6f\n", aligned ? (double)(t[11] + t[13]) / (double)aligned : 0.0);
+    for (k = 0; k < 3; k++)
+        for (i = 0; i < one[k].bins; i++)
+            if (t[one[k].first + i]) fprintf(f, "%s\t%d%s\t%llu\n", one[k].tag, i, one[k].folds && i == one[k].bins - 1 ? "+" : "", (unsigned long long)t[one[k].first + i]);
+    for (i = 0; i < 512; i++)
+        if (t[728 + i] | t[1240 + i] | t[1752 + i] | t[2264 + i])
+            fprintf(f, "CY\t%d%s\t%llu\t%llu\t%llu\t%llu\n", i, i == 511 ? "+" : "", (unsigned long long)t[728 + i], (unsigned long long)t[1240 + i],
+                    (unsigned long long)t[1752 + i], (unsigned long long)t[2264 + i]);
+    for (i = 0; i < 16; i++)
+        if (t[2776 + i]) fprintf(f, "SU\t%c\t%c\t%llu\n", "ACGT"[i >> 2], "ACGT"[i & 3], (unsigned long long)t[2776 + i]);
+    for (i = 0; i < 96; i++)
+        if (t[2792 + i] | t[2888 + i])
+            fprintf(f, "BQ\t%d\t%llu\t%llu\t%.2f\n", i, (unsigned long long)t[2792 + i], (unsigned long long)t[2888 + i],
+                    -10.0 * log10(((double)t[2888 + i] + 1.0) / ((double)t[2792 + i] + 2.0)));
+    for (k = 0; k < 2; k++)
+        for (i = 0; i < 64; i++)
+            if (t[lens[k].first + i]) fprintf(f, "%s\t%d%s\t%llu\n", lens[k].tag, i, i == 63 ? "+" : "", (unsigned long long)t[lens[k].first + i]);
+    return ferror(f) ? -1 : 0;
+}
 
 void slh_buffer_free(slh_buffer *b) {
     free(b->data);

@@ -135,6 +135,8 @@ int slh_parse_gt_params(int argc, char **argv, int *ploidy_out, int *err_out, in
 int slh_parse_sb_params(int argc, char **argv, int *fs_out);
 /* -wq (no value; needs -gt): whether it is there */
 int slh_parse_wq(int argc, char **argv);
+/* -stats (no value; a mode of its own that runs as -paf does and takes -minq): whether it is there */
+int slh_parse_stats(int argc, char **argv);
 /* -depth: is it given? */
 int slh_parse_depth(int argc, char **argv);
 /* -dedup and -dslots N, a power of two in [64, 2^32] (0): bit 0 of the result says that -dedup is there, bit 1 that -dslots is;
@@ -312,6 +314,18 @@ int slh_format_depth_windows(slh_buffer *buf, const char *record_name, uint64_t 
 /* -depth: the line of a record for stderr: "> Depth of NAME: L positions, C covered (P %), mean depth M", P = 10000 * C // L and
  * M = 100 * sum // L printed as above (both 0.00 for a record of no rows) */
 int slh_format_depth_summary(slh_buffer *buf, const char *record_name, uint64_t length, uint64_t covered, uint64_t sum);
+/* -stats: the report of a table of SLH_STATS_WORDS counters (the sections of include/slamem_hip.h), tab-separated,
+ * the first column a section tag; histogram rows whose counts are all zero are left out, and a last bin that takes every higher
+ * value prints its number with a `+`:
+ *   SN name value     the sixteen totals, then clipped letters (counted letters - segment letters) and, per aligned letter
+ *                     (matches + mismatches), mismatch rate and indel rate (insertions + deletions) as %.6f
+ *   MQ q n            RL len n (511+)            NM edits n (127+)
+ *   CY cycle aligned mismatches inserted deletions (511+)
+ *   SU ref read n     BQ q aligned mismatches empirical, empirical = -10 log10((mismatches + 1) / (aligned + 2)) as %.2f
+ *   IL len n (63+)    DL len n (63+)
+ * Returns 0, or -1 when the file reports an error. */
+#define SLH_STATS_WORDS 3112
+int slh_write_stats(const uint64_t *table, FILE *f);
 void slh_buffer_free(slh_buffer *b);
 /* make room for `bytes` more characters in one step (slh_format_block grows the buffer by doubling otherwise) */
 int slh_buffer_reserve(slh_buffer *b, size_t bytes);
