@@ -412,6 +412,12 @@ int slamem_find_exts_device(const slamem_index *idx, const void *queries_dev, co
  * are refused with SLAMEM_ERR_ARG as for -ext.  The workspace is slamem_find_alns_workspace_bytes() bytes. */
 #define SLAMEM_ALN_EDITS_DEFAULT 0xFFFFFFFFu
 #define SLAMEM_ALN_EDITS_MAX 127u
+/* Gap-affine costs (option -affine) travel in the upper 24 bits of every max_edits word: x per mismatch
+ * (1..31), o per gap opened (0..63), e per gap letter (1..31); a gap closes iff its cost is at most o + e * E, which may not
+ * exceed SLAMEM_ALN_COST_MAX.  Upper bits of zero: unit cost, as before; SLAMEM_ALN_EDITS_DEFAULT stays unit cost with 31. */
+#define SLAMEM_ALN_AFFINE(E, x, o, e) ((uint32_t)(E) | (uint32_t)(x) << 8 | (uint32_t)(o) << 16 | (uint32_t)(e) << 24)
+#define SLAMEM_ALN_COST_MAX 512u
+/* (include/slamem_aln_word.h decodes and checks such a word, for the library and its front end alike) */
 int slamem_find_alns_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
                                      uint64_t ops_capacity, uint32_t max_edits, uint64_t *bytes_out);
 int slamem_find_alns_device(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,

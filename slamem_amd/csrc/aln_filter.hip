@@ -15,6 +15,8 @@
 //                           points f[s][k] per edit count s and diagonal k = y - x, lanes hold the diagonals, the previous
 //                           wavefront in LDS, every wavefront in the workgroup's slab for the traceback; the slide is the
 //                           64-letter XOR compare.  The traceback needs f only: D[x][y] is the first s with f[s][k] >= x.
+//   k_aln_wave_affine       the same for gap-affine costs (-affine): three furthest-reaching components per score
+//                           s <= C = o + e E, earlier wavefronts read back from the workgroup's slab
 //   k_aln_count / 3 scans   runs, edits and segment starts per row -> places
 //   k_aln_segs / k_aln_write  block offsets, segment starts; a lane per row writes its runs (merged with the neighbours'), the
 //                           segment's rightmost row writes the segment
@@ -31,6 +33,30 @@ inline unsigned aln_wave_grid(uint32_t max_edits) {
     const uint64_t slab = (uint64_t)(max_edits + 1) * (2 * max_edits + 1) * 4, fit = (64ull << 20) / slab;
     return (unsigned)(fit > 8192 ? 8192 : fit < 256 ? 256 : fit);
 }
+// Gap-affine costs: the costs of a filter's max_edits word (resolve_filter_params has checked it), a workgroup's slab of three
+// components for the scores 0 .. C over the diagonals |k| <= E, and the grid by the same 64 MiB rule (C <= kAlnMaxCost bounds a
+// slab by 1.6 MB, so at least 41 workgroups fit; 1,286 at the default 31 edits and costs 4,6,2).
+inline AlnCosts aln_costs(uint32_t word) {
+    AlnCosts c;
+    int affine = 0;
+    (void)slamem_decode_aln_word(word, &c.E, &c.x, &c.o, &c.e, &affine);
+    c.affine = affine != 0;
+    c.C = c.o + c.e * c.E;
+    return c;
+}
+inline uint64_t aln_affine_slab_words(const AlnCosts& c) { return 3ull * (c.C + 1) * (2 * c.E + 1); }
+inline unsigned aln_affine_grid(const AlnCosts& c) {
+    const uint64_t fit = (64ull << 20) / (aln_affine_slab_words(c) * 4);
+    return (unsigned)(fit > 8192 ? 8192 : fit < 1 ? 1 : fit);
+}
+inline uint64_t aln_slabs_bytes(uint32_t word) {
+    const AlnCosts c = aln_costs(word);
+    return c.affine ? (uint64_t)aln_affine_grid(c) * aln_affine_slab_words(c) * 4
+                    : (uint64_t)aln_wave_grid(c.E) * (c.E + 1) * (2 * c.E + 1) * 4;
+}
+// Runs of an affine gap: every run but those of `=` costs at least min(x, e) >= 1 (L mismatches cost L x, a gap of L letters
+// o + L e), so there are at most C of them, and two runs of `=` have one of the others between them: at most 2 C + 1 runs.
+constexpr uint32_t kAffineRuns = 2 * kAlnMaxCost + 1;
 constexpr uint32_t kOpEq = 7u, kOpX = 8u, kOpI = 1u, kOpD = 2u;  // BAM's codes
 constexpr uint32_t kFirst = 1u, kLast = 2u, kClosed = 4u, kListed = 8u, kGapEq = 16u, kRev = 32u;
 constexpr int32_t kNeg = -1;
@@ -85,7 +111,7 @@ AlnLayout aln_layout(const FilterBatch& b, const FilterParams& p) {
     m.off_scan = off;   off = align_up(off + need, 256);
     m.off_segstart = off; off = align_up(off + (capacity + 2) * 4, 256);                // the rightmost row of every segment
     m.off_slab = off;   off = align_up(off + (ops_capacity + 1) * 4, 256);              // the runs of listed gaps
-    m.off_f = off;      off = align_up(off + (uint64_t)aln_wave_grid(max_edits) * (max_edits + 1) * (2 * max_edits + 1) * 4, 256);  // wavefronts
+    m.off_f = off;      off = align_up(off + aln_slabs_bytes(max_edits), 256);          // wavefronts
     m.bytes = off;
     return m;
 }
@@ -159,7 +185,7 @@ __global__ void __launch_bounds__(256) k_aln_geom(const uint64_t* __restrict__ c
                                                   uint64_t cap, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ uoff,
                                                   const QueryUnit* __restrict__ units, const TextPlanes* __restrict__ tpl, uint32_t n,
                                                   uint32_t strands, uint32_t penalty, uint32_t xdrop, uint32_t max_edits,
-                                                  AlnRow* __restrict__ rows, uint32_t* __restrict__ list, unsigned long long* __restrict__ ctr) {
+                                                  uint32_t cost_x, uint32_t inline_d, uint32_t cost_bound, AlnRow* __restrict__ rows, uint32_t* __restrict__ list, unsigned long long* __restrict__ ctr) {
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     uint64_t K = coff[nb];
     if (K > cap) K = cap;
@@ -213,8 +239,10 @@ __global__ void __launch_bounds__(256) k_aln_geom(const uint64_t* __restrict__ c
             // substitutions reach it, hence D = d.  The same holds for every pair of prefixes of one length (they have at most d
             // differing letters too), so D[x][x] = the differing letters in front of x, and the rule's diagonal step applies
             // at every cell of the diagonal.  (Three differing letters may cost 2: an inserted and a deleted letter.)
-            if (!bad && d <= 2u) {
-                if ((int64_t)d <= E) {
+            // With costs x, o, e leaving the diagonal costs at least 2 (o + e), so d x <= 2 (o + e) letters stay
+            // on it: inline_d = 2 (o + e) / x, closed iff d x <= C = o + e E.  Unit cost is x = 1, o = 0, e = 1: 2 and E, as above.
+            if (!bad && d <= inline_d) {
+                if (d * cost_x <= cost_bound) {
                     // runs of the mask: one per maximal stretch of equal bits
                     const uint64_t tr = (m ^ (m >> 1)) & low_mask(a - 1);
                     r.gapn = (uint32_t)__popcll(tr) + 1u;
@@ -418,6 +446,184 @@ __global__ void __launch_bounds__(64) k_aln_wave(const uint32_t* __restrict__ li
     }
 }
 
+// ---- a wave per listed gap, gap-affine costs -------------------------------------------------------------------
+
+// The furthest-reaching points of three matrices per score s = 0 .. C and diagonal k = y - x, |k| <= E: M[s][k] the largest x with
+// H[x][x + k] <= s, I and D the same for Im (the last step is a strand letter) and Dm (a text letter); -1: no such cell.  A score
+// holds cells on the diagonals |k| <= (s - o) / e only (k = 0 below o + e), and nothing at all when none of its three sources
+// s - x, s - o - e, s - e holds any: such a score is skipped, its part of the slab is never read (alive[]).  Earlier wavefronts are
+// up to max(x, o + e) scores back; they are read from the workgroup's slab, behind the barrier that ends every score.
+__global__ void __launch_bounds__(64) k_aln_wave_affine(const uint32_t* __restrict__ list, const unsigned long long* __restrict__ ctr_in,
+                                                        AlnRow* rows, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ uoff,
+                                                        const QueryUnit* __restrict__ units, const TextPlanes* __restrict__ tpl, uint32_t n,
+                                                        uint32_t max_edits, uint32_t cost_x, uint32_t cost_o, uint32_t cost_e, int32_t* fslab,
+                                                        uint32_t* __restrict__ slab, uint64_t slab_cap, unsigned long long* __restrict__ ctr) {
+    __shared__ uint32_t rbuf[kAffineRuns];       // the traceback's runs, last first
+    __shared__ uint8_t alive[kAlnMaxCost + 1];   // per score: some cell of some component exists (and the slab holds the score)
+    __shared__ unsigned long long s_off;
+    const uint32_t lane = threadIdx.x;
+    const int32_t E = (int32_t)max_edits, W = 2 * E + 1;
+    const int32_t X = (int32_t)cost_x, O = (int32_t)(cost_o + cost_e), G = (int32_t)cost_e, C = (int32_t)(cost_o + cost_e * max_edits);
+    const int64_t plane = (int64_t)(C + 1) * W;
+    int32_t* FM = fslab + (uint64_t)blockIdx.x * 3u * (uint64_t)plane;
+    int32_t* FI = FM + plane;
+    int32_t* FD = FI + plane;
+    // the diagonals of score sp: |k| <= kmax; a cell of the slab may be read iff it was written
+    auto kmax_of = [&](int32_t sp) -> int32_t {
+        if (sp < O) return 0;
+        const int32_t v = (sp - (int32_t)cost_o) / G;
+        return v < E ? v : E;
+    };
+    auto held = [&](int32_t sp, int32_t k) -> bool {
+        if (sp < 0 || sp > C || !alive[sp]) return false;
+        const int32_t km = kmax_of(sp);
+        return k >= -km && k <= km;
+    };
+    const uint64_t nl = ctr_in[3];
+    for (uint64_t li = blockIdx.x; li < nl; li += gridDim.x) {
+        const uint32_t g = list[li];
+        const AlnRow r = rows[g];
+        const Seqs sq = seqs_of(r.rec, (r.flags & kRev) != 0u, offsets, uoff, units, tpl, n);
+        const int64_t a = r.a, b = r.b;
+        const int64_t qa = (int64_t)r.tq - a, pb = (int64_t)r.tp - b;
+        bool bad = false;
+        for (int64_t w = lane; w * 64 < a; w += 64) {
+            const Win q = strand_window(sq.Q, sq.qn, sq.len, sq.rev, qa + 64 * w);
+            if (q.bad & low_mask(a - 64 * w)) bad = true;
+        }
+        for (int64_t w = lane; w * 64 < b; w += 64) {
+            const Win t = window(sq.T, sq.tn, sq.n, pb + 64 * w);
+            if (t.bad & low_mask(b - 64 * w)) bad = true;
+        }
+        // (nobody reads the last gap's LDS or slab any more: every lane stores the same alive[] and rbuf[] words, and reads them
+        // behind a barrier)
+        if (__syncthreads_or(bad ? 1 : 0)) continue;
+        const int32_t kfin = (int32_t)(b - a);
+        int32_t s = 0;
+        bool closed = false;
+        for (;; s++) {
+            const int32_t sx = s - X, so = s - O, sg = s - G;
+            const bool sources = s == 0 || (sx >= 0 && alive[sx]) || (so >= 0 && alive[so]) || (sg >= 0 && alive[sg]);
+            if (!sources) {  // (uniform: alive[] is the same for every lane)
+                alive[s] = 0;
+                if (s == C) break;
+                continue;
+            }
+            const int32_t km = kmax_of(s);
+            bool fin = false, live = false;
+            for (int32_t d = E - km + (int32_t)lane; d <= E + km; d += 64) {
+                const int32_t k = d - E;
+                int64_t ci = kNeg, cd = kNeg, c = kNeg;
+                if (s == 0) {
+                    c = 0;
+                } else {
+                    {  // a strand letter: from diagonal k + 1, x + 1; it opens a gap behind M or goes on in I
+                        int64_t src = held(so, k + 1) ? FM[(int64_t)so * W + d + 1] : kNeg;
+                        const int64_t go = held(sg, k + 1) ? FI[(int64_t)sg * W + d + 1] : kNeg;
+                        if (go > src) src = go;
+                        if (src >= 0) {
+                            const int64_t v = src + 1 < a ? src + 1 : a, least = -k - 1 > 0 ? -k - 1 : 0;
+                            if (v - 1 >= least) ci = v;
+                        }
+                    }
+                    {  // a text letter: from diagonal k - 1, x stays
+                        int64_t src = held(so, k - 1) ? FM[(int64_t)so * W + d - 1] : kNeg;
+                        const int64_t go = held(sg, k - 1) ? FD[(int64_t)sg * W + d - 1] : kNeg;
+                        if (go > src) src = go;
+                        if (src >= 0) {
+                            const int64_t v = src < b - k ? src : b - k, least = 1 - k > 0 ? 1 - k : 0;
+                            if (v >= least) cd = v;
+                        }
+                    }
+                    const int64_t fk = held(sx, k) ? FM[(int64_t)sx * W + d] : kNeg;
+                    if (fk >= 0) {  // one more letter of both, or none at an end
+                        c = fk + 1;
+                        if (c > a) c = a;
+                        if (c > b - k) c = b - k;
+                    }
+                    if (ci > c) c = ci;
+                    if (cd > c) c = cd;
+                }
+                if (c >= 0) {
+                    const int64_t lim = a - c < b - (c + k) ? a - c : b - (c + k);
+                    if (lim > 0) c += slide_fwd(sq, qa, pb, c, c + k, lim);
+                }
+                FM[(int64_t)s * W + d] = (int32_t)c;
+                FI[(int64_t)s * W + d] = (int32_t)ci;
+                FD[(int64_t)s * W + d] = (int32_t)cd;
+                if (c >= 0 || ci >= 0 || cd >= 0) live = true;
+                if (k == kfin && c >= a) fin = true;
+            }
+            const bool any_live = __ballot(live) != 0ull, any_fin = __ballot(fin) != 0ull;
+            alive[s] = any_live ? 1 : 0;
+            __syncthreads();  // the score's cells are in the slab (and alive[s] in LDS) for every lane
+            if (any_fin) { closed = true; break; }
+            if (s == C) break;
+        }
+        if (!closed) continue;
+        // The traceback of 4.29 from the stored points, uniform in the wave as k_aln_wave's: in state H the diagonal step on equal
+        // letters (a slide backwards), X iff M[s - x][k] >= x - 1, else state D iff D[s][k] >= x, else state I; in state D a text
+        // letter, and back to H iff M[s - o - e][k - 1] >= x, else s - e; state I the same with k + 1 and x - 1.
+        bool overrun = false;
+        int64_t x = a, y = b;
+        int32_t sc = s;
+        uint32_t state = 0, nr = 0, code = 0, len = 0, ned = 0;
+        while (x > 0 || y > 0) {
+            uint32_t op;
+            const int32_t k = (int32_t)(y - x);
+            if (state == 0u) {
+                if (x > 0 && y > 0) {
+                    const int64_t run = slide_back(sq, qa, pb, x, y, x < y ? x : y);
+                    if (run) {
+                        if (code != kOpEq) { if (len) rbuf[nr++] = (len << 4) | code; code = kOpEq; len = 0; }
+                        len += (uint32_t)run;
+                        x -= run;
+                        y -= run;
+                        if (nr >= kAffineRuns - 1u) { overrun = true; break; }
+                        continue;
+                    }
+                }
+                const int32_t m_same = held(sc - X, k) ? FM[(int64_t)(sc - X) * W + k + E] : kNeg;
+                if (x > 0 && y > 0 && m_same >= 0 && (int64_t)m_same >= x - 1) { op = kOpX; x--; y--; sc -= X; }
+                else {
+                    const int32_t d_here = held(sc, k) ? FD[(int64_t)sc * W + k + E] : kNeg;
+                    state = (y > 0 && (x == 0 || (d_here >= 0 && (int64_t)d_here >= x))) ? 1u : 2u;
+                    continue;
+                }
+            } else if (state == 1u) {
+                const int32_t m_open = held(sc - O, k - 1) ? FM[(int64_t)(sc - O) * W + k - 1 + E] : kNeg;
+                op = kOpD;
+                if (m_open >= 0 && (int64_t)m_open >= x) { sc -= O; state = 0u; } else { sc -= G; }
+                y--;
+            } else {
+                const int32_t m_open = held(sc - O, k + 1) ? FM[(int64_t)(sc - O) * W + k + 1 + E] : kNeg;
+                op = kOpI;
+                if (m_open >= 0 && (int64_t)m_open >= x - 1) { sc -= O; state = 0u; } else { sc -= G; }
+                x--;
+            }
+            ned++;
+            if (code != op) { if (len) rbuf[nr++] = (len << 4) | code; code = op; len = 0; }
+            len++;
+            if (nr >= kAffineRuns - 1u || sc < 0 || x < 0 || y < 0) { overrun = true; break; }  // (never, by the count of runs; if it were, the gap is left broken)
+        }
+        if (overrun) continue;  // (uniform)
+        if (len) rbuf[nr++] = (len << 4) | code;
+        if (lane == 0u) s_off = atomicAdd(&ctr[4], (unsigned long long)nr);
+        __syncthreads();
+        const uint64_t at = s_off;
+        if (at + nr <= slab_cap)
+            for (uint32_t t = lane; t < nr; t += 64u) slab[at + t] = rbuf[nr - 1u - t];
+        if (lane == 0u) {
+            AlnRow* o = rows + g;
+            o->gapn = nr;
+            o->gapd = ned;
+            o->slab = (uint32_t)(at < 0xFFFFFFFFull ? at : 0xFFFFFFFFull);
+            o->flags = r.flags | kClosed | ((nr && (rbuf[0] & 15u) == kOpEq) ? kGapEq : 0u);
+        }
+        __syncthreads();  // rbuf[] and s_off are read before the next gap's traceback stores to them
+    }
+}
+
 // ---- places ------------------------------------------------------------------------------------------------------------------
 
 // a row's anchor goes into the run of the row to its left when its gap is closed and empty
@@ -545,6 +751,7 @@ int aln_after_chain(void* ws, const FilterBatch& b, const FilterParams& args, ui
     const uint64_t num_queries = b.num_queries, num_blocks = b.num_blocks(), capacity = b.capacity;
     const uint32_t strands = b.strands;
     const AlnLayout m = aln_layout(b, args);
+    const AlnCosts costs = aln_costs(args.max_edits);
     char* p = static_cast<char*>(ws);
     unsigned long long* ctr = reinterpret_cast<unsigned long long*>(p + m.off_ctr);
     slamem_mem* crows = reinterpret_cast<slamem_mem*>(p + m.off_crows);
@@ -571,12 +778,19 @@ int aln_after_chain(void* ws, const FilterBatch& b, const FilterParams& args, ui
     if (num_blocks) {
         hipLaunchKernelGGL(k_aln_geom, dim3(grid_for(capacity)), dim3(256), 0, stream, (const uint64_t*)coff, num_blocks,
                            (const slamem_mem*)crows, capacity, offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n,
-                           strands, args.penalty, args.xdrop, args.max_edits, rows, list, ctr);
+                           strands, args.penalty, args.xdrop, costs.E, costs.x, 2u * (costs.o + costs.e) / costs.x, costs.C, rows, list, ctr);
         ASTEP(hipGetLastError(), "k_aln_geom");
-        hipLaunchKernelGGL(k_aln_wave, dim3(aln_wave_grid(args.max_edits)), dim3(64), 0, stream, (const uint32_t*)list, (const unsigned long long*)ctr, rows,
-                           offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n, args.max_edits, fslab, slab,
-                           args.ops_capacity, ctr);
-        ASTEP(hipGetLastError(), "k_aln_wave");
+        if (costs.affine) {
+            hipLaunchKernelGGL(k_aln_wave_affine, dim3(aln_affine_grid(costs)), dim3(64), 0, stream, (const uint32_t*)list,
+                               (const unsigned long long*)ctr, rows, offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n,
+                               costs.E, costs.x, costs.o, costs.e, fslab, slab, args.ops_capacity, ctr);
+            ASTEP(hipGetLastError(), "k_aln_wave_affine");
+        } else {
+            hipLaunchKernelGGL(k_aln_wave, dim3(aln_wave_grid(costs.E)), dim3(64), 0, stream, (const uint32_t*)list, (const unsigned long long*)ctr, rows,
+                               offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n, costs.E, fslab, slab,
+                               args.ops_capacity, ctr);
+            ASTEP(hipGetLastError(), "k_aln_wave");
+        }
     }
     hipLaunchKernelGGL(k_aln_count, dim3(grid_for(capacity + 2)), dim3(256), 0, stream, (const uint64_t*)coff, num_blocks, capacity,
                        (const AlnRow*)rows, nruns, flag, ed);

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "../../include/slamem_hip.h"
+#include "../../include/slamem_aln_word.h"
 
 namespace slamem {
 
@@ -326,6 +327,16 @@ struct FilterParams {
 };
 constexpr uint32_t kChainDefaultGap = 5000, kExtDefaultPenalty = 4, kExtDefaultXdrop = 20, kAlnDefaultEdits = 31;
 constexpr uint32_t kExtXdropUnset = 0xFFFFFFFFu, kAlnEditsUnset = 0xFFFFFFFFu, kAlnMaxEdits = 127;
+// The max_edits word of the public interface, decoded (SLAMEM_ALN_AFFINE): E, the costs of a mismatch, of a gap
+// opened and of a gap letter, the bound C = o + e E on a gap's cost, and whether the word carries costs (else 1, 0, 1: unit cost).
+constexpr uint32_t kAlnMaxCost = 512;
+struct AlnCosts {
+    uint32_t E, x, o, e, C;
+    bool affine;
+    uint32_t word() const { return affine ? E | x << 8 | o << 16 | e << 24 : E; }  // the default resolved
+};
+// The one check of such a word (kAlnEditsUnset: the default): SLAMEM_OK and *out, or SLAMEM_ERR_ARG with `who` in the message.
+int decode_aln_word(const char* who, uint32_t word, AlnCosts* out);
 // The placeholders (0: no cap, kChainDefaultGap, kExtDefaultPenalty; kExtXdropUnset; kAlnEditsUnset) -> values, the outputs null.
 // SLAMEM_ERR_ARG, with `who` in the message: a gap of 2^31 or more, more than kAlnMaxEdits edits.
 int resolve_filter_params(const char* who, uint32_t max_occ, uint32_t max_gap, uint32_t penalty, uint32_t xdrop, uint32_t max_edits,

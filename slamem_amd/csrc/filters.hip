@@ -38,14 +38,27 @@ int resolve_filter_params(const char* who, uint32_t max_occ, uint32_t max_gap, u
         set_error("%s: the maximum gap must be below 2^31 (0: the default, %u)", who, kChainDefaultGap);
         return SLAMEM_ERR_ARG;
     }
-    if (max_edits == kAlnEditsUnset) max_edits = kAlnDefaultEdits;
-    if (max_edits > kAlnMaxEdits) {
-        set_error("%s: at most %u edits a gap (SLAMEM_ALN_EDITS_DEFAULT: the default, %u)", who, kAlnMaxEdits, kAlnDefaultEdits);
-        return SLAMEM_ERR_ARG;
-    }
+    AlnCosts c;
+    if (int bad = decode_aln_word(who, max_edits, &c)) return bad;
     *out = FilterParams{max_occ, max_gap ? max_gap : kChainDefaultGap, penalty ? penalty : kExtDefaultPenalty,
-                        xdrop == kExtXdropUnset ? kExtDefaultXdrop : xdrop, max_edits, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr};
+                        xdrop == kExtXdropUnset ? kExtDefaultXdrop : xdrop, c.word(), nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr};
     return SLAMEM_OK;
+}
+
+int decode_aln_word(const char* who, uint32_t word, AlnCosts* out) {
+    int affine = 0;
+    const int bad = slamem_decode_aln_word(word, &out->E, &out->x, &out->o, &out->e, &affine);
+    out->affine = affine != 0;
+    out->C = out->o + out->e * out->E;
+    switch (bad) {
+    case 0: return SLAMEM_OK;
+    case 1: set_error("%s: at most %u edits a gap (SLAMEM_ALN_EDITS_DEFAULT: the default, %u)", who, kAlnMaxEdits, kAlnDefaultEdits); break;
+    case 2: set_error("%s: the cost of a mismatch is %u, outside 1 to 31 (SLAMEM_ALN_AFFINE)", who, out->x); break;
+    case 3: set_error("%s: the cost of a gap opened is %u, above 63 (SLAMEM_ALN_AFFINE)", who, out->o); break;
+    case 4: set_error("%s: the cost of a gap letter is %u, outside 1 to 31 (SLAMEM_ALN_AFFINE)", who, out->e); break;
+    default: set_error("%s: the bound on a gap's cost, o + e E = %u + %u * %u, is above %u", who, out->o, out->e, out->E, kAlnMaxCost); break;
+    }
+    return SLAMEM_ERR_ARG;
 }
 
 void filter_list_buffers(void* ws, uint64_t num_blocks, uint64_t capacity, slamem_mem** rows_out, uint64_t** boff_out) {

@@ -3632,11 +3632,12 @@ int SearchJob::init(const slamem_index* idx_, const void* queries_dev_, const ui
             set_error("%s", filter->limits);
             return SLAMEM_ERR_ARG;
         }
-        if (segments && (!params.op_offsets || (!params.segs && params.segs_capacity) || (!params.ops && params.ops_capacity) ||
-                         params.max_edits > kAlnMaxEdits)) {
-            set_error("slamem_find_alns_device: null argument, or more than %u edits a gap", kAlnMaxEdits);
+        if (segments && (!params.op_offsets || (!params.segs && params.segs_capacity) || (!params.ops && params.ops_capacity))) {
+            set_error("slamem_find_alns_device: null argument");
             return SLAMEM_ERR_ARG;
         }
+        AlnCosts costs;
+        if (segments && decode_aln_word("slamem_find_alns_device", params.max_edits, &costs) != SLAMEM_OK) return SLAMEM_ERR_ARG;
         match_type = 0;
         need_ws += filter->workspace_bytes(batch, params);
     }

@@ -977,10 +977,8 @@ int slamem_stream_set_max_edits(slamem_stream* s, uint32_t max_edits) {
         set_error("slamem_stream_set_max_edits: an edit limit needs match type 6 (-aln)");
         return SLAMEM_ERR_ARG;
     }
-    if (max_edits != kAlnEditsUnset && max_edits > kAlnMaxEdits) {
-        set_error("slamem_stream_set_max_edits: at most %u edits a gap", kAlnMaxEdits);
-        return SLAMEM_ERR_ARG;
-    }
+    AlnCosts costs;
+    if (decode_aln_word("slamem_stream_set_max_edits", max_edits, &costs) != SLAMEM_OK) return SLAMEM_ERR_ARG;
     if (has_batches(s, "slamem_stream_set_max_edits", "set the limit")) return SLAMEM_ERR_ARG;
     s->max_edits = max_edits;
     return SLAMEM_OK;

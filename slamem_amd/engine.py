@@ -295,18 +295,20 @@ class Index:
         return self._find(queries, offsets, min_len, both_strands, False, False, False, 0, False, 0, True, penalty, xdrop)
 
     def find_alns(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-                  xdrop=None, max_edits=None, capacities=None):
+                  xdrop=None, max_edits=None, capacities=None, gap_costs=None):
         """-aln mode: (segments, block_offsets, ops, op_offsets) -- per strand block the gapped alignment built on its best
         chain.  segments: a structured array (ref_pos, query_pos, ref_len, query_len, edits), the segments
         of a block with the query start descending; block_offsets: per strand block; ops: uint32 CIGAR operations, length << 4
         | code with BAM's codes (CIGAR_OPS), left to right in the scanned strand; op_offsets: per segment.  max_gap, penalty
         and xdrop as for find_chains and find_exts; max_edits: the most edits in one gap (None: 31; at most 127).
+        gap_costs=(x, o, e): the gaps are closed at gap-affine cost (aln_word); None: unit cost.
         capacities: (mems, segments, operations) to run with exactly that room (slamem.capi.SlamemError with
         SLAMEM_ERR_CAPACITY and .totals = what is needed when it is too small); None: grow until the batch fits."""
-        return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, False)
+        return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, aln_word(max_edits, gap_costs), capacities,
+                              False)
 
     def map_reads(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-                  xdrop=None, max_edits=None, capacities=None, md: bool = False):
+                  xdrop=None, max_edits=None, capacities=None, md: bool = False, gap_costs=None):
         """-paf mode: (segments, read_offsets, ops, op_offsets, reads) -- one mapping per read.  Per read the
         strand block whose best chain scores highest is the primary one (the forward block on a tie) and only that block is
         aligned, as find_alns aligns it; segments, ops and op_offsets are as find_alns returns them, in the coordinates of the
@@ -317,7 +319,8 @@ class Index:
         all segments, uint32 `m << 4 | d << 2 | c` and a closing `m << 4 | 8` per segment (md_text makes the tag of one segment's),
         their offsets per segment, the letters under = per segment, and per read the index of its primary segment within the
         read's range (0xFFFFFFFF: the read has no segment)."""
-        return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, True, md=md)
+        return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, aln_word(max_edits, gap_costs), capacities,
+                              True, md=md)
 
     def _md_pass(self, segs, nseg, roff, num, ops, ooff, cap):
         """slamem_maps_md_device over a mapped batch as it lies on the device, with room for cap entries: (md, md_offsets, seg_eq,
@@ -438,6 +441,21 @@ class Index:
 XDROP_DEFAULT = 0xFFFFFFFF  # SLAMEM_EXT_XDROP_DEFAULT: "the default drop" in the C ABI (0 is a drop of its own)
 
 
+def aln_word(max_edits=None, gap_costs=None):
+    """The max_edits word of the C ABI (SLAMEM_ALN_AFFINE).  gap_costs=None: max_edits as it is given (unit
+    cost).  gap_costs=(x, o, e): the cost of a mismatch (1 to 31), of a gap opened (0 to 63) and of a gap letter (1 to 31) in the
+    upper 24 bits, above max_edits (None: 31); a gap then closes when its cost is at most o + e * max_edits (at most 512)."""
+    if gap_costs is None:
+        return max_edits
+    x, o, e = (int(v) for v in gap_costs)
+    E = 31 if max_edits is None else int(max_edits)
+    if not (0 <= E <= 127 and 1 <= x <= 31 and 0 <= o <= 63 and 1 <= e <= 31):
+        raise ValueError("gap_costs=(x, o, e) needs 1 <= x <= 31, 0 <= o <= 63, 1 <= e <= 31, and max_edits in [0, 127]")
+    if o + e * E > 512:
+        raise ValueError(f"gap_costs: the bound on a gap's cost, o + e * max_edits = {o + e * E}, is above 512")
+    return E | x << 8 | o << 16 | e << 24
+
+
 def _xdrop_arg(xdrop) -> int:
     return XDROP_DEFAULT if xdrop is None else int(xdrop)
 
@@ -547,7 +565,8 @@ class Pileup:
             self.forward = self._view(h)
 
     def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-            xdrop=None, max_edits=None, min_mapq: int = 0, lowq=None, dedup: bool = False, quals=None, phred_offset: int = 33):
+            xdrop=None, max_edits=None, min_mapq: int = 0, lowq=None, dedup: bool = False, quals=None, phred_offset: int = 33,
+            gap_costs=None):
         """Maps the batch as Index.map_reads does and adds the mappings of the reads with mapq >= min_mapq (0 to 60) to the table,
         on the device: segments and operations are not downloaded.  Returns the read records of map_reads (MAP_DTYPE).  lowq: the
         batch's low-quality mask (DESIGN.md 4.21), a uint64 array of at least (offsets[-1] + 63) // 64 words (numpy, or a tensor on
@@ -584,7 +603,7 @@ class Pileup:
                     raise ValueError("lowq must be a uint64 array")
             if lowq.shape[0] < need:
                 raise ValueError(f"lowq has {lowq.shape[0]} words, the batch's letters need {need}")
-        recs = self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, None, True,
+        recs = self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, aln_word(max_edits, gap_costs), None, True,
                                     pile=(self, int(min_mapq), lowq, bool(dedup), None if quals is None else (quals, int(phred_offset))))
         return (recs, self.last_dup) if dedup else recs
 
@@ -914,13 +933,13 @@ class MapStats:
         self.last_add_ms = 0.0  # device time of the last add's own kernel (the mapping in front of it not counted)
 
     def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0, xdrop=None,
-            max_edits=None, min_mapq: int = 0, quals=None, phred_offset: int = 33):
+            max_edits=None, min_mapq: int = 0, quals=None, phred_offset: int = 33, gap_costs=None):
         """Maps the batch as Index.map_reads does and adds it to the table on the device: segments and operations are not
         downloaded.  Returns the read records of map_reads (MAP_DTYPE).  quals: the batch's quality bytes, a uint8 array (numpy, or
         a tensor on the index's device) of at least offsets[-1] bytes in which byte offsets[r] + i belongs to letter i of read r as
         given, Phred + phred_offset (0 to 126); None: the sections q_aln and q_mm stay as they are."""
         quals = self._check(offsets, min_mapq, quals, phred_offset)
-        return self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, None, True,
+        return self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, aln_word(max_edits, gap_costs), None, True,
                                     pile=(self, int(min_mapq), None, False, None if quals is None else (quals, int(phred_offset))))
 
     def add_mapped(self, queries, offsets, result, min_mapq: int = 0, quals=None, phred_offset: int = 33) -> None:
@@ -1120,8 +1139,10 @@ class Stream:
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
                  max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False,
                  pile: "Pileup" = None, min_mapq: int = 0, md: bool = False, dedup: bool = False, quals: bool = False,
-                 phred_offset: int = 33, stats: "MapStats" = None):
-        """stats=<MapStats> (with paf=True or pile=<Pileup>): every batch is also added to the table on the device,
+                 phred_offset: int = 33, stats: "MapStats" = None, gap_costs=None):
+        """gap_costs=(x, o, e) (with aln, paf or pile): the gaps of every batch are closed at gap-affine cost, as
+        Index.find_alns(gap_costs=) closes them.
+        stats=<MapStats> (with paf=True or pile=<Pileup>): every batch is also added to the table on the device,
         behind its map pass, counting the reads with mapq >= min_mapq; with quals=True the batches come through submit_quals and
         their quality bytes feed the table's quality sections (on a pile= stream whose accumulator has quality sums, they feed both).
         md=True (with paf=True): every batch also goes through the MD pass and mds() gives (md, md_offsets,
@@ -1153,6 +1174,9 @@ class Stream:
             raise ValueError("aln, paf and pile exclude mam, mum, smem, chain, ext and each other: one match type per search")
         if max_edits is not None and not (aln or paf):
             raise ValueError("max_edits is the edit limit of aln and paf: it needs aln=True or paf=True")
+        if gap_costs is not None and not (aln or paf):
+            raise ValueError("gap_costs are the costs of aln and paf: it needs aln=True, paf=True or pile=<Pileup>")
+        max_edits = aln_word(max_edits, gap_costs)
         if md and not (paf and pile is None):
             raise ValueError("md is the MD pass of paf: it needs paf=True")
         self.paf = bool(paf)

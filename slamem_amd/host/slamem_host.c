@@ -2,6 +2,7 @@
  * front end.  Plain C, no GPU code; see slamem_host.h for the reference lines each piece restates. */
 #include "slamem_host.h"
 #include "../../include/slamem_fisher.h"
+#include "../../include/slamem_aln_word.h"
 
 #include <limits.h>
 #include <math.h>
@@ -919,20 +920,21 @@ int slh_parse_argument(int argc, char **argv, const char *optionchars, int parse
  * one-letter row: when it is exactly two characters long) and the third-letter rule holds.  Everything that has to know an
  * option reads it here: which arguments are file names (slh_parse_options), the value and its range (option_value), the
  * refusal of a bad value and of a second mode (slh_parse_run). */
-enum { V_NONE, V_INT, V_POW2, V_DIGITS, V_LEVELS, V_ATOI, V_INDEX, V_STRING };
+enum { V_NONE, V_INT, V_POW2, V_DIGITS, V_LEVELS, V_COSTS, V_ATOI, V_INDEX, V_STRING };
 typedef struct {
     const char *name;   /* as usage() spells it; "l": a one-letter option */
     char third, unless; /* third != 0: the third letter is name[2] (-maxed, -dedup); unless: the third letter is not this one (-mam, -depth) */
     char kind;          /* V_NONE: no value.  V_INT: strtol's whole number in [lo, hi]; V_POW2: such a power of two; V_DIGITS: a number
-                           that begins with a digit; V_LEVELS: 1 to 16 of those, ascending, with commas; V_ATOI, V_INDEX, V_STRING: the
-                           reference's -l and -m (atoi), -o and -v (where the value stands) and -r */
+                           that begins with a digit; V_LEVELS: 1 to 16 of those, ascending, with commas; V_COSTS: three of those with
+                           commas, X in 1..31, O in 0..63, E in 1..31, handed out as X | O << 8 | E << 16; V_ATOI, V_INDEX, V_STRING:
+                           the reference's -l and -m (atoi), -o and -v (where the value stands) and -r */
     char mode;          /* the match type the option selects (0: none) */
     uint64_t lo, hi;
     long long dflt;     /* what the entry points hand out when the option is absent */
     const char *refusal; /* of a bad value; a mode's: of another mode beside it */
 } option_row;
 enum { O_MEM, O_MAM, O_MUM, O_SMEM, O_OCC, O_CHAIN, O_MGAP, O_EXT, O_PEN, O_XDROP, O_ALN, O_MAXED, O_PAF, O_SAM, O_PILE, O_MINQ, O_BQ,
-       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_WQ, O_EVS, O_STATS,
+       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_WQ, O_EVS, O_STATS, O_AFFINE,
        O_L, O_O, O_B, O_N, O_M, O_R, O_V, O_S, O_C, NUM_OPTIONS };
 #define PEN_XDROP "Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"
 static const option_row OPTIONS[NUM_OPTIONS] = {
@@ -973,6 +975,7 @@ static const option_row OPTIONS[NUM_OPTIONS] = {
     [O_WQ] = {"wq", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
     [O_EVS] = {"evs", 0, 0, V_POW2, 0, 64, 1ull << 31, 0, "Option -evs needs a power of two of at least 64"},
     [O_STATS] = {"stats", 0, 0, V_NONE, 7, 0, 0, 0, "Option -stats excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -sam, -pile, -sites, -vcf, -cons and -depth"},
+    [O_AFFINE] = {"affine", 0, 0, V_COSTS, 0, 0, 0, -1, "Option -affine needs three whole numbers X,O,E: X from 1 to 31, O from 0 to 63, E from 1 to 31, separated by commas"},
     [O_L] = {"l", 0, 0, V_ATOI, 0, 0, 0, 20, NULL},
     [O_O] = {"o", 0, 0, V_INDEX, 0, 0, 0, -1, NULL},
     [O_B] = {"b", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
@@ -1025,6 +1028,20 @@ static int option_value(const option_row *r, const char *a, uint64_t *out, uint3
     const int digits = r->kind == V_DIGITS || r->kind == V_LEVELS;
     uint64_t v, k = 0;
     char *end;
+    if (r->kind == V_COSTS) {
+        static const uint64_t lo[3] = {1, 0, 1}, hi[3] = {31, 63, 31};
+        uint64_t packed = 0;
+        for (k = 0; k < 3; k++) {
+            if (a[0] < '0' || a[0] > '9') return -1;
+            errno = 0;
+            v = strtoull(a, &end, 10);
+            if (errno != 0 || v < lo[k] || v > hi[k] || *end != (k < 2 ? ',' : '\0')) return -1;
+            packed |= v << (8 * k);
+            a = end + 1;
+        }
+        *out = packed;
+        return 0;
+    }
     for (;;) {
         errno = 0;
         if (digits) {
@@ -1113,6 +1130,21 @@ int slh_parse_sb_params(int argc, char **argv, int *fs_out) {
     const int rc = scan_options(argc, argv, ids, 2, 0, v, NULL);
     *fs_out = (int)(long long)v[1];
     return rc < 0 ? -1 : rc;
+}
+int slh_parse_affine(int argc, char **argv, int *x_out, int *o_out, int *e_out) {
+    uint64_t v;
+    const int rc = scan_one(argc, argv, O_AFFINE, &v);
+    *x_out = rc > 0 ? (int)(v & 0xFF) : 0;
+    *o_out = rc > 0 ? (int)((v >> 8) & 0xFF) : 0;
+    *e_out = rc > 0 ? (int)((v >> 16) & 0xFF) : 0;
+    return rc;
+}
+uint32_t slh_aln_word(int max_edits, int affine, int x, int o, int e) {
+    if (!affine) return max_edits >= 0 ? (uint32_t)max_edits : SLAMEM_ALN_EDITS_DEFAULT;
+    return SLAMEM_ALN_AFFINE(max_edits >= 0 ? max_edits : 31, x, o, e);
+}
+int slh_aln_word_decode(uint32_t word, uint32_t *fields_out, int *affine_out) {
+    return slamem_decode_aln_word(word, &fields_out[0], &fields_out[1], &fields_out[2], &fields_out[3], affine_out);
 }
 int slh_parse_wq(int argc, char **argv) { return has_option(argc, argv, O_WQ); }
 int slh_parse_stats(int argc, char **argv) { return has_option(argc, argv, O_STATS); }
@@ -1211,7 +1243,7 @@ static int refuse(const char **refusal, const char *msg, int rc) {
 
 int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     slh_options *o = &r->o;
-    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct, sb, fs;
+    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct, sb, fs, aff, costs[3];
     *refusal = NULL;
     memset(r, 0, sizeof(*r));
     if (slh_parse_options(argc, argv, o) != 0) return refuse(refusal, "Out of memory", -1);
@@ -1236,6 +1268,7 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     evs = slh_parse_event_slots(argc, argv, &r->ev_slots);
     dd = slh_parse_dedup(argc, argv, &r->dd_slots);
     sb = slh_parse_sb_params(argc, argv, &fs); /* (the values are the caller's to ask for: slh_run keeps its layout) */
+    aff = slh_parse_affine(argc, argv, &costs[0], &costs[1], &costs[2]); /* (the same) */
     r->dedup = dd > 0 && (dd & 1);
     if (o->usage || o->hidden_sort || o->hidden_clean) return 0; /* (the caller's business, before any refusal) */
 
@@ -1254,6 +1287,10 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     REFUSE_IF(ext && t != 5 && t != 6 && t != 7 && t != 8, "Options -pen and -xdrop need -ext");
     REFUSE_IF(edits < 0, OPTIONS[O_MAXED].refusal);
     REFUSE_IF(edits && t != 6 && t != 7 && t != 8, "Option -maxed needs -aln");
+    REFUSE_IF(aff < 0, OPTIONS[O_AFFINE].refusal);
+    REFUSE_IF(aff && t != 6 && t != 7 && t != 8, "Option -affine needs -aln");
+    REFUSE_IF(aff && (uint32_t)(costs[1] + costs[2] * (r->max_edits >= 0 ? r->max_edits : 31)) > SLAMEM_ALN_COST_MAX,
+              "Option -affine: a gap's cost is bounded by O + E * maxed, which may be at most 512");
     REFUSE_IF(mapq < 0, OPTIONS[O_MINQ].refusal);
     REFUSE_IF(mapq && t != 8 && !has_option(argc, argv, O_STATS), "Option -minq needs -pile");
     REFUSE_IF(r->bq_given < 0, OPTIONS[O_BQ].refusal);

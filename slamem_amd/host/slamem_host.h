@@ -121,6 +121,11 @@ int slh_option_info(int k, const char **name_out);
 int slh_parse_max_occ(int argc, char **argv, int *out);
 int slh_parse_max_gap(int argc, char **argv, int *out);
 int slh_parse_max_edits(int argc, char **argv, int *out);
+/* -affine X,O,E: 0 absent, 1 there with the three costs, -1 refused; the max_edits word the library takes
+ * (SLAMEM_ALN_AFFINE; max_edits < 0: the default), and that word's fields E, x, o, e with the rule it breaks (0: none) */
+int slh_parse_affine(int argc, char **argv, int *x_out, int *o_out, int *e_out);
+uint32_t slh_aln_word(int max_edits, int affine, int x, int o, int e);
+int slh_aln_word_decode(uint32_t word, uint32_t *fields_out, int *affine_out);
 int slh_parse_min_mapq(int argc, char **argv, int *out);
 int slh_parse_min_bq(int argc, char **argv, int *out);
 int slh_parse_event_slots(int argc, char **argv, uint64_t *out);
