@@ -427,6 +427,50 @@ int slamem_find_alns_device(const slamem_index *idx, const void *queries_dev, co
                             uint64_t ops_capacity, uint64_t *op_offsets_dev, void *workspace_dev, uint64_t workspace_bytes,
                             void *stream, uint64_t *totals_out);
 
+/* Gapped outer ends (option -gext): the forms with end_band beside max_edits.  end_band = Z, 1..31
+ * (SLAMEM_ALN_END_BAND_MAX), lets each of a block's two outer ends hold indels of at most Z letters of net diagonal drift: the
+ * end is the gapped X-drop attempt of 4.30 when that scores strictly more than the ungapped side, else the ungapped side as
+ * before.  It needs gap-affine costs in max_edits (SLAMEM_ALN_AFFINE); 0 is the form without it, byte for byte.  The same
+ * holds for slamem_find_maps_*_gext, slamem_find_maps_md_host_gext and slamem_stream_set_end_band (after
+ * slamem_stream_set_max_edits, before the first submit).  A workspace is sized with the same end_band as the call it serves. */
+#define SLAMEM_ALN_END_BAND_MAX 31u
+/* What the last slamem_find_alns_device_gext or slamem_find_maps_device_gext call in workspace_dev did with its outer ends, read
+ * from that workspace (the sizing arguments are those of the call; it waits for `stream`): counts_out[0] the ends that went to
+ * the gapped attempt (the others were kept inline, fact (c) of DESIGN.md 4.30), counts_out[1] the ends the attempt replaced. */
+int slamem_find_alns_end_counts_device(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                       uint64_t ops_capacity, uint32_t max_edits, uint32_t end_band, const void *workspace_dev,
+                                       void *stream, uint64_t *counts_out);
+int slamem_find_alns_workspace_bytes_gext(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                          uint64_t ops_capacity, uint32_t max_edits, uint32_t end_band, uint64_t *bytes_out);
+int slamem_find_alns_device_gext(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,
+                                 uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap,
+                                 uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits, uint32_t end_band,
+                                 uint64_t mems_capacity, slamem_aln *segs_dev, uint64_t segs_capacity, uint64_t *block_offsets_dev,
+                                 uint32_t *ops_dev, uint64_t ops_capacity, uint64_t *op_offsets_dev, void *workspace_dev,
+                                 uint64_t workspace_bytes, void *stream, uint64_t *totals_out);
+int slamem_find_maps_workspace_bytes_gext(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                          uint64_t ops_capacity, uint32_t max_edits, uint32_t end_band, uint64_t *bytes_out);
+int slamem_find_maps_device_gext(const slamem_index *idx, const void *queries_dev, const uint64_t *offsets_dev,
+                                 uint32_t num_queries, uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap,
+                                 uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits, uint32_t end_band,
+                                 uint64_t mems_capacity, slamem_aln *segs_dev, uint64_t segs_capacity, uint64_t *read_offsets_dev,
+                                 uint32_t *ops_dev, uint64_t ops_capacity, uint64_t *op_offsets_dev, slamem_map *reads_dev,
+                                 void *workspace_dev, uint64_t workspace_bytes, void *stream, uint64_t *totals_out);
+int slamem_find_alns_host_gext(const slamem_index *idx, const char *queries, const uint64_t *offsets, uint32_t num_queries,
+                               uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
+                               uint32_t max_edits, uint32_t end_band, slamem_aln **segs_out, uint64_t **block_offsets_out,
+                               uint32_t **ops_out, uint64_t **op_offsets_out, uint64_t *totals_out);
+int slamem_find_maps_host_gext(const slamem_index *idx, const char *queries, const uint64_t *offsets, uint32_t num_queries,
+                               uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
+                               uint32_t max_edits, uint32_t end_band, slamem_aln **segs_out, uint64_t **read_offsets_out,
+                               uint32_t **ops_out, uint64_t **op_offsets_out, slamem_map **reads_out, uint64_t *totals_out);
+int slamem_find_maps_md_host_gext(const slamem_index *idx, const char *queries, const uint64_t *offsets, uint32_t num_queries,
+                                  uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
+                                  uint32_t max_edits, uint32_t end_band, slamem_aln **segs_out, uint64_t **read_offsets_out,
+                                  uint32_t **ops_out, uint64_t **op_offsets_out, slamem_map **reads_out, uint64_t *totals_out,
+                                  uint32_t **md_out, uint64_t **md_offsets_out, uint32_t **seg_eq_out, uint32_t **primary_out,
+                                  uint64_t *md_total_out);
+
 /* The same batch in mapping mode (option -paf: matchType 7): one mapping per read.  Per read the strand block
  * whose best chain scores highest is the primary one (the forward block on a tie); only that block is aligned, exactly as
  * slamem_find_alns_device aligns it, and the other block gives no segments.  reads_dev takes a slamem_map per read: the strand,
@@ -1017,6 +1061,8 @@ int slamem_stream_set_max_gap(slamem_stream *s, uint32_t max_gap);
 int slamem_stream_set_ext_params(slamem_stream *s, uint32_t mismatch_penalty, uint32_t xdrop);
 int slamem_stream_mismatches(slamem_stream *s, const uint32_t **out);
 int slamem_stream_set_max_edits(slamem_stream *s, uint32_t max_edits);
+/* -gext: the band of the gapped outer ends, after slamem_stream_set_max_edits and before the first submit */
+int slamem_stream_set_end_band(slamem_stream *s, uint32_t end_band);
 int slamem_stream_alns(slamem_stream *s, const slamem_aln **segs_out, const uint32_t **ops_out, const uint64_t **op_offsets_out,
                        uint64_t *num_ops_out);
 /* -paf, -pile: the read records (num_queries of them) of the batch slamem_stream_next returned last, in the stream's pinned memory;

@@ -47,6 +47,9 @@ ABI_SYMBOLS = (
     "slamem_stream_set_ext_params", "slamem_stream_mismatches",
     "slamem_find_alns_workspace_bytes", "slamem_find_alns_device", "slamem_find_alns_host",
     "slamem_stream_set_max_edits", "slamem_stream_alns",
+    "slamem_find_alns_workspace_bytes_gext", "slamem_find_alns_device_gext", "slamem_find_alns_host_gext",
+    "slamem_find_maps_workspace_bytes_gext", "slamem_find_maps_device_gext", "slamem_find_maps_host_gext",
+    "slamem_find_maps_md_host_gext", "slamem_stream_set_end_band", "slamem_find_alns_end_counts_device",
     "slamem_find_maps_workspace_bytes", "slamem_find_maps_device", "slamem_find_maps_host", "slamem_stream_maps",
     "slamem_maps_md_workspace_bytes", "slamem_maps_md_device", "slamem_find_maps_md_host", "slamem_stream_set_md", "slamem_stream_md",
     "slamem_pileup_create", "slamem_pileup_free", "slamem_pileup_reset", "slamem_pileup_add_device",
@@ -201,6 +204,22 @@ def _declare(L):
     L.slamem_find_maps_host.argtypes = [vp, C.c_char_p, vp, u32, u32, i32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(vp),
                                         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.slamem_stream_maps.argtypes = [vp, C.POINTER(vp)]
+    # the forms with end_band behind max_edits (-gext)
+    L.slamem_stream_set_end_band.argtypes = [vp, u32]
+    L.slamem_find_alns_end_counts_device.argtypes = [u32, i32, u64, u64, u64, u32, u32, vp, vp, C.POINTER(u64)]
+    L.slamem_find_maps_md_host_gext.argtypes = [vp, C.c_char_p, vp, u32, u32, i32, u32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(vp),
+                                                C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp),
+                                                C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    L.slamem_find_alns_workspace_bytes_gext.argtypes = [u32, i32, u64, u64, u64, u32, u32, C.POINTER(u64)]
+    L.slamem_find_maps_workspace_bytes_gext.argtypes = [u32, i32, u64, u64, u64, u32, u32, C.POINTER(u64)]
+    L.slamem_find_alns_device_gext.argtypes = [vp, vp, vp, u32, u64, u32, i32, u32, u32, u32, u32, u32, u64, vp, u64, vp, vp, u64, vp,
+                                               vp, u64, vp, C.POINTER(u64)]
+    L.slamem_find_maps_device_gext.argtypes = [vp, vp, vp, u32, u64, u32, i32, u32, u32, u32, u32, u32, u64, vp, u64, vp, vp, u64, vp,
+                                               vp, vp, u64, vp, C.POINTER(u64)]
+    L.slamem_find_alns_host_gext.argtypes = [vp, C.c_char_p, vp, u32, u32, i32, u32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(vp),
+                                             C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    L.slamem_find_maps_host_gext.argtypes = [vp, C.c_char_p, vp, u32, u32, i32, u32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(vp),
+                                             C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.slamem_maps_md_workspace_bytes.argtypes = [u64, u32, C.POINTER(u64)]
     L.slamem_maps_md_device.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
     L.slamem_find_maps_md_host.argtypes = [vp, C.c_char_p, vp, u32, u32, i32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(vp),

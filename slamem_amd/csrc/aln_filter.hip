@@ -49,10 +49,20 @@ inline unsigned aln_affine_grid(const AlnCosts& c) {
     const uint64_t fit = (64ull << 20) / (aln_affine_slab_words(c) * 4);
     return (unsigned)(fit > 8192 ? 8192 : fit < 1 ? 1 : fit);
 }
-inline uint64_t aln_slabs_bytes(uint32_t word) {
+// Outer ends (-gext): three components for the scores 0 .. Cp over the diagonals |k| <= Z, the same rule (388 KB a
+// workgroup at Z = 31: 173 workgroups; 641 at Z = 8)
+inline uint64_t aln_end_slab_words(uint32_t band) { return 3ull * (kAlnMaxCost + 1) * (2 * band + 1); }
+inline unsigned aln_end_grid(uint32_t band) {
+    const uint64_t fit = (64ull << 20) / (aln_end_slab_words(band) * 4);
+    return (unsigned)(fit > 8192 ? 8192 : fit < 1 ? 1 : fit);
+}
+// (the gap kernel and the end kernel run one after the other and share the room)
+inline uint64_t aln_slabs_bytes(uint32_t word, uint32_t band) {
     const AlnCosts c = aln_costs(word);
-    return c.affine ? (uint64_t)aln_affine_grid(c) * aln_affine_slab_words(c) * 4
-                    : (uint64_t)aln_wave_grid(c.E) * (c.E + 1) * (2 * c.E + 1) * 4;
+    const uint64_t gaps = c.affine ? (uint64_t)aln_affine_grid(c) * aln_affine_slab_words(c) * 4
+                                   : (uint64_t)aln_wave_grid(c.E) * (c.E + 1) * (2 * c.E + 1) * 4;
+    const uint64_t ends = band ? (uint64_t)aln_end_grid(band) * aln_end_slab_words(band) * 4 : 0;
+    return gaps > ends ? gaps : ends;
 }
 // Runs of an affine gap: every run but those of `=` costs at least min(x, e) >= 1 (L mismatches cost L x, a gap of L letters
 // o + L e), so there are at most C of them, and two runs of `=` have one of the others between them: at most 2 C + 1 runs.
@@ -67,8 +77,12 @@ struct AlnRow {
     uint32_t a, b;          // letters of the strand / of the text between the predecessor's end and the anchor
     uint32_t extl, extr;    // outer ends (the block's first / last chain row only)
     uint32_t flags;         // kFirst: first of its block in the list (the chain's LAST row); kLast: the chain's first row
-    uint32_t nfix;          // runs of the outer ends
-    uint32_t edits;         // mismatches of the outer ends
+    uint32_t nfl, nfr;      // runs of the outer ends
+    uint32_t edl, edr;      // edits of the outer ends
+    uint32_t extl_t, extr_t;  // the ends' letters of the text (extl, extr: of the strand; they differ in a replaced end only)
+    uint32_t scl, scr;      // the ungapped sides' scores (4.13's best)
+    uint32_t sll, slr;      // a replaced end's runs: where in the slab, left to right
+    uint32_t repl, repr;    // 1: the end is the gapped attempt's (-gext)
     uint32_t gapn, gapd;    // a closed gap's runs and distance
     uint32_t slab;          // a listed gap's runs: where in the slab
     uint32_t rec;           // the record of the batch
@@ -76,7 +90,7 @@ struct AlnRow {
 
 struct AlnLayout {
     uint64_t chain_bytes, off_ctr, off_crows, off_coff, off_ucnt, off_uoff, off_uscan, uscan_bytes, off_long, off_units, off_rows,
-        off_list, off_n, off_flag, off_ed, off_sn, off_sflag, off_sed, off_scan, scan_bytes, off_segstart, off_slab, off_f, bytes;
+        off_list, off_ends, off_n, off_flag, off_ed, off_sn, off_sflag, off_sed, off_scan, scan_bytes, off_segstart, off_slab, off_f, bytes;
 };
 
 AlnLayout aln_layout(const FilterBatch& b, const FilterParams& p) {
@@ -86,7 +100,7 @@ AlnLayout aln_layout(const FilterBatch& b, const FilterParams& p) {
     AlnLayout m;
     m.chain_bytes = align_up(chain_workspace_bytes(b, p), 256);  // (the -mem list K9 places lies in here)
     uint64_t off = m.chain_bytes;
-    m.off_ctr = off;    off = align_up(off + 64, 256);                                  // [2] listed records, [3] listed gaps, [4] slab words
+    m.off_ctr = off;    off = align_up(off + 64, 256);                                  // [2] listed records, [3] listed gaps, [4] slab words, [5] listed ends, [6] ends replaced
     m.off_crows = off;  off = align_up(off + capacity * sizeof(slamem_mem) + 16, 256);  // the chains' rows
     m.off_coff = off;   off = align_up(off + (num_blocks + 1) * 8, 256);                // ... and their block offsets
     m.off_ucnt = off;   off = align_up(off + (num_queries + 1) * 4, 256);
@@ -99,6 +113,7 @@ AlnLayout aln_layout(const FilterBatch& b, const FilterParams& p) {
     m.off_units = off;  off = align_up(off + (query_bytes / 64 + num_queries + 1) * sizeof(QueryUnit), 256);
     m.off_rows = off;   off = align_up(off + (capacity + 1) * sizeof(AlnRow), 256);
     m.off_list = off;   off = align_up(off + (capacity + 1) * 4, 256);                  // listed gaps (their rows)
+    m.off_ends = off;   if (p.end_band) off = align_up(off + (capacity + 1) * 8, 256);  // listed ends (row << 1 | right), two a row at most
     m.off_n = off;      off = align_up(off + (capacity + 2) * 4, 256);                  // runs per row
     m.off_flag = off;   off = align_up(off + (capacity + 2) * 4, 256);                  // 1: the row is the rightmost of a segment
     m.off_ed = off;     off = align_up(off + (capacity + 2) * 4, 256);                  // edits per row
@@ -111,7 +126,7 @@ AlnLayout aln_layout(const FilterBatch& b, const FilterParams& p) {
     m.off_scan = off;   off = align_up(off + need, 256);
     m.off_segstart = off; off = align_up(off + (capacity + 2) * 4, 256);                // the rightmost row of every segment
     m.off_slab = off;   off = align_up(off + (ops_capacity + 1) * 4, 256);              // the runs of listed gaps
-    m.off_f = off;      off = align_up(off + aln_slabs_bytes(max_edits), 256);          // wavefronts
+    m.off_f = off;      off = align_up(off + aln_slabs_bytes(max_edits, p.end_band), 256);          // wavefronts
     m.bytes = off;
     return m;
 }
@@ -179,13 +194,31 @@ __device__ __forceinline__ void diag_runs(const Seqs& s, int64_t q0, int64_t p0,
     }
 }
 
+// runs that a wave kernel left in the slab
+__device__ __forceinline__ void slab_runs(const uint32_t* __restrict__ slab, uint64_t slab_cap, uint32_t from, uint32_t n, Emit& em) {
+    for (uint32_t k = 0; k < n; k++) {
+        const uint64_t at = (uint64_t)from + k;
+        const uint32_t w = at < slab_cap ? slab[at] : 0u;
+        em.push(w & 15u, w >> 4);
+    }
+}
+
+// -gext, fact (c) of DESIGN.md 4.30: an attempt that beats the ungapped side holds a gap and scores at most a - (o + e), so a
+// side that scores as much is kept here.  a is known when the walk ended at the strand's own end or bad letter (bit `fb` of the
+// last window's bad mask, at distance t0 + fb = everything the walk looked at); any other end is listed.
+__device__ __forceinline__ bool lists_end(uint64_t qbad, const Side& d, uint64_t t0, uint32_t gap_oe) {
+    if (!qbad) return true;
+    const uint64_t a = t0 + (uint64_t)__builtin_ctzll(qbad);
+    return d.best + (int64_t)gap_oe < (int64_t)a;
+}
+
 // ---- a lane per chain row ----------------------------------------------------------------------------------------------------
 
 __global__ void __launch_bounds__(256) k_aln_geom(const uint64_t* __restrict__ coff, uint64_t nb, const slamem_mem* __restrict__ crows,
                                                   uint64_t cap, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ uoff,
                                                   const QueryUnit* __restrict__ units, const TextPlanes* __restrict__ tpl, uint32_t n,
                                                   uint32_t strands, uint32_t penalty, uint32_t xdrop, uint32_t max_edits,
-                                                  uint32_t cost_x, uint32_t inline_d, uint32_t cost_bound, AlnRow* __restrict__ rows, uint32_t* __restrict__ list, unsigned long long* __restrict__ ctr) {
+                                                  uint32_t cost_x, uint32_t inline_d, uint32_t cost_bound, uint32_t end_band, uint32_t gap_oe, AlnRow* __restrict__ rows, uint32_t* __restrict__ list, uint32_t* __restrict__ ends, unsigned long long* __restrict__ ctr) {
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     uint64_t K = coff[nb];
     if (K > cap) K = cap;
@@ -218,7 +251,8 @@ __global__ void __launch_bounds__(256) k_aln_geom(const uint64_t* __restrict__ c
     r.tq = (uint32_t)(q + o);
     r.tl = (uint32_t)(L - o);
     r.flags = (g == s ? kFirst : 0u) | (g + 1u == e ? kLast : 0u) | (rev ? kRev : 0u);
-    r.extl = r.extr = r.nfix = r.edits = r.gapn = r.gapd = r.slab = 0u;
+    r.extl = r.extr = r.nfl = r.nfr = r.edl = r.edr = r.gapn = r.gapd = r.slab = 0u;
+    r.extl_t = r.extr_t = r.scl = r.scr = r.sll = r.slr = r.repl = r.repr = 0u;
     r.rec = (uint32_t)rec;
     const int64_t a = has_gap ? q + o - eqj : 0, b = has_gap ? p + o - epj : 0;
     r.a = (uint32_t)a;
@@ -263,30 +297,38 @@ __global__ void __launch_bounds__(256) k_aln_geom(const uint64_t* __restrict__ c
         if (r.flags & kLast) {  // (the chain's first row is not trimmed)
             Side left = {0, 0, 0, 0, 0, 0};
             Win ql = mirrored(strand_window(sq.Q, sq.qn, sq.len, rev, q - 64)), tl = mirrored(window(sq.T, sq.tn, sq.n, p - 64));
-            for (uint64_t t0 = 0; !walk(left, ql, tl, t0, P, X);) {
+            uint64_t t0 = 0;
+            while (!walk(left, ql, tl, t0, P, X)) {
                 t0 += 64u;
                 ql = mirrored(strand_window(sq.Q, sq.qn, sq.len, rev, q - 64 - (int64_t)t0));
                 tl = mirrored(window(sq.T, sq.tn, sq.n, p - 64 - (int64_t)t0));
             }
-            r.extl = (uint32_t)left.ext;
-            r.edits += left.mm_best;
+            r.extl = r.extl_t = (uint32_t)left.ext;
+            r.edl = left.mm_best;
+            r.scl = (uint32_t)left.best;
             diag_runs(sq, q - (int64_t)left.ext, p - (int64_t)left.ext, (int64_t)left.ext, em);
             em.flush();
+            r.nfl = em.n;
+            if (end_band && g < 0x80000000ull && lists_end(ql.bad, left, t0, gap_oe)) ends[atomicAdd(&ctr[5], 1ull)] = (uint32_t)g << 1;
         }
         if (r.flags & kFirst) {
             Side right = {0, 0, 0, 0, 0, 0};
             Win qr = strand_window(sq.Q, sq.qn, sq.len, rev, q + L), tr = window(sq.T, sq.tn, sq.n, p + L);
-            for (uint64_t t0 = 0; !walk(right, qr, tr, t0, P, X);) {
+            uint64_t t0 = 0;
+            while (!walk(right, qr, tr, t0, P, X)) {
                 t0 += 64u;
                 qr = strand_window(sq.Q, sq.qn, sq.len, rev, q + L + (int64_t)t0);
                 tr = window(sq.T, sq.tn, sq.n, p + L + (int64_t)t0);
             }
-            r.extr = (uint32_t)right.ext;
-            r.edits += right.mm_best;
+            r.extr = r.extr_t = (uint32_t)right.ext;
+            r.edr = right.mm_best;
+            r.scr = (uint32_t)right.best;
+            const uint32_t before = em.n;
             diag_runs(sq, q + L, p + L, (int64_t)right.ext, em);
             em.flush();
+            r.nfr = em.n - before;
+            if (end_band && g < 0x80000000ull && lists_end(qr.bad, right, t0, gap_oe)) ends[atomicAdd(&ctr[5], 1ull)] = ((uint32_t)g << 1) | 1u;
         }
-        r.nfix = em.n;
     }
     rows[g] = r;
 }
@@ -624,6 +666,206 @@ __global__ void __launch_bounds__(64) k_aln_wave_affine(const uint32_t* __restri
     }
 }
 
+// ---- a wave per listed outer end (-gext) ------------------------------------------------------------------------
+
+// Runs of an end: every run but those of `=` costs at least min(x', o' + e') >= 3 of the penalty p <= Cp, and two runs of `=` have
+// one of the others between them.
+constexpr uint32_t kEndRuns = 2 * (kAlnMaxCost / 3) + 1;
+
+// The gapped X-drop attempt of one end on the penalty p with 2S = x + y - p (x' = 2P + 2, o' = 2o, e' = 2e + 1): 4.29's three
+// components per score on the diagonals |k| <= Z (a lane each, 2Z + 1 <= 63), in the coordinates of the end -- x letters of the
+// strand and y of the text away from the anchor, to the right, or to the left on the mirrored windows.  A cell whose start lies
+// more than 2X under best2 is dead; best2 and the best cell are wave-uniform, and so are the pruning's inputs, alive[], the end
+// of the attempt and the traceback.
+__global__ void __launch_bounds__(64) k_aln_wave_ends(const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ ctr_in,
+                                                      AlnRow* rows, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ uoff,
+                                                      const QueryUnit* __restrict__ units, const TextPlanes* __restrict__ tpl, uint32_t n,
+                                                      uint32_t band, uint32_t penalty, uint32_t xdrop, uint32_t cost_o, uint32_t cost_e,
+                                                      int32_t* fslab, uint32_t* __restrict__ slab, uint64_t slab_cap,
+                                                      unsigned long long* __restrict__ ctr) {
+    __shared__ uint32_t rbuf[kEndRuns];          // the traceback's runs, the farthest from the anchor first
+    __shared__ uint8_t alive[kAlnMaxCost + 1];   // per score: some cell is live (and the slab holds the score)
+    __shared__ unsigned long long s_off;
+    const uint32_t lane = threadIdx.x;
+    const int32_t Z = (int32_t)band, W = 2 * Z + 1, C = (int32_t)kAlnMaxCost;
+    const int32_t X = 2 * (int32_t)penalty + 2, G = 2 * (int32_t)cost_e + 1, o2 = 2 * (int32_t)cost_o, O = o2 + G;
+    const int32_t back = X > O ? X : O;
+    const int64_t drop2 = 2 * (int64_t)xdrop, kBias = 1ll << 34;
+    const int64_t plane = (int64_t)(C + 1) * W;
+    int32_t* FM = fslab + (uint64_t)blockIdx.x * 3u * (uint64_t)plane;
+    int32_t* FI = FM + plane;
+    int32_t* FD = FI + plane;
+    auto kmax_of = [&](int32_t sp) -> int32_t {
+        if (sp < O) return 0;
+        const int32_t v = (sp - o2) / G;
+        return v < Z ? v : Z;
+    };
+    auto held = [&](int32_t sp, int32_t k) -> bool {
+        if (sp < 0 || sp > C || !alive[sp]) return false;
+        const int32_t km = kmax_of(sp);
+        return k >= -km && k <= km;
+    };
+    const uint64_t nl = ctr_in[5];
+    for (uint64_t li = blockIdx.x; li < nl; li += gridDim.x) {
+        const uint32_t en = ends[li], g = en >> 1;
+        const bool right = (en & 1u) != 0u;
+        const AlnRow r = rows[g];
+        const Seqs sq = seqs_of(r.rec, (r.flags & kRev) != 0u, offsets, uoff, units, tpl, n);
+        const int64_t q0 = (int64_t)r.tq + (right ? (int64_t)r.tl : 0), p0 = (int64_t)r.tp + (right ? (int64_t)r.tl : 0);
+        // the pieces: letters up to the first that is not A,C,G,T or lies outside (window() calls those bad), 4,096 per trip
+        auto piece_len = [&](bool text, int64_t limit) -> int64_t {
+            for (int64_t w0 = 0;; w0 += 64) {
+                const int64_t w = w0 + lane;
+                Win v;
+                if (text) v = right ? window(sq.T, sq.tn, sq.n, p0 + 64 * w) : mirrored(window(sq.T, sq.tn, sq.n, p0 - 64 - 64 * w));
+                else v = right ? strand_window(sq.Q, sq.qn, sq.len, sq.rev, q0 + 64 * w)
+                               : mirrored(strand_window(sq.Q, sq.qn, sq.len, sq.rev, q0 - 64 - 64 * w));
+                const uint64_t hit = __ballot(v.bad != 0ull);
+                if (hit) {
+                    const int first = (int)__builtin_ctzll(hit);
+                    const int64_t mine = 64 * w + (v.bad ? (int64_t)__builtin_ctzll(v.bad) : 0);
+                    const int64_t len = __shfl(mine, first);
+                    return len < limit ? len : limit;
+                }
+                if (64 * (w0 + 64) >= limit) return limit;
+            }
+        };
+        const int64_t a = piece_len(false, (int64_t)1 << 40);
+        const int64_t b = piece_len(true, a + Z);
+        auto slide_out = [&](int64_t x, int64_t y, int64_t lim) -> int64_t {  // matching letters from (x, y) on, away from the anchor
+            return right ? slide_fwd(sq, q0, p0, x, y, lim) : slide_back(sq, q0, p0, -x, -y, lim);
+        };
+        auto slide_in = [&](int64_t x, int64_t y, int64_t lim) -> int64_t {   // ... in front of (x, y), towards the anchor
+            return right ? slide_back(sq, q0, p0, x, y, lim) : slide_fwd(sq, q0, p0, -x, -y, lim);
+        };
+        __syncthreads();  // (nobody reads the last end's LDS any more)
+        int64_t best2 = 0, bx = 0;
+        int32_t bs = 0, bk = 0, last_live = 0;
+        for (int32_t s = 0; s <= C; s++) {
+            if (s - last_live > back) break;  // (uniform)
+            const int32_t sx = s - X, so = s - O, sg = s - G;
+            const bool sources = s == 0 || (sx >= 0 && alive[sx]) || (so >= 0 && alive[so]) || (sg >= 0 && alive[sg]);
+            if (!sources) { alive[s] = 0; continue; }
+            const int32_t km = kmax_of(s), d = Z - km + (int32_t)lane, k = d - Z;
+            long long key = -1;
+            if (d <= Z + km) {
+                int64_t ci = kNeg, cd = kNeg, c = kNeg;
+                if (s == 0) {
+                    c = 0;
+                } else {
+                    {  // a strand letter: from diagonal k + 1, x + 1
+                        int64_t src = held(so, k + 1) ? FM[(int64_t)so * W + d + 1] : kNeg;
+                        const int64_t go = held(sg, k + 1) ? FI[(int64_t)sg * W + d + 1] : kNeg;
+                        if (go > src) src = go;
+                        if (src >= 0) {
+                            const int64_t v = src + 1 < a ? src + 1 : a, least = -k - 1 > 0 ? -k - 1 : 0;
+                            if (v - 1 >= least) ci = v;
+                        }
+                    }
+                    {  // a text letter: from diagonal k - 1, x stays
+                        int64_t src = held(so, k - 1) ? FM[(int64_t)so * W + d - 1] : kNeg;
+                        const int64_t go = held(sg, k - 1) ? FD[(int64_t)sg * W + d - 1] : kNeg;
+                        if (go > src) src = go;
+                        if (src >= 0) {
+                            const int64_t v = src < b - k ? src : b - k, least = 1 - k > 0 ? 1 - k : 0;
+                            if (v >= least) cd = v;
+                        }
+                    }
+                    const int64_t fk = held(sx, k) ? FM[(int64_t)sx * W + d] : kNeg;
+                    if (fk >= 0) {
+                        c = fk + 1;
+                        if (c > a) c = a;
+                        if (c > b - k) c = b - k;
+                    }
+                    if (ci > c) c = ci;
+                    if (cd > c) c = cd;
+                }
+                if (c >= 0 && best2 - (2 * c + k - s) > drop2) c = ci = cd = kNeg;  // dead
+                if (c >= 0) {
+                    const int64_t lim = a - c < b - (c + k) ? a - c : b - (c + k);
+                    if (lim > 0) c += slide_out(c, c + k, lim);
+                    const int32_t rank = k < 0 ? -2 * k - 1 : 2 * k;  // k = 0, -1, +1, -2, ..
+                    key = ((long long)(2 * c + k - s + kBias) << 7) | (long long)(127 - rank);
+                }
+                FM[(int64_t)s * W + d] = (int32_t)c;
+                FI[(int64_t)s * W + d] = (int32_t)ci;
+                FD[(int64_t)s * W + d] = (int32_t)cd;
+            }
+            for (int m = 32; m; m >>= 1) {
+                const long long other = __shfl_xor(key, m);
+                if (other > key) key = other;
+            }
+            alive[s] = key >= 0 ? 1 : 0;
+            __syncthreads();  // the score's cells are in the slab (and alive[s] in LDS) for every lane
+            if (key >= 0) {
+                last_live = s;
+                const int64_t val = (int64_t)(key >> 7) - kBias;
+                const int32_t rank = 127 - (int32_t)(key & 127), kb = (rank & 1) ? -(rank + 1) / 2 : rank / 2;
+                if (val > best2) { best2 = val; bs = s; bk = kb; bx = (val - kb + s) / 2; }
+            }
+        }
+        if (best2 <= 2 * (int64_t)(right ? r.scr : r.scl)) continue;  // (uniform) 4.13's side stays, a tie included
+        // 4.29's traceback from the stored points, started at the best cell
+        bool overrun = false;
+        int64_t x = bx, y = bx + bk;
+        int32_t sc = bs;
+        uint32_t state = 0, nr = 0, code = 0, len = 0, ned = 0;
+        while (x > 0 || y > 0) {
+            uint32_t op;
+            const int32_t k = (int32_t)(y - x);
+            if (state == 0u) {
+                if (x > 0 && y > 0) {
+                    const int64_t run = slide_in(x, y, x < y ? x : y);
+                    if (run) {
+                        if (code != kOpEq) { if (len) rbuf[nr++] = (len << 4) | code; code = kOpEq; len = 0; }
+                        len += (uint32_t)run;
+                        x -= run;
+                        y -= run;
+                        if (nr >= kEndRuns - 1u) { overrun = true; break; }
+                        continue;
+                    }
+                }
+                const int32_t m_same = held(sc - X, k) ? FM[(int64_t)(sc - X) * W + k + Z] : kNeg;
+                if (x > 0 && y > 0 && m_same >= 0 && (int64_t)m_same >= x - 1) { op = kOpX; x--; y--; sc -= X; }
+                else {
+                    const int32_t d_here = held(sc, k) ? FD[(int64_t)sc * W + k + Z] : kNeg;
+                    state = (y > 0 && (x == 0 || (d_here >= 0 && (int64_t)d_here >= x))) ? 1u : 2u;
+                    continue;
+                }
+            } else if (state == 1u) {
+                const int32_t m_open = held(sc - O, k - 1) ? FM[(int64_t)(sc - O) * W + k - 1 + Z] : kNeg;
+                op = kOpD;
+                if (m_open >= 0 && (int64_t)m_open >= x) { sc -= O; state = 0u; } else { sc -= G; }
+                y--;
+            } else {
+                const int32_t m_open = held(sc - O, k + 1) ? FM[(int64_t)(sc - O) * W + k + 1 + Z] : kNeg;
+                op = kOpI;
+                if (m_open >= 0 && (int64_t)m_open >= x - 1) { sc -= O; state = 0u; } else { sc -= G; }
+                x--;
+            }
+            ned++;
+            if (code != op) { if (len) rbuf[nr++] = (len << 4) | code; code = op; len = 0; }
+            len++;
+            if (nr >= kEndRuns - 1u || sc < 0 || x < 0 || y < 0) { overrun = true; break; }  // (never, by the count of runs)
+        }
+        // (the anchor is a MEM, so the letters next to it differ and the run next to it is never `=`; k_aln_count relies on it)
+        if (overrun || code == kOpEq || !len) continue;  // (uniform)
+        rbuf[nr++] = (len << 4) | code;
+        if (lane == 0u) s_off = atomicAdd(&ctr[4], (unsigned long long)nr);
+        __syncthreads();
+        const uint64_t at = s_off;
+        if (at + nr <= slab_cap)
+            for (uint32_t t = lane; t < nr; t += 64u) slab[at + t] = rbuf[right ? nr - 1u - t : t];  // left to right in the strand
+        if (lane == 0u) {
+            AlnRow* o = rows + g;
+            const uint32_t where = (uint32_t)(at < 0xFFFFFFFFull ? at : 0xFFFFFFFFull);
+            if (right) { o->extr = (uint32_t)bx; o->extr_t = (uint32_t)(bx + bk); o->nfr = nr; o->edr = ned; o->slr = where; o->repr = 1u; }
+            else { o->extl = (uint32_t)bx; o->extl_t = (uint32_t)(bx + bk); o->nfl = nr; o->edl = ned; o->sll = where; o->repl = 1u; }
+            atomicAdd(&ctr[6], 1ull);
+        }
+    }
+}
+
 // ---- places ------------------------------------------------------------------------------------------------------------------
 
 // a row's anchor goes into the run of the row to its left when its gap is closed and empty
@@ -640,8 +882,8 @@ __global__ void __launch_bounds__(256) k_aln_count(const uint64_t* __restrict__ 
     const AlnRow r = rows[g];
     const bool closed = (r.flags & kClosed) != 0u;
     const bool own_anchor = !(closed && (r.gapn == 0u || (r.flags & kGapEq)));
-    nruns[g] = r.nfix + (closed ? r.gapn : 0u) + (own_anchor ? 1u : 0u);
-    ed[g] = r.edits + (closed ? r.gapd : 0u);
+    nruns[g] = r.nfl + r.nfr + (closed ? r.gapn : 0u) + (own_anchor ? 1u : 0u);
+    ed[g] = r.edl + r.edr + (closed ? r.gapd : 0u);
     // the gap to the right of row g is row g - 1's
     flag[g] = ((r.flags & kFirst) || !(rows[g - 1u].flags & kClosed)) ? 1u : 0u;
 }
@@ -683,14 +925,11 @@ __global__ void __launch_bounds__(256) k_aln_write(const uint64_t* __restrict__ 
     const Seqs sq = seqs_of(r.rec, (r.flags & kRev) != 0u, offsets, uoff, units, tpl, n);
     Emit em = {ops, sn[g0] + (sn[g1p] - sn[g + 1u]), ops_cap, 0, 0, 0, true};
     if (!(joins_left(r) && g + 1u < g1p)) {
-        if ((r.flags & kLast) && r.extl) diag_runs(sq, (int64_t)r.tq - r.extl, (int64_t)r.tp - r.extl, r.extl, em);
+        if ((r.flags & kLast) && r.repl) slab_runs(slab, slab_cap, r.sll, r.nfl, em);
+        else if ((r.flags & kLast) && r.extl) diag_runs(sq, (int64_t)r.tq - r.extl, (int64_t)r.tp - r.extl, r.extl, em);
         if ((r.flags & kClosed) && r.gapn) {
             if (r.flags & kListed) {
-                for (uint32_t k = 0; k < r.gapn; k++) {
-                    const uint64_t at = (uint64_t)r.slab + k;
-                    const uint32_t w = at < slab_cap ? slab[at] : 0u;
-                    em.push(w & 15u, w >> 4);
-                }
+                slab_runs(slab, slab_cap, r.slab, r.gapn, em);
             } else {
                 diag_runs(sq, (int64_t)r.tq - r.a, (int64_t)r.tp - r.b, r.a, em);
             }
@@ -704,14 +943,15 @@ __global__ void __launch_bounds__(256) k_aln_write(const uint64_t* __restrict__ 
         }
         em.push(kOpEq, len);
     }
-    if ((r.flags & kFirst) && r.extr) diag_runs(sq, (int64_t)r.tq + r.tl, (int64_t)r.tp + r.tl, r.extr, em);
+    if ((r.flags & kFirst) && r.repr) slab_runs(slab, slab_cap, r.slr, r.nfr, em);
+    else if ((r.flags & kFirst) && r.extr) diag_runs(sq, (int64_t)r.tq + r.tl, (int64_t)r.tp + r.tl, r.extr, em);
     em.flush();
     if (g == g0 && sg < seg_cap) {
         const AlnRow rl = rows[g1p - 1u];
         slamem_aln o;
-        o.ref_pos = rl.tp - rl.extl;
+        o.ref_pos = rl.tp - rl.extl_t;
         o.query_pos = rl.tq - rl.extl;
-        o.ref_len = r.tp + r.tl + r.extr - o.ref_pos;
+        o.ref_len = r.tp + r.tl + r.extr_t - o.ref_pos;
         o.query_len = r.tq + r.tl + r.extr - o.query_pos;
         o.edits = (uint32_t)(sed[g1p] - sed[g0]);
         segs[sg] = o;
@@ -722,6 +962,7 @@ __global__ void __launch_bounds__(256) k_aln_write(const uint64_t* __restrict__ 
 }  // namespace
 
 uint64_t aln_workspace_bytes(const FilterBatch& b, const FilterParams& p) { return aln_layout(b, p).bytes; }
+uint64_t aln_counters_offset(const FilterBatch& b, const FilterParams& p) { return aln_layout(b, p).off_ctr; }
 
 #define ASTEP(call, what) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__); } while (0)
 
@@ -762,6 +1003,7 @@ int aln_after_chain(void* ws, const FilterBatch& b, const FilterParams& args, ui
     QueryUnit* units = reinterpret_cast<QueryUnit*>(p + m.off_units);
     AlnRow* rows = reinterpret_cast<AlnRow*>(p + m.off_rows);
     uint32_t* list = reinterpret_cast<uint32_t*>(p + m.off_list);
+    uint32_t* ends = reinterpret_cast<uint32_t*>(p + m.off_ends);
     uint32_t* nruns = reinterpret_cast<uint32_t*>(p + m.off_n);
     uint32_t* flag = reinterpret_cast<uint32_t*>(p + m.off_flag);
     uint32_t* ed = reinterpret_cast<uint32_t*>(p + m.off_ed);
@@ -778,13 +1020,20 @@ int aln_after_chain(void* ws, const FilterBatch& b, const FilterParams& args, ui
     if (num_blocks) {
         hipLaunchKernelGGL(k_aln_geom, dim3(grid_for(capacity)), dim3(256), 0, stream, (const uint64_t*)coff, num_blocks,
                            (const slamem_mem*)crows, capacity, offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n,
-                           strands, args.penalty, args.xdrop, costs.E, costs.x, 2u * (costs.o + costs.e) / costs.x, costs.C, rows, list, ctr);
+                           strands, args.penalty, args.xdrop, costs.E, costs.x, 2u * (costs.o + costs.e) / costs.x, costs.C,
+                           args.end_band, costs.o + costs.e, rows, list, ends, ctr);
         ASTEP(hipGetLastError(), "k_aln_geom");
         if (costs.affine) {
             hipLaunchKernelGGL(k_aln_wave_affine, dim3(aln_affine_grid(costs)), dim3(64), 0, stream, (const uint32_t*)list,
                                (const unsigned long long*)ctr, rows, offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n,
                                costs.E, costs.x, costs.o, costs.e, fslab, slab, args.ops_capacity, ctr);
             ASTEP(hipGetLastError(), "k_aln_wave_affine");
+            if (args.end_band) {
+                hipLaunchKernelGGL(k_aln_wave_ends, dim3(aln_end_grid(args.end_band)), dim3(64), 0, stream, (const uint32_t*)ends,
+                                   (const unsigned long long*)ctr, rows, offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl,
+                                   ix.n, args.end_band, args.penalty, args.xdrop, costs.o, costs.e, fslab, slab, args.ops_capacity, ctr);
+                ASTEP(hipGetLastError(), "k_aln_wave_ends");
+            }
         } else {
             hipLaunchKernelGGL(k_aln_wave, dim3(aln_wave_grid(costs.E)), dim3(64), 0, stream, (const uint32_t*)list, (const unsigned long long*)ctr, rows,
                                offsets_dev, (const uint64_t*)uoff, (const QueryUnit*)units, ix.tpl, ix.n, costs.E, fslab, slab,

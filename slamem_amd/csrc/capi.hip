@@ -468,10 +468,11 @@ int slamem_find_mams_device(const slamem_index* idx, const void* queries_dev, co
 
 // The filtered searches: the placeholders of the public interface -> values (resolve_filter_params), then the one search.
 static int filter_workspace_bytes(const char* who, int match_type, uint32_t num_queries, int both_strands, uint64_t query_bytes,
-                                  uint64_t mems_capacity, uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out) {
+                                  uint64_t mems_capacity, uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out, uint32_t end_band = 0) {
     if (!bytes_out) return SLAMEM_ERR_ARG;
     FilterParams p;
     if (int bad = resolve_filter_params(who, 0, 0, 0, kExtXdropUnset, max_edits, &p)) return bad;
+    if (int bad = set_end_band(who, end_band, &p)) return bad;
     p.ops_capacity = ops_capacity;
     *bytes_out = search_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity, match_type, p);
     return SLAMEM_OK;
@@ -550,14 +551,45 @@ int slamem_find_exts_device(const slamem_index* idx, const void* queries_dev, co
 
 int slamem_find_alns_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
                                      uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out) {
+    return slamem_find_alns_workspace_bytes_gext(num_queries, both_strands, query_bytes, mems_capacity, ops_capacity, max_edits, 0, bytes_out);
+}
+
+int slamem_find_alns_workspace_bytes_gext(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                          uint64_t ops_capacity, uint32_t max_edits, uint32_t end_band, uint64_t* bytes_out) {
     return filter_workspace_bytes("slamem_find_alns_workspace_bytes", 6, num_queries, both_strands, query_bytes, mems_capacity,
-                                  ops_capacity, max_edits, bytes_out);
+                                  ops_capacity, max_edits, bytes_out, end_band);
 }
 
 int slamem_find_maps_workspace_bytes(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
                                      uint64_t ops_capacity, uint32_t max_edits, uint64_t* bytes_out) {
+    return slamem_find_maps_workspace_bytes_gext(num_queries, both_strands, query_bytes, mems_capacity, ops_capacity, max_edits, 0, bytes_out);
+}
+
+int slamem_find_maps_workspace_bytes_gext(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                          uint64_t ops_capacity, uint32_t max_edits, uint32_t end_band, uint64_t* bytes_out) {
     return filter_workspace_bytes("slamem_find_maps_workspace_bytes", 7, num_queries, both_strands, query_bytes, mems_capacity,
-                                  ops_capacity, max_edits, bytes_out);
+                                  ops_capacity, max_edits, bytes_out, end_band);
+}
+
+// -gext: the two counters the kernels of the last call left in its workspace (sized by the same arguments)
+int slamem_find_alns_end_counts_device(uint32_t num_queries, int both_strands, uint64_t query_bytes, uint64_t mems_capacity,
+                                       uint64_t ops_capacity, uint32_t max_edits, uint32_t end_band, const void* workspace_dev,
+                                       void* stream, uint64_t* counts_out) {
+    const char* who = "slamem_find_alns_end_counts_device";
+    if (!workspace_dev || !counts_out) { set_error("%s: null argument", who); return SLAMEM_ERR_ARG; }
+    FilterParams p;
+    if (int bad = resolve_filter_params(who, 0, 0, 0, kExtXdropUnset, max_edits, &p)) return bad;
+    if (int bad = set_end_band(who, end_band, &p)) return bad;
+    p.ops_capacity = ops_capacity;
+    const FilterBatch b = {nullptr, nullptr, nullptr, num_queries, both_strands ? 2u : 1u, query_bytes, mems_capacity};
+    const char* ctr = static_cast<const char*>(workspace_dev) + find_mems_workspace_bytes(num_queries, both_strands, query_bytes, mems_capacity) +
+                      aln_counters_offset(b, p);
+    unsigned long long h[2] = {0, 0};
+    SLAMEM_HIP(hipMemcpyAsync(h, ctr + 5 * 8, 16, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
+    SLAMEM_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    counts_out[0] = h[0];
+    counts_out[1] = h[1];
+    return SLAMEM_OK;
 }
 
 // -aln and -paf (reads_dev: -paf's record per read, then offsets_out_dev takes num_queries + 1 read offsets)
@@ -566,11 +598,12 @@ static int find_segments_device(const char* who, const slamem_index* idx, const 
                                 uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity, slamem_aln* segs_dev,
                                 uint64_t segs_capacity, uint64_t* offsets_out_dev, uint32_t* ops_dev, uint64_t ops_capacity,
                                 uint64_t* op_offsets_dev, slamem_map* reads_dev, int match_type, void* workspace_dev,
-                                uint64_t workspace_bytes, void* stream, uint64_t* totals_out) {
+                                uint64_t workspace_bytes, void* stream, uint64_t* totals_out, uint32_t end_band) {
     if (!totals_out) { set_error("%s: null argument", who); return SLAMEM_ERR_ARG; }
     totals_out[0] = totals_out[1] = totals_out[2] = 0;
     FilterParams p;
     if (int bad = resolve_filter_params(who, 0, max_gap, mismatch_penalty, xdrop, max_edits, &p)) return bad;
+    if (int bad = set_end_band(who, end_band, &p)) return bad;
     p.segs = segs_dev;
     p.segs_capacity = segs_capacity;
     p.ops = ops_dev;
@@ -588,9 +621,19 @@ int slamem_find_alns_device(const slamem_index* idx, const void* queries_dev, co
                             uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity, slamem_aln* segs_dev, uint64_t segs_capacity,
                             uint64_t* block_offsets_dev, uint32_t* ops_dev, uint64_t ops_capacity, uint64_t* op_offsets_dev,
                             void* workspace_dev, uint64_t workspace_bytes, void* stream, uint64_t* totals_out) {
+    return slamem_find_alns_device_gext(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, max_gap,
+                                        mismatch_penalty, xdrop, max_edits, 0, mems_capacity, segs_dev, segs_capacity, block_offsets_dev,
+                                        ops_dev, ops_capacity, op_offsets_dev, workspace_dev, workspace_bytes, stream, totals_out);
+}
+
+int slamem_find_alns_device_gext(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                                 uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty,
+                                 uint32_t xdrop, uint32_t max_edits, uint32_t end_band, uint64_t mems_capacity, slamem_aln* segs_dev,
+                                 uint64_t segs_capacity, uint64_t* block_offsets_dev, uint32_t* ops_dev, uint64_t ops_capacity,
+                                 uint64_t* op_offsets_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream, uint64_t* totals_out) {
     return find_segments_device("slamem_find_alns_device", idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands,
                                 max_gap, mismatch_penalty, xdrop, max_edits, mems_capacity, segs_dev, segs_capacity, block_offsets_dev,
-                                ops_dev, ops_capacity, op_offsets_dev, nullptr, 6, workspace_dev, workspace_bytes, stream, totals_out);
+                                ops_dev, ops_capacity, op_offsets_dev, nullptr, 6, workspace_dev, workspace_bytes, stream, totals_out, end_band);
 }
 
 int slamem_find_maps_device(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
@@ -598,9 +641,20 @@ int slamem_find_maps_device(const slamem_index* idx, const void* queries_dev, co
                             uint32_t xdrop, uint32_t max_edits, uint64_t mems_capacity, slamem_aln* segs_dev, uint64_t segs_capacity,
                             uint64_t* read_offsets_dev, uint32_t* ops_dev, uint64_t ops_capacity, uint64_t* op_offsets_dev,
                             slamem_map* reads_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream, uint64_t* totals_out) {
+    return slamem_find_maps_device_gext(idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands, max_gap,
+                                        mismatch_penalty, xdrop, max_edits, 0, mems_capacity, segs_dev, segs_capacity, read_offsets_dev,
+                                        ops_dev, ops_capacity, op_offsets_dev, reads_dev, workspace_dev, workspace_bytes, stream, totals_out);
+}
+
+int slamem_find_maps_device_gext(const slamem_index* idx, const void* queries_dev, const uint64_t* offsets_dev, uint32_t num_queries,
+                                 uint64_t query_bytes, uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty,
+                                 uint32_t xdrop, uint32_t max_edits, uint32_t end_band, uint64_t mems_capacity, slamem_aln* segs_dev,
+                                 uint64_t segs_capacity, uint64_t* read_offsets_dev, uint32_t* ops_dev, uint64_t ops_capacity,
+                                 uint64_t* op_offsets_dev, slamem_map* reads_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream,
+                                 uint64_t* totals_out) {
     return find_segments_device("slamem_find_maps_device", idx, queries_dev, offsets_dev, num_queries, query_bytes, min_len, both_strands,
                                 max_gap, mismatch_penalty, xdrop, max_edits, mems_capacity, segs_dev, segs_capacity, read_offsets_dev,
-                                ops_dev, ops_capacity, op_offsets_dev, reads_dev, 7, workspace_dev, workspace_bytes, stream, totals_out);
+                                ops_dev, ops_capacity, op_offsets_dev, reads_dev, 7, workspace_dev, workspace_bytes, stream, totals_out, end_band);
 }
 
 // -aln and -paf for a caller with host memory (reads_out: -paf; then the offsets are per read).  Four attempts: the -mem rows,
@@ -608,12 +662,13 @@ int slamem_find_maps_device(const slamem_index* idx, const void* queries_dev, co
 static int find_segments_host(const char* who, const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
                               uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
                               uint32_t max_edits, slamem_aln** segs_out, uint64_t** offsets_out, uint32_t** ops_out,
-                              uint64_t** op_offsets_out, slamem_map** reads_out, uint64_t* totals_out) {
+                              uint64_t** op_offsets_out, slamem_map** reads_out, uint64_t* totals_out, uint32_t end_band) {
     *segs_out = nullptr; *offsets_out = nullptr; *ops_out = nullptr; *op_offsets_out = nullptr;
     if (reads_out) *reads_out = nullptr;
     totals_out[0] = totals_out[1] = totals_out[2] = 0;
     FilterParams checked;
     if (int bad = resolve_filter_params(who, 0, max_gap, mismatch_penalty, xdrop, max_edits, &checked)) return bad;
+    if (int bad = set_end_band(who, end_band, &checked)) return bad;
     const uint64_t qbytes = offsets[num_queries] - offsets[0];
     const uint64_t num_blocks = (uint64_t)num_queries * (both_strands ? 2u : 1u);
     const uint64_t noff = (reads_out ? (uint64_t)num_queries : num_blocks) + 1;  // offsets that go back
@@ -639,7 +694,7 @@ static int find_segments_host(const char* who, const slamem_index* idx, const ch
     for (int attempt = 0; attempt < 4; attempt++) {
         uint64_t ws_bytes = 0;
         SLAMEM_TRY(filter_workspace_bytes(reads_out ? "slamem_find_maps_workspace_bytes" : "slamem_find_alns_workspace_bytes", reads_out ? 7 : 6,
-                                          num_queries, both_strands, qbytes, cap, ocap, max_edits, &ws_bytes));
+                                          num_queries, both_strands, qbytes, cap, ocap, max_edits, &ws_bytes, end_band));
         SLAMEM_TRY(d_segs.reserve(scap + 1));
         SLAMEM_TRY(d_ops.reserve(ocap + 1));
         SLAMEM_TRY(d_ooff.reserve(scap + 2));
@@ -647,7 +702,7 @@ static int find_segments_host(const char* who, const slamem_index* idx, const ch
         rc = find_segments_device(reads_out ? "slamem_find_maps_device" : "slamem_find_alns_device", idx, d_q.get(), d_off.get(), num_queries,
                                   qbytes, min_len, both_strands, max_gap, mismatch_penalty, xdrop, max_edits, cap, d_segs.get(), scap,
                                   d_boff.get(), d_ops.get(), ocap, d_ooff.get(), d_reads.get(), reads_out ? 7 : 6, d_ws.get(), ws_bytes, nullptr,
-                                  totals_out);
+                                  totals_out, end_band);
         if (rc != SLAMEM_ERR_CAPACITY) break;
         d_segs.release(); d_ops.release(); d_ooff.release(); d_ws.release();  // all of the old before any of the new
         if (totals_out[0] > cap) cap = totals_out[0] + 1024;
@@ -675,24 +730,40 @@ int slamem_find_alns_host(const slamem_index* idx, const char* queries, const ui
                           int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
                           slamem_aln** segs_out, uint64_t** block_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
                           uint64_t* totals_out) {
+    return slamem_find_alns_host_gext(idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty, xdrop, max_edits, 0,
+                                      segs_out, block_offsets_out, ops_out, op_offsets_out, totals_out);
+}
+
+int slamem_find_alns_host_gext(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
+                               int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
+                               uint32_t end_band, slamem_aln** segs_out, uint64_t** block_offsets_out, uint32_t** ops_out,
+                               uint64_t** op_offsets_out, uint64_t* totals_out) {
     if (!idx || !offsets || !segs_out || !block_offsets_out || !ops_out || !op_offsets_out || !totals_out || (num_queries && !queries)) {
         set_error("slamem_find_alns_host: null argument");
         return SLAMEM_ERR_ARG;
     }
     return find_segments_host("slamem_find_alns_host", idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty,
-                              xdrop, max_edits, segs_out, block_offsets_out, ops_out, op_offsets_out, nullptr, totals_out);
+                              xdrop, max_edits, segs_out, block_offsets_out, ops_out, op_offsets_out, nullptr, totals_out, end_band);
 }
 
 int slamem_find_maps_host(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
                           int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
                           slamem_aln** segs_out, uint64_t** read_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
                           slamem_map** reads_out, uint64_t* totals_out) {
+    return slamem_find_maps_host_gext(idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty, xdrop, max_edits, 0,
+                                      segs_out, read_offsets_out, ops_out, op_offsets_out, reads_out, totals_out);
+}
+
+int slamem_find_maps_host_gext(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries, uint32_t min_len,
+                               int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop, uint32_t max_edits,
+                               uint32_t end_band, slamem_aln** segs_out, uint64_t** read_offsets_out, uint32_t** ops_out,
+                               uint64_t** op_offsets_out, slamem_map** reads_out, uint64_t* totals_out) {
     if (!idx || !offsets || !segs_out || !read_offsets_out || !ops_out || !op_offsets_out || !reads_out || !totals_out || (num_queries && !queries)) {
         set_error("slamem_find_maps_host: null argument");
         return SLAMEM_ERR_ARG;
     }
     return find_segments_host("slamem_find_maps_host", idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty,
-                              xdrop, max_edits, segs_out, read_offsets_out, ops_out, op_offsets_out, reads_out, totals_out);
+                              xdrop, max_edits, segs_out, read_offsets_out, ops_out, op_offsets_out, reads_out, totals_out, end_band);
 }
 
 void slamem_host_free(void* p) { free(p); }

@@ -324,7 +324,12 @@ struct FilterParams {
     uint64_t ops_capacity;
     uint64_t* op_offsets;  // segs_capacity + 1
     slamem_map* reads;     // -paf: a record per read (then block_offsets_dev takes num_queries + 1 read offsets)
+    uint32_t end_band;     // -aln, -paf: the band Z of the gapped outer ends (-gext; 0: 4.13's ungapped ends); set_end_band sets it
 };
+constexpr uint32_t kAlnMaxEndBand = 31;
+// The one check of an end band beside a max_edits word that the resolver has accepted: at most kAlnMaxEndBand, and a band other
+// than 0 needs gap-affine costs in the word.  SLAMEM_OK and p->end_band, or SLAMEM_ERR_ARG with `who` in the message.
+int set_end_band(const char* who, uint32_t end_band, FilterParams* p);
 constexpr uint32_t kChainDefaultGap = 5000, kExtDefaultPenalty = 4, kExtDefaultXdrop = 20, kAlnDefaultEdits = 31;
 constexpr uint32_t kExtXdropUnset = 0xFFFFFFFFu, kAlnEditsUnset = 0xFFFFFFFFu, kAlnMaxEdits = 127;
 // The max_edits word of the public interface, decoded (SLAMEM_ALN_AFFINE): E, the costs of a mismatch, of a gap
@@ -434,6 +439,8 @@ uint64_t aln_workspace_bytes(const FilterBatch& b, const FilterParams& p);
 int aln_filter(void* ws, const FilterBatch& b, const FilterParams& p, slamem_mem* out_mems, uint64_t* out_boff,
                unsigned long long* host_scalars, hipStream_t stream);
 // (aln_filter = chain_pass + chain_compact into aln_chain_buffers + aln_after_chain, which -paf runs behind its own choice of chains)
+// where in -aln's workspace (and -paf's, which begins with it) the counter block lies: [5] ends listed, [6] ends replaced (-gext)
+uint64_t aln_counters_offset(const FilterBatch& b, const FilterParams& p);
 void aln_chain_buffers(void* aln_ws, const FilterBatch& b, const FilterParams& p, slamem_mem** crows_out, uint64_t** coff_out);
 int aln_after_chain(void* aln_ws, const FilterBatch& b, const FilterParams& p, uint64_t* out_boff, unsigned long long* host_scalars,
                     hipStream_t stream);

@@ -45,6 +45,19 @@ int resolve_filter_params(const char* who, uint32_t max_occ, uint32_t max_gap, u
     return SLAMEM_OK;
 }
 
+int set_end_band(const char* who, uint32_t end_band, FilterParams* p) {
+    if (end_band > kAlnMaxEndBand) {
+        set_error("%s: the end band is %u, above %u", who, end_band, kAlnMaxEndBand);
+        return SLAMEM_ERR_ARG;
+    }
+    if (end_band && !(p->max_edits >> 8)) {
+        set_error("%s: an end band needs gap-affine costs in the max_edits word (SLAMEM_ALN_AFFINE)", who);
+        return SLAMEM_ERR_ARG;
+    }
+    p->end_band = end_band;
+    return SLAMEM_OK;
+}
+
 int decode_aln_word(const char* who, uint32_t word, AlnCosts* out) {
     int affine = 0;
     const int bad = slamem_decode_aln_word(word, &out->E, &out->x, &out->o, &out->e, &affine);

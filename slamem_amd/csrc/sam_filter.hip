@@ -282,6 +282,17 @@ int slamem_find_maps_md_host(const slamem_index* idx, const char* queries, const
                              slamem_aln** segs_out, uint64_t** read_offsets_out, uint32_t** ops_out, uint64_t** op_offsets_out,
                              slamem_map** reads_out, uint64_t* totals_out, uint32_t** md_out, uint64_t** md_offsets_out,
                              uint32_t** seg_eq_out, uint32_t** primary_out, uint64_t* md_total_out) {
+    return slamem_find_maps_md_host_gext(idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty, xdrop, max_edits,
+                                         0, segs_out, read_offsets_out, ops_out, op_offsets_out, reads_out, totals_out, md_out, md_offsets_out,
+                                         seg_eq_out, primary_out, md_total_out);
+}
+
+int slamem_find_maps_md_host_gext(const slamem_index* idx, const char* queries, const uint64_t* offsets, uint32_t num_queries,
+                                  uint32_t min_len, int both_strands, uint32_t max_gap, uint32_t mismatch_penalty, uint32_t xdrop,
+                                  uint32_t max_edits, uint32_t end_band, slamem_aln** segs_out, uint64_t** read_offsets_out,
+                                  uint32_t** ops_out, uint64_t** op_offsets_out, slamem_map** reads_out, uint64_t* totals_out,
+                                  uint32_t** md_out, uint64_t** md_offsets_out, uint32_t** seg_eq_out, uint32_t** primary_out,
+                                  uint64_t* md_total_out) {
     if (!md_out || !md_offsets_out || !seg_eq_out || !primary_out || !md_total_out) {
         set_error("slamem_find_maps_md_host: null argument");
         return SLAMEM_ERR_ARG;
@@ -292,8 +303,8 @@ int slamem_find_maps_md_host(const slamem_index* idx, const char* queries, const
                   "index has none (the compact layout, or one built with the seed sections switched off)");
         return SLAMEM_ERR_ARG;
     }
-    int rc = slamem_find_maps_host(idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty, xdrop, max_edits,
-                                   segs_out, read_offsets_out, ops_out, op_offsets_out, reads_out, totals_out);
+    int rc = slamem_find_maps_host_gext(idx, queries, offsets, num_queries, min_len, both_strands, max_gap, mismatch_penalty, xdrop, max_edits,
+                                   end_band, segs_out, read_offsets_out, ops_out, op_offsets_out, reads_out, totals_out);
     if (rc != SLAMEM_OK) return rc;
     rc = md_of_host_maps(idx, num_queries, *segs_out, *read_offsets_out, *ops_out, *op_offsets_out, totals_out, md_out, md_offsets_out,
                          seg_eq_out, primary_out, md_total_out);

@@ -153,6 +153,7 @@ struct slamem_stream {
     uint32_t max_occ = 0;  // -smem: the occurrence cap of every batch (slamem_stream_set_max_occ; 0: none)
     uint32_t max_gap = 0;  // -chain: the maximum gap of every batch (slamem_stream_set_max_gap; 0: the default)
     uint32_t ext_penalty = 0, ext_xdrop = kExtXdropUnset;  // -ext, -aln: penalty and drop of every batch (slamem_stream_set_ext_params)
+    uint32_t end_band = 0;                // -aln: the band of the gapped outer ends (slamem_stream_set_end_band; 0: ungapped)
     uint32_t max_edits = kAlnEditsUnset;  // -aln: the most edits in a gap (slamem_stream_set_max_edits; kAlnEditsUnset: the default)
     slamem_pileup* pile = nullptr;          // -pile: the accumulator every batch is added to (slamem_stream_set_pileup)
     uint32_t min_mapq = 0;                  // -pile: the least mapping quality that counts
@@ -206,6 +207,7 @@ inline int job_type(const slamem_stream* s) { return s->match_type == 8 ? 7 : s-
 FilterParams slot_params(const slamem_stream* s, const Slot& sl) {
     FilterParams p = {};  // (the setters have refused what the resolver refuses)
     (void)resolve_filter_params("slamem_stream", s->max_occ, s->max_gap, s->ext_penalty, s->ext_xdrop, s->max_edits, &p);
+    (void)set_end_band("slamem_stream", s->end_band, &p);  // (both setters keep band and word consistent, so this cannot refuse)
     if (s->match_type == 5) p.column_dev = sl.d_mm.get();
     if (is_aln(s)) {
         p.segs = sl.d_segs.get(); p.segs_capacity = sl.cap;
@@ -979,8 +981,27 @@ int slamem_stream_set_max_edits(slamem_stream* s, uint32_t max_edits) {
     }
     AlnCosts costs;
     if (decode_aln_word("slamem_stream_set_max_edits", max_edits, &costs) != SLAMEM_OK) return SLAMEM_ERR_ARG;
+    if (s->end_band && !costs.affine) {
+        set_error("slamem_stream_set_max_edits: the stream has an end band (slamem_stream_set_end_band), which needs gap-affine costs in the word");
+        return SLAMEM_ERR_ARG;
+    }
     if (has_batches(s, "slamem_stream_set_max_edits", "set the limit")) return SLAMEM_ERR_ARG;
     s->max_edits = max_edits;
+    return SLAMEM_OK;
+}
+
+int slamem_stream_set_end_band(slamem_stream* s, uint32_t end_band) {
+    if (!s) { set_error("slamem_stream_set_end_band: null argument"); return SLAMEM_ERR_ARG; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (!is_aln(s) && end_band) {
+        set_error("slamem_stream_set_end_band: an end band needs match type 6 (-aln)");
+        return SLAMEM_ERR_ARG;
+    }
+    FilterParams p = {};
+    p.max_edits = s->max_edits == kAlnEditsUnset ? 0u : s->max_edits;
+    if (set_end_band("slamem_stream_set_end_band", end_band, &p) != SLAMEM_OK) return SLAMEM_ERR_ARG;
+    if (has_batches(s, "slamem_stream_set_end_band", "set the band")) return SLAMEM_ERR_ARG;
+    s->end_band = end_band;
     return SLAMEM_OK;
 }
 

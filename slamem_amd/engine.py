@@ -295,20 +295,22 @@ class Index:
         return self._find(queries, offsets, min_len, both_strands, False, False, False, 0, False, 0, True, penalty, xdrop)
 
     def find_alns(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-                  xdrop=None, max_edits=None, capacities=None, gap_costs=None):
+                  xdrop=None, max_edits=None, capacities=None, gap_costs=None, end_band: int = 0):
         """-aln mode: (segments, block_offsets, ops, op_offsets) -- per strand block the gapped alignment built on its best
         chain.  segments: a structured array (ref_pos, query_pos, ref_len, query_len, edits), the segments
         of a block with the query start descending; block_offsets: per strand block; ops: uint32 CIGAR operations, length << 4
         | code with BAM's codes (CIGAR_OPS), left to right in the scanned strand; op_offsets: per segment.  max_gap, penalty
         and xdrop as for find_chains and find_exts; max_edits: the most edits in one gap (None: 31; at most 127).
         gap_costs=(x, o, e): the gaps are closed at gap-affine cost (aln_word); None: unit cost.
+        end_band=Z (1 to 31, with gap_costs): each of a block's two outer ends may hold indels of at most Z letters
+        of net diagonal drift -- the gapped X-drop attempt where it scores more than the ungapped side; 0: ungapped ends.
         capacities: (mems, segments, operations) to run with exactly that room (slamem.capi.SlamemError with
         SLAMEM_ERR_CAPACITY and .totals = what is needed when it is too small); None: grow until the batch fits."""
         return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, aln_word(max_edits, gap_costs), capacities,
-                              False)
+                              False, end_band=_end_band(end_band, gap_costs))
 
     def map_reads(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
-                  xdrop=None, max_edits=None, capacities=None, md: bool = False, gap_costs=None):
+                  xdrop=None, max_edits=None, capacities=None, md: bool = False, gap_costs=None, end_band: int = 0):
         """-paf mode: (segments, read_offsets, ops, op_offsets, reads) -- one mapping per read.  Per read the
         strand block whose best chain scores highest is the primary one (the forward block on a tie) and only that block is
         aligned, as find_alns aligns it; segments, ops and op_offsets are as find_alns returns them, in the coordinates of the
@@ -320,7 +322,7 @@ class Index:
         their offsets per segment, the letters under = per segment, and per read the index of its primary segment within the
         read's range (0xFFFFFFFF: the read has no segment)."""
         return self._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, aln_word(max_edits, gap_costs), capacities,
-                              True, md=md)
+                              True, md=md, end_band=_end_band(end_band, gap_costs))
 
     def _md_pass(self, segs, nseg, roff, num, ops, ooff, cap):
         """slamem_maps_md_device over a mapped batch as it lies on the device, with room for cap entries: (md, md_offsets, seg_eq,
@@ -345,7 +347,7 @@ class Index:
                 prim[:num].cpu().numpy().view(np.uint32))
 
     def _aln_like(self, queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, max_edits, capacities, mapping,
-                  pile=None, md=False):
+                  pile=None, md=False, end_band=0):
         """pile: (Pileup, min_mapq) -- the batch's mappings are added to the accumulator on the device and only the read records
         come back (Pileup.add)."""
         dev = self.device
@@ -364,10 +366,10 @@ class Index:
         L = capi.lib()
         boff = torch.zeros((num if mapping else nb) + 1, dtype=torch.int64, device=dev)
         recs = torch.zeros((num + 1) * 12, dtype=torch.uint8, device=dev) if mapping else None
-        ws_bytes = L.slamem_find_maps_workspace_bytes if mapping else L.slamem_find_alns_workspace_bytes
+        ws_bytes = L.slamem_find_maps_workspace_bytes_gext if mapping else L.slamem_find_alns_workspace_bytes_gext
         while True:
             need = C.c_uint64()
-            capi.check(ws_bytes(num, int(both_strands), qbytes, cap, ocap, edits, C.byref(need)))
+            capi.check(ws_bytes(num, int(both_strands), qbytes, cap, ocap, edits, int(end_band), C.byref(need)))
             ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
             segs = torch.zeros((scap + 1) * 5, dtype=torch.int32, device=dev)
             ops = torch.zeros(ocap + 1, dtype=torch.int32, device=dev)
@@ -376,13 +378,13 @@ class Index:
             with torch.cuda.device(dev):
                 torch.cuda.current_stream(dev).synchronize()
                 if mapping:
-                    rc = L.slamem_find_maps_device(self._h, _ptr(qd), _ptr(od), num, qbytes, int(min_len), int(both_strands),
-                                                   int(max_gap), int(penalty), _xdrop_arg(xdrop), edits, cap, _ptr(segs), scap,
+                    rc = L.slamem_find_maps_device_gext(self._h, _ptr(qd), _ptr(od), num, qbytes, int(min_len), int(both_strands),
+                                                   int(max_gap), int(penalty), _xdrop_arg(xdrop), edits, int(end_band), cap, _ptr(segs), scap,
                                                    _ptr(boff), _ptr(ops), ocap, _ptr(ooff), _ptr(recs), _ptr(ws), need.value, None,
                                                    totals)
                 else:
-                    rc = L.slamem_find_alns_device(self._h, _ptr(qd), _ptr(od), num, qbytes, int(min_len), int(both_strands),
-                                                   int(max_gap), int(penalty), _xdrop_arg(xdrop), edits, cap, _ptr(segs), scap,
+                    rc = L.slamem_find_alns_device_gext(self._h, _ptr(qd), _ptr(od), num, qbytes, int(min_len), int(both_strands),
+                                                   int(max_gap), int(penalty), _xdrop_arg(xdrop), edits, int(end_band), cap, _ptr(segs), scap,
                                                    _ptr(boff), _ptr(ops), ocap, _ptr(ooff), _ptr(ws), need.value, None, totals)
             if rc == capi.SLAMEM_ERR_CAPACITY and capacities is None:
                 cap, scap, ocap = max(cap, int(totals[0])), max(scap, int(totals[1])), max(ocap, int(totals[2]))
@@ -454,6 +456,16 @@ def aln_word(max_edits=None, gap_costs=None):
     if o + e * E > 512:
         raise ValueError(f"gap_costs: the bound on a gap's cost, o + e * max_edits = {o + e * E}, is above 512")
     return E | x << 8 | o << 16 | e << 24
+
+
+def _end_band(end_band, gap_costs) -> int:
+    """end_band= checked: 0 to 31, and a band other than 0 needs gap_costs."""
+    z = int(end_band)
+    if not 0 <= z <= 31:
+        raise ValueError("end_band must be in [0, 31]")
+    if z and gap_costs is None:
+        raise ValueError("end_band is the band of the gapped outer ends: it needs gap_costs=(x, o, e)")
+    return z
 
 
 def _xdrop_arg(xdrop) -> int:
@@ -566,7 +578,7 @@ class Pileup:
 
     def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0,
             xdrop=None, max_edits=None, min_mapq: int = 0, lowq=None, dedup: bool = False, quals=None, phred_offset: int = 33,
-            gap_costs=None):
+            gap_costs=None, end_band: int = 0):
         """Maps the batch as Index.map_reads does and adds the mappings of the reads with mapq >= min_mapq (0 to 60) to the table,
         on the device: segments and operations are not downloaded.  Returns the read records of map_reads (MAP_DTYPE).  lowq: the
         batch's low-quality mask (DESIGN.md 4.21), a uint64 array of at least (offsets[-1] + 63) // 64 words (numpy, or a tensor on
@@ -576,7 +588,7 @@ class Pileup:
         per read: 0 kept or no candidate, 1 duplicate (not piled), 2 no room in the filter's table (piled).  quals (an accumulator
         made with quals=True): the batch's quality bytes, a uint8 array (numpy, or a tensor on the index's device)
         of at least offsets[-1] bytes in which byte offsets[r] + i belongs to letter i of read r as given, Phred + phred_offset; it
-        works with lowq= and dedup= as they are."""
+        works with lowq= and dedup= as they are.  gap_costs and end_band: as for Index.map_reads."""
         if not 0 <= int(min_mapq) <= 60:
             raise ValueError("min_mapq must be in [0, 60]")
         if quals is not None:
@@ -604,7 +616,8 @@ class Pileup:
             if lowq.shape[0] < need:
                 raise ValueError(f"lowq has {lowq.shape[0]} words, the batch's letters need {need}")
         recs = self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, aln_word(max_edits, gap_costs), None, True,
-                                    pile=(self, int(min_mapq), lowq, bool(dedup), None if quals is None else (quals, int(phred_offset))))
+                                    pile=(self, int(min_mapq), lowq, bool(dedup), None if quals is None else (quals, int(phred_offset))),
+                                    end_band=_end_band(end_band, gap_costs))
         return (recs, self.last_dup) if dedup else recs
 
     def _add_device(self, qd, od, num, segs, roff, ops, ooff, recs, min_mapq, lowq=None, dedup=False, quals=None):
@@ -933,14 +946,16 @@ class MapStats:
         self.last_add_ms = 0.0  # device time of the last add's own kernel (the mapping in front of it not counted)
 
     def add(self, queries, offsets, min_len: int = 20, both_strands: bool = False, max_gap: int = 0, penalty: int = 0, xdrop=None,
-            max_edits=None, min_mapq: int = 0, quals=None, phred_offset: int = 33, gap_costs=None):
+            max_edits=None, min_mapq: int = 0, quals=None, phred_offset: int = 33, gap_costs=None, end_band: int = 0):
         """Maps the batch as Index.map_reads does and adds it to the table on the device: segments and operations are not
         downloaded.  Returns the read records of map_reads (MAP_DTYPE).  quals: the batch's quality bytes, a uint8 array (numpy, or
         a tensor on the index's device) of at least offsets[-1] bytes in which byte offsets[r] + i belongs to letter i of read r as
-        given, Phred + phred_offset (0 to 126); None: the sections q_aln and q_mm stay as they are."""
+        given, Phred + phred_offset (0 to 126); None: the sections q_aln and q_mm stay as they are.  gap_costs and end_band: as for
+        Index.map_reads."""
         quals = self._check(offsets, min_mapq, quals, phred_offset)
         return self.index._aln_like(queries, offsets, min_len, both_strands, max_gap, penalty, xdrop, aln_word(max_edits, gap_costs), None, True,
-                                    pile=(self, int(min_mapq), None, False, None if quals is None else (quals, int(phred_offset))))
+                                    pile=(self, int(min_mapq), None, False, None if quals is None else (quals, int(phred_offset))),
+                                    end_band=_end_band(end_band, gap_costs))
 
     def add_mapped(self, queries, offsets, result, min_mapq: int = 0, quals=None, phred_offset: int = 33) -> None:
         """Adds a batch that is mapped already: result is what Index.map_reads returned for (queries, offsets) -- its first five
@@ -1139,9 +1154,10 @@ class Stream:
                  mam: bool = False, mum: bool = False, smem: bool = False, max_occ: int = 0, chain: bool = False,
                  max_gap: int = 0, ext: bool = False, penalty: int = 0, xdrop=None, aln: bool = False, max_edits=None, paf: bool = False,
                  pile: "Pileup" = None, min_mapq: int = 0, md: bool = False, dedup: bool = False, quals: bool = False,
-                 phred_offset: int = 33, stats: "MapStats" = None, gap_costs=None):
+                 phred_offset: int = 33, stats: "MapStats" = None, gap_costs=None, end_band: int = 0):
         """gap_costs=(x, o, e) (with aln, paf or pile): the gaps of every batch are closed at gap-affine cost, as
         Index.find_alns(gap_costs=) closes them.
+        end_band=Z (with gap_costs): the outer ends of every batch as Index.find_alns(end_band=) builds them.
         stats=<MapStats> (with paf=True or pile=<Pileup>): every batch is also added to the table on the device,
         behind its map pass, counting the reads with mapq >= min_mapq; with quals=True the batches come through submit_quals and
         their quality bytes feed the table's quality sections (on a pile= stream whose accumulator has quality sums, they feed both).
@@ -1177,6 +1193,7 @@ class Stream:
         if gap_costs is not None and not (aln or paf):
             raise ValueError("gap_costs are the costs of aln and paf: it needs aln=True, paf=True or pile=<Pileup>")
         max_edits = aln_word(max_edits, gap_costs)
+        end_band = _end_band(end_band, gap_costs)
         if md and not (paf and pile is None):
             raise ValueError("md is the MD pass of paf: it needs paf=True")
         self.paf = bool(paf)
@@ -1197,6 +1214,8 @@ class Stream:
                 capi.check(capi.lib().slamem_stream_set_ext_params(self._h, int(penalty), _xdrop_arg(xdrop)))
             if max_edits is not None:
                 capi.check(capi.lib().slamem_stream_set_max_edits(self._h, int(max_edits)))
+            if end_band:
+                capi.check(capi.lib().slamem_stream_set_end_band(self._h, end_band))
             if pile is not None:
                 capi.check(capi.lib().slamem_stream_set_pileup(self._h, pile._h, int(min_mapq)))
             if dedup:

@@ -682,6 +682,7 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-aln\tgapped alignment of the best chain of each strand; writes ref_pos query_pos ref_len query_len edits cigar\n");
     printf("\t-maxed\twith -aln: most edits in the gap between two chained MEMs, 0 to 127 (default=31); -mgap, -pen, -xdrop apply\n");
     printf("\t-affine\twith -aln and every mode that takes -maxed: X,O,E, gap-affine costs of the gap between two chained MEMs: X per mismatch (1 to 31), O per gap opened (0 to 63), E per gap letter (1 to 31); the gap closes when its cost is at most O + E * maxed (at most 512); without it: unit costs\n");
+    printf("\t-gext\twith -affine: Z, a whole number from 1 to 31; each of an alignment's two outer ends may hold indels of at most Z letters of net diagonal drift (gapped X-drop extension); without it: ungapped ends\n");
     printf("\t-paf\tone mapping per read with a mapping quality, written as PAF with a cg:Z: CIGAR; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-sam\tthe mappings of -paf written as SAM: a line per segment with soft clips, NM:i:, MD:Z: (built on the GPU), s1:i:, s2:i: and SA:Z:; an unmapped read gets a line with flag 4; FASTQ queries keep their qualities; -mgap, -pen, -xdrop, -maxed apply\n");
     printf("\t-pile\tper-base pileup of the mappings of -paf: record, position, letter and the counts A C G T D I; -mgap, -pen, -xdrop, -maxed apply\n");
@@ -749,6 +750,7 @@ typedef struct {
     slamem_index *gpus[16];
     int ngpu;
     slamem_pileup *piles[16];
+    int gext;              /* -gext Z: the band of the gapped outer ends; 0: the option is absent */
     int affine, costs[3];  /* -affine X,O,E: gap-affine costs of the gaps between chain anchors */
     int stats;             /* -stats: the mapping QC table; runs as -paf, nothing is formatted per read */
     int stats_fasta;       /* ... a batch without quality bytes was submitted (said once) */
@@ -801,6 +803,7 @@ static int parse_and_refuse(run_t *R, int *status) {
     if (rc == -1) exit_message(refusal);
     R->sb = slh_parse_sb_params(argc, argv, &R->fs) & 1; /* (refused above when the value of -fs is not one) */
     R->affine = slh_parse_affine(argc, argv, &R->costs[0], &R->costs[1], &R->costs[2]) > 0; /* (the same) */
+    if (slh_parse_gext(argc, argv, &R->gext) <= 0) R->gext = 0;
     memset(&R->gtp, 0, sizeof(R->gtp));
     if (R->p.gt) { /* host arithmetic: the three costs of a letter at the error rate of -err */
         uint32_t costs[3];
@@ -953,6 +956,7 @@ static void open_output(run_t *R) {
     if (t == 6 || t == 7 || t == 8)
         say(" ; maximum gap = %d ; mismatch penalty = %d ; X-drop = %d ; maximum edits = %d", gap, pen, xdrop, p->max_edits >= 0 ? p->max_edits : 31);
     if (R->affine) say(" ; gap costs = %d,%d,%d", R->costs[0], R->costs[1], R->costs[2]);
+    if (R->gext) say(" ; end band = %d", R->gext);
     if (t == 8 || R->stats) say(" ; minimum mapping quality = %d", p->min_mapq);
     if (p->bq_given == 1) say(" ; minimum base quality = %d", p->min_bq); /* (only when asked for: the line of a run without -bq stays) */
     if (p->gt) say(" ; minimum depth = %d ; ploidy = %d ; error rate = %d Phred ; prior = %d Phred ; minimum quality = %d", p->min_depth, p->gt_ploidy, p->gt_err, p->gt_hetq, p->gt_qual);
@@ -1119,6 +1123,7 @@ static void open_streams(run_t *R) {
         if (rc == SLAMEM_OK && (t == 5 || t == 6 || t == 7 || t == 8)) rc = slamem_stream_set_ext_params(s, (uint32_t)p->ext_pen, xdrop);
         if (rc == SLAMEM_OK && (t == 6 || t == 7 || t == 8))
             rc = slamem_stream_set_max_edits(s, slh_aln_word(p->max_edits, R->affine, R->costs[0], R->costs[1], R->costs[2]));
+        if (rc == SLAMEM_OK && R->gext) rc = slamem_stream_set_end_band(s, (uint32_t)R->gext);
         if (rc == SLAMEM_OK && p->sam) rc = slamem_stream_set_md(s, 1); /* every batch also goes through the MD pass */
         if (rc == SLAMEM_OK && R->stats) { /* one table per GPU: they are added up before the report */
             rc = slamem_stats_create(R->gpus[g], &R->tables[g]);

@@ -934,7 +934,7 @@ typedef struct {
     const char *refusal; /* of a bad value; a mode's: of another mode beside it */
 } option_row;
 enum { O_MEM, O_MAM, O_MUM, O_SMEM, O_OCC, O_CHAIN, O_MGAP, O_EXT, O_PEN, O_XDROP, O_ALN, O_MAXED, O_PAF, O_SAM, O_PILE, O_MINQ, O_BQ,
-       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_WQ, O_EVS, O_STATS, O_AFFINE,
+       O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_WQ, O_EVS, O_STATS, O_AFFINE, O_GEXT,
        O_L, O_O, O_B, O_N, O_M, O_R, O_V, O_S, O_C, NUM_OPTIONS };
 #define PEN_XDROP "Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"
 static const option_row OPTIONS[NUM_OPTIONS] = {
@@ -976,6 +976,7 @@ static const option_row OPTIONS[NUM_OPTIONS] = {
     [O_EVS] = {"evs", 0, 0, V_POW2, 0, 64, 1ull << 31, 0, "Option -evs needs a power of two of at least 64"},
     [O_STATS] = {"stats", 0, 0, V_NONE, 7, 0, 0, 0, "Option -stats excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -sam, -pile, -sites, -vcf, -cons and -depth"},
     [O_AFFINE] = {"affine", 0, 0, V_COSTS, 0, 0, 0, -1, "Option -affine needs three whole numbers X,O,E: X from 1 to 31, O from 0 to 63, E from 1 to 31, separated by commas"},
+    [O_GEXT] = {"gext", 0, 0, V_INT, 0, 1, 31, 0, "Option -gext needs a whole number from 1 to 31"},
     [O_L] = {"l", 0, 0, V_ATOI, 0, 0, 0, 20, NULL},
     [O_O] = {"o", 0, 0, V_INDEX, 0, 0, 0, -1, NULL},
     [O_B] = {"b", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
@@ -1139,6 +1140,7 @@ int slh_parse_affine(int argc, char **argv, int *x_out, int *o_out, int *e_out) 
     *e_out = rc > 0 ? (int)((v >> 16) & 0xFF) : 0;
     return rc;
 }
+int slh_parse_gext(int argc, char **argv, int *out) { return scan_whole(argc, argv, O_GEXT, out); }
 uint32_t slh_aln_word(int max_edits, int affine, int x, int o, int e) {
     if (!affine) return max_edits >= 0 ? (uint32_t)max_edits : SLAMEM_ALN_EDITS_DEFAULT;
     return SLAMEM_ALN_AFFINE(max_edits >= 0 ? max_edits : 31, x, o, e);
@@ -1243,7 +1245,7 @@ static int refuse(const char **refusal, const char *msg, int rc) {
 
 int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     slh_options *o = &r->o;
-    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct, sb, fs, aff, costs[3];
+    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct, sb, fs, aff, costs[3], gx, band;
     *refusal = NULL;
     memset(r, 0, sizeof(*r));
     if (slh_parse_options(argc, argv, o) != 0) return refuse(refusal, "Out of memory", -1);
@@ -1269,6 +1271,7 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     dd = slh_parse_dedup(argc, argv, &r->dd_slots);
     sb = slh_parse_sb_params(argc, argv, &fs); /* (the values are the caller's to ask for: slh_run keeps its layout) */
     aff = slh_parse_affine(argc, argv, &costs[0], &costs[1], &costs[2]); /* (the same) */
+    gx = slh_parse_gext(argc, argv, &band); /* (the same) */
     r->dedup = dd > 0 && (dd & 1);
     if (o->usage || o->hidden_sort || o->hidden_clean) return 0; /* (the caller's business, before any refusal) */
 
@@ -1291,6 +1294,9 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     REFUSE_IF(aff && t != 6 && t != 7 && t != 8, "Option -affine needs -aln");
     REFUSE_IF(aff && (uint32_t)(costs[1] + costs[2] * (r->max_edits >= 0 ? r->max_edits : 31)) > SLAMEM_ALN_COST_MAX,
               "Option -affine: a gap's cost is bounded by O + E * maxed, which may be at most 512");
+    REFUSE_IF(gx < 0, OPTIONS[O_GEXT].refusal);
+    REFUSE_IF(gx && t != 6 && t != 7 && t != 8, "Option -gext needs -aln");
+    REFUSE_IF(gx && !aff, "Option -gext needs -affine");
     REFUSE_IF(mapq < 0, OPTIONS[O_MINQ].refusal);
     REFUSE_IF(mapq && t != 8 && !has_option(argc, argv, O_STATS), "Option -minq needs -pile");
     REFUSE_IF(r->bq_given < 0, OPTIONS[O_BQ].refusal);

@@ -125,6 +125,8 @@ int slh_parse_max_edits(int argc, char **argv, int *out);
  * (SLAMEM_ALN_AFFINE; max_edits < 0: the default), and that word's fields E, x, o, e with the rule it breaks (0: none) */
 int slh_parse_affine(int argc, char **argv, int *x_out, int *o_out, int *e_out);
 uint32_t slh_aln_word(int max_edits, int affine, int x, int o, int e);
+/* -gext Z: 0 absent (*out = 0), 1 there with the band 1..31, -1 refused */
+int slh_parse_gext(int argc, char **argv, int *out);
 int slh_aln_word_decode(uint32_t word, uint32_t *fields_out, int *affine_out);
 int slh_parse_min_mapq(int argc, char **argv, int *out);
 int slh_parse_min_bq(int argc, char **argv, int *out);
