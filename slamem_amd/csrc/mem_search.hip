@@ -2454,14 +2454,20 @@ __global__ void __launch_bounds__(256) k_prefilter_list(SearchArgs A, const uint
 //      64-byte line (and the spill list behind a bucket of 13 to 28 k-mers) gives every text position of the window AND of
 //      its reverse complement -- the window of the reverse strand that covers the same letters (strand offset len - k - o;
 //      those offsets form a residue class mod s too, so the reverse strand's MEMs all hold one).  One lane per window, in two
-//      rounds when the windows lie close: every m-th window first; a window of the other kind that lies inside a run a
-//      first-round compare measured, and whose k-mer occurs once in the text (a plane of the text units), is not looked up
-//      (one strand asked for: first-round hits in the other orientation are compared too, for these marks only);
-//   2. a hit (strand, text position p, strand offset o) is a diagonal d = p - o; the MEM around the window is the run of
-//      agreeing letters on that diagonal: the strand (bit-planes in LDS) XOR the text (four 32-byte units = the 192 letters
-//      from d on), one lane per compare.  A run that holds a first-round window is reported by the first of those, one that
-//      holds none by its first window (a hit whose neighbour window hit the same diagonal is dropped before the compare when
-//      the two windows overlap or touch); a window that is its own reverse complement is compared on both strands;
+//      rounds when the windows lie close: a few windows spread over the read first; a window of the other kind that lies
+//      inside k agreeing letters a first-round compare measured, and whose k-mer occurs once in the text (a plane of the text
+//      units), is not looked up (one strand asked for: first-round hits in the other orientation are compared too, for these
+//      marks only);
+//   2. a hit (strand, text position p, strand offset o) is a diagonal d = p - o.  Within a wave a (read, strand, diagonal) is
+//      compared at most once: the strand (bit-planes in LDS) XOR the text (four 32-byte units = the 192 letters from d on),
+//      one lane per compare.  That compare reports EVERY run of at least L agreeing letters on the diagonal as a MEM, marks
+//      every window that lies inside a run of at least k agreeing letters and occurs once in the text as accounted for, and
+//      stays in the wave's job list, where later hits on the same diagonal find it and are dropped.  This is exact: a MEM of
+//      at least L letters holds a window at a multiple of s.  If that window is looked up, the table (it is exact) hits the
+//      MEM's diagonal, which is compared now or was compared before -- and that compare reported the MEM.  If the window
+//      was marked, it was marked under its only occurrence, on that same diagonal, by a compare that reported the MEM.  A
+//      marked window in a run shorter than L has no MEM to lose.  A k-mer that is its own reverse complement never counts as
+//      occurring once; a window that is its own reverse complement is compared on both strands;
 //   3. the MEMs of a strand are ranked in the reference's emission order -- start descending, then length descending
 //      (slamem.c:114,139-193: the scan runs right to left, a position reports its deepest interval first), MEMs with the same
 //      start and length as the rows of the suffix array lie around the interval the walk came up from (slamem.c:140,165:
@@ -2514,7 +2520,7 @@ struct SeedWave {
     uint32_t bad[R];                    // the read holds a letter that is not A,C,G,T (and the text holds such letters too)
     uint64_t pn[R][NW + 1];             // forward strand, bit per letter: not A,C,G,T (a text without such letters: it agrees with nothing)
     uint32_t hasn;                      // some read of the wave has such a letter
-    unsigned long long expl[R];         // bit per window of a read: its only occurrence in the text is accounted for (round A)
+    uint64_t expl[R][NW];               // bit per letter of the forward strand: the window that starts there is accounted for (round A)
     union {
         uint16_t ring[128];             // window ids (read << 8 | window) waiting for a full trip
         unsigned long long smask[2 * R];  // ... later: per strand, which MEMs of the wave's list are its own
@@ -2522,6 +2528,9 @@ struct SeedWave {
     uint32_t flags;                     // bit per read: it is left to K8 (both strands)
     uint32_t pad[3];
 };
+// (four blocks of four waves a CU: 160 KB of LDS, handed out 1,280 bytes at a time.  No margin is left: a block takes 40,832
+//  bytes, 40,960 as allocated, and four of those are the 160 KB -- one more word per read here costs a block a CU)
+static_assert((sizeof(SeedWave<3, SLAMEM_SEED_READS>) * 4u + 1279u) / 1280u * 1280u * 4u <= 160u * 1024u, "the three-word form runs four blocks a CU");
 
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2536,6 +2545,30 @@ __device__ __forceinline__ uint64_t bits_below(int x) {  // the bits [0, x)
     return c == 0 ? 0ull : (~0ull >> (64 - c));
 }
 __device__ __forceinline__ uint64_t bits_range(int lo, int hi) { return bits_below(hi) & ~bits_below(lo); }
+// a value of N words: its bits [sh, sh + 64 N), zeros coming in (sh in 0..63); its lowest set bit (there is one); without it
+template <uint32_t N>
+__device__ __forceinline__ void shr_words(const uint64_t (&x)[N], uint32_t sh, uint64_t (&y)[N]) {
+#pragma unroll
+    for (uint32_t w = 0; w < N; w++) y[w] = funnel64(x[w], w + 1u < N ? x[w + 1u] : 0ull, sh);
+}
+template <uint32_t N>
+__device__ __forceinline__ uint32_t lowest_bit(const uint64_t (&x)[N]) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int w = (int)N - 1; w >= 0; w--)
+        if (x[w]) r = 64u * (uint32_t)w + (uint32_t)__ffsll((unsigned long long)x[w]) - 1u;
+    return r;
+}
+template <uint32_t N>
+__device__ __forceinline__ void drop_lowest_bit(uint64_t (&x)[N]) {
+    bool done = false;
+#pragma unroll
+    for (uint32_t w = 0; w < N; w++) {
+        const bool here = !done && x[w] != 0ull;
+        x[w] = here ? x[w] & (x[w] - 1ull) : x[w];
+        done = done || here;
+    }
+}
 __device__ __forceinline__ uint32_t sel4(const uint4& v, uint32_t a) {
     const uint32_t lo = (a & 1u) ? v.y : v.x, hi = (a & 1u) ? v.w : v.z;
     return (a & 2u) ? hi : lo;
@@ -2758,27 +2791,37 @@ __global__ void __launch_bounds__(256, SLAMEM_SEED_WAVES) k_seed_mems(SearchArgs
     wave_sync();
     // ---- which windows are looked up, and when ----------------------------------------------------------------------------
     // Two rounds when the windows lie close (mstep > 1).  Round A looks up every mstep-th window of a read and compares its hits;
-    // a compare that finds the exact run [a, b) around its window also reads the "occurs once" plane of the text under it: a
-    // window of the other kind that lies inside [a, b) and whose k-mer occurs once in the text has its ONLY occurrence on this
+    // a compare measures the whole diagonal and also reads the "occurs once" plane of the text under it: a window of the other
+    // kind that lies inside k agreeing letters and whose k-mer occurs once in the text has its ONLY occurrence on this
     // diagonal, where it is accounted for -- its lookup would bring that one hit and nothing else, so it is not made.  Round B
-    // looks up what is left: the windows with an error in them and the repeats (headline batch: 27 windows a read, 72 % of
-    // them free of errors: 9 lookups in round A, 5-6 in round B).  A match that holds a round-A window is reported in round A
-    // by the first of those (forward offset); one that holds none, in round B by its first window.
-    // (as many windows apart as still overlap or touch, k / s -- 3 on the headline, 6 for 18-letter seeds at -l 20 -- and at
-    //  least every second one while the windows lie within 12 letters of each other)
+    // looks up what is left: the windows with an error in them and the repeats.  Round A only has to find a read's diagonal
+    // once, so it takes kSeedProbes windows spread evenly over the longest read of the wave (headline batch: 27 windows a
+    // read, 72 % of them free of errors: 3 lookups in round A, the 7-8 windows with an error and the repeats in round B; a
+    // read none of whose probes is free of errors, 0.28^3 = 2 % there, has all its windows looked up in round B).  More
+    // probes buy little: each costs every read a lookup, and saves (27 - probes) lookups only for the reads the others missed.
+    // Never closer than the stride that was used while a run was reported by a round-A window inside it (as many windows
+    // apart as still overlap or touch, k / s, and at least every second one while the windows lie within 12 letters of each
+    // other); one round where that rule gave one (few windows a read: -l 50).
+    constexpr uint32_t kSeedProbes = 3;
     const uint32_t mfit = k / s > 6u ? 6u : k / s;
-    const uint32_t mstep = A.seed_step ? A.seed_step : mfit >= 3u ? mfit : s <= 12u ? 2u : 1u;
+    const uint32_t mnear = mfit >= 3u ? mfit : s <= 12u ? 2u : 1u;
 
     const bool wave_hasn = __builtin_amdgcn_readfirstlane((int)S.hasn) != 0;
     uint32_t lg_slots = 0;  // lanes a read takes in the queueing of its windows: the power of two that holds the most windows of a read of the wave
+    uint32_t nw_max = 0;    // the most windows of a read of the wave
     {
         const uint32_t nwl = lane < nr ? S.nwin[lane] : 0u;
 #pragma unroll
         for (uint32_t t = 1, lg = 1; t <= 32u; t <<= 1, lg++)
             if (__ballot(nwl > t) != 0ull) lg_slots = lg;
+#pragma unroll
+        for (uint32_t t = 64u; t != 0u; t >>= 1)
+            if (__ballot(nwl >= nw_max + t) != 0ull) nw_max += t;
     }
-    if (lane < R) S.expl[lane] = 0ull;
-    uint32_t njobs = 0, nmems = 0;
+    const uint32_t mfar = (nw_max + kSeedProbes - 1u) / kSeedProbes;
+    const uint32_t mstep = A.seed_step ? A.seed_step : mnear == 1u ? 1u : mfar > mnear ? mfar : mnear;  // (at most 22: a read has at most 64 windows)
+    for (uint32_t i = lane; i < R * NW; i += 64u) (&S.expl[0][0])[i] = 0ull;
+    uint32_t njobs = 0, jfirst = 0, nmems = 0;  // (the job list: jfirst jobs that were compared, then those that wait)
 
     // (the lookups and the compares in two forms, chosen per wave: with the code for reads that hold a letter which is not
     //  A,C,G,T, and without it -- merely compiling that code into the one form cost the headline batch 3.7 %)
@@ -2831,31 +2874,27 @@ __global__ void __launch_bounds__(256, SLAMEM_SEED_WAVES) k_seed_mems(SearchArgs
         // a window that is its own reverse complement lies in both strands: every hit is a compare for each
         const bool both = pal != 0u && strands == 2u;
         if (kStats && both && hits) atomicAdd(A.stats + SC_SEED_WHY + 2u, 1ull);  // (counted, no longer a reason to leave the read)
-        // Every hit is a compare -- except one whose neighbour (the lane before: the window `step` windows earlier in the forward
-        // strand of the same read) hit the same diagonal while the two windows overlap or touch: they lie in the same match and
-        // that window, or one before it, reports the MEM.  (The neighbour's first hit is looked at; a hit this misses is
-        // sorted out by its compare.)
+        // Every hit is a job -- except one whose neighbour (the lane before: the window `step` windows earlier in the forward
+        // strand of the same read) hit the same diagonal: that hit, or one before it, is in the job list, and one compare does
+        // the whole diagonal.  (A lane's n-th hit looks at the neighbour's n-th: neighbouring windows inside a repeat meet its
+        // copies in the same order, and a trip's worth of such windows would not fit the list otherwise.  A cheap first
+        // filter; what it misses is settled against the job list before the compares.)
         const uint32_t e1 = hits ? (uint32_t)__ffs((int)hits) - 1u : 0u;
         const uint32_t p1 = sel12(b0, b1, b2, e1);
         const uint32_t st1 = (rev >> e1) & 1u;
         const uint32_t dist = step * s;  // letters between the neighbour's window and this one
-        uint32_t pn = 0, pp1 = 0, ps1 = 0;  // the neighbour's first hit: position and strand (positions take all 32 bits at 3.1 Gbp)
-        if (dist <= k) {
-            pp1 = __shfl_up(p1, 1);
-            ps1 = __shfl_up(hits ? st1 : 2u, 1);
-            const uint32_t pent = __shfl_up(act ? ent : 0xFFFFFFFFu, 1);
-            pn = (lane == 0u || wi < step || pent != ent - step || ps1 == 2u) ? 0u : 1u;
-        }
-        const uint32_t njobs0 = njobs;
-        auto push = [&](bool hv, uint32_t p, uint32_t st) {
+        const uint32_t pent = __shfl_up(act ? ent : 0xFFFFFFFFu, 1);
+        const bool pn = !(lane == 0u || wi < step || pent != ent - step);  // the lane before holds the neighbour window
+        // (pp, ps: the neighbour's hit, position and strand -- 2: none; positions take all 32 bits at 3.1 Gbp)
+        auto push = [&](bool hv, uint32_t p, uint32_t st, uint32_t pp, uint32_t ps) {
             const uint32_t w = st ? p + dist : p - dist;
-            const bool job = hv && !(pn && pp1 == w && ps1 == st);
+            const bool job = hv && !(pn && pp == w && ps == st);
             const unsigned long long qb = __ballot(job);
             const uint32_t at = njobs + (uint32_t)__popcll(qb & below);
             if (job && at < SeedWave<NW, R>::kJobs) {
                 S.job_p[at] = p;
                 S.job_x[at] = (st ? Lr - k - o : o) | (st << 15) | (rs << 16);
-            }
+            } else if (job) atomicOr(&S.flags, 1u << rs);  // (the list is full: a read that loses a job is left to K8)
             njobs += (uint32_t)__popcll(qb);
         };
         uint32_t rem = hits;
@@ -2864,8 +2903,10 @@ __global__ void __launch_bounds__(256, SLAMEM_SEED_WAVES) k_seed_mems(SearchArgs
             const uint32_t e = it == 0u ? e1 : hv ? (uint32_t)__ffs((int)rem) - 1u : 0u;
             rem &= rem - 1u;
             const uint32_t p = it == 0u ? p1 : sel12(b0, b1, b2, e);
-            push(hv, p, (rev >> e) & 1u);
-            if (__ballot(hv && both) != 0ull) push(hv && both, p, 1u);
+            const uint32_t st = it == 0u ? st1 : (rev >> e) & 1u;
+            const uint32_t pp = __shfl_up(p, 1), ps = __shfl_up(hv ? st : 2u, 1);
+            push(hv, p, st, pp, ps);
+            if (__ballot(hv && both) != 0ull) push(hv && both, p, 1u, pp, ps);
         }
         for (uint32_t e0 = 0; __ballot(e0 < xn) != 0ull; e0 += 4u) {  // (rare) four entries of the spill list per round
             const bool on = e0 < xn;
@@ -2881,67 +2922,68 @@ __global__ void __launch_bounds__(256, SLAMEM_SEED_WAVES) k_seed_mems(SearchArgs
                 const uint32_t st = d >> 7;
                 const bool hv = on && e0 + q < xn && (d & 0x7Fu) == 0u && !(strands == 1u && st && step == 1u);
                 if (__ballot(hv) == 0ull) continue;
-                push(hv, p, st);
-                if (__ballot(hv && both) != 0ull) push(hv && both, p, 1u);
+                push(hv, p, st, 0u, 2u);
+                if (__ballot(hv && both) != 0ull) push(hv && both, p, 1u, 0u, 2u);
             }
         }
-        if (njobs > SeedWave<NW, R>::kJobs) {  // (many repeated windows) every read of this trip is left to K8
-            if (act) atomicOr(&S.flags, 1u << rs);
+        if (njobs > SeedWave<NW, R>::kJobs) {  // (many repeated windows) the reads whose jobs did not fit are left to K8 (above)
             if (kStats && lane == 0u) atomicAdd(A.stats + SC_SEED_WHY + 3u, 1ull);
-            njobs = njobs0;
+            njobs = SeedWave<NW, R>::kJobs;
         }
     };
-    // the windows of a round, read after read, 64 to a trip (a ring of window ids in LDS takes what does not fill a trip yet)
-    auto lookups = [&](uint32_t round) {
-        const uint32_t step = round == 0u ? mstep : 1u;
-        uint32_t cnt = 0;
-        // (as many reads an iteration as fit the wave with a power of two of lanes each: two of the headline's, 27 windows a read,
-        //  sixteen at -l 50, 4 windows a read)
-        const uint32_t per = 64u >> lg_slots, wi = lane & ((1u << lg_slots) - 1u);
-        const uint32_t wmod = wi - mstep * ((wi * (65536u / mstep + 1u)) >> 16);  // wi % mstep (wi < 64, mstep <= 6)
-        for (uint32_t r = 0;; r += per) {
-            if (r < nr) {
-                const uint32_t rr = r + (lane >> lg_slots);
-                // (a read that is left to K8 already -- a bucket beyond the spill list, lists that ran over: repeat families do
-                //  that -- asks for nothing more)
-                const uint32_t nw = (rr >= nr || ((S.flags >> rr) & 1u)) ? 0u : S.nwin[rr];
-                const bool pred = wi < nw && (round == 0u ? wmod == 0u : wmod != 0u && ((S.expl[rr] >> wi) & 1ull) == 0ull);
-                const unsigned long long pm = __ballot(pred);
-                if (pred) S.ring[cnt + (uint32_t)__popcll(pm & below)] = (uint16_t)((rr << 8) | wi);
-                cnt += (uint32_t)__popcll(pm);
-            }
-            const bool last = r >= nr;  // (what is left in the ring)
-            if (cnt >= 64u || (last && cnt != 0u)) {
-                wave_sync();
-                const bool act = lane < cnt;
-                const uint32_t ent = act ? S.ring[lane] : 0u;
-                const uint32_t over = lane + 64u < cnt ? S.ring[lane + 64u] : 0u;
-                wave_sync();
-                if (lane + 64u < cnt) S.ring[lane] = (uint16_t)over;
-                cnt = cnt > 64u ? cnt - 64u : 0u;
-                trip(ent, act, step);
-            }
-            if (last) break;
-        }
-        wave_sync();
-    };
-
     // ---- compares: one lane per job: the strand against the text on the hit's diagonal -------------------------------------
+    // (the job list holds both rounds: in front the jobs that were compared, `first` of them from the round before, behind them
+    //  the jobs of this round; a job that is compared moves to the front part, the others go)
     auto compares = [&](uint32_t round) {
+        const uint32_t first = jfirst;
         const bool mark = round == 0u && mstep > 1u;
-        const uint32_t ms = mstep * s;
         const uint32_t gone = S.flags;  // reads that are left to K8 already: their compares are not made
-        for (uint32_t jb = 0; jb < njobs; jb += 64u) {
+        uint32_t ndone = first;
+        for (uint32_t jb = first; jb < njobs; jb += 64u) {
             const bool listed = jb + lane < njobs;
             const uint32_t p = listed ? S.job_p[jb + lane] : 0u, xx = listed ? S.job_x[jb + lane] : 0u;
             const uint32_t os = xx & 0x7FFFu, st = (xx >> 15) & 1u, jr = xx >> 16;
-            const bool has = listed && ((gone >> jr) & 1u) == 0u;
+            // A job whose (read, strand, diagonal) was compared, or stands earlier among these 64, is dropped.  The jobs to look
+            // at, 64 at a time (the compared ones, seldom more than 64, then these), say in a mask per strand which of them are
+            // that strand's; a lane looks at those of its own strand only.  The full diagonal decides, not its low 32 bits:
+            // text positions take all 32 bits at 3.1 Gbp and a diagonal may be negative.
+            bool dup = false;
+            for (uint32_t eb = 0;; eb += 64u) {
+                const bool own = eb >= ndone;  // (the last pass: these 64 jobs, each lane the ones before its own)
+                const uint32_t base = own ? jb : eb, lim = own ? njobs : ndone;
+                if (lane < 2u * R) S.smask[lane] = 0ull;
+                wave_sync();
+                if (base + lane < lim) {
+                    const uint32_t ex = S.job_x[base + lane];
+                    atomicOr(&S.smask[2u * (ex >> 16) + ((ex >> 15) & 1u)], 1ull << lane);
+                }
+                wave_sync();
+                unsigned long long em = listed ? S.smask[2u * jr + st] & (own ? below : ~0ull) : 0ull;
+                for (; __ballot(em != 0ull) != 0ull; em &= em - 1ull) {
+                    if (em == 0ull) continue;
+                    const uint32_t e = base + (uint32_t)__ffsll(em) - 1u;
+                    dup = dup || (int64_t)S.job_p[e] - (int64_t)(S.job_x[e] & 0x7FFFu) == (int64_t)p - (int64_t)os;
+                }
+                wave_sync();
+                if (own) break;
+            }
+            const bool has = listed && !dup && ((gone >> jr) & 1u) == 0u;
+            {   // (at most 64 jobs a pass join the front part, which ends before this pass's jobs start, or where they do)
+                const unsigned long long kb = __ballot(has);
+                if (has) { const uint32_t at = ndone + (uint32_t)__popcll(kb & below); S.job_p[at] = p; S.job_x[at] = xx; }
+                ndone += (uint32_t)__popcll(kb);
+                wave_sync();
+            }
             const uint32_t Lj = S.len[jr];
             const int64_t d = (int64_t)p - (int64_t)os;   // text position of the strand's first letter
             const int64_t u0 = d >> 6;
             const uint32_t sh = (uint32_t)(d & 63);
-            bool is_mem = false;
-            uint32_t key = 0, ref = 0, sig = 0;
+            // what the compare leaves for the reports behind it: where the runs of at least k agreeing letters start, where their
+            // last k letters start, and the text's planes under the strand (the letters behind a MEM)
+            uint64_t run_a[NW], run_e[NW], tp0[NW], tp1[NW];
+#pragma unroll
+            for (int w = 0; w < (int)NW; w++) { run_a[w] = 0ull; run_e[w] = 0ull; tp0[w] = 0ull; tp1[w] = 0ull; }
+            bool sig_ok = false;
             if (has) {
                 constexpr int NU = (int)NW + 1;  // units of the text the strand faces: NW words from any start inside a unit
                 int64_t ui[NU];
@@ -2961,9 +3003,12 @@ __global__ void __launch_bounds__(256, SLAMEM_SEED_WAVES) k_seed_mems(SearchArgs
                 const uint64_t* R1 = S.pl[jr][st][1];
                 uint64_t mm[NW];
 #pragma unroll
-                for (int w = 0; w < (int)NW; w++)
-                    mm[w] = (funnel64(u64_of(tu[w].x, tu[w].y), u64_of(tu[w + 1].x, tu[w + 1].y), sh) ^ R0[w]) |
-                            (funnel64(u64_of(tu[w].z, tu[w].w), u64_of(tu[w + 1].z, tu[w + 1].w), sh) ^ R1[w]) | funnel64(nu[w], nu[w + 1], sh);
+                for (int w = 0; w < (int)NW; w++) {
+                    tp0[w] = funnel64(u64_of(tu[w].x, tu[w].y), u64_of(tu[w + 1].x, tu[w + 1].y), sh);
+                    tp1[w] = funnel64(u64_of(tu[w].z, tu[w].w), u64_of(tu[w + 1].z, tu[w + 1].w), sh);
+                    mm[w] = (tp0[w] ^ R0[w]) | (tp1[w] ^ R1[w]) | funnel64(nu[w], nu[w + 1], sh);
+                }
+                sig_ok = anyn == 0u;
                 if (hasn) {  // the strand's letters that are not A,C,G,T disagree with whatever they face
                     const uint64_t* PN = S.pn[jr];
                     if (st == 0u) {
@@ -2985,63 +3030,68 @@ __global__ void __launch_bounds__(256, SLAMEM_SEED_WAVES) k_seed_mems(SearchArgs
                 const int hi = room < (int64_t)Lj ? (int)room : (int)Lj;
 #pragma unroll
                 for (int w = 0; w < (int)NW; w++) mm[w] |= ~bits_range(lo - 64 * w, hi - 64 * w);
-                // the run of agreeing letters around the window [os, os + k): [a, b)
-                uint32_t a = 0, b = kMaxLen;
-                bool broken = false;
+                // zk: bit x = the k letters from x on all agree (ANDs of the agreement mask with itself, moved down by 1, 2, 4 ..
+                // letters and by what is left of k); zeros come in at the top: behind the strand nothing agrees
+                uint64_t zk[NW], zt[NW];
 #pragma unroll
-                for (int w = 0; w < (int)NW; w++) {
-                    const uint64_t lw = mm[w] & bits_range(0, (int)os - 64 * w);
-                    if (lw) a = 64u * w + 64u - (uint32_t)__clzll((long long)lw);
-                    if (mm[w] & bits_range((int)os - 64 * w, (int)(os + k) - 64 * w)) broken = true;
-                }
+                for (int w = 0; w < (int)NW; w++) zk[w] = ~mm[w];
+                uint32_t have = 1;
+                for (; 2u * have <= k; have *= 2u) {
+                    shr_words<NW>(zk, have, zt);
 #pragma unroll
-                for (int w = (int)NW - 1; w >= 0; w--) {
-                    const uint64_t hw = mm[w] & ~bits_range(0, (int)(os + k) - 64 * w);
-                    if (hw) b = 64u * w + (uint32_t)__ffsll((unsigned long long)hw) - 1u;
+                    for (int w = 0; w < (int)NW; w++) zk[w] &= zt[w];
                 }
-                // in forward offsets (the windows are laid out along the forward strand): the run [af, bf), the window at of
-                const uint32_t af = st ? Lj - b : a, bf = st ? Lj - a : b, of = st ? Lj - k - os : os;
-                bool owner;
-                if (round == 0u) owner = !(of >= ms && of - ms >= af);  // the first round-A window inside the run
-                else {
-                    const uint32_t oa = (af + ms - 1u) / ms * ms;       // the first round-A window at or behind af: inside?
-                    owner = !(mstep > 1u && oa + k <= bf) && !(of >= s && of - s >= af);
+                if (k > have) {
+                    shr_words<NW>(zk, k - have, zt);
+#pragma unroll
+                    for (int w = 0; w < (int)NW; w++) zk[w] &= zt[w];
                 }
-                if (broken) {  // (cannot happen: the table is exact) -- leave the strand to K8
+                uint64_t hitw = 0ull;  // the hit's own window agrees: the table is exact
+#pragma unroll
+                for (int w = 0; w < (int)NW; w++) hitw = (os >> 6) == (uint32_t)w ? zk[w] : hitw;
+                const bool broken = ((hitw >> (os & 63u)) & 1ull) == 0ull;
+                if (broken) {  // (cannot happen) -- leave the read to K8
                     atomicOr(&S.flags, 1u << jr);
                     if (kStats) atomicAdd(A.stats + SC_SEED_WHY + 4u, 1ull);
-                }
-                else if (owner && b - a >= L && (strands == 2u || st == 0u)) {  // (one strand asked for: the other's compares only mark windows)
-                    is_mem = true; key = (a << 16) | (b - a); ref = (uint32_t)(d + (int64_t)a);
-                    // what the text goes on with behind the match: orders MEMs of one strand with the same start and length
-                    // (phase 3) as the rows of the suffix array would
-                    if (!anyn && b + kSigLetters <= kMaxLen && d + (int64_t)b + (int64_t)kSigLetters <= (int64_t)ix.n) {
-                        const uint32_t wb = b >> 6, sb = b & 63u;
-                        uint64_t l0 = 0, h0 = 0, l1 = 0, h1 = 0;
+                } else {
+                    if (strands == 2u || st == 0u) {  // (one strand asked for: the other's compares only mark windows)
+                        // a run of zk starts where the bit below is clear and ends where the bit above is: the agreeing letters
+                        // from the first of these to k behind the second
+                        shr_words<NW>(zk, 1u, zt);
 #pragma unroll
                         for (int w = 0; w < (int)NW; w++) {
-                            const uint64_t t0 = funnel64(u64_of(tu[w].x, tu[w].y), u64_of(tu[w + 1].x, tu[w + 1].y), sh);
-                            const uint64_t t1 = funnel64(u64_of(tu[w].z, tu[w].w), u64_of(tu[w + 1].z, tu[w + 1].w), sh);
-                            if ((uint32_t)w == wb) { l0 = t0; l1 = t1; }
-                            if ((uint32_t)w == wb + 1u) { h0 = t0; h1 = t1; }
+                            run_a[w] = zk[w] & ~((zk[w] << 1) | (w ? zk[w ? w - 1 : 0] >> 63 : 0ull));
+                            run_e[w] = zk[w] & ~zt[w];
                         }
-                        sig = kSigKnown | ((uint32_t)funnel64(l0, h0, sb) & kSigMask) | (((uint32_t)funnel64(l1, h1, sb) & kSigMask) << kSigLetters);
                     }
-                }
-                if (mark && !broken && bf >= af + k) {
-                    // the other windows inside the run whose k-mer occurs once in the text: accounted for
-                    uint64_t uqs[NW];
+                    if (mark) {
+                        // the windows inside k agreeing letters whose k-mer occurs once in the text: accounted for.  In letters
+                        // of the forward strand, where the windows are laid out: letter x of the reverse strand's window is
+                        // where the forward window at len - k - x starts
+                        uint64_t once[NW];
 #pragma unroll
-                    for (int w = 0; w < (int)NW; w++) uqs[w] = funnel64(uq[w], uq[w + 1], sh);
-                    unsigned long long done = 0ull;
-                    for (uint32_t wi = (af + s - 1u) / s, wl = (bf - k) / s; wi <= wl; wi++) {
-                        const uint32_t x = st ? Lj - k - wi * s : wi * s;  // the window's first letter in the strand
-                        uint64_t word = 0ull;
+                        for (int w = 0; w < (int)NW; w++) once[w] = zk[w] & funnel64(uq[w], uq[w + 1], sh);
+                        if (st) {
+                            // (bit x of the whole value goes to 64 NW - 1 - x when the words are reversed, and comes down from there)
+                            const uint32_t c = kMaxLen - 1u - Lj + k, cq = c >> 6, cr = c & 63u;
+                            uint64_t rv[NW];
 #pragma unroll
-                        for (int w = 0; w < (int)NW; w++) word = (x >> 6) == (uint32_t)w ? uqs[w] : word;
-                        if ((word >> (x & 63u)) & 1ull) done |= 1ull << wi;
+                            for (int w = 0; w < (int)NW; w++) rv[w] = __brevll(once[NW - 1 - w]);
+#pragma unroll
+                            for (int w = 0; w < (int)NW; w++) {
+                                uint64_t lo64 = 0ull, hi64 = 0ull;
+#pragma unroll
+                                for (int v = 0; v < (int)NW; v++) {
+                                    lo64 = (uint32_t)w + cq == (uint32_t)v ? rv[v] : lo64;
+                                    hi64 = (uint32_t)w + cq + 1u == (uint32_t)v ? rv[v] : hi64;
+                                }
+                                once[w] = funnel64(lo64, hi64, cr);
+                            }
+                        }
+#pragma unroll
+                        for (int w = 0; w < (int)NW; w++)
+                            if (once[w]) atomicOr((unsigned long long*)&S.expl[jr][w], (unsigned long long)once[w]);
                     }
-                    if (done) atomicOr(&S.expl[jr], done);
                 }
             }
             if (kStats) {
@@ -3049,22 +3099,113 @@ __global__ void __launch_bounds__(256, SLAMEM_SEED_WAVES) k_seed_mems(SearchArgs
                 n_cmp += nh;
                 if (mark && lane == 0u) atomicAdd(A.stats + SC_SEED_ONCE, (unsigned long long)nh);
             }
-            const unsigned long long mb = __ballot(is_mem);
-            if (is_mem) {
-                const uint32_t at = nmems + (uint32_t)__popcll(mb & below);
-                if (at < SeedWave<NW, R>::kMems) { S.mem_key[at] = key; S.mem_ref[at] = ref; S.mem_sig[at] = sig | ((2u * jr + st) << 25); }
-                else { atomicOr(&S.flags, 1u << jr); if (kStats) atomicAdd(A.stats + SC_SEED_WHY + 5u, 1ull); }
+            // every run of at least L agreeing letters is a MEM: the runs of the wave's compares, one of each lane at a time
+            for (;;) {
+                uint64_t any_a = 0ull;
+#pragma unroll
+                for (int w = 0; w < (int)NW; w++) any_a |= run_a[w];
+                if (__ballot(any_a != 0ull) == 0ull) break;
+                const uint32_t a = lowest_bit<NW>(run_a), b = lowest_bit<NW>(run_e) + k;
+                drop_lowest_bit<NW>(run_a);
+                drop_lowest_bit<NW>(run_e);
+                const bool is_mem = any_a != 0ull && b - a >= L;
+                uint32_t sig = 0;
+                // what the text goes on with behind the match: orders MEMs of one strand with the same start and length
+                // (phase 3) as the rows of the suffix array would
+                if (is_mem && sig_ok && b + kSigLetters <= kMaxLen && d + (int64_t)b + (int64_t)kSigLetters <= (int64_t)ix.n) {
+                    const uint32_t wb = b >> 6, sb = b & 63u;
+                    uint64_t l0 = 0, h0 = 0, l1 = 0, h1 = 0;
+#pragma unroll
+                    for (int w = 0; w < (int)NW; w++) {
+                        if ((uint32_t)w == wb) { l0 = tp0[w]; l1 = tp1[w]; }
+                        if ((uint32_t)w == wb + 1u) { h0 = tp0[w]; h1 = tp1[w]; }
+                    }
+                    sig = kSigKnown | ((uint32_t)funnel64(l0, h0, sb) & kSigMask) | (((uint32_t)funnel64(l1, h1, sb) & kSigMask) << kSigLetters);
+                }
+                const unsigned long long mb = __ballot(is_mem);
+                if (is_mem) {
+                    const uint32_t at = nmems + (uint32_t)__popcll(mb & below);
+                    if (at < SeedWave<NW, R>::kMems) {
+                        S.mem_key[at] = (a << 16) | (b - a); S.mem_ref[at] = (uint32_t)(d + (int64_t)a); S.mem_sig[at] = sig | ((2u * jr + st) << 25);
+                    } else { atomicOr(&S.flags, 1u << jr); if (kStats) atomicAdd(A.stats + SC_SEED_WHY + 5u, 1ull); }
+                }
+                nmems += (uint32_t)__popcll(mb);
             }
-            nmems += (uint32_t)__popcll(mb);
+        }
+        njobs = ndone;
+        jfirst = ndone;
+        wave_sync();
+    };
+
+    // the windows of a round, read after read, 64 to a trip (a ring of window ids in LDS takes what does not fill a trip yet)
+    const uint32_t nrounds = mstep > 1u ? 2u : 1u;
+    auto lookups = [&](uint32_t round) {
+        const uint32_t step = round == 0u ? mstep : 1u;
+        uint32_t cnt = 0;
+        // (as many reads an iteration as fit the wave with a power of two of lanes each: two of the headline's, 27 windows a read,
+        //  sixteen at -l 50, 4 windows a read)
+        const uint32_t per = 64u >> lg_slots, wi = lane & ((1u << lg_slots) - 1u);
+        // wi % mstep (wi < 64, mstep <= 64: the quotient comes out too large by less than 64 / 65536, and wi / mstep lies at
+        // least 1 / 64 below the next integer)
+        const uint32_t wmod = wi - mstep * ((wi * (65536u / mstep + 1u)) >> 16);
+        for (uint32_t r = 0;; r += per) {
+            if (r < nr) {
+                const uint32_t rr = r + (lane >> lg_slots);
+                // (a read that is left to K8 already -- a bucket beyond the spill list, lists that ran over: repeat families do
+                //  that -- asks for nothing more)
+                const uint32_t nw = (rr >= nr || ((S.flags >> rr) & 1u)) ? 0u : S.nwin[rr];
+                const uint32_t ow = wi < nw ? wi * s : 0u;  // the window's first letter
+                const bool pred = wi < nw && (round == 0u ? wmod == 0u : wmod != 0u && ((S.expl[rr][ow >> 6] >> (ow & 63u)) & 1ull) == 0ull);
+                const unsigned long long pm = __ballot(pred);
+                if (pred) S.ring[cnt + (uint32_t)__popcll(pm & below)] = (uint16_t)((rr << 8) | wi);
+                cnt += (uint32_t)__popcll(pm);
+            }
+            const bool last = r >= nr;  // (what is left in the ring)
+            if (cnt >= 64u || (last && cnt != 0u)) {
+                wave_sync();
+                const bool act = lane < cnt;
+                const uint32_t ent = act ? S.ring[lane] : 0u;
+                const uint32_t over = lane + 64u < cnt ? S.ring[lane + 64u] : 0u;
+                wave_sync();
+                if (lane + 64u < cnt) S.ring[lane] = (uint16_t)over;
+                cnt = cnt > 64u ? cnt - 64u : 0u;
+                trip(ent, act, step);
+            }
+            // The compares, when the round's lookups are through -- and before that when many jobs wait: windows of a repeat
+            // bring the same few diagonals again and again, and the list has room for them once they are settled.  (The
+            // compares use the ring's space for their masks: what waits in the ring, less than a trip, steps aside.)
+            if (last || njobs - jfirst > SeedWave<NW, R>::kJobs / 3u || (njobs > jfirst && njobs > SeedWave<NW, R>::kJobs / 2u)) {
+                wave_sync();
+                const uint32_t waits = lane < cnt ? S.ring[lane] : 0u;
+                wave_sync();
+                compares(round);
+                if (lane < cnt) S.ring[lane] = (uint16_t)waits;
+                wave_sync();
+                if (!last && round + 1u == nrounds) {
+                    // the last round, reads still to come: a read whose windows are all through brings no more hits, so
+                    // its jobs leave the list (the reads are queued in order: the first one in the ring, or the next)
+                    const uint32_t from = cnt ? (uint32_t)__builtin_amdgcn_readfirstlane((int)waits) >> 8 : r + per;
+                    uint32_t kept = 0;
+                    for (uint32_t jb = 0; jb < njobs; jb += 64u) {
+                        const bool in = jb + lane < njobs;
+                        const uint32_t jp = in ? S.job_p[jb + lane] : 0u, jx = in ? S.job_x[jb + lane] : 0u;
+                        const bool keep = in && (jx >> 16) >= from;
+                        wave_sync();
+                        const unsigned long long kb = __ballot(keep);
+                        if (keep) { const uint32_t at = kept + (uint32_t)__popcll(kb & below); S.job_p[at] = jp; S.job_x[at] = jx; }
+                        kept += (uint32_t)__popcll(kb);
+                        wave_sync();
+                    }
+                    njobs = kept;
+                    jfirst = kept;
+                }
+            }
+            if (last) break;
         }
         wave_sync();
     };
 
-    for (uint32_t round = 0; round < (mstep > 1u ? 2u : 1u); round++) {
-        njobs = 0;
-        lookups(round);
-        compares(round);
-    }
+    for (uint32_t round = 0; round < nrounds; round++) lookups(round);
     };
     if (wave_hasn) search(std::true_type{}); else search(std::false_type{});
     {
