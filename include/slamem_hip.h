@@ -906,6 +906,46 @@ int slamem_pileup_genotypes_weighted_host(slamem_pileup *pile, uint64_t first, u
                                           uint64_t capacity, uint64_t *pos, uint32_t *counts, slamem_genotype *gts, uint32_t *qsums,
                                           uint64_t *total_out);
 
+/* ---- (b''''''''''') junctions: long deletions and insertions between segments (option -sv) ---------------------
+ * A gap between two chain anchors that -aln does not close ends a segment; the table and the events above hold nothing of what
+ * lies between two segments of one read.  With junctions enabled every add of reads also looks at each adjacent pair (a, b) of a
+ * contributing read's segments, in ascending order of the scanned strand: dr text rows B and dq read letters A lie between a's end
+ * and b's start, m = min(dr, dq), L = |dr - dq|.  Counted and not stored, looked at in this order -- skipped[0]: L == 0 (a
+ * divergent stretch, no indel); skipped[3]: m > 64; skipped[2]: a row of B, or a compared letter of A, that is none of A,C,G,T;
+ * skipped[3] again: the best split has more than max_mis mismatches; skipped[1]: no room in the table.  The best split shares the
+ * m letters out between a's diagonal (the first t) and b's (the rest) with the fewest mismatches, the smallest such t; the
+ * junction is then a deletion of L rows from a's end + t (dr > dq) or an insertion of L letters in front of that row (dq > dr),
+ * left-normalised by the two rules of the events, without their length limits.  The table maps (pos, kind, len) to fwd and rev as
+ * the events' does; the inserted letters are NOT part of the key: two different insertions of one length at one place are one
+ * key.  The six columns of the pileup are unchanged: the deleted rows get no D.
+ *
+ *   slamem_pileup_enable_junctions  allocates the table of `slots` slots (a power of two of at least 64; 0: the smallest power of
+ *                          two that is at least max(65536, n / 64)) as slamem_pileup_enable_events does; max_mis: 0 to 64.
+ *                          Enabled already, a bad number: SLAMEM_ERR_ARG; too little free HBM: SLAMEM_ERR_NOMEM.
+ *                          slamem_pileup_reset also clears this table and its counters.
+ *   slamem_pileup_junctions_device  the keys with first <= pos < first + count, fwd + rev >= min_count (>= 1) and len >= min_len,
+ *                          ascending in (pos, kind, len), and the four counters; the capacity protocol, the one host round trip
+ *                          and the rules about concurrent calls of slamem_pileup_events_device.
+ *   slamem_pileup_junctions_host  the same into host memory; waits for the device first.
+ *   slamem_pileup_add_junctions_device  every given junction with its fwd and rev: a deletion is validated (inside the text, its
+ *                          rows A,C,G,T) and normalised, an insertion (pos < n) is taken where it is given, its letters being no
+ *                          part of the record; anything else adds to skipped[2].  The merge of another accumulator's read-out.
+ *   slamem_pileup_add_junctions_host  the same from host memory; returns when the junctions are added. */
+typedef struct {
+    uint64_t pos;
+    uint32_t len, fwd, rev;
+    uint8_t kind;   /* 0 a deletion of len rows from pos, 1 an insertion of len letters in front of pos */
+    uint8_t pad[3]; /* 0 */
+} slamem_junction;
+int slamem_pileup_enable_junctions(slamem_pileup *pile, uint64_t slots, uint32_t max_mis);
+int slamem_pileup_junctions_device(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t min_count, uint32_t min_len,
+                                   uint64_t capacity, slamem_junction *junctions_dev, uint64_t *skipped_out /* 4 */,
+                                   uint64_t *total_out, void *stream);
+int slamem_pileup_junctions_host(slamem_pileup *pile, uint64_t first, uint64_t count, uint32_t min_count, uint32_t min_len,
+                                 uint64_t capacity, slamem_junction *junctions, uint64_t *skipped_out /* 4 */, uint64_t *total_out);
+int slamem_pileup_add_junctions_device(slamem_pileup *pile, const slamem_junction *junctions_dev, uint64_t m, void *stream);
+int slamem_pileup_add_junctions_host(slamem_pileup *pile, const slamem_junction *junctions, uint64_t m);
+
 /* ---- (c) mapping QC tables (-stats) -----------------------------------------------------------------------------
  * A slamem_stats is an accumulator of SLAMEM_STATS_WORDS unsigned 64-bit counters on the index's device, the sum over every batch
  * added since creation or the last reset, whatever the split into batches, their order and their streams: every number is a

@@ -68,6 +68,8 @@ ABI_SYMBOLS = (
     "slamem_pileup_genotypes_weighted_host", "slamem_stream_set_quals", "slamem_stream_submit_quals",
     "slamem_stats_create", "slamem_stats_free", "slamem_stats_reset", "slamem_stats_add_device", "slamem_stats_table_device",
     "slamem_stats_table_host", "slamem_stats_add_table_host", "slamem_stream_set_stats",
+    "slamem_pileup_enable_junctions", "slamem_pileup_junctions_device", "slamem_pileup_junctions_host",
+    "slamem_pileup_add_junctions_device", "slamem_pileup_add_junctions_host",
     "slamem_stream_destroy",
     "slamem_pinned_alloc", "slamem_pinned_free", "slamem_copy_to_host",
 )
@@ -246,6 +248,11 @@ def _declare(L):
     L.slamem_pileup_events_host.argtypes = [vp, u64, u64, u32, u64, vp, C.POINTER(u64), C.POINTER(u64)]
     L.slamem_pileup_add_events_device.argtypes = [vp, vp, u64, vp]
     L.slamem_pileup_add_events_host.argtypes = [vp, vp, u64]
+    L.slamem_pileup_enable_junctions.argtypes = [vp, u64, u32]
+    L.slamem_pileup_junctions_device.argtypes = [vp, u64, u64, u32, u32, u64, vp, C.POINTER(u64), C.POINTER(u64), vp]
+    L.slamem_pileup_junctions_host.argtypes = [vp, u64, u64, u32, u32, u64, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.slamem_pileup_add_junctions_device.argtypes = [vp, vp, u64, vp]
+    L.slamem_pileup_add_junctions_host.argtypes = [vp, vp, u64]
     L.slamem_pileup_rows_at_device.argtypes = [vp, vp, u64, vp, vp]
     L.slamem_pileup_rows_at_host.argtypes = [vp, vp, u64, vp]
     L.slamem_pileup_consensus_device.argtypes = [vp, u64, u64, u32, u64, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), vp]

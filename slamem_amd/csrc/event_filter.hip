@@ -2,11 +2,8 @@
 // of a contributing read (strand != 0, mapq >= min_mapq) is an observation of an event; the event is left-normalised against the
 // text and counted per strand in a hash table in HBM, keyed by (pos, kind, len, inserted letters).
 //
-// A slot is 24 bytes: key0 (bit 63, pos in bits 0..39, kind in bit 40, len in bits 41..47), key1 (bit 63, the inserted letters two
-// bits each, the first one highest), fwd, rev.  0 in a key word means empty.  An insert probes linearly from a hash of key0 and
-// per probe does CAS(key0, 0 -> w0), on 0 or w0 CAS(key1, 0 -> w1), on 0 or w1 the atomic adds; otherwise the next slot; after
-// kEvProbes probes the observation is counted in skipped[1].  No lane waits for another lane's store: no loop here has a bound
-// that another lane can move (4.18 has the argument why equal keys meet in one slot and why no slot keeps a key0 without a key1).
+// The table, its 24-byte slot and its two-CAS insert are ev_table.h's, shared with sv_filter.hip; here key0 also holds len in bits
+// 41..47 and key1 the inserted letters two bits each, the first one highest.
 //   k_events_lane / k_events_wave   the walks of k_pile_lane / k_pile_wave (pile_filter.hip), acting on I and D alone
 //   k_events_insert                 a lane per given event with its two counts: the merge of two tables, and the tests' planting tool
 //   k_ev_count / k_ev_emit          the read-out: the slots of the range with enough observations per tile of kEvTile slots, and
@@ -14,100 +11,28 @@
 //   k_ev_sort_key / k_ev_gather     the second sort's key (pos, kind, len from key0) and the slamem_event records in order
 //   k_pile_rows_at                  rows of counts() at listed positions, a wave per position
 #include "buffers.h"
-#include "pile_shared.h"
-#include "prims.h"
+#include "ev_table.h"
 
 #include <new>
 
 namespace slamem {
 
-struct EvSlot {
-    unsigned long long key0, key1;
-    uint32_t fwd, rev;
-};
-static_assert(sizeof(EvSlot) == 24 && sizeof(slamem_event) == 32, "a slot is 24 bytes, a record 32");
-
-struct EvTable {
-    EvSlot* slots;
-    uint64_t nslots;              // a power of two, 64 to 2^31
-    unsigned long long* skipped;  // 3 counters
-    uint64_t* sel;                // the read-out's selected slots per tile: nslots / kEvTile + 2 words
-    uint64_t *ka, *kb;            // the read-out's sort keys, nslots each
-    uint32_t *va, *vb;            // ... and slot numbers
-    void* tmp;                    // sort_pairs_u64_u32's scratch for nslots pairs
-    size_t tmp_bytes;
-};
+static_assert(sizeof(slamem_event) == 32, "a record is 32 bytes");
 
 namespace {
 
-constexpr uint32_t kEvProbes = 128;   // slots an insert looks at before it gives up
-constexpr uint32_t kEvTile = 2048;    // slots per workgroup of the read-out (256 lanes x 8)
 constexpr uint32_t kEvMaxIns = 31, kEvMaxDel = 127;
-constexpr unsigned long long kEvSet = 1ull << 63;
-
-struct EvAcc {
-    const TextPlanes* tpl;
-    EvSlot* slots;
-    uint64_t mask;  // nslots - 1
-    unsigned long long* skipped;
-    uint64_t n;
-};
-
-// the text's letter at x (x < n): A 0, C 1, G 2, T 3; anything else 4
-__device__ __forceinline__ uint32_t ev_text(const TextPlanes* __restrict__ tpl, uint64_t x) {
-    const TextPlanes* u = tpl + (x >> 6);
-    const uint32_t bit = (uint32_t)(x & 63u);
-    if ((u->nm >> bit) & 1ull) return 4u;
-    return (uint32_t)((u->p0 >> bit) & 1ull) | ((uint32_t)((u->p1 >> bit) & 1ull) << 1);
-}
-
-// is any of rows [p, p + k) (p + k <= n, k >= 1) none of A,C,G,T?
-__device__ __forceinline__ bool ev_rows_bad(const TextPlanes* __restrict__ tpl, uint64_t p, uint64_t k) {
-    const uint64_t e = p + k;
-    uint64_t any = 0;
-    for (uint64_t u = p >> 6; u <= (e - 1) >> 6; u++) {
-        uint64_t m = tpl[u].nm;
-        if (u == p >> 6) m &= ~0ull << (p & 63u);
-        if (u == (e - 1) >> 6 && (e & 63u)) m &= (1ull << (e & 63u)) - 1ull;
-        any |= m;
-    }
-    return any != 0;
-}
-
-__device__ __forceinline__ uint64_t ev_hash(uint64_t x) {
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
-    return x;
-}
 
 // a valid event in canonical form: its slot gets `fwd` and `rev`; no room within kEvProbes probes: skipped[1]
 __device__ __forceinline__ void ev_insert(const EvAcc& a, uint64_t pos, uint32_t kind, uint32_t len, uint64_t letters, uint32_t fwd,
                                           uint32_t rev) {
-    const unsigned long long w0 = kEvSet | ((unsigned long long)len << 41) | ((unsigned long long)kind << 40) | pos;
-    const unsigned long long w1 = kEvSet | letters;
-    const uint64_t h = ev_hash(w0);
-    const uint32_t probes = a.mask + 1u < kEvProbes ? (uint32_t)(a.mask + 1u) : kEvProbes;
-    for (uint32_t i = 0; i < probes; i++) {
-        EvSlot* s = a.slots + ((h + i) & a.mask);
-        const unsigned long long r = atomicCAS(&s->key0, 0ull, w0);
-        if (r != 0ull && r != w0) continue;
-        const unsigned long long r1 = atomicCAS(&s->key1, 0ull, w1);  // (every lane that set or met w0 comes here: key1 never stays empty)
-        if (r1 != 0ull && r1 != w1) continue;
-        if (fwd) atomicAdd(&s->fwd, fwd);
-        if (rev) atomicAdd(&s->rev, rev);
-        return;
-    }
-    atomicAdd(&a.skipped[1], (unsigned long long)fwd + rev);
+    ev_probe(a, kEvSet | ((unsigned long long)len << 41) | ((unsigned long long)kind << 40) | pos, kEvSet | letters, fwd, rev);
 }
 
 // a deletion of rows [p, p + k), valid (1 <= k <= kEvMaxDel, p + k <= n, the rows A,C,G,T): as far left as it goes, then inserted.
 // The loop runs at most p times: p is fixed before it starts.
 __device__ __forceinline__ void ev_deletion(const EvAcc& a, uint64_t p, uint32_t k, uint32_t fwd, uint32_t rev) {
-    for (uint64_t left = p; left > 0; left--) {
-        const uint32_t c = ev_text(a.tpl, p - 1u);
-        if (c >= 4u || c != ev_text(a.tpl, p + k - 1u)) break;
-        p--;
-    }
-    ev_insert(a, p, 0u, k, 0ull, fwd, rev);
+    ev_insert(a, ev_deletion_left(a.tpl, p, k), 0u, k, 0ull, fwd, rev);
 }
 
 // an insertion of k letters S (1 <= k <= kEvMaxIns, letter i at bits 2 (k - 1 - i)) in front of row p < n
@@ -222,78 +147,15 @@ __global__ void __launch_bounds__(256) k_events_insert(const slamem_event* __res
 
 // ---- read-out --------------------------------------------------------------------------------------------------------------
 
-struct EvRule {
-    uint64_t first, end;  // first <= pos < end
-    uint64_t min_count;   // fwd + rev at least this (>= 1)
-};
-
-__device__ __forceinline__ bool ev_selected(const EvSlot* __restrict__ slots, uint64_t x, uint64_t nslots, const EvRule& r) {
-    if (x >= nslots) return false;
-    const unsigned long long k0 = slots[x].key0;
-    if (k0 == 0ull) return false;
-    const uint64_t pos = k0 & ((1ull << 40) - 1ull);
-    return pos >= r.first && pos < r.end && (uint64_t)slots[x].fwd + slots[x].rev >= r.min_count;
-}
-
-// a workgroup per tile of slots: sel[blockIdx.x] = how many of them the rule selects
+// a workgroup per tile of slots: sel[blockIdx.x] = how many of them the rule selects (ev_table.h)
 __global__ void __launch_bounds__(256) k_ev_count(const EvSlot* __restrict__ slots, uint64_t nslots, EvRule rule, uint64_t* __restrict__ sel) {
-    __shared__ uint32_t wsum[4];
-    const uint64_t base = (uint64_t)blockIdx.x * kEvTile;
-    uint32_t mine = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kEvTile / 256u; j++) mine += ev_selected(slots, base + j * 256u + threadIdx.x, nslots, rule) ? 1u : 0u;
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1) mine += __shfl_xor(mine, d, 64);
-    if ((threadIdx.x & 63u) == 0u) wsum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) sel[blockIdx.x] = (uint64_t)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    ev_count_body<false>(slots, nslots, rule, sel);
 }
 
-// a workgroup per tile: key1 and the slot number of its selected slots at sel[blockIdx.x] + rank in the tile (the scheme of
-// k_sites_emit: ballots and popcounts in a wave, the waves' totals through LDS).  room: the entries of keys / vals.
+// a workgroup per tile: key1 and the slot number of its selected slots at sel[blockIdx.x] + rank in the tile (ev_table.h)
 __global__ void __launch_bounds__(256) k_ev_emit(const EvSlot* __restrict__ slots, uint64_t nslots, EvRule rule, const uint64_t* __restrict__ sel,
                                                  uint64_t room, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-    constexpr uint32_t per = kEvTile / 256u;
-    __shared__ uint32_t wcnt[per * 4u];
-    const uint64_t out0 = sel[blockIdx.x];
-    if (sel[blockIdx.x + 1] == out0) return;  // (the whole workgroup: nothing selected)
-    const uint64_t base = (uint64_t)blockIdx.x * kEvTile;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    bool take[per];
-    uint32_t below[per];
-#pragma unroll
-    for (uint32_t j = 0; j < per; j++) {
-        take[j] = ev_selected(slots, base + j * 256u + threadIdx.x, nslots, rule);
-        const unsigned long long b = __ballot(take[j]);
-        below[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-        if (lane == 0u) wcnt[j * 4u + wave] = (uint32_t)__popcll(b);
-    }
-    __syncthreads();
-    uint32_t run = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < per; j++) {
-        uint32_t mine = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4u; w++) {
-            if (w == wave) mine = run;
-            run += wcnt[j * 4u + w];
-        }
-        const uint64_t o = out0 + mine + below[j];
-        if (!take[j] || o >= room) continue;
-        const uint64_t x = base + j * 256u + threadIdx.x;
-        keys[o] = slots[x].key1 & ~kEvSet;
-        vals[o] = (uint32_t)x;
-    }
-}
-
-// the second sort's key of entry i: pos, kind, len in this order of weight (key0 holds them the other way round)
-__global__ void __launch_bounds__(256) k_ev_sort_key(const EvSlot* __restrict__ slots, uint64_t nslots, const uint32_t* __restrict__ vals,
-                                                     uint64_t m, uint64_t* __restrict__ keys) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= m) return;
-    const uint64_t x = vals[i];
-    const unsigned long long k0 = x < nslots ? slots[x].key0 : 0ull;
-    keys[i] = ((k0 & ((1ull << 40) - 1ull)) << 8) | (((k0 >> 40) & 1ull) << 7) | ((k0 >> 41) & 127ull);
+    ev_emit_body<false>(slots, nslots, rule, sel, room, keys, vals);
 }
 
 // record i (i < m, i < capacity) from the slot the sorts put there
@@ -307,7 +169,7 @@ __global__ void __launch_bounds__(256) k_ev_gather(const EvSlot* __restrict__ sl
     for (int k = 0; k < 6; k++) e.pad[k] = 0;
     if (x < nslots) {
         const EvSlot s = slots[x];
-        e.pos = s.key0 & ((1ull << 40) - 1ull);
+        e.pos = s.key0 & kEvPosMask;
         e.kind = (uint8_t)((s.key0 >> 40) & 1ull);
         e.len = (uint8_t)((s.key0 >> 41) & 127ull);
         e.letters = s.key1 & ~kEvSet;
@@ -354,8 +216,6 @@ EvAcc ev_acc(const slamem_pileup* pile) {
     return a;
 }
 
-inline uint64_t ev_tiles(uint64_t nslots) { return (nslots + kEvTile - 1) / kEvTile; }
-
 }  // namespace
 
 int events_add(slamem_pileup* pile, const void* batch, hipStream_t stream) {
@@ -378,14 +238,7 @@ int events_reset(slamem_pileup* pile) {
 void events_free(slamem_pileup* pile) {
     EvTable* t = pile->ev;
     if (!t) return;
-    if (t->slots) (void)hipFree(t->slots);
-    if (t->skipped) (void)hipFree(t->skipped);
-    if (t->sel) (void)hipFree(t->sel);
-    if (t->ka) (void)hipFree(t->ka);
-    if (t->kb) (void)hipFree(t->kb);
-    if (t->va) (void)hipFree(t->va);
-    if (t->vb) (void)hipFree(t->vb);
-    if (t->tmp) (void)hipFree(t->tmp);
+    ev_table_release(t);
     delete t;
     pile->ev = nullptr;
 }
@@ -410,9 +263,7 @@ int slamem_pileup_enable_events(slamem_pileup* pile, uint64_t slots) {
     }
     SLAMEM_HIP(hipSetDevice(pile->device));
     size_t tmp_bytes = 0;
-    (void)sort_pairs_u64_u32(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)slots, 0, 8, nullptr);
-    const uint64_t tiles = ev_tiles(slots) + 2;
-    const uint64_t need = slots * (sizeof(EvSlot) + 24) + tiles * 8 + tmp_bytes + 24;
+    const uint64_t need = ev_table_bytes(slots, 3, &tmp_bytes);
     size_t free_b = 0, total_b = 0;
     SLAMEM_HIP(hipMemGetInfo(&free_b, &total_b));
     if (need > free_b) {
@@ -423,21 +274,8 @@ int slamem_pileup_enable_events(slamem_pileup* pile, uint64_t slots) {
     }
     EvTable* t = new (std::nothrow) EvTable();
     if (!t) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
-    *t = EvTable{};
-    t->nslots = slots;
-    t->tmp_bytes = tmp_bytes;
     pile->ev = t;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->slots), slots * sizeof(EvSlot));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->skipped), 3 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->sel), tiles * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->ka), slots * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->kb), slots * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->va), slots * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->vb), slots * 4);
-    if (e == hipSuccess) e = hipMalloc(&t->tmp, tmp_bytes);
-    if (e == hipSuccess) e = hipMemset(t->slots, 0, slots * sizeof(EvSlot));
-    if (e == hipSuccess) e = hipMemset(t->skipped, 0, 3 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+    const hipError_t e = ev_table_alloc(t, slots, tmp_bytes, 3);
     if (e != hipSuccess) {
         events_free(pile);
         return hip_fail(e, "slamem_pileup_enable_events", __FILE__, __LINE__);
@@ -491,7 +329,7 @@ int slamem_pileup_events_device(slamem_pileup* pile, uint64_t first, uint64_t co
     hipStream_t st = static_cast<hipStream_t>(stream);
     EvTable* t = pile->ev;
     const uint64_t tiles = ev_tiles(t->nslots);
-    const EvRule rule{first, first + count, min_count};
+    const EvRule rule{first, first + count, min_count, 0};
     hipLaunchKernelGGL(k_ev_count, dim3((unsigned)tiles), dim3(256), 0, st, (const EvSlot*)t->slots, t->nslots, rule, t->sel);
     SLAMEM_HIP(hipGetLastError());
     int rc = pile_scan_counts(t->sel, tiles, st);  // (tiles + 1 <= nslots / kEvTile + 2 words)

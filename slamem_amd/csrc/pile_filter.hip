@@ -568,7 +568,8 @@ int pileup_add_masked(slamem_pileup* pile, const void* queries_dev, const uint64
         hipLaunchKernelGGL(k_pile_wave, wave_grid, dim3(64), 0, stream, b, a);
         SLAMEM_HIP(hipGetLastError());
     }
-    if (pile->ev) return events_add(pile, &b, stream);  // (the indel events of the same batch, behind the two kernels)
+    if (pile->ev) SLAMEM_TRY(events_add(pile, &b, stream));  // (the indel events of the same batch, behind the two kernels)
+    if (pile->sv) SLAMEM_TRY(junctions_add(pile, &b, stream));  // (the breaks between the batch's segments)
     return SLAMEM_OK;
 }
 
@@ -625,7 +626,7 @@ static int pile_new(const slamem_index* idx, const char* fn, int role, slamem_pi
     slamem_pileup* p = new (std::nothrow) slamem_pileup();
     if (!p) { set_error("out of host memory"); return SLAMEM_ERR_NOMEM; }
     p->idx = idx; p->device = idx->device; p->n = (uint32_t)n;
-    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr; p->cons = nullptr; p->depth = nullptr; p->dd = nullptr;
+    p->diff = nullptr; p->cnt = nullptr; p->tile = nullptr; p->sel = nullptr; p->ev = nullptr; p->sv = nullptr; p->cons = nullptr; p->depth = nullptr; p->dd = nullptr;
     p->fwd = nullptr; p->qual = nullptr; p->child = false; p->child_qual = false; p->used.store(false, std::memory_order_relaxed);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->diff), (n + 1) * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->cnt), n * 24 + 16);
@@ -708,6 +709,7 @@ static void pile_release(slamem_pileup* p) {
     if (p->tile) (void)hipFree(p->tile);
     if (p->sel) (void)hipFree(p->sel);
     events_free(p);
+    junctions_free(p);
     cons_free(p);
     depth_free(p);
     dedup_free(p);
@@ -728,6 +730,7 @@ int slamem_pileup_reset(slamem_pileup* p) {
     SLAMEM_HIP(hipMemset(p->diff, 0, ((uint64_t)p->n + 1) * 4));
     SLAMEM_HIP(hipMemset(p->cnt, 0, (uint64_t)p->n * 24));
     if (p->ev) { const int rc = events_reset(p); if (rc != SLAMEM_OK) return rc; }
+    if (p->sv) { const int rc = junctions_reset(p); if (rc != SLAMEM_OK) return rc; }
     if (p->dd) { const int rc = dedup_reset(p); if (rc != SLAMEM_OK) return rc; }
     for (slamem_pileup* c : {p->fwd, p->qual}) {  // (a forward or a quality accumulator has neither events nor a filter)
         if (!c) continue;

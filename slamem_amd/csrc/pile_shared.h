@@ -10,7 +10,8 @@
 
 namespace slamem {
 
-struct EvTable;  // event_filter.hip: the hash table of the indel events, its counters and its read-out's scratch
+struct EvTable;  // ev_table.h: the hash table of the indel events, its counters and its read-out's scratch
+struct SvTable;  // sv_filter.hip: the hash table of the junctions, the same table with its own counters
 struct ConsScratch;  // cons_filter.hip: the consensus read-out's scratch (a flag byte per row, the sorted events and their marks)
 struct DepthScratch;  // depth_filter.hip: the depth read-out's scratch (three numbers per tile)
 struct DdTable;  // dedup_filter.hip: the hash table of the duplicate filter, its counters and the order of its adds
@@ -26,6 +27,7 @@ struct slamem_pileup {
     uint32_t* tile;  // the read-out's tile sums: n / kPileTile + 2 words
     uint64_t* sel;   // the sparse read-out's selected rows per tile: n / kPileTile + 2 words of 64 bits
     slamem::EvTable* ev;  // nullptr: events are not enabled
+    slamem::SvTable* sv;  // nullptr: junctions are not enabled
     slamem::ConsScratch* cons;  // nullptr: no consensus was read yet
     slamem::DepthScratch* depth;  // nullptr: no depth runs were read yet
     slamem::DdTable* dd;  // nullptr: the duplicate filter is not enabled
@@ -206,6 +208,12 @@ int pile_scan_counts(uint64_t* sel, uint64_t tiles, hipStream_t stream);
 int events_add(slamem_pileup* pile, const void* batch /* PileBatch */, hipStream_t stream);
 int events_reset(slamem_pileup* pile);
 void events_free(slamem_pileup* pile);
+
+// sv_filter.hip, for pile_filter.hip: the junction kernel behind the pile kernels of an add (junctions enabled), and what reset and
+// free do to the table
+int junctions_add(slamem_pileup* pile, const void* batch /* PileBatch */, hipStream_t stream);
+int junctions_reset(slamem_pileup* pile);
+void junctions_free(slamem_pileup* pile);
 
 // cons_filter.hip, for pile_filter.hip: what free does to the consensus read-out's scratch
 void cons_free(slamem_pileup* pile);

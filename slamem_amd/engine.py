@@ -27,6 +27,8 @@ EVENT_DTYPE = np.dtype([("pos", "<u8"), ("letters", "<u8"), ("fwd", "<u4"), ("re
 SAM_LANE_OPS = 32  # -sam: the MD entries of a segment of up to this many operations are written by one lane, of a longer one by a wave (sam_filter.hip)
 MD_CLOSE = 8  # the closing entry of a segment: m << 4 | 8
 PILE_LANE_OPS = 32  # -pile: a segment of up to this many operations is walked by one lane, a longer one by a wave (pile_filter.hip)
+# slamem_junction: kind 0 a deletion of len rows from pos, 1 an insertion of len letters in front of pos
+JUNCTION_DTYPE = np.dtype([("pos", "<u8"), ("len", "<u4"), ("fwd", "<u4"), ("rev", "<u4"), ("kind", "u1"), ("pad", "u1", (3,))])
 # slamem_genotype: a <= b letter columns (SNV) or allele numbers 0 / 1 (event); scores in milli-Phred
 GENOTYPE_DTYPE = np.dtype([("qual", "<u4"), ("gq", "<u4"), ("a", "u1"), ("b", "u1"), ("ploidy", "u1"), ("ref", "u1"), ("pl", "<u4", (10,)),
                            ("pad", "u1", (4,))])
@@ -519,10 +521,13 @@ class Pileup:
     which receives exactly what the reads of strand 1 contribute, in the same kernels; 28 more bytes per text letter.  The reverse
     strand's rows are counts() - forward.counts().  quals=True (-wq): the accumulator owns a second one, `quality`,
     whose A C G T columns hold the sum of the base qualities of the letters that the same columns of counts() count; every add
-    then needs quals=, and genotypes(weighted=True) scores each letter by its own quality; 28 more bytes per text letter."""
+    then needs quals=, and genotypes(weighted=True) scores each letter by its own quality; 28 more bytes per text letter.
+    junctions=True (-sv): every add also records the long deletions and insertions between two segments of one read
+    in a hash table of junction_slots slots (a power of two of at least 64; 0: the default), a split between the two segments
+    having at most junction_max_mis (0 to 64) mismatches -- see junctions()."""
 
     def __init__(self, index: Index, events: bool = False, event_slots: int = 0, dedup: bool = False, dedup_slots: int = 0,
-                 strands: bool = False, quals: bool = False):
+                 strands: bool = False, quals: bool = False, junctions: bool = False, junction_slots: int = 0, junction_max_mis: int = 3):
         self.index = index
         self._h = C.c_void_p()
         self._owner = None  # (a forward or quality view: the Pileup that owns the handle)
@@ -532,12 +537,17 @@ class Pileup:
             raise ValueError("event_slots is the size of the event table: it needs events=True")
         if dedup_slots and not dedup:
             raise ValueError("dedup_slots is the size of the duplicate filter's table: it needs dedup=True")
+        if junction_slots and not junctions:
+            raise ValueError("junction_slots is the size of the junction table: it needs junctions=True")
+        if not 0 <= int(junction_max_mis) <= 64:
+            raise ValueError("junction_max_mis must be in [0, 64]")
         capi.check(capi.lib().slamem_pileup_create(index._h, C.byref(self._h)))
-        for on, enable, slots in ((events, capi.lib().slamem_pileup_enable_events, event_slots),
-                                  (dedup, capi.lib().slamem_pileup_enable_dedup, dedup_slots)):
+        for on, enable, slots in ((events, capi.lib().slamem_pileup_enable_events, (event_slots,)),
+                                  (dedup, capi.lib().slamem_pileup_enable_dedup, (dedup_slots,)),
+                                  (junctions, capi.lib().slamem_pileup_enable_junctions, (junction_slots, junction_max_mis))):
             if not on:
                 continue
-            rc = enable(self._h, int(slots))
+            rc = enable(self._h, *(int(v) for v in slots))
             if rc != capi.SLAMEM_OK:
                 h, self._h = self._h, None
                 try:
@@ -758,6 +768,44 @@ class Pileup:
         with torch.cuda.device(dev):
             capi.check(capi.lib().slamem_pileup_add_events_device(self._h, _ptr(t) if len(a) else None, len(a), _stream_handle(dev)))
             torch.cuda.current_stream(dev).synchronize()  # (the events' tensor goes when the caller returns)
+
+    def junctions(self, min_count: int = 1, min_len: int = 1, first: int = 0, count=None, capacity=None):
+        """(junctions, skipped): the junctions with first <= pos < first + count, fwd + rev >= min_count and
+        len >= min_len, sorted on the device by (pos, kind, len), as a structured array of JUNCTION_DTYPE, and the four counters of
+        junctions that were not stored (balanced; no room in the table; a letter that is none of A,C,G,T; too much slop or too many
+        mismatches).  capacity: junctions of room for the first attempt (default 4,096); when there are more the call is made once
+        more with the need it reported."""
+        first = int(first)
+        count = self.index.n - first if count is None else int(count)
+        dev = self.index.device
+        cap = 4096 if capacity is None else int(capacity)
+        total = C.c_uint64()
+        skipped = (C.c_uint64 * 4)()
+        with torch.cuda.device(dev):
+            for attempt in (0, 1):
+                buf = torch.empty(max(cap, 1) * 24, dtype=torch.uint8, device=dev)
+                rc = capi.lib().slamem_pileup_junctions_device(self._h, first, count, int(min_count), int(min_len), cap, _ptr(buf), skipped,
+                                                               C.byref(total), _stream_handle(dev))
+                if rc != capi.SLAMEM_ERR_CAPACITY or attempt:
+                    break
+                cap = int(total.value)
+            capi.check(rc)
+            torch.cuda.current_stream(dev).synchronize()
+        m = int(total.value)
+        return buf[:m * 24].cpu().numpy().view(JUNCTION_DTYPE).copy(), [int(v) for v in skipped]
+
+    def add_junctions(self, junctions) -> None:
+        """Adds junctions (a structured array of JUNCTION_DTYPE) with their fwd and rev counts: with junctions() of another
+        accumulator of the same text the table becomes the sum of both.  A deletion is normalised; an insertion stays where it is
+        given."""
+        a = np.ascontiguousarray(np.asarray(junctions))
+        if a.dtype != JUNCTION_DTYPE or a.ndim != 1:
+            raise ValueError("add_junctions takes a one-dimensional array of JUNCTION_DTYPE")
+        dev = self.index.device
+        t = torch.from_numpy(a.view(np.uint8).copy()).to(dev) if len(a) else None
+        with torch.cuda.device(dev):
+            capi.check(capi.lib().slamem_pileup_add_junctions_device(self._h, _ptr(t) if len(a) else None, len(a), _stream_handle(dev)))
+            torch.cuda.current_stream(dev).synchronize()  # (the junctions' tensor goes when the caller returns)
 
     def rows_at(self, positions) -> np.ndarray:
         """The rows of counts() at the listed positions as an (m, 6) uint32 array; a position at or beyond n gives zeros."""

@@ -704,6 +704,10 @@ static void usage(const char *prog) { /* slamem.c:533-553 */
     printf("\t-sb\twith -gt: strand counts in the pileup (a second accumulator on the GPU, fed by the forward-strand reads in the same pass); every line gets the strand table SB = reference forward, reference reverse, alternative forward, alternative reverse in the sample column and FS, the Phred-scaled Fisher exact test of it, in INFO\n");
     printf("\t-wq\twith -gt: every letter weighs with its own base quality in the likelihood of an SNV (a third accumulator on the GPU holds the sum of the qualities per row and letter); every SNV line gets ADQ, the quality sum per allele in AD's order; -err still scores the indel events and the letters of FASTA queries\n");
     printf("\t-fs\twith -sb: FILTER is sb for a line whose FS is above this whole number, 0 to 999, and PASS otherwise (default: FILTER stays .)\n");
+    printf("\t-sv\twith -vcf: the long deletions and insertions that lie between two segments of one read (gaps that -maxed edits do not close), found on the GPU and written as <DEL> and <INS> lines with SVTYPE, END and SVLEN; not with -gt\n");
+    printf("\t-svmin\twith -sv: least length of a junction that is written (default: maxed + 1)\n");
+    printf("\t-svmis\twith -sv: mismatches the letters that both segments own may have in the best split between them, 0 to 64 (default=3)\n");
+    printf("\t-svslots\twith -sv: slots of the junction table on the GPU, a power of two of at least 64 (default: at least 65536 and a 64th of the reference)\n");
     printf("\t-evs\twith -vcf: slots of the event table on the GPU, a power of two of at least 64 (default: at least 65536 and a sixteenth of the reference)\n");
     printf("\t-stats\tmap the reads as -paf does and write the mapping statistics, added up on the GPU: totals (reads, mapped, strands, mismatch and indel rates), MAPQ, read lengths, edits per read, per-cycle and per-base-quality error tables, the substitution spectrum and indel lengths; -minq sets the least mapping quality of the reads that count\n");
     printf("\t-l\tminimum match length (default=20)\n");
@@ -750,6 +754,8 @@ typedef struct {
     slamem_index *gpus[16];
     int ngpu;
     slamem_pileup *piles[16];
+    int sv, sv_min, sv_mis; /* -sv: junctions in the -vcf file; the least length written; mismatches of a split */
+    uint64_t sv_slots, sv_skipped[4], sv_stored, sv_counts[2]; /* ... the table's slots; what GPUs 1.. did not store; keys; lines and first rows */
     int gext;              /* -gext Z: the band of the gapped outer ends; 0: the option is absent */
     int affine, costs[3];  /* -affine X,O,E: gap-affine costs of the gaps between chain anchors */
     int stats;             /* -stats: the mapping QC table; runs as -paf, nothing is formatted per read */
@@ -804,6 +810,8 @@ static int parse_and_refuse(run_t *R, int *status) {
     R->sb = slh_parse_sb_params(argc, argv, &R->fs) & 1; /* (refused above when the value of -fs is not one) */
     R->affine = slh_parse_affine(argc, argv, &R->costs[0], &R->costs[1], &R->costs[2]) > 0; /* (the same) */
     if (slh_parse_gext(argc, argv, &R->gext) <= 0) R->gext = 0;
+    R->sv = slh_parse_sv(argc, argv, &R->sv_min, &R->sv_mis, &R->sv_slots) & 1; /* (a bad value, -sv without -vcf or with -gt: refused above) */
+    if (R->sv_min < 0) R->sv_min = (R->p.max_edits >= 0 ? R->p.max_edits : 31) + 1;
     memset(&R->gtp, 0, sizeof(R->gtp));
     if (R->p.gt) { /* host arithmetic: the three costs of a letter at the error rate of -err */
         uint32_t costs[3];
@@ -966,6 +974,7 @@ static void open_output(run_t *R) {
     if (R->wq) say(" ; base qualities in the likelihood = on");
     if (p->cons) say(" ; minimum depth = %d", p->min_depth);
     if (p->depth) say(" ; covered from depth = %d", p->min_depth);
+    if (R->sv) say(" ; sv min = %d", R->sv_min);
     say("\n");
     R->out = fopen(R->out_name, "w");
     if (!R->out) {
@@ -1114,6 +1123,7 @@ static void open_streams(run_t *R) {
             if (rc == SLAMEM_OK && R->sb) rc = slamem_pileup_enable_strands(R->piles[g]);
             if (rc == SLAMEM_OK && R->wq) rc = slamem_pileup_enable_quals(R->piles[g]);
             if (rc == SLAMEM_OK && (p->vcf || p->cons)) rc = slamem_pileup_enable_events(R->piles[g], p->ev_slots);
+            if (rc == SLAMEM_OK && R->sv) rc = slamem_pileup_enable_junctions(R->piles[g], R->sv_slots, (uint32_t)R->sv_mis);
             if (rc == SLAMEM_OK && p->dedup) rc = slamem_pileup_enable_dedup(R->piles[g], p->dd_slots);
             if (rc == SLAMEM_OK) rc = slamem_stream_set_pileup(s, R->piles[g], (uint32_t)p->min_mapq);
             if (rc == SLAMEM_OK && p->dedup) rc = slamem_stream_set_dedup(s, 1);
@@ -1363,6 +1373,17 @@ static int fetch_events(void *ctx, uint64_t cap, uint64_t *total) {
     return slamem_pileup_events_host(c->pile, c->x0, c->cnt, 1, cap, c->evs, c->sk, total);
 }
 
+typedef struct { /* a range of a pileup and where its junctions go */
+    slamem_pileup *pile;
+    uint64_t x0, cnt, sk[4];
+    uint32_t min_len;
+    slamem_junction *jns;
+} junctions_call;
+static int fetch_junctions(void *ctx, uint64_t cap, uint64_t *total) {
+    junctions_call *c = (junctions_call *)ctx;
+    return slamem_pileup_junctions_host(c->pile, c->x0, c->cnt, 1, c->min_len, cap, c->jns, c->sk, total);
+}
+
 #define FOR_RANGES(x0, cnt) for (x0 = 0; x0 < n && (cnt = n - x0 < R->readout_rows ? n - x0 : R->readout_rows) > 0; x0 += R->readout_rows)
 
 /* the tables of GPUs 1.. are added into GPU 0's, and their events, which arrive normalised and stay as they are */
@@ -1415,6 +1436,35 @@ static void merge_gpu_tables(run_t *R) {
         R->skipped[0] += ec.sk[0]; R->skipped[1] += ec.sk[1]; R->skipped[2] += ec.sk[2]; /* (what GPU g could not store) */
     }
     free(ec.evs);
+    if (R->sv) { /* -sv: the junctions of GPUs 1.., whatever their length; they arrive normalised and stay as they are */
+        uint64_t jcap = 1ull << 12;
+        junctions_call jc;
+        const grow_buf jbufs[1] = {{(void **)&jc.jns, sizeof(slamem_junction), 0}};
+        int k;
+        memset(&jc, 0, sizeof(jc));
+        for (g = 1; g < g_nstreams; g++) {
+            jc.pile = R->piles[g]; jc.x0 = 0; jc.cnt = n; jc.min_len = 0;
+            rc = fetch_growing(&jcap, jbufs, 1, fetch_junctions, &jc, &total);
+            if (rc == SLAMEM_OK) rc = slamem_pileup_add_junctions_host(R->piles[0], jc.jns, total);
+            if (rc != SLAMEM_OK) pipeline_gpu_fail("adding up the junctions of the GPUs", rc);
+            for (k = 0; k < 4; k++) R->sv_skipped[k] += jc.sk[k]; /* (what GPU g did not store) */
+        }
+        free(jc.jns);
+    }
+}
+
+/* -sv: what became of the junctions, on stderr when there is anything to say */
+static void report_junctions(run_t *R, const uint64_t sk[4]) {
+    uint64_t s[4], total = 0;
+    int k;
+    if (slamem_pileup_junctions_host(R->piles[0], 0, R->ref.total, 1, 0, 0, NULL, s, &total) != SLAMEM_ERR_CAPACITY) total = 0;
+    for (k = 0; k < 4; k++) s[k] = R->sv_skipped[k] + sk[k];
+    if (total | R->sv_counts[0] | R->sv_counts[1] | s[0] | s[1] | s[2] | s[3])
+        fprintf(stderr, "> Junctions: %llu stored, %llu lines written, %llu at a record's first row left out; not stored: %llu balanced, "
+                        "%llu without room in the table%s, %llu with a letter that is none of A,C,G,T, %llu with more than 64 shared letters "
+                        "or too many mismatches\n", (unsigned long long)total, (unsigned long long)R->sv_counts[0],
+                (unsigned long long)R->sv_counts[1], (unsigned long long)s[0], (unsigned long long)s[1], s[1] ? " (a larger table: -svslots)" : "",
+                (unsigned long long)s[2], (unsigned long long)s[3]);
 }
 
 /* -vcf, -cons: GPU 0's own counters (the merge included) come on top of the other GPUs' */
@@ -1478,7 +1528,10 @@ static void write_sites_or_vcf(run_t *R) {
     const slh_run *p = &R->p;
     const slh_seqset *ref = &R->ref;
     const uint64_t n = ref->total;
-    uint64_t x0, cnt, cap = 1ull << 20, ecap = 1ull << 16, total, etotal, k, ek, e, ee, j, *anchors = NULL;
+    uint64_t x0, cnt, cap = 1ull << 20, ecap = 1ull << 16, jcap = 1ull << 12, total, etotal, jtotal, k, ek, e, ee, j, jk, je, *anchors = NULL;
+    uint64_t *janchors = NULL; /* -sv: the junctions of the range, their anchor rows pos - 1 and the pileup rows there */
+    uint32_t *jrows = NULL;
+    junctions_call jc;
     uint32_t *arows = NULL, *frows = NULL, *afrows = NULL; /* -sb: the forward accumulator's rows at the sites and at the anchors */
     slamem_pileup *fwd = NULL;
     slamem_genotype *egts = NULL; /* -gt: the genotypes of the events, and which events are called */
@@ -1489,15 +1542,19 @@ static void write_sites_or_vcf(run_t *R) {
                                {(void **)&frows, 24, 0}, {(void **)&sc.qsums, 16, 0}};
     const grow_buf ebufs[6] = {{(void **)&ec.evs, sizeof(slamem_event), 0}, {(void **)&anchors, 8, 0}, {(void **)&arows, 24, 0},
                                {(void **)&egts, sizeof(slamem_genotype), 0}, {(void **)&ecalled, 1, 0}, {(void **)&afrows, 24, 0}};
+    const grow_buf jbufs[3] = {{(void **)&jc.jns, sizeof(slamem_junction), 0}, {(void **)&janchors, 8, 0}, {(void **)&jrows, 24, 0}};
     int r = 0, m, pi, rc;
     memset(&sc, 0, sizeof(sc));
     memset(&ec, 0, sizeof(ec));
+    memset(&jc, 0, sizeof(jc));
     sc.R = R;
-    ec.pile = R->piles[0];
+    ec.pile = jc.pile = R->piles[0];
+    jc.min_len = (uint32_t)R->sv_min;
     if (R->sb && (rc = slamem_pileup_forward(R->piles[0], &fwd)) != SLAMEM_OK) pipeline_gpu_fail("reading the forward-strand pileup from the GPU", rc);
     if (p->vcf && (R->wq ? slh_format_vcf_wq_header(&R->buf, ref->recs, ref->num, R->sb, R->fs)
                    : R->sb ? slh_format_vcf_sb_header(&R->buf, ref->recs, ref->num, R->fs)
-                   : p->gt ? slh_format_vcf_gt_header(&R->buf, ref->recs, ref->num) : slh_format_vcf_header(&R->buf, ref->recs, ref->num)))
+                   : p->gt ? slh_format_vcf_gt_header(&R->buf, ref->recs, ref->num)
+                   : R->sv ? slh_format_vcf_sv_header(&R->buf, ref->recs, ref->num) : slh_format_vcf_header(&R->buf, ref->recs, ref->num)))
         pipeline_fail("Out of memory");
     FOR_RANGES(x0, cnt) {
         sc.x0 = ec.x0 = x0;
@@ -1524,7 +1581,16 @@ static void write_sites_or_vcf(run_t *R) {
                 if (rc != SLAMEM_OK) pipeline_gpu_fail("genotyping the indel events on the GPU", rc);
             }
         }
-        for (pi = 0, k = ek = 0; pi < m && (k < total || ek < etotal); pi++, k = e, ek = ee) { /* the rows and events of one record after the other */
+        jtotal = 0;
+        if (R->sv) { /* the junctions of the range and the pileup rows of their anchors (a junction at row 0 has none: any row does) */
+            jc.x0 = x0; jc.cnt = cnt;
+            rc = fetch_growing(&jcap, jbufs, 3, fetch_junctions, &jc, &jtotal);
+            if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the junctions from the GPU", rc);
+            for (j = 0; j < jtotal; j++) janchors[j] = jc.jns[j].pos ? jc.jns[j].pos - 1 : 0;
+            rc = slamem_pileup_rows_at_host(R->piles[0], janchors, jtotal, jrows);
+            if (rc != SLAMEM_OK) pipeline_gpu_fail("reading the pileup rows of the junctions from the GPU", rc);
+        }
+        for (pi = 0, k = ek = jk = 0; pi < m && (k < total || ek < etotal || jk < jtotal); pi++, k = e, ek = ee, jk = je) { /* the rows and events of one record after the other */
             const slh_piece *pc = &R->pcs[pi];
             const char *name = ref->recs[pc->rec].name;
             const uint32_t size = ref->recs[pc->rec].size;
@@ -1532,7 +1598,9 @@ static void write_sites_or_vcf(run_t *R) {
             while (ek < etotal && ec.evs[ek].pos < pc->start) ek++;
             for (e = k; e < total && sc.pos[e] < pc->b; e++) {}
             for (ee = ek; ee < etotal && ec.evs[ee].pos < pc->start + size; ee++) {}
-            if (e == k && ee == ek) continue;
+            while (jk < jtotal && jc.jns[jk].pos < pc->start) jk++;
+            for (je = jk; je < jtotal && jc.jns[je].pos < pc->start + size; je++) {}
+            if (e == k && ee == ek && je == jk) continue;
             if (!p->vcf ? slh_format_site_rows(&R->buf, name, pc->start, ref->chars, sc.pos + k, sc.rows + k * 6, sc.alleles + k, e - k)
                 : R->wq ? slh_format_vcf_wq_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6, frows + k * 6,
                                                  sc.qsums + k * 4, (const slh_genotype *)(sc.gts + k), e - k, (const slh_event *)(ec.evs + ek),
@@ -1544,6 +1612,9 @@ static void write_sites_or_vcf(run_t *R) {
                 : p->gt ? slh_format_vcf_gt_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6,
                                                  (const slh_genotype *)(sc.gts + k), e - k, (const slh_event *)(ec.evs + ek), arows + ek * 6,
                                                  (const slh_genotype *)(egts + ek), ecalled + ek, ee - ek)
+                : R->sv ? slh_format_vcf_sv_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6, sc.alleles + k, e - k,
+                                                 (const slh_event *)(ec.evs + ek), arows + ek * 6, ee - ek, (const slh_junction *)(jc.jns + jk),
+                                                 jrows + jk * 6, je - jk, (uint32_t)p->min_depth, (uint32_t)p->min_pct, R->sv_counts)
                         : slh_format_vcf_rows(&R->buf, name, pc->start, size, ref->chars, sc.pos + k, sc.rows + k * 6, sc.alleles + k, e - k,
                                               (const slh_event *)(ec.evs + ek), arows + ek * 6, ee - ek, (uint32_t)p->min_depth,
                                               (uint32_t)p->min_pct))
@@ -1553,7 +1624,9 @@ static void write_sites_or_vcf(run_t *R) {
     }
     free(sc.pos); free(sc.rows); free(sc.alleles); free(sc.gts); free(sc.qsums);
     free(ec.evs); free(anchors); free(arows); free(egts); free(ecalled); free(frows); free(afrows);
+    free(jc.jns); free(janchors); free(jrows);
     if (p->vcf) warn_skipped(R, ec.sk);
+    if (R->sv) report_junctions(R, jc.sk);
 }
 
 typedef struct { /* -cons: the consensus of a range, cut at the bounds */

@@ -923,7 +923,8 @@ int slh_parse_argument(int argc, char **argv, const char *optionchars, int parse
 enum { V_NONE, V_INT, V_POW2, V_DIGITS, V_LEVELS, V_COSTS, V_ATOI, V_INDEX, V_STRING };
 typedef struct {
     const char *name;   /* as usage() spells it; "l": a one-letter option */
-    char third, unless; /* third != 0: the third letter is name[2] (-maxed, -dedup); unless: the third letter is not this one (-mam, -depth) */
+    char third, unless; /* third == 1: the third letter is name[2] (-maxed, -dedup; -sv: the name ends there); third == 2: the whole name
+                           counts (-svmin, -svmis, -svslots); unless: the third letter is not this one (-mam, -depth) */
     char kind;          /* V_NONE: no value.  V_INT: strtol's whole number in [lo, hi]; V_POW2: such a power of two; V_DIGITS: a number
                            that begins with a digit; V_LEVELS: 1 to 16 of those, ascending, with commas; V_COSTS: three of those with
                            commas, X in 1..31, O in 0..63, E in 1..31, handed out as X | O << 8 | E << 16; V_ATOI, V_INDEX, V_STRING:
@@ -935,6 +936,7 @@ typedef struct {
 } option_row;
 enum { O_MEM, O_MAM, O_MUM, O_SMEM, O_OCC, O_CHAIN, O_MGAP, O_EXT, O_PEN, O_XDROP, O_ALN, O_MAXED, O_PAF, O_SAM, O_PILE, O_MINQ, O_BQ,
        O_SITES, O_MDEP, O_MPCT, O_VCF, O_CONS, O_DEPTH, O_LEV, O_WIN, O_DEDUP, O_DSLOTS, O_GT, O_PLOIDY, O_ERR, O_HETQ, O_QUAL, O_SB, O_FS, O_WQ, O_EVS, O_STATS, O_AFFINE, O_GEXT,
+       O_SV, O_SVMIN, O_SVMIS, O_SVSLOTS,
        O_L, O_O, O_B, O_N, O_M, O_R, O_V, O_S, O_C, NUM_OPTIONS };
 #define PEN_XDROP "Option -pen needs a whole number of at least 1, option -xdrop one of at least 0"
 static const option_row OPTIONS[NUM_OPTIONS] = {
@@ -977,6 +979,10 @@ static const option_row OPTIONS[NUM_OPTIONS] = {
     [O_STATS] = {"stats", 0, 0, V_NONE, 7, 0, 0, 0, "Option -stats excludes -mam, -mum, -smem, -chain, -ext, -aln, -paf, -sam, -pile, -sites, -vcf, -cons and -depth"},
     [O_AFFINE] = {"affine", 0, 0, V_COSTS, 0, 0, 0, -1, "Option -affine needs three whole numbers X,O,E: X from 1 to 31, O from 0 to 63, E from 1 to 31, separated by commas"},
     [O_GEXT] = {"gext", 0, 0, V_INT, 0, 1, 31, 0, "Option -gext needs a whole number from 1 to 31"},
+    [O_SV] = {"sv", 1, 0, V_NONE, 0, 0, 0, 0, NULL},
+    [O_SVMIN] = {"svmin", 2, 0, V_INT, 0, 1, 0x7FFFFFFF, -1, "Option -svmin needs a whole number of at least 1"},
+    [O_SVMIS] = {"svmis", 2, 0, V_INT, 0, 0, 64, 3, "Option -svmis needs a whole number from 0 to 64"},
+    [O_SVSLOTS] = {"svslots", 2, 0, V_POW2, 0, 64, 1ull << 31, 0, "Option -svslots needs a power of two of at least 64"},
     [O_L] = {"l", 0, 0, V_ATOI, 0, 0, 0, 20, NULL},
     [O_O] = {"o", 0, 0, V_INDEX, 0, 0, 0, -1, NULL},
     [O_B] = {"b", 0, 0, V_NONE, 0, 0, 0, 0, NULL},
@@ -998,6 +1004,11 @@ static int is_option(const char *a, int id) {
     if (a[0] != '-' || a[1] == '\0' || lower(a[1]) != r->name[0]) return 0;
     if (r->name[1] == '\0') return a[2] == '\0';
     if (lower(a[2]) != r->name[1]) return 0;
+    if (r->third == 2) {
+        size_t k;
+        for (k = 2; r->name[k] != '\0' && lower(a[k + 1]) == r->name[k]; k++) {}
+        return r->name[k] == '\0' && a[k + 1] == '\0';
+    }
     if (r->third) return lower(a[3]) == r->name[2];
     return !r->unless || lower(a[3]) != r->unless;
 }
@@ -1141,6 +1152,17 @@ int slh_parse_affine(int argc, char **argv, int *x_out, int *o_out, int *e_out) 
     return rc;
 }
 int slh_parse_gext(int argc, char **argv, int *out) { return scan_whole(argc, argv, O_GEXT, out); }
+/* -sv and its three values: bit 0 -sv, bit 1 -svmin, bit 2 -svmis, bit 3 -svslots; -(k + 1): the value of row k is refused.
+ * *min_len_out is -1 when -svmin is absent (the caller's default is maxed + 1). */
+int slh_parse_sv(int argc, char **argv, int *min_len_out, int *max_mis_out, uint64_t *slots_out) {
+    static const int ids[4] = {O_SV, O_SVMIN, O_SVMIS, O_SVSLOTS};
+    uint64_t v[4];
+    const int rc = scan_options(argc, argv, ids, 4, 0, v, NULL);
+    *min_len_out = (int)(long long)v[1];
+    *max_mis_out = (int)(long long)v[2];
+    *slots_out = v[3];
+    return rc;
+}
 uint32_t slh_aln_word(int max_edits, int affine, int x, int o, int e) {
     if (!affine) return max_edits >= 0 ? (uint32_t)max_edits : SLAMEM_ALN_EDITS_DEFAULT;
     return SLAMEM_ALN_AFFINE(max_edits >= 0 ? max_edits : 31, x, o, e);
@@ -1245,7 +1267,8 @@ static int refuse(const char **refusal, const char *msg, int rc) {
 
 int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     slh_options *o = &r->o;
-    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct, sb, fs, aff, costs[3], gx, band;
+    int t, k, occ, gap, ext, edits, mapq, sparams, gtp, dparams, evs, dd, mpct, sb, fs, aff, costs[3], gx, band, sv, svmin, svmis;
+    uint64_t svslots;
     *refusal = NULL;
     memset(r, 0, sizeof(*r));
     if (slh_parse_options(argc, argv, o) != 0) return refuse(refusal, "Out of memory", -1);
@@ -1272,6 +1295,7 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     sb = slh_parse_sb_params(argc, argv, &fs); /* (the values are the caller's to ask for: slh_run keeps its layout) */
     aff = slh_parse_affine(argc, argv, &costs[0], &costs[1], &costs[2]); /* (the same) */
     gx = slh_parse_gext(argc, argv, &band); /* (the same) */
+    sv = slh_parse_sv(argc, argv, &svmin, &svmis, &svslots); /* (the same) */
     r->dedup = dd > 0 && (dd & 1);
     if (o->usage || o->hidden_sort || o->hidden_clean) return 0; /* (the caller's business, before any refusal) */
 
@@ -1328,6 +1352,12 @@ int slh_parse_run(int argc, char **argv, slh_run *r, const char **refusal) {
     REFUSE_IF(dd < 0, OPTIONS[O_DSLOTS].refusal);
     REFUSE_IF(dd == 2, "Option -dslots needs -dedup");
     REFUSE_IF(dd && t != 8, "Option -dedup needs -pile, -sites, -vcf, -cons or -depth");
+    REFUSE_IF(sv < 0, OPTIONS[O_SV - 1 - sv].refusal);
+    REFUSE_IF((sv & 1) && !r->vcf, "Option -sv needs -vcf");
+    REFUSE_IF((sv & 2) && !(sv & 1), "Option -svmin needs -sv");
+    REFUSE_IF((sv & 4) && !(sv & 1), "Option -svmis needs -sv");
+    REFUSE_IF((sv & 8) && !(sv & 1), "Option -svslots needs -sv");
+    REFUSE_IF((sv & 1) && r->gt, "Option -sv excludes -gt");
 #undef REFUSE_IF
     /* (here the caller refuses what depends on more than the arguments) */
     if (o->num_files < 2) return refuse(refusal, "Not enough input sequence files provided", -2);
@@ -1747,6 +1777,88 @@ int slh_format_vcf_rows(slh_buffer *buf, const char *record_name, uint64_t recor
         }
     }
     return 0;
+}
+
+/* ---- -vcf -sv ---- */
+
+int slh_format_vcf_sv_header(slh_buffer *buf, const slh_record *refs, int num_refs) {
+    static const char *const COLUMNS = "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+    static const char *const SV =
+        "##ALT=<ID=DEL,Description=\"Deletion of the rows between two segments of a read\">\n"
+        "##ALT=<ID=INS,Description=\"Insertion of the letters between two segments of a read\">\n"
+        "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of the junction: DEL or INS\">\n"
+        "##INFO=<ID=END,Number=1,Type=Integer,Description=\"Last deleted position; POS for an insertion\">\n"
+        "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"Inserted letters, or the deleted positions as a negative number\">\n";
+    const size_t cl = strlen(COLUMNS), sl = strlen(SV);
+    if (slh_format_vcf_header(buf, refs, num_refs)) return -1;
+    if (buf_reserve(buf, sl)) return -1;
+    memcpy(buf->data + buf->len - cl, SV, sl); /* (in front of the column line, which the header ends with) */
+    memcpy(buf->data + buf->len - cl + sl, COLUMNS, cl);
+    buf->len += sl;
+    return 0;
+}
+
+/* slh_format_vcf_rows with the junctions of the record (ascending in pos, kind, len; jrows: the pileup rows of their anchors
+ * pos - 1) behind the SNVs and the events of a POS.  counts_out[0] += the lines written, [1] += the junctions at the record's
+ * first row, which have no anchor and give no line. */
+int slh_format_vcf_sv_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                           const uint64_t *site_pos, const uint32_t *site_counts, const uint8_t *site_alleles, uint64_t sites,
+                           const slh_event *events, const uint32_t *anchor_rows, uint64_t num_events, const slh_junction *junctions,
+                           const uint32_t *jrows, uint64_t num_junctions, uint32_t min_depth, uint32_t min_pct, uint64_t *counts_out) {
+    const size_t nl = cut_name_len(record_name);
+    uint64_t i = 0, e = 0, j = 0;
+    int rc = 0;
+    while (!rc && (i < sites || e < num_events || j < num_junctions)) { /* the order of slh_format_vcf_rows, a line group at a time */
+        uint64_t spos = i < sites ? site_pos[i] - record_start + 1 : ~0ull, epos = ~0ull, jpos = ~0ull;
+        if (e < num_events) epos = events[e].pos > record_start ? events[e].pos - record_start : 1;
+        if (j < num_junctions) {
+            if (junctions[j].pos <= record_start) { counts_out[1]++; j++; continue; }
+            jpos = junctions[j].pos - record_start;
+        }
+        if (spos <= epos && spos <= jpos) {
+            rc = slh_format_vcf_rows(buf, record_name, record_start, record_size, text, site_pos + i, site_counts + 6 * i, site_alleles + i, 1,
+                                     NULL, NULL, 0, min_depth, min_pct);
+            i++;
+        } else if (epos <= jpos) {
+            rc = slh_format_vcf_rows(buf, record_name, record_start, record_size, text, NULL, NULL, NULL, 0, events + e, anchor_rows + 6 * e, 1,
+                                     min_depth, min_pct);
+            e++;
+        } else {
+            const slh_junction *jn = &junctions[j];
+            const uint32_t *c = jrows + 6 * j;
+            const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4], ao = (uint64_t)jn->fwd + jn->rev;
+            char *p;
+            j++;
+            if (d < min_depth || 100ull * ao < (uint64_t)min_pct * d) continue;
+            if (buf_reserve(buf, nl + 192)) return -1;
+            p = vcf_line_head(buf->data + buf->len, record_name, nl, (uint32_t)jpos);
+            *p++ = upper_letter(text[jn->pos - 1]);
+#define PUT(str) do { memcpy(p, str, sizeof(str) - 1); p += sizeof(str) - 1; } while (0)
+            if (jn->kind == 0) {
+                PUT("\t<DEL>\t.\t.\tSVTYPE=DEL;END=");
+                p = vcf_put_u64(p, jpos + jn->len);
+                PUT(";SVLEN=-");
+            } else {
+                PUT("\t<INS>\t.\t.\tSVTYPE=INS;END=");
+                p = vcf_put_u64(p, jpos);
+                PUT(";SVLEN=");
+            }
+            p = put_u32(p, jn->len);
+            PUT(";DP=");
+            p = vcf_put_u64(p, d);
+            PUT(";AO=");
+            p = vcf_put_u64(p, ao);
+            PUT(";SF=");
+            p = put_u32(p, jn->fwd);
+            PUT(";SR=");
+            p = put_u32(p, jn->rev);
+#undef PUT
+            *p++ = '\n';
+            buf->len = (size_t)(p - buf->data);
+            counts_out[0]++;
+        }
+    }
+    return rc;
 }
 
 /* ---- -vcf -gt ---- */

@@ -250,6 +250,29 @@ int slh_format_vcf_rows(slh_buffer *buf, const char *record_name, uint64_t recor
                         const uint64_t *site_pos, const uint32_t *site_counts, const uint8_t *site_alleles, uint64_t sites,
                         const slh_event *events, const uint32_t *anchor_rows, uint64_t num_events, uint32_t min_depth,
                         uint32_t min_pct);
+/* -vcf -sv.  -sv and its values -svmin N (>= 1; *min_len_out -1 when absent: maxed + 1), -svmis N (0 to 64,
+ * default 3) and -svslots N (a power of two in [64, 2^31], 0 when absent): the options seen as bits 0..3 in this order, or
+ * -2, -3, -4 when the value of -svmin, -svmis, -svslots is refused. */
+int slh_parse_sv(int argc, char **argv, int *min_len_out, int *max_mis_out, uint64_t *slots_out);
+/* A junction as the engine reads it out (the layout of slamem_junction). */
+typedef struct {
+    uint64_t pos;
+    uint32_t len, fwd, rev;
+    uint8_t kind;
+    uint8_t pad[3];
+} slh_junction;
+/* The head of the -vcf -sv file: that of -vcf with the ##ALT lines of DEL and INS and the ##INFO lines of SVTYPE, END and SVLEN
+ * in front of the column line. */
+int slh_format_vcf_sv_header(slh_buffer *buf, const slh_record *refs, int num_refs);
+/* slh_format_vcf_rows with the record's junctions (ascending in pos, kind, len; jrows[6 j ..]: the pileup row of junction j's
+ * anchor pos - 1): a junction is called by the events' rule at its anchor and written, with x the anchor's position in the record,
+ * as POS x, REF the anchor's letter, ALT <DEL> with SVTYPE=DEL;END=x+len;SVLEN=-len or ALT <INS> with SVTYPE=INS;END=x;SVLEN=len,
+ * then DP, AO, SF, SR; at one POS behind the SNVs and the events.  A junction at the record's first row has no anchor and gives
+ * no line.  counts_out[0] += the junction lines written, counts_out[1] += the junctions at a first row. */
+int slh_format_vcf_sv_rows(slh_buffer *buf, const char *record_name, uint64_t record_start, uint64_t record_size, const char *text,
+                           const uint64_t *site_pos, const uint32_t *site_counts, const uint8_t *site_alleles, uint64_t sites,
+                           const slh_event *events, const uint32_t *anchor_rows, uint64_t num_events, const slh_junction *junctions,
+                           const uint32_t *jrows, uint64_t num_junctions, uint32_t min_depth, uint32_t min_pct, uint64_t *counts_out);
 /* -vcf -gt.  A genotype as the engine writes it (the layout of slamem_genotype): scores in milli-Phred, a <= b
  * letter columns (SNV) or allele numbers 0 / 1 (event), pl by genotype number. */
 typedef struct {
