@@ -906,6 +906,40 @@ int slamem_pileup_genotypes_weighted_host(slamem_pileup *pile, uint64_t first, u
                                           uint64_t capacity, uint64_t *pos, uint32_t *counts, slamem_genotype *gts, uint32_t *qsums,
                                           uint64_t *total_out);
 
+/* ---- the consensus by genotype likelihood (no option of the front end yet) -------------------------------------------------
+ * slamem_pileup_consensus_* with every decision made by the likelihood of -gt.  `row` holds the ploidy, the three costs and the
+ * prior of the rows -- what slamem_pileup_genotypes_* would take, -wq's costs when weighted -- and `event` those of the events --
+ * what slamem_pileup_genotype_events_* would take; min_depth and min_qual inside the two are not looked at.  A genotype is
+ * confident when its GQ, in 64 bits before saturation, is at least 1000 * min_gq.  An event is applied iff its anchor row a (as
+ * above) holds one of A,C,G,T, d(a) >= min_depth, and the best genotype of the event against everything else at a is homozygous
+ * for it (1/1, or 1 at ploidy 1) and confident; a heterozygous event is not applied.  Row p emits, in this order:
+ *   1. and 2. as slamem_pileup_consensus_* over the events applied by this rule;
+ *   3. else N if not ACGT(p);
+ *   4. else L(p) in lower case if d(p) < min_depth, or A+C+G+T == 0, or the genotype of the row (with its quality sums when
+ *      weighted != 0) is not confident;
+ *   5. else the best genotype (a, b) in upper case: the letter when a == b, else the IUPAC code of the two (AC M, AG R, AT W,
+ *      CG S, CT Y, GT K), also when one of them is L(p).  Ties are those of slamem_pileup_genotypes_*.
+ * stats_out has 8 entries: the five of slamem_pileup_consensus_* -- [0] every row of rule 4, [1] rows of rule 5 whose byte is not
+ * L(p), an IUPAC code included -- then [5] rows that emit an IUPAC code, [6] rows of rule 4 with d(p) >= min_depth and
+ * A+C+G+T > 0 (uncalled for GQ alone), [7] events with first <= pos < first + count whose best genotype is heterozygous and
+ * confident, whatever their anchor.  Every range's bytes are a slice of the whole text's and the statistics add up over disjoint
+ * ranges.  Capacity, bounds and stream contracts, scratch and what is left unmodified: as slamem_pileup_consensus_*.
+ * SLAMEM_ERR_ARG besides: a ploidy, cost or prior outside the ranges of slamem_gt_params, min_depth of 0 or of 2^31 and more,
+ * min_gq above 999, weighted above 1, weighted on an accumulator without quality sums. */
+typedef struct {
+    slamem_gt_params row;   /* ploidy, match_cost, het_cost, err_cost, het_prior of the rows */
+    slamem_gt_params event; /* ... of the events */
+    uint32_t min_depth;     /* A+C+G+T+D at least this, 1 to 2^31 - 1 */
+    uint32_t min_gq;        /* in Phred, 0 to 999 */
+    uint32_t weighted;      /* 1: the rows' quality sums count (an accumulator with slamem_pileup_enable_quals) */
+} slamem_cons_gt_params;
+int slamem_pileup_consensus_gt_device(slamem_pileup *pile, uint64_t first, uint64_t count, const slamem_cons_gt_params *params,
+                                      uint64_t capacity, uint8_t *out_dev, const uint64_t *bounds_dev, uint64_t m, uint64_t *offs_dev,
+                                      uint64_t *stats_out /* 8 */, uint64_t *total_out, void *stream);
+int slamem_pileup_consensus_gt_host(slamem_pileup *pile, uint64_t first, uint64_t count, const slamem_cons_gt_params *params,
+                                    uint64_t capacity, uint8_t *out, const uint64_t *bounds, uint64_t m, uint64_t *offs,
+                                    uint64_t *stats_out /* 8 */, uint64_t *total_out);
+
 /* ---- (b''''''''''') junctions: long deletions and insertions between segments (option -sv) ---------------------
  * A gap between two chain anchors that -aln does not close ends a segment; the table and the events above hold nothing of what
  * lies between two segments of one read.  With junctions enabled every add of reads also looks at each adjacent pair (a, b) of a

@@ -57,7 +57,8 @@ ABI_SYMBOLS = (
     "slamem_pileup_sites_device", "slamem_pileup_sites_host", "slamem_pileup_add_counts_device", "slamem_pileup_add_counts_host",
     "slamem_pileup_enable_events", "slamem_pileup_events_device", "slamem_pileup_events_host", "slamem_pileup_add_events_device",
     "slamem_pileup_add_events_host", "slamem_pileup_rows_at_device", "slamem_pileup_rows_at_host",
-    "slamem_pileup_consensus_device", "slamem_pileup_consensus_host", "slamem_pileup_depth_runs_device", "slamem_pileup_depth_runs_host",
+    "slamem_pileup_consensus_device", "slamem_pileup_consensus_host", "slamem_pileup_consensus_gt_device",
+    "slamem_pileup_consensus_gt_host", "slamem_pileup_depth_runs_device", "slamem_pileup_depth_runs_host",
     "slamem_stream_create", "slamem_stream_set_max_occ", "slamem_stream_set_max_gap", "slamem_stream_submit", "slamem_stream_submit_packed", "slamem_pack_reads", "slamem_stream_next",
     "slamem_pack_lowq_device", "slamem_pack_lowq", "slamem_pileup_add_masked_device", "slamem_stream_submit_masked",
     "slamem_pileup_enable_dedup", "slamem_pileup_add_dedup_device", "slamem_pileup_dedup_stats", "slamem_stream_set_dedup", "slamem_stream_dups",
@@ -133,6 +134,11 @@ class GtParams(C.Structure):
     """slamem_gt_params (-gt)"""
     _fields_ = [("ploidy", C.c_uint32), ("match_cost", C.c_uint32), ("het_cost", C.c_uint32), ("err_cost", C.c_uint32),
                 ("het_prior", C.c_uint32), ("min_depth", C.c_uint32), ("min_qual", C.c_uint32)]
+
+
+class ConsGtParams(C.Structure):
+    """slamem_cons_gt_params (the consensus by genotype likelihood)"""
+    _fields_ = [("row", GtParams), ("event", GtParams), ("min_depth", C.c_uint32), ("min_gq", C.c_uint32), ("weighted", C.c_uint32)]
 
 
 def _declare(L):
@@ -257,6 +263,8 @@ def _declare(L):
     L.slamem_pileup_rows_at_host.argtypes = [vp, vp, u64, vp]
     L.slamem_pileup_consensus_device.argtypes = [vp, u64, u64, u32, u64, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), vp]
     L.slamem_pileup_consensus_host.argtypes = [vp, u64, u64, u32, u64, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.slamem_pileup_consensus_gt_device.argtypes = [vp, u64, u64, C.POINTER(ConsGtParams), u64, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), vp]
+    L.slamem_pileup_consensus_gt_host.argtypes = [vp, u64, u64, C.POINTER(ConsGtParams), u64, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
     L.slamem_pileup_depth_runs_device.argtypes = [vp, u64, u64, vp, u32, u32, u64, vp, vp, u64, vp, C.POINTER(u64), vp]
     L.slamem_pileup_depth_runs_host.argtypes = [vp, u64, u64, vp, u32, u32, u64, vp, vp, u64, vp, C.POINTER(u64)]
     L.slamem_stream_set_pileup.argtypes = [vp, vp, u32]

@@ -891,14 +891,22 @@ class Pileup:
             torch.cuda.current_stream(dev).synchronize()
         return gts[:m * GENOTYPE_DTYPE.itemsize].cpu().numpy().view(GENOTYPE_DTYPE).copy(), called[:m].cpu().numpy()
 
-    def consensus(self, min_depth: int = 4, first: int = 0, count=None, bounds=None, capacity=None):
+    def consensus(self, min_depth: int = 4, first: int = 0, count=None, bounds=None, capacity=None, genotype=None):
         """The consensus sequence of rows [first, first + count), built on the device, as (bytes uint8 (total,),
         offs uint64 (m,), stats): the text with the majority alleles applied -- per row the plurality letter in upper case, the
         text's letter in lower case where the depth A+C+G+T+D is below min_depth, N where the text has none of A,C,G,T, and the
         indel events that more than half of their anchor row's depth show.  bounds: rows in [first, first + count]; offs[j] is
         the number of bytes the rows in front of bounds[j] emit.  stats: rows uncalled, rows called unlike the text, rows deleted,
         insertions emitted, letters inserted.  capacity: bytes of room for the first attempt (default: the range and a 64th, at
-        least 4,096); when the consensus is longer the call is made once more with the need it reported."""
+        least 4,096); when the consensus is longer the call is made once more with the need it reported.
+        genotype: None, or a dict with any of ploidy=2, err_q=20, het_q=30, min_gq=20, weighted=False, costs=None (the one form:
+        there are no keyword arguments beside it) -- the consensus by genotype likelihood.  A row is called by the
+        genotype of genotypes(ploidy, err_q, het_q, weighted=, costs=): the text's letter in lower case unless the depth reaches
+        min_depth, A+C+G+T > 0 and the genotype's GQ reaches min_gq Phred (0 to 999); else the best genotype in upper case, a
+        heterozygous one as its IUPAC code.  An event is applied when the genotype of genotype_events(ploidy, err_q, het_q) at
+        its anchor row is homozygous for it with that GQ.  weighted=True needs an accumulator made with quals=True; the rows'
+        costs are then WQ_COSTS unless costs= gives (M, H, E).  stats has 8 entries: the five above (an IUPAC code counts as
+        unlike the text), rows with an IUPAC code, rows left to the text for GQ alone, heterozygous events that were not applied."""
         first = int(first)
         count = self.index.n - first if count is None else int(count)
         dev = self.index.device
@@ -906,15 +914,33 @@ class Pileup:
         m = len(b)
         cap = max(4096, count + count // 64) if capacity is None else int(capacity)
         total = C.c_uint64()
-        stats = (C.c_uint64 * 5)()
+        params = None
+        if genotype is not None:
+            g = dict(ploidy=2, err_q=20, het_q=30, min_gq=20, weighted=False, costs=None)
+            unknown = set(genotype) - set(g)
+            if unknown:
+                raise ValueError(f"genotype= takes ploidy, err_q, het_q, min_gq, weighted and costs, not {sorted(unknown)}")
+            g.update(genotype)
+            weighted = bool(g["weighted"])
+            row = _gt_params(g["ploidy"], g["err_q"], g["het_q"], min_depth, 0, WQ_COSTS if weighted and g["costs"] is None else g["costs"])
+            if not 0 <= int(g["min_gq"]) < 2 ** 32:
+                raise ValueError("min_gq is an unsigned 32-bit number")
+            params = capi.ConsGtParams(row, _gt_params(g["ploidy"], g["err_q"], g["het_q"], min_depth, 0), int(min_depth), int(g["min_gq"]),
+                                       int(weighted))
+        stats = (C.c_uint64 * (5 if params is None else 8))()
         with torch.cuda.device(dev):
             bd = torch.from_numpy(b.view(np.int64)).to(dev) if m else None
             offs = torch.zeros(max(m, 1), dtype=torch.int64, device=dev)
             for attempt in (0, 1):
                 out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-                rc = capi.lib().slamem_pileup_consensus_device(self._h, first, count, int(min_depth), cap, _ptr(out),
-                                                               _ptr(bd) if m else None, m, _ptr(offs) if m else None, stats,
-                                                               C.byref(total), _stream_handle(dev))
+                if params is None:
+                    rc = capi.lib().slamem_pileup_consensus_device(self._h, first, count, int(min_depth), cap, _ptr(out),
+                                                                   _ptr(bd) if m else None, m, _ptr(offs) if m else None, stats,
+                                                                   C.byref(total), _stream_handle(dev))
+                else:
+                    rc = capi.lib().slamem_pileup_consensus_gt_device(self._h, first, count, C.byref(params), cap, _ptr(out),
+                                                                      _ptr(bd) if m else None, m, _ptr(offs) if m else None, stats,
+                                                                      C.byref(total), _stream_handle(dev))
                 if rc != capi.SLAMEM_ERR_CAPACITY or attempt:
                     break
                 cap = int(total.value)
